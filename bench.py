@@ -19,10 +19,14 @@ Metric value = sum over instances of Information.iter / time.
           at N = 8): "scaling": "strong".  `--batch B` forces B instances per GPU instead (weak scaling).
 Instances are independent: no data-path collective; only the timing / iteration counters are reduced.
 
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line.  With --full,
 `config.summary` of the line carries one compact entry per workload: the headline, "soc" -- the same step on the MPC-SOC
 variant of the pattern (332 second-order cones of dimension 3), so that the metric's "SOCP" is what
 gets timed -- and, at N = 1, every other BASELINE.json config (dense-front batch 512, three LPnetlib patterns at batch 256,
-MPC02 at batch 512 and 4096).  The full per-workload objects go to stderr / gpurun_out/bench_details.json.
+MPC02 at batch 512 and 4096), the host-array round trip and the CPU baseline of every leg.  The full per-workload objects go to stderr.
+
+--dump-outputs DIR writes what the timed path computed in its last step (dump_outputs) so that two builds can be compared
+output for output: the inputs are generated from a fixed seed, identical from run to run for the same arguments.
 """
 import argparse
 import hashlib
@@ -38,6 +42,32 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md); 6290 measured achievable
 TOTAL_STRONG = 4096    # BASELINE.json configs[2]
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(solver, outdir, first, total, dist=None):
+    """--dump-outputs DIR: what a caller of the timed path receives after its last step -- x, y, z, s and every field of the
+    per-instance Information except the wall time solve_us -- as DIR/<name>.npy in float64, one row per instance, with the global
+    index of every row in DIR/instance.npy.  When all `total` instances do not fit in DUMP_BYTES, the rows are a sample of them drawn
+    with a fixed seed, the same for any sharding of the batch.  Over torch.distributed every rank passes its rows to rank 0, which writes."""
+    from eicos_amd.generate import SEED
+    y, z, s = solver.duals()
+    out = {"x": solver.solution(), "y": y, "z": z, "s": s,
+           **{"info_" + k: v for k, v in solver.info_arrays().items() if k not in ("solve_us", "reserved_")}}
+    row_bytes = 8 * (1 + sum(v.shape[1] if v.ndim == 2 else 1 for v in out.values()))  # (+1: the instance index)
+    keep = (DUMP_BYTES - 1024 * (len(out) + 1)) // row_bytes  # (.npy headers)
+    rows = np.arange(total) if total <= keep else np.sort(np.random.default_rng(SEED).choice(total, keep, replace=False))
+    mine = rows[(rows >= first) & (rows < first + len(out["x"]))]
+    part = {"instance": mine.astype(np.float64), **{k: np.asarray(v, dtype=np.float64)[mine - first] for k, v in out.items()}}
+    if dist is not None:
+        parts = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
+        dist.gather_object(part, parts, dst=0)
+        if parts is None:
+            return
+        part = {k: np.concatenate([p[k] for p in parts]) for k in part}  # (ranks own contiguous shards in rank order)
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in part.items():
+        np.save(os.path.join(outdir, k + ".npy"), v)
 
 
 def usable_cores():
@@ -421,7 +451,7 @@ def summarise(rep):
 def run_config(args, name, pattern, batch, local_rank, perturb=False, soc=False, steps=10, warmup=3, cpu_s=6.0, min_seconds=0.3):
     """One additional BASELINE.json config on this GPU, timed like the headline (updateData + solve per step; at least `steps` steps AND
     `min_seconds` of timed work, after `warmup` steps that bring the clocks back up behind the previous leg's CPU baseline): its own
-    value, roofline and CPU baseline (a smaller sample than the headline's, so that the default run stays within minutes)."""
+    value, roofline and CPU baseline (a smaller sample than the headline's, so that the --full run stays within minutes)."""
     import copy
     import eicos_amd
     a = copy.copy(args)
@@ -445,7 +475,7 @@ def run_config(args, name, pattern, batch, local_rank, perturb=False, soc=False,
 
 
 def aux_legs():
-    """The auxiliary legs of the default N = 1 line: (summary key, run_config arguments).  Every leg: >= 10 steps and >= 0.3 s timed, warm-up 3."""
+    """The auxiliary legs of the --full N = 1 line: (summary key, run_config arguments).  Every leg: >= 10 steps and >= 0.3 s timed, warm-up 3."""
     legs = [("dense_front_b512", dict(name="dense_front", pattern="dense-front", batch=512, cpu_s=8.0))]
     legs += [(f"{nm}_b256", dict(name=nm, pattern=nm, batch=256, perturb=True, cpu_s=4.0)) for nm in ("lp_afiro", "lp_bandm", "lp_25fv47")]
     legs += [("mpc_b512", dict(name="mpc_b512", pattern="MPC02", batch=512, cpu_s=6.0)),
@@ -457,8 +487,8 @@ PREV_LIB = os.path.join(ROOT, "build_exp", "r05", "libeicos_amd.so")  # the prev
 
 
 def legs_only(args, local_rank=0):
-    """`--legs-json`: every workload of the default line (headline, soc, the auxiliary legs) on whatever library EICOS_AMD_LIB names, GPU part
-    only (no CPU baseline), one compact json object on stdout.  The default run calls this in CHILD processes for the previous round's
+    """`--legs-json`: every workload of the --full line (headline, soc, the auxiliary legs) on whatever library EICOS_AMD_LIB names, GPU part
+    only (no CPU baseline), one compact json object on stdout.  The --full run calls this in CHILD processes for the previous round's
     library and for the current one, back to back on the same box: `config.summary.prev_round`."""
     r3 = lambda v: float(f"{v:.4g}")
     out = {}
@@ -536,7 +566,7 @@ def main():
     ap.add_argument("--perturb", action="store_true", help="LPnetlib-style batch: perturb c,h of the fixture "
                     "(SURVEY.md 8d config 4) instead of generating strictly feasible (c,h,b)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the additional BASELINE.json configs of the default N = 1 line "
+    ap.add_argument("--no-configs", action="store_true", help="skip the additional BASELINE.json configs of the --full N = 1 line "
                     "(dense-front batch 512, LPnetlib batch 256, MPC02 batch 512)")
     ap.add_argument("--resolve", type=float, default=0.0, metavar="EPS", help="MPC-style re-solves: steps alternate between "
                     "the batch and a copy with c, h perturbed by EPS (relative), so every solve follows an updateData with "
@@ -549,10 +579,17 @@ def main():
     ap.add_argument("--io", choices=("local", "root"), default="local", help="local: every rank regenerates its own shard "
                     "(no collective, default); root: rank 0 holds the whole batch and scatters shards over RCCL/xGMI "
                     "before the timed region, results are gathered back after it (times reported in config)")
-    ap.add_argument("--legs-json", action="store_true", help="(internal) the GPU part of every workload of the default line on the library "
-                    "EICOS_AMD_LIB names; used by the default run for config.summary.prev_round")
+    ap.add_argument("--legs-json", action="store_true", help="(internal) the GPU part of every workload of the --full line on the library "
+                    "EICOS_AMD_LIB names; used by the --full run for config.summary.prev_round")
     ap.add_argument("--no-prev-round", action="store_true", help="skip the previous-round comparison legs (config.summary.prev_round)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the MPC-SOC leg, the CPU baselines and parity "
+                    "counts, and at N = 1 the other BASELINE.json configs, the host-array round trip and the previous round's library "
+                    "(each still subject to the --no-* options above).  Without it a run times the headline workload alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last step computed "
+                    "(x, y, z, s, Information per instance; a fixed sample of the instances beyond 64 MB) as DIR/<name>.npy in float64")
     args = ap.parse_args()
+    if not args.full:
+        args.no_soc = args.no_cpu_baseline = args.no_configs = args.no_prev_round = True
     if args.legs_json:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         import torch  # noqa: F401
@@ -640,6 +677,8 @@ def main():
         job.devs[0] = dev
 
     res = job.run(dist, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(job.solver, args.dump_outputs, first, total, dist)
 
     if io_ms:  # results back to the root: x [B, n] straight from the instance slabs, then one gather
         torch.cuda.synchronize(); dist.barrier(); t_g = time.perf_counter()

@@ -288,3 +288,40 @@ def test_bench_launch_mode_never_runs_fewer_gpus_than_asked():
         import subprocess, sys
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], capture_output=True, text=True, cwd=ROOT)
         assert out.returncode != 0 and "visible devices" in out.stderr and not out.stdout.strip()
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_within_the_byte_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 files, one row per instance with its global index; beyond the byte cap a seeded sample of the
+    instances, the same rows whether the batch is dumped whole or shard by shard."""
+    import bench
+
+    class Fake:  # the result surface of BatchSolver / MultiBatchSolver over instances first .. first + B - 1
+        def __init__(self, first, B):
+            self.g = np.arange(first, first + B, dtype=np.float64)[:, None]
+        def solution(self):
+            return self.g * np.ones((1, 5))
+        def duals(self):
+            return self.g * np.ones((1, 2)), -self.g * np.ones((1, 3)), 2 * self.g * np.ones((1, 3))
+        def info_arrays(self):
+            return {"exitcode": np.zeros(len(self.g), np.int32), "iter": self.g[:, 0].astype(np.int32), "pcost": -self.g[:, 0],
+                    "solve_us": np.random.rand(len(self.g)), "reserved_": np.zeros(len(self.g), np.int32)}
+
+    total = 100
+    bench.dump_outputs(Fake(0, total), str(tmp_path / "whole"), 0, total)
+    whole = {f[:-4]: np.load(tmp_path / "whole" / f) for f in os.listdir(tmp_path / "whole")}
+    assert set(whole) == {"instance", "x", "y", "z", "s", "info_exitcode", "info_iter", "info_pcost"}
+    assert all(v.dtype == np.float64 and len(v) == total for v in whole.values())
+    assert np.array_equal(whole["instance"], np.arange(total)) and np.array_equal(whole["x"][:, 0], np.arange(total))
+    row = 8 * (1 + 5 + 2 + 3 + 3 + 3)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 30 * row + 1024 * 8)  # (eight files: 1 KB of header room each)
+    for tag in ("a", "b"):
+        bench.dump_outputs(Fake(0, total), str(tmp_path / tag), 0, total)
+    for lo, hi in ((0, 37), (37, 100)):
+        bench.dump_outputs(Fake(lo, hi - lo), str(tmp_path / f"shard{lo}"), lo, total)
+    a, b = ({f[:-4]: np.load(tmp_path / t / f) for f in os.listdir(tmp_path / t)} for t in ("a", "b"))
+    sh = [{f[:-4]: np.load(tmp_path / f"shard{lo}" / f) for f in os.listdir(tmp_path / f"shard{lo}")} for lo in (0, 37)]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BYTES
+    assert len(a["instance"]) == 30 and np.all(np.diff(a["instance"]) > 0) and not np.array_equal(a["instance"], np.arange(30))
+    for k in a:
+        assert np.array_equal(a[k], b[k]) and np.array_equal(a[k], np.concatenate([s_[k] for s_ in sh])), k
+    assert np.array_equal(a["x"][:, 0], a["instance"]) and np.array_equal(a["info_pcost"], -a["instance"])

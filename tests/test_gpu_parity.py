@@ -1375,7 +1375,7 @@ def test_bench_emits_the_contract_json_line():
     # bench.py's one-line JSON: metric/unit of BASELINE.json, roofline and cpu_baseline objects, whole-job value
     import json, os, subprocess, sys
     from conftest import ROOT
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64", "--full"],
                          capture_output=True, text=True, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -1407,6 +1407,30 @@ def test_bench_emits_the_contract_json_line():
     for e in (d["config"]["summary"]["headline"], s):
         assert e["steps"] == 2 and e["value_kernel"] >= e["value"] > 0 and len(e["step_ms"]) == 3 and e["step_ms"][0] <= e["step_ms"][1] <= e["step_ms"][2]
 
+
+def test_bench_plain_run_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    # without --full: the headline workload alone, exactly --steps timed steps, no CPU baseline and no other leg; --dump-outputs holds what
+    # a caller of the timed path receives after its last step -- the same bits as a handle that solves the same seeded batch once
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "64", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["metric"] == "ipm_iterations_per_sec" and d["unit"] == "iter/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["config"]["summary"]["headline"]["steps"] == 3 and d["config"]["optimal"] == 64
+    assert "cpu_baseline" not in d and set(d["config"]["summary"]) == {"headline"} and "cpu" not in d["config"]["summary"]["headline"]
+    assert abs(d["value"] - d["config"]["mean_iter"] * 64 * 3 / (d["ms_per_step"] * 3e-3)) <= 1e-6 * d["value"]
+    pat, sets = load_fixture("MPC02")
+    v = feasible_batch(pat, sets[0], 0, 64, SEED)
+    g = eicos_amd.BatchSolver(pat, 64)
+    g.update(v["Gpr"], v["Apr"], v["c"], v["h"], v["b"])
+    codes = g.solve(); x = g.solution(); y, z, s = g.duals(); ia = g.info_arrays()
+    g.close()
+    dump = {f[:-len(".npy")]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert all(a.dtype == np.float64 for a in dump.values()) and np.array_equal(dump["instance"], np.arange(64))
+    for k, ref in (("x", x), ("y", y), ("z", z), ("s", s), ("info_exitcode", codes), ("info_iter", ia["iter"]), ("info_pcost", ia["pcost"])):
+        assert np.array_equal(dump[k], ref), k
 
 def test_bench_legs_json_is_what_prev_round_parses():
     # `bench.py --legs-json` (the child process behind config.summary.prev_round: every leg of the default line, GPU part only, on the library

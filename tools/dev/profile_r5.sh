@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 out=gpurun_out/prof_r5
 rm -rf $out; mkdir -p $out
-python3 bench.py --steps 10 --warmup 2 > $out/bench_plain.json 2> $out/bench_plain.err
+python3 bench.py --full --steps 10 --warmup 2 > $out/bench_plain.json 2> $out/bench_plain.err
 tail -1 $out/bench_plain.json | cut -c1-200
 # rehearsal of the N > 1 measurement path on this one GPU: eight shards of 512 through eicos_multi_* 
 python3 bench.py --multi 0,0,0,0,0,0,0,0 --total 4096 --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_multi8.json 2> $out/bench_multi8.err
