@@ -41,7 +41,7 @@ using namespace eicos;
 //   and the share is what it costs (measured f = 2/3 behind two rounds: 0.63; f = 1/3 behind five: 0.22).
 // MPC02 on 256 CUs: 3 per CU for 513 ... 768 instances only; 1024, 1536, 2048, 3072 and 4096 run at two (measured: +4 % at 1536, +2.5 % at
 // 3072, +-1 % at 2048, -2 % at 4096 against three per CU -- inside the +-3 % spread between two processes on one box -- on 1.18 x instead of
-// 1.33 x the algorithmic HBM traffic), so the set-up no longer runs twice for the large batches (eicos_batch_create).
+// 1.33 x the algorithmic HBM traffic), so eicos_batch_create keeps the dense apex for the large batches.
 static int launch_blocks_per_cu(int batch, int n_cu, int max_r, int threads) {
     double best = 1e300; int best_r = 1;
     for (int r = 1; r <= max_r; r++) {
@@ -145,53 +145,16 @@ struct SlabLayout {
 
 } // namespace
 
-extern "C" {
+// ---- handle creation ----
+// eicos_batch_create runs five steps, each once: pattern intake (take_pattern), analysis (analyse), plan (build_plan: pure host code),
+// launch shape (launch_shape: LDS budget, occupancy probes, kernel build) and allocation (allocate: the only step that makes device
+// resources).  Only the last two hold the per-device creation lock, so the shards of an eicos_multi -- created on parallel host threads --
+// overlap their analyses and plans.
 
-const char *eicos_last_error(void) { return g_err.c_str(); }
-
-int eicos_set_arithmetic_profile(int profile) {
-    if (profile != 0 && profile != 1) return fail(EICOS_E_INVALID, "arithmetic profile must be 0 or 1");
-    g_arith_profile.store(profile);
-    return EICOS_OK;
-}
-int eicos_get_arithmetic_profile(void) { return g_arith_profile.load(); }
-
-int eicos_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *q, const int *Gjc, const int *Gir, const int *Ajc, const int *Air,
-                             int batch, int device, bool allow_apex, eicos_batch **out);
-constexpr int EICOS_RETRY_NO_APEX = -99; // (internal: never leaves eicos_batch_create)
-// The dense apex (symbolic.hpp) keeps an image of its block in LDS.  Whether that costs the launch a resident workgroup per CU is only
-// known once the real LDS layout and the runtime's occupancy answer exist -- at the end of the set-up.  So: set up with the apex; if the
-// batch is one that would run MORE workgroups per CU than came out, set up once more without it and keep the better launch shape
-// (MPC02: batches >= 1536 run three per CU without the apex, two with it: the third workgroup is worth more).
-int eicos_batch_create(int n, int m, int p, int l, int ncones, const int *q,
-                       const int *Gjc, const int *Gir, const int *Ajc, const int *Air,
-                       int batch, int device, eicos_batch **out) {
-    int rc = batch_create_impl(n, m, p, l, ncones, q, Gjc, Gir, Ajc, Air, batch, device, g_arith_profile.load() == 0, out);
-    if (rc == EICOS_RETRY_NO_APEX) return batch_create_impl(n, m, p, l, ncones, q, Gjc, Gir, Ajc, Air, batch, device, false, out);
-    if (rc != EICOS_OK || (*out)->sym.apex0 < 0) return rc;
-    eicos_batch *h = *out;
-    if (launch_blocks_per_cu(batch, h->n_cu, h->bpc + 1, h->threads) <= h->bpc) return rc; // one more per CU would not be taken anyway
-    eicos_batch *h0 = nullptr;
-    if (batch_create_impl(n, m, p, l, ncones, q, Gjc, Gir, Ajc, Air, batch, h->device, false, &h0) != EICOS_OK) {
-        static std::atomic<bool> told{false}; // (e.g. out of memory with both handles alive: the launch shape WITH the apex is kept -- say so once)
-        if (!told.exchange(true)) std::fprintf(stderr, "eicos_amd: the set-up without the dense apex failed (%s); keeping %d workgroup(s) per CU\n", g_err.c_str(), h->bpc);
-        return rc;
-    }
-    if (h0->bpc > h->bpc) { eicos_batch_destroy(h); *out = h0; } else eicos_batch_destroy(h0);
-    return EICOS_OK;
-}
-
-static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *q,
-                       const int *Gjc, const int *Gir, const int *Ajc, const int *Air,
-                       int batch, int device, bool allow_apex, eicos_batch **out) {
-    if (!out) return fail(EICOS_E_INVALID, "out is NULL");
-    *out = nullptr;
+// Pattern intake: the C arguments as a validated ProblemPattern.  `device` (creation; NULL for the host-only debug entries) is resolved
+// after the argument checks and before the CSC checks, so that a machine without a GPU answers EICOS_E_NOGPU there.
+static int take_pattern(int n, int m, int p, int l, int ncones, const int *q, const int *Gjc, const int *Gir, const int *Ajc, const int *Air,
+                        int batch, int *device, ProblemPattern &P) {
     if (n < 0 || m < 0 || p < 0 || ncones < 0 || batch < 1) return fail(EICOS_E_INVALID, "negative dimension or batch < 1");
     if (ncones > 0 && !q) return fail(EICOS_E_INVALID, "ncones > 0 but q is NULL");
     const bool haveG = Gjc && Gir, haveA = Ajc && Air;
@@ -204,95 +167,193 @@ static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *
         for (int c = 0; c < ncones; c++) qs += q[c];
         if ((long long)l + qs != (long long)m) return fail(EICOS_E_INVALID, "l + sum(q) != m (pass l < 0 to derive l as the reference does)");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(EICOS_E_NOGPU, "no HIP device visible: the solver has no CPU fallback");
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    if (device >= ndev) return fail(EICOS_E_INVALID, "device index out of range");
-
-    eicos_batch *h = new eicos_batch();
+    if (device) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+            return fail(EICOS_E_NOGPU, "no HIP device visible: the solver has no CPU fallback");
+        if (*device < 0) { if (hipGetDevice(device) != hipSuccess) *device = 0; }
+        if (*device >= ndev) return fail(EICOS_E_INVALID, "device index out of range");
+    }
+    // compressed CSC as the reference assumes (src/eicos.cpp:2038-2039): pointers start at 0 and do not decrease,
+    // row indices in range and strictly increasing inside a column
+    auto take = [&](const int *jc, const int *ir, int rows, std::vector<int> &ojc, std::vector<int> &oir, const char *nm) {
+        if (jc[0] != 0) throw std::invalid_argument(std::string(nm) + ": column pointers must start at 0");
+        for (int j = 0; j < n; j++) if (jc[j + 1] < jc[j]) throw std::invalid_argument(std::string(nm) + ": column pointers decrease");
+        ojc.assign(jc, jc + n + 1); oir.assign(ir, ir + jc[n]);
+        for (int j = 0; j < n; j++)
+            for (int k = jc[j]; k < jc[j + 1]; k++) {
+                if (ir[k] < 0 || ir[k] >= rows) throw std::invalid_argument(std::string(nm) + " row index out of range");
+                if (k > jc[j] && ir[k] <= ir[k - 1]) throw std::invalid_argument(std::string(nm) + ": row indices of a column must be strictly increasing");
+            }
+    };
     try {
-        ProblemPattern &P = h->pat;
         P.n = n; P.m = m; P.p = p; P.nc = ncones;
         P.q.assign(q, q + ncones);
-        // compressed CSC as the reference assumes (src/eicos.cpp:2038-2039): pointers start at 0 and do not decrease,
-        // row indices in range and strictly increasing inside a column
-        auto take = [&](const int *jc, const int *ir, int rows, std::vector<int> &ojc, std::vector<int> &oir, const char *nm) {
-            if (jc[0] != 0) throw std::invalid_argument(std::string(nm) + ": column pointers must start at 0");
-            for (int j = 0; j < n; j++) if (jc[j + 1] < jc[j]) throw std::invalid_argument(std::string(nm) + ": column pointers decrease");
-            ojc.assign(jc, jc + n + 1); oir.assign(ir, ir + jc[n]);
-            for (int j = 0; j < n; j++)
-                for (int k = jc[j]; k < jc[j + 1]; k++) {
-                    if (ir[k] < 0 || ir[k] >= rows) throw std::invalid_argument(std::string(nm) + " row index out of range");
-                    if (k > jc[j] && ir[k] <= ir[k - 1]) throw std::invalid_argument(std::string(nm) + ": row indices of a column must be strictly increasing");
-                }
-        };
         if (haveG) take(Gjc, Gir, m, P.Gjc, P.Gir, "G"); else P.Gjc.assign(n + 1, 0);
         if (haveA) take(Ajc, Air, p, P.Ajc, P.Air, "A"); else P.Ajc.assign(n + 1, 0);
-        // (experiment knobs, envknob.hpp: honoured only under EICOS_EXPERIMENT=1, range-checked)
-        h->sym = analyze(P, env_knob("EICOS_ORDER", -1, 0, 16), env_knob("EICOS_TILES", -1, 0, 2));
-        if (h->sym.tile) h->tiles = build_tile_plan(h->sym);
-    } catch (const std::invalid_argument &e) { delete h; return fail(EICOS_E_INVALID, e.what()); }
-    catch (const std::runtime_error &e) { delete h; return fail(EICOS_E_UNSUPPORTED, e.what()); }
-    catch (const std::exception &e) { delete h; return fail(EICOS_E_INVALID, e.what()); }
+    } catch (const std::exception &e) { return fail(EICOS_E_INVALID, e.what()); }
+    return EICOS_OK;
+}
 
-    const Symbolic &S = h->sym;
-    const ProblemPattern &P = h->pat;
-    h->batch = batch; h->device = device;
-    DevPat &D = h->dp;
-    auto env_int = [](const char *k, int dflt, int lo, int hi) { return env_knob(k, dflt, lo, hi); };
-    {
-        // workgroup size by problem size (measured, batch 256: dim_K 129 -> 128, 1249 -> 256, >= 3815 -> 512 threads);
-        // batches beyond one workgroup per CU are throughput-bound: 256 threads issue a third fewer wavefront-slices
-        // per instance than 512 and fit three workgroups per CU (MPC02 pattern: 500 k vs 414 k iterations/s)
-        const int dimK = n + p + m + 2 * ncones;
-        int n_cu = 256;
-        { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device < 0 ? 0 : device) == hipSuccess) n_cu = pr.multiProcessorCount; }
-        // (sparse factors only: with ~50 entries per row of L -- the dense-front config -- 512 threads stay ahead)
-        // (arithmetic profile 1: every choice that shapes a PLAN -- and with it the order of the floating-point operations -- is made as for a
-        // batch beyond one workgroup per CU, whatever the batch really is: workgroup size by pattern size alone, no dense apex, the
-        // single-wavefront tree top; the launch shape itself -- grid, LDS residency, dual solves, which are bit-neutral -- follows the real batch)
-        h->arith_profile = g_arith_profile.load();
-        const bool as_large = h->arith_profile == 1;
-        const bool throughput_bound = (batch > n_cu || as_large) && (long long)S.nnzL < 16LL * S.N;
-        // one workgroup per CU (batch <= CUs): latency-bound, more wavefronts per instance pay earlier (measured at batch 256 with
-        // the 256-VGPR build of the 512-thread kernels: lp_blend / lp_adlittle, dim_K ~ 300: 256 threads +5..8 % over 128;
-        // lp_beaconfd / lp_bandm / lp_agg, dim_K 763..1718: 512 threads +7..12 % over 256)
-        const int dflt = throughput_bound ? (dimK < 400 ? 128 : 256) : (dimK < 250 ? 128 : (dimK < 700 ? 256 : 512));
-        const int t = env_int("EICOS_THREADS", dflt, 128, 512);
-        if (t != 128 && t != 256 && t != 512) { delete h; return fail(EICOS_E_INVALID, "EICOS_THREADS must be 128, 256 or 512"); }
-        h->threads = t;
-        // ---- dense apex: not with 128-thread workgroups (small patterns; kernels.hip: apex_on), not when the caller found that it costs a
-        // resident workgroup (eicos_batch_create above) ----
-        // (128 threads: only the LDS-resident build carries an apex -- its images then live in the LDS copy of the workspace slab; whether that
-        // build is taken is known after the slab layout: if not, the set-up is repeated without the apex, EICOS_RETRY_NO_APEX below)
-        if (h->sym.apex0 >= 0 && ((t < 256 && !(t == 128 && env_knob("EICOS_LDSRES", 1, 0, 1) && batch <= n_cu)) || !allow_apex)) h->sym.apex0 = -1;
-        // small patterns whose narrow tree top would go to the tile path (hybrid): the level schedule + dense apex does better there -- a
-        // handful of 16 x 16 blocks costs two workgroup-wide block levels each, the apex swallows the whole tail in 2 x 64 register steps
-        // (lp_adlittle 1.13 -> 1.33 M, lp_blend 0.92 -> 1.08 M iter/s at batch 256; larger tops -- lp_bandm, lp_agg, lp_25fv47 -- stay hybrid:
-        // their top blocks are dense and the MFMA factorisation of the block is what pays there)
-        if (h->sym.tile == 2 && S.N < APEX_OVER_HYBRID_BELOW && t >= 256 && allow_apex && env_knob("EICOS_TILES", -1, 0, 2) < 0) {
-            try {
-                Symbolic alt = analyze(P, env_knob("EICOS_ORDER", -1, 0, 16), 0);
-                if (alt.apex0 >= 0) { h->sym = std::move(alt); h->tiles = TilePlan(); }
-            } catch (const std::exception &) { /* keep the hybrid analysis */ }
-        }
-        h->n_cu = n_cu;
+namespace {
+
+struct Analysis { Symbolic sym; TilePlan tiles; }; // a symbolic analysis (+ the dense-front plan of the tile and hybrid paths)
+
+// What the analysis step decides: the workgroup size, whether plans carry the dense apex, and which analysis a plan is built from.
+struct Analyses {
+    Analysis main;         // EICOS_ORDER / EICOS_TILES as set
+    Analysis apex_alt;     // small hybrid patterns at 256 / 512 threads: the scalar analysis with a dense apex (has_alt)
+    bool has_alt = false;
+    int threads = 256;
+    bool apex = false;     // the dense apex is allowed (profile 0, and a workgroup size / batch that can carry it)
+    Analysis &for_plan(bool with_apex) { return with_apex && has_alt ? apex_alt : main; }
+};
+
+// Everything the plan step produces: the DevPat offsets and counts, the backward value slots, and the pattern image with the places its
+// arrays' device addresses go (filled by the allocation step).  `slots` points into this object, so a Plan is never copied or moved.
+struct Plan {
+    Analysis *an = nullptr;  // the analysis it was built from
+    bool apex = false;       // the sweeps end in the dense apex (Symbolic::apex0)
+    int threads = 256;
+    DevPat dp{};
+    std::vector<int> posB;   // CSC entry of L -> slot in the backward value array
+    int ub_len = 1;
+    IntPool pool;
+    struct Slot { const int **dst; size_t off; };
+    std::vector<Slot> slots;
+    // pool arrays whose DevPat fields are typed (slice tables) or chosen by the launch shape (stored-L / deferred-L factor operands)
+    const int *fsl = nullptr, *bsl = nullptr, *cag_sl = nullptr, *rA_sl = nullptr, *rG_sl = nullptr, *fac_sl = nullptr;
+    const int *fac_pb_f = nullptr, *fac_pb_u = nullptr, *fac_p16_f = nullptr, *fac_p16_u = nullptr;
+    Plan() = default;
+    Plan(const Plan &) = delete;
+    Plan &operator=(const Plan &) = delete;
+    void put(const int *&field, const std::vector<int> &v) { slots.push_back({&field, pool.add(v)}); }
+};
+
+// The launch shape of a plan (launch_shape).
+struct Shape {
+    int nlds = 0, ldsres = 0, w2 = 0, ubl = 0;
+    size_t dyn_lds = 0;
+    int bpc = 1, grid = 0, order_min = 0;
+    int upd_grid = 0, upd_vals_lds = 1; size_t upd_lds = 0;
+    bool apex_unplaced = false; // a 128-thread plan with the apex that does not get the LDS-resident build: it cannot run (no probes done)
+};
+
+// G in dense 16 x 16 tiles (dense-front patterns on the tile path: the products are bandwidth-bound).
+// Row block = 16 consecutive rows of G; its tiles = the sorted union of the columns of those rows, cut into groups of 16
+// (so a tile's columns need not be consecutive).  One pass over the tiles yields G x (per row block, in registers) and the
+// partial column sums of G' z (per tile, reduced per column in a second, fixed-order pass): G is streamed ONCE per
+// evaluation instead of once in column form and once in row form, with no index bytes.  Taken when the tiles are at
+// least half full; the sliced-ELL plans of the products then hold A only.
+struct GTiles { int on = 0, nrb = 0, nt = 0, W = 0; std::vector<int> rbptr, col, src, cidx; };
+GTiles plan_g_tiles(const Symbolic &S, int gv_rel) {
+    GTiles GT;
+    if (!(S.tile == 1 && S.nnzG > 0 && env_knob("EICOS_GTILES", 1, 0, 2))) return GT;
+    const int nrb = (S.m + 15) / 16;
+    GT.nrb = nrb; GT.rbptr.assign(nrb + 1, 0);
+    std::vector<std::vector<int>> rbcols(nrb);
+    for (int rb = 0; rb < nrb; rb++) {
+        std::vector<int> &cs = rbcols[rb];
+        for (int i = rb * 16; i < std::min(S.m, rb * 16 + 16); i++) for (int e = S.Gt_ptr[i]; e < S.Gt_ptr[i + 1]; e++) cs.push_back(S.Gt_col[e]);
+        std::sort(cs.begin(), cs.end()); cs.erase(std::unique(cs.begin(), cs.end()), cs.end());
+        GT.rbptr[rb + 1] = GT.rbptr[rb] + ((int)cs.size() + 15) / 16;
     }
-    h->npairs = S.npairs;
-    if (S.npairs >= (int64_t)1 << 31) { delete h; return fail(EICOS_E_UNSUPPORTED, "factor program exceeds 2^31 pairs"); }
-    if (S.tile) { // the tile image, the tile arrays of L and their workspace offsets are indexed with 32-bit ints
-        const long long img = ((long long)h->tiles.nb + h->tiles.nt) * 256;
-        if (img >= IMG_BASE || (long long)S.N + img >= DIAG_POS / 2 || 3 * img * (long long)sizeof(double) > (8LL << 30)) {
-            delete h; return fail(EICOS_E_UNSUPPORTED, "dense-front pattern too large: the tile image of L exceeds the per-workgroup workspace budget");
+    GT.nt = GT.rbptr[nrb];
+    if (GT.nt > 0 && ((double)S.nnzG >= 0.5 * 256.0 * GT.nt || env_knob("EICOS_GTILES", 1, 0, 2) == 2)) { // (2: tests force it on sparse G)
+        GT.on = 1;
+        GT.col.assign((size_t)GT.nt * 16, -1); GT.src.assign((size_t)GT.nt * 256 + 1, -1);
+        std::vector<int> ccount(S.n, 0);
+        for (int rb = 0; rb < nrb; rb++) {
+            const std::vector<int> &cs = rbcols[rb];
+            for (size_t q = 0; q < cs.size(); q++) { GT.col[(size_t)GT.rbptr[rb] * 16 + q] = cs[q]; ccount[cs[q]]++; }
+            for (int i = rb * 16; i < std::min(S.m, rb * 16 + 16); i++)
+                for (int e = S.Gt_ptr[i]; e < S.Gt_ptr[i + 1]; e++) {
+                    const int q = (int)(std::lower_bound(cs.begin(), cs.end(), S.Gt_col[e]) - cs.begin());
+                    GT.src[(size_t)(GT.rbptr[rb] + q / 16) * 256 + tile_op(i - rb * 16, q % 16)] = gv_rel + S.Gt_pos[e];
+                }
+        }
+        GT.W = 8; // contributions per column the kernel adds (fixed width, padded)
+        if (*std::max_element(ccount.begin(), ccount.end()) > GT.W) GT.on = 0; // (a column met by more than 8 tiles: keep the ELL products)
+        GT.cidx.assign((size_t)S.n * GT.W, -1); // padding
+        std::fill(ccount.begin(), ccount.end(), 0);
+        if (GT.on) for (int t = 0; t < GT.nt; t++) for (int k = 0; k < 16; k++) { const int j = GT.col[(size_t)t * 16 + k]; if (j >= 0) GT.cidx[(size_t)j * GT.W + ccount[j]++] = t * 16 + k; }
+    }
+    return GT;
+}
+
+// ---- device form of the slice tables (PackedSlice) and 16-bit gather indices ----
+// One 8-byte entry per lane and slice = its ELL_KMAX gather indices; entry position = off16 of the slice + lane;
+// the entry after the last slice is all padding (read by inactive lanes).  Used when every index fits 16 bits (else *ok = false).
+std::vector<int> lane_offsets(const std::vector<SliceMeta> &sl, int &dummy) {
+    std::vector<int> off16(sl.size());
+    int pos = 0;
+    for (size_t i = 0; i < sl.size(); i++) { off16[i] = pos; pos += sl[i].cnt << sl[i].lg; }
+    dummy = pos;
+    return off16;
+}
+std::vector<int> pack16(const std::vector<SliceMeta> &sl, const std::vector<int> &off16, int dummy, const std::vector<int> &idx, int pad, bool *ok) {
+    std::vector<int> words(((size_t)dummy + 1) * 2, 0); // two 32-bit words = four 16-bit indices per lane entry
+    auto set = [&](size_t entry, int kk, int v) {
+        if (v < 0 || v > 65535) { *ok = false; v = 0; }
+        words[entry * 2 + (kk >> 1)] |= v << (16 * (kk & 1));
+    };
+    for (size_t i = 0; i < sl.size(); i++) {
+        const int lanes = sl[i].cnt << sl[i].lg;
+        for (int t = 0; t < lanes; t++)
+            for (int kk = 0; kk < ELL_KMAX; kk++)
+                set((size_t)off16[i] + t, kk, kk < sl[i].K ? idx[(size_t)sl[i].off + (size_t)kk * lanes + t] : pad);
+    }
+    for (int kk = 0; kk < ELL_KMAX; kk++) set((size_t)dummy, kk, pad);
+    return words;
+}
+std::vector<int> meta_ints(const std::vector<SliceMeta> &v, const std::vector<int> &off16) {
+    std::vector<int> o(v.size() * 4);
+    for (size_t i = 0; i < v.size(); i++) {
+        const PackedSlice ps = pack_slice(v[i], off16.empty() ? 0 : off16[i]);
+        std::memcpy(o.data() + 4 * i, &ps, sizeof ps);
+    }
+    return o;
+}
+
+// The plan step, in three parts that share the intermediate arrays: slab layouts and the sliced-ELL plans of the products
+// (layout_and_products), the sweep and factor programs (programs), the pattern image (pool_image).  Pure host code.
+struct Planner {
+    const ProblemPattern &P; const Symbolic &S; const TilePlan &TP; Plan &pl; DevPat &D;
+    const int batch, n_cu, profile;
+    const bool tile;  // some part of L lives in 16 x 16 tiles: all of it (S.tile == 1) or the top block (hybrid, == 2)
+    const bool tile1; // pure tile mode: no scalar programs at all
+    const int NV;     // length of the KKT-space vectors on the device: dim_K in elimination order, or (tile mode) the blocks padded to 16
+    SlabLayout Wl;    // the workspace slab
+    std::vector<int> zexp0;
+    GTiles GT;
+    EllPlan pcag, prA, prG;
+    std::vector<int> cag_idx_k, cag_idx_yz, cag_src, rA_idx, rA_src, rG_idx, rG_src, rA_idx_k, rG_idx_k, ipx, ipy, ipz, ipv, ipu;
+    TriPlan planF, planB;
+    FactorPlan planX;
+    std::vector<int> col_of;
+    std::vector<int> f_w16, b_w16, cag_k_w16, cag_yz_w16, rA_w16, rA_k_w16, rG_w16, rG_k_w16, fac_w16, fac_w16d, fac_k16;
+    std::vector<int> fsl_i, bsl_i, fac_sl_i, cag_sl_i, rA_sl_i, rG_sl_i;
+
+    Planner(const ProblemPattern &P_, const Analysis &an, Plan &pl_, int batch_, int n_cu_, int profile_)
+        : P(P_), S(an.sym), TP(an.tiles), pl(pl_), D(pl_.dp), batch(batch_), n_cu(n_cu_), profile(profile_),
+          tile(an.sym.tile != 0), tile1(an.sym.tile == 1), NV(an.sym.tile != 0 ? an.tiles.N16 : an.sym.N) {}
+    int posK(int old) const { return tile ? TP.slot[S.iperm[old]] : S.iperm[old]; } // KKT index -> device slot
+    int srcoff(int kind, int src) const {
+        switch (kind) {
+        case SRC_A: return D.i_Av + src;
+        case SRC_G: return D.i_Gv + src;
+        case SRC_V: return D.i_Vv + src;
+        case SRC_POSDELTA: return D.i_cst + 0;
+        case SRC_NEGDELTA: return D.i_cst + 1;
+        default: return D.i_cst + 2;
         }
     }
-    const bool tile = S.tile != 0;  // some part of L lives in 16 x 16 tiles: all of it (S.tile == 1) or the top block (hybrid, == 2)
-    const bool tile1 = S.tile == 1; // pure tile mode: no scalar programs at all
-    const TilePlan &TP = h->tiles;
-    // NV = length of the KKT-space vectors on the device: dim_K in elimination order, or (tile mode) the blocks padded to 16
-    const int NV = tile ? TP.N16 : S.N;
-    auto posK = [&](int old) { return tile ? TP.slot[S.iperm[old]] : S.iperm[old]; }; // KKT index -> device slot
+    int layout_and_products();
+    int programs();
+    void pool_image();
+};
+
+int Planner::layout_and_products() {
     D.n = S.n; D.p = S.p; D.m = S.m; D.l = S.l; D.nc = S.nc; D.N = NV; D.mt = S.mt; D.nV = S.nV;
     D.nnzA = S.nnzA; D.nnzG = S.nnzG; D.nnzL = S.nnzL; D.nlev = S.nlev;
 
@@ -301,55 +362,18 @@ static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *
     D.i_Av = L.add(S.nnzA); D.i_Gv = L.add(S.nnzG);
     // sliced-ELL plans of the matrix-vector products
     std::vector<int> cag_ptr(S.n + 1, 0), cag_val, cag_k, cag_yz; // stacked columns of [A; G]
-    std::vector<int> zexp0(S.m);
+    zexp0.assign(S.m, 0);
     { for (int i = 0; i < S.l; i++) zexp0[i] = i; for (int c = 0; c < S.nc; c++) for (int k = 0; k < S.q[c]; k++) zexp0[S.cone_off[c] + k] = S.cone_off[c] + k + 2 * c; }
     const int gv_rel = D.i_Gv - D.i_Av;
-    // ---- G in dense 16 x 16 tiles (dense-front patterns on the tile path: the products are bandwidth-bound) ----
-    // Row block = 16 consecutive rows of G; its tiles = the sorted union of the columns of those rows, cut into groups of 16
-    // (so a tile's columns need not be consecutive).  One pass over the tiles yields G x (per row block, in registers) and the
-    // partial column sums of G' z (per tile, reduced per column in a second, fixed-order pass): G is streamed ONCE per
-    // evaluation instead of once in column form and once in row form, with no index bytes.  Taken when the tiles are at
-    // least half full; the sliced-ELL plans of the products then hold A only.
-    struct GTiles { int on = 0, nrb = 0, nt = 0, W = 0; std::vector<int> rbptr, col, src, cidx; } GT;
-    if (S.tile == 1 && S.nnzG > 0 && env_int("EICOS_GTILES", 1, 0, 2)) {
-        const int nrb = (S.m + 15) / 16;
-        GT.nrb = nrb; GT.rbptr.assign(nrb + 1, 0);
-        std::vector<std::vector<int>> rbcols(nrb);
-        for (int rb = 0; rb < nrb; rb++) {
-            std::vector<int> &cs = rbcols[rb];
-            for (int i = rb * 16; i < std::min(S.m, rb * 16 + 16); i++) for (int e = S.Gt_ptr[i]; e < S.Gt_ptr[i + 1]; e++) cs.push_back(S.Gt_col[e]);
-            std::sort(cs.begin(), cs.end()); cs.erase(std::unique(cs.begin(), cs.end()), cs.end());
-            GT.rbptr[rb + 1] = GT.rbptr[rb] + ((int)cs.size() + 15) / 16;
-        }
-        GT.nt = GT.rbptr[nrb];
-        if (GT.nt > 0 && ((double)S.nnzG >= 0.5 * 256.0 * GT.nt || env_int("EICOS_GTILES", 1, 0, 2) == 2)) { // (2: tests force it on sparse G)
-            GT.on = 1;
-            GT.col.assign((size_t)GT.nt * 16, -1); GT.src.assign((size_t)GT.nt * 256 + 1, -1);
-            std::vector<int> ccount(S.n, 0);
-            for (int rb = 0; rb < nrb; rb++) {
-                const std::vector<int> &cs = rbcols[rb];
-                for (size_t q = 0; q < cs.size(); q++) { GT.col[(size_t)GT.rbptr[rb] * 16 + q] = cs[q]; ccount[cs[q]]++; }
-                for (int i = rb * 16; i < std::min(S.m, rb * 16 + 16); i++)
-                    for (int e = S.Gt_ptr[i]; e < S.Gt_ptr[i + 1]; e++) {
-                        const int q = (int)(std::lower_bound(cs.begin(), cs.end(), S.Gt_col[e]) - cs.begin());
-                        GT.src[(size_t)(GT.rbptr[rb] + q / 16) * 256 + tile_op(i - rb * 16, q % 16)] = gv_rel + S.Gt_pos[e];
-                    }
-            }
-            GT.W = 8; // contributions per column the kernel adds (fixed width, padded)
-            if (*std::max_element(ccount.begin(), ccount.end()) > GT.W) GT.on = 0; // (a column met by more than 8 tiles: keep the ELL products)
-            GT.cidx.assign((size_t)S.n * GT.W, -1); // padding
-            std::fill(ccount.begin(), ccount.end(), 0);
-            if (GT.on) for (int t = 0; t < GT.nt; t++) for (int k = 0; k < 16; k++) { const int j = GT.col[(size_t)t * 16 + k]; if (j >= 0) GT.cidx[(size_t)j * GT.W + ccount[j]++] = t * 16 + k; }
-        }
-    }
+    GT = plan_g_tiles(S, gv_rel);
     const std::vector<int> Gt_ptr_used = GT.on ? std::vector<int>(S.m + 1, 0) : S.Gt_ptr; // (rows without entries: the epilogue still runs)
     for (int j = 0; j < S.n; j++) {
         for (int k = P.Ajc[j]; k < P.Ajc[j + 1]; k++) { cag_val.push_back(k); cag_k.push_back(S.n + P.Air[k]); cag_yz.push_back(P.Air[k]); }
         if (!GT.on) for (int k = P.Gjc[j]; k < P.Gjc[j + 1]; k++) { cag_val.push_back(gv_rel + k); cag_k.push_back(S.n + S.p + zexp0[P.Gir[k]]); cag_yz.push_back(-1 - P.Gir[k]); }
         cag_ptr[j + 1] = (int)cag_val.size();
     }
-    EllPlan pcag = build_ell_plan(cag_ptr, S.n, h->threads), prA = build_ell_plan(S.At_ptr, S.p, h->threads),
-            prG = build_ell_plan(Gt_ptr_used, S.m, h->threads);
+    pcag = build_ell_plan(cag_ptr, S.n, pl.threads); prA = build_ell_plan(S.At_ptr, S.p, pl.threads);
+    prG = build_ell_plan(Gt_ptr_used, S.m, pl.threads);
     D.cag_ns = (int)pcag.sl.size(); D.rA_ns = (int)prA.sl.size(); D.rG_ns = (int)prG.sl.size();
     {   auto real = [](const std::vector<SliceMeta> &sl) { int c = (int)sl.size(); while (c > 0 && sl[(size_t)c - 1].cnt == 0) c--; return c; };
         D.cag_ns_r = real(pcag.sl); D.rA_ns_r = real(prA.sl); D.rG_ns_r = real(prG.sl); }
@@ -362,28 +386,27 @@ static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *
     D.i_Vv = L.add(S.nV); D.i_cst = L.add(4);
     D.i_x = L.add(S.n); D.i_y = L.add(S.p); D.i_z = L.add(S.m); D.i_s = L.add(S.m);
     D.i_info = L.add(DEVINFO_DOUBLES);
-    std::vector<int> cag_idx_k(pcag.src.size()), cag_idx_yz(pcag.src.size()), cag_src(pcag.src.size());
+    cag_idx_k.resize(pcag.src.size()); cag_idx_yz.resize(pcag.src.size()); cag_src.resize(pcag.src.size());
     for (size_t sl = 0; sl < pcag.src.size(); sl++) {
         const int e = pcag.src[sl];
         cag_src[sl] = e < 0 ? -1 : cag_val[e];
         cag_idx_k[sl] = e < 0 ? NV : posK(cag_k[e]);                         // elimination order; padding -> zero slot N
         cag_idx_yz[sl] = e < 0 ? 0 : (cag_yz[e] >= 0 ? cag_yz[e] : (D.i_z - D.i_y) + (-1 - cag_yz[e])); // offset from y
     }
-    std::vector<int> rA_idx(prA.src.size()), rA_src(prA.src.size()), rG_idx(prG.src.size()), rG_src(prG.src.size());
-    std::vector<int> rA_idx_k(prA.src.size()), rG_idx_k(prG.src.size());
+    rA_idx.resize(prA.src.size()); rA_src.resize(prA.src.size()); rG_idx.resize(prG.src.size()); rG_src.resize(prG.src.size());
+    rA_idx_k.resize(prA.src.size()); rG_idx_k.resize(prG.src.size());
     for (size_t sl = 0; sl < prA.src.size(); sl++) { const int e = prA.src[sl]; rA_src[sl] = e < 0 ? -1 : S.At_pos[e]; rA_idx[sl] = e < 0 ? 0 : S.At_col[e]; rA_idx_k[sl] = e < 0 ? NV : posK(S.At_col[e]); }
     for (size_t sl = 0; sl < prG.src.size(); sl++) { const int e = prG.src[sl]; rG_src[sl] = e < 0 ? -1 : gv_rel + S.Gt_pos[e]; rG_idx[sl] = e < 0 ? 0 : S.Gt_col[e]; rG_idx_k[sl] = e < 0 ? NV : posK(S.Gt_col[e]); }
-    std::vector<int> ipx(S.n), ipy(S.p), ipz(S.m), ipv(S.nc), ipu(S.nc);
+    ipx.resize(S.n); ipy.resize(S.p); ipz.resize(S.m); ipv.resize(S.nc); ipu.resize(S.nc);
     for (int j = 0; j < S.n; j++) ipx[j] = posK(j);
     for (int r = 0; r < S.p; r++) ipy[r] = posK(S.n + r);
     for (int i = 0; i < S.m; i++) ipz[i] = posK(S.n + S.p + zexp0[i]);
     for (int c = 0; c < S.nc; c++) { const int e0 = S.n + S.p + S.cone_off[c] + 2 * c + S.q[c]; ipv[c] = posK(e0); ipu[c] = posK(e0 + 1); }
     D.inst_stride = L.size;
-    SlabLayout Wl;
     // second buffer set of the iterate (ShI::cur / best in kernels.hip): same spacing of y and z as in the instance slab -- the stacked
     // product [A' G'] gathers (y, z) through ONE index array relative to y
     D.w_lam = Wl.add(S.m); D.w_bx = Wl.add(S.n); D.w_by = Wl.add(S.p); D.w_bz = Wl.add(S.m); D.w_bs = Wl.add(S.m);
-    if (D.w_bz - D.w_by != D.i_z - D.i_y) { delete h; return fail(EICOS_E_INVALID, "internal: the two buffer sets of the iterate are laid out differently"); }
+    if (D.w_bz - D.w_by != D.i_z - D.i_y) return fail(EICOS_E_INVALID, "internal: the two buffer sets of the iterate are laid out differently");
     D.w_rz = Wl.add(S.m);
     D.w_rhs1k = Wl.add((size_t)S.n + S.p + S.m); D.w_rhs2k = Wl.add((size_t)S.n + S.p + S.m);       // [x | y | z] order
     D.w_dx1 = Wl.add((size_t)S.n + S.p + S.m); D.w_dy1 = D.w_dx1 + S.n; D.w_dz1 = D.w_dy1 + S.p; // [dx | dy | dz]: one array each
@@ -397,41 +420,17 @@ static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *
     // ---- the arrays of the factorisation / KKT solve ----
     D.w_xk = Wl.add((size_t)NV + 16); D.w_ek = Wl.add((size_t)NV + 16); D.w_dxr = Wl.add(NV);
     D.w_D = Wl.add(NV); D.w_invD = Wl.add((size_t)NV + 8); // (+ the always-zero slot fac_kpad of the deferred-L factorisation) // w_UF / w_UB are added once the slice plans are known
+    return EICOS_OK;
+}
 
-    // ---- pattern arrays ----
-    IntPool pool;
-    std::vector<int> zexp(S.m), zdsign(S.m, 1), cone_vbase(S.nc), cone_small, cone_big;
-    for (int i = 0; i < S.l; i++) zexp[i] = i;
-    {
-        int vb = S.l;
-        for (int c = 0; c < S.nc; c++) {
-            const int o = S.cone_off[c], d = S.q[c];
-            for (int k = 0; k < d; k++) zexp[o + k] = o + k + 2 * c;
-            zdsign[o + d - 1] = -1; // last cone row: -delta in the refinement operator (ref src/eicos.cpp:1552)
-            cone_vbase[c] = vb; vb += 3 * d + 1;
-            (d >= CONE_BIG ? cone_big : cone_small).push_back(c);
-        }
-    }
-    auto srcoff = [&](int kind, int src) {
-        switch (kind) {
-        case SRC_A: return D.i_Av + src;
-        case SRC_G: return D.i_Gv + src;
-        case SRC_V: return D.i_Vv + src;
-        case SRC_POSDELTA: return D.i_cst + 0;
-        case SRC_NEGDELTA: return D.i_cst + 1;
-        default: return D.i_cst + 2;
-        }
-    };
-
-
+int Planner::programs() {
     // ---- sliced-ELL plans of the two triangular sweeps (device_types.hpp: SliceMeta) ----
     // (tile mode: the sweeps and the factorisation run over the tile plan instead; the scalar plans stay empty)
-    TriPlan planF, planB;
     // A handle of at most one workgroup per CU gives NO level to a single wavefront: the idle wavefronts of such a part are issue slots for a
     // neighbour on the CU -- without one, every extra sweep call only adds a cold start (lp_bandm +2.2 %, lp_beaconfd +2.6 %, lp_blend +4 %,
     // lp_adlittle +2 %, lp_agg +0.6 %, lp_25fv47 +-0; MPC02 at three per CU -3 ... -7 %, which keeps its single-wavefront tree top)
-    const bool solo_ok = batch > h->n_cu || h->arith_profile == 1;
-    if (!tile1) { planF = build_tri_plan(S, h->threads, true, solo_ok); planB = build_tri_plan(S, h->threads, false, solo_ok); }
+    const bool solo_ok = batch > n_cu || profile == 1;
+    if (!tile1) { planF = build_tri_plan(S, pl.threads, true, solo_ok, pl.apex); planB = build_tri_plan(S, pl.threads, false, solo_ok, pl.apex); }
     else { planF.idx.assign(1, NV); planB.idx.assign(1, NV); planF.pos.assign(S.nnzL, 0); planB.pos.assign(S.nnzL, 0); }
     D.nfs = planF.n_wide; D.nbs = planB.n_wide; D.nfs_solo = planF.n_solo; D.nbs_solo = planB.n_solo; D.nfs_ext = planF.n_ext; D.nUF = planF.slots; D.nUB = planB.slots;
     {   // the real slices of every section: its length without the trailing padding (empty slices)
@@ -441,25 +440,23 @@ static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *
         D.nbs_solo_r = real(planB.sl, 0, planB.n_solo); D.nbs_r = real(planB.sl, planB.n_solo, planB.n_wide);
     }
     // every section of a sweep plan is a whole number of queue-depth trips (tri_sweep's remainder loop executes full trips)
-    if (D.nfs % TRI_DEPTH || D.nbs % TRI_DEPTH || D.nfs_ext % TRI_DEPTH || D.nfs_solo % TRI_DEPTH_SOLO || D.nbs_solo % TRI_DEPTH_SOLO) {
-        delete h; return fail(EICOS_E_INVALID, "internal: a section of a sweep plan is not padded to its queue depth");
-    }
+    if (D.nfs % TRI_DEPTH || D.nbs % TRI_DEPTH || D.nfs_ext % TRI_DEPTH || D.nfs_solo % TRI_DEPTH_SOLO || D.nbs_solo % TRI_DEPTH_SOLO)
+        return fail(EICOS_E_INVALID, "internal: a section of a sweep plan is not padded to its queue depth");
     // (value arrays: the plan's slots + the dummy slot, then -- dense apex -- the folded image of the block's own entries (APEX_IMG doubles), zero wherever no
     // entry of L lands: the work slabs are zeroed at creation and the factor program only ever writes entry slots)
     D.w_UF = Wl.add((size_t)planF.ulen + 8); D.w_UB = Wl.add((size_t)planB.ulen + 8);
-    const bool apex = !tile && S.apex0 >= 0;
+    const bool apex = !tile && pl.apex;
     D.apex_na = apex ? S.N - S.apex0 : 0; D.apex_n0 = apex ? S.apex0 : 0; D.apex_f = planF.apex_base; D.apex_b = planB.apex_base;
     D.apex_split_n = apex ? planF.split_n : 0; D.apex_split_slot = planF.split_slot0; D.apex_split_lane = planF.split_row - D.apex_n0;
     // (the parts' pseudo-rows N + 1 ... use the spare slots of the sweep vector: checked here against the plan's own bound and below, where the
     // vector's stride D.Npad is fixed, against that stride itself)
-    if (D.apex_split_n > 0 && (tile || planF.split_slot0 + planF.split_n > scalar_npad(NV))) { delete h; return fail(EICOS_E_INVALID, "internal: the split row of the apex does not fit the spare slots of the sweep vector"); }
-    h->posB = planB.pos; h->ub_len = planB.ulen;
+    if (D.apex_split_n > 0 && (tile || planF.split_slot0 + planF.split_n > scalar_npad(NV))) return fail(EICOS_E_INVALID, "internal: the split row of the apex does not fit the spare slots of the sweep vector");
+    pl.posB = planB.pos; pl.ub_len = planB.ulen;
     // numeric factorisation program: reads L.*D through the backward (column) slots; slot nUB is the zero dummy
-    FactorPlan planX;
-    if (!tile1) planX = build_factor_plan(S, h->threads, planB.pos, planB.slots, planF.pos, planF.slots);
+    if (!tile1) planX = build_factor_plan(S, pl.threads, planB.pos, planB.slots, planF.pos, planF.slots);
     else { planX.pa.assign(1, 0); planX.pb.assign(1, 0); planX.pbU.assign(1, 0); planX.pk.assign(1, 0); }
     D.fac_ns = (int)planX.sl.size(); D.fac_slots = planX.slots; D.fac_nt = (int)planX.target.size();
-    if ((long long)planB.ulen + 1 >= IMG_BASE || (long long)S.N >= DIAG_POS / 2) { delete h; return fail(EICOS_E_UNSUPPORTED, "pattern too large for the factor program's destination codes"); }
+    if ((long long)planB.ulen + 1 >= IMG_BASE || (long long)S.N >= DIAG_POS / 2) return fail(EICOS_E_UNSUPPORTED, "pattern too large for the factor program's destination codes");
     {   // level 0 of the factor program: the leaves of the elimination tree have no pairs; the kernel streams over their targets
         // (diagonals first: the per-level task order is stable for equal pair counts) instead of walking their slices
         D.fac_s1 = 0; D.fac_nd0 = 0; D.fac_nt0 = 0;
@@ -487,69 +484,47 @@ static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *
     }
     D.w_dual_xk = Wl.add(2 * ((size_t)NV + 16)); D.w_dual_ek = Wl.add(2 * ((size_t)NV + 16)); // dual right-hand-side solves
     D.work_stride = Wl.size;
-    std::vector<int> fac_src(planX.target.size()), fac_dst(planX.target.size()), fac_dstF(planX.target.size()), fac_col(planX.target.size(), 0);
-    std::vector<int> col_of(S.nnzL);
+    col_of.resize(S.nnzL);
     for (int j = 0; j < S.N; j++) for (int e = S.Lp[j]; e < S.Lp[j + 1]; e++) col_of[e] = j;
-    // ---- device form of the slice tables (PackedSlice) and 16-bit gather indices ----
-    // One 8-byte entry per lane and slice = its ELL_KMAX gather indices; entry position = off16 of the slice + lane;
-    // the entry after the last slice is all padding (read by inactive lanes).  Used when every index fits 16 bits.
+    // the slice tables in device form (PackedSlice) and their 16-bit gather indices
     bool idx16_ok = true;
-    auto lane_offsets = [](const std::vector<SliceMeta> &sl, int &dummy) {
-        std::vector<int> off16(sl.size());
-        int pos = 0;
-        for (size_t i = 0; i < sl.size(); i++) { off16[i] = pos; pos += sl[i].cnt << sl[i].lg; }
-        dummy = pos;
-        return off16;
-    };
-    auto pack16 = [&](const std::vector<SliceMeta> &sl, const std::vector<int> &off16, int dummy, const std::vector<int> &idx, int pad) {
-        std::vector<int> words(((size_t)dummy + 1) * 2, 0); // two 32-bit words = four 16-bit indices per lane entry
-        auto set = [&](size_t entry, int kk, int v) {
-            if (v < 0 || v > 65535) { idx16_ok = false; v = 0; }
-            words[entry * 2 + (kk >> 1)] |= v << (16 * (kk & 1));
-        };
-        for (size_t i = 0; i < sl.size(); i++) {
-            const int lanes = sl[i].cnt << sl[i].lg;
-            for (int t = 0; t < lanes; t++)
-                for (int kk = 0; kk < ELL_KMAX; kk++)
-                    set((size_t)off16[i] + t, kk, kk < sl[i].K ? idx[(size_t)sl[i].off + (size_t)kk * lanes + t] : pad);
-        }
-        for (int kk = 0; kk < ELL_KMAX; kk++) set((size_t)dummy, kk, pad);
-        return words;
-    };
-    auto meta_ints = [](const std::vector<SliceMeta> &v, const std::vector<int> &off16) {
-        std::vector<int> o(v.size() * 4);
-        for (size_t i = 0; i < v.size(); i++) {
-            const PackedSlice ps = pack_slice(v[i], off16.empty() ? 0 : off16[i]);
-            std::memcpy(o.data() + 4 * i, &ps, sizeof ps);
-        }
-        return o;
-    };
     const std::vector<int> f_o16 = lane_offsets(planF.sl, D.f_d16), b_o16 = lane_offsets(planB.sl, D.b_d16);
     const std::vector<int> cag_o16 = lane_offsets(pcag.sl, D.cag_d16), rA_o16 = lane_offsets(prA.sl, D.rA_d16), rG_o16 = lane_offsets(prG.sl, D.rG_d16);
-    const std::vector<int> f_w16 = pack16(planF.sl, f_o16, D.f_d16, planF.idx, NV), b_w16 = pack16(planB.sl, b_o16, D.b_d16, planB.idx, NV);
-    const std::vector<int> cag_k_w16 = pack16(pcag.sl, cag_o16, D.cag_d16, cag_idx_k, NV), cag_yz_w16 = pack16(pcag.sl, cag_o16, D.cag_d16, cag_idx_yz, 0);
-    const std::vector<int> rA_w16 = pack16(prA.sl, rA_o16, D.rA_d16, rA_idx, 0), rA_k_w16 = pack16(prA.sl, rA_o16, D.rA_d16, rA_idx_k, NV);
-    const std::vector<int> rG_w16 = pack16(prG.sl, rG_o16, D.rG_d16, rG_idx, 0), rG_k_w16 = pack16(prG.sl, rG_o16, D.rG_d16, rG_idx_k, NV);
+    f_w16 = pack16(planF.sl, f_o16, D.f_d16, planF.idx, NV, &idx16_ok); b_w16 = pack16(planB.sl, b_o16, D.b_d16, planB.idx, NV, &idx16_ok);
+    cag_k_w16 = pack16(pcag.sl, cag_o16, D.cag_d16, cag_idx_k, NV, &idx16_ok); cag_yz_w16 = pack16(pcag.sl, cag_o16, D.cag_d16, cag_idx_yz, 0, &idx16_ok);
+    rA_w16 = pack16(prA.sl, rA_o16, D.rA_d16, rA_idx, 0, &idx16_ok); rA_k_w16 = pack16(prA.sl, rA_o16, D.rA_d16, rA_idx_k, NV, &idx16_ok);
+    rG_w16 = pack16(prG.sl, rG_o16, D.rG_d16, rG_idx, 0, &idx16_ok); rG_k_w16 = pack16(prG.sl, rG_o16, D.rG_d16, rG_idx_k, NV, &idx16_ok);
     // factor program: the (pa, pb) slot pairs of a lane, 16 bytes per lane and slice (pa words then pb words)
     const std::vector<int> x_o16 = lane_offsets(planX.sl, D.fac_d16);
-    std::vector<int> fac_w16, fac_w16d, fac_k16;
     {
-        const std::vector<int> wa = pack16(planX.sl, x_o16, D.fac_d16, planX.pa, planB.slots), wb = pack16(planX.sl, x_o16, D.fac_d16, planX.pb, planF.slots);
-        const std::vector<int> wu = pack16(planX.sl, x_o16, D.fac_d16, planX.pbU, planB.slots); // deferred-L form: both operands are UB slots
-        fac_k16 = pack16(planX.sl, x_o16, D.fac_d16, planX.pk, S.N);                             // ... and the pivot column of every pair
+        const std::vector<int> wa = pack16(planX.sl, x_o16, D.fac_d16, planX.pa, planB.slots, &idx16_ok), wb = pack16(planX.sl, x_o16, D.fac_d16, planX.pb, planF.slots, &idx16_ok);
+        const std::vector<int> wu = pack16(planX.sl, x_o16, D.fac_d16, planX.pbU, planB.slots, &idx16_ok); // deferred-L form: both operands are UB slots
+        fac_k16 = pack16(planX.sl, x_o16, D.fac_d16, planX.pk, S.N, &idx16_ok);                             // ... and the pivot column of every pair
         fac_w16.resize(wa.size() * 2); fac_w16d.resize(wa.size() * 2);
         for (size_t e = 0; e * 2 < wa.size(); e++) {
             fac_w16[4 * e] = wa[2 * e]; fac_w16[4 * e + 1] = wa[2 * e + 1]; fac_w16[4 * e + 2] = wb[2 * e]; fac_w16[4 * e + 3] = wb[2 * e + 1];
             fac_w16d[4 * e] = wa[2 * e]; fac_w16d[4 * e + 1] = wa[2 * e + 1]; fac_w16d[4 * e + 2] = wu[2 * e]; fac_w16d[4 * e + 3] = wu[2 * e + 1];
         }
     }
-    D.idx16 = (idx16_ok && env_int("EICOS_IDX16", 1, 0, 1)) ? 1 : 0;
-    std::vector<int> fsl_i = meta_ints(planF.sl, f_o16), bsl_i = meta_ints(planB.sl, b_o16), fac_sl_i = meta_ints(planX.sl, x_o16);
-    std::vector<int> cag_sl_i = meta_ints(pcag.sl, cag_o16), rA_sl_i = meta_ints(prA.sl, rA_o16), rG_sl_i = meta_ints(prG.sl, rG_o16);
+    D.idx16 = (idx16_ok && env_knob("EICOS_IDX16", 1, 0, 1)) ? 1 : 0;
+    fsl_i = meta_ints(planF.sl, f_o16); bsl_i = meta_ints(planB.sl, b_o16); fac_sl_i = meta_ints(planX.sl, x_o16);
+    cag_sl_i = meta_ints(pcag.sl, cag_o16); rA_sl_i = meta_ints(prA.sl, rA_o16); rG_sl_i = meta_ints(prG.sl, rG_o16);
+    return EICOS_OK;
+}
 
-    struct Slot { const int **dst; size_t off; };
-    std::vector<Slot> slots;
-    auto put = [&](const int *&field, const std::vector<int> &v) { slots.push_back({&field, pool.add(v)}); };
+// the pattern arrays, in the order they enter the pool (that order fixes pattern_bytes and the pool's contents)
+void Planner::pool_image() {
+    auto put = [&](const int *&field, const std::vector<int> &v) { pl.put(field, v); };
+    std::vector<int> zdsign(S.m, 1), cone_vbase(S.nc), cone_small, cone_big;
+    {
+        int vb = S.l;
+        for (int c = 0; c < S.nc; c++) {
+            const int o = S.cone_off[c], d = S.q[c];
+            zdsign[o + d - 1] = -1; // last cone row: -delta in the refinement operator (ref src/eicos.cpp:1552)
+            cone_vbase[c] = vb; vb += 3 * d + 1;
+            (d >= CONE_BIG ? cone_big : cone_small).push_back(c);
+        }
+    }
     put(D.Ajc, P.Ajc); put(D.Air, P.Air); put(D.At_ptr, S.At_ptr); put(D.At_pos, S.At_pos);
     put(D.Gjc, P.Gjc); put(D.Gir, P.Gir); put(D.Gt_ptr, S.Gt_ptr); put(D.Gt_pos, S.Gt_pos);
     {
@@ -579,8 +554,7 @@ static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *
     put(D.f_idx, planF.idx); put(D.b_idx, planB.idx);
     put(D.f_idx16, f_w16); put(D.b_idx16, b_w16); put(D.cag_k16, cag_k_w16); put(D.cag_yz16, cag_yz_w16);
     put(D.rA_16, rA_w16); put(D.rA_k16, rA_k_w16); put(D.rG_16, rG_w16); put(D.rG_k16, rG_k_w16);
-    const int *fsl_p = nullptr, *bsl_p = nullptr, *cag_sl_p = nullptr, *rA_sl_p = nullptr, *rG_sl_p = nullptr;
-    put(fsl_p, fsl_i); put(bsl_p, bsl_i); put(cag_sl_p, cag_sl_i); put(rA_sl_p, rA_sl_i); put(rG_sl_p, rG_sl_i);
+    put(pl.fsl, fsl_i); put(pl.bsl, bsl_i); put(pl.cag_sl, cag_sl_i); put(pl.rA_sl, rA_sl_i); put(pl.rG_sl, rG_sl_i);
     put(D.cag_idx_k, cag_idx_k); put(D.cag_idx_yz, cag_idx_yz); put(D.cag_src, cag_src);
     put(D.rA_idx, rA_idx); put(D.rA_src, rA_src); put(D.rG_idx, rG_idx); put(D.rG_src, rG_src);
     put(D.rA_idx_k, rA_idx_k); put(D.rG_idx_k, rG_idx_k);
@@ -593,12 +567,11 @@ static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *
     put(D.ipx, ipx); put(D.ipy, ipy); put(D.ipz, ipz); put(D.ipv, ipv); put(D.ipu, ipu);
     std::vector<int> ipk(ipx); ipk.insert(ipk.end(), ipy.begin(), ipy.end()); ipk.insert(ipk.end(), ipz.begin(), ipz.end());
     put(D.ipk, ipk);
-    const int Npad_v = tile ? NV + 16 : (NV + 1 + 15) & ~15; // (= D.Npad below)
     std::vector<int> zpos; // sweep-vector slots no x / y / z entry lands in: cone expansions, padding (inside the blocks in tile layouts)
     {
-        std::vector<char> hit((size_t)Npad_v, 0);
+        std::vector<char> hit((size_t)D.Npad, 0);
         for (int o : ipk) hit[o] = 1;
-        for (int i = 0; i < Npad_v; i++) if (!hit[i]) zpos.push_back(i);
+        for (int i = 0; i < D.Npad; i++) if (!hit[i]) zpos.push_back(i);
     }
     D.nzpos = (int)zpos.size();
     put(D.zpos, zpos);
@@ -611,6 +584,7 @@ static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *
         for (int c = 0; c < S.nc; c++) { if (orig == k + S.q[c] + 1) return true; k += S.q[c] + 2; }
         return false;
     };
+    std::vector<int> fac_src(planX.target.size()), fac_dst(planX.target.size()), fac_dstF(planX.target.size()), fac_col(planX.target.size(), 0);
     for (size_t t = 0; t < planX.target.size(); t++) {
         const int tgt = planX.target[t];
         if (tgt < S.N) { fac_src[t] = srcoff(S.Dkind[tgt], S.Dsrc[tgt]); fac_dst[t] = -tgt - 1 - (pivot_positive(tgt) ? DIAG_POS : 0); fac_dstF[t] = 0; }
@@ -645,7 +619,7 @@ static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *
     put(D.tl_pa, TP.pa); put(D.tl_pb, TP.pb); put(D.tl_pk, TP.pk); put(D.tl_fin_lev, TP.fin_lev_ptr); put(D.tl_fin, TP.fin);
     TileSweeps TSW;
     // (hybrid patterns whose vectors certainly live in LDS -- a serially swept block system relies on the in-order LDS accesses of one wavefront)
-    if (tile) TSW = build_tile_sweeps(TP, h->threads / 64, TILE_STRIP, (S.tile == 2 && TP.N16 <= 4096) ? env_int("EICOS_TILE_SERIAL_MAX", 48, 0, 100000) : 0);
+    if (tile) TSW = build_tile_sweeps(TP, pl.threads / 64, TILE_STRIP, (S.tile == 2 && TP.N16 <= 4096) ? env_knob("EICOS_TILE_SERIAL_MAX", 48, 0, 100000) : 0);
     put(D.tl_fops, TSW.fops); put(D.tl_bops, TSW.bops); put(D.tl_fptr, TSW.fptr); put(D.tl_bptr, TSW.bptr);
     put(D.tl_fsplit, TSW.fsplit); put(D.tl_bsplit, TSW.bsplit); put(D.tl_fend, TSW.fend); put(D.tl_bend, TSW.bend);
     TileFactorOps TFO;
@@ -654,216 +628,362 @@ static int batch_create_impl(int n, int m, int p, int l, int ncones, const int *
         // a load; the image tile they would have read stays zero and is never touched (hybrid: the scalar program writes every tile)
         std::vector<char> img_zero((size_t)TP.nb + TP.nt, tile1 ? 1 : 0);
         for (int d : img_dst) img_zero[d / 256] = 0;
-        TFO = build_tile_factor_ops(TP, h->threads / 64, TILE_FTRIP, &img_zero);
+        TFO = build_tile_factor_ops(TP, pl.threads / 64, TILE_FTRIP, &img_zero);
     }
     put(D.tl_facops, TFO.ops); put(D.tl_facptr, TFO.ptr);
     put(D.tl_ident, TP.ident);
     put(D.tl_trow, TP.t_row); put(D.tl_tcol, TP.t_col); put(D.tl_tc_ptr, TP.tc_ptr); put(D.tl_tr_ptr, TP.tr_ptr); put(D.tl_tr_tile, TP.tr_tile);
     put(D.v2t, v2t);
-    const int *fac_sl_p = nullptr;
-    put(fac_sl_p, fac_sl_i);
-    const int *fac_pb_f = nullptr, *fac_pb_u = nullptr, *fac_p16_f = nullptr, *fac_p16_u = nullptr; // (stored-L / deferred-L forms: chosen with NLDS below)
-    put(D.fac_pa, planX.pa); put(fac_pb_f, planX.pb); put(fac_pb_u, planX.pbU); put(fac_p16_f, fac_w16); put(fac_p16_u, fac_w16d);
+    put(pl.fac_sl, fac_sl_i);
+    // (stored-L / deferred-L forms of the factor operands: the launch shape chooses, allocate() points DevPat at one)
+    put(D.fac_pa, planX.pa); put(pl.fac_pb_f, planX.pb); put(pl.fac_pb_u, planX.pbU); put(pl.fac_p16_f, fac_w16); put(pl.fac_p16_u, fac_w16d);
     put(D.fac_pk, planX.pk); put(D.fac_k16, fac_k16);
     put(D.fac_src, fac_src); put(D.fac_dst, fac_dst); put(D.fac_dstF, fac_dstF); put(D.fac_col, fac_col);
+}
 
-    // ---- device resources ----
-    auto bail = [&](int code, const std::string &msg) { eicos_batch_destroy(h); return fail(code, msg); };
-#define HIP_TRY_H(expr)                                                                            \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return bail(EICOS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-    // (device set-up -- kernel attributes, occupancy probes, allocations, the constant-memory slot; the shards of an eicos_multi are
-    // created on parallel host threads, which overlaps their symbolic analyses above)
-    // One lock PER DEVICE: the shards of an eicos_multi that live on different GPUs set their devices up in parallel, two handles on one
-    // GPU still take turns (the occupancy probes and hipFuncSetAttribute calls of one device must not interleave).
-    static std::mutex g_create_map_mu;
-    static std::map<int, std::mutex> g_create_mu;
-    std::mutex *dev_mu;
-    { std::lock_guard<std::mutex> lk(g_create_map_mu); dev_mu = &g_create_mu[device]; }
-    std::lock_guard<std::mutex> create_lock(*dev_mu);
-    HIP_TRY_H(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIP_TRY_H(hipGetDeviceProperties(&prop, device));
-    // launch shape: env overrides are for experiments (bench sweeps); defaults chosen from measurements
+} // namespace
+
+// Analysis step: the pattern's symbolic analysis, the workgroup size, whether plans may carry the dense apex, and -- small hybrid patterns
+// -- the scalar analysis with a dense apex that such a plan uses instead.  `profile` = eicos_set_arithmetic_profile at creation.
+static int analyse(const ProblemPattern &P, int batch, int n_cu, int profile, Analyses &A) {
+    // (experiment knobs, envknob.hpp: honoured only under EICOS_EXPERIMENT=1, range-checked)
+    const int order = env_knob("EICOS_ORDER", -1, 0, 16), tiles = env_knob("EICOS_TILES", -1, 0, 2);
+    try {
+        A.main.sym = analyze(P, order, tiles);
+        if (A.main.sym.tile) A.main.tiles = build_tile_plan(A.main.sym);
+    } catch (const std::invalid_argument &e) { return fail(EICOS_E_INVALID, e.what()); }
+    catch (const std::runtime_error &e) { return fail(EICOS_E_UNSUPPORTED, e.what()); }
+    catch (const std::exception &e) { return fail(EICOS_E_INVALID, e.what()); }
+    const Symbolic &S = A.main.sym;
+    // workgroup size by problem size (measured, batch 256: dim_K 129 -> 128, 1249 -> 256, >= 3815 -> 512 threads);
+    // batches beyond one workgroup per CU are throughput-bound: 256 threads issue a third fewer wavefront-slices
+    // per instance than 512 and fit three workgroups per CU (MPC02 pattern: 500 k vs 414 k iterations/s)
+    const int dimK = P.n + P.p + P.m + 2 * P.nc;
+    // (sparse factors only: with ~50 entries per row of L -- the dense-front config -- 512 threads stay ahead)
+    // (arithmetic profile 1: every choice that shapes a PLAN -- and with it the order of the floating-point operations -- is made as for a
+    // batch beyond one workgroup per CU, whatever the batch really is: workgroup size by pattern size alone, no dense apex, the
+    // single-wavefront tree top; the launch shape itself -- grid, LDS residency, dual solves, which are bit-neutral -- follows the real batch)
+    const bool as_large = profile == 1;
+    const bool throughput_bound = (batch > n_cu || as_large) && (long long)S.nnzL < 16LL * S.N;
+    // one workgroup per CU (batch <= CUs): latency-bound, more wavefronts per instance pay earlier (measured at batch 256 with
+    // the 256-VGPR build of the 512-thread kernels: lp_blend / lp_adlittle, dim_K ~ 300: 256 threads +5..8 % over 128;
+    // lp_beaconfd / lp_bandm / lp_agg, dim_K 763..1718: 512 threads +7..12 % over 256)
+    const int dflt = throughput_bound ? (dimK < 400 ? 128 : 256) : (dimK < 250 ? 128 : (dimK < 700 ? 256 : 512));
+    const int t = env_knob("EICOS_THREADS", dflt, 128, 512);
+    if (t != 128 && t != 256 && t != 512) return fail(EICOS_E_INVALID, "EICOS_THREADS must be 128, 256 or 512");
+    A.threads = t;
+    // ---- dense apex: not under profile 1, not with 128-thread workgroups (small patterns; kernels.hip: apex_on) -- except in the
+    // LDS-resident build, whose images then live in the LDS copy of the workspace slab; whether that build is taken is known from the
+    // launch shape (eicos_batch_create) ----
+    A.apex = profile == 0 && (t >= 256 || (t == 128 && env_knob("EICOS_LDSRES", 1, 0, 1) && batch <= n_cu));
+    // small patterns whose narrow tree top would go to the tile path (hybrid): the level schedule + dense apex does better there -- a
+    // handful of 16 x 16 blocks costs two workgroup-wide block levels each, the apex swallows the whole tail in 2 x 64 register steps
+    // (lp_adlittle 1.13 -> 1.33 M, lp_blend 0.92 -> 1.08 M iter/s at batch 256; larger tops -- lp_bandm, lp_agg, lp_25fv47 -- stay hybrid:
+    // their top blocks are dense and the MFMA factorisation of the block is what pays there)
+    if (A.apex && S.tile == 2 && S.N < APEX_OVER_HYBRID_BELOW && t >= 256 && tiles < 0) {
+        try {
+            Symbolic alt = analyze(P, order, 0);
+            if (alt.apex0 >= 0) { A.apex_alt.sym = std::move(alt); A.has_alt = true; }
+        } catch (const std::exception &) { /* keep the hybrid analysis */ }
+    }
+    return EICOS_OK;
+}
+
+// Plan step: pure host code (no HIP call, no eicos_batch).  `apex`: the plan carries the dense apex when its analysis has one.
+static int build_plan(const ProblemPattern &P, Analyses &A, bool apex, int batch, int n_cu, int profile, Plan &pl) {
+    Analysis &an = A.for_plan(apex);
+    const Symbolic &S = an.sym;
+    pl.an = &an; pl.apex = apex && S.apex0 >= 0; pl.threads = A.threads;
+    if (S.npairs >= (int64_t)1 << 31) return fail(EICOS_E_UNSUPPORTED, "factor program exceeds 2^31 pairs");
+    if (S.tile) { // the tile image, the tile arrays of L and their workspace offsets are indexed with 32-bit ints
+        const long long img = ((long long)an.tiles.nb + an.tiles.nt) * 256;
+        if (img >= IMG_BASE || (long long)S.N + img >= DIAG_POS / 2 || 3 * img * (long long)sizeof(double) > (8LL << 30))
+            return fail(EICOS_E_UNSUPPORTED, "dense-front pattern too large: the tile image of L exceeds the per-workgroup workspace budget");
+    }
+    Planner pr(P, an, pl, batch, n_cu, profile);
+    int rc = pr.layout_and_products();
+    if (rc == EICOS_OK) rc = pr.programs();
+    if (rc != EICOS_OK) return rc;
+    DevPat &D = pl.dp;
+    D.Npad = pr.tile ? pr.NV + 16 : (pr.NV + 1 + 15) & ~15; // >= N+1: slot N is the always-zero target of ELL padding (tile mode: a whole zero block)
+    if (D.apex_split_n > 0 && D.apex_split_slot + D.apex_split_n > D.Npad) return fail(EICOS_E_INVALID, "internal: the split row of the apex runs past the sweep vector's stride");
+    pr.pool_image();
+    return EICOS_OK;
+}
+
+// One creation lock PER DEVICE: the shards of an eicos_multi that live on different GPUs set their devices up in parallel, two handles on
+// one GPU take turns (the occupancy probes and hipFuncSetAttribute calls of one device must not interleave).
+static std::mutex &create_mutex(int device) {
+    static std::mutex map_mu;
+    static std::map<int, std::mutex> mus;
+    std::lock_guard<std::mutex> lk(map_mu);
+    return mus[device];
+}
+
+// The LDS budget of a plan (pure host code): which KKT-space vectors and slice tables live in LDS, dual right-hand sides, the
+// deferred-L factorisation, the LDS-resident build.  Fills the LDS fields of the plan's DevPat.
+static void lds_budget(Plan &pl, int batch, int n_cu, Shape &sh) {
+    const Symbolic &S = pl.an->sym;
+    DevPat &D = pl.dp;
+    const bool tile = S.tile != 0, tile1 = S.tile == 1;
+    const int NV = D.N, threads = pl.threads;
     // KKT-space vectors (solve vector, current solution, refinement residual) live in LDS when they fit:
     // 160 KiB per CU minus the static block (reductions + scalar state)
-    if (D.apex_split_n > 0 && D.apex_split_slot + D.apex_split_n > Npad_v) { delete h; return fail(EICOS_E_INVALID, "internal: the split row of the apex runs past the sweep vector's stride"); }
-    D.Npad = Npad_v; // tile ? NV + 16 : (NV + 1 + 15) & ~15 // >= N+1: slot N is the always-zero target of ELL padding (tile mode: a whole zero block)
-    {
-        D.lm_f = 0; D.lm_b = D.lm_f + D.nfs + D.nfs_solo + D.nfs_ext; D.lm_cag = D.lm_b + D.nbs + D.nbs_solo; D.lm_rA = D.lm_cag + D.cag_ns; D.lm_rG = D.lm_rA + D.rA_ns;
-        D.lm_total = D.lm_rG + D.rG_ns;
-        const size_t avail = 160 * 1024 - 4096, vec = (size_t)std::max(D.Npad, 16) * sizeof(double);
-        const size_t lds_static = 4096; // struct Sh + the per-instance states of kernels.hip (reductions + scalar state), rounded up
-        // tile mode: one 16 x 17 fp64 scratch tile per wavefront (dense LDL' of the diagonal tiles), behind the tables
-        // ... and the partial-sum slots of split blocks in the tile sweeps (TILE_PARTS x 16 rows x two right-hand sides)
-        // dense apex: the packed image of the block's L (same place: the scalar path has no tile scratch)
-        const size_t apex_img = (D.apex_na > 0 && h->threads >= 256) ? (size_t)APEX_IMG * sizeof(double) : 0; // (128 threads: the image IS the slab's, in LDS)
-        const size_t scratch = tile ? ((size_t)(h->threads / 64) * TILE_SCR + (size_t)TILE_PARTS * 16 * KI_MAX_HOST) * sizeof(double) : apex_img;
-        // workgroups per CU that 160 KB of LDS allow with one vector + tables of `slices` entries
-        const int wgs_by_regs = (h->threads == 256 ? 3 : (h->threads == 512 ? 2 : 4)) * 4 / (h->threads / 64); // waves_per_eu<T>() of kernels.hip
-        auto wgs_per_cu = [&](int slices) {
-            return std::min(wgs_by_regs, (int)((160 * 1024) / (vec + (size_t)slices * sizeof(PackedSlice) + scratch + lds_static)));
-        };
-        // the factor program's table goes to LDS too when it is small and does not cost a resident workgroup
-        if (D.fac_ns <= 512 && wgs_per_cu(D.lm_total + D.fac_ns) == wgs_per_cu(D.lm_total)) {
-            D.lm_fac = D.lm_total; D.lm_total += D.fac_ns;
-        } else D.lm_fac = -1;
-        const size_t meta = (size_t)D.lm_total * sizeof(PackedSlice) + scratch;
-        // NLDS >= 1 also stages both slice tables in LDS; if they do not fit beside one vector the
-        // all-global variant (NLDS = 0, plain __syncthreads between levels) is used
-        // KKT-space vectors in LDS: E (rhs / residual / solve vector) and X (current solution), + both slice tables
-        int fit = 0;
-        if (NV > 0 && meta + vec <= avail) fit = (meta + 2 * vec <= avail) ? 2 : 1;
-        // more instances than CUs: keep only E in LDS so that several workgroups share a CU (measured)
-        int want = fit;
-        if (batch > prop.multiProcessorCount && fit == 2 && 2 * (vec + meta + 4096) <= 160 * 1024) want = 1;
-        h->nlds = std::max(0, std::min(fit, env_int("EICOS_NLDS", want, 0, 2)));
-        // Dual right-hand-side solves (the two independent systems of the initialisation and of every pass share one
-        // sweep over the factor): needs two vectors in LDS.  Pure tile mode (bandwidth-bound on streaming L and G): always.
-        // Scalar / hybrid programs: when the batch fits one workgroup per CU -- the sweeps are then a dependent chain of level
-        // steps, and a step for two right-hand sides costs far less than two steps
-        int dual = (fit == 2 && (tile1 || batch <= prop.multiProcessorCount)) ? 1 : 0;
-        dual = env_int("EICOS_DUAL", dual, 0, 1);
-        if (fit < 2) dual = 0;
-        if (dual) h->nlds = 1;
-        D.dual = dual;
-        const int nvec = dual ? 2 : h->nlds; // vectors of Npad doubles at the start of the dynamic LDS
-        D.meta_lds = h->nlds >= 1 ? 1 : 0;
-        // deferred-L factorisation (device_types.hpp: fac_defer): needs the idle LDS solve vector for the mirror of 1/D
-        // It trades one LDS read per pair for a write + read of every L entry and one barrier per level: measured +1.5..3.3 % on MPC02 and
-        // nine Netlib patterns (pairs/nnzL 1.7..7.5), -1 % on lp_25fv47 (10.1) -- profiles/r03_log_defer.log; the rule below is that fit.
-        const int defer_auto = (double)S.npairs <= 8.0 * (double)S.nnzL ? 1 : 0;
-        D.fac_defer = (!tile1 && h->nlds >= 1 && env_int("EICOS_FAC_DEFER", defer_auto, 0, 1)) ? 1 : 0;
-        D.fac_kpad = S.N;
-        h->dyn_lds = h->nlds >= 1 ? (size_t)nvec * vec + meta : (tile ? scratch : 0); // (no LDS vector: the apex sweeps read the global images, no LDS image)
-        D.lds_tab = h->nlds >= 1 ? nvec * D.Npad : 0;
-        D.tl_scratch = h->nlds >= 1 ? nvec * D.Npad + D.lm_total * 2 : 0; // in doubles from the start of the dynamic LDS
-        D.tl_part = D.tl_scratch + (h->threads / 64) * TILE_SCR;
-        D.apex_lds = (D.apex_na > 0 && h->nlds >= 1) ? D.tl_scratch : -1; // (no LDS vector: the apex sweeps read the global images)
-        D.apex_inplace = 0;
-        // LDS-resident variant (small patterns, kernels_ldsres.hip): when the instance slab and the workspace slab fit LDS
-        // beside the vectors and tables, k_solve works on LDS copies of both, so the elementwise stages and the products wait
-        // for LDS instead of L2 (+12 % on lp_afiro at batch 256; the level-by-level sweeps are issue-bound and do not change:
-        // DESIGN.md 5.1).  Only for batches that fit the grid in one round -- beyond that the eight small workgroups per CU
-        // of the HBM-slab kernel hide more latency than the <= 3 that LDS holds here (measured, lp_afiro batch 2048).
-        h->ldsres = 0; D.lr_inst = D.lr_work = 0;
-        if (!tile && h->nlds >= 1 && h->threads == 128 && env_int("EICOS_LDSRES", 1, 0, 1)) {
-            const size_t base = (h->dyn_lds + 15) & ~(size_t)15, islab = (D.inst_stride + 1) & ~(size_t)1, wslab = (D.work_stride + 1) & ~(size_t)1;
-            const size_t total = base + (islab + wslab) * sizeof(double);
-            const size_t per_cu = (160 * 1024) / (total + lds_static); // workgroups per CU that LDS allows
-            if (per_cu >= 1 && (size_t)batch <= per_cu * (size_t)prop.multiProcessorCount) {
-                h->ldsres = 1; D.lr_inst = (int)(base / sizeof(double)); D.lr_work = D.lr_inst + (int)islab;
-                h->dyn_lds = total;
-            }
-        }
-        if (D.apex_na > 0 && h->threads == 128) { // the apex of a 128-thread handle reads the forward image where it is: the LDS copy of the workspace slab
-            if (!h->ldsres) return bail(EICOS_RETRY_NO_APEX, "internal: 128-thread handle with an apex but without the LDS-resident build");
-            D.apex_lds = D.lr_work + D.w_UF + D.apex_f; D.apex_inplace = 1;
+    D.lm_f = 0; D.lm_b = D.lm_f + D.nfs + D.nfs_solo + D.nfs_ext; D.lm_cag = D.lm_b + D.nbs + D.nbs_solo; D.lm_rA = D.lm_cag + D.cag_ns; D.lm_rG = D.lm_rA + D.rA_ns;
+    D.lm_total = D.lm_rG + D.rG_ns;
+    const size_t avail = 160 * 1024 - 4096, vec = (size_t)std::max(D.Npad, 16) * sizeof(double);
+    const size_t lds_static = 4096; // struct Sh + the per-instance states of kernels.hip (reductions + scalar state), rounded up
+    // tile mode: one 16 x 17 fp64 scratch tile per wavefront (dense LDL' of the diagonal tiles), behind the tables
+    // ... and the partial-sum slots of split blocks in the tile sweeps (TILE_PARTS x 16 rows x two right-hand sides)
+    // dense apex: the packed image of the block's L (same place: the scalar path has no tile scratch)
+    const size_t apex_img = (D.apex_na > 0 && threads >= 256) ? (size_t)APEX_IMG * sizeof(double) : 0; // (128 threads: the image IS the slab's, in LDS)
+    const size_t scratch = tile ? ((size_t)(threads / 64) * TILE_SCR + (size_t)TILE_PARTS * 16 * KI_MAX_HOST) * sizeof(double) : apex_img;
+    // workgroups per CU that 160 KB of LDS allow with one vector + tables of `slices` entries
+    const int wgs_by_regs = (threads == 256 ? 3 : (threads == 512 ? 2 : 4)) * 4 / (threads / 64); // waves_per_eu<T>() of kernels.hip
+    auto wgs_per_cu = [&](int slices) {
+        return std::min(wgs_by_regs, (int)((160 * 1024) / (vec + (size_t)slices * sizeof(PackedSlice) + scratch + lds_static)));
+    };
+    // the factor program's table goes to LDS too when it is small and does not cost a resident workgroup
+    if (D.fac_ns <= 512 && wgs_per_cu(D.lm_total + D.fac_ns) == wgs_per_cu(D.lm_total)) {
+        D.lm_fac = D.lm_total; D.lm_total += D.fac_ns;
+    } else D.lm_fac = -1;
+    const size_t meta = (size_t)D.lm_total * sizeof(PackedSlice) + scratch;
+    // NLDS >= 1 also stages both slice tables in LDS; if they do not fit beside one vector the
+    // all-global variant (NLDS = 0, plain __syncthreads between levels) is used
+    // KKT-space vectors in LDS: E (rhs / residual / solve vector) and X (current solution), + both slice tables
+    int fit = 0;
+    if (NV > 0 && meta + vec <= avail) fit = (meta + 2 * vec <= avail) ? 2 : 1;
+    // more instances than CUs: keep only E in LDS so that several workgroups share a CU (measured)
+    int want = fit;
+    if (batch > n_cu && fit == 2 && 2 * (vec + meta + 4096) <= 160 * 1024) want = 1;
+    sh.nlds = std::max(0, std::min(fit, env_knob("EICOS_NLDS", want, 0, 2)));
+    // Dual right-hand-side solves (the two independent systems of the initialisation and of every pass share one
+    // sweep over the factor): needs two vectors in LDS.  Pure tile mode (bandwidth-bound on streaming L and G): always.
+    // Scalar / hybrid programs: when the batch fits one workgroup per CU -- the sweeps are then a dependent chain of level
+    // steps, and a step for two right-hand sides costs far less than two steps
+    int dual = (fit == 2 && (tile1 || batch <= n_cu)) ? 1 : 0;
+    dual = env_knob("EICOS_DUAL", dual, 0, 1);
+    if (fit < 2) dual = 0;
+    if (dual) sh.nlds = 1;
+    D.dual = dual;
+    const int nvec = dual ? 2 : sh.nlds; // vectors of Npad doubles at the start of the dynamic LDS
+    D.meta_lds = sh.nlds >= 1 ? 1 : 0;
+    // deferred-L factorisation (device_types.hpp: fac_defer): needs the idle LDS solve vector for the mirror of 1/D
+    // It trades one LDS read per pair for a write + read of every L entry and one barrier per level: measured +1.5..3.3 % on MPC02 and
+    // nine Netlib patterns (pairs/nnzL 1.7..7.5), -1 % on lp_25fv47 (10.1) -- profiles/r03_log_defer.log; the rule below is that fit.
+    const int defer_auto = (double)S.npairs <= 8.0 * (double)S.nnzL ? 1 : 0;
+    D.fac_defer = (!tile1 && sh.nlds >= 1 && env_knob("EICOS_FAC_DEFER", defer_auto, 0, 1)) ? 1 : 0;
+    D.fac_kpad = S.N;
+    sh.dyn_lds = sh.nlds >= 1 ? (size_t)nvec * vec + meta : (tile ? scratch : 0); // (no LDS vector: the apex sweeps read the global images, no LDS image)
+    D.lds_tab = sh.nlds >= 1 ? nvec * D.Npad : 0;
+    D.tl_scratch = sh.nlds >= 1 ? nvec * D.Npad + D.lm_total * 2 : 0; // in doubles from the start of the dynamic LDS
+    D.tl_part = D.tl_scratch + (threads / 64) * TILE_SCR;
+    D.apex_lds = (D.apex_na > 0 && sh.nlds >= 1) ? D.tl_scratch : -1; // (no LDS vector: the apex sweeps read the global images)
+    D.apex_inplace = 0;
+    // LDS-resident variant (small patterns, kernels_ldsres.hip): when the instance slab and the workspace slab fit LDS
+    // beside the vectors and tables, k_solve works on LDS copies of both, so the elementwise stages and the products wait
+    // for LDS instead of L2 (+12 % on lp_afiro at batch 256; the level-by-level sweeps are issue-bound and do not change:
+    // DESIGN.md 5.1).  Only for batches that fit the grid in one round -- beyond that the eight small workgroups per CU
+    // of the HBM-slab kernel hide more latency than the <= 3 that LDS holds here (measured, lp_afiro batch 2048).
+    sh.ldsres = 0; D.lr_inst = D.lr_work = 0;
+    if (!tile && sh.nlds >= 1 && threads == 128 && env_knob("EICOS_LDSRES", 1, 0, 1)) {
+        const size_t base = (sh.dyn_lds + 15) & ~(size_t)15, islab = (D.inst_stride + 1) & ~(size_t)1, wslab = (D.work_stride + 1) & ~(size_t)1;
+        const size_t total = base + (islab + wslab) * sizeof(double);
+        const size_t per_cu = (160 * 1024) / (total + lds_static); // workgroups per CU that LDS allows
+        if (per_cu >= 1 && (size_t)batch <= per_cu * (size_t)n_cu) {
+            sh.ldsres = 1; D.lr_inst = (int)(base / sizeof(double)); D.lr_work = D.lr_inst + (int)islab;
+            sh.dyn_lds = total;
         }
     }
+    if (D.apex_na > 0 && threads == 128) { // the apex of a 128-thread handle reads the forward image where it is: the LDS copy of the workspace slab
+        if (!sh.ldsres) { sh.apex_unplaced = true; return; }
+        D.apex_lds = D.lr_work + D.w_UF + D.apex_f; D.apex_inplace = 1;
+    }
+}
+
+// Launch-shape step: the LDS budget, then -- under the device's creation lock -- the occupancy probes and the choice of the kernel build
+// (w2 / U in LDS), the LDS head of the refinement residual, the grid and the updateData kernel.  Allocates nothing.
+static int launch_shape(Plan &pl, int batch, int device, Shape &sh) {
+    std::lock_guard<std::mutex> create_lock(create_mutex(device));
+    HIP_TRY(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    const int n_cu = prop.multiProcessorCount, threads = pl.threads;
+    lds_budget(pl, batch, n_cu, sh);
+    if (sh.apex_unplaced) return EICOS_OK;
+    const Symbolic &S = pl.an->sym;
+    DevPat &D = pl.dp;
+    const int idx16 = D.idx16;
     int bpc = 1;
     {
-        const SolveBuild sb = solve_build(h->threads, h->ldsres, false);
-        HIP_TRY_H(sb.set_max_lds(h->threads, h->nlds, h->dp.idx16, h->dyn_lds));
-        HIP_TRY_H(sb.occupancy(h->threads, h->nlds, h->dp.idx16, h->dyn_lds, &bpc));
+        const SolveBuild sb = solve_build(threads, sh.ldsres, false);
+        HIP_TRY(sb.set_max_lds(threads, sh.nlds, idx16, sh.dyn_lds));
+        HIP_TRY(sb.occupancy(threads, sh.nlds, idx16, sh.dyn_lds, &bpc));
     }
     bpc = std::max(1, std::min(bpc, 8));
-    HIP_TRY_H(update_set_max_lds()); // (per handle = per device, after hipSetDevice: the entry-parallel updateData kernels use up to 160 KB of dynamic LDS)
-    {
-        // Workgroups per CU for this batch: the cheapest estimate (launch_blocks_per_cu, measured constants)
-        bpc = launch_blocks_per_cu(batch, prop.multiProcessorCount, bpc, h->threads);
-    }
-    bpc = std::max(1, std::min(bpc, env_int("EICOS_BLOCKS_PER_CU", bpc, 1, 8)));
+    HIP_TRY(update_set_max_lds()); // (per handle = per device, after hipSetDevice: the entry-parallel updateData kernels use up to 160 KB of dynamic LDS)
+    bpc = launch_blocks_per_cu(batch, n_cu, bpc, threads); // workgroups per CU for this batch: the cheapest estimate (measured constants)
+    bpc = std::max(1, std::min(bpc, env_knob("EICOS_BLOCKS_PER_CU", bpc, 1, 8)));
     // 256 threads at <= 2 workgroups per CU: the build with 256 VGPRs per thread (the default one is held to 168 so that three fit)
-    h->w2 = 0;
-    if (!h->ldsres && h->threads == 256 && bpc <= 2 && env_int("EICOS_W2", 1, 0, 1)) {
+    sh.w2 = 0;
+    if (!sh.ldsres && threads == 256 && bpc <= 2 && env_knob("EICOS_W2", 1, 0, 1)) {
+        const SolveBuild wb = solve_build(threads, false, true);
         int got = 0;
-        HIP_TRY_H(w2::solve_set_max_lds(h->threads, h->nlds, h->dp.idx16, h->dyn_lds));
-        HIP_TRY_H(w2::solve_occupancy(h->threads, h->nlds, h->dp.idx16, h->dyn_lds, &got));
-        if (got >= bpc) h->w2 = 1;
+        HIP_TRY(wb.set_max_lds(threads, sh.nlds, idx16, sh.dyn_lds));
+        HIP_TRY(wb.occupancy(threads, sh.nlds, idx16, sh.dyn_lds, &got));
+        if (got >= bpc) sh.w2 = 1;
     }
     // One workgroup per CU (batch <= CUs) and the factor operand array U = L.*D fits the LDS that the lone workgroup leaves idle: the build that
     // keeps it there (kernels_ubl*.hip).  The numeric factorisation of a deep pattern is a chain of levels that each wait for operand gathers
     // and for their stores to land -- L2 round trips with U in the workspace slab, LDS round trips here; bit-identical results.
-    h->ubl = 0; D.ub_lds = -1; D.ub_len = h->ub_len;
-    if (!h->ldsres && (h->threads == 256 || h->threads == 512) && bpc == 1 && batch <= prop.multiProcessorCount && h->nlds >= 1 && D.fac_defer && !tile1 &&
-        !(D.apex_na > 0 && D.apex_lds < 0) && env_int("EICOS_UBL", 1, 0, 1)) {
-        const size_t base = (h->dyn_lds + 15) & ~(size_t)15, need = base + ((size_t)h->ub_len + 8) * sizeof(double);
+    sh.ubl = 0; D.ub_lds = -1; D.ub_len = pl.ub_len;
+    if (!sh.ldsres && (threads == 256 || threads == 512) && bpc == 1 && batch <= n_cu && sh.nlds >= 1 && D.fac_defer && S.tile != 1 &&
+        !(D.apex_na > 0 && D.apex_lds < 0) && env_knob("EICOS_UBL", 1, 0, 1)) {
+        const size_t base = (sh.dyn_lds + 15) & ~(size_t)15, need = base + ((size_t)pl.ub_len + 8) * sizeof(double);
         if (need + 4096 <= 160 * 1024) { // (4 KB: the static block, as budgeted above)
-            const SolveBuild ub = solve_build(h->threads, false, false, true);
+            const SolveBuild ub = solve_build(threads, false, false, true);
             int got = 0;
-            HIP_TRY_H(ub.set_max_lds(h->threads, h->nlds, h->dp.idx16, need));
-            HIP_TRY_H(ub.occupancy(h->threads, h->nlds, h->dp.idx16, need, &got));
-            if (got >= 1) { h->ubl = 1; h->w2 = 0; D.ub_lds = (int)(base / sizeof(double)); h->dyn_lds = need; }
+            HIP_TRY(ub.set_max_lds(threads, sh.nlds, idx16, need));
+            HIP_TRY(ub.occupancy(threads, sh.nlds, idx16, need, &got));
+            if (got >= 1) { sh.ubl = 1; sh.w2 = 0; D.ub_lds = (int)(base / sizeof(double)); sh.dyn_lds = need; }
         }
     }
-    const SolveBuild sbuild = solve_build(h->threads, h->ldsres, h->w2, h->ubl);
-    auto v_set_max_lds = sbuild.set_max_lds;
-    auto v_occupancy = sbuild.occupancy;
+    const SolveBuild sbuild = solve_build(threads, sh.ldsres, sh.w2, sh.ubl);
     // The LDS that `bpc` resident workgroups leave free takes the head of the refinement residual E (device_types.hpp: e_lds): its
     // scattered stores and the read-back stay on chip.  Verified against the runtime's occupancy for the enlarged allocation.
     D.e_lds = 0; D.e_off = 0;
-    if (!h->ldsres && h->nlds == 1 && !D.dual && S.tile != 1) {
-        const size_t base = (h->dyn_lds + 15) & ~(size_t)15, room = (160 * 1024) / (size_t)bpc;
-        size_t xs = room > base + 4096 + 1024 ? std::min<size_t>((size_t)NV, (room - base - 4096 - 1024) / sizeof(double)) & ~(size_t)15 : 0;
+    if (!sh.ldsres && sh.nlds == 1 && !D.dual && S.tile != 1) {
+        const size_t base = (sh.dyn_lds + 15) & ~(size_t)15, room = (160 * 1024) / (size_t)bpc;
+        size_t xs = room > base + 4096 + 1024 ? std::min<size_t>((size_t)D.N, (room - base - 4096 - 1024) / sizeof(double)) & ~(size_t)15 : 0;
         while (xs > 0) {
             int got = 0;
-            HIP_TRY_H(v_set_max_lds(h->threads, h->nlds, h->dp.idx16, base + xs * sizeof(double)));
-            HIP_TRY_H(v_occupancy(h->threads, h->nlds, h->dp.idx16, base + xs * sizeof(double), &got));
+            HIP_TRY(sbuild.set_max_lds(threads, sh.nlds, idx16, base + xs * sizeof(double)));
+            HIP_TRY(sbuild.occupancy(threads, sh.nlds, idx16, base + xs * sizeof(double), &got));
             if (got >= bpc) break;
             xs = (xs * 3 / 4) & ~(size_t)15;
         }
-        if (xs > 0) { D.e_lds = (int)xs; D.e_off = (int)(base / sizeof(double)); h->dyn_lds = base + xs * sizeof(double); }
+        if (xs > 0) { D.e_lds = (int)xs; D.e_off = (int)(base / sizeof(double)); sh.dyn_lds = base + xs * sizeof(double); }
     }
-    h->bpc = bpc;
-    const int resident = prop.multiProcessorCount * bpc;
-    h->grid = std::min(batch, resident);
-    h->order_min = prop.multiProcessorCount;
-    h->upd_grid = std::min(batch, prop.multiProcessorCount * 4);
+    sh.bpc = bpc;
+    sh.grid = std::min(batch, n_cu * bpc);
+    sh.order_min = n_cu;
+    sh.upd_grid = std::min(batch, n_cu * 4);
     {   // entry-parallel updateData: needs the A / G values and the row / column maxima in LDS and <= 8 vector entries per thread
         const size_t need = ((size_t)S.nnzA + S.nnzG + S.n + S.p + S.m + 8) * sizeof(double);
         const size_t need_max = ((size_t)S.n + S.p + S.m + 8) * sizeof(double); // the row / column maxima alone
         const bool small_vecs = S.n <= 8 * 512 && S.p <= 8 * 512 && S.m <= 16 * 512;
-        const int mode = env_int("EICOS_UPDATE_LDS", 1, 0, 2); // 0: thread-per-column kernel, 2: force the streamed-values variant
-        if (need <= 156 * 1024 && small_vecs && mode == 1) { h->upd_lds = need; h->upd_vals_lds = 1; h->upd_grid = std::min(batch, prop.multiProcessorCount); }
+        const int mode = env_knob("EICOS_UPDATE_LDS", 1, 0, 2); // 0: thread-per-column kernel, 2: force the streamed-values variant
+        if (need <= 156 * 1024 && small_vecs && mode == 1) { sh.upd_lds = need; sh.upd_vals_lds = 1; sh.upd_grid = std::min(batch, n_cu); }
         else if (need_max <= 156 * 1024 && small_vecs && mode >= 1) { // values streamed in place, maxima in LDS: as many 512-thread workgroups per CU as fit (<= 4)
-            h->upd_lds = need_max; h->upd_vals_lds = 0;
+            sh.upd_lds = need_max; sh.upd_vals_lds = 0;
             const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / (need_max + 1024)));
-            h->upd_grid = std::min(batch, prop.multiProcessorCount * per_cu);
+            sh.upd_grid = std::min(batch, n_cu * per_cu);
         }
     }
-    h->pattern_ints = pool.data.size();
-    HIP_TRY_H(hipMalloc(&h->d_pattern, pool.data.size() * sizeof(int)));
-    HIP_TRY_H(hipMemcpy(h->d_pattern, pool.data.data(), pool.data.size() * sizeof(int), hipMemcpyHostToDevice));
-    for (auto &s : slots) *s.dst = h->d_pattern + s.off;
-    D.fac_pb = D.fac_defer ? fac_pb_u : fac_pb_f; D.fac_p16 = D.fac_defer ? fac_p16_u : fac_p16_f;
-    D.fsl = reinterpret_cast<const PackedSlice *>(fsl_p); D.bsl = reinterpret_cast<const PackedSlice *>(bsl_p);
-    D.cag_sl = reinterpret_cast<const PackedSlice *>(cag_sl_p); D.rA_sl = reinterpret_cast<const PackedSlice *>(rA_sl_p);
-    D.rG_sl = reinterpret_cast<const PackedSlice *>(rG_sl_p);
-    D.fac_sl = reinterpret_cast<const PackedSlice *>(fac_sl_p);
-    {
-        std::lock_guard<std::mutex> lk(g_slot_mu);
-        std::vector<char> &used = g_slot_used[device];
-        used.resize((size_t)max_patterns(), 0);
-        for (int q = 0; q < max_patterns(); q++) if (!used[q]) { h->pslot = q; used[q] = 1; break; }
-    }
-    if (h->pslot < 0) return bail(EICOS_E_INVALID, "too many live handles on this device (64)");
-    HIP_TRY_H(upload_pattern(h->pslot, h->dp)); // (the default namespace always: updateData and the debug kernels live there)
-    if (sbuild.upload != upload_pattern) HIP_TRY_H(sbuild.upload(h->pslot, h->dp));
-    HIP_TRY_H(hipMalloc(&h->d_inst, (size_t)batch * D.inst_stride * sizeof(double)));
-    HIP_TRY_H(hipMemset(h->d_inst, 0, (size_t)batch * D.inst_stride * sizeof(double)));
-    HIP_TRY_H(hipMalloc(&h->d_work, (size_t)h->grid * D.work_stride * sizeof(double)));
-    HIP_TRY_H(hipMemset(h->d_work, 0, (size_t)h->grid * D.work_stride * sizeof(double)));
-    HIP_TRY_H(hipMalloc(&h->d_queue, (16 + (size_t)batch) * sizeof(int))); // [0] queue head, [16..] longest-first order
-    HIP_TRY_H(hipMalloc(&h->d_scratch, (size_t)h->upd_grid * (size_t)(S.n + S.p + S.m + 8) * sizeof(double)));
-    HIP_TRY_H(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-    h->stream = h->own_stream;
-    // (the event pairs of the timing rings are created on first use: next_events)
-    HIP_TRY_H(hipDeviceSynchronize());
+    return EICOS_OK;
+}
+
+// Allocation step: the only code that gives a handle device resources -- the pattern image, the descriptor slot (uploaded to the default
+// build and to the chosen one), the slabs, the instance queue, the updateData scratch and the stream.  One cleanup path:
+// eicos_batch_destroy takes a partly set-up handle.
+static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, int device, int n_cu, int profile, eicos_batch **out) {
+    std::lock_guard<std::mutex> create_lock(create_mutex(device));
+    eicos_batch *h = new eicos_batch();
+    h->batch = batch; h->device = device; h->n_cu = n_cu; h->arith_profile = profile;
+    h->threads = pl.threads; h->posB = std::move(pl.posB); h->ub_len = pl.ub_len; h->npairs = pl.an->sym.npairs;
+    h->nlds = sh.nlds; h->ldsres = sh.ldsres; h->w2 = sh.w2; h->ubl = sh.ubl; h->dyn_lds = sh.dyn_lds;
+    h->bpc = sh.bpc; h->grid = sh.grid; h->order_min = sh.order_min;
+    h->upd_grid = sh.upd_grid; h->upd_lds = sh.upd_lds; h->upd_vals_lds = sh.upd_vals_lds;
+    h->pattern_ints = pl.pool.data.size();
+    const Symbolic &S = pl.an->sym;
+    const int rc = [&]() -> int {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipMalloc(&h->d_pattern, pl.pool.data.size() * sizeof(int)));
+        HIP_TRY(hipMemcpy(h->d_pattern, pl.pool.data.data(), pl.pool.data.size() * sizeof(int), hipMemcpyHostToDevice));
+        DevPat &D = pl.dp;
+        for (auto &s : pl.slots) *s.dst = h->d_pattern + s.off;
+        D.fac_pb = D.fac_defer ? pl.fac_pb_u : pl.fac_pb_f; D.fac_p16 = D.fac_defer ? pl.fac_p16_u : pl.fac_p16_f;
+        D.fsl = reinterpret_cast<const PackedSlice *>(pl.fsl); D.bsl = reinterpret_cast<const PackedSlice *>(pl.bsl);
+        D.cag_sl = reinterpret_cast<const PackedSlice *>(pl.cag_sl); D.rA_sl = reinterpret_cast<const PackedSlice *>(pl.rA_sl);
+        D.rG_sl = reinterpret_cast<const PackedSlice *>(pl.rG_sl);
+        D.fac_sl = reinterpret_cast<const PackedSlice *>(pl.fac_sl);
+        h->dp = D;
+        {
+            std::lock_guard<std::mutex> lk(g_slot_mu);
+            std::vector<char> &used = g_slot_used[device];
+            used.resize((size_t)max_patterns(), 0);
+            for (int q = 0; q < max_patterns(); q++) if (!used[q]) { h->pslot = q; used[q] = 1; break; }
+        }
+        if (h->pslot < 0) return fail(EICOS_E_INVALID, "too many live handles on this device (64)");
+        HIP_TRY(upload_pattern(h->pslot, h->dp)); // (the default namespace always: updateData and the debug kernels live there)
+        const SolveBuild sbuild = solve_build(h->threads, h->ldsres, h->w2, h->ubl);
+        if (sbuild.upload != upload_pattern) HIP_TRY(sbuild.upload(h->pslot, h->dp));
+        HIP_TRY(hipMalloc(&h->d_inst, (size_t)batch * D.inst_stride * sizeof(double)));
+        HIP_TRY(hipMemset(h->d_inst, 0, (size_t)batch * D.inst_stride * sizeof(double)));
+        HIP_TRY(hipMalloc(&h->d_work, (size_t)h->grid * D.work_stride * sizeof(double)));
+        HIP_TRY(hipMemset(h->d_work, 0, (size_t)h->grid * D.work_stride * sizeof(double)));
+        HIP_TRY(hipMalloc(&h->d_queue, (16 + (size_t)batch) * sizeof(int))); // [0] queue head, [16..] longest-first order
+        HIP_TRY(hipMalloc(&h->d_scratch, (size_t)h->upd_grid * (size_t)(S.n + S.p + S.m + 8) * sizeof(double)));
+        HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+        h->stream = h->own_stream;
+        // (the event pairs of the timing rings are created on first use: next_events)
+        HIP_TRY(hipDeviceSynchronize());
+        return EICOS_OK;
+    }();
+    if (rc != EICOS_OK) { eicos_batch_destroy(h); return rc; }
+    h->pat = std::move(P); h->sym = std::move(pl.an->sym); h->tiles = std::move(pl.an->tiles);
     *out = h;
     return EICOS_OK;
+}
+
+
+extern "C" {
+
+const char *eicos_last_error(void) { return g_err.c_str(); }
+
+int eicos_set_arithmetic_profile(int profile) {
+    if (profile != 0 && profile != 1) return fail(EICOS_E_INVALID, "arithmetic profile must be 0 or 1");
+    g_arith_profile.store(profile);
+    return EICOS_OK;
+}
+int eicos_get_arithmetic_profile(void) { return g_arith_profile.load(); }
+
+int eicos_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+// The dense apex (symbolic.hpp) keeps an image of its block in LDS.  Whether that costs the launch a resident workgroup per CU is only
+// known from the launch shape.  So: plan and shape with the apex; plan and shape once more without it when the apex cannot run (128
+// threads without the LDS-resident build) or when the batch is one that would run one more workgroup per CU than came out, and keep
+// the shape with more workgroups per CU (MPC02 on 256 CUs: batches 513 ... 768 run three per CU without the apex, two with it:
+// launch_blocks_per_cu).  Only the kept plan is allocated.
+int eicos_batch_create(int n, int m, int p, int l, int ncones, const int *q,
+                       const int *Gjc, const int *Gir, const int *Ajc, const int *Air,
+                       int batch, int device, eicos_batch **out) {
+    if (!out) return fail(EICOS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    ProblemPattern P;
+    int rc = take_pattern(n, m, p, l, ncones, q, Gjc, Gir, Ajc, Air, batch, &device, P);
+    if (rc != EICOS_OK) return rc;
+    const int profile = g_arith_profile.load();
+    int n_cu = 256;
+    { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess) n_cu = pr.multiProcessorCount; }
+    Analyses A;
+    if ((rc = analyse(P, batch, n_cu, profile, A)) != EICOS_OK) return rc;
+    Plan with, without;
+    Shape sw, so;
+    if ((rc = build_plan(P, A, A.apex, batch, n_cu, profile, with)) != EICOS_OK) return rc;
+    if ((rc = launch_shape(with, batch, device, sw)) != EICOS_OK) return rc;
+    const bool try_without = with.apex && (sw.apex_unplaced || launch_blocks_per_cu(batch, n_cu, sw.bpc + 1, with.threads) > sw.bpc);
+    if (!try_without) return allocate(std::move(P), with, sw, batch, device, n_cu, profile, out);
+    rc = build_plan(P, A, false, batch, n_cu, profile, without);
+    if (rc == EICOS_OK) rc = launch_shape(without, batch, device, so);
+    if (sw.apex_unplaced) return rc != EICOS_OK ? rc : allocate(std::move(P), without, so, batch, device, n_cu, profile, out);
+    const bool take_without = rc == EICOS_OK && so.bpc > sw.bpc; // (a plan without the apex that fails keeps the one with it)
+    return take_without ? allocate(std::move(P), without, so, batch, device, n_cu, profile, out)
+                        : allocate(std::move(P), with, sw, batch, device, n_cu, profile, out);
 }
 
 // ---- single-instance surface: a batch of one (reference include/eicos.hpp:151-163, test/ecos.h:11-34)
@@ -1656,6 +1776,141 @@ int eicos_debug_pattern(eicos_batch *h, int *perm, int *Lp, int *Li) {
 }
 
 
+} // extern "C"
+
+// ---- host-only self checks (no GPU needed): the pieces the scalar and the tile / hybrid checks share ----
+namespace {
+
+struct CheckRng { // the checks' random stream: the values of K first, then the right-hand side
+    unsigned long long st;
+    explicit CheckRng(unsigned seed) : st(seed * 2654435761ull + 12345) {}
+    double operator()() { st = st * 6364136223846793005ull + 1442695040888963407ull; return ((st >> 11) & 0xFFFFFFFFFFFFull) / (double)(1ull << 48); }
+};
+
+// Random quasi-definite values on the KKT pattern (Kv per entry of K) and their scatter into P K P' (Lv per entry of L, Dv per
+// diagonal).  false: an entry of K has no place in L.
+bool random_kkt(const Symbolic &S, CheckRng &rnd, std::vector<double> &Kv, std::vector<double> &Lv, std::vector<double> &Dv) {
+    Kv.assign(S.nnzK, 0.0); Lv.assign(S.nnzL, 0.0); Dv.assign(S.N, 0.0);
+    for (int e = 0; e < S.nnzK; e++) {
+        const int r = S.K_row[e], c = S.K_col[e];
+        if (r == c) Kv[e] = (r < S.n ? 1.0 : -1.0) * (4.0 + rnd());
+        else Kv[e] = 0.2 * (rnd() - 0.5);
+    }
+    for (int e = 0; e < S.nnzK; e++) {
+        const int a = S.iperm[S.K_row[e]], b = S.iperm[S.K_col[e]];
+        if (a == b) Dv[a] = Kv[e];
+        else {
+            const int i = std::max(a, b), j = std::min(a, b);
+            auto it = std::lower_bound(S.Li.begin() + S.Lp[j], S.Li.begin() + S.Lp[j + 1], i);
+            if (it == S.Li.begin() + S.Lp[j + 1] || *it != i) return false;
+            Lv[it - S.Li.begin()] = Kv[e];
+        }
+    }
+    return true;
+}
+
+// || K x - b ||_inf / || b ||_inf
+double kkt_residual(const Symbolic &S, const std::vector<double> &Kv, const std::vector<double> &rhs, const std::vector<double> &x) {
+    std::vector<double> r(rhs);
+    for (int e = 0; e < S.nnzK; e++) {
+        const int a = S.K_row[e], b = S.K_col[e];
+        r[a] -= Kv[e] * x[b];
+        if (a != b) r[b] -= Kv[e] * x[a];
+    }
+    double nr = 0, nb = 0;
+    for (int i = 0; i < S.N; i++) { nr = std::max(nr, std::fabs(r[i])); nb = std::max(nb, std::fabs(rhs[i])); }
+    return S.N ? nr / nb : 0.0;
+}
+
+// The sliced-ELL factor program of workgroup size T, lane by lane as stage_factor walks it: one level at a time, phase A (U into UB,
+// D / invD), then phase B (L = U / D[col] into UF).  Targets in columns >= n0 -- a hybrid's top block -- go to the tile image `img` instead
+// (the plan step's destination codes); n0 = N: none.  Returns what is wrong with a slice that the kernel could not run, else nullptr.
+const char *walk_factor_program(const Symbolic &S, const FactorPlan &px, const TriPlan &pf, const TriPlan &pb, int T,
+                                const std::vector<double> &Lv, const std::vector<double> &Dv, int n0, const TilePlan *TP, std::vector<double> *img,
+                                std::vector<double> &UF, std::vector<double> &UB, std::vector<double> &D, std::vector<double> &invD) {
+    const int N = S.N;
+    std::vector<int> colof(S.nnzL);
+    for (int j = 0; j < N; j++) for (int e = S.Lp[j]; e < S.Lp[j + 1]; e++) colof[e] = j;
+    size_t s0 = 0;
+    std::vector<double> carry;
+    while (s0 < px.sl.size()) {
+        size_t s1 = s0 + 1;
+        while (s1 < px.sl.size() && !(px.sl[s1].newlev & 1)) s1++;
+        for (size_t si = s0; si < s1; si++) {
+            const SliceMeta &m = px.sl[si];
+            const int g = 1 << m.lg, lanes = m.cnt * g;
+            if (lanes > T) return "factor slice wider than the workgroup";
+            if (m.K > ELL_KMAX) return "factor slice deeper than the prefetch depth";
+            if (!m.cont) carry.assign(m.cnt, 0.0);
+            for (int r = 0; r < m.cnt; r++) {
+                double acc = carry[r];
+                for (int q = 0; q < g; q++)
+                    for (int kk = 0; kk < m.K; kk++) { const int slot = m.off + kk * lanes + r * g + q; acc += UB[px.pa[slot]] * UF[px.pb[slot]]; }
+                if (m.more) { carry[r] = acc; continue; } // sub-slices of one set of targets accumulate
+                const int tgt = px.target[m.row0 + r];
+                if (tgt < N) {
+                    if (tgt >= n0) (*img)[TP->D_img[tgt]] = Dv[tgt] - acc;
+                    else { D[tgt] = Dv[tgt] - acc; invD[tgt] = 1.0 / D[tgt]; }
+                } else {
+                    const int e = tgt - N;
+                    if (colof[e] >= n0) (*img)[TP->Le_img[e]] = Lv[e] - acc;
+                    else UB[pb.pos[e]] = Lv[e] - acc;
+                }
+            }
+        }
+        for (size_t si = s0; si < s1; si++)
+            for (int r = 0; r < px.sl[si].cnt && !px.sl[si].more; r++) {
+                const int tgt = px.target[px.sl[si].row0 + r];
+                if (tgt >= N && colof[tgt - N] < n0) { const int e = tgt - N; UF[pf.pos[e]] = UB[pb.pos[e]] * invD[colof[e]]; }
+            }
+        s0 = s1;
+    }
+    return nullptr;
+}
+
+// One sweep of a sliced-ELL triangular plan over ws, slice by slice as tri_sweep runs it: L y = b forward, x = (y - U' x) / D backward.
+// Returns what is wrong with a slice that the kernel could not run, else nullptr.
+const char *ell_sweep(const TriPlan &pl, const std::vector<double> &val, bool fwd, int T, std::vector<double> &ws, const std::vector<double> &invD) {
+    for (const SliceMeta &m : pl.sl) {
+        const int g = 1 << m.lg, lanes = m.cnt * g;
+        if (lanes > T) return "slice wider than the workgroup";
+        if (m.K > ELL_KMAX) return "slice deeper than the prefetch depth";
+        std::vector<double> acc(m.cnt, 0.0);
+        for (int t = 0; t < lanes; t++)
+            for (int kk = 0; kk < m.K; kk++) { const int slot = m.off + kk * lanes + t; acc[t / g] += val[slot] * ws[pl.idx[slot]]; }
+        for (int r = 0; r < m.cnt; r++) {
+            const int i = m.row0 + r;
+            ws[i] = (fwd || m.more) ? ws[i] - acc[r] : (ws[i] - acc[r]) * invD[i];
+        }
+    }
+    return nullptr;
+}
+
+// developer aid (EICOS_PLAN_STATS): shape of the three programs for workgroup size T
+void print_plan_stats(const Symbolic &S, int T, const TriPlan &pf, const TriPlan &pb, const FactorPlan &px) {
+    auto stat = [&](const char *nm, const std::vector<SliceMeta> &sl, int slots) {
+        int lev = 0, kmax = 0; long lanes = 0, kl = 0;
+        for (const SliceMeta &m : sl) { lev += m.newlev & 1; kmax = std::max(kmax, m.K); lanes += (long)m.cnt << m.lg; kl += (long)m.K; }
+        fprintf(stderr, "[plan T=%d] %-8s slices %zu levels %d slots %d sum(K) %ld maxK %d active-lane slices %.2f\n", T, nm,
+                sl.size(), lev, slots, kl, kmax, (double)lanes / T);
+    };
+    stat("forward", pf.sl, pf.slots); stat("backward", pb.sl, pb.slots); stat("factor", px.sl, px.slots);
+    fprintf(stderr, "[plan T=%d] factor targets %zu pairs %lld\n", T, px.target.size(), (long long)S.tp.back());
+    if (T == 512 || (T == 256 && getenv("EICOS_PLAN_STATS")[0] == '2')) {
+        fprintf(stderr, "[plan] level sizes:");
+        for (int v = 0; v < S.nlev; v++) fprintf(stderr, " %d", S.lev_ptr[v + 1] - S.lev_ptr[v]);
+        fprintf(stderr, "\n[plan T=%d] backward slices (lanes x K):", T);
+        for (const SliceMeta &m : pb.sl) fprintf(stderr, " %d%sx%d", m.cnt << m.lg, (m.newlev & 1) ? "*" : "", m.K);
+        fprintf(stderr, "\n[plan T=%d] forward slices (lanes x K):", T);
+        for (const SliceMeta &m : pf.sl) fprintf(stderr, " %d%sx%d", m.cnt << m.lg, (m.newlev & 1) ? "*" : "", m.K);
+        fprintf(stderr, "\n");
+    }
+}
+
+} // namespace
+
+extern "C" {
+
 // Host-only self check of the symbolic analysis (no GPU needed): random quasi-definite values
 // on the KKT pattern, the factor program and the level-scheduled gather solves executed
 // sequentially exactly as the kernels index them, then || K x - b ||_inf / || b ||_inf.
@@ -1663,120 +1918,43 @@ double eicos_debug_host_check(int n, int m, int p, int ncones, const int *q, con
                               const int *Ajc, const int *Air, unsigned seed, int order_mode, int *stats /*[8] or NULL*/) {
     try {
         ProblemPattern P;
-        P.n = n; P.m = m; P.p = p; P.nc = ncones; P.q.assign(q, q + ncones);
-        if (Gjc && Gir) { P.Gjc.assign(Gjc, Gjc + n + 1); P.Gir.assign(Gir, Gir + Gjc[n]); } else { P.Gjc.assign(n + 1, 0); P.m = 0; P.nc = 0; P.q.clear(); }
-        if (Ajc && Air) { P.Ajc.assign(Ajc, Ajc + n + 1); P.Air.assign(Air, Air + Ajc[n]); } else { P.Ajc.assign(n + 1, 0); P.p = 0; }
+        if (take_pattern(n, m, p, -1, ncones, q, Gjc, Gir, Ajc, Air, 1, nullptr, P) != EICOS_OK) return -2.0;
         Symbolic S = analyze(P, order_mode, 0); // the scalar programs (the tile and hybrid paths have their own checks)
         const int N = S.N;
         if (stats) { stats[0] = N; stats[1] = S.nnzK; stats[2] = S.nnzL; stats[3] = S.nlev; stats[4] = (int)std::min<int64_t>(S.npairs, 2147483647); stats[5] = S.order_mode; stats[6] = S.max_row_len; stats[7] = S.max_col_len; }
         // permutation sanity
         std::vector<char> seen(N, 0);
         for (int k = 0; k < N; k++) { if (S.perm[k] < 0 || S.perm[k] >= N || seen[S.perm[k]]) return -1.0; seen[S.perm[k]] = 1; }
-        unsigned long long st = seed * 2654435761ull + 12345;
-        auto rnd = [&]() { st = st * 6364136223846793005ull + 1442695040888963407ull; return ((st >> 11) & 0xFFFFFFFFFFFFull) / (double)(1ull << 48); };
-        std::vector<double> Kv(S.nnzK);
-        for (int e = 0; e < S.nnzK; e++) {
-            const int r = S.K_row[e], c = S.K_col[e];
-            if (r == c) Kv[e] = (r < S.n ? 1.0 : -1.0) * (4.0 + rnd());
-            else Kv[e] = 0.2 * (rnd() - 0.5);
-        }
-        // values per L entry / diagonal in permuted order
-        std::vector<double> U(S.nnzL, 0.0), Ur(S.nnzL, 0.0), D(N, 0.0), invD(N, 0.0), Lv(S.nnzL, 0.0), Dv(N, 0.0);
-        for (int e = 0; e < S.nnzK; e++) {
-            const int a = S.iperm[S.K_row[e]], b = S.iperm[S.K_col[e]];
-            if (a == b) Dv[a] = Kv[e];
-            else {
-                const int i = std::max(a, b), j = std::min(a, b);
-                auto it = std::lower_bound(S.Li.begin() + S.Lp[j], S.Li.begin() + S.Lp[j + 1], i);
-                Lv[it - S.Li.begin()] = Kv[e];
-            }
-        }
+        CheckRng rnd(seed);
+        std::vector<double> Kv, Lv, Dv;
+        if (!random_kkt(S, rnd, Kv, Lv, Dv)) return -4.0;
+        // reference factorisation: the symbolic factor program, task by task
+        std::vector<double> U(S.nnzL, 0.0), D(N, 0.0), invD(N, 0.0);
         for (int v = 0; v < S.nlev; v++)
             for (int t = S.ftask_ptr[v]; t < S.ftask_ptr[v + 1]; t++) {
                 const int tgt = S.ftask[t];
                 double s = 0;
                 for (int64_t k = S.tp[tgt]; k < S.tp[tgt + 1]; k++) s += U[S.pa[k]] * U[S.pb[k]] * invD[S.pk[k]];
                 if (tgt < N) { D[tgt] = Dv[tgt] - s; invD[tgt] = 1.0 / D[tgt]; }
-                else { const int e = tgt - N; U[e] = Lv[e] - s; Ur[S.Cpos[e]] = U[e]; }
+                else { const int e = tgt - N; U[e] = Lv[e] - s; }
             }
         std::vector<double> rhs(N), x(N);
         for (int i = 0; i < N; i++) rhs[i] = rnd() - 0.5;
-        // the two sweeps exactly as the kernel walks its sliced-ELL plans (lane by lane)
+        // the factor program and the two sweeps exactly as the kernel walks its sliced-ELL plans (lane by lane)
         double plan_err = 0;
         for (int T : {128, 256, 512}) {
             TriPlan pf = build_tri_plan(S, T, true), pb = build_tri_plan(S, T, false);
             std::vector<double> UF(pf.ulen, 0.0), UB(pb.ulen, 0.0), ws(scalar_npad(N), 0.0);
-            { // numeric factorisation through the sliced-ELL factor plan, lane by lane as the kernel does it
+            {
                 FactorPlan px = build_factor_plan(S, T, pb.pos, pb.slots, pf.pos, pf.slots);
-                if (getenv("EICOS_PLAN_STATS")) { // developer aid: shape of the three programs for this workgroup size
-                    auto stat = [&](const char *nm, const std::vector<SliceMeta> &sl, int slots) {
-                        int lev = 0, kmax = 0; long lanes = 0, kl = 0;
-                        for (const SliceMeta &m : sl) { lev += m.newlev & 1; kmax = std::max(kmax, m.K); lanes += (long)m.cnt << m.lg; kl += (long)m.K; }
-                        fprintf(stderr, "[plan T=%d] %-8s slices %zu levels %d slots %d sum(K) %ld maxK %d active-lane slices %.2f\n", T, nm,
-                                sl.size(), lev, slots, kl, kmax, (double)lanes / T);
-                    };
-                    stat("forward", pf.sl, pf.slots); stat("backward", pb.sl, pb.slots); stat("factor", px.sl, px.slots);
-                    fprintf(stderr, "[plan T=%d] factor targets %zu pairs %lld\n", T, px.target.size(), (long long)S.tp.back());
-                    if (T == 512 || (T == 256 && getenv("EICOS_PLAN_STATS")[0] == '2')) {
-                        fprintf(stderr, "[plan] level sizes:");
-                        for (int v = 0; v < S.nlev; v++) fprintf(stderr, " %d", S.lev_ptr[v + 1] - S.lev_ptr[v]);
-                        fprintf(stderr, "\n[plan T=%d] backward slices (lanes x K):", T);
-                        for (const SliceMeta &m : pb.sl) fprintf(stderr, " %d%sx%d", m.cnt << m.lg, (m.newlev & 1) ? "*" : "", m.K);
-                        fprintf(stderr, "\n[plan T=%d] forward slices (lanes x K):", T);
-                        for (const SliceMeta &m : pf.sl) fprintf(stderr, " %d%sx%d", m.cnt << m.lg, (m.newlev & 1) ? "*" : "", m.K);
-                        fprintf(stderr, "\n");
-                    }
-                }
+                if (getenv("EICOS_PLAN_STATS")) print_plan_stats(S, T, pf, pb, px);
                 std::vector<double> D2(N, 0.0), iD2(N, 0.0);
-                std::vector<int> colof(S.nnzL);
-                for (int j = 0; j < N; j++) for (int e = S.Lp[j]; e < S.Lp[j + 1]; e++) colof[e] = j;
-                size_t s0 = 0;
-                std::vector<double> carry;
-                while (s0 < px.sl.size()) { // one level at a time: phase A (U, D), then phase B (L = U / D[col])
-                    size_t s1 = s0 + 1;
-                    while (s1 < px.sl.size() && !(px.sl[s1].newlev & 1)) s1++;
-                    for (size_t si = s0; si < s1; si++) {
-                        const SliceMeta &m = px.sl[si];
-                        const int g = 1 << m.lg, lanes = m.cnt * g;
-                        if (lanes > T) throw std::logic_error("factor slice wider than the workgroup");
-                        if (m.K > ELL_KMAX) throw std::logic_error("factor slice deeper than the prefetch depth");
-                        if (!m.cont) carry.assign(m.cnt, 0.0);
-                        for (int r = 0; r < m.cnt; r++) {
-                            double acc = carry[r];
-                            for (int q = 0; q < g; q++)
-                                for (int kk = 0; kk < m.K; kk++) { const int slot = m.off + kk * lanes + r * g + q; acc += UB[px.pa[slot]] * UF[px.pb[slot]]; }
-                            if (m.more) { carry[r] = acc; continue; } // sub-slices of one set of targets accumulate
-                            const int tgt = px.target[m.row0 + r];
-                            if (tgt < N) { D2[tgt] = Dv[tgt] - acc; iD2[tgt] = 1.0 / D2[tgt]; }
-                            else { const int e = tgt - N; UB[pb.pos[e]] = Lv[e] - acc; }
-                        }
-                    }
-                    for (size_t si = s0; si < s1; si++)
-                        for (int r = 0; r < px.sl[si].cnt && !px.sl[si].more; r++) {
-                            const int tgt = px.target[px.sl[si].row0 + r];
-                            if (tgt >= N) { const int e = tgt - N; UF[pf.pos[e]] = UB[pb.pos[e]] * iD2[colof[e]]; }
-                        }
-                    s0 = s1;
-                }
+                if (const char *bad = walk_factor_program(S, px, pf, pb, T, Lv, Dv, N, nullptr, nullptr, UF, UB, D2, iD2)) throw std::logic_error(bad);
                 for (int e = 0; e < S.nnzL; e++) plan_err = std::max(plan_err, std::fabs(UB[pb.pos[e]] - U[e]) / (1.0 + std::fabs(U[e])));
                 for (int jn = 0; jn < N; jn++) plan_err = std::max(plan_err, std::fabs(D2[jn] - D[jn]) / (1.0 + std::fabs(D[jn])));
             }
             for (int i = 0; i < N; i++) ws[i] = rhs[S.perm[i]];
-            auto sweep = [&](const TriPlan &pl, const std::vector<double> &val, bool fwd) {
-                for (const SliceMeta &m : pl.sl) {
-                    const int g = 1 << m.lg, lanes = m.cnt * g;
-                    if (lanes > T) throw std::logic_error("slice wider than the workgroup");
-                    std::vector<double> acc(m.cnt, 0.0);
-                    for (int t = 0; t < lanes; t++)
-                        for (int kk = 0; kk < m.K; kk++) { const int slot = m.off + kk * lanes + t; acc[t / g] += val[slot] * ws[pl.idx[slot]]; }
-                    if (m.K > ELL_KMAX) throw std::logic_error("slice deeper than the prefetch depth");
-                    for (int r = 0; r < m.cnt; r++) {
-                        const int i = m.row0 + r;
-                        ws[i] = (fwd || m.more) ? ws[i] - acc[r] : (ws[i] - acc[r]) * invD[i]; // L y = b ; x = (y - U' x) / D
-                    }
-                }
-            };
-            sweep(pf, UF, true);
+            if (const char *bad = ell_sweep(pf, UF, true, T, ws, invD)) throw std::logic_error(bad);
             if (S.apex0 >= 0) { // the dense apex as apex_solve walks it: a column of the block per forward step, a row per backward step
                 const int n0 = S.apex0, na = N - n0;
                 for (int q_ = 0; q_ < pf.split_n; q_++) { ws[pf.split_row] += ws[pf.split_slot0 + q_]; ws[pf.split_slot0 + q_] = 0.; } // the parts of the split row
@@ -1787,22 +1965,14 @@ double eicos_debug_host_check(int n, int m, int p, int ncones, const int *q, con
                     for (int k = 0; k < i; k++) ws[n0 + k] -= UB[pb.apex_base + apex_img_at(i, k)] * ws[n0 + i];
                 }
             }
-            sweep(pb, UB, false);
+            if (const char *bad = ell_sweep(pb, UB, false, T, ws, invD)) throw std::logic_error(bad);
             std::vector<double> xt(N);
             for (int j = 0; j < N; j++) xt[S.perm[j]] = ws[j];
             if (T == 128) x = xt;
             for (int j = 0; j < N; j++) plan_err = std::max(plan_err, std::fabs(xt[j] - x[j]));
         }
         if (plan_err > 1e-9) return -3.0;
-        std::vector<double> r(rhs);
-        for (int e = 0; e < S.nnzK; e++) {
-            const int a = S.K_row[e], b = S.K_col[e];
-            r[a] -= Kv[e] * x[b];
-            if (a != b) r[b] -= Kv[e] * x[a];
-        }
-        double nr = 0, nb = 0;
-        for (int i = 0; i < N; i++) { nr = std::max(nr, std::fabs(r[i])); nb = std::max(nb, std::fabs(rhs[i])); }
-        return N ? nr / nb : 0.0;
+        return kkt_residual(S, Kv, rhs, x);
     } catch (const std::exception &e) { g_err = e.what(); return -2.0; }
 }
 
@@ -1815,9 +1985,7 @@ static double host_check_tiles_impl(int n, int m, int p, int ncones, const int *
                                     const int *Ajc, const int *Air, unsigned seed, int order_mode, int *stats, int mode) {
     try {
         ProblemPattern P;
-        P.n = n; P.m = m; P.p = p; P.nc = ncones; P.q.assign(q, q + ncones);
-        if (Gjc && Gir) { P.Gjc.assign(Gjc, Gjc + n + 1); P.Gir.assign(Gir, Gir + Gjc[n]); } else { P.Gjc.assign(n + 1, 0); P.m = 0; P.nc = 0; P.q.clear(); }
-        if (Ajc && Air) { P.Ajc.assign(Ajc, Ajc + n + 1); P.Air.assign(Air, Air + Ajc[n]); } else { P.Ajc.assign(n + 1, 0); P.p = 0; }
+        if (take_pattern(n, m, p, -1, ncones, q, Gjc, Gir, Ajc, Air, 1, nullptr, P) != EICOS_OK) return -2.0;
         Symbolic S = analyze(P, order_mode, mode);
         if (S.tile != mode) return -10.0; // (hybrid requested, but the schedule has no tail worth handing to the tile path)
         TilePlan TP = build_tile_plan(S);
@@ -1825,26 +1993,9 @@ static double host_check_tiles_impl(int n, int m, int p, int ncones, const int *
         if (getenv("EICOS_PLAN_STATS")) (void)build_tile_sweeps(TP, 8, TILE_PF);
         const int N = S.N, nb = TP.nb, nt = TP.nt, N16 = TP.N16;
         if (stats) { stats[0] = N; stats[1] = S.nnzK; stats[2] = S.nnzL; stats[3] = TP.nblev; stats[4] = (int)std::min<int64_t>(TP.npairs, 2147483647); stats[5] = S.order_mode; stats[6] = nb; stats[7] = nt; }
-        unsigned long long st = seed * 2654435761ull + 12345;
-        auto rnd = [&]() { st = st * 6364136223846793005ull + 1442695040888963407ull; return ((st >> 11) & 0xFFFFFFFFFFFFull) / (double)(1ull << 48); };
-        std::vector<double> Kv(S.nnzK);
-        for (int e = 0; e < S.nnzK; e++) {
-            const int r = S.K_row[e], c = S.K_col[e];
-            if (r == c) Kv[e] = (r < S.n ? 1.0 : -1.0) * (4.0 + rnd());
-            else Kv[e] = 0.2 * (rnd() - 0.5);
-        }
-        // values of P K P' per entry of L / per diagonal
-        std::vector<double> Lv(S.nnzL, 0.0), Dv(N, 0.0);
-        for (int e = 0; e < S.nnzK; e++) {
-            const int a = S.iperm[S.K_row[e]], b = S.iperm[S.K_col[e]];
-            if (a == b) Dv[a] = Kv[e];
-            else {
-                const int i = std::max(a, b), j = std::min(a, b);
-                auto it = std::lower_bound(S.Li.begin() + S.Lp[j], S.Li.begin() + S.Lp[j + 1], i);
-                if (it == S.Li.begin() + S.Lp[j + 1] || *it != i) return -4.0;
-                Lv[it - S.Li.begin()] = Kv[e];
-            }
-        }
+        CheckRng rnd(seed);
+        std::vector<double> Kv, Lv, Dv; // values of P K P' per entry of L / per diagonal
+        if (!random_kkt(S, rnd, Kv, Lv, Dv)) return -4.0;
         // the tile image: pure tile mode -- P K P' itself (what the solve prologue scatters from the instance slab);
         // hybrid -- written by the scalar factor program below (K minus the updates from the columns under the top block)
         std::vector<double> img((size_t)(nb + nt) * 256, 0.0);
@@ -1857,46 +2008,11 @@ static double host_check_tiles_impl(int n, int m, int p, int ncones, const int *
         if (mode == 1) {
             for (int j = 0; j < N; j++) img[TP.D_img[j]] = Dv[j];
             for (int e = 0; e < S.nnzL; e++) img[TP.Le_img[e]] = Lv[e];
-        } else {
-            // ---- hybrid: the scalar factor program, lane by lane as stage_factor walks it (api.cpp's destination codes) ----
+        } else { // hybrid: the scalar factor program below the cut, its top-block targets into the image
             pf = build_tri_plan(S, TW, true); pb = build_tri_plan(S, TW, false);
             FactorPlan px = build_factor_plan(S, TW, pb.pos, pb.slots, pf.pos, pf.slots);
             UF.assign(pf.slots + 1, 0.0); UB.assign(pb.slots + 1, 0.0);
-            std::vector<int> colof(S.nnzL);
-            for (int j = 0; j < N; j++) for (int e = S.Lp[j]; e < S.Lp[j + 1]; e++) colof[e] = j;
-            size_t s0 = 0;
-            std::vector<double> carry;
-            while (s0 < px.sl.size()) {
-                size_t s1 = s0 + 1;
-                while (s1 < px.sl.size() && !(px.sl[s1].newlev & 1)) s1++;
-                for (size_t si = s0; si < s1; si++) {
-                    const SliceMeta &sm = px.sl[si];
-                    const int g = 1 << sm.lg, lanes = sm.cnt * g;
-                    if (lanes > TW || sm.K > ELL_KMAX) return -6.0;
-                    if (!sm.cont) carry.assign(sm.cnt, 0.0);
-                    for (int r = 0; r < sm.cnt; r++) {
-                        double acc = carry[r];
-                        for (int qq = 0; qq < g; qq++)
-                            for (int kk = 0; kk < sm.K; kk++) { const int slot = sm.off + kk * lanes + r * g + qq; acc += UB[px.pa[slot]] * UF[px.pb[slot]]; }
-                        if (sm.more) { carry[r] = acc; continue; }
-                        const int tgt = px.target[sm.row0 + r];
-                        if (tgt < N) {
-                            if (tgt >= n0) img[TP.D_img[tgt]] = Dv[tgt] - acc;                         // top block: image
-                            else { Dall[tgt] = Dv[tgt] - acc; invDall[tgt] = 1.0 / Dall[tgt]; }
-                        } else {
-                            const int e = tgt - N;
-                            if (colof[e] >= n0) img[TP.Le_img[e]] = Lv[e] - acc;                       // top block: image
-                            else UB[pb.pos[e]] = Lv[e] - acc;
-                        }
-                    }
-                }
-                for (size_t si = s0; si < s1; si++)
-                    for (int r = 0; r < px.sl[si].cnt && !px.sl[si].more; r++) {
-                        const int tgt = px.target[px.sl[si].row0 + r];
-                        if (tgt >= N && colof[tgt - N] < n0) { const int e = tgt - N; UF[pf.pos[e]] = UB[pb.pos[e]] * invDall[colof[e]]; }
-                    }
-                s0 = s1;
-            }
+            if (walk_factor_program(S, px, pf, pb, TW, Lv, Dv, n0, &TP, &img, UF, UB, Dall, invDall)) return -6.0;
         }
         for (int v = 0; v < TP.nblev; v++) {
             for (int qi = TP.tgt_lev_ptr[v]; qi < TP.tgt_lev_ptr[v + 1]; qi++) { // phase 1
@@ -1936,19 +2052,7 @@ static double host_check_tiles_impl(int n, int m, int p, int ncones, const int *
         for (int i = 0; i < N; i++) rhs[i] = rnd() - 0.5;
         for (int i = 0; i < N; i++) wsall[TP.slot[i]] = rhs[S.perm[i]];
         double *ws = wsall.data() + n0; // block-relative view
-        auto ell_sweep = [&](const TriPlan &pl, const std::vector<double> &val, bool fwd) { // the scalar sweeps, slice by slice
-            for (const SliceMeta &sm : pl.sl) {
-                const int g = 1 << sm.lg, lanes = sm.cnt * g;
-                std::vector<double> acc(sm.cnt, 0.0);
-                for (int t = 0; t < lanes; t++)
-                    for (int kk = 0; kk < sm.K; kk++) { const int slot = sm.off + kk * lanes + t; acc[t / g] += val[slot] * wsall[pl.idx[slot]]; }
-                for (int r = 0; r < sm.cnt; r++) {
-                    const int i = sm.row0 + r;
-                    wsall[i] = (fwd || sm.more) ? wsall[i] - acc[r] : (wsall[i] - acc[r]) * invDall[i];
-                }
-            }
-        };
-        if (mode == 2) ell_sweep(pf, UF, true); // levels under the top block, then its rows against them (the plan's extra level)
+        if (mode == 2 && ell_sweep(pf, UF, true, TW, wsall, invDall)) return -6.0; // levels under the top block, then its rows against them (the plan's extra level)
         auto block = [&](int B, const std::vector<int> &tiles_of, int e0, int e1, const std::vector<double> &val, const std::vector<double> &dia, bool fwd) {
             double acc[16] = {0};
             for (int e = e0; e < e1; e++) {
@@ -1964,19 +2068,11 @@ static double host_check_tiles_impl(int n, int m, int p, int ncones, const int *
         };
         for (int v = 0; v < TP.nblev; v++) for (int B = TP.blev_ptr[v]; B < TP.blev_ptr[v + 1]; B++) block(B, TP.tr_tile, TP.tr_ptr[B], TP.tr_ptr[B + 1], LC, DC, true);
         for (int v = TP.nblev - 1; v >= 0; v--) for (int B = TP.blev_ptr[v]; B < TP.blev_ptr[v + 1]; B++) block(B, TP.tr_tile, TP.tc_ptr[B], TP.tc_ptr[B + 1], LR, DR, false);
-        if (mode == 2) ell_sweep(pb, UB, false);
+        if (mode == 2 && ell_sweep(pb, UB, false, TW, wsall, invDall)) return -6.0;
         std::vector<double> x(N);
         for (int j = 0; j < N; j++) x[S.perm[j]] = wsall[TP.slot[j]];
         for (int s_ = 0; s_ < N16; s_++) { bool real = false; for (int j = 0; j < N && !real; j++) real = TP.slot[j] == s_; if (!real && wsall[s_] != 0.0) return -5.0; if (N > 4000) break; } // padding slots stay 0
-        std::vector<double> r(rhs);
-        for (int e = 0; e < S.nnzK; e++) {
-            const int a = S.K_row[e], b = S.K_col[e];
-            r[a] -= Kv[e] * x[b];
-            if (a != b) r[b] -= Kv[e] * x[a];
-        }
-        double nr = 0, nbn = 0;
-        for (int i = 0; i < N; i++) { nr = std::max(nr, std::fabs(r[i])); nbn = std::max(nbn, std::fabs(rhs[i])); }
-        return N ? nr / nbn : 0.0;
+        return kkt_residual(S, Kv, rhs, x);
     } catch (const std::exception &e) { g_err = e.what(); return -2.0; }
 }
 
@@ -1987,9 +2083,7 @@ int eicos_debug_host_tile_order(int n, int m, int p, int ncones, const int *q, c
                                 const int *Ajc, const int *Air, int order_mode, int *perm, int *blk_ptr, int *stats, int *Lp, int *Li) {
     try {
         ProblemPattern P;
-        P.n = n; P.m = m; P.p = p; P.nc = ncones; P.q.assign(q, q + ncones);
-        if (Gjc && Gir) { P.Gjc.assign(Gjc, Gjc + n + 1); P.Gir.assign(Gir, Gir + Gjc[n]); } else { P.Gjc.assign(n + 1, 0); P.m = 0; P.nc = 0; P.q.clear(); }
-        if (Ajc && Air) { P.Ajc.assign(Ajc, Ajc + n + 1); P.Air.assign(Air, Air + Ajc[n]); } else { P.Ajc.assign(n + 1, 0); P.p = 0; }
+        if (take_pattern(n, m, p, -1, ncones, q, Gjc, Gir, Ajc, Air, 1, nullptr, P) != EICOS_OK) return -2;
         Symbolic S = analyze(P, order_mode, 1);
         TilePlan TP = build_tile_plan(S);
         if (perm) std::copy(S.perm.begin(), S.perm.end(), perm);

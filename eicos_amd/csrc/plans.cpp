@@ -22,7 +22,7 @@ static void push_subslices(std::vector<SliceMeta> &sl, SliceMeta m) {
     }
 }
 
-TriPlan build_tri_plan(const Symbolic &S, int T, bool forward, bool allow_solo) {
+TriPlan build_tri_plan(const Symbolic &S, int T, bool forward, bool allow_solo, bool with_apex) {
     TriPlan pl;
     pl.pos.assign(S.nnzL, 0);
     const std::vector<int> &ptr = forward ? S.Rp : S.Lp;
@@ -30,7 +30,7 @@ TriPlan build_tri_plan(const Symbolic &S, int T, bool forward, bool allow_solo) 
     // hybrid: the sweeps cover the levels below the cut; a row of the top block keeps only its entries in columns < n0
     // (a prefix: the columns of a row ascend), a column below the cut keeps all its rows
     // (dense apex, Symbolic::apex0: the same cut on the scalar path -- the block above it is swept by apex_solve instead of the tile sweeps)
-    const bool apex = S.tile == 0 && S.apex0 >= 0;
+    const bool apex = with_apex && S.tile == 0 && S.apex0 >= 0;
     const bool hyb = S.tile == 2 || apex;
     const int cut_n0 = apex ? S.apex0 : S.n0;
     const int nlev = hyb ? (apex ? S.apex_lev : S.lev_cut) : S.nlev;

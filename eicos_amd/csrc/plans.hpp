@@ -36,8 +36,9 @@ struct TriPlan {
 // length of the KKT-space vectors of the scalar path on the device (>= N + 1: slot N is the always-zero target of ELL padding)
 inline int scalar_npad(int N) { return (N + 1 + 15) & ~15; }
 
-// T = workgroup size the plan is laid out for.
-TriPlan build_tri_plan(const Symbolic &S, int T, bool forward, bool allow_solo = true);
+// T = workgroup size the plan is laid out for.  with_apex = false: the plan of the same analysis without its dense apex (a handle that
+// does not carry it).
+TriPlan build_tri_plan(const Symbolic &S, int T, bool forward, bool allow_solo = true, bool with_apex = true);
 
 // Sliced-ELL plan of a plain row-wise sparse product (no levels): rows [0,nrows) of a CSR-like
 // pattern `ptr`, consecutive rows per slice.  src[slot] = CSR entry stored in that slot, -1 = padding.

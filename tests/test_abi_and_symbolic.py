@@ -214,6 +214,26 @@ def test_tile_and_hybrid_plans_on_the_host():
         assert 0 <= r < 1e-12, (seed, r)
 
 
+def test_host_debug_entries_refuse_malformed_csc():
+    # the host-only debug entries take the pattern through the same checks as eicos_batch_create: an out-of-range row index and
+    # decreasing column pointers are refused with the entry's error value and a message, not read out of bounds
+    import ctypes as C
+    from eicos_amd.binding import _lib, _ip
+    L = _lib()
+    pat, _ = load_fixture("lp_afiro")
+    q, Gjc, Gir, Ajc, Air = [np.ascontiguousarray(a, dtype=np.int32) for a in (pat.q, pat.Gjc, pat.Gir, pat.Ajc, pat.Air)]
+    qp = _ip(q) if pat.ncones else None
+    bad_row = Gir.copy(); bad_row[-1] = pat.m + 1000
+    bad_ptr = Gjc.copy(); j = pat.n // 2; bad_ptr[j] = bad_ptr[j + 1] + 1
+    for jc, ir, msg in ((Gjc, bad_row, b"G row index out of range"), (bad_ptr, Gir, b"G: column pointers decrease")):
+        args = (pat.n, pat.m, pat.p, pat.ncones, qp, _ip(jc), _ip(ir), _ip(Ajc), _ip(Air))
+        for fn in (L.eicos_debug_host_check, L.eicos_debug_host_check_tiles, L.eicos_debug_host_check_hybrid):
+            assert fn(*args, 1, -1, None) == -2.0 and msg in L.eicos_last_error(), (fn, L.eicos_last_error())
+        r = L.eicos_debug_host_tile_order(*args, C.c_int(-1), None, None, None, None, None)
+        assert r == -2 and msg in L.eicos_last_error(), (r, L.eicos_last_error())
+    assert L.eicos_debug_host_check(pat.n, pat.m, pat.p, pat.ncones, qp, _ip(Gjc), _ip(Gir), _ip(Ajc), _ip(Air), 1, -1, None) >= 0
+
+
 def test_multi_gpu_layer_refuses_bad_arguments_and_has_no_cpu_fallback():
     # eicos_multi_* (SURVEY.md 8b / 8e): argument checks run before any device is touched; without a GPU creation fails with
     # EICOS_E_NOGPU like the single-GPU entry point (no CPU fallback anywhere)

@@ -246,7 +246,7 @@ def test_dense_apex_agrees_with_the_level_schedule(env, monkeypatch):
 def test_dense_apex_in_the_lds_resident_build(monkeypatch):
     # lp_afiro (dim_K 129: levels 1..9 of its 10, 59 nodes, are the apex; 128 threads, slabs AND the apex image in LDS): against the same
     # build with the apex off -- equal exit codes and iteration counts, x to 1e-8 (perturbed data, |x| = 500) -- on the Netlib data and a perturbed batch; a batch
-    # beyond one instance per CU takes the HBM-slab kernel, which carries no apex (the set-up is repeated without it)
+    # beyond one instance per CU takes the HBM-slab kernel, which carries no apex (the handle is planned without it)
     from eicos_amd.generate import perturbed_batch
     pat, sets = load_fixture("lp_afiro")
     d = perturbed_batch(pat, sets[0], 0, 64, seed=11)
@@ -269,6 +269,42 @@ def test_dense_apex_in_the_lds_resident_build(monkeypatch):
     g.update(dd["Gpr"], dd["Apr"], dd["c"], dd["h"], dd["b"]); codes = g.solve()
     assert np.array_equal(codes[:64], out[0][0]) and np.array_equal(g.solution()[:64], out[0][2])  # (= the apex-off bits of the same instances)
     g.close()
+
+
+# Launch shape of every branch of handle creation (values measured on the library before creation was split into plan, launch-shape and
+# allocation steps): (pattern, batch, profile) -> threads, workgroups per CU (resident_blocks = min(batch, k * CUs)), kernel build, dense-apex
+# nodes, LDS-resident, factor path, dual right-hand sides, dynamic LDS bytes, pattern bytes
+CREATION_SHAPES = [
+    ("MPC02", 1024, 0, 256, 2, "w2", 63, 0, 0, 0, 76752, 2854576),          # apex kept, two per CU (the headline)
+    ("MPC02", 768, 0, 256, 3, "default", 0, 0, 0, 0, 49936, 2858192),       # apex dropped for a third workgroup per CU
+    ("lp_afiro", 4, 0, 128, 1, "lds-resident", 59, 1, 0, 1, 85616, 64112),  # LDS-resident build with the apex
+    ("lp_afiro", 1024, 0, 128, 4, "default", 0, 0, 0, 0, 2784, 66144),      # 128 threads on the slabs in HBM: no apex
+    ("lp_adlittle", 256, 0, 256, 1, "u-in-lds", 51, 0, 0, 1, 49184, 352976),  # the apex instead of the hybrid
+    ("lp_bandm", 256, 0, 512, 1, "u-in-lds", 0, 0, 2, 1, 136952, 1926176),  # hybrid, U in LDS
+    ("MPC02", 700, 1, 256, 3, "default", 0, 0, 0, 0, 49936, 2858192),       # arithmetic profile 1: never an apex
+]
+
+
+@pytest.mark.parametrize("name,B,profile,threads,per_cu,build,apex,ldsres,path,dual,lds,pbytes", CREATION_SHAPES)
+def test_creation_launch_shapes(name, B, profile, threads, per_cu, build, apex, ldsres, path, dual, lds, pbytes):
+    import ctypes
+    from eicos_amd.binding import _lib
+    n = ctypes.c_int()
+    assert _lib().hipDeviceGetAttribute(ctypes.byref(n), 63, 0) == 0  # (hipDeviceAttributeMultiprocessorCount, through the solver's runtime)
+    n_cu = n.value
+    if n_cu != 256:
+        pytest.skip("the recorded shapes are those of a 256-CU device")
+    pat, _ = load_fixture(name)
+    eicos_amd.set_arithmetic_profile(profile)
+    try:
+        g = eicos_amd.BatchSolver(pat, B)
+    finally:
+        eicos_amd.set_arithmetic_profile(0)
+    d, kb = g.dims(), g.kernel_build()
+    g.close()
+    assert (d["threads_per_block"], d["resident_blocks"], kb) == (threads, min(B, per_cu * n_cu), build)
+    assert (d["apex_nodes"], d["lds_resident"], d["factor_path"], d["dual_rhs"], d["arithmetic_profile"]) == (apex, ldsres, path, dual, profile)
+    assert (d["lds_bytes"], d["pattern_bytes"]) == (lds, pbytes)
 
 
 def test_kernel_build_reported_for_the_handle(monkeypatch):
