@@ -91,6 +91,16 @@ def _lib():
         if hasattr(L, "eicos_batch_update_solve"):  # (round 6)
             L.eicos_batch_update_solve.argtypes = [vp, dp, dp, dp, dp, dp, dp, ip]
             L.eicos_batch_update_solve.restype = C.c_int
+        if hasattr(L, "eicos_batch_update_rhs"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            L.eicos_batch_update_rhs.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp]
+            L.eicos_batch_update_rhs_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+            L.eicos_batch_update_rhs_solve.argtypes = [vp, dp, dp, dp, dp, ip]
+            L.eicos_multi_update_rhs.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp]
+            L.eicos_multi_update_rhs_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+            L.eicos_multi_update_rhs_solve.argtypes = [vp, dp, dp, dp, dp, ip]
+            for f in ("eicos_batch_update_rhs", "eicos_batch_update_rhs_device", "eicos_batch_update_rhs_solve", "eicos_multi_update_rhs",
+                      "eicos_multi_update_rhs_device", "eicos_multi_update_rhs_solve"):
+                getattr(L, f).restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -204,6 +214,20 @@ def host_unregister(a):
     _chk(_lib().eicos_host_unregister(C.c_void_p(a.ctypes.data)))
 
 
+def _rhs_ptrs(pat, count, c, h, b):
+    """c, h, b as C pointers for a right-hand-side-only update of `count` instances (None keeps the group; sizes checked)."""
+    ptr = []
+    for a, w in zip((c, h, b), (pat.n, pat.m, pat.p)):
+        if a is None:
+            ptr.append((None, None))
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size != count * w:
+            raise ValueError(f"array has {a.size} elements, expected {count}x{w}")
+        ptr.append((a, _dp(a) if a.size else _dp(np.zeros(1))))  # (zero-width groups: NULL-safe dummies)
+    return [a for a, _ in ptr], [p for _, p in ptr]
+
+
 UPDATE_PATHS = {0: "none", 1: "pinned bounce", 2: "pinned source in place", 3: "peer GPU in place", 4: "staged peer copies", 5: "fused into the solve", 6: "fused into the solve, staged while it runs"}
 
 
@@ -262,6 +286,30 @@ class BatchSolver:
         """Raw device pointers (ints, e.g. torch.Tensor.data_ptr()); 0 keeps the group."""
         count = self.batch if count is None else count
         _chk(_lib().eicos_batch_update_device(self._h, first, count, *[C.c_void_p(int(p) or None) for p in (dG, dA, dc, dh, db)]))
+
+    # ---- right-hand-side-only updateData (G, A and the equilibration kept; include/eicos_amd.h: eicos_batch_update_rhs) ----
+    def update_rhs(self, c=None, h=None, b=None, first: int = 0, count: int | None = None):
+        """New c, h, b (host arrays [count, ...]; None keeps the group) for instances [first, first + count), divided by the stored
+        scalings: bit for bit what update() with the unchanged Gpr, Apr and these vectors gives."""
+        if count is None:
+            count = next((np.shape(a)[0] for a in (c, h, b) if a is not None and np.ndim(a) == 2), self.batch)
+        _keep, ptr = _rhs_ptrs(self.pat, count, c, h, b)
+        _chk(_lib().eicos_batch_update_rhs(self._h, first, count, *ptr))
+
+    def update_rhs_device(self, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
+        """update_rhs from raw device pointers (ints); 0 keeps the group.  Asynchronous, like update_device."""
+        count = self.batch if count is None else count
+        _chk(_lib().eicos_batch_update_rhs_device(self._h, first, count, *[C.c_void_p(int(p) or None) for p in (dc, dh, db)]))
+
+    def update_rhs_solve(self, c=None, h=None, b=None, x_out=None):
+        """update_rhs + solve of the whole batch in one call (eicos_batch_update_rhs_solve): with pinned / registered arrays the solve
+        kernel scales every instance's vectors itself.  Returns the exit codes."""
+        _keep, ptr = _rhs_ptrs(self.pat, self.batch, c, h, b)
+        if x_out is not None:
+            assert x_out.dtype == np.float64 and x_out.flags.c_contiguous and x_out.shape == (self.batch, self.pat.n)
+        codes = np.zeros(self.batch, np.int32)
+        _chk(_lib().eicos_batch_update_rhs_solve(self._h, *ptr, _dp(x_out) if (x_out is not None and x_out.size) else None, _ip(codes)))
+        return codes
 
     # ---- solve ----
     def solve(self):
@@ -441,6 +489,27 @@ class MultiBatchSolver:
         """Raw pointers into the HBM of GPU `src_device` (arrays [count, ...]); 0 keeps the group."""
         count = self.batch if count is None else count
         _mchk(_lib().eicos_multi_update_device(self._h, int(src_device), first, count, *[C.c_void_p(int(p) or None) for p in (dG, dA, dc, dh, db)]))
+
+    def update_rhs(self, c=None, h=None, b=None, first: int = 0, count: int | None = None):
+        """BatchSolver.update_rhs over the shards (global instance order)."""
+        if count is None:
+            count = next((np.shape(a)[0] for a in (c, h, b) if a is not None and np.ndim(a) == 2), self.batch)
+        _keep, ptr = _rhs_ptrs(self.pat, count, c, h, b)
+        _mchk(_lib().eicos_multi_update_rhs(self._h, first, count, *ptr))
+
+    def update_rhs_device(self, src_device: int, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
+        """update_rhs from raw pointers into the HBM of GPU `src_device` (arrays [count, ...]); 0 keeps the group.  Asynchronous."""
+        count = self.batch if count is None else count
+        _mchk(_lib().eicos_multi_update_rhs_device(self._h, int(src_device), first, count, *[C.c_void_p(int(p) or None) for p in (dc, dh, db)]))
+
+    def update_rhs_solve(self, c=None, h=None, b=None, x_out=None):
+        """BatchSolver.update_rhs_solve on every shard, concurrently.  Returns the exit codes."""
+        _keep, ptr = _rhs_ptrs(self.pat, self.batch, c, h, b)
+        if x_out is not None:
+            assert x_out.dtype == np.float64 and x_out.flags.c_contiguous and x_out.shape == (self.batch, self.pat.n)
+        codes = np.zeros(self.batch, np.int32)
+        _mchk(_lib().eicos_multi_update_rhs_solve(self._h, *ptr, _dp(x_out) if (x_out is not None and x_out.size) else None, _ip(codes)))
+        return codes
 
     def solve(self):
         codes = np.zeros(self.batch, np.int32)

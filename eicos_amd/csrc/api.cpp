@@ -1080,6 +1080,19 @@ int eicos_batch_update_device(eicos_batch *h, int first, int count, const double
     return EICOS_OK;
 }
 
+// right-hand-side-only updateData (kernels.hip: rhs_instance): the given vectors divided by every instance's stored scalings; A, G and the
+// equilibration stay as they are
+int eicos_batch_update_rhs_device(eicos_batch *h, int first, int count, const double *dc, const double *dh, const double *db) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (first < 0 || count < 0 || first + count > h->batch) return fail(EICOS_E_INVALID, "instance range out of bounds");
+    HIP_TRY(hipSetDevice(h->device));
+    const int width = (dc ? h->dp.n : 0) + (dh ? h->dp.m : 0) + (db ? h->dp.p : 0);
+    if (!h->in_chunked_update) { const int rc = begin_update_timing(h); if (rc != EICOS_OK) return rc; }
+    HIP_TRY(launch_update_rhs(h->pslot, h->d_inst, first, count, dc, dh, db, width, h->stream));
+    if (!h->in_chunked_update) { HIP_TRY(hipEventRecord(h->ev_u1, h->stream)); h->update_timed = true; }
+    return EICOS_OK;
+}
+
 // ---- host memory helpers -------------------------------------------------------------------------------------------------
 // A few persistent host threads that split large memcpy calls between pageable and pinned memory (one core copies ~10 GB/s, a PCIe 5
 // x16 link moves ~50 GB/s: a single-threaded bounce copy would be the slowest stage of a host-pointer updateData).  Shared by every
@@ -1254,8 +1267,9 @@ int eicos_batch_last_update_path(eicos_batch *h) { return h ? h->last_update_pat
 //                    waits for it, so that the caller may overwrite them on return -- the reference's updateData is synchronous too
 //   peer, access on: the kernel reads the other GPU's HBM in place over xGMI (asynchronous, like eicos_batch_update_device)
 //   peer, no access: hipMemcpyPeerAsync into a device staging buffer, chunk by chunk
+// rhs = 1: the right-hand-side-only update (G, A must be NULL; h and b are read on their own) over the same paths.
 int eicos_internal_update_staged(eicos_batch *h, int first, int count, const double *G, const double *A,
-                                 const double *c, const double *hh, const double *b, int src_dev) {
+                                 const double *c, const double *hh, const double *b, int src_dev, int rhs) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     if (first < 0 || count < 0 || first + count > h->batch) return fail(EICOS_E_INVALID, "instance range out of bounds");
     const DevPat &D = h->dp;
@@ -1263,17 +1277,21 @@ int eicos_internal_update_staged(eicos_batch *h, int first, int count, const dou
     if (A && !b && D.p > 0) return fail(EICOS_E_INVALID, "Apr given without b");
     HIP_TRY(hipSetDevice(h->device));
     if (count == 0) return EICOS_OK;
-    const double *hv = G ? hh : nullptr, *bv = A ? b : nullptr; // (h is read only with Gpr, b only with Apr: reference src/eicos.cpp:2053-2074)
+    // (h is read only with Gpr, b only with Apr: reference src/eicos.cpp:2053-2074; the right-hand-side-only update reads them on their own)
+    const double *hv = (G || rhs) ? hh : nullptr, *bv = (A || rhs) ? b : nullptr;
+    auto launch = [&](int f, int cnt, const double *dG, const double *dA, const double *dc, const double *dh, const double *db) {
+        return rhs ? eicos_batch_update_rhs_device(h, f, cnt, dc, dh, db) : eicos_batch_update_device(h, f, cnt, dG, dA, dc, dh, db);
+    };
     struct Arr { const double *src; size_t w; };
     const Arr arr[5] = {{G, (size_t)D.nnzG}, {A, (size_t)D.nnzA}, {c, (size_t)D.n}, {hv, (size_t)D.m}, {bv, (size_t)D.p}};
     size_t per = 0; // doubles per instance that are actually given (+ 8 of padding per array keeps every row 64-byte aligned)
     for (const Arr &a : arr) if (a.src) per += a.w;
-    if (per == 0) { // nothing given: everything is kept -- still a valid updateData (re-equilibrates what is there)
-        return eicos_batch_update_device(h, first, count, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (per == 0) { // nothing given: everything is kept -- still a valid updateData (re-equilibrates what is there; the right-hand-side-only one changes nothing)
+        return launch(first, count, nullptr, nullptr, nullptr, nullptr, nullptr);
     }
     auto whole_range = [&](int path) { // one launch on the caller's pointers
         h->last_update_path = path;
-        return eicos_batch_update_device(h, first, count, G, A, c, hv, bv);
+        return launch(first, count, G, A, c, hv, bv);
     };
     if (src_dev >= 0) {
         int can = 0;
@@ -1308,7 +1326,7 @@ int eicos_internal_update_staged(eicos_batch *h, int first, int count, const dou
                     rc = fail(EICOS_E_HIP, "hipMemcpyPeerAsync failed");
                 at += (size_t)cnt * arr[k].w + 8;
             }
-            if (rc == EICOS_OK) rc = eicos_batch_update_device(h, first + o, cnt, dptr[0], dptr[1], dptr[2], dptr[3], dptr[4]);
+            if (rc == EICOS_OK) rc = launch(first + o, cnt, dptr[0], dptr[1], dptr[2], dptr[3], dptr[4]);
             // the staging buffer is reused by the next chunk
             if (rc == EICOS_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(EICOS_E_HIP, "stream sync failed in update");
         }
@@ -1325,7 +1343,8 @@ int eicos_internal_update_staged(eicos_batch *h, int first, int count, const dou
         if (kind != 1 || !is_pinned_host(a.src, (size_t)count * a.w * sizeof(double))) all_pinned = false;
     }
     // a device pointer handed to the HOST-pointer entry point must not reach the bounce copy (a host memcpy from it would fault)
-    if (any_device) return fail(EICOS_E_INVALID, "eicos_batch_update takes host pointers: an array lives in device memory (use eicos_batch_update_device)");
+    if (any_device) return fail(EICOS_E_INVALID, rhs ? "eicos_batch_update_rhs takes host pointers: an array lives in device memory (use eicos_batch_update_rhs_device)"
+                                                      : "eicos_batch_update takes host pointers: an array lives in device memory (use eicos_batch_update_device)");
     if (all_pinned && !env_knob("EICOS_HOST_BOUNCE", 0, 0, 1)) {
         const int rc = whole_range(2);
         if (rc != EICOS_OK) return rc;
@@ -1358,7 +1377,7 @@ int eicos_internal_update_staged(eicos_batch *h, int first, int count, const dou
             if (arr[q].w) pool.copy(at, arr[q].src + (size_t)o * arr[q].w, (size_t)cnt * arr[q].w * sizeof(double));
             at += (size_t)cnt * arr[q].w + 8;
         }
-        rc = eicos_batch_update_device(h, first + o, cnt, dptr[0], dptr[1], dptr[2], dptr[3], dptr[4]); // reads the pinned buffer in place
+        rc = launch(first + o, cnt, dptr[0], dptr[1], dptr[2], dptr[3], dptr[4]); // reads the pinned buffer in place
         if (rc == EICOS_OK) {
             if (hipEventRecord(h->pin_ev[bi], h->stream) != hipSuccess) rc = fail(EICOS_E_HIP, "event record failed in update");
             else h->pin_busy[bi] = true;
@@ -1371,7 +1390,11 @@ int eicos_internal_update_staged(eicos_batch *h, int first, int count, const dou
 
 int eicos_batch_update(eicos_batch *h, int first, int count, const double *G, const double *A,
                        const double *c, const double *hh, const double *b) {
-    return eicos_internal_update_staged(h, first, count, G, A, c, hh, b, -1);
+    return eicos_internal_update_staged(h, first, count, G, A, c, hh, b, -1, 0);
+}
+
+int eicos_batch_update_rhs(eicos_batch *h, int first, int count, const double *c, const double *hh, const double *b) {
+    return eicos_internal_update_staged(h, first, count, nullptr, nullptr, c, hh, b, -1, 1);
 }
 
 int eicos_batch_solve_async(eicos_batch *h) {
@@ -1476,19 +1499,22 @@ int eicos_batch_solve(eicos_batch *h, int *exitcodes) {
 // is filled by eicos_batch_solution afterwards.  Anything else (pageable inputs -- unless staging is switched on, below --, a handle without an
 // LDS vector, vectors beyond the in-register scaling accumulators) takes eicos_batch_update + eicos_batch_solve: same results, bit for bit, on
 // every path.
-// Synchronous; exitcodes optional.
-int eicos_batch_update_solve(eicos_batch *h, const double *G, const double *A, const double *c, const double *hh, const double *b,
-                             double *x_out, int *exitcodes) {
+// Synchronous; exitcodes optional.  rhs = true: the right-hand-side-only update (G, A NULL; h and b read on their own; no accumulator limit:
+// the fused form divides by the stored scalings, kernels.hip: rhs_instance), eicos_batch_update_rhs_solve.
+static int update_solve(eicos_batch *h, const double *G, const double *A, const double *c, const double *hh, const double *b,
+                        double *x_out, int *exitcodes, bool rhs) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     const DevPat &D = h->dp;
     if (G && !hh && D.m > 0) return fail(EICOS_E_INVALID, "Gpr given without h");
     if (A && !b && D.p > 0) return fail(EICOS_E_INVALID, "Apr given without b");
     HIP_TRY(hipSetDevice(h->device));
-    const double *hv = G ? hh : nullptr, *bv = A ? b : nullptr; // (h is read only with Gpr, b only with Apr: reference src/eicos.cpp:2053-2074)
+    // (h is read only with Gpr, b only with Apr: reference src/eicos.cpp:2053-2074; the right-hand-side-only update reads them on their own)
+    const double *hv = (G || rhs) ? hh : nullptr, *bv = (A || rhs) ? b : nullptr;
     struct Arr { const double *src; size_t w; };
     const Arr arr[5] = {{G, (size_t)D.nnzG}, {A, (size_t)D.nnzA}, {c, (size_t)D.n}, {hv, (size_t)D.m}, {bv, (size_t)D.p}};
     auto gpu_addressable = [&](const void *ptr, size_t bytes) { const int k = pointer_kind(ptr); return k == 2 || (k == 1 && is_pinned_host(ptr, bytes)); };
-    const bool fused = h->nlds >= 1 && D.n <= 8 * h->threads && D.p <= 8 * h->threads && D.m <= 16 * h->threads && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
+    const bool fused = h->nlds >= 1 && (rhs || (D.n <= 8 * h->threads && D.p <= 8 * h->threads && D.m <= 16 * h->threads)) &&
+                       env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
     // arrays the GPU cannot address (pageable memory) are STAGED: copied into the handle's pinned staging buffer while the kernel runs
     bool staged[5] = {false, false, false, false, false};
     size_t stage_need = 0;
@@ -1505,7 +1531,8 @@ int eicos_batch_update_solve(eicos_batch *h, const double *G, const double *A, c
     if (!fused || (any_staged && !env_knob("EICOS_FUSED_STAGED", 0, 0, 1))) {
         bool all_device = true; // (device arrays on a handle without the fused path: the device-pointer updateData)
         for (int k = 0; k < 5; k++) if (arr[k].src && arr[k].w && pointer_kind(arr[k].src) != 2) all_device = false;
-        rc = all_device ? eicos_batch_update_device(h, 0, h->batch, G, A, c, hh, b) : eicos_batch_update(h, 0, h->batch, G, A, c, hh, b);
+        if (rhs) rc = all_device ? eicos_batch_update_rhs_device(h, 0, h->batch, c, hv, bv) : eicos_batch_update_rhs(h, 0, h->batch, c, hv, bv);
+        else rc = all_device ? eicos_batch_update_device(h, 0, h->batch, G, A, c, hh, b) : eicos_batch_update(h, 0, h->batch, G, A, c, hh, b);
         if (rc == EICOS_OK) rc = eicos_batch_solve_async(h);
         if (rc != EICOS_OK) return rc;
         rc = eicos_batch_sync(h);
@@ -1543,7 +1570,7 @@ int eicos_batch_update_solve(eicos_batch *h, const double *G, const double *A, c
         rc = begin_update_timing(h); // (an empty updateData interval in the timing ring: the work is inside the solve launch)
         if (rc != EICOS_OK) return rc;
         HIP_TRY(hipEventRecord(h->ev_u1, h->stream)); h->update_timed = true;
-        h->fused = UpdArgs{ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], x_direct ? x_out : nullptr, 1,
+        h->fused = UpdArgs{ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], x_direct ? x_out : nullptr, rhs ? UPD_RHS : UPD_FULL,
                            any_staged ? h->stage_flags : nullptr, chunk, h->stage_seq, h->d_err};
         h->fused_pending = true;
         rc = eicos_batch_solve_async(h);
@@ -1573,6 +1600,14 @@ int eicos_batch_update_solve(eicos_batch *h, const double *G, const double *A, c
         for (int i = 0; i < h->batch; i++) exitcodes[i] = info[i].exitcode;
     }
     return EICOS_OK;
+}
+
+int eicos_batch_update_solve(eicos_batch *h, const double *G, const double *A, const double *c, const double *hh, const double *b,
+                             double *x_out, int *exitcodes) {
+    return update_solve(h, G, A, c, hh, b, x_out, exitcodes, false);
+}
+int eicos_batch_update_rhs_solve(eicos_batch *h, const double *c, const double *hh, const double *b, double *x_out, int *exitcodes) {
+    return update_solve(h, nullptr, nullptr, c, hh, b, x_out, exitcodes, true);
 }
 
 int eicos_batch_solution(eicos_batch *h, double *x) {

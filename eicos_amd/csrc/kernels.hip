@@ -3170,6 +3170,30 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void update_inst
     __syncthreads();
 }
 
+// Right-hand-side-only updateData of one instance (eicos_batch_update_rhs*; no reference counterpart): the given vectors divided by the
+// scalings the instance's last updateData stored.  update_instance and k_update end with the same division by the same values, so the
+// bits equal those of an updateData that re-sends unchanged G and A.  Before the first updateData (zero-filled slab,
+// DevInfo::equilibrated = 0) the scalings count as 1: the vectors are stored as given -- exactly how a later updateData that keeps them
+// treats them.  A, G, the scalings and the constants are not touched.  `q` = row of this instance in the input arrays (NULL = keep).
+// rhs_entry = one entry; rhs_instance = one instance by one workgroup (k_solve, fused: eicos_batch_update_rhs_solve); k_update_rhs_range
+// below covers a range of instances.
+__device__ __forceinline__ void rhs_entry(hbm_p I, int e, int wc, int wh, size_t q, const DevPat &P, bool eq, const double *cin,
+                                          const double *hin, const double *bin) {
+    if (e < wc) I[P.i_c + e] = cin[q * P.n + e] / (eq ? I[P.i_xe + e] : 1.);
+    else if (e < wc + wh) { const int i = e - wc; I[P.i_h + i] = hin[q * P.m + i] / (eq ? I[P.i_ge + i] : 1.); }
+    else { const int r = e - wc - wh; I[P.i_b + r] = bin[q * P.p + r] / (eq ? I[P.i_ae + r] : 1.); }
+}
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void rhs_instance(int ps, hbm_p I, size_t q, const double *cin, const double *hin,
+                                                                                   const double *bin) {
+    ps = uni(ps); I = uni_ptr(I);
+    const DevPat &P = c_pat[ps];
+    const bool eq = reinterpret_cast<const DevInfo EICOS_GLOBAL *>(I + P.i_info)->equilibrated != 0;
+    const int wc = cin ? P.n : 0, wh = hin ? P.m : 0, w = wc + wh + (bin ? P.p : 0);
+    FOR_T(e, w) rhs_entry(I, e, wc, wh, q, P, eq, cin, hin, bin);
+    __syncthreads(); // (the solve -- or the LDS-resident build's copy of the slab -- reads entries other threads wrote)
+}
+
 template <int T, int NLDS, bool I16>
 __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     int ps, double *inst, double *work, int B, int *queue, const int *order, double warm, double dyn_delta, double dyn_eps, UpdArgs upd) {
@@ -3221,7 +3245,8 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
                     __syncthreads();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, ""); // (system scope: the rows this workgroup reads next were written by the host)
                 }
-                update_instance<T, false>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.G, upd.A, upd.c, upd.h, upd.b);
+                if (upd.on == UPD_RHS) rhs_instance<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.c, upd.h, upd.b);
+                else update_instance<T, false>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.G, upd.A, upd.c, upd.h, upd.b);
             }
         }
 #if EICOS_LDSRES
@@ -3388,6 +3413,20 @@ __global__ __launch_bounds__(T) void k_update_lds(int ps, double *inst, int firs
         update_instance<T, LDSV>(ps, (hbm_p)inst + (size_t)(first + q) * P.inst_stride, (size_t)q, Gpr, Apr, cin, hin, bin);
 }
 
+// right-hand-side-only updateData of a range of instances (rhs_instance): ENTRY-parallel -- blockIdx.y strides over the instances,
+// the x dimension over the given entries [c | h | b] of one instance (unit stride in the inputs and in the slab)
+template <int T>
+__global__ __launch_bounds__(T) void k_update_rhs_range(int ps, double *inst, int first, int count, const double *cin, const double *hin,
+                                                        const double *bin) {
+    const DevPat &P = c_pat[ps];
+    const int wc = cin ? P.n : 0, wh = hin ? P.m : 0, w = wc + wh + (bin ? P.p : 0);
+    for (int q = blockIdx.y; q < count; q += gridDim.y) {
+        hbm_p I = (hbm_p)inst + (size_t)(first + q) * P.inst_stride;
+        const bool eq = reinterpret_cast<const DevInfo EICOS_GLOBAL *>(I + P.i_info)->equilibrated != 0;
+        for (int e = blockIdx.x * T + threadIdx.x; e < w; e += gridDim.x * T) rhs_entry(I, e, wc, wh, (size_t)q, P, eq, cin, hin, bin);
+    }
+}
+
 // Debug: factorise instance `i` with the KKT scaling block as it stands in memory (runs the solver's own stage).
 template <int T>
 __global__ __launch_bounds__(T, waves_per_eu<T>()) void k_debug_factor(int ps, double *inst, double *work, int i) {
@@ -3474,7 +3513,7 @@ template <class F> static auto dispatch_solve(int threads, int nlds, int idx16, 
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds,
                         int idx16, int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd_in) {
     UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr};
-    if (upd.on && nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector)
+    if (upd.on && nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector; both modes live in the NLDS >= 1 kernels)
     if (B <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(queue, 0, sizeof(int), st); // group queue of this launch
     if (e != hipSuccess) return e;
@@ -3504,6 +3543,14 @@ hipError_t launch_update(int ps, double *inst, int first, int count, const doubl
     } else if (lds_bytes > 0) { // values + maxima fit LDS: the entry-parallel kernel, 512 threads, one workgroup per CU at a time
         hipLaunchKernelGGL((k_update_lds<512, true>), dim3(grid), dim3(512), lds_bytes, st, ps, inst, first, count, Gpr, Apr, c, h, b);
     } else hipLaunchKernelGGL(k_update<256>, dim3(grid), dim3(256), 0, st, ps, inst, first, count, Gpr, Apr, c, h, b, scratch);
+    return hipGetLastError();
+}
+hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st) {
+    if (count <= 0 || width <= 0) return hipSuccess;
+    constexpr int T = 256;
+    const int gx = (width + T - 1) / T, gy = count;
+    const dim3 grid((unsigned)(gx < 64 ? gx : 64), (unsigned)(gy < 16384 ? gy : 16384));
+    hipLaunchKernelGGL(k_update_rhs_range<T>, grid, dim3(T), 0, st, ps, inst, first, count, c, h, b);
     return hipGetLastError();
 }
 // the dynamic-LDS ceiling of the two entry-parallel updateData kernels, set once per handle on the handle's device

@@ -10,11 +10,17 @@ namespace eicos {
 // STAGED host arrays (pageable memory): the arrays are the handle's pinned staging buffer, which the host fills chunk by chunk WHILE the
 // kernel runs -- flags[instance / chunk] == seq once the chunk holding an instance has been copied (pinned, host-written); the workgroup polls
 // it before it touches the instance's rows (bounded: after ~5 s it gives up and raises *err).
+// on = UPD_FULL: updateData (G, A, c, h, b); on = UPD_RHS: the right-hand-side-only update (c, h, b scaled by the stored scalings; G, A
+// unused); 0: off.
+enum { UPD_FULL = 1, UPD_RHS = 2 };
 struct UpdArgs { const double *G, *A, *c, *h, *b; double *x; int on; const unsigned *flags; int chunk; unsigned seq; int *err; };
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
                         int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
 hipError_t launch_update(int ps, double *inst, int first, int count, const double *Gpr, const double *Apr,
                          const double *c, const double *h, const double *b, double *scratch, int grid, size_t lds_bytes, int vals_in_lds, hipStream_t st);
+// right-hand-side-only updateData of instances [first, first + count): rows of c [count][n], h [count][m], b [count][p] (NULL = keep)
+// divided by each instance's stored scalings; `width` = the summed widths of the given groups (sizes the grid)
+hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st);
 hipError_t update_set_max_lds();
 hipError_t launch_debug_factor(int ps, double *inst, double *work, int i, int threads, size_t dyn_lds, hipStream_t st);
 hipError_t launch_debug_scalings(int ps, double *inst, double *work, int i, int *ok, int threads, hipStream_t st);

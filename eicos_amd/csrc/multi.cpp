@@ -20,7 +20,7 @@
 #include <vector>
 
 extern "C" int eicos_internal_update_staged(eicos_batch *h, int first, int count, const double *G, const double *A,
-                                            const double *c, const double *hh, const double *b, int src_dev);
+                                            const double *c, const double *hh, const double *b, int src_dev, int rhs);
 extern "C" int eicos_internal_device(const eicos_batch *h);
 extern "C" int eicos_internal_solve_span_ms(eicos_batch *from, eicos_batch *to, float *ms);
 
@@ -186,7 +186,22 @@ int eicos_multi_update_device(eicos_multi *mh, int src_device, int first, int co
         const char *e_ = std::getenv("EICOS_EXPERIMENT"), *k_ = std::getenv("EICOS_MULTI_FORCE_PEER");
         const bool force_peer = e_ && !std::strcmp(e_, "1") && k_ && !std::strcmp(k_, "1");
         if (mh->device[s] == src_device && !force_peer) return eicos_batch_update_device(mh->shard[s], f, cnt, G, A, cc, hh, bb); // already in this GPU's HBM: no copy
-        return eicos_internal_update_staged(mh->shard[s], f, cnt, G, A, cc, hh, bb, src_device);                  // peer copies (xGMI), then the same kernel
+        return eicos_internal_update_staged(mh->shard[s], f, cnt, G, A, cc, hh, bb, src_device, 0);               // peer copies (xGMI), then the same kernel
+    });
+}
+
+int eicos_multi_update_rhs(eicos_multi *mh, int first, int count, const double *c, const double *h, const double *b) {
+    return for_range(mh, first, count, [&](int s, int f, int cnt, size_t off) {
+        return eicos_batch_update_rhs(mh->shard[s], f, cnt, at(c, off, mh->n), at(h, off, mh->m), at(b, off, mh->p));
+    });
+}
+
+int eicos_multi_update_rhs_device(eicos_multi *mh, int src_device, int first, int count, const double *dc, const double *dh, const double *db) {
+    if (src_device < 0) return mfail(EICOS_E_INVALID, "src_device must name the GPU that holds the inputs");
+    return for_range(mh, first, count, [&](int s, int f, int cnt, size_t off) {
+        const double *cc = at(dc, off, mh->n), *hh = at(dh, off, mh->m), *bb = at(db, off, mh->p);
+        if (mh->device[s] == src_device) return eicos_batch_update_rhs_device(mh->shard[s], f, cnt, cc, hh, bb);
+        return eicos_internal_update_staged(mh->shard[s], f, cnt, nullptr, nullptr, cc, hh, bb, src_device, 1);
     });
 }
 
@@ -232,6 +247,15 @@ int eicos_multi_update_solve(eicos_multi *mh, const double *G, const double *A, 
         const size_t r = (size_t)mh->first[s];
         return eicos_batch_update_solve(mh->shard[s], at(G, r, mh->nnzG), at(A, r, mh->nnzA), at(c, r, mh->n), at(hh, r, mh->m), at(b, r, mh->p),
                                         x_out ? x_out + r * (size_t)mh->n : nullptr, exitcodes ? exitcodes + r : nullptr);
+    });
+}
+
+int eicos_multi_update_rhs_solve(eicos_multi *mh, const double *c, const double *hh, const double *b, double *x_out, int *exitcodes) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    return for_shards(mh, [&](int s) {
+        const size_t r = (size_t)mh->first[s];
+        return eicos_batch_update_rhs_solve(mh->shard[s], at(c, r, mh->n), at(hh, r, mh->m), at(b, r, mh->p),
+                                            x_out ? x_out + r * (size_t)mh->n : nullptr, exitcodes ? exitcodes + r : nullptr);
     });
 }
 

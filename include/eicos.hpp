@@ -135,6 +135,17 @@ namespace EiCOS
         {
             mcheck(eicos_multi_update_device(h_, src_device, first, count < 0 ? batch_ : count, dGpr, dApr, dc, dh, db), "eicos_multi_update_device");
         }
+        // Extension (not in the reference, whose updateData reads h only with Gpr and b only with Apr): new c, h, b (nullptr keeps a group)
+        // with G, A and their equilibration kept -- the vectors are divided by the stored scalings, bit for bit what updateData with the
+        // unchanged matrices gives (eicos_batch_update_rhs of eicos_amd.h)
+        void updateRHS(const double *c, const double *h, const double *b, int first = 0, int count = -1)
+        {
+            mcheck(eicos_multi_update_rhs(h_, first, count < 0 ? batch_ : count, c, h, b), "eicos_multi_update_rhs");
+        }
+        void updateRHSDevice(int src_device, const double *dc, const double *dh, const double *db, int first = 0, int count = -1)
+        {
+            mcheck(eicos_multi_update_rhs_device(h_, src_device, first, count < 0 ? batch_ : count, dc, dh, db), "eicos_multi_update_rhs_device");
+        }
         // Extension (not in the reference): re-solves start from the previous solution, see eicos_amd.h
         void setWarmStart(double shift) { mcheck(eicos_multi_set_warm_start(h_, shift), "eicos_multi_set_warm_start"); }
         // Extension: ECOS-style dynamic regularisation (the reference's Settings::delta / ::eps are never read)
@@ -157,6 +168,15 @@ namespace EiCOS
         {
             std::vector<int> codes(batch_);
             mcheck(eicos_multi_update_solve(h_, Gpr, Apr, c, h, b, x_out, codes.data()), "eicos_multi_update_solve");
+            std::vector<exitcode> out(batch_);
+            for (int i = 0; i < batch_; i++) out[i] = static_cast<exitcode>(codes[i]);
+            return out;
+        }
+        // updateRHS(...) + solve() in ONE call (same paths as the form above; the solve kernel scales the vectors of pinned arrays itself)
+        std::vector<exitcode> solve(const double *c, const double *h, const double *b, double *x_out = nullptr)
+        {
+            std::vector<int> codes(batch_);
+            mcheck(eicos_multi_update_rhs_solve(h_, c, h, b, x_out, codes.data()), "eicos_multi_update_rhs_solve");
             std::vector<exitcode> out(batch_);
             for (int i = 0; i < batch_; i++) out[i] = static_cast<exitcode>(codes[i]);
             return out;

@@ -144,6 +144,23 @@ int eicos_batch_update_device(eicos_batch *hd, int first, int count,
                               const double *dGpr, const double *dApr,
                               const double *dc, const double *dh, const double *db);
 
+/* ---- right-hand-side-only updateData (no reference counterpart: the reference's updateData reads h only with Gpr and b only with Apr,
+ * src/eicos.cpp:2053-2074, so changing a vector there means re-sending the matrices).  Instances [first, first+count); arrays [count][n],
+ * [count][m], [count][p], row-major; NULL = keep that group, and h and b are read on their own.  A, G and the equilibration are not touched:
+ * the new vectors are divided by the scalings the instance's last updateData stored -- the very division updateData ends with, so the
+ * result equals, bit for bit, an eicos_batch_update that re-sends unchanged Gpr and Apr with the same vectors.  An instance that has had
+ * no updateData yet has no scalings: its vectors are stored as given (scalings of 1), and a later eicos_batch_update that keeps them
+ * equilibrates them exactly as if they had been given to it.  Host arrays take the paths of eicos_batch_update (pageable: the bounce
+ * pipeline, path 1; pinned / registered: read in place, path 2; synchronous in the same way). */
+int eicos_batch_update_rhs(eicos_batch *hd, int first, int count, const double *c, const double *h, const double *b);
+/* Same, DEVICE pointers; asynchronous like eicos_batch_update_device. */
+int eicos_batch_update_rhs_device(eicos_batch *hd, int first, int count, const double *dc, const double *dh, const double *db);
+/* right-hand-side-only updateData + solve of the whole batch in one synchronous call: eicos_batch_update_solve's paths and conventions
+ * (x_out [batch][n] and exitcodes [batch] optional).  When every given array is GPU-addressable (pinned / registered host memory or device
+ * memory) each workgroup of the solve kernel scales its instance's vectors right before it solves it (path 5); otherwise, and on handles
+ * without an LDS vector, eicos_batch_update_rhs + eicos_batch_solve.  Bit-identical on every path. */
+int eicos_batch_update_rhs_solve(eicos_batch *hd, const double *c, const double *h, const double *b, double *x_out, int *exitcodes);
+
 /* ---- solve: replaces exitcode Solver::solve(bool) (reference include/eicos.hpp:158,
  * src/eicos.cpp:848-1262) for every instance of the batch.  exitcodes (host, [batch]) may be
  * NULL.  Synchronous: returns after the GPU work has completed. */
@@ -243,6 +260,12 @@ int eicos_multi_update_solve(eicos_multi *mh, const double *Gpr, const double *A
  * src_device must have completed before the call (the shards' streams are not ordered against the producer's stream). */
 int eicos_multi_update_device(eicos_multi *mh, int src_device, int first, int count, const double *dGpr, const double *dApr,
                               const double *dc, const double *dh, const double *db);
+/* right-hand-side-only updateData (eicos_batch_update_rhs / _device / _solve on every shard, in global instance order): from host arrays,
+ * from arrays in the HBM of ONE GPU (src_device; asynchronous, with the source-buffer rules of eicos_multi_update_device), and fused with
+ * the solve of the whole batch (x_out / exitcodes optional) */
+int eicos_multi_update_rhs(eicos_multi *mh, int first, int count, const double *c, const double *h, const double *b);
+int eicos_multi_update_rhs_device(eicos_multi *mh, int src_device, int first, int count, const double *dc, const double *dh, const double *db);
+int eicos_multi_update_rhs_solve(eicos_multi *mh, const double *c, const double *h, const double *b, double *x_out, int *exitcodes);
 /* solve: async = enqueue every shard's kernels on its stream and return; sync waits for all; eicos_multi_solve = both (+ exit codes, may be NULL) */
 int eicos_multi_solve_async(eicos_multi *mh);
 int eicos_multi_sync(eicos_multi *mh);
