@@ -214,155 +214,177 @@ def host_unregister(a):
     _chk(_lib().eicos_host_unregister(C.c_void_p(a.ctypes.data)))
 
 
+def _group_ptrs(groups, widths, count):
+    """Any subset of the input groups as (keep-alive arrays, C pointers): contiguous float64 [count, width] each, sizes checked; None keeps
+    a group (NULL)."""
+    arrs, ptrs = [], []
+    for a, w in zip(groups, widths):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != count * w:
+                raise ValueError(f"array has {a.size} elements, expected {count}x{w}")
+        arrs.append(a)
+        ptrs.append(None if a is None else _dp(a) if a.size else _dp(np.zeros(1)))  # (zero-width groups: NULL-safe dummies)
+    return arrs, ptrs
+
+
 def _rhs_ptrs(pat, count, c, h, b):
     """c, h, b as C pointers for a right-hand-side-only update of `count` instances (None keeps the group; sizes checked)."""
-    ptr = []
-    for a, w in zip((c, h, b), (pat.n, pat.m, pat.p)):
-        if a is None:
-            ptr.append((None, None))
-            continue
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        if a.size != count * w:
-            raise ValueError(f"array has {a.size} elements, expected {count}x{w}")
-        ptr.append((a, _dp(a) if a.size else _dp(np.zeros(1))))  # (zero-width groups: NULL-safe dummies)
-    return [a for a, _ in ptr], [p for _, p in ptr]
+    return _group_ptrs((c, h, b), (pat.n, pat.m, pat.p), count)
+
+
+def _rows(groups, default):
+    """The instance count of an update: the leading dimension of the first two-dimensional array given."""
+    return next((np.shape(a)[0] for a in groups if a is not None and np.ndim(a) == 2), default)
+
+
+def _pattern_ptrs(pat):
+    """(keep-alive int32 arrays, [q, Gjc, Gir, Ajc, Air] as C pointers) of a pattern; empty groups are NULL."""
+    keep = [np.ascontiguousarray(a, dtype=np.int32) for a in (pat.q, pat.Gjc, pat.Gir, pat.Ajc, pat.Air)]
+    q, Gjc, Gir, Ajc, Air = keep
+    return keep, [_ip(q) if pat.ncones else None, _ip(Gjc) if pat.m > 0 else None, _ip(Gir) if pat.m > 0 else None,
+                  _ip(Ajc) if pat.p > 0 else None, _ip(Air) if pat.p > 0 else None]
 
 
 UPDATE_PATHS = {0: "none", 1: "pinned bounce", 2: "pinned source in place", 3: "peer GPU in place", 4: "staged peer copies", 5: "fused into the solve", 6: "fused into the solve, staged while it runs"}
 
 
-class BatchSolver:
-    """One sparsity pattern, `batch` numeric instances on one GPU.
+class _Solver:
+    """What BatchSolver (eicos_batch_*) and MultiBatchSolver (eicos_multi_*) share: the same calls on host arrays in global instance
+    order, told apart by the C prefix and the error getter."""
+    _prefix = _error = None
 
-    Mirrors the reference's Solver surface (ctor / updateData / solve / solution / getInfo,
-    reference include/eicos.hpp:137-163) with a leading batch dimension on every array.
-    """
+    def _call(self, name, *args):
+        rc = getattr(_lib(), self._prefix + name)(self._h, *args)
+        if rc != 0:
+            raise RuntimeError(f"eicos_amd error {rc}: {getattr(_lib(), self._error)().decode()}")
 
-    def __init__(self, pat, batch: int, device: int = -1):
-        L = _lib()
-        self.pat, self.batch = pat, int(batch)
-        self._keep = [np.ascontiguousarray(a, dtype=np.int32) for a in (pat.q, pat.Gjc, pat.Gir, pat.Ajc, pat.Air)]
-        q, Gjc, Gir, Ajc, Air = self._keep
-        h = C.c_void_p()
-        _chk(L.eicos_batch_create(pat.n, pat.m, pat.p, pat.l, pat.ncones, _ip(q) if pat.ncones else None,
-                                  _ip(Gjc) if pat.m > 0 else None, _ip(Gir) if pat.m > 0 else None,
-                                  _ip(Ajc) if pat.p > 0 else None, _ip(Air) if pat.p > 0 else None,
-                                  self.batch, device, C.byref(h)))
-        self._h = h
+    def _widths(self):
+        pat = self.pat
+        return pat.nnzG, pat.nnzA, pat.n, pat.m, pat.p
+
+    def _solve_with(self, name, ptr, x_out):
+        if x_out is not None:
+            assert x_out.dtype == np.float64 and x_out.flags.c_contiguous and x_out.shape == (self.batch, self.pat.n)
+        codes = np.zeros(self.batch, np.int32)
+        self._call(name, *ptr, _dp(x_out) if (x_out is not None and x_out.size) else None, _ip(codes))
+        return codes
 
     # ---- updateData ----
     def update(self, Gpr=None, Apr=None, c=None, h=None, b=None, first: int = 0, count: int | None = None):
         """Host arrays shaped [count, ...]; None keeps the group (reference semantics)."""
-        arrs = []
-        for a in (Gpr, Apr, c, h, b):
-            arrs.append(None if a is None else np.ascontiguousarray(a, dtype=np.float64))
-        if count is None:
-            count = next((a.shape[0] for a in arrs if a is not None and a.ndim == 2), self.batch)
-        pat = self.pat
-        for a, w in zip(arrs, (pat.nnzG, pat.nnzA, pat.n, pat.m, pat.p)):
-            if a is not None and a.size != count * w:
-                raise ValueError(f"array has {a.size} elements, expected {count}x{w}")
-        # zero-width groups are passed as NULL-safe dummies
-        ptr = [(_dp(a) if (a is not None and a.size) else (_dp(np.zeros(1)) if a is not None else None)) for a in arrs]
-        _chk(_lib().eicos_batch_update(self._h, first, count, *ptr))
-
-    def update_solve(self, Gpr=None, Apr=None, c=None, h=None, b=None, x_out=None):
-        """updateData + solve in one call (eicos_batch_update_solve): host arrays shaped [batch, ...] (None keeps the group).  With pinned /
-        registered arrays the solve kernel pulls every instance's inputs itself (no separate updateData launch) and writes x into a pinned
-        `x_out`.  Returns the exit codes."""
-        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (Gpr, Apr, c, h, b)]
-        pat = self.pat
-        for a, w in zip(arrs, (pat.nnzG, pat.nnzA, pat.n, pat.m, pat.p)):
-            if a is not None and a.size != self.batch * w:
-                raise ValueError(f"array has {a.size} elements, expected {self.batch}x{w}")
-        ptr = [(_dp(a) if (a is not None and a.size) else (_dp(np.zeros(1)) if a is not None else None)) for a in arrs]
-        if x_out is not None:
-            assert x_out.dtype == np.float64 and x_out.flags.c_contiguous and x_out.shape == (self.batch, pat.n)
-        codes = np.zeros(self.batch, np.int32)
-        _chk(_lib().eicos_batch_update_solve(self._h, *ptr, _dp(x_out) if (x_out is not None and x_out.size) else None, _ip(codes)))
-        return codes
-
-    def update_device(self, dG=0, dA=0, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
-        """Raw device pointers (ints, e.g. torch.Tensor.data_ptr()); 0 keeps the group."""
-        count = self.batch if count is None else count
-        _chk(_lib().eicos_batch_update_device(self._h, first, count, *[C.c_void_p(int(p) or None) for p in (dG, dA, dc, dh, db)]))
+        count = _rows((Gpr, Apr, c, h, b), self.batch) if count is None else count
+        _keep, ptr = _group_ptrs((Gpr, Apr, c, h, b), self._widths(), count)
+        self._call("update", first, count, *ptr)
 
     # ---- right-hand-side-only updateData (G, A and the equilibration kept; include/eicos_amd.h: eicos_batch_update_rhs) ----
     def update_rhs(self, c=None, h=None, b=None, first: int = 0, count: int | None = None):
         """New c, h, b (host arrays [count, ...]; None keeps the group) for instances [first, first + count), divided by the stored
         scalings: bit for bit what update() with the unchanged Gpr, Apr and these vectors gives."""
-        if count is None:
-            count = next((np.shape(a)[0] for a in (c, h, b) if a is not None and np.ndim(a) == 2), self.batch)
+        count = _rows((c, h, b), self.batch) if count is None else count
         _keep, ptr = _rhs_ptrs(self.pat, count, c, h, b)
-        _chk(_lib().eicos_batch_update_rhs(self._h, first, count, *ptr))
-
-    def update_rhs_device(self, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
-        """update_rhs from raw device pointers (ints); 0 keeps the group.  Asynchronous, like update_device."""
-        count = self.batch if count is None else count
-        _chk(_lib().eicos_batch_update_rhs_device(self._h, first, count, *[C.c_void_p(int(p) or None) for p in (dc, dh, db)]))
+        self._call("update_rhs", first, count, *ptr)
 
     def update_rhs_solve(self, c=None, h=None, b=None, x_out=None):
-        """update_rhs + solve of the whole batch in one call (eicos_batch_update_rhs_solve): with pinned / registered arrays the solve
-        kernel scales every instance's vectors itself.  Returns the exit codes."""
+        """update_rhs + solve of the whole batch in one call (eicos_batch_update_rhs_solve; on every shard, concurrently): with pinned /
+        registered arrays the solve kernel scales every instance's vectors itself.  Returns the exit codes."""
         _keep, ptr = _rhs_ptrs(self.pat, self.batch, c, h, b)
-        if x_out is not None:
-            assert x_out.dtype == np.float64 and x_out.flags.c_contiguous and x_out.shape == (self.batch, self.pat.n)
-        codes = np.zeros(self.batch, np.int32)
-        _chk(_lib().eicos_batch_update_rhs_solve(self._h, *ptr, _dp(x_out) if (x_out is not None and x_out.size) else None, _ip(codes)))
-        return codes
+        return self._solve_with("update_rhs_solve", ptr, x_out)
 
     # ---- solve ----
     def solve(self):
         codes = np.zeros(self.batch, np.int32)
-        _chk(_lib().eicos_batch_solve(self._h, _ip(codes)))
+        self._call("solve", _ip(codes))
         return codes
 
     def solve_async(self):
-        _chk(_lib().eicos_batch_solve_async(self._h))
+        self._call("solve_async")
 
     def sync(self):
-        _chk(_lib().eicos_batch_sync(self._h))
+        self._call("sync")
 
     def set_warm_start(self, shift: float):
         """shift > 0: re-solves start from the previous solution (not in the reference; see include/eicos_amd.h)."""
-        _chk(_lib().eicos_batch_set_warm_start(self._h, float(shift)))
+        self._call("set_warm_start", float(shift))
 
     def set_dynamic_regularization(self, delta: float, eps: float):
         """delta > 0: ECOS-style dynamic regularisation of the LDL' pivots (not in the reference)."""
-        _chk(_lib().eicos_batch_set_dynamic_regularization(self._h, float(delta), float(eps)))
-
-    def set_stream(self, stream_ptr: int):
-        _chk(_lib().eicos_batch_set_stream(self._h, C.c_void_p(int(stream_ptr) or None)))
+        self._call("set_dynamic_regularization", float(delta), float(eps))
 
     # ---- results ----
     def solution(self):
-        x = np.zeros((self.batch, max(self.pat.n, 1)))
+        x = np.zeros((self.batch, self.pat.n))
         if self.pat.n:
-            x = np.zeros((self.batch, self.pat.n))
-            _chk(_lib().eicos_batch_solution(self._h, _dp(x)))
-            return x
-        return x[:, :0]
+            self._call("solution", _dp(x))
+        return x
 
     def duals(self):
         pat = self.pat
         y, z, s = np.zeros((self.batch, pat.p)), np.zeros((self.batch, pat.m)), np.zeros((self.batch, pat.m))
-        _chk(_lib().eicos_batch_duals(self._h, _dp(y) if pat.p else None, _dp(z) if pat.m else None, _dp(s) if pat.m else None))
+        self._call("duals", _dp(y) if pat.p else None, _dp(z) if pat.m else None, _dp(s) if pat.m else None)
         return y, z, s
-
-    def info(self):
-        arr = (Info * self.batch)()
-        _chk(_lib().eicos_batch_info(self._h, arr))
-        return [arr[i].asdict() for i in range(self.batch)]
 
     def info_arrays(self):
         arr = (Info * self.batch)()
-        _chk(_lib().eicos_batch_info(self._h, arr))
+        self._call("info", arr)
         raw = np.frombuffer(arr, dtype=np.dtype([(k, "f8" if t is C.c_double else "i4") for k, t in Info._fields_]))  # (declaration order)
         return {k: raw[k].copy() for k in raw.dtype.names}
 
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(_lib(), self._prefix + "destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BatchSolver(_Solver):
+    """One sparsity pattern, `batch` numeric instances on one GPU.
+
+    Mirrors the reference's Solver surface (ctor / updateData / solve / solution / getInfo,
+    reference include/eicos.hpp:137-163) with a leading batch dimension on every array.
+    """
+    _prefix, _error = "eicos_batch_", "eicos_last_error"
+
+    def __init__(self, pat, batch: int, device: int = -1):
+        self.pat, self.batch = pat, int(batch)
+        self._keep, ptrs = _pattern_ptrs(pat)
+        h = C.c_void_p()
+        _chk(_lib().eicos_batch_create(pat.n, pat.m, pat.p, pat.l, pat.ncones, *ptrs, self.batch, device, C.byref(h)))
+        self._h = h
+
+    def update_solve(self, Gpr=None, Apr=None, c=None, h=None, b=None, x_out=None):
+        """updateData + solve in one call (eicos_batch_update_solve): host arrays shaped [batch, ...] (None keeps the group).  With pinned /
+        registered arrays the solve kernel pulls every instance's inputs itself (no separate updateData launch) and writes x into a pinned
+        `x_out`.  Returns the exit codes."""
+        _keep, ptr = _group_ptrs((Gpr, Apr, c, h, b), self._widths(), self.batch)
+        return self._solve_with("update_solve", ptr, x_out)
+
+    def update_device(self, dG=0, dA=0, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
+        """Raw device pointers (ints, e.g. torch.Tensor.data_ptr()); 0 keeps the group."""
+        count = self.batch if count is None else count
+        self._call("update_device", first, count, *[C.c_void_p(int(p) or None) for p in (dG, dA, dc, dh, db)])
+
+    def update_rhs_device(self, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
+        """update_rhs from raw device pointers (ints); 0 keeps the group.  Asynchronous, like update_device."""
+        count = self.batch if count is None else count
+        self._call("update_rhs_device", first, count, *[C.c_void_p(int(p) or None) for p in (dc, dh, db)])
+
+    def set_stream(self, stream_ptr: int):
+        self._call("set_stream", C.c_void_p(int(stream_ptr) or None))
+
+    def info(self):
+        arr = (Info * self.batch)()
+        self._call("info", arr)
+        return [arr[i].asdict() for i in range(self.batch)]
+
     def dims(self) -> dict:
         d = Dims()
-        _chk(_lib().eicos_batch_dims(self._h, C.byref(d)))
+        self._call("dims", C.byref(d))
         return d.asdict()
 
     def kernel_build(self) -> str:
@@ -442,103 +464,35 @@ class BatchSolver:
         _chk(_lib().eicos_debug_pattern(self._h, _ip(perm), _ip(Lp), _ip(Li)))
         return perm[: d["dim_K"]], Lp, Li[: d["nnzL"]]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib().eicos_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _mchk(rc):
     if rc != 0:
         raise RuntimeError(f"eicos_amd error {rc}: {_lib().eicos_multi_last_error().decode()}")
 
 
-class MultiBatchSolver:
+class MultiBatchSolver(_Solver):
     """One sparsity pattern, `batch` instances in contiguous shards over `device_ids` (eicos_multi_* of include/eicos_amd.h):
     ONE process drives every listed GPU, one handle + stream per list entry, no collective.  Arrays are [batch, ...] in global
     instance order; a device may be listed more than once (its shards run concurrently on that GPU)."""
+    _prefix, _error = "eicos_multi_", "eicos_multi_last_error"
 
     def __init__(self, pat, batch: int, device_ids):
-        L = _lib()
         self.pat, self.batch = pat, int(batch)
-        self._keep = [np.ascontiguousarray(a, dtype=np.int32) for a in (pat.q, pat.Gjc, pat.Gir, pat.Ajc, pat.Air)]
-        q, Gjc, Gir, Ajc, Air = self._keep
+        self._keep, ptrs = _pattern_ptrs(pat)
         dev = np.ascontiguousarray(device_ids, dtype=np.int32)
         h = C.c_void_p()
-        _mchk(L.eicos_multi_create(pat.n, pat.m, pat.p, pat.l, pat.ncones, _ip(q) if pat.ncones else None,
-                                   _ip(Gjc) if pat.m > 0 else None, _ip(Gir) if pat.m > 0 else None,
-                                   _ip(Ajc) if pat.p > 0 else None, _ip(Air) if pat.p > 0 else None,
-                                   self.batch, _ip(dev), len(dev), C.byref(h)))
+        _mchk(_lib().eicos_multi_create(pat.n, pat.m, pat.p, pat.l, pat.ncones, *ptrs, self.batch, _ip(dev), len(dev), C.byref(h)))
         self._h = h
-
-    def update(self, Gpr=None, Apr=None, c=None, h=None, b=None, first: int = 0, count: int | None = None):
-        """Host arrays shaped [count, ...]; None keeps the group (reference semantics)."""
-        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (Gpr, Apr, c, h, b)]
-        if count is None:
-            count = next((a.shape[0] for a in arrs if a is not None and a.ndim == 2), self.batch)
-        ptr = [(_dp(a) if (a is not None and a.size) else (_dp(np.zeros(1)) if a is not None else None)) for a in arrs]
-        _mchk(_lib().eicos_multi_update(self._h, first, count, *ptr))
 
     def update_device(self, src_device: int, dG=0, dA=0, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
         """Raw pointers into the HBM of GPU `src_device` (arrays [count, ...]); 0 keeps the group."""
         count = self.batch if count is None else count
-        _mchk(_lib().eicos_multi_update_device(self._h, int(src_device), first, count, *[C.c_void_p(int(p) or None) for p in (dG, dA, dc, dh, db)]))
-
-    def update_rhs(self, c=None, h=None, b=None, first: int = 0, count: int | None = None):
-        """BatchSolver.update_rhs over the shards (global instance order)."""
-        if count is None:
-            count = next((np.shape(a)[0] for a in (c, h, b) if a is not None and np.ndim(a) == 2), self.batch)
-        _keep, ptr = _rhs_ptrs(self.pat, count, c, h, b)
-        _mchk(_lib().eicos_multi_update_rhs(self._h, first, count, *ptr))
+        self._call("update_device", int(src_device), first, count, *[C.c_void_p(int(p) or None) for p in (dG, dA, dc, dh, db)])
 
     def update_rhs_device(self, src_device: int, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
         """update_rhs from raw pointers into the HBM of GPU `src_device` (arrays [count, ...]); 0 keeps the group.  Asynchronous."""
         count = self.batch if count is None else count
-        _mchk(_lib().eicos_multi_update_rhs_device(self._h, int(src_device), first, count, *[C.c_void_p(int(p) or None) for p in (dc, dh, db)]))
-
-    def update_rhs_solve(self, c=None, h=None, b=None, x_out=None):
-        """BatchSolver.update_rhs_solve on every shard, concurrently.  Returns the exit codes."""
-        _keep, ptr = _rhs_ptrs(self.pat, self.batch, c, h, b)
-        if x_out is not None:
-            assert x_out.dtype == np.float64 and x_out.flags.c_contiguous and x_out.shape == (self.batch, self.pat.n)
-        codes = np.zeros(self.batch, np.int32)
-        _mchk(_lib().eicos_multi_update_rhs_solve(self._h, *ptr, _dp(x_out) if (x_out is not None and x_out.size) else None, _ip(codes)))
-        return codes
-
-    def solve(self):
-        codes = np.zeros(self.batch, np.int32)
-        _mchk(_lib().eicos_multi_solve(self._h, _ip(codes)))
-        return codes
-
-    def solve_async(self):
-        _mchk(_lib().eicos_multi_solve_async(self._h))
-
-    def sync(self):
-        _mchk(_lib().eicos_multi_sync(self._h))
-
-    def solution(self):
-        x = np.zeros((self.batch, self.pat.n))
-        if self.pat.n:
-            _mchk(_lib().eicos_multi_solution(self._h, _dp(x)))
-        return x
-
-    def duals(self):
-        pat = self.pat
-        y, z, s = np.zeros((self.batch, pat.p)), np.zeros((self.batch, pat.m)), np.zeros((self.batch, pat.m))
-        _mchk(_lib().eicos_multi_duals(self._h, _dp(y) if pat.p else None, _dp(z) if pat.m else None, _dp(s) if pat.m else None))
-        return y, z, s
-
-    def info_arrays(self):
-        arr = (Info * self.batch)()
-        _mchk(_lib().eicos_multi_info(self._h, arr))
-        raw = np.frombuffer(arr, dtype=np.dtype([(k, "f8" if t is C.c_double else "i4") for k, t in Info._fields_]))
-        return {k: raw[k].copy() for k in raw.dtype.names}
+        self._call("update_rhs_device", int(src_device), first, count, *[C.c_void_p(int(p) or None) for p in (dc, dh, db)])
 
     def shards(self):
         """[(first, count, device)] of every shard."""
@@ -578,43 +532,22 @@ class MultiBatchSolver:
         _mchk(_lib().eicos_multi_last_solve_ms(self._h, C.byref(mx), per))
         return float(mx.value), [float(v) for v in per]
 
-    def set_warm_start(self, shift: float):
-        _mchk(_lib().eicos_multi_set_warm_start(self._h, float(shift)))
 
-    def set_dynamic_regularization(self, delta: float, eps: float):
-        _mchk(_lib().eicos_multi_set_dynamic_regularization(self._h, float(delta), float(eps)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib().eicos_multi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _host_check(fn, keys, pat, seed, order_mode):
+    _keep, ptrs = _pattern_ptrs(pat)
+    st = np.zeros(8, np.int32)
+    r = fn(pat.n, pat.m, pat.p, pat.ncones, *ptrs, seed, order_mode, _ip(st))
+    return float(r), dict(zip(keys, (int(v) for v in st)))
 
 
 def host_check_tiles(pat, seed: int = 1, order_mode: int = -1, hybrid: bool = False):
     """Host-only check of the tile (dense-front) plan, or of the hybrid plan (scalar programs + tiles on the top block
     of the tree; residual -10 = the pattern does not qualify) -- no GPU: returns (relative residual, stats dict)."""
-    q, Gjc, Gir, Ajc, Air = [np.ascontiguousarray(a, dtype=np.int32) for a in (pat.q, pat.Gjc, pat.Gir, pat.Ajc, pat.Air)]
-    st = np.zeros(8, np.int32)
     fn = _lib().eicos_debug_host_check_hybrid if hybrid else _lib().eicos_debug_host_check_tiles
-    r = fn(pat.n, pat.m, pat.p, pat.ncones, _ip(q) if pat.ncones else None,
-                                            _ip(Gjc) if pat.m else None, _ip(Gir) if pat.m else None,
-                                            _ip(Ajc) if pat.p else None, _ip(Air) if pat.p else None, seed, order_mode, _ip(st))
-    keys = ("dim_K", "nnzK", "nnzL", "block_levels", "tile_pairs", "order_mode", "blocks", "tiles")
-    return float(r), dict(zip(keys, (int(v) for v in st)))
+    return _host_check(fn, ("dim_K", "nnzK", "nnzL", "block_levels", "tile_pairs", "order_mode", "blocks", "tiles"), pat, seed, order_mode)
 
 
 def host_check(pat, seed: int = 1, order_mode: int = -1):
     """Host-only check of the symbolic analysis (no GPU): returns (relative residual, stats dict)."""
-    q, Gjc, Gir, Ajc, Air = [np.ascontiguousarray(a, dtype=np.int32) for a in (pat.q, pat.Gjc, pat.Gir, pat.Ajc, pat.Air)]
-    st = np.zeros(8, np.int32)
-    r = _lib().eicos_debug_host_check(pat.n, pat.m, pat.p, pat.ncones, _ip(q) if pat.ncones else None,
-                                      _ip(Gjc) if pat.m else None, _ip(Gir) if pat.m else None,
-                                      _ip(Ajc) if pat.p else None, _ip(Air) if pat.p else None, seed, order_mode, _ip(st))
     keys = ("dim_K", "nnzK", "nnzL", "nlevels", "factor_pairs", "order_mode", "max_row", "max_col")
-    return float(r), dict(zip(keys, (int(v) for v in st)))
+    return _host_check(_lib().eicos_debug_host_check, keys, pat, seed, order_mode)

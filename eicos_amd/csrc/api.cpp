@@ -28,6 +28,7 @@
 #include "plans.hpp"
 #include "tiles.hpp"
 #include "envknob.hpp"
+#include "internal.hpp"
 
 using namespace eicos;
 // Workgroups per CU for a batch, at most `max_r`: the cheapest estimate of the launch's duration wins.
@@ -94,7 +95,7 @@ struct eicos_batch {
     // while the host copies chunk k out.  pin_ev[i]: the last GPU work that touches pin[i].
     double *pin[2] = {nullptr, nullptr}; size_t pin_doubles = 0;
     hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_busy[2] = {false, false};
-    int last_update_path = 0; // how the most recent host/peer updateData moved its inputs: 1 pinned bounce, 2 zero-copy (pinned source), 3 peer zero-copy, 4 peer staged copies, 5 fused into the solve launch
+    int last_update_path = 0; // how the most recent host/peer updateData moved its inputs: 1 pinned bounce, 2 zero-copy (pinned source), 3 peer zero-copy, 4 peer staged copies, 5 fused into the solve launch, 6 the same with pageable arrays staged while the kernel runs
     int *d_flag = nullptr;   // debug hooks
     double warm_shift = 0.; // > 0: warm start (eicos_batch_set_warm_start)
     double dyn_delta = 0., dyn_eps = 0.; // > 0: dynamic regularisation (eicos_batch_set_dynamic_regularization)
@@ -108,7 +109,6 @@ struct eicos_batch {
     long n_solve_rec = 0, n_update_rec = 0;
     hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr, ev_u0 = nullptr, ev_u1 = nullptr;
     bool solve_timed = false, update_timed = false;
-    bool in_chunked_update = false; // eicos_batch_update records ev_u0/ev_u1 around ALL of its chunks
     int64_t npairs = 0;
     std::vector<int> posB; // CSC entry of L -> slot in the backward value array
     int ub_len = 1;        // length of that array (plan slots + dummy, + the dense apex image)
@@ -1060,36 +1060,19 @@ static int next_events(hipEvent_t (*ring)[2], long &count, hipEvent_t &e0, hipEv
     e0 = slot[0]; e1 = slot[1]; count++;
     return EICOS_OK;
 }
+// One updateData call = one pair of the update ring: ev_u0, the call's kernels, ev_u1 on the handle's stream.  The public entry points and
+// the chunk loops wrap their whole body in this pair; the function that launches the kernel for a row range (launch_range) records nothing.
 static int begin_update_timing(eicos_batch *h) {
     int rc = next_events(h->ring_u, h->n_update_rec, h->ev_u0, h->ev_u1);
     if (rc != EICOS_OK) return rc;
     HIP_TRY(hipEventRecord(h->ev_u0, h->stream));
     return EICOS_OK;
 }
-
-int eicos_batch_update_device(eicos_batch *h, int first, int count, const double *dG, const double *dA,
-                              const double *dc, const double *dh, const double *db) {
-    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
-    if (first < 0 || count < 0 || first + count > h->batch) return fail(EICOS_E_INVALID, "instance range out of bounds");
-    if (dG && !dh && h->dp.m > 0) return fail(EICOS_E_INVALID, "Gpr given without h");
-    if (dA && !db && h->dp.p > 0) return fail(EICOS_E_INVALID, "Apr given without b");
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->in_chunked_update) { const int rc = begin_update_timing(h); if (rc != EICOS_OK) return rc; }
-    HIP_TRY(launch_update(h->pslot, h->d_inst, first, count, dG, dA, dc, dh, db, h->d_scratch, std::min(count, h->upd_grid), h->upd_lds, h->upd_vals_lds, h->stream));
-    if (!h->in_chunked_update) { HIP_TRY(hipEventRecord(h->ev_u1, h->stream)); h->update_timed = true; }
-    return EICOS_OK;
-}
-
-// right-hand-side-only updateData (kernels.hip: rhs_instance): the given vectors divided by every instance's stored scalings; A, G and the
-// equilibration stay as they are
-int eicos_batch_update_rhs_device(eicos_batch *h, int first, int count, const double *dc, const double *dh, const double *db) {
-    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
-    if (first < 0 || count < 0 || first + count > h->batch) return fail(EICOS_E_INVALID, "instance range out of bounds");
-    HIP_TRY(hipSetDevice(h->device));
-    const int width = (dc ? h->dp.n : 0) + (dh ? h->dp.m : 0) + (db ? h->dp.p : 0);
-    if (!h->in_chunked_update) { const int rc = begin_update_timing(h); if (rc != EICOS_OK) return rc; }
-    HIP_TRY(launch_update_rhs(h->pslot, h->d_inst, first, count, dc, dh, db, width, h->stream));
-    if (!h->in_chunked_update) { HIP_TRY(hipEventRecord(h->ev_u1, h->stream)); h->update_timed = true; }
+// rc: what the body between the two gave (a failed call records no end and leaves update_timed as it was)
+static int end_update_timing(eicos_batch *h, int rc) {
+    if (rc != EICOS_OK) return rc;
+    HIP_TRY(hipEventRecord(h->ev_u1, h->stream));
+    h->update_timed = true;
     return EICOS_OK;
 }
 
@@ -1186,28 +1169,30 @@ class CopyPool {
     std::mutex mu_; std::condition_variable cv_;
 };
 
-// Is `p` host memory the GPU can address directly (hipHostMalloc / hipHostRegister / eicos_host_alloc)?  Then kernels read or write it
-// in place over PCIe and no bounce copy is needed.
-// 0 = pageable (or managed) host-addressable memory, 1 = pinned / registered host memory, 2 = device memory
-int pointer_kind(const void *p) {
-    if (!p) return 0;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return 0; } // (plain malloc memory: "invalid value")
-    if (a.type == hipMemoryTypeHost) return 1;
-    if (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeArray) return 2;
-    return 0; // (managed memory is host-addressable: it takes the bounce path like pageable memory)
-}
-// Is the WHOLE extent [p, p + bytes) pinned / registered host memory?  The kernels read (updateData) or the copy engine writes (results) every byte of
-// it in place, so the first byte alone does not decide: a pointer into a registered buffer with a count that runs past its end, or a buffer
-// registered a second time with a larger size (hipHostRegister reports "already registered" and maps nothing new), would be a GPU page
-// fault instead of an error code.  First byte, last byte and one probe per 2 MB in between (a lookup costs about a microsecond).
-bool is_pinned_host(const void *p, size_t bytes) {
-    if (pointer_kind(p) != 1) return false;
-    if (bytes <= 1) return true;
+// What kind of memory the extent [p, p + bytes) is -- the one place that asks the runtime:
+//   MEM_DEVICE  : the first byte is device memory
+//   MEM_PINNED  : the WHOLE extent is host memory the GPU addresses directly (hipHostMalloc / hipHostRegister / eicos_host_alloc): kernels read
+//                 or write it in place over PCIe and no bounce copy is needed
+//   MEM_PAGEABLE: everything else (managed memory is host-addressable: it takes the bounce path like pageable memory), partly pinned extents included
+// The kernels read (updateData) or the copy engine writes (results) every byte of a pinned extent in place, so the first byte alone does not
+// decide: a pointer into a registered buffer with a count that runs past its end, or a buffer registered a second time with a larger size
+// (hipHostRegister reports "already registered" and maps nothing new), would be a GPU page fault instead of an error code.  First byte,
+// last byte and one probe per 2 MB in between (a lookup costs about a microsecond).
+enum MemKind { MEM_PAGEABLE = 0, MEM_PINNED = 1, MEM_DEVICE = 2 };
+MemKind memory_kind(const void *p, size_t bytes) {
+    auto probe = [](const void *q) {
+        hipPointerAttribute_t a;
+        if (hipPointerGetAttributes(&a, q) != hipSuccess) { (void)hipGetLastError(); return MEM_PAGEABLE; } // (plain malloc memory: "invalid value")
+        if (a.type == hipMemoryTypeHost) return MEM_PINNED;
+        return (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeArray) ? MEM_DEVICE : MEM_PAGEABLE;
+    };
+    if (!p) return MEM_PAGEABLE;
+    const MemKind first = probe(p);
+    if (first != MEM_PINNED || bytes <= 1) return first;
     const char *b = (const char *)p;
-    if (pointer_kind(b + bytes - 1) != 1) return false;
-    for (size_t o = 2u << 20; o < bytes - 1; o += 2u << 20) if (pointer_kind(b + o) != 1) return false;
-    return true;
+    if (probe(b + bytes - 1) != MEM_PINNED) return MEM_PAGEABLE;
+    for (size_t o = 2u << 20; o < bytes - 1; o += 2u << 20) if (probe(b + o) != MEM_PINNED) return MEM_PAGEABLE;
+    return MEM_PINNED;
 }
 // the handle's two pinned bounce buffers hold at least `doubles` each
 int ensure_pin(eicos_batch *h, size_t doubles) {
@@ -1244,7 +1229,7 @@ int eicos_host_register(void *p, size_t bytes) {
     const hipError_t e = hipHostRegister(p, bytes, hipHostRegisterDefault);
     if (e == hipErrorHostMemoryAlreadyRegistered) { // fine only if the existing registration covers the whole range asked for
         (void)hipGetLastError();
-        if (is_pinned_host(p, bytes)) return EICOS_OK;
+        if (memory_kind(p, bytes) == MEM_PINNED) return EICOS_OK;
         return fail(EICOS_E_INVALID, "eicos_host_register: the pointer is already registered with a SMALLER extent (unregister it first)");
     }
     if (e != hipSuccess) return fail(EICOS_E_HIP, std::string("hipHostRegister: ") + hipGetErrorString(e));
@@ -1256,136 +1241,194 @@ int eicos_host_unregister(void *p) {
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(EICOS_E_HIP, std::string("hipHostUnregister: ") + hipGetErrorString(e)); }
     return EICOS_OK;
 }
-int eicos_batch_last_update_path(eicos_batch *h) { return h ? h->last_update_path : fail(EICOS_E_INVALID, "NULL handle"); }
 
-// updateData from buffers that are not in the handle's HBM: host memory (src_dev < 0) or the HBM of another GPU (src_dev = that device,
-// eicos_multi_update_device).
-//   host, pageable : rows go through the two pinned bounce buffers in chunks -- the host copies chunk k + 1 in (CopyPool) while the
-//                    updateData kernel of chunk k reads its inputs straight from the other buffer over PCIe; returns when the last chunk
-//                    has been COPIED (the caller's arrays are free again), the kernels are still in flight on the handle's stream
-//   host, pinned   : (every given array addressable by the GPU) ONE kernel launch reads the caller's arrays in place; the call
-//                    waits for it, so that the caller may overwrite them on return -- the reference's updateData is synchronous too
-//   peer, access on: the kernel reads the other GPU's HBM in place over xGMI (asynchronous, like eicos_batch_update_device)
-//   peer, no access: hipMemcpyPeerAsync into a device staging buffer, chunk by chunk
-// rhs = 1: the right-hand-side-only update (G, A must be NULL; h and b are read on their own) over the same paths.
-int eicos_internal_update_staged(eicos_batch *h, int first, int count, const double *G, const double *A,
-                                 const double *c, const double *hh, const double *b, int src_dev, int rhs) {
+// ---- updateData: one description of a call's inputs ----------------------------------------------------------------------
+// Everything an updateData call is given, validated once (take_inputs): the five groups as the kernels read them, their widths, and --
+// for the entry points that decide by it -- what kind of memory each given array is.  Whoever holds one needs to know neither the
+// h / b rule nor the widths nor how kinds are found.
+namespace {
+struct UpdateInputs {
+    eicos_batch *h;
+    int first, count;
+    bool rhs;             // the right-hand-side-only update (G, A not given)
+    const double *src[5]; // G, A, c, h, b, rows of `count` instances; NULL keeps the group
+    size_t w[5];          // doubles per instance
+    MemKind kind[5];      // of the arrays that hold data, when the entry point asked for kinds
+    size_t per;           // doubles per instance over the given groups
+    bool holds_data(int k) const { return src[k] && w[k]; }
+    bool any(MemKind m) const { for (int k = 0; k < 5; k++) if (holds_data(k) && kind[k] == m) return true; return false; }
+    bool all(MemKind m) const { for (int k = 0; k < 5; k++) if (holds_data(k) && kind[k] != m) return false; return true; }
+};
+struct Staging { // where the two staged paths (update_in_chunks) differ
+    std::function<int(int k, double *&area)> area;                        // the staging area of chunk k, free to be overwritten
+    std::function<int(double *dst, const double *src, size_t bytes)> put; // rows of one array into it
+    std::function<int(int k)> launched;                                   // behind chunk k's launch: what orders the reuse of its area
+};
+} // namespace
+
+// kinds: classify the given arrays (the host entry points and eicos_batch_update_solve; the device and peer forms take the caller's word)
+static int take_inputs(UpdateInputs &in, eicos_batch *h, int first, int count, const double *G, const double *A,
+                       const double *c, const double *hh, const double *b, bool rhs, bool kinds) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     if (first < 0 || count < 0 || first + count > h->batch) return fail(EICOS_E_INVALID, "instance range out of bounds");
     const DevPat &D = h->dp;
     if (G && !hh && D.m > 0) return fail(EICOS_E_INVALID, "Gpr given without h");
     if (A && !b && D.p > 0) return fail(EICOS_E_INVALID, "Apr given without b");
     HIP_TRY(hipSetDevice(h->device));
-    if (count == 0) return EICOS_OK;
     // (h is read only with Gpr, b only with Apr: reference src/eicos.cpp:2053-2074; the right-hand-side-only update reads them on their own)
-    const double *hv = (G || rhs) ? hh : nullptr, *bv = (A || rhs) ? b : nullptr;
-    auto launch = [&](int f, int cnt, const double *dG, const double *dA, const double *dc, const double *dh, const double *db) {
-        return rhs ? eicos_batch_update_rhs_device(h, f, cnt, dc, dh, db) : eicos_batch_update_device(h, f, cnt, dG, dA, dc, dh, db);
+    in = UpdateInputs{h, first, count, rhs, {G, A, c, (G || rhs) ? hh : nullptr, (A || rhs) ? b : nullptr},
+                      {(size_t)D.nnzG, (size_t)D.nnzA, (size_t)D.n, (size_t)D.m, (size_t)D.p}, {}, 0};
+    for (int k = 0; k < 5; k++) {
+        if (in.src[k]) in.per += in.w[k];
+        if (kinds && in.holds_data(k)) in.kind[k] = memory_kind(in.src[k], (size_t)count * in.w[k] * sizeof(double));
+    }
+    return EICOS_OK;
+}
+
+// the updateData kernel (full or right-hand-side-only, kernels.hip: rhs_instance) of rows [first, first + count) on five pointers the GPU addresses
+static int launch_range(const UpdateInputs &in, int first, int count, const double *const p[5]) {
+    eicos_batch *h = in.h;
+    if (in.rhs) HIP_TRY(launch_update_rhs(h->pslot, h->d_inst, first, count, p[2], p[3], p[4], (int)in.per, h->stream));
+    else HIP_TRY(launch_update(h->pslot, h->d_inst, first, count, p[0], p[1], p[2], p[3], p[4], h->d_scratch, std::min(count, h->upd_grid), h->upd_lds, h->upd_vals_lds, h->stream));
+    return EICOS_OK;
+}
+
+// one launch on the caller's pointers; path > 0 is left as the witness of eicos_batch_last_update_path
+static int update_in_place(const UpdateInputs &in, int path) {
+    if (path) in.h->last_update_path = path;
+    int rc = begin_update_timing(in.h);
+    if (rc == EICOS_OK) rc = launch_range(in, in.first, in.count, in.src);
+    return end_update_timing(in.h, rc);
+}
+
+// The two staged paths: rows travel in chunks of `chunk` instances through a staging area the GPU addresses, the given arrays of a chunk
+// packed behind each other (+ 8 doubles of padding per array keep every row 64-byte aligned), one launch per chunk on the packed pointers.
+static size_t staging_doubles(const UpdateInputs &in, int chunk) { return (size_t)chunk * (in.per + 5 * 8); }
+static int update_in_chunks(const UpdateInputs &in, int chunk, const Staging &st) {
+    int rc = begin_update_timing(in.h), k = 0;
+    for (int o = 0; o < in.count && rc == EICOS_OK; o += chunk, k++) {
+        const int cnt = std::min(chunk, in.count - o);
+        const double *packed[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        double *at = nullptr;
+        rc = st.area(k, at);
+        for (int q = 0; q < 5 && rc == EICOS_OK; q++) {
+            if (!in.src[q]) continue;
+            packed[q] = at;
+            if (in.w[q]) rc = st.put(at, in.src[q] + (size_t)o * in.w[q], (size_t)cnt * in.w[q] * sizeof(double));
+            at += (size_t)cnt * in.w[q] + 8;
+        }
+        if (rc == EICOS_OK) rc = launch_range(in, in.first + o, cnt, packed);
+        if (rc == EICOS_OK) rc = st.launched(k);
+    }
+    return end_update_timing(in.h, rc);
+}
+
+//   peer, access on: the kernel reads the other GPU's HBM in place over xGMI (asynchronous, like eicos_batch_update_device)
+//   peer, no access: hipMemcpyPeerAsync into a device staging buffer, chunk by chunk
+static int peer_update(const UpdateInputs &in, int src_dev) {
+    eicos_batch *h = in.h;
+    int can = 0;
+    if (src_dev == h->device) can = 1;
+    else if (hipDeviceCanAccessPeer(&can, h->device, src_dev) != hipSuccess) { (void)hipGetLastError(); can = 0; }
+    if (can && src_dev != h->device) {
+        const hipError_t e = hipDeviceEnablePeerAccess(src_dev, 0);
+        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) can = 0;
+        (void)hipGetLastError();
+    }
+    if (can && !env_knob("EICOS_PEER_STAGED", 0, 0, 1)) return update_in_place(in, 3);
+    // no peer access: staged peer copies, one chunk at a time through the device staging buffer
+    h->last_update_path = 4;
+    const int chunk = 256;
+    const size_t need = staging_doubles(in, std::min(in.count, chunk));
+    if (need > h->stage_doubles) {
+        if (h->d_stage) { HIP_TRY(hipStreamSynchronize(h->stream)); (void)hipFree(h->d_stage); h->d_stage = nullptr; h->stage_doubles = 0; }
+        HIP_TRY(hipMalloc(&h->d_stage, need * sizeof(double)));
+        h->stage_doubles = need;
+    }
+    Staging st;
+    st.area = [&](int, double *&area) -> int { area = h->d_stage; return EICOS_OK; };
+    st.put = [&](double *dst, const double *src, size_t bytes) -> int {
+        return hipMemcpyPeerAsync(dst, h->device, src, src_dev, bytes, h->stream) == hipSuccess ? EICOS_OK : fail(EICOS_E_HIP, "hipMemcpyPeerAsync failed");
     };
-    struct Arr { const double *src; size_t w; };
-    const Arr arr[5] = {{G, (size_t)D.nnzG}, {A, (size_t)D.nnzA}, {c, (size_t)D.n}, {hv, (size_t)D.m}, {bv, (size_t)D.p}};
-    size_t per = 0; // doubles per instance that are actually given (+ 8 of padding per array keeps every row 64-byte aligned)
-    for (const Arr &a : arr) if (a.src) per += a.w;
-    if (per == 0) { // nothing given: everything is kept -- still a valid updateData (re-equilibrates what is there; the right-hand-side-only one changes nothing)
-        return launch(first, count, nullptr, nullptr, nullptr, nullptr, nullptr);
-    }
-    auto whole_range = [&](int path) { // one launch on the caller's pointers
-        h->last_update_path = path;
-        return launch(first, count, G, A, c, hv, bv);
+    st.launched = [&](int) -> int { // the staging buffer is reused by the next chunk
+        return hipStreamSynchronize(h->stream) == hipSuccess ? EICOS_OK : fail(EICOS_E_HIP, "stream sync failed in update");
     };
-    if (src_dev >= 0) {
-        int can = 0;
-        if (src_dev == h->device) can = 1;
-        else if (hipDeviceCanAccessPeer(&can, h->device, src_dev) != hipSuccess) { (void)hipGetLastError(); can = 0; }
-        if (can && src_dev != h->device) {
-            const hipError_t e = hipDeviceEnablePeerAccess(src_dev, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) can = 0;
-            (void)hipGetLastError();
-        }
-        if (can && !env_knob("EICOS_PEER_STAGED", 0, 0, 1)) return whole_range(3);
-        // no peer access: staged peer copies, one chunk at a time through the device staging buffer
-        h->last_update_path = 4;
-        const int chunk = 256;
-        const size_t need = (size_t)std::min(count, chunk) * (per + 5 * 8);
-        if (need > h->stage_doubles) {
-            if (h->d_stage) { HIP_TRY(hipStreamSynchronize(h->stream)); (void)hipFree(h->d_stage); h->d_stage = nullptr; h->stage_doubles = 0; }
-            HIP_TRY(hipMalloc(&h->d_stage, need * sizeof(double)));
-            h->stage_doubles = need;
-        }
-        int rc = EICOS_OK;
-        { const int rc0 = begin_update_timing(h); if (rc0 != EICOS_OK) return rc0; }
-        h->in_chunked_update = true;
-        for (int o = 0; o < count && rc == EICOS_OK; o += chunk) {
-            const int cnt = std::min(chunk, count - o);
-            const double *dptr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-            double *at = h->d_stage;
-            for (int k = 0; k < 5 && rc == EICOS_OK; k++) {
-                if (!arr[k].src) continue;
-                dptr[k] = at;
-                if (arr[k].w && hipMemcpyPeerAsync(at, h->device, arr[k].src + (size_t)o * arr[k].w, src_dev, (size_t)cnt * arr[k].w * sizeof(double), h->stream) != hipSuccess)
-                    rc = fail(EICOS_E_HIP, "hipMemcpyPeerAsync failed");
-                at += (size_t)cnt * arr[k].w + 8;
-            }
-            if (rc == EICOS_OK) rc = launch(first + o, cnt, dptr[0], dptr[1], dptr[2], dptr[3], dptr[4]);
-            // the staging buffer is reused by the next chunk
-            if (rc == EICOS_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(EICOS_E_HIP, "stream sync failed in update");
-        }
-        h->in_chunked_update = false;
-        if (rc == EICOS_OK) { HIP_TRY(hipEventRecord(h->ev_u1, h->stream)); h->update_timed = true; }
-        return rc;
-    }
-    // ---- host pointers ----
-    bool all_pinned = true, any_device = false;
-    for (const Arr &a : arr) if (a.src && a.w) {
-        const int kind = pointer_kind(a.src);
-        if (kind == 2) any_device = true;
-        // pinned in place only when EVERY byte the kernel will read is mapped (else the bounce path, which reads with the host's own loads)
-        if (kind != 1 || !is_pinned_host(a.src, (size_t)count * a.w * sizeof(double))) all_pinned = false;
-    }
+    return update_in_chunks(in, chunk, st);
+}
+
+//   host, pageable : rows go through the two pinned bounce buffers in chunks -- the host copies chunk k + 1 in (CopyPool) while the
+//                    updateData kernel of chunk k reads its inputs straight from the other buffer over PCIe; returns when the last chunk
+//                    has been COPIED (the caller's arrays are free again), the kernels are still in flight on the handle's stream
+//   host, pinned   : (every given array addressable by the GPU) ONE kernel launch reads the caller's arrays in place; the call
+//                    waits for it, so that the caller may overwrite them on return -- the reference's updateData is synchronous too
+static int host_update(const UpdateInputs &in) {
+    eicos_batch *h = in.h;
     // a device pointer handed to the HOST-pointer entry point must not reach the bounce copy (a host memcpy from it would fault)
-    if (any_device) return fail(EICOS_E_INVALID, rhs ? "eicos_batch_update_rhs takes host pointers: an array lives in device memory (use eicos_batch_update_rhs_device)"
-                                                      : "eicos_batch_update takes host pointers: an array lives in device memory (use eicos_batch_update_device)");
-    if (all_pinned && !env_knob("EICOS_HOST_BOUNCE", 0, 0, 1)) {
-        const int rc = whole_range(2);
+    if (in.any(MEM_DEVICE)) return fail(EICOS_E_INVALID, in.rhs ? "eicos_batch_update_rhs takes host pointers: an array lives in device memory (use eicos_batch_update_rhs_device)"
+                                                                 : "eicos_batch_update takes host pointers: an array lives in device memory (use eicos_batch_update_device)");
+    // pinned in place only when EVERY byte the kernel will read is mapped (else the bounce path, which reads with the host's own loads)
+    if (in.all(MEM_PINNED) && !env_knob("EICOS_HOST_BOUNCE", 0, 0, 1)) {
+        const int rc = update_in_place(in, 2);
         if (rc != EICOS_OK) return rc;
         HIP_TRY(hipStreamSynchronize(h->stream)); // the caller may overwrite its arrays on return
         return EICOS_OK;
     }
     h->last_update_path = 1;
-    const size_t row = per + 5 * 8;
-    int chunk = (int)std::max<size_t>(16, PIN_CHUNK_BYTES / (row * sizeof(double)));
-    chunk = std::min(chunk, count);
-    if (count > chunk && count < 2 * chunk) chunk = (count + 1) / 2; // two even chunks rather than a long one and a stub
-    int rc = ensure_pin(h, (size_t)chunk * row);
+    int chunk = (int)std::max<size_t>(16, PIN_CHUNK_BYTES / (staging_doubles(in, 1) * sizeof(double)));
+    chunk = std::min(chunk, in.count);
+    if (in.count > chunk && in.count < 2 * chunk) chunk = (in.count + 1) / 2; // two even chunks rather than a long one and a stub
+    const int rc = ensure_pin(h, staging_doubles(in, chunk));
     if (rc != EICOS_OK) return rc;
-    rc = begin_update_timing(h);
-    if (rc != EICOS_OK) return rc;
-    h->in_chunked_update = true;
     CopyPool &pool = CopyPool::get();
-    int k = 0;
-    for (int o = 0; o < count && rc == EICOS_OK; o += chunk, k++) {
-        const int cnt = std::min(chunk, count - o), bi = k & 1;
-        if (h->pin_busy[bi]) { // the kernel that read this buffer two chunks ago (or an earlier call's) must have finished
-            if (hipEventSynchronize(h->pin_ev[bi]) != hipSuccess) { rc = fail(EICOS_E_HIP, "event sync failed in update"); break; }
-            h->pin_busy[bi] = false;
-        }
-        const double *dptr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        double *at = h->pin[bi];
-        for (int q = 0; q < 5; q++) {
-            if (!arr[q].src) continue;
-            dptr[q] = at;
-            if (arr[q].w) pool.copy(at, arr[q].src + (size_t)o * arr[q].w, (size_t)cnt * arr[q].w * sizeof(double));
-            at += (size_t)cnt * arr[q].w + 8;
-        }
-        rc = launch(first + o, cnt, dptr[0], dptr[1], dptr[2], dptr[3], dptr[4]); // reads the pinned buffer in place
-        if (rc == EICOS_OK) {
-            if (hipEventRecord(h->pin_ev[bi], h->stream) != hipSuccess) rc = fail(EICOS_E_HIP, "event record failed in update");
-            else h->pin_busy[bi] = true;
-        }
-    }
-    h->in_chunked_update = false;
-    if (rc == EICOS_OK) { HIP_TRY(hipEventRecord(h->ev_u1, h->stream)); h->update_timed = true; }
-    return rc;
+    Staging st;
+    st.area = [&](int k, double *&area) -> int { // the kernel that read this buffer two chunks ago (or an earlier call's) must have finished
+        const int bi = k & 1;
+        if (h->pin_busy[bi] && hipEventSynchronize(h->pin_ev[bi]) != hipSuccess) return fail(EICOS_E_HIP, "event sync failed in update");
+        h->pin_busy[bi] = false;
+        area = h->pin[bi];
+        return EICOS_OK;
+    };
+    st.put = [&](double *dst, const double *src, size_t bytes) -> int { pool.copy(dst, src, bytes); return EICOS_OK; };
+    st.launched = [&](int k) -> int { // (the launch reads the pinned buffer in place)
+        if (hipEventRecord(h->pin_ev[k & 1], h->stream) != hipSuccess) return fail(EICOS_E_HIP, "event record failed in update");
+        h->pin_busy[k & 1] = true;
+        return EICOS_OK;
+    };
+    return update_in_chunks(in, chunk, st);
+}
+
+// updateData from buffers that are not in the handle's HBM: host memory (src_dev < 0; `in` with kinds) or the HBM of another GPU
+// (src_dev = that device, eicos_multi_update_device), over the paths above.
+static int staged_update(const UpdateInputs &in, int src_dev) {
+    if (in.count == 0) return EICOS_OK;
+    // nothing given: everything is kept -- still a valid updateData (re-equilibrates what is there; the right-hand-side-only one changes nothing)
+    if (in.per == 0) return update_in_place(in, 0);
+    return src_dev >= 0 ? peer_update(in, src_dev) : host_update(in);
+}
+
+int eicos_batch_last_update_path(eicos_batch *h) { return h ? h->last_update_path : fail(EICOS_E_INVALID, "NULL handle"); }
+
+int eicos_batch_update_device(eicos_batch *h, int first, int count, const double *dG, const double *dA,
+                              const double *dc, const double *dh, const double *db) {
+    UpdateInputs in;
+    const int rc = take_inputs(in, h, first, count, dG, dA, dc, dh, db, false, false);
+    return rc != EICOS_OK ? rc : update_in_place(in, 0);
+}
+
+// right-hand-side-only updateData (kernels.hip: rhs_instance): the given vectors divided by every instance's stored scalings; A, G and the
+// equilibration stay as they are
+int eicos_batch_update_rhs_device(eicos_batch *h, int first, int count, const double *dc, const double *dh, const double *db) {
+    UpdateInputs in;
+    const int rc = take_inputs(in, h, first, count, nullptr, nullptr, dc, dh, db, true, false);
+    return rc != EICOS_OK ? rc : update_in_place(in, 0);
+}
+
+// rhs = 1: the right-hand-side-only update (G, A must be NULL; h and b are read on their own) over the same paths.
+int eicos_internal_update_staged(eicos_batch *h, int first, int count, const double *G, const double *A,
+                                 const double *c, const double *hh, const double *b, int src_dev, int rhs) {
+    UpdateInputs in;
+    const int rc = take_inputs(in, h, first, count, G, A, c, hh, b, rhs != 0, src_dev < 0);
+    return rc != EICOS_OK ? rc : staged_update(in, src_dev);
 }
 
 int eicos_batch_update(eicos_batch *h, int first, int count, const double *G, const double *A,
@@ -1425,7 +1468,8 @@ int eicos_batch_sync(eicos_batch *h) {
 static int fetch_rows(eicos_batch *h, double *dst, int off, int width) {
     if (!dst || width == 0) return EICOS_OK;
     const size_t wb = (size_t)width * sizeof(double), pitch = h->dp.inst_stride * sizeof(double);
-    if (is_pinned_host(dst, (size_t)h->batch * wb) || (pointer_kind(dst) != 1 && (size_t)h->batch * wb < (256u << 10))) {
+    // (a small result takes the one strided copy as well, unless it starts in pinned memory that ends before it does)
+    if (memory_kind(dst, (size_t)h->batch * wb) == MEM_PINNED || ((size_t)h->batch * wb < (256u << 10) && memory_kind(dst, 1) != MEM_PINNED)) {
         HIP_TRY(hipMemcpy2DAsync(dst, wb, h->d_inst + off, pitch, wb, (size_t)h->batch, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         return EICOS_OK;
@@ -1476,18 +1520,21 @@ int eicos_batch_info(eicos_batch *h, eicos_info *info) {
     return EICOS_OK;
 }
 
+// the exit codes of the batch out of eicos_batch_info (out: optional)
+static int exit_codes(eicos_batch *h, int *out) {
+    if (!out) return EICOS_OK;
+    std::vector<eicos_info> info(h->batch);
+    const int rc = eicos_batch_info(h, info.data());
+    for (int i = 0; rc == EICOS_OK && i < h->batch; i++) out[i] = info[i].exitcode;
+    return rc;
+}
+
 int eicos_batch_solve(eicos_batch *h, int *exitcodes) {
     int rc = eicos_batch_solve_async(h);
     if (rc != EICOS_OK) return rc;
     rc = eicos_batch_sync(h);
     if (rc != EICOS_OK) return rc;
-    if (exitcodes) {
-        std::vector<eicos_info> info(h->batch);
-        rc = eicos_batch_info(h, info.data());
-        if (rc != EICOS_OK) return rc;
-        for (int i = 0; i < h->batch; i++) exitcodes[i] = info[i].exitcode;
-    }
-    return EICOS_OK;
+    return exit_codes(h, exitcodes);
 }
 
 // updateData + solve in ONE call: the reference's updateData(double *...) followed by solve() (include/eicos.hpp:155-158) for the whole batch.
@@ -1496,54 +1543,48 @@ int eicos_batch_solve(eicos_batch *h, int *exitcodes) {
 // PCIe is the workgroups' loads, spread over the launch and hidden behind the other workgroups' compute -- a separate updateData kernel can
 // only run BEFORE the solve (the registers and the LDS of a CU are fully owned by its resident solve workgroups), so its transfer time adds to
 // every step.  x_out (optional, [batch][n]): pinned host / device memory is written by the kernel as each instance finishes; pageable memory
-// is filled by eicos_batch_solution afterwards.  Anything else (pageable inputs -- unless staging is switched on, below --, a handle without an
+// is filled by eicos_batch_solution afterwards (device memory, where the update is not fused, by a copy on the device).  Anything else (pageable inputs -- unless staging is switched on, below --, a handle without an
 // LDS vector, vectors beyond the in-register scaling accumulators) takes eicos_batch_update + eicos_batch_solve: same results, bit for bit, on
 // every path.
 // Synchronous; exitcodes optional.  rhs = true: the right-hand-side-only update (G, A NULL; h and b read on their own; no accumulator limit:
 // the fused form divides by the stored scalings, kernels.hip: rhs_instance), eicos_batch_update_rhs_solve.
 static int update_solve(eicos_batch *h, const double *G, const double *A, const double *c, const double *hh, const double *b,
                         double *x_out, int *exitcodes, bool rhs) {
-    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    UpdateInputs in;
+    int rc = take_inputs(in, h, 0, h ? h->batch : 0, G, A, c, hh, b, rhs, true);
+    if (rc != EICOS_OK) return rc;
     const DevPat &D = h->dp;
-    if (G && !hh && D.m > 0) return fail(EICOS_E_INVALID, "Gpr given without h");
-    if (A && !b && D.p > 0) return fail(EICOS_E_INVALID, "Apr given without b");
-    HIP_TRY(hipSetDevice(h->device));
-    // (h is read only with Gpr, b only with Apr: reference src/eicos.cpp:2053-2074; the right-hand-side-only update reads them on their own)
-    const double *hv = (G || rhs) ? hh : nullptr, *bv = (A || rhs) ? b : nullptr;
-    struct Arr { const double *src; size_t w; };
-    const Arr arr[5] = {{G, (size_t)D.nnzG}, {A, (size_t)D.nnzA}, {c, (size_t)D.n}, {hv, (size_t)D.m}, {bv, (size_t)D.p}};
-    auto gpu_addressable = [&](const void *ptr, size_t bytes) { const int k = pointer_kind(ptr); return k == 2 || (k == 1 && is_pinned_host(ptr, bytes)); };
     const bool fused = h->nlds >= 1 && (rhs || (D.n <= 8 * h->threads && D.p <= 8 * h->threads && D.m <= 16 * h->threads)) &&
                        env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
     // arrays the GPU cannot address (pageable memory) are STAGED: copied into the handle's pinned staging buffer while the kernel runs
-    bool staged[5] = {false, false, false, false, false};
-    size_t stage_need = 0;
-    for (int k = 0; k < 5; k++) if (arr[k].src && arr[k].w && !gpu_addressable(arr[k].src, (size_t)h->batch * arr[k].w * sizeof(double))) {
-        if (pointer_kind(arr[k].src) == 2) return fail(EICOS_E_INVALID, "an array straddles device memory");
-        staged[k] = true; stage_need += (size_t)h->batch * arr[k].w + 8;
-    }
-    const bool any_staged = stage_need > 0;
-    const bool x_direct = x_out && D.n > 0 && gpu_addressable(x_out, (size_t)h->batch * D.n * sizeof(double));
-    int rc;
+    const bool any_staged = in.any(MEM_PAGEABLE);
+    if (D.n == 0) x_out = nullptr;
+    const MemKind x_kind = memory_kind(x_out, (size_t)h->batch * D.n * sizeof(double));
     // (staging pageable arrays while the kernel runs is OFF by default: measured on five boxes against the bounce pipeline + solve it is
     // +5.7 ... -6.2 % -- the host's copy is the pace either way, and on a box with slow host cores the kernel's own PCIe pulls and flag polls
     // slow that copy further; EICOS_FUSED_STAGED=1 under EICOS_EXPERIMENT=1 turns it on: docs/HISTORY.md A.11 item 9)
     if (!fused || (any_staged && !env_knob("EICOS_FUSED_STAGED", 0, 0, 1))) {
-        bool all_device = true; // (device arrays on a handle without the fused path: the device-pointer updateData)
-        for (int k = 0; k < 5; k++) if (arr[k].src && arr[k].w && pointer_kind(arr[k].src) != 2) all_device = false;
-        if (rhs) rc = all_device ? eicos_batch_update_rhs_device(h, 0, h->batch, c, hv, bv) : eicos_batch_update_rhs(h, 0, h->batch, c, hv, bv);
-        else rc = all_device ? eicos_batch_update_device(h, 0, h->batch, G, A, c, hh, b) : eicos_batch_update(h, 0, h->batch, G, A, c, hh, b);
+        // (device arrays on a handle without the fused path: the device-pointer updateData)
+        rc = in.all(MEM_DEVICE) ? update_in_place(in, 0) : staged_update(in, -1);
         if (rc == EICOS_OK) rc = eicos_batch_solve_async(h);
         if (rc != EICOS_OK) return rc;
         rc = eicos_batch_sync(h);
         if (rc != EICOS_OK) return rc;
-        if (x_out && D.n > 0) { rc = fetch_rows(h, x_out, D.i_x, D.n); if (rc != EICOS_OK) return rc; }
+        if (x_kind == MEM_DEVICE) { // a result array in device memory: one strided copy on the device
+            const size_t wb = (size_t)D.n * sizeof(double);
+            HIP_TRY(hipMemcpy2DAsync(x_out, wb, h->d_inst + D.i_x, D.inst_stride * sizeof(double), wb, (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        } else if (x_out) { rc = fetch_rows(h, x_out, D.i_x, D.n); if (rc != EICOS_OK) return rc; }
     } else {
-        const double *ptr[5] = {G, A, c, hv, bv};
+        const double *ptr[5] = {in.src[0], in.src[1], in.src[2], in.src[3], in.src[4]};
+        bool staged[5];
+        size_t per = 0, stage_need = 0;
+        for (int k = 0; k < 5; k++) {
+            staged[k] = in.holds_data(k) && in.kind[k] == MEM_PAGEABLE;
+            if (staged[k]) { per += in.w[k]; stage_need += (size_t)h->batch * in.w[k] + 8; }
+        }
         // chunks of ~12 MB over the staged arrays: the copy pool splits an array's share of a chunk into pieces of >= 1 MB over its threads, so
         // a chunk must be large enough to keep them busy and small enough that the first workgroups start after a fraction of the whole copy
-        size_t per = 0;
-        for (int k = 0; k < 5; k++) if (staged[k]) per += arr[k].w;
         const int chunk = any_staged ? (int)std::max<size_t>(8, std::min<size_t>((size_t)h->batch, (12u << 20) / std::max<size_t>(per * sizeof(double), 1))) : h->batch;
         const int nchunks = (h->batch + chunk - 1) / chunk;
         if (any_staged) {
@@ -1562,15 +1603,14 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
             }
             if (!h->d_err) { HIP_TRY(hipMalloc((void **)&h->d_err, sizeof(int))); HIP_TRY(hipMemset(h->d_err, 0, sizeof(int))); }
             double *at = h->stage_pin;
-            for (int k = 0; k < 5; k++) if (staged[k]) { ptr[k] = at; at += (size_t)h->batch * arr[k].w + 8; }
+            for (int k = 0; k < 5; k++) if (staged[k]) { ptr[k] = at; at += (size_t)h->batch * in.w[k] + 8; }
             h->stage_seq++;
             if (h->stage_seq == 0) { std::memset(h->stage_flags, 0, (size_t)h->stage_nflags * sizeof(unsigned)); h->stage_seq = 1; } // (wrapped)
         }
         h->last_update_path = any_staged ? 6 : 5;
-        rc = begin_update_timing(h); // (an empty updateData interval in the timing ring: the work is inside the solve launch)
+        rc = end_update_timing(h, begin_update_timing(h)); // (an empty updateData interval in the timing ring: the work is inside the solve launch)
         if (rc != EICOS_OK) return rc;
-        HIP_TRY(hipEventRecord(h->ev_u1, h->stream)); h->update_timed = true;
-        h->fused = UpdArgs{ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], x_direct ? x_out : nullptr, rhs ? UPD_RHS : UPD_FULL,
+        h->fused = UpdArgs{ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], x_kind != MEM_PAGEABLE ? x_out : nullptr, rhs ? UPD_RHS : UPD_FULL,
                            any_staged ? h->stage_flags : nullptr, chunk, h->stage_seq, h->d_err};
         h->fused_pending = true;
         rc = eicos_batch_solve_async(h);
@@ -1580,7 +1620,7 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
             CopyPool &pool = CopyPool::get();
             for (int q = 0; q < nchunks; q++) {
                 const size_t r0 = (size_t)q * chunk, rows = std::min<size_t>((size_t)chunk, (size_t)h->batch - r0);
-                for (int k = 0; k < 5; k++) if (staged[k]) pool.copy(const_cast<double *>(ptr[k]) + r0 * arr[k].w, arr[k].src + r0 * arr[k].w, rows * arr[k].w * sizeof(double));
+                for (int k = 0; k < 5; k++) if (staged[k]) pool.copy(const_cast<double *>(ptr[k]) + r0 * in.w[k], in.src[k] + r0 * in.w[k], rows * in.w[k] * sizeof(double));
                 __atomic_store_n(&h->stage_flags[q], h->stage_seq, __ATOMIC_RELEASE); // (stream_copy ends with an sfence: the rows are visible before the flag)
             }
         }
@@ -1591,15 +1631,9 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
             HIP_TRY(hipMemcpy(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
             if (err) { HIP_TRY(hipMemset(h->d_err, 0, sizeof(int))); return fail(EICOS_E_HIP, "fused updateData: a workgroup timed out waiting for its staged rows"); }
         }
-        if (x_out && D.n > 0 && !x_direct) { rc = fetch_rows(h, x_out, D.i_x, D.n); if (rc != EICOS_OK) return rc; }
+        if (x_out && x_kind == MEM_PAGEABLE) { rc = fetch_rows(h, x_out, D.i_x, D.n); if (rc != EICOS_OK) return rc; }
     }
-    if (exitcodes) {
-        std::vector<eicos_info> info(h->batch);
-        rc = eicos_batch_info(h, info.data());
-        if (rc != EICOS_OK) return rc;
-        for (int i = 0; i < h->batch; i++) exitcodes[i] = info[i].exitcode;
-    }
-    return EICOS_OK;
+    return exit_codes(h, exitcodes);
 }
 
 int eicos_batch_update_solve(eicos_batch *h, const double *G, const double *A, const double *c, const double *hh, const double *b,

@@ -19,10 +19,7 @@
 #include <thread>
 #include <vector>
 
-extern "C" int eicos_internal_update_staged(eicos_batch *h, int first, int count, const double *G, const double *A,
-                                            const double *c, const double *hh, const double *b, int src_dev, int rhs);
-extern "C" int eicos_internal_device(const eicos_batch *h);
-extern "C" int eicos_internal_solve_span_ms(eicos_batch *from, eicos_batch *to, float *ms);
+#include "internal.hpp"
 
 namespace {
 // One persistent host thread per shard: blocking calls of the shards (symbolic analysis at creation, the chunked host-pointer

@@ -136,7 +136,8 @@ int eicos_batch_last_update_path(eicos_batch *hd);
  * copies the arrays chunk by chunk into a pinned staging buffer WHILE it runs, one flag per chunk, path 6: faster on some hosts, slower on
  * others, off by default).  x_out: optional [batch][n] result array
  * (pinned host / device memory is written by the kernel as instances finish).  Handles without an LDS vector (patterns too large for LDS)
- * run eicos_batch_update + eicos_batch_solve (+ eicos_batch_solution).  Results are bit-identical on every path.  exitcodes: optional [batch]. */
+ * run eicos_batch_update + eicos_batch_solve (+ eicos_batch_solution).  A device x_out is honoured on every branch: where the kernel does
+ * not write it, it is filled by one strided copy on the device.  Results are bit-identical on every path.  exitcodes: optional [batch]. */
 int eicos_batch_update_solve(eicos_batch *hd, const double *Gpr, const double *Apr, const double *c, const double *h, const double *b,
                              double *x_out, int *exitcodes);
 /* Same, DEVICE pointers (inputs already resident in HBM; no PCIe traffic). */

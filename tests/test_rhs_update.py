@@ -227,6 +227,21 @@ def test_fused_rhs_update_solve_is_bit_identical_to_update_rhs_then_solve(name, 
         g.update_rhs(c=d["c"])
         g.update_rhs_device(*dev)
         _assert_same(_outputs(g, g.solve()), out_ref, "update_rhs_device")
+        # without the fused path the same call takes the device-pointer update, and a device x_out is filled by a copy on the device
+        monkeypatch.setenv("EICOS_FUSED_UPDATE", "0")
+        dx = _device_arrays((np.zeros((B, pat.n)),))
+        try:
+            g.update_rhs(c=d["c"])
+            codes = np.zeros(B, np.int32)
+            assert L.eicos_batch_update_rhs_solve(g._h, *[C.cast(p_, C.POINTER(C.c_double)) for p_ in dev], C.cast(dx[0], C.POINTER(C.c_double)),
+                                                  codes.ctypes.data_as(C.POINTER(C.c_int))) == 0
+            xd = np.full((B, pat.n), np.nan)
+            assert L.hipMemcpy(xd.ctypes.data, dx[0], xd.nbytes, 2) == 0  # hipMemcpyDeviceToHost
+            _assert_same(_outputs(g, codes), out_ref, "device, not fused")
+            assert np.array_equal(xd, out_ref[1]) and np.array_equal(xd, g.solution())
+        finally:
+            _free_device(dx)
+            monkeypatch.delenv("EICOS_FUSED_UPDATE")
         # a device pointer handed to the host-pointer entry point is refused, naming the right call
         assert L.eicos_batch_update_rhs(g._h, 0, B, C.cast(dev[0], C.POINTER(C.c_double)), None, None) == -1
         assert b"eicos_batch_update_rhs_device" in L.eicos_last_error()
