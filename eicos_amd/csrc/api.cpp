@@ -849,6 +849,9 @@ static int launch_shape(Plan &pl, int batch, int device, Shape &sh) {
         }
     }
     const SolveBuild sbuild = solve_build(threads, sh.ldsres, sh.w2, sh.ubl);
+    // The two-waves-per-SIMD build with one LDS vector and one right-hand side keeps the parked refinement iterate in registers of the owning
+    // threads (device_types.hpp: xpark) when a thread's share fits; larger patterns park it in the workspace slab as every other build does.
+    D.xpark = (sh.w2 && sh.nlds == 1 && !D.dual && D.N <= XPARK_CAP * threads && env_knob("EICOS_XPARK", 1, 0, 1)) ? 1 : 0;
     // The LDS that `bpc` resident workgroups leave free takes the head of the refinement residual E (device_types.hpp: e_lds): its
     // scattered stores and the read-back stay on chip.  Verified against the runtime's occupancy for the enlarged allocation.
     D.e_lds = 0; D.e_off = 0;
@@ -1695,6 +1698,7 @@ int eicos_batch_dims(eicos_batch *h, eicos_dims *o) {
     o->threads_per_block = h->threads; o->resident_blocks = h->grid; o->lds_bytes = (int)h->dyn_lds; o->instances_per_block = 1;
     o->lds_resident = h->ldsres; o->factor_path = h->sym.tile; o->cone_order = h->sym.cone_order; o->dual_rhs = h->dp.dual;
     o->arithmetic_profile = h->arith_profile; o->apex_nodes = h->dp.apex_na; o->solo_slices = h->dp.nfs_solo + h->dp.nbs_solo;
+    o->iterate_park = h->dp.xpark;
     return EICOS_OK;
 }
 

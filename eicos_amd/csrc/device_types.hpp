@@ -159,6 +159,9 @@ struct DevPat {
     // NLDS = 1 without dual right-hand sides: elimination positions [0, e_lds) of the refinement residual E are kept in LDS at g_dyn + e_off
     // (doubles) -- the part of the CU's LDS that the chosen number of resident workgroups leaves unused
     int e_lds, e_off;
+    // NLDS = 1, one right-hand side, the two-waves-per-SIMD build (kernels_w2.hip): 1 = a refinement step parks the iterate X in registers of the
+    // thread that owns each element (element i: thread i mod T, at most XPARK_R per thread) instead of in the workspace slab (w_xk); 0 = the slab
+    int xpark;
     // U-in-LDS builds (kernels_ubl*.hip; one workgroup per CU): the factor operand array U = L.*D (w_UB, ub_len doubles incl. padding and dummy slots)
     // lives at g_dyn + ub_lds (doubles) instead of in the workspace slab; -1 = not this build
     int ub_lds, ub_len;
@@ -232,6 +235,12 @@ static_assert(TILE_FTRIP % TILE_FPF == 0 && TILE_STRIP % TILE_PF == 0, "the regi
 constexpr int FOP_INIT = 1, FOP_END = 2, FOP_PAD = 4, FOP_ZERO = 8, FOP_SHIFT = 4; // tile factor op flags: start a target from its K tile / finish it / padding / (with INIT) the K tile is structurally zero: start from 0, no 2 KB load; target id above
 constexpr int TILE_SCR = 16 * 17;   // doubles of LDS scratch per wavefront in tile mode (one padded 16 x 16 tile)
 constexpr int TRACE_COLS = 12, TRACE_ROWS = 102; // per-iteration history rows (iter 0..100)
+// the parked refinement iterate (DevPat::xpark): handles of at most XPARK_CAP elements per thread take the path, and the first XPARK_R
+// elements of every thread are the ones that stay in registers (MPC02 has 24 per thread at 256 threads, its cone variant 26)
+#ifndef EICOS_XPARK_R
+#define EICOS_XPARK_R 26
+#endif
+constexpr int XPARK_CAP = 26, XPARK_R = EICOS_XPARK_R;
 constexpr int CONE_BIG = 32;       // cones of at least this dimension get a wavefront each
 constexpr int TINY_D = 4, TINY_INTS = 12; // tiny cones: dimension <= TINY_D (DevPat::cone_tiny)
 constexpr int CSC_STRIDE = 24;     // doubles of scaling state per cone: three 64-byte sectors, the committed scalars CS_* (what the per-solve cone loops read) fill the first

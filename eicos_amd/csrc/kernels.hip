@@ -883,7 +883,13 @@ __device__ __forceinline__ void apex_solve_lds(const DevPat &P, gcdbl_p invD, WS
 #pragma unroll
     for (int r = 0; r < KI; r++) y[r] = 0.;
     // ---- forward: lane i reads its own row of L at column k ----
-    const int cbase = img + (lane >= 32 ? (63 - lane) * 65 : lane * 65 + 63), cstep = lane >= 32 ? 1 : -1;
+    const int cbase = img + (lane >= 32 ? (63 - lane) * 65 : lane * 65 + 63);
+    int cstep = lane >= 32 ? 1 : -1;
+#if EICOS_W2
+    // (a fresh copy per call: the 63 column offsets cstep * k are otherwise hoisted out of the caller's refinement loop and held in registers
+    // across it -- registers the parked iterate of kkt_solve needs; spilled, they are reloaded from scratch inside this serial chain)
+    asm volatile("" : "+v"(cstep));
+#endif
     double a[2][APEX_BLK];
     auto load_cols = [&](int k0, double (&o)[APEX_BLK]) {
 #pragma unroll
@@ -2249,6 +2255,18 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
     auto X = [&] { if constexpr (NLDS >= 2) return g_dyn + P.Npad; else if constexpr (NLDS == 1) return g_dyn; else return Wg + P.w_xk; }();
     auto E = [&] { if constexpr (DUAL) return Wg + P.w_dual_ek; else if constexpr (NLDS == 1) return Wg + P.w_ek; else return SV; }();
     gdbl_p Xg = DUAL ? Wg + P.w_dual_xk : Wg + P.w_xk; // NLDS = 1: the iterate while the LDS vector serves the triangular sweeps
+    // ... or, in the two-waves-per-SIMD build (DevPat::xpark), in registers: every pass over the iterate is element-wise with element i on thread
+    // i mod T, so the owning thread keeps its share of the first XPARK_R T elements (static indices, bounds as predicates) and their slab copy is
+    // neither written nor read back; elements [xn, N) beyond them stay in the slab.  Same values, same order of operations: bit-identical.
+    constexpr bool XPARK = (NLDS == 1 && KI == 1 && EICOS_W2 != 0);
+    const int xn = (XPARK && uni(P.xpark) != 0) ? min(N, XPARK_R * T) : 0; // (workgroup-uniform; 0 = everything in the slab)
+    double xp[XPARK ? XPARK_R : 1] = {}; // (carried by the refinement loop from the park of one step to the un-park of the next; never read before a park has written it)
+    auto for_xp = [&](auto &&fn) __attribute__((always_inline)) { // fn(u, i) for the thread's elements i = tid + u T < xn
+        int t_ = tid, n_ = xn;
+        asm volatile("" : "+v"(t_), "+s"(n_)); // (fresh copies: the XPARK_R addresses and predicates are otherwise hoisted out of the refinement loop and spill across the sweeps)
+#pragma unroll
+        for (int u = 0; u < XPARK_R; u++) { const int i = t_ + u * T; if (i < n_) fn(u, i); }
+    };
     // NLDS = 1, one right-hand side: the first e_lds elimination positions of E live in the LDS the launch shape leaves free
     // behind the tables (api.cpp) -- E is written by scattered 8-byte stores (partial lines in HBM) and read back once
     constexpr bool ESPLIT = (NLDS == 1 && !DUAL);
@@ -2374,7 +2392,9 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
         }
         // x = first solve / x += dx_ref (ref :1602); an instance that has stopped keeps its iterate
         if constexpr (NLDS == 1) { // the LDS vector becomes X again: previous iterate (slab copy Xg) + increment
-            if (pass > 0) for_t_pre<T, 6>(N, [&](int i) { VKI<KI> r; ldK<KI>(Xg, i, r.v); return r; }, [&](int i, const VKI<KI> &r) {
+            if constexpr (XPARK) { if (pass > 0) for_xp([&](int u, int i) { const double c = SV[i]; SV[i] = rdone[0] ? xp[u] : xp[u] + c; }); }
+            if (pass > 0) for_t_pre<T, 6>(N - xn, [&](int j) { VKI<KI> r; ldK<KI>(Xg, xn + j, r.v); return r; }, [&](int j, const VKI<KI> &r) {
+                const int i = xn + j;
                 double c[KI], o[KI];
                 ldK<KI>(SV, i, c);
 #pragma unroll
@@ -2551,17 +2571,32 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
 #pragma unroll
         for (int k = 0; k < KI; k++) {
             if (!undo[k]) continue;
-            if constexpr (NLDS == 1) { FOR_T(i, N) X[i * KI + k] = Xg[i * KI + k]; } // Xg still holds the previous iterate
+            if constexpr (XPARK) for_xp([&](int u, int i) { X[i] = xp[u]; }); // (the parked registers still hold the previous iterate, and so does ...)
+            if constexpr (NLDS == 1) { FOR_T(j, N - xn) X[(xn + j) * KI + k] = Xg[(xn + j) * KI + k]; } // ... Xg
             else { FOR_T(i, N) X[i] -= dxr[i]; }
         }
         if (all_done) break;
         if constexpr (NLDS == 1) { // another step: park the iterate in the slab, residual -> sweep vector (unit stride)
             __syncthreads();
-            for_t_pre<T, 6>(N, [&](int i) {
+            if constexpr (XPARK) { // (the residual's loads U at a time, as for_t_pre issues them)
+                constexpr int U = 6;
+                int t_ = tid, n_ = xn;
+                asm volatile("" : "+v"(t_), "+s"(n_)); // (as in for_xp)
+#pragma unroll
+                for (int u0 = 0; u0 < XPARK_R; u0 += U) if (u0 * T < n_) {
+                    double e[U];
+#pragma unroll
+                    for (int u = 0; u < U; u++) if (u0 + u < XPARK_R) { const int i = t_ + (u0 + u) * T; e[u] = ldE(i < n_ ? i : 0, 0); }
+#pragma unroll
+                    for (int u = 0; u < U; u++) if (u0 + u < XPARK_R) { const int i = t_ + (u0 + u) * T; if (i < n_) { xp[u0 + u] = X[i]; SV[i] = e[u]; } }
+                }
+            }
+            for_t_pre<T, 6>(N - xn, [&](int j) {
                 VKI<KI> r;
-                if constexpr (ESPLIT) r.v[0] = ldE(i, 0); else ldK<KI>(E, i, r.v);
+                if constexpr (ESPLIT) r.v[0] = ldE(xn + j, 0); else ldK<KI>(E, xn + j, r.v);
                 return r;
-            }, [&](int i, const VKI<KI> &r) {
+            }, [&](int j, const VKI<KI> &r) {
+                const int i = xn + j;
                 double c[KI];
                 ldK<KI>(X, i, c); stK<KI>(Xg, i, c); stK<KI>(SV, i, r.v);
             });

@@ -79,6 +79,9 @@ typedef struct eicos_dims {
      * single-wavefront part of the two sweep plans (0 = no split); two handles on one pattern with equal threads_per_block, factor_path,
      * apex_nodes and solo_slices give bit-identical results for equal data */
     int arithmetic_profile, apex_nodes, solo_slices;
+    int iterate_park; /* where a refinement step of the KKT solve keeps the iterate while the LDS vector serves the sweeps: 1 = registers of
+                       * the owning threads (two-waves-per-SIMD build, dim_K <= 26 * threads_per_block), 0 = the workspace slab (or the
+                       * iterate has an LDS vector of its own); the results are bit-identical */
 } eicos_dims;
 
 /* Process-wide choice of how a handle's PLANS are shaped, read by eicos_batch_create / eicos_multi_create (no reference counterpart: the
