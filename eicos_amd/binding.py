@@ -46,6 +46,11 @@ class Dims(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AffineMap(C.Structure):
+    """struct eicos_affine_map: base vector + CSR matrix of one group of a parameter map."""
+    _fields_ = [("base", C.POINTER(C.c_double)), ("rowptr", C.POINTER(C.c_int)), ("col", C.POINTER(C.c_int)), ("val", C.POINTER(C.c_double))]
+
+
 def library_path() -> str:
     # EICOS_AMD_LIB: alternative build of the same library (used by tuning sweeps only)
     return os.environ.get("EICOS_AMD_LIB") or os.path.join(_HERE, "libeicos_amd.so")
@@ -102,6 +107,15 @@ def _lib():
             for f in ("eicos_batch_update_rhs", "eicos_batch_update_rhs_device", "eicos_batch_update_rhs_solve", "eicos_multi_update_rhs",
                       "eicos_multi_update_rhs_device", "eicos_multi_update_rhs_solve"):
                 getattr(L, f).restype = C.c_int
+        if hasattr(L, "eicos_batch_set_param_map"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            mp = C.POINTER(AffineMap)
+            L.eicos_batch_set_param_map.argtypes = L.eicos_multi_set_param_map.argtypes = [vp, C.c_int, mp, mp, mp]
+            L.eicos_batch_param_count.argtypes = L.eicos_multi_param_count.argtypes = [vp]
+            L.eicos_batch_update_param.argtypes = L.eicos_multi_update_param.argtypes = [vp, C.c_int, C.c_int, dp]
+            L.eicos_batch_update_param_device.argtypes = [vp, C.c_int, C.c_int, vp]
+            L.eicos_multi_update_param_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+            for f in ("set_param_map", "param_count", "update_param", "update_param_device"):
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -234,6 +248,70 @@ def _rhs_ptrs(pat, count, c, h, b):
     return _group_ptrs((c, h, b), (pat.n, pat.m, pat.p), count)
 
 
+class ParamMap:
+    """Right-hand sides affine in a parameter row theta of length k: c = c0 + C theta, h = h0 + H theta, b = b0 + B theta.  Per group
+    `(base, rowptr, col, val)` -- base vector and CSR matrix with k columns -- or None: that group is not parametric (an update keeps it).
+    evaluate() is the host restatement of what update_param computes on the GPU, in the same rounding order."""
+
+    def __init__(self, k: int, c=None, h=None, b=None):
+        self.k = int(k)
+        self.c, self.h, self.b = (None if g is None else (np.ascontiguousarray(g[0], np.float64), np.ascontiguousarray(g[1], np.int32),
+                                                          np.ascontiguousarray(g[2], np.int32), np.ascontiguousarray(g[3], np.float64))
+                                  for g in (c, h, b))
+
+    def groups(self):
+        return self.c, self.h, self.b
+
+    def evaluate(self, theta):
+        """(c, h, b) for theta [B, k]: arrays [B, rows], None for a group without a map.  Row r: acc = base[r], then for every stored entry
+        t of the row, in stored order, acc = acc + (val[t] * theta[col[t]]) -- the product and the sum each rounded to float64 (numpy
+        has no fused multiply-add), which is the order of eicos_batch_update_param."""
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.k:
+            raise ValueError(f"theta has shape {theta.shape}, expected [count, {self.k}]")
+        out = []
+        for g in self.groups():
+            if g is None:
+                out.append(None)
+                continue
+            base, rowptr, col, val = g
+            acc = np.repeat(base[None, :], theta.shape[0], axis=0)
+            length = np.diff(rowptr)
+            for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
+                rows = np.nonzero(length > j)[0]
+                t = rowptr[rows] + j
+                acc[:, rows] = acc[:, rows] + val[t][None, :] * theta[:, col[t]]
+            out.append(acc)
+        return tuple(out)
+
+
+def _param_map_ptrs(pmap, pat):
+    """A ParamMap as (keep-alive structs, [c, h, b] as C pointers to eicos_affine_map or None); array sizes are checked here, their
+    contents (row pointers, column range, group present in the pattern) by the library."""
+    keep, ptrs = [], []
+    for name, g, rows in zip("chb", pmap.groups(), (pat.n, pat.m, pat.p)):
+        if g is None:
+            ptrs.append(None)
+            continue
+        base, rowptr, col, val = g
+        if base.size != rows or rowptr.size != rows + 1 or col.size != val.size or (rowptr.size and rowptr[-1] > col.size):
+            raise ValueError(f"parameter map of {name}: base[{base.size}], rowptr[{rowptr.size}], col[{col.size}], val[{val.size}] "
+                             f"do not describe {rows} rows")
+        one = np.zeros(1)
+        m = AffineMap(_dp(base if base.size else one), _ip(rowptr), _ip(col if col.size else np.zeros(1, np.int32)), _dp(val if val.size else one))
+        keep.append((m, one))
+        ptrs.append(C.pointer(m))
+    return keep, ptrs
+
+
+def _theta_rows(theta, k, count):
+    """theta as a contiguous float64 [count, k] array (count None: its leading dimension); ValueError otherwise."""
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    if theta.ndim != 2 or theta.shape[1] != k or (count is not None and theta.shape[0] != count):
+        raise ValueError(f"theta has shape {theta.shape}, expected [{'count' if count is None else count}, {k}]")
+    return theta, theta.shape[0]
+
+
 def _rows(groups, default):
     """The instance count of an update: the leading dimension of the first two-dimensional array given."""
     return next((np.shape(a)[0] for a in groups if a is not None and np.ndim(a) == 2), default)
@@ -291,6 +369,30 @@ class _Solver:
         registered arrays the solve kernel scales every instance's vectors itself.  Returns the exit codes."""
         _keep, ptr = _rhs_ptrs(self.pat, self.batch, c, h, b)
         return self._solve_with("update_rhs_solve", ptr, x_out)
+
+    # ---- parametric right-hand sides (include/eicos_amd.h: eicos_batch_set_param_map / eicos_batch_update_param) ----
+    def set_param_map(self, pmap: "ParamMap | None"):
+        """Install (copy) a ParamMap for all instances; None, or a map without groups, removes the installed one."""
+        if pmap is None:
+            self._call("set_param_map", 0, None, None, None)
+            return
+        _keep, ptr = _param_map_ptrs(pmap, self.pat)
+        self._call("set_param_map", pmap.k, *ptr)
+
+    def param_count(self) -> int:
+        """k of the installed parameter map, 0 without one."""
+        return int(getattr(_lib(), self._prefix + "param_count")(self._h))
+
+    def update_param(self, theta, first: int = 0, count: int | None = None):
+        """theta [count, k] (host array) for instances [first, first + count): the GPU expands it into the mapped groups of c, h, b and
+        divides by the stored scalings -- bit for bit what update_rhs(*map.evaluate(theta)) leaves."""
+        k = self.param_count()
+        if k > 0:
+            theta, count = _theta_rows(theta, k, count)
+        else:  # (the library refuses: "no parameter map")
+            theta = np.ascontiguousarray(theta, dtype=np.float64)
+            count = (theta.shape[0] if theta.ndim == 2 else self.batch) if count is None else count
+        self._call("update_param", first, count, _dp(theta) if theta.size else _dp(np.zeros(1)))
 
     # ---- solve ----
     def solve(self):
@@ -374,6 +476,11 @@ class BatchSolver(_Solver):
         """update_rhs from raw device pointers (ints); 0 keeps the group.  Asynchronous, like update_device."""
         count = self.batch if count is None else count
         self._call("update_rhs_device", first, count, *[C.c_void_p(int(p) or None) for p in (dc, dh, db)])
+
+    def update_param_device(self, dtheta, first: int = 0, count: int | None = None):
+        """update_param from a raw device pointer (int) to theta [count, k].  Asynchronous, like update_rhs_device."""
+        count = self.batch if count is None else count
+        self._call("update_param_device", first, count, C.c_void_p(int(dtheta) or None))
 
     def set_stream(self, stream_ptr: int):
         self._call("set_stream", C.c_void_p(int(stream_ptr) or None))
@@ -494,6 +601,11 @@ class MultiBatchSolver(_Solver):
         """update_rhs from raw pointers into the HBM of GPU `src_device` (arrays [count, ...]); 0 keeps the group.  Asynchronous."""
         count = self.batch if count is None else count
         self._call("update_rhs_device", int(src_device), first, count, *[C.c_void_p(int(p) or None) for p in (dc, dh, db)])
+
+    def update_param_device(self, src_device: int, dtheta, first: int = 0, count: int | None = None):
+        """update_param from a raw pointer into the HBM of GPU `src_device` (theta [count, k], global instance order).  Asynchronous."""
+        count = self.batch if count is None else count
+        self._call("update_param_device", int(src_device), first, count, C.c_void_p(int(dtheta) or None))
 
     def shards(self):
         """[(first, count, device)] of every shard."""

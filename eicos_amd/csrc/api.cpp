@@ -118,6 +118,8 @@ struct eicos_batch {
     // ... from pageable host memory: one pinned staging buffer for the whole batch (+ one ready flag per chunk), filled while the kernel runs
     double *stage_pin = nullptr; size_t stage_pin_doubles = 0; unsigned *stage_flags = nullptr; int stage_nflags = 0; unsigned stage_seq = 0;
     int *d_err = nullptr;
+    // parametric right-hand sides (eicos_batch_set_param_map): the map's arrays in one device allocation, param.k = 0 while none is installed
+    ParamMapDev param{}; void *d_param = nullptr;
     TilePlan tiles;        // tile mode (Symbolic::tile): the dense-front plan
 };
 
@@ -1026,7 +1028,7 @@ int eicos_batch_destroy(eicos_batch *h) {
     for (int i = 0; i < eicos_batch::EV_RING; i++)
         for (hipEvent_t e : {h->ring_s[i][0], h->ring_s[i][1], h->ring_u[i][0], h->ring_u[i][1]}) if (e) (void)hipEventDestroy(e);
     for (void *ptr : {(void *)h->d_pattern, (void *)h->d_inst, (void *)h->d_work, (void *)h->d_queue, (void *)h->d_scratch,
-                      (void *)h->d_stage, (void *)h->d_flag})
+                      (void *)h->d_stage, (void *)h->d_flag, h->d_param})
         if (ptr) (void)hipFree(ptr);
     for (int i = 0; i < 2; i++) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     if (h->stage_pin) (void)hipHostFree(h->stage_pin);
@@ -1254,6 +1256,7 @@ struct UpdateInputs {
     eicos_batch *h;
     int first, count;
     bool rhs;             // the right-hand-side-only update (G, A not given)
+    bool param;           // the parametric update (take_theta): the ONE given group is theta, [count][k], in the slot of c
     const double *src[5]; // G, A, c, h, b, rows of `count` instances; NULL keeps the group
     size_t w[5];          // doubles per instance
     MemKind kind[5];      // of the arrays that hold data, when the entry point asked for kinds
@@ -1279,7 +1282,7 @@ static int take_inputs(UpdateInputs &in, eicos_batch *h, int first, int count, c
     if (A && !b && D.p > 0) return fail(EICOS_E_INVALID, "Apr given without b");
     HIP_TRY(hipSetDevice(h->device));
     // (h is read only with Gpr, b only with Apr: reference src/eicos.cpp:2053-2074; the right-hand-side-only update reads them on their own)
-    in = UpdateInputs{h, first, count, rhs, {G, A, c, (G || rhs) ? hh : nullptr, (A || rhs) ? b : nullptr},
+    in = UpdateInputs{h, first, count, rhs, false, {G, A, c, (G || rhs) ? hh : nullptr, (A || rhs) ? b : nullptr},
                       {(size_t)D.nnzG, (size_t)D.nnzA, (size_t)D.n, (size_t)D.m, (size_t)D.p}, {}, 0};
     for (int k = 0; k < 5; k++) {
         if (in.src[k]) in.per += in.w[k];
@@ -1288,10 +1291,28 @@ static int take_inputs(UpdateInputs &in, eicos_batch *h, int first, int count, c
     return EICOS_OK;
 }
 
-// the updateData kernel (full or right-hand-side-only, kernels.hip: rhs_instance) of rows [first, first + count) on five pointers the GPU addresses
+// The inputs of a parametric update (eicos_batch_update_param*): one more kind of UpdateInputs -- a single group, theta, `k` doubles per
+// instance -- so that the rows travel over the very paths of the other updates (bounce, pinned in place, device, peer in place / staged).
+static int take_theta(UpdateInputs &in, eicos_batch *h, int first, int count, const double *theta, bool kinds) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (h->param.k == 0) return fail(EICOS_E_INVALID, "no parameter map (eicos_batch_set_param_map installs one)");
+    if (first < 0 || count < 0 || first + count > h->batch) return fail(EICOS_E_INVALID, "instance range out of bounds");
+    if (!theta) return fail(EICOS_E_INVALID, "theta is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t k = (size_t)h->param.k;
+    in = UpdateInputs{h, first, count, false, true, {nullptr, nullptr, theta, nullptr, nullptr}, {0, 0, k, 0, 0}, {}, k};
+    if (kinds) in.kind[2] = memory_kind(theta, (size_t)count * k * sizeof(double));
+    return EICOS_OK;
+}
+
+// the updateData kernel (full, right-hand-side-only -- kernels.hip: rhs_instance -- or parametric: k_update_param_range) of rows [first, first + count) on five pointers the GPU addresses
 static int launch_range(const UpdateInputs &in, int first, int count, const double *const p[5]) {
     eicos_batch *h = in.h;
-    if (in.rhs) HIP_TRY(launch_update_rhs(h->pslot, h->d_inst, first, count, p[2], p[3], p[4], (int)in.per, h->stream));
+    if (in.param) {
+        const DevPat &D = h->dp;
+        const int width = (h->param.g[0].base ? D.n : 0) + (h->param.g[1].base ? D.m : 0) + (h->param.g[2].base ? D.p : 0);
+        HIP_TRY(launch_update_param(h->pslot, h->d_inst, first, count, h->param, p[2], width, h->stream));
+    } else if (in.rhs) HIP_TRY(launch_update_rhs(h->pslot, h->d_inst, first, count, p[2], p[3], p[4], (int)in.per, h->stream));
     else HIP_TRY(launch_update(h->pslot, h->d_inst, first, count, p[0], p[1], p[2], p[3], p[4], h->d_scratch, std::min(count, h->upd_grid), h->upd_lds, h->upd_vals_lds, h->stream));
     return EICOS_OK;
 }
@@ -1367,7 +1388,8 @@ static int peer_update(const UpdateInputs &in, int src_dev) {
 static int host_update(const UpdateInputs &in) {
     eicos_batch *h = in.h;
     // a device pointer handed to the HOST-pointer entry point must not reach the bounce copy (a host memcpy from it would fault)
-    if (in.any(MEM_DEVICE)) return fail(EICOS_E_INVALID, in.rhs ? "eicos_batch_update_rhs takes host pointers: an array lives in device memory (use eicos_batch_update_rhs_device)"
+    if (in.any(MEM_DEVICE)) return fail(EICOS_E_INVALID, in.param ? "eicos_batch_update_param takes a host pointer: theta lives in device memory (use eicos_batch_update_param_device)"
+                                                         : in.rhs ? "eicos_batch_update_rhs takes host pointers: an array lives in device memory (use eicos_batch_update_rhs_device)"
                                                                  : "eicos_batch_update takes host pointers: an array lives in device memory (use eicos_batch_update_device)");
     // pinned in place only when EVERY byte the kernel will read is mapped (else the bounce path, which reads with the host's own loads)
     if (in.all(MEM_PINNED) && !env_knob("EICOS_HOST_BOUNCE", 0, 0, 1)) {
@@ -1441,6 +1463,81 @@ int eicos_batch_update(eicos_batch *h, int first, int count, const double *G, co
 
 int eicos_batch_update_rhs(eicos_batch *h, int first, int count, const double *c, const double *hh, const double *b) {
     return eicos_internal_update_staged(h, first, count, nullptr, nullptr, c, hh, b, -1, 1);
+}
+
+// ---- parametric right-hand sides: c, h, b affine in a short parameter row theta (no reference counterpart) ----
+// The map is validated on the host, packed into ONE device allocation ([doubles: base, val per group | ints: rowptr, col per group]) and
+// handed to the kernel by value (ParamMapDev); a later call replaces it, all groups NULL or k = 0 removes it.
+int eicos_batch_set_param_map(eicos_batch *h, int k, const eicos_affine_map *c, const eicos_affine_map *hh, const eicos_affine_map *b) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (k < 0) return fail(EICOS_E_INVALID, "parameter map: k must not be negative");
+    const DevPat &D = h->dp;
+    const eicos_affine_map *g[3] = {c, hh, b};
+    const int rows[3] = {D.n, D.m, D.p};
+    const char *name[3] = {"c", "h", "b"};
+    const bool remove = k == 0 || (!c && !hh && !b);
+    size_t nd = 0, ni = 0;
+    for (int q = 0; q < 3 && !remove; q++) {
+        if (!g[q]) continue;
+        const std::string who = std::string("parameter map of ") + name[q] + ": ";
+        if (rows[q] == 0) return fail(EICOS_E_INVALID, who + "the pattern has no such group (its size is 0)");
+        if (!g[q]->base || !g[q]->rowptr) return fail(EICOS_E_INVALID, who + "base or rowptr is NULL");
+        const int *rp = g[q]->rowptr;
+        if (rp[0] != 0) return fail(EICOS_E_INVALID, who + "rowptr[0] must be 0");
+        for (int r = 0; r < rows[q]; r++)
+            if (rp[r + 1] < rp[r]) return fail(EICOS_E_INVALID, who + "rowptr decreases at row " + std::to_string(r));
+        const int nnz = rp[rows[q]];
+        if (nnz > 0 && (!g[q]->col || !g[q]->val)) return fail(EICOS_E_INVALID, who + "col or val is NULL");
+        for (int t = 0; t < nnz; t++)
+            if (g[q]->col[t] < 0 || g[q]->col[t] >= k) return fail(EICOS_E_INVALID, who + "column " + std::to_string(g[q]->col[t]) + " of entry " + std::to_string(t) + " is outside [0, k)");
+        nd += (size_t)rows[q] + nnz; ni += (size_t)rows[q] + 1 + nnz;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream)); // (an update in flight may still read the map that goes away)
+    if (h->d_param) { (void)hipFree(h->d_param); h->d_param = nullptr; }
+    h->param = ParamMapDev{};
+    if (remove) return EICOS_OK;
+    std::vector<char> buf(nd * sizeof(double) + ni * sizeof(int));
+    double *hd_ = reinterpret_cast<double *>(buf.data());
+    int *hi_ = reinterpret_cast<int *>(buf.data() + nd * sizeof(double));
+    void *dev = nullptr;
+    HIP_TRY(hipMalloc(&dev, buf.size()));
+    const double *dd = static_cast<const double *>(dev);
+    const int *di = reinterpret_cast<const int *>(static_cast<const char *>(dev) + nd * sizeof(double));
+    ParamMapDev M{};
+    M.k = k;
+    size_t od = 0, oi = 0;
+    for (int q = 0; q < 3; q++) {
+        if (!g[q]) continue;
+        const int nnz = g[q]->rowptr[rows[q]];
+        M.g[q].base = dd + od; std::copy(g[q]->base, g[q]->base + rows[q], hd_ + od); od += rows[q];
+        M.g[q].val = dd + od; if (nnz) std::copy(g[q]->val, g[q]->val + nnz, hd_ + od); od += nnz;
+        M.g[q].rowptr = di + oi; std::copy(g[q]->rowptr, g[q]->rowptr + rows[q] + 1, hi_ + oi); oi += rows[q] + 1;
+        M.g[q].col = di + oi; if (nnz) std::copy(g[q]->col, g[q]->col + nnz, hi_ + oi); oi += nnz;
+    }
+    const hipError_t e = hipMemcpy(dev, buf.data(), buf.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the parameter map: ") + hipGetErrorString(e)); }
+    h->d_param = dev; h->param = M;
+    return EICOS_OK;
+}
+
+int eicos_batch_param_count(eicos_batch *h) { return h ? h->param.k : fail(EICOS_E_INVALID, "NULL handle"); }
+
+// theta from buffers that are not in the handle's HBM (host: src_dev < 0; another GPU: eicos_multi_update_param_device)
+int eicos_internal_update_param_staged(eicos_batch *h, int first, int count, const double *theta, int src_dev) {
+    UpdateInputs in;
+    const int rc = take_theta(in, h, first, count, theta, src_dev < 0);
+    return rc != EICOS_OK ? rc : staged_update(in, src_dev);
+}
+
+int eicos_batch_update_param(eicos_batch *h, int first, int count, const double *theta) {
+    return eicos_internal_update_param_staged(h, first, count, theta, -1);
+}
+
+int eicos_batch_update_param_device(eicos_batch *h, int first, int count, const double *dtheta) {
+    UpdateInputs in;
+    const int rc = take_theta(in, h, first, count, dtheta, false);
+    return rc != EICOS_OK ? rc : update_in_place(in, 0);
 }
 
 int eicos_batch_solve_async(eicos_batch *h) {

@@ -3462,6 +3462,65 @@ __global__ __launch_bounds__(T) void k_update_rhs_range(int ps, double *inst, in
     }
 }
 
+// Parametric right-hand-side update of a range of instances (eicos_batch_update_param*): the vectors are affine in a short parameter
+// row, c = c0 + C theta, h = h0 + H theta, b = b0 + B theta (ParamMapDev: CSR rows, shared by the batch; a group without a base is kept),
+// and each entry ends with rhs_entry's division by the instance's stored scaling.  ENTRY-parallel like k_update_rhs_range: the x dimension
+// takes consecutive entries of the mapped groups [c | h | b] (unit-stride 8-byte stores into the slab), blockIdx.y strides over groups of
+// PARAM_Q instances.  A thread reads its row's (col, val) run once per group of instances -- the map is the same for all of them and is
+// served from L2 -- and carries one accumulator per instance; the theta rows of the group (contiguous in the input) are staged in LDS
+// when LDS, and read through the cache otherwise: the arithmetic is the same either way.
+// Rounding: acc = acc + (val * theta[col]) in stored order, the product and the sum EACH rounded to fp64 (__dmul_rn / __dadd_rn, no
+// FMA).  That is what a numpy restatement on the host computes (numpy has no FMA), so update_param(theta) leaves the bits of
+// update_rhs(c(theta), h(theta), b(theta)); and the kernel is bound by the slab write of ~48 kB per instance, not by its arithmetic.
+constexpr int PARAM_Q = 4;
+template <int T, bool LDS>
+__global__ __launch_bounds__(T) void k_update_param_range(int ps, double *inst, int first, int count, ParamMapDev M, const double *theta) {
+    const DevPat &P = c_pat[ps];
+    const int k = M.k;
+    const int wc = M.g[0].base ? P.n : 0, wh = M.g[1].base ? P.m : 0, w = wc + wh + (M.g[2].base ? P.p : 0);
+    for (int e0 = blockIdx.x * T; e0 < w; e0 += gridDim.x * T) { // (uniform over the workgroup: the barriers below are met by all)
+        const int e = e0 + threadIdx.x;
+        const bool act = e < w;
+        const int grp = e < wc ? 0 : (e < wc + wh ? 1 : 2), r = e - (grp == 0 ? 0 : (grp == 1 ? wc : wc + wh));
+        const AffineDev A = grp == 0 ? M.g[0] : (grp == 1 ? M.g[1] : M.g[2]);
+        const int i_dst = (grp == 0 ? P.i_c : (grp == 1 ? P.i_h : P.i_b)) + r, i_scl = (grp == 0 ? P.i_xe : (grp == 1 ? P.i_ge : P.i_ae)) + r;
+        double base = 0.;
+        int t0 = 0, t1 = 0;
+        if (act) { base = A.base[r]; t0 = A.rowptr[r]; t1 = A.rowptr[r + 1]; }
+        for (int q0 = blockIdx.y * PARAM_Q; q0 < count; q0 += gridDim.y * PARAM_Q) {
+            const int nq = count - q0 < PARAM_Q ? count - q0 : PARAM_Q;
+            const double *th = theta + (size_t)q0 * k; // rows q0 .. q0 + nq - 1
+            if constexpr (LDS) {
+                __syncthreads(); // (the previous group's rows have been read)
+                for (int j = threadIdx.x; j < nq * k; j += T) g_dyn[j] = th[j];
+                __syncthreads();
+            }
+            if (!act) continue;
+            double acc[PARAM_Q];
+#pragma unroll
+            for (int j = 0; j < PARAM_Q; j++) acc[j] = base;
+            for (int t = t0; t < t1; t++) {
+                const int col = A.col[t];
+                const double v = A.val[t];
+#pragma unroll
+                for (int j = 0; j < PARAM_Q; j++)
+                    if (j < nq) {
+                        double x;
+                        if constexpr (LDS) x = g_dyn[j * k + col]; else x = th[(size_t)j * k + col];
+                        acc[j] = __dadd_rn(acc[j], __dmul_rn(v, x));
+                    }
+            }
+#pragma unroll
+            for (int j = 0; j < PARAM_Q; j++)
+                if (j < nq) {
+                    hbm_p I = (hbm_p)inst + (size_t)(first + q0 + j) * P.inst_stride;
+                    const bool eq = reinterpret_cast<const DevInfo EICOS_GLOBAL *>(I + P.i_info)->equilibrated != 0;
+                    I[i_dst] = acc[j] / (eq ? I[i_scl] : 1.);
+                }
+        }
+    }
+}
+
 // Debug: factorise instance `i` with the KKT scaling block as it stands in memory (runs the solver's own stage).
 template <int T>
 __global__ __launch_bounds__(T, waves_per_eu<T>()) void k_debug_factor(int ps, double *inst, double *work, int i) {
@@ -3586,6 +3645,17 @@ hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const d
     const int gx = (width + T - 1) / T, gy = count;
     const dim3 grid((unsigned)(gx < 64 ? gx : 64), (unsigned)(gy < 16384 ? gy : 16384));
     hipLaunchKernelGGL(k_update_rhs_range<T>, grid, dim3(T), 0, st, ps, inst, first, count, c, h, b);
+    return hipGetLastError();
+}
+// grid: x = up to 16 workgroups over the entries (a longer [c | h | b] takes further passes), y = groups of PARAM_Q instances, about
+// 2048 workgroups in all (the rest by stride).  The theta rows of a group go to LDS while they fit 32 KB (k <= 1024).
+hipError_t launch_update_param(int ps, double *inst, int first, int count, const ParamMapDev &map, const double *theta, int width, hipStream_t st) {
+    if (count <= 0 || width <= 0) return hipSuccess;
+    constexpr int T = 256;
+    const int nx = (width + T - 1) / T, gx = nx < 16 ? nx : 16, ny = (count + PARAM_Q - 1) / PARAM_Q, gy = ny < 2048 / gx ? ny : 2048 / gx;
+    const size_t lds = (size_t)PARAM_Q * map.k * sizeof(double);
+    if (lds <= 32 * 1024) hipLaunchKernelGGL((k_update_param_range<T, true>), dim3((unsigned)gx, (unsigned)gy), dim3(T), lds, st, ps, inst, first, count, map, theta);
+    else hipLaunchKernelGGL((k_update_param_range<T, false>), dim3((unsigned)gx, (unsigned)gy), dim3(T), 0, st, ps, inst, first, count, map, theta);
     return hipGetLastError();
 }
 // the dynamic-LDS ceiling of the two entry-parallel updateData kernels, set once per handle on the handle's device

@@ -21,6 +21,13 @@ hipError_t launch_update(int ps, double *inst, int first, int count, const doubl
 // right-hand-side-only updateData of instances [first, first + count): rows of c [count][n], h [count][m], b [count][p] (NULL = keep)
 // divided by each instance's stored scalings; `width` = the summed widths of the given groups (sizes the grid)
 hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st);
+// Parametric right-hand sides (eicos_batch_set_param_map): per group c, h, b a base vector and a CSR matrix with k columns, in device
+// memory, shared by every instance of the handle; base == NULL: the group has no map and is kept.  Passed to the kernel by value.
+struct AffineDev { const double *base; const int *rowptr, *col; const double *val; };
+struct ParamMapDev { int k; AffineDev g[3]; };
+// instances [first, first + count) from rows of theta [count][k]: entry = (base[r] + sum val * theta[col], every product and sum
+// rounded on its own, in stored order) divided by the instance's stored scaling -- the bits launch_update_rhs leaves for the same vectors
+hipError_t launch_update_param(int ps, double *inst, int first, int count, const ParamMapDev &map, const double *theta, int width, hipStream_t st);
 hipError_t update_set_max_lds();
 hipError_t launch_debug_factor(int ps, double *inst, double *work, int i, int threads, size_t dyn_lds, hipStream_t st);
 hipError_t launch_debug_scalings(int ps, double *inst, double *work, int i, int *ok, int threads, hipStream_t st);

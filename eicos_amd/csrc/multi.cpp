@@ -202,6 +202,31 @@ int eicos_multi_update_rhs_device(eicos_multi *mh, int src_device, int first, in
     });
 }
 
+int eicos_multi_set_param_map(eicos_multi *mh, int k, const eicos_affine_map *c, const eicos_affine_map *h, const eicos_affine_map *b) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    return for_shards(mh, [&](int s) { return eicos_batch_set_param_map(mh->shard[s], k, c, h, b); });
+}
+
+int eicos_multi_param_count(eicos_multi *mh) { return mh ? eicos_batch_param_count(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
+
+int eicos_multi_update_param(eicos_multi *mh, int first, int count, const double *theta) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    const int k = eicos_batch_param_count(mh->shard[0]); // (0: every shard refuses, "no parameter map")
+    return for_range(mh, first, count, [&](int s, int f, int cnt, size_t off) {
+        return eicos_batch_update_param(mh->shard[s], f, cnt, at(theta, off, k));
+    });
+}
+
+int eicos_multi_update_param_device(eicos_multi *mh, int src_device, int first, int count, const double *dtheta) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    if (src_device < 0) return mfail(EICOS_E_INVALID, "src_device must name the GPU that holds the inputs");
+    const int k = eicos_batch_param_count(mh->shard[0]);
+    return for_range(mh, first, count, [&](int s, int f, int cnt, size_t off) {
+        if (mh->device[s] == src_device) return eicos_batch_update_param_device(mh->shard[s], f, cnt, at(dtheta, off, k));
+        return eicos_internal_update_param_staged(mh->shard[s], f, cnt, at(dtheta, off, k), src_device);
+    });
+}
+
 int eicos_multi_solve_async(eicos_multi *mh) {
     if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
     for (size_t s = 0; s < mh->shard.size(); s++) { // enqueue only: every shard's kernels start on its own stream, the call returns at once

@@ -1,0 +1,189 @@
+// Parametric right-hand-side updates from host C++ (no torch): in an MPC loop c, h and b are affine in a few numbers (the measured state,
+// a reference, some bounds).  EiCOS::BatchSolver::setParamMap installs c = c0 + C theta, h = h0 + H theta, b = b0 + B theta once;
+// updateParam then sends k doubles per instance and the GPU expands them -- the result must equal, bit for bit, updateRHS of the vectors
+// evaluated on the host in the same order (every product and every sum rounded on its own).  Runs over a device list (a device may be
+// listed twice: 0,0), checks updateParam + solve and a sub-range against updateRHS, then runs a short closed loop with warm starts --
+// theta moves a little every step -- in three forms side by side, each on its own solver, and prints the median step time (update
+// call -> end of solve) of each: updateRHS from pageable host vectors, updateParam from a pageable theta, updateRHSDevice from vectors
+// already in device memory (that leg needs the HIP runtime's allocation calls, looked up at run time; "n/a" without them).
+//   g++ -std=c++17 -Iinclude examples/param_update_demo.cpp -Leicos_amd -leicos_amd -Wl,-rpath,$PWD/eicos_amd -o param_update_demo
+//   ./param_update_demo tests/golden/MPC02.epb 64 0,0 [k = 16] [steps = 20]
+#include <dlfcn.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iterator>
+#include <sstream>
+#include <vector>
+
+#include "eicos.hpp"
+
+// the host restatement must not fuse the product into the sum
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#elif defined(__GNUC__)
+#pragma GCC optimize("fp-contract=off")
+#endif
+
+struct Group { // one group of the map: base vector + CSR matrix with k columns
+    std::vector<double> base, val;
+    std::vector<int> rowptr, col;
+    eicos_affine_map view() const { return {base.data(), rowptr.data(), col.data(), val.data()}; }
+    // out[i][r] = base[r] + sum over the row's entries, in stored order, of val * theta[i][col]
+    void evaluate(const std::vector<double> &theta, int k, int B, std::vector<double> &out) const {
+        const size_t rows = base.size();
+        out.resize((size_t)B * rows);
+        for (int i = 0; i < B; i++)
+            for (size_t r = 0; r < rows; r++) {
+                double acc = base[r];
+                for (int t = rowptr[r]; t < rowptr[r + 1]; t++) { const double prod = val[t] * theta[(size_t)i * k + col[t]]; acc = acc + prod; }
+                out[(size_t)i * rows + r] = acc;
+            }
+    }
+};
+
+// 0 - 4 entries per row (some rows empty), values about 1e-3 of the base
+static Group make_group(const double *base, int rows, int k, unsigned seed) {
+    Group g;
+    unsigned long long st = seed * 2654435761ull + 99991;
+    auto rnd = [&] { st = st * 6364136223846793005ull + 1442695040888963407ull; return (double)((st >> 11) & 0xFFFFFFFFFFFFull) / (double)(1ull << 48); };
+    g.base.assign(base, base + rows);
+    g.rowptr.assign(1, 0);
+    for (int r = 0; r < rows; r++) {
+        const int len = std::min(k, (int)(rnd() * 5));
+        const int c0 = (int)(rnd() * k);
+        for (int j = 0; j < len; j++) { g.col.push_back((c0 + j) % k); g.val.push_back(1e-3 * (1 + std::fabs(base[r])) * (2 * rnd() - 1)); }
+        g.rowptr.push_back((int)g.col.size());
+    }
+    return g;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 4) { std::fprintf(stderr, "usage: %s problem.epb batch dev[,dev...] [k] [steps]\n", argv[0]); return 2; }
+    std::ifstream f(argv[1], std::ios::binary);
+    std::vector<char> raw((std::istreambuf_iterator<char>(f)), {});
+    if (raw.size() < 36 || std::memcmp(raw.data(), "EPB1", 4)) { std::fprintf(stderr, "not an EPB1 file\n"); return 2; }
+    const int B = std::atoi(argv[2]);
+    std::vector<int> devs;
+    { std::stringstream ss(argv[3]); std::string tok; while (std::getline(ss, tok, ',')) devs.push_back(std::atoi(tok.c_str())); }
+    const int k = argc > 4 ? std::atoi(argv[4]) : 16, steps = argc > 5 ? std::atoi(argv[5]) : 20;
+    if (B < 4 || k < 1 || steps < 1) { std::fprintf(stderr, "need batch >= 4, k >= 1, steps >= 1\n"); return 2; }
+    const int *hd = reinterpret_cast<const int *>(raw.data() + 4);
+    const int n = hd[0], m = hd[1], p = hd[2], nc = hd[4], nnzG = hd[5], nnzA = hd[6];
+    const int *ip = hd + 8;
+    std::vector<int> q(ip, ip + nc); ip += nc;
+    std::vector<int> Gjc(ip, ip + n + 1); ip += n + 1;
+    std::vector<int> Gir(ip, ip + nnzG); ip += nnzG;
+    std::vector<int> Ajc(ip, ip + n + 1); ip += n + 1;
+    std::vector<int> Air(ip, ip + nnzA); ip += nnzA;
+    const double *dp = reinterpret_cast<const double *>(ip);
+    const double *Gpr = dp, *Apr = Gpr + nnzG, *c = Apr + nnzA, *h = c + n, *b = h + m;
+    std::vector<double> G((size_t)B * nnzG), A((size_t)B * nnzA), C0((size_t)B * n), H0((size_t)B * m), B0((size_t)B * p);
+    for (int i = 0; i < B; i++) {
+        std::copy(Gpr, Gpr + nnzG, G.begin() + (size_t)i * nnzG);
+        std::copy(Apr, Apr + nnzA, A.begin() + (size_t)i * nnzA);
+        std::copy(c, c + n, C0.begin() + (size_t)i * n);
+        std::copy(h, h + m, H0.begin() + (size_t)i * m);
+        std::copy(b, b + p, B0.begin() + (size_t)i * p);
+    }
+    // the map (a group the pattern does not have is left out) and theta of step s: every instance its own slowly moving point in [0, 1]^k
+    const Group gc = make_group(c, n, k, 1), gh = make_group(h, m, k, 2), gb = make_group(b, p, k, 3);
+    const eicos_affine_map mc = gc.view(), mh = gh.view(), mb = gb.view();
+    auto theta_of = [&](int s) {
+        std::vector<double> th((size_t)B * k);
+        for (int i = 0; i < B; i++)
+            for (int j = 0; j < k; j++) th[(size_t)i * k + j] = 0.5 + 0.4 * std::sin(0.05 * s + 0.01 * i + j);
+        return th;
+    };
+    auto vectors_of = [&](const std::vector<double> &th, std::vector<double> &C, std::vector<double> &H, std::vector<double> &Bv) {
+        gc.evaluate(th, k, B, C); gh.evaluate(th, k, B, H); gb.evaluate(th, k, B, Bv);
+    };
+    auto make = [&] {
+        auto *s = new EiCOS::BatchSolver(n, m, p, nc, q.data(), m ? Gjc.data() : nullptr, m ? Gir.data() : nullptr, p ? Ajc.data() : nullptr,
+                                         p ? Air.data() : nullptr, B, devs);
+        s->updateData(m ? G.data() : nullptr, p ? A.data() : nullptr, C0.data(), m ? H0.data() : nullptr, p ? B0.data() : nullptr);
+        s->solve();
+        return s;
+    };
+    auto same = [&](const std::vector<double> &x, const std::vector<double> &y) { return x.size() == y.size() && std::memcmp(x.data(), y.data(), x.size() * sizeof(double)) == 0; };
+
+    // (1) updateParam + solve against updateRHS of the host-evaluated vectors
+    std::vector<double> C, H, Bv;
+    const std::vector<double> th0 = theta_of(0), th1 = theta_of(1);
+    EiCOS::BatchSolver *ref = make(), *s = make();
+    s->setParamMap(k, &mc, m ? &mh : nullptr, p ? &mb : nullptr);
+    vectors_of(th0, C, H, Bv);
+    ref->updateRHS(C.data(), m ? H.data() : nullptr, p ? Bv.data() : nullptr);
+    const std::vector<EiCOS::exitcode> codes_ref = ref->solve();
+    s->updateParam(th0.data());
+    const bool same_all = s->solve() == codes_ref && same(ref->solution(), s->solution());
+    int ok = 0;
+    for (auto cd : codes_ref) ok += cd == EiCOS::exitcode::optimal;
+    std::printf("%d / %d optimal over %zu shard(s)\n", ok, B, devs.size());
+    std::printf("updateParam + solve vs updateRHS of the host-evaluated vectors: %s\n", same_all ? "bit-identical" : "DIFFERENT");
+    // (2) a sub-range: instances [B/4, B/2) move on to step 1's theta
+    const int first = B / 4, count = B / 2 - B / 4;
+    vectors_of(th1, C, H, Bv);
+    ref->updateRHS(C.data() + (size_t)first * n, m ? H.data() + (size_t)first * m : nullptr, p ? Bv.data() + (size_t)first * p : nullptr, first, count);
+    s->updateParam(th1.data() + (size_t)first * k, first, count);
+    const bool same_sub = ref->solve() == s->solve() && same(ref->solution(), s->solution());
+    std::printf("sub-range updateParam: %s\n", same_sub ? "bit-identical" : "DIFFERENT");
+    delete ref; delete s;
+
+    // (3) closed loop with warm starts, three forms side by side (each on its own solver, the same data in the same order)
+    typedef int (*malloc_fn)(void **, size_t);
+    typedef int (*memcpy_fn)(void *, const void *, size_t, int);
+    typedef int (*free_fn)(void *);
+    typedef int (*setdev_fn)(int);
+    const malloc_fn dmalloc = (malloc_fn)dlsym(RTLD_DEFAULT, "hipMalloc");
+    const memcpy_fn dmemcpy = (memcpy_fn)dlsym(RTLD_DEFAULT, "hipMemcpy");
+    const free_fn dfree = (free_fn)dlsym(RTLD_DEFAULT, "hipFree");
+    const setdev_fn dsetdev = (setdev_fn)dlsym(RTLD_DEFAULT, "hipSetDevice");
+    EiCOS::BatchSolver *sa = make(), *sb = make(), *sc = nullptr;
+    double *dC = nullptr, *dH = nullptr, *dB = nullptr;
+    if (dmalloc && dmemcpy && dfree && dsetdev && dsetdev(devs[0]) == 0 && dmalloc((void **)&dC, C0.size() * 8 + 8) == 0 &&
+        dmalloc((void **)&dH, H0.size() * 8 + 8) == 0 && dmalloc((void **)&dB, B0.size() * 8 + 8) == 0)
+        sc = make();
+    sb->setParamMap(k, &mc, m ? &mh : nullptr, p ? &mb : nullptr);
+    for (EiCOS::BatchSolver *v : {sa, sb, sc}) if (v) v->setWarmStart(0.1);
+    std::vector<double> ta, tb, tc;
+    bool same_loop = true;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms = [](std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1) { return std::chrono::duration<double, std::milli>(t1 - t0).count(); };
+    for (int st = 0; st < steps + 2; st++) { // (the first two steps warm the paths up and are not timed)
+        const std::vector<double> th = theta_of(st + 2);
+        vectors_of(th, C, H, Bv);
+        auto t0 = now();
+        sa->updateRHS(C.data(), m ? H.data() : nullptr, p ? Bv.data() : nullptr);
+        const std::vector<EiCOS::exitcode> ca = sa->solve();
+        auto t1 = now();
+        sb->updateParam(th.data());
+        const std::vector<EiCOS::exitcode> cb = sb->solve();
+        auto t2 = now();
+        same_loop = same_loop && ca == cb && same(sa->solution(), sb->solution());
+        if (st >= 2) { ta.push_back(ms(t0, t1)); tb.push_back(ms(t1, t2)); }
+        if (sc) {
+            dmemcpy(dC, C.data(), C.size() * 8, 1); dmemcpy(dH, H.data(), H.size() * 8, 1); dmemcpy(dB, Bv.data(), Bv.size() * 8, 1); // (host to device)
+            auto t3 = now();
+            sc->updateRHSDevice(devs[0], dC, m ? dH : nullptr, p ? dB : nullptr);
+            const std::vector<EiCOS::exitcode> cc = sc->solve();
+            auto t4 = now();
+            same_loop = same_loop && ca == cc && same(sa->solution(), sc->solution());
+            if (st >= 2) tc.push_back(ms(t3, t4));
+        }
+    }
+    const bool device_leg = sc != nullptr;
+    delete sa; delete sb; delete sc;
+    if (dfree) for (double *d : {dC, dH, dB}) if (d) dfree(d);
+    std::printf("closed loop, every step: %s\n", same_loop ? "bit-identical" : "DIFFERENT");
+    auto median = [](std::vector<double> v) { std::sort(v.begin(), v.end()); return v.empty() ? 0. : 0.5 * (v[(v.size() - 1) / 2] + v[v.size() / 2]); };
+    std::printf("closed loop step (update call -> end of solve), batch %d, median of %d steps: updateRHS %.3f ms (%.1f kB per instance), "
+                "updateParam k = %d %.3f ms (%.3f kB per instance)", B, steps, median(ta), 8e-3 * (n + m + p), k, median(tb), 8e-3 * k);
+    if (device_leg) std::printf(", updateRHSDevice %.3f ms\n", median(tc)); else std::printf(", updateRHSDevice n/a\n");
+    return (same_all && same_sub && same_loop) ? 0 : 1; // (bit-identity is the contract: it holds for every exit code)
+}

@@ -146,6 +146,22 @@ namespace EiCOS
         {
             mcheck(eicos_multi_update_rhs_device(h_, src_device, first, count < 0 ? batch_ : count, dc, dh, db), "eicos_multi_update_rhs_device");
         }
+        // Extension: right-hand sides that are affine in a short parameter row, c = c0 + C theta, h = h0 + H theta, b = b0 + B theta
+        // (eicos_affine_map: base vector + CSR matrix with k columns; nullptr = that group is not parametric and is kept).  The map is
+        // copied to every shard once; updateParam then sends [count][k] doubles and the GPU expands them -- bit for bit what updateRHS of
+        // the host-evaluated vectors leaves (rounding order: eicos_batch_update_param of eicos_amd.h).  All groups nullptr removes the map.
+        void setParamMap(int k, const eicos_affine_map *c, const eicos_affine_map *h, const eicos_affine_map *b)
+        {
+            mcheck(eicos_multi_set_param_map(h_, k, c, h, b), "eicos_multi_set_param_map");
+        }
+        void updateParam(const double *theta, int first = 0, int count = -1)
+        {
+            mcheck(eicos_multi_update_param(h_, first, count < 0 ? batch_ : count, theta), "eicos_multi_update_param");
+        }
+        void updateParamDevice(int src_device, const double *dtheta, int first = 0, int count = -1)
+        {
+            mcheck(eicos_multi_update_param_device(h_, src_device, first, count < 0 ? batch_ : count, dtheta), "eicos_multi_update_param_device");
+        }
         // Extension (not in the reference): re-solves start from the previous solution, see eicos_amd.h
         void setWarmStart(double shift) { mcheck(eicos_multi_set_warm_start(h_, shift), "eicos_multi_set_warm_start"); }
         // Extension: ECOS-style dynamic regularisation (the reference's Settings::delta / ::eps are never read)

@@ -165,6 +165,27 @@ int eicos_batch_update_rhs_device(eicos_batch *hd, int first, int count, const d
  * without an LDS vector, eicos_batch_update_rhs + eicos_batch_solve.  Bit-identical on every path. */
 int eicos_batch_update_rhs_solve(eicos_batch *hd, const double *c, const double *h, const double *b, double *x_out, int *exitcodes);
 
+/* ---- parametric right-hand sides (no reference counterpart).  In a closed loop c, h and b are usually affine in a few numbers -- the
+ * measured state, a reference, some bounds: c = c0 + C theta, h = h0 + H theta, b = b0 + B theta with theta of length k.  A handle holds
+ * one such map for all its instances; per step only theta travels ([count][k] doubles, 8 k bytes per instance) and the GPU expands it.
+ * eicos_affine_map: base[rows] and a CSR matrix rows x k (rowptr[rows + 1], col / val[rowptr[rows]]), rows = n, m, p for c, h, b.
+ * eicos_batch_set_param_map COPIES the host arrays; a NULL group is not parametric and is kept by the update, exactly as a NULL group of
+ * eicos_batch_update_rhs; a later call replaces the map, all groups NULL (or k = 0) removes it.  EICOS_E_INVALID, with a message naming the
+ * fault, for rowptr[0] != 0, decreasing row pointers, a column outside [0, k) and a map for a group the pattern does not have (values are
+ * not checked for finiteness, as elsewhere).  eicos_batch_param_count: k, 0 = no map installed.
+ * eicos_batch_update_param for instance i, row r of a mapped group:
+ *     acc = base[r];  for t in rowptr[r] .. rowptr[r+1]-1, in stored order:  acc = acc + (val[t] * theta[i][col[t]])
+ * with the product and the sum EACH rounded to fp64 (no fused multiply-add), then the division by the stored scaling with which
+ * eicos_batch_update_rhs ends.  The state it leaves therefore equals, bit for bit, that of eicos_batch_update_rhs on vectors evaluated
+ * on the host in that order; A, G, the scalings and the solve state are not touched.  theta takes the paths of eicos_batch_update
+ * (pageable: bounce pipeline, path 1; pinned / registered: read in place, path 2); the host form is synchronous in the same way, the
+ * _device form asynchronous like eicos_batch_update_rhs_device.  EICOS_E_INVALID without a map ("no parameter map"). */
+typedef struct eicos_affine_map { const double *base; const int *rowptr; const int *col; const double *val; } eicos_affine_map;
+int eicos_batch_set_param_map(eicos_batch *hd, int k, const eicos_affine_map *c, const eicos_affine_map *h, const eicos_affine_map *b);
+int eicos_batch_param_count(eicos_batch *hd);
+int eicos_batch_update_param(eicos_batch *hd, int first, int count, const double *theta /* host [count][k] */);
+int eicos_batch_update_param_device(eicos_batch *hd, int first, int count, const double *dtheta);
+
 /* ---- solve: replaces exitcode Solver::solve(bool) (reference include/eicos.hpp:158,
  * src/eicos.cpp:848-1262) for every instance of the batch.  exitcodes (host, [batch]) may be
  * NULL.  Synchronous: returns after the GPU work has completed. */
@@ -270,6 +291,12 @@ int eicos_multi_update_device(eicos_multi *mh, int src_device, int first, int co
 int eicos_multi_update_rhs(eicos_multi *mh, int first, int count, const double *c, const double *h, const double *b);
 int eicos_multi_update_rhs_device(eicos_multi *mh, int src_device, int first, int count, const double *dc, const double *dh, const double *db);
 int eicos_multi_update_rhs_solve(eicos_multi *mh, const double *c, const double *h, const double *b, double *x_out, int *exitcodes);
+/* parametric right-hand sides (eicos_batch_set_param_map / _update_param / _update_param_device on every shard): the map is installed on
+ * every shard, theta rows [count][k] are in global instance order; src_device as for eicos_multi_update_rhs_device */
+int eicos_multi_set_param_map(eicos_multi *mh, int k, const eicos_affine_map *c, const eicos_affine_map *h, const eicos_affine_map *b);
+int eicos_multi_param_count(eicos_multi *mh);
+int eicos_multi_update_param(eicos_multi *mh, int first, int count, const double *theta);
+int eicos_multi_update_param_device(eicos_multi *mh, int src_device, int first, int count, const double *dtheta);
 /* solve: async = enqueue every shard's kernels on its stream and return; sync waits for all; eicos_multi_solve = both (+ exit codes, may be NULL) */
 int eicos_multi_solve_async(eicos_multi *mh);
 int eicos_multi_sync(eicos_multi *mh);
