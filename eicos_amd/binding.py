@@ -116,6 +116,16 @@ def _lib():
             L.eicos_multi_update_param_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
             for f in ("set_param_map", "param_count", "update_param", "update_param_device"):
                 getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+        if hasattr(L, "eicos_batch_set_output_map"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            mp = C.POINTER(AffineMap)
+            L.eicos_batch_set_output_map.argtypes = L.eicos_multi_set_output_map.argtypes = [vp, C.c_int, mp]
+            L.eicos_batch_output_count.argtypes = L.eicos_multi_output_count.argtypes = [vp]
+            L.eicos_batch_outputs.argtypes = L.eicos_multi_outputs.argtypes = [vp, C.c_int, C.c_int, dp]
+            L.eicos_batch_outputs_device.argtypes = [vp, C.c_int, C.c_int, vp]
+            L.eicos_batch_update_param_solve.argtypes = L.eicos_multi_update_param_solve.argtypes = [vp, dp, dp, dp, ip]
+            for f in ("set_output_map", "output_count", "outputs", "update_param_solve"):
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+            L.eicos_batch_outputs_device.restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -304,6 +314,53 @@ def _param_map_ptrs(pmap, pat):
     return keep, ptrs
 
 
+class OutputMap:
+    """The numbers of x a controller applies, u = u0 + U x with u of length r: `(base, rowptr, col, val)` -- base[r] and a CSR matrix with
+    n columns -- shared by all instances.  evaluate() is the host restatement of what outputs() / update_param_solve compute on the GPU,
+    in the same rounding order."""
+
+    def __init__(self, n: int, u):
+        self.n = int(n)
+        self.base, self.rowptr, self.col, self.val = (np.ascontiguousarray(u[0], np.float64), np.ascontiguousarray(u[1], np.int32),
+                                                      np.ascontiguousarray(u[2], np.int32), np.ascontiguousarray(u[3], np.float64))
+        self.r = int(self.base.size)
+
+    def evaluate(self, x):
+        """u [B, r] for x [B, n].  Row `row`: acc = base[row], then for every stored entry t of the row, in stored order,
+        acc = acc + (val[t] * x[col[t]]) -- the product and the sum each rounded to float64 (numpy has no fused multiply-add), which is
+        the order of eicos_batch_outputs."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self.n:
+            raise ValueError(f"x has shape {x.shape}, expected [count, {self.n}]")
+        acc = np.repeat(self.base[None, :], x.shape[0], axis=0)
+        length = np.diff(self.rowptr)
+        for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
+            rows = np.nonzero(length > j)[0]
+            t = self.rowptr[rows] + j
+            acc[:, rows] = acc[:, rows] + self.val[t][None, :] * x[:, self.col[t]]
+        return acc
+
+
+def _output_map_ptr(omap, pat):
+    """An OutputMap as (keep-alive objects, C pointer to eicos_affine_map); array sizes are checked here, their contents (row pointers,
+    column range) by the library."""
+    base, rowptr, col, val = omap.base, omap.rowptr, omap.col, omap.val
+    if omap.n != pat.n or rowptr.size != omap.r + 1 or col.size != val.size or rowptr[-1] > col.size:
+        raise ValueError(f"output map: n = {omap.n}, base[{base.size}], rowptr[{rowptr.size}], col[{col.size}], val[{val.size}] do not "
+                         f"describe {omap.r} rows over {pat.n} variables")
+    one = np.zeros(1)
+    m = AffineMap(_dp(base if base.size else one), _ip(rowptr), _ip(col if col.size else np.zeros(1, np.int32)), _dp(val if val.size else one))
+    return (m, one), C.pointer(m)
+
+
+def _result_rows(a, rows, width, name):
+    """A caller-owned result array: C-contiguous float64 [rows, width] (None passes); ValueError otherwise."""
+    if a is not None and not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == (rows, width)):
+        raise ValueError(f"{name} must be a C-contiguous float64 array of shape [{rows}, {width}]"
+                         + (f", not {a.dtype} {a.shape}" if isinstance(a, np.ndarray) else ""))
+    return a
+
+
 def _theta_rows(theta, k, count):
     """theta as a contiguous float64 [count, k] array (count None: its leading dimension); ValueError otherwise."""
     theta = np.ascontiguousarray(theta, dtype=np.float64)
@@ -394,6 +451,43 @@ class _Solver:
             count = (theta.shape[0] if theta.ndim == 2 else self.batch) if count is None else count
         self._call("update_param", first, count, _dp(theta) if theta.size else _dp(np.zeros(1)))
 
+    # ---- output map and the closed-loop step (include/eicos_amd.h: eicos_batch_set_output_map / eicos_batch_update_param_solve) ----
+    def set_output_map(self, omap: "OutputMap | None"):
+        """Install (copy) an OutputMap for all instances; None, or a map without rows, removes the installed one."""
+        if omap is None or omap.r == 0:
+            self._call("set_output_map", 0, None)
+            return
+        _keep, ptr = _output_map_ptr(omap, self.pat)
+        self._call("set_output_map", omap.r, ptr)
+
+    def output_count(self) -> int:
+        """r of the installed output map, 0 without one."""
+        return int(getattr(_lib(), self._prefix + "output_count")(self._h))
+
+    def outputs(self, first: int = 0, count: int | None = None):
+        """u [count, r] of instances [first, first + count): the output map applied to their current x -- bit for bit
+        OutputMap.evaluate(solution()[first:first + count])."""
+        count = self.batch - first if count is None else count
+        u = np.zeros((max(count, 0), self.output_count()))
+        self._call("outputs", first, count, _dp(u) if u.size else _dp(np.zeros(1)))
+        return u
+
+    def update_param_solve(self, theta, u_out=None, x_out=None):
+        """The closed-loop step in one call: update_param(theta) + solve() of the whole batch, u (and x) delivered into `u_out` [batch, r]
+        (and `x_out` [batch, n]) -- with pinned / registered theta the solve kernel expands every instance's theta row itself and writes
+        its rows into pinned result arrays.  Returns the exit codes."""
+        k = self.param_count()
+        if k > 0:
+            theta, _ = _theta_rows(theta, k, self.batch)
+        else:  # (the library refuses: "no parameter map")
+            theta = np.ascontiguousarray(theta, dtype=np.float64)
+        _result_rows(u_out, self.batch, self.output_count(), "u_out")
+        _result_rows(x_out, self.batch, self.pat.n, "x_out")
+        codes = np.zeros(self.batch, np.int32)
+        self._call("update_param_solve", _dp(theta) if theta.size else _dp(np.zeros(1)), _dp(u_out) if (u_out is not None and u_out.size) else None,
+                   _dp(x_out) if (x_out is not None and x_out.size) else None, _ip(codes))
+        return codes
+
     # ---- solve ----
     def solve(self):
         codes = np.zeros(self.batch, np.int32)
@@ -481,6 +575,11 @@ class BatchSolver(_Solver):
         """update_param from a raw device pointer (int) to theta [count, k].  Asynchronous, like update_rhs_device."""
         count = self.batch if count is None else count
         self._call("update_param_device", first, count, C.c_void_p(int(dtheta) or None))
+
+    def outputs_device(self, du, first: int = 0, count: int | None = None):
+        """outputs() into a raw device pointer (int) to u [count, r].  Asynchronous on the handle's stream."""
+        count = self.batch - first if count is None else count
+        self._call("outputs_device", first, count, C.c_void_p(int(du) or None))
 
     def set_stream(self, stream_ptr: int):
         self._call("set_stream", C.c_void_p(int(stream_ptr) or None))

@@ -119,7 +119,11 @@ struct eicos_batch {
     double *stage_pin = nullptr; size_t stage_pin_doubles = 0; unsigned *stage_flags = nullptr; int stage_nflags = 0; unsigned stage_seq = 0;
     int *d_err = nullptr;
     // parametric right-hand sides (eicos_batch_set_param_map): the map's arrays in one device allocation, param.k = 0 while none is installed
+    // (d_param starts with a device copy of `param` itself, MAP_HEADER bytes: what the fused step's workgroups read -- launch.hpp: UpdArgs)
     ParamMapDev param{}; void *d_param = nullptr;
+    // output map (eicos_batch_set_output_map): one device allocation [OutMapDev | u rows of the batch | base, val | rowptr, col], out.r = 0
+    // while none is installed; d_u = the [batch][r] rows the range kernel fills for a host destination
+    OutMapDev out{}; void *d_out = nullptr; double *d_u = nullptr;
     TilePlan tiles;        // tile mode (Symbolic::tile): the dense-front plan
 };
 
@@ -1028,7 +1032,7 @@ int eicos_batch_destroy(eicos_batch *h) {
     for (int i = 0; i < eicos_batch::EV_RING; i++)
         for (hipEvent_t e : {h->ring_s[i][0], h->ring_s[i][1], h->ring_u[i][0], h->ring_u[i][1]}) if (e) (void)hipEventDestroy(e);
     for (void *ptr : {(void *)h->d_pattern, (void *)h->d_inst, (void *)h->d_work, (void *)h->d_queue, (void *)h->d_scratch,
-                      (void *)h->d_stage, (void *)h->d_flag, h->d_param})
+                      (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out})
         if (ptr) (void)hipFree(ptr);
     for (int i = 0; i < 2; i++) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     if (h->stage_pin) (void)hipHostFree(h->stage_pin);
@@ -1467,7 +1471,10 @@ int eicos_batch_update_rhs(eicos_batch *h, int first, int count, const double *c
 
 // ---- parametric right-hand sides: c, h, b affine in a short parameter row theta (no reference counterpart) ----
 // The map is validated on the host, packed into ONE device allocation ([doubles: base, val per group | ints: rowptr, col per group]) and
-// handed to the kernel by value (ParamMapDev); a later call replaces it, all groups NULL or k = 0 removes it.
+// handed to the range kernel by value (ParamMapDev); the allocation starts with a copy of that descriptor, which the fused step reads
+// through a pointer.  A later call replaces the map, all groups NULL or k = 0 removes it.
+static constexpr size_t MAP_HEADER = 128; // bytes kept for the descriptor in front of a map's arrays (keeps the doubles aligned)
+static_assert(sizeof(ParamMapDev) <= MAP_HEADER && sizeof(OutMapDev) <= MAP_HEADER, "map descriptor larger than its header");
 int eicos_batch_set_param_map(eicos_batch *h, int k, const eicos_affine_map *c, const eicos_affine_map *hh, const eicos_affine_map *b) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     if (k < 0) return fail(EICOS_E_INVALID, "parameter map: k must not be negative");
@@ -1497,13 +1504,13 @@ int eicos_batch_set_param_map(eicos_batch *h, int k, const eicos_affine_map *c, 
     if (h->d_param) { (void)hipFree(h->d_param); h->d_param = nullptr; }
     h->param = ParamMapDev{};
     if (remove) return EICOS_OK;
-    std::vector<char> buf(nd * sizeof(double) + ni * sizeof(int));
-    double *hd_ = reinterpret_cast<double *>(buf.data());
-    int *hi_ = reinterpret_cast<int *>(buf.data() + nd * sizeof(double));
+    std::vector<char> buf(MAP_HEADER + nd * sizeof(double) + ni * sizeof(int));
+    double *hd_ = reinterpret_cast<double *>(buf.data() + MAP_HEADER);
+    int *hi_ = reinterpret_cast<int *>(buf.data() + MAP_HEADER + nd * sizeof(double));
     void *dev = nullptr;
     HIP_TRY(hipMalloc(&dev, buf.size()));
-    const double *dd = static_cast<const double *>(dev);
-    const int *di = reinterpret_cast<const int *>(static_cast<const char *>(dev) + nd * sizeof(double));
+    const double *dd = reinterpret_cast<const double *>(static_cast<const char *>(dev) + MAP_HEADER);
+    const int *di = reinterpret_cast<const int *>(static_cast<const char *>(dev) + MAP_HEADER + nd * sizeof(double));
     ParamMapDev M{};
     M.k = k;
     size_t od = 0, oi = 0;
@@ -1515,6 +1522,7 @@ int eicos_batch_set_param_map(eicos_batch *h, int k, const eicos_affine_map *c, 
         M.g[q].rowptr = di + oi; std::copy(g[q]->rowptr, g[q]->rowptr + rows[q] + 1, hi_ + oi); oi += rows[q] + 1;
         M.g[q].col = di + oi; if (nnz) std::copy(g[q]->col, g[q]->col + nnz, hi_ + oi); oi += nnz;
     }
+    std::memcpy(buf.data(), &M, sizeof M);
     const hipError_t e = hipMemcpy(dev, buf.data(), buf.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the parameter map: ") + hipGetErrorString(e)); }
     h->d_param = dev; h->param = M;
@@ -1538,6 +1546,94 @@ int eicos_batch_update_param_device(eicos_batch *h, int first, int count, const 
     UpdateInputs in;
     const int rc = take_theta(in, h, first, count, dtheta, false);
     return rc != EICOS_OK ? rc : update_in_place(in, 0);
+}
+
+// ---- output map: u = u0 + U x, the few numbers of x a controller applies (no reference counterpart) ----
+// Validated like the parameter map and packed into ONE device allocation: [OutMapDev (MAP_HEADER bytes) | u rows of the batch | base, val |
+// rowptr, col].  The range kernel takes the descriptor by value, the fused step through a pointer to its device copy.
+int eicos_batch_set_output_map(eicos_batch *h, int r, const eicos_affine_map *u) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (r < 0) return fail(EICOS_E_INVALID, "output map: r must not be negative");
+    const DevPat &D = h->dp;
+    const bool remove = r == 0 || !u;
+    int nnz = 0;
+    if (!remove) {
+        const std::string who = "output map: ";
+        if (D.n == 0) return fail(EICOS_E_INVALID, who + "the pattern has no variables (n = 0)");
+        if (!u->base || !u->rowptr) return fail(EICOS_E_INVALID, who + "base or rowptr is NULL");
+        const int *rp = u->rowptr;
+        if (rp[0] != 0) return fail(EICOS_E_INVALID, who + "rowptr[0] must be 0");
+        for (int q = 0; q < r; q++)
+            if (rp[q + 1] < rp[q]) return fail(EICOS_E_INVALID, who + "rowptr decreases at row " + std::to_string(q));
+        nnz = rp[r];
+        if (nnz > 0 && (!u->col || !u->val)) return fail(EICOS_E_INVALID, who + "col or val is NULL");
+        for (int t = 0; t < nnz; t++)
+            if (u->col[t] < 0 || u->col[t] >= D.n) return fail(EICOS_E_INVALID, who + "column " + std::to_string(u->col[t]) + " of entry " + std::to_string(t) + " is outside [0, n)");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
+    if (h->d_out) { (void)hipFree(h->d_out); h->d_out = nullptr; }
+    h->out = OutMapDev{}; h->d_u = nullptr;
+    if (remove) return EICOS_OK;
+    const size_t rows_b = (size_t)h->batch * r * sizeof(double), nd = (size_t)r + nnz, ni = (size_t)r + 1 + nnz;
+    std::vector<char> buf(MAP_HEADER + nd * sizeof(double) + ni * sizeof(int)); // (everything but the u rows, which stay uninitialised)
+    void *dev = nullptr;
+    HIP_TRY(hipMalloc(&dev, MAP_HEADER + rows_b + nd * sizeof(double) + ni * sizeof(int)));
+    char *dc = static_cast<char *>(dev);
+    const double *dd = reinterpret_cast<const double *>(dc + MAP_HEADER + rows_b);
+    const int *di = reinterpret_cast<const int *>(dc + MAP_HEADER + rows_b + nd * sizeof(double));
+    double *hd_ = reinterpret_cast<double *>(buf.data() + MAP_HEADER);
+    int *hi_ = reinterpret_cast<int *>(buf.data() + MAP_HEADER + nd * sizeof(double));
+    OutMapDev M{};
+    M.r = r;
+    M.a.base = dd; std::copy(u->base, u->base + r, hd_);
+    M.a.val = dd + r; if (nnz) std::copy(u->val, u->val + nnz, hd_ + r);
+    M.a.rowptr = di; std::copy(u->rowptr, u->rowptr + r + 1, hi_);
+    M.a.col = di + r + 1; if (nnz) std::copy(u->col, u->col + nnz, hi_ + r + 1);
+    std::memcpy(buf.data(), &M, sizeof M);
+    hipError_t e = hipMemcpy(dc, buf.data(), MAP_HEADER, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dc + MAP_HEADER + rows_b, buf.data() + MAP_HEADER, buf.size() - MAP_HEADER, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the output map: ") + hipGetErrorString(e)); }
+    h->d_out = dev; h->out = M; h->d_u = reinterpret_cast<double *>(dc + MAP_HEADER);
+    return EICOS_OK;
+}
+
+int eicos_batch_output_count(eicos_batch *h) { return h ? h->out.r : fail(EICOS_E_INVALID, "NULL handle"); }
+
+static int fetch_strided(eicos_batch *h, double *dst, const double *src, size_t pitch, int width, int count); // (with the result paths, below)
+static int take_output_range(eicos_batch *h, int first, int count, const double *u) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (h->out.r == 0) return fail(EICOS_E_INVALID, "no output map (eicos_batch_set_output_map installs one)");
+    if (first < 0 || count < 0 || first + count > h->batch) return fail(EICOS_E_INVALID, "instance range out of bounds");
+    if (!u && count > 0) return fail(EICOS_E_INVALID, "u is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    return EICOS_OK;
+}
+
+// the output rows of instances [first, first + count) into `u` [count][r], wherever it lives: device memory is written by the range kernel
+// itself (asynchronous), host memory gets the handle's rows d_u over the paths of fetch_strided (synchronous)
+static int outputs_to(eicos_batch *h, int first, int count, double *u, MemKind kind) {
+    if (count == 0) return EICOS_OK;
+    if (kind == MEM_DEVICE) { HIP_TRY(launch_outputs(h->pslot, h->d_inst, first, count, h->out, u, h->stream)); return EICOS_OK; }
+    double *rows = h->d_u + (size_t)first * h->out.r;
+    HIP_TRY(launch_outputs(h->pslot, h->d_inst, first, count, h->out, rows, h->stream));
+    const int rc = fetch_strided(h, u, rows, (size_t)h->out.r * sizeof(double), h->out.r, count);
+    if (rc != EICOS_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return EICOS_OK;
+}
+
+int eicos_batch_outputs(eicos_batch *h, int first, int count, double *u) {
+    const int rc = take_output_range(h, first, count, u);
+    if (rc != EICOS_OK) return rc;
+    if (count > 0 && memory_kind(u, 1) == MEM_DEVICE) return fail(EICOS_E_INVALID, "eicos_batch_outputs takes a host pointer: u lives in device memory (use eicos_batch_outputs_device)");
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return outputs_to(h, first, count, u, MEM_PAGEABLE);
+}
+
+int eicos_batch_outputs_device(eicos_batch *h, int first, int count, double *du) {
+    const int rc = take_output_range(h, first, count, du);
+    return rc != EICOS_OK ? rc : outputs_to(h, first, count, du, MEM_DEVICE);
 }
 
 int eicos_batch_solve_async(eicos_batch *h) {
@@ -1565,38 +1661,42 @@ int eicos_batch_sync(eicos_batch *h) {
 // rows [off, off + width) of every instance slab -> dst[batch][width] on the host.  Pinned destination: one strided device-to-host copy
 // straight into it.  Pageable destination: chunks through the two pinned bounce buffers, the copy of chunk k + 1 in flight while the
 // host copies chunk k out (a strided hipMemcpy2D into pageable memory is staged by the runtime row by row).
-static int fetch_rows(eicos_batch *h, double *dst, int off, int width) {
-    if (!dst || width == 0) return EICOS_OK;
-    const size_t wb = (size_t)width * sizeof(double), pitch = h->dp.inst_stride * sizeof(double);
+// fetch_strided: `count` rows of `width` doubles, `pitch` bytes apart in device memory at src (the output rows of eicos_batch_outputs too).
+static int fetch_strided(eicos_batch *h, double *dst, const double *src, size_t pitch, int width, int count) {
+    if (!dst || width == 0 || count == 0) return EICOS_OK;
+    const size_t wb = (size_t)width * sizeof(double), stride = pitch / sizeof(double);
     // (a small result takes the one strided copy as well, unless it starts in pinned memory that ends before it does)
-    if (memory_kind(dst, (size_t)h->batch * wb) == MEM_PINNED || ((size_t)h->batch * wb < (256u << 10) && memory_kind(dst, 1) != MEM_PINNED)) {
-        HIP_TRY(hipMemcpy2DAsync(dst, wb, h->d_inst + off, pitch, wb, (size_t)h->batch, hipMemcpyDeviceToHost, h->stream));
+    if (memory_kind(dst, (size_t)count * wb) == MEM_PINNED || ((size_t)count * wb < (256u << 10) && memory_kind(dst, 1) != MEM_PINNED)) {
+        HIP_TRY(hipMemcpy2DAsync(dst, wb, src, pitch, wb, (size_t)count, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         return EICOS_OK;
     }
     // (chunks of ~4 MB: small enough that the device-to-host copy of one chunk and the host copy of the previous one overlap on a result of a few MB)
     int chunk = (int)std::max<size_t>(16, (PIN_CHUNK_BYTES / 4) / wb);
-    chunk = std::min(chunk, h->batch);
+    chunk = std::min(chunk, count);
     int rc = ensure_pin(h, (size_t)chunk * width);
     if (rc != EICOS_OK) return rc;
     for (int i = 0; i < 2; i++) if (h->pin_busy[i]) { HIP_TRY(hipEventSynchronize(h->pin_ev[i])); h->pin_busy[i] = false; }
     CopyPool &pool = CopyPool::get();
     auto issue = [&](int o, int bi) -> int {
-        const int cnt = std::min(chunk, h->batch - o);
-        HIP_TRY(hipMemcpy2DAsync(h->pin[bi], wb, h->d_inst + (size_t)o * h->dp.inst_stride + off, pitch, wb, (size_t)cnt, hipMemcpyDeviceToHost, h->stream));
+        const int cnt = std::min(chunk, count - o);
+        HIP_TRY(hipMemcpy2DAsync(h->pin[bi], wb, src + (size_t)o * stride, pitch, wb, (size_t)cnt, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipEventRecord(h->pin_ev[bi], h->stream));
         return EICOS_OK;
     };
     rc = issue(0, 0);
     int k = 0;
-    for (int o = 0; o < h->batch && rc == EICOS_OK; o += chunk, k++) {
-        const int cnt = std::min(chunk, h->batch - o), bi = k & 1;
-        if (o + chunk < h->batch) rc = issue(o + chunk, bi ^ 1);
+    for (int o = 0; o < count && rc == EICOS_OK; o += chunk, k++) {
+        const int cnt = std::min(chunk, count - o), bi = k & 1;
+        if (o + chunk < count) rc = issue(o + chunk, bi ^ 1);
         if (rc != EICOS_OK) break;
         HIP_TRY(hipEventSynchronize(h->pin_ev[bi]));
         pool.copy(dst + (size_t)o * width, h->pin[bi], (size_t)cnt * wb);
     }
     return rc;
+}
+static int fetch_rows(eicos_batch *h, double *dst, int off, int width) {
+    return fetch_strided(h, dst, h->d_inst + off, h->dp.inst_stride * sizeof(double), width, h->batch);
 }
 
 int eicos_batch_info(eicos_batch *h, eicos_info *info) {
@@ -1648,22 +1748,30 @@ int eicos_batch_solve(eicos_batch *h, int *exitcodes) {
 // every path.
 // Synchronous; exitcodes optional.  rhs = true: the right-hand-side-only update (G, A NULL; h and b read on their own; no accumulator limit:
 // the fused form divides by the stored scalings, kernels.hip: rhs_instance), eicos_batch_update_rhs_solve.
+// kind = STEP_PARAM: the parametric update (theta [batch][k] through the installed map, the five arrays NULL; fused while a theta row fits
+// the LDS vector the workgroup stages it in, kernels.hip: param_instance; pageable theta is never staged), eicos_batch_update_param_solve.
+// u_out (optional, [batch][r]; any kind, needs an output map): the output map applied to every instance's x, delivered like x_out -- written
+// by the kernel where it can be, by the range kernel and a copy otherwise.
+enum StepKind { STEP_FULL = 0, STEP_RHS = 1, STEP_PARAM = 2 };
 static int update_solve(eicos_batch *h, const double *G, const double *A, const double *c, const double *hh, const double *b,
-                        double *x_out, int *exitcodes, bool rhs) {
+                        const double *theta, double *u_out, double *x_out, int *exitcodes, StepKind kind) {
     UpdateInputs in;
-    int rc = take_inputs(in, h, 0, h ? h->batch : 0, G, A, c, hh, b, rhs, true);
+    const bool rhs = kind == STEP_RHS, param = kind == STEP_PARAM;
+    int rc = param ? take_theta(in, h, 0, h ? h->batch : 0, theta, true) : take_inputs(in, h, 0, h ? h->batch : 0, G, A, c, hh, b, rhs, true);
     if (rc != EICOS_OK) return rc;
+    if (u_out && h->out.r == 0) return fail(EICOS_E_INVALID, "no output map (eicos_batch_set_output_map installs one)");
     const DevPat &D = h->dp;
-    const bool fused = h->nlds >= 1 && (rhs || (D.n <= 8 * h->threads && D.p <= 8 * h->threads && D.m <= 16 * h->threads)) &&
-                       env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
+    const bool fits = param ? h->param.k <= D.Npad : (rhs || (D.n <= 8 * h->threads && D.p <= 8 * h->threads && D.m <= 16 * h->threads));
+    const bool fused = h->nlds >= 1 && fits && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
     // arrays the GPU cannot address (pageable memory) are STAGED: copied into the handle's pinned staging buffer while the kernel runs
     const bool any_staged = in.any(MEM_PAGEABLE);
     if (D.n == 0) x_out = nullptr;
     const MemKind x_kind = memory_kind(x_out, (size_t)h->batch * D.n * sizeof(double));
+    const MemKind u_kind = memory_kind(u_out, (size_t)h->batch * h->out.r * sizeof(double));
     // (staging pageable arrays while the kernel runs is OFF by default: measured on five boxes against the bounce pipeline + solve it is
     // +5.7 ... -6.2 % -- the host's copy is the pace either way, and on a box with slow host cores the kernel's own PCIe pulls and flag polls
     // slow that copy further; EICOS_FUSED_STAGED=1 under EICOS_EXPERIMENT=1 turns it on: docs/HISTORY.md A.11 item 9)
-    if (!fused || (any_staged && !env_knob("EICOS_FUSED_STAGED", 0, 0, 1))) {
+    if (!fused || (any_staged && (param || !env_knob("EICOS_FUSED_STAGED", 0, 0, 1)))) {
         // (device arrays on a handle without the fused path: the device-pointer updateData)
         rc = in.all(MEM_DEVICE) ? update_in_place(in, 0) : staged_update(in, -1);
         if (rc == EICOS_OK) rc = eicos_batch_solve_async(h);
@@ -1675,6 +1783,11 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
             HIP_TRY(hipMemcpy2DAsync(x_out, wb, h->d_inst + D.i_x, D.inst_stride * sizeof(double), wb, (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
         } else if (x_out) { rc = fetch_rows(h, x_out, D.i_x, D.n); if (rc != EICOS_OK) return rc; }
+        if (u_out) {
+            rc = outputs_to(h, 0, h->batch, u_out, u_kind);
+            if (rc != EICOS_OK) return rc;
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        }
     } else {
         const double *ptr[5] = {in.src[0], in.src[1], in.src[2], in.src[3], in.src[4]};
         bool staged[5];
@@ -1710,8 +1823,10 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
         h->last_update_path = any_staged ? 6 : 5;
         rc = end_update_timing(h, begin_update_timing(h)); // (an empty updateData interval in the timing ring: the work is inside the solve launch)
         if (rc != EICOS_OK) return rc;
-        h->fused = UpdArgs{ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], x_kind != MEM_PAGEABLE ? x_out : nullptr, rhs ? UPD_RHS : UPD_FULL,
-                           any_staged ? h->stage_flags : nullptr, chunk, h->stage_seq, h->d_err};
+        h->fused = UpdArgs{ptr[0], ptr[1], param ? nullptr : ptr[2], ptr[3], ptr[4], x_kind != MEM_PAGEABLE ? x_out : nullptr,
+                           param ? UPD_PARAM : (rhs ? UPD_RHS : UPD_FULL), any_staged ? h->stage_flags : nullptr, chunk, h->stage_seq, h->d_err,
+                           static_cast<const ParamMapDev *>(h->d_param), static_cast<const OutMapDev *>(h->d_out), param ? ptr[2] : nullptr,
+                           u_kind != MEM_PAGEABLE ? u_out : nullptr};
         h->fused_pending = true;
         rc = eicos_batch_solve_async(h);
         h->fused_pending = false;
@@ -1732,16 +1847,20 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
             if (err) { HIP_TRY(hipMemset(h->d_err, 0, sizeof(int))); return fail(EICOS_E_HIP, "fused updateData: a workgroup timed out waiting for its staged rows"); }
         }
         if (x_out && x_kind == MEM_PAGEABLE) { rc = fetch_rows(h, x_out, D.i_x, D.n); if (rc != EICOS_OK) return rc; }
+        if (u_out && u_kind == MEM_PAGEABLE) { rc = outputs_to(h, 0, h->batch, u_out, u_kind); if (rc != EICOS_OK) return rc; }
     }
     return exit_codes(h, exitcodes);
 }
 
 int eicos_batch_update_solve(eicos_batch *h, const double *G, const double *A, const double *c, const double *hh, const double *b,
                              double *x_out, int *exitcodes) {
-    return update_solve(h, G, A, c, hh, b, x_out, exitcodes, false);
+    return update_solve(h, G, A, c, hh, b, nullptr, nullptr, x_out, exitcodes, STEP_FULL);
 }
 int eicos_batch_update_rhs_solve(eicos_batch *h, const double *c, const double *hh, const double *b, double *x_out, int *exitcodes) {
-    return update_solve(h, nullptr, nullptr, c, hh, b, x_out, exitcodes, true);
+    return update_solve(h, nullptr, nullptr, c, hh, b, nullptr, nullptr, x_out, exitcodes, STEP_RHS);
+}
+int eicos_batch_update_param_solve(eicos_batch *h, const double *theta, double *u_out, double *x_out, int *exitcodes) {
+    return update_solve(h, nullptr, nullptr, nullptr, nullptr, nullptr, theta, u_out, x_out, exitcodes, STEP_PARAM);
 }
 
 int eicos_batch_solution(eicos_batch *h, double *x) {

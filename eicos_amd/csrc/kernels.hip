@@ -3229,6 +3229,53 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void rhs_instanc
     __syncthreads(); // (the solve -- or the LDS-resident build's copy of the slab -- reads entries other threads wrote)
 }
 
+// Parametric right-hand-side update of one instance by one workgroup (k_solve, fused: eicos_batch_update_param_solve; the range form is
+// k_update_param_range below): the instance's theta row is staged ONCE into the idle LDS KKT-space vector with unit-stride loads -- for
+// pinned host theta the only PCIe reads of the step --, then threads run over the entries of the mapped groups [c | h | b], each
+// accumulating its CSR row in stored order (product and sum rounded on their own) from the LDS copy and ending with rhs_entry's division
+// by the stored scaling.  The map (device memory, *Mp) is the same for every instance: served from L2.  k <= Npad (api.cpp).
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void param_instance(int ps, hbm_p I, size_t q, const ParamMapDev *Mp, const double *theta) {
+    ps = uni(ps); I = uni_ptr(I); Mp = uni_ptr(Mp); theta = uni_ptr(theta);
+    const DevPat &P = c_pat[ps];
+    const int k = Mp->k;
+    const AffineDev gc = Mp->g[0], gh = Mp->g[1], gb = Mp->g[2];
+    const bool eq = reinterpret_cast<const DevInfo EICOS_GLOBAL *>(I + P.i_info)->equilibrated != 0;
+    const int wc = gc.base ? P.n : 0, wh = gh.base ? P.m : 0, w = wc + wh + (gb.base ? P.p : 0);
+    const double *row = theta + q * (size_t)k;
+    double *th = g_dyn;
+    FOR_T(j, k) th[j] = row[j];
+    __syncthreads();
+    FOR_T(e, w) {
+        const int grp = e < wc ? 0 : (e < wc + wh ? 1 : 2), r = e - (grp == 0 ? 0 : (grp == 1 ? wc : wc + wh));
+        const AffineDev A = grp == 0 ? gc : (grp == 1 ? gh : gb);
+        const int i_dst = (grp == 0 ? P.i_c : (grp == 1 ? P.i_h : P.i_b)) + r, i_scl = (grp == 0 ? P.i_xe : (grp == 1 ? P.i_ge : P.i_ae)) + r;
+        double acc = A.base[r];
+        const int t1 = A.rowptr[r + 1];
+        for (int t = A.rowptr[r]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], th[A.col[t]]));
+        I[i_dst] = acc / (eq ? I[i_scl] : 1.);
+    }
+    __syncthreads(); // (the solve -- or the LDS-resident build's copy of the slab -- reads entries other threads wrote; the LDS vector is free again)
+}
+
+// The output map of one instance by one workgroup (k_solve, after solve_instance and its barrier): threads run over the r rows,
+// u[row] = base[row] + sum val * x[col] in stored order, product and sum rounded on their own, x read where the solve left it (the LDS
+// copy of the slab in the LDS-resident build, before the write-back) and the row stored straight to the caller's array.
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void outputs_instance(int ps, gcdbl_p I, size_t q, const OutMapDev *Mp, double *u) {
+    ps = uni(ps); I = uni_ptr(I); Mp = uni_ptr(Mp); u = uni_ptr(u);
+    const DevPat &P = c_pat[ps];
+    const int r = Mp->r;
+    const AffineDev A = Mp->a;
+    gcdbl_p x = I + P.i_x;
+    FOR_T(row, r) {
+        double acc = A.base[row];
+        const int t1 = A.rowptr[row + 1];
+        for (int t = A.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], x[A.col[t]]));
+        u[q * (size_t)r + row] = acc;
+    }
+}
+
 template <int T, int NLDS, bool I16>
 __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     int ps, double *inst, double *work, int B, int *queue, const int *order, double warm, double dyn_delta, double dyn_eps, UpdArgs upd) {
@@ -3280,7 +3327,8 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
                     __syncthreads();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, ""); // (system scope: the rows this workgroup reads next were written by the host)
                 }
-                if (upd.on == UPD_RHS) rhs_instance<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.c, upd.h, upd.b);
+                if (upd.on == UPD_PARAM) param_instance<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.pmap, upd.theta);
+                else if (upd.on == UPD_RHS) rhs_instance<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.c, upd.h, upd.b);
                 else update_instance<T, false>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.G, upd.A, upd.c, upd.h, upd.b);
             }
         }
@@ -3298,6 +3346,7 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
         solve_instance<T, NLDS, I16>(ps, I, W, warm);
         __syncthreads();
         if (upd.x) for (int j = threadIdx.x; j < P.n; j += T) upd.x[(size_t)id * P.n + j] = I[P.i_x + j]; // (fused path: the result straight to the caller's array)
+        if (upd.u) outputs_instance<T>(ps, I, (size_t)id, upd.omap, upd.u); // (the selected outputs of x, r doubles, likewise)
 #if EICOS_LDSRES
         { // results, persistent per-instance state and (for the debug readbacks) the workspace go back to HBM
             double *Ig = inst + (size_t)id * P.inst_stride;
@@ -3521,6 +3570,23 @@ __global__ __launch_bounds__(T) void k_update_param_range(int ps, double *inst, 
     }
 }
 
+// The output map over a range of instances (eicos_batch_outputs*; outputs_instance is the fused form): ROW-parallel over the count * r
+// rows, the map by value and served from L2, x read from the instance slabs.  Same arithmetic as outputs_instance.
+template <int T>
+__global__ __launch_bounds__(T) void k_outputs_range(int ps, const double *inst, int first, int count, OutMapDev M, double *u) {
+    const DevPat &P = c_pat[ps];
+    const size_t r = (size_t)M.r, total = (size_t)count * r;
+    for (size_t e = (size_t)blockIdx.x * T + threadIdx.x; e < total; e += (size_t)gridDim.x * T) {
+        const size_t q = e / r;
+        const int row = (int)(e - q * r);
+        const double *x = inst + (size_t)(first + q) * P.inst_stride + P.i_x;
+        double acc = M.a.base[row];
+        const int t1 = M.a.rowptr[row + 1];
+        for (int t = M.a.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(M.a.val[t], x[M.a.col[t]]));
+        u[e] = acc;
+    }
+}
+
 // Debug: factorise instance `i` with the KKT scaling block as it stands in memory (runs the solver's own stage).
 template <int T>
 __global__ __launch_bounds__(T, waves_per_eu<T>()) void k_debug_factor(int ps, double *inst, double *work, int i) {
@@ -3606,7 +3672,7 @@ template <class F> static auto dispatch_solve(int threads, int nlds, int idx16, 
 #endif
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds,
                         int idx16, int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd_in) {
-    UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr};
+    UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (upd.on && nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector; both modes live in the NLDS >= 1 kernels)
     if (B <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(queue, 0, sizeof(int), st); // group queue of this launch
@@ -3656,6 +3722,13 @@ hipError_t launch_update_param(int ps, double *inst, int first, int count, const
     const size_t lds = (size_t)PARAM_Q * map.k * sizeof(double);
     if (lds <= 32 * 1024) hipLaunchKernelGGL((k_update_param_range<T, true>), dim3((unsigned)gx, (unsigned)gy), dim3(T), lds, st, ps, inst, first, count, map, theta);
     else hipLaunchKernelGGL((k_update_param_range<T, false>), dim3((unsigned)gx, (unsigned)gy), dim3(T), 0, st, ps, inst, first, count, map, theta);
+    return hipGetLastError();
+}
+hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st) {
+    if (count <= 0 || map.r <= 0) return hipSuccess;
+    constexpr int T = 256;
+    const size_t nb = ((size_t)count * map.r + T - 1) / T;
+    hipLaunchKernelGGL(k_outputs_range<T>, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(T), 0, st, ps, inst, first, count, map, u);
     return hipGetLastError();
 }
 // the dynamic-LDS ceiling of the two entry-parallel updateData kernels, set once per handle on the handle's device

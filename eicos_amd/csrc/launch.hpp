@@ -11,9 +11,19 @@ namespace eicos {
 // kernel runs -- flags[instance / chunk] == seq once the chunk holding an instance has been copied (pinned, host-written); the workgroup polls
 // it before it touches the instance's rows (bounded: after ~5 s it gives up and raises *err).
 // on = UPD_FULL: updateData (G, A, c, h, b); on = UPD_RHS: the right-hand-side-only update (c, h, b scaled by the stored scalings; G, A
-// unused); 0: off.
-enum { UPD_FULL = 1, UPD_RHS = 2 };
-struct UpdArgs { const double *G, *A, *c, *h, *b; double *x; int on; const unsigned *flags; int chunk; unsigned seq; int *err; };
+// unused); on = UPD_PARAM: the parametric update (eicos_batch_update_param_solve) -- row `instance` of theta [batch][pmap->k] expanded
+// through *pmap, the five arrays unused; 0: off.
+// u != NULL (any mode, 0 included): row `instance` of u [batch][omap->r] = the output map applied to the instance's x, written like x.
+// The two maps stay in device memory and travel as pointers: a launch that uses neither pays four words of kernel arguments for them.
+enum { UPD_FULL = 1, UPD_RHS = 2, UPD_PARAM = 3 };
+struct AffineDev { const double *base; const int *rowptr, *col; const double *val; };
+struct ParamMapDev { int k; AffineDev g[3]; };
+// Output map (eicos_batch_set_output_map): u = base + U x, r rows, CSR with n columns, in device memory, shared by every instance
+struct OutMapDev { int r; AffineDev a; };
+struct UpdArgs {
+    const double *G, *A, *c, *h, *b; double *x; int on; const unsigned *flags; int chunk; unsigned seq; int *err;
+    const ParamMapDev *pmap; const OutMapDev *omap; const double *theta; double *u; // (device copies of the handle's maps)
+};
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
                         int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
 hipError_t launch_update(int ps, double *inst, int first, int count, const double *Gpr, const double *Apr,
@@ -22,12 +32,14 @@ hipError_t launch_update(int ps, double *inst, int first, int count, const doubl
 // divided by each instance's stored scalings; `width` = the summed widths of the given groups (sizes the grid)
 hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st);
 // Parametric right-hand sides (eicos_batch_set_param_map): per group c, h, b a base vector and a CSR matrix with k columns, in device
-// memory, shared by every instance of the handle; base == NULL: the group has no map and is kept.  Passed to the kernel by value.
-struct AffineDev { const double *base; const int *rowptr, *col; const double *val; };
-struct ParamMapDev { int k; AffineDev g[3]; };
+// memory, shared by every instance of the handle; base == NULL: the group has no map and is kept (AffineDev, ParamMapDev: above).  Passed
+// to the range kernel by value.
 // instances [first, first + count) from rows of theta [count][k]: entry = (base[r] + sum val * theta[col], every product and sum
 // rounded on its own, in stored order) divided by the instance's stored scaling -- the bits launch_update_rhs leaves for the same vectors
 hipError_t launch_update_param(int ps, double *inst, int first, int count, const ParamMapDev &map, const double *theta, int width, hipStream_t st);
+// rows [first, first + count) of u [count][map.r] = the output map applied to the current x of those instances: acc = base[row], then
+// acc = acc + (val * x[col]) in stored order, every product and sum rounded on its own
+hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st);
 hipError_t update_set_max_lds();
 hipError_t launch_debug_factor(int ps, double *inst, double *work, int i, int threads, size_t dyn_lds, hipStream_t st);
 hipError_t launch_debug_scalings(int ps, double *inst, double *work, int i, int *ok, int threads, hipStream_t st);

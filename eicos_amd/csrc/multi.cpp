@@ -227,6 +227,21 @@ int eicos_multi_update_param_device(eicos_multi *mh, int src_device, int first, 
     });
 }
 
+int eicos_multi_set_output_map(eicos_multi *mh, int r, const eicos_affine_map *u) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    return for_shards(mh, [&](int s) { return eicos_batch_set_output_map(mh->shard[s], r, u); });
+}
+
+int eicos_multi_output_count(eicos_multi *mh) { return mh ? eicos_batch_output_count(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
+
+int eicos_multi_outputs(eicos_multi *mh, int first, int count, double *u) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    const int r = eicos_batch_output_count(mh->shard[0]); // (0: every shard refuses, "no output map")
+    return for_range(mh, first, count, [&](int s, int f, int cnt, size_t off) {
+        return eicos_batch_outputs(mh->shard[s], f, cnt, u ? u + off * (size_t)r : nullptr);
+    });
+}
+
 int eicos_multi_solve_async(eicos_multi *mh) {
     if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
     for (size_t s = 0; s < mh->shard.size(); s++) { // enqueue only: every shard's kernels start on its own stream, the call returns at once
@@ -278,6 +293,17 @@ int eicos_multi_update_rhs_solve(eicos_multi *mh, const double *c, const double 
         const size_t r = (size_t)mh->first[s];
         return eicos_batch_update_rhs_solve(mh->shard[s], at(c, r, mh->n), at(hh, r, mh->m), at(b, r, mh->p),
                                             x_out ? x_out + r * (size_t)mh->n : nullptr, exitcodes ? exitcodes + r : nullptr);
+    });
+}
+
+// the closed-loop step over every shard (eicos_batch_update_param_solve per shard on its rows of theta, u_out and x_out, the shards concurrently)
+int eicos_multi_update_param_solve(eicos_multi *mh, const double *theta, double *u_out, double *x_out, int *exitcodes) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    const int k = eicos_batch_param_count(mh->shard[0]), ro = eicos_batch_output_count(mh->shard[0]);
+    return for_shards(mh, [&](int s) {
+        const size_t r = (size_t)mh->first[s];
+        return eicos_batch_update_param_solve(mh->shard[s], at(theta, r, k), u_out ? u_out + r * (size_t)ro : nullptr,
+                                              x_out ? x_out + r * (size_t)mh->n : nullptr, exitcodes ? exitcodes + r : nullptr);
     });
 }
 

@@ -3,9 +3,11 @@
 // updateParam then sends k doubles per instance and the GPU expands them -- the result must equal, bit for bit, updateRHS of the vectors
 // evaluated on the host in the same order (every product and every sum rounded on its own).  Runs over a device list (a device may be
 // listed twice: 0,0), checks updateParam + solve and a sub-range against updateRHS, then runs a short closed loop with warm starts --
-// theta moves a little every step -- in three forms side by side, each on its own solver, and prints the median step time (update
-// call -> end of solve) of each: updateRHS from pageable host vectors, updateParam from a pageable theta, updateRHSDevice from vectors
-// already in device memory (that leg needs the HIP runtime's allocation calls, looked up at run time; "n/a" without them).
+// theta moves a little every step -- in four forms side by side, each on its own solver, and prints the median step time (update call ->
+// result on the host) and the bytes per instance each way of each: updateRHS from pageable host vectors + solve + solution, updateParam
+// from a pageable theta + solve + outputs, updateRHSDevice from vectors already in device memory + solve + solution (that leg needs the
+// HIP runtime's allocation calls, looked up at run time; "n/a" without them), and stepParam -- the whole step in one call, pinned theta in,
+// the r selected outputs u = u0 + U x into a pinned array out.  stepParam's u must equal the output map applied to solution() bit for bit.
 //   g++ -std=c++17 -Iinclude examples/param_update_demo.cpp -Leicos_amd -leicos_amd -Wl,-rpath,$PWD/eicos_amd -o param_update_demo
 //   ./param_update_demo tests/golden/MPC02.epb 64 0,0 [k = 16] [steps = 20]
 #include <dlfcn.h>
@@ -135,7 +137,19 @@ int main(int argc, char **argv) {
     std::printf("sub-range updateParam: %s\n", same_sub ? "bit-identical" : "DIFFERENT");
     delete ref; delete s;
 
-    // (3) closed loop with warm starts, three forms side by side (each on its own solver, the same data in the same order)
+    // the output map: the first R variables, un-scaled (row j = u0[j] + a * x[j] + b * x[j + 1]; the last row has one entry)
+    const int R = std::min(4, n);
+    Group go;
+    go.rowptr.assign(1, 0);
+    for (int j = 0; j < R; j++) {
+        go.base.push_back(0.25 * j - 0.5);
+        go.col.push_back(j); go.val.push_back(1.5 + 0.125 * j);
+        if (j + 1 < R) { go.col.push_back(j + 1); go.val.push_back(-1. / 3.); }
+        go.rowptr.push_back((int)go.col.size());
+    }
+    const eicos_affine_map mo = go.view();
+
+    // (3) closed loop with warm starts, four forms side by side (each on its own solver, the same data in the same order)
     typedef int (*malloc_fn)(void **, size_t);
     typedef int (*memcpy_fn)(void *, const void *, size_t, int);
     typedef int (*free_fn)(void *);
@@ -144,15 +158,16 @@ int main(int argc, char **argv) {
     const memcpy_fn dmemcpy = (memcpy_fn)dlsym(RTLD_DEFAULT, "hipMemcpy");
     const free_fn dfree = (free_fn)dlsym(RTLD_DEFAULT, "hipFree");
     const setdev_fn dsetdev = (setdev_fn)dlsym(RTLD_DEFAULT, "hipSetDevice");
-    EiCOS::BatchSolver *sa = make(), *sb = make(), *sc = nullptr;
+    EiCOS::BatchSolver *sa = make(), *sb = make(), *sc = nullptr, *sd = make();
     double *dC = nullptr, *dH = nullptr, *dB = nullptr;
     if (dmalloc && dmemcpy && dfree && dsetdev && dsetdev(devs[0]) == 0 && dmalloc((void **)&dC, C0.size() * 8 + 8) == 0 &&
         dmalloc((void **)&dH, H0.size() * 8 + 8) == 0 && dmalloc((void **)&dB, B0.size() * 8 + 8) == 0)
         sc = make();
-    sb->setParamMap(k, &mc, m ? &mh : nullptr, p ? &mb : nullptr);
-    for (EiCOS::BatchSolver *v : {sa, sb, sc}) if (v) v->setWarmStart(0.1);
-    std::vector<double> ta, tb, tc;
-    bool same_loop = true;
+    for (EiCOS::BatchSolver *v : {sb, sd}) { v->setParamMap(k, &mc, m ? &mh : nullptr, p ? &mb : nullptr); v->setOutputMap(R, &mo); }
+    for (EiCOS::BatchSolver *v : {sa, sb, sc, sd}) if (v) v->setWarmStart(0.1);
+    double *pth = EiCOS::BatchSolver::hostAlloc((size_t)B * k), *pu = EiCOS::BatchSolver::hostAlloc((size_t)B * R); // stepParam: pinned both ways
+    std::vector<double> ta, tb, tc, td, xa((size_t)B * n), xc((size_t)B * n), ub((size_t)B * R), ud, uwant;
+    bool same_loop = true, same_u = true;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1) { return std::chrono::duration<double, std::milli>(t1 - t0).count(); };
     for (int st = 0; st < steps + 2; st++) { // (the first two steps warm the paths up and are not timed)
@@ -161,29 +176,46 @@ int main(int argc, char **argv) {
         auto t0 = now();
         sa->updateRHS(C.data(), m ? H.data() : nullptr, p ? Bv.data() : nullptr);
         const std::vector<EiCOS::exitcode> ca = sa->solve();
+        sa->solution(xa.data());
         auto t1 = now();
         sb->updateParam(th.data());
         const std::vector<EiCOS::exitcode> cb = sb->solve();
+        sb->outputs(ub.data());
         auto t2 = now();
-        same_loop = same_loop && ca == cb && same(sa->solution(), sb->solution());
+        same_loop = same_loop && ca == cb && same(xa, sb->solution());
+        std::copy(th.begin(), th.end(), pth);
+        auto t5 = now();
+        const std::vector<EiCOS::exitcode> cd = sd->stepParam(pth, pu);
+        auto t6 = now();
+        ud.assign(pu, pu + (size_t)B * R);
+        go.evaluate(xa, n, B, uwant); // (the map applied to solution(), on the host in the stated order)
+        same_loop = same_loop && ca == cd && same(xa, sd->solution());
+        same_u = same_u && same(ud, uwant) && same(ub, uwant);
+        if (st >= 2) td.push_back(ms(t5, t6));
         if (st >= 2) { ta.push_back(ms(t0, t1)); tb.push_back(ms(t1, t2)); }
         if (sc) {
             dmemcpy(dC, C.data(), C.size() * 8, 1); dmemcpy(dH, H.data(), H.size() * 8, 1); dmemcpy(dB, Bv.data(), Bv.size() * 8, 1); // (host to device)
             auto t3 = now();
             sc->updateRHSDevice(devs[0], dC, m ? dH : nullptr, p ? dB : nullptr);
             const std::vector<EiCOS::exitcode> cc = sc->solve();
+            sc->solution(xc.data());
             auto t4 = now();
-            same_loop = same_loop && ca == cc && same(sa->solution(), sc->solution());
+            same_loop = same_loop && ca == cc && same(xa, xc);
             if (st >= 2) tc.push_back(ms(t3, t4));
         }
     }
     const bool device_leg = sc != nullptr;
-    delete sa; delete sb; delete sc;
+    delete sa; delete sb; delete sc; delete sd;
+    EiCOS::BatchSolver::hostFree(pth); EiCOS::BatchSolver::hostFree(pu);
     if (dfree) for (double *d : {dC, dH, dB}) if (d) dfree(d);
     std::printf("closed loop, every step: %s\n", same_loop ? "bit-identical" : "DIFFERENT");
     auto median = [](std::vector<double> v) { std::sort(v.begin(), v.end()); return v.empty() ? 0. : 0.5 * (v[(v.size() - 1) / 2] + v[v.size() / 2]); };
-    std::printf("closed loop step (update call -> end of solve), batch %d, median of %d steps: updateRHS %.3f ms (%.1f kB per instance), "
-                "updateParam k = %d %.3f ms (%.3f kB per instance)", B, steps, median(ta), 8e-3 * (n + m + p), k, median(tb), 8e-3 * k);
-    if (device_leg) std::printf(", updateRHSDevice %.3f ms\n", median(tc)); else std::printf(", updateRHSDevice n/a\n");
-    return (same_all && same_sub && same_loop) ? 0 : 1; // (bit-identity is the contract: it holds for every exit code)
+    std::printf("stepParam u vs the output map applied to solution(): %s\n", same_u ? "bit-identical" : "DIFFERENT");
+    std::printf("closed loop step (update call -> result on the host), batch %d, k = %d, r = %d, median of %d steps; bytes per instance in / out:\n", B, k, R, steps);
+    std::printf("  updateRHS + solve + solution         %8.3f ms  %7d B in  %6d B out\n", median(ta), 8 * (n + m + p), 8 * n);
+    std::printf("  updateParam + solve + outputs        %8.3f ms  %7d B in  %6d B out\n", median(tb), 8 * k, 8 * R);
+    if (device_leg) std::printf("  updateRHSDevice + solve + solution   %8.3f ms  %7d B in  %6d B out  (inputs already in device memory)\n", median(tc), 0, 8 * n);
+    else std::printf("  updateRHSDevice + solve + solution        n/a\n");
+    std::printf("  stepParam (pinned theta, pinned u)   %8.3f ms  %7d B in  %6d B out\n", median(td), 8 * k, 8 * R);
+    return (same_all && same_sub && same_loop && same_u) ? 0 : 1; // (bit-identity is the contract: it holds for every exit code)
 }

@@ -162,6 +162,25 @@ namespace EiCOS
         {
             mcheck(eicos_multi_update_param_device(h_, src_device, first, count < 0 ? batch_ : count, dtheta), "eicos_multi_update_param_device");
         }
+        // Extension: the few numbers of x a controller applies, u = u0 + U x (eicos_affine_map: base[r] + CSR matrix r x n), one map for
+        // all instances, copied to every shard; r = 0 or nullptr removes it.  outputs() evaluates it on the current x of instances
+        // [first, first + count) -- bit for bit the map applied to solution() in the rounding order of eicos_amd.h.
+        void setOutputMap(int r, const eicos_affine_map *u) { mcheck(eicos_multi_set_output_map(h_, r, u), "eicos_multi_set_output_map"); }
+        void outputs(double *u, int first = 0, int count = -1)
+        {
+            mcheck(eicos_multi_outputs(h_, first, count < 0 ? batch_ : count, u), "eicos_multi_outputs");
+        }
+        // The closed-loop step in ONE call: updateParam(theta) + solve() + outputs(u_out) (+ solution(x_out)).  With theta from hostAlloc /
+        // hostRegister the solve kernel's workgroups expand every instance's theta row themselves and write its u row (and x row) into
+        // pinned u_out / x_out as instances finish: 8 k bytes in and 8 r bytes out per instance, one launch.  Same results on every path.
+        std::vector<exitcode> stepParam(const double *theta, double *u_out, double *x_out = nullptr)
+        {
+            std::vector<int> codes(batch_);
+            mcheck(eicos_multi_update_param_solve(h_, theta, u_out, x_out, codes.data()), "eicos_multi_update_param_solve");
+            std::vector<exitcode> out(batch_);
+            for (int i = 0; i < batch_; i++) out[i] = static_cast<exitcode>(codes[i]);
+            return out;
+        }
         // Extension (not in the reference): re-solves start from the previous solution, see eicos_amd.h
         void setWarmStart(double shift) { mcheck(eicos_multi_set_warm_start(h_, shift), "eicos_multi_set_warm_start"); }
         // Extension: ECOS-style dynamic regularisation (the reference's Settings::delta / ::eps are never read)

@@ -186,6 +186,36 @@ int eicos_batch_param_count(eicos_batch *hd);
 int eicos_batch_update_param(eicos_batch *hd, int first, int count, const double *theta /* host [count][k] */);
 int eicos_batch_update_param_device(eicos_batch *hd, int first, int count, const double *dtheta);
 
+/* ---- output map and the closed-loop step (no reference counterpart).  A controller applies a few numbers of x -- the first move,
+ * usually after an affine un-scaling: u = u0 + U x with u of length r.  A handle holds one such map for all its instances, mirroring the
+ * parameter map: eicos_affine_map with base[r] and a CSR matrix r x n (rowptr[r + 1], col / val[rowptr[r]]; columns index x).
+ * eicos_batch_set_output_map COPIES the host arrays into one device allocation; a later call replaces the map, r = 0 or u = NULL removes
+ * it.  EICOS_E_INVALID, with a message naming the fault, for rowptr[0] != 0, decreasing row pointers, a column outside [0, n), r < 0 and a
+ * pattern with n = 0.  eicos_batch_output_count: r, 0 = no map installed.
+ * Row `row` of instance i:
+ *     acc = base[row];  for t in rowptr[row] .. rowptr[row+1]-1, in stored order:  acc = acc + (val[t] * x[i][col[t]])
+ * with the product and the sum EACH rounded to fp64 (no fused multiply-add) and x the solution as eicos_batch_solution returns it: u is,
+ * bit for bit, what a host restatement in that order computes from eicos_batch_solution.  It is computed from whatever x the instance
+ * ended with, whatever its exit code (as x_out is).
+ * eicos_batch_outputs: synchronous -- waits for the handle's stream, evaluates the map on the current x of instances [first, first+count)
+ * and fetches the rows (a pinned destination gets one copy, a pageable one goes through the bounce buffers like eicos_batch_solution).
+ * eicos_batch_outputs_device: the same into caller-owned device memory, asynchronous on the handle's stream.  Both: EICOS_E_INVALID
+ * without a map ("no output map").
+ * eicos_batch_update_param_solve: eicos_batch_update_param + eicos_batch_solve + eicos_batch_outputs of the whole batch in ONE synchronous
+ * call, with the conventions of eicos_batch_update_rhs_solve (u_out [batch][r], x_out [batch][n], exitcodes [batch]: each optional).  When
+ * theta is memory the GPU addresses directly (pinned / registered host memory or device memory), the handle has an LDS vector and a theta
+ * row fits it, each workgroup of the solve kernel expands the theta row of the instance it is about to solve and, when it is done, writes
+ * that instance's u row (and x row, if asked) straight to the caller's pinned or device array (path 5): 8 k bytes in, 8 r bytes out per
+ * instance, one launch.  Otherwise (pageable theta, EICOS_FUSED_UPDATE=0, no LDS vector, k beyond the LDS vector) it runs the three calls;
+ * a device or pageable u_out the kernel did not write is filled by the range kernel and a copy, as x_out is.  Bit-identical on every path.
+ * EICOS_E_INVALID for u_out != NULL without an output map ("no output map") and without a parameter map ("no parameter map"). */
+int eicos_batch_set_output_map(eicos_batch *hd, int r, const eicos_affine_map *u);
+int eicos_batch_output_count(eicos_batch *hd);
+int eicos_batch_outputs(eicos_batch *hd, int first, int count, double *u /* host [count][r] */);
+int eicos_batch_outputs_device(eicos_batch *hd, int first, int count, double *du);
+int eicos_batch_update_param_solve(eicos_batch *hd, const double *theta /* [batch][k] */, double *u_out /* [batch][r], optional */,
+                                   double *x_out /* [batch][n], optional */, int *exitcodes /* optional */);
+
 /* ---- solve: replaces exitcode Solver::solve(bool) (reference include/eicos.hpp:158,
  * src/eicos.cpp:848-1262) for every instance of the batch.  exitcodes (host, [batch]) may be
  * NULL.  Synchronous: returns after the GPU work has completed. */
@@ -297,6 +327,13 @@ int eicos_multi_set_param_map(eicos_multi *mh, int k, const eicos_affine_map *c,
 int eicos_multi_param_count(eicos_multi *mh);
 int eicos_multi_update_param(eicos_multi *mh, int first, int count, const double *theta);
 int eicos_multi_update_param_device(eicos_multi *mh, int src_device, int first, int count, const double *dtheta);
+/* output map and the closed-loop step (eicos_batch_set_output_map / _output_count / _outputs / _update_param_solve on every shard): the map
+ * is installed on every shard; theta, u, u_out and x_out are in global instance order, every shard takes its rows, the shards of
+ * eicos_multi_update_param_solve run concurrently */
+int eicos_multi_set_output_map(eicos_multi *mh, int r, const eicos_affine_map *u);
+int eicos_multi_output_count(eicos_multi *mh);
+int eicos_multi_outputs(eicos_multi *mh, int first, int count, double *u);
+int eicos_multi_update_param_solve(eicos_multi *mh, const double *theta, double *u_out, double *x_out, int *exitcodes);
 /* solve: async = enqueue every shard's kernels on its stream and return; sync waits for all; eicos_multi_solve = both (+ exit codes, may be NULL) */
 int eicos_multi_solve_async(eicos_multi *mh);
 int eicos_multi_sync(eicos_multi *mh);
