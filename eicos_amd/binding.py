@@ -126,6 +126,15 @@ def _lib():
             for f in ("set_output_map", "output_count", "outputs", "update_param_solve"):
                 getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
             L.eicos_batch_outputs_device.restype = C.c_int
+        if hasattr(L, "eicos_batch_set_plant_map"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            mp = C.POINTER(AffineMap)
+            L.eicos_batch_set_plant_map.argtypes = L.eicos_multi_set_plant_map.argtypes = [vp, mp]
+            L.eicos_batch_has_plant_map.argtypes = L.eicos_multi_has_plant_map.argtypes = [vp]
+            L.eicos_batch_rollout.argtypes = L.eicos_multi_rollout.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip, ip]
+            for f in ("set_plant_map", "has_plant_map", "rollout"):
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+            L.eicos_batch_last_rollout_launches.argtypes = [vp]
+            L.eicos_batch_last_rollout_launches.restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -353,6 +362,61 @@ def _output_map_ptr(omap, pat):
     return (m, one), C.pointer(m)
 
 
+class PlantMap:
+    """The simulated plant of a closed loop, theta+ = f0 + F [theta | u] (+ w): `(base, rowptr, col, val)` -- base[k] and a CSR matrix
+    with k rows whose columns index z = [theta (k) | u (r)], i.e. lie in [0, k + r) -- shared by all instances.  evaluate() is the host
+    restatement of what rollout() computes on the GPU between two steps, in the same rounding order."""
+
+    def __init__(self, k: int, r: int, f):
+        self.k, self.r = int(k), int(r)
+        self.base, self.rowptr, self.col, self.val = (np.ascontiguousarray(f[0], np.float64), np.ascontiguousarray(f[1], np.int32),
+                                                      np.ascontiguousarray(f[2], np.int32), np.ascontiguousarray(f[3], np.float64))
+
+    def evaluate(self, theta, u, w=None):
+        """theta+ [B, k] for theta [B, k], u [B, r] and, optionally, the disturbance w [B, k].  Row j: acc = base[j], then for every
+        stored entry s of the row, in stored order, acc = acc + (val[s] * z[col[s]]) with z = [theta | u], then acc = acc + w[j] -- the
+        product and every sum each rounded to float64 (numpy has no fused multiply-add), which is the order of eicos_batch_rollout."""
+        theta, u = np.ascontiguousarray(theta, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.k:
+            raise ValueError(f"theta has shape {theta.shape}, expected [count, {self.k}]")
+        if u.shape != (theta.shape[0], self.r):
+            raise ValueError(f"u has shape {u.shape}, expected [{theta.shape[0]}, {self.r}]")
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != theta.shape:
+                raise ValueError(f"w has shape {w.shape}, expected {theta.shape}")
+        z = np.concatenate((theta, u), axis=1)
+        acc = np.repeat(self.base[None, :], z.shape[0], axis=0)
+        length = np.diff(self.rowptr)
+        for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
+            rows = np.nonzero(length > j)[0]
+            t = self.rowptr[rows] + j
+            acc[:, rows] = acc[:, rows] + self.val[t][None, :] * z[:, self.col[t]]
+        return acc if w is None else acc + w
+
+
+def _plant_map_ptr(fmap, k, r):
+    """A PlantMap as (keep-alive objects, C pointer to eicos_affine_map) for a handle with k parameters and r outputs; array sizes are
+    checked here, their contents (row pointers, column range) by the library."""
+    base, rowptr, col, val = fmap.base, fmap.rowptr, fmap.col, fmap.val
+    if fmap.k != k or fmap.r != r or base.size != k or rowptr.size != k + 1 or col.size != val.size or rowptr[-1] > col.size:
+        raise ValueError(f"plant map: k = {fmap.k}, r = {fmap.r}, base[{base.size}], rowptr[{rowptr.size}], col[{col.size}], val[{val.size}] "
+                         f"do not describe {k} rows over {k} parameters and {r} outputs")
+    one = np.zeros(1)
+    m = AffineMap(_dp(base if base.size else one), _ip(rowptr), _ip(col if col.size else np.zeros(1, np.int32)), _dp(val if val.size else one))
+    return (m, one), C.pointer(m)
+
+
+def _disturbance(w, count, steps, k):
+    """w as a contiguous float64 [count, steps, k] array (None passes); ValueError otherwise."""
+    if w is None:
+        return None
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.shape != (count, steps, k):
+        raise ValueError(f"w has shape {w.shape}, expected [{count}, {steps}, {k}]")
+    return w
+
+
 def _result_rows(a, rows, width, name):
     """A caller-owned result array: C-contiguous float64 [rows, width] (None passes); ValueError otherwise."""
     if a is not None and not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == (rows, width)):
@@ -487,6 +551,39 @@ class _Solver:
         self._call("update_param_solve", _dp(theta) if theta.size else _dp(np.zeros(1)), _dp(u_out) if (u_out is not None and u_out.size) else None,
                    _dp(x_out) if (x_out is not None and x_out.size) else None, _ip(codes))
         return codes
+
+    # ---- plant map and the closed-loop rollout (include/eicos_amd.h: eicos_batch_set_plant_map / eicos_batch_rollout) ----
+    def set_plant_map(self, fmap: "PlantMap | None"):
+        """Install (copy) a PlantMap for all instances, behind the parameter and the output map it refers to; None removes it."""
+        if fmap is None:
+            self._call("set_plant_map", None)
+            return
+        _keep, ptr = _plant_map_ptr(fmap, self.param_count(), self.output_count())
+        self._call("set_plant_map", ptr)
+
+    def has_plant_map(self) -> bool:
+        return bool(getattr(_lib(), self._prefix + "has_plant_map")(self._h))
+
+    def rollout(self, theta0, steps: int, w=None):
+        """`steps` closed-loop steps of the whole batch in one call: from theta0 [batch, k], every step is update_param_solve on the
+        current theta row and then the plant map, theta+ = PlantMap.evaluate(theta, u, w[:, t]) -- with an LDS vector on the handle one
+        launch in which every workgroup takes its instances through all their steps.  Returns u_traj [batch, steps, r], theta_traj
+        [batch, steps + 1, k], exitcodes and iters [batch, steps]: bit for bit what the host loop over update_param_solve gives."""
+        steps = int(steps)
+        k, r = self.param_count(), self.output_count()
+        if k > 0:
+            theta0, _ = _theta_rows(theta0, k, self.batch)
+            w = _disturbance(w, self.batch, steps, k)
+        else:  # (the library refuses: "no parameter map")
+            theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
+            w = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
+        T = max(steps, 0)
+        u_traj, theta_traj = np.zeros((self.batch, T, r)), np.zeros((self.batch, T + 1, k))
+        codes, iters = np.zeros((self.batch, T), np.int32), np.zeros((self.batch, T), np.int32)
+        one = np.zeros(1)
+        self._call("rollout", steps, _dp(theta0 if theta0.size else one), None if w is None else _dp(w if w.size else one),
+                   _dp(u_traj if u_traj.size else one), _dp(theta_traj if theta_traj.size else one), _ip(codes), _ip(iters))
+        return u_traj, theta_traj, codes, iters
 
     # ---- solve ----
     def solve(self):
@@ -623,6 +720,10 @@ class BatchSolver(_Solver):
         if n < 0:
             _chk(n)
         return [float(buf[i]) for i in range(n)]
+
+    def last_rollout_launches(self) -> int:
+        """Solve-kernel launches of the most recent rollout(): 1 = the steps ran inside one launch, `steps` = one launch per step."""
+        return int(_lib().eicos_batch_last_rollout_launches(self._h))
 
     def last_update_path(self) -> str:
         """How the most recent host-pointer / peer updateData moved its inputs (UPDATE_PATHS)."""

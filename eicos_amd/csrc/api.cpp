@@ -124,6 +124,11 @@ struct eicos_batch {
     // output map (eicos_batch_set_output_map): one device allocation [OutMapDev | u rows of the batch | base, val | rowptr, col], out.r = 0
     // while none is installed; d_u = the [batch][r] rows the range kernel fills for a host destination
     OutMapDev out{}; void *d_out = nullptr; double *d_u = nullptr;
+    // plant map (eicos_batch_set_plant_map): one device allocation [MAP_HEADER | base, val | rowptr, col], plant.k = 0 while none is installed
+    PlantMapDev plant{}; void *d_plant = nullptr;
+    // rollout (eicos_batch_rollout): one device allocation, grown on demand: [RolloutDev (MAP_HEADER bytes) | theta, u, w trajectories | two
+    // theta rows of the batch (the path that is not fused) | codes, iters]; roll = the host copy of the record of the most recent call
+    RolloutDev roll{}; void *d_roll = nullptr; size_t roll_bytes = 0; int rollout_launches = 0;
     TilePlan tiles;        // tile mode (Symbolic::tile): the dense-front plan
 };
 
@@ -1032,7 +1037,7 @@ int eicos_batch_destroy(eicos_batch *h) {
     for (int i = 0; i < eicos_batch::EV_RING; i++)
         for (hipEvent_t e : {h->ring_s[i][0], h->ring_s[i][1], h->ring_u[i][0], h->ring_u[i][1]}) if (e) (void)hipEventDestroy(e);
     for (void *ptr : {(void *)h->d_pattern, (void *)h->d_inst, (void *)h->d_work, (void *)h->d_queue, (void *)h->d_scratch,
-                      (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out})
+                      (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out, h->d_plant, h->d_roll})
         if (ptr) (void)hipFree(ptr);
     for (int i = 0; i < 2; i++) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     if (h->stage_pin) (void)hipHostFree(h->stage_pin);
@@ -1474,7 +1479,7 @@ int eicos_batch_update_rhs(eicos_batch *h, int first, int count, const double *c
 // handed to the range kernel by value (ParamMapDev); the allocation starts with a copy of that descriptor, which the fused step reads
 // through a pointer.  A later call replaces the map, all groups NULL or k = 0 removes it.
 static constexpr size_t MAP_HEADER = 128; // bytes kept for the descriptor in front of a map's arrays (keeps the doubles aligned)
-static_assert(sizeof(ParamMapDev) <= MAP_HEADER && sizeof(OutMapDev) <= MAP_HEADER, "map descriptor larger than its header");
+static_assert(sizeof(ParamMapDev) <= MAP_HEADER && sizeof(OutMapDev) <= MAP_HEADER && sizeof(RolloutDev) <= MAP_HEADER, "map descriptor larger than its header");
 int eicos_batch_set_param_map(eicos_batch *h, int k, const eicos_affine_map *c, const eicos_affine_map *hh, const eicos_affine_map *b) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     if (k < 0) return fail(EICOS_E_INVALID, "parameter map: k must not be negative");
@@ -1861,6 +1866,128 @@ int eicos_batch_update_rhs_solve(eicos_batch *h, const double *c, const double *
 }
 int eicos_batch_update_param_solve(eicos_batch *h, const double *theta, double *u_out, double *x_out, int *exitcodes) {
     return update_solve(h, nullptr, nullptr, nullptr, nullptr, nullptr, theta, u_out, x_out, exitcodes, STEP_PARAM);
+}
+
+// ---- plant map and rollout: theta+ = f0 + F [theta | u] (+ w), and `steps` closed-loop steps in one call (no reference counterpart) ----
+// The map is validated like the other two and packed into ONE device allocation: [MAP_HEADER bytes, unused | base, val | rowptr, col]; it
+// reaches the kernels inside the rollout's record (RolloutDev), by value in the range kernel and through a pointer in the fused launch.
+int eicos_batch_set_plant_map(eicos_batch *h, const eicos_affine_map *f) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    const int k = h->param.k, r = h->out.r;
+    int nnz = 0;
+    if (f) {
+        const std::string who = "plant map: ";
+        if (k == 0) return fail(EICOS_E_INVALID, who + "no parameter map (eicos_batch_set_param_map installs one)");
+        if (r == 0) return fail(EICOS_E_INVALID, who + "no output map (eicos_batch_set_output_map installs one)");
+        if (!f->base || !f->rowptr) return fail(EICOS_E_INVALID, who + "base or rowptr is NULL");
+        const int *rp = f->rowptr;
+        if (rp[0] != 0) return fail(EICOS_E_INVALID, who + "rowptr[0] must be 0");
+        for (int q = 0; q < k; q++)
+            if (rp[q + 1] < rp[q]) return fail(EICOS_E_INVALID, who + "rowptr decreases at row " + std::to_string(q));
+        nnz = rp[k];
+        if (nnz > 0 && (!f->col || !f->val)) return fail(EICOS_E_INVALID, who + "col or val is NULL");
+        for (int t = 0; t < nnz; t++)
+            if (f->col[t] < 0 || f->col[t] >= k + r) return fail(EICOS_E_INVALID, who + "column " + std::to_string(f->col[t]) + " of entry " + std::to_string(t) + " is outside [0, k + r)");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
+    if (h->d_plant) { (void)hipFree(h->d_plant); h->d_plant = nullptr; }
+    h->plant = PlantMapDev{};
+    if (!f) return EICOS_OK;
+    const size_t nd = (size_t)k + nnz, ni = (size_t)k + 1 + nnz;
+    std::vector<char> buf(MAP_HEADER + nd * sizeof(double) + ni * sizeof(int));
+    double *hd_ = reinterpret_cast<double *>(buf.data() + MAP_HEADER);
+    int *hi_ = reinterpret_cast<int *>(buf.data() + MAP_HEADER + nd * sizeof(double));
+    void *dev = nullptr;
+    HIP_TRY(hipMalloc(&dev, buf.size()));
+    const double *dd = reinterpret_cast<const double *>(static_cast<const char *>(dev) + MAP_HEADER);
+    const int *di = reinterpret_cast<const int *>(static_cast<const char *>(dev) + MAP_HEADER + nd * sizeof(double));
+    PlantMapDev M{};
+    M.k = k; M.r = r;
+    M.a.base = dd; std::copy(f->base, f->base + k, hd_);
+    M.a.val = dd + k; if (nnz) std::copy(f->val, f->val + nnz, hd_ + k);
+    M.a.rowptr = di; std::copy(f->rowptr, f->rowptr + k + 1, hi_);
+    M.a.col = di + k + 1; if (nnz) std::copy(f->col, f->col + nnz, hi_ + k + 1);
+    const hipError_t e = hipMemcpy(dev, buf.data(), buf.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the plant map: ") + hipGetErrorString(e)); }
+    h->d_plant = dev; h->plant = M;
+    return EICOS_OK;
+}
+
+int eicos_batch_has_plant_map(eicos_batch *h) { return h ? (h->plant.k > 0 ? 1 : 0) : fail(EICOS_E_INVALID, "NULL handle"); }
+int eicos_batch_last_rollout_launches(eicos_batch *h) { return h ? h->rollout_launches : fail(EICOS_E_INVALID, "NULL handle"); }
+
+// Fused: ONE solve launch whose workgroups run the steps of their instances themselves (kernels.hip: k_solve, plant_instance); the
+// trajectories live in the handle's device buffer and the caller's arrays -- of any kind of memory -- are copied in before and out after.
+// Not fused: the same buffer, and per step four launches on the stream, the step's theta rows in two contiguous [batch][k] buffers that
+// take turns (the range kernels read and write rows k / r doubles apart; k_plant_range moves them into the trajectories).
+int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
+                        int *exitcodes, int *iters) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (steps < 1) return fail(EICOS_E_INVALID, "rollout: steps must be at least 1");
+    if (h->param.k == 0) return fail(EICOS_E_INVALID, "no parameter map (eicos_batch_set_param_map installs one)");
+    if (h->out.r == 0) return fail(EICOS_E_INVALID, "no output map (eicos_batch_set_output_map installs one)");
+    if (h->plant.k == 0) return fail(EICOS_E_INVALID, "no plant map (eicos_batch_set_plant_map installs one)");
+    const int k = h->param.k, r = h->out.r;
+    if (h->plant.k != k || h->plant.r != r)
+        return fail(EICOS_E_INVALID, "rollout: the plant map was installed for (k, r) = (" + std::to_string(h->plant.k) + ", " + std::to_string(h->plant.r) +
+                                         "), the maps now installed have (" + std::to_string(k) + ", " + std::to_string(r) + "): install it again");
+    if (!theta0) return fail(EICOS_E_INVALID, "rollout: theta0 is NULL");
+    if (!u_traj) return fail(EICOS_E_INVALID, "rollout: u_traj is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    const DevPat &D = h->dp;
+    const size_t B = (size_t)h->batch, T = (size_t)steps;
+    const size_t n_th = B * (T + 1) * k, n_u = B * T * r, n_w = w ? B * T * k : 0, n_cur = 2 * B * k, n_rec = B * T;
+    const size_t need = MAP_HEADER + (n_th + n_u + n_w + n_cur) * sizeof(double) + 2 * n_rec * sizeof(int);
+    if (need > h->roll_bytes) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->d_roll) { (void)hipFree(h->d_roll); h->d_roll = nullptr; h->roll_bytes = 0; }
+        HIP_TRY(hipMalloc(&h->d_roll, need));
+        h->roll_bytes = need;
+    }
+    double *d_th = reinterpret_cast<double *>(static_cast<char *>(h->d_roll) + MAP_HEADER), *d_uu = d_th + n_th, *d_w = d_uu + n_u, *d_cur = d_w + n_w;
+    int *d_codes = reinterpret_cast<int *>(d_cur + n_cur), *d_iters = d_codes + n_rec;
+    h->roll = RolloutDev{steps, h->plant, d_th, d_uu, w ? d_w : nullptr, d_codes, d_iters};
+    const size_t row_b = (size_t)k * sizeof(double);
+    HIP_TRY(hipMemcpyAsync(h->d_roll, &h->roll, sizeof(RolloutDev), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpy2DAsync(d_th, (T + 1) * row_b, theta0, row_b, row_b, B, hipMemcpyDefault, h->stream)); // row 0 of every trajectory
+    if (w) HIP_TRY(hipMemcpyAsync(d_w, w, n_w * sizeof(double), hipMemcpyDefault, h->stream));
+    const bool fused = h->nlds >= 1 && k + r <= D.Npad && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
+    int rc = EICOS_OK;
+    if (fused) {
+        h->last_update_path = 5;
+        rc = end_update_timing(h, begin_update_timing(h)); // (an empty updateData interval in the timing ring: the work is inside the solve launch)
+        if (rc != EICOS_OK) return rc;
+        h->fused = UpdArgs{};
+        h->fused.on = UPD_ROLL; h->fused.chunk = 1;
+        h->fused.pmap = static_cast<const ParamMapDev *>(h->d_param); h->fused.omap = static_cast<const OutMapDev *>(h->d_out);
+        h->fused.roll = static_cast<const RolloutDev *>(h->d_roll);
+        h->fused_pending = true;
+        rc = eicos_batch_solve_async(h);
+        h->fused_pending = false;
+        if (rc != EICOS_OK) return rc;
+    } else {
+        const int width = (h->param.g[0].base ? D.n : 0) + (h->param.g[1].base ? D.m : 0) + (h->param.g[2].base ? D.p : 0);
+        HIP_TRY(hipMemcpy2DAsync(d_cur, row_b, d_th, (T + 1) * row_b, row_b, B, hipMemcpyDeviceToDevice, h->stream));
+        for (int t = 0; t < steps; t++) {
+            const double *cur = d_cur + (size_t)(t & 1) * B * k;
+            double *next = d_cur + (size_t)((t + 1) & 1) * B * k;
+            rc = begin_update_timing(h);
+            if (rc == EICOS_OK && hipSuccess != launch_update_param(h->pslot, h->d_inst, 0, h->batch, h->param, cur, width, h->stream)) rc = fail(EICOS_E_HIP, "rollout: launch of the parametric update failed");
+            rc = end_update_timing(h, rc);
+            if (rc == EICOS_OK) rc = eicos_batch_solve_async(h);
+            if (rc != EICOS_OK) return rc;
+            HIP_TRY(launch_outputs(h->pslot, h->d_inst, 0, h->batch, h->out, h->d_u, h->stream));
+            HIP_TRY(launch_plant(h->pslot, h->d_inst, 0, h->batch, h->roll, t, cur, h->d_u, next, h->stream));
+        }
+    }
+    h->rollout_launches = fused ? 1 : steps;
+    HIP_TRY(hipMemcpyAsync(u_traj, d_uu, n_u * sizeof(double), hipMemcpyDefault, h->stream));
+    if (theta_traj) HIP_TRY(hipMemcpyAsync(theta_traj, d_th, n_th * sizeof(double), hipMemcpyDefault, h->stream));
+    if (exitcodes) HIP_TRY(hipMemcpyAsync(exitcodes, d_codes, n_rec * sizeof(int), hipMemcpyDefault, h->stream));
+    if (iters) HIP_TRY(hipMemcpyAsync(iters, d_iters, n_rec * sizeof(int), hipMemcpyDefault, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return EICOS_OK;
 }
 
 int eicos_batch_solution(eicos_batch *h, double *x) {

@@ -155,6 +155,10 @@ struct alignas(16) Sh : ShI {
     double red[2 * RED_SLOTS];
     double dyn_delta, dyn_eps; // dynamic regularisation of the pivots (extension; 0 = off), set by k_solve
     int next; // next instance of this workgroup (k_solve's queue)
+    // a rollout (k_solve with UpdArgs::roll): the step of the instance's rollout that is running, and what rollout_param / rollout_step need of
+    // the kernel's arguments -- kept here, so that k_solve holds nothing more in registers across its stages than it does without a rollout
+    int step;
+    const RolloutDev *roll; const ParamMapDev *pmap; const OutMapDev *omap; int *queue;
 };
 constexpr int KI_MAX = 2; // right-hand sides of a dual solve (kkt_solve<..., 2, true>)
 enum { TK_FACTOR = 0, TK_LDL, TK_KRES, TK_KPOST, TK_RESID, TK_FWD, TK_COUNT, TK_FA = 8, TK_FW1, TK_FB, TK_FW2 }; // 8..11: inside the factor
@@ -3258,6 +3262,15 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void param_insta
     __syncthreads(); // (the solve -- or the LDS-resident build's copy of the slab -- reads entries other threads wrote; the LDS vector is free again)
 }
 
+// The solution of one instance into row q of the caller's x [batch][n] (k_solve, after solve_instance and its barrier).  Out of line like
+// outputs_instance: the row's per-thread address is not carried through the solve.
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void solution_instance(int ps, gcdbl_p I, size_t q, double *x) {
+    ps = uni(ps); I = uni_ptr(I); x = uni_ptr(x);
+    const DevPat &P = c_pat[ps];
+    FOR_T(j, P.n) x[q * P.n + j] = I[P.i_x + j];
+}
+
 // The output map of one instance by one workgroup (k_solve, after solve_instance and its barrier): threads run over the r rows,
 // u[row] = base[row] + sum val * x[col] in stored order, product and sum rounded on their own, x read where the solve left it (the LDS
 // copy of the slab in the LDS-resident build, before the write-back) and the row stored straight to the caller's array.
@@ -3273,6 +3286,64 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void outputs_ins
         const int t1 = A.rowptr[row + 1];
         for (int t = A.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], x[A.col[t]]));
         u[q * (size_t)r + row] = acc;
+    }
+}
+
+// The plant map of one instance by one workgroup (k_solve, a rollout: after outputs_instance and the record of step t): row t + 1 of the
+// instance's theta trajectory = base + F z (+ w), z = [theta row t | u row t].  Both rows were written by THIS workgroup a moment ago
+// (the u row by outputs_instance, the theta row by the previous step), so they are read with ordinary global loads behind a barrier and
+// staged in the LDS KKT-space vector, idle between two solves (k + r <= Npad: api.cpp); threads then run over the k rows, accumulating
+// in stored order, product and sum rounded on their own, the disturbance added last.  plant_row = one row (k_plant_range shares it).
+__device__ __forceinline__ double plant_row(const AffineDev &A, int row, const double *z, const double *w) {
+    double acc = A.base[row];
+    const int t1 = A.rowptr[row + 1];
+    for (int t = A.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], z[A.col[t]]));
+    if (w) acc = __dadd_rn(acc, w[row]);
+    return acc;
+}
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void plant_instance(const RolloutDev *Rp, int id, int t) {
+    Rp = uni_ptr(Rp); id = uni(id); t = uni(t);
+    const int steps = Rp->steps, k = Rp->plant.k, r = Rp->plant.r;
+    const AffineDev A = Rp->plant.a;
+    const size_t at = (size_t)id * steps + t;
+    double *th = Rp->theta + (at + id) * k; // row t of [steps + 1] rows; row t + 1 follows it
+    const double *u = Rp->u + at * r, *w = Rp->w ? Rp->w + at * k : nullptr;
+    double *z = g_dyn;
+    __syncthreads(); // (the u row is complete; nothing reads the LDS vector any more)
+    FOR_T(j, k + r) z[j] = j < k ? th[j] : u[j - k];
+    __syncthreads();
+    FOR_T(row, k) th[k + row] = plant_row(A, row, z, w);
+    __syncthreads(); // (the next step reads the new row, and entries of the slab other threads wrote; the LDS vector is free again)
+}
+
+// One step of a rollout around the solve (k_solve with UpdArgs::roll; g_S.step = the step that is running).  rollout_param: the parametric
+// update from row g_S.step of the instance's theta trajectory, which the step before formed.  rollout_step, after the solve and its
+// barrier: the u row into the trajectory, the exit code and iteration count into their records, the plant map; then the step counter
+// moves on and -- after the last step -- the next instance is pulled from k_solve's queue.  Out of line, so that k_solve carries no state of the rollout across its stages.
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_param(int ps, hbm_p I, int id) {
+    id = uni(id);
+    __syncthreads(); // (the first step of the workgroup's first instance: k_solve has just filled g_S)
+    const RolloutDev *Rp = uni_ptr(g_S.roll);
+    param_instance<T>(ps, I, 0, g_S.pmap, Rp->theta + ((size_t)id * (Rp->steps + 1) + g_S.step) * Rp->plant.k);
+}
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_step(int ps, gcdbl_p I, int id) {
+    ps = uni(ps); I = uni_ptr(I); id = uni(id);
+    const RolloutDev *Rp = uni_ptr(g_S.roll);
+    const int t = g_S.step, steps = Rp->steps;
+    const size_t at = (size_t)id * steps + t;
+    outputs_instance<T>(ps, I, 0, g_S.omap, Rp->u + at * Rp->plant.r);
+    if (threadIdx.x == 0) {
+        const DevInfo EICOS_DATA *di = reinterpret_cast<const DevInfo EICOS_DATA *>(I + c_pat[ps].i_info);
+        Rp->codes[at] = di->exitcode; Rp->iters[at] = di->iter;
+    }
+    plant_instance<T>(Rp, id, t); // (ends with a barrier: every thread has read the step)
+    if (threadIdx.x == 0) {
+        const bool last = t + 1 >= steps;
+        g_S.step = last ? 0 : t + 1;
+        if (last) g_S.next = (int)gridDim.x + atomicAdd(g_S.queue, 1); // (k_solve's queue pull; otherwise g_S.next stays: the same instance again)
     }
 }
 
@@ -3304,13 +3375,14 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     for (int q = threadIdx.x; q < P.ub_len; q += T) g_dyn[P.ub_lds + q] = 0.;
     __syncthreads();
 #endif
-    if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; }
+    if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.step = 0; g_S.next = (int)blockIdx.x; } // (next: the instance that is running)
+    if constexpr (NLDS >= 1) { if (threadIdx.x == 0) { g_S.roll = upd.roll; g_S.pmap = upd.pmap; g_S.omap = upd.omap; g_S.queue = queue; } }
     // Instances differ in iteration count (12..18 on the headline batch): after its first instance (= its own index, so
     // that workspace slot g holds the history of instance g when the batch fits the grid) a workgroup pulls the next
     // unsolved instance from a queue instead of striding through the batch.
     // `order` (batches larger than one instance per CU): instances sorted by the work their previous solve took, longest first.
     for (int g = blockIdx.x; g < B;) {
-        const int id = order ? order[g] : g;
+        const int id = uni(order ? order[g] : g); // (uniform over the workgroup: slab addresses on the scalar side)
         if constexpr (NLDS >= 1) { // fused updateData (launch.hpp: UpdArgs): the maxima live in the sweep vector, idle between two instances
             if (upd.on) {
                 if (upd.flags) { // staged host arrays: the host is still copying -- wait for the chunk that holds this instance (launch.hpp: UpdArgs)
@@ -3327,7 +3399,8 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
                     __syncthreads();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, ""); // (system scope: the rows this workgroup reads next were written by the host)
                 }
-                if (upd.on == UPD_PARAM) param_instance<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.pmap, upd.theta);
+                if (upd.on == UPD_ROLL) rollout_param<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, id); // (launch.hpp: RolloutDev)
+                else if (upd.on == UPD_PARAM) param_instance<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.pmap, upd.theta);
                 else if (upd.on == UPD_RHS) rhs_instance<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.c, upd.h, upd.b);
                 else update_instance<T, false>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.G, upd.A, upd.c, upd.h, upd.b);
             }
@@ -3345,8 +3418,14 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
 #endif
         solve_instance<T, NLDS, I16>(ps, I, W, warm);
         __syncthreads();
-        if (upd.x) for (int j = threadIdx.x; j < P.n; j += T) upd.x[(size_t)id * P.n + j] = I[P.i_x + j]; // (fused path: the result straight to the caller's array)
+        if (upd.x) solution_instance<T>(ps, I, (size_t)id, upd.x); // (fused path: the result straight to the caller's array)
         if (upd.u) outputs_instance<T>(ps, I, (size_t)id, upd.omap, upd.u); // (the selected outputs of x, r doubles, likewise)
+        // A rollout keeps the instance for its next step (rollout_step: the step's u row and records, the plant map, the step counter) and
+        // pulls the next one from the queue after its last step; everything else pulls here.
+        bool rolling = false;
+        if constexpr (NLDS >= 1) { rolling = upd.on == UPD_ROLL; }
+        if (rolling) rollout_step<T>(ps, I, id);
+        else if (threadIdx.x == 0) g_S.next = (int)gridDim.x + atomicAdd(queue, 1);
 #if EICOS_LDSRES
         { // results, persistent per-instance state and (for the debug readbacks) the workspace go back to HBM
             double *Ig = inst + (size_t)id * P.inst_stride;
@@ -3354,7 +3433,6 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
             for (int q = threadIdx.x; q < (int)P.work_stride; q += T) Wglob[q] = W[q];
         }
 #endif
-        if (threadIdx.x == 0) g_S.next = (int)gridDim.x + atomicAdd(queue, 1);
         __syncthreads();
         g = g_S.next;
     }
@@ -3587,6 +3665,35 @@ __global__ __launch_bounds__(T) void k_outputs_range(int ps, const double *inst,
     }
 }
 
+// One step of a rollout that is not fused (launch.hpp: launch_plant; plant_instance is the fused form): ROW-parallel over the count * k
+// rows of theta+, the map served from L2, z read from the step's contiguous theta and u rows.  Same arithmetic as plant_instance.  The
+// threads of the first r / the first row of an instance also move its u row, exit code and iteration count into the trajectories.
+template <int T>
+__global__ __launch_bounds__(T) void k_plant_range(int ps, const double *inst, int first, int count, RolloutDev R, int t, const double *theta_cur,
+                                                   const double *u_cur, double *theta_next) {
+    const DevPat &P = c_pat[ps];
+    const size_t k = (size_t)R.plant.k, r = (size_t)R.plant.r, total = (size_t)count * k, steps = (size_t)R.steps;
+    for (size_t e = (size_t)blockIdx.x * T + threadIdx.x; e < total; e += (size_t)gridDim.x * T) {
+        const size_t q = e / k, at = (first + q) * steps + t;
+        const int row = (int)(e - q * k);
+        const double *th = theta_cur + q * k, *u = u_cur + q * r;
+        double acc = R.plant.a.base[row];
+        const int t1 = R.plant.a.rowptr[row + 1];
+        for (int s = R.plant.a.rowptr[row]; s < t1; s++) {
+            const int col = R.plant.a.col[s];
+            acc = __dadd_rn(acc, __dmul_rn(R.plant.a.val[s], (size_t)col < k ? th[col] : u[col - k]));
+        }
+        if (R.w) acc = __dadd_rn(acc, R.w[at * k + row]);
+        theta_next[e] = acc;
+        R.theta[(at + first + q + 1) * k + row] = acc;
+        for (size_t j = row; j < r; j += k) R.u[at * r + j] = u[j];
+        if (row == 0) {
+            const DevInfo *di = reinterpret_cast<const DevInfo *>(inst + (first + q) * P.inst_stride + P.i_info);
+            R.codes[at] = di->exitcode; R.iters[at] = di->iter;
+        }
+    }
+}
+
 // Debug: factorise instance `i` with the KKT scaling block as it stands in memory (runs the solver's own stage).
 template <int T>
 __global__ __launch_bounds__(T, waves_per_eu<T>()) void k_debug_factor(int ps, double *inst, double *work, int i) {
@@ -3672,7 +3779,7 @@ template <class F> static auto dispatch_solve(int threads, int nlds, int idx16, 
 #endif
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds,
                         int idx16, int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd_in) {
-    UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr, nullptr, nullptr, nullptr, nullptr};
+    UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (upd.on && nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector; both modes live in the NLDS >= 1 kernels)
     if (B <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(queue, 0, sizeof(int), st); // group queue of this launch
@@ -3729,6 +3836,14 @@ hipError_t launch_outputs(int ps, const double *inst, int first, int count, cons
     constexpr int T = 256;
     const size_t nb = ((size_t)count * map.r + T - 1) / T;
     hipLaunchKernelGGL(k_outputs_range<T>, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(T), 0, st, ps, inst, first, count, map, u);
+    return hipGetLastError();
+}
+hipError_t launch_plant(int ps, const double *inst, int first, int count, const RolloutDev &roll, int t, const double *theta_cur,
+                        const double *u_cur, double *theta_next, hipStream_t st) {
+    if (count <= 0 || roll.plant.k <= 0) return hipSuccess;
+    constexpr int T = 256;
+    const size_t nb = ((size_t)count * roll.plant.k + T - 1) / T;
+    hipLaunchKernelGGL(k_plant_range<T>, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(T), 0, st, ps, inst, first, count, roll, t, theta_cur, u_cur, theta_next);
     return hipGetLastError();
 }
 // the dynamic-LDS ceiling of the two entry-parallel updateData kernels, set once per handle on the handle's device

@@ -15,14 +15,25 @@ namespace eicos {
 // through *pmap, the five arrays unused; 0: off.
 // u != NULL (any mode, 0 included): row `instance` of u [batch][omap->r] = the output map applied to the instance's x, written like x.
 // The two maps stay in device memory and travel as pointers: a launch that uses neither pays four words of kernel arguments for them.
-enum { UPD_FULL = 1, UPD_RHS = 2, UPD_PARAM = 3 };
+// on = UPD_ROLL with roll != NULL (eicos_batch_rollout; theta and u unused): the workgroup takes its instance through roll->steps closed-loop
+// steps before it pulls the next one -- per step the parametric update from row t of the instance's theta trajectory, the solve, the
+// output row into the u trajectory, the exit code and iteration count into their records, and the plant map, which forms row t + 1 of the
+// theta trajectory (RolloutDev, below).  Every other mode leaves roll NULL and pays one more word of kernel arguments for it.
+enum { UPD_FULL = 1, UPD_RHS = 2, UPD_PARAM = 3, UPD_ROLL = 4 };
 struct AffineDev { const double *base; const int *rowptr, *col; const double *val; };
 struct ParamMapDev { int k; AffineDev g[3]; };
 // Output map (eicos_batch_set_output_map): u = base + U x, r rows, CSR with n columns, in device memory, shared by every instance
 struct OutMapDev { int r; AffineDev a; };
+// Plant map (eicos_batch_set_plant_map): theta+ = base + F z, k rows, CSR with k + r columns over z = [theta (k) | u (r)], in device
+// memory, shared by every instance; k, r = the parameter and output counts it was validated for
+struct PlantMapDev { int k, r; AffineDev a; };
+// One rollout, in device memory: theta [batch][steps + 1][k] (row 0 given, the others written by the plant map), u [batch][steps][r],
+// w [batch][steps][k] (NULL: no disturbance), codes / iters [batch][steps]
+struct RolloutDev { int steps; PlantMapDev plant; double *theta, *u; const double *w; int *codes, *iters; };
 struct UpdArgs {
     const double *G, *A, *c, *h, *b; double *x; int on; const unsigned *flags; int chunk; unsigned seq; int *err;
     const ParamMapDev *pmap; const OutMapDev *omap; const double *theta; double *u; // (device copies of the handle's maps)
+    const RolloutDev *roll;
 };
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
                         int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
@@ -40,6 +51,13 @@ hipError_t launch_update_param(int ps, double *inst, int first, int count, const
 // rows [first, first + count) of u [count][map.r] = the output map applied to the current x of those instances: acc = base[row], then
 // acc = acc + (val * x[col]) in stored order, every product and sum rounded on its own
 hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st);
+// One step of a rollout that is not fused into the solve launch, for instances [first, first + count), behind that step's solve and
+// output kernels: z = [row of theta_cur [count][k] | row of u_cur [count][r]] goes through the plant map -- acc = base[row], then
+// acc = acc + (val * z[col]) in stored order, then + w when given, every product and sum rounded on its own -- into theta_next [count][k]
+// and into row t + 1 of the instance's theta trajectory; the u row is copied to row t of the u trajectory and the instance's exit code
+// and iteration count to its records (roll: the trajectories of the whole batch, host copy of the launch's RolloutDev)
+hipError_t launch_plant(int ps, const double *inst, int first, int count, const RolloutDev &roll, int t, const double *theta_cur,
+                        const double *u_cur, double *theta_next, hipStream_t st);
 hipError_t update_set_max_lds();
 hipError_t launch_debug_factor(int ps, double *inst, double *work, int i, int threads, size_t dyn_lds, hipStream_t st);
 hipError_t launch_debug_scalings(int ps, double *inst, double *work, int i, int *ok, int threads, hipStream_t st);

@@ -307,6 +307,28 @@ int eicos_multi_update_param_solve(eicos_multi *mh, const double *theta, double 
     });
 }
 
+// plant map and rollout over every shard (eicos_batch_rollout per shard on its rows, the shards concurrently): with [batch][steps][...]
+// arrays the rows of a shard are contiguous, so every shard gets plain offsets into the caller's arrays
+int eicos_multi_set_plant_map(eicos_multi *mh, const eicos_affine_map *f) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    return for_shards(mh, [&](int s) { return eicos_batch_set_plant_map(mh->shard[s], f); });
+}
+
+int eicos_multi_has_plant_map(eicos_multi *mh) { return mh ? eicos_batch_has_plant_map(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
+
+int eicos_multi_rollout(eicos_multi *mh, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
+                        int *exitcodes, int *iters) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    if (steps < 1) return mfail(EICOS_E_INVALID, "rollout: steps must be at least 1");
+    const size_t k = (size_t)eicos_batch_param_count(mh->shard[0]), ro = (size_t)eicos_batch_output_count(mh->shard[0]), T = (size_t)steps;
+    return for_shards(mh, [&](int s) {
+        const size_t f = (size_t)mh->first[s];
+        return eicos_batch_rollout(mh->shard[s], steps, theta0 ? theta0 + f * k : nullptr, w ? w + f * T * k : nullptr,
+                                   u_traj ? u_traj + f * T * ro : nullptr, theta_traj ? theta_traj + f * (T + 1) * k : nullptr,
+                                   exitcodes ? exitcodes + f * T : nullptr, iters ? iters + f * T : nullptr);
+    });
+}
+
 int eicos_multi_solution(eicos_multi *mh, double *x) {
     if (!mh || !x) return mfail(EICOS_E_INVALID, "NULL argument");
     if (mh->n == 0) return EICOS_OK;

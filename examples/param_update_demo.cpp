@@ -8,6 +8,9 @@
 // from a pageable theta + solve + outputs, updateRHSDevice from vectors already in device memory + solve + solution (that leg needs the
 // HIP runtime's allocation calls, looked up at run time; "n/a" without them), and stepParam -- the whole step in one call, pinned theta in,
 // the r selected outputs u = u0 + U x into a pinned array out.  stepParam's u must equal the output map applied to solution() bit for bit.
+// Last, a rollout: setPlantMap installs theta+ = f0 + F [theta | u] and rollout() runs 20 closed-loop steps of every instance in one call;
+// its u and theta trajectories must equal, bit for bit, those of 20 stepParam calls on pinned theta with the plant evaluated on the host,
+// and the wall time of both is printed (median of 5).
 //   g++ -std=c++17 -Iinclude examples/param_update_demo.cpp -Leicos_amd -leicos_amd -Wl,-rpath,$PWD/eicos_amd -o param_update_demo
 //   ./param_update_demo tests/golden/MPC02.epb 64 0,0 [k = 16] [steps = 20]
 #include <dlfcn.h>
@@ -204,6 +207,49 @@ int main(int argc, char **argv) {
             if (st >= 2) tc.push_back(ms(t3, t4));
         }
     }
+    // (4) the rollout: T = 20 steps in one call against 20 stepParam calls with the plant on the host, the same solver state on both sides
+    const int T = 20, REPS = 5;
+    Group gf; // row j: theta+[j] = 0.05 + 0.9 theta[j] + 1e-3 u[j mod R] (the first row also a second theta entry, stored after the u entry)
+    gf.rowptr.assign(1, 0);
+    for (int j = 0; j < k; j++) {
+        gf.base.push_back(0.05);
+        gf.col.push_back(j); gf.val.push_back(0.9);
+        gf.col.push_back(k + j % R); gf.val.push_back(1e-3);
+        if (j == 0 && k > 1) { gf.col.push_back(k - 1); gf.val.push_back(-0.01); }
+        gf.rowptr.push_back((int)gf.col.size());
+    }
+    const eicos_affine_map mf = gf.view();
+    EiCOS::BatchSolver *se = make(), *sf = make();
+    for (EiCOS::BatchSolver *v : {se, sf}) { v->setParamMap(k, &mc, m ? &mh : nullptr, p ? &mb : nullptr); v->setOutputMap(R, &mo); v->setWarmStart(0.1); }
+    se->setPlantMap(&mf);
+    std::vector<double> ut((size_t)B * T * R), tt((size_t)B * (T + 1) * k), ut_ref(ut.size()), tt_ref(tt.size()), z((size_t)B * (k + R)), nxt;
+    std::vector<double> tr, tl;
+    bool same_roll = true;
+    for (int rep = 0; rep < REPS + 1; rep++) { // (the first repetition warms the paths up and is not timed)
+        const std::vector<double> th = theta_of(rep);
+        auto t0 = now();
+        const std::vector<EiCOS::exitcode> ce = se->rollout(T, th.data(), ut.data(), nullptr, tt.data());
+        auto t1 = now();
+        std::copy(th.begin(), th.end(), pth);
+        std::vector<EiCOS::exitcode> cf((size_t)B * T);
+        for (int t = 0; t < T; t++) {
+            for (int i = 0; i < B; i++) std::copy(pth + (size_t)i * k, pth + (size_t)(i + 1) * k, tt_ref.begin() + ((size_t)i * (T + 1) + t) * k);
+            const std::vector<EiCOS::exitcode> cd = sf->stepParam(pth, pu);
+            for (int i = 0; i < B; i++) {
+                cf[(size_t)i * T + t] = cd[i];
+                std::copy(pu + (size_t)i * R, pu + (size_t)(i + 1) * R, ut_ref.begin() + ((size_t)i * T + t) * R);
+                std::copy(pth + (size_t)i * k, pth + (size_t)(i + 1) * k, z.begin() + (size_t)i * (k + R));
+                std::copy(pu + (size_t)i * R, pu + (size_t)(i + 1) * R, z.begin() + (size_t)i * (k + R) + k);
+            }
+            gf.evaluate(z, k + R, B, nxt); // (the plant on the host, in the stated order)
+            std::copy(nxt.begin(), nxt.end(), pth);
+        }
+        for (int i = 0; i < B; i++) std::copy(pth + (size_t)i * k, pth + (size_t)(i + 1) * k, tt_ref.begin() + ((size_t)i * (T + 1) + T) * k);
+        auto t2 = now();
+        same_roll = same_roll && ce == cf && same(ut, ut_ref) && same(tt, tt_ref) && same(se->solution(), sf->solution());
+        if (rep >= 1) { tr.push_back(ms(t0, t1)); tl.push_back(ms(t1, t2)); }
+    }
+    delete se; delete sf;
     const bool device_leg = sc != nullptr;
     delete sa; delete sb; delete sc; delete sd;
     EiCOS::BatchSolver::hostFree(pth); EiCOS::BatchSolver::hostFree(pu);
@@ -217,5 +263,9 @@ int main(int argc, char **argv) {
     if (device_leg) std::printf("  updateRHSDevice + solve + solution   %8.3f ms  %7d B in  %6d B out  (inputs already in device memory)\n", median(tc), 0, 8 * n);
     else std::printf("  updateRHSDevice + solve + solution        n/a\n");
     std::printf("  stepParam (pinned theta, pinned u)   %8.3f ms  %7d B in  %6d B out\n", median(td), 8 * k, 8 * R);
-    return (same_all && same_sub && same_loop && same_u) ? 0 : 1; // (bit-identity is the contract: it holds for every exit code)
+    std::printf("rollout vs %d stepParam calls with the plant on the host: %s\n", T, same_roll ? "bit-identical" : "DIFFERENT");
+    std::printf("closed loop of %d steps, batch %d, k = %d, r = %d, median of %d:\n", T, B, k, R, REPS);
+    std::printf("  rollout (one call)                   %8.3f ms\n", median(tr));
+    std::printf("  %d x stepParam, plant on the host    %8.3f ms\n", T, median(tl));
+    return (same_all && same_sub && same_loop && same_u && same_roll) ? 0 : 1; // (bit-identity is the contract: it holds for every exit code)
 }

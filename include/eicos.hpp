@@ -181,6 +181,22 @@ namespace EiCOS
             for (int i = 0; i < batch_; i++) out[i] = static_cast<exitcode>(codes[i]);
             return out;
         }
+        // Extension: the simulated plant of a closed loop, theta+ = f0 + F [theta | u] (+ w) (eicos_affine_map: base[k] + CSR matrix
+        // k x (k + r)), installed behind the parameter and the output map; nullptr removes it.  rollout() then runs `steps` closed-loop
+        // steps of every instance in ONE call -- stepParam on the current theta row, then the plant map -- from theta0 [batch][k] and the
+        // optional disturbance w [batch][steps][k] into u_traj [batch][steps][r] and, optionally, theta_traj [batch][steps + 1][k] and
+        // iters [batch][steps]: bit for bit what the loop over stepParam gives, with an LDS vector on the handle in one launch per shard.
+        // Returns the exit codes, [batch][steps].
+        void setPlantMap(const eicos_affine_map *f) { mcheck(eicos_multi_set_plant_map(h_, f), "eicos_multi_set_plant_map"); }
+        std::vector<exitcode> rollout(int steps, const double *theta0, double *u_traj, const double *w = nullptr, double *theta_traj = nullptr,
+                                      int *iters = nullptr)
+        {
+            std::vector<int> codes((size_t)batch_ * (steps > 0 ? steps : 0));
+            mcheck(eicos_multi_rollout(h_, steps, theta0, w, u_traj, theta_traj, codes.data(), iters), "eicos_multi_rollout");
+            std::vector<exitcode> out(codes.size());
+            for (size_t i = 0; i < codes.size(); i++) out[i] = static_cast<exitcode>(codes[i]);
+            return out;
+        }
         // Extension (not in the reference): re-solves start from the previous solution, see eicos_amd.h
         void setWarmStart(double shift) { mcheck(eicos_multi_set_warm_start(h_, shift), "eicos_multi_set_warm_start"); }
         // Extension: ECOS-style dynamic regularisation (the reference's Settings::delta / ::eps are never read)

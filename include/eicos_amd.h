@@ -216,6 +216,41 @@ int eicos_batch_outputs_device(eicos_batch *hd, int first, int count, double *du
 int eicos_batch_update_param_solve(eicos_batch *hd, const double *theta /* [batch][k] */, double *u_out /* [batch][r], optional */,
                                    double *x_out /* [batch][n], optional */, int *exitcodes /* optional */);
 
+/* ---- plant map and the closed-loop rollout (no reference counterpart).  In a simulated closed loop the next parameter row is itself
+ * affine in the current one and in the move just computed: theta+ = f0 + F [theta | u] (+ w).  A handle holds one such map beside the
+ * other two: eicos_affine_map with base[k] and a CSR matrix k x (k + r) (rowptr[k + 1], col / val[rowptr[k]]; columns index
+ * z = [theta (k) | u (r)], i.e. lie in [0, k + r)).  eicos_batch_set_plant_map COPIES the host arrays into one device allocation; a later
+ * call replaces the map, f = NULL removes it.  It needs a parameter map (k > 0) and an output map (r > 0) and remembers the (k, r) it was
+ * validated for.  EICOS_E_INVALID, with a message naming the fault, for rowptr[0] != 0, decreasing row pointers, a column outside
+ * [0, k + r), "no parameter map" and "no output map".  eicos_batch_has_plant_map: 1 / 0.
+ * eicos_batch_rollout takes every instance through `steps` closed-loop steps in ONE synchronous call.  For instance i:
+ *     theta_traj[i][0] = theta0[i], copied verbatim;
+ *     for t = 0 .. steps-1: exactly what eicos_batch_update_param_solve does for the row theta_traj[i][t] -- the update, the solve (with the
+ *     warm start and dynamic regularisation set on the handle) and the output row: u_traj[i][t] = that row, exitcodes[i][t] / iters[i][t]
+ *     = that solve's exit code / iteration count -- and then row j of theta_traj[i][t+1]:
+ *         acc = base[j];  for s in rowptr[j] .. rowptr[j+1]-1, in stored order:  acc = acc + (val[s] * z[col[s]])
+ *         with z = [theta_traj[i][t] | u_traj[i][t]];  then, if w != NULL:  acc = acc + w[i][t][j]
+ *     with every product and every sum rounded to fp64 on its own (no fused multiply-add).
+ * A step whose solve does not end OPTIMAL still produces its u row and the loop goes on (as u_out does); the per-step codes are the
+ * caller's record.  The rollout leaves the handle (instance slabs, eicos_batch_info / _solution / _duals, the KKT values of eicos_debug_kkt)
+ * and the returned arrays equal, bit for bit, to `steps` calls of eicos_batch_update_param_solve whose theta rows a host loop advances in
+ * the order above, on every build of the solve kernel and on both paths below; afterwards eicos_batch_info / _solution describe the last step.
+ * FUSED (eicos_batch_last_rollout_launches = 1): one launch of the solve kernel, in which a workgroup takes an instance through all its
+ * steps before it pulls the next one -- no launch, no transfer and no barrier across the batch between steps.  Taken when the handle has
+ * an LDS vector, k + r <= the length of that vector (the padded KKT dimension: the plant map stages [theta | u] there) and
+ * EICOS_FUSED_UPDATE is not 0.  Otherwise (= steps) the call enqueues, per step, the parametric range kernel, the solve launch, the output
+ * range kernel and the plant range kernel on the handle's stream, without host synchronisation in between.
+ * Every array may be pageable, pinned / registered or device memory: the handle keeps device copies of the trajectories (grown on
+ * demand), copies theta0 and w in before the launch and the results out after it.  theta_traj, exitcodes and iters are optional.
+ * EICOS_E_INVALID for steps < 1, u_traj == NULL, theta0 == NULL, a missing map of any of the three kinds, and a plant map installed for
+ * another (k, r) than the maps now installed (the message names both pairs). */
+int eicos_batch_set_plant_map(eicos_batch *hd, const eicos_affine_map *f);
+int eicos_batch_has_plant_map(eicos_batch *hd);
+int eicos_batch_rollout(eicos_batch *hd, int steps, const double *theta0 /* [batch][k] */, const double *w /* [batch][steps][k], optional */,
+                        double *u_traj /* [batch][steps][r] */, double *theta_traj /* [batch][steps + 1][k], optional */,
+                        int *exitcodes /* [batch][steps], optional */, int *iters /* [batch][steps], optional */);
+int eicos_batch_last_rollout_launches(eicos_batch *hd); /* solve-kernel launches of the most recent rollout: 1 = fused */
+
 /* ---- solve: replaces exitcode Solver::solve(bool) (reference include/eicos.hpp:158,
  * src/eicos.cpp:848-1262) for every instance of the batch.  exitcodes (host, [batch]) may be
  * NULL.  Synchronous: returns after the GPU work has completed. */
@@ -334,6 +369,12 @@ int eicos_multi_set_output_map(eicos_multi *mh, int r, const eicos_affine_map *u
 int eicos_multi_output_count(eicos_multi *mh);
 int eicos_multi_outputs(eicos_multi *mh, int first, int count, double *u);
 int eicos_multi_update_param_solve(eicos_multi *mh, const double *theta, double *u_out, double *x_out, int *exitcodes);
+/* plant map and rollout (eicos_batch_set_plant_map / _has_plant_map / _rollout on every shard): the map is installed on every shard; the
+ * arrays are in global instance order ([batch][steps][...]: every shard's rows are contiguous), the shards run concurrently */
+int eicos_multi_set_plant_map(eicos_multi *mh, const eicos_affine_map *f);
+int eicos_multi_has_plant_map(eicos_multi *mh);
+int eicos_multi_rollout(eicos_multi *mh, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
+                        int *exitcodes, int *iters);
 /* solve: async = enqueue every shard's kernels on its stream and return; sync waits for all; eicos_multi_solve = both (+ exit codes, may be NULL) */
 int eicos_multi_solve_async(eicos_multi *mh);
 int eicos_multi_sync(eicos_multi *mh);
