@@ -135,6 +135,12 @@ def _lib():
                 getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
             L.eicos_batch_last_rollout_launches.argtypes = [vp]
             L.eicos_batch_last_rollout_launches.restype = C.c_int
+        if hasattr(L, "eicos_batch_set_matrix_map"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            mp = C.POINTER(AffineMap)
+            L.eicos_batch_set_matrix_map.argtypes = L.eicos_multi_set_matrix_map.argtypes = [vp, mp, mp]
+            L.eicos_batch_has_matrix_map.argtypes = L.eicos_multi_has_matrix_map.argtypes = [vp]
+            for f in ("set_matrix_map", "has_matrix_map"):
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -407,6 +413,63 @@ def _plant_map_ptr(fmap, k, r):
     return (m, one), C.pointer(m)
 
 
+class MatrixMap:
+    """The stored values of G and A affine in the parameter row theta of length k: Gpr = G0 + Gm theta, Apr = A0 + Am theta.  Per matrix
+    `(base, rowptr, col, val)` -- base[nnz] and a CSR matrix with one row per stored value (CSC order of Gpr / Apr) and k columns -- or
+    None: that matrix is not mapped (an update keeps and re-equilibrates it).  evaluate() is the host restatement of what a parametric
+    update forms on the GPU under the map, in the same rounding order."""
+
+    def __init__(self, k: int, G=None, A=None):
+        self.k = int(k)
+        self.G, self.A = (None if g is None else (np.ascontiguousarray(g[0], np.float64), np.ascontiguousarray(g[1], np.int32),
+                                                  np.ascontiguousarray(g[2], np.int32), np.ascontiguousarray(g[3], np.float64))
+                          for g in (G, A))
+
+    def groups(self):
+        return self.G, self.A
+
+    def evaluate(self, theta):
+        """(Gpr, Apr) for theta [B, k]: arrays [B, nnz], None for a matrix without a map.  Entry e: acc = base[e], then for every stored
+        entry t of row e, in stored order, acc = acc + (val[t] * theta[col[t]]) -- the product and the sum each rounded to float64
+        (numpy has no fused multiply-add), which is the order of eicos_batch_set_matrix_map."""
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.k:
+            raise ValueError(f"theta has shape {theta.shape}, expected [count, {self.k}]")
+        out = []
+        for g in self.groups():
+            if g is None:
+                out.append(None)
+                continue
+            base, rowptr, col, val = g
+            acc = np.repeat(base[None, :], theta.shape[0], axis=0)
+            length = np.diff(rowptr)
+            for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
+                rows = np.nonzero(length > j)[0]
+                t = rowptr[rows] + j
+                acc[:, rows] = acc[:, rows] + val[t][None, :] * theta[:, col[t]]
+            out.append(acc)
+        return tuple(out)
+
+
+def _matrix_map_ptrs(mmap, nnzG, nnzA):
+    """A MatrixMap as (keep-alive structs, [G, A] as C pointers to eicos_affine_map or None); array sizes are checked here, their
+    contents (row pointers, column range, matrix present in the pattern, the parameter map it needs) by the library."""
+    keep, ptrs = [], []
+    for name, g, rows in zip("GA", mmap.groups(), (nnzG, nnzA)):
+        if g is None:
+            ptrs.append(None)
+            continue
+        base, rowptr, col, val = g
+        if base.size != rows or rowptr.size != rows + 1 or col.size != val.size or (rowptr.size and rowptr[-1] > col.size):
+            raise ValueError(f"matrix map of {name}: base[{base.size}], rowptr[{rowptr.size}], col[{col.size}], val[{val.size}] "
+                             f"do not describe {rows} stored values")
+        one = np.zeros(1)
+        m = AffineMap(_dp(base if base.size else one), _ip(rowptr), _ip(col if col.size else np.zeros(1, np.int32)), _dp(val if val.size else one))
+        keep.append((m, one))
+        ptrs.append(C.pointer(m))
+    return keep, ptrs
+
+
 def _disturbance(w, count, steps, k):
     """w as a contiguous float64 [count, steps, k] array (None passes); ValueError otherwise."""
     if w is None:
@@ -563,6 +626,21 @@ class _Solver:
 
     def has_plant_map(self) -> bool:
         return bool(getattr(_lib(), self._prefix + "has_plant_map")(self._h))
+
+    # ---- matrix map: G and A affine in theta (include/eicos_amd.h: eicos_batch_set_matrix_map) ----
+    def set_matrix_map(self, mmap: "MatrixMap | None"):
+        """Install (copy) a MatrixMap for all instances, behind the parameter map it refers to; None removes it.  update_param,
+        update_param_device, update_param_solve and rollout then run a full updateData whose inputs the GPU forms from theta: the state
+        of update(*mmap.evaluate(theta), *pmap.evaluate(theta)) in the contract of eicos_batch_set_matrix_map, bit for bit."""
+        if mmap is None:
+            self._call("set_matrix_map", None, None)
+            return
+        _keep, ptrs = _matrix_map_ptrs(mmap, self.pat.nnzG, self.pat.nnzA)
+        self._call("set_matrix_map", *ptrs)
+
+    def has_matrix_map(self) -> int:
+        """Bit 0: G is mapped, bit 1: A is mapped; 0: no matrix map."""
+        return int(getattr(_lib(), self._prefix + "has_matrix_map")(self._h))
 
     def rollout(self, theta0, steps: int, w=None):
         """`steps` closed-loop steps of the whole batch in one call: from theta0 [batch, k], every step is update_param_solve on the

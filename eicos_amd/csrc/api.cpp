@@ -129,6 +129,10 @@ struct eicos_batch {
     // rollout (eicos_batch_rollout): one device allocation, grown on demand: [RolloutDev (MAP_HEADER bytes) | theta, u, w trajectories | two
     // theta rows of the batch (the path that is not fused) | codes, iters]; roll = the host copy of the record of the most recent call
     RolloutDev roll{}; void *d_roll = nullptr; size_t roll_bytes = 0; int rollout_launches = 0;
+    // matrix map (eicos_batch_set_matrix_map): one device allocation [MatrixMapDev (MAP_HEADER bytes) | base, val | rowptr, col], mat.k = 0
+    // while none is installed; d_mstage = the device staging buffer the range path expands [Gpr | Apr | c | h | b] of a chunk of instances
+    // into (param_range), grown on demand up to MSTAGE_CAP_MB
+    MatrixMapDev mat{}; void *d_mat = nullptr; double *d_mstage = nullptr; size_t mstage_doubles = 0;
     TilePlan tiles;        // tile mode (Symbolic::tile): the dense-front plan
 };
 
@@ -1037,7 +1041,7 @@ int eicos_batch_destroy(eicos_batch *h) {
     for (int i = 0; i < eicos_batch::EV_RING; i++)
         for (hipEvent_t e : {h->ring_s[i][0], h->ring_s[i][1], h->ring_u[i][0], h->ring_u[i][1]}) if (e) (void)hipEventDestroy(e);
     for (void *ptr : {(void *)h->d_pattern, (void *)h->d_inst, (void *)h->d_work, (void *)h->d_queue, (void *)h->d_scratch,
-                      (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out, h->d_plant, h->d_roll})
+                      (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out, h->d_plant, h->d_roll, h->d_mat, (void *)h->d_mstage})
         if (ptr) (void)hipFree(ptr);
     for (int i = 0; i < 2; i++) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     if (h->stage_pin) (void)hipHostFree(h->stage_pin);
@@ -1300,6 +1304,21 @@ static int take_inputs(UpdateInputs &in, eicos_batch *h, int first, int count, c
     return EICOS_OK;
 }
 
+// A matrix map (eicos_batch_set_matrix_map) against the parameter map installed NOW -- checked where the map is installed and again by
+// every call that consumes theta, because the parameter map can be replaced in between: the same k, and the vector updateData reads with
+// a matrix (h with Gpr, b with Apr: take_inputs) mapped too.
+static int matrix_map_fits(const eicos_batch *h) {
+    if (h->mat.k == 0) return EICOS_OK;
+    if (h->mat.k != h->param.k)
+        return fail(EICOS_E_INVALID, "matrix map: installed for k = " + std::to_string(h->mat.k) + ", the parameter map now installed has k = " +
+                                         std::to_string(h->param.k) + ": install it again");
+    if (h->mat.g[0].base && h->dp.m > 0 && !h->param.g[1].base)
+        return fail(EICOS_E_INVALID, "matrix map of G: the parameter map has no h group (updateData reads h with Gpr)");
+    if (h->mat.g[1].base && h->dp.p > 0 && !h->param.g[2].base)
+        return fail(EICOS_E_INVALID, "matrix map of A: the parameter map has no b group (updateData reads b with Apr)");
+    return EICOS_OK;
+}
+
 // The inputs of a parametric update (eicos_batch_update_param*): one more kind of UpdateInputs -- a single group, theta, `k` doubles per
 // instance -- so that the rows travel over the very paths of the other updates (bounce, pinned in place, device, peer in place / staged).
 static int take_theta(UpdateInputs &in, eicos_batch *h, int first, int count, const double *theta, bool kinds) {
@@ -1307,6 +1326,7 @@ static int take_theta(UpdateInputs &in, eicos_batch *h, int first, int count, co
     if (h->param.k == 0) return fail(EICOS_E_INVALID, "no parameter map (eicos_batch_set_param_map installs one)");
     if (first < 0 || count < 0 || first + count > h->batch) return fail(EICOS_E_INVALID, "instance range out of bounds");
     if (!theta) return fail(EICOS_E_INVALID, "theta is NULL");
+    { const int rc = matrix_map_fits(h); if (rc != EICOS_OK) return rc; }
     HIP_TRY(hipSetDevice(h->device));
     const size_t k = (size_t)h->param.k;
     in = UpdateInputs{h, first, count, false, true, {nullptr, nullptr, theta, nullptr, nullptr}, {0, 0, k, 0, 0}, {}, k};
@@ -1315,12 +1335,64 @@ static int take_theta(UpdateInputs &in, eicos_batch *h, int first, int count, co
 }
 
 // the updateData kernel (full, right-hand-side-only -- kernels.hip: rhs_instance -- or parametric: k_update_param_range) of rows [first, first + count) on five pointers the GPU addresses
+// The parametric update of instances [first, first + count) from rows of theta the GPU addresses, on the handle's stream.  Without a
+// matrix map: the right-hand-side kernel.  With one the update is a FULL updateData whose inputs are formed on the GPU: chunk by chunk,
+// the mapped groups [Gpr | Apr | c | h | b] are expanded into the handle's device staging buffer (launch_expand_affine; h only with G, b
+// only with A, as updateData reads them) and the unchanged launch_update runs on those pointers -- stream order keeps a chunk's expansion
+// behind the previous chunk's updateData; the buffer grows on demand up to MSTAGE_CAP_MB.  A vector mapped without its matrix then goes
+// through the right-hand-side kernel, which divides by the scalings that updateData has just stored.
+static constexpr int MSTAGE_CAP_MB = 64; // (EICOS_MATRIX_STAGE_MB under EICOS_EXPERIMENT=1: tests reach several chunks with a small batch)
+static int param_range(eicos_batch *h, int first, int count, const double *theta) {
+    const DevPat &D = h->dp;
+    const ParamMapDev &M = h->param;
+    if (h->mat.k == 0) {
+        const int width = (M.g[0].base ? D.n : 0) + (M.g[1].base ? D.m : 0) + (M.g[2].base ? D.p : 0);
+        HIP_TRY(launch_update_param(h->pslot, h->d_inst, first, count, M, theta, width, h->stream));
+        return EICOS_OK;
+    }
+    if (count == 0) return EICOS_OK;
+    const bool mG = h->mat.g[0].base != nullptr, mA = h->mat.g[1].base != nullptr;
+    const AffineDev *src[5] = {mG ? &h->mat.g[0] : nullptr, mA ? &h->mat.g[1] : nullptr, M.g[0].base ? &M.g[0] : nullptr,
+                               mG && D.m > 0 ? &M.g[1] : nullptr, mA && D.p > 0 ? &M.g[2] : nullptr};
+    const int w[5] = {D.nnzG, D.nnzA, D.n, D.m, D.p};
+    size_t per = 0;
+    for (int g = 0; g < 5; g++) if (src[g]) per += (size_t)w[g] + 8; // (+ 8 doubles per array: every array of a chunk starts 64-byte aligned)
+    const size_t cap = (size_t)env_knob("EICOS_MATRIX_STAGE_MB", MSTAGE_CAP_MB, 1, 4096) * ((1u << 20) / sizeof(double));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, cap / per));
+    const size_t need = (size_t)chunk * per;
+    if (need > h->mstage_doubles) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->d_mstage) { (void)hipFree(h->d_mstage); h->d_mstage = nullptr; h->mstage_doubles = 0; }
+        HIP_TRY(hipMalloc((void **)&h->d_mstage, need * sizeof(double)));
+        h->mstage_doubles = need;
+    }
+    for (int o = 0; o < count; o += chunk) {
+        const int cnt = std::min(chunk, count - o);
+        const double *arr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        double *at = h->d_mstage;
+        for (int g = 0; g < 5; g++) {
+            if (!src[g]) continue;
+            arr[g] = at;
+            HIP_TRY(launch_expand_affine(*src[g], w[g], M.k, theta + (size_t)o * M.k, cnt, at, h->stream));
+            at += ((size_t)cnt * w[g] + 7) / 8 * 8;
+        }
+        HIP_TRY(launch_update(h->pslot, h->d_inst, first + o, cnt, arr[0], arr[1], arr[2], arr[3], arr[4], h->d_scratch, std::min(cnt, h->upd_grid),
+                              h->upd_lds, h->upd_vals_lds, h->stream));
+    }
+    ParamMapDev rest{};
+    rest.k = M.k;
+    if (!mG) rest.g[1] = M.g[1];
+    if (!mA) rest.g[2] = M.g[2];
+    const int width = (rest.g[1].base ? D.m : 0) + (rest.g[2].base ? D.p : 0);
+    HIP_TRY(launch_update_param(h->pslot, h->d_inst, first, count, rest, theta, width, h->stream));
+    return EICOS_OK;
+}
+
 static int launch_range(const UpdateInputs &in, int first, int count, const double *const p[5]) {
     eicos_batch *h = in.h;
     if (in.param) {
-        const DevPat &D = h->dp;
-        const int width = (h->param.g[0].base ? D.n : 0) + (h->param.g[1].base ? D.m : 0) + (h->param.g[2].base ? D.p : 0);
-        HIP_TRY(launch_update_param(h->pslot, h->d_inst, first, count, h->param, p[2], width, h->stream));
+        const int rc = param_range(h, first, count, p[2]);
+        if (rc != EICOS_OK) return rc;
     } else if (in.rhs) HIP_TRY(launch_update_rhs(h->pslot, h->d_inst, first, count, p[2], p[3], p[4], (int)in.per, h->stream));
     else HIP_TRY(launch_update(h->pslot, h->d_inst, first, count, p[0], p[1], p[2], p[3], p[4], h->d_scratch, std::min(count, h->upd_grid), h->upd_lds, h->upd_vals_lds, h->stream));
     return EICOS_OK;
@@ -1755,6 +1827,8 @@ int eicos_batch_solve(eicos_batch *h, int *exitcodes) {
 // the fused form divides by the stored scalings, kernels.hip: rhs_instance), eicos_batch_update_rhs_solve.
 // kind = STEP_PARAM: the parametric update (theta [batch][k] through the installed map, the five arrays NULL; fused while a theta row fits
 // the LDS vector the workgroup stages it in, kernels.hip: param_instance; pageable theta is never staged), eicos_batch_update_param_solve.
+// With a matrix map installed the step is a full updateData from theta (kernels.hip: matrix_param_instance): fused under the conditions of
+// both, a theta row that fits and the accumulator limit of the full update.
 // u_out (optional, [batch][r]; any kind, needs an output map): the output map applied to every instance's x, delivered like x_out -- written
 // by the kernel where it can be, by the range kernel and a copy otherwise.
 enum StepKind { STEP_FULL = 0, STEP_RHS = 1, STEP_PARAM = 2 };
@@ -1766,7 +1840,9 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
     if (rc != EICOS_OK) return rc;
     if (u_out && h->out.r == 0) return fail(EICOS_E_INVALID, "no output map (eicos_batch_set_output_map installs one)");
     const DevPat &D = h->dp;
-    const bool fits = param ? h->param.k <= D.Npad : (rhs || (D.n <= 8 * h->threads && D.p <= 8 * h->threads && D.m <= 16 * h->threads));
+    // (the in-register scaling accumulators of update_instance: a full updateData, or a parametric one under a matrix map, needs them)
+    const bool own = D.n <= 8 * h->threads && D.p <= 8 * h->threads && D.m <= 16 * h->threads;
+    const bool fits = param ? (h->param.k <= D.Npad && (h->mat.k == 0 || own)) : (rhs || own);
     const bool fused = h->nlds >= 1 && fits && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
     // arrays the GPU cannot address (pageable memory) are STAGED: copied into the handle's pinned staging buffer while the kernel runs
     const bool any_staged = in.any(MEM_PAGEABLE);
@@ -1831,7 +1907,7 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
         h->fused = UpdArgs{ptr[0], ptr[1], param ? nullptr : ptr[2], ptr[3], ptr[4], x_kind != MEM_PAGEABLE ? x_out : nullptr,
                            param ? UPD_PARAM : (rhs ? UPD_RHS : UPD_FULL), any_staged ? h->stage_flags : nullptr, chunk, h->stage_seq, h->d_err,
                            static_cast<const ParamMapDev *>(h->d_param), static_cast<const OutMapDev *>(h->d_out), param ? ptr[2] : nullptr,
-                           u_kind != MEM_PAGEABLE ? u_out : nullptr};
+                           u_kind != MEM_PAGEABLE ? u_out : nullptr, nullptr, param && h->mat.k ? static_cast<const MatrixMapDev *>(h->d_mat) : nullptr};
         h->fused_pending = true;
         rc = eicos_batch_solve_async(h);
         h->fused_pending = false;
@@ -1914,6 +1990,73 @@ int eicos_batch_set_plant_map(eicos_batch *h, const eicos_affine_map *f) {
     return EICOS_OK;
 }
 
+// ---- matrix map: the stored values of G and A affine in theta (no reference counterpart) ----
+// Validated like the other maps and packed into ONE device allocation of its own: [MatrixMapDev (MAP_HEADER bytes) | base, val | rowptr,
+// col] -- the range path takes the groups by value, the fused step reads the descriptor through a pointer (UpdArgs::mmap).
+static_assert(sizeof(MatrixMapDev) <= MAP_HEADER, "map descriptor larger than its header");
+int eicos_batch_set_matrix_map(eicos_batch *h, const eicos_affine_map *G, const eicos_affine_map *A) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    const DevPat &D = h->dp;
+    const int k = h->param.k;
+    const eicos_affine_map *g[2] = {G, A};
+    const int rows[2] = {D.nnzG, D.nnzA};
+    const char *name[2] = {"G", "A"};
+    const bool remove = !G && !A;
+    size_t nd = 0, ni = 0;
+    for (int q = 0; q < 2 && !remove; q++) {
+        if (!g[q]) continue;
+        const std::string who = std::string("matrix map of ") + name[q] + ": ";
+        if (k == 0) return fail(EICOS_E_INVALID, who + "no parameter map (eicos_batch_set_param_map installs one)");
+        if (rows[q] == 0) return fail(EICOS_E_INVALID, who + "the pattern has no such matrix (it stores no entries)");
+        if (!g[q]->base || !g[q]->rowptr) return fail(EICOS_E_INVALID, who + "base or rowptr is NULL");
+        const int *rp = g[q]->rowptr;
+        if (rp[0] != 0) return fail(EICOS_E_INVALID, who + "rowptr[0] must be 0");
+        for (int r = 0; r < rows[q]; r++)
+            if (rp[r + 1] < rp[r]) return fail(EICOS_E_INVALID, who + "rowptr decreases at row " + std::to_string(r));
+        const int nnz = rp[rows[q]];
+        if (nnz > 0 && (!g[q]->col || !g[q]->val)) return fail(EICOS_E_INVALID, who + "col or val is NULL");
+        for (int t = 0; t < nnz; t++)
+            if (g[q]->col[t] < 0 || g[q]->col[t] >= k) return fail(EICOS_E_INVALID, who + "column " + std::to_string(g[q]->col[t]) + " of entry " + std::to_string(t) + " is outside [0, k)");
+        nd += (size_t)rows[q] + nnz; ni += (size_t)rows[q] + 1 + nnz;
+    }
+    MatrixMapDev M{};
+    M.k = remove ? 0 : k;
+    if (!remove) { // (against the parameter map as it is now; every call that consumes theta checks again: matrix_map_fits)
+        if (G && D.m > 0 && !h->param.g[1].base) return fail(EICOS_E_INVALID, "matrix map of G: the parameter map has no h group (updateData reads h with Gpr)");
+        if (A && D.p > 0 && !h->param.g[2].base) return fail(EICOS_E_INVALID, "matrix map of A: the parameter map has no b group (updateData reads b with Apr)");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
+    if (h->d_mat) { (void)hipFree(h->d_mat); h->d_mat = nullptr; }
+    h->mat = MatrixMapDev{};
+    if (remove) return EICOS_OK;
+    std::vector<char> buf(MAP_HEADER + nd * sizeof(double) + ni * sizeof(int));
+    double *hd_ = reinterpret_cast<double *>(buf.data() + MAP_HEADER);
+    int *hi_ = reinterpret_cast<int *>(buf.data() + MAP_HEADER + nd * sizeof(double));
+    void *dev = nullptr;
+    HIP_TRY(hipMalloc(&dev, buf.size()));
+    const double *dd = reinterpret_cast<const double *>(static_cast<const char *>(dev) + MAP_HEADER);
+    const int *di = reinterpret_cast<const int *>(static_cast<const char *>(dev) + MAP_HEADER + nd * sizeof(double));
+    size_t od = 0, oi = 0;
+    for (int q = 0; q < 2; q++) {
+        if (!g[q]) continue;
+        const int nnz = g[q]->rowptr[rows[q]];
+        M.g[q].base = dd + od; std::copy(g[q]->base, g[q]->base + rows[q], hd_ + od); od += rows[q];
+        M.g[q].val = dd + od; if (nnz) std::copy(g[q]->val, g[q]->val + nnz, hd_ + od); od += nnz;
+        M.g[q].rowptr = di + oi; std::copy(g[q]->rowptr, g[q]->rowptr + rows[q] + 1, hi_ + oi); oi += rows[q] + 1;
+        M.g[q].col = di + oi; if (nnz) std::copy(g[q]->col, g[q]->col + nnz, hi_ + oi); oi += nnz;
+    }
+    std::memcpy(buf.data(), &M, sizeof M);
+    const hipError_t e = hipMemcpy(dev, buf.data(), buf.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the matrix map: ") + hipGetErrorString(e)); }
+    h->d_mat = dev; h->mat = M;
+    return EICOS_OK;
+}
+
+int eicos_batch_has_matrix_map(eicos_batch *h) {
+    return h ? ((h->mat.g[0].base ? 1 : 0) | (h->mat.g[1].base ? 2 : 0)) : fail(EICOS_E_INVALID, "NULL handle");
+}
+
 int eicos_batch_has_plant_map(eicos_batch *h) { return h ? (h->plant.k > 0 ? 1 : 0) : fail(EICOS_E_INVALID, "NULL handle"); }
 int eicos_batch_last_rollout_launches(eicos_batch *h) { return h ? h->rollout_launches : fail(EICOS_E_INVALID, "NULL handle"); }
 
@@ -1932,6 +2075,7 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
     if (h->plant.k != k || h->plant.r != r)
         return fail(EICOS_E_INVALID, "rollout: the plant map was installed for (k, r) = (" + std::to_string(h->plant.k) + ", " + std::to_string(h->plant.r) +
                                          "), the maps now installed have (" + std::to_string(k) + ", " + std::to_string(r) + "): install it again");
+    { const int rc = matrix_map_fits(h); if (rc != EICOS_OK) return rc; }
     if (!theta0) return fail(EICOS_E_INVALID, "rollout: theta0 is NULL");
     if (!u_traj) return fail(EICOS_E_INVALID, "rollout: u_traj is NULL");
     HIP_TRY(hipSetDevice(h->device));
@@ -1952,7 +2096,8 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
     HIP_TRY(hipMemcpyAsync(h->d_roll, &h->roll, sizeof(RolloutDev), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpy2DAsync(d_th, (T + 1) * row_b, theta0, row_b, row_b, B, hipMemcpyDefault, h->stream)); // row 0 of every trajectory
     if (w) HIP_TRY(hipMemcpyAsync(d_w, w, n_w * sizeof(double), hipMemcpyDefault, h->stream));
-    const bool fused = h->nlds >= 1 && k + r <= D.Npad && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
+    const bool own = h->mat.k == 0 || (D.n <= 8 * h->threads && D.p <= 8 * h->threads && D.m <= 16 * h->threads); // (update_solve: the accumulator limit)
+    const bool fused = h->nlds >= 1 && k + r <= D.Npad && own && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
     int rc = EICOS_OK;
     if (fused) {
         h->last_update_path = 5;
@@ -1962,18 +2107,18 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
         h->fused.on = UPD_ROLL; h->fused.chunk = 1;
         h->fused.pmap = static_cast<const ParamMapDev *>(h->d_param); h->fused.omap = static_cast<const OutMapDev *>(h->d_out);
         h->fused.roll = static_cast<const RolloutDev *>(h->d_roll);
+        h->fused.mmap = h->mat.k ? static_cast<const MatrixMapDev *>(h->d_mat) : nullptr;
         h->fused_pending = true;
         rc = eicos_batch_solve_async(h);
         h->fused_pending = false;
         if (rc != EICOS_OK) return rc;
     } else {
-        const int width = (h->param.g[0].base ? D.n : 0) + (h->param.g[1].base ? D.m : 0) + (h->param.g[2].base ? D.p : 0);
         HIP_TRY(hipMemcpy2DAsync(d_cur, row_b, d_th, (T + 1) * row_b, row_b, B, hipMemcpyDeviceToDevice, h->stream));
         for (int t = 0; t < steps; t++) {
             const double *cur = d_cur + (size_t)(t & 1) * B * k;
             double *next = d_cur + (size_t)((t + 1) & 1) * B * k;
             rc = begin_update_timing(h);
-            if (rc == EICOS_OK && hipSuccess != launch_update_param(h->pslot, h->d_inst, 0, h->batch, h->param, cur, width, h->stream)) rc = fail(EICOS_E_HIP, "rollout: launch of the parametric update failed");
+            if (rc == EICOS_OK) rc = param_range(h, 0, h->batch, cur);
             rc = end_update_timing(h, rc);
             if (rc == EICOS_OK) rc = eicos_batch_solve_async(h);
             if (rc != EICOS_OK) return rc;

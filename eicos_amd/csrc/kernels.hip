@@ -159,6 +159,7 @@ struct alignas(16) Sh : ShI {
     // the kernel's arguments -- kept here, so that k_solve holds nothing more in registers across its stages than it does without a rollout
     int step;
     const RolloutDev *roll; const ParamMapDev *pmap; const OutMapDev *omap; int *queue;
+    const MatrixMapDev *mmap; // (UpdArgs::mmap: a rollout's steps run matrix_param_instance when it is set)
 };
 constexpr int KI_MAX = 2; // right-hand sides of a dual solve (kkt_solve<..., 2, true>)
 enum { TK_FACTOR = 0, TK_LDL, TK_KRES, TK_KPOST, TK_RESID, TK_FWD, TK_COUNT, TK_FA = 8, TK_FW1, TK_FB, TK_FW2 }; // 8..11: inside the factor
@@ -3106,8 +3107,10 @@ __device__ __forceinline__ void solve_instance(int ps, gdbl_p I, gdbl_p W, doubl
 // so that a batch handed over in (pinned) HOST memory is pulled over PCIe by the solve's own workgroups while other workgroups compute:
 // the registers and the LDS of a CU are fully owned by its resident solve workgroups, no other kernel could run beside them.
 // `q` = row of this instance in the input arrays (NULL = keep that group), I = its slab in HBM.
+// PRE (matrix_param_instance, LDSV = false only): the caller has already left the un-equilibrated values and vectors in the slab -- the first
+// phase is skipped and the input arrays are not read; everything from the equilibration sweeps on is this one body.
 typedef double EICOS_GLOBAL *hbm_p; // (global memory in every build: the LDS-resident build's gdbl_p is an LDS pointer)
-template <int T, bool LDSV>
+template <int T, bool LDSV, bool PRE = false>
 static __device__ __noinline__ __attribute__((not_tail_called)) void update_instance(int ps, hbm_p I, size_t q, const double *Gpr, const double *Apr, const double *cin,
                                                                                       const double *hin, const double *bin) {
     ps = uni(ps); I = uni_ptr(I);
@@ -3119,23 +3122,26 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void update_inst
     hbm_p Av = I + P.i_Av, Gv = I + P.i_Gv, cagv = I + P.i_cag, rAv = I + P.i_rA, rGv = I + P.i_rG;
     hbm_p cv = I + P.i_c, hv = I + P.i_h, bv = I + P.i_b, xe = I + P.i_xe, ae = I + P.i_ae, ge = I + P.i_ge;
     DevInfo *ginfo = reinterpret_cast<DevInfo *>(I + P.i_info);
-    const bool was_eq = ginfo->equilibrated != 0;
+    static_assert(!PRE || !LDSV, "a caller that prepares the values leaves them in the slab");
+    [[maybe_unused]] const bool was_eq = ginfo->equilibrated != 0;
     auto sA = [&] { if constexpr (LDSV) return gt + m; else return Av; }(); // working copy of the values: LDS, or in place
     auto sG = [&] { if constexpr (LDSV) return gt + m + nnzA; else return Gv; }();
-    __syncthreads();
-    // un-equilibrate what is kept, overwrite what is given (ref :2053-2074, :389-404) -> working copy of the values
-    for_t_pre<T, 4>(nnzA, [&](int k) {
-        if (Apr) return V3{Apr[(size_t)q * nnzA + k], 1., 1.};
-        return was_eq ? V3{Av[k], ae[P.Air[k]], xe[P.Acol[k]]} : V3{Av[k], 1., 1.};
-    }, [&](int k, const V3 &r) { sA[k] = (Apr || !was_eq) ? r.a : r.a * (r.b * r.c); });
-    for_t_pre<T, 4>(nnzG, [&](int k) {
-        if (Gpr) return V3{Gpr[(size_t)q * nnzG + k], 1., 1.};
-        return was_eq ? V3{Gv[k], ge[P.Gir[k]], xe[P.Gcol[k]]} : V3{Gv[k], 1., 1.};
-    }, [&](int k, const V3 &r) { sG[k] = (Gpr || !was_eq) ? r.a : r.a * (r.b * r.c); });
-    FOR_T(j, n) cv[j] = cin ? cin[(size_t)q * n + j] : (was_eq ? cv[j] * xe[j] : cv[j]);
-    FOR_T(r, p) bv[r] = Apr ? bin[(size_t)q * p + r] : (was_eq ? bv[r] * ae[r] : bv[r]);
-    FOR_T(i, m) hv[i] = Gpr ? hin[(size_t)q * m + i] : (was_eq ? hv[i] * ge[i] : hv[i]);
-    __syncthreads();
+    if constexpr (!PRE) {
+        __syncthreads();
+        // un-equilibrate what is kept, overwrite what is given (ref :2053-2074, :389-404) -> working copy of the values
+        for_t_pre<T, 4>(nnzA, [&](int k) {
+            if (Apr) return V3{Apr[(size_t)q * nnzA + k], 1., 1.};
+            return was_eq ? V3{Av[k], ae[P.Air[k]], xe[P.Acol[k]]} : V3{Av[k], 1., 1.};
+        }, [&](int k, const V3 &r) { sA[k] = (Apr || !was_eq) ? r.a : r.a * (r.b * r.c); });
+        for_t_pre<T, 4>(nnzG, [&](int k) {
+            if (Gpr) return V3{Gpr[(size_t)q * nnzG + k], 1., 1.};
+            return was_eq ? V3{Gv[k], ge[P.Gir[k]], xe[P.Gcol[k]]} : V3{Gv[k], 1., 1.};
+        }, [&](int k, const V3 &r) { sG[k] = (Gpr || !was_eq) ? r.a : r.a * (r.b * r.c); });
+        FOR_T(j, n) cv[j] = cin ? cin[(size_t)q * n + j] : (was_eq ? cv[j] * xe[j] : cv[j]);
+        FOR_T(r, p) bv[r] = Apr ? bin[(size_t)q * p + r] : (was_eq ? bv[r] * ae[r] : bv[r]);
+        FOR_T(i, m) hv[i] = Gpr ? hin[(size_t)q * m + i] : (was_eq ? hv[i] * ge[i] : hv[i]);
+    }
+    __syncthreads(); // (PRE: the caller's values are complete, and its theta row in the LDS vector is dead before the maxima reuse it)
     // the accumulated scalings live in registers of the thread that owns the index (fixed FOR_T mapping); they are
     // written once at the end.  Up to 8 indices per thread and vector: patterns beyond that take the generic kernel.
     constexpr int OWN = 8;
@@ -3262,6 +3268,42 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void param_insta
     __syncthreads(); // (the solve -- or the LDS-resident build's copy of the slab -- reads entries other threads wrote; the LDS vector is free again)
 }
 
+// The parametric update of one instance under a MATRIX map (eicos_batch_set_matrix_map; k_solve, fused: eicos_batch_update_param_solve and
+// the steps of eicos_batch_rollout): a full updateData whose inputs are formed from theta on the spot.  The theta row is staged once into
+// the idle LDS vector as in param_instance; then this function does what the first phase of update_instance does -- a mapped group gets
+// base + sum val * theta[col] (affine_row: stored order, product and sum rounded on their own), a kept group is un-equilibrated -- and
+// leaves the result in the slab, where update_instance<T, false> keeps its working copy anyway; the sweeps, the write-back, the ELL / tile
+// copies and the constants are update_instance's own body (PRE).  A vector mapped without its matrix (h without G, b without A) is
+// evaluated here as well: the write-back's division by the NEW scaling is the bits of a right-hand-side-only update behind the updateData.
+__device__ __forceinline__ double affine_row(const AffineDev &A, int row, const double *z) {
+    double acc = A.base[row];
+    const int t1 = A.rowptr[row + 1];
+    for (int t = A.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], z[A.col[t]]));
+    return acc;
+}
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void matrix_param_instance(int ps, hbm_p I, size_t q, const ParamMapDev *Mp, const MatrixMapDev *Xp,
+                                                                                            const double *theta) {
+    ps = uni(ps); I = uni_ptr(I); Mp = uni_ptr(Mp); Xp = uni_ptr(Xp); theta = uni_ptr(theta);
+    const DevPat &P = c_pat[ps];
+    const int k = Mp->k;
+    const AffineDev gG = Xp->g[0], gA = Xp->g[1], gc = Mp->g[0], gh = Mp->g[1], gb = Mp->g[2];
+    const bool was_eq = reinterpret_cast<const DevInfo EICOS_GLOBAL *>(I + P.i_info)->equilibrated != 0;
+    hbm_p Av = I + P.i_Av, Gv = I + P.i_Gv, cv = I + P.i_c, hv = I + P.i_h, bv = I + P.i_b, xe = I + P.i_xe, ae = I + P.i_ae, ge = I + P.i_ge;
+    const double *row = theta + q * (size_t)k;
+    double *th = g_dyn;
+    FOR_T(j, k) th[j] = row[j];
+    __syncthreads();
+    if (gA.base) { FOR_T(e, P.nnzA) Av[e] = affine_row(gA, e, th); }
+    else if (was_eq) for_t_pre<T, 4>(P.nnzA, [&](int e) { return V3{Av[e], ae[P.Air[e]], xe[P.Acol[e]]}; }, [&](int e, const V3 &r) { Av[e] = r.a * (r.b * r.c); });
+    if (gG.base) { FOR_T(e, P.nnzG) Gv[e] = affine_row(gG, e, th); }
+    else if (was_eq) for_t_pre<T, 4>(P.nnzG, [&](int e) { return V3{Gv[e], ge[P.Gir[e]], xe[P.Gcol[e]]}; }, [&](int e, const V3 &r) { Gv[e] = r.a * (r.b * r.c); });
+    if (gc.base) { FOR_T(j, P.n) cv[j] = affine_row(gc, j, th); } else if (was_eq) { FOR_T(j, P.n) cv[j] = cv[j] * xe[j]; }
+    if (gb.base) { FOR_T(r, P.p) bv[r] = affine_row(gb, r, th); } else if (was_eq) { FOR_T(r, P.p) bv[r] = bv[r] * ae[r]; }
+    if (gh.base) { FOR_T(i, P.m) hv[i] = affine_row(gh, i, th); } else if (was_eq) { FOR_T(i, P.m) hv[i] = hv[i] * ge[i]; }
+    update_instance<T, false, true>(ps, I, 0, nullptr, nullptr, nullptr, nullptr, nullptr); // (starts with the barrier behind this phase)
+}
+
 // The solution of one instance into row q of the caller's x [batch][n] (k_solve, after solve_instance and its barrier).  Out of line like
 // outputs_instance: the row's per-thread address is not carried through the solve.
 template <int T>
@@ -3326,7 +3368,9 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_par
     id = uni(id);
     __syncthreads(); // (the first step of the workgroup's first instance: k_solve has just filled g_S)
     const RolloutDev *Rp = uni_ptr(g_S.roll);
-    param_instance<T>(ps, I, 0, g_S.pmap, Rp->theta + ((size_t)id * (Rp->steps + 1) + g_S.step) * Rp->plant.k);
+    const double *row = Rp->theta + ((size_t)id * (Rp->steps + 1) + g_S.step) * Rp->plant.k;
+    if (g_S.mmap) matrix_param_instance<T>(ps, I, 0, g_S.pmap, g_S.mmap, row);
+    else param_instance<T>(ps, I, 0, g_S.pmap, row);
 }
 template <int T>
 static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_step(int ps, gcdbl_p I, int id) {
@@ -3376,7 +3420,7 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     __syncthreads();
 #endif
     if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.step = 0; g_S.next = (int)blockIdx.x; } // (next: the instance that is running)
-    if constexpr (NLDS >= 1) { if (threadIdx.x == 0) { g_S.roll = upd.roll; g_S.pmap = upd.pmap; g_S.omap = upd.omap; g_S.queue = queue; } }
+    if constexpr (NLDS >= 1) { if (threadIdx.x == 0) { g_S.roll = upd.roll; g_S.pmap = upd.pmap; g_S.omap = upd.omap; g_S.queue = queue; g_S.mmap = upd.mmap; } }
     // Instances differ in iteration count (12..18 on the headline batch): after its first instance (= its own index, so
     // that workspace slot g holds the history of instance g when the batch fits the grid) a workgroup pulls the next
     // unsolved instance from a queue instead of striding through the batch.
@@ -3400,6 +3444,7 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, ""); // (system scope: the rows this workgroup reads next were written by the host)
                 }
                 if (upd.on == UPD_ROLL) rollout_param<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, id); // (launch.hpp: RolloutDev)
+                else if (upd.on == UPD_PARAM && upd.mmap) matrix_param_instance<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.pmap, upd.mmap, upd.theta);
                 else if (upd.on == UPD_PARAM) param_instance<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.pmap, upd.theta);
                 else if (upd.on == UPD_RHS) rhs_instance<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.c, upd.h, upd.b);
                 else update_instance<T, false>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, (size_t)id, upd.G, upd.A, upd.c, upd.h, upd.b);
@@ -3648,6 +3693,51 @@ __global__ __launch_bounds__(T) void k_update_param_range(int ps, double *inst, 
     }
 }
 
+// One affine group over a range of theta rows, UNSCALED, into a contiguous [count][rows] array (launch.hpp: launch_expand_affine): with a
+// matrix map installed (eicos_batch_set_matrix_map) the parametric update expands [Gpr | Apr | c | h | b] of a chunk of instances into a
+// device staging buffer this way, one launch per group, and the unchanged updateData kernels then read that buffer like any caller's
+// arrays.  ROW-parallel with the shape of k_update_param_range: the x dimension takes consecutive rows (unit-stride 8-byte stores),
+// blockIdx.y strides over groups of PARAM_Q instances, a thread reads its row's base and (col, val) run once per group -- most rows of a
+// matrix map are empty: two row pointers, the base and PARAM_Q stores --, the theta rows of the group are staged in LDS when LDS and read
+// through the cache otherwise.  Same rounding as every other map: acc = acc + (val * theta[col]) in stored order, no FMA.
+template <int T, bool LDS>
+__global__ __launch_bounds__(T) void k_expand_affine(AffineDev A, int rows, int k, const double *theta, int count, double *dst) {
+    for (int e0 = blockIdx.x * T; e0 < rows; e0 += gridDim.x * T) { // (uniform over the workgroup: the barriers below are met by all)
+        const int r = e0 + threadIdx.x;
+        const bool act = r < rows;
+        double base = 0.;
+        int t0 = 0, t1 = 0;
+        if (act) { base = A.base[r]; t0 = A.rowptr[r]; t1 = A.rowptr[r + 1]; }
+        for (int q0 = blockIdx.y * PARAM_Q; q0 < count; q0 += gridDim.y * PARAM_Q) {
+            const int nq = count - q0 < PARAM_Q ? count - q0 : PARAM_Q;
+            const double *th = theta + (size_t)q0 * k; // rows q0 .. q0 + nq - 1
+            if constexpr (LDS) {
+                __syncthreads(); // (the previous group's rows have been read)
+                for (int j = threadIdx.x; j < nq * k; j += T) g_dyn[j] = th[j];
+                __syncthreads();
+            }
+            if (!act) continue;
+            double acc[PARAM_Q];
+#pragma unroll
+            for (int j = 0; j < PARAM_Q; j++) acc[j] = base;
+            for (int t = t0; t < t1; t++) {
+                const int col = A.col[t];
+                const double v = A.val[t];
+#pragma unroll
+                for (int j = 0; j < PARAM_Q; j++)
+                    if (j < nq) {
+                        double x;
+                        if constexpr (LDS) x = g_dyn[j * k + col]; else x = th[(size_t)j * k + col];
+                        acc[j] = __dadd_rn(acc[j], __dmul_rn(v, x));
+                    }
+            }
+#pragma unroll
+            for (int j = 0; j < PARAM_Q; j++)
+                if (j < nq) dst[(size_t)(q0 + j) * rows + r] = acc[j];
+        }
+    }
+}
+
 // The output map over a range of instances (eicos_batch_outputs*; outputs_instance is the fused form): ROW-parallel over the count * r
 // rows, the map by value and served from L2, x read from the instance slabs.  Same arithmetic as outputs_instance.
 template <int T>
@@ -3779,7 +3869,7 @@ template <class F> static auto dispatch_solve(int threads, int nlds, int idx16, 
 #endif
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds,
                         int idx16, int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd_in) {
-    UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (upd.on && nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector; both modes live in the NLDS >= 1 kernels)
     if (B <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(queue, 0, sizeof(int), st); // group queue of this launch
@@ -3829,6 +3919,16 @@ hipError_t launch_update_param(int ps, double *inst, int first, int count, const
     const size_t lds = (size_t)PARAM_Q * map.k * sizeof(double);
     if (lds <= 32 * 1024) hipLaunchKernelGGL((k_update_param_range<T, true>), dim3((unsigned)gx, (unsigned)gy), dim3(T), lds, st, ps, inst, first, count, map, theta);
     else hipLaunchKernelGGL((k_update_param_range<T, false>), dim3((unsigned)gx, (unsigned)gy), dim3(T), 0, st, ps, inst, first, count, map, theta);
+    return hipGetLastError();
+}
+// grid as launch_update_param's: x = up to 16 workgroups over the rows, y = groups of PARAM_Q instances, about 2048 workgroups in all
+hipError_t launch_expand_affine(const AffineDev &map, int rows, int k, const double *theta, int count, double *dst, hipStream_t st) {
+    if (count <= 0 || rows <= 0) return hipSuccess;
+    constexpr int T = 256;
+    const int nx = (rows + T - 1) / T, gx = nx < 16 ? nx : 16, ny = (count + PARAM_Q - 1) / PARAM_Q, gy = ny < 2048 / gx ? ny : 2048 / gx;
+    const size_t lds = (size_t)PARAM_Q * k * sizeof(double);
+    if (lds <= 32 * 1024) hipLaunchKernelGGL((k_expand_affine<T, true>), dim3((unsigned)gx, (unsigned)gy), dim3(T), lds, st, map, rows, k, theta, count, dst);
+    else hipLaunchKernelGGL((k_expand_affine<T, false>), dim3((unsigned)gx, (unsigned)gy), dim3(T), 0, st, map, rows, k, theta, count, dst);
     return hipGetLastError();
 }
 hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st) {

@@ -30,10 +30,15 @@ struct PlantMapDev { int k, r; AffineDev a; };
 // One rollout, in device memory: theta [batch][steps + 1][k] (row 0 given, the others written by the plant map), u [batch][steps][r],
 // w [batch][steps][k] (NULL: no disturbance), codes / iters [batch][steps]
 struct RolloutDev { int steps; PlantMapDev plant; double *theta, *u; const double *w; int *codes, *iters; };
+// Matrix map (eicos_batch_set_matrix_map): the stored values of G and A affine in theta -- g[0] with nnzG rows, g[1] with nnzA rows, in the
+// CSC order of Gpr / Apr, CSR with k columns, in device memory, shared by every instance; base == NULL: that matrix is not mapped; k = the
+// parameter count it was validated for
+struct MatrixMapDev { int k; AffineDev g[2]; };
 struct UpdArgs {
     const double *G, *A, *c, *h, *b; double *x; int on; const unsigned *flags; int chunk; unsigned seq; int *err;
     const ParamMapDev *pmap; const OutMapDev *omap; const double *theta; double *u; // (device copies of the handle's maps)
     const RolloutDev *roll;
+    const MatrixMapDev *mmap; // UPD_PARAM / UPD_ROLL with a matrix map: the step is a full updateData from theta (kernels.hip: matrix_param_instance)
 };
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
                         int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
@@ -48,6 +53,10 @@ hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const d
 // instances [first, first + count) from rows of theta [count][k]: entry = (base[r] + sum val * theta[col], every product and sum
 // rounded on its own, in stored order) divided by the instance's stored scaling -- the bits launch_update_rhs leaves for the same vectors
 hipError_t launch_update_param(int ps, double *inst, int first, int count, const ParamMapDev &map, const double *theta, int width, hipStream_t st);
+// One affine group over rows of theta [count][k] into dst [count][rows], unscaled: dst[q][r] = base[r] + sum val * theta[q][col], in stored
+// order, every product and sum rounded on its own.  With a matrix map installed the parametric update expands [Gpr | Apr | c | h | b] this
+// way into a device staging buffer and hands it to launch_update.
+hipError_t launch_expand_affine(const AffineDev &map, int rows, int k, const double *theta, int count, double *dst, hipStream_t st);
 // rows [first, first + count) of u [count][map.r] = the output map applied to the current x of those instances: acc = base[row], then
 // acc = acc + (val * x[col]) in stored order, every product and sum rounded on its own
 hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st);

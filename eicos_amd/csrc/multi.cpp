@@ -314,6 +314,12 @@ int eicos_multi_set_plant_map(eicos_multi *mh, const eicos_affine_map *f) {
     return for_shards(mh, [&](int s) { return eicos_batch_set_plant_map(mh->shard[s], f); });
 }
 
+int eicos_multi_set_matrix_map(eicos_multi *mh, const eicos_affine_map *G, const eicos_affine_map *A) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    return for_shards(mh, [&](int s) { return eicos_batch_set_matrix_map(mh->shard[s], G, A); });
+}
+int eicos_multi_has_matrix_map(eicos_multi *mh) { return mh ? eicos_batch_has_matrix_map(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
+
 int eicos_multi_has_plant_map(eicos_multi *mh) { return mh ? eicos_batch_has_plant_map(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
 
 int eicos_multi_rollout(eicos_multi *mh, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,

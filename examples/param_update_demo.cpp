@@ -11,6 +11,10 @@
 // Last, a rollout: setPlantMap installs theta+ = f0 + F [theta | u] and rollout() runs 20 closed-loop steps of every instance in one call;
 // its u and theta trajectories must equal, bit for bit, those of 20 stepParam calls on pinned theta with the plant evaluated on the host,
 // and the wall time of both is printed (median of 5).
+// Then the matrix map: setMatrixMap installs Gpr = G0 + Gm theta, Apr = A0 + Am theta (about a fifth of the stored values move), and the
+// same closed-loop step runs two ways -- solve(Gpr, Apr, c, h, b, x) on pinned arrays evaluated on the host (the evaluation timed on its
+// own) and stepParam under the matrix map, where only theta travels and the solve kernel forms the arrays itself; x must be equal bit for
+// bit, and the median step time of 20 steps and the bytes per instance each way are printed.
 //   g++ -std=c++17 -Iinclude examples/param_update_demo.cpp -Leicos_amd -leicos_amd -Wl,-rpath,$PWD/eicos_amd -o param_update_demo
 //   ./param_update_demo tests/golden/MPC02.epb 64 0,0 [k = 16] [steps = 20]
 #include <dlfcn.h>
@@ -61,6 +65,22 @@ static Group make_group(const double *base, int rows, int k, unsigned seed) {
     g.rowptr.assign(1, 0);
     for (int r = 0; r < rows; r++) {
         const int len = std::min(k, (int)(rnd() * 5));
+        const int c0 = (int)(rnd() * k);
+        for (int j = 0; j < len; j++) { g.col.push_back((c0 + j) % k); g.val.push_back(1e-3 * (1 + std::fabs(base[r])) * (2 * rnd() - 1)); }
+        g.rowptr.push_back((int)g.col.size());
+    }
+    return g;
+}
+
+// a matrix of the matrix map: about 80 % of the stored values fixed (empty rows), the others with 1 - 3 entries of about 1e-3 of the base
+static Group make_matrix_group(const double *base, int rows, int k, unsigned seed) {
+    Group g;
+    unsigned long long st = seed * 2654435761ull + 99991;
+    auto rnd = [&] { st = st * 6364136223846793005ull + 1442695040888963407ull; return (double)((st >> 11) & 0xFFFFFFFFFFFFull) / (double)(1ull << 48); };
+    g.base.assign(base, base + rows);
+    g.rowptr.assign(1, 0);
+    for (int r = 0; r < rows; r++) {
+        const int len = rnd() < 0.8 ? 0 : std::min(k, 1 + (int)(rnd() * 3));
         const int c0 = (int)(rnd() * k);
         for (int j = 0; j < len; j++) { g.col.push_back((c0 + j) % k); g.val.push_back(1e-3 * (1 + std::fabs(base[r])) * (2 * rnd() - 1)); }
         g.rowptr.push_back((int)g.col.size());
@@ -250,6 +270,40 @@ int main(int argc, char **argv) {
         if (rep >= 1) { tr.push_back(ms(t0, t1)); tl.push_back(ms(t1, t2)); }
     }
     delete se; delete sf;
+    // (5) the matrix map: the same step from pinned host-evaluated full arrays and from theta alone
+    const Group gG = make_matrix_group(Gpr, nnzG, k, 4), gA = make_matrix_group(Apr, nnzA, k, 5);
+    const eicos_affine_map mG = gG.view(), mA = gA.view();
+    EiCOS::BatchSolver *sg = make(), *sm = make();
+    for (EiCOS::BatchSolver *v : {sg, sm}) v->setWarmStart(0.1);
+    sm->setParamMap(k, &mc, m ? &mh : nullptr, p ? &mb : nullptr); sm->setOutputMap(R, &mo);
+    EiCOS::MatrixMap mm;
+    mm.G = nnzG ? &mG : nullptr; mm.A = nnzA ? &mA : nullptr;
+    sm->setMatrixMap(mm);
+    double *pG = EiCOS::BatchSolver::hostAlloc((size_t)B * nnzG), *pA = EiCOS::BatchSolver::hostAlloc((size_t)B * nnzA), *pC = EiCOS::BatchSolver::hostAlloc((size_t)B * n),
+           *pH = EiCOS::BatchSolver::hostAlloc((size_t)B * m), *pB = EiCOS::BatchSolver::hostAlloc((size_t)B * p), *px = EiCOS::BatchSolver::hostAlloc((size_t)B * n);
+    std::vector<double> Gt, At, te, tg, tm, xg((size_t)B * n);
+    bool same_mat = true;
+    for (int st = 0; st < steps + 2; st++) { // (the first two steps warm the paths up and are not timed)
+        const std::vector<double> th = theta_of(st + 2);
+        auto t0 = now();
+        gG.evaluate(th, k, B, Gt); gA.evaluate(th, k, B, At); vectors_of(th, C, H, Bv);
+        std::copy(Gt.begin(), Gt.end(), pG); std::copy(At.begin(), At.end(), pA); std::copy(C.begin(), C.end(), pC);
+        std::copy(H.begin(), H.end(), pH); std::copy(Bv.begin(), Bv.end(), pB);
+        auto t1 = now();
+        const std::vector<EiCOS::exitcode> cg = sg->solve(nnzG ? pG : nullptr, nnzA ? pA : nullptr, pC, nnzG ? pH : nullptr, nnzA ? pB : nullptr, px);
+        auto t2 = now();
+        xg.assign(px, px + (size_t)B * n);
+        std::copy(th.begin(), th.end(), pth);
+        auto t3 = now();
+        const std::vector<EiCOS::exitcode> cm = sm->stepParam(pth, pu);
+        auto t4 = now();
+        go.evaluate(xg, n, B, uwant);
+        ud.assign(pu, pu + (size_t)B * R);
+        same_mat = same_mat && cg == cm && same(xg, sm->solution()) && same(ud, uwant);
+        if (st >= 2) { te.push_back(ms(t0, t1)); tg.push_back(ms(t1, t2)); tm.push_back(ms(t3, t4)); }
+    }
+    delete sg; delete sm;
+    for (double *d : {pG, pA, pC, pH, pB, px}) EiCOS::BatchSolver::hostFree(d);
     const bool device_leg = sc != nullptr;
     delete sa; delete sb; delete sc; delete sd;
     EiCOS::BatchSolver::hostFree(pth); EiCOS::BatchSolver::hostFree(pu);
@@ -267,5 +321,10 @@ int main(int argc, char **argv) {
     std::printf("closed loop of %d steps, batch %d, k = %d, r = %d, median of %d:\n", T, B, k, R, REPS);
     std::printf("  rollout (one call)                   %8.3f ms\n", median(tr));
     std::printf("  %d x stepParam, plant on the host    %8.3f ms\n", T, median(tl));
-    return (same_all && same_sub && same_loop && same_u && same_roll) ? 0 : 1; // (bit-identity is the contract: it holds for every exit code)
+    std::printf("matrix map stepParam vs solve(Gpr, Apr, c, h, b) of the host-evaluated arrays: %s\n", same_mat ? "bit-identical" : "DIFFERENT");
+    std::printf("closed loop step with moving matrices, batch %d, k = %d, r = %d, median of %d steps; bytes per instance in / out:\n", B, k, R, steps);
+    std::printf("  solve(full pinned arrays, x)         %8.3f ms  %7d B in  %6d B out  (+ %8.3f ms to evaluate the arrays on the host)\n", median(tg),
+                8 * (nnzG + nnzA + n + m + p), 8 * n, median(te));
+    std::printf("  stepParam under the matrix map       %8.3f ms  %7d B in  %6d B out\n", median(tm), 8 * k, 8 * R);
+    return (same_all && same_sub && same_loop && same_u && same_roll && same_mat) ? 0 : 1; // (bit-identity is the contract: it holds for every exit code)
 }

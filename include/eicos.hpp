@@ -103,6 +103,15 @@ namespace EiCOS
         }
     }
 
+    // Extension: the matrix map of BatchSolver::setMatrixMap -- the stored values of G and / or A affine in the parameter row theta, one
+    // eicos_affine_map row per stored value in the CSC order of Gpr / Apr (nullptr: that matrix is not mapped).  The arrays are the
+    // caller's and are copied at installation.
+    struct MatrixMap
+    {
+        const eicos_affine_map *G = nullptr;
+        const eicos_affine_map *A = nullptr;
+    };
+
     // Batched engine: one pattern, `batch` instances.  Arrays are [batch][...] row-major in global instance order.
     // One GPU (device, -1 = current) or several: with a list of device ids the batch is cut into contiguous shards, one per
     // list entry, solved concurrently (eicos_multi_* of eicos_amd.h; a device may be listed more than once).
@@ -197,6 +206,11 @@ namespace EiCOS
             for (size_t i = 0; i < codes.size(); i++) out[i] = static_cast<exitcode>(codes[i]);
             return out;
         }
+        // Extension: the stored values of G and A affine in theta (MatrixMap: per matrix an eicos_affine_map with one row per stored
+        // value, CSC order, k columns), installed behind the parameter map; both nullptr removes it.  updateParam, stepParam and rollout
+        // then run a full updateData whose inputs the GPU forms from theta -- bit for bit update() of the host-evaluated arrays
+        // (contract and rounding order: eicos_batch_set_matrix_map of eicos_amd.h).
+        void setMatrixMap(const MatrixMap &m) { mcheck(eicos_multi_set_matrix_map(h_, m.G, m.A), "eicos_multi_set_matrix_map"); }
         // Extension (not in the reference): re-solves start from the previous solution, see eicos_amd.h
         void setWarmStart(double shift) { mcheck(eicos_multi_set_warm_start(h_, shift), "eicos_multi_set_warm_start"); }
         // Extension: ECOS-style dynamic regularisation (the reference's Settings::delta / ::eps are never read)

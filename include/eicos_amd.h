@@ -251,6 +251,42 @@ int eicos_batch_rollout(eicos_batch *hd, int steps, const double *theta0 /* [bat
                         int *exitcodes /* [batch][steps], optional */, int *iters /* [batch][steps], optional */);
 int eicos_batch_last_rollout_launches(eicos_batch *hd); /* solve-kernel launches of the most recent rollout: 1 = fused */
 
+/* ---- matrix map: G and A affine in theta (no reference counterpart).  When a model is linearised around the measured state, a gain is
+ * scheduled or a cone constraint depends on the state, the VALUES of G and A move with theta as well: Gpr = G0 + Gm theta,
+ * Apr = A0 + Am theta.  A handle holds one such map beside the parameter map: per matrix an eicos_affine_map with rows = nnzG (resp. nnzA),
+ * one row per stored value in the CSC order of Gpr / Apr -- base[rows] and a CSR matrix rows x k (rowptr[rows + 1], col / val[rowptr[rows]];
+ * columns lie in [0, k), k = the installed parameter map's theta length).  Most rows of a realistic map are empty: that value is base[e].
+ * eicos_batch_set_matrix_map COPIES the host arrays into one device allocation of its own; a NULL matrix is not mapped; a later call
+ * replaces the map, both NULL removes it.  It needs a parameter map (k > 0) and remembers the k it was validated for.
+ * eicos_batch_has_matrix_map: bit 0 = G mapped, bit 1 = A mapped, 0 = none.
+ * Entry e of instance i:
+ *     acc = base[e];  for t in rowptr[e] .. rowptr[e+1]-1, in stored order:  acc = acc + (val[t] * theta[i][col[t]])
+ * with the product and the sum EACH rounded to fp64 (no fused multiply-add).
+ * There are no new update entry points: with a matrix map installed, every call that consumes theta -- eicos_batch_update_param,
+ * _update_param_device, _update_param_solve, eicos_batch_rollout and their eicos_multi_* forms -- becomes a FULL updateData
+ * (re-equilibration included) whose inputs the GPU forms from theta.  The state such a call leaves for an instance (instance slabs, the
+ * KKT values of eicos_debug_kkt, every later solve / solution / duals / info) equals, bit for bit, this host sequence on arrays
+ * evaluated on the host in the order above (and c, h, b in the order of eicos_batch_update_param):
+ *     1. eicos_batch_update(first, count, G(theta) or NULL, A(theta) or NULL, c(theta) or NULL, h(theta), b(theta)) with h(theta) passed
+ *        only if G is mapped and b(theta) only if A is mapped; an unmapped group is NULL: kept and re-equilibrated, as updateData does;
+ *     2. then eicos_batch_update_rhs(NULL, h(theta) if h is mapped and G is not, b(theta) if b is mapped and A is not), when not empty.
+ * Without a matrix map nothing changes for any call.
+ * Range path (eicos_batch_update_param / _device, peer theta, and the step / rollout when they are not fused): a row-parallel kernel expands
+ * [Gpr | Apr | c | h | b] of a chunk of instances into a device staging buffer of the handle (grown on demand and capped: a large batch
+ * goes in several chunks, stream-ordered) and the unchanged updateData kernel runs on it; then the right-hand-side kernel for step 2.
+ * Fused path (eicos_batch_update_param_solve: path 5; eicos_batch_rollout: one launch): each workgroup of the solve kernel evaluates its
+ * instance's entries from the theta row and runs updateData's equilibration right before it solves.  Taken when the conditions of the
+ * fused eicos_batch_update_solve hold (an LDS vector; n, p <= 8 and m <= 16 entries per thread of the workgroup) AND those of
+ * eicos_batch_update_param_solve / _rollout (GPU-addressable theta, k resp. k + r <= the LDS vector, EICOS_FUSED_UPDATE not 0); otherwise
+ * the calls run per step through the range path.  Bit-identical on every path.
+ * EICOS_E_INVALID, with a message naming the fault, for rowptr[0] != 0, decreasing row pointers, a column outside [0, k), a map for a
+ * matrix the pattern stores no entries of, "no parameter map", and a G map while the parameter map has no h group and m > 0 / an A map
+ * while it has no b group and p > 0 (updateData reads h only with Gpr and b only with Apr).  The last two are checked again by every call
+ * that consumes theta, because the parameter map can be replaced afterwards; such a call also refuses a matrix map installed for another k
+ * than the one now installed (the message names both). */
+int eicos_batch_set_matrix_map(eicos_batch *hd, const eicos_affine_map *G, const eicos_affine_map *A);
+int eicos_batch_has_matrix_map(eicos_batch *hd);
+
 /* ---- solve: replaces exitcode Solver::solve(bool) (reference include/eicos.hpp:158,
  * src/eicos.cpp:848-1262) for every instance of the batch.  exitcodes (host, [batch]) may be
  * NULL.  Synchronous: returns after the GPU work has completed. */
@@ -375,6 +411,10 @@ int eicos_multi_set_plant_map(eicos_multi *mh, const eicos_affine_map *f);
 int eicos_multi_has_plant_map(eicos_multi *mh);
 int eicos_multi_rollout(eicos_multi *mh, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
                         int *exitcodes, int *iters);
+/* matrix map (eicos_batch_set_matrix_map / _has_matrix_map on every shard): installed on every shard; the theta-consuming calls above pick
+ * it up shard by shard */
+int eicos_multi_set_matrix_map(eicos_multi *mh, const eicos_affine_map *G, const eicos_affine_map *A);
+int eicos_multi_has_matrix_map(eicos_multi *mh);
 /* solve: async = enqueue every shard's kernels on its stream and return; sync waits for all; eicos_multi_solve = both (+ exit codes, may be NULL) */
 int eicos_multi_solve_async(eicos_multi *mh);
 int eicos_multi_sync(eicos_multi *mh);
