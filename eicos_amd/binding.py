@@ -141,6 +141,15 @@ def _lib():
             L.eicos_batch_has_matrix_map.argtypes = L.eicos_multi_has_matrix_map.argtypes = [vp]
             for f in ("set_matrix_map", "has_matrix_map"):
                 getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+        if hasattr(L, "eicos_batch_set_shift_map"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            mp = C.POINTER(AffineMap)
+            L.eicos_batch_set_shift_map.argtypes = L.eicos_multi_set_shift_map.argtypes = [vp, mp, mp, mp, mp]
+            L.eicos_batch_has_shift_map.argtypes = L.eicos_multi_has_shift_map.argtypes = [vp]
+            L.eicos_batch_set_iterate.argtypes = L.eicos_multi_set_iterate.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp]
+            L.eicos_batch_set_iterate_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
+            for f in ("set_shift_map", "has_shift_map", "set_iterate"):
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+            L.eicos_batch_set_iterate_device.restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -470,6 +479,82 @@ def _matrix_map_ptrs(mmap, nnzG, nnzA):
     return keep, ptrs
 
 
+class ShiftMap:
+    """The warm start of a re-solve moved by an affine map: per vector x, y, z, s `(base, rowptr, col, val)` -- base[rows] and a SQUARE CSR
+    matrix with rows = n, p, m, m -- or None: that vector is not shifted.  Installed with set_shift_map, a solve that warm-starts an
+    instance first replaces its vectors by the shifted ones (the receding-horizon shift: stage t + 1 becomes stage t).  evaluate() is the
+    host restatement of what the solve kernel computes, in the same rounding order."""
+
+    def __init__(self, n: int, p: int, m: int, x=None, y=None, z=None, s=None):
+        self.n, self.p, self.m = int(n), int(p), int(m)
+        self.x, self.y, self.z, self.s = (None if g is None else (np.ascontiguousarray(g[0], np.float64), np.ascontiguousarray(g[1], np.int32),
+                                                                  np.ascontiguousarray(g[2], np.int32), np.ascontiguousarray(g[3], np.float64))
+                                          for g in (x, y, z, s))
+
+    @classmethod
+    def from_sources(cls, n: int, p: int, m: int, x_src=None, y_src=None, z_src=None, s_src=None):
+        """The pure permutation / duplication shift: row j of a group copies entry src[j] of the same vector (base 0, one stored value
+        1.0 per row); None leaves the group unshifted."""
+        def group(src, rows, name):
+            if src is None:
+                return None
+            src = np.ascontiguousarray(src, dtype=np.int32)
+            if src.shape != (rows,):
+                raise ValueError(f"{name}_src has shape {src.shape}, expected [{rows}]")
+            return np.zeros(rows), np.arange(rows + 1, dtype=np.int32), src, np.ones(rows)
+        return cls(n, p, m, group(x_src, n, "x"), group(y_src, p, "y"), group(z_src, m, "z"), group(s_src, m, "s"))
+
+    def groups(self):
+        return self.x, self.y, self.z, self.s
+
+    def rows(self):
+        return self.n, self.p, self.m, self.m
+
+    def evaluate(self, x=None, y=None, z=None, s=None):
+        """(x', y', z', s') for vectors [B, rows]: a group without a map (or not given) comes back as it was passed.  Row j:
+        acc = base[j], then for every stored entry t of the row, in stored order, acc = acc + (val[t] * v[col[t]]) with v the group's
+        vector BEFORE the shift -- the product and the sum each rounded to float64 (numpy has no fused multiply-add), which is the order
+        of eicos_batch_set_shift_map."""
+        out = []
+        for name, g, rows, v in zip("xyzs", self.groups(), self.rows(), (x, y, z, s)):
+            if g is None or v is None:
+                out.append(v)
+                continue
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if v.ndim != 2 or v.shape[1] != rows:
+                raise ValueError(f"{name} has shape {v.shape}, expected [count, {rows}]")
+            base, rowptr, col, val = g
+            acc = np.repeat(base[None, :], v.shape[0], axis=0)
+            length = np.diff(rowptr)
+            for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
+                r = np.nonzero(length > j)[0]
+                t = rowptr[r] + j
+                acc[:, r] = acc[:, r] + val[t][None, :] * v[:, col[t]]
+            out.append(acc)
+        return tuple(out)
+
+
+def _shift_map_ptrs(smap, pat):
+    """A ShiftMap as (keep-alive structs, [x, y, z, s] as C pointers to eicos_affine_map or None); array sizes are checked here, their
+    contents (row pointers, column range, group present in the pattern) by the library."""
+    if (smap.n, smap.p, smap.m) != (pat.n, pat.p, pat.m):
+        raise ValueError(f"shift map: built for (n, p, m) = ({smap.n}, {smap.p}, {smap.m}), the pattern has ({pat.n}, {pat.p}, {pat.m})")
+    keep, ptrs = [], []
+    for name, g, rows in zip("xyzs", smap.groups(), smap.rows()):
+        if g is None:
+            ptrs.append(None)
+            continue
+        base, rowptr, col, val = g
+        if base.size != rows or rowptr.size != rows + 1 or col.size != val.size or (rowptr.size and rowptr[-1] > col.size):
+            raise ValueError(f"shift map of {name}: base[{base.size}], rowptr[{rowptr.size}], col[{col.size}], val[{val.size}] "
+                             f"do not describe {rows} rows")
+        one = np.zeros(1)
+        m = AffineMap(_dp(base if base.size else one), _ip(rowptr), _ip(col if col.size else np.zeros(1, np.int32)), _dp(val if val.size else one))
+        keep.append((m, one))
+        ptrs.append(C.pointer(m))
+    return keep, ptrs
+
+
 def _disturbance(w, count, steps, k):
     """w as a contiguous float64 [count, steps, k] array (None passes); ValueError otherwise."""
     if w is None:
@@ -642,6 +727,33 @@ class _Solver:
         """Bit 0: G is mapped, bit 1: A is mapped; 0: no matrix map."""
         return int(getattr(_lib(), self._prefix + "has_matrix_map")(self._h))
 
+    # ---- starting point and shift map (include/eicos_amd.h: eicos_batch_set_iterate / eicos_batch_set_shift_map) ----
+    def set_iterate(self, x=None, y=None, z=None, s=None, first: int = 0, count: int | None = None):
+        """A caller-supplied starting point for instances [first, first + count): host arrays x [count, n], y [count, p], z, s [count, m]
+        in the units of solution() / duals(); None keeps a group.  The instances are marked warm-startable: with set_warm_start(> 0) the
+        next solve starts from the point, with warm start 0 it runs cold and overwrites it."""
+        pat = self.pat
+        count = _rows((x, y, z, s), self.batch - first) if count is None else count
+        for name, a, w in zip("xyzs", (x, y, z, s), (pat.n, pat.p, pat.m, pat.m)):
+            if a is not None and np.shape(a) != (count, w):
+                raise ValueError(f"{name} has shape {np.shape(a)}, expected [{count}, {w}]")
+        _keep, ptr = _group_ptrs((x, y, z, s), (pat.n, pat.p, pat.m, pat.m), count)
+        self._call("set_iterate", first, count, *ptr)
+
+    def set_shift_map(self, smap: "ShiftMap | None"):
+        """Install (copy) a ShiftMap for all instances; None, or a map without groups, removes the installed one.  Every solve that
+        warm-starts an instance then first takes its x, y, z, s through the map: bit for bit set_iterate(*smap.evaluate(solution(),
+        *duals())) on the warm-startable instances before the same solve (contract: eicos_batch_set_shift_map)."""
+        if smap is None:
+            self._call("set_shift_map", None, None, None, None)
+            return
+        _keep, ptrs = _shift_map_ptrs(smap, self.pat)
+        self._call("set_shift_map", *ptrs)
+
+    def has_shift_map(self) -> int:
+        """Bit 0: x, 1: y, 2: z, 3: s is mapped; 0: no shift map."""
+        return int(getattr(_lib(), self._prefix + "has_shift_map")(self._h))
+
     def rollout(self, theta0, steps: int, w=None):
         """`steps` closed-loop steps of the whole batch in one call: from theta0 [batch, k], every step is update_param_solve on the
         current theta row and then the plant map, theta+ = PlantMap.evaluate(theta, u, w[:, t]) -- with an LDS vector on the handle one
@@ -750,6 +862,12 @@ class BatchSolver(_Solver):
         """update_param from a raw device pointer (int) to theta [count, k].  Asynchronous, like update_rhs_device."""
         count = self.batch if count is None else count
         self._call("update_param_device", first, count, C.c_void_p(int(dtheta) or None))
+
+    def set_iterate_device(self, dx=0, dy=0, dz=0, ds=0, first: int = 0, count: int | None = None):
+        """set_iterate from raw device pointers (ints) to x [count, n], y [count, p], z, s [count, m]; 0 keeps the group.  Asynchronous on
+        the handle's stream."""
+        count = self.batch - first if count is None else count
+        self._call("set_iterate_device", first, count, *[C.c_void_p(int(p) or None) for p in (dx, dy, dz, ds)])
 
     def outputs_device(self, du, first: int = 0, count: int | None = None):
         """outputs() into a raw device pointer (int) to u [count, r].  Asynchronous on the handle's stream."""

@@ -133,6 +133,9 @@ struct eicos_batch {
     // while none is installed; d_mstage = the device staging buffer the range path expands [Gpr | Apr | c | h | b] of a chunk of instances
     // into (param_range), grown on demand up to MSTAGE_CAP_MB
     MatrixMapDev mat{}; void *d_mat = nullptr; double *d_mstage = nullptr; size_t mstage_doubles = 0;
+    // shift map (eicos_batch_set_shift_map): one device allocation [ShiftMapDev (MAP_HEADER bytes) | base, val | rowptr, col]; every solve
+    // launch of the handle carries its address (UpdArgs::smap), d_shift = NULL while none is installed
+    ShiftMapDev shift{}; void *d_shift = nullptr;
     TilePlan tiles;        // tile mode (Symbolic::tile): the dense-front plan
 };
 
@@ -1041,7 +1044,7 @@ int eicos_batch_destroy(eicos_batch *h) {
     for (int i = 0; i < eicos_batch::EV_RING; i++)
         for (hipEvent_t e : {h->ring_s[i][0], h->ring_s[i][1], h->ring_u[i][0], h->ring_u[i][1]}) if (e) (void)hipEventDestroy(e);
     for (void *ptr : {(void *)h->d_pattern, (void *)h->d_inst, (void *)h->d_work, (void *)h->d_queue, (void *)h->d_scratch,
-                      (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out, h->d_plant, h->d_roll, h->d_mat, (void *)h->d_mstage})
+                      (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out, h->d_plant, h->d_roll, h->d_mat, (void *)h->d_mstage, h->d_shift})
         if (ptr) (void)hipFree(ptr);
     for (int i = 0; i < 2; i++) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     if (h->stage_pin) (void)hipHostFree(h->stage_pin);
@@ -1274,6 +1277,7 @@ struct UpdateInputs {
     size_t w[5];          // doubles per instance
     MemKind kind[5];      // of the arrays that hold data, when the entry point asked for kinds
     size_t per;           // doubles per instance over the given groups
+    bool iterate = false; // a starting point (take_iterate): the groups are x, y, z, s in the slots of G, A, c, h
     bool holds_data(int k) const { return src[k] && w[k]; }
     bool any(MemKind m) const { for (int k = 0; k < 5; k++) if (holds_data(k) && kind[k] == m) return true; return false; }
     bool all(MemKind m) const { for (int k = 0; k < 5; k++) if (holds_data(k) && kind[k] != m) return false; return true; }
@@ -1390,7 +1394,8 @@ static int param_range(eicos_batch *h, int first, int count, const double *theta
 
 static int launch_range(const UpdateInputs &in, int first, int count, const double *const p[5]) {
     eicos_batch *h = in.h;
-    if (in.param) {
+    if (in.iterate) HIP_TRY(launch_set_iterate(h->pslot, h->d_inst, first, count, p[0], p[1], p[2], p[3], (int)in.per, h->stream));
+    else if (in.param) {
         const int rc = param_range(h, first, count, p[2]);
         if (rc != EICOS_OK) return rc;
     } else if (in.rhs) HIP_TRY(launch_update_rhs(h->pslot, h->d_inst, first, count, p[2], p[3], p[4], (int)in.per, h->stream));
@@ -1469,7 +1474,8 @@ static int peer_update(const UpdateInputs &in, int src_dev) {
 static int host_update(const UpdateInputs &in) {
     eicos_batch *h = in.h;
     // a device pointer handed to the HOST-pointer entry point must not reach the bounce copy (a host memcpy from it would fault)
-    if (in.any(MEM_DEVICE)) return fail(EICOS_E_INVALID, in.param ? "eicos_batch_update_param takes a host pointer: theta lives in device memory (use eicos_batch_update_param_device)"
+    if (in.any(MEM_DEVICE)) return fail(EICOS_E_INVALID, in.iterate ? "eicos_batch_set_iterate takes host pointers: an array lives in device memory (use eicos_batch_set_iterate_device)"
+                                                         : in.param ? "eicos_batch_update_param takes a host pointer: theta lives in device memory (use eicos_batch_update_param_device)"
                                                          : in.rhs ? "eicos_batch_update_rhs takes host pointers: an array lives in device memory (use eicos_batch_update_rhs_device)"
                                                                  : "eicos_batch_update takes host pointers: an array lives in device memory (use eicos_batch_update_device)");
     // pinned in place only when EVERY byte the kernel will read is mapped (else the bounce path, which reads with the host's own loads)
@@ -1544,6 +1550,43 @@ int eicos_batch_update(eicos_batch *h, int first, int count, const double *G, co
 
 int eicos_batch_update_rhs(eicos_batch *h, int first, int count, const double *c, const double *hh, const double *b) {
     return eicos_internal_update_staged(h, first, count, nullptr, nullptr, c, hh, b, -1, 1);
+}
+
+// ---- a caller-supplied starting point (no reference counterpart) ----
+// One more kind of UpdateInputs: up to four groups, x [n], y [p], z [m], s [m] per instance, in the slots of G, A, c, h -- so that the rows
+// travel over the very paths of the updates (bounce, pinned in place, device) into k_set_iterate_range, which stores them in the slabs as
+// they are and marks the instances warm-startable.
+static int take_iterate(UpdateInputs &in, eicos_batch *h, int first, int count, const double *x, const double *y, const double *z,
+                        const double *s, bool kinds) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (first < 0 || count < 0 || first + count > h->batch) return fail(EICOS_E_INVALID, "instance range out of bounds");
+    if (!x && !y && !z && !s) return fail(EICOS_E_INVALID, "set_iterate: x, y, z and s are all NULL");
+    const DevPat &D = h->dp;
+    if (y && D.p == 0) return fail(EICOS_E_INVALID, "set_iterate: y given, but the pattern has no equality rows (p = 0)");
+    if (z && D.m == 0) return fail(EICOS_E_INVALID, "set_iterate: z given, but the pattern has no cone rows (m = 0)");
+    if (s && D.m == 0) return fail(EICOS_E_INVALID, "set_iterate: s given, but the pattern has no cone rows (m = 0)");
+    HIP_TRY(hipSetDevice(h->device));
+    in = UpdateInputs{h, first, count, false, false, {x, y, z, s, nullptr}, {(size_t)D.n, (size_t)D.p, (size_t)D.m, (size_t)D.m, 0}, {}, 0};
+    in.iterate = true;
+    for (int k = 0; k < 4; k++) {
+        if (in.src[k]) in.per += in.w[k];
+        if (kinds && in.holds_data(k)) in.kind[k] = memory_kind(in.src[k], (size_t)count * in.w[k] * sizeof(double));
+    }
+    return EICOS_OK;
+}
+
+// host arrays: pageable through the bounce buffers, pinned / registered read in place; synchronous like eicos_batch_update_rhs
+int eicos_batch_set_iterate(eicos_batch *h, int first, int count, const double *x, const double *y, const double *z, const double *s) {
+    UpdateInputs in;
+    const int rc = take_iterate(in, h, first, count, x, y, z, s, true);
+    return rc != EICOS_OK ? rc : staged_update(in, -1);
+}
+
+// device arrays: one launch on the handle's stream, asynchronous
+int eicos_batch_set_iterate_device(eicos_batch *h, int first, int count, const double *dx, const double *dy, const double *dz, const double *ds) {
+    UpdateInputs in;
+    const int rc = take_iterate(in, h, first, count, dx, dy, dz, ds, false);
+    return rc != EICOS_OK ? rc : update_in_place(in, 0);
 }
 
 // ---- parametric right-hand sides: c, h, b affine in a short parameter row theta (no reference counterpart) ----
@@ -1719,9 +1762,13 @@ int eicos_batch_solve_async(eicos_batch *h) {
     { const int rc = next_events(h->ring_s, h->n_solve_rec, h->ev_s0, h->ev_s1); if (rc != EICOS_OK) return rc; }
     h->ring_step0[(h->n_solve_rec - 1) % eicos_batch::EV_RING] = h->update_timed ? h->ev_u0 : h->ev_s0;
     HIP_TRY(hipEventRecord(h->ev_s0, h->stream));
+    // (a shift map travels with EVERY launch, the ones without a fused update included: instance_begin reads it)
+    UpdArgs args = h->fused_pending ? h->fused : UpdArgs{};
+    if (!h->fused_pending) args.chunk = 1;
+    args.smap = static_cast<const ShiftMapDev *>(h->d_shift);
     HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(h->pslot, h->d_inst, h->d_work, h->batch, h->d_queue, h->d_queue + 16, h->grid, h->threads, h->nlds,
                                                              h->dp.idx16, h->order_min, h->warm_shift, h->dyn_delta, h->dyn_eps, h->dyn_lds, h->stream,
-                                                             h->fused_pending ? &h->fused : nullptr));
+                                                             (h->fused_pending || args.smap) ? &args : nullptr));
     HIP_TRY(hipEventRecord(h->ev_s1, h->stream));
     h->solve_timed = true;
     h->last_ordered = h->batch > h->order_min;
@@ -2055,6 +2102,69 @@ int eicos_batch_set_matrix_map(eicos_batch *h, const eicos_affine_map *G, const 
 
 int eicos_batch_has_matrix_map(eicos_batch *h) {
     return h ? ((h->mat.g[0].base ? 1 : 0) | (h->mat.g[1].base ? 2 : 0)) : fail(EICOS_E_INVALID, "NULL handle");
+}
+
+// ---- shift map: the warm-start vectors x, y, z, s through a square affine map each (no reference counterpart) ----
+// Validated like the other maps and packed into ONE device allocation of its own: [ShiftMapDev (MAP_HEADER bytes) | base, val | rowptr,
+// col] -- every solve launch of the handle carries the address of the descriptor (eicos_batch_solve_async).
+static_assert(sizeof(ShiftMapDev) <= MAP_HEADER, "map descriptor larger than its header");
+int eicos_batch_set_shift_map(eicos_batch *h, const eicos_affine_map *x, const eicos_affine_map *y, const eicos_affine_map *z, const eicos_affine_map *sl) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    const DevPat &D = h->dp;
+    const eicos_affine_map *g[4] = {x, y, z, sl};
+    const int rows[4] = {D.n, D.p, D.m, D.m};
+    const char *name[4] = {"x", "y", "z", "s"};
+    const bool remove = !x && !y && !z && !sl;
+    size_t nd = 0, ni = 0;
+    for (int q = 0; q < 4; q++) {
+        if (!g[q]) continue;
+        const std::string who = std::string("shift map of ") + name[q] + ": ";
+        if (rows[q] == 0) return fail(EICOS_E_INVALID, who + "the pattern has no such vector (it has no rows)");
+        if (!g[q]->base || !g[q]->rowptr) return fail(EICOS_E_INVALID, who + "base or rowptr is NULL");
+        const int *rp = g[q]->rowptr;
+        if (rp[0] != 0) return fail(EICOS_E_INVALID, who + "rowptr[0] must be 0");
+        for (int r = 0; r < rows[q]; r++)
+            if (rp[r + 1] < rp[r]) return fail(EICOS_E_INVALID, who + "rowptr decreases at row " + std::to_string(r));
+        const int nnz = rp[rows[q]];
+        if (nnz > 0 && (!g[q]->col || !g[q]->val)) return fail(EICOS_E_INVALID, who + "col or val is NULL");
+        for (int t = 0; t < nnz; t++)
+            if (g[q]->col[t] < 0 || g[q]->col[t] >= rows[q]) return fail(EICOS_E_INVALID, who + "column " + std::to_string(g[q]->col[t]) + " of entry " + std::to_string(t) + " is outside [0, rows)");
+        nd += (size_t)rows[q] + nnz; ni += (size_t)rows[q] + 1 + nnz;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
+    if (h->d_shift) { (void)hipFree(h->d_shift); h->d_shift = nullptr; }
+    h->shift = ShiftMapDev{};
+    if (remove) return EICOS_OK;
+    ShiftMapDev M{};
+    std::vector<char> buf(MAP_HEADER + nd * sizeof(double) + ni * sizeof(int));
+    double *hd_ = reinterpret_cast<double *>(buf.data() + MAP_HEADER);
+    int *hi_ = reinterpret_cast<int *>(buf.data() + MAP_HEADER + nd * sizeof(double));
+    void *dev = nullptr;
+    HIP_TRY(hipMalloc(&dev, buf.size()));
+    const double *dd = reinterpret_cast<const double *>(static_cast<const char *>(dev) + MAP_HEADER);
+    const int *di = reinterpret_cast<const int *>(static_cast<const char *>(dev) + MAP_HEADER + nd * sizeof(double));
+    size_t od = 0, oi = 0;
+    for (int q = 0; q < 4; q++) {
+        if (!g[q]) continue;
+        const int nnz = g[q]->rowptr[rows[q]];
+        M.g[q].base = dd + od; std::copy(g[q]->base, g[q]->base + rows[q], hd_ + od); od += rows[q];
+        M.g[q].val = dd + od; if (nnz) std::copy(g[q]->val, g[q]->val + nnz, hd_ + od); od += nnz;
+        M.g[q].rowptr = di + oi; std::copy(g[q]->rowptr, g[q]->rowptr + rows[q] + 1, hi_ + oi); oi += rows[q] + 1;
+        M.g[q].col = di + oi; if (nnz) std::copy(g[q]->col, g[q]->col + nnz, hi_ + oi); oi += nnz;
+    }
+    std::memcpy(buf.data(), &M, sizeof M);
+    const hipError_t e = hipMemcpy(dev, buf.data(), buf.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the shift map: ") + hipGetErrorString(e)); }
+    h->d_shift = dev; h->shift = M;
+    return EICOS_OK;
+}
+
+int eicos_batch_has_shift_map(eicos_batch *h) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    int bits = 0;
+    for (int q = 0; q < 4; q++) if (h->shift.g[q].base) bits |= 1 << q;
+    return bits;
 }
 
 int eicos_batch_has_plant_map(eicos_batch *h) { return h ? (h->plant.k > 0 ? 1 : 0) : fail(EICOS_E_INVALID, "NULL handle"); }

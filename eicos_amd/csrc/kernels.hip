@@ -160,6 +160,7 @@ struct alignas(16) Sh : ShI {
     int step;
     const RolloutDev *roll; const ParamMapDev *pmap; const OutMapDev *omap; int *queue;
     const MatrixMapDev *mmap; // (UpdArgs::mmap: a rollout's steps run matrix_param_instance when it is set)
+    const ShiftMapDev *smap;  // (UpdArgs::smap, every build and every launch: instance_begin shifts a warm start through it when it is set)
 };
 constexpr int KI_MAX = 2; // right-hand sides of a dual solve (kkt_solve<..., 2, true>)
 enum { TK_FACTOR = 0, TK_LDL, TK_KRES, TK_KPOST, TK_RESID, TK_FWD, TK_COUNT, TK_FA = 8, TK_FW1, TK_FB, TK_FW2 }; // 8..11: inside the factor
@@ -2929,8 +2930,38 @@ __device__ __forceinline__ int kkt_post_any(int ps, gdbl_p I, gdbl_p W, int stag
     return kkt_post<T, false>(ps, I, W, stage);
 }
 
+// The shift map of one instance by one workgroup (instance_begin, a warm start only): every mapped vector v of x, y, z, s, as the previous
+// solve left it in the slab (backscaled), becomes new[j] = base[j], then new[j] = new[j] + (val[t] * old[col[t]]) over row j in stored
+// order, the product and the sum each rounded on its own.  Rows read other entries of their own vector, so the old values are staged
+// first: in the LDS KKT-space vector where the kernel has one (idle between two instances, as plant_instance relies on), otherwise in
+// the workspace's sweep vector (w_ek, which kkt_solve writes in full before it reads it); either holds max(n, p, m), so the groups go
+// one after another.  Out of line: a launch without a map pays the pointer test of the call site and nothing else.
+template <class ZP> __device__ __forceinline__ double shift_row(const AffineDev &A, int row, ZP z) {
+    double acc = A.base[row];
+    const int t1 = A.rowptr[row + 1];
+    for (int t = A.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], z[A.col[t]]));
+    return acc;
+}
+template <int T, bool LDSV>
+static __device__ __noinline__ __attribute__((not_tail_called)) void shift_instance(int ps, gdbl_p I, gdbl_p W, const ShiftMapDev *Sp) {
+    ps = uni(ps); I = uni_ptr(I); W = uni_ptr(W); Sp = uni_ptr(Sp);
+    const DevPat &P = c_pat[ps];
+    auto z = [&] { if constexpr (LDSV) return (double *)g_dyn; else return W + P.w_ek; }();
+    for (int q = 0; q < 4; q++) {
+        const AffineDev A = Sp->g[q];
+        if (!A.base) continue;
+        const int rows = q == 0 ? P.n : (q == 1 ? P.p : P.m);
+        gdbl_p v = I + (q == 0 ? P.i_x : (q == 1 ? P.i_y : (q == 2 ? P.i_z : P.i_s)));
+        FOR_T(j, rows) z[j] = v[j]; // (instance_begin's barrier is behind us: nothing reads the staging vector)
+        __syncthreads();
+        FOR_T(j, rows) v[j] = shift_row(A, j, z);
+        __syncthreads(); // (the next group overwrites the staging vector; the warm start reads entries other threads wrote)
+    }
+}
+
 // ---------------- per-instance prologue of a solve (its state ends up in g_S); returns 1 if it was warm-started ----------------
-template <int T>
+// LDSV: the kernel has an LDS KKT-space vector (NLDS >= 1), which a shift map stages in
+template <int T, bool LDSV>
 static __device__ __noinline__ __attribute__((not_tail_called)) int instance_begin(int ps, gdbl_p I, gdbl_p W, double warm) {
     ps = uni(ps); I = uni_ptr(I); W = uni_ptr(W);
     const DevPat &P = c_pat[ps];
@@ -2991,6 +3022,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int instance_beg
     }
     __syncthreads();
     if (!g_S.fl[FL_WARM]) return 0;
+    if (g_S.smap) shift_instance<T, LDSV>(ps, I, W, g_S.smap); // (eicos_batch_set_shift_map: the vectors move before they are re-equilibrated)
     {
         // ---- warm start: previous (x, y, z, s) of this instance (still in its slab, backscaled) re-equilibrated and
         // pushed into the cone -- LP rows floored at warm * mean|.|, cone heads at ||tail|| + the same margin --
@@ -3048,7 +3080,7 @@ template <int T, int NLDS, bool I16>
 __device__ __forceinline__ void solve_instance(int ps, gdbl_p I, gdbl_p W, double warm) {
     const DevPat &P = c_pat[ps];
     int stage = ST_FACTOR, iter = -1; // iter = -1 while initialising
-    if (instance_begin<T>(ps, I, W, warm)) { stage = ST_RESID; iter = 0; } // warm start: no initialisation solves
+    if (instance_begin<T, (NLDS >= 1)>(ps, I, W, warm)) { stage = ST_RESID; iter = 0; } // warm start: no initialisation solves
     __syncthreads();
     while (stage != ST_DONE) {
         if (stage == ST_FACTOR) {
@@ -3419,7 +3451,7 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     for (int q = threadIdx.x; q < P.ub_len; q += T) g_dyn[P.ub_lds + q] = 0.;
     __syncthreads();
 #endif
-    if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.step = 0; g_S.next = (int)blockIdx.x; } // (next: the instance that is running)
+    if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.step = 0; g_S.next = (int)blockIdx.x; g_S.smap = upd.smap; } // (next: the instance that is running)
     if constexpr (NLDS >= 1) { if (threadIdx.x == 0) { g_S.roll = upd.roll; g_S.pmap = upd.pmap; g_S.omap = upd.omap; g_S.queue = queue; g_S.mmap = upd.mmap; } }
     // Instances differ in iteration count (12..18 on the headline batch): after its first instance (= its own index, so
     // that workspace slot g holds the history of instance g when the batch fits the grid) a workgroup pulls the next
@@ -3755,6 +3787,31 @@ __global__ __launch_bounds__(T) void k_outputs_range(int ps, const double *inst,
     }
 }
 
+// A caller-supplied starting point for a range of instances (launch.hpp: launch_set_iterate): ENTRY-parallel like k_update_rhs_range --
+// blockIdx.y strides over the instances, the x dimension over the given entries [x | y | z | s] of one instance (unit stride in the inputs
+// and in the slab, plain 8-byte stores, no scaling: the slab holds these vectors backscaled between two solves).  One thread per instance
+// then marks the record by the rule instance_begin reads: warm-startable means n_factor > 0 and an exit code of 0 or 10.
+template <int T>
+__global__ __launch_bounds__(T) void k_set_iterate_range(int ps, double *inst, int first, int count, const double *x, const double *y,
+                                                         const double *z, const double *s) {
+    const DevPat &P = c_pat[ps];
+    const int wx = x ? P.n : 0, wy = y ? P.p : 0, wz = z ? P.m : 0, w = wx + wy + wz + (s ? P.m : 0);
+    for (int q = blockIdx.y; q < count; q += gridDim.y) {
+        hbm_p I = (hbm_p)inst + (size_t)(first + q) * P.inst_stride;
+        for (int e = blockIdx.x * T + threadIdx.x; e < w; e += gridDim.x * T) {
+            if (e < wx) I[P.i_x + e] = x[(size_t)q * P.n + e];
+            else if (e < wx + wy) I[P.i_y + (e - wx)] = y[(size_t)q * P.p + (e - wx)];
+            else if (e < wx + wy + wz) I[P.i_z + (e - wx - wy)] = z[(size_t)q * P.m + (e - wx - wy)];
+            else I[P.i_s + (e - wx - wy - wz)] = s[(size_t)q * P.m + (e - wx - wy - wz)];
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            DevInfo EICOS_GLOBAL *di = reinterpret_cast<DevInfo EICOS_GLOBAL *>(I + P.i_info);
+            if (di->exitcode != 0 && di->exitcode != 10) di->exitcode = 0;
+            if (di->n_factor == 0) di->n_factor = 1;
+        }
+    }
+}
+
 // One step of a rollout that is not fused (launch.hpp: launch_plant; plant_instance is the fused form): ROW-parallel over the count * k
 // rows of theta+, the map served from L2, z read from the step's contiguous theta and u rows.  Same arithmetic as plant_instance.  The
 // threads of the first r / the first row of an instance also move its u row, exit code and iteration count into the trajectories.
@@ -3869,7 +3926,7 @@ template <class F> static auto dispatch_solve(int threads, int nlds, int idx16, 
 #endif
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds,
                         int idx16, int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd_in) {
-    UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (upd.on && nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector; both modes live in the NLDS >= 1 kernels)
     if (B <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(queue, 0, sizeof(int), st); // group queue of this launch
@@ -3929,6 +3986,15 @@ hipError_t launch_expand_affine(const AffineDev &map, int rows, int k, const dou
     const size_t lds = (size_t)PARAM_Q * k * sizeof(double);
     if (lds <= 32 * 1024) hipLaunchKernelGGL((k_expand_affine<T, true>), dim3((unsigned)gx, (unsigned)gy), dim3(T), lds, st, map, rows, k, theta, count, dst);
     else hipLaunchKernelGGL((k_expand_affine<T, false>), dim3((unsigned)gx, (unsigned)gy), dim3(T), 0, st, map, rows, k, theta, count, dst);
+    return hipGetLastError();
+}
+hipError_t launch_set_iterate(int ps, double *inst, int first, int count, const double *x, const double *y, const double *z, const double *s,
+                              int width, hipStream_t st) {
+    if (count <= 0 || width <= 0) return hipSuccess;
+    constexpr int T = 256;
+    const int gx = (width + T - 1) / T, gy = count;
+    const dim3 grid((unsigned)(gx < 64 ? gx : 64), (unsigned)(gy < 16384 ? gy : 16384));
+    hipLaunchKernelGGL(k_set_iterate_range<T>, grid, dim3(T), 0, st, ps, inst, first, count, x, y, z, s);
     return hipGetLastError();
 }
 hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st) {

@@ -34,11 +34,17 @@ struct RolloutDev { int steps; PlantMapDev plant; double *theta, *u; const doubl
 // CSC order of Gpr / Apr, CSR with k columns, in device memory, shared by every instance; base == NULL: that matrix is not mapped; k = the
 // parameter count it was validated for
 struct MatrixMapDev { int k; AffineDev g[2]; };
+// Shift map (eicos_batch_set_shift_map): the warm-start vectors x, y, z, s of an instance through one square affine map each -- g[0..3] with
+// n, p, m, m rows and as many columns, CSR, in device memory, shared by every instance; base == NULL: that vector is not shifted
+struct ShiftMapDev { AffineDev g[4]; };
 struct UpdArgs {
     const double *G, *A, *c, *h, *b; double *x; int on; const unsigned *flags; int chunk; unsigned seq; int *err;
     const ParamMapDev *pmap; const OutMapDev *omap; const double *theta; double *u; // (device copies of the handle's maps)
     const RolloutDev *roll;
     const MatrixMapDev *mmap; // UPD_PARAM / UPD_ROLL with a matrix map: the step is a full updateData from theta (kernels.hip: matrix_param_instance)
+    // Every mode, 0 included: a solve that warm-starts an instance first takes its x, y, z, s through this map (kernels.hip: shift_instance);
+    // NULL: no shift map.  One more word of kernel arguments, and one pointer test per instance.
+    const ShiftMapDev *smap;
 };
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
                         int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
@@ -57,6 +63,11 @@ hipError_t launch_update_param(int ps, double *inst, int first, int count, const
 // order, every product and sum rounded on its own.  With a matrix map installed the parametric update expands [Gpr | Apr | c | h | b] this
 // way into a device staging buffer and hands it to launch_update.
 hipError_t launch_expand_affine(const AffineDev &map, int rows, int k, const double *theta, int count, double *dst, hipStream_t st);
+// A caller-supplied starting point (eicos_batch_set_iterate*): rows of x [count][n], y [count][p], z [count][m], s [count][m] (NULL = keep)
+// into the slabs of instances [first, first + count) as they are, and every instance marked warm-startable (exit code OPTIMAL unless it is
+// OPTIMAL or close to it already, n_factor 1 if it was 0); `width` = the summed widths of the given groups (sizes the grid)
+hipError_t launch_set_iterate(int ps, double *inst, int first, int count, const double *x, const double *y, const double *z, const double *s,
+                              int width, hipStream_t st);
 // rows [first, first + count) of u [count][map.r] = the output map applied to the current x of those instances: acc = base[row], then
 // acc = acc + (val * x[col]) in stored order, every product and sum rounded on its own
 hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st);

@@ -320,6 +320,19 @@ int eicos_multi_set_matrix_map(eicos_multi *mh, const eicos_affine_map *G, const
 }
 int eicos_multi_has_matrix_map(eicos_multi *mh) { return mh ? eicos_batch_has_matrix_map(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
 
+int eicos_multi_set_shift_map(eicos_multi *mh, const eicos_affine_map *x, const eicos_affine_map *y, const eicos_affine_map *z, const eicos_affine_map *s) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    return for_shards(mh, [&](int sh) { return eicos_batch_set_shift_map(mh->shard[sh], x, y, z, s); });
+}
+int eicos_multi_has_shift_map(eicos_multi *mh) { return mh ? eicos_batch_has_shift_map(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
+
+// rows in global instance order: every shard takes its own
+int eicos_multi_set_iterate(eicos_multi *mh, int first, int count, const double *x, const double *y, const double *z, const double *s) {
+    return for_range(mh, first, count, [&](int sh, int f, int cnt, size_t off) {
+        return eicos_batch_set_iterate(mh->shard[sh], f, cnt, at(x, off, mh->n), at(y, off, mh->p), at(z, off, mh->m), at(s, off, mh->m));
+    });
+}
+
 int eicos_multi_has_plant_map(eicos_multi *mh) { return mh ? eicos_batch_has_plant_map(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
 
 int eicos_multi_rollout(eicos_multi *mh, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,

@@ -112,6 +112,16 @@ namespace EiCOS
         const eicos_affine_map *A = nullptr;
     };
 
+    // Extension: the shift map of BatchSolver::setShiftMap -- the warm-start vectors x, y, z, s through a square eicos_affine_map each
+    // (rows = n, p, m, m; nullptr: that vector is not shifted).  The arrays are the caller's and are copied at installation.
+    struct ShiftMap
+    {
+        const eicos_affine_map *x = nullptr;
+        const eicos_affine_map *y = nullptr;
+        const eicos_affine_map *z = nullptr;
+        const eicos_affine_map *s = nullptr;
+    };
+
     // Batched engine: one pattern, `batch` instances.  Arrays are [batch][...] row-major in global instance order.
     // One GPU (device, -1 = current) or several: with a list of device ids the batch is cut into contiguous shards, one per
     // list entry, solved concurrently (eicos_multi_* of eicos_amd.h; a device may be listed more than once).
@@ -211,6 +221,18 @@ namespace EiCOS
         // then run a full updateData whose inputs the GPU forms from theta -- bit for bit update() of the host-evaluated arrays
         // (contract and rounding order: eicos_batch_set_matrix_map of eicos_amd.h).
         void setMatrixMap(const MatrixMap &m) { mcheck(eicos_multi_set_matrix_map(h_, m.G, m.A), "eicos_multi_set_matrix_map"); }
+        // Extension: the warm start moved by an affine map inside the solve kernel (ShiftMap; the receding-horizon shift: stage t + 1
+        // becomes stage t).  Every solve that warm-starts an instance -- solve, stepParam, every step of rollout -- first replaces its
+        // x, y, z, s by the shifted ones: bit for bit setIterate of the host-evaluated vectors before the same solve (contract and
+        // rounding order: eicos_batch_set_shift_map of eicos_amd.h).  All four nullptr removes it.
+        void setShiftMap(const ShiftMap &m) { mcheck(eicos_multi_set_shift_map(h_, m.x, m.y, m.z, m.s), "eicos_multi_set_shift_map"); }
+        // Extension: a caller-supplied starting point for instances [first, first + count): rows of x [count][n], y [count][p],
+        // z, s [count][m] in the units of solution() (nullptr keeps a group).  With setWarmStart(> 0) the next solve starts from it;
+        // with warm start 0 it is ignored (eicos_batch_set_iterate of eicos_amd.h).
+        void setIterate(const double *x, const double *y, const double *z, const double *s, int first = 0, int count = -1)
+        {
+            mcheck(eicos_multi_set_iterate(h_, first, count < 0 ? batch_ : count, x, y, z, s), "eicos_multi_set_iterate");
+        }
         // Extension (not in the reference): re-solves start from the previous solution, see eicos_amd.h
         void setWarmStart(double shift) { mcheck(eicos_multi_set_warm_start(h_, shift), "eicos_multi_set_warm_start"); }
         // Extension: ECOS-style dynamic regularisation (the reference's Settings::delta / ::eps are never read)

@@ -311,6 +311,55 @@ int eicos_batch_solution_device(eicos_batch *hd, const double **dx, size_t *stri
  * 0.1 is a good value for MPC re-solves (1 % data perturbation: 13-15 -> 8-10 iterations). */
 int eicos_batch_set_warm_start(eicos_batch *hd, double shift);
 
+/* ---- a caller-supplied starting point (no reference counterpart).  The warm start above can only reuse what the previous solve of the
+ * same instance left in its slab; eicos_batch_set_iterate writes a starting point there instead -- from another handle, a coarser model, a
+ * neighbouring instance, a run saved to disk.  Rows of x [count][n], y [count][p], z [count][m], s [count][m], row-major, for instances
+ * [first, first + count), in the units of eicos_batch_solution / eicos_batch_duals (backscaled); NULL keeps a group as it is, all four NULL
+ * is EICOS_E_INVALID.  The rows are stored in the instances' slabs as they are, and every instance of the range is marked warm-startable
+ * by the rule the solve kernel reads: its info record gets exitcode = EICOS_OPTIMAL unless it is EICOS_OPTIMAL or EICOS_OPTIMAL +
+ * EICOS_INACC_OFFSET already, and n_factor = 1 if it was 0; nothing else of the record changes.  eicos_batch_solution, _duals and _info
+ * return exactly that afterwards.
+ * With warm start shift > 0 the next solve of such an instance starts from the supplied point through the unchanged warm path
+ * (re-equilibrated, s and z pushed into the cone: they need not lie in it).  With shift == 0 the point is ignored: the next solve runs
+ * cold and overwrites it.  Values are not checked for finiteness, as elsewhere.
+ * Host form: the paths of eicos_batch_update_rhs -- pageable arrays through the pinned bounce buffers, pinned / registered arrays read in
+ * place -- synchronous in the same way, eicos_batch_last_update_path reports the path.  Device form: one launch on the handle's stream,
+ * asynchronous.  Both run one row-parallel kernel with plain stores.
+ * EICOS_E_INVALID, with a message naming the fault: NULL handle, a range outside the batch, y with p = 0, z or s with m = 0. */
+int eicos_batch_set_iterate(eicos_batch *hd, int first, int count, const double *x /* [count][n] */, const double *y /* [count][p] */,
+                            const double *z /* [count][m] */, const double *s /* [count][m] */);
+int eicos_batch_set_iterate_device(eicos_batch *hd, int first, int count, const double *dx, const double *dy, const double *dz, const double *ds);
+
+/* ---- shift map: the warm start moved by an affine map, inside the solve kernel (no reference counterpart).  The standard warm start of
+ * a receding-horizon controller is the previous solution moved one stage forward: stage t + 1 becomes stage t, the last stage is
+ * repeated.  A handle holds one such map: per vector x, y, z, s an eicos_affine_map with rows = n, p, m, m -- base[rows] and a SQUARE CSR
+ * matrix rows x rows (rowptr[rows + 1], col / val[rowptr[rows]]; columns lie in [0, rows)).  A NULL group is not shifted.
+ * eicos_batch_set_shift_map COPIES the host arrays into one device allocation of its own; a later call replaces the map, all four NULL
+ * removes it.  eicos_batch_has_shift_map: bit 0 = x, 1 = y, 2 = z, 3 = s mapped; 0 = none.
+ * When a solve of the handle WARM-STARTS an instance (warm start shift > 0, and the instance's last exit code is EICOS_OPTIMAL or
+ * EICOS_OPTIMAL + EICOS_INACC_OFFSET), the workgroup first replaces that instance's vectors -- for every mapped group v and row j
+ *     new[j] = base[j];  for t in rowptr[j] .. rowptr[j+1]-1, in stored order:  new[j] = new[j] + (val[t] * old[col[t]])
+ * with the product and the sum EACH rounded to fp64 (no fused multiply-add), old = the group's vector before the shift (the backscaled
+ * values eicos_batch_solution / _duals return) -- and the warm start's re-equilibration and cone push follow: a shifted s or z that leaves
+ * the cone is pushed back by construction.  A solve that does not warm-start an instance (shift == 0, or a previous exit that is neither
+ * OPTIMAL nor close to it) leaves its vectors alone and runs cold, as without a map.
+ * There is no new update call: the shift is part of the per-instance prologue of the solve kernel, so eicos_batch_solve, _solve_async,
+ * _update_solve, _update_rhs_solve, _update_param_solve and every step of eicos_batch_rollout (fused or per step) pick it up, on every
+ * build of the solve kernel and on handles without an LDS vector.  Without a shift map a launch pays one pointer test per instance and
+ * every result stays bit-identical.
+ * Contract: on a handle with a shift map and warm start shift > 0, any solve leaves the same state -- instance slabs, solution, duals,
+ * info, the KKT values of eicos_debug_kkt -- bit for bit, as a twin WITHOUT the map on which the host runs, before the same solve:
+ *     1. eicos_batch_solution / _duals / _info, for every instance whose last solve ended with exit code 0 or 10;
+ *     2. the map evaluated on those vectors in the order above;
+ *     3. eicos_batch_set_iterate with the result.
+ * For eicos_batch_rollout the twin is the host loop of eicos_batch_update_param_solve calls with the plant evaluated on the host, and
+ * steps 1-3 before each of them.
+ * EICOS_E_INVALID, with a message naming the fault, for rowptr[0] != 0, decreasing row pointers, a column outside [0, rows) and a map for
+ * a vector the pattern does not have (y with p = 0, z or s with m = 0). */
+int eicos_batch_set_shift_map(eicos_batch *hd, const eicos_affine_map *x, const eicos_affine_map *y, const eicos_affine_map *z,
+                              const eicos_affine_map *s);
+int eicos_batch_has_shift_map(eicos_batch *hd); /* bit 0 x, 1 y, 2 z, 3 s; 0 = none */
+
 /* ---- dynamic regularisation (N4 of SURVEY.md 8f; NOT in the reference, whose Settings::delta / ::eps are dead,
  * include/eicos.hpp:26,28).  delta > 0: during the numeric LDL' a pivot whose sign disagrees with the quasi-definite
  * sign pattern of the KKT matrix, or whose magnitude is below eps, is replaced by sign * delta (ECOS: delta = 2e-7,
@@ -415,6 +464,12 @@ int eicos_multi_rollout(eicos_multi *mh, int steps, const double *theta0, const 
  * it up shard by shard */
 int eicos_multi_set_matrix_map(eicos_multi *mh, const eicos_affine_map *G, const eicos_affine_map *A);
 int eicos_multi_has_matrix_map(eicos_multi *mh);
+/* starting point and shift map (eicos_batch_set_iterate / _set_shift_map / _has_shift_map): the rows of set_iterate are in global
+ * instance order and every shard takes its own; the shift map is installed on every shard */
+int eicos_multi_set_iterate(eicos_multi *mh, int first, int count, const double *x, const double *y, const double *z, const double *s);
+int eicos_multi_set_shift_map(eicos_multi *mh, const eicos_affine_map *x, const eicos_affine_map *y, const eicos_affine_map *z,
+                              const eicos_affine_map *s);
+int eicos_multi_has_shift_map(eicos_multi *mh);
 /* solve: async = enqueue every shard's kernels on its stream and return; sync waits for all; eicos_multi_solve = both (+ exit codes, may be NULL) */
 int eicos_multi_solve_async(eicos_multi *mh);
 int eicos_multi_sync(eicos_multi *mh);
