@@ -51,6 +51,18 @@ class AffineMap(C.Structure):
     _fields_ = [("base", C.POINTER(C.c_double)), ("rowptr", C.POINTER(C.c_int)), ("col", C.POINTER(C.c_int)), ("val", C.POINTER(C.c_double))]
 
 
+class Settings(C.Structure):
+    """struct eicos_settings: the runtime solver settings of a handle (tolerances, iteration cap, refinement)."""
+    _fields_ = [(k, C.c_double) for k in ("feastol", "abstol", "reltol", "feastol_inacc", "abstol_inacc", "reltol_inacc",
+                                          "linsysacc", "irerrfact")] + [("iter_max", C.c_int), ("nitref", C.c_int)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+SETTINGS_FIELDS = tuple(k for k, _ in Settings._fields_)
+
+
 def library_path() -> str:
     # EICOS_AMD_LIB: alternative build of the same library (used by tuning sweeps only)
     return os.environ.get("EICOS_AMD_LIB") or os.path.join(_HERE, "libeicos_amd.so")
@@ -150,6 +162,17 @@ def _lib():
             for f in ("set_shift_map", "has_shift_map", "set_iterate"):
                 getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
             L.eicos_batch_set_iterate_device.restype = C.c_int
+        if hasattr(L, "eicos_batch_set_settings"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            sp = C.POINTER(Settings)
+            L.eicos_settings_default.argtypes = [sp]
+            L.eicos_settings_default.restype = None
+            L.eicos_settings_size.argtypes = []
+            L.eicos_settings_size.restype = C.c_size_t
+            if L.eicos_settings_size() != C.sizeof(Settings):
+                raise RuntimeError(f"{path}: struct eicos_settings has {L.eicos_settings_size()} bytes, the ctypes mirror {C.sizeof(Settings)}")
+            for f in ("set_settings", "get_settings"):
+                getattr(L, "eicos_batch_" + f).argtypes = getattr(L, "eicos_multi_" + f).argtypes = [vp, sp]
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -207,6 +230,13 @@ def _lib():
 def set_arithmetic_profile(profile: int) -> None:
     """0 (default): plans shaped by the launch; 1: by the pattern alone -- batch- and shard-independent bits (eicos_set_arithmetic_profile)."""
     _chk(_lib().eicos_set_arithmetic_profile(int(profile)))
+
+
+def default_settings() -> dict:
+    """The ten runtime settings at their defaults (eicos_settings_default: the reference's values); needs no GPU."""
+    st = Settings()
+    _lib().eicos_settings_default(C.byref(st))
+    return st.asdict()
 
 
 def device_count() -> int:
@@ -794,6 +824,25 @@ class _Solver:
     def set_dynamic_regularization(self, delta: float, eps: float):
         """delta > 0: ECOS-style dynamic regularisation of the LDL' pivots (not in the reference)."""
         self._call("set_dynamic_regularization", float(delta), float(eps))
+
+    def set_settings(self, **fields):
+        """Runtime solver settings of the handle (every shard of a multi-GPU one): feastol, abstol, reltol, their _inacc counterparts,
+        linsysacc, irerrfact, iter_max, nitref (ranges and semantics: eicos_settings of include/eicos_amd.h).  Fields that are not
+        named keep their current value; the change takes effect from the next solve launch.  An unknown name raises TypeError before
+        the library is called, a refused value RuntimeError with the handle's settings unchanged."""
+        unknown = sorted(set(fields) - set(SETTINGS_FIELDS))
+        if unknown:
+            raise TypeError(f"set_settings: unknown field(s) {', '.join(unknown)} (the settings are {', '.join(SETTINGS_FIELDS)})")
+        st = Settings()
+        self._call("get_settings", C.byref(st))
+        for k, v in fields.items():
+            setattr(st, k, int(v) if k in ("iter_max", "nitref") else float(v))
+        self._call("set_settings", C.byref(st))
+
+    def settings(self) -> dict:
+        st = Settings()
+        self._call("get_settings", C.byref(st))
+        return st.asdict()
 
     # ---- results ----
     def solution(self):

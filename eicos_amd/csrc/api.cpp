@@ -99,6 +99,7 @@ struct eicos_batch {
     int *d_flag = nullptr;   // debug hooks
     double warm_shift = 0.; // > 0: warm start (eicos_batch_set_warm_start)
     double dyn_delta = 0., dyn_eps = 0.; // > 0: dynamic regularisation (eicos_batch_set_dynamic_regularization)
+    SolveCfg cfg = solve_cfg_default(); // runtime settings (eicos_batch_set_settings): every solve launch carries a copy by value
     hipStream_t own_stream = nullptr, stream = nullptr;
     // HIP events around every solve launch / every updateData call, on the handle's stream.  A RING of pairs: the durations of the last
     // EV_RING launches can be read after the fact (eicos_batch_ms_history), so that a caller timing K back-to-back steps need not
@@ -1068,6 +1069,46 @@ int eicos_batch_set_dynamic_regularization(eicos_batch *h, double delta, double 
     return EICOS_OK;
 }
 
+// ---- runtime settings (include/eicos_amd.h: eicos_settings).  SolveCfg (launch.hpp) is the same ten fields in the same order.
+static_assert(sizeof(eicos_settings) == sizeof(SolveCfg), "eicos_settings and SolveCfg mirror each other");
+void eicos_settings_default(eicos_settings *out) {
+    if (!out) return;
+    const SolveCfg d = solve_cfg_default();
+    *out = eicos_settings{d.feastol, d.abstol, d.reltol, d.feastol_inacc, d.abstol_inacc, d.reltol_inacc, d.linsysacc, d.irerrfact, d.iter_max, d.nitref};
+}
+size_t eicos_settings_size(void) { return sizeof(eicos_settings); }
+
+// NULL when `s` is acceptable, else the message naming the refused field
+static const char *settings_fault(const eicos_settings &s, std::string &msg) {
+    const struct { const char *name; double v; } pos[] = {
+        {"feastol", s.feastol}, {"abstol", s.abstol}, {"reltol", s.reltol}, {"feastol_inacc", s.feastol_inacc},
+        {"abstol_inacc", s.abstol_inacc}, {"reltol_inacc", s.reltol_inacc}, {"linsysacc", s.linsysacc}, {"irerrfact", s.irerrfact}};
+    for (const auto &f : pos)
+        if (!(std::isfinite(f.v) && f.v > 0.)) { msg = std::string("settings: ") + f.name + " must be finite and positive"; return msg.c_str(); }
+    // (the per-pass trace rows -- DevPat::w_trace, eicos_debug_trace's out[102][12] -- are sized for 100 passes, and only pass 0 creates the
+    // best iterate that the iteration-cap exit may restore; nothing in the KKT solve is sized by nitref: 100 bounds the loop, no more)
+    if (s.iter_max < 1 || s.iter_max > 100) { msg = "settings: iter_max must lie in [1, 100]"; return msg.c_str(); }
+    if (s.nitref < 0 || s.nitref > 100) { msg = "settings: nitref must lie in [0, 100]"; return msg.c_str(); }
+    return nullptr;
+}
+
+int eicos_batch_set_settings(eicos_batch *h, const eicos_settings *s) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (!s) return fail(EICOS_E_INVALID, "settings: NULL struct");
+    std::string msg;
+    if (settings_fault(*s, msg)) return fail(EICOS_E_INVALID, msg);
+    h->cfg = SolveCfg{s->feastol, s->abstol, s->reltol, s->feastol_inacc, s->abstol_inacc, s->reltol_inacc, s->linsysacc, s->irerrfact, s->iter_max, s->nitref};
+    return EICOS_OK;
+}
+
+int eicos_batch_get_settings(eicos_batch *h, eicos_settings *out) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (!out) return fail(EICOS_E_INVALID, "settings: NULL struct");
+    const SolveCfg &c = h->cfg;
+    *out = eicos_settings{c.feastol, c.abstol, c.reltol, c.feastol_inacc, c.abstol_inacc, c.reltol_inacc, c.linsysacc, c.irerrfact, c.iter_max, c.nitref};
+    return EICOS_OK;
+}
+
 int eicos_batch_set_stream(eicos_batch *h, void *hip_stream) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
@@ -1767,7 +1808,7 @@ int eicos_batch_solve_async(eicos_batch *h) {
     if (!h->fused_pending) args.chunk = 1;
     args.smap = static_cast<const ShiftMapDev *>(h->d_shift);
     HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(h->pslot, h->d_inst, h->d_work, h->batch, h->d_queue, h->d_queue + 16, h->grid, h->threads, h->nlds,
-                                                             h->dp.idx16, h->order_min, h->warm_shift, h->dyn_delta, h->dyn_eps, h->dyn_lds, h->stream,
+                                                             h->dp.idx16, h->order_min, h->warm_shift, h->dyn_delta, h->dyn_eps, h->cfg, h->dyn_lds, h->stream,
                                                              (h->fused_pending || args.smap) ? &args : nullptr));
     HIP_TRY(hipEventRecord(h->ev_s1, h->stream));
     h->solve_timed = true;

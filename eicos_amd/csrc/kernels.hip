@@ -99,11 +99,11 @@ namespace t512 {
 #endif
 
 // ---- constants of struct Settings (reference include/eicos.hpp:23-47) ----
+// The three tolerances, their _inacc counterparts, linsysacc, irerrfact, iter_max and nitref are runtime settings (launch.hpp: SolveCfg;
+// g_S.cfg below); the constants here shape the arithmetic of every pass and stay compile-time.
 __device__ constexpr double GAMMA = 0.99, DELTASTAT = 7e-8;
-__device__ constexpr double FEASTOL = 1e-8, ABSTOL = 1e-8, RELTOL = 1e-8;
-__device__ constexpr double FEASTOL_INACC = 1e-4, ABSTOL_INACC = 5e-5, RELTOL_INACC = 5e-5;
-__device__ constexpr int NITREF = 9, EQUIL_ITERS = 3, ITER_MAX = 100;
-__device__ constexpr double LINSYSACC = 1e-14, IRERRFACT = 6., STEPMIN = 1e-6, STEPMAX = 0.999;
+__device__ constexpr int EQUIL_ITERS = 3;
+__device__ constexpr double STEPMIN = 1e-6, STEPMAX = 0.999;
 __device__ constexpr double SIGMAMIN = 1e-4, SIGMAMAX = 1.0, SAFEGUARD = 500.;
 constexpr int EX_NOT_CONVERGED = -87;
 
@@ -154,6 +154,7 @@ struct ShI {
 struct alignas(16) Sh : ShI {
     double red[2 * RED_SLOTS];
     double dyn_delta, dyn_eps; // dynamic regularisation of the pivots (extension; 0 = off), set by k_solve
+    SolveCfg cfg; // runtime settings of this launch (eicos_batch_set_settings), set by k_solve: the stage functions read them here
     int next; // next instance of this workgroup (k_solve's queue)
     // a rollout (k_solve with UpdArgs::roll): the step of the instance's rollout that is running, and what rollout_param / rollout_step need of
     // the kernel's arguments -- kept here, so that k_solve holds nothing more in registers across its stages than it does without a rollout
@@ -1173,9 +1174,10 @@ __device__ __forceinline__ double lp_line_search(double rmin, double smin, int l
 // ---------------- checkExitConditions (ref :526-641), thread 0 only, on g_S.wi ----------------
 __device__ __forceinline__ int dev_check_exit(bool reduced) {
     DevInfo &wi = g_S.wi;
-    const double feastol = reduced ? FEASTOL_INACC : FEASTOL;
-    const double abstol = reduced ? ABSTOL_INACC : ABSTOL;
-    const double reltol = reduced ? RELTOL_INACC : RELTOL;
+    const SolveCfg &cfg = g_S.cfg;
+    const double feastol = reduced ? cfg.feastol_inacc : cfg.feastol;
+    const double abstol = reduced ? cfg.abstol_inacc : cfg.abstol;
+    const double reltol = reduced ? cfg.reltol_inacc : cfg.reltol;
     const bool relgap_lt = !wi.has_relgap || wi.relgap < reltol;    // optional<double> < x: true if empty
     const bool pinfres_lt = !wi.has_pinfres || wi.pinfres < feastol;
     if ((-wi.cx > 0. || -wi.by - wi.hz >= -abstol) && (wi.pres < feastol && wi.dres < feastol) &&
@@ -1914,8 +1916,9 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(
         const double nrz = nrz2 / fmax(resz0 + nx + ns, 1.);
         wi.pres = fmax(nry, nrz) / wi.tau;
         wi.dres = nrx / fmax(resx0 + ny + nz, 1.) / wi.tau;
-        if ((wi.hz + wi.by) / fmax(ny + nz, 1.) < -RELTOL) { wi.pinfres = hresx / fmax(ny + nz, 1.); wi.has_pinfres = 1; }
-        if (wi.cx / fmax(nx, 1.) < -RELTOL) {
+        const double reltol = g_S.cfg.reltol;
+        if ((wi.hz + wi.by) / fmax(ny + nz, 1.) < -reltol) { wi.pinfres = hresx / fmax(ny + nz, 1.); wi.has_pinfres = 1; }
+        if (wi.cx / fmax(nx, 1.) < -reltol) {
             wi.dinfres = fmax(hresy / fmax(nx, 1.), hresz / fmax(nx + ns, 1.)); wi.has_dinfres = 1;
         }
         { // per-iteration history (the reference's verbose table, ref :733-753), kept per workspace slot
@@ -1939,7 +1942,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(
                     code = dev_check_exit(true);
                     if (code == EX_NOT_CONVERGED) code = -2;
                     action = ACT_BREAK;
-                } else if (iter == ITER_MAX) {
+                } else if (iter == g_S.cfg.iter_max) {
                     if (!dev_better_than()) { restore_scalars(); restore = 1; }
                     code = dev_check_exit(true);
                     if (code == EX_NOT_CONVERGED) code = -1;
@@ -2319,7 +2322,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
         });
         blk_reduce<OpMax, T, KI>(phase, nr);
 #pragma unroll
-        for (int k = 0; k < KI; k++) { thr[k] = (1. + nr[k]) * LINSYSACC; nerr_prev[k] = DBL_MAX; kcnt[k] = -1; rdone[k] = !((amask >> k) & 1); }
+        for (int k = 0; k < KI; k++) { thr[k] = (1. + nr[k]) * g_S.cfg.linsysacc; nerr_prev[k] = DBL_MAX; kcnt[k] = -1; rdone[k] = !((amask >> k) & 1); }
     }
     for (int pass = 0;; pass++) {
         // -------- SV <- L^-T D^-1 L^-1 SV in elimination order (replaces ldlt.solve, ref :1477,1599) --------
@@ -2564,6 +2567,8 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
         for (int k = 0; k < KI; k++) { nv[3 * k] = nex[k]; nv[3 * k + 1] = ney[k]; nv[3 * k + 2] = nez[k]; }
         blk_reduce<OpMax, T, 3 * KI>(phase, nv);
         bool undo[KI], all_done = true;
+        const int nitref = uni(g_S.cfg.nitref); // (read where they are used: nothing of the settings is held across the sweeps)
+        const double irerrfact = g_S.cfg.irerrfact;
 #pragma unroll
         for (int k = 0; k < KI; k++) {
             undo[k] = false;
@@ -2571,7 +2576,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
             double nerr = fmax(nv[3 * k], nv[3 * k + 2]);
             if (p > 0) nerr = fmax(nerr, nv[3 * k + 1]);
             if (kcnt[k] > 0 && nerr > nerr_prev[k]) { undo[k] = true; kcnt[k]--; rdone[k] = true; } // got worse: undo and quit (ref :1579-1585)
-            else if (kcnt[k] == NITREF || nerr < thr[k] || (kcnt[k] > 0 && nerr_prev[k] < IRERRFACT * nerr)) rdone[k] = true;
+            else if (kcnt[k] == nitref || nerr < thr[k] || (kcnt[k] > 0 && nerr_prev[k] < irerrfact * nerr)) rdone[k] = true;
             else { nerr_prev[k] = nerr; all_done = false; }
         }
 #pragma unroll
@@ -3425,7 +3430,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_ste
 
 template <int T, int NLDS, bool I16>
 __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
-    int ps, double *inst, double *work, int B, int *queue, const int *order, double warm, double dyn_delta, double dyn_eps, UpdArgs upd) {
+    int ps, double *inst, double *work, int B, int *queue, const int *order, double warm, double dyn_delta, double dyn_eps, SolveCfg cfg, UpdArgs upd) {
     const DevPat &P = c_pat[ps];
 #if EICOS_LDSRES
     static_assert(NLDS >= 1, "LDS-resident variant: sweep vector + tables in LDS");
@@ -3451,7 +3456,7 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     for (int q = threadIdx.x; q < P.ub_len; q += T) g_dyn[P.ub_lds + q] = 0.;
     __syncthreads();
 #endif
-    if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.step = 0; g_S.next = (int)blockIdx.x; g_S.smap = upd.smap; } // (next: the instance that is running)
+    if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.cfg = cfg; g_S.step = 0; g_S.next = (int)blockIdx.x; g_S.smap = upd.smap; } // (next: the instance that is running)
     if constexpr (NLDS >= 1) { if (threadIdx.x == 0) { g_S.roll = upd.roll; g_S.pmap = upd.pmap; g_S.omap = upd.omap; g_S.queue = queue; g_S.mmap = upd.mmap; } }
     // Instances differ in iteration count (12..18 on the headline batch): after its first instance (= its own index, so
     // that workspace slot g holds the history of instance g when the batch fits the grid) a workgroup pulls the next
@@ -3845,7 +3850,7 @@ __global__ __launch_bounds__(T) void k_plant_range(int ps, const double *inst, i
 template <int T>
 __global__ __launch_bounds__(T, waves_per_eu<T>()) void k_debug_factor(int ps, double *inst, double *work, int i) {
     const DevPat &P = c_pat[ps];
-    if (threadIdx.x == 0) { g_S.fl[FL_FATAL] = 0; g_S.wi.n_factor = 0; g_S.dyn_delta = 0.; g_S.dyn_eps = 0.; for (int k = 0; k < 12; k++) g_S.tick[k] = 0; }
+    if (threadIdx.x == 0) { g_S.fl[FL_FATAL] = 0; g_S.wi.n_factor = 0; g_S.dyn_delta = 0.; g_S.dyn_eps = 0.; g_S.cfg = solve_cfg_default(); for (int k = 0; k < 12; k++) g_S.tick[k] = 0; }
     gdbl_p I = (gdbl_p)inst + (size_t)i * P.inst_stride, Kt = (gdbl_p)work + P.w_Kt;
     if (P.tile) { // launched with the solve kernel's dynamic LDS size: the per-wave scratch sits at the same offset
         gdbl_p Kimg = (gdbl_p)work + P.w_Kimg;
@@ -3875,7 +3880,7 @@ __global__ __launch_bounds__(T, waves_per_eu<T>()) void k_debug_scalings(int ps,
         g_S.sv[SV_PRESPREV] = DBL_MAX;
         for (int k = 0; k < FL_COUNT; k++) g_S.fl[k] = 0;
         for (int k = 0; k < 12; k++) g_S.tick[k] = 0;
-        g_S.dyn_delta = 0.; g_S.dyn_eps = 0.;
+        g_S.dyn_delta = 0.; g_S.dyn_eps = 0.; g_S.cfg = solve_cfg_default();
         g_S.cur = 0; g_S.best = -1;
     }
     for (int j = threadIdx.x; j < P.n; j += T) I[P.i_x + j] = 0.;
@@ -3925,8 +3930,9 @@ template <class F> static auto dispatch_solve(int threads, int nlds, int idx16, 
 }
 #endif
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds,
-                        int idx16, int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd_in) {
+                        int idx16, int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg_in, size_t dyn_lds, hipStream_t st, const UpdArgs *upd_in) {
     UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    SolveCfg cfg = cfg_in; // (by value into the kernel arguments: a launch in flight keeps the settings it was enqueued with)
     if (upd.on && nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector; both modes live in the NLDS >= 1 kernels)
     if (B <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(queue, 0, sizeof(int), st); // group queue of this launch
@@ -3944,7 +3950,7 @@ hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, i
     }
     return dispatch_solve(threads, nlds, idx16, [&](const void *fn) {
         void *args[] = {(void *)&ps, (void *)&inst, (void *)&work, (void *)&B, (void *)&queue, (void *)&order, (void *)&warm, (void *)&dyn_delta,
-                        (void *)&dyn_eps, (void *)&upd};
+                        (void *)&dyn_eps, (void *)&cfg, (void *)&upd};
         return hipLaunchKernel(fn, dim3(grid), dim3(threads), args, dyn_lds, st);
     });
 }

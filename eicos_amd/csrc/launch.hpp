@@ -46,8 +46,14 @@ struct UpdArgs {
     // NULL: no shift map.  One more word of kernel arguments, and one pointer test per instance.
     const ShiftMapDev *smap;
 };
+// Runtime solver settings (eicos_batch_set_settings; eicos_settings of include/eicos_amd.h, same fields and defaults): one by-value argument
+// of k_solve, copied into LDS by thread 0 (kernels.hip: Sh::cfg) before the workgroup's first instance, where the stage functions read
+// it -- the exit test and the two infeasibility-residual comparisons (tolerances), the iteration cap, and kkt_solve's refinement stop test
+// (linsysacc, irerrfact, nitref).  Every other constant of the reference's Settings stays compile-time (kernels.hip).
+struct SolveCfg { double feastol, abstol, reltol, feastol_inacc, abstol_inacc, reltol_inacc, linsysacc, irerrfact; int iter_max, nitref; };
+constexpr SolveCfg solve_cfg_default() { return {1e-8, 1e-8, 1e-8, 1e-4, 5e-5, 5e-5, 1e-14, 6., 100, 9}; }
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
+                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
 hipError_t launch_update(int ps, double *inst, int first, int count, const double *Gpr, const double *Apr,
                          const double *c, const double *h, const double *b, double *scratch, int grid, size_t lds_bytes, int vals_in_lds, hipStream_t st);
 // right-hand-side-only updateData of instances [first, first + count): rows of c [count][n], h [count][m], b [count][p] (NULL = keep)
@@ -88,7 +94,7 @@ int max_patterns();
 // LDS-resident variant of k_solve (kernels_ldsres.hip = kernels.hip compiled with EICOS_LDSRES): same arguments
 namespace ldsres {
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
+                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
 hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
 hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
 hipError_t upload_pattern(int ps, const DevPat &P);
@@ -96,7 +102,7 @@ hipError_t upload_pattern(int ps, const DevPat &P);
 // 256-thread k_solve with the register budget of two waves per SIMD (kernels_w2.hip = kernels.hip compiled with EICOS_W2)
 namespace w2 {
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
+                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
 hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
 hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
 hipError_t upload_pattern(int ps, const DevPat &P);
@@ -105,14 +111,14 @@ hipError_t upload_pattern(int ps, const DevPat &P);
 // compiled with EICOS_TSPLIT): the default namespace keeps the 256-thread one
 namespace t128 {
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
+                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
 hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
 hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
 hipError_t upload_pattern(int ps, const DevPat &P);
 } // namespace t128
 namespace t512 {
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
+                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
 hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
 hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
 hipError_t upload_pattern(int ps, const DevPat &P);
@@ -121,14 +127,14 @@ hipError_t upload_pattern(int ps, const DevPat &P);
 // with EICOS_UBL): launches of one workgroup per CU whose U fits the idle LDS
 namespace ubl256 {
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
+                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
 hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
 hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
 hipError_t upload_pattern(int ps, const DevPat &P);
 } // namespace ubl256
 namespace ubl512 {
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
+                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
 hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
 hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
 hipError_t upload_pattern(int ps, const DevPat &P);

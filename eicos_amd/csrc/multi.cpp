@@ -374,6 +374,19 @@ int eicos_multi_set_dynamic_regularization(eicos_multi *mh, double delta, double
     return EICOS_OK;
 }
 
+// (validation does not depend on the shard: the first shard refuses what any would, before one of them has changed)
+int eicos_multi_set_settings(eicos_multi *mh, const eicos_settings *st) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    for (eicos_batch *h : mh->shard) { const int rc = eicos_batch_set_settings(h, st); if (rc != EICOS_OK) return mfail(rc, eicos_last_error()); }
+    return EICOS_OK;
+}
+
+int eicos_multi_get_settings(eicos_multi *mh, eicos_settings *out) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    const int rc = eicos_batch_get_settings(mh->shard[0], out);
+    return rc != EICOS_OK ? mfail(rc, eicos_last_error()) : EICOS_OK;
+}
+
 int eicos_multi_last_solve_ms(eicos_multi *mh, float *ms_max, float *per_shard) {
     if (!mh || !ms_max) return mfail(EICOS_E_INVALID, "NULL argument");
     *ms_max = 0.f;

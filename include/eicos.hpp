@@ -44,30 +44,50 @@ namespace EiCOS
         not_converged_yet = -87
     };
 
-    struct Settings // reference include/eicos.hpp:23-47; all but `verbose` are compile-time
-    {               // constants of the GPU kernels (eicos_amd/csrc/kernels.hip)
+    // reference include/eicos.hpp:23-47.  The ten members without `const` are the runtime settings of the GPU kernels (eicos_settings of
+    // eicos_amd.h: ranges and semantics there): Solver::solve() and BatchSolver::setSettings hand them to the handle.  `maxit` is the
+    // reference's second name for the iteration cap: `iter_max` is the one that is read.  The const members are compile-time constants of
+    // the kernels (eicos_amd/csrc/kernels.hip).
+    struct Settings
+    {
         const double gamma = 0.99;
         const double delta = 2e-7;
         const double deltastat = 7e-8;
         const double eps = 1e13;
-        const double feastol = 1e-8;
-        const double abstol = 1e-8;
-        const double reltol = 1e-8;
-        const double feastol_inacc = 1e-4;
-        const double abstol_inacc = 5e-5;
-        const double reltol_inacc = 5e-5;
-        const size_t nitref = 9;
+        double feastol = 1e-8;
+        double abstol = 1e-8;
+        double reltol = 1e-8;
+        double feastol_inacc = 1e-4;
+        double abstol_inacc = 5e-5;
+        double reltol_inacc = 5e-5;
+        size_t nitref = 9;
         const size_t maxit = 100;
         bool verbose = false;
-        const double linsysacc = 1e-14;
-        const double irerrfact = 6;
+        double linsysacc = 1e-14;
+        double irerrfact = 6;
         const double stepmin = 1e-6;
         const double stepmax = 0.999;
         const double sigmamin = 1e-4;
         const double sigmamax = 1.;
         const size_t equil_iters = 3;
-        const size_t iter_max = 100;
+        size_t iter_max = 100;
         const size_t safeguard = 500;
+
+        // the ten runtime members as the C ABI takes them (a count beyond the int range becomes one the library refuses)
+        eicos_settings to_c() const
+        {
+            const size_t big = 1u << 20;
+            return eicos_settings{feastol, abstol, reltol, feastol_inacc, abstol_inacc, reltol_inacc, linsysacc, irerrfact,
+                                  (int)(iter_max < big ? iter_max : big), (int)(nitref < big ? nitref : big)};
+        }
+        static Settings from(const eicos_settings &c)
+        {
+            Settings s;
+            s.feastol = c.feastol; s.abstol = c.abstol; s.reltol = c.reltol;
+            s.feastol_inacc = c.feastol_inacc; s.abstol_inacc = c.abstol_inacc; s.reltol_inacc = c.reltol_inacc;
+            s.linsysacc = c.linsysacc; s.irerrfact = c.irerrfact; s.iter_max = (size_t)c.iter_max; s.nitref = (size_t)c.nitref;
+            return s;
+        }
     };
 
     struct Information // reference include/eicos.hpp:49-73
@@ -240,6 +260,19 @@ namespace EiCOS
         {
             mcheck(eicos_multi_set_dynamic_regularization(h_, delta, eps), "eicos_multi_set_dynamic_regularization");
         }
+        // Runtime settings (the ten non-const members of Settings; eicos_settings of eicos_amd.h), on every shard: in effect from the next
+        // solve, stepParam or rollout.  A refused value throws and changes nothing.
+        void setSettings(const Settings &s)
+        {
+            const eicos_settings c = s.to_c();
+            mcheck(eicos_multi_set_settings(h_, &c), "eicos_multi_set_settings");
+        }
+        Settings settings() const
+        {
+            eicos_settings c;
+            mcheck(eicos_multi_get_settings(h_, &c), "eicos_multi_get_settings");
+            return Settings::from(c);
+        }
         std::vector<exitcode> solve()
         {
             std::vector<int> codes(batch_);
@@ -379,6 +412,14 @@ namespace EiCOS
         {
             settings_.verbose = verbose;
             int code = EICOS_FATAL;
+            { // getSettings() hands out a reference: whatever the caller wrote there since the last solve goes to the handle now
+                const eicos_settings c = settings_.to_c();
+                if (!same(c, pushed_))
+                {
+                    if (eicos_batch_set_settings(h_, &c) != EICOS_OK) return exitcode::fatal; // (a refused value: eicos_last_error() names it)
+                    pushed_ = c;
+                }
+            }
             if (eicos_batch_solve(h_, &code) != EICOS_OK) return exitcode::fatal;
             eicos_info raw;
             if (eicos_batch_info(h_, &raw) != EICOS_OK) return exitcode::fatal;
@@ -408,8 +449,15 @@ namespace EiCOS
     private:
         eicos_batch *h_ = nullptr;
         Settings settings_;
+        eicos_settings pushed_ = Settings().to_c(); // what the handle holds: it starts with the defaults
         Information info_;
         SolutionVector x_;
+        static bool same(const eicos_settings &a, const eicos_settings &b)
+        {
+            return a.feastol == b.feastol && a.abstol == b.abstol && a.reltol == b.reltol && a.feastol_inacc == b.feastol_inacc &&
+                   a.abstol_inacc == b.abstol_inacc && a.reltol_inacc == b.reltol_inacc && a.linsysacc == b.linsysacc &&
+                   a.irerrfact == b.irerrfact && a.iter_max == b.iter_max && a.nitref == b.nitref;
+        }
         void resize_solution(int n)
         {
 #ifdef EICOS_HAVE_EIGEN

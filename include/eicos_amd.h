@@ -367,6 +367,39 @@ int eicos_batch_has_shift_map(eicos_batch *hd); /* bit 0 x, 1 y, 2 z, 3 s; 0 = n
  * EICOS_FATAL as in the reference (src/eicos.cpp:1166-1170). */
 int eicos_batch_set_dynamic_regularization(eicos_batch *hd, double delta, double eps);
 
+/* ---- runtime solver settings: the fields of struct EiCOS::Settings (reference include/eicos.hpp:23-47) a caller tunes per application --
+ * the exit tolerances and their relaxed ("inaccurate") counterparts, the iteration cap, and the iterative refinement of the KKT solves.
+ * Defaults = the reference's values (right column).  Where the solve kernel reads them (reference src/eicos.cpp):
+ *   feastol, abstol, reltol (+ _inacc)  checkExitConditions (:533-546); reltol also decides whether the infeasibility residuals pinfres /
+ *                                       dinfres exist (:720, :724)
+ *   iter_max                            the pass at which the main loop gives up (:990): EICOS_MAXIT, or EICOS_OPTIMAL / _PINF / _DINF +
+ *                                       EICOS_INACC_OFFSET when the relaxed test passes there
+ *   linsysacc, irerrfact, nitref        the stop test of the iterative refinement of every KKT solve (:1479, :1495, :1588-1590):
+ *                                       nitref = 0 means no refinement step at all
+ * Ranges: the eight doubles finite and > 0; iter_max in [1, 100] (the per-pass trace rows -- eicos_debug_trace's out[102][12] -- are sized
+ * for 100 passes, and only pass 0 creates the best iterate that the iteration-cap exit may restore); nitref in [0, 100] (nothing in the
+ * KKT solve is sized by it; 100 merely bounds the loop).
+ * Scope: exactly these ten.  gamma, deltastat, stepmin / stepmax, sigmamin / sigmamax, safeguard and equil_iters stay compile-time
+ * constants of the kernel: they shape the arithmetic of every pass, and delta / eps have eicos_batch_set_dynamic_regularization.
+ * A handle starts with the defaults.  eicos_batch_set_settings stores a COPY and takes effect from the next solve launch the handle
+ * enqueues -- eicos_batch_solve, _solve_async, _update_solve, _update_rhs_solve, _update_param_solve and every step of eicos_batch_rollout,
+ * fused or per step, on every build of the solve kernel and on handles without an LDS vector.  A launch already in flight keeps the values
+ * it was enqueued with: they travel as kernel arguments by value.  Settings are per handle, not per instance.
+ * A handle on which eicos_batch_set_settings was never called, or was called with eicos_settings_default's values, gives bit-identical
+ * results on every path.
+ * EICOS_E_INVALID, with a message naming the field, and the handle's settings UNCHANGED, for a NULL handle or struct, a non-finite or
+ * non-positive tolerance / linsysacc / irerrfact, iter_max outside [1, 100] and nitref outside [0, 100]. */
+typedef struct eicos_settings {
+    double feastol, abstol, reltol;                    /* 1e-8, 1e-8, 1e-8  */
+    double feastol_inacc, abstol_inacc, reltol_inacc;  /* 1e-4, 5e-5, 5e-5  */
+    double linsysacc, irerrfact;                       /* 1e-14, 6          */
+    int iter_max, nitref;                              /* 100, 9            */
+} eicos_settings;
+void   eicos_settings_default(eicos_settings *out);   /* no handle, no GPU needed */
+size_t eicos_settings_size(void);                     /* sizeof(eicos_settings), for bindings that mirror the struct */
+int eicos_batch_set_settings(eicos_batch *hd, const eicos_settings *s);
+int eicos_batch_get_settings(eicos_batch *hd, eicos_settings *out);
+
 /* ---- plumbing */
 int eicos_batch_dims(eicos_batch *hd, eicos_dims *out);
 /* Which compilation of the solve kernel this handle launches (chosen at creation from pattern size and batch; no reference
@@ -480,6 +513,9 @@ int eicos_multi_duals(eicos_multi *mh, double *y, double *z, double *s);
 int eicos_multi_info(eicos_multi *mh, eicos_info *info /* [batch] */);
 int eicos_multi_set_warm_start(eicos_multi *mh, double shift);
 int eicos_multi_set_dynamic_regularization(eicos_multi *mh, double delta, double eps);
+/* runtime settings (eicos_batch_set_settings on every shard; a refused struct changes no shard); get: the first shard's */
+int eicos_multi_set_settings(eicos_multi *mh, const eicos_settings *s);
+int eicos_multi_get_settings(eicos_multi *mh, eicos_settings *out);
 /* the shards: their number, and shard s's single-GPU handle (every eicos_batch_* call works on it), instance range and device */
 int eicos_multi_num_shards(eicos_multi *mh);
 int eicos_multi_shard(eicos_multi *mh, int s, eicos_batch **handle, int *first, int *count, int *device);
