@@ -98,6 +98,9 @@ def _lib():
         L.eicos_batch_solution_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
         L.eicos_batch_dims.argtypes = [vp, C.POINTER(Dims)]
         L.eicos_batch_kernel_build.argtypes = [vp]
+        if hasattr(L, "eicos_batch_shared_values"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            L.eicos_batch_shared_values.argtypes = [vp]
+            L.eicos_batch_shared_values.restype = C.c_int
         L.eicos_batch_set_stream.argtypes = [vp, vp]
         L.eicos_batch_set_warm_start.argtypes = [vp, C.c_double]
         L.eicos_batch_set_warm_start.restype = C.c_int
@@ -944,6 +947,14 @@ class BatchSolver(_Solver):
             _chk(v)
         return ("default", "lds-resident", "w2", "u-in-lds")[v]
 
+    def shared_values(self) -> bool:
+        """True when the handle's last updateData found every instance's G and A bit-identical to instance 0's, so that the next solve's
+        products stream one copy of the values (eicos_batch_shared_values); waits for the handle's stream."""
+        v = _lib().eicos_batch_shared_values(self._h)
+        if v < 0:
+            _chk(v)
+        return bool(v)
+
     def last_solve_ms(self) -> float:
         ms = C.c_float()
         _chk(_lib().eicos_batch_last_solve_ms(self._h, C.byref(ms)))
@@ -1075,6 +1086,15 @@ class MultiBatchSolver(_Solver):
         ms = C.c_float()
         _chk(_lib().eicos_batch_last_update_ms(hh, C.byref(ms)))
         return UPDATE_PATHS[_lib().eicos_batch_last_update_path(hh)], float(ms.value)
+
+    def shard_shared_values(self, s: int) -> bool:
+        """BatchSolver.shared_values of shard s: every shard compares with ITS first instance and reads its own reference."""
+        hh = C.c_void_p()
+        _mchk(_lib().eicos_multi_shard(self._h, s, C.byref(hh), None, None, None))
+        v = _lib().eicos_batch_shared_values(hh)
+        if v < 0:
+            _chk(v)
+        return bool(v)
 
     def shard_dims(self, s: int = 0) -> dict:
         hh = C.c_void_p()

@@ -138,6 +138,14 @@ struct eicos_batch {
     // launch of the handle carries its address (UpdArgs::smap), d_shift = NULL while none is installed
     ShiftMapDev shift{}; void *d_shift = nullptr;
     TilePlan tiles;        // tile mode (Symbolic::tile): the dense-front plan
+    // Shared product values (eicos_batch_shared_values): ONE device word.  -1: every instance streams the product values of
+    // its own slab.  0: the last writer of matrix values was a full updateData over [0, batch) from arrays the GPU addresses, and its
+    // kernel found every row of Gpr / Apr bit-identical to row 0 -- the solve's products then all stream instance 0's copies.  ONE place
+    // sets it (shared_detect, in front of that launch); every other launch that writes matrix values of any instance (i_Av, i_Gv, i_cag,
+    // i_rA, i_rG, i_Gt: a sub-range or group-keeping updateData, the chunked paths, the matrix map, the fused forms) is preceded by
+    // shared_clear on the handle's stream.  shared_on: EICOS_SHARED_VALUES (default 1) and not the LDS-resident build, whose values are
+    // in LDS already; shared_maybe: the word may be 0 (spares the clearing memset of a handle that never shares).
+    int *d_shared = nullptr; bool shared_on = false, shared_maybe = false;
 };
 
 namespace {
@@ -945,6 +953,9 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
         HIP_TRY(hipMalloc(&h->d_work, (size_t)h->grid * D.work_stride * sizeof(double)));
         HIP_TRY(hipMemset(h->d_work, 0, (size_t)h->grid * D.work_stride * sizeof(double)));
         HIP_TRY(hipMalloc(&h->d_queue, (16 + (size_t)batch) * sizeof(int))); // [0] queue head, [16..] longest-first order
+        HIP_TRY(hipMalloc(&h->d_shared, 64));
+        HIP_TRY(hipMemset(h->d_shared, 0xFF, 64)); // (-1: nothing shared)
+        h->shared_on = !h->ldsres && env_knob("EICOS_SHARED_VALUES", 1, 0, 1) != 0;
         HIP_TRY(hipMalloc(&h->d_scratch, (size_t)h->upd_grid * (size_t)(S.n + S.p + S.m + 8) * sizeof(double)));
         HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
         h->stream = h->own_stream;
@@ -1044,7 +1055,7 @@ int eicos_batch_destroy(eicos_batch *h) {
     if (h->own_stream) { (void)hipStreamSynchronize(h->own_stream); (void)hipStreamDestroy(h->own_stream); }
     for (int i = 0; i < eicos_batch::EV_RING; i++)
         for (hipEvent_t e : {h->ring_s[i][0], h->ring_s[i][1], h->ring_u[i][0], h->ring_u[i][1]}) if (e) (void)hipEventDestroy(e);
-    for (void *ptr : {(void *)h->d_pattern, (void *)h->d_inst, (void *)h->d_work, (void *)h->d_queue, (void *)h->d_scratch,
+    for (void *ptr : {(void *)h->d_pattern, (void *)h->d_inst, (void *)h->d_work, (void *)h->d_queue, (void *)h->d_shared, (void *)h->d_scratch,
                       (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out, h->d_plant, h->d_roll, h->d_mat, (void *)h->d_mstage, h->d_shift})
         if (ptr) (void)hipFree(ptr);
     for (int i = 0; i < 2; i++) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
@@ -1319,6 +1330,8 @@ struct UpdateInputs {
     MemKind kind[5];      // of the arrays that hold data, when the entry point asked for kinds
     size_t per;           // doubles per instance over the given groups
     bool iterate = false; // a starting point (take_iterate): the groups are x, y, z, s in the slots of G, A, c, h
+    bool detect = false;  // eicos_batch_update_device: arrays in the GPU's own memory, where reading row 0 once more per instance is an L2 hit (pinned host
+                          // rows and another GPU's would cross the link twice) -- its launch may set the shared-values word
     bool holds_data(int k) const { return src[k] && w[k]; }
     bool any(MemKind m) const { for (int k = 0; k < 5; k++) if (holds_data(k) && kind[k] == m) return true; return false; }
     bool all(MemKind m) const { for (int k = 0; k < 5; k++) if (holds_data(k) && kind[k] != m) return false; return true; }
@@ -1386,6 +1399,20 @@ static int take_theta(UpdateInputs &in, eicos_batch *h, int first, int count, co
 // only with A, as updateData reads them) and the unchanged launch_update runs on those pointers -- stream order keeps a chunk's expansion
 // behind the previous chunk's updateData; the buffer grows on demand up to MSTAGE_CAP_MB.  A vector mapped without its matrix then goes
 // through the right-hand-side kernel, which divides by the scalings that updateData has just stored.
+// The shared-values word (eicos_batch::d_shared), on the handle's stream.  shared_clear: in front of every launch that writes matrix values
+// of any instance and is not the detecting one.  shared_detect: in front of the ONE launch that may leave it set.
+static int shared_clear(eicos_batch *h) {
+    if (!h->shared_maybe) return EICOS_OK;
+    HIP_TRY(hipMemsetAsync(h->d_shared, 0xFF, sizeof(int), h->stream));
+    h->shared_maybe = false;
+    return EICOS_OK;
+}
+static int shared_detect(eicos_batch *h) {
+    HIP_TRY(hipMemsetAsync(h->d_shared, 0, sizeof(int), h->stream));
+    h->shared_maybe = true;
+    return EICOS_OK;
+}
+
 static constexpr int MSTAGE_CAP_MB = 64; // (EICOS_MATRIX_STAGE_MB under EICOS_EXPERIMENT=1: tests reach several chunks with a small batch)
 static int param_range(eicos_batch *h, int first, int count, const double *theta) {
     const DevPat &D = h->dp;
@@ -1396,6 +1423,7 @@ static int param_range(eicos_batch *h, int first, int count, const double *theta
         return EICOS_OK;
     }
     if (count == 0) return EICOS_OK;
+    { const int rc = shared_clear(h); if (rc != EICOS_OK) return rc; } // (every instance gets matrices of its own theta)
     const bool mG = h->mat.g[0].base != nullptr, mA = h->mat.g[1].base != nullptr;
     const AffineDev *src[5] = {mG ? &h->mat.g[0] : nullptr, mA ? &h->mat.g[1] : nullptr, M.g[0].base ? &M.g[0] : nullptr,
                                mG && D.m > 0 ? &M.g[1] : nullptr, mA && D.p > 0 ? &M.g[2] : nullptr};
@@ -1433,14 +1461,24 @@ static int param_range(eicos_batch *h, int first, int count, const double *theta
     return EICOS_OK;
 }
 
-static int launch_range(const UpdateInputs &in, int first, int count, const double *const p[5]) {
+// in_place: the launch reads the caller's own arrays (update_in_place) -- with UpdateInputs::detect, the whole batch and every matrix the
+// pattern has among them it is the launch that compares every row of Gpr / Apr with row 0 (launch.hpp: launch_update)
+static int launch_range(const UpdateInputs &in, int first, int count, const double *const p[5], bool in_place = false) {
     eicos_batch *h = in.h;
     if (in.iterate) HIP_TRY(launch_set_iterate(h->pslot, h->d_inst, first, count, p[0], p[1], p[2], p[3], (int)in.per, h->stream));
     else if (in.param) {
         const int rc = param_range(h, first, count, p[2]);
         if (rc != EICOS_OK) return rc;
     } else if (in.rhs) HIP_TRY(launch_update_rhs(h->pslot, h->d_inst, first, count, p[2], p[3], p[4], (int)in.per, h->stream));
-    else HIP_TRY(launch_update(h->pslot, h->d_inst, first, count, p[0], p[1], p[2], p[3], p[4], h->d_scratch, std::min(count, h->upd_grid), h->upd_lds, h->upd_vals_lds, h->stream));
+    else {
+        const DevPat &D = h->dp;
+        const bool detect = in_place && in.detect && h->shared_on && first == 0 && count == h->batch && D.nnzG + D.nnzA > 0 &&
+                            (p[0] || D.nnzG == 0) && (p[1] || D.nnzA == 0);
+        const int rc = detect ? shared_detect(h) : (count > 0 ? shared_clear(h) : EICOS_OK);
+        if (rc != EICOS_OK) return rc;
+        HIP_TRY(launch_update(h->pslot, h->d_inst, first, count, p[0], p[1], p[2], p[3], p[4], h->d_scratch, std::min(count, h->upd_grid), h->upd_lds, h->upd_vals_lds, h->stream,
+                              detect ? h->d_shared : nullptr));
+    }
     return EICOS_OK;
 }
 
@@ -1448,7 +1486,7 @@ static int launch_range(const UpdateInputs &in, int first, int count, const doub
 static int update_in_place(const UpdateInputs &in, int path) {
     if (path) in.h->last_update_path = path;
     int rc = begin_update_timing(in.h);
-    if (rc == EICOS_OK) rc = launch_range(in, in.first, in.count, in.src);
+    if (rc == EICOS_OK) rc = launch_range(in, in.first, in.count, in.src, true);
     return end_update_timing(in.h, rc);
 }
 
@@ -1565,6 +1603,7 @@ int eicos_batch_update_device(eicos_batch *h, int first, int count, const double
                               const double *dc, const double *dh, const double *db) {
     UpdateInputs in;
     const int rc = take_inputs(in, h, first, count, dG, dA, dc, dh, db, false, false);
+    in.detect = true;
     return rc != EICOS_OK ? rc : update_in_place(in, 0);
 }
 
@@ -1807,9 +1846,15 @@ int eicos_batch_solve_async(eicos_batch *h) {
     UpdArgs args = h->fused_pending ? h->fused : UpdArgs{};
     if (!h->fused_pending) args.chunk = 1;
     args.smap = static_cast<const ShiftMapDev *>(h->d_shift);
+    // a fused update that writes matrix values (full updateData; a parametric step or a rollout under a matrix map) drops the shared values
+    if (h->fused_pending && (args.on == UPD_FULL || ((args.on == UPD_PARAM || args.on == UPD_ROLL) && args.mmap))) {
+        const int rc = shared_clear(h);
+        if (rc != EICOS_OK) return rc;
+    }
+    args.shared = h->shared_on ? h->d_shared : nullptr;
     HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(h->pslot, h->d_inst, h->d_work, h->batch, h->d_queue, h->d_queue + 16, h->grid, h->threads, h->nlds,
                                                              h->dp.idx16, h->order_min, h->warm_shift, h->dyn_delta, h->dyn_eps, h->cfg, h->dyn_lds, h->stream,
-                                                             (h->fused_pending || args.smap) ? &args : nullptr));
+                                                             (h->fused_pending || args.smap || args.shared) ? &args : nullptr));
     HIP_TRY(hipEventRecord(h->ev_s1, h->stream));
     h->solve_timed = true;
     h->last_ordered = h->batch > h->order_min;
@@ -2307,6 +2352,15 @@ int eicos_batch_solution_device(eicos_batch *h, const double **dx, size_t *strid
     if (!h || !dx || !stride) return fail(EICOS_E_INVALID, "NULL argument");
     *dx = h->d_inst + h->dp.i_x; *stride = h->dp.inst_stride;
     return EICOS_OK;
+}
+
+int eicos_batch_shared_values(eicos_batch *h) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    int v = -1;
+    HIP_TRY(hipMemcpy(&v, h->d_shared, sizeof(int), hipMemcpyDeviceToHost));
+    return (h->shared_on && v >= 0) ? 1 : 0;
 }
 
 int eicos_batch_kernel_build(eicos_batch *h) {

@@ -162,6 +162,10 @@ struct alignas(16) Sh : ShI {
     const RolloutDev *roll; const ParamMapDev *pmap; const OutMapDev *omap; int *queue;
     const MatrixMapDev *mmap; // (UpdArgs::mmap: a rollout's steps run matrix_param_instance when it is set)
     const ShiftMapDev *smap;  // (UpdArgs::smap, every build and every launch: instance_begin shifts a warm start through it when it is set)
+    // the slab whose product values (i_cag, i_rA, i_rG, i_Gt) stage_resid and kkt_solve stream: the instance's own, or -- UpdArgs::shared says
+    // that every instance of the batch holds the same bits there -- the reference instance's, which then stays in L2 for all of them
+    const double *vals;
+    int vshared; // 1: `vals` is the reference instance's slab, read by every instance -> the stages' PLAIN instantiations (solve_instance)
 };
 constexpr int KI_MAX = 2; // right-hand sides of a dual solve (kkt_solve<..., 2, true>)
 enum { TK_FACTOR = 0, TK_LDL, TK_KRES, TK_KPOST, TK_RESID, TK_FWD, TK_COUNT, TK_FA = 8, TK_FW1, TK_FB, TK_FW2 }; // 8..11: inside the factor
@@ -496,9 +500,17 @@ template <bool I16> __device__ __forceinline__ void load_indices(int (&ni)[ELL_K
     }
 }
 
+// A matrix value of a product plan (ell_dots, ell_dots_k).  An instance's own copy is streamed once per pass: the non-temporal hint keeps the
+// shared index arrays in L2 (docs/HISTORY.md A.11 item 6 v).  PLAIN: the ONE copy every instance of the batch reads (Sh::vals) -- a plain load,
+// so that the lines stay in every XCD's L2; under the hint the whole chip would fetch the same 197 KB from the same channels over and over
+// (docs/HISTORY.md A.13: -5 % with the hint, +6.5 % without).
+template <bool PLAIN, class B> __device__ __forceinline__ double ld_val(B base, int i) {
+    if constexpr (PLAIN) return ld_u32(base, i);
+    else return ld_u32_nt(base, i);
+}
 // `pre(row)` loads whatever the epilogue needs per row (rhs entry, destination index, ...); it is issued with the
 // slice's index/value loads, ELL_DEPTH slices ahead, so that `epi(row, sum, pre(row))` starts no global load itself.
-template <int T, bool I16, class SM, class V, class X, class Pre, class Epi>
+template <int T, bool I16, bool PLAIN, class SM, class V, class X, class Pre, class Epi>
 __device__ __forceinline__ void ell_dots(const SM *sm, int ns, int nr, gint_p eidx, gint_p eidx16, int d16, V eval, X x, int dummy_slot,
                                          Pre &&pre, Epi &&epi) {
     if (nr == 0) return; // no rows  (ns: slices incl. the host's padding, nr: the real ones -- see tri_sweep)
@@ -517,7 +529,7 @@ __device__ __forceinline__ void ell_dots(const SM *sm, int ns, int nr, gint_p ei
 #ifdef EICOS_PROBE_NOVAL // (dev probe: what would the products cost with their value stream free?  wrong numerics, timing only)
             nv[kk] = 1e-3 * (double)(slot & 7);
 #else
-            nv[kk] = ld_u32_nt(eval, slot); // streamed once per pass: keep the shared index arrays in L2
+            nv[kk] = ld_val<PLAIN>(eval, slot);
 #endif
         }
         nr = pre(act ? nm.row0 + (t >> nm.lg) : 0);
@@ -566,7 +578,7 @@ __device__ __forceinline__ void ell_dots(const SM *sm, int ns, int nr, gint_p ei
 // ell_dots for KI right-hand sides at once: the slice descriptors, gather indices and (SHARED: the dual solve of ONE instance)
 // the matrix values are loaded once, the gathered vector x is KI-interleaved; `pre(k, row)` / `epi(k, row, sum, pre)` get the
 // number of the right-hand side.
-template <int T, bool I16, int KI, bool SHARED, class SM, class X, class Pre, class Epi>
+template <int T, bool I16, int KI, bool SHARED, bool PLAIN, class SM, class X, class Pre, class Epi>
 __device__ __forceinline__ void ell_dots_k(const SM *sm, int ns, int nr, gint_p eidx, gint_p eidx16, int d16, const gcdbl_p (&eval)[KI], X x, int dummy_slot,
                                            Pre &&pre, Epi &&epi) {
     if (nr == 0) return; // no rows
@@ -584,15 +596,14 @@ __device__ __forceinline__ void ell_dots_k(const SM *sm, int ns, int nr, gint_p 
 #pragma unroll
         for (int kk = 0; kk < ELL_KMAX; kk++) {
             const int slot = (act && kk < nm.K) ? nm.off + kk * lanes + t : dummy_slot;
-            // streamed once per pass: keep the shared index arrays in L2.  SHARED (dual right-hand sides of ONE instance):
-            // the KI vectors are multiplied by the same matrix values -> one load
+            // SHARED (dual right-hand sides of ONE instance): the KI vectors are multiplied by the same matrix values -> one load
 #ifdef EICOS_PROBE_NOVAL
             nv[kk][0] = 1e-3 * (double)(slot & 7);
 #else
-            nv[kk][0] = ld_u32_nt(eval[0], slot);
+            nv[kk][0] = ld_val<PLAIN>(eval[0], slot);
 #endif
 #pragma unroll
-            for (int k = 1; k < KI; k++) nv[kk][k] = SHARED ? nv[kk][0] : ld_u32_nt(eval[k], slot);
+            for (int k = 1; k < KI; k++) nv[kk][k] = SHARED ? nv[kk][0] : ld_val<PLAIN>(eval[k], slot);
         }
 #pragma unroll
         for (int k = 0; k < KI; k++) nr[k] = pre(k, act ? nm.row0 + (t >> nm.lg) : 0);
@@ -1847,18 +1858,29 @@ __device__ __forceinline__ IterBuf iter_buf(const DevPat &P, gdbl_p I, gdbl_p W,
     return which ? IterBuf{W + P.w_bx, W + P.w_by, W + P.w_bz, W + P.w_bs} : IterBuf{I + P.i_x, I + P.i_y, I + P.i_z, I + P.i_s};
 }
 
+// The slab the products read their matrix values from (Sh::vals, set by k_solve per instance): workgroup-uniform.  The LDS-resident build
+// has copied the instance's own values into LDS already.
+__device__ __forceinline__ gcdbl_p product_values(gdbl_p I) {
+#if EICOS_LDSRES
+    return I;
+#else
+    return uni_ptr((gcdbl_p)g_S.vals);
+#endif
+}
+
 // ---------------- ST_RESID: residuals, statistics, exit logic, scalings ----------------
-template <int T, int NLDS, bool I16>
+template <int T, int NLDS, bool I16, bool PLAIN = false> // (PLAIN: the product values are the batch's shared copy -- ld_val)
 static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(int ps, gdbl_p I, gdbl_p W, int iter) {
     STAGE_PROLOGUE
     iter = uni(iter);
-    gcdbl_p cagv = I + P.i_cag, rAv = I + P.i_rA, rGv = I + P.i_rG;
     gdbl_p cv = I + P.i_c, hv = I + P.i_h, bv = I + P.i_b, Vv = I + P.i_Vv;
     gdbl_p lam = W + P.w_lam, rz = W + P.w_rz, rhs2k = W + P.w_rhs2k;
     gdbl_p lpw = W + P.w_lpw, lpv = W + P.w_lpv, csc = W + P.w_csc, qv = W + P.w_qv;
     __syncthreads();
     const IterBuf it = iter_buf(P, I, W, g_S.cur); // (after the barrier: the previous stage's thread 0 may just have switched sets)
     gdbl_p wx = it.x, wy = it.y, wz = it.z, wsl = it.s;
+    const gcdbl_p PV = product_values(I);
+    gcdbl_p cagv = PV + P.i_cag, rAv = PV + P.i_rA, rGv = PV + P.i_rG;
     TICK_BEGIN;
     // ---- computeResiduals (ref :643-689) + updateStatistics (ref :691-754) ----
     const double tau = wi.tau;
@@ -1870,16 +1892,16 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(
     struct Pre3 { double a, b, c, g; };
     const bool gt = P.gt_on != 0; // G in tiles: one pass gives G x (gzv) and G' z (gxv); the ELL plans below then hold A only
     gdbl_p gxv = W + P.w_gx, gzv = W + P.w_gz;
-    if (gt) g_tile_products<T, 1>(P, I + P.i_Gt, P.gt_col, [&](int c, int) { return c < 0 ? 0. : wx[c]; }, [&](int i, int) { return wz[i]; },
+    if (gt) g_tile_products<T, 1>(P, PV + P.i_Gt, P.gt_col, [&](int c, int) { return c < 0 ? 0. : wx[c]; }, [&](int i, int) { return wz[i]; },
                                   W + P.w_gpart, gxv, gzv);
-    ell_dots<T, I16>(tab_cag, P.cag_ns, P.cag_ns_r, P.cag_idx_yz, P.cag_yz16, P.cag_d16, cagv, wy, P.cag_slots, [&](int j) { return Pre2{cv[j], wx[j], gt ? gxv[j] : 0.}; },
+    ell_dots<T, I16, PLAIN>(tab_cag, P.cag_ns, P.cag_ns_r, P.cag_idx_yz, P.cag_yz16, P.cag_d16, cagv, wy, P.cag_slots, [&](int j) { return Pre2{cv[j], wx[j], gt ? gxv[j] : 0.}; },
                 [&](int j, double s, const Pre2 &pr) { // -G'z - A'y: (y,z) contiguous
         const double hr = -(s + pr.g), c_ = pr.a, xj = pr.b;
         const double r = hr - tau * c_;
         rhs2k[j] = r; // (rx, only ever read as the x part of RHSaffine)
         r8[0] += hr * hr; r8[1] += r * r; r8[2] += c_ * xj; r8[3] += xj * xj;
     });
-    ell_dots<T, I16>(tab_rA, P.rA_ns, P.rA_ns_r, P.rA_idx, P.rA_16, P.rA_d16, rAv, wx, P.rA_slots, [&](int r) { return Pre2{bv[r], wy[r], 0.}; },
+    ell_dots<T, I16, PLAIN>(tab_rA, P.rA_ns, P.rA_ns_r, P.rA_idx, P.rA_16, P.rA_d16, rAv, wx, P.rA_slots, [&](int r) { return Pre2{bv[r], wy[r], 0.}; },
                 [&](int r, double s, const Pre2 &pr) {
         const double b_ = pr.a, yr = pr.b;
         const double rr = s - tau * b_;
@@ -1888,7 +1910,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(
     });
     blk_reduce<OpSum, T, 8>(phase, r8);
     double q6[6] = {0, 0, 0, 0, 0, 0}; // hresz2 rz2 hz nz2 ns2 gap
-    ell_dots<T, I16>(tab_rG, P.rG_ns, P.rG_ns_r, P.rG_idx, P.rG_16, P.rG_d16, rGv, wx, P.rG_slots, [&](int i) { return Pre3{wsl[i], wz[i], hv[i], gt ? gzv[i] : 0.}; },
+    ell_dots<T, I16, PLAIN>(tab_rG, P.rG_ns, P.rG_ns_r, P.rG_idx, P.rG_16, P.rG_d16, rGv, wx, P.rG_slots, [&](int i) { return Pre3{wsl[i], wz[i], hv[i], gt ? gzv[i] : 0.}; },
                 [&](int i, double s, const Pre3 &pr) {
         const double si = pr.a, zi = pr.b, h_ = pr.c;
         const double hr = si + (s + pr.g), r = hr - tau * h_;
@@ -2228,7 +2250,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(
 // right-hand side k at 2 i + k); every right-hand side keeps its own refinement state (step count, previous error, done
 // flag): the loop runs until both have stopped, one that has stopped keeps its iterate while the other takes further
 // steps (its lanes still compute, the result is discarded).  amask: bit k set = right-hand side k takes part.
-template <int T, int NLDS, bool I16, int KI, bool DUAL = false>
+template <int T, int NLDS, bool I16, int KI, bool DUAL = false, bool PLAIN = false> // (PLAIN: as stage_resid's)
 static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(int ps, gdbl_p I0, gdbl_p I1, gdbl_p Wg, int stage, int amask) {
     ps = uni(ps); I0 = uni_ptr(I0); I1 = uni_ptr(I1); Wg = uni_ptr(Wg); stage = uni(stage); amask = uni(amask);
     const DevPat &P = c_pat[ps];
@@ -2242,11 +2264,12 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
     const bool first = (stage == ST_KKT_INIT1 || stage == ST_KKT1);
     gcdbl_p cagv[KI], rAv[KI], rGv[KI], bx[KI], by[KI], bz[KI], lpv[KI], csc[KI], qv[KI];
     gdbl_p dx[KI], dy[KI], dz[KI];
+    const gcdbl_p PV = product_values(I0); // (every right-hand side belongs to the one instance the workgroup is solving)
 #pragma unroll
     for (int k = 0; k < KI; k++) {
-        gdbl_p I = Ik[k], W = Wg;
+        gdbl_p W = Wg;
         const bool fk = DUAL ? (k == 0) : first; // dual: right-hand side 0 is rhs1 -> (dx1, dy1, dz1), 1 is rhs2 -> (dx2, dy2, dz2)
-        cagv[k] = I + P.i_cag; rAv[k] = I + P.i_rA; rGv[k] = I + P.i_rG;
+        cagv[k] = PV + P.i_cag; rAv[k] = PV + P.i_rA; rGv[k] = PV + P.i_rG;
         gcdbl_p rhsk = W + (fk ? P.w_rhs1k : P.w_rhs2k);               // the right-hand side as [x | y | z]
         bx[k] = rhsk; by[k] = rhsk + n; bz[k] = rhsk + np;
         lpv[k] = W + P.w_lpv; csc[k] = W + P.w_csc; qv[k] = W + P.w_qv;
@@ -2430,23 +2453,23 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
         struct PreK { double b, w; int o, sg; double g; }; // rhs entry, LP scaling, elimination-order slot, sign of the regularisation, G-tile term
         const bool gt = P.gt_on != 0; // G in tiles: one pass gives G dx and G' dz for all KI right-hand sides
         gdbl_p gxv = Wg + P.w_gx, gzv = Wg + P.w_gz;
-        if (gt) g_tile_products<T, KI>(P, I0 + P.i_Gt, P.gt_colk, [&](int c, int k) { return X[c * KI + k]; },
+        if (gt) g_tile_products<T, KI>(P, PV + P.i_Gt, P.gt_colk, [&](int c, int k) { return X[c * KI + k]; },
                                        [&](int i, int k) { return X[P.gt_zslot[i] * KI + k]; }, Wg + P.w_gpart, gxv, gzv);
-        ell_dots_k<T, I16, KI, DUAL>(tab_cag, P.cag_ns, P.cag_ns_r, P.cag_idx_k, P.cag_k16, P.cag_d16, cagv, X, P.cag_slots,
+        ell_dots_k<T, I16, KI, DUAL, PLAIN>(tab_cag, P.cag_ns, P.cag_ns_r, P.cag_idx_k, P.cag_k16, P.cag_d16, cagv, X, P.cag_slots,
                     [&](int k, int j) { return PreK{ld_u32(bx[k], j), 0., ld_u32(P.ipx, j), 0, gt ? gxv[j * KI + k] : 0.}; },
                     [&](int k, int j, double s, const PreK &pr) {
             const int o = pr.o;
             const double e = pr.b - (s + pr.g) - DELTASTAT * X[o * KI + k]; // ex = bx - G'dz - A'dy - delta dx
             stE(o, k, e); nex[k] = fmax(nex[k], fabs(e));
         });
-        ell_dots_k<T, I16, KI, DUAL>(tab_rA, P.rA_ns, P.rA_ns_r, P.rA_idx_k, P.rA_k16, P.rA_d16, rAv, X, P.rA_slots,
+        ell_dots_k<T, I16, KI, DUAL, PLAIN>(tab_rA, P.rA_ns, P.rA_ns_r, P.rA_idx_k, P.rA_k16, P.rA_d16, rAv, X, P.rA_slots,
                     [&](int k, int r) { return PreK{ld_u32(by[k], r), 0., ld_u32(P.ipy, r), 0, 0.}; },
                     [&](int k, int r, double s, const PreK &pr) {
             const int o = pr.o;
             const double e = pr.b - s + DELTASTAT * X[o * KI + k]; // ey = by - A dx + delta dy
             stE(o, k, e); ney[k] = fmax(ney[k], fabs(e));
         });
-        ell_dots_k<T, I16, KI, DUAL>(tab_rG, P.rG_ns, P.rG_ns_r, P.rG_idx_k, P.rG_k16, P.rG_d16, rGv, X, P.rG_slots,
+        ell_dots_k<T, I16, KI, DUAL, PLAIN>(tab_rG, P.rG_ns, P.rG_ns_r, P.rG_idx_k, P.rG_k16, P.rG_d16, rGv, X, P.rG_slots,
                     [&](int k, int i) { return PreK{ld_u32(bz[k], i), ld_u32(lpv[k], i < l ? i : 0), ld_u32(P.ipz, i), ld_u32(P.zdsign, i), gt ? gzv[i * KI + k] : 0.}; },
                     [&](int k, int i, double s, const PreK &pr) {
             const int o = pr.o;
@@ -3087,6 +3110,13 @@ __device__ __forceinline__ void solve_instance(int ps, gdbl_p I, gdbl_p W, doubl
     int stage = ST_FACTOR, iter = -1; // iter = -1 while initialising
     if (instance_begin<T, (NLDS >= 1)>(ps, I, W, warm)) { stage = ST_RESID; iter = 0; } // warm start: no initialisation solves
     __syncthreads();
+    // shared product values: the two stages that stream them run their plain-load instantiation -- one uniform branch per stage call,
+    // outside every loop (k_solve set the flag in front of this instance)
+#if EICOS_LDSRES
+    constexpr bool plain = false;
+#else
+    const bool plain = uni(g_S.vshared) != 0;
+#endif
     while (stage != ST_DONE) {
         if (stage == ST_FACTOR) {
             if (P.tile != 1) { if (P.fac_defer) stage_factor<T, NLDS, I16, true>(ps, W); else stage_factor<T, NLDS, I16, false>(ps, W); } // scalar program (hybrid: everything below the top block + its image)
@@ -3103,13 +3133,14 @@ __device__ __forceinline__ void solve_instance(int ps, gdbl_p I, gdbl_p W, doubl
             }
             else stage = (iter < 0) ? ST_KKT_INIT1 : ST_KKT1;
         } else if (stage == ST_RESID) {
-            if (stage_resid<T, NLDS, I16>(ps, I, W, iter) == ST_DONE) { __syncthreads(); instance_end(P, I, W); stage = ST_DONE; }
+            const int next = plain ? stage_resid<T, NLDS, I16, true>(ps, I, W, iter) : stage_resid<T, NLDS, I16, false>(ps, I, W, iter);
+            if (next == ST_DONE) { __syncthreads(); instance_end(P, I, W); stage = ST_DONE; }
             else stage = ST_FACTOR;
         } else if (NLDS == 1 && P.dual && (stage == ST_KKT_INIT1 || stage == ST_KKT1)) {
             // the two right-hand sides of this point of the algorithm do not depend on each other: one dual solve
             if constexpr (NLDS == 1) {
                 if (stage == ST_KKT1) kkt_post_any<T>(ps, I, W, ST_KKT1); // RHSaffine (ref :1176) needs the residuals only
-                kkt_solve<T, 1, I16, 2, true>(ps, I, I, W, stage, 3);
+                if (plain) kkt_solve<T, 1, I16, 2, true, true>(ps, I, I, W, stage, 3); else kkt_solve<T, 1, I16, 2, true, false>(ps, I, I, W, stage, 3);
                 const int second = (stage == ST_KKT1) ? ST_KKT_AFF : ST_KKT_INIT2;
                 if (stage == ST_KKT_INIT1) kkt_post_any<T>(ps, I, W, ST_KKT_INIT1);
                 __syncthreads();
@@ -3120,7 +3151,7 @@ __device__ __forceinline__ void solve_instance(int ps, gdbl_p I, gdbl_p W, doubl
                 stage = next;
             }
         } else {
-            kkt_solve<T, NLDS, I16, 1>(ps, I, I, W, stage, 1);
+            if (plain) kkt_solve<T, NLDS, I16, 1, false, true>(ps, I, I, W, stage, 1); else kkt_solve<T, NLDS, I16, 1, false, false>(ps, I, I, W, stage, 1);
             const int next = kkt_post_any<T>(ps, I, W, stage);
             if (next == ST_RESID) iter = (stage == ST_KKT_INIT2) ? 0 : iter + 1; // a pass of the main loop completed
             stage = next;
@@ -3146,10 +3177,15 @@ __device__ __forceinline__ void solve_instance(int ps, gdbl_p I, gdbl_p W, doubl
 // `q` = row of this instance in the input arrays (NULL = keep that group), I = its slab in HBM.
 // PRE (matrix_param_instance, LDSV = false only): the caller has already left the un-equilibrated values and vectors in the slab -- the first
 // phase is skipped and the input arrays are not read; everything from the equilibration sweeps on is this one body.
-typedef double EICOS_GLOBAL *hbm_p; // (global memory in every build: the LDS-resident build's gdbl_p is an LDS pointer)
-template <int T, bool LDSV, bool PRE = false>
+// DET with `shared` (the update launch that covers the whole batch with both matrices given: launch_update): the first phase also loads the
+// same entry of ROW 0 of Gpr / Apr (L2-resident: no further HBM pass) and compares bit patterns -- -0.0 differs from +0.0, a NaN equals
+// only itself; a thread that saw a difference stores -1 to *shared (the host set it to 0 in front of the launch; a plain store, every
+// writer stores the same value).  Equilibration reads A and G only, so equal rows give equal bits in every slab's value copies.
+typedef double EICOS_GLOBAL *hbm_p;
+__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); } // (global memory in every build: the LDS-resident build's gdbl_p is an LDS pointer)
+template <int T, bool LDSV, bool PRE = false, bool DET = false>
 static __device__ __noinline__ __attribute__((not_tail_called)) void update_instance(int ps, hbm_p I, size_t q, const double *Gpr, const double *Apr, const double *cin,
-                                                                                      const double *hin, const double *bin) {
+                                                                                      const double *hin, const double *bin, int *shared = nullptr) {
     ps = uni(ps); I = uni_ptr(I);
     const DevPat &P = c_pat[ps];
     const int n = P.n, p = P.p, m = P.m, l = P.l, nnzA = P.nnzA, nnzG = P.nnzG;
@@ -3165,15 +3201,26 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void update_inst
     auto sG = [&] { if constexpr (LDSV) return gt + m + nnzA; else return Gv; }();
     if constexpr (!PRE) {
         __syncthreads();
+        [[maybe_unused]] const bool det = DET && shared != nullptr;
+        [[maybe_unused]] bool differs = false;
         // un-equilibrate what is kept, overwrite what is given (ref :2053-2074, :389-404) -> working copy of the values
         for_t_pre<T, 4>(nnzA, [&](int k) {
+            if constexpr (DET) { if (det) return V3{Apr[(size_t)q * nnzA + k], Apr[k], 1.}; } // (det: both matrices are given; .b = the entry of row 0)
             if (Apr) return V3{Apr[(size_t)q * nnzA + k], 1., 1.};
             return was_eq ? V3{Av[k], ae[P.Air[k]], xe[P.Acol[k]]} : V3{Av[k], 1., 1.};
-        }, [&](int k, const V3 &r) { sA[k] = (Apr || !was_eq) ? r.a : r.a * (r.b * r.c); });
+        }, [&](int k, const V3 &r) {
+            if constexpr (DET) { if (det) differs |= !same_bits(r.a, r.b); }
+            sA[k] = (Apr || !was_eq) ? r.a : r.a * (r.b * r.c);
+        });
         for_t_pre<T, 4>(nnzG, [&](int k) {
+            if constexpr (DET) { if (det) return V3{Gpr[(size_t)q * nnzG + k], Gpr[k], 1.}; }
             if (Gpr) return V3{Gpr[(size_t)q * nnzG + k], 1., 1.};
             return was_eq ? V3{Gv[k], ge[P.Gir[k]], xe[P.Gcol[k]]} : V3{Gv[k], 1., 1.};
-        }, [&](int k, const V3 &r) { sG[k] = (Gpr || !was_eq) ? r.a : r.a * (r.b * r.c); });
+        }, [&](int k, const V3 &r) {
+            if constexpr (DET) { if (det) differs |= !same_bits(r.a, r.b); }
+            sG[k] = (Gpr || !was_eq) ? r.a : r.a * (r.b * r.c);
+        });
+        if constexpr (DET) { if (differs) *shared = -1; }
         FOR_T(j, n) cv[j] = cin ? cin[(size_t)q * n + j] : (was_eq ? cv[j] * xe[j] : cv[j]);
         FOR_T(r, p) bv[r] = Apr ? bin[(size_t)q * p + r] : (was_eq ? bv[r] * ae[r] : bv[r]);
         FOR_T(i, m) hv[i] = Gpr ? hin[(size_t)q * m + i] : (was_eq ? hv[i] * ge[i] : hv[i]);
@@ -3497,6 +3544,13 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
         }
 #else
         gdbl_p I = (gdbl_p)inst + (size_t)id * P.inst_stride;
+        // shared product values (launch.hpp: UpdArgs::shared): read once per instance, behind this instance's fused update if there is one;
+        // solve_instance's first barrier stands between this store and the stages that read it
+        if (threadIdx.x == 0) {
+            const int ref = upd.shared ? *upd.shared : -1;
+            g_S.vals = inst + (size_t)(ref >= 0 ? ref : id) * P.inst_stride;
+            g_S.vshared = ref >= 0;
+        }
 #endif
         solve_instance<T, NLDS, I16>(ps, I, W, warm);
         __syncthreads();
@@ -3559,7 +3613,7 @@ __global__ __launch_bounds__(1024) void k_order(int ps, const double *inst, int 
 template <int T>
 __global__ __launch_bounds__(T) void k_update(int ps, double *inst, int first, int count,
                                               const double *Gpr, const double *Apr, const double *cin,
-                                              const double *hin, const double *bin, double *scratch) {
+                                              const double *hin, const double *bin, double *scratch, int *shared) {
     const DevPat &P = c_pat[ps];
     const int n = P.n, p = P.p, m = P.m, l = P.l;
     gdbl_p xt = (gdbl_p)scratch + (size_t)blockIdx.x * (size_t)(n + p + m), at = xt + n, gt = at + p;
@@ -3570,15 +3624,21 @@ __global__ __launch_bounds__(T) void k_update(int ps, double *inst, int first, i
         DevInfo *ginfo = reinterpret_cast<DevInfo *>(I + P.i_info);
         const bool was_eq = ginfo->equilibrated != 0;
         __syncthreads();
-        // un-equilibrate what is kept, overwrite what is given
+        // un-equilibrate what is kept, overwrite what is given; `shared` (update_instance: DET): compare with row 0 of the given matrices
+        bool differs = false;
         FOR_T(j, n) {
             const double xj = was_eq ? xe[j] : 1.;
-            for (int k = P.Ajc[j]; k < P.Ajc[j + 1]; k++)
+            for (int k = P.Ajc[j]; k < P.Ajc[j + 1]; k++) {
                 Av[k] = Apr ? Apr[(size_t)q * P.nnzA + k] : (was_eq ? Av[k] * (ae[P.Air[k]] * xj) : Av[k]);
-            for (int k = P.Gjc[j]; k < P.Gjc[j + 1]; k++)
+                if (shared) differs |= !same_bits(Av[k], Apr[k]);
+            }
+            for (int k = P.Gjc[j]; k < P.Gjc[j + 1]; k++) {
                 Gv[k] = Gpr ? Gpr[(size_t)q * P.nnzG + k] : (was_eq ? Gv[k] * (ge[P.Gir[k]] * xj) : Gv[k]);
+                if (shared) differs |= !same_bits(Gv[k], Gpr[k]);
+            }
             cv[j] = cin ? cin[(size_t)q * n + j] : (was_eq ? cv[j] * xj : cv[j]);
         }
+        if (differs) *shared = -1;
         FOR_T(r, p) bv[r] = Apr ? bin[(size_t)q * p + r] : (was_eq ? bv[r] * ae[r] : bv[r]);
         FOR_T(i, m) hv[i] = Gpr ? hin[(size_t)q * m + i] : (was_eq ? hv[i] * ge[i] : hv[i]);
         __syncthreads();
@@ -3651,10 +3711,10 @@ __global__ __launch_bounds__(T) void k_update(int ps, double *inst, int first, i
 template <int T, bool LDSV>
 __global__ __launch_bounds__(T) void k_update_lds(int ps, double *inst, int first, int count,
                                                   const double *Gpr, const double *Apr, const double *cin,
-                                                  const double *hin, const double *bin) {
+                                                  const double *hin, const double *bin, int *shared) {
     const DevPat &P = c_pat[ps];
     for (int q = blockIdx.x; q < count; q += gridDim.x)
-        update_instance<T, LDSV>(ps, (hbm_p)inst + (size_t)(first + q) * P.inst_stride, (size_t)q, Gpr, Apr, cin, hin, bin);
+        update_instance<T, LDSV, false, true>(ps, (hbm_p)inst + (size_t)(first + q) * P.inst_stride, (size_t)q, Gpr, Apr, cin, hin, bin, shared);
 }
 
 // right-hand-side-only updateData of a range of instances (rhs_instance): ENTRY-parallel -- blockIdx.y strides over the instances,
@@ -3882,6 +3942,7 @@ __global__ __launch_bounds__(T, waves_per_eu<T>()) void k_debug_scalings(int ps,
         for (int k = 0; k < 12; k++) g_S.tick[k] = 0;
         g_S.dyn_delta = 0.; g_S.dyn_eps = 0.; g_S.cfg = solve_cfg_default();
         g_S.cur = 0; g_S.best = -1;
+        g_S.vals = inst + (size_t)i * P.inst_stride;
     }
     for (int j = threadIdx.x; j < P.n; j += T) I[P.i_x + j] = 0.;
     for (int j = threadIdx.x; j < P.p; j += T) I[P.i_y + j] = 0.;
@@ -3931,7 +3992,7 @@ template <class F> static auto dispatch_solve(int threads, int nlds, int idx16, 
 #endif
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds,
                         int idx16, int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg_in, size_t dyn_lds, hipStream_t st, const UpdArgs *upd_in) {
-    UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     SolveCfg cfg = cfg_in; // (by value into the kernel arguments: a launch in flight keeps the settings it was enqueued with)
     if (upd.on && nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector; both modes live in the NLDS >= 1 kernels)
     if (B <= 0) return hipSuccess;
@@ -3956,13 +4017,14 @@ hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, i
 }
 #if EICOS_MAIN_BUILD
 hipError_t launch_update(int ps, double *inst, int first, int count, const double *Gpr, const double *Apr,
-                         const double *c, const double *h, const double *b, double *scratch, int grid, size_t lds_bytes, int vals_in_lds, hipStream_t st) {
+                         const double *c, const double *h, const double *b, double *scratch, int grid, size_t lds_bytes, int vals_in_lds, hipStream_t st,
+                         int *shared) {
     if (count <= 0) return hipSuccess;
     if (lds_bytes > 0 && !vals_in_lds) { // entry-parallel, maxima in LDS, values streamed in place in the slab (several workgroups per CU)
-        hipLaunchKernelGGL((k_update_lds<512, false>), dim3(grid), dim3(512), lds_bytes, st, ps, inst, first, count, Gpr, Apr, c, h, b);
+        hipLaunchKernelGGL((k_update_lds<512, false>), dim3(grid), dim3(512), lds_bytes, st, ps, inst, first, count, Gpr, Apr, c, h, b, shared);
     } else if (lds_bytes > 0) { // values + maxima fit LDS: the entry-parallel kernel, 512 threads, one workgroup per CU at a time
-        hipLaunchKernelGGL((k_update_lds<512, true>), dim3(grid), dim3(512), lds_bytes, st, ps, inst, first, count, Gpr, Apr, c, h, b);
-    } else hipLaunchKernelGGL(k_update<256>, dim3(grid), dim3(256), 0, st, ps, inst, first, count, Gpr, Apr, c, h, b, scratch);
+        hipLaunchKernelGGL((k_update_lds<512, true>), dim3(grid), dim3(512), lds_bytes, st, ps, inst, first, count, Gpr, Apr, c, h, b, shared);
+    } else hipLaunchKernelGGL(k_update<256>, dim3(grid), dim3(256), 0, st, ps, inst, first, count, Gpr, Apr, c, h, b, scratch, shared);
     return hipGetLastError();
 }
 hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st) {

@@ -45,6 +45,10 @@ struct UpdArgs {
     // Every mode, 0 included: a solve that warm-starts an instance first takes its x, y, z, s through this map (kernels.hip: shift_instance);
     // NULL: no shift map.  One more word of kernel arguments, and one pointer test per instance.
     const ShiftMapDev *smap;
+    // Every mode, 0 included: the handle's shared-values word (eicos_batch_shared_values), read by thread 0 once per instance before the
+    // instance's solve.  -1: every instance streams the product values (the sliced-ELL copies of [A' G'], A, G and the G tiles) of its own
+    // slab; r >= 0: every instance of the batch holds the bits of instance r there, and all of them stream instance r's.  NULL counts as -1.
+    const int *shared;
 };
 // Runtime solver settings (eicos_batch_set_settings; eicos_settings of include/eicos_amd.h, same fields and defaults): one by-value argument
 // of k_solve, copied into LDS by thread 0 (kernels.hip: Sh::cfg) before the workgroup's first instance, where the stage functions read
@@ -54,8 +58,12 @@ struct SolveCfg { double feastol, abstol, reltol, feastol_inacc, abstol_inacc, r
 constexpr SolveCfg solve_cfg_default() { return {1e-8, 1e-8, 1e-8, 1e-4, 5e-5, 5e-5, 1e-14, 6., 100, 9}; }
 hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
                         int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
+// shared != NULL (only the launch that covers the whole batch, first = 0, with every matrix the pattern has given): the handle's shared-values
+// word, which the host has set to 0 on `st` in front of this launch -- a workgroup whose rows of Gpr / Apr differ from row 0 in any bit
+// stores -1 (kernels.hip: update_instance)
 hipError_t launch_update(int ps, double *inst, int first, int count, const double *Gpr, const double *Apr,
-                         const double *c, const double *h, const double *b, double *scratch, int grid, size_t lds_bytes, int vals_in_lds, hipStream_t st);
+                         const double *c, const double *h, const double *b, double *scratch, int grid, size_t lds_bytes, int vals_in_lds, hipStream_t st,
+                         int *shared = nullptr);
 // right-hand-side-only updateData of instances [first, first + count): rows of c [count][n], h [count][m], b [count][p] (NULL = keep)
 // divided by each instance's stored scalings; `width` = the summed widths of the given groups (sizes the grid)
 hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st);

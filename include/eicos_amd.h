@@ -407,6 +407,20 @@ int eicos_batch_dims(eicos_batch *hd, eicos_dims *out);
  * compiled for two waves per SIMD (launches of at most two workgroups per CU), 3 = the 256- / 512-thread kernel with the factor operand
  * array resident in LDS (launches of one workgroup per CU whose factor fits the idle LDS).  Negative: error code. */
 int eicos_batch_kernel_build(eicos_batch *hd);
+/* Shared matrix values (no reference counterpart; transparent: results are bit-identical with it on and off).  Many batches are one plant
+ * with many states or scenarios: every instance gets the same Gpr and Apr and only c, h, b differ.  Equilibration reads A and G only, so
+ * every instance then holds the same bits in the value copies its matrix-vector products stream, and the solve kernel reads ONE copy --
+ * instance 0's, resident in L2 -- instead of one per instance from HBM.  The handle finds this out by itself:
+ *   sets it    eicos_batch_update_device over the whole batch (first = 0, count = batch) with Gpr and Apr both given (a pattern without A: Gpr):
+ *              its kernel compares every row with row 0 bit for bit (-0.0 differs from +0.0, a NaN equals only the same NaN) and the
+ *              values are shared when no row differs;
+ *   keeps it   everything that leaves matrix values alone: eicos_batch_update_rhs*, _update_param* without a matrix map, _update_rhs_solve,
+ *              _update_param_solve and eicos_batch_rollout without a matrix map, warm start, starting points, settings, solves;
+ *   drops it   every other updateData: host-pointer and other-GPU forms, sub-ranges, calls that keep Gpr or Apr, eicos_batch_update_solve,
+ *              and the parametric forms and rollouts under a matrix map.
+ * eicos_batch_shared_values: 1 when the next solve will read shared values, else 0; waits for the handle's stream.  Always 0 on the
+ * LDS-resident build (eicos_batch_kernel_build = 1), whose values are in LDS anyway.  Negative: error code. */
+int eicos_batch_shared_values(eicos_batch *hd);
 /* Use a caller-owned HIP stream (hipStream_t passed as void*); NULL restores the own stream. */
 int eicos_batch_set_stream(eicos_batch *hd, void *hip_stream);
 /* HIP-event timing of the most recent solve / update kernels on the handle's stream (ms). */
