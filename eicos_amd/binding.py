@@ -315,6 +315,49 @@ def _rhs_ptrs(pat, count, c, h, b):
     return _group_ptrs((c, h, b), (pat.n, pat.m, pat.p), count)
 
 
+def _as_group(g):
+    """One group `(base, rowptr, col, val)` of an affine map -- base vector and CSR matrix -- as contiguous float64 / int32 / int32 /
+    float64 arrays; None (no such group) passes."""
+    if g is None:
+        return None
+    return (np.ascontiguousarray(g[0], np.float64), np.ascontiguousarray(g[1], np.int32), np.ascontiguousarray(g[2], np.int32),
+            np.ascontiguousarray(g[3], np.float64))
+
+
+def _affine_eval(group, v):
+    """base + M v for the rows of v [B, columns]: [B, rows].  Row r: acc = base[r], then for every stored entry t of the row, in stored
+    order, acc = acc + (val[t] * v[col[t]]) -- the product and the sum each rounded to float64 (numpy has no fused multiply-add).  This
+    is the rounding order every map keeps on the GPU; the evaluate() of all five map classes is this function."""
+    base, rowptr, col, val = group
+    acc = np.repeat(base[None, :], v.shape[0], axis=0)
+    length = np.diff(rowptr)
+    for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
+        rows = np.nonzero(length > j)[0]
+        t = rowptr[rows] + j
+        acc[:, rows] = acc[:, rows] + val[t][None, :] * v[:, col[t]]
+    return acc
+
+
+def _affine_ptr(group, rows, who, what, fits=True):
+    """One group as (keep-alive objects, C pointer to eicos_affine_map), (None, None) for None.  The array sizes are checked here --
+    ValueError `who`base[..], rowptr[..], col[..], val[..] do not describe `what`, also when the caller's own condition `fits` fails --,
+    their contents (row pointers, column range, what the pattern and the handle must have) by the library."""
+    if group is None:
+        return None, None
+    base, rowptr, col, val = group
+    if not fits or base.size != rows or rowptr.size != rows + 1 or col.size != val.size or rowptr[-1] > col.size:
+        raise ValueError(f"{who}base[{base.size}], rowptr[{rowptr.size}], col[{col.size}], val[{val.size}] do not describe {what}")
+    one = np.zeros(1)
+    m = AffineMap(_dp(base if base.size else one), _ip(rowptr), _ip(col if col.size else np.zeros(1, np.int32)), _dp(val if val.size else one))
+    return (m, one), C.pointer(m)
+
+
+def _affine_ptrs(groups):
+    """_affine_ptr over (group, rows, who, what) tuples: (keep-alive objects, [C pointer or None per group])."""
+    pairs = [_affine_ptr(*g) for g in groups]
+    return [k for k, _ in pairs], [p for _, p in pairs]
+
+
 class ParamMap:
     """Right-hand sides affine in a parameter row theta of length k: c = c0 + C theta, h = h0 + H theta, b = b0 + B theta.  Per group
     `(base, rowptr, col, val)` -- base vector and CSR matrix with k columns -- or None: that group is not parametric (an update keeps it).
@@ -322,53 +365,21 @@ class ParamMap:
 
     def __init__(self, k: int, c=None, h=None, b=None):
         self.k = int(k)
-        self.c, self.h, self.b = (None if g is None else (np.ascontiguousarray(g[0], np.float64), np.ascontiguousarray(g[1], np.int32),
-                                                          np.ascontiguousarray(g[2], np.int32), np.ascontiguousarray(g[3], np.float64))
-                                  for g in (c, h, b))
+        self.c, self.h, self.b = _as_group(c), _as_group(h), _as_group(b)
 
     def groups(self):
         return self.c, self.h, self.b
 
     def evaluate(self, theta):
-        """(c, h, b) for theta [B, k]: arrays [B, rows], None for a group without a map.  Row r: acc = base[r], then for every stored entry
-        t of the row, in stored order, acc = acc + (val[t] * theta[col[t]]) -- the product and the sum each rounded to float64 (numpy
-        has no fused multiply-add), which is the order of eicos_batch_update_param."""
-        theta = np.ascontiguousarray(theta, dtype=np.float64)
-        if theta.ndim != 2 or theta.shape[1] != self.k:
-            raise ValueError(f"theta has shape {theta.shape}, expected [count, {self.k}]")
-        out = []
-        for g in self.groups():
-            if g is None:
-                out.append(None)
-                continue
-            base, rowptr, col, val = g
-            acc = np.repeat(base[None, :], theta.shape[0], axis=0)
-            length = np.diff(rowptr)
-            for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
-                rows = np.nonzero(length > j)[0]
-                t = rowptr[rows] + j
-                acc[:, rows] = acc[:, rows] + val[t][None, :] * theta[:, col[t]]
-            out.append(acc)
-        return tuple(out)
+        """(c, h, b) for theta [B, k]: arrays [B, rows], None for a group without a map, in the order of eicos_batch_update_param
+        (_affine_eval)."""
+        theta = _theta_rows(theta, self.k, None)[0]
+        return tuple(None if g is None else _affine_eval(g, theta) for g in self.groups())
 
 
 def _param_map_ptrs(pmap, pat):
-    """A ParamMap as (keep-alive structs, [c, h, b] as C pointers to eicos_affine_map or None); array sizes are checked here, their
-    contents (row pointers, column range, group present in the pattern) by the library."""
-    keep, ptrs = [], []
-    for name, g, rows in zip("chb", pmap.groups(), (pat.n, pat.m, pat.p)):
-        if g is None:
-            ptrs.append(None)
-            continue
-        base, rowptr, col, val = g
-        if base.size != rows or rowptr.size != rows + 1 or col.size != val.size or (rowptr.size and rowptr[-1] > col.size):
-            raise ValueError(f"parameter map of {name}: base[{base.size}], rowptr[{rowptr.size}], col[{col.size}], val[{val.size}] "
-                             f"do not describe {rows} rows")
-        one = np.zeros(1)
-        m = AffineMap(_dp(base if base.size else one), _ip(rowptr), _ip(col if col.size else np.zeros(1, np.int32)), _dp(val if val.size else one))
-        keep.append((m, one))
-        ptrs.append(C.pointer(m))
-    return keep, ptrs
+    """A ParamMap as (keep-alive structs, [c, h, b] as C pointers to eicos_affine_map or None)."""
+    return _affine_ptrs((g, rows, f"parameter map of {name}: ", f"{rows} rows") for name, g, rows in zip("chb", pmap.groups(), (pat.n, pat.m, pat.p)))
 
 
 class OutputMap:
@@ -378,36 +389,21 @@ class OutputMap:
 
     def __init__(self, n: int, u):
         self.n = int(n)
-        self.base, self.rowptr, self.col, self.val = (np.ascontiguousarray(u[0], np.float64), np.ascontiguousarray(u[1], np.int32),
-                                                      np.ascontiguousarray(u[2], np.int32), np.ascontiguousarray(u[3], np.float64))
+        self.base, self.rowptr, self.col, self.val = _as_group(u)
         self.r = int(self.base.size)
 
     def evaluate(self, x):
-        """u [B, r] for x [B, n].  Row `row`: acc = base[row], then for every stored entry t of the row, in stored order,
-        acc = acc + (val[t] * x[col[t]]) -- the product and the sum each rounded to float64 (numpy has no fused multiply-add), which is
-        the order of eicos_batch_outputs."""
+        """u [B, r] for x [B, n], in the order of eicos_batch_outputs (_affine_eval)."""
         x = np.ascontiguousarray(x, dtype=np.float64)
         if x.ndim != 2 or x.shape[1] != self.n:
             raise ValueError(f"x has shape {x.shape}, expected [count, {self.n}]")
-        acc = np.repeat(self.base[None, :], x.shape[0], axis=0)
-        length = np.diff(self.rowptr)
-        for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
-            rows = np.nonzero(length > j)[0]
-            t = self.rowptr[rows] + j
-            acc[:, rows] = acc[:, rows] + self.val[t][None, :] * x[:, self.col[t]]
-        return acc
+        return _affine_eval((self.base, self.rowptr, self.col, self.val), x)
 
 
 def _output_map_ptr(omap, pat):
-    """An OutputMap as (keep-alive objects, C pointer to eicos_affine_map); array sizes are checked here, their contents (row pointers,
-    column range) by the library."""
-    base, rowptr, col, val = omap.base, omap.rowptr, omap.col, omap.val
-    if omap.n != pat.n or rowptr.size != omap.r + 1 or col.size != val.size or rowptr[-1] > col.size:
-        raise ValueError(f"output map: n = {omap.n}, base[{base.size}], rowptr[{rowptr.size}], col[{col.size}], val[{val.size}] do not "
-                         f"describe {omap.r} rows over {pat.n} variables")
-    one = np.zeros(1)
-    m = AffineMap(_dp(base if base.size else one), _ip(rowptr), _ip(col if col.size else np.zeros(1, np.int32)), _dp(val if val.size else one))
-    return (m, one), C.pointer(m)
+    """An OutputMap as (keep-alive objects, C pointer to eicos_affine_map)."""
+    return _affine_ptr((omap.base, omap.rowptr, omap.col, omap.val), omap.r, f"output map: n = {omap.n}, ",
+                       f"{omap.r} rows over {pat.n} variables", omap.n == pat.n)
 
 
 class PlantMap:
@@ -417,42 +413,26 @@ class PlantMap:
 
     def __init__(self, k: int, r: int, f):
         self.k, self.r = int(k), int(r)
-        self.base, self.rowptr, self.col, self.val = (np.ascontiguousarray(f[0], np.float64), np.ascontiguousarray(f[1], np.int32),
-                                                      np.ascontiguousarray(f[2], np.int32), np.ascontiguousarray(f[3], np.float64))
+        self.base, self.rowptr, self.col, self.val = _as_group(f)
 
     def evaluate(self, theta, u, w=None):
-        """theta+ [B, k] for theta [B, k], u [B, r] and, optionally, the disturbance w [B, k].  Row j: acc = base[j], then for every
-        stored entry s of the row, in stored order, acc = acc + (val[s] * z[col[s]]) with z = [theta | u], then acc = acc + w[j] -- the
-        product and every sum each rounded to float64 (numpy has no fused multiply-add), which is the order of eicos_batch_rollout."""
-        theta, u = np.ascontiguousarray(theta, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
-        if theta.ndim != 2 or theta.shape[1] != self.k:
-            raise ValueError(f"theta has shape {theta.shape}, expected [count, {self.k}]")
+        """theta+ [B, k] for theta [B, k], u [B, r] and, optionally, the disturbance w [B, k]: the map over z = [theta | u]
+        (_affine_eval), then acc = acc + w[j], one more rounded sum -- the order of eicos_batch_rollout."""
+        theta, u = _theta_rows(theta, self.k, None)[0], np.ascontiguousarray(u, dtype=np.float64)
         if u.shape != (theta.shape[0], self.r):
             raise ValueError(f"u has shape {u.shape}, expected [{theta.shape[0]}, {self.r}]")
         if w is not None:
             w = np.ascontiguousarray(w, dtype=np.float64)
             if w.shape != theta.shape:
                 raise ValueError(f"w has shape {w.shape}, expected {theta.shape}")
-        z = np.concatenate((theta, u), axis=1)
-        acc = np.repeat(self.base[None, :], z.shape[0], axis=0)
-        length = np.diff(self.rowptr)
-        for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
-            rows = np.nonzero(length > j)[0]
-            t = self.rowptr[rows] + j
-            acc[:, rows] = acc[:, rows] + self.val[t][None, :] * z[:, self.col[t]]
+        acc = _affine_eval((self.base, self.rowptr, self.col, self.val), np.concatenate((theta, u), axis=1))
         return acc if w is None else acc + w
 
 
 def _plant_map_ptr(fmap, k, r):
-    """A PlantMap as (keep-alive objects, C pointer to eicos_affine_map) for a handle with k parameters and r outputs; array sizes are
-    checked here, their contents (row pointers, column range) by the library."""
-    base, rowptr, col, val = fmap.base, fmap.rowptr, fmap.col, fmap.val
-    if fmap.k != k or fmap.r != r or base.size != k or rowptr.size != k + 1 or col.size != val.size or rowptr[-1] > col.size:
-        raise ValueError(f"plant map: k = {fmap.k}, r = {fmap.r}, base[{base.size}], rowptr[{rowptr.size}], col[{col.size}], val[{val.size}] "
-                         f"do not describe {k} rows over {k} parameters and {r} outputs")
-    one = np.zeros(1)
-    m = AffineMap(_dp(base if base.size else one), _ip(rowptr), _ip(col if col.size else np.zeros(1, np.int32)), _dp(val if val.size else one))
-    return (m, one), C.pointer(m)
+    """A PlantMap as (keep-alive objects, C pointer to eicos_affine_map) for a handle with k parameters and r outputs."""
+    return _affine_ptr((fmap.base, fmap.rowptr, fmap.col, fmap.val), k, f"plant map: k = {fmap.k}, r = {fmap.r}, ",
+                       f"{k} rows over {k} parameters and {r} outputs", fmap.k == k and fmap.r == r)
 
 
 class MatrixMap:
@@ -463,53 +443,21 @@ class MatrixMap:
 
     def __init__(self, k: int, G=None, A=None):
         self.k = int(k)
-        self.G, self.A = (None if g is None else (np.ascontiguousarray(g[0], np.float64), np.ascontiguousarray(g[1], np.int32),
-                                                  np.ascontiguousarray(g[2], np.int32), np.ascontiguousarray(g[3], np.float64))
-                          for g in (G, A))
+        self.G, self.A = _as_group(G), _as_group(A)
 
     def groups(self):
         return self.G, self.A
 
     def evaluate(self, theta):
-        """(Gpr, Apr) for theta [B, k]: arrays [B, nnz], None for a matrix without a map.  Entry e: acc = base[e], then for every stored
-        entry t of row e, in stored order, acc = acc + (val[t] * theta[col[t]]) -- the product and the sum each rounded to float64
-        (numpy has no fused multiply-add), which is the order of eicos_batch_set_matrix_map."""
-        theta = np.ascontiguousarray(theta, dtype=np.float64)
-        if theta.ndim != 2 or theta.shape[1] != self.k:
-            raise ValueError(f"theta has shape {theta.shape}, expected [count, {self.k}]")
-        out = []
-        for g in self.groups():
-            if g is None:
-                out.append(None)
-                continue
-            base, rowptr, col, val = g
-            acc = np.repeat(base[None, :], theta.shape[0], axis=0)
-            length = np.diff(rowptr)
-            for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
-                rows = np.nonzero(length > j)[0]
-                t = rowptr[rows] + j
-                acc[:, rows] = acc[:, rows] + val[t][None, :] * theta[:, col[t]]
-            out.append(acc)
-        return tuple(out)
+        """(Gpr, Apr) for theta [B, k]: arrays [B, nnz], None for a matrix without a map, in the order of eicos_batch_set_matrix_map
+        (_affine_eval)."""
+        theta = _theta_rows(theta, self.k, None)[0]
+        return tuple(None if g is None else _affine_eval(g, theta) for g in self.groups())
 
 
 def _matrix_map_ptrs(mmap, nnzG, nnzA):
-    """A MatrixMap as (keep-alive structs, [G, A] as C pointers to eicos_affine_map or None); array sizes are checked here, their
-    contents (row pointers, column range, matrix present in the pattern, the parameter map it needs) by the library."""
-    keep, ptrs = [], []
-    for name, g, rows in zip("GA", mmap.groups(), (nnzG, nnzA)):
-        if g is None:
-            ptrs.append(None)
-            continue
-        base, rowptr, col, val = g
-        if base.size != rows or rowptr.size != rows + 1 or col.size != val.size or (rowptr.size and rowptr[-1] > col.size):
-            raise ValueError(f"matrix map of {name}: base[{base.size}], rowptr[{rowptr.size}], col[{col.size}], val[{val.size}] "
-                             f"do not describe {rows} stored values")
-        one = np.zeros(1)
-        m = AffineMap(_dp(base if base.size else one), _ip(rowptr), _ip(col if col.size else np.zeros(1, np.int32)), _dp(val if val.size else one))
-        keep.append((m, one))
-        ptrs.append(C.pointer(m))
-    return keep, ptrs
+    """A MatrixMap as (keep-alive structs, [G, A] as C pointers to eicos_affine_map or None)."""
+    return _affine_ptrs((g, rows, f"matrix map of {name}: ", f"{rows} stored values") for name, g, rows in zip("GA", mmap.groups(), (nnzG, nnzA)))
 
 
 class ShiftMap:
@@ -520,9 +468,7 @@ class ShiftMap:
 
     def __init__(self, n: int, p: int, m: int, x=None, y=None, z=None, s=None):
         self.n, self.p, self.m = int(n), int(p), int(m)
-        self.x, self.y, self.z, self.s = (None if g is None else (np.ascontiguousarray(g[0], np.float64), np.ascontiguousarray(g[1], np.int32),
-                                                                  np.ascontiguousarray(g[2], np.int32), np.ascontiguousarray(g[3], np.float64))
-                                          for g in (x, y, z, s))
+        self.x, self.y, self.z, self.s = _as_group(x), _as_group(y), _as_group(z), _as_group(s)
 
     @classmethod
     def from_sources(cls, n: int, p: int, m: int, x_src=None, y_src=None, z_src=None, s_src=None):
@@ -544,10 +490,8 @@ class ShiftMap:
         return self.n, self.p, self.m, self.m
 
     def evaluate(self, x=None, y=None, z=None, s=None):
-        """(x', y', z', s') for vectors [B, rows]: a group without a map (or not given) comes back as it was passed.  Row j:
-        acc = base[j], then for every stored entry t of the row, in stored order, acc = acc + (val[t] * v[col[t]]) with v the group's
-        vector BEFORE the shift -- the product and the sum each rounded to float64 (numpy has no fused multiply-add), which is the order
-        of eicos_batch_set_shift_map."""
+        """(x', y', z', s') for vectors [B, rows]: a group without a map (or not given) comes back as it was passed; a mapped one goes
+        through its map as it was BEFORE the shift, in the order of eicos_batch_set_shift_map (_affine_eval)."""
         out = []
         for name, g, rows, v in zip("xyzs", self.groups(), self.rows(), (x, y, z, s)):
             if g is None or v is None:
@@ -556,36 +500,15 @@ class ShiftMap:
             v = np.ascontiguousarray(v, dtype=np.float64)
             if v.ndim != 2 or v.shape[1] != rows:
                 raise ValueError(f"{name} has shape {v.shape}, expected [count, {rows}]")
-            base, rowptr, col, val = g
-            acc = np.repeat(base[None, :], v.shape[0], axis=0)
-            length = np.diff(rowptr)
-            for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
-                r = np.nonzero(length > j)[0]
-                t = rowptr[r] + j
-                acc[:, r] = acc[:, r] + val[t][None, :] * v[:, col[t]]
-            out.append(acc)
+            out.append(_affine_eval(g, v))
         return tuple(out)
 
 
 def _shift_map_ptrs(smap, pat):
-    """A ShiftMap as (keep-alive structs, [x, y, z, s] as C pointers to eicos_affine_map or None); array sizes are checked here, their
-    contents (row pointers, column range, group present in the pattern) by the library."""
+    """A ShiftMap as (keep-alive structs, [x, y, z, s] as C pointers to eicos_affine_map or None)."""
     if (smap.n, smap.p, smap.m) != (pat.n, pat.p, pat.m):
         raise ValueError(f"shift map: built for (n, p, m) = ({smap.n}, {smap.p}, {smap.m}), the pattern has ({pat.n}, {pat.p}, {pat.m})")
-    keep, ptrs = [], []
-    for name, g, rows in zip("xyzs", smap.groups(), smap.rows()):
-        if g is None:
-            ptrs.append(None)
-            continue
-        base, rowptr, col, val = g
-        if base.size != rows or rowptr.size != rows + 1 or col.size != val.size or (rowptr.size and rowptr[-1] > col.size):
-            raise ValueError(f"shift map of {name}: base[{base.size}], rowptr[{rowptr.size}], col[{col.size}], val[{val.size}] "
-                             f"do not describe {rows} rows")
-        one = np.zeros(1)
-        m = AffineMap(_dp(base if base.size else one), _ip(rowptr), _ip(col if col.size else np.zeros(1, np.int32)), _dp(val if val.size else one))
-        keep.append((m, one))
-        ptrs.append(C.pointer(m))
-    return keep, ptrs
+    return _affine_ptrs((g, rows, f"shift map of {name}: ", f"{rows} rows") for name, g, rows in zip("xyzs", smap.groups(), smap.rows()))
 
 
 def _disturbance(w, count, steps, k):

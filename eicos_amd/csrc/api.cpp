@@ -29,6 +29,7 @@
 #include "tiles.hpp"
 #include "envknob.hpp"
 #include "internal.hpp"
+#include "affine_pack.hpp"
 
 using namespace eicos;
 // Workgroups per CU for a batch, at most `max_r`: the cheapest estimate of the launch's duration wins.
@@ -125,7 +126,7 @@ struct eicos_batch {
     // output map (eicos_batch_set_output_map): one device allocation [OutMapDev | u rows of the batch | base, val | rowptr, col], out.r = 0
     // while none is installed; d_u = the [batch][r] rows the range kernel fills for a host destination
     OutMapDev out{}; void *d_out = nullptr; double *d_u = nullptr;
-    // plant map (eicos_batch_set_plant_map): one device allocation [MAP_HEADER | base, val | rowptr, col], plant.k = 0 while none is installed
+    // plant map (eicos_batch_set_plant_map): one device allocation [PlantMapDev (MAP_HEADER bytes) | base, val | rowptr, col], plant.k = 0 while none is installed
     PlantMapDev plant{}; void *d_plant = nullptr;
     // rollout (eicos_batch_rollout): one device allocation, grown on demand: [RolloutDev (MAP_HEADER bytes) | theta, u, w trajectories | two
     // theta rows of the batch (the path that is not fused) | codes, iters]; roll = the host copy of the record of the most recent call
@@ -969,6 +970,37 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
     return EICOS_OK;
 }
 
+// ---- affine maps (no reference counterpart): parameter, output, plant, matrix and shift map through one path ----
+// A setter states its own preconditions and its groups (affine_pack.hpp: AffineGroup); affine_fault validates a group, install_map packs
+// the groups into ONE device allocation [descriptor (MAP_HEADER bytes) | gap | base, val per group | rowptr, col per group] and swaps it
+// for the one in the handle.  A later call replaces a map; DESIGN.md, "Affine maps: one path".
+static constexpr size_t MAP_HEADER = 128; // bytes kept for the descriptor in front of a map's arrays (keeps the doubles aligned)
+static_assert(sizeof(ParamMapDev) <= MAP_HEADER && sizeof(OutMapDev) <= MAP_HEADER && sizeof(PlantMapDev) <= MAP_HEADER &&
+              sizeof(RolloutDev) <= MAP_HEADER && sizeof(MatrixMapDev) <= MAP_HEADER && sizeof(ShiftMapDev) <= MAP_HEADER,
+              "map descriptor larger than its header");
+
+// The map in `slot` (its device allocation) and `cur` (the handle's copy of its descriptor) goes away; M != NULL: the n validated groups
+// g take its place -- *M is the new descriptor and `out` its AffineDev array of n, filled here; `gap` bytes behind the header stay
+// uninitialised (the output map's u rows).
+template <class Desc>
+static int install_map(eicos_batch *h, void *&slot, Desc &cur, const char *name, const AffineGroup *g, int n, size_t gap, Desc *M, AffineDev *out) {
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
+    if (slot) { (void)hipFree(slot); slot = nullptr; }
+    cur = Desc{};
+    if (!M) return EICOS_OK;
+    const AffineLayout lay = affine_layout(g, n, MAP_HEADER, gap);
+    void *dev = nullptr;
+    HIP_TRY(hipMalloc(&dev, lay.bytes()));
+    std::vector<char> image = affine_pack(g, n, lay, dev, out);
+    std::memcpy(image.data(), M, sizeof *M);
+    char *dc = static_cast<char *>(dev);
+    hipError_t e = hipMemcpy(dc, image.data(), gap ? MAP_HEADER : image.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && gap) e = hipMemcpy(dc + MAP_HEADER + gap, image.data() + MAP_HEADER, image.size() - MAP_HEADER, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the ") + name + " map: " + hipGetErrorString(e)); }
+    slot = dev; cur = *M;
+    return EICOS_OK;
+}
 
 extern "C" {
 
@@ -1669,64 +1701,25 @@ int eicos_batch_set_iterate_device(eicos_batch *h, int first, int count, const d
     return rc != EICOS_OK ? rc : update_in_place(in, 0);
 }
 
-// ---- parametric right-hand sides: c, h, b affine in a short parameter row theta (no reference counterpart) ----
-// The map is validated on the host, packed into ONE device allocation ([doubles: base, val per group | ints: rowptr, col per group]) and
-// handed to the range kernel by value (ParamMapDev); the allocation starts with a copy of that descriptor, which the fused step reads
-// through a pointer.  A later call replaces the map, all groups NULL or k = 0 removes it.
-static constexpr size_t MAP_HEADER = 128; // bytes kept for the descriptor in front of a map's arrays (keeps the doubles aligned)
-static_assert(sizeof(ParamMapDev) <= MAP_HEADER && sizeof(OutMapDev) <= MAP_HEADER && sizeof(RolloutDev) <= MAP_HEADER, "map descriptor larger than its header");
+// ---- parametric right-hand sides: c, h, b affine in a short parameter row theta (an affine map: install_map, above) ----
+// The range kernel takes the descriptor by value, the fused
+// step reads its device copy through a pointer.  All groups NULL or k = 0 removes the map.
 int eicos_batch_set_param_map(eicos_batch *h, int k, const eicos_affine_map *c, const eicos_affine_map *hh, const eicos_affine_map *b) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     if (k < 0) return fail(EICOS_E_INVALID, "parameter map: k must not be negative");
     const DevPat &D = h->dp;
-    const eicos_affine_map *g[3] = {c, hh, b};
-    const int rows[3] = {D.n, D.m, D.p};
-    const char *name[3] = {"c", "h", "b"};
+    const AffineGroup g[3] = {{c, D.n, k, "parameter map of c: ", "[0, k)"}, {hh, D.m, k, "parameter map of h: ", "[0, k)"},
+                              {b, D.p, k, "parameter map of b: ", "[0, k)"}};
     const bool remove = k == 0 || (!c && !hh && !b);
-    size_t nd = 0, ni = 0;
+    std::string msg;
     for (int q = 0; q < 3 && !remove; q++) {
-        if (!g[q]) continue;
-        const std::string who = std::string("parameter map of ") + name[q] + ": ";
-        if (rows[q] == 0) return fail(EICOS_E_INVALID, who + "the pattern has no such group (its size is 0)");
-        if (!g[q]->base || !g[q]->rowptr) return fail(EICOS_E_INVALID, who + "base or rowptr is NULL");
-        const int *rp = g[q]->rowptr;
-        if (rp[0] != 0) return fail(EICOS_E_INVALID, who + "rowptr[0] must be 0");
-        for (int r = 0; r < rows[q]; r++)
-            if (rp[r + 1] < rp[r]) return fail(EICOS_E_INVALID, who + "rowptr decreases at row " + std::to_string(r));
-        const int nnz = rp[rows[q]];
-        if (nnz > 0 && (!g[q]->col || !g[q]->val)) return fail(EICOS_E_INVALID, who + "col or val is NULL");
-        for (int t = 0; t < nnz; t++)
-            if (g[q]->col[t] < 0 || g[q]->col[t] >= k) return fail(EICOS_E_INVALID, who + "column " + std::to_string(g[q]->col[t]) + " of entry " + std::to_string(t) + " is outside [0, k)");
-        nd += (size_t)rows[q] + nnz; ni += (size_t)rows[q] + 1 + nnz;
+        if (!g[q].map) continue;
+        if (g[q].rows == 0) return fail(EICOS_E_INVALID, g[q].who + "the pattern has no such group (its size is 0)");
+        if (affine_fault(g[q], msg)) return fail(EICOS_E_INVALID, msg);
     }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream)); // (an update in flight may still read the map that goes away)
-    if (h->d_param) { (void)hipFree(h->d_param); h->d_param = nullptr; }
-    h->param = ParamMapDev{};
-    if (remove) return EICOS_OK;
-    std::vector<char> buf(MAP_HEADER + nd * sizeof(double) + ni * sizeof(int));
-    double *hd_ = reinterpret_cast<double *>(buf.data() + MAP_HEADER);
-    int *hi_ = reinterpret_cast<int *>(buf.data() + MAP_HEADER + nd * sizeof(double));
-    void *dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, buf.size()));
-    const double *dd = reinterpret_cast<const double *>(static_cast<const char *>(dev) + MAP_HEADER);
-    const int *di = reinterpret_cast<const int *>(static_cast<const char *>(dev) + MAP_HEADER + nd * sizeof(double));
     ParamMapDev M{};
     M.k = k;
-    size_t od = 0, oi = 0;
-    for (int q = 0; q < 3; q++) {
-        if (!g[q]) continue;
-        const int nnz = g[q]->rowptr[rows[q]];
-        M.g[q].base = dd + od; std::copy(g[q]->base, g[q]->base + rows[q], hd_ + od); od += rows[q];
-        M.g[q].val = dd + od; if (nnz) std::copy(g[q]->val, g[q]->val + nnz, hd_ + od); od += nnz;
-        M.g[q].rowptr = di + oi; std::copy(g[q]->rowptr, g[q]->rowptr + rows[q] + 1, hi_ + oi); oi += rows[q] + 1;
-        M.g[q].col = di + oi; if (nnz) std::copy(g[q]->col, g[q]->col + nnz, hi_ + oi); oi += nnz;
-    }
-    std::memcpy(buf.data(), &M, sizeof M);
-    const hipError_t e = hipMemcpy(dev, buf.data(), buf.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the parameter map: ") + hipGetErrorString(e)); }
-    h->d_param = dev; h->param = M;
-    return EICOS_OK;
+    return install_map(h, h->d_param, h->param, "parameter", g, 3, 0, remove ? nullptr : &M, M.g);
 }
 
 int eicos_batch_param_count(eicos_batch *h) { return h ? h->param.k : fail(EICOS_E_INVALID, "NULL handle"); }
@@ -1748,54 +1741,24 @@ int eicos_batch_update_param_device(eicos_batch *h, int first, int count, const 
     return rc != EICOS_OK ? rc : update_in_place(in, 0);
 }
 
-// ---- output map: u = u0 + U x, the few numbers of x a controller applies (no reference counterpart) ----
-// Validated like the parameter map and packed into ONE device allocation: [OutMapDev (MAP_HEADER bytes) | u rows of the batch | base, val |
-// rowptr, col].  The range kernel takes the descriptor by value, the fused step through a pointer to its device copy.
+// ---- output map: u = u0 + U x, the few numbers of x a controller applies ----
+// The allocation keeps the u rows of the batch between the descriptor and the arrays (d_u: what the range kernel fills for a host
+// destination).  The range kernel takes the descriptor by value, the fused step through a pointer to its device copy.
 int eicos_batch_set_output_map(eicos_batch *h, int r, const eicos_affine_map *u) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     if (r < 0) return fail(EICOS_E_INVALID, "output map: r must not be negative");
-    const DevPat &D = h->dp;
+    const AffineGroup g = {u, r, h->dp.n, "output map: ", "[0, n)"};
     const bool remove = r == 0 || !u;
-    int nnz = 0;
+    std::string msg;
     if (!remove) {
-        const std::string who = "output map: ";
-        if (D.n == 0) return fail(EICOS_E_INVALID, who + "the pattern has no variables (n = 0)");
-        if (!u->base || !u->rowptr) return fail(EICOS_E_INVALID, who + "base or rowptr is NULL");
-        const int *rp = u->rowptr;
-        if (rp[0] != 0) return fail(EICOS_E_INVALID, who + "rowptr[0] must be 0");
-        for (int q = 0; q < r; q++)
-            if (rp[q + 1] < rp[q]) return fail(EICOS_E_INVALID, who + "rowptr decreases at row " + std::to_string(q));
-        nnz = rp[r];
-        if (nnz > 0 && (!u->col || !u->val)) return fail(EICOS_E_INVALID, who + "col or val is NULL");
-        for (int t = 0; t < nnz; t++)
-            if (u->col[t] < 0 || u->col[t] >= D.n) return fail(EICOS_E_INVALID, who + "column " + std::to_string(u->col[t]) + " of entry " + std::to_string(t) + " is outside [0, n)");
+        if (h->dp.n == 0) return fail(EICOS_E_INVALID, g.who + "the pattern has no variables (n = 0)");
+        if (affine_fault(g, msg)) return fail(EICOS_E_INVALID, msg);
     }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
-    if (h->d_out) { (void)hipFree(h->d_out); h->d_out = nullptr; }
-    h->out = OutMapDev{}; h->d_u = nullptr;
-    if (remove) return EICOS_OK;
-    const size_t rows_b = (size_t)h->batch * r * sizeof(double), nd = (size_t)r + nnz, ni = (size_t)r + 1 + nnz;
-    std::vector<char> buf(MAP_HEADER + nd * sizeof(double) + ni * sizeof(int)); // (everything but the u rows, which stay uninitialised)
-    void *dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, MAP_HEADER + rows_b + nd * sizeof(double) + ni * sizeof(int)));
-    char *dc = static_cast<char *>(dev);
-    const double *dd = reinterpret_cast<const double *>(dc + MAP_HEADER + rows_b);
-    const int *di = reinterpret_cast<const int *>(dc + MAP_HEADER + rows_b + nd * sizeof(double));
-    double *hd_ = reinterpret_cast<double *>(buf.data() + MAP_HEADER);
-    int *hi_ = reinterpret_cast<int *>(buf.data() + MAP_HEADER + nd * sizeof(double));
     OutMapDev M{};
     M.r = r;
-    M.a.base = dd; std::copy(u->base, u->base + r, hd_);
-    M.a.val = dd + r; if (nnz) std::copy(u->val, u->val + nnz, hd_ + r);
-    M.a.rowptr = di; std::copy(u->rowptr, u->rowptr + r + 1, hi_);
-    M.a.col = di + r + 1; if (nnz) std::copy(u->col, u->col + nnz, hi_ + r + 1);
-    std::memcpy(buf.data(), &M, sizeof M);
-    hipError_t e = hipMemcpy(dc, buf.data(), MAP_HEADER, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dc + MAP_HEADER + rows_b, buf.data() + MAP_HEADER, buf.size() - MAP_HEADER, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the output map: ") + hipGetErrorString(e)); }
-    h->d_out = dev; h->out = M; h->d_u = reinterpret_cast<double *>(dc + MAP_HEADER);
-    return EICOS_OK;
+    const int rc = install_map(h, h->d_out, h->out, "output", &g, 1, (size_t)h->batch * r * sizeof(double), remove ? nullptr : &M, &M.a);
+    h->d_u = h->d_out ? reinterpret_cast<double *>(static_cast<char *>(h->d_out) + MAP_HEADER) : nullptr;
+    return rc;
 }
 
 int eicos_batch_output_count(eicos_batch *h) { return h ? h->out.r : fail(EICOS_E_INVALID, "NULL handle"); }
@@ -2077,173 +2040,67 @@ int eicos_batch_update_param_solve(eicos_batch *h, const double *theta, double *
     return update_solve(h, nullptr, nullptr, nullptr, nullptr, nullptr, theta, u_out, x_out, exitcodes, STEP_PARAM);
 }
 
-// ---- plant map and rollout: theta+ = f0 + F [theta | u] (+ w), and `steps` closed-loop steps in one call (no reference counterpart) ----
-// The map is validated like the other two and packed into ONE device allocation: [MAP_HEADER bytes, unused | base, val | rowptr, col]; it
-// reaches the kernels inside the rollout's record (RolloutDev), by value in the range kernel and through a pointer in the fused launch.
+// ---- plant map and rollout: theta+ = f0 + F [theta | u] (+ w), and `steps` closed-loop steps in one call ----
+// The map reaches the kernels inside the rollout's record (RolloutDev), by value in the range kernel and through a pointer in the fused
+// launch; k, r = the parameter and output counts installed NOW, which it is validated for.
 int eicos_batch_set_plant_map(eicos_batch *h, const eicos_affine_map *f) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     const int k = h->param.k, r = h->out.r;
-    int nnz = 0;
+    const AffineGroup g = {f, k, k + r, "plant map: ", "[0, k + r)"};
+    std::string msg;
     if (f) {
-        const std::string who = "plant map: ";
-        if (k == 0) return fail(EICOS_E_INVALID, who + "no parameter map (eicos_batch_set_param_map installs one)");
-        if (r == 0) return fail(EICOS_E_INVALID, who + "no output map (eicos_batch_set_output_map installs one)");
-        if (!f->base || !f->rowptr) return fail(EICOS_E_INVALID, who + "base or rowptr is NULL");
-        const int *rp = f->rowptr;
-        if (rp[0] != 0) return fail(EICOS_E_INVALID, who + "rowptr[0] must be 0");
-        for (int q = 0; q < k; q++)
-            if (rp[q + 1] < rp[q]) return fail(EICOS_E_INVALID, who + "rowptr decreases at row " + std::to_string(q));
-        nnz = rp[k];
-        if (nnz > 0 && (!f->col || !f->val)) return fail(EICOS_E_INVALID, who + "col or val is NULL");
-        for (int t = 0; t < nnz; t++)
-            if (f->col[t] < 0 || f->col[t] >= k + r) return fail(EICOS_E_INVALID, who + "column " + std::to_string(f->col[t]) + " of entry " + std::to_string(t) + " is outside [0, k + r)");
+        if (k == 0) return fail(EICOS_E_INVALID, g.who + "no parameter map (eicos_batch_set_param_map installs one)");
+        if (r == 0) return fail(EICOS_E_INVALID, g.who + "no output map (eicos_batch_set_output_map installs one)");
+        if (affine_fault(g, msg)) return fail(EICOS_E_INVALID, msg);
     }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
-    if (h->d_plant) { (void)hipFree(h->d_plant); h->d_plant = nullptr; }
-    h->plant = PlantMapDev{};
-    if (!f) return EICOS_OK;
-    const size_t nd = (size_t)k + nnz, ni = (size_t)k + 1 + nnz;
-    std::vector<char> buf(MAP_HEADER + nd * sizeof(double) + ni * sizeof(int));
-    double *hd_ = reinterpret_cast<double *>(buf.data() + MAP_HEADER);
-    int *hi_ = reinterpret_cast<int *>(buf.data() + MAP_HEADER + nd * sizeof(double));
-    void *dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, buf.size()));
-    const double *dd = reinterpret_cast<const double *>(static_cast<const char *>(dev) + MAP_HEADER);
-    const int *di = reinterpret_cast<const int *>(static_cast<const char *>(dev) + MAP_HEADER + nd * sizeof(double));
     PlantMapDev M{};
     M.k = k; M.r = r;
-    M.a.base = dd; std::copy(f->base, f->base + k, hd_);
-    M.a.val = dd + k; if (nnz) std::copy(f->val, f->val + nnz, hd_ + k);
-    M.a.rowptr = di; std::copy(f->rowptr, f->rowptr + k + 1, hi_);
-    M.a.col = di + k + 1; if (nnz) std::copy(f->col, f->col + nnz, hi_ + k + 1);
-    const hipError_t e = hipMemcpy(dev, buf.data(), buf.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the plant map: ") + hipGetErrorString(e)); }
-    h->d_plant = dev; h->plant = M;
-    return EICOS_OK;
+    return install_map(h, h->d_plant, h->plant, "plant", &g, 1, 0, f ? &M : nullptr, &M.a);
 }
 
-// ---- matrix map: the stored values of G and A affine in theta (no reference counterpart) ----
-// Validated like the other maps and packed into ONE device allocation of its own: [MatrixMapDev (MAP_HEADER bytes) | base, val | rowptr,
-// col] -- the range path takes the groups by value, the fused step reads the descriptor through a pointer (UpdArgs::mmap).
-static_assert(sizeof(MatrixMapDev) <= MAP_HEADER, "map descriptor larger than its header");
+// ---- matrix map: the stored values of G and A affine in theta ----
+// The range path takes the groups by value, the fused step reads the descriptor through a pointer (UpdArgs::mmap).
 int eicos_batch_set_matrix_map(eicos_batch *h, const eicos_affine_map *G, const eicos_affine_map *A) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     const DevPat &D = h->dp;
     const int k = h->param.k;
-    const eicos_affine_map *g[2] = {G, A};
-    const int rows[2] = {D.nnzG, D.nnzA};
-    const char *name[2] = {"G", "A"};
+    const AffineGroup g[2] = {{G, D.nnzG, k, "matrix map of G: ", "[0, k)"}, {A, D.nnzA, k, "matrix map of A: ", "[0, k)"}};
     const bool remove = !G && !A;
-    size_t nd = 0, ni = 0;
-    for (int q = 0; q < 2 && !remove; q++) {
-        if (!g[q]) continue;
-        const std::string who = std::string("matrix map of ") + name[q] + ": ";
-        if (k == 0) return fail(EICOS_E_INVALID, who + "no parameter map (eicos_batch_set_param_map installs one)");
-        if (rows[q] == 0) return fail(EICOS_E_INVALID, who + "the pattern has no such matrix (it stores no entries)");
-        if (!g[q]->base || !g[q]->rowptr) return fail(EICOS_E_INVALID, who + "base or rowptr is NULL");
-        const int *rp = g[q]->rowptr;
-        if (rp[0] != 0) return fail(EICOS_E_INVALID, who + "rowptr[0] must be 0");
-        for (int r = 0; r < rows[q]; r++)
-            if (rp[r + 1] < rp[r]) return fail(EICOS_E_INVALID, who + "rowptr decreases at row " + std::to_string(r));
-        const int nnz = rp[rows[q]];
-        if (nnz > 0 && (!g[q]->col || !g[q]->val)) return fail(EICOS_E_INVALID, who + "col or val is NULL");
-        for (int t = 0; t < nnz; t++)
-            if (g[q]->col[t] < 0 || g[q]->col[t] >= k) return fail(EICOS_E_INVALID, who + "column " + std::to_string(g[q]->col[t]) + " of entry " + std::to_string(t) + " is outside [0, k)");
-        nd += (size_t)rows[q] + nnz; ni += (size_t)rows[q] + 1 + nnz;
-    }
-    MatrixMapDev M{};
-    M.k = remove ? 0 : k;
-    if (!remove) { // (against the parameter map as it is now; every call that consumes theta checks again: matrix_map_fits)
-        if (G && D.m > 0 && !h->param.g[1].base) return fail(EICOS_E_INVALID, "matrix map of G: the parameter map has no h group (updateData reads h with Gpr)");
-        if (A && D.p > 0 && !h->param.g[2].base) return fail(EICOS_E_INVALID, "matrix map of A: the parameter map has no b group (updateData reads b with Apr)");
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
-    if (h->d_mat) { (void)hipFree(h->d_mat); h->d_mat = nullptr; }
-    h->mat = MatrixMapDev{};
-    if (remove) return EICOS_OK;
-    std::vector<char> buf(MAP_HEADER + nd * sizeof(double) + ni * sizeof(int));
-    double *hd_ = reinterpret_cast<double *>(buf.data() + MAP_HEADER);
-    int *hi_ = reinterpret_cast<int *>(buf.data() + MAP_HEADER + nd * sizeof(double));
-    void *dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, buf.size()));
-    const double *dd = reinterpret_cast<const double *>(static_cast<const char *>(dev) + MAP_HEADER);
-    const int *di = reinterpret_cast<const int *>(static_cast<const char *>(dev) + MAP_HEADER + nd * sizeof(double));
-    size_t od = 0, oi = 0;
+    std::string msg;
     for (int q = 0; q < 2; q++) {
-        if (!g[q]) continue;
-        const int nnz = g[q]->rowptr[rows[q]];
-        M.g[q].base = dd + od; std::copy(g[q]->base, g[q]->base + rows[q], hd_ + od); od += rows[q];
-        M.g[q].val = dd + od; if (nnz) std::copy(g[q]->val, g[q]->val + nnz, hd_ + od); od += nnz;
-        M.g[q].rowptr = di + oi; std::copy(g[q]->rowptr, g[q]->rowptr + rows[q] + 1, hi_ + oi); oi += rows[q] + 1;
-        M.g[q].col = di + oi; if (nnz) std::copy(g[q]->col, g[q]->col + nnz, hi_ + oi); oi += nnz;
+        if (!g[q].map) continue;
+        if (k == 0) return fail(EICOS_E_INVALID, g[q].who + "no parameter map (eicos_batch_set_param_map installs one)");
+        if (g[q].rows == 0) return fail(EICOS_E_INVALID, g[q].who + "the pattern has no such matrix (it stores no entries)");
+        if (affine_fault(g[q], msg)) return fail(EICOS_E_INVALID, msg);
     }
-    std::memcpy(buf.data(), &M, sizeof M);
-    const hipError_t e = hipMemcpy(dev, buf.data(), buf.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the matrix map: ") + hipGetErrorString(e)); }
-    h->d_mat = dev; h->mat = M;
-    return EICOS_OK;
+    // (against the parameter map as it is now; every call that consumes theta checks again: matrix_map_fits)
+    if (G && D.m > 0 && !h->param.g[1].base) return fail(EICOS_E_INVALID, "matrix map of G: the parameter map has no h group (updateData reads h with Gpr)");
+    if (A && D.p > 0 && !h->param.g[2].base) return fail(EICOS_E_INVALID, "matrix map of A: the parameter map has no b group (updateData reads b with Apr)");
+    MatrixMapDev M{};
+    M.k = k;
+    return install_map(h, h->d_mat, h->mat, "matrix", g, 2, 0, remove ? nullptr : &M, M.g);
 }
 
 int eicos_batch_has_matrix_map(eicos_batch *h) {
     return h ? ((h->mat.g[0].base ? 1 : 0) | (h->mat.g[1].base ? 2 : 0)) : fail(EICOS_E_INVALID, "NULL handle");
 }
 
-// ---- shift map: the warm-start vectors x, y, z, s through a square affine map each (no reference counterpart) ----
-// Validated like the other maps and packed into ONE device allocation of its own: [ShiftMapDev (MAP_HEADER bytes) | base, val | rowptr,
-// col] -- every solve launch of the handle carries the address of the descriptor (eicos_batch_solve_async).
-static_assert(sizeof(ShiftMapDev) <= MAP_HEADER, "map descriptor larger than its header");
+// ---- shift map: the warm-start vectors x, y, z, s through a square affine map each ----
+// Every solve launch of the handle carries the address of the descriptor (eicos_batch_solve_async).
 int eicos_batch_set_shift_map(eicos_batch *h, const eicos_affine_map *x, const eicos_affine_map *y, const eicos_affine_map *z, const eicos_affine_map *sl) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     const DevPat &D = h->dp;
-    const eicos_affine_map *g[4] = {x, y, z, sl};
-    const int rows[4] = {D.n, D.p, D.m, D.m};
-    const char *name[4] = {"x", "y", "z", "s"};
+    const AffineGroup g[4] = {{x, D.n, D.n, "shift map of x: ", "[0, rows)"}, {y, D.p, D.p, "shift map of y: ", "[0, rows)"},
+                              {z, D.m, D.m, "shift map of z: ", "[0, rows)"}, {sl, D.m, D.m, "shift map of s: ", "[0, rows)"}};
     const bool remove = !x && !y && !z && !sl;
-    size_t nd = 0, ni = 0;
+    std::string msg;
     for (int q = 0; q < 4; q++) {
-        if (!g[q]) continue;
-        const std::string who = std::string("shift map of ") + name[q] + ": ";
-        if (rows[q] == 0) return fail(EICOS_E_INVALID, who + "the pattern has no such vector (it has no rows)");
-        if (!g[q]->base || !g[q]->rowptr) return fail(EICOS_E_INVALID, who + "base or rowptr is NULL");
-        const int *rp = g[q]->rowptr;
-        if (rp[0] != 0) return fail(EICOS_E_INVALID, who + "rowptr[0] must be 0");
-        for (int r = 0; r < rows[q]; r++)
-            if (rp[r + 1] < rp[r]) return fail(EICOS_E_INVALID, who + "rowptr decreases at row " + std::to_string(r));
-        const int nnz = rp[rows[q]];
-        if (nnz > 0 && (!g[q]->col || !g[q]->val)) return fail(EICOS_E_INVALID, who + "col or val is NULL");
-        for (int t = 0; t < nnz; t++)
-            if (g[q]->col[t] < 0 || g[q]->col[t] >= rows[q]) return fail(EICOS_E_INVALID, who + "column " + std::to_string(g[q]->col[t]) + " of entry " + std::to_string(t) + " is outside [0, rows)");
-        nd += (size_t)rows[q] + nnz; ni += (size_t)rows[q] + 1 + nnz;
+        if (!g[q].map) continue;
+        if (g[q].rows == 0) return fail(EICOS_E_INVALID, g[q].who + "the pattern has no such vector (it has no rows)");
+        if (affine_fault(g[q], msg)) return fail(EICOS_E_INVALID, msg);
     }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
-    if (h->d_shift) { (void)hipFree(h->d_shift); h->d_shift = nullptr; }
-    h->shift = ShiftMapDev{};
-    if (remove) return EICOS_OK;
     ShiftMapDev M{};
-    std::vector<char> buf(MAP_HEADER + nd * sizeof(double) + ni * sizeof(int));
-    double *hd_ = reinterpret_cast<double *>(buf.data() + MAP_HEADER);
-    int *hi_ = reinterpret_cast<int *>(buf.data() + MAP_HEADER + nd * sizeof(double));
-    void *dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, buf.size()));
-    const double *dd = reinterpret_cast<const double *>(static_cast<const char *>(dev) + MAP_HEADER);
-    const int *di = reinterpret_cast<const int *>(static_cast<const char *>(dev) + MAP_HEADER + nd * sizeof(double));
-    size_t od = 0, oi = 0;
-    for (int q = 0; q < 4; q++) {
-        if (!g[q]) continue;
-        const int nnz = g[q]->rowptr[rows[q]];
-        M.g[q].base = dd + od; std::copy(g[q]->base, g[q]->base + rows[q], hd_ + od); od += rows[q];
-        M.g[q].val = dd + od; if (nnz) std::copy(g[q]->val, g[q]->val + nnz, hd_ + od); od += nnz;
-        M.g[q].rowptr = di + oi; std::copy(g[q]->rowptr, g[q]->rowptr + rows[q] + 1, hi_ + oi); oi += rows[q] + 1;
-        M.g[q].col = di + oi; if (nnz) std::copy(g[q]->col, g[q]->col + nnz, hi_ + oi); oi += nnz;
-    }
-    std::memcpy(buf.data(), &M, sizeof M);
-    const hipError_t e = hipMemcpy(dev, buf.data(), buf.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the shift map: ") + hipGetErrorString(e)); }
-    h->d_shift = dev; h->shift = M;
-    return EICOS_OK;
+    return install_map(h, h->d_shift, h->shift, "shift", g, 4, 0, remove ? nullptr : &M, M.g);
 }
 
 int eicos_batch_has_shift_map(eicos_batch *h) {

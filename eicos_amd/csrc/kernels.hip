@@ -2958,18 +2958,22 @@ __device__ __forceinline__ int kkt_post_any(int ps, gdbl_p I, gdbl_p W, int stag
     return kkt_post<T, false>(ps, I, W, stage);
 }
 
+// One row of an affine map, the arithmetic every map shares: acc = base[row], then acc = acc + (val[t] * z[col[t]]) over the row's entries
+// in stored order, the product and the sum EACH rounded to fp64 (__dmul_rn / __dadd_rn, no FMA) -- what a numpy restatement on the host
+// computes.  z: anything indexable by a column (a pointer into global memory or LDS; PlantZ).
+template <class ZP> __device__ __forceinline__ double affine_row(const AffineDev &A, int row, ZP z) {
+    double acc = A.base[row];
+    const int t1 = A.rowptr[row + 1];
+    for (int t = A.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], z[A.col[t]]));
+    return acc;
+}
+
 // The shift map of one instance by one workgroup (instance_begin, a warm start only): every mapped vector v of x, y, z, s, as the previous
 // solve left it in the slab (backscaled), becomes new[j] = base[j], then new[j] = new[j] + (val[t] * old[col[t]]) over row j in stored
 // order, the product and the sum each rounded on its own.  Rows read other entries of their own vector, so the old values are staged
 // first: in the LDS KKT-space vector where the kernel has one (idle between two instances, as plant_instance relies on), otherwise in
 // the workspace's sweep vector (w_ek, which kkt_solve writes in full before it reads it); either holds max(n, p, m), so the groups go
 // one after another.  Out of line: a launch without a map pays the pointer test of the call site and nothing else.
-template <class ZP> __device__ __forceinline__ double shift_row(const AffineDev &A, int row, ZP z) {
-    double acc = A.base[row];
-    const int t1 = A.rowptr[row + 1];
-    for (int t = A.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], z[A.col[t]]));
-    return acc;
-}
 template <int T, bool LDSV>
 static __device__ __noinline__ __attribute__((not_tail_called)) void shift_instance(int ps, gdbl_p I, gdbl_p W, const ShiftMapDev *Sp) {
     ps = uni(ps); I = uni_ptr(I); W = uni_ptr(W); Sp = uni_ptr(Sp);
@@ -2982,7 +2986,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void shift_insta
         gdbl_p v = I + (q == 0 ? P.i_x : (q == 1 ? P.i_y : (q == 2 ? P.i_z : P.i_s)));
         FOR_T(j, rows) z[j] = v[j]; // (instance_begin's barrier is behind us: nothing reads the staging vector)
         __syncthreads();
-        FOR_T(j, rows) v[j] = shift_row(A, j, z);
+        FOR_T(j, rows) v[j] = affine_row(A, j, z);
         __syncthreads(); // (the next group overwrites the staging vector; the warm start reads entries other threads wrote)
     }
 }
@@ -3344,10 +3348,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void param_insta
         const int grp = e < wc ? 0 : (e < wc + wh ? 1 : 2), r = e - (grp == 0 ? 0 : (grp == 1 ? wc : wc + wh));
         const AffineDev A = grp == 0 ? gc : (grp == 1 ? gh : gb);
         const int i_dst = (grp == 0 ? P.i_c : (grp == 1 ? P.i_h : P.i_b)) + r, i_scl = (grp == 0 ? P.i_xe : (grp == 1 ? P.i_ge : P.i_ae)) + r;
-        double acc = A.base[r];
-        const int t1 = A.rowptr[r + 1];
-        for (int t = A.rowptr[r]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], th[A.col[t]]));
-        I[i_dst] = acc / (eq ? I[i_scl] : 1.);
+        I[i_dst] = affine_row(A, r, th) / (eq ? I[i_scl] : 1.);
     }
     __syncthreads(); // (the solve -- or the LDS-resident build's copy of the slab -- reads entries other threads wrote; the LDS vector is free again)
 }
@@ -3359,12 +3360,6 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void param_insta
 // leaves the result in the slab, where update_instance<T, false> keeps its working copy anyway; the sweeps, the write-back, the ELL / tile
 // copies and the constants are update_instance's own body (PRE).  A vector mapped without its matrix (h without G, b without A) is
 // evaluated here as well: the write-back's division by the NEW scaling is the bits of a right-hand-side-only update behind the updateData.
-__device__ __forceinline__ double affine_row(const AffineDev &A, int row, const double *z) {
-    double acc = A.base[row];
-    const int t1 = A.rowptr[row + 1];
-    for (int t = A.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], z[A.col[t]]));
-    return acc;
-}
 template <int T>
 static __device__ __noinline__ __attribute__((not_tail_called)) void matrix_param_instance(int ps, hbm_p I, size_t q, const ParamMapDev *Mp, const MatrixMapDev *Xp,
                                                                                             const double *theta) {
@@ -3407,25 +3402,17 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void outputs_ins
     const int r = Mp->r;
     const AffineDev A = Mp->a;
     gcdbl_p x = I + P.i_x;
-    FOR_T(row, r) {
-        double acc = A.base[row];
-        const int t1 = A.rowptr[row + 1];
-        for (int t = A.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], x[A.col[t]]));
-        u[q * (size_t)r + row] = acc;
-    }
+    FOR_T(row, r) u[q * (size_t)r + row] = affine_row(A, row, x);
 }
 
 // The plant map of one instance by one workgroup (k_solve, a rollout: after outputs_instance and the record of step t): row t + 1 of the
 // instance's theta trajectory = base + F z (+ w), z = [theta row t | u row t].  Both rows were written by THIS workgroup a moment ago
 // (the u row by outputs_instance, the theta row by the previous step), so they are read with ordinary global loads behind a barrier and
 // staged in the LDS KKT-space vector, idle between two solves (k + r <= Npad: api.cpp); threads then run over the k rows, accumulating
-// in stored order, product and sum rounded on their own, the disturbance added last.  plant_row = one row (k_plant_range shares it).
-__device__ __forceinline__ double plant_row(const AffineDev &A, int row, const double *z, const double *w) {
-    double acc = A.base[row];
-    const int t1 = A.rowptr[row + 1];
-    for (int t = A.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(A.val[t], z[A.col[t]]));
-    if (w) acc = __dadd_rn(acc, w[row]);
-    return acc;
+// in stored order, product and sum rounded on their own, the disturbance added last.  plant_row = one row (k_plant_range shares it, with z = PlantZ).
+template <class ZP> __device__ __forceinline__ double plant_row(const AffineDev &A, int row, ZP z, const double *w) {
+    const double acc = affine_row(A, row, z);
+    return w ? __dadd_rn(acc, w[row]) : acc;
 }
 template <int T>
 static __device__ __noinline__ __attribute__((not_tail_called)) void plant_instance(const RolloutDev *Rp, int id, int t) {
@@ -3742,6 +3729,33 @@ __global__ __launch_bounds__(T) void k_update_rhs_range(int ps, double *inst, in
 // FMA).  That is what a numpy restatement on the host computes (numpy has no FMA), so update_param(theta) leaves the bits of
 // update_rhs(c(theta), h(theta), b(theta)); and the kernel is bound by the slab write of ~48 kB per instance, not by its arithmetic.
 constexpr int PARAM_Q = 4;
+// The part k_update_param_range and k_expand_affine share, for one group of nq <= PARAM_Q instances whose theta rows start at th: the rows
+// are staged in LDS (when LDS; met by every thread of the workgroup, active or not), then an active thread accumulates entries [t0, t1)
+// of its row of A into one accumulator per instance, each starting from base.  Returns act.
+template <int T, bool LDS>
+__device__ __forceinline__ bool param_q_rows(const AffineDev &A, bool act, double base, int t0, int t1, const double *th, int nq, int k,
+                                             double (&acc)[PARAM_Q]) {
+    if constexpr (LDS) {
+        __syncthreads(); // (the previous group's rows have been read)
+        for (int j = threadIdx.x; j < nq * k; j += T) g_dyn[j] = th[j];
+        __syncthreads();
+    }
+    if (!act) return false;
+#pragma unroll
+    for (int j = 0; j < PARAM_Q; j++) acc[j] = base;
+    for (int t = t0; t < t1; t++) {
+        const int col = A.col[t];
+        const double v = A.val[t];
+#pragma unroll
+        for (int j = 0; j < PARAM_Q; j++)
+            if (j < nq) {
+                double x;
+                if constexpr (LDS) x = g_dyn[j * k + col]; else x = th[(size_t)j * k + col];
+                acc[j] = __dadd_rn(acc[j], __dmul_rn(v, x));
+            }
+    }
+    return true;
+}
 template <int T, bool LDS>
 __global__ __launch_bounds__(T) void k_update_param_range(int ps, double *inst, int first, int count, ParamMapDev M, const double *theta) {
     const DevPat &P = c_pat[ps];
@@ -3759,26 +3773,8 @@ __global__ __launch_bounds__(T) void k_update_param_range(int ps, double *inst, 
         for (int q0 = blockIdx.y * PARAM_Q; q0 < count; q0 += gridDim.y * PARAM_Q) {
             const int nq = count - q0 < PARAM_Q ? count - q0 : PARAM_Q;
             const double *th = theta + (size_t)q0 * k; // rows q0 .. q0 + nq - 1
-            if constexpr (LDS) {
-                __syncthreads(); // (the previous group's rows have been read)
-                for (int j = threadIdx.x; j < nq * k; j += T) g_dyn[j] = th[j];
-                __syncthreads();
-            }
-            if (!act) continue;
             double acc[PARAM_Q];
-#pragma unroll
-            for (int j = 0; j < PARAM_Q; j++) acc[j] = base;
-            for (int t = t0; t < t1; t++) {
-                const int col = A.col[t];
-                const double v = A.val[t];
-#pragma unroll
-                for (int j = 0; j < PARAM_Q; j++)
-                    if (j < nq) {
-                        double x;
-                        if constexpr (LDS) x = g_dyn[j * k + col]; else x = th[(size_t)j * k + col];
-                        acc[j] = __dadd_rn(acc[j], __dmul_rn(v, x));
-                    }
-            }
+            if (!param_q_rows<T, LDS>(A, act, base, t0, t1, th, nq, k, acc)) continue;
 #pragma unroll
             for (int j = 0; j < PARAM_Q; j++)
                 if (j < nq) {
@@ -3808,26 +3804,8 @@ __global__ __launch_bounds__(T) void k_expand_affine(AffineDev A, int rows, int 
         for (int q0 = blockIdx.y * PARAM_Q; q0 < count; q0 += gridDim.y * PARAM_Q) {
             const int nq = count - q0 < PARAM_Q ? count - q0 : PARAM_Q;
             const double *th = theta + (size_t)q0 * k; // rows q0 .. q0 + nq - 1
-            if constexpr (LDS) {
-                __syncthreads(); // (the previous group's rows have been read)
-                for (int j = threadIdx.x; j < nq * k; j += T) g_dyn[j] = th[j];
-                __syncthreads();
-            }
-            if (!act) continue;
             double acc[PARAM_Q];
-#pragma unroll
-            for (int j = 0; j < PARAM_Q; j++) acc[j] = base;
-            for (int t = t0; t < t1; t++) {
-                const int col = A.col[t];
-                const double v = A.val[t];
-#pragma unroll
-                for (int j = 0; j < PARAM_Q; j++)
-                    if (j < nq) {
-                        double x;
-                        if constexpr (LDS) x = g_dyn[j * k + col]; else x = th[(size_t)j * k + col];
-                        acc[j] = __dadd_rn(acc[j], __dmul_rn(v, x));
-                    }
-            }
+            if (!param_q_rows<T, LDS>(A, act, base, t0, t1, th, nq, k, acc)) continue;
 #pragma unroll
             for (int j = 0; j < PARAM_Q; j++)
                 if (j < nq) dst[(size_t)(q0 + j) * rows + r] = acc[j];
@@ -3845,10 +3823,7 @@ __global__ __launch_bounds__(T) void k_outputs_range(int ps, const double *inst,
         const size_t q = e / r;
         const int row = (int)(e - q * r);
         const double *x = inst + (size_t)(first + q) * P.inst_stride + P.i_x;
-        double acc = M.a.base[row];
-        const int t1 = M.a.rowptr[row + 1];
-        for (int t = M.a.rowptr[row]; t < t1; t++) acc = __dadd_rn(acc, __dmul_rn(M.a.val[t], x[M.a.col[t]]));
-        u[e] = acc;
+        u[e] = affine_row(M.a, row, x);
     }
 }
 
@@ -3880,6 +3855,10 @@ __global__ __launch_bounds__(T) void k_set_iterate_range(int ps, double *inst, i
 // One step of a rollout that is not fused (launch.hpp: launch_plant; plant_instance is the fused form): ROW-parallel over the count * k
 // rows of theta+, the map served from L2, z read from the step's contiguous theta and u rows.  Same arithmetic as plant_instance.  The
 // threads of the first r / the first row of an instance also move its u row, exit code and iteration count into the trajectories.
+struct PlantZ { // z = [theta (k) | u (r)] read from its two rows
+    const double *th, *u; size_t k;
+    __device__ double operator[](int col) const { return (size_t)col < k ? th[col] : u[col - k]; }
+};
 template <int T>
 __global__ __launch_bounds__(T) void k_plant_range(int ps, const double *inst, int first, int count, RolloutDev R, int t, const double *theta_cur,
                                                    const double *u_cur, double *theta_next) {
@@ -3889,13 +3868,7 @@ __global__ __launch_bounds__(T) void k_plant_range(int ps, const double *inst, i
         const size_t q = e / k, at = (first + q) * steps + t;
         const int row = (int)(e - q * k);
         const double *th = theta_cur + q * k, *u = u_cur + q * r;
-        double acc = R.plant.a.base[row];
-        const int t1 = R.plant.a.rowptr[row + 1];
-        for (int s = R.plant.a.rowptr[row]; s < t1; s++) {
-            const int col = R.plant.a.col[s];
-            acc = __dadd_rn(acc, __dmul_rn(R.plant.a.val[s], (size_t)col < k ? th[col] : u[col - k]));
-        }
-        if (R.w) acc = __dadd_rn(acc, R.w[at * k + row]);
+        const double acc = plant_row(R.plant.a, row, PlantZ{th, u, k}, R.w ? R.w + at * k : nullptr);
         theta_next[e] = acc;
         R.theta[(at + first + q + 1) * k + row] = acc;
         for (size_t j = row; j < r; j += k) R.u[at * r + j] = u[j];
