@@ -30,6 +30,7 @@
 #include "envknob.hpp"
 #include "internal.hpp"
 #include "affine_pack.hpp"
+#include "fused_fit.hpp"
 
 using namespace eicos;
 // Workgroups per CU for a batch, at most `max_r`: the cheapest estimate of the launch's duration wins.
@@ -82,9 +83,9 @@ struct eicos_batch {
     int pslot = -1; // slot of this handle's DevPat in the kernels' constant-memory table
     size_t dyn_lds = 0;
     int nlds = 0;
-    int w2 = 0;               // 1: solves run the two-waves-per-SIMD build of the 256-thread kernel (w2::launch_solve)
-    int ubl = 0;              // 1: solves run the build with the factor operand array U in LDS (ubl256:: / ubl512::launch_solve; one workgroup per CU)
-    int ldsres = 0;           // 1: solves run the LDS-resident kernel (ldsres::launch_solve), slabs copied in and out per instance
+    int w2 = 0;               // 1: solves run the two-waves-per-SIMD build of the 256-thread kernel (w2::solve_entries)
+    int ubl = 0;              // 1: solves run the build with the factor operand array U in LDS (ubl256:: / ubl512::solve_entries; one workgroup per CU)
+    int ldsres = 0;           // 1: solves run the LDS-resident kernel (ldsres::solve_entries), slabs copied in and out per instance
     size_t pattern_ints = 0;
     double *d_inst = nullptr, *d_work = nullptr, *d_scratch = nullptr;
     int *d_queue = nullptr; // instance queue of the solve kernel (reset per launch)
@@ -116,8 +117,7 @@ struct eicos_batch {
     int ub_len = 1;        // length of that array (plan slots + dummy, + the dense apex image)
     int bpc = 1, n_cu = 256; // workgroups per CU of the solve launch; CUs of the device
     int arith_profile = 0;   // eicos_set_arithmetic_profile at creation
-    UpdArgs fused{}; bool fused_pending = false; // eicos_batch_update_solve: the arrays the next solve launch pulls in itself
-    // ... from pageable host memory: one pinned staging buffer for the whole batch (+ one ready flag per chunk), filled while the kernel runs
+    // eicos_batch_update_solve from pageable host memory: one pinned staging buffer for the whole batch (+ one ready flag per chunk), filled while the kernel runs
     double *stage_pin = nullptr; size_t stage_pin_doubles = 0; unsigned *stage_flags = nullptr; int stage_nflags = 0; unsigned stage_seq = 0;
     int *d_err = nullptr;
     // parametric right-hand sides (eicos_batch_set_param_map): the map's arrays in one device allocation, param.k = 0 while none is installed
@@ -902,7 +902,7 @@ static int launch_shape(Plan &pl, int batch, int device, Shape &sh) {
     {   // entry-parallel updateData: needs the A / G values and the row / column maxima in LDS and <= 8 vector entries per thread
         const size_t need = ((size_t)S.nnzA + S.nnzG + S.n + S.p + S.m + 8) * sizeof(double);
         const size_t need_max = ((size_t)S.n + S.p + S.m + 8) * sizeof(double); // the row / column maxima alone
-        const bool small_vecs = S.n <= 8 * 512 && S.p <= 8 * 512 && S.m <= 16 * 512;
+        const bool small_vecs = update_vectors_fit(S.n, S.p, S.m);
         const int mode = env_knob("EICOS_UPDATE_LDS", 1, 0, 2); // 0: thread-per-column kernel, 2: force the streamed-values variant
         if (need <= 156 * 1024 && small_vecs && mode == 1) { sh.upd_lds = need; sh.upd_vals_lds = 1; sh.upd_grid = std::min(batch, n_cu); }
         else if (need_max <= 156 * 1024 && small_vecs && mode >= 1) { // values streamed in place, maxima in LDS: as many 512-thread workgroups per CU as fit (<= 4)
@@ -946,9 +946,9 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
             for (int q = 0; q < max_patterns(); q++) if (!used[q]) { h->pslot = q; used[q] = 1; break; }
         }
         if (h->pslot < 0) return fail(EICOS_E_INVALID, "too many live handles on this device (64)");
-        HIP_TRY(upload_pattern(h->pslot, h->dp)); // (the default namespace always: updateData and the debug kernels live there)
-        const SolveBuild sbuild = solve_build(h->threads, h->ldsres, h->w2, h->ubl);
-        if (sbuild.upload != upload_pattern) HIP_TRY(sbuild.upload(h->pslot, h->dp));
+        const SolveBuild main_build = solve_entries(), sbuild = solve_build(h->threads, h->ldsres, h->w2, h->ubl);
+        HIP_TRY(main_build.upload(h->pslot, h->dp)); // (the default namespace always: updateData and the debug kernels live there)
+        if (!(sbuild == main_build)) HIP_TRY(sbuild.upload(h->pslot, h->dp));
         HIP_TRY(hipMalloc(&h->d_inst, (size_t)batch * D.inst_stride * sizeof(double)));
         HIP_TRY(hipMemset(h->d_inst, 0, (size_t)batch * D.inst_stride * sizeof(double)));
         HIP_TRY(hipMalloc(&h->d_work, (size_t)h->grid * D.work_stride * sizeof(double)));
@@ -1799,30 +1799,34 @@ int eicos_batch_outputs_device(eicos_batch *h, int first, int count, double *du)
     return rc != EICOS_OK ? rc : outputs_to(h, first, count, du, MEM_DEVICE);
 }
 
-int eicos_batch_solve_async(eicos_batch *h) {
-    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+// the launch record of a handle's solves (launch.hpp)
+static SolveLaunch solve_launch(const eicos_batch *h) {
+    SolveLaunch L{};
+    L.ps = h->pslot; L.inst = h->d_inst; L.work = h->d_work; L.B = h->batch; L.queue = h->d_queue; L.order = h->d_queue + 16;
+    L.grid = h->grid; L.threads = h->threads; L.nlds = h->nlds; L.idx16 = h->dp.idx16; L.order_min = h->order_min;
+    L.warm = h->warm_shift; L.dyn_delta = h->dyn_delta; L.dyn_eps = h->dyn_eps; L.cfg = h->cfg; L.dyn_lds = h->dyn_lds;
+    return L;
+}
+// The one place that enqueues k_solve on the handle's stream.  step: the update fused into this launch (update_solve, the rollout), NULL
+// for a plain solve; it lives for this call only.
+static int enqueue_solve(eicos_batch *h, const UpdArgs *step) {
     HIP_TRY(hipSetDevice(h->device));
     { const int rc = next_events(h->ring_s, h->n_solve_rec, h->ev_s0, h->ev_s1); if (rc != EICOS_OK) return rc; }
     h->ring_step0[(h->n_solve_rec - 1) % eicos_batch::EV_RING] = h->update_timed ? h->ev_u0 : h->ev_s0;
     HIP_TRY(hipEventRecord(h->ev_s0, h->stream));
-    // (a shift map travels with EVERY launch, the ones without a fused update included: instance_begin reads it)
-    UpdArgs args = h->fused_pending ? h->fused : UpdArgs{};
-    if (!h->fused_pending) args.chunk = 1;
+    UpdArgs args = step ? *step : UpdArgs{};
+    // (a shift map and the shared-values word travel with EVERY launch, the ones without a fused update included: instance_begin reads them)
     args.smap = static_cast<const ShiftMapDev *>(h->d_shift);
-    // a fused update that writes matrix values (full updateData; a parametric step or a rollout under a matrix map) drops the shared values
-    if (h->fused_pending && (args.on == UPD_FULL || ((args.on == UPD_PARAM || args.on == UPD_ROLL) && args.mmap))) {
-        const int rc = shared_clear(h);
-        if (rc != EICOS_OK) return rc;
-    }
+    if (writes_matrix_values(args)) { const int rc = shared_clear(h); if (rc != EICOS_OK) return rc; } // (the step drops the shared values)
     args.shared = h->shared_on ? h->d_shared : nullptr;
-    HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(h->pslot, h->d_inst, h->d_work, h->batch, h->d_queue, h->d_queue + 16, h->grid, h->threads, h->nlds,
-                                                             h->dp.idx16, h->order_min, h->warm_shift, h->dyn_delta, h->dyn_eps, h->cfg, h->dyn_lds, h->stream,
-                                                             (h->fused_pending || args.smap || args.shared) ? &args : nullptr));
+    HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(solve_launch(h), h->stream, args));
     HIP_TRY(hipEventRecord(h->ev_s1, h->stream));
     h->solve_timed = true;
     h->last_ordered = h->batch > h->order_min;
     return EICOS_OK;
 }
+
+int eicos_batch_solve_async(eicos_batch *h) { return h ? enqueue_solve(h, nullptr) : fail(EICOS_E_INVALID, "NULL handle"); }
 
 int eicos_batch_sync(eicos_batch *h) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
@@ -1910,6 +1914,49 @@ int eicos_batch_solve(eicos_batch *h, int *exitcodes) {
     return exit_codes(h, exitcodes);
 }
 
+// ---- steps fused into the solve launch: the helpers of update_solve and the rollout ----
+static FitShape fit_shape(const eicos_batch *h) { return {h->dp.n, h->dp.p, h->dp.m, h->dp.Npad, h->nlds, h->threads}; }
+// a step that runs inside the solve launch: its witness (5, or 6 with staged arrays) and an empty updateData interval in the timing ring
+static int fused_step_begins(eicos_batch *h, int path) {
+    h->last_update_path = path;
+    return end_update_timing(h, begin_update_timing(h));
+}
+// the pinned staging buffer (`doubles`), the ready flags (`nchunks`) and the time-out word of a staged fused update, grown on demand
+static int grow_staging(eicos_batch *h, size_t doubles, int nchunks) {
+    if (doubles > h->stage_pin_doubles) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->stage_pin) { (void)hipHostFree(h->stage_pin); h->stage_pin = nullptr; h->stage_pin_doubles = 0; }
+        HIP_TRY(hipHostMalloc((void **)&h->stage_pin, doubles * sizeof(double), hipHostMallocDefault));
+        h->stage_pin_doubles = doubles;
+    }
+    if (nchunks > h->stage_nflags) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->stage_flags) { (void)hipHostFree(h->stage_flags); h->stage_flags = nullptr; h->stage_nflags = 0; }
+        HIP_TRY(hipHostMalloc((void **)&h->stage_flags, (size_t)nchunks * sizeof(unsigned), hipHostMallocDefault));
+        std::memset(h->stage_flags, 0, (size_t)nchunks * sizeof(unsigned));
+        h->stage_nflags = nchunks; h->stage_seq = 0;
+    }
+    if (!h->d_err) { HIP_TRY(hipMalloc((void **)&h->d_err, sizeof(int))); HIP_TRY(hipMemset(h->d_err, 0, sizeof(int))); }
+    return EICOS_OK;
+}
+// x_out [batch][n], u_out [batch][r] (NULL: not asked for) behind a finished solve, by kind of memory unless the kernel wrote it; complete on return
+static int deliver_results(eicos_batch *h, double *x_out, MemKind x_kind, bool x_written, double *u_out, MemKind u_kind, bool u_written) {
+    const DevPat &D = h->dp;
+    if (x_out && !x_written) {
+        if (x_kind == MEM_DEVICE) { // a result array in device memory: one strided copy on the device
+            const size_t wb = (size_t)D.n * sizeof(double);
+            HIP_TRY(hipMemcpy2DAsync(x_out, wb, h->d_inst + D.i_x, D.inst_stride * sizeof(double), wb, (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        } else { const int rc = fetch_rows(h, x_out, D.i_x, D.n); if (rc != EICOS_OK) return rc; }
+    }
+    if (u_out && !u_written) {
+        const int rc = outputs_to(h, 0, h->batch, u_out, u_kind);
+        if (rc != EICOS_OK) return rc;
+        if (u_kind == MEM_DEVICE) HIP_TRY(hipStreamSynchronize(h->stream)); // (the range kernel writes device memory asynchronously)
+    }
+    return EICOS_OK;
+}
+
 // updateData + solve in ONE call: the reference's updateData(double *...) followed by solve() (include/eicos.hpp:155-158) for the whole batch.
 // When every given array is memory the GPU addresses directly (pinned / registered host memory, or device memory) the updateData of an
 // instance is run by the solve kernel's own workgroup right before it solves that instance (kernels.hip: update_instance): the transfer over
@@ -1930,103 +1977,82 @@ int eicos_batch_solve(eicos_batch *h, int *exitcodes) {
 enum StepKind { STEP_FULL = 0, STEP_RHS = 1, STEP_PARAM = 2 };
 static int update_solve(eicos_batch *h, const double *G, const double *A, const double *c, const double *hh, const double *b,
                         const double *theta, double *u_out, double *x_out, int *exitcodes, StepKind kind) {
+    // ---- classify the inputs and the outputs
     UpdateInputs in;
     const bool rhs = kind == STEP_RHS, param = kind == STEP_PARAM;
     int rc = param ? take_theta(in, h, 0, h ? h->batch : 0, theta, true) : take_inputs(in, h, 0, h ? h->batch : 0, G, A, c, hh, b, rhs, true);
     if (rc != EICOS_OK) return rc;
     if (u_out && h->out.r == 0) return fail(EICOS_E_INVALID, "no output map (eicos_batch_set_output_map installs one)");
     const DevPat &D = h->dp;
-    // (the in-register scaling accumulators of update_instance: a full updateData, or a parametric one under a matrix map, needs them)
-    const bool own = D.n <= 8 * h->threads && D.p <= 8 * h->threads && D.m <= 16 * h->threads;
-    const bool fits = param ? (h->param.k <= D.Npad && (h->mat.k == 0 || own)) : (rhs || own);
-    const bool fused = h->nlds >= 1 && fits && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
     // arrays the GPU cannot address (pageable memory) are STAGED: copied into the handle's pinned staging buffer while the kernel runs
     const bool any_staged = in.any(MEM_PAGEABLE);
     if (D.n == 0) x_out = nullptr;
     const MemKind x_kind = memory_kind(x_out, (size_t)h->batch * D.n * sizeof(double));
     const MemKind u_kind = memory_kind(u_out, (size_t)h->batch * h->out.r * sizeof(double));
+    // ---- choose the path
+    const FitShape fs = fit_shape(h);
+    const bool fits = param ? fused_param_fits(fs, h->param.k, h->mat.k != 0) : (rhs ? fused_rhs_fits(fs) : fused_full_fits(fs));
+    const bool fused = fits && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
     // (staging pageable arrays while the kernel runs is OFF by default: measured on five boxes against the bounce pipeline + solve it is
     // +5.7 ... -6.2 % -- the host's copy is the pace either way, and on a box with slow host cores the kernel's own PCIe pulls and flag polls
     // slow that copy further; EICOS_FUSED_STAGED=1 under EICOS_EXPERIMENT=1 turns it on: docs/HISTORY.md A.11 item 9)
     if (!fused || (any_staged && (param || !env_knob("EICOS_FUSED_STAGED", 0, 0, 1)))) {
-        // (device arrays on a handle without the fused path: the device-pointer updateData)
+        // ---- separate launches (device arrays on a handle without the fused path: the device-pointer updateData)
         rc = in.all(MEM_DEVICE) ? update_in_place(in, 0) : staged_update(in, -1);
-        if (rc == EICOS_OK) rc = eicos_batch_solve_async(h);
-        if (rc != EICOS_OK) return rc;
-        rc = eicos_batch_sync(h);
-        if (rc != EICOS_OK) return rc;
-        if (x_kind == MEM_DEVICE) { // a result array in device memory: one strided copy on the device
-            const size_t wb = (size_t)D.n * sizeof(double);
-            HIP_TRY(hipMemcpy2DAsync(x_out, wb, h->d_inst + D.i_x, D.inst_stride * sizeof(double), wb, (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-        } else if (x_out) { rc = fetch_rows(h, x_out, D.i_x, D.n); if (rc != EICOS_OK) return rc; }
-        if (u_out) {
-            rc = outputs_to(h, 0, h->batch, u_out, u_kind);
-            if (rc != EICOS_OK) return rc;
-            HIP_TRY(hipStreamSynchronize(h->stream));
-        }
-    } else {
-        const double *ptr[5] = {in.src[0], in.src[1], in.src[2], in.src[3], in.src[4]};
-        bool staged[5];
-        size_t per = 0, stage_need = 0;
-        for (int k = 0; k < 5; k++) {
-            staged[k] = in.holds_data(k) && in.kind[k] == MEM_PAGEABLE;
-            if (staged[k]) { per += in.w[k]; stage_need += (size_t)h->batch * in.w[k] + 8; }
-        }
-        // chunks of ~12 MB over the staged arrays: the copy pool splits an array's share of a chunk into pieces of >= 1 MB over its threads, so
-        // a chunk must be large enough to keep them busy and small enough that the first workgroups start after a fraction of the whole copy
-        const int chunk = any_staged ? (int)std::max<size_t>(8, std::min<size_t>((size_t)h->batch, (12u << 20) / std::max<size_t>(per * sizeof(double), 1))) : h->batch;
-        const int nchunks = (h->batch + chunk - 1) / chunk;
-        if (any_staged) {
-            if (stage_need > h->stage_pin_doubles) {
-                HIP_TRY(hipStreamSynchronize(h->stream));
-                if (h->stage_pin) { (void)hipHostFree(h->stage_pin); h->stage_pin = nullptr; h->stage_pin_doubles = 0; }
-                HIP_TRY(hipHostMalloc((void **)&h->stage_pin, stage_need * sizeof(double), hipHostMallocDefault));
-                h->stage_pin_doubles = stage_need;
-            }
-            if (nchunks > h->stage_nflags) {
-                HIP_TRY(hipStreamSynchronize(h->stream));
-                if (h->stage_flags) { (void)hipHostFree(h->stage_flags); h->stage_flags = nullptr; h->stage_nflags = 0; }
-                HIP_TRY(hipHostMalloc((void **)&h->stage_flags, (size_t)nchunks * sizeof(unsigned), hipHostMallocDefault));
-                std::memset(h->stage_flags, 0, (size_t)nchunks * sizeof(unsigned));
-                h->stage_nflags = nchunks; h->stage_seq = 0;
-            }
-            if (!h->d_err) { HIP_TRY(hipMalloc((void **)&h->d_err, sizeof(int))); HIP_TRY(hipMemset(h->d_err, 0, sizeof(int))); }
-            double *at = h->stage_pin;
-            for (int k = 0; k < 5; k++) if (staged[k]) { ptr[k] = at; at += (size_t)h->batch * in.w[k] + 8; }
-            h->stage_seq++;
-            if (h->stage_seq == 0) { std::memset(h->stage_flags, 0, (size_t)h->stage_nflags * sizeof(unsigned)); h->stage_seq = 1; } // (wrapped)
-        }
-        h->last_update_path = any_staged ? 6 : 5;
-        rc = end_update_timing(h, begin_update_timing(h)); // (an empty updateData interval in the timing ring: the work is inside the solve launch)
-        if (rc != EICOS_OK) return rc;
-        h->fused = UpdArgs{ptr[0], ptr[1], param ? nullptr : ptr[2], ptr[3], ptr[4], x_kind != MEM_PAGEABLE ? x_out : nullptr,
-                           param ? UPD_PARAM : (rhs ? UPD_RHS : UPD_FULL), any_staged ? h->stage_flags : nullptr, chunk, h->stage_seq, h->d_err,
-                           static_cast<const ParamMapDev *>(h->d_param), static_cast<const OutMapDev *>(h->d_out), param ? ptr[2] : nullptr,
-                           u_kind != MEM_PAGEABLE ? u_out : nullptr, nullptr, param && h->mat.k ? static_cast<const MatrixMapDev *>(h->d_mat) : nullptr};
-        h->fused_pending = true;
-        rc = eicos_batch_solve_async(h);
-        h->fused_pending = false;
-        if (rc != EICOS_OK) return rc; // (nothing was launched: no workgroup waits for a flag)
-        if (any_staged) { // the kernel is running: copy chunk by chunk and release each chunk's flag behind its rows
-            CopyPool &pool = CopyPool::get();
-            for (int q = 0; q < nchunks; q++) {
-                const size_t r0 = (size_t)q * chunk, rows = std::min<size_t>((size_t)chunk, (size_t)h->batch - r0);
-                for (int k = 0; k < 5; k++) if (staged[k]) pool.copy(const_cast<double *>(ptr[k]) + r0 * in.w[k], in.src[k] + r0 * in.w[k], rows * in.w[k] * sizeof(double));
-                __atomic_store_n(&h->stage_flags[q], h->stage_seq, __ATOMIC_RELEASE); // (stream_copy ends with an sfence: the rows are visible before the flag)
-            }
-        }
-        rc = eicos_batch_sync(h);
-        if (rc != EICOS_OK) return rc;
-        if (any_staged) {
-            int err = 0;
-            HIP_TRY(hipMemcpy(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
-            if (err) { HIP_TRY(hipMemset(h->d_err, 0, sizeof(int))); return fail(EICOS_E_HIP, "fused updateData: a workgroup timed out waiting for its staged rows"); }
-        }
-        if (x_out && x_kind == MEM_PAGEABLE) { rc = fetch_rows(h, x_out, D.i_x, D.n); if (rc != EICOS_OK) return rc; }
-        if (u_out && u_kind == MEM_PAGEABLE) { rc = outputs_to(h, 0, h->batch, u_out, u_kind); if (rc != EICOS_OK) return rc; }
+        if (rc == EICOS_OK) rc = enqueue_solve(h, nullptr);
+        if (rc == EICOS_OK) rc = eicos_batch_sync(h);
+        if (rc == EICOS_OK) rc = deliver_results(h, x_out, x_kind, false, u_out, u_kind, false);
+        return rc != EICOS_OK ? rc : exit_codes(h, exitcodes);
     }
-    return exit_codes(h, exitcodes);
+    // ---- one launch: the kernel reads the arrays and writes the outputs it can address
+    const double *ptr[5] = {in.src[0], in.src[1], in.src[2], in.src[3], in.src[4]};
+    bool staged[5];
+    size_t per = 0, stage_need = 0;
+    for (int k = 0; k < 5; k++) {
+        staged[k] = in.holds_data(k) && in.kind[k] == MEM_PAGEABLE;
+        if (staged[k]) { per += in.w[k]; stage_need += (size_t)h->batch * in.w[k] + 8; }
+    }
+    // chunks of ~12 MB over the staged arrays: the copy pool splits an array's share of a chunk into pieces of >= 1 MB over its threads, so
+    // a chunk must be large enough to keep them busy and small enough that the first workgroups start after a fraction of the whole copy
+    const int chunk = any_staged ? (int)std::max<size_t>(8, std::min<size_t>((size_t)h->batch, (12u << 20) / std::max<size_t>(per * sizeof(double), 1))) : h->batch;
+    const int nchunks = (h->batch + chunk - 1) / chunk;
+    if (any_staged) {
+        rc = grow_staging(h, stage_need, nchunks);
+        if (rc != EICOS_OK) return rc;
+        double *at = h->stage_pin;
+        for (int k = 0; k < 5; k++) if (staged[k]) { ptr[k] = at; at += (size_t)h->batch * in.w[k] + 8; }
+        h->stage_seq++;
+        if (h->stage_seq == 0) { std::memset(h->stage_flags, 0, (size_t)h->stage_nflags * sizeof(unsigned)); h->stage_seq = 1; } // (wrapped)
+    }
+    rc = fused_step_begins(h, any_staged ? 6 : 5);
+    if (rc != EICOS_OK) return rc;
+    const bool x_written = x_kind != MEM_PAGEABLE, u_written = u_kind != MEM_PAGEABLE;
+    UpdArgs step;
+    step.on = param ? UPD_PARAM : (rhs ? UPD_RHS : UPD_FULL);
+    step.G = ptr[0]; step.A = ptr[1]; (param ? step.theta : step.c) = ptr[2]; step.h = ptr[3]; step.b = ptr[4];
+    step.x = x_written ? x_out : nullptr; step.u = u_written ? u_out : nullptr;
+    step.flags = any_staged ? h->stage_flags : nullptr; step.chunk = chunk; step.seq = h->stage_seq; step.err = h->d_err;
+    step.pmap = static_cast<const ParamMapDev *>(h->d_param); step.omap = static_cast<const OutMapDev *>(h->d_out);
+    if (param && h->mat.k) step.mmap = static_cast<const MatrixMapDev *>(h->d_mat);
+    rc = enqueue_solve(h, &step);
+    if (rc != EICOS_OK) return rc; // (nothing was launched: no workgroup waits for a flag)
+    if (any_staged) { // the kernel is running: copy chunk by chunk and release each chunk's flag behind its rows
+        CopyPool &pool = CopyPool::get();
+        for (int q = 0; q < nchunks; q++) {
+            const size_t r0 = (size_t)q * chunk, rows = std::min<size_t>((size_t)chunk, (size_t)h->batch - r0);
+            for (int k = 0; k < 5; k++) if (staged[k]) pool.copy(const_cast<double *>(ptr[k]) + r0 * in.w[k], in.src[k] + r0 * in.w[k], rows * in.w[k] * sizeof(double));
+            __atomic_store_n(&h->stage_flags[q], h->stage_seq, __ATOMIC_RELEASE); // (stream_copy ends with an sfence: the rows are visible before the flag)
+        }
+    }
+    rc = eicos_batch_sync(h);
+    if (rc != EICOS_OK) return rc;
+    if (any_staged) {
+        int err = 0;
+        HIP_TRY(hipMemcpy(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
+        if (err) { HIP_TRY(hipMemset(h->d_err, 0, sizeof(int))); return fail(EICOS_E_HIP, "fused updateData: a workgroup timed out waiting for its staged rows"); }
+    }
+    rc = deliver_results(h, x_out, x_kind, x_written, u_out, u_kind, u_written);
+    return rc != EICOS_OK ? rc : exit_codes(h, exitcodes);
 }
 
 int eicos_batch_update_solve(eicos_batch *h, const double *G, const double *A, const double *c, const double *hh, const double *b,
@@ -2086,7 +2112,7 @@ int eicos_batch_has_matrix_map(eicos_batch *h) {
 }
 
 // ---- shift map: the warm-start vectors x, y, z, s through a square affine map each ----
-// Every solve launch of the handle carries the address of the descriptor (eicos_batch_solve_async).
+// Every solve launch of the handle carries the address of the descriptor (enqueue_solve).
 int eicos_batch_set_shift_map(eicos_batch *h, const eicos_affine_map *x, const eicos_affine_map *y, const eicos_affine_map *z, const eicos_affine_map *sl) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     const DevPat &D = h->dp;
@@ -2132,7 +2158,6 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
     if (!theta0) return fail(EICOS_E_INVALID, "rollout: theta0 is NULL");
     if (!u_traj) return fail(EICOS_E_INVALID, "rollout: u_traj is NULL");
     HIP_TRY(hipSetDevice(h->device));
-    const DevPat &D = h->dp;
     const size_t B = (size_t)h->batch, T = (size_t)steps;
     const size_t n_th = B * (T + 1) * k, n_u = B * T * r, n_w = w ? B * T * k : 0, n_cur = 2 * B * k, n_rec = B * T;
     const size_t need = MAP_HEADER + (n_th + n_u + n_w + n_cur) * sizeof(double) + 2 * n_rec * sizeof(int);
@@ -2149,21 +2174,16 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
     HIP_TRY(hipMemcpyAsync(h->d_roll, &h->roll, sizeof(RolloutDev), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpy2DAsync(d_th, (T + 1) * row_b, theta0, row_b, row_b, B, hipMemcpyDefault, h->stream)); // row 0 of every trajectory
     if (w) HIP_TRY(hipMemcpyAsync(d_w, w, n_w * sizeof(double), hipMemcpyDefault, h->stream));
-    const bool own = h->mat.k == 0 || (D.n <= 8 * h->threads && D.p <= 8 * h->threads && D.m <= 16 * h->threads); // (update_solve: the accumulator limit)
-    const bool fused = h->nlds >= 1 && k + r <= D.Npad && own && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
+    const bool fused = fused_rollout_fits(fit_shape(h), k, r, h->mat.k != 0) && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
     int rc = EICOS_OK;
     if (fused) {
-        h->last_update_path = 5;
-        rc = end_update_timing(h, begin_update_timing(h)); // (an empty updateData interval in the timing ring: the work is inside the solve launch)
+        rc = fused_step_begins(h, 5);
         if (rc != EICOS_OK) return rc;
-        h->fused = UpdArgs{};
-        h->fused.on = UPD_ROLL; h->fused.chunk = 1;
-        h->fused.pmap = static_cast<const ParamMapDev *>(h->d_param); h->fused.omap = static_cast<const OutMapDev *>(h->d_out);
-        h->fused.roll = static_cast<const RolloutDev *>(h->d_roll);
-        h->fused.mmap = h->mat.k ? static_cast<const MatrixMapDev *>(h->d_mat) : nullptr;
-        h->fused_pending = true;
-        rc = eicos_batch_solve_async(h);
-        h->fused_pending = false;
+        UpdArgs step;
+        step.on = UPD_ROLL; step.roll = static_cast<const RolloutDev *>(h->d_roll);
+        step.pmap = static_cast<const ParamMapDev *>(h->d_param); step.omap = static_cast<const OutMapDev *>(h->d_out);
+        if (h->mat.k) step.mmap = static_cast<const MatrixMapDev *>(h->d_mat);
+        rc = enqueue_solve(h, &step);
         if (rc != EICOS_OK) return rc;
     } else {
         HIP_TRY(hipMemcpy2DAsync(d_cur, row_b, d_th, (T + 1) * row_b, row_b, B, hipMemcpyDeviceToDevice, h->stream));
@@ -2173,7 +2193,7 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
             rc = begin_update_timing(h);
             if (rc == EICOS_OK) rc = param_range(h, 0, h->batch, cur);
             rc = end_update_timing(h, rc);
-            if (rc == EICOS_OK) rc = eicos_batch_solve_async(h);
+            if (rc == EICOS_OK) rc = enqueue_solve(h, nullptr);
             if (rc != EICOS_OK) return rc;
             HIP_TRY(launch_outputs(h->pslot, h->d_inst, 0, h->batch, h->out, h->d_u, h->stream));
             HIP_TRY(launch_plant(h->pslot, h->d_inst, 0, h->batch, h->roll, t, cur, h->d_u, next, h->stream));

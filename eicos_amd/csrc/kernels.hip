@@ -3928,64 +3928,39 @@ __global__ __launch_bounds__(T, waves_per_eu<T>()) void k_debug_scalings(int ps,
 
 // ---- launchers (called from api.cpp) ----
 #ifndef EICOS_ISA_PROBE // (tools/dev/isa_probe.sh compiles single stage functions without the kernel instantiations)
-#if EICOS_LDSRES
-template <class F> static auto dispatch_solve(int threads, int nlds, int idx16, F &&f) {
-    auto byT = [&](auto tc) {
-        constexpr int T = decltype(tc)::value;
-        if (idx16) return nlds >= 2 ? f((const void *)k_solve<T, 2, true>) : f((const void *)k_solve<T, 1, true>);
-        return nlds >= 2 ? f((const void *)k_solve<T, 2, false>) : f((const void *)k_solve<T, 1, false>);
+// The k_solve instantiations of this translation unit: ONE workgroup size (the LDS-resident build 128, kernels_t128.o / _t512.o / _ubl*.o theirs,
+// kernels.o / kernels_w2.o 256), 16- or 32-bit indices, and two, one or -- except LDS-resident and U-in-LDS: api.cpp never asks -- no vector in LDS.
+constexpr int SOLVE_T = EICOS_LDSRES ? 128 : EICOS_TSPLIT ? EICOS_TSPLIT : EICOS_UBL ? EICOS_UBL : 256;
+template <class F> static auto dispatch_solve(int nlds, int idx16, F &&f) {
+    auto byI = [&](auto ic) {
+        constexpr bool I16 = decltype(ic)::value;
+        if (nlds >= 2) return f((const void *)k_solve<SOLVE_T, 2, I16>);
+        if constexpr (EICOS_LDSRES != 0 || EICOS_UBL != 0) return f((const void *)k_solve<SOLVE_T, 1, I16>);
+        else return nlds == 1 ? f((const void *)k_solve<SOLVE_T, 1, I16>) : f((const void *)k_solve<SOLVE_T, 0, I16>);
     };
-    return byT(std::integral_constant<int, 128>{}); // (small patterns run 128 threads)
+    return idx16 ? byI(std::true_type{}) : byI(std::false_type{});
 }
-#else
-template <class F> static auto dispatch_solve(int threads, int nlds, int idx16, F &&f) {
-    auto byT = [&](auto tc) {
-        constexpr int T = decltype(tc)::value;
-        if (idx16) {
-            if (nlds >= 2) return f((const void *)k_solve<T, 2, true>);
-            if (nlds == 1 || EICOS_UBL != 0) return f((const void *)k_solve<T, 1, true>); // (U-in-LDS builds: api.cpp never asks for nlds = 0)
-#if !EICOS_UBL
-            return f((const void *)k_solve<T, 0, true>);
-#endif
-        }
-        if (nlds >= 2) return f((const void *)k_solve<T, 2, false>);
-        if (nlds == 1 || EICOS_UBL != 0) return f((const void *)k_solve<T, 1, false>);
-#if !EICOS_UBL
-        return f((const void *)k_solve<T, 0, false>);
-#endif
-    };
-#if EICOS_TSPLIT
-    return byT(std::integral_constant<int, EICOS_TSPLIT>{}); // (this build exists for one workgroup size only)
-#elif EICOS_UBL
-    return byT(std::integral_constant<int, EICOS_UBL>{});
-#else
-    return byT(std::integral_constant<int, 256>{}); // (kernels.o / kernels_w2.o: 256 threads; 128 and 512 live in kernels_t128.o / kernels_t512.o)
-#endif
-}
-#endif
-hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds,
-                        int idx16, int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg_in, size_t dyn_lds, hipStream_t st, const UpdArgs *upd_in) {
-    UpdArgs upd = upd_in ? *upd_in : UpdArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    SolveCfg cfg = cfg_in; // (by value into the kernel arguments: a launch in flight keeps the settings it was enqueued with)
-    if (upd.on && nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector; both modes live in the NLDS >= 1 kernels)
-    if (B <= 0) return hipSuccess;
-    hipError_t e = hipMemsetAsync(queue, 0, sizeof(int), st); // group queue of this launch
+static hipError_t launch_solve(const SolveLaunch &launch, hipStream_t st, const UpdArgs &step) {
+    // (copies: hipLaunchKernel takes non-const pointers; cfg travels by value, so a launch in flight keeps the settings it was enqueued with)
+    SolveLaunch L = launch; UpdArgs upd = step;
+    if (upd.on && L.nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector; both modes live in the NLDS >= 1 kernels)
+    if (L.B <= 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(L.queue, 0, sizeof(int), st); // group queue of this launch
     if (e != hipSuccess) return e;
     // Longest-first order (by the work of the previous solve) whenever a CU gets more than one workgroup: for a batch larger
     // than the grid it is the queue's processing order; for a one-round batch it makes the dispatcher pair a long instance
     // with a short one on each CU, which then finishes the long one alone (+7 % at batch 512 on 256 CUs).
-    if (B <= order_min) order = nullptr; // at most one instance per CU: identity
+    if (L.B <= L.order_min) L.order = nullptr; // at most one instance per CU: identity
     else {
         // (EICOS_SNAKE=0 under EICOS_EXPERIMENT=1: plain descending order, for A/B runs.  Laying out the first round of a MULTI-round launch the
         // same way measured +-0: profiles/r05_log_snake_order.log)
         static const int snake_on = [] { const char *e = getenv("EICOS_EXPERIMENT"), *k = getenv("EICOS_SNAKE"); return !(e && k && !strcmp(e, "1") && !strcmp(k, "0")); }();
-        hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, st, ps, inst, B, order, (snake_on && B <= grid) ? B : 0, order_min);
+        hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, st, L.ps, L.inst, L.B, L.order, (snake_on && L.B <= L.grid) ? L.B : 0, L.order_min);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    return dispatch_solve(threads, nlds, idx16, [&](const void *fn) {
-        void *args[] = {(void *)&ps, (void *)&inst, (void *)&work, (void *)&B, (void *)&queue, (void *)&order, (void *)&warm, (void *)&dyn_delta,
-                        (void *)&dyn_eps, (void *)&cfg, (void *)&upd};
-        return hipLaunchKernel(fn, dim3(grid), dim3(threads), args, dyn_lds, st);
+    return dispatch_solve(L.nlds, L.idx16, [&](const void *fn) {
+        void *args[] = {&L.ps, &L.inst, &L.work, &L.B, &L.queue, &L.order, &L.warm, &L.dyn_delta, &L.dyn_eps, &L.cfg, &upd};
+        return hipLaunchKernel(fn, dim3(L.grid), dim3(L.threads), args, L.dyn_lds, st);
     });
 }
 #if EICOS_MAIN_BUILD
@@ -4059,45 +4034,50 @@ hipError_t update_set_max_lds() {
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute((const void *)k_update_lds<512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
 }
-hipError_t launch_debug_factor(int ps, double *inst, double *work, int i, int threads, size_t dyn_lds, hipStream_t st) {
-    auto big = [&](const void *fn) { if (dyn_lds > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds); };
-    switch (threads) { // the factor program is built for the handle's workgroup size
-    case 128: big((const void *)k_debug_factor<128>); hipLaunchKernelGGL(k_debug_factor<128>, dim3(1), dim3(128), dyn_lds, st, ps, inst, work, i); break;
-    case 256: big((const void *)k_debug_factor<256>); hipLaunchKernelGGL(k_debug_factor<256>, dim3(1), dim3(256), dyn_lds, st, ps, inst, work, i); break;
-    case 512: big((const void *)k_debug_factor<512>); hipLaunchKernelGGL(k_debug_factor<512>, dim3(1), dim3(512), dyn_lds, st, ps, inst, work, i); break;
+// f(integral_constant<int, T>) for T = a handle's workgroup size (the factor program is built for it), then the launch's error
+template <class F> static hipError_t by_threads(int threads, F &&f) {
+    switch (threads) {
+    case 128: f(std::integral_constant<int, 128>{}); break;
+    case 256: f(std::integral_constant<int, 256>{}); break;
+    case 512: f(std::integral_constant<int, 512>{}); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+hipError_t launch_debug_factor(int ps, double *inst, double *work, int i, int threads, size_t dyn_lds, hipStream_t st) {
+    return by_threads(threads, [&](auto tc) {
+        constexpr int T = decltype(tc)::value;
+        if (dyn_lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)k_debug_factor<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds);
+        hipLaunchKernelGGL(k_debug_factor<T>, dim3(1), dim3(T), dyn_lds, st, ps, inst, work, i);
+    });
 }
 hipError_t launch_debug_scalings(int ps, double *inst, double *work, int i, int *ok, int threads, hipStream_t st) {
-    switch (threads) {
-    case 128: hipLaunchKernelGGL(k_debug_scalings<128>, dim3(1), dim3(128), 0, st, ps, inst, work, i, ok); break;
-    case 256: hipLaunchKernelGGL(k_debug_scalings<256>, dim3(1), dim3(256), 0, st, ps, inst, work, i, ok); break;
-    case 512: hipLaunchKernelGGL(k_debug_scalings<512>, dim3(1), dim3(512), 0, st, ps, inst, work, i, ok); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return by_threads(threads, [&](auto tc) {
+        constexpr int T = decltype(tc)::value;
+        hipLaunchKernelGGL(k_debug_scalings<T>, dim3(1), dim3(T), 0, st, ps, inst, work, i, ok);
+    });
 }
 #endif // EICOS_MAIN_BUILD
-hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu) {
-    return dispatch_solve(threads, nlds, idx16, [&](const void *fn) {
+static hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu) {
+    return dispatch_solve(nlds, idx16, [&](const void *fn) {
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, threads, dyn_lds);
     });
 }
-hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds) {
+static hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds) {
     if (dyn_lds == 0) return hipSuccess;
     // The attribute belongs to the kernel, not to a handle: several live handles (other patterns, the shards of an eicos_multi on one
     // device) launch the same instantiation with different dynamic LDS sizes, so it is always raised to the device's ceiling (160 KB
     // minus the 4 KB budgeted for the static block) and never lowered; the size a launch really uses is its own dyn_lds.
-    return dispatch_solve(threads, nlds, idx16, [&](const void *fn) {
+    return dispatch_solve(nlds, idx16, [&](const void *fn) {
         return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
     });
 }
 
-hipError_t upload_pattern(int ps, const DevPat &P) {
+static hipError_t upload_pattern(int ps, const DevPat &P) {
     if (ps < 0 || ps >= MAX_PATTERNS) return hipErrorInvalidValue;
     return hipMemcpyToSymbol(HIP_SYMBOL(c_pat), &P, sizeof(DevPat), (size_t)ps * sizeof(DevPat), hipMemcpyHostToDevice);
 }
+SolveBuild solve_entries() { return {launch_solve, solve_occupancy, solve_set_max_lds, upload_pattern}; } // (launch.hpp: one per build namespace)
 #endif // EICOS_ISA_PROBE
 #if EICOS_LDSRES
 } // namespace ldsres

@@ -37,27 +37,50 @@ struct MatrixMapDev { int k; AffineDev g[2]; };
 // Shift map (eicos_batch_set_shift_map): the warm-start vectors x, y, z, s of an instance through one square affine map each -- g[0..3] with
 // n, p, m, m rows and as many columns, CSR, in device memory, shared by every instance; base == NULL: that vector is not shifted
 struct ShiftMapDev { AffineDev g[4]; };
-struct UpdArgs {
-    const double *G, *A, *c, *h, *b; double *x; int on; const unsigned *flags; int chunk; unsigned seq; int *err;
-    const ParamMapDev *pmap; const OutMapDev *omap; const double *theta; double *u; // (device copies of the handle's maps)
-    const RolloutDev *roll;
-    const MatrixMapDev *mmap; // UPD_PARAM / UPD_ROLL with a matrix map: the step is a full updateData from theta (kernels.hip: matrix_param_instance)
-    // Every mode, 0 included: a solve that warm-starts an instance first takes its x, y, z, s through this map (kernels.hip: shift_instance);
-    // NULL: no shift map.  One more word of kernel arguments, and one pointer test per instance.
-    const ShiftMapDev *smap;
-    // Every mode, 0 included: the handle's shared-values word (eicos_batch_shared_values), read by thread 0 once per instance before the
+struct UpdArgs { // UpdArgs{} = the neutral launch: no fused step, no maps; every builder assigns fields by name
+    // inputs: rows of the five updateData arrays, [batch][...]
+    const double *G = nullptr, *A = nullptr, *c = nullptr, *h = nullptr, *b = nullptr;
+    // outputs: x [batch][n], and the mode (UPD_*, 0: no fused step)
+    double *x = nullptr; int on = 0;
+    // staging: ready flags of the chunks (NULL: nothing is staged), instances per chunk, the flag value of this launch, the time-out word
+    const unsigned *flags = nullptr; int chunk = 1; unsigned seq = 0; int *err = nullptr;
+    // maps (device copies of the handle's descriptors) with the input theta and the output u of the parametric step
+    const ParamMapDev *pmap = nullptr; const OutMapDev *omap = nullptr; const double *theta = nullptr; double *u = nullptr;
+    const RolloutDev *roll = nullptr;
+    const MatrixMapDev *mmap = nullptr; // UPD_PARAM / UPD_ROLL with a matrix map: the step is a full updateData from theta (kernels.hip: matrix_param_instance)
+    // every-launch fields, mode 0 included.  smap: a solve that warm-starts an instance first takes its x, y, z, s through this map
+    // (kernels.hip: shift_instance); NULL: no shift map.  One more word of kernel arguments, and one pointer test per instance.
+    const ShiftMapDev *smap = nullptr;
+    // shared: the handle's shared-values word (eicos_batch_shared_values), read by thread 0 once per instance before the
     // instance's solve.  -1: every instance streams the product values (the sliced-ELL copies of [A' G'], A, G and the G tiles) of its own
     // slab; r >= 0: every instance of the batch holds the bits of instance r there, and all of them stream instance r's.  NULL counts as -1.
-    const int *shared;
+    const int *shared = nullptr;
 };
+// the fused step writes matrix values of its instances: full updateData; a parametric step or a rollout under a matrix map (the host then
+// drops the handle's shared values in front of the launch: api.cpp, shared_clear)
+inline bool writes_matrix_values(const UpdArgs &a) { return a.on == UPD_FULL || ((a.on == UPD_PARAM || a.on == UPD_ROLL) && a.mmap); }
 // Runtime solver settings (eicos_batch_set_settings; eicos_settings of include/eicos_amd.h, same fields and defaults): one by-value argument
 // of k_solve, copied into LDS by thread 0 (kernels.hip: Sh::cfg) before the workgroup's first instance, where the stage functions read
 // it -- the exit test and the two infeasibility-residual comparisons (tolerances), the iteration cap, and kkt_solve's refinement stop test
 // (linsysacc, irerrfact, nitref).  Every other constant of the reference's Settings stays compile-time (kernels.hip).
 struct SolveCfg { double feastol, abstol, reltol, feastol_inacc, abstol_inacc, reltol_inacc, linsysacc, irerrfact; int iter_max, nitref; };
 constexpr SolveCfg solve_cfg_default() { return {1e-8, 1e-8, 1e-8, 1e-4, 5e-5, 5e-5, 1e-14, 6., 100, 9}; }
-hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
+// One k_solve launch of a handle, as the host describes it: the pattern slot, the slabs and the queue, the launch shape, and what travels
+// to the kernel by value.  order = the longest-first order array (used when B > order_min); cfg is copied into the kernel arguments, so
+// a launch in flight keeps the settings it was enqueued with.
+struct SolveLaunch {
+    int ps; double *inst, *work; int B; int *queue, *order;
+    int grid, threads, nlds, idx16, order_min;
+    double warm, dyn_delta, dyn_eps; SolveCfg cfg; size_t dyn_lds;
+};
+// One k_solve build = these four entry points.  launch always receives an UpdArgs: UpdArgs{} when no step is fused into it.
+struct SolveBuild {
+    hipError_t (*launch)(const SolveLaunch &L, hipStream_t st, const UpdArgs &upd);
+    hipError_t (*occupancy)(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
+    hipError_t (*set_max_lds)(int threads, int nlds, int idx16, size_t dyn_lds);
+    hipError_t (*upload)(int ps, const DevPat &P);
+    bool operator==(const SolveBuild &o) const { return launch == o.launch; }
+};
 // shared != NULL (only the launch that covers the whole batch, first = 0, with every matrix the pattern has given): the handle's shared-values
 // word, which the host has set to 0 on `st` in front of this launch -- a workgroup whose rows of Gpr / Apr differ from row 0 in any bit
 // stores -1 (kernels.hip: update_instance)
@@ -95,74 +118,26 @@ hipError_t launch_plant(int ps, const double *inst, int first, int count, const 
 hipError_t update_set_max_lds();
 hipError_t launch_debug_factor(int ps, double *inst, double *work, int i, int threads, size_t dyn_lds, hipStream_t st);
 hipError_t launch_debug_scalings(int ps, double *inst, double *work, int i, int *ok, int threads, hipStream_t st);
-hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
-hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
-hipError_t upload_pattern(int ps, const DevPat &P);
 int max_patterns();
-// LDS-resident variant of k_solve (kernels_ldsres.hip = kernels.hip compiled with EICOS_LDSRES): same arguments
-namespace ldsres {
-hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
-hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
-hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
-hipError_t upload_pattern(int ps, const DevPat &P);
-} // namespace ldsres
-// 256-thread k_solve with the register budget of two waves per SIMD (kernels_w2.hip = kernels.hip compiled with EICOS_W2)
-namespace w2 {
-hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
-hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
-hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
-hipError_t upload_pattern(int ps, const DevPat &P);
-} // namespace w2
-// the 128- and 512-thread k_solve of the default build, in their own translation units (kernels_t128.hip / kernels_t512.hip = kernels.hip
-// compiled with EICOS_TSPLIT): the default namespace keeps the 256-thread one
-namespace t128 {
-hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
-hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
-hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
-hipError_t upload_pattern(int ps, const DevPat &P);
-} // namespace t128
-namespace t512 {
-hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
-hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
-hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
-hipError_t upload_pattern(int ps, const DevPat &P);
-} // namespace t512
-// the 256- / 512-thread k_solve with the factor operand array U resident in LDS (kernels_ubl256.hip / kernels_ubl512.hip = kernels.hip compiled
-// with EICOS_UBL): launches of one workgroup per CU whose U fits the idle LDS
-namespace ubl256 {
-hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
-hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
-hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
-hipError_t upload_pattern(int ps, const DevPat &P);
-} // namespace ubl256
-namespace ubl512 {
-hipError_t launch_solve(int ps, double *inst, double *work, int B, int *queue, int *order, int grid, int threads, int nlds, int idx16,
-                        int order_min, double warm, double dyn_delta, double dyn_eps, const SolveCfg &cfg, size_t dyn_lds, hipStream_t st, const UpdArgs *upd = nullptr);
-hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
-hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds);
-hipError_t upload_pattern(int ps, const DevPat &P);
-} // namespace ubl512
-// one k_solve build = these four entry points
-struct SolveBuild {
-    decltype(&launch_solve) launch;
-    decltype(&solve_occupancy) occupancy;
-    decltype(&solve_set_max_lds) set_max_lds;
-    decltype(&upload_pattern) upload;
-};
+// The seven compilations of kernels.hip (the note at its top) export their build through one function each: the default namespace (256
+// threads; updateData and the debug kernels live here too), the LDS-resident k_solve (128), the 256-thread k_solve at two waves per SIMD, the
+// 128- / 512-thread k_solve of the default build, the 256- / 512-thread k_solve with U in LDS (one workgroup per CU whose U fits the idle LDS).
+SolveBuild solve_entries();
+namespace ldsres { SolveBuild solve_entries(); }
+namespace w2 { SolveBuild solve_entries(); }
+namespace t128 { SolveBuild solve_entries(); }
+namespace t512 { SolveBuild solve_entries(); }
+namespace ubl256 { SolveBuild solve_entries(); }
+namespace ubl512 { SolveBuild solve_entries(); }
 // the build a handle's solves run: U in LDS (one workgroup per CU, 256 / 512 threads), LDS-resident (128 threads), two-waves-per-SIMD (256 threads),
 // or the default one of its workgroup size
 inline SolveBuild solve_build(int threads, bool ldsres, bool w2, bool ubl = false) {
-    if (ubl && threads == 256) return {ubl256::launch_solve, ubl256::solve_occupancy, ubl256::solve_set_max_lds, ubl256::upload_pattern};
-    if (ubl && threads == 512) return {ubl512::launch_solve, ubl512::solve_occupancy, ubl512::solve_set_max_lds, ubl512::upload_pattern};
-    if (ldsres) return {ldsres::launch_solve, ldsres::solve_occupancy, ldsres::solve_set_max_lds, ldsres::upload_pattern};
-    if (w2) return {w2::launch_solve, w2::solve_occupancy, w2::solve_set_max_lds, w2::upload_pattern};
-    if (threads == 128) return {t128::launch_solve, t128::solve_occupancy, t128::solve_set_max_lds, t128::upload_pattern};
-    if (threads == 512) return {t512::launch_solve, t512::solve_occupancy, t512::solve_set_max_lds, t512::upload_pattern};
-    return {launch_solve, solve_occupancy, solve_set_max_lds, upload_pattern};
+    if (ubl && threads == 256) return ubl256::solve_entries();
+    if (ubl && threads == 512) return ubl512::solve_entries();
+    if (ldsres) return ldsres::solve_entries();
+    if (w2) return w2::solve_entries();
+    if (threads == 128) return t128::solve_entries();
+    if (threads == 512) return t512::solve_entries();
+    return solve_entries();
 }
 } // namespace eicos
