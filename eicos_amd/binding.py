@@ -18,6 +18,13 @@ _LIB = None
 EXIT_NAMES = {0: "optimal", 1: "primal_infeasible", 2: "dual_infeasible", -1: "maxit", -2: "numerics",
               -3: "outcone", -7: "fatal", 10: "close_to_optimal", 11: "close_to_primal_infeasible",
               12: "close_to_dual_infeasible", -87: "not_converged_yet"}
+# exit classes (EICOS_SEL_* of include/eicos_amd.h): the mask bits of select() / solve_where(); exit_class(code, n_factor) gives an
+# instance's bit.  UNSOLVED (n_factor == 0: never solved, never given a starting point) takes precedence over the code.
+SEL_OPTIMAL, SEL_PINF, SEL_DINF, SEL_OPTIMAL_INACC, SEL_PINF_INACC, SEL_DINF_INACC = (1 << k for k in range(6))
+SEL_MAXIT, SEL_NUMERICS, SEL_OUTCONE, SEL_FATAL, SEL_OTHER, SEL_UNSOLVED = (1 << k for k in range(6, 12))
+SEL_FAILED = SEL_MAXIT | SEL_NUMERICS | SEL_OUTCONE | SEL_FATAL
+SEL_ALL = (1 << 12) - 1
+SEL_NOT_OPTIMAL = SEL_ALL & ~SEL_OPTIMAL
 
 
 class Info(C.Structure):
@@ -176,6 +183,16 @@ def _lib():
             for f in ("set_settings", "get_settings"):
                 getattr(L, "eicos_batch_" + f).argtypes = getattr(L, "eicos_multi_" + f).argtypes = [vp, sp]
                 getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+        if hasattr(L, "eicos_batch_solve_subset"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            L.eicos_exit_class.argtypes = [C.c_int, C.c_int]
+            L.eicos_exit_class.restype = C.c_int
+            L.eicos_batch_select.argtypes = L.eicos_multi_select.argtypes = [vp, C.c_uint, ip, ip]
+            L.eicos_batch_solve_subset_async.argtypes = L.eicos_multi_solve_subset_async.argtypes = [vp, ip, C.c_int]
+            L.eicos_batch_solve_subset.argtypes = L.eicos_multi_solve_subset.argtypes = [vp, ip, C.c_int, ip]
+            L.eicos_batch_solve_where.argtypes = L.eicos_multi_solve_where.argtypes = [vp, C.c_uint, ip, ip, ip]
+            L.eicos_batch_gather.argtypes = L.eicos_multi_gather.argtypes = [vp, ip, C.c_int, dp, dp, dp, dp, C.POINTER(Info)]
+            for f in ("select", "solve_subset_async", "solve_subset", "solve_where", "gather"):
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -240,6 +257,12 @@ def default_settings() -> dict:
     st = Settings()
     _lib().eicos_settings_default(C.byref(st))
     return st.asdict()
+
+
+def exit_class(exitcode: int, n_factor: int = 1) -> int:
+    """The SEL_* bit of an instance with this exit code and n_factor (eicos_exit_class: the function the selection kernel runs on the
+    GPU); needs no handle and no GPU."""
+    return int(_lib().eicos_exit_class(int(exitcode), int(n_factor)))
 
 
 def device_count() -> int:
@@ -742,6 +765,52 @@ class _Solver:
 
     def sync(self):
         self._call("sync")
+
+    # ---- subset solves: by index list or by exit class (include/eicos_amd.h: eicos_batch_solve_subset / _solve_where) ----
+    @staticmethod
+    def _index_list(indices):
+        """indices as a contiguous int32 vector (the library checks range and duplicates); a 1-element dummy keeps the pointer valid."""
+        idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        return idx, (_ip(idx) if idx.size else _ip(np.zeros(1, np.int32)))
+
+    def select(self, mask: int):
+        """The ascending ids of the instances whose exit class is in `mask` (an OR of SEL_* bits), found by the selection kernel on the
+        GPU: only the count and the ids travel."""
+        ids, count = np.zeros(self.batch, np.int32), C.c_int(0)
+        self._call("select", C.c_uint(int(mask)), _ip(ids), C.byref(count))
+        return ids[: count.value].copy()
+
+    def solve_subset(self, indices):
+        """One solve launch over the instances `indices` (each at most once) instead of the whole batch: they end, bit for bit, as
+        solve() would leave them, every other instance keeps its state and its info record.  Returns their exit codes in list order;
+        an empty list launches nothing."""
+        idx, ptr = self._index_list(indices)
+        codes = np.zeros(idx.size, np.int32)
+        self._call("solve_subset", ptr, int(idx.size), _ip(codes) if idx.size else None)
+        return codes
+
+    def solve_subset_async(self, indices):
+        """solve_subset without waiting for the GPU (sync() waits)."""
+        idx, ptr = self._index_list(indices)
+        self._call("solve_subset_async", ptr, int(idx.size))
+
+    def solve_where(self, mask: int):
+        """select(mask) + solve_subset with the id list used in place on the GPU: (ids ascending, their exit codes).  A class nobody is
+        in launches nothing and returns two empty arrays."""
+        ids, codes, count = np.zeros(self.batch, np.int32), np.zeros(self.batch, np.int32), C.c_int(0)
+        self._call("solve_where", C.c_uint(int(mask)), _ip(ids), C.byref(count), _ip(codes))
+        return ids[: count.value].copy(), codes[: count.value].copy()
+
+    def gather(self, indices):
+        """The rows of the instances `indices`, in list order, packed on the GPU and fetched with one copy: a dict of x [count, n],
+        y [count, p], z, s [count, m] -- the rows solution() / duals() return -- and info, a dict of arrays like info_arrays()."""
+        idx, ptr = self._index_list(indices)
+        pat, k = self.pat, int(idx.size)
+        x, y, z, s = np.zeros((k, pat.n)), np.zeros((k, pat.p)), np.zeros((k, pat.m)), np.zeros((k, pat.m))
+        arr = (Info * max(k, 1))()
+        self._call("gather", ptr, k, *[_dp(a) if a.size else None for a in (x, y, z, s)], arr)
+        raw = np.frombuffer(arr, dtype=np.dtype([(f, "f8" if t is C.c_double else "i4") for f, t in Info._fields_]))[:k]
+        return {"x": x, "y": y, "z": z, "s": s, "info": {f: raw[f].copy() for f in raw.dtype.names}}
 
     def set_warm_start(self, shift: float):
         """shift > 0: re-solves start from the previous solution (not in the reference; see include/eicos_amd.h)."""

@@ -31,6 +31,7 @@
 #include "internal.hpp"
 #include "affine_pack.hpp"
 #include "fused_fit.hpp"
+#include "exit_class.hpp"
 
 using namespace eicos;
 // Workgroups per CU for a batch, at most `max_r`: the cheapest estimate of the launch's duration wins.
@@ -77,6 +78,7 @@ struct eicos_batch {
     int batch = 0, device = 0, threads = 256, grid = 0, upd_grid = 0;
     int order_min = 0;        // batches up to this size (one instance per CU) are solved in identity order, larger ones longest-first
     bool last_ordered = false; // how the most recent solve was launched (eicos_debug_trace)
+    bool last_subset = false; int last_count = 0; // ... whether it took a chosen subset (eicos_batch_solve_subset / _solve_where), and how many instances
     size_t upd_lds = 0;       // > 0: updateData runs the entry-parallel kernel with this much dynamic LDS (values + maxima)
     int upd_vals_lds = 1;     // 1: its working copy of the values is in LDS too; 0: streamed in place in the instance slab
     int *d_pattern = nullptr;
@@ -88,7 +90,11 @@ struct eicos_batch {
     int ldsres = 0;           // 1: solves run the LDS-resident kernel (ldsres::solve_entries), slabs copied in and out per instance
     size_t pattern_ints = 0;
     double *d_inst = nullptr, *d_work = nullptr, *d_scratch = nullptr;
-    int *d_queue = nullptr; // instance queue of the solve kernel (reset per launch)
+    int *d_queue = nullptr; // instance queue of the solve kernel (reset per launch): [16-int header | launch order [batch] | candidates of a subset launch [batch]]
+    // subset calls: a host index list travels through one pinned buffer of `batch` ints (sub_ev: its last upload); the row gather packs the
+    // chosen instances' rows into d_gather = [ids | rows], grown on demand
+    int *sub_pin = nullptr; hipEvent_t sub_ev = nullptr; bool sub_busy = false;
+    char *d_gather = nullptr; size_t gather_bytes = 0;
     double *d_stage = nullptr; size_t stage_doubles = 0; // peer-copy updateData without peer access: persistent staging buffer (one chunk)
     // host-pointer updateData / results (the reference's real signature: updateData(double *...), solution() on the host): two PINNED
     // bounce buffers (hipHostMalloc).  Input chunk k is copied into pin[k & 1] by the host while the GPU's updateData kernel reads chunk
@@ -953,7 +959,7 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
         HIP_TRY(hipMemset(h->d_inst, 0, (size_t)batch * D.inst_stride * sizeof(double)));
         HIP_TRY(hipMalloc(&h->d_work, (size_t)h->grid * D.work_stride * sizeof(double)));
         HIP_TRY(hipMemset(h->d_work, 0, (size_t)h->grid * D.work_stride * sizeof(double)));
-        HIP_TRY(hipMalloc(&h->d_queue, (16 + (size_t)batch) * sizeof(int))); // [0] queue head, [16..] longest-first order
+        HIP_TRY(hipMalloc(&h->d_queue, (16 + 2 * (size_t)batch) * sizeof(int))); // [0] queue head, [1] the count of a selection, [16..] launch order, [16 + batch..] candidates
         HIP_TRY(hipMalloc(&h->d_shared, 64));
         HIP_TRY(hipMemset(h->d_shared, 0xFF, 64)); // (-1: nothing shared)
         h->shared_on = !h->ldsres && env_knob("EICOS_SHARED_VALUES", 1, 0, 1) != 0;
@@ -1088,8 +1094,11 @@ int eicos_batch_destroy(eicos_batch *h) {
     for (int i = 0; i < eicos_batch::EV_RING; i++)
         for (hipEvent_t e : {h->ring_s[i][0], h->ring_s[i][1], h->ring_u[i][0], h->ring_u[i][1]}) if (e) (void)hipEventDestroy(e);
     for (void *ptr : {(void *)h->d_pattern, (void *)h->d_inst, (void *)h->d_work, (void *)h->d_queue, (void *)h->d_shared, (void *)h->d_scratch,
-                      (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out, h->d_plant, h->d_roll, h->d_mat, (void *)h->d_mstage, h->d_shift})
+                      (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out, h->d_plant, h->d_roll, h->d_mat, (void *)h->d_mstage, h->d_shift,
+                      (void *)h->d_gather})
         if (ptr) (void)hipFree(ptr);
+    if (h->sub_pin) (void)hipHostFree(h->sub_pin);
+    if (h->sub_ev) (void)hipEventDestroy(h->sub_ev);
     for (int i = 0; i < 2; i++) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     if (h->stage_pin) (void)hipHostFree(h->stage_pin);
     if (h->stage_flags) (void)hipHostFree(h->stage_flags);
@@ -1799,17 +1808,21 @@ int eicos_batch_outputs_device(eicos_batch *h, int first, int count, double *du)
     return rc != EICOS_OK ? rc : outputs_to(h, first, count, du, MEM_DEVICE);
 }
 
-// the launch record of a handle's solves (launch.hpp)
-static SolveLaunch solve_launch(const eicos_batch *h) {
+// the candidate ids of a subset launch, in device memory behind the launch order
+static int *subset_ids(const eicos_batch *h) { return h->d_queue + 16 + h->batch; }
+// the launch record of a handle's solves (launch.hpp); subset >= 0: a launch over the `subset` ids in subset_ids(h) instead of the batch
+static SolveLaunch solve_launch(const eicos_batch *h, int subset) {
     SolveLaunch L{};
     L.ps = h->pslot; L.inst = h->d_inst; L.work = h->d_work; L.B = h->batch; L.queue = h->d_queue; L.order = h->d_queue + 16;
     L.grid = h->grid; L.threads = h->threads; L.nlds = h->nlds; L.idx16 = h->dp.idx16; L.order_min = h->order_min;
     L.warm = h->warm_shift; L.dyn_delta = h->dyn_delta; L.dyn_eps = h->dyn_eps; L.cfg = h->cfg; L.dyn_lds = h->dyn_lds;
+    L.batch = h->batch; L.full_grid = h->grid;
+    if (subset >= 0) { L.list = subset_ids(h); L.B = subset; L.grid = std::min(h->grid, subset); }
     return L;
 }
 // The one place that enqueues k_solve on the handle's stream.  step: the update fused into this launch (update_solve, the rollout), NULL
-// for a plain solve; it lives for this call only.
-static int enqueue_solve(eicos_batch *h, const UpdArgs *step) {
+// for a plain solve; it lives for this call only.  subset >= 0: the launch takes that many chosen instances (solve_launch).
+static int enqueue_solve(eicos_batch *h, const UpdArgs *step, int subset = -1) {
     HIP_TRY(hipSetDevice(h->device));
     { const int rc = next_events(h->ring_s, h->n_solve_rec, h->ev_s0, h->ev_s1); if (rc != EICOS_OK) return rc; }
     h->ring_step0[(h->n_solve_rec - 1) % eicos_batch::EV_RING] = h->update_timed ? h->ev_u0 : h->ev_s0;
@@ -1819,10 +1832,11 @@ static int enqueue_solve(eicos_batch *h, const UpdArgs *step) {
     args.smap = static_cast<const ShiftMapDev *>(h->d_shift);
     if (writes_matrix_values(args)) { const int rc = shared_clear(h); if (rc != EICOS_OK) return rc; } // (the step drops the shared values)
     args.shared = h->shared_on ? h->d_shared : nullptr;
-    HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(solve_launch(h), h->stream, args));
+    HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(solve_launch(h, subset), h->stream, args));
     HIP_TRY(hipEventRecord(h->ev_s1, h->stream));
     h->solve_timed = true;
-    h->last_ordered = h->batch > h->order_min;
+    h->last_subset = subset >= 0; h->last_count = subset >= 0 ? subset : h->batch;
+    h->last_ordered = h->last_subset || h->batch > h->order_min; // (a subset launch always goes through the order array)
     return EICOS_OK;
 }
 
@@ -1876,16 +1890,8 @@ static int fetch_rows(eicos_batch *h, double *dst, int off, int width) {
     return fetch_strided(h, dst, h->d_inst + off, h->dp.inst_stride * sizeof(double), width, h->batch);
 }
 
-int eicos_batch_info(eicos_batch *h, eicos_info *info) {
-    if (!h || !info) return fail(EICOS_E_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    std::vector<DevInfo> tmp(h->batch);
-    HIP_TRY(hipMemcpy2D(tmp.data(), sizeof(DevInfo), h->d_inst + h->dp.i_info, h->dp.inst_stride * sizeof(double),
-                        sizeof(DevInfo), (size_t)h->batch, hipMemcpyDeviceToHost));
-    for (int i = 0; i < h->batch; i++) {
-        const DevInfo &d = tmp[i];
-        eicos_info &o = info[i];
+// the public form of an instance's info record
+static void info_from(const DevInfo &d, eicos_info &o) {
         o.pcost = d.pcost; o.dcost = d.dcost; o.pres = d.pres; o.dres = d.dres; o.gap = d.gap; o.relgap = d.relgap;
         o.sigma = d.sigma; o.mu = d.mu; o.step = d.step; o.step_aff = d.step_aff; o.kapovert = d.kapovert;
         o.pinfres = d.pinfres; o.dinfres = d.dinfres; o.tau = d.tau; o.kap = d.kap;
@@ -1893,7 +1899,16 @@ int eicos_batch_info(eicos_batch *h, eicos_info *info) {
         o.pinf = d.pinf; o.dinf = d.dinf; o.iter = d.iter; o.nitref1 = d.nitref1; o.nitref2 = d.nitref2;
         o.nitref3 = d.nitref3; o.exitcode = d.exitcode; o.n_factor = d.n_factor; o.n_ldlsolve = d.n_ldlsolve;
         o.n_sweep = d.n_sweep; o.reserved_ = 0; o.solve_us = d.solve_us;
-    }
+}
+
+int eicos_batch_info(eicos_batch *h, eicos_info *info) {
+    if (!h || !info) return fail(EICOS_E_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::vector<DevInfo> tmp(h->batch);
+    HIP_TRY(hipMemcpy2D(tmp.data(), sizeof(DevInfo), h->d_inst + h->dp.i_info, h->dp.inst_stride * sizeof(double),
+                        sizeof(DevInfo), (size_t)h->batch, hipMemcpyDeviceToHost));
+    for (int i = 0; i < h->batch; i++) info_from(tmp[i], info[i]);
     return EICOS_OK;
 }
 
@@ -1912,6 +1927,135 @@ int eicos_batch_solve(eicos_batch *h, int *exitcodes) {
     rc = eicos_batch_sync(h);
     if (rc != EICOS_OK) return rc;
     return exit_codes(h, exitcodes);
+}
+
+// ---- subset solves: by index list or by exit class (include/eicos_amd.h) ----
+// A subset solve is an ordinary launch (enqueue_solve) whose order array the selection kernel fills from subset_ids(h); the exit codes
+// and rows of chosen instances come back through the row-gather kernel and ONE copy of its compact buffer (fetch_strided).
+int eicos_exit_class(int exitcode, int n_factor) { return (int)exit_class(exitcode, n_factor); }
+
+// the checks every subset call makes before anything is enqueued: a refused list or mask changes no state
+static int take_index_list(const eicos_batch *h, const int *idx, int count, const char *who) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    const std::string msg = index_list_fault(idx, count, h->batch);
+    return msg.empty() ? EICOS_OK : fail(EICOS_E_INVALID, std::string(who) + ": " + msg);
+}
+static int take_class_mask(const eicos_batch *h, unsigned mask, const char *who) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    const std::string msg = class_mask_fault(mask);
+    return msg.empty() ? EICOS_OK : fail(EICOS_E_INVALID, std::string(who) + ": " + msg);
+}
+// `count` validated ids from the host into device memory at dst, on the handle's stream, through the pinned list buffer
+static int upload_ids(eicos_batch *h, const int *idx, int count, int *dst) {
+    if (!h->sub_pin) HIP_TRY(hipHostMalloc((void **)&h->sub_pin, (size_t)h->batch * sizeof(int), hipHostMallocDefault));
+    if (!h->sub_ev) HIP_TRY(hipEventCreateWithFlags(&h->sub_ev, hipEventDisableTiming));
+    if (h->sub_busy) { HIP_TRY(hipEventSynchronize(h->sub_ev)); h->sub_busy = false; } // (the previous list may still be on its way)
+    std::memcpy(h->sub_pin, idx, (size_t)count * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(dst, h->sub_pin, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipEventRecord(h->sub_ev, h->stream));
+    h->sub_busy = true;
+    return EICOS_OK;
+}
+// the compact buffer of the row gather: [ids of `count` instances | count rows of `width` doubles], grown on demand
+static size_t gather_rows_at(int count) { return (((size_t)count * sizeof(int)) + 63) & ~(size_t)63; }
+static int grow_gather(eicos_batch *h, int count, int width) {
+    const size_t need = gather_rows_at(count) + (size_t)count * width * sizeof(double);
+    if (need <= h->gather_bytes) return EICOS_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->d_gather) { (void)hipFree(h->d_gather); h->d_gather = nullptr; h->gather_bytes = 0; }
+    HIP_TRY(hipMalloc((void **)&h->d_gather, need));
+    h->gather_bytes = need;
+    return EICOS_OK;
+}
+// rows of the instances d_list[0 .. count) (device memory; NULL: the ids already at the head of d_gather) into the caller's arrays, any
+// NULL: the gather kernel, one copy of the compact buffer, and the split into groups on the host.  Complete on return.
+static int gather_rows(eicos_batch *h, const int *d_list, int count, double *x, double *y, double *z, double *s, eicos_info *info, int *codes) {
+    const DevPat &D = h->dp;
+    const int want = (x && D.n ? GATHER_X : 0) | (y && D.p ? GATHER_Y : 0) | (z && D.m ? GATHER_Z : 0) | (s && D.m ? GATHER_S : 0) | (info || codes ? GATHER_INFO : 0);
+    if (count == 0 || want == 0) return EICOS_OK;
+    const int width = gather_width(want, D.n, D.p, D.m);
+    const int rc = grow_gather(h, count, width);
+    if (rc != EICOS_OK) return rc;
+    double *rows = reinterpret_cast<double *>(h->d_gather + gather_rows_at(count));
+    HIP_TRY(launch_gather_rows(h->pslot, h->d_inst, d_list ? d_list : reinterpret_cast<const int *>(h->d_gather), count, want, rows, h->stream));
+    std::vector<double> host((size_t)count * width);
+    const int frc = fetch_strided(h, host.data(), rows, (size_t)width * sizeof(double), width, count);
+    if (frc != EICOS_OK) return frc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    double *dst[4] = {x, y, z, s};
+    const int bit[4] = {GATHER_X, GATHER_Y, GATHER_Z, GATHER_S}, w[4] = {D.n, D.p, D.m, D.m};
+    for (int q = 0; q < count; q++) {
+        const double *row = host.data() + (size_t)q * width;
+        for (int g = 0; g < 4; g++)
+            if (want & bit[g]) { std::memcpy(dst[g] + (size_t)q * w[g], row, (size_t)w[g] * sizeof(double)); row += w[g]; }
+        if (want & GATHER_INFO) {
+            DevInfo d;
+            std::memcpy(&d, row, sizeof d);
+            if (info) info_from(d, info[q]);
+            if (codes) codes[q] = d.exitcode;
+        }
+    }
+    return EICOS_OK;
+}
+// the selection kernel over the whole batch behind everything on the handle's stream: ids into subset_ids(h), their number into *count
+// (and, if asked, the ids into idx_out): the one host synchronisation of eicos_batch_select / _solve_where
+static int select_ids(eicos_batch *h, unsigned mask, int *idx_out, int *count) {
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(launch_select(h->pslot, h->d_inst, h->batch, mask, subset_ids(h), h->d_queue + 1, h->stream));
+    HIP_TRY(hipMemcpyAsync(count, h->d_queue + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (*count < 0 || *count > h->batch) return fail(EICOS_E_HIP, "internal: the selection kernel returned a count outside the batch");
+    if (idx_out && *count > 0) {
+        HIP_TRY(hipMemcpyAsync(idx_out, subset_ids(h), (size_t)*count * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return EICOS_OK;
+}
+
+int eicos_batch_select(eicos_batch *h, unsigned mask, int *idx_out, int *count_out) {
+    int rc = take_class_mask(h, mask, "eicos_batch_select"), count = 0;
+    if (rc == EICOS_OK) rc = select_ids(h, mask, idx_out, &count);
+    if (rc == EICOS_OK && count_out) *count_out = count;
+    return rc;
+}
+
+int eicos_batch_solve_subset_async(eicos_batch *h, const int *idx, int count) {
+    int rc = take_index_list(h, idx, count, "eicos_batch_solve_subset");
+    if (rc != EICOS_OK || count == 0) return rc; // (an empty subset: no launch, nothing recorded)
+    HIP_TRY(hipSetDevice(h->device));
+    rc = upload_ids(h, idx, count, subset_ids(h));
+    return rc != EICOS_OK ? rc : enqueue_solve(h, nullptr, count);
+}
+
+int eicos_batch_solve_subset(eicos_batch *h, const int *idx, int count, int *exitcodes) {
+    int rc = eicos_batch_solve_subset_async(h, idx, count);
+    if (rc != EICOS_OK || count == 0) return rc;
+    rc = eicos_batch_sync(h);
+    return rc != EICOS_OK ? rc : gather_rows(h, subset_ids(h), count, nullptr, nullptr, nullptr, nullptr, nullptr, exitcodes);
+}
+
+int eicos_batch_solve_where(eicos_batch *h, unsigned mask, int *idx_out, int *count_out, int *exitcodes) {
+    int rc = take_class_mask(h, mask, "eicos_batch_solve_where"), count = 0;
+    if (rc == EICOS_OK) rc = select_ids(h, mask, idx_out, &count);
+    if (rc != EICOS_OK) return rc;
+    if (count_out) *count_out = count;
+    if (count == 0) return EICOS_OK; // (nobody is in the class: no launch, nothing recorded)
+    rc = enqueue_solve(h, nullptr, count); // (the ids are used where the selection kernel left them)
+    if (rc == EICOS_OK) rc = eicos_batch_sync(h);
+    return rc != EICOS_OK ? rc : gather_rows(h, subset_ids(h), count, nullptr, nullptr, nullptr, nullptr, nullptr, exitcodes);
+}
+
+int eicos_batch_gather(eicos_batch *h, const int *idx, int count, double *x, double *y, double *z, double *s, eicos_info *info) {
+    int rc = take_index_list(h, idx, count, "eicos_batch_gather");
+    if (rc != EICOS_OK || count == 0) return rc;
+    if (!x && !y && !z && !s && !info) return EICOS_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    // (the buffer for the widest row a call can ask for, so that the ids at its head stay where they are)
+    rc = grow_gather(h, count, gather_width(GATHER_X | GATHER_Y | GATHER_Z | GATHER_S | GATHER_INFO, h->dp.n, h->dp.p, h->dp.m));
+    if (rc == EICOS_OK) rc = upload_ids(h, idx, count, reinterpret_cast<int *>(h->d_gather));
+    return rc != EICOS_OK ? rc : gather_rows(h, nullptr, count, x, y, z, s, info, nullptr);
 }
 
 // ---- steps fused into the solve launch: the helpers of update_solve and the rollout ----
@@ -2394,15 +2538,18 @@ int eicos_debug_scalings(eicos_batch *h, int inst, const double *s, const double
 
 int eicos_debug_trace(eicos_batch *h, int inst, double *out) {
     if (!h || !out || inst < 0 || inst >= h->batch) return fail(EICOS_E_INVALID, "bad argument");
-    if (h->batch > h->grid) return fail(EICOS_E_INVALID, "trace is per workspace slot: needs batch <= resident instances");
+    // (a subset launch: its own count decides, and only its instances have a slot)
+    const int launched = h->last_subset ? h->last_count : h->batch;
+    if (launched > h->grid) return fail(EICOS_E_INVALID, h->last_subset ? "trace is per workspace slot: needs the subset's count <= resident instances"
+                                                                         : "trace is per workspace slot: needs batch <= resident instances");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     int slot = inst;
-    if (h->last_ordered) { // the launch took the instances in longest-first order: slot q holds instance order[q]
-        std::vector<int> ord(h->batch);
-        HIP_TRY(hipMemcpy(ord.data(), h->d_queue + 16, (size_t)h->batch * sizeof(int), hipMemcpyDeviceToHost));
+    if (h->last_ordered) { // the launch took the instances through the order array: slot q holds instance order[q], q < launched
+        std::vector<int> ord(launched);
+        HIP_TRY(hipMemcpy(ord.data(), h->d_queue + 16, (size_t)launched * sizeof(int), hipMemcpyDeviceToHost));
         slot = (int)(std::find(ord.begin(), ord.end(), inst) - ord.begin());
-        if (slot >= h->batch) return fail(EICOS_E_INVALID, "instance not found in the launch order");
+        if (slot >= launched) return fail(EICOS_E_INVALID, h->last_subset ? "instance not in the last launch" : "instance not found in the launch order");
     }
     HIP_TRY(hipMemcpy(out, h->d_work + (size_t)slot * h->dp.work_stride + h->dp.w_trace,
                       (size_t)TRACE_ROWS * TRACE_COLS * sizeof(double), hipMemcpyDeviceToHost));

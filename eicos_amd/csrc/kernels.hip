@@ -35,6 +35,7 @@
 
 #include "device_types.hpp"
 #include "launch.hpp"
+#include "exit_class.hpp"
 
 // This file is ONE source compiled FIVE times (kernels.hip, kernels_t128.hip, kernels_t512.hip, kernels_ldsres.hip, kernels_w2.hip: translation
 // units that build side by side; launch.hpp: solve_build() picks a handle's).  EICOS_LDSRES = 0: the slabs of an instance live in HBM.  EICOS_LDSRES = 1
@@ -3589,6 +3590,68 @@ __global__ __launch_bounds__(1024) void k_order(int ps, const double *inst, int 
         order[pos] = i;
     }
 }
+// Selection and launch order of a SUBSET launch (eicos_batch_select, _solve_subset, _solve_where): k_order for a chosen set of instances.
+// One workgroup of NB threads.  Two sources of candidates:
+//   list != NULL: the ids list[0 .. nlist) as they are (the host has checked them: inside [0, batch), no duplicates);
+//   list == NULL: every instance of 0 .. batch-1 whose exit class (exit_class.hpp: the function eicos_exit_class runs on the host) is in
+//                 `mask`, compacted in ascending order into cand [batch]; their number goes to *count_out (a spare word of the queue header).
+// order != NULL: the candidates into order[0 .. count) as k_order lays out a whole batch -- up to ncu of them (one instance per CU) in
+// candidate order, more than that by descending n_ldlsolve key, snake layout when the launch is one round (count <= full_grid, the
+// handle's resident workgroups: a subset launch runs min(full_grid, count) of them).  The counting sort cannot run in place: cand and
+// order are two arrays.  Plain vector stores throughout.
+__global__ __launch_bounds__(1024) void k_select_order(int ps, const double *inst, int batch, const int *list, int nlist, unsigned mask,
+                                                       int *cand, int *count_out, int *order, int snake_on, int full_grid, int ncu) {
+    const DevPat &P = c_pat[ps];
+    constexpr int NB = 1024;
+    __shared__ int cnt[NB];
+    const int tid = threadIdx.x;
+    auto info = [&](int i) { return reinterpret_cast<const DevInfo *>(inst + (size_t)i * P.inst_stride + P.i_info); };
+    const int *src = list;
+    int total = nlist;
+    if (!list) { // tiles of NB instances: inclusive scan of the selection flags in LDS, base = the selected ones of the tiles before
+        int base = 0;
+        for (int i0 = 0; i0 < batch; i0 += NB) {
+            const int i = i0 + tid;
+            int f = 0;
+            if (i < batch) { const DevInfo *di = info(i); f = (exit_class(di->exitcode, di->n_factor) & mask) != 0; }
+            cnt[tid] = f;
+            __syncthreads();
+            for (int d = 1; d < NB; d <<= 1) {
+                const int v = tid >= d ? cnt[tid - d] : 0;
+                __syncthreads();
+                cnt[tid] += v;
+                __syncthreads();
+            }
+            if (f) cand[base + cnt[tid] - 1] = i; // (base + rank < the instances seen so far <= batch)
+            base += cnt[NB - 1];
+            __syncthreads();
+        }
+        src = cand; total = base;
+        if (tid == 0) *count_out = total;
+    }
+    if (!order) return;
+    if (total <= ncu) { // at most one instance per CU: candidate order (k_solve's identity order for a whole batch)
+        for (int q = tid; q < total; q += NB) order[q] = src[q];
+        return;
+    }
+    const int snake = (snake_on && total <= full_grid) ? total : 0;
+    for (int k = tid; k < NB; k += NB) cnt[k] = 0;
+    __syncthreads();
+    auto key = [&](int i) { return NB - 1 - min(max(info(i)->n_ldlsolve, 0), NB - 1); }; // descending
+    for (int q = tid; q < total; q += NB) atomicAdd(&cnt[key(src[q])], 1);
+    __syncthreads();
+    if (tid == 0) { int run = 0; for (int k = 0; k < NB; k++) { const int c = cnt[k]; cnt[k] = run; run += c; } }
+    __syncthreads();
+    for (int q = tid; q < total; q += NB) {
+        const int i = src[q];
+        int pos = atomicAdd(&cnt[key(i)], 1); // rank in descending work (ties in arrival order), < total
+        if (snake && pos < snake) { // (k_order's boustrophedon layout of a one-round launch)
+            const int row = pos / ncu, col = pos % ncu, len = min(ncu, snake - row * ncu);
+            if (row & 1) pos = row * ncu + (len - 1 - col);
+        }
+        order[pos] = i;
+    }
+}
 
 // ============================================================================================
 // updateData for a range of instances: reference updateData(double*...) src/eicos.cpp:2053-2082
@@ -3879,6 +3942,26 @@ __global__ __launch_bounds__(T) void k_plant_range(int ps, const double *inst, i
     }
 }
 
+// Row gather (launch.hpp: launch_gather_rows): row q of dst = the wanted groups of instance list[q], back to back -- x, y, z, s as they
+// stand in the slab and the info record, each copied as doubles with plain loads and stores.  grid: x over a row's entries, y over the rows.
+template <int T>
+__global__ __launch_bounds__(T) void k_gather_rows(int ps, const double *inst, const int *list, int count, int want, double *dst) {
+    const DevPat &P = c_pat[ps];
+    const int wx = want & GATHER_X ? P.n : 0, wy = want & GATHER_Y ? P.p : 0, wz = want & GATHER_Z ? P.m : 0, ws = want & GATHER_S ? P.m : 0;
+    const int w = wx + wy + wz + ws + (want & GATHER_INFO ? GATHER_INFO_DOUBLES : 0);
+    for (int q = blockIdx.y; q < count; q += gridDim.y) {
+        const double *I = inst + (size_t)list[q] * P.inst_stride;
+        double *row = dst + (size_t)q * w;
+        for (int e = blockIdx.x * T + threadIdx.x; e < w; e += gridDim.x * T) {
+            if (e < wx) row[e] = I[P.i_x + e];
+            else if (e < wx + wy) row[e] = I[P.i_y + (e - wx)];
+            else if (e < wx + wy + wz) row[e] = I[P.i_z + (e - wx - wy)];
+            else if (e < wx + wy + wz + ws) row[e] = I[P.i_s + (e - wx - wy - wz)];
+            else row[e] = I[P.i_info + (e - wx - wy - wz - ws)];
+        }
+    }
+}
+
 // Debug: factorise instance `i` with the KKT scaling block as it stands in memory (runs the solver's own stage).
 template <int T>
 __global__ __launch_bounds__(T, waves_per_eu<T>()) void k_debug_factor(int ps, double *inst, double *work, int i) {
@@ -3950,11 +4033,15 @@ static hipError_t launch_solve(const SolveLaunch &launch, hipStream_t st, const 
     // Longest-first order (by the work of the previous solve) whenever a CU gets more than one workgroup: for a batch larger
     // than the grid it is the queue's processing order; for a one-round batch it makes the dispatcher pair a long instance
     // with a short one on each CU, which then finishes the long one alone (+7 % at batch 512 on 256 CUs).
-    if (L.B <= L.order_min) L.order = nullptr; // at most one instance per CU: identity
+    // (EICOS_SNAKE=0 under EICOS_EXPERIMENT=1: plain descending order, for A/B runs.  Laying out the first round of a MULTI-round launch the
+    // same way measured +-0: profiles/r05_log_snake_order.log)
+    static const int snake_on = [] { const char *e = getenv("EICOS_EXPERIMENT"), *k = getenv("EICOS_SNAKE"); return !(e && k && !strcmp(e, "1") && !strcmp(k, "0")); }();
+    if (L.list) { // a subset launch (launch.hpp: SolveLaunch): order = the chosen ids, arranged by the selection kernel, never NULL
+        hipLaunchKernelGGL(k_select_order, dim3(1), dim3(1024), 0, st, L.ps, (const double *)L.inst, L.batch, L.list, L.B, 0u, (int *)nullptr, (int *)nullptr,
+                           L.order, snake_on, L.full_grid, L.order_min);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    } else if (L.B <= L.order_min) L.order = nullptr; // at most one instance per CU: identity
     else {
-        // (EICOS_SNAKE=0 under EICOS_EXPERIMENT=1: plain descending order, for A/B runs.  Laying out the first round of a MULTI-round launch the
-        // same way measured +-0: profiles/r05_log_snake_order.log)
-        static const int snake_on = [] { const char *e = getenv("EICOS_EXPERIMENT"), *k = getenv("EICOS_SNAKE"); return !(e && k && !strcmp(e, "1") && !strcmp(k, "0")); }();
         hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, st, L.ps, L.inst, L.B, L.order, (snake_on && L.B <= L.grid) ? L.B : 0, L.order_min);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
@@ -4026,6 +4113,18 @@ hipError_t launch_plant(int ps, const double *inst, int first, int count, const 
     constexpr int T = 256;
     const size_t nb = ((size_t)count * roll.plant.k + T - 1) / T;
     hipLaunchKernelGGL(k_plant_range<T>, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(T), 0, st, ps, inst, first, count, roll, t, theta_cur, u_cur, theta_next);
+    return hipGetLastError();
+}
+hipError_t launch_select(int ps, const double *inst, int batch, unsigned mask, int *cand, int *count, hipStream_t st) {
+    if (batch <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_select_order, dim3(1), dim3(1024), 0, st, ps, inst, batch, (const int *)nullptr, 0, mask, cand, count, (int *)nullptr, 0, 0, 0);
+    return hipGetLastError();
+}
+hipError_t launch_gather_rows(int ps, const double *inst, const int *list, int count, int want, double *dst, hipStream_t st) {
+    if (count <= 0 || want == 0) return hipSuccess;
+    constexpr int T = 256;
+    const int gx = 4, gy = count; // (rows of a few thousand doubles at the most: four workgroups a row)
+    hipLaunchKernelGGL(k_gather_rows<T>, dim3((unsigned)gx, (unsigned)(gy < 16384 ? gy : 16384)), dim3(T), 0, st, ps, inst, list, count, want, dst);
     return hipGetLastError();
 }
 // the dynamic-LDS ceiling of the two entry-parallel updateData kernels, set once per handle on the handle's device

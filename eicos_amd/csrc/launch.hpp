@@ -68,10 +68,14 @@ constexpr SolveCfg solve_cfg_default() { return {1e-8, 1e-8, 1e-8, 1e-4, 5e-5, 5
 // One k_solve launch of a handle, as the host describes it: the pattern slot, the slabs and the queue, the launch shape, and what travels
 // to the kernel by value.  order = the longest-first order array (used when B > order_min); cfg is copied into the kernel arguments, so
 // a launch in flight keeps the settings it was enqueued with.
+// A SUBSET launch (eicos_batch_solve_subset / _solve_where) is the same launch with list != NULL: B ids of distinct instances in device
+// memory.  The selection kernel arranges them in `order` (never NULL then: list order up to order_min ids, longest first beyond), B =
+// their number and grid = min(the handle's grid, B); batch = the handle's batch (the ids lie in [0, batch)).
 struct SolveLaunch {
     int ps; double *inst, *work; int B; int *queue, *order;
     int grid, threads, nlds, idx16, order_min;
     double warm, dyn_delta, dyn_eps; SolveCfg cfg; size_t dyn_lds;
+    const int *list; int batch, full_grid; // subset launches: the chosen ids, the handle's batch and its whole-batch grid
 };
 // One k_solve build = these four entry points.  launch always receives an UpdArgs: UpdArgs{} when no step is fused into it.
 struct SolveBuild {
@@ -115,6 +119,20 @@ hipError_t launch_outputs(int ps, const double *inst, int first, int count, cons
 // and iteration count to its records (roll: the trajectories of the whole batch, host copy of the launch's RolloutDev)
 hipError_t launch_plant(int ps, const double *inst, int first, int count, const RolloutDev &roll, int t, const double *theta_cur,
                         const double *u_cur, double *theta_next, hipStream_t st);
+// Selection (eicos_batch_select, _solve_where): the instances of 0 .. batch-1 whose exit class (exit_class.hpp) is in `mask`, compacted
+// in ascending order into cand [batch], their number into *count (both device memory).  The kernel is the one that orders a subset launch
+// (kernels.hip: k_select_order), run without an order array.
+hipError_t launch_select(int ps, const double *inst, int batch, unsigned mask, int *cand, int *count, hipStream_t st);
+// Row gather (eicos_batch_gather, the exit codes of the subset solves): for q < count the wanted groups (GATHER_* bits) of instance
+// list[q] -- x, y, z, s as they stand in the slab (what eicos_batch_solution / _duals return) and the info record -- back to back into
+// row q of dst [count][gather_width]; list and dst in device memory
+enum { GATHER_X = 1, GATHER_Y = 2, GATHER_Z = 4, GATHER_S = 8, GATHER_INFO = 16 };
+constexpr int GATHER_INFO_DOUBLES = (int)(sizeof(DevInfo) / sizeof(double));
+static_assert(sizeof(DevInfo) % sizeof(double) == 0, "the info record is gathered as doubles");
+inline int gather_width(int want, int n, int p, int m) {
+    return (want & GATHER_X ? n : 0) + (want & GATHER_Y ? p : 0) + (want & GATHER_Z ? m : 0) + (want & GATHER_S ? m : 0) + (want & GATHER_INFO ? GATHER_INFO_DOUBLES : 0);
+}
+hipError_t launch_gather_rows(int ps, const double *inst, const int *list, int count, int want, double *dst, hipStream_t st);
 hipError_t update_set_max_lds();
 hipError_t launch_debug_factor(int ps, double *inst, double *work, int i, int threads, size_t dyn_lds, hipStream_t st);
 hipError_t launch_debug_scalings(int ps, double *inst, double *work, int i, int *ok, int threads, hipStream_t st);

@@ -276,6 +276,116 @@ int eicos_multi_solve(eicos_multi *mh, int *exitcodes) {
     return EICOS_OK;
 }
 
+} // extern "C"
+
+// ---- subset calls (eicos_batch_select / _solve_subset / _solve_where / _gather per shard): GLOBAL instance ids.  A list is checked as a
+// whole before any shard sees its share, so a refused list changes no shard; shards with an empty share are skipped.
+namespace {
+struct Shares { std::vector<std::vector<int>> ids, pos; }; // per shard: its ids, reduced by the shard's first instance, and their positions in the caller's list
+int split_list(eicos_multi *mh, const int *idx, int count, const char *who, Shares &sh) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    const std::string msg = eicos::index_list_fault(idx, count, mh->batch);
+    if (!msg.empty()) return mfail(EICOS_E_INVALID, std::string(who) + ": " + msg);
+    const int ns = (int)mh->shard.size();
+    sh.ids.assign(ns, {}); sh.pos.assign(ns, {});
+    for (int q = 0; q < count; q++) {
+        const int s = (int)(std::upper_bound(mh->first.begin(), mh->first.end(), idx[q]) - mh->first.begin()) - 1; // (first[] ascends from 0)
+        sh.ids[s].push_back(idx[q] - mh->first[s]); sh.pos[s].push_back(q);
+    }
+    return EICOS_OK;
+}
+int check_mask(eicos_multi *mh, unsigned mask, const char *who) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    const std::string msg = eicos::class_mask_fault(mask);
+    return msg.empty() ? (int)EICOS_OK : mfail(EICOS_E_INVALID, std::string(who) + ": " + msg);
+}
+// per shard: the ids a mask call selected (local) and their exit codes; concatenated in shard order they are the ascending global list
+int concat_selected(eicos_multi *mh, const std::vector<std::vector<int>> &ids, const std::vector<int> &cnt, const std::vector<std::vector<int>> *codes,
+                    int *idx_out, int *count_out, int *exitcodes) {
+    int at = 0;
+    for (size_t s = 0; s < mh->shard.size(); s++)
+        for (int q = 0; q < cnt[s]; q++, at++) {
+            if (idx_out) idx_out[at] = ids[s][q] + mh->first[s];
+            if (exitcodes && codes) exitcodes[at] = (*codes)[s][q];
+        }
+    if (count_out) *count_out = at;
+    return EICOS_OK;
+}
+} // namespace
+
+extern "C" {
+
+int eicos_multi_select(eicos_multi *mh, unsigned mask, int *idx_out, int *count_out) {
+    int rc = check_mask(mh, mask, "eicos_multi_select");
+    if (rc != EICOS_OK) return rc;
+    const size_t ns = mh->shard.size();
+    std::vector<std::vector<int>> ids(ns);
+    std::vector<int> cnt(ns, 0);
+    rc = for_shards(mh, [&](int s) { ids[s].resize(mh->count[s]); return eicos_batch_select(mh->shard[s], mask, ids[s].data(), &cnt[s]); });
+    return rc != EICOS_OK ? rc : concat_selected(mh, ids, cnt, nullptr, idx_out, count_out, nullptr);
+}
+
+int eicos_multi_solve_subset_async(eicos_multi *mh, const int *idx, int count) {
+    Shares sh;
+    const int rc = split_list(mh, idx, count, "eicos_multi_solve_subset", sh);
+    if (rc != EICOS_OK) return rc;
+    for (size_t s = 0; s < mh->shard.size(); s++) { // enqueue only, as eicos_multi_solve_async
+        if (sh.ids[s].empty()) continue;
+        const int r = eicos_batch_solve_subset_async(mh->shard[s], sh.ids[s].data(), (int)sh.ids[s].size());
+        if (r != EICOS_OK) return mfail(r, "shard " + std::to_string(s) + ": " + eicos_last_error());
+    }
+    return EICOS_OK;
+}
+
+int eicos_multi_solve_subset(eicos_multi *mh, const int *idx, int count, int *exitcodes) {
+    Shares sh;
+    const int rc = split_list(mh, idx, count, "eicos_multi_solve_subset", sh);
+    if (rc != EICOS_OK) return rc;
+    return for_shards(mh, [&](int s) {
+        const int k = (int)sh.ids[s].size();
+        if (k == 0) return (int)EICOS_OK;
+        std::vector<int> codes(k);
+        const int r = eicos_batch_solve_subset(mh->shard[s], sh.ids[s].data(), k, exitcodes ? codes.data() : nullptr);
+        for (int q = 0; r == EICOS_OK && exitcodes && q < k; q++) exitcodes[sh.pos[s][q]] = codes[q];
+        return r;
+    });
+}
+
+int eicos_multi_solve_where(eicos_multi *mh, unsigned mask, int *idx_out, int *count_out, int *exitcodes) {
+    int rc = check_mask(mh, mask, "eicos_multi_solve_where");
+    if (rc != EICOS_OK) return rc;
+    const size_t ns = mh->shard.size();
+    std::vector<std::vector<int>> ids(ns), codes(ns);
+    std::vector<int> cnt(ns, 0);
+    rc = for_shards(mh, [&](int s) {
+        ids[s].resize(mh->count[s]); codes[s].resize(mh->count[s]);
+        return eicos_batch_solve_where(mh->shard[s], mask, ids[s].data(), &cnt[s], codes[s].data());
+    });
+    return rc != EICOS_OK ? rc : concat_selected(mh, ids, cnt, &codes, idx_out, count_out, exitcodes);
+}
+
+int eicos_multi_gather(eicos_multi *mh, const int *idx, int count, double *x, double *y, double *z, double *sl, eicos_info *info) {
+    Shares sh;
+    const int rc = split_list(mh, idx, count, "eicos_multi_gather", sh);
+    if (rc != EICOS_OK) return rc;
+    return for_shards(mh, [&](int s) {
+        const size_t k = sh.ids[s].size();
+        if (k == 0) return (int)EICOS_OK;
+        // the shard's rows in its own compact arrays, then every row to its position in the caller's list
+        std::vector<double> tx(x ? k * mh->n : 0), ty(y ? k * mh->p : 0), tz(z ? k * mh->m : 0), ts(sl ? k * mh->m : 0);
+        std::vector<eicos_info> ti(info ? k : 0);
+        const int r = eicos_batch_gather(mh->shard[s], sh.ids[s].data(), (int)k, x ? tx.data() : nullptr, y ? ty.data() : nullptr,
+                                         z ? tz.data() : nullptr, sl ? ts.data() : nullptr, info ? ti.data() : nullptr);
+        if (r != EICOS_OK) return r;
+        auto rows = [&](double *dst, const std::vector<double> &src, int w) {
+            if (dst && w > 0) for (size_t q = 0; q < k; q++) std::memcpy(dst + (size_t)sh.pos[s][q] * w, src.data() + q * w, (size_t)w * sizeof(double));
+        };
+        rows(x, tx, mh->n); rows(y, ty, mh->p); rows(z, tz, mh->m); rows(sl, ts, mh->m);
+        for (size_t q = 0; info && q < k; q++) info[sh.pos[s][q]] = ti[q];
+        return (int)EICOS_OK;
+    });
+}
+
 // updateData + solve in one call over every shard (eicos_batch_update_solve per shard on its rows, the shards concurrently)
 int eicos_multi_update_solve(eicos_multi *mh, const double *G, const double *A, const double *c, const double *hh, const double *b,
                              double *x_out, int *exitcodes) {

@@ -17,6 +17,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "eicos_amd.h"
@@ -42,6 +43,17 @@ namespace EiCOS
         close_to_primal_infeasible = 11,
         close_to_dual_infeasible = 12,
         not_converged_yet = -87
+    };
+
+    // Extension: the exit classes of BatchSolver::select / solveWhere (EICOS_SEL_* of eicos_amd.h): every instance is in exactly one, by
+    // the exit code and n_factor of its info record; a mask is an OR of these
+    enum sel : unsigned
+    {
+        sel_optimal = EICOS_SEL_OPTIMAL, sel_pinf = EICOS_SEL_PINF, sel_dinf = EICOS_SEL_DINF,
+        sel_optimal_inacc = EICOS_SEL_OPTIMAL_INACC, sel_pinf_inacc = EICOS_SEL_PINF_INACC, sel_dinf_inacc = EICOS_SEL_DINF_INACC,
+        sel_maxit = EICOS_SEL_MAXIT, sel_numerics = EICOS_SEL_NUMERICS, sel_outcone = EICOS_SEL_OUTCONE, sel_fatal = EICOS_SEL_FATAL,
+        sel_other = EICOS_SEL_OTHER, sel_unsolved = EICOS_SEL_UNSOLVED,
+        sel_failed = EICOS_SEL_FAILED, sel_not_optimal = EICOS_SEL_NOT_OPTIMAL, sel_all = EICOS_SEL_ALL
     };
 
     // reference include/eicos.hpp:23-47.  The ten members without `const` are the runtime settings of the GPU kernels (eicos_settings of
@@ -300,6 +312,46 @@ namespace EiCOS
             std::vector<exitcode> out(batch_);
             for (int i = 0; i < batch_; i++) out[i] = static_cast<exitcode>(codes[i]);
             return out;
+        }
+        // Extension: solve a chosen subset of the batch (eicos_batch_solve_subset / _solve_where of eicos_amd.h: contract and refusals
+        // there).  Indices are global instance ids, each at most once.  An instance of the subset ends, bit for bit, as a solve() of the
+        // whole batch would leave it; every other instance keeps its state, its info record included.  Settings, warm start and
+        // regularisation are the handle's: set them for the retry, solve the subset, set them back.
+        // select: the ascending ids of the instances whose exit class is in `mask` (an OR of EiCOS::sel values), found on the GPU.
+        std::vector<int> select(unsigned mask) const
+        {
+            std::vector<int> ids(batch_);
+            int count = 0;
+            mcheck(eicos_multi_select(h_, mask, ids.data(), &count), "eicos_multi_select");
+            ids.resize(count);
+            return ids;
+        }
+        // solveSubset: one launch over `indices`; the exit codes in list order.  An empty list launches nothing.
+        std::vector<exitcode> solveSubset(const std::vector<int> &indices)
+        {
+            std::vector<int> codes(indices.size());
+            mcheck(eicos_multi_solve_subset(h_, indices.data(), (int)indices.size(), codes.data()), "eicos_multi_solve_subset");
+            std::vector<exitcode> out(codes.size());
+            for (size_t i = 0; i < codes.size(); i++) out[i] = static_cast<exitcode>(codes[i]);
+            return out;
+        }
+        // solveWhere: select(mask) + solveSubset with the id list used in place on the GPU; (ids ascending, their exit codes)
+        std::pair<std::vector<int>, std::vector<exitcode>> solveWhere(unsigned mask)
+        {
+            std::vector<int> ids(batch_), codes(batch_);
+            int count = 0;
+            mcheck(eicos_multi_solve_where(h_, mask, ids.data(), &count, codes.data()), "eicos_multi_solve_where");
+            ids.resize(count);
+            std::vector<exitcode> out(count);
+            for (int i = 0; i < count; i++) out[i] = static_cast<exitcode>(codes[i]);
+            return {ids, out};
+        }
+        // gather: the rows of `indices`, in list order, into x [count][n], y [count][p], z, s [count][m] and info [count] (any nullptr):
+        // packed on the GPU and fetched with one copy, instead of whole-batch solution() / duals() / getInfo()
+        void gather(const std::vector<int> &indices, double *x, double *y = nullptr, double *z = nullptr, double *s = nullptr,
+                    eicos_info *info = nullptr) const
+        {
+            mcheck(eicos_multi_gather(h_, indices.data(), (int)indices.size(), x, y, z, s, info), "eicos_multi_gather");
         }
         void solveAsync() { mcheck(eicos_multi_solve_async(h_), "eicos_multi_solve_async"); } // enqueue on every shard's stream
         void sync() { mcheck(eicos_multi_sync(h_), "eicos_multi_sync"); }

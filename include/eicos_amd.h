@@ -295,6 +295,62 @@ int eicos_batch_solve(eicos_batch *hd, int *exitcodes);
 int eicos_batch_solve_async(eicos_batch *hd);
 int eicos_batch_sync(eicos_batch *hd);
 
+/* ---- solve a chosen subset of the batch: by index list or by exit class (no reference counterpart).  The update calls work on ranges
+ * of instances; these are the matching solve calls, for "retry the three instances that stopped at the iteration cap under other
+ * settings", "only the controllers whose sample time fired", "only the scenarios still alive".
+ * Exit classes: every instance is in exactly ONE class, by the exit code and n_factor of its info record.  eicos_exit_class returns that
+ * bit; it needs no handle and no GPU, and the selection kernel on the GPU evaluates the very same function.
+ *   EICOS_SEL_OPTIMAL (0)  _PINF (1)  _DINF (2)  _OPTIMAL_INACC (10)  _PINF_INACC (11)  _DINF_INACC (12)
+ *   EICOS_SEL_MAXIT (-1)  _NUMERICS (-2)  _OUTCONE (-3)  _FATAL (-7)  EICOS_SEL_OTHER (any other code)
+ *   EICOS_SEL_UNSOLVED: n_factor == 0 -- never solved and never given a starting point; it takes precedence over the code, which is 0
+ *   in a fresh record. */
+enum {
+    EICOS_SEL_OPTIMAL = 1 << 0, EICOS_SEL_PINF = 1 << 1, EICOS_SEL_DINF = 1 << 2,
+    EICOS_SEL_OPTIMAL_INACC = 1 << 3, EICOS_SEL_PINF_INACC = 1 << 4, EICOS_SEL_DINF_INACC = 1 << 5,
+    EICOS_SEL_MAXIT = 1 << 6, EICOS_SEL_NUMERICS = 1 << 7, EICOS_SEL_OUTCONE = 1 << 8, EICOS_SEL_FATAL = 1 << 9,
+    EICOS_SEL_OTHER = 1 << 10, EICOS_SEL_UNSOLVED = 1 << 11,
+    EICOS_SEL_FAILED = EICOS_SEL_MAXIT | EICOS_SEL_NUMERICS | EICOS_SEL_OUTCONE | EICOS_SEL_FATAL,
+    EICOS_SEL_ALL = (1 << 12) - 1,
+    EICOS_SEL_NOT_OPTIMAL = EICOS_SEL_ALL & ~EICOS_SEL_OPTIMAL
+};
+int eicos_exit_class(int exitcode, int n_factor);
+/* eicos_batch_select: the instances whose class is in `mask`, ascending, into idx_out ([batch], optional) and their number into
+ * *count_out (optional).  Waits for the handle's stream, runs the selection kernel over the info records in HBM and copies the count
+ * (and the ids, if asked) back: no info record travels.
+ * eicos_batch_solve_subset_async / _solve_subset: an ORDINARY solve launch over the instances idx[0 .. count) (host array) instead of
+ * the whole batch -- the same kernel with the launch order = the chosen ids and the batch = their number, min(resident workgroups,
+ * count) workgroups, and everything else as for eicos_batch_solve: warm start, shift map, a caller-supplied iterate, shared matrix
+ * values, settings and dynamic regularisation by value, the timing ring.  Up to one instance per CU the ids are taken in list order;
+ * beyond that longest first, as a whole-batch launch orders its instances.  The synchronous form returns the exit codes of the chosen
+ * instances in list order (exitcodes [count], optional), gathered on the GPU: no info record of another instance travels.
+ * eicos_batch_solve_where = select + subset solve, with the id list used in place on the GPU: it waits for the handle's stream, runs
+ * the selection kernel, reads the count (and the ids, if asked) -- the one host synchronisation; a retry follows a finished solve anyway
+ * -- and launches; it returns when the solve has finished, like eicos_batch_solve.  idx_out ([batch], optional, ascending), *count_out (optional), exitcodes ([*count_out], order of idx_out, optional).
+ * Contract, for every instance IN the subset: take a twin handle on which eicos_batch_solve ran at the same point of the same call
+ * sequence; the instance ends in the same state as on the twin, bit for bit -- slab, eicos_batch_solution, _duals, _info except solve_us,
+ * eicos_debug_kkt -- cold, warm, under a shift map, from a caller-supplied iterate and with shared matrix values.
+ * Contract, for every instance OUTSIDE the subset: nothing the host can read changes, its info record and solve_us included (the
+ * LDS-resident build writes back only the slabs it solved; shared matrix values are kept).
+ * An empty subset (count == 0, or a mask nobody is in) is EICOS_OK with no launch and nothing recorded: eicos_batch_last_solve_ms and the
+ * timing ring keep their last entry.
+ * eicos_batch_gather: rows of the chosen instances -- x [count][n], y [count][p], z, s [count][m] exactly as eicos_batch_solution /
+ * _duals return them, info [count] -- in list order; any destination may be NULL.  A row-gather kernel packs them into a compact device
+ * buffer of the handle (grown on demand) and ONE copy takes that buffer to the host, over the paths of eicos_batch_solution.
+ * eicos_debug_trace after a subset launch: workspace slot q holds instance order[q], q < count; it needs count <= resident workgroups
+ * (instead of batch <=), and an instance that was not in the last launch is EICOS_E_INVALID ("instance not in the last launch").
+ * EICOS_E_INVALID, with a message naming the fault and NO state changed (checked on the host before anything is enqueued): a NULL handle;
+ * count < 0 or count > batch; NULL idx with count > 0; an index outside [0, batch) (the message names index and position); a DUPLICATE
+ * index (named: two workgroups would solve one slab at once; eicos_batch_gather refuses it like the solve calls); mask == 0 or bits above
+ * bit 11.
+ * Out of scope: fused update + solve over a subset (eicos_batch_update_solve and its kin take the whole batch), rollouts over a subset,
+ * and index-list forms of the update calls (they take ranges). */
+int eicos_batch_select(eicos_batch *hd, unsigned mask, int *idx_out /* [batch], ascending, optional */, int *count_out);
+int eicos_batch_solve_subset_async(eicos_batch *hd, const int *idx /* host [count] */, int count);
+int eicos_batch_solve_subset(eicos_batch *hd, const int *idx, int count, int *exitcodes /* [count], list order, optional */);
+int eicos_batch_solve_where(eicos_batch *hd, unsigned mask, int *idx_out /* [batch], optional, ascending */, int *count_out,
+                            int *exitcodes /* [*count_out], order of idx_out, optional */);
+int eicos_batch_gather(eicos_batch *hd, const int *idx, int count, double *x, double *y, double *z, double *s, eicos_info *info);
+
 /* ---- results: replaces solution() (reference include/eicos.hpp:160) / getInfo() (:163).
  * x: [batch][n] host.  y,z,s are extras the reference keeps private; any may be NULL.  A pinned destination receives one strided
  * device-to-host copy; a pageable one is filled through the pinned bounce buffers (copy of chunk k + 1 in flight while chunk k is copied out). */
@@ -521,6 +577,15 @@ int eicos_multi_has_shift_map(eicos_multi *mh);
 int eicos_multi_solve_async(eicos_multi *mh);
 int eicos_multi_sync(eicos_multi *mh);
 int eicos_multi_solve(eicos_multi *mh, int *exitcodes);
+/* subset solves (eicos_batch_select / _solve_subset(_async) / _solve_where / _gather): indices are GLOBAL instance ids.  A list is checked
+ * as a whole first -- a refused list changes no shard --, then split by shard, every id reduced by the shard's first instance; shards with
+ * an empty share are skipped, the others run concurrently.  Ids, exit codes and rows come back in global order (select, solve_where:
+ * ascending) or in list order (solve_subset, gather). */
+int eicos_multi_select(eicos_multi *mh, unsigned mask, int *idx_out, int *count_out);
+int eicos_multi_solve_subset_async(eicos_multi *mh, const int *idx, int count);
+int eicos_multi_solve_subset(eicos_multi *mh, const int *idx, int count, int *exitcodes);
+int eicos_multi_solve_where(eicos_multi *mh, unsigned mask, int *idx_out, int *count_out, int *exitcodes);
+int eicos_multi_gather(eicos_multi *mh, const int *idx, int count, double *x, double *y, double *z, double *s, eicos_info *info);
 /* results gathered into the caller's host arrays in global instance order (the "gather" of north_star: per-device copies) */
 int eicos_multi_solution(eicos_multi *mh, double *x);
 int eicos_multi_duals(eicos_multi *mh, double *y, double *z, double *s);
@@ -547,7 +612,8 @@ int eicos_device_count(void);
  * stand, and one LDL' solve. Host buffers. */
 int eicos_debug_factor(eicos_batch *hd, int inst, double *D /*[dim_K], permuted*/, double *U /*[nnzL] CSC, permuted*/);
 /* per-iteration history of instance `inst` in the last solve: out[102][12] = {pcost,dcost,gap,pres,dres,
- * kap/tau,mu,step,sigma,tau,kap,nitref3} per IPM pass (valid while batch <= resident workgroups). */
+ * kap/tau,mu,step,sigma,tau,kap,nitref3} per IPM pass (valid while batch <= resident workgroups; after a subset launch: while its
+ * count <= resident workgroups, for the instances of that launch). */
 int eicos_debug_trace(eicos_batch *hd, int inst, double *out);
 int eicos_debug_pattern(eicos_batch *hd, int *perm /*[dim_K]*/, int *Lp /*[dim_K+1]*/, int *Li /*[nnzL]*/);
 /* upper triangle of instance `inst`'s KKT matrix as the numeric factorisation reads it (equilibrated A/G values,
