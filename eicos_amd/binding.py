@@ -47,7 +47,7 @@ class Dims(C.Structure):
                 ("lds_bytes", C.c_int), ("instances_per_block", C.c_int),
                 ("lds_resident", C.c_int), ("factor_path", C.c_int), ("cone_order", C.c_int), ("dual_rhs", C.c_int),
                 ("arithmetic_profile", C.c_int), ("apex_nodes", C.c_int), ("solo_slices", C.c_int),
-                ("iterate_park", C.c_int)]
+                ("shared_operands", C.c_int), ("iterate_park", C.c_int)]
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

@@ -153,6 +153,10 @@ struct eicos_batch {
     // shared_clear on the handle's stream.  shared_on: EICOS_SHARED_VALUES (default 1) and not the LDS-resident build, whose values are
     // in LDS already; shared_maybe: the word may be 0 (spares the clearing memset of a handle that never shares).
     int *d_shared = nullptr; bool shared_on = false, shared_maybe = false;
+    // Shared factor operands (DevPat::kt0 / ub0): one allocation [kt0 | ub0], filled from instance 0 on the handle's stream behind
+    // every launch that may leave the word above at 0 (launch_range) -- so its contents are valid exactly while the word is 0, and only the
+    // stages' PLAIN instantiations, which run exactly then, read it.  NULL: not on this handle (eicos_dims.shared_operands = 0).
+    double *d_shop = nullptr;
 };
 
 namespace {
@@ -258,6 +262,7 @@ struct Plan {
     // pool arrays whose DevPat fields are typed (slice tables) or chosen by the launch shape (stored-L / deferred-L factor operands)
     const int *fsl = nullptr, *bsl = nullptr, *cag_sl = nullptr, *rA_sl = nullptr, *rG_sl = nullptr, *fac_sl = nullptr;
     const int *fac_pb_f = nullptr, *fac_pb_u = nullptr, *fac_p16_f = nullptr, *fac_p16_u = nullptr;
+    SharedOperands shop;     // which factor operands a batch that shares its matrices may read from one copy (plans.hpp); allocate() decides
     Plan() = default;
     Plan(const Plan &) = delete;
     Plan &operator=(const Plan &) = delete;
@@ -508,6 +513,9 @@ int Planner::programs() {
             if (pairless && diag_first) { D.fac_s1 = (int)s1; D.fac_nd0 = nd0; D.fac_nt0 = nt0; }
         }
     }
+    // (shared factor operands: what the plan allows; the fields stay off here -- allocate() turns them on for the handles that take the path)
+    if (!tile1) pl.shop = plan_shared_operands(S, planB, planX, D.fac_s1, D.fac_nd0, D.fac_nt0);
+    D.ub0 = nullptr; D.kt0 = nullptr; D.ub0_off = 0x7fffffff; D.kt0_pass = 0;
     // KKT entries in target order: the factor's only per-target value stream; tile mode: the dense tile image
     D.w_Kt = Wl.add((tile1 ? (size_t)(TP.nb + TP.nt) * 256 : planX.target.size()) + 8);
     D.w_Kimg = tile1 ? D.w_Kt : (tile ? Wl.add((size_t)(TP.nb + TP.nt) * 256 + 8) : 0); // hybrid: the top block's image beside the scalar stream
@@ -542,6 +550,7 @@ int Planner::programs() {
     }
     D.idx16 = (idx16_ok && env_knob("EICOS_IDX16", 1, 0, 1)) ? 1 : 0;
     fsl_i = meta_ints(planF.sl, f_o16); bsl_i = meta_ints(planB.sl, b_o16); fac_sl_i = meta_ints(planX.sl, x_o16);
+    for (size_t i = 0; i < pl.shop.slice_static.size(); i++) if (pl.shop.slice_static[i]) fac_sl_i[4 * i + 3] |= 1 << PS_STATIC; // (PackedSlice::bits)
     cag_sl_i = meta_ints(pcag.sl, cag_o16); rA_sl_i = meta_ints(prA.sl, rA_o16); rG_sl_i = meta_ints(prG.sl, rG_o16);
     return EICOS_OK;
 }
@@ -944,6 +953,16 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
         D.cag_sl = reinterpret_cast<const PackedSlice *>(pl.cag_sl); D.rA_sl = reinterpret_cast<const PackedSlice *>(pl.rA_sl);
         D.rG_sl = reinterpret_cast<const PackedSlice *>(pl.rG_sl);
         D.fac_sl = reinterpret_cast<const PackedSlice *>(pl.fac_sl);
+        h->shared_on = !h->ldsres && env_knob("EICOS_SHARED_VALUES", 1, 0, 1) != 0;
+        // shared factor operands: the scalar factor path of the builds that keep U in the workspace slab and the sweep vector in LDS
+        if (h->shared_on && !h->ubl && sh.nlds >= 1 && S.tile == 0 && pl.shop.any() && env_knob("EICOS_SHARED_OPERANDS", 1, 0, 1)) {
+            const bool ub0 = pl.shop.ub0_off != 0x7fffffff;
+            const size_t kt_len = ((size_t)D.fac_nt + 8 + 7) & ~(size_t)7, ub_len = ub0 ? (size_t)(D.nUB + 1 - pl.shop.ub0_off) + 8 : 0;
+            HIP_TRY(hipMalloc(&h->d_shop, (kt_len + ub_len) * sizeof(double)));
+            HIP_TRY(hipMemset(h->d_shop, 0, (kt_len + ub_len) * sizeof(double))); // (the padding slots and the dummy slot of ub0 stay 0)
+            D.kt0 = h->d_shop; D.kt0_pass = pl.shop.pass;
+            if (ub0) { D.ub0 = h->d_shop + kt_len; D.ub0_off = pl.shop.ub0_off; }
+        }
         h->dp = D;
         {
             std::lock_guard<std::mutex> lk(g_slot_mu);
@@ -962,7 +981,6 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
         HIP_TRY(hipMalloc(&h->d_queue, (16 + 2 * (size_t)batch) * sizeof(int))); // [0] queue head, [1] the count of a selection, [16..] launch order, [16 + batch..] candidates
         HIP_TRY(hipMalloc(&h->d_shared, 64));
         HIP_TRY(hipMemset(h->d_shared, 0xFF, 64)); // (-1: nothing shared)
-        h->shared_on = !h->ldsres && env_knob("EICOS_SHARED_VALUES", 1, 0, 1) != 0;
         HIP_TRY(hipMalloc(&h->d_scratch, (size_t)h->upd_grid * (size_t)(S.n + S.p + S.m + 8) * sizeof(double)));
         HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
         h->stream = h->own_stream;
@@ -1093,7 +1111,7 @@ int eicos_batch_destroy(eicos_batch *h) {
     if (h->own_stream) { (void)hipStreamSynchronize(h->own_stream); (void)hipStreamDestroy(h->own_stream); }
     for (int i = 0; i < eicos_batch::EV_RING; i++)
         for (hipEvent_t e : {h->ring_s[i][0], h->ring_s[i][1], h->ring_u[i][0], h->ring_u[i][1]}) if (e) (void)hipEventDestroy(e);
-    for (void *ptr : {(void *)h->d_pattern, (void *)h->d_inst, (void *)h->d_work, (void *)h->d_queue, (void *)h->d_shared, (void *)h->d_scratch,
+    for (void *ptr : {(void *)h->d_pattern, (void *)h->d_inst, (void *)h->d_work, (void *)h->d_queue, (void *)h->d_shared, (void *)h->d_shop, (void *)h->d_scratch,
                       (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out, h->d_plant, h->d_roll, h->d_mat, (void *)h->d_mstage, h->d_shift,
                       (void *)h->d_gather})
         if (ptr) (void)hipFree(ptr);
@@ -1519,6 +1537,8 @@ static int launch_range(const UpdateInputs &in, int first, int count, const doub
         if (rc != EICOS_OK) return rc;
         HIP_TRY(launch_update(h->pslot, h->d_inst, first, count, p[0], p[1], p[2], p[3], p[4], h->d_scratch, std::min(count, h->upd_grid), h->upd_lds, h->upd_vals_lds, h->stream,
                               detect ? h->d_shared : nullptr));
+        // (the one launch that may leave the word at 0: the shared factor operands follow it on the stream, from instance 0's fresh values)
+        if (detect && h->d_shop) HIP_TRY(launch_shared_operands(h->pslot, h->d_inst, h->d_shop, const_cast<double *>(D.ub0), h->stream));
     }
     return EICOS_OK;
 }
@@ -2412,6 +2432,7 @@ int eicos_batch_dims(eicos_batch *h, eicos_dims *o) {
     o->threads_per_block = h->threads; o->resident_blocks = h->grid; o->lds_bytes = (int)h->dyn_lds; o->instances_per_block = 1;
     o->lds_resident = h->ldsres; o->factor_path = h->sym.tile; o->cone_order = h->sym.cone_order; o->dual_rhs = h->dp.dual;
     o->arithmetic_profile = h->arith_profile; o->apex_nodes = h->dp.apex_na; o->solo_slices = h->dp.nfs_solo + h->dp.nbs_solo;
+    o->shared_operands = h->d_shop ? 1 : 0;
     o->iterate_park = h->dp.xpark;
     return EICOS_OK;
 }

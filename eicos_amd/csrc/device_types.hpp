@@ -48,8 +48,9 @@ constexpr int IMG_BASE = 1 << 28; // hybrid: dst >= IMG_BASE = entry (dst - IMG_
 // Device form of a slice: 16 bytes = one ds_read_b128 / s_load_dwordx4.  off16 = index of the slice's first lane
 // in the plan's packed 16-bit gather-index array (one 8-byte entry = ELL_KMAX indices per lane), see api.cpp.
 // bits: cnt [0,11) | lg [11,14) | K [14,17) | newlev 17 | last slice of its level 18 (factor plan) | more 19 | cont 20
+//       | static 21 (factor plan: no target of the slice takes its K entry from the scaling block -- DevPat::kt0; set by the host on the packed table)
 struct PackedSlice { int row0, off, off16, bits; };
-constexpr int PS_LG = 11, PS_K = 14, PS_NEWLEV = 17, PS_LAST = 18, PS_MORE = 19, PS_CONT = 20;
+constexpr int PS_LG = 11, PS_K = 14, PS_NEWLEV = 17, PS_LAST = 18, PS_MORE = 19, PS_CONT = 20, PS_STATIC = 21;
 inline PackedSlice pack_slice(const SliceMeta &m, int off16) {
     return PackedSlice{m.row0, m.off, off16,
                        m.cnt | (m.lg << PS_LG) | (m.K << PS_K) | ((m.newlev & 1) << PS_NEWLEV) | (((m.newlev >> 1) & 1) << PS_LAST) |
@@ -207,6 +208,15 @@ struct DevPat {
     // gt_cidx: per column gt_W indices into the partial sums, gt_src: value source of every tile element (updateData)
     int gt_on, gt_nrb, gt_nt, gt_W, i_Gt, w_gpart, w_gx, w_gz;
     gint_p gt_rbptr, gt_col, gt_colk, gt_zslot, gt_cidx, gt_src;
+    // Shared factor operands (plans.hpp: SharedOperands): two handle-owned arrays that hold, for the whole batch, the operands of
+    // the LDL' code whose value is a plain A, G, +-delta or 0 entry of K -- the same bits in every instance while the handle's shared-values
+    // word is 0 (filled from instance 0 behind the launch that sets the word; read only by the PLAIN instantiations of the stages).
+    //   kt0 [fac_nt]: the K stream of the factorisation in target order (entries sourced from the scaling block are never read);
+    //   ub0 [nUB + 1 - ub0_off]: the backward-sweep slots of level 0, i.e. UB slots [ub0_off, nUB] (padding and the dummy slot hold 0).
+    // ub0_off = INT_MAX / kt0 = NULL: not on this handle.  kt0_pass bit 0 / 1: the diagonal / off-diagonal streaming pass over the level-0
+    // targets has no scaling-block entry and reads kt0; a slice of the factor table says the same with its PS_STATIC bit.
+    gcdbl_p ub0, kt0;
+    int ub0_off, kt0_pass;
     size_t inst_stride, work_stride; // in doubles
 };
 

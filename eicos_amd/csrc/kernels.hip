@@ -476,17 +476,17 @@ __device__ __forceinline__ void for_t_pre3(int n0, int n1, int n2, L &&ld, F &&f
 // multiple of ELL_DEPTH slices and hold at most ELL_KMAX entries per lane and slice (longer rows are
 // cut into sub-slices whose partial sums are carried in a register).  `sm` may live in LDS (staged by k_solve) or in global memory.
 // Decoded slice descriptor; every field is workgroup-uniform (SGPRs).
-struct Sl { int row0, off, off16, cnt, lg, K, newlev, last, more, cont; };
+struct Sl { int row0, off, off16, cnt, lg, K, newlev, last, more, cont, stat; }; // (stat: PS_STATIC, factor table only)
 __device__ __forceinline__ Sl slice_decode(const PackedSlice &w) {
     const int b = uni(w.bits);
     return Sl{uni(w.row0), uni(w.off), uni(w.off16), b & ((1 << PS_LG) - 1), (b >> PS_LG) & 7, (b >> PS_K) & 7,
-              (b >> PS_NEWLEV) & 1, (b >> PS_LAST) & 1, (b >> PS_MORE) & 1, (b >> PS_CONT) & 1};
+              (b >> PS_NEWLEV) & 1, (b >> PS_LAST) & 1, (b >> PS_MORE) & 1, (b >> PS_CONT) & 1, (b >> PS_STATIC) & 1};
 }
 template <class Tab> __device__ __forceinline__ Sl slice_at(const Tab *tab, int s) {
     const PackedSlice w = tab[s]; // 16 bytes: one ds_read_b128 (LDS copy) or one global/scalar load
     const int b = uni(w.bits);
     return Sl{uni(w.row0), uni(w.off), uni(w.off16), b & ((1 << PS_LG) - 1), (b >> PS_LG) & 7, (b >> PS_K) & 7,
-              (b >> PS_NEWLEV) & 1, (b >> PS_LAST) & 1, (b >> PS_MORE) & 1, (b >> PS_CONT) & 1};
+              (b >> PS_NEWLEV) & 1, (b >> PS_LAST) & 1, (b >> PS_MORE) & 1, (b >> PS_CONT) & 1, (b >> PS_STATIC) & 1};
 }
 // The ELL_KMAX gather indices of one lane: four 32-bit loads, or (I16) one 8-byte load of four packed 16-bit indices.
 typedef const uint2 EICOS_GLOBAL *gidx16_p;
@@ -679,9 +679,14 @@ __device__ __forceinline__ void lds_barrier() {
 // workgroup barrier between its levels (one wavefront's LDS accesses execute in order), the other wavefronts
 // wait at the caller's barrier instead of issuing a full slice of masked-off instructions per level.
 // VSH (dual right-hand sides of ONE instance): the vector ws is KI-interleaved, the factor (eval, invD) is a single one.
-template <int T, bool FORWARD, bool LDSBAR, bool SOLO, bool I16, int KI, bool VSH = false, class SM, class EV, class WS>
+// SH0 (the workgroup-wide part of the backward sweep of a batch that shares its matrices: DevPat::ub0): slices whose slots start at or behind
+// ub0_off -- level 0, the tail of the plan -- take their values from the batch's one copy ub0 (slot s at ub0[s - ub0_off]; the dummy slot and
+// the padding lie in that range too and hold 0 there) instead of from the instance's own U: the same bits.  The choice is a uniform branch
+// around the value loads of a slice with the SAME number of loads in both arms, so the trips keep their counted waits; the shared copy is
+// read with plain loads (it should stay in every L2), the instance's own stream keeps the non-temporal hint.
+template <int T, bool FORWARD, bool LDSBAR, bool SOLO, bool I16, int KI, bool VSH = false, bool SH0 = false, class SM, class EV, class WS>
 __device__ __forceinline__ void tri_sweep(const SM *sm, int ns, int nr, gint_p eidx, gint_p eidx16, int d16, EV eval, gcdbl_p invD, WS ws,
-                                          int dummy_slot) {
+                                          int dummy_slot, const double EICOS_GLOBAL *ub0 = nullptr, int ub0_off = 0) {
     // KI = 2 (with VSH): the two right-hand sides of a dual solve -- one factor, the sweep vector ws 2-interleaved, so every
     // gather / store of the pair is one 16-byte LDS access
     // ns = slices of this section of the plan INCLUDING the empty ones the host pads it with (to a multiple of the queue depth: the refills
@@ -689,6 +694,7 @@ __device__ __forceinline__ void tri_sweep(const SM *sm, int ns, int nr, gint_p e
     // full step of the dependent chain (lp_afiro: three of the five steps of its forward sweep)
     if (nr == 0) { if (!SOLO) __syncthreads(); return; }
     const int t = threadIdx.x;
+    [[maybe_unused]] const double EICOS_GLOBAL *ub0r = SH0 ? ub0 - ub0_off : nullptr; // (slot s of the plan at ub0r[s])
     // the narrow tree top (SOLO, one wavefront) runs short steps: the same lead time needs a deeper queue than the workgroup-wide levels
     constexpr int DEPTH = SOLO ? TRI_DEPTH_SOLO : TRI_DEPTH;
     constexpr int TRIP = SOLO ? ((TRI_TRIP + TRI_DEPTH_SOLO - 1) / TRI_DEPTH_SOLO) * TRI_DEPTH_SOLO : TRI_TRIP; // (a multiple of the queue depth)
@@ -704,16 +710,23 @@ __device__ __forceinline__ void tri_sweep(const SM *sm, int ns, int nr, gint_p e
         o.lanes = nm.cnt << o.lg;
         const bool act = t < o.lanes;
         load_indices<I16>(o.idx, eidx, eidx16, act, o.K, o.off, o.lanes, t, dummy_slot, nm.off16, d16);
+        auto load_vals = [&](auto ntc, auto base) __attribute__((always_inline)) {
+            constexpr bool NT = decltype(ntc)::value;
 #pragma unroll
-        for (int kk = 0; kk < ELL_KMAX; kk++) {
-            const int slot = (act && kk < o.K) ? o.off + kk * o.lanes + t : dummy_slot;
-            if constexpr (VSH) { // one value for both right-hand sides
-                double v1[1];
-                ldK_g<1, true>(eval, slot, v1);
+            for (int kk = 0; kk < ELL_KMAX; kk++) {
+                const int slot = (act && kk < o.K) ? o.off + kk * o.lanes + t : dummy_slot;
+                if constexpr (VSH) { // one value for both right-hand sides
+                    double v1[1];
+                    ldK_g<1, NT>(base, slot, v1);
 #pragma unroll
-                for (int k = 0; k < KI; k++) o.val[kk][k] = v1[0];
-            } else ldK_g<KI, true>(eval, slot, o.val[kk]); // streamed once per sweep: do not displace the index arrays in L2
-        }
+                    for (int k = 0; k < KI; k++) o.val[kk][k] = v1[0];
+                } else ldK_g<KI, NT>(base, slot, o.val[kk]);
+            }
+        };
+        if constexpr (SH0) {
+            if (nm.off >= ub0_off) load_vals(std::false_type{}, ub0r); // level 0: the batch's one copy
+            else load_vals(std::true_type{}, eval);
+        } else load_vals(std::true_type{}, eval); // streamed once per sweep: do not displace the index arrays in L2
         const int r = act ? o.row0 + (t >> o.lg) : 0;
         if constexpr (FORWARD) { // forward is L y = b with unit-lower L: no pivot needed
 #pragma unroll
@@ -1248,7 +1261,9 @@ enum Stage { ST_FACTOR = 0, ST_KKT_INIT1, ST_KKT_INIT2, ST_RESID, ST_KKT1, ST_KK
 
 // ---------------- ST_FACTOR: numeric LDL' (replaces ldlt.factorize, ref :900,1164) ----------------
 // Wg = the workgroup's workspace slab.  Left-looking sliced-ELL program over the level schedule (host: plans.cpp, api.cpp).
-template <int T, int NLDS, bool I16, bool DEFER>
+// SH0 (a batch that shares its matrices, solve_instance's `plain`): the K entries of the level-0 passes and of the slices that hold no
+// scaling-block target (DevPat::kt0_pass, PS_STATIC) come from the batch's one copy DevPat::kt0 -- a uniform select of the base address.
+template <int T, int NLDS, bool I16, bool DEFER, bool SH0 = false>
 static __device__ __noinline__ __attribute__((not_tail_called)) void stage_factor(int ps, gdbl_p Wg) {
     ps = uni(ps); Wg = uni_ptr(Wg);
     const DevPat &P = c_pat[ps];
@@ -1256,6 +1271,12 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void stage_facto
     gdbl_p UF = Wg + P.w_UF, D = Wg + P.w_D, invD = Wg + P.w_invD;
     ubdbl_p U = [&] { if constexpr (EICOS_UBL != 0) return (ubdbl_p)(g_dyn + P.ub_lds); else return (ubdbl_p)(Wg + P.w_UB); }(); // pa/pb index UB slots
     gcdbl_p Kt = Wg + P.w_Kt;    // KKT entries in target order (solve prologue + updateKKTScalings)
+    gcdbl_p Kt0 = Kt, KtD = Kt, KtO = Kt; // static slices / the diagonal / the off-diagonal pass of level 0
+#if !EICOS_LDSRES && !EICOS_UBL
+    if constexpr (SH0) {
+        if (P.kt0) { Kt0 = uni_ptr(P.kt0); const int ps0 = uni(P.kt0_pass); if (ps0 & 1) KtD = Kt0; if (ps0 & 2) KtO = Kt0; }
+    }
+#endif
     gdbl_p Kimg = Wg + P.w_Kimg; // hybrid: targets of the top block go to its tile image
     __syncthreads();
     unsigned long long tk0_ = (tid == 0) ? wall_clock64() : 0ull;
@@ -1304,7 +1325,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void stage_facto
             }
         }
         const int t = act ? o.row0 + (tid >> o.lg) : 0;
-        o.kv = ld_u32(Kt, t);
+        if constexpr (SH0) o.kv = ld_u32(nm.stat ? Kt0 : Kt, t); else o.kv = ld_u32(Kt, t);
         o.dst = ld_u32(P.fac_dst, t);
     };
     // a diagonal target: pivot (with the optional dynamic regularisation, extension N4) -> D, 1/D; zero pivot -> fatal
@@ -1328,7 +1349,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void stage_facto
     const int sbeg = P.fac_s1;
     if constexpr (NLDS >= 1) { if (defer) { if (tid == 0) g_dyn[P.fac_kpad] = 0.; __syncthreads(); } } // (what padding pairs read; the global array keeps a 0 there)
     if (P.fac_nt0 > 0) {
-        for_t_pre<T, 8>(P.fac_nd0, [&](int t) { return IV1{ld_u32(P.fac_dst, t), ld_u32(Kt, t)}; }, [&](int t, const IV1 &r) {
+        for_t_pre<T, 8>(P.fac_nd0, [&](int t) { return IV1{ld_u32(P.fac_dst, t), ld_u32(KtD, t)}; }, [&](int t, const IV1 &r) {
             if (r.i >= IMG_BASE) Kimg[r.i - IMG_BASE] = r.a; else pivot(r.i, r.a);
         });
         __syncthreads();
@@ -1336,7 +1357,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void stage_facto
         for_t_pre<T, 8>(P.fac_nt0 - P.fac_nd0, [&](int q_) {
             const int t = P.fac_nd0 + q_;
             const int col = ld_u32(P.fac_col, t);
-            return F1{ld_u32(P.fac_dst, t), ld_u32(P.fac_dstF, t), ld_u32(Kt, t), defer ? inv_of(col) : invD[col]};
+            return F1{ld_u32(P.fac_dst, t), ld_u32(P.fac_dstF, t), ld_u32(KtO, t), defer ? inv_of(col) : invD[col]};
         }, [&](int, const F1 &r) {
             if (r.dst >= IMG_BASE) { Kimg[r.dst - IMG_BASE] = r.kv; return; }
             U[r.dst] = r.kv;
@@ -2394,7 +2415,10 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
 #endif
             }
             __syncthreads();
-            tri_sweep<T, false, true, false, I16, KI, DUAL>(tabs + P.lm_b + P.nbs_solo, P.nbs, P.nbs_r, P.b_idx, P.b_idx16, P.b_d16, UB, invD, SV, P.nUB);
+            // (a batch that shares its matrices: the level-0 slices from the batch's one copy -- DevPat::ub0; INT_MAX = not on this handle)
+            constexpr bool SH0 = PLAIN && EICOS_UBL == 0 && EICOS_LDSRES == 0;
+            tri_sweep<T, false, true, false, I16, KI, DUAL, SH0>(tabs + P.lm_b + P.nbs_solo, P.nbs, P.nbs_r, P.b_idx, P.b_idx16, P.b_d16, UB, invD, SV, P.nUB,
+                                                                 uni_ptr(P.ub0), uni(P.ub0_off));
         } else {
             tri_sweep<T, true, false, false, I16, KI, DUAL>(P.fsl, P.nfs, P.nfs_r, P.f_idx, P.f_idx16, P.f_d16, UF, invD, SV, P.nUF);
             if (P.tile == 2) {
@@ -3124,7 +3148,13 @@ __device__ __forceinline__ void solve_instance(int ps, gdbl_p I, gdbl_p W, doubl
 #endif
     while (stage != ST_DONE) {
         if (stage == ST_FACTOR) {
-            if (P.tile != 1) { if (P.fac_defer) stage_factor<T, NLDS, I16, true>(ps, W); else stage_factor<T, NLDS, I16, false>(ps, W); } // scalar program (hybrid: everything below the top block + its image)
+            if (P.tile != 1) { // scalar program (hybrid: everything below the top block + its image)
+                constexpr bool SHOP = NLDS >= 1 && EICOS_UBL == 0 && EICOS_LDSRES == 0; // (builds that can carry the shared factor operands: DevPat::kt0)
+                if constexpr (SHOP) {
+                    if (plain) { if (P.fac_defer) stage_factor<T, NLDS, I16, true, true>(ps, W); else stage_factor<T, NLDS, I16, false, true>(ps, W); }
+                    else if (P.fac_defer) stage_factor<T, NLDS, I16, true>(ps, W); else stage_factor<T, NLDS, I16, false>(ps, W);
+                } else { if (P.fac_defer) stage_factor<T, NLDS, I16, true>(ps, W); else stage_factor<T, NLDS, I16, false>(ps, W); }
+            }
             if (P.tile) stage_factor_tiles<T, NLDS>(ps, I, W, iter);
             if (g_S.fl[FL_FATAL]) { // zero pivot -> fatal, no backscale (ref :901-905,1166-1170): the iterate as it stands is the result
                 if (g_S.cur != 0) {
@@ -3962,6 +3992,19 @@ __global__ __launch_bounds__(T) void k_gather_rows(int ps, const double *inst, c
     }
 }
 
+// The shared factor operands of a handle (launch.hpp: launch_shared_operands; DevPat::kt0 / ub0) from instance 0's slab: the K entry of every
+// target, and the entries of the level-0 columns once more at their backward slot.  Grid-stride over the targets; ub0's other slots keep their 0.
+template <int T>
+__global__ __launch_bounds__(T) void k_shared_operands(int ps, const double *inst, double *kt0, double *ub0) {
+    const DevPat &P = c_pat[ps];
+    for (int t = blockIdx.x * T + threadIdx.x; t < P.fac_nt; t += gridDim.x * T) {
+        const double v = inst[P.fac_src[t]];
+        kt0[t] = v;
+        const int dst = P.fac_dst[t]; // (the slots [ub0_off, nUB) hold the entries of the level-0 columns and nothing else)
+        if (ub0 && dst >= P.ub0_off && dst < P.nUB) ub0[dst - P.ub0_off] = v;
+    }
+}
+
 // Debug: factorise instance `i` with the KKT scaling block as it stands in memory (runs the solver's own stage).
 template <int T>
 __global__ __launch_bounds__(T, waves_per_eu<T>()) void k_debug_factor(int ps, double *inst, double *work, int i) {
@@ -4060,6 +4103,11 @@ hipError_t launch_update(int ps, double *inst, int first, int count, const doubl
     } else if (lds_bytes > 0) { // values + maxima fit LDS: the entry-parallel kernel, 512 threads, one workgroup per CU at a time
         hipLaunchKernelGGL((k_update_lds<512, true>), dim3(grid), dim3(512), lds_bytes, st, ps, inst, first, count, Gpr, Apr, c, h, b, shared);
     } else hipLaunchKernelGGL(k_update<256>, dim3(grid), dim3(256), 0, st, ps, inst, first, count, Gpr, Apr, c, h, b, scratch, shared);
+    return hipGetLastError();
+}
+hipError_t launch_shared_operands(int ps, const double *inst, double *kt0, double *ub0, hipStream_t st) {
+    constexpr int T = 256;
+    hipLaunchKernelGGL(k_shared_operands<T>, dim3(32), dim3(T), 0, st, ps, inst, kt0, ub0);
     return hipGetLastError();
 }
 hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st) {

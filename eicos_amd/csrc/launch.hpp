@@ -91,6 +91,10 @@ struct SolveBuild {
 hipError_t launch_update(int ps, double *inst, int first, int count, const double *Gpr, const double *Apr,
                          const double *c, const double *h, const double *b, double *scratch, int grid, size_t lds_bytes, int vals_in_lds, hipStream_t st,
                          int *shared = nullptr);
+// The shared factor operands of a handle (DevPat::kt0 / ub0), behind the launch_update that was given `shared`: kt0[t] = the K entry of target
+// t as instance 0's slab holds it (DevPat::fac_src), and every level-0 off-diagonal target that lands in a backward slot >= ub0_off also
+// into ub0 (ub0 == NULL: the handle shares the K stream only).  Plain copies: the bits instance_begin and the factorisation would produce.
+hipError_t launch_shared_operands(int ps, const double *inst, double *kt0, double *ub0, hipStream_t st);
 // right-hand-side-only updateData of instances [first, first + count): rows of c [count][n], h [count][m], b [count][p] (NULL = keep)
 // divided by each instance's stored scalings; `width` = the summed widths of the given groups (sizes the grid)
 hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st);

@@ -206,6 +206,45 @@ FactorPlan build_factor_plan(const Symbolic &S, int T, const std::vector<int> &p
     return pl;
 }
 
+SharedOperands plan_shared_operands(const Symbolic &S, const TriPlan &planB, const FactorPlan &planX, int s1, int nd0, int nt0) {
+    SharedOperands so;
+    so.slice_static.assign(planX.sl.size(), 0);
+    if (S.tile != 0) return so;
+    // ---- level 0 of the backward sweep: the last level of the workgroup-wide section ----
+    int first = -1;
+    for (int s = planB.n_solo; s < planB.n_solo + planB.n_wide; s++)
+        if (planB.sl[(size_t)s].cnt > 0 && (planB.sl[(size_t)s].newlev & 1)) first = s;
+    if (first >= 0 && S.nlev > 0 && planB.sl[(size_t)first].row0 == S.lev_ptr[0]) {
+        const int off0 = planB.sl[(size_t)first].off;
+        bool ok = true;
+        for (int s = planB.n_solo; s < first && ok; s++) { // every earlier slice of the section ends in front of the level's slots
+            const SliceMeta &m = planB.sl[(size_t)s];
+            if (m.cnt > 0 && m.off + m.K * (m.cnt << m.lg) > off0) ok = false;
+        }
+        for (int j = S.lev_ptr[0]; j < S.lev_ptr[1] && ok; j++)
+            for (int e = S.Lp[j]; e < S.Lp[j + 1] && ok; e++) {
+                if (S.Lkind[(size_t)e] == SRC_V) ok = false;                                      // an entry of the scaling block: per instance and pass
+                if (planB.pos[(size_t)e] < off0 || planB.pos[(size_t)e] >= planB.slots) ok = false; // (by construction: never)
+            }
+        if (ok) { so.ub0_off = off0; so.ub0_slice = first - planB.n_solo; }
+    }
+    // ---- the K stream of the factorisation ----
+    auto from_v = [&](int t) {
+        const int tgt = planX.target[(size_t)t];
+        return (tgt < S.N ? S.Dkind[(size_t)tgt] : S.Lkind[(size_t)(tgt - S.N)]) == SRC_V;
+    };
+    auto none_from_v = [&](int t0, int t1) { for (int t = t0; t < t1; t++) if (from_v(t)) return false; return true; };
+    if (nt0 > 0) {
+        if (nd0 > 0 && none_from_v(0, nd0)) { so.pass |= 1; so.static_targets += nd0; }
+        if (nt0 > nd0 && none_from_v(nd0, nt0)) { so.pass |= 2; so.static_targets += nt0 - nd0; }
+    }
+    for (size_t i = (size_t)std::max(s1, 0); i < planX.sl.size(); i++) {
+        const SliceMeta &m = planX.sl[i];
+        if (m.cnt > 0 && none_from_v(m.row0, m.row0 + m.cnt)) { so.slice_static[i] = 1; if (!m.cont) so.static_targets += m.cnt; }
+    }
+    return so;
+}
+
 EllPlan build_ell_plan(const std::vector<int> &ptr, int nrows, int T) {
     EllPlan pl;
     auto len = [&](int r) { return ptr[r + 1] - ptr[r]; };

@@ -63,4 +63,21 @@ struct FactorPlan {
 FactorPlan build_factor_plan(const Symbolic &S, int T, const std::vector<int> &posB, int dummyB,
                              const std::vector<int> &posF, int dummyF);
 
+// Shared factor operands (DevPat::ub0 / kt0): which operands of the scalar LDL' code are plain A, G, +-delta or 0 entries of K -- the same
+// bits in every instance of a batch that shares its matrices -- by Symbolic::Lkind / Dkind.
+//   ub0_off: first value slot of level 0 of the backward plan's workgroup-wide section (the level is the section's last, its slots the tail
+//     of the value array, so slots [ub0_off, planB.slots] -- padding and the dummy included -- are exactly what the sweep reads from there
+//     on); INT_MAX when the pattern has no such section, or when a level-0 column holds an entry of the scaling block (refused as a whole).
+//   pass: bit 0 / 1 = the diagonal / off-diagonal targets of the factor program's level 0 ([0, nd0) / [nd0, nt0)) hold no scaling-block entry.
+//   slice_static[i] = 1: no target of slice i of the factor plan is a scaling-block entry (sub-slices of one row set share the flag).
+// Everything off on the tile and hybrid paths.
+struct SharedOperands {
+    int ub0_off = 0x7fffffff, ub0_slice = -1; // (ub0_slice: that level's first slice, counted from the start of the wide section)
+    int pass = 0;
+    std::vector<char> slice_static;
+    int static_targets = 0; // targets of level >= 1 slices flagged static + the targets of static level-0 passes (for the byte accounting)
+    bool any() const { return ub0_off != 0x7fffffff || pass != 0 || static_targets > 0; }
+};
+SharedOperands plan_shared_operands(const Symbolic &S, const TriPlan &planB, const FactorPlan &planX, int s1, int nd0, int nt0);
+
 } // namespace eicos

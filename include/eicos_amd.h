@@ -79,6 +79,10 @@ typedef struct eicos_dims {
      * single-wavefront part of the two sweep plans (0 = no split); two handles on one pattern with equal threads_per_block, factor_path,
      * apex_nodes and solo_slices give bit-identical results for equal data */
     int arithmetic_profile, apex_nodes, solo_slices;
+    int shared_operands; /* 1: the handle keeps one copy of the factor operands that are plain entries of A, G or constants (the K entries of
+                          * the numeric factorisation outside the scaling block, the level-0 columns of the backward sweep), filled when
+                          * eicos_batch_shared_values turns 1 and read by every instance while it stays 1; 0: every instance reads its own
+                          * (builds that keep the factor in LDS, the tile paths, EICOS_SHARED_VALUES=0).  Results are bit-identical. */
     int iterate_park; /* where a refinement step of the KKT solve keeps the iterate while the LDS vector serves the sweeps: 1 = registers of
                        * the owning threads (two-waves-per-SIMD build, dim_K <= 26 * threads_per_block), 0 = the workspace slab (or the
                        * iterate has an LDS vector of its own); the results are bit-identical */
