@@ -32,6 +32,7 @@
 #include "affine_pack.hpp"
 #include "fused_fit.hpp"
 #include "exit_class.hpp"
+#include "resources.hpp"
 
 using namespace eicos;
 // Workgroups per CU for a batch, at most `max_r`: the cheapest estimate of the launch's duration wins.
@@ -65,11 +66,39 @@ static std::atomic<int> g_arith_profile{0};
 static std::mutex g_slot_mu;
 static std::map<int, std::vector<char>> g_slot_used; // per device: which constant-memory descriptor slots are taken (under g_slot_mu)
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
-#define HIP_TRY(expr)                                                                              \
+// HIP_TRY_AS: the message names the HIP call `what` -- for calls made through the handle's buffers (resources.hpp), so that their
+// failures read as they did when the call stood here itself ("hipMalloc...: out of memory").  HIP_TRY: the expression is the name.
+#define HIP_TRY_AS(what, expr)                                                                     \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(EICOS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) return fail(EICOS_E_HIP, std::string(what) + ": " + hipGetErrorString(e_)); \
     } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(#expr, expr)
+
+// The memory and event policies of the handle's buffers (resources.hpp): the only places that allocate or free for a handle.
+struct HipPolicy {
+    using error_t = hipError_t; using stream_t = hipStream_t;
+    static constexpr hipError_t ok = hipSuccess;
+    static hipError_t sync(hipStream_t s) { return hipStreamSynchronize(s); }
+};
+struct DeviceMem : HipPolicy {
+    static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void *p) { (void)hipFree(p); }
+};
+struct PinnedMem : HipPolicy {
+    static hipError_t alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+struct HipEvent {
+    using event_t = hipEvent_t;
+    static hipError_t create(hipEvent_t *e) { return hipEventCreateWithFlags(e, hipEventDisableTiming); }
+    static void destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+    static hipError_t record(hipEvent_t e, hipStream_t s) { return hipEventRecord(e, s); }
+    static hipError_t sync(hipEvent_t e) { return hipEventSynchronize(e); }
+};
+using DevBuf = Buffer<DeviceMem>;
+using PinBuf = Buffer<PinnedMem>;
+using PinSlot = PinnedSlot<PinnedMem, HipEvent>;
 
 struct eicos_batch {
     ProblemPattern pat;
@@ -81,7 +110,7 @@ struct eicos_batch {
     bool last_subset = false; int last_count = 0; // ... whether it took a chosen subset (eicos_batch_solve_subset / _solve_where), and how many instances
     size_t upd_lds = 0;       // > 0: updateData runs the entry-parallel kernel with this much dynamic LDS (values + maxima)
     int upd_vals_lds = 1;     // 1: its working copy of the values is in LDS too; 0: streamed in place in the instance slab
-    int *d_pattern = nullptr;
+    DevBuf d_pattern;        // the pattern image (int32 arrays; DevPat points into it)
     int pslot = -1; // slot of this handle's DevPat in the kernels' constant-memory table
     size_t dyn_lds = 0;
     int nlds = 0;
@@ -89,22 +118,25 @@ struct eicos_batch {
     int ubl = 0;              // 1: solves run the build with the factor operand array U in LDS (ubl256:: / ubl512::solve_entries; one workgroup per CU)
     int ldsres = 0;           // 1: solves run the LDS-resident kernel (ldsres::solve_entries), slabs copied in and out per instance
     size_t pattern_ints = 0;
-    double *d_inst = nullptr, *d_work = nullptr, *d_scratch = nullptr;
-    int *d_queue = nullptr; // instance queue of the solve kernel (reset per launch): [16-int header | launch order [batch] | candidates of a subset launch [batch]]
-    // subset calls: a host index list travels through one pinned buffer of `batch` ints (sub_ev: its last upload); the row gather packs the
-    // chosen instances' rows into d_gather = [ids | rows], grown on demand
-    int *sub_pin = nullptr; hipEvent_t sub_ev = nullptr; bool sub_busy = false;
-    char *d_gather = nullptr; size_t gather_bytes = 0;
-    double *d_stage = nullptr; size_t stage_doubles = 0; // peer-copy updateData without peer access: persistent staging buffer (one chunk)
+    DevBuf d_inst, d_work, d_scratch; // the instance slabs, the workspace slabs of the resident workgroups, the updateData scratch
+    DevBuf d_queue; // instance queue of the solve kernel (reset per launch): [16-int header | launch order [batch] | candidates of a subset launch [batch]]
+    // (what the enqueue path reads of them: a member load each)
+    double *inst() const { return d_inst.as<double>(); }
+    double *work() const { return d_work.as<double>(); }
+    int *queue() const { return d_queue.as<int>(); }
+    // subset calls: a host index list travels through one pinned buffer of `batch` ints; the row gather packs the chosen instances' rows
+    // into d_gather = [ids | rows]
+    PinSlot sub;
+    DevBuf d_gather;
+    DevBuf d_stage; // peer-copy updateData without peer access: staging buffer (one chunk)
     // host-pointer updateData / results (the reference's real signature: updateData(double *...), solution() on the host): two PINNED
     // bounce buffers (hipHostMalloc).  Input chunk k is copied into pin[k & 1] by the host while the GPU's updateData kernel reads chunk
     // k - 1 straight out of the other one over PCIe (the kernel's loads are the transfer: no device-side staging copy, no per-chunk
     // stream synchronisation); results come back through the same buffers, the strided device-to-host copy of chunk k + 1 in flight
-    // while the host copies chunk k out.  pin_ev[i]: the last GPU work that touches pin[i].
-    double *pin[2] = {nullptr, nullptr}; size_t pin_doubles = 0;
-    hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_busy[2] = {false, false};
+    // while the host copies chunk k out.
+    PinSlot pin[2];
     int last_update_path = 0; // how the most recent host/peer updateData moved its inputs: 1 pinned bounce, 2 zero-copy (pinned source), 3 peer zero-copy, 4 peer staged copies, 5 fused into the solve launch, 6 the same with pageable arrays staged while the kernel runs
-    int *d_flag = nullptr;   // debug hooks
+    DevBuf d_flag;           // debug hooks
     double warm_shift = 0.; // > 0: warm start (eicos_batch_set_warm_start)
     double dyn_delta = 0., dyn_eps = 0.; // > 0: dynamic regularisation (eicos_batch_set_dynamic_regularization)
     SolveCfg cfg = solve_cfg_default(); // runtime settings (eicos_batch_set_settings): every solve launch carries a copy by value
@@ -124,26 +156,26 @@ struct eicos_batch {
     int bpc = 1, n_cu = 256; // workgroups per CU of the solve launch; CUs of the device
     int arith_profile = 0;   // eicos_set_arithmetic_profile at creation
     // eicos_batch_update_solve from pageable host memory: one pinned staging buffer for the whole batch (+ one ready flag per chunk), filled while the kernel runs
-    double *stage_pin = nullptr; size_t stage_pin_doubles = 0; unsigned *stage_flags = nullptr; int stage_nflags = 0; unsigned stage_seq = 0;
-    int *d_err = nullptr;
+    PinBuf stage_pin, stage_flags; unsigned stage_seq = 0;
+    DevBuf d_err;
     // parametric right-hand sides (eicos_batch_set_param_map): the map's arrays in one device allocation, param.k = 0 while none is installed
     // (d_param starts with a device copy of `param` itself, MAP_HEADER bytes: what the fused step's workgroups read -- launch.hpp: UpdArgs)
-    ParamMapDev param{}; void *d_param = nullptr;
+    ParamMapDev param{}; DevBuf d_param;
     // output map (eicos_batch_set_output_map): one device allocation [OutMapDev | u rows of the batch | base, val | rowptr, col], out.r = 0
     // while none is installed; d_u = the [batch][r] rows the range kernel fills for a host destination
-    OutMapDev out{}; void *d_out = nullptr; double *d_u = nullptr;
+    OutMapDev out{}; DevBuf d_out; double *d_u = nullptr;
     // plant map (eicos_batch_set_plant_map): one device allocation [PlantMapDev (MAP_HEADER bytes) | base, val | rowptr, col], plant.k = 0 while none is installed
-    PlantMapDev plant{}; void *d_plant = nullptr;
-    // rollout (eicos_batch_rollout): one device allocation, grown on demand: [RolloutDev (MAP_HEADER bytes) | theta, u, w trajectories | two
+    PlantMapDev plant{}; DevBuf d_plant;
+    // rollout (eicos_batch_rollout): one device allocation: [RolloutDev (MAP_HEADER bytes) | theta, u, w trajectories | two
     // theta rows of the batch (the path that is not fused) | codes, iters]; roll = the host copy of the record of the most recent call
-    RolloutDev roll{}; void *d_roll = nullptr; size_t roll_bytes = 0; int rollout_launches = 0;
+    RolloutDev roll{}; DevBuf d_roll; int rollout_launches = 0;
     // matrix map (eicos_batch_set_matrix_map): one device allocation [MatrixMapDev (MAP_HEADER bytes) | base, val | rowptr, col], mat.k = 0
     // while none is installed; d_mstage = the device staging buffer the range path expands [Gpr | Apr | c | h | b] of a chunk of instances
-    // into (param_range), grown on demand up to MSTAGE_CAP_MB
-    MatrixMapDev mat{}; void *d_mat = nullptr; double *d_mstage = nullptr; size_t mstage_doubles = 0;
+    // into (param_range), up to MSTAGE_CAP_MB
+    MatrixMapDev mat{}; DevBuf d_mat, d_mstage;
     // shift map (eicos_batch_set_shift_map): one device allocation [ShiftMapDev (MAP_HEADER bytes) | base, val | rowptr, col]; every solve
-    // launch of the handle carries its address (UpdArgs::smap), d_shift = NULL while none is installed
-    ShiftMapDev shift{}; void *d_shift = nullptr;
+    // launch of the handle carries its address (UpdArgs::smap), d_shift empty while none is installed
+    ShiftMapDev shift{}; DevBuf d_shift;
     TilePlan tiles;        // tile mode (Symbolic::tile): the dense-front plan
     // Shared product values (eicos_batch_shared_values): ONE device word.  -1: every instance streams the product values of
     // its own slab.  0: the last writer of matrix values was a full updateData over [0, batch) from arrays the GPU addresses, and its
@@ -152,11 +184,19 @@ struct eicos_batch {
     // i_rA, i_rG, i_Gt: a sub-range or group-keeping updateData, the chunked paths, the matrix map, the fused forms) is preceded by
     // shared_clear on the handle's stream.  shared_on: EICOS_SHARED_VALUES (default 1) and not the LDS-resident build, whose values are
     // in LDS already; shared_maybe: the word may be 0 (spares the clearing memset of a handle that never shares).
-    int *d_shared = nullptr; bool shared_on = false, shared_maybe = false;
+    DevBuf d_shared; bool shared_on = false, shared_maybe = false;
     // Shared factor operands (DevPat::kt0 / ub0): one allocation [kt0 | ub0], filled from instance 0 on the handle's stream behind
     // every launch that may leave the word above at 0 (launch_range) -- so its contents are valid exactly while the word is 0, and only the
-    // stages' PLAIN instantiations, which run exactly then, read it.  NULL: not on this handle (eicos_dims.shared_operands = 0).
-    double *d_shop = nullptr;
+    // stages' PLAIN instantiations, which run exactly then, read it.  Empty: not on this handle (eicos_dims.shared_operands = 0).
+    DevBuf d_shop;
+
+    // The events and the stream the handle made; the buffers free themselves after this body.  eicos_batch_destroy has set the device and
+    // waited for both streams: nothing here synchronises.
+    ~eicos_batch() {
+        if (own_stream) (void)hipStreamDestroy(own_stream);
+        for (int i = 0; i < EV_RING; i++)
+            for (hipEvent_t e : {ring_s[i][0], ring_s[i][1], ring_u[i][0], ring_u[i][1]}) if (e) (void)hipEventDestroy(e);
+    }
 };
 
 namespace {
@@ -931,7 +971,7 @@ static int launch_shape(Plan &pl, int batch, int device, Shape &sh) {
 
 // Allocation step: the only code that gives a handle device resources -- the pattern image, the descriptor slot (uploaded to the default
 // build and to the chosen one), the slabs, the instance queue, the updateData scratch and the stream.  One cleanup path:
-// eicos_batch_destroy takes a partly set-up handle.
+// eicos_batch_destroy takes a partly set-up handle, whose members free what was made.
 static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, int device, int n_cu, int profile, eicos_batch **out) {
     std::lock_guard<std::mutex> create_lock(create_mutex(device));
     eicos_batch *h = new eicos_batch();
@@ -944,10 +984,10 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
     const Symbolic &S = pl.an->sym;
     const int rc = [&]() -> int {
         HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipMalloc(&h->d_pattern, pl.pool.data.size() * sizeof(int)));
-        HIP_TRY(hipMemcpy(h->d_pattern, pl.pool.data.data(), pl.pool.data.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY_AS("hipMalloc", h->d_pattern.alloc(pl.pool.data.size() * sizeof(int)));
+        HIP_TRY(hipMemcpy(h->d_pattern.p, pl.pool.data.data(), pl.pool.data.size() * sizeof(int), hipMemcpyHostToDevice));
         DevPat &D = pl.dp;
-        for (auto &s : pl.slots) *s.dst = h->d_pattern + s.off;
+        for (auto &s : pl.slots) *s.dst = h->d_pattern.as<int>() + s.off;
         D.fac_pb = D.fac_defer ? pl.fac_pb_u : pl.fac_pb_f; D.fac_p16 = D.fac_defer ? pl.fac_p16_u : pl.fac_p16_f;
         D.fsl = reinterpret_cast<const PackedSlice *>(pl.fsl); D.bsl = reinterpret_cast<const PackedSlice *>(pl.bsl);
         D.cag_sl = reinterpret_cast<const PackedSlice *>(pl.cag_sl); D.rA_sl = reinterpret_cast<const PackedSlice *>(pl.rA_sl);
@@ -958,10 +998,10 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
         if (h->shared_on && !h->ubl && sh.nlds >= 1 && S.tile == 0 && pl.shop.any() && env_knob("EICOS_SHARED_OPERANDS", 1, 0, 1)) {
             const bool ub0 = pl.shop.ub0_off != 0x7fffffff;
             const size_t kt_len = ((size_t)D.fac_nt + 8 + 7) & ~(size_t)7, ub_len = ub0 ? (size_t)(D.nUB + 1 - pl.shop.ub0_off) + 8 : 0;
-            HIP_TRY(hipMalloc(&h->d_shop, (kt_len + ub_len) * sizeof(double)));
-            HIP_TRY(hipMemset(h->d_shop, 0, (kt_len + ub_len) * sizeof(double))); // (the padding slots and the dummy slot of ub0 stay 0)
-            D.kt0 = h->d_shop; D.kt0_pass = pl.shop.pass;
-            if (ub0) { D.ub0 = h->d_shop + kt_len; D.ub0_off = pl.shop.ub0_off; }
+            HIP_TRY_AS("hipMalloc", h->d_shop.alloc((kt_len + ub_len) * sizeof(double)));
+            HIP_TRY(hipMemset(h->d_shop.p, 0, h->d_shop.bytes)); // (the padding slots and the dummy slot of ub0 stay 0)
+            D.kt0 = h->d_shop.as<double>(); D.kt0_pass = pl.shop.pass;
+            if (ub0) { D.ub0 = h->d_shop.as<double>() + kt_len; D.ub0_off = pl.shop.ub0_off; }
         }
         h->dp = D;
         {
@@ -974,14 +1014,14 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
         const SolveBuild main_build = solve_entries(), sbuild = solve_build(h->threads, h->ldsres, h->w2, h->ubl);
         HIP_TRY(main_build.upload(h->pslot, h->dp)); // (the default namespace always: updateData and the debug kernels live there)
         if (!(sbuild == main_build)) HIP_TRY(sbuild.upload(h->pslot, h->dp));
-        HIP_TRY(hipMalloc(&h->d_inst, (size_t)batch * D.inst_stride * sizeof(double)));
-        HIP_TRY(hipMemset(h->d_inst, 0, (size_t)batch * D.inst_stride * sizeof(double)));
-        HIP_TRY(hipMalloc(&h->d_work, (size_t)h->grid * D.work_stride * sizeof(double)));
-        HIP_TRY(hipMemset(h->d_work, 0, (size_t)h->grid * D.work_stride * sizeof(double)));
-        HIP_TRY(hipMalloc(&h->d_queue, (16 + 2 * (size_t)batch) * sizeof(int))); // [0] queue head, [1] the count of a selection, [16..] launch order, [16 + batch..] candidates
-        HIP_TRY(hipMalloc(&h->d_shared, 64));
-        HIP_TRY(hipMemset(h->d_shared, 0xFF, 64)); // (-1: nothing shared)
-        HIP_TRY(hipMalloc(&h->d_scratch, (size_t)h->upd_grid * (size_t)(S.n + S.p + S.m + 8) * sizeof(double)));
+        HIP_TRY_AS("hipMalloc", h->d_inst.alloc((size_t)batch * D.inst_stride * sizeof(double)));
+        HIP_TRY(hipMemset(h->d_inst.p, 0, h->d_inst.bytes));
+        HIP_TRY_AS("hipMalloc", h->d_work.alloc((size_t)h->grid * D.work_stride * sizeof(double)));
+        HIP_TRY(hipMemset(h->d_work.p, 0, h->d_work.bytes));
+        HIP_TRY_AS("hipMalloc", h->d_queue.alloc((16 + 2 * (size_t)batch) * sizeof(int))); // [0] queue head, [1] the count of a selection, [16..] launch order, [16 + batch..] candidates
+        HIP_TRY_AS("hipMalloc", h->d_shared.alloc(64));
+        HIP_TRY(hipMemset(h->d_shared.p, 0xFF, 64)); // (-1: nothing shared)
+        HIP_TRY_AS("hipMalloc", h->d_scratch.alloc((size_t)h->upd_grid * (size_t)(S.n + S.p + S.m + 8) * sizeof(double)));
         HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
         h->stream = h->own_stream;
         // (the event pairs of the timing rings are created on first use: next_events)
@@ -1007,22 +1047,22 @@ static_assert(sizeof(ParamMapDev) <= MAP_HEADER && sizeof(OutMapDev) <= MAP_HEAD
 // g take its place -- *M is the new descriptor and `out` its AffineDev array of n, filled here; `gap` bytes behind the header stay
 // uninitialised (the output map's u rows).
 template <class Desc>
-static int install_map(eicos_batch *h, void *&slot, Desc &cur, const char *name, const AffineGroup *g, int n, size_t gap, Desc *M, AffineDev *out) {
+static int install_map(eicos_batch *h, DevBuf &slot, Desc &cur, const char *name, const AffineGroup *g, int n, size_t gap, Desc *M, AffineDev *out) {
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
-    if (slot) { (void)hipFree(slot); slot = nullptr; }
+    slot.reset(); // (first, so that the old and the new map never coexist; a failure below leaves the handle without this map)
     cur = Desc{};
     if (!M) return EICOS_OK;
     const AffineLayout lay = affine_layout(g, n, MAP_HEADER, gap);
-    void *dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, lay.bytes()));
-    std::vector<char> image = affine_pack(g, n, lay, dev, out);
+    DevBuf dev;
+    HIP_TRY_AS("hipMalloc", dev.alloc(lay.bytes()));
+    std::vector<char> image = affine_pack(g, n, lay, dev.p, out);
     std::memcpy(image.data(), M, sizeof *M);
-    char *dc = static_cast<char *>(dev);
+    char *dc = dev.as<char>();
     hipError_t e = hipMemcpy(dc, image.data(), gap ? MAP_HEADER : image.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess && gap) e = hipMemcpy(dc + MAP_HEADER + gap, image.data() + MAP_HEADER, image.size() - MAP_HEADER, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(dev); return fail(EICOS_E_HIP, std::string("hipMemcpy of the ") + name + " map: " + hipGetErrorString(e)); }
-    slot = dev; cur = *M;
+    if (e != hipSuccess) return fail(EICOS_E_HIP, std::string("hipMemcpy of the ") + name + " map: " + hipGetErrorString(e));
+    slot = std::move(dev); cur = *M;
     return EICOS_OK;
 }
 
@@ -1108,22 +1148,10 @@ int eicos_batch_destroy(eicos_batch *h) {
     (void)hipSetDevice(h->device);
     // in-flight work may sit on a caller stream (eicos_batch_set_stream): wait for it before the slabs go away
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->own_stream) { (void)hipStreamSynchronize(h->own_stream); (void)hipStreamDestroy(h->own_stream); }
-    for (int i = 0; i < eicos_batch::EV_RING; i++)
-        for (hipEvent_t e : {h->ring_s[i][0], h->ring_s[i][1], h->ring_u[i][0], h->ring_u[i][1]}) if (e) (void)hipEventDestroy(e);
-    for (void *ptr : {(void *)h->d_pattern, (void *)h->d_inst, (void *)h->d_work, (void *)h->d_queue, (void *)h->d_shared, (void *)h->d_shop, (void *)h->d_scratch,
-                      (void *)h->d_stage, (void *)h->d_flag, h->d_param, h->d_out, h->d_plant, h->d_roll, h->d_mat, (void *)h->d_mstage, h->d_shift,
-                      (void *)h->d_gather})
-        if (ptr) (void)hipFree(ptr);
-    if (h->sub_pin) (void)hipHostFree(h->sub_pin);
-    if (h->sub_ev) (void)hipEventDestroy(h->sub_ev);
-    for (int i = 0; i < 2; i++) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
-    if (h->stage_pin) (void)hipHostFree(h->stage_pin);
-    if (h->stage_flags) (void)hipHostFree(h->stage_flags);
-    if (h->d_err) (void)hipFree(h->d_err);
+    if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
     // the constant-memory descriptor slot is handed out again only after nothing can read it any more
     if (h->pslot >= 0) { std::lock_guard<std::mutex> lk(g_slot_mu); g_slot_used[h->device][h->pslot] = 0; }
-    delete h;
+    delete h; // (~eicos_batch: events and stream, then every buffer)
     return EICOS_OK;
 }
 
@@ -1328,15 +1356,7 @@ MemKind memory_kind(const void *p, size_t bytes) {
 }
 // the handle's two pinned bounce buffers hold at least `doubles` each
 int ensure_pin(eicos_batch *h, size_t doubles) {
-    if (doubles <= h->pin_doubles) return EICOS_OK;
-    for (int i = 0; i < 2; i++) {
-        if (h->pin_busy[i]) { HIP_TRY(hipEventSynchronize(h->pin_ev[i])); h->pin_busy[i] = false; }
-        if (h->pin[i]) { (void)hipHostFree(h->pin[i]); h->pin[i] = nullptr; }
-        if (!h->pin_ev[i]) HIP_TRY(hipEventCreateWithFlags(&h->pin_ev[i], hipEventDisableTiming));
-    }
-    h->pin_doubles = 0;
-    for (int i = 0; i < 2; i++) HIP_TRY(hipHostMalloc((void **)&h->pin[i], doubles * sizeof(double), hipHostMallocDefault));
-    h->pin_doubles = doubles;
+    for (PinSlot &s : h->pin) HIP_TRY_AS("hipHostMalloc", s.reserve(doubles * sizeof(double)));
     return EICOS_OK;
 }
 constexpr size_t PIN_CHUNK_BYTES = 16u << 20; // bounce buffer size aimed at (per buffer)
@@ -1462,12 +1482,12 @@ static int take_theta(UpdateInputs &in, eicos_batch *h, int first, int count, co
 // of any instance and is not the detecting one.  shared_detect: in front of the ONE launch that may leave it set.
 static int shared_clear(eicos_batch *h) {
     if (!h->shared_maybe) return EICOS_OK;
-    HIP_TRY(hipMemsetAsync(h->d_shared, 0xFF, sizeof(int), h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_shared.p, 0xFF, sizeof(int), h->stream));
     h->shared_maybe = false;
     return EICOS_OK;
 }
 static int shared_detect(eicos_batch *h) {
-    HIP_TRY(hipMemsetAsync(h->d_shared, 0, sizeof(int), h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_shared.p, 0, sizeof(int), h->stream));
     h->shared_maybe = true;
     return EICOS_OK;
 }
@@ -1478,7 +1498,7 @@ static int param_range(eicos_batch *h, int first, int count, const double *theta
     const ParamMapDev &M = h->param;
     if (h->mat.k == 0) {
         const int width = (M.g[0].base ? D.n : 0) + (M.g[1].base ? D.m : 0) + (M.g[2].base ? D.p : 0);
-        HIP_TRY(launch_update_param(h->pslot, h->d_inst, first, count, M, theta, width, h->stream));
+        HIP_TRY(launch_update_param(h->pslot, h->inst(), first, count, M, theta, width, h->stream));
         return EICOS_OK;
     }
     if (count == 0) return EICOS_OK;
@@ -1491,24 +1511,18 @@ static int param_range(eicos_batch *h, int first, int count, const double *theta
     for (int g = 0; g < 5; g++) if (src[g]) per += (size_t)w[g] + 8; // (+ 8 doubles per array: every array of a chunk starts 64-byte aligned)
     const size_t cap = (size_t)env_knob("EICOS_MATRIX_STAGE_MB", MSTAGE_CAP_MB, 1, 4096) * ((1u << 20) / sizeof(double));
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, cap / per));
-    const size_t need = (size_t)chunk * per;
-    if (need > h->mstage_doubles) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->d_mstage) { (void)hipFree(h->d_mstage); h->d_mstage = nullptr; h->mstage_doubles = 0; }
-        HIP_TRY(hipMalloc((void **)&h->d_mstage, need * sizeof(double)));
-        h->mstage_doubles = need;
-    }
+    HIP_TRY_AS("hipMalloc", h->d_mstage.reserve((size_t)chunk * per * sizeof(double), h->stream));
     for (int o = 0; o < count; o += chunk) {
         const int cnt = std::min(chunk, count - o);
         const double *arr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        double *at = h->d_mstage;
+        double *at = h->d_mstage.as<double>();
         for (int g = 0; g < 5; g++) {
             if (!src[g]) continue;
             arr[g] = at;
             HIP_TRY(launch_expand_affine(*src[g], w[g], M.k, theta + (size_t)o * M.k, cnt, at, h->stream));
             at += ((size_t)cnt * w[g] + 7) / 8 * 8;
         }
-        HIP_TRY(launch_update(h->pslot, h->d_inst, first + o, cnt, arr[0], arr[1], arr[2], arr[3], arr[4], h->d_scratch, std::min(cnt, h->upd_grid),
+        HIP_TRY(launch_update(h->pslot, h->inst(), first + o, cnt, arr[0], arr[1], arr[2], arr[3], arr[4], h->d_scratch.as<double>(), std::min(cnt, h->upd_grid),
                               h->upd_lds, h->upd_vals_lds, h->stream));
     }
     ParamMapDev rest{};
@@ -1516,7 +1530,7 @@ static int param_range(eicos_batch *h, int first, int count, const double *theta
     if (!mG) rest.g[1] = M.g[1];
     if (!mA) rest.g[2] = M.g[2];
     const int width = (rest.g[1].base ? D.m : 0) + (rest.g[2].base ? D.p : 0);
-    HIP_TRY(launch_update_param(h->pslot, h->d_inst, first, count, rest, theta, width, h->stream));
+    HIP_TRY(launch_update_param(h->pslot, h->inst(), first, count, rest, theta, width, h->stream));
     return EICOS_OK;
 }
 
@@ -1524,21 +1538,21 @@ static int param_range(eicos_batch *h, int first, int count, const double *theta
 // pattern has among them it is the launch that compares every row of Gpr / Apr with row 0 (launch.hpp: launch_update)
 static int launch_range(const UpdateInputs &in, int first, int count, const double *const p[5], bool in_place = false) {
     eicos_batch *h = in.h;
-    if (in.iterate) HIP_TRY(launch_set_iterate(h->pslot, h->d_inst, first, count, p[0], p[1], p[2], p[3], (int)in.per, h->stream));
+    if (in.iterate) HIP_TRY(launch_set_iterate(h->pslot, h->inst(), first, count, p[0], p[1], p[2], p[3], (int)in.per, h->stream));
     else if (in.param) {
         const int rc = param_range(h, first, count, p[2]);
         if (rc != EICOS_OK) return rc;
-    } else if (in.rhs) HIP_TRY(launch_update_rhs(h->pslot, h->d_inst, first, count, p[2], p[3], p[4], (int)in.per, h->stream));
+    } else if (in.rhs) HIP_TRY(launch_update_rhs(h->pslot, h->inst(), first, count, p[2], p[3], p[4], (int)in.per, h->stream));
     else {
         const DevPat &D = h->dp;
         const bool detect = in_place && in.detect && h->shared_on && first == 0 && count == h->batch && D.nnzG + D.nnzA > 0 &&
                             (p[0] || D.nnzG == 0) && (p[1] || D.nnzA == 0);
         const int rc = detect ? shared_detect(h) : (count > 0 ? shared_clear(h) : EICOS_OK);
         if (rc != EICOS_OK) return rc;
-        HIP_TRY(launch_update(h->pslot, h->d_inst, first, count, p[0], p[1], p[2], p[3], p[4], h->d_scratch, std::min(count, h->upd_grid), h->upd_lds, h->upd_vals_lds, h->stream,
-                              detect ? h->d_shared : nullptr));
+        HIP_TRY(launch_update(h->pslot, h->inst(), first, count, p[0], p[1], p[2], p[3], p[4], h->d_scratch.as<double>(), std::min(count, h->upd_grid), h->upd_lds, h->upd_vals_lds, h->stream,
+                              detect ? h->d_shared.as<int>() : nullptr));
         // (the one launch that may leave the word at 0: the shared factor operands follow it on the stream, from instance 0's fresh values)
-        if (detect && h->d_shop) HIP_TRY(launch_shared_operands(h->pslot, h->d_inst, h->d_shop, const_cast<double *>(D.ub0), h->stream));
+        if (detect && h->d_shop) HIP_TRY(launch_shared_operands(h->pslot, h->inst(), h->d_shop.as<double>(), const_cast<double *>(D.ub0), h->stream));
     }
     return EICOS_OK;
 }
@@ -1589,14 +1603,9 @@ static int peer_update(const UpdateInputs &in, int src_dev) {
     // no peer access: staged peer copies, one chunk at a time through the device staging buffer
     h->last_update_path = 4;
     const int chunk = 256;
-    const size_t need = staging_doubles(in, std::min(in.count, chunk));
-    if (need > h->stage_doubles) {
-        if (h->d_stage) { HIP_TRY(hipStreamSynchronize(h->stream)); (void)hipFree(h->d_stage); h->d_stage = nullptr; h->stage_doubles = 0; }
-        HIP_TRY(hipMalloc(&h->d_stage, need * sizeof(double)));
-        h->stage_doubles = need;
-    }
+    HIP_TRY_AS("hipMalloc", h->d_stage.reserve(staging_doubles(in, std::min(in.count, chunk)) * sizeof(double), h->stream));
     Staging st;
-    st.area = [&](int, double *&area) -> int { area = h->d_stage; return EICOS_OK; };
+    st.area = [&](int, double *&area) -> int { area = h->d_stage.as<double>(); return EICOS_OK; };
     st.put = [&](double *dst, const double *src, size_t bytes) -> int {
         return hipMemcpyPeerAsync(dst, h->device, src, src_dev, bytes, h->stream) == hipSuccess ? EICOS_OK : fail(EICOS_E_HIP, "hipMemcpyPeerAsync failed");
     };
@@ -1634,17 +1643,13 @@ static int host_update(const UpdateInputs &in) {
     CopyPool &pool = CopyPool::get();
     Staging st;
     st.area = [&](int k, double *&area) -> int { // the kernel that read this buffer two chunks ago (or an earlier call's) must have finished
-        const int bi = k & 1;
-        if (h->pin_busy[bi] && hipEventSynchronize(h->pin_ev[bi]) != hipSuccess) return fail(EICOS_E_HIP, "event sync failed in update");
-        h->pin_busy[bi] = false;
-        area = h->pin[bi];
+        if (h->pin[k & 1].wait() != hipSuccess) return fail(EICOS_E_HIP, "event sync failed in update");
+        area = h->pin[k & 1].as<double>();
         return EICOS_OK;
     };
     st.put = [&](double *dst, const double *src, size_t bytes) -> int { pool.copy(dst, src, bytes); return EICOS_OK; };
     st.launched = [&](int k) -> int { // (the launch reads the pinned buffer in place)
-        if (hipEventRecord(h->pin_ev[k & 1], h->stream) != hipSuccess) return fail(EICOS_E_HIP, "event record failed in update");
-        h->pin_busy[k & 1] = true;
-        return EICOS_OK;
+        return h->pin[k & 1].mark(h->stream) == hipSuccess ? EICOS_OK : fail(EICOS_E_HIP, "event record failed in update");
     };
     return update_in_chunks(in, chunk, st);
 }
@@ -1786,7 +1791,7 @@ int eicos_batch_set_output_map(eicos_batch *h, int r, const eicos_affine_map *u)
     OutMapDev M{};
     M.r = r;
     const int rc = install_map(h, h->d_out, h->out, "output", &g, 1, (size_t)h->batch * r * sizeof(double), remove ? nullptr : &M, &M.a);
-    h->d_u = h->d_out ? reinterpret_cast<double *>(static_cast<char *>(h->d_out) + MAP_HEADER) : nullptr;
+    h->d_u = h->d_out ? reinterpret_cast<double *>(h->d_out.as<char>() + MAP_HEADER) : nullptr;
     return rc;
 }
 
@@ -1806,9 +1811,9 @@ static int take_output_range(eicos_batch *h, int first, int count, const double 
 // itself (asynchronous), host memory gets the handle's rows d_u over the paths of fetch_strided (synchronous)
 static int outputs_to(eicos_batch *h, int first, int count, double *u, MemKind kind) {
     if (count == 0) return EICOS_OK;
-    if (kind == MEM_DEVICE) { HIP_TRY(launch_outputs(h->pslot, h->d_inst, first, count, h->out, u, h->stream)); return EICOS_OK; }
+    if (kind == MEM_DEVICE) { HIP_TRY(launch_outputs(h->pslot, h->inst(), first, count, h->out, u, h->stream)); return EICOS_OK; }
     double *rows = h->d_u + (size_t)first * h->out.r;
-    HIP_TRY(launch_outputs(h->pslot, h->d_inst, first, count, h->out, rows, h->stream));
+    HIP_TRY(launch_outputs(h->pslot, h->inst(), first, count, h->out, rows, h->stream));
     const int rc = fetch_strided(h, u, rows, (size_t)h->out.r * sizeof(double), h->out.r, count);
     if (rc != EICOS_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1829,11 +1834,11 @@ int eicos_batch_outputs_device(eicos_batch *h, int first, int count, double *du)
 }
 
 // the candidate ids of a subset launch, in device memory behind the launch order
-static int *subset_ids(const eicos_batch *h) { return h->d_queue + 16 + h->batch; }
+static int *subset_ids(const eicos_batch *h) { return h->queue() + 16 + h->batch; }
 // the launch record of a handle's solves (launch.hpp); subset >= 0: a launch over the `subset` ids in subset_ids(h) instead of the batch
 static SolveLaunch solve_launch(const eicos_batch *h, int subset) {
     SolveLaunch L{};
-    L.ps = h->pslot; L.inst = h->d_inst; L.work = h->d_work; L.B = h->batch; L.queue = h->d_queue; L.order = h->d_queue + 16;
+    L.ps = h->pslot; L.inst = h->inst(); L.work = h->work(); L.B = h->batch; L.queue = h->queue(); L.order = h->queue() + 16;
     L.grid = h->grid; L.threads = h->threads; L.nlds = h->nlds; L.idx16 = h->dp.idx16; L.order_min = h->order_min;
     L.warm = h->warm_shift; L.dyn_delta = h->dyn_delta; L.dyn_eps = h->dyn_eps; L.cfg = h->cfg; L.dyn_lds = h->dyn_lds;
     L.batch = h->batch; L.full_grid = h->grid;
@@ -1849,9 +1854,9 @@ static int enqueue_solve(eicos_batch *h, const UpdArgs *step, int subset = -1) {
     HIP_TRY(hipEventRecord(h->ev_s0, h->stream));
     UpdArgs args = step ? *step : UpdArgs{};
     // (a shift map and the shared-values word travel with EVERY launch, the ones without a fused update included: instance_begin reads them)
-    args.smap = static_cast<const ShiftMapDev *>(h->d_shift);
+    args.smap = h->d_shift.as<const ShiftMapDev>();
     if (writes_matrix_values(args)) { const int rc = shared_clear(h); if (rc != EICOS_OK) return rc; } // (the step drops the shared values)
-    args.shared = h->shared_on ? h->d_shared : nullptr;
+    args.shared = h->shared_on ? h->d_shared.as<int>() : nullptr;
     HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(solve_launch(h, subset), h->stream, args));
     HIP_TRY(hipEventRecord(h->ev_s1, h->stream));
     h->solve_timed = true;
@@ -1887,12 +1892,12 @@ static int fetch_strided(eicos_batch *h, double *dst, const double *src, size_t 
     chunk = std::min(chunk, count);
     int rc = ensure_pin(h, (size_t)chunk * width);
     if (rc != EICOS_OK) return rc;
-    for (int i = 0; i < 2; i++) if (h->pin_busy[i]) { HIP_TRY(hipEventSynchronize(h->pin_ev[i])); h->pin_busy[i] = false; }
+    for (PinSlot &s : h->pin) HIP_TRY_AS("hipEventSynchronize", s.wait());
     CopyPool &pool = CopyPool::get();
     auto issue = [&](int o, int bi) -> int {
         const int cnt = std::min(chunk, count - o);
-        HIP_TRY(hipMemcpy2DAsync(h->pin[bi], wb, src + (size_t)o * stride, pitch, wb, (size_t)cnt, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipEventRecord(h->pin_ev[bi], h->stream));
+        HIP_TRY(hipMemcpy2DAsync(h->pin[bi].as<void>(), wb, src + (size_t)o * stride, pitch, wb, (size_t)cnt, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY_AS("hipEventRecord", h->pin[bi].mark(h->stream));
         return EICOS_OK;
     };
     rc = issue(0, 0);
@@ -1901,13 +1906,13 @@ static int fetch_strided(eicos_batch *h, double *dst, const double *src, size_t 
         const int cnt = std::min(chunk, count - o), bi = k & 1;
         if (o + chunk < count) rc = issue(o + chunk, bi ^ 1);
         if (rc != EICOS_OK) break;
-        HIP_TRY(hipEventSynchronize(h->pin_ev[bi]));
-        pool.copy(dst + (size_t)o * width, h->pin[bi], (size_t)cnt * wb);
+        HIP_TRY_AS("hipEventSynchronize", h->pin[bi].wait());
+        pool.copy(dst + (size_t)o * width, h->pin[bi].as<void>(), (size_t)cnt * wb);
     }
     return rc;
 }
 static int fetch_rows(eicos_batch *h, double *dst, int off, int width) {
-    return fetch_strided(h, dst, h->d_inst + off, h->dp.inst_stride * sizeof(double), width, h->batch);
+    return fetch_strided(h, dst, h->inst() + off, h->dp.inst_stride * sizeof(double), width, h->batch);
 }
 
 // the public form of an instance's info record
@@ -1926,7 +1931,7 @@ int eicos_batch_info(eicos_batch *h, eicos_info *info) {
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     std::vector<DevInfo> tmp(h->batch);
-    HIP_TRY(hipMemcpy2D(tmp.data(), sizeof(DevInfo), h->d_inst + h->dp.i_info, h->dp.inst_stride * sizeof(double),
+    HIP_TRY(hipMemcpy2D(tmp.data(), sizeof(DevInfo), h->inst() + h->dp.i_info, h->dp.inst_stride * sizeof(double),
                         sizeof(DevInfo), (size_t)h->batch, hipMemcpyDeviceToHost));
     for (int i = 0; i < h->batch; i++) info_from(tmp[i], info[i]);
     return EICOS_OK;
@@ -1967,24 +1972,17 @@ static int take_class_mask(const eicos_batch *h, unsigned mask, const char *who)
 }
 // `count` validated ids from the host into device memory at dst, on the handle's stream, through the pinned list buffer
 static int upload_ids(eicos_batch *h, const int *idx, int count, int *dst) {
-    if (!h->sub_pin) HIP_TRY(hipHostMalloc((void **)&h->sub_pin, (size_t)h->batch * sizeof(int), hipHostMallocDefault));
-    if (!h->sub_ev) HIP_TRY(hipEventCreateWithFlags(&h->sub_ev, hipEventDisableTiming));
-    if (h->sub_busy) { HIP_TRY(hipEventSynchronize(h->sub_ev)); h->sub_busy = false; } // (the previous list may still be on its way)
-    std::memcpy(h->sub_pin, idx, (size_t)count * sizeof(int));
-    HIP_TRY(hipMemcpyAsync(dst, h->sub_pin, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipEventRecord(h->sub_ev, h->stream));
-    h->sub_busy = true;
+    HIP_TRY_AS("hipHostMalloc", h->sub.reserve((size_t)h->batch * sizeof(int))); // (once: every list fits)
+    HIP_TRY_AS("hipEventSynchronize", h->sub.wait()); // (the previous list may still be on its way)
+    std::memcpy(h->sub.as<int>(), idx, (size_t)count * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(dst, h->sub.as<int>(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY_AS("hipEventRecord", h->sub.mark(h->stream));
     return EICOS_OK;
 }
-// the compact buffer of the row gather: [ids of `count` instances | count rows of `width` doubles], grown on demand
+// the compact buffer of the row gather: [ids of `count` instances | count rows of `width` doubles]
 static size_t gather_rows_at(int count) { return (((size_t)count * sizeof(int)) + 63) & ~(size_t)63; }
 static int grow_gather(eicos_batch *h, int count, int width) {
-    const size_t need = gather_rows_at(count) + (size_t)count * width * sizeof(double);
-    if (need <= h->gather_bytes) return EICOS_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->d_gather) { (void)hipFree(h->d_gather); h->d_gather = nullptr; h->gather_bytes = 0; }
-    HIP_TRY(hipMalloc((void **)&h->d_gather, need));
-    h->gather_bytes = need;
+    HIP_TRY_AS("hipMalloc", h->d_gather.reserve(gather_rows_at(count) + (size_t)count * width * sizeof(double), h->stream));
     return EICOS_OK;
 }
 // rows of the instances d_list[0 .. count) (device memory; NULL: the ids already at the head of d_gather) into the caller's arrays, any
@@ -1996,8 +1994,8 @@ static int gather_rows(eicos_batch *h, const int *d_list, int count, double *x, 
     const int width = gather_width(want, D.n, D.p, D.m);
     const int rc = grow_gather(h, count, width);
     if (rc != EICOS_OK) return rc;
-    double *rows = reinterpret_cast<double *>(h->d_gather + gather_rows_at(count));
-    HIP_TRY(launch_gather_rows(h->pslot, h->d_inst, d_list ? d_list : reinterpret_cast<const int *>(h->d_gather), count, want, rows, h->stream));
+    double *rows = reinterpret_cast<double *>(h->d_gather.as<char>() + gather_rows_at(count));
+    HIP_TRY(launch_gather_rows(h->pslot, h->inst(), d_list ? d_list : h->d_gather.as<const int>(), count, want, rows, h->stream));
     std::vector<double> host((size_t)count * width);
     const int frc = fetch_strided(h, host.data(), rows, (size_t)width * sizeof(double), width, count);
     if (frc != EICOS_OK) return frc;
@@ -2022,8 +2020,8 @@ static int gather_rows(eicos_batch *h, const int *d_list, int count, double *x, 
 static int select_ids(eicos_batch *h, unsigned mask, int *idx_out, int *count) {
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(launch_select(h->pslot, h->d_inst, h->batch, mask, subset_ids(h), h->d_queue + 1, h->stream));
-    HIP_TRY(hipMemcpyAsync(count, h->d_queue + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(launch_select(h->pslot, h->inst(), h->batch, mask, subset_ids(h), h->queue() + 1, h->stream));
+    HIP_TRY(hipMemcpyAsync(count, h->queue() + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (*count < 0 || *count > h->batch) return fail(EICOS_E_HIP, "internal: the selection kernel returned a count outside the batch");
     if (idx_out && *count > 0) {
@@ -2074,7 +2072,7 @@ int eicos_batch_gather(eicos_batch *h, const int *idx, int count, double *x, dou
     HIP_TRY(hipStreamSynchronize(h->stream));
     // (the buffer for the widest row a call can ask for, so that the ids at its head stay where they are)
     rc = grow_gather(h, count, gather_width(GATHER_X | GATHER_Y | GATHER_Z | GATHER_S | GATHER_INFO, h->dp.n, h->dp.p, h->dp.m));
-    if (rc == EICOS_OK) rc = upload_ids(h, idx, count, reinterpret_cast<int *>(h->d_gather));
+    if (rc == EICOS_OK) rc = upload_ids(h, idx, count, h->d_gather.as<int>());
     return rc != EICOS_OK ? rc : gather_rows(h, nullptr, count, x, y, z, s, info, nullptr);
 }
 
@@ -2085,22 +2083,13 @@ static int fused_step_begins(eicos_batch *h, int path) {
     h->last_update_path = path;
     return end_update_timing(h, begin_update_timing(h));
 }
-// the pinned staging buffer (`doubles`), the ready flags (`nchunks`) and the time-out word of a staged fused update, grown on demand
+// the pinned staging buffer (`doubles`), the ready flags (`nchunks`) and the time-out word of a staged fused update
 static int grow_staging(eicos_batch *h, size_t doubles, int nchunks) {
-    if (doubles > h->stage_pin_doubles) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->stage_pin) { (void)hipHostFree(h->stage_pin); h->stage_pin = nullptr; h->stage_pin_doubles = 0; }
-        HIP_TRY(hipHostMalloc((void **)&h->stage_pin, doubles * sizeof(double), hipHostMallocDefault));
-        h->stage_pin_doubles = doubles;
-    }
-    if (nchunks > h->stage_nflags) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->stage_flags) { (void)hipHostFree(h->stage_flags); h->stage_flags = nullptr; h->stage_nflags = 0; }
-        HIP_TRY(hipHostMalloc((void **)&h->stage_flags, (size_t)nchunks * sizeof(unsigned), hipHostMallocDefault));
-        std::memset(h->stage_flags, 0, (size_t)nchunks * sizeof(unsigned));
-        h->stage_nflags = nchunks; h->stage_seq = 0;
-    }
-    if (!h->d_err) { HIP_TRY(hipMalloc((void **)&h->d_err, sizeof(int))); HIP_TRY(hipMemset(h->d_err, 0, sizeof(int))); }
+    bool new_flags = false;
+    HIP_TRY_AS("hipHostMalloc", h->stage_pin.reserve(doubles * sizeof(double), h->stream));
+    HIP_TRY_AS("hipHostMalloc", h->stage_flags.reserve((size_t)nchunks * sizeof(unsigned), h->stream, &new_flags));
+    if (new_flags) { std::memset(h->stage_flags.p, 0, h->stage_flags.bytes); h->stage_seq = 0; } // (fresh flags: the sequence starts over)
+    if (!h->d_err) { HIP_TRY_AS("hipMalloc", h->d_err.alloc(sizeof(int))); HIP_TRY(hipMemset(h->d_err.p, 0, sizeof(int))); }
     return EICOS_OK;
 }
 // x_out [batch][n], u_out [batch][r] (NULL: not asked for) behind a finished solve, by kind of memory unless the kernel wrote it; complete on return
@@ -2109,7 +2098,7 @@ static int deliver_results(eicos_batch *h, double *x_out, MemKind x_kind, bool x
     if (x_out && !x_written) {
         if (x_kind == MEM_DEVICE) { // a result array in device memory: one strided copy on the device
             const size_t wb = (size_t)D.n * sizeof(double);
-            HIP_TRY(hipMemcpy2DAsync(x_out, wb, h->d_inst + D.i_x, D.inst_stride * sizeof(double), wb, (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipMemcpy2DAsync(x_out, wb, h->inst() + D.i_x, D.inst_stride * sizeof(double), wb, (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
         } else { const int rc = fetch_rows(h, x_out, D.i_x, D.n); if (rc != EICOS_OK) return rc; }
     }
@@ -2183,10 +2172,10 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
     if (any_staged) {
         rc = grow_staging(h, stage_need, nchunks);
         if (rc != EICOS_OK) return rc;
-        double *at = h->stage_pin;
+        double *at = h->stage_pin.as<double>();
         for (int k = 0; k < 5; k++) if (staged[k]) { ptr[k] = at; at += (size_t)h->batch * in.w[k] + 8; }
         h->stage_seq++;
-        if (h->stage_seq == 0) { std::memset(h->stage_flags, 0, (size_t)h->stage_nflags * sizeof(unsigned)); h->stage_seq = 1; } // (wrapped)
+        if (h->stage_seq == 0) { std::memset(h->stage_flags.p, 0, h->stage_flags.bytes); h->stage_seq = 1; } // (wrapped)
     }
     rc = fused_step_begins(h, any_staged ? 6 : 5);
     if (rc != EICOS_OK) return rc;
@@ -2195,9 +2184,9 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
     step.on = param ? UPD_PARAM : (rhs ? UPD_RHS : UPD_FULL);
     step.G = ptr[0]; step.A = ptr[1]; (param ? step.theta : step.c) = ptr[2]; step.h = ptr[3]; step.b = ptr[4];
     step.x = x_written ? x_out : nullptr; step.u = u_written ? u_out : nullptr;
-    step.flags = any_staged ? h->stage_flags : nullptr; step.chunk = chunk; step.seq = h->stage_seq; step.err = h->d_err;
-    step.pmap = static_cast<const ParamMapDev *>(h->d_param); step.omap = static_cast<const OutMapDev *>(h->d_out);
-    if (param && h->mat.k) step.mmap = static_cast<const MatrixMapDev *>(h->d_mat);
+    step.flags = any_staged ? h->stage_flags.as<unsigned>() : nullptr; step.chunk = chunk; step.seq = h->stage_seq; step.err = h->d_err.as<int>();
+    step.pmap = h->d_param.as<const ParamMapDev>(); step.omap = h->d_out.as<const OutMapDev>();
+    if (param && h->mat.k) step.mmap = h->d_mat.as<const MatrixMapDev>();
     rc = enqueue_solve(h, &step);
     if (rc != EICOS_OK) return rc; // (nothing was launched: no workgroup waits for a flag)
     if (any_staged) { // the kernel is running: copy chunk by chunk and release each chunk's flag behind its rows
@@ -2205,15 +2194,15 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
         for (int q = 0; q < nchunks; q++) {
             const size_t r0 = (size_t)q * chunk, rows = std::min<size_t>((size_t)chunk, (size_t)h->batch - r0);
             for (int k = 0; k < 5; k++) if (staged[k]) pool.copy(const_cast<double *>(ptr[k]) + r0 * in.w[k], in.src[k] + r0 * in.w[k], rows * in.w[k] * sizeof(double));
-            __atomic_store_n(&h->stage_flags[q], h->stage_seq, __ATOMIC_RELEASE); // (stream_copy ends with an sfence: the rows are visible before the flag)
+            __atomic_store_n(&h->stage_flags.as<unsigned>()[q], h->stage_seq, __ATOMIC_RELEASE); // (stream_copy ends with an sfence: the rows are visible before the flag)
         }
     }
     rc = eicos_batch_sync(h);
     if (rc != EICOS_OK) return rc;
     if (any_staged) {
         int err = 0;
-        HIP_TRY(hipMemcpy(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
-        if (err) { HIP_TRY(hipMemset(h->d_err, 0, sizeof(int))); return fail(EICOS_E_HIP, "fused updateData: a workgroup timed out waiting for its staged rows"); }
+        HIP_TRY(hipMemcpy(&err, h->d_err.p, sizeof(int), hipMemcpyDeviceToHost));
+        if (err) { HIP_TRY(hipMemset(h->d_err.p, 0, sizeof(int))); return fail(EICOS_E_HIP, "fused updateData: a workgroup timed out waiting for its staged rows"); }
     }
     rc = deliver_results(h, x_out, x_kind, x_written, u_out, u_kind, u_written);
     return rc != EICOS_OK ? rc : exit_codes(h, exitcodes);
@@ -2324,18 +2313,12 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = (size_t)h->batch, T = (size_t)steps;
     const size_t n_th = B * (T + 1) * k, n_u = B * T * r, n_w = w ? B * T * k : 0, n_cur = 2 * B * k, n_rec = B * T;
-    const size_t need = MAP_HEADER + (n_th + n_u + n_w + n_cur) * sizeof(double) + 2 * n_rec * sizeof(int);
-    if (need > h->roll_bytes) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->d_roll) { (void)hipFree(h->d_roll); h->d_roll = nullptr; h->roll_bytes = 0; }
-        HIP_TRY(hipMalloc(&h->d_roll, need));
-        h->roll_bytes = need;
-    }
-    double *d_th = reinterpret_cast<double *>(static_cast<char *>(h->d_roll) + MAP_HEADER), *d_uu = d_th + n_th, *d_w = d_uu + n_u, *d_cur = d_w + n_w;
+    HIP_TRY_AS("hipMalloc", h->d_roll.reserve(MAP_HEADER + (n_th + n_u + n_w + n_cur) * sizeof(double) + 2 * n_rec * sizeof(int), h->stream));
+    double *d_th = reinterpret_cast<double *>(h->d_roll.as<char>() + MAP_HEADER), *d_uu = d_th + n_th, *d_w = d_uu + n_u, *d_cur = d_w + n_w;
     int *d_codes = reinterpret_cast<int *>(d_cur + n_cur), *d_iters = d_codes + n_rec;
     h->roll = RolloutDev{steps, h->plant, d_th, d_uu, w ? d_w : nullptr, d_codes, d_iters};
     const size_t row_b = (size_t)k * sizeof(double);
-    HIP_TRY(hipMemcpyAsync(h->d_roll, &h->roll, sizeof(RolloutDev), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_roll.p, &h->roll, sizeof(RolloutDev), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpy2DAsync(d_th, (T + 1) * row_b, theta0, row_b, row_b, B, hipMemcpyDefault, h->stream)); // row 0 of every trajectory
     if (w) HIP_TRY(hipMemcpyAsync(d_w, w, n_w * sizeof(double), hipMemcpyDefault, h->stream));
     const bool fused = fused_rollout_fits(fit_shape(h), k, r, h->mat.k != 0) && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
@@ -2344,9 +2327,9 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
         rc = fused_step_begins(h, 5);
         if (rc != EICOS_OK) return rc;
         UpdArgs step;
-        step.on = UPD_ROLL; step.roll = static_cast<const RolloutDev *>(h->d_roll);
-        step.pmap = static_cast<const ParamMapDev *>(h->d_param); step.omap = static_cast<const OutMapDev *>(h->d_out);
-        if (h->mat.k) step.mmap = static_cast<const MatrixMapDev *>(h->d_mat);
+        step.on = UPD_ROLL; step.roll = h->d_roll.as<const RolloutDev>();
+        step.pmap = h->d_param.as<const ParamMapDev>(); step.omap = h->d_out.as<const OutMapDev>();
+        if (h->mat.k) step.mmap = h->d_mat.as<const MatrixMapDev>();
         rc = enqueue_solve(h, &step);
         if (rc != EICOS_OK) return rc;
     } else {
@@ -2359,8 +2342,8 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
             rc = end_update_timing(h, rc);
             if (rc == EICOS_OK) rc = enqueue_solve(h, nullptr);
             if (rc != EICOS_OK) return rc;
-            HIP_TRY(launch_outputs(h->pslot, h->d_inst, 0, h->batch, h->out, h->d_u, h->stream));
-            HIP_TRY(launch_plant(h->pslot, h->d_inst, 0, h->batch, h->roll, t, cur, h->d_u, next, h->stream));
+            HIP_TRY(launch_outputs(h->pslot, h->inst(), 0, h->batch, h->out, h->d_u, h->stream));
+            HIP_TRY(launch_plant(h->pslot, h->inst(), 0, h->batch, h->roll, t, cur, h->d_u, next, h->stream));
         }
     }
     h->rollout_launches = fused ? 1 : steps;
@@ -2391,7 +2374,7 @@ int eicos_batch_duals(eicos_batch *h, double *y, double *z, double *s) {
 
 int eicos_batch_solution_device(eicos_batch *h, const double **dx, size_t *stride) {
     if (!h || !dx || !stride) return fail(EICOS_E_INVALID, "NULL argument");
-    *dx = h->d_inst + h->dp.i_x; *stride = h->dp.inst_stride;
+    *dx = h->inst() + h->dp.i_x; *stride = h->dp.inst_stride;
     return EICOS_OK;
 }
 
@@ -2400,7 +2383,7 @@ int eicos_batch_shared_values(eicos_batch *h) {
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     int v = -1;
-    HIP_TRY(hipMemcpy(&v, h->d_shared, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&v, h->d_shared.p, sizeof(int), hipMemcpyDeviceToHost));
     return (h->shared_on && v >= 0) ? 1 : 0;
 }
 
@@ -2471,26 +2454,26 @@ int eicos_debug_factor(eicos_batch *h, int inst, double *Dout, double *Uout) {
     if (!h || inst < 0 || inst >= h->batch) return fail(EICOS_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(launch_debug_factor(h->pslot, h->d_inst, h->d_work, inst, h->threads, h->sym.tile ? h->dyn_lds : 0, h->stream));
+    HIP_TRY(launch_debug_factor(h->pslot, h->inst(), h->work(), inst, h->threads, h->sym.tile ? h->dyn_lds : 0, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const DevPat &P = h->dp;
     if (h->sym.tile) { // tiles -> the scalar view (D per elimination position, U = L D per CSC entry of L)
         const Symbolic &S = h->sym;
         const TilePlan &TP = h->tiles;
         std::vector<double> Dv((size_t)TP.N16), LR((size_t)TP.nt * 256 + 1);
-        HIP_TRY(hipMemcpy(Dv.data(), h->d_work + P.w_D, Dv.size() * sizeof(double), hipMemcpyDeviceToHost));
-        if (TP.nt) HIP_TRY(hipMemcpy(LR.data(), h->d_work + P.w_LR, (size_t)TP.nt * 256 * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(Dv.data(), h->work() + P.w_D, Dv.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (TP.nt) HIP_TRY(hipMemcpy(LR.data(), h->work() + P.w_LR, (size_t)TP.nt * 256 * sizeof(double), hipMemcpyDeviceToHost));
         if (Dout) for (int j = 0; j < S.N; j++) Dout[j] = Dv[TP.slot[j]];
         if (Uout) {
             // the diagonal tiles themselves (strictly lower part, row-major) as the factorisation's triangular solves read them
             std::vector<double> Ld((size_t)TP.nb * 256, 0.0);
-            HIP_TRY(hipMemcpy(Ld.data(), h->d_work + P.w_DL, Ld.size() * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(Ld.data(), h->work() + P.w_DL, Ld.size() * sizeof(double), hipMemcpyDeviceToHost));
             std::vector<int> colj(S.nnzL);
             for (int j = 0; j < S.N; j++) for (int e = S.Lp[j]; e < S.Lp[j + 1]; e++) colj[e] = j;
             std::vector<double> ub;
             if (S.tile == 2) { // hybrid: the columns below the top block are in the scalar backward slots
                 ub.resize((size_t)P.nUB + 1);
-                HIP_TRY(hipMemcpy(ub.data(), h->d_work + P.w_UB, (size_t)P.nUB * sizeof(double), hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(ub.data(), h->work() + P.w_UB, (size_t)P.nUB * sizeof(double), hipMemcpyDeviceToHost));
             }
             for (int e = 0; e < S.nnzL; e++) {
                 if (S.tile == 2 && colj[e] < S.n0) { Uout[e] = ub[h->posB[e]]; continue; }
@@ -2501,10 +2484,10 @@ int eicos_debug_factor(eicos_batch *h, int inst, double *Dout, double *Uout) {
         }
         return EICOS_OK;
     }
-    if (Dout) HIP_TRY(hipMemcpy(Dout, h->d_work + h->dp.w_D, (size_t)h->sym.N * sizeof(double), hipMemcpyDeviceToHost));
+    if (Dout) HIP_TRY(hipMemcpy(Dout, h->work() + h->dp.w_D, (size_t)h->sym.N * sizeof(double), hipMemcpyDeviceToHost));
     if (Uout) {
         std::vector<double> ub((size_t)h->ub_len + 1);
-        HIP_TRY(hipMemcpy(ub.data(), h->d_work + h->dp.w_UB, (size_t)h->ub_len * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ub.data(), h->work() + h->dp.w_UB, (size_t)h->ub_len * sizeof(double), hipMemcpyDeviceToHost));
         for (int e = 0; e < h->dp.nnzL; e++) Uout[e] = ub[h->posB[e]];
     }
     return EICOS_OK;
@@ -2520,7 +2503,7 @@ int eicos_debug_kkt(eicos_batch *h, int inst, int *rows, int *cols, double *vals
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipStreamSynchronize(h->stream));
         std::vector<double> slab(D.inst_stride);
-        HIP_TRY(hipMemcpy(slab.data(), h->d_inst + (size_t)inst * D.inst_stride, D.inst_stride * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(slab.data(), h->inst() + (size_t)inst * D.inst_stride, D.inst_stride * sizeof(double), hipMemcpyDeviceToHost));
         for (int e = 0; e < S.nnzK; e++) {
             int off;
             switch (S.K_kind[e]) { // same sources as the factor's value stream (srcoff in eicos_batch_create)
@@ -2542,16 +2525,16 @@ int eicos_debug_scalings(eicos_batch *h, int inst, const double *s, const double
     const DevPat &D = h->dp;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (!h->d_flag) HIP_TRY(hipMalloc(&h->d_flag, 16 * sizeof(int)));
-    double *I = h->d_inst + (size_t)inst * D.inst_stride;
+    if (!h->d_flag) HIP_TRY_AS("hipMalloc", h->d_flag.alloc(16 * sizeof(int)));
+    double *I = h->inst() + (size_t)inst * D.inst_stride;
     if (D.m > 0) {
         HIP_TRY(hipMemcpy(I + D.i_s, s, (size_t)D.m * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(I + D.i_z, z, (size_t)D.m * sizeof(double), hipMemcpyHostToDevice));
     }
-    HIP_TRY(launch_debug_scalings(h->pslot, h->d_inst, h->d_work, inst, h->d_flag, h->threads, h->stream));
+    HIP_TRY(launch_debug_scalings(h->pslot, h->inst(), h->work(), inst, h->d_flag.as<int>(), h->threads, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     int ok = 0;
-    HIP_TRY(hipMemcpy(&ok, h->d_flag, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&ok, h->d_flag.p, sizeof(int), hipMemcpyDeviceToHost));
     if (ran) *ran = ok;
     if (V && D.nV > 0) HIP_TRY(hipMemcpy(V, I + D.i_Vv, (size_t)D.nV * sizeof(double), hipMemcpyDeviceToHost));
     return EICOS_OK;
@@ -2568,11 +2551,11 @@ int eicos_debug_trace(eicos_batch *h, int inst, double *out) {
     int slot = inst;
     if (h->last_ordered) { // the launch took the instances through the order array: slot q holds instance order[q], q < launched
         std::vector<int> ord(launched);
-        HIP_TRY(hipMemcpy(ord.data(), h->d_queue + 16, (size_t)launched * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ord.data(), h->queue() + 16, (size_t)launched * sizeof(int), hipMemcpyDeviceToHost));
         slot = (int)(std::find(ord.begin(), ord.end(), inst) - ord.begin());
         if (slot >= launched) return fail(EICOS_E_INVALID, h->last_subset ? "instance not in the last launch" : "instance not found in the launch order");
     }
-    HIP_TRY(hipMemcpy(out, h->d_work + (size_t)slot * h->dp.work_stride + h->dp.w_trace,
+    HIP_TRY(hipMemcpy(out, h->work() + (size_t)slot * h->dp.work_stride + h->dp.w_trace,
                       (size_t)TRACE_ROWS * TRACE_COLS * sizeof(double), hipMemcpyDeviceToHost));
     return EICOS_OK;
 }
