@@ -193,6 +193,22 @@ def _lib():
             L.eicos_batch_gather.argtypes = L.eicos_multi_gather.argtypes = [vp, ip, C.c_int, dp, dp, dp, dp, C.POINTER(Info)]
             for f in ("select", "solve_subset_async", "solve_subset", "solve_where", "gather"):
                 getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+        if hasattr(L, "eicos_batch_update_param_solve_subset"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            L.eicos_batch_update_indexed.argtypes = L.eicos_multi_update_indexed.argtypes = [vp, ip, C.c_int, dp, dp, dp, dp, dp]
+            L.eicos_batch_update_rhs_indexed.argtypes = L.eicos_multi_update_rhs_indexed.argtypes = [vp, ip, C.c_int, dp, dp, dp]
+            L.eicos_batch_update_param_indexed.argtypes = L.eicos_multi_update_param_indexed.argtypes = [vp, ip, C.c_int, dp]
+            L.eicos_batch_set_iterate_indexed.argtypes = L.eicos_multi_set_iterate_indexed.argtypes = [vp, ip, C.c_int, dp, dp, dp, dp]
+            L.eicos_batch_outputs_indexed.argtypes = L.eicos_multi_outputs_indexed.argtypes = [vp, ip, C.c_int, dp]
+            L.eicos_batch_update_param_solve_subset.argtypes = L.eicos_multi_update_param_solve_subset.argtypes = [vp, ip, C.c_int, dp, dp, dp, ip]
+            L.eicos_batch_update_indexed_device.argtypes = [vp, ip, C.c_int, vp, vp, vp, vp, vp]
+            L.eicos_batch_update_rhs_indexed_device.argtypes = [vp, ip, C.c_int, vp, vp, vp]
+            L.eicos_batch_update_param_indexed_device.argtypes = [vp, ip, C.c_int, vp]
+            L.eicos_batch_set_iterate_indexed_device.argtypes = [vp, ip, C.c_int, vp, vp, vp, vp]
+            L.eicos_batch_outputs_indexed_device.argtypes = [vp, ip, C.c_int, vp]
+            for f in ("update_indexed", "update_rhs_indexed", "update_param_indexed", "set_iterate_indexed", "outputs_indexed", "update_param_solve_subset"):
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+            for f in ("update_indexed", "update_rhs_indexed", "update_param_indexed", "set_iterate_indexed", "outputs_indexed"):
+                getattr(L, "eicos_batch_" + f + "_device").restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -560,6 +576,27 @@ def _theta_rows(theta, k, count):
     return theta, theta.shape[0]
 
 
+def _index_rows(indices):
+    """The index list of an indexed call: a contiguous int32 vector and its pointer (a 1-element dummy keeps the pointer valid).  Anything
+    that is not a one-dimensional list of integers is a TypeError / ValueError here; range and duplicates are the library's to check."""
+    idx = np.asarray(indices)
+    if idx.size and not np.issubdtype(idx.dtype, np.integer):
+        raise TypeError(f"indices must be integers, not {idx.dtype}")
+    if idx.ndim > 1:
+        raise ValueError(f"indices must be one-dimensional, not of shape {idx.shape}")
+    idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+    return idx, (_ip(idx) if idx.size else _ip(np.zeros(1, np.int32)))
+
+
+def _indexed_groups(names, groups, widths, count):
+    """The row arrays of an indexed call as (keep-alive arrays, C pointers): every given array is [count, width] with count =
+    len(indices); ValueError otherwise.  None keeps a group."""
+    for name, a, w in zip(names, groups, widths):
+        if a is not None and np.shape(a) != (count, w):
+            raise ValueError(f"{name} has shape {np.shape(a)}, expected [{count}, {w}] (one row per index)")
+    return _group_ptrs(groups, widths, count)
+
+
 def _rows(groups, default):
     """The instance count of an update: the leading dimension of the first two-dimensional array given."""
     return next((np.shape(a)[0] for a in groups if a is not None and np.ndim(a) == 2), default)
@@ -812,6 +849,68 @@ class _Solver:
         raw = np.frombuffer(arr, dtype=np.dtype([(f, "f8" if t is C.c_double else "i4") for f, t in Info._fields_]))[:k]
         return {"x": x, "y": y, "z": z, "s": s, "info": {f: raw[f].copy() for f in raw.dtype.names}}
 
+    # ---- update, read and step a chosen subset (include/eicos_amd.h: eicos_batch_update_indexed ... _update_param_solve_subset) ----
+    def update_indexed(self, indices, Gpr=None, Apr=None, c=None, h=None, b=None):
+        """update() for the instances `indices` (each at most once): row q of every array [len(indices), ...] belongs to instance
+        indices[q]; None keeps the group.  Bit for bit the loop of update(first=indices[q], count=1) calls."""
+        idx, ptr = _index_rows(indices)
+        _keep, rows = _indexed_groups(("Gpr", "Apr", "c", "h", "b"), (Gpr, Apr, c, h, b), self._widths(), int(idx.size))
+        self._call("update_indexed", ptr, int(idx.size), *rows)
+
+    def update_rhs_indexed(self, indices, c=None, h=None, b=None):
+        """update_rhs() for the instances `indices`, rows in list order."""
+        idx, ptr = _index_rows(indices)
+        pat = self.pat
+        _keep, rows = _indexed_groups("chb", (c, h, b), (pat.n, pat.m, pat.p), int(idx.size))
+        self._call("update_rhs_indexed", ptr, int(idx.size), *rows)
+
+    def update_param_indexed(self, indices, theta):
+        """update_param() for the instances `indices`: theta [len(indices), k], row q for instance indices[q]."""
+        idx, ptr = _index_rows(indices)
+        theta = self._theta_for(theta, int(idx.size))
+        self._call("update_param_indexed", ptr, int(idx.size), _dp(theta) if theta.size else _dp(np.zeros(1)))
+
+    def set_iterate_indexed(self, indices, x=None, y=None, z=None, s=None):
+        """set_iterate() for the instances `indices`, rows in list order."""
+        idx, ptr = _index_rows(indices)
+        pat = self.pat
+        _keep, rows = _indexed_groups("xyzs", (x, y, z, s), (pat.n, pat.p, pat.m, pat.m), int(idx.size))
+        self._call("set_iterate_indexed", ptr, int(idx.size), *rows)
+
+    def outputs_indexed(self, indices):
+        """u [len(indices), r]: row q = the output map on the current x of instance indices[q] -- row indices[q] of outputs()."""
+        idx, ptr = _index_rows(indices)
+        u = np.zeros((int(idx.size), self.output_count()))
+        self._call("outputs_indexed", ptr, int(idx.size), _dp(u) if u.size else _dp(np.zeros(1)))
+        return u
+
+    def update_param_solve_subset(self, indices, theta, u_out=None, x_out=None):
+        """The closed-loop step over the instances `indices` in one call: update_param_indexed + solve_subset + outputs_indexed, theta
+        [len(indices), k], u_out [len(indices), r] and x_out [len(indices), n] in list order -- with pinned / registered theta ONE subset
+        launch whose workgroups expand their own theta row and write their rows into pinned result arrays.  Every other instance keeps
+        its state.  Returns the exit codes in list order; an empty list launches nothing."""
+        idx, ptr = _index_rows(indices)
+        count = int(idx.size)
+        theta = self._theta_for(theta, count)
+        _result_rows(u_out, count, self.output_count(), "u_out")
+        _result_rows(x_out, count, self.pat.n, "x_out")
+        codes = np.zeros(count, np.int32)
+        self._call("update_param_solve_subset", ptr, count, _dp(theta) if theta.size else _dp(np.zeros(1)),
+                   _dp(u_out) if (u_out is not None and u_out.size) else None, _dp(x_out) if (x_out is not None and x_out.size) else None,
+                   _ip(codes) if count else None)
+        return codes
+
+    def _theta_for(self, theta, count):
+        """theta rows of an indexed call: [count, k] when a parameter map is installed (ValueError otherwise); without one the library
+        refuses ("no parameter map"), so only the leading dimension is checked."""
+        k = self.param_count()
+        if k > 0:
+            return _theta_rows(theta, k, count)[0]
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim == 2 and theta.shape[0] != count:
+            raise ValueError(f"theta has {theta.shape[0]} rows, expected {count} (one row per index)")
+        return theta
+
     def set_warm_start(self, shift: float):
         """shift > 0: re-solves start from the previous solution (not in the reference; see include/eicos_amd.h)."""
         self._call("set_warm_start", float(shift))
@@ -917,6 +1016,28 @@ class BatchSolver(_Solver):
         """outputs() into a raw device pointer (int) to u [count, r].  Asynchronous on the handle's stream."""
         count = self.batch - first if count is None else count
         self._call("outputs_device", first, count, C.c_void_p(int(du) or None))
+
+    # ---- the indexed calls from raw device pointers (ints); `indices` stays a host list.  Asynchronous on the handle's stream ----
+    def update_indexed_device(self, indices, dG=0, dA=0, dc=0, dh=0, db=0):
+        idx, ptr = _index_rows(indices)
+        self._call("update_indexed_device", ptr, int(idx.size), *[C.c_void_p(int(p) or None) for p in (dG, dA, dc, dh, db)])
+
+    def update_rhs_indexed_device(self, indices, dc=0, dh=0, db=0):
+        idx, ptr = _index_rows(indices)
+        self._call("update_rhs_indexed_device", ptr, int(idx.size), *[C.c_void_p(int(p) or None) for p in (dc, dh, db)])
+
+    def update_param_indexed_device(self, indices, dtheta):
+        idx, ptr = _index_rows(indices)
+        self._call("update_param_indexed_device", ptr, int(idx.size), C.c_void_p(int(dtheta) or None))
+
+    def set_iterate_indexed_device(self, indices, dx=0, dy=0, dz=0, ds=0):
+        idx, ptr = _index_rows(indices)
+        self._call("set_iterate_indexed_device", ptr, int(idx.size), *[C.c_void_p(int(p) or None) for p in (dx, dy, dz, ds)])
+
+    def outputs_indexed_device(self, indices, du):
+        """outputs_indexed() into a raw device pointer (int) to u [len(indices), r]."""
+        idx, ptr = _index_rows(indices)
+        self._call("outputs_indexed_device", ptr, int(idx.size), C.c_void_p(int(du) or None))
 
     def set_stream(self, stream_ptr: int):
         self._call("set_stream", C.c_void_p(int(stream_ptr) or None))

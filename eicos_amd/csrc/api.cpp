@@ -119,7 +119,7 @@ struct eicos_batch {
     int ldsres = 0;           // 1: solves run the LDS-resident kernel (ldsres::solve_entries), slabs copied in and out per instance
     size_t pattern_ints = 0;
     DevBuf d_inst, d_work, d_scratch; // the instance slabs, the workspace slabs of the resident workgroups, the updateData scratch
-    DevBuf d_queue; // instance queue of the solve kernel (reset per launch): [16-int header | launch order [batch] | candidates of a subset launch [batch]]
+    DevBuf d_queue; // instance queue of the solve kernel (reset per launch): [16-int header | launch order [batch] | candidates of a subset launch [batch] | row map of a step over a subset [batch]]
     // (what the enqueue path reads of them: a member load each)
     double *inst() const { return d_inst.as<double>(); }
     double *work() const { return d_work.as<double>(); }
@@ -128,6 +128,9 @@ struct eicos_batch {
     // into d_gather = [ids | rows]
     PinSlot sub;
     DevBuf d_gather;
+    // index-list updates and outputs (eicos_batch_*_indexed): their validated ids in device memory, `batch` ints of their own -- the
+    // candidates behind the launch order belong to the subset launches, and one that is queued still reads them
+    DevBuf d_upd_ids;
     DevBuf d_stage; // peer-copy updateData without peer access: staging buffer (one chunk)
     // host-pointer updateData / results (the reference's real signature: updateData(double *...), solution() on the host): two PINNED
     // bounce buffers (hipHostMalloc).  Input chunk k is copied into pin[k & 1] by the host while the GPU's updateData kernel reads chunk
@@ -1018,7 +1021,7 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
         HIP_TRY(hipMemset(h->d_inst.p, 0, h->d_inst.bytes));
         HIP_TRY_AS("hipMalloc", h->d_work.alloc((size_t)h->grid * D.work_stride * sizeof(double)));
         HIP_TRY(hipMemset(h->d_work.p, 0, h->d_work.bytes));
-        HIP_TRY_AS("hipMalloc", h->d_queue.alloc((16 + 2 * (size_t)batch) * sizeof(int))); // [0] queue head, [1] the count of a selection, [16..] launch order, [16 + batch..] candidates
+        HIP_TRY_AS("hipMalloc", h->d_queue.alloc((16 + 3 * (size_t)batch) * sizeof(int))); // [0] queue head, [1] the count of a selection, [16..] launch order, [16 + batch..] candidates, [16 + 2 batch..] row map
         HIP_TRY_AS("hipMalloc", h->d_shared.alloc(64));
         HIP_TRY(hipMemset(h->d_shared.p, 0xFF, 64)); // (-1: nothing shared)
         HIP_TRY_AS("hipMalloc", h->d_scratch.alloc((size_t)h->upd_grid * (size_t)(S.n + S.p + S.m + 8) * sizeof(double)));
@@ -1409,6 +1412,8 @@ struct UpdateInputs {
     MemKind kind[5];      // of the arrays that hold data, when the entry point asked for kinds
     size_t per;           // doubles per instance over the given groups
     bool iterate = false; // a starting point (take_iterate): the groups are x, y, z, s in the slots of G, A, c, h
+    const int *ids = nullptr; // the index-list forms (eicos_batch_*_indexed): `count` ids in device memory -- row q of the arrays belongs to
+                              // instance ids[q], first = 0 counts positions of the list; NULL: the range [first, first + count)
     bool detect = false;  // eicos_batch_update_device: arrays in the GPU's own memory, where reading row 0 once more per instance is an L2 hit (pinned host
                           // rows and another GPU's would cross the link twice) -- its launch may set the shared-values word
     bool holds_data(int k) const { return src[k] && w[k]; }
@@ -1493,12 +1498,13 @@ static int shared_detect(eicos_batch *h) {
 }
 
 static constexpr int MSTAGE_CAP_MB = 64; // (EICOS_MATRIX_STAGE_MB under EICOS_EXPERIMENT=1: tests reach several chunks with a small batch)
-static int param_range(eicos_batch *h, int first, int count, const double *theta) {
+// list != NULL (UpdateInputs::ids + the position the rows start at): row q belongs to instance list[q] and `first` is unused.
+static int param_range(eicos_batch *h, int first, int count, const double *theta, const int *list) {
     const DevPat &D = h->dp;
     const ParamMapDev &M = h->param;
     if (h->mat.k == 0) {
         const int width = (M.g[0].base ? D.n : 0) + (M.g[1].base ? D.m : 0) + (M.g[2].base ? D.p : 0);
-        HIP_TRY(launch_update_param(h->pslot, h->inst(), first, count, M, theta, width, h->stream));
+        HIP_TRY(launch_update_param(h->pslot, h->inst(), first, count, M, theta, width, h->stream, list));
         return EICOS_OK;
     }
     if (count == 0) return EICOS_OK;
@@ -1523,14 +1529,14 @@ static int param_range(eicos_batch *h, int first, int count, const double *theta
             at += ((size_t)cnt * w[g] + 7) / 8 * 8;
         }
         HIP_TRY(launch_update(h->pslot, h->inst(), first + o, cnt, arr[0], arr[1], arr[2], arr[3], arr[4], h->d_scratch.as<double>(), std::min(cnt, h->upd_grid),
-                              h->upd_lds, h->upd_vals_lds, h->stream));
+                              h->upd_lds, h->upd_vals_lds, h->stream, nullptr, list ? list + o : nullptr));
     }
     ParamMapDev rest{};
     rest.k = M.k;
     if (!mG) rest.g[1] = M.g[1];
     if (!mA) rest.g[2] = M.g[2];
     const int width = (rest.g[1].base ? D.m : 0) + (rest.g[2].base ? D.p : 0);
-    HIP_TRY(launch_update_param(h->pslot, h->inst(), first, count, rest, theta, width, h->stream));
+    HIP_TRY(launch_update_param(h->pslot, h->inst(), first, count, rest, theta, width, h->stream, list));
     return EICOS_OK;
 }
 
@@ -1538,19 +1544,20 @@ static int param_range(eicos_batch *h, int first, int count, const double *theta
 // pattern has among them it is the launch that compares every row of Gpr / Apr with row 0 (launch.hpp: launch_update)
 static int launch_range(const UpdateInputs &in, int first, int count, const double *const p[5], bool in_place = false) {
     eicos_batch *h = in.h;
-    if (in.iterate) HIP_TRY(launch_set_iterate(h->pslot, h->inst(), first, count, p[0], p[1], p[2], p[3], (int)in.per, h->stream));
+    const int *list = in.ids ? in.ids + first : nullptr; // (an index list: `first` is the position in it the rows start at)
+    if (in.iterate) HIP_TRY(launch_set_iterate(h->pslot, h->inst(), first, count, p[0], p[1], p[2], p[3], (int)in.per, h->stream, list));
     else if (in.param) {
-        const int rc = param_range(h, first, count, p[2]);
+        const int rc = param_range(h, first, count, p[2], list);
         if (rc != EICOS_OK) return rc;
-    } else if (in.rhs) HIP_TRY(launch_update_rhs(h->pslot, h->inst(), first, count, p[2], p[3], p[4], (int)in.per, h->stream));
+    } else if (in.rhs) HIP_TRY(launch_update_rhs(h->pslot, h->inst(), first, count, p[2], p[3], p[4], (int)in.per, h->stream, list));
     else {
         const DevPat &D = h->dp;
-        const bool detect = in_place && in.detect && h->shared_on && first == 0 && count == h->batch && D.nnzG + D.nnzA > 0 &&
+        const bool detect = in_place && in.detect && !list && h->shared_on && first == 0 && count == h->batch && D.nnzG + D.nnzA > 0 &&
                             (p[0] || D.nnzG == 0) && (p[1] || D.nnzA == 0);
         const int rc = detect ? shared_detect(h) : (count > 0 ? shared_clear(h) : EICOS_OK);
         if (rc != EICOS_OK) return rc;
         HIP_TRY(launch_update(h->pslot, h->inst(), first, count, p[0], p[1], p[2], p[3], p[4], h->d_scratch.as<double>(), std::min(count, h->upd_grid), h->upd_lds, h->upd_vals_lds, h->stream,
-                              detect ? h->d_shared.as<int>() : nullptr));
+                              detect ? h->d_shared.as<int>() : nullptr, list));
         // (the one launch that may leave the word at 0: the shared factor operands follow it on the stream, from instance 0's fresh values)
         if (detect && h->d_shop) HIP_TRY(launch_shared_operands(h->pslot, h->inst(), h->d_shop.as<double>(), const_cast<double *>(D.ub0), h->stream));
     }
@@ -1809,11 +1816,12 @@ static int take_output_range(eicos_batch *h, int first, int count, const double 
 
 // the output rows of instances [first, first + count) into `u` [count][r], wherever it lives: device memory is written by the range kernel
 // itself (asynchronous), host memory gets the handle's rows d_u over the paths of fetch_strided (synchronous)
-static int outputs_to(eicos_batch *h, int first, int count, double *u, MemKind kind) {
+// list != NULL (device memory, `count` ids): row q is the output row of instance list[q] and `first` is unused
+static int outputs_to(eicos_batch *h, int first, int count, double *u, MemKind kind, const int *list = nullptr) {
     if (count == 0) return EICOS_OK;
-    if (kind == MEM_DEVICE) { HIP_TRY(launch_outputs(h->pslot, h->inst(), first, count, h->out, u, h->stream)); return EICOS_OK; }
-    double *rows = h->d_u + (size_t)first * h->out.r;
-    HIP_TRY(launch_outputs(h->pslot, h->inst(), first, count, h->out, rows, h->stream));
+    if (kind == MEM_DEVICE) { HIP_TRY(launch_outputs(h->pslot, h->inst(), first, count, h->out, u, h->stream, list)); return EICOS_OK; }
+    double *rows = h->d_u + (list ? 0 : (size_t)first * h->out.r);
+    HIP_TRY(launch_outputs(h->pslot, h->inst(), first, count, h->out, rows, h->stream, list));
     const int rc = fetch_strided(h, u, rows, (size_t)h->out.r * sizeof(double), h->out.r, count);
     if (rc != EICOS_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1835,6 +1843,8 @@ int eicos_batch_outputs_device(eicos_batch *h, int first, int count, double *du)
 
 // the candidate ids of a subset launch, in device memory behind the launch order
 static int *subset_ids(const eicos_batch *h) { return h->queue() + 16 + h->batch; }
+// the row map of a step over a subset (launch.hpp: UpdArgs::rows_at), behind the candidates: its place in the queue allocation, in ints
+static int subset_rows_at(const eicos_batch *h) { return 16 + 2 * h->batch; }
 // the launch record of a handle's solves (launch.hpp); subset >= 0: a launch over the `subset` ids in subset_ids(h) instead of the batch
 static SolveLaunch solve_launch(const eicos_batch *h, int subset) {
     SolveLaunch L{};
@@ -1857,7 +1867,9 @@ static int enqueue_solve(eicos_batch *h, const UpdArgs *step, int subset = -1) {
     args.smap = h->d_shift.as<const ShiftMapDev>();
     if (writes_matrix_values(args)) { const int rc = shared_clear(h); if (rc != EICOS_OK) return rc; } // (the step drops the shared values)
     args.shared = h->shared_on ? h->d_shared.as<int>() : nullptr;
-    HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(solve_launch(h, subset), h->stream, args));
+    SolveLaunch L = solve_launch(h, subset);
+    if (args.rows_at) L.rows = h->queue() + args.rows_at; // (a step in list order: the selection kernel of this launch fills the row map it reads)
+    HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(L, h->stream, args));
     HIP_TRY(hipEventRecord(h->ev_s1, h->stream));
     h->solve_timed = true;
     h->last_subset = subset >= 0; h->last_count = subset >= 0 ? subset : h->batch;
@@ -2219,6 +2231,150 @@ int eicos_batch_update_param_solve(eicos_batch *h, const double *theta, double *
     return update_solve(h, nullptr, nullptr, nullptr, nullptr, nullptr, theta, u_out, x_out, exitcodes, STEP_PARAM);
 }
 
+// ---- index-list forms: update, read and step a chosen subset (include/eicos_amd.h) ----
+// An indexed update is its range namesake with one more field in the descriptor (UpdateInputs::ids): the list is checked like a subset
+// solve's (take_index_list: a refused list changes no state), the arrays by the namesake's own take_* over `count` rows, the ids go to
+// device memory through the pinned list buffer (upload_ids, into d_upd_ids) and the rows travel over the namesake's paths.
+// An empty list: EICOS_OK, nothing enqueued, nothing recorded.
+static int ids_to_device(UpdateInputs &in, const int *idx) {
+    eicos_batch *h = in.h;
+    HIP_TRY_AS("hipMalloc", h->d_upd_ids.reserve((size_t)h->batch * sizeof(int), h->stream)); // (once: every list fits)
+    const int rc = upload_ids(h, idx, in.count, h->d_upd_ids.as<int>());
+    in.ids = h->d_upd_ids.as<const int>();
+    return rc;
+}
+// host: the arrays are host memory (pageable: bounce pipeline; pinned: in place, synchronous); else device memory, one asynchronous launch
+static int indexed_update(UpdateInputs &in, const int *idx, bool host) {
+    const int rc = ids_to_device(in, idx);
+    if (rc != EICOS_OK) return rc;
+    return host ? staged_update(in, -1) : update_in_place(in, 0);
+}
+static int update_indexed(eicos_batch *h, const int *idx, int count, const double *G, const double *A, const double *c, const double *hh,
+                          const double *b, bool rhs, bool host, const char *who) {
+    int rc = take_index_list(h, idx, count, who);
+    if (rc != EICOS_OK || count == 0) return rc;
+    UpdateInputs in;
+    rc = take_inputs(in, h, 0, count, G, A, c, hh, b, rhs, host);
+    return rc != EICOS_OK ? rc : indexed_update(in, idx, host);
+}
+static int update_param_indexed(eicos_batch *h, const int *idx, int count, const double *theta, bool host, const char *who) {
+    int rc = take_index_list(h, idx, count, who);
+    if (rc != EICOS_OK || count == 0) return rc;
+    UpdateInputs in;
+    rc = take_theta(in, h, 0, count, theta, host);
+    return rc != EICOS_OK ? rc : indexed_update(in, idx, host);
+}
+static int set_iterate_indexed(eicos_batch *h, const int *idx, int count, const double *x, const double *y, const double *z, const double *s,
+                               bool host, const char *who) {
+    int rc = take_index_list(h, idx, count, who);
+    if (rc != EICOS_OK || count == 0) return rc;
+    UpdateInputs in;
+    rc = take_iterate(in, h, 0, count, x, y, z, s, host);
+    return rc != EICOS_OK ? rc : indexed_update(in, idx, host);
+}
+
+int eicos_batch_update_indexed(eicos_batch *h, const int *idx, int count, const double *G, const double *A, const double *c, const double *hh,
+                               const double *b) {
+    return update_indexed(h, idx, count, G, A, c, hh, b, false, true, "eicos_batch_update_indexed");
+}
+int eicos_batch_update_indexed_device(eicos_batch *h, const int *idx, int count, const double *dG, const double *dA, const double *dc,
+                                      const double *dh, const double *db) {
+    return update_indexed(h, idx, count, dG, dA, dc, dh, db, false, false, "eicos_batch_update_indexed_device");
+}
+int eicos_batch_update_rhs_indexed(eicos_batch *h, const int *idx, int count, const double *c, const double *hh, const double *b) {
+    return update_indexed(h, idx, count, nullptr, nullptr, c, hh, b, true, true, "eicos_batch_update_rhs_indexed");
+}
+int eicos_batch_update_rhs_indexed_device(eicos_batch *h, const int *idx, int count, const double *dc, const double *dh, const double *db) {
+    return update_indexed(h, idx, count, nullptr, nullptr, dc, dh, db, true, false, "eicos_batch_update_rhs_indexed_device");
+}
+int eicos_batch_update_param_indexed(eicos_batch *h, const int *idx, int count, const double *theta) {
+    return update_param_indexed(h, idx, count, theta, true, "eicos_batch_update_param_indexed");
+}
+int eicos_batch_update_param_indexed_device(eicos_batch *h, const int *idx, int count, const double *dtheta) {
+    return update_param_indexed(h, idx, count, dtheta, false, "eicos_batch_update_param_indexed_device");
+}
+int eicos_batch_set_iterate_indexed(eicos_batch *h, const int *idx, int count, const double *x, const double *y, const double *z, const double *s) {
+    return set_iterate_indexed(h, idx, count, x, y, z, s, true, "eicos_batch_set_iterate_indexed");
+}
+int eicos_batch_set_iterate_indexed_device(eicos_batch *h, const int *idx, int count, const double *dx, const double *dy, const double *dz,
+                                           const double *ds) {
+    return set_iterate_indexed(h, idx, count, dx, dy, dz, ds, false, "eicos_batch_set_iterate_indexed_device");
+}
+
+// the output rows of the listed instances, row q = instance idx[q]: eicos_batch_outputs* with the range kernel reading the slab list[q]
+static int outputs_indexed(eicos_batch *h, const int *idx, int count, double *u, bool host, const char *who) {
+    int rc = take_index_list(h, idx, count, who);
+    if (rc != EICOS_OK || count == 0) return rc;
+    rc = take_output_range(h, 0, count, u);
+    if (rc != EICOS_OK) return rc;
+    if (host) {
+        if (memory_kind(u, 1) == MEM_DEVICE) return fail(EICOS_E_INVALID, std::string(who) + " takes a host pointer: u lives in device memory (use eicos_batch_outputs_indexed_device)");
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    HIP_TRY_AS("hipMalloc", h->d_upd_ids.reserve((size_t)h->batch * sizeof(int), h->stream));
+    rc = upload_ids(h, idx, count, h->d_upd_ids.as<int>());
+    return rc != EICOS_OK ? rc : outputs_to(h, 0, count, u, host ? MEM_PAGEABLE : MEM_DEVICE, h->d_upd_ids.as<const int>());
+}
+int eicos_batch_outputs_indexed(eicos_batch *h, const int *idx, int count, double *u) {
+    return outputs_indexed(h, idx, count, u, true, "eicos_batch_outputs_indexed");
+}
+int eicos_batch_outputs_indexed_device(eicos_batch *h, const int *idx, int count, double *du) {
+    return outputs_indexed(h, idx, count, du, false, "eicos_batch_outputs_indexed_device");
+}
+
+// The closed-loop step over a chosen subset: eicos_batch_update_param_indexed + eicos_batch_solve_subset + eicos_batch_outputs_indexed (+ the
+// x rows), every array in list order.  Fused under the conditions of eicos_batch_update_param_solve (update_solve, above: an LDS vector,
+// a theta row that fits, theta the GPU addresses, EICOS_FUSED_UPDATE not 0; witness 5): ONE subset launch whose selection kernel also
+// leaves the row map (launch.hpp: UpdArgs::rows_at), so that the workgroup that solves instance idx[q] expands row q of theta first and writes row q of
+// u_out / x_out (pinned or device memory) when it is done.  Otherwise the three calls run; rows the kernel did not write come through the
+// indexed output kernel and the row gather.  Same bits on either path.  Synchronous; u_out, x_out, exitcodes optional.
+int eicos_batch_update_param_solve_subset(eicos_batch *h, const int *idx, int count, const double *theta, double *u_out, double *x_out,
+                                          int *exitcodes) {
+    int rc = take_index_list(h, idx, count, "eicos_batch_update_param_solve_subset");
+    if (rc != EICOS_OK || count == 0) return rc; // (an empty subset: no launch, nothing recorded)
+    UpdateInputs in;
+    rc = take_theta(in, h, 0, count, theta, true);
+    if (rc != EICOS_OK) return rc;
+    if (u_out && h->out.r == 0) return fail(EICOS_E_INVALID, "no output map (eicos_batch_set_output_map installs one)");
+    const DevPat &D = h->dp;
+    if (D.n == 0) x_out = nullptr;
+    const MemKind x_kind = memory_kind(x_out, (size_t)count * D.n * sizeof(double));
+    const MemKind u_kind = memory_kind(u_out, (size_t)count * h->out.r * sizeof(double));
+    const bool fused = fused_param_fits(fit_shape(h), h->param.k, h->mat.k != 0) && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1) && !in.any(MEM_PAGEABLE);
+    bool x_written = false, u_written = false;
+    if (!fused) { // the update on its own, then the subset launch
+        rc = ids_to_device(in, idx);
+        if (rc == EICOS_OK) rc = in.all(MEM_DEVICE) ? update_in_place(in, 0) : staged_update(in, -1);
+        if (rc == EICOS_OK) rc = upload_ids(h, idx, count, subset_ids(h));
+        if (rc == EICOS_OK) rc = enqueue_solve(h, nullptr, count);
+    } else {
+        rc = upload_ids(h, idx, count, subset_ids(h));
+        if (rc == EICOS_OK) rc = fused_step_begins(h, 5);
+        if (rc != EICOS_OK) return rc;
+        x_written = x_out && x_kind != MEM_PAGEABLE; u_written = u_out && u_kind != MEM_PAGEABLE;
+        UpdArgs step;
+        step.on = UPD_PARAM; step.rows_at = subset_rows_at(h); step.theta = in.src[2];
+        step.x = x_written ? x_out : nullptr; step.u = u_written ? u_out : nullptr;
+        step.pmap = h->d_param.as<const ParamMapDev>(); step.omap = h->d_out.as<const OutMapDev>();
+        if (h->mat.k) step.mmap = h->d_mat.as<const MatrixMapDev>();
+        rc = enqueue_solve(h, &step, count);
+    }
+    if (rc == EICOS_OK) rc = eicos_batch_sync(h);
+    if (rc != EICOS_OK) return rc;
+    // ---- the rows the kernel did not write, and the exit codes (deliver_results for a subset)
+    if (u_out && !u_written) {
+        rc = outputs_to(h, 0, count, u_out, u_kind, subset_ids(h));
+        if (rc != EICOS_OK) return rc;
+        if (u_kind == MEM_DEVICE) HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    if (x_out && !x_written && x_kind == MEM_DEVICE) { // the gather kernel straight into the caller's device rows
+        HIP_TRY(launch_gather_rows(h->pslot, h->inst(), subset_ids(h), count, GATHER_X, x_out, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        x_written = true;
+    }
+    return gather_rows(h, subset_ids(h), count, x_written ? nullptr : x_out, nullptr, nullptr, nullptr, nullptr, exitcodes);
+}
+
 // ---- plant map and rollout: theta+ = f0 + F [theta | u] (+ w), and `steps` closed-loop steps in one call ----
 // The map reaches the kernels inside the rollout's record (RolloutDev), by value in the range kernel and through a pointer in the fused
 // launch; k, r = the parameter and output counts installed NOW, which it is validated for.
@@ -2338,7 +2494,7 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
             const double *cur = d_cur + (size_t)(t & 1) * B * k;
             double *next = d_cur + (size_t)((t + 1) & 1) * B * k;
             rc = begin_update_timing(h);
-            if (rc == EICOS_OK) rc = param_range(h, 0, h->batch, cur);
+            if (rc == EICOS_OK) rc = param_range(h, 0, h->batch, cur, nullptr);
             rc = end_update_timing(h, rc);
             if (rc == EICOS_OK) rc = enqueue_solve(h, nullptr);
             if (rc != EICOS_OK) return rc;

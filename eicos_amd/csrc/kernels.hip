@@ -167,6 +167,9 @@ struct alignas(16) Sh : ShI {
     // that every instance of the batch holds the same bits there -- the reference instance's, which then stays in L2 for all of them
     const double *vals;
     int vshared; // 1: `vals` is the reference instance's slab, read by every instance -> the stages' PLAIN instantiations (solve_instance)
+    // a parametric step over a chosen subset (UpdArgs::rows_at, set by k_solve once): the row map starts at queue[rows_at]; 0: row = instance.
+    // Kept here (in what was padding) and read by list_row, so that k_solve's loop is the same code with and without a list.
+    int rows_at;
 };
 constexpr int KI_MAX = 2; // right-hand sides of a dual solve (kkt_solve<..., 2, true>)
 enum { TK_FACTOR = 0, TK_LDL, TK_KRES, TK_KPOST, TK_RESID, TK_FWD, TK_COUNT, TK_FA = 8, TK_FW1, TK_FB, TK_FW2 }; // 8..11: inside the factor
@@ -3363,9 +3366,16 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void rhs_instanc
 // pinned host theta the only PCIe reads of the step --, then threads run over the entries of the mapped groups [c | h | b], each
 // accumulating its CSR row in stored order (product and sum rounded on their own) from the LDS copy and ending with rhs_entry's division
 // by the stored scaling.  The map (device memory, *Mp) is the same for every instance: served from L2.  k <= Npad (api.cpp).
+// list_row: the row of the caller's theta / x / u arrays that belongs to the instance k_solve passes as `q` -- q itself, or, in a step
+// over a chosen subset (launch.hpp: UpdArgs::rows_at), its position in the caller's list from the row map in the queue allocation.
+// Uniform over the workgroup; the map is `batch` ints, L2-resident.  (A rollout passes q = 0 with its own row pointer and never has a map.)
+__device__ __forceinline__ size_t list_row(size_t q) {
+    const int at = uni(g_S.rows_at);
+    return at ? (size_t)uni(g_S.queue[at + (int)q]) : q;
+}
 template <int T>
 static __device__ __noinline__ __attribute__((not_tail_called)) void param_instance(int ps, hbm_p I, size_t q, const ParamMapDev *Mp, const double *theta) {
-    ps = uni(ps); I = uni_ptr(I); Mp = uni_ptr(Mp); theta = uni_ptr(theta);
+    ps = uni(ps); I = uni_ptr(I); Mp = uni_ptr(Mp); theta = uni_ptr(theta); q = list_row(q);
     const DevPat &P = c_pat[ps];
     const int k = Mp->k;
     const AffineDev gc = Mp->g[0], gh = Mp->g[1], gb = Mp->g[2];
@@ -3394,7 +3404,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void param_insta
 template <int T>
 static __device__ __noinline__ __attribute__((not_tail_called)) void matrix_param_instance(int ps, hbm_p I, size_t q, const ParamMapDev *Mp, const MatrixMapDev *Xp,
                                                                                             const double *theta) {
-    ps = uni(ps); I = uni_ptr(I); Mp = uni_ptr(Mp); Xp = uni_ptr(Xp); theta = uni_ptr(theta);
+    ps = uni(ps); I = uni_ptr(I); Mp = uni_ptr(Mp); Xp = uni_ptr(Xp); theta = uni_ptr(theta); q = list_row(q);
     const DevPat &P = c_pat[ps];
     const int k = Mp->k;
     const AffineDev gG = Xp->g[0], gA = Xp->g[1], gc = Mp->g[0], gh = Mp->g[1], gb = Mp->g[2];
@@ -3418,7 +3428,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void matrix_para
 // outputs_instance: the row's per-thread address is not carried through the solve.
 template <int T>
 static __device__ __noinline__ __attribute__((not_tail_called)) void solution_instance(int ps, gcdbl_p I, size_t q, double *x) {
-    ps = uni(ps); I = uni_ptr(I); x = uni_ptr(x);
+    ps = uni(ps); I = uni_ptr(I); x = uni_ptr(x); q = list_row(q);
     const DevPat &P = c_pat[ps];
     FOR_T(j, P.n) x[q * P.n + j] = I[P.i_x + j];
 }
@@ -3428,7 +3438,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void solution_in
 // copy of the slab in the LDS-resident build, before the write-back) and the row stored straight to the caller's array.
 template <int T>
 static __device__ __noinline__ __attribute__((not_tail_called)) void outputs_instance(int ps, gcdbl_p I, size_t q, const OutMapDev *Mp, double *u) {
-    ps = uni(ps); I = uni_ptr(I); Mp = uni_ptr(Mp); u = uni_ptr(u);
+    ps = uni(ps); I = uni_ptr(I); Mp = uni_ptr(Mp); u = uni_ptr(u); q = list_row(q);
     const DevPat &P = c_pat[ps];
     const int r = Mp->r;
     const AffineDev A = Mp->a;
@@ -3506,6 +3516,7 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     gdbl_p W = (gdbl_p)work + (size_t)blockIdx.x * P.work_stride;
 #endif
     if constexpr (NLDS >= 1) { // every slice table -> LDS, once per workgroup (same plans for every instance)
+        if (threadIdx.x == 0) { g_S.rows_at = upd.rows_at; g_S.queue = queue; } // (list_row: the barrier below stands in front of its first read)
         int *dst = reinterpret_cast<int *>(g_dyn + P.lds_tab); // (doubles from the start of the dynamic LDS: behind the vectors)
         auto stage = [&](const PackedSlice EICOS_GLOBAL *src, int cnt, int at) {
             gint_p si = reinterpret_cast<gint_p>(src);
@@ -3521,8 +3532,8 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     for (int q = threadIdx.x; q < P.ub_len; q += T) g_dyn[P.ub_lds + q] = 0.;
     __syncthreads();
 #endif
-    if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.cfg = cfg; g_S.step = 0; g_S.next = (int)blockIdx.x; g_S.smap = upd.smap; } // (next: the instance that is running)
-    if constexpr (NLDS >= 1) { if (threadIdx.x == 0) { g_S.roll = upd.roll; g_S.pmap = upd.pmap; g_S.omap = upd.omap; g_S.queue = queue; g_S.mmap = upd.mmap; } }
+    if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.cfg = cfg; g_S.step = 0; g_S.next = (int)blockIdx.x; g_S.smap = upd.smap; if constexpr (NLDS == 0) g_S.rows_at = 0; } // (next: the instance that is running)
+    if constexpr (NLDS >= 1) { if (threadIdx.x == 0) { g_S.roll = upd.roll; g_S.pmap = upd.pmap; g_S.omap = upd.omap; g_S.mmap = upd.mmap; } }
     // Instances differ in iteration count (12..18 on the headline batch): after its first instance (= its own index, so
     // that workspace slot g holds the history of instance g when the batch fits the grid) a workgroup pulls the next
     // unsolved instance from a queue instead of striding through the batch.
@@ -3629,8 +3640,10 @@ __global__ __launch_bounds__(1024) void k_order(int ps, const double *inst, int 
 // candidate order, more than that by descending n_ldlsolve key, snake layout when the launch is one round (count <= full_grid, the
 // handle's resident workgroups: a subset launch runs min(full_grid, count) of them).  The counting sort cannot run in place: cand and
 // order are two arrays.  Plain vector stores throughout.
+// rows != NULL (a fused step over the subset: launch.hpp, UpdArgs::rows_at): rows[id] = the position of id among the candidates, for every
+// candidate -- [batch] ints, the other entries are not touched and not read.
 __global__ __launch_bounds__(1024) void k_select_order(int ps, const double *inst, int batch, const int *list, int nlist, unsigned mask,
-                                                       int *cand, int *count_out, int *order, int snake_on, int full_grid, int ncu) {
+                                                       int *cand, int *count_out, int *order, int snake_on, int full_grid, int ncu, int *rows) {
     const DevPat &P = c_pat[ps];
     constexpr int NB = 1024;
     __shared__ int cnt[NB];
@@ -3659,6 +3672,7 @@ __global__ __launch_bounds__(1024) void k_select_order(int ps, const double *ins
         src = cand; total = base;
         if (tid == 0) *count_out = total;
     }
+    if (rows) for (int q = tid; q < total; q += NB) rows[src[q]] = q; // (indexed by ID: the launch order below permutes positions, not rows)
     if (!order) return;
     if (total <= ncu) { // at most one instance per CU: candidate order (k_solve's identity order for a whole batch)
         for (int q = tid; q < total; q += NB) order[q] = src[q];
@@ -3690,15 +3704,18 @@ __global__ __launch_bounds__(1024) void k_select_order(int ps, const double *ins
 //  equilibrated A/G values in place through DevPat::Lsrc.)
 // ============================================================================================
 #if EICOS_MAIN_BUILD // (updateData and the debug kernels work on the slabs in HBM: main build only)
+// The instance whose slab row q of a range launch's arrays belongs to (launch.hpp: the launchers' `list`): first + q, or -- the index-list
+// forms, eicos_batch_*_indexed -- list[q].  The row of the caller's arrays stays q.
+__device__ __forceinline__ int slab_of(const int *list, int first, int q) { return list ? list[q] : first + q; }
 template <int T>
 __global__ __launch_bounds__(T) void k_update(int ps, double *inst, int first, int count,
                                               const double *Gpr, const double *Apr, const double *cin,
-                                              const double *hin, const double *bin, double *scratch, int *shared) {
+                                              const double *hin, const double *bin, double *scratch, int *shared, const int *list) {
     const DevPat &P = c_pat[ps];
     const int n = P.n, p = P.p, m = P.m, l = P.l;
     gdbl_p xt = (gdbl_p)scratch + (size_t)blockIdx.x * (size_t)(n + p + m), at = xt + n, gt = at + p;
     for (int q = blockIdx.x; q < count; q += gridDim.x) {
-        gdbl_p I = (gdbl_p)inst + (size_t)(first + q) * P.inst_stride;
+        gdbl_p I = (gdbl_p)inst + (size_t)slab_of(list, first, q) * P.inst_stride;
         gdbl_p Av = I + P.i_Av, Gv = I + P.i_Gv, cagv = I + P.i_cag, rAv = I + P.i_rA, rGv = I + P.i_rG;
         gdbl_p cv = I + P.i_c, hv = I + P.i_h, bv = I + P.i_b, xe = I + P.i_xe, ae = I + P.i_ae, ge = I + P.i_ge;
         DevInfo *ginfo = reinterpret_cast<DevInfo *>(I + P.i_info);
@@ -3791,21 +3808,21 @@ __global__ __launch_bounds__(T) void k_update(int ps, double *inst, int first, i
 template <int T, bool LDSV>
 __global__ __launch_bounds__(T) void k_update_lds(int ps, double *inst, int first, int count,
                                                   const double *Gpr, const double *Apr, const double *cin,
-                                                  const double *hin, const double *bin, int *shared) {
+                                                  const double *hin, const double *bin, int *shared, const int *list) {
     const DevPat &P = c_pat[ps];
     for (int q = blockIdx.x; q < count; q += gridDim.x)
-        update_instance<T, LDSV, false, true>(ps, (hbm_p)inst + (size_t)(first + q) * P.inst_stride, (size_t)q, Gpr, Apr, cin, hin, bin, shared);
+        update_instance<T, LDSV, false, true>(ps, (hbm_p)inst + (size_t)slab_of(list, first, q) * P.inst_stride, (size_t)q, Gpr, Apr, cin, hin, bin, shared);
 }
 
 // right-hand-side-only updateData of a range of instances (rhs_instance): ENTRY-parallel -- blockIdx.y strides over the instances,
 // the x dimension over the given entries [c | h | b] of one instance (unit stride in the inputs and in the slab)
 template <int T>
 __global__ __launch_bounds__(T) void k_update_rhs_range(int ps, double *inst, int first, int count, const double *cin, const double *hin,
-                                                        const double *bin) {
+                                                        const double *bin, const int *list) {
     const DevPat &P = c_pat[ps];
     const int wc = cin ? P.n : 0, wh = hin ? P.m : 0, w = wc + wh + (bin ? P.p : 0);
     for (int q = blockIdx.y; q < count; q += gridDim.y) {
-        hbm_p I = (hbm_p)inst + (size_t)(first + q) * P.inst_stride;
+        hbm_p I = (hbm_p)inst + (size_t)slab_of(list, first, q) * P.inst_stride;
         const bool eq = reinterpret_cast<const DevInfo EICOS_GLOBAL *>(I + P.i_info)->equilibrated != 0;
         for (int e = blockIdx.x * T + threadIdx.x; e < w; e += gridDim.x * T) rhs_entry(I, e, wc, wh, (size_t)q, P, eq, cin, hin, bin);
     }
@@ -3850,7 +3867,7 @@ __device__ __forceinline__ bool param_q_rows(const AffineDev &A, bool act, doubl
     return true;
 }
 template <int T, bool LDS>
-__global__ __launch_bounds__(T) void k_update_param_range(int ps, double *inst, int first, int count, ParamMapDev M, const double *theta) {
+__global__ __launch_bounds__(T) void k_update_param_range(int ps, double *inst, int first, int count, ParamMapDev M, const double *theta, const int *list) {
     const DevPat &P = c_pat[ps];
     const int k = M.k;
     const int wc = M.g[0].base ? P.n : 0, wh = M.g[1].base ? P.m : 0, w = wc + wh + (M.g[2].base ? P.p : 0);
@@ -3871,7 +3888,7 @@ __global__ __launch_bounds__(T) void k_update_param_range(int ps, double *inst, 
 #pragma unroll
             for (int j = 0; j < PARAM_Q; j++)
                 if (j < nq) {
-                    hbm_p I = (hbm_p)inst + (size_t)(first + q0 + j) * P.inst_stride;
+                    hbm_p I = (hbm_p)inst + (size_t)slab_of(list, first, q0 + j) * P.inst_stride;
                     const bool eq = reinterpret_cast<const DevInfo EICOS_GLOBAL *>(I + P.i_info)->equilibrated != 0;
                     I[i_dst] = acc[j] / (eq ? I[i_scl] : 1.);
                 }
@@ -3909,13 +3926,13 @@ __global__ __launch_bounds__(T) void k_expand_affine(AffineDev A, int rows, int 
 // The output map over a range of instances (eicos_batch_outputs*; outputs_instance is the fused form): ROW-parallel over the count * r
 // rows, the map by value and served from L2, x read from the instance slabs.  Same arithmetic as outputs_instance.
 template <int T>
-__global__ __launch_bounds__(T) void k_outputs_range(int ps, const double *inst, int first, int count, OutMapDev M, double *u) {
+__global__ __launch_bounds__(T) void k_outputs_range(int ps, const double *inst, int first, int count, OutMapDev M, double *u, const int *list) {
     const DevPat &P = c_pat[ps];
     const size_t r = (size_t)M.r, total = (size_t)count * r;
     for (size_t e = (size_t)blockIdx.x * T + threadIdx.x; e < total; e += (size_t)gridDim.x * T) {
         const size_t q = e / r;
         const int row = (int)(e - q * r);
-        const double *x = inst + (size_t)(first + q) * P.inst_stride + P.i_x;
+        const double *x = inst + (size_t)slab_of(list, first, (int)q) * P.inst_stride + P.i_x;
         u[e] = affine_row(M.a, row, x);
     }
 }
@@ -3926,11 +3943,11 @@ __global__ __launch_bounds__(T) void k_outputs_range(int ps, const double *inst,
 // then marks the record by the rule instance_begin reads: warm-startable means n_factor > 0 and an exit code of 0 or 10.
 template <int T>
 __global__ __launch_bounds__(T) void k_set_iterate_range(int ps, double *inst, int first, int count, const double *x, const double *y,
-                                                         const double *z, const double *s) {
+                                                         const double *z, const double *s, const int *list) {
     const DevPat &P = c_pat[ps];
     const int wx = x ? P.n : 0, wy = y ? P.p : 0, wz = z ? P.m : 0, w = wx + wy + wz + (s ? P.m : 0);
     for (int q = blockIdx.y; q < count; q += gridDim.y) {
-        hbm_p I = (hbm_p)inst + (size_t)(first + q) * P.inst_stride;
+        hbm_p I = (hbm_p)inst + (size_t)slab_of(list, first, q) * P.inst_stride;
         for (int e = blockIdx.x * T + threadIdx.x; e < w; e += gridDim.x * T) {
             if (e < wx) I[P.i_x + e] = x[(size_t)q * P.n + e];
             else if (e < wx + wy) I[P.i_y + (e - wx)] = y[(size_t)q * P.p + (e - wx)];
@@ -4069,6 +4086,7 @@ template <class F> static auto dispatch_solve(int nlds, int idx16, F &&f) {
 static hipError_t launch_solve(const SolveLaunch &launch, hipStream_t st, const UpdArgs &step) {
     // (copies: hipLaunchKernel takes non-const pointers; cfg travels by value, so a launch in flight keeps the settings it was enqueued with)
     SolveLaunch L = launch; UpdArgs upd = step;
+    if ((upd.rows_at != 0) != (L.rows != nullptr) || (L.rows && (!L.list || upd.on != UPD_PARAM || L.rows != L.queue + upd.rows_at))) return hipErrorInvalidValue; // (a step in list order reads the row map THIS launch's selection kernel writes)
     if (upd.on && L.nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector; both modes live in the NLDS >= 1 kernels)
     if (L.B <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(L.queue, 0, sizeof(int), st); // group queue of this launch
@@ -4081,7 +4099,7 @@ static hipError_t launch_solve(const SolveLaunch &launch, hipStream_t st, const 
     static const int snake_on = [] { const char *e = getenv("EICOS_EXPERIMENT"), *k = getenv("EICOS_SNAKE"); return !(e && k && !strcmp(e, "1") && !strcmp(k, "0")); }();
     if (L.list) { // a subset launch (launch.hpp: SolveLaunch): order = the chosen ids, arranged by the selection kernel, never NULL
         hipLaunchKernelGGL(k_select_order, dim3(1), dim3(1024), 0, st, L.ps, (const double *)L.inst, L.batch, L.list, L.B, 0u, (int *)nullptr, (int *)nullptr,
-                           L.order, snake_on, L.full_grid, L.order_min);
+                           L.order, snake_on, L.full_grid, L.order_min, L.rows);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     } else if (L.B <= L.order_min) L.order = nullptr; // at most one instance per CU: identity
     else {
@@ -4096,13 +4114,13 @@ static hipError_t launch_solve(const SolveLaunch &launch, hipStream_t st, const 
 #if EICOS_MAIN_BUILD
 hipError_t launch_update(int ps, double *inst, int first, int count, const double *Gpr, const double *Apr,
                          const double *c, const double *h, const double *b, double *scratch, int grid, size_t lds_bytes, int vals_in_lds, hipStream_t st,
-                         int *shared) {
+                         int *shared, const int *list) {
     if (count <= 0) return hipSuccess;
     if (lds_bytes > 0 && !vals_in_lds) { // entry-parallel, maxima in LDS, values streamed in place in the slab (several workgroups per CU)
-        hipLaunchKernelGGL((k_update_lds<512, false>), dim3(grid), dim3(512), lds_bytes, st, ps, inst, first, count, Gpr, Apr, c, h, b, shared);
+        hipLaunchKernelGGL((k_update_lds<512, false>), dim3(grid), dim3(512), lds_bytes, st, ps, inst, first, count, Gpr, Apr, c, h, b, shared, list);
     } else if (lds_bytes > 0) { // values + maxima fit LDS: the entry-parallel kernel, 512 threads, one workgroup per CU at a time
-        hipLaunchKernelGGL((k_update_lds<512, true>), dim3(grid), dim3(512), lds_bytes, st, ps, inst, first, count, Gpr, Apr, c, h, b, shared);
-    } else hipLaunchKernelGGL(k_update<256>, dim3(grid), dim3(256), 0, st, ps, inst, first, count, Gpr, Apr, c, h, b, scratch, shared);
+        hipLaunchKernelGGL((k_update_lds<512, true>), dim3(grid), dim3(512), lds_bytes, st, ps, inst, first, count, Gpr, Apr, c, h, b, shared, list);
+    } else hipLaunchKernelGGL(k_update<256>, dim3(grid), dim3(256), 0, st, ps, inst, first, count, Gpr, Apr, c, h, b, scratch, shared, list);
     return hipGetLastError();
 }
 hipError_t launch_shared_operands(int ps, const double *inst, double *kt0, double *ub0, hipStream_t st) {
@@ -4110,23 +4128,25 @@ hipError_t launch_shared_operands(int ps, const double *inst, double *kt0, doubl
     hipLaunchKernelGGL(k_shared_operands<T>, dim3(32), dim3(T), 0, st, ps, inst, kt0, ub0);
     return hipGetLastError();
 }
-hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st) {
+hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st,
+                             const int *list) {
     if (count <= 0 || width <= 0) return hipSuccess;
     constexpr int T = 256;
     const int gx = (width + T - 1) / T, gy = count;
     const dim3 grid((unsigned)(gx < 64 ? gx : 64), (unsigned)(gy < 16384 ? gy : 16384));
-    hipLaunchKernelGGL(k_update_rhs_range<T>, grid, dim3(T), 0, st, ps, inst, first, count, c, h, b);
+    hipLaunchKernelGGL(k_update_rhs_range<T>, grid, dim3(T), 0, st, ps, inst, first, count, c, h, b, list);
     return hipGetLastError();
 }
 // grid: x = up to 16 workgroups over the entries (a longer [c | h | b] takes further passes), y = groups of PARAM_Q instances, about
 // 2048 workgroups in all (the rest by stride).  The theta rows of a group go to LDS while they fit 32 KB (k <= 1024).
-hipError_t launch_update_param(int ps, double *inst, int first, int count, const ParamMapDev &map, const double *theta, int width, hipStream_t st) {
+hipError_t launch_update_param(int ps, double *inst, int first, int count, const ParamMapDev &map, const double *theta, int width, hipStream_t st,
+                               const int *list) {
     if (count <= 0 || width <= 0) return hipSuccess;
     constexpr int T = 256;
     const int nx = (width + T - 1) / T, gx = nx < 16 ? nx : 16, ny = (count + PARAM_Q - 1) / PARAM_Q, gy = ny < 2048 / gx ? ny : 2048 / gx;
     const size_t lds = (size_t)PARAM_Q * map.k * sizeof(double);
-    if (lds <= 32 * 1024) hipLaunchKernelGGL((k_update_param_range<T, true>), dim3((unsigned)gx, (unsigned)gy), dim3(T), lds, st, ps, inst, first, count, map, theta);
-    else hipLaunchKernelGGL((k_update_param_range<T, false>), dim3((unsigned)gx, (unsigned)gy), dim3(T), 0, st, ps, inst, first, count, map, theta);
+    if (lds <= 32 * 1024) hipLaunchKernelGGL((k_update_param_range<T, true>), dim3((unsigned)gx, (unsigned)gy), dim3(T), lds, st, ps, inst, first, count, map, theta, list);
+    else hipLaunchKernelGGL((k_update_param_range<T, false>), dim3((unsigned)gx, (unsigned)gy), dim3(T), 0, st, ps, inst, first, count, map, theta, list);
     return hipGetLastError();
 }
 // grid as launch_update_param's: x = up to 16 workgroups over the rows, y = groups of PARAM_Q instances, about 2048 workgroups in all
@@ -4140,19 +4160,19 @@ hipError_t launch_expand_affine(const AffineDev &map, int rows, int k, const dou
     return hipGetLastError();
 }
 hipError_t launch_set_iterate(int ps, double *inst, int first, int count, const double *x, const double *y, const double *z, const double *s,
-                              int width, hipStream_t st) {
+                              int width, hipStream_t st, const int *list) {
     if (count <= 0 || width <= 0) return hipSuccess;
     constexpr int T = 256;
     const int gx = (width + T - 1) / T, gy = count;
     const dim3 grid((unsigned)(gx < 64 ? gx : 64), (unsigned)(gy < 16384 ? gy : 16384));
-    hipLaunchKernelGGL(k_set_iterate_range<T>, grid, dim3(T), 0, st, ps, inst, first, count, x, y, z, s);
+    hipLaunchKernelGGL(k_set_iterate_range<T>, grid, dim3(T), 0, st, ps, inst, first, count, x, y, z, s, list);
     return hipGetLastError();
 }
-hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st) {
+hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st, const int *list) {
     if (count <= 0 || map.r <= 0) return hipSuccess;
     constexpr int T = 256;
     const size_t nb = ((size_t)count * map.r + T - 1) / T;
-    hipLaunchKernelGGL(k_outputs_range<T>, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(T), 0, st, ps, inst, first, count, map, u);
+    hipLaunchKernelGGL(k_outputs_range<T>, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(T), 0, st, ps, inst, first, count, map, u, list);
     return hipGetLastError();
 }
 hipError_t launch_plant(int ps, const double *inst, int first, int count, const RolloutDev &roll, int t, const double *theta_cur,
@@ -4165,7 +4185,7 @@ hipError_t launch_plant(int ps, const double *inst, int first, int count, const 
 }
 hipError_t launch_select(int ps, const double *inst, int batch, unsigned mask, int *cand, int *count, hipStream_t st) {
     if (batch <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_select_order, dim3(1), dim3(1024), 0, st, ps, inst, batch, (const int *)nullptr, 0, mask, cand, count, (int *)nullptr, 0, 0, 0);
+    hipLaunchKernelGGL(k_select_order, dim3(1), dim3(1024), 0, st, ps, inst, batch, (const int *)nullptr, 0, mask, cand, count, (int *)nullptr, 0, 0, 0, (int *)nullptr);
     return hipGetLastError();
 }
 hipError_t launch_gather_rows(int ps, const double *inst, const int *list, int count, int want, double *dst, hipStream_t st) {

@@ -13,6 +13,11 @@ namespace eicos {
 // on = UPD_FULL: updateData (G, A, c, h, b); on = UPD_RHS: the right-hand-side-only update (c, h, b scaled by the stored scalings; G, A
 // unused); on = UPD_PARAM: the parametric update (eicos_batch_update_param_solve) -- row `instance` of theta [batch][pmap->k] expanded
 // through *pmap, the five arrays unused; 0: off.
+// rows_at != 0 with on = UPD_PARAM (eicos_batch_update_param_solve_subset: a SUBSET launch): theta, x and u are [count][...] arrays in the
+// order of the caller's list -- the row of instance `id` is rows[id], the ROW MAP the selection kernel of this launch has written
+// (SolveLaunch::rows).  The map lives in the handle's queue allocation, `batch` ints starting at int rows_at of it.  k_solve parks
+// rows_at in its LDS state once and passes `id` on as it always does; the per-instance functions that read or write a caller's row
+// (kernels.hip: list_row) translate it.  Slab addresses always come from id.
 // u != NULL (any mode, 0 included): row `instance` of u [batch][omap->r] = the output map applied to the instance's x, written like x.
 // The two maps stay in device memory and travel as pointers: a launch that uses neither pays four words of kernel arguments for them.
 // on = UPD_ROLL with roll != NULL (eicos_batch_rollout; theta and u unused): the workgroup takes its instance through roll->steps closed-loop
@@ -42,6 +47,7 @@ struct UpdArgs { // UpdArgs{} = the neutral launch: no fused step, no maps; ever
     const double *G = nullptr, *A = nullptr, *c = nullptr, *h = nullptr, *b = nullptr;
     // outputs: x [batch][n], and the mode (UPD_*, 0: no fused step)
     double *x = nullptr; int on = 0;
+    int rows_at = 0; // a parametric step over a chosen subset: where in the queue allocation (in ints) its row map starts; 0: row = instance (above)
     // staging: ready flags of the chunks (NULL: nothing is staged), instances per chunk, the flag value of this launch, the time-out word
     const unsigned *flags = nullptr; int chunk = 1; unsigned seq = 0; int *err = nullptr;
     // maps (device copies of the handle's descriptors) with the input theta and the output u of the parametric step
@@ -76,6 +82,7 @@ struct SolveLaunch {
     int grid, threads, nlds, idx16, order_min;
     double warm, dyn_delta, dyn_eps; SolveCfg cfg; size_t dyn_lds;
     const int *list; int batch, full_grid; // subset launches: the chosen ids, the handle's batch and its whole-batch grid
+    int *rows; // subset launches with a step in list order (UpdArgs::rows_at): the selection kernel leaves rows[list[q]] = q here; NULL: not asked for
 };
 // One k_solve build = these four entry points.  launch always receives an UpdArgs: UpdArgs{} when no step is fused into it.
 struct SolveBuild {
@@ -85,25 +92,30 @@ struct SolveBuild {
     hipError_t (*upload)(int ps, const DevPat &P);
     bool operator==(const SolveBuild &o) const { return launch == o.launch; }
 };
+// The range launchers below (updateData in its four kinds and the output map) take an optional `list`: `count` ids of distinct instances
+// in device memory.  Row q of the input or output arrays then belongs to the slab of instance list[q] instead of first + q (`first` is
+// unused); NULL: the range.  The arithmetic per instance is the same either way.
 // shared != NULL (only the launch that covers the whole batch, first = 0, with every matrix the pattern has given): the handle's shared-values
 // word, which the host has set to 0 on `st` in front of this launch -- a workgroup whose rows of Gpr / Apr differ from row 0 in any bit
 // stores -1 (kernels.hip: update_instance)
 hipError_t launch_update(int ps, double *inst, int first, int count, const double *Gpr, const double *Apr,
                          const double *c, const double *h, const double *b, double *scratch, int grid, size_t lds_bytes, int vals_in_lds, hipStream_t st,
-                         int *shared = nullptr);
+                         int *shared = nullptr, const int *list = nullptr);
 // The shared factor operands of a handle (DevPat::kt0 / ub0), behind the launch_update that was given `shared`: kt0[t] = the K entry of target
 // t as instance 0's slab holds it (DevPat::fac_src), and every level-0 off-diagonal target that lands in a backward slot >= ub0_off also
 // into ub0 (ub0 == NULL: the handle shares the K stream only).  Plain copies: the bits instance_begin and the factorisation would produce.
 hipError_t launch_shared_operands(int ps, const double *inst, double *kt0, double *ub0, hipStream_t st);
 // right-hand-side-only updateData of instances [first, first + count): rows of c [count][n], h [count][m], b [count][p] (NULL = keep)
 // divided by each instance's stored scalings; `width` = the summed widths of the given groups (sizes the grid)
-hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st);
+hipError_t launch_update_rhs(int ps, double *inst, int first, int count, const double *c, const double *h, const double *b, int width, hipStream_t st,
+                             const int *list = nullptr);
 // Parametric right-hand sides (eicos_batch_set_param_map): per group c, h, b a base vector and a CSR matrix with k columns, in device
 // memory, shared by every instance of the handle; base == NULL: the group has no map and is kept (AffineDev, ParamMapDev: above).  Passed
 // to the range kernel by value.
 // instances [first, first + count) from rows of theta [count][k]: entry = (base[r] + sum val * theta[col], every product and sum
 // rounded on its own, in stored order) divided by the instance's stored scaling -- the bits launch_update_rhs leaves for the same vectors
-hipError_t launch_update_param(int ps, double *inst, int first, int count, const ParamMapDev &map, const double *theta, int width, hipStream_t st);
+hipError_t launch_update_param(int ps, double *inst, int first, int count, const ParamMapDev &map, const double *theta, int width, hipStream_t st,
+                               const int *list = nullptr);
 // One affine group over rows of theta [count][k] into dst [count][rows], unscaled: dst[q][r] = base[r] + sum val * theta[q][col], in stored
 // order, every product and sum rounded on its own.  With a matrix map installed the parametric update expands [Gpr | Apr | c | h | b] this
 // way into a device staging buffer and hands it to launch_update.
@@ -112,10 +124,10 @@ hipError_t launch_expand_affine(const AffineDev &map, int rows, int k, const dou
 // into the slabs of instances [first, first + count) as they are, and every instance marked warm-startable (exit code OPTIMAL unless it is
 // OPTIMAL or close to it already, n_factor 1 if it was 0); `width` = the summed widths of the given groups (sizes the grid)
 hipError_t launch_set_iterate(int ps, double *inst, int first, int count, const double *x, const double *y, const double *z, const double *s,
-                              int width, hipStream_t st);
+                              int width, hipStream_t st, const int *list = nullptr);
 // rows [first, first + count) of u [count][map.r] = the output map applied to the current x of those instances: acc = base[row], then
 // acc = acc + (val * x[col]) in stored order, every product and sum rounded on its own
-hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st);
+hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st, const int *list = nullptr);
 // One step of a rollout that is not fused into the solve launch, for instances [first, first + count), behind that step's solve and
 // output kernels: z = [row of theta_cur [count][k] | row of u_cur [count][r]] goes through the plant map -- acc = base[row], then
 // acc = acc + (val * z[col]) in stored order, then + w when given, every product and sum rounded on its own -- into theta_next [count][k]

@@ -386,6 +386,121 @@ int eicos_multi_gather(eicos_multi *mh, const int *idx, int count, double *x, do
     });
 }
 
+} // extern "C"
+
+// ---- index-list updates, output rows and the closed-loop step over a subset (eicos_batch_*_indexed per shard): global ids, host arrays
+// in list order.  The pattern of eicos_multi_gather: a shard's rows are packed into its own compact arrays (pack), results go back to
+// their positions in the caller's list (unpack).  A handle of ONE shard hands the caller's list and arrays on as they are: pinned arrays
+// stay pinned, so the step over a subset keeps its one-launch path.
+namespace {
+// rows pos[0 .. k) of src [count][w] behind each other; NULL or w = 0: nothing (data() of an empty vector is handed on as NULL)
+std::vector<double> pack(const double *src, const std::vector<int> &pos, int w) {
+    std::vector<double> out(src && w > 0 ? pos.size() * (size_t)w : 0);
+    for (size_t q = 0; q < pos.size() && !out.empty(); q++) std::memcpy(out.data() + q * w, src + (size_t)pos[q] * w, (size_t)w * sizeof(double));
+    return out;
+}
+void unpack(double *dst, const std::vector<double> &src, const std::vector<int> &pos, int w) {
+    if (dst && w > 0) for (size_t q = 0; q < pos.size(); q++) std::memcpy(dst + (size_t)pos[q] * w, src.data() + q * w, (size_t)w * sizeof(double));
+}
+// a group the caller gave stays given for the shard even where its width is 0 (the h / b rules look at the pointers)
+const double *given(const double *src, const std::vector<double> &packed) { return src ? (packed.empty() ? src : packed.data()) : nullptr; }
+} // namespace
+
+extern "C" {
+
+int eicos_multi_update_indexed(eicos_multi *mh, const int *idx, int count, const double *G, const double *A, const double *c, const double *hh,
+                               const double *b) {
+    Shares sh;
+    const int rc = split_list(mh, idx, count, "eicos_multi_update_indexed", sh);
+    if (rc != EICOS_OK) return rc;
+    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_update_indexed(mh->shard[0], idx, count, G, A, c, hh, b); });
+    return for_shards(mh, [&](int s) {
+        const std::vector<int> &pos = sh.pos[s];
+        if (pos.empty()) return (int)EICOS_OK;
+        const std::vector<double> tG = pack(G, pos, mh->nnzG), tA = pack(A, pos, mh->nnzA), tc = pack(c, pos, mh->n), th = pack(hh, pos, mh->m), tb = pack(b, pos, mh->p);
+        return eicos_batch_update_indexed(mh->shard[s], sh.ids[s].data(), (int)pos.size(), given(G, tG), given(A, tA), given(c, tc), given(hh, th), given(b, tb));
+    });
+}
+
+int eicos_multi_update_rhs_indexed(eicos_multi *mh, const int *idx, int count, const double *c, const double *hh, const double *b) {
+    Shares sh;
+    const int rc = split_list(mh, idx, count, "eicos_multi_update_rhs_indexed", sh);
+    if (rc != EICOS_OK) return rc;
+    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_update_rhs_indexed(mh->shard[0], idx, count, c, hh, b); });
+    return for_shards(mh, [&](int s) {
+        const std::vector<int> &pos = sh.pos[s];
+        if (pos.empty()) return (int)EICOS_OK;
+        const std::vector<double> tc = pack(c, pos, mh->n), th = pack(hh, pos, mh->m), tb = pack(b, pos, mh->p);
+        return eicos_batch_update_rhs_indexed(mh->shard[s], sh.ids[s].data(), (int)pos.size(), given(c, tc), given(hh, th), given(b, tb));
+    });
+}
+
+int eicos_multi_update_param_indexed(eicos_multi *mh, const int *idx, int count, const double *theta) {
+    Shares sh;
+    const int rc = split_list(mh, idx, count, "eicos_multi_update_param_indexed", sh);
+    if (rc != EICOS_OK) return rc;
+    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_update_param_indexed(mh->shard[0], idx, count, theta); });
+    const int k = std::max(0, eicos_batch_param_count(mh->shard[0]));
+    return for_shards(mh, [&](int s) {
+        const std::vector<int> &pos = sh.pos[s];
+        if (pos.empty()) return (int)EICOS_OK;
+        const std::vector<double> tt = pack(theta, pos, k);
+        return eicos_batch_update_param_indexed(mh->shard[s], sh.ids[s].data(), (int)pos.size(), given(theta, tt));
+    });
+}
+
+int eicos_multi_set_iterate_indexed(eicos_multi *mh, const int *idx, int count, const double *x, const double *y, const double *z, const double *sl) {
+    Shares sh;
+    const int rc = split_list(mh, idx, count, "eicos_multi_set_iterate_indexed", sh);
+    if (rc != EICOS_OK) return rc;
+    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_set_iterate_indexed(mh->shard[0], idx, count, x, y, z, sl); });
+    return for_shards(mh, [&](int s) {
+        const std::vector<int> &pos = sh.pos[s];
+        if (pos.empty()) return (int)EICOS_OK;
+        const std::vector<double> tx = pack(x, pos, mh->n), ty = pack(y, pos, mh->p), tz = pack(z, pos, mh->m), ts = pack(sl, pos, mh->m);
+        return eicos_batch_set_iterate_indexed(mh->shard[s], sh.ids[s].data(), (int)pos.size(), given(x, tx), given(y, ty), given(z, tz), given(sl, ts));
+    });
+}
+
+int eicos_multi_outputs_indexed(eicos_multi *mh, const int *idx, int count, double *u) {
+    Shares sh;
+    const int rc = split_list(mh, idx, count, "eicos_multi_outputs_indexed", sh);
+    if (rc != EICOS_OK) return rc;
+    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_outputs_indexed(mh->shard[0], idx, count, u); });
+    const int r = std::max(0, eicos_batch_output_count(mh->shard[0]));
+    return for_shards(mh, [&](int s) {
+        const std::vector<int> &pos = sh.pos[s];
+        if (pos.empty()) return (int)EICOS_OK;
+        std::vector<double> tu(u ? pos.size() * (size_t)r : 0);
+        const int e = eicos_batch_outputs_indexed(mh->shard[s], sh.ids[s].data(), (int)pos.size(), u ? (tu.empty() ? u : tu.data()) : nullptr);
+        if (e == EICOS_OK) unpack(u, tu, pos, r);
+        return e;
+    });
+}
+
+int eicos_multi_update_param_solve_subset(eicos_multi *mh, const int *idx, int count, const double *theta, double *u_out, double *x_out,
+                                          int *exitcodes) {
+    Shares sh;
+    const int rc = split_list(mh, idx, count, "eicos_multi_update_param_solve_subset", sh);
+    if (rc != EICOS_OK) return rc;
+    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_update_param_solve_subset(mh->shard[0], idx, count, theta, u_out, x_out, exitcodes); });
+    const int k = std::max(0, eicos_batch_param_count(mh->shard[0])), r = std::max(0, eicos_batch_output_count(mh->shard[0]));
+    return for_shards(mh, [&](int s) {
+        const std::vector<int> &pos = sh.pos[s];
+        if (pos.empty()) return (int)EICOS_OK;
+        const std::vector<double> tt = pack(theta, pos, k);
+        std::vector<double> tu(u_out ? pos.size() * (size_t)r : 0), tx(x_out ? pos.size() * (size_t)mh->n : 0);
+        std::vector<int> codes(exitcodes ? pos.size() : 0);
+        const int e = eicos_batch_update_param_solve_subset(mh->shard[s], sh.ids[s].data(), (int)pos.size(), given(theta, tt),
+                                                            u_out ? (tu.empty() ? u_out : tu.data()) : nullptr, tx.empty() ? nullptr : tx.data(),
+                                                            exitcodes ? codes.data() : nullptr);
+        if (e != EICOS_OK) return e;
+        unpack(u_out, tu, pos, r); unpack(x_out, tx, pos, mh->n);
+        for (size_t q = 0; exitcodes && q < pos.size(); q++) exitcodes[pos[q]] = codes[q];
+        return (int)EICOS_OK;
+    });
+}
+
 // updateData + solve in one call over every shard (eicos_batch_update_solve per shard on its rows, the shards concurrently)
 int eicos_multi_update_solve(eicos_multi *mh, const double *G, const double *A, const double *c, const double *hh, const double *b,
                              double *x_out, int *exitcodes) {

@@ -353,6 +353,43 @@ namespace EiCOS
         {
             mcheck(eicos_multi_gather(h_, indices.data(), (int)indices.size(), x, y, z, s, info), "eicos_multi_gather");
         }
+        // Extension: update, read and step a chosen SUBSET (eicos_multi_*_indexed, _update_param_solve_subset of eicos_amd.h).  `indices` are
+        // distinct global instance ids; row q of every array ([indices.size()][...]) belongs to instance indices[q], nullptr keeps a group.
+        // Each overload leaves, bit for bit, what the loop of count = 1 calls of its range namesake leaves; the other instances keep
+        // their state.  An empty list does nothing; a refused list (out of range, duplicate) throws and changes nothing.
+        void updateData(const std::vector<int> &indices, const double *Gpr, const double *Apr, const double *c, const double *h, const double *b)
+        {
+            mcheck(eicos_multi_update_indexed(h_, indices.data(), (int)indices.size(), Gpr, Apr, c, h, b), "eicos_multi_update_indexed");
+        }
+        void updateRHS(const std::vector<int> &indices, const double *c, const double *h, const double *b)
+        {
+            mcheck(eicos_multi_update_rhs_indexed(h_, indices.data(), (int)indices.size(), c, h, b), "eicos_multi_update_rhs_indexed");
+        }
+        void updateParam(const std::vector<int> &indices, const double *theta)
+        {
+            mcheck(eicos_multi_update_param_indexed(h_, indices.data(), (int)indices.size(), theta), "eicos_multi_update_param_indexed");
+        }
+        void setIterate(const std::vector<int> &indices, const double *x, const double *y, const double *z, const double *s)
+        {
+            mcheck(eicos_multi_set_iterate_indexed(h_, indices.data(), (int)indices.size(), x, y, z, s), "eicos_multi_set_iterate_indexed");
+        }
+        void outputs(const std::vector<int> &indices, double *u)
+        {
+            mcheck(eicos_multi_outputs_indexed(h_, indices.data(), (int)indices.size(), u), "eicos_multi_outputs_indexed");
+        }
+        // stepParamSubset: the closed-loop step for the instances `indices` only -- updateParam(indices, theta) + solveSubset(indices) +
+        // outputs(indices, u_out) (+ the x rows) in ONE call; theta [count][k], u_out [count][r], x_out [count][n] in list order.  With
+        // theta from hostAlloc / hostRegister it is one subset launch per shard whose workgroups expand their own theta row and write
+        // their rows of pinned result arrays.  Returns the exit codes in list order.
+        std::vector<exitcode> stepParamSubset(const std::vector<int> &indices, const double *theta, double *u_out, double *x_out = nullptr)
+        {
+            std::vector<int> codes(indices.size());
+            mcheck(eicos_multi_update_param_solve_subset(h_, indices.data(), (int)indices.size(), theta, u_out, x_out, codes.data()),
+                   "eicos_multi_update_param_solve_subset");
+            std::vector<exitcode> out(indices.size());
+            for (size_t i = 0; i < indices.size(); i++) out[i] = static_cast<exitcode>(codes[i]);
+            return out;
+        }
         void solveAsync() { mcheck(eicos_multi_solve_async(h_), "eicos_multi_solve_async"); } // enqueue on every shard's stream
         void sync() { mcheck(eicos_multi_sync(h_), "eicos_multi_sync"); }
         std::vector<double> solution() const

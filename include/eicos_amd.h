@@ -346,14 +346,64 @@ int eicos_exit_class(int exitcode, int n_factor);
  * count < 0 or count > batch; NULL idx with count > 0; an index outside [0, batch) (the message names index and position); a DUPLICATE
  * index (named: two workgroups would solve one slab at once; eicos_batch_gather refuses it like the solve calls); mask == 0 or bits above
  * bit 11.
- * Out of scope: fused update + solve over a subset (eicos_batch_update_solve and its kin take the whole batch), rollouts over a subset,
- * and index-list forms of the update calls (they take ranges). */
+ * Feeding a subset: the index-list forms of the update calls and the closed-loop step over a subset, below.
+ * Out of scope: rollouts over a subset, fused FULL and right-hand-side steps over a subset (eicos_batch_update_solve / _update_rhs_solve
+ * take the whole batch), and id lists that live on the GPU (a "step where"). */
 int eicos_batch_select(eicos_batch *hd, unsigned mask, int *idx_out /* [batch], ascending, optional */, int *count_out);
 int eicos_batch_solve_subset_async(eicos_batch *hd, const int *idx /* host [count] */, int count);
 int eicos_batch_solve_subset(eicos_batch *hd, const int *idx, int count, int *exitcodes /* [count], list order, optional */);
 int eicos_batch_solve_where(eicos_batch *hd, unsigned mask, int *idx_out /* [batch], optional, ascending */, int *count_out,
                             int *exitcodes /* [*count_out], order of idx_out, optional */);
 int eicos_batch_gather(eicos_batch *hd, const int *idx, int count, double *x, double *y, double *z, double *s, eicos_info *info);
+
+/* ---- update, read and step a chosen subset (no reference counterpart): the index-list forms of the update calls.
+ * idx is always a HOST array of `count` distinct ids in [0, batch); row q of every data array ([count][...], row-major) belongs to
+ * instance idx[q] -- the list-order convention of eicos_batch_solve_subset and _gather.  Everything else is the range namesake's
+ * (eicos_batch_update / _update_rhs / _update_param / _set_iterate and their _device forms): NULL groups, h read only with Gpr and b only
+ * with Apr in the full form, the memory kinds and transfer paths (pageable host arrays through the bounce pipeline in chunks, pinned or
+ * registered arrays read in place, device arrays read in place by one asynchronous launch), synchrony, eicos_batch_last_update_path, the
+ * timing ring, a matrix map turning update_param_indexed into a full updateData (expanded on the GPU, chunked), and the namesake's
+ * refusals.  The list is checked as for the subset solves (NULL handle, count outside [0, batch], NULL idx, an id out of range, a
+ * DUPLICATE -- two workgroups would write one slab): EICOS_E_INVALID with a message naming the fault and no state changed.  An empty list
+ * is EICOS_OK: nothing enqueued, nothing recorded.
+ * Contract: the state the call leaves (slabs, solution, duals, info, eicos_debug_kkt, every later solve) equals, bit for bit, that of the
+ * loop  for q: range_form(first = idx[q], count = 1, row q)  on a twin handle; instances outside the list keep everything the host can
+ * read.  Shared matrix values (eicos_batch_shared_values) are kept by the rhs, param (without a matrix map) and iterate forms and dropped
+ * by eicos_batch_update_indexed and by the param form under a matrix map, as a sub-range call drops them; an indexed call never detects.
+ * The ids travel through the handle's pinned list buffer into a device area of their own: a queued subset launch keeps its ids. */
+int eicos_batch_update_indexed(eicos_batch *hd, const int *idx /* host [count] */, int count, const double *Gpr, const double *Apr,
+                               const double *c, const double *h, const double *b);
+int eicos_batch_update_rhs_indexed(eicos_batch *hd, const int *idx, int count, const double *c, const double *h, const double *b);
+int eicos_batch_update_param_indexed(eicos_batch *hd, const int *idx, int count, const double *theta /* [count][k] */);
+int eicos_batch_set_iterate_indexed(eicos_batch *hd, const int *idx, int count, const double *x, const double *y, const double *z, const double *s);
+/* ... data arrays in device memory (idx stays a host array), asynchronous on the handle's stream like their range namesakes */
+int eicos_batch_update_indexed_device(eicos_batch *hd, const int *idx, int count, const double *dGpr, const double *dApr, const double *dc,
+                                      const double *dh, const double *db);
+int eicos_batch_update_rhs_indexed_device(eicos_batch *hd, const int *idx, int count, const double *dc, const double *dh, const double *db);
+int eicos_batch_update_param_indexed_device(eicos_batch *hd, const int *idx, int count, const double *dtheta);
+int eicos_batch_set_iterate_indexed_device(eicos_batch *hd, const int *idx, int count, const double *dx, const double *dy, const double *dz,
+                                           const double *ds);
+/* eicos_batch_outputs_indexed / _device: row q of u [count][r] = the output map on the current x of instance idx[q], bit-identical to row
+ * idx[q] of eicos_batch_outputs (the same range kernel, reading the slab of idx[q]).  Refusals: those of eicos_batch_outputs (no output
+ * map, NULL u, a device pointer handed to the host form) and of the list check. */
+int eicos_batch_outputs_indexed(eicos_batch *hd, const int *idx, int count, double *u /* host [count][r] */);
+int eicos_batch_outputs_indexed_device(eicos_batch *hd, const int *idx, int count, double *du);
+/* eicos_batch_update_param_solve_subset: the closed-loop step over a subset = eicos_batch_update_param_indexed + eicos_batch_solve_subset
+ * + eicos_batch_outputs_indexed (+ the x rows), every array in list order; synchronous.
+ * Fused under exactly the conditions of eicos_batch_update_param_solve (an LDS vector, a theta row that fits it, GPU-addressable theta,
+ * EICOS_FUSED_UPDATE not 0; witness: eicos_batch_last_update_path == 5): ONE subset launch in which each workgroup expands row q of
+ * theta for the instance idx[q] it is about to solve (a full updateData from theta under a matrix map) and writes row q of u_out / x_out
+ * when it is done, if that array is pinned or device memory -- 8 k bytes in and 8 r bytes out per CHOSEN instance.  The selection kernel
+ * in front of the launch leaves a row map (id -> position in the list) next to the launch order; slab addresses still come from the id.
+ * Otherwise the three calls run; a pageable or unwritten u_out / x_out is filled through the indexed output kernel and the row gather.
+ * Contract: for every instance in the list, the state and the returned rows equal, bit for bit, those of a twin that ran the three
+ * calls -- cold, warm, under a shift map, under a matrix map, with shared matrix values (kept without a matrix map, dropped with one).
+ * Every instance outside the list keeps everything the host can read, info and solve_us included.  With idx = 0 .. batch-1 the call
+ * equals eicos_batch_update_param_solve.  An empty list is EICOS_OK with no launch.  Refusals: the list check, those of
+ * eicos_batch_update_param (no parameter map, NULL theta, a matrix map that no longer fits), u_out without an output map. */
+int eicos_batch_update_param_solve_subset(eicos_batch *hd, const int *idx, int count, const double *theta /* [count][k] */,
+                                          double *u_out /* [count][r], optional */, double *x_out /* [count][n], optional */,
+                                          int *exitcodes /* [count], optional */);
 
 /* ---- results: replaces solution() (reference include/eicos.hpp:160) / getInfo() (:163).
  * x: [batch][n] host.  y,z,s are extras the reference keeps private; any may be NULL.  A pinned destination receives one strided
@@ -590,6 +640,18 @@ int eicos_multi_solve_subset_async(eicos_multi *mh, const int *idx, int count);
 int eicos_multi_solve_subset(eicos_multi *mh, const int *idx, int count, int *exitcodes);
 int eicos_multi_solve_where(eicos_multi *mh, unsigned mask, int *idx_out, int *count_out, int *exitcodes);
 int eicos_multi_gather(eicos_multi *mh, const int *idx, int count, double *x, double *y, double *z, double *s, eicos_info *info);
+/* index-list updates, output rows and the closed-loop step over a subset (eicos_batch_*_indexed, _outputs_indexed,
+ * _update_param_solve_subset) with GLOBAL ids and host arrays in list order: the list is checked as a whole first -- a refused list
+ * changes no shard --, every shard's rows are packed on the host and handed to its handle with shard-local ids, results are scattered back
+ * to list order; the shards of eicos_multi_update_param_solve_subset run concurrently.  The _indexed_device forms have no multi form. */
+int eicos_multi_update_indexed(eicos_multi *mh, const int *idx, int count, const double *Gpr, const double *Apr, const double *c,
+                               const double *h, const double *b);
+int eicos_multi_update_rhs_indexed(eicos_multi *mh, const int *idx, int count, const double *c, const double *h, const double *b);
+int eicos_multi_update_param_indexed(eicos_multi *mh, const int *idx, int count, const double *theta);
+int eicos_multi_set_iterate_indexed(eicos_multi *mh, const int *idx, int count, const double *x, const double *y, const double *z, const double *s);
+int eicos_multi_outputs_indexed(eicos_multi *mh, const int *idx, int count, double *u);
+int eicos_multi_update_param_solve_subset(eicos_multi *mh, const int *idx, int count, const double *theta, double *u_out, double *x_out,
+                                          int *exitcodes);
 /* results gathered into the caller's host arrays in global instance order (the "gather" of north_star: per-device copies) */
 int eicos_multi_solution(eicos_multi *mh, double *x);
 int eicos_multi_duals(eicos_multi *mh, double *y, double *z, double *s);
