@@ -675,7 +675,9 @@ const char *eicos_last_error(void);
 int eicos_device_count(void);
 
 /* Debug/parity hooks (tests only): numeric LDL' of instance `inst` with the KKT values as they
- * stand, and one LDL' solve. Host buffers. */
+ * stand. Host buffers. There is no hook for a single LDL' solve: the triangular sweeps are checked
+ * through the solve kernel itself, run with eicos_settings.nitref = 0 so that no refinement step
+ * follows them, against the CPU oracle under the same setting (tests/test_unrefined_solves.py). */
 int eicos_debug_factor(eicos_batch *hd, int inst, double *D /*[dim_K], permuted*/, double *U /*[nnzL] CSC, permuted*/);
 /* per-iteration history of instance `inst` in the last solve: out[102][12] = {pcost,dcost,gap,pres,dres,
  * kap/tau,mu,step,sigma,tau,kap,nitref3} per IPM pass (valid while batch <= resident workgroups; after a subset launch: while its

@@ -43,11 +43,17 @@ using ivec = std::vector<int>;
 
 /* ---- settings: constants of struct Settings, ref include/eicos.hpp:23-47 ---- */
 constexpr double GAMMA = 0.99, DELTASTAT = 7e-8;
-constexpr double FEASTOL = 1e-8, ABSTOL = 1e-8, RELTOL = 1e-8;
-constexpr double FEASTOL_INACC = 1e-4, ABSTOL_INACC = 5e-5, RELTOL_INACC = 5e-5;
-constexpr int NITREF = 9, EQUIL_ITERS = 3, ITER_MAX = 100;
-constexpr double LINSYSACC = 1e-14, IRERRFACT = 6, STEPMIN = 1e-6, STEPMAX = 0.999;
+constexpr int EQUIL_ITERS = 3;
+constexpr double STEPMIN = 1e-6, STEPMAX = 0.999;
 constexpr double SIGMAMIN = 1e-4, SIGMAMAX = 1.0, SAFEGUARD = 500;
+
+/* the ten settings a caller may change (oracle_set_settings): members of each Solver, defaults = the reference's values */
+struct Settings {
+    double FEASTOL = 1e-8, ABSTOL = 1e-8, RELTOL = 1e-8;
+    double FEASTOL_INACC = 1e-4, ABSTOL_INACC = 5e-5, RELTOL_INACC = 5e-5;
+    double LINSYSACC = 1e-14, IRERRFACT = 6;
+    int ITER_MAX = 100, NITREF = 9;
+};
 
 enum { EX_OPTIMAL = 0, EX_PINF = 1, EX_DINF = 2, EX_MAXIT = -1, EX_NUMERICS = -2,
        EX_FATAL = -7, EX_INACC = 10, EX_NOT_CONVERGED = -87 };
@@ -206,6 +212,7 @@ struct Ldl {
 
     /* x = P' L^-T D^-1 L^-1 P b   (ref: ldlt.solve, src/eicos.cpp:1477,1599) */
     mutable vec wtmp;
+    double perturb = 0.; /* test hook oracle_debug_perturb_sweep: 0 = the clean sweep below */
     void solve(const vec &b, vec &x) const {
         if ((int)wtmp.size() != N) wtmp.assign(N, 0.0);
         vec &w = wtmp;
@@ -215,10 +222,19 @@ struct Ldl {
             for (int p = Lp[j]; p < Lp[j] + Lnz[j]; p++) w[Li[p]] -= Lx[p] * wj;
         }
         for (int j = 0; j < N; j++) w[j] /= D[j];
-        for (int j = N - 1; j >= 0; j--) {
-            double s = w[j];
-            for (int p = Lp[j]; p < Lp[j] + Lnz[j]; p++) s -= Lx[p] * w[Li[p]];
-            w[j] = s;
+        if (perturb == 0.) {
+            for (int j = N - 1; j >= 0; j--) {
+                double s = w[j];
+                for (int p = Lp[j]; p < Lp[j] + Lnz[j]; p++) s -= Lx[p] * w[Li[p]];
+                w[j] = s;
+            }
+        } else { /* a deliberately wrong backward substitution: the last stored entry of every column j % 7 == 3 is scaled */
+            for (int j = N - 1; j >= 0; j--) {
+                double s = w[j];
+                const int last = Lp[j] + Lnz[j] - 1;
+                for (int p = Lp[j]; p <= last; p++) s -= Lx[p] * w[Li[p]] * ((j % 7 == 3 && p == last) ? 1. + perturb : 1.);
+                w[j] = s;
+            }
         }
         x.resize(N);
         for (int k = 0; k < N; k++) x[perm[k]] = w[k];
@@ -257,6 +273,7 @@ struct Work { /* ref Work include/eicos.hpp:97-114 */
 };
 
 struct Solver {
+    Settings cfg;
     int n = 0, p = 0, m = 0, l = 0, nc = 0, N = 0, mt = 0;
     std::vector<Cone> cones;
     vec lpw, lpv;
@@ -534,7 +551,7 @@ struct Solver {
     /* ---------- ref solveKKT src/eicos.cpp:1471-1620 ---------- */
     int solve_kkt(const vec &rhs, vec &dx, vec &dy, vec &dz, bool init) {
         vec &x = kx; ldl.solve(rhs, x); n_ldlsolve++;
-        const double thr = (1. + norminf(rhs.data(), N)) * LINSYSACC;
+        const double thr = (1. + norminf(rhs.data(), N)) * cfg.LINSYSACC;
         double nerr_prev = std::numeric_limits<double>::max();
         if ((int)kdxref.size() != N) { kdxref.assign(N, 0.0); ke.assign(N, 0.0); kGdx.assign(m, 0.0); }
         vec &dxref = kdxref, &e = ke, &Gdx = kGdx;
@@ -551,7 +568,7 @@ struct Solver {
             }
         };
         int k;
-        for (k = 0; k <= NITREF; k++) {
+        for (k = 0; k <= cfg.NITREF; k++) {
             unpack();
             double *ex = e.data(), *ey = e.data() + n, *ez = e.data() + n + p;
             /* ex = bx - G'dz - A'dy - delta dx   (ref :1515-1521) */
@@ -586,7 +603,7 @@ struct Solver {
                 for (int i = 0; i < N; i++) x[i] -= dxref[i];
                 k--; break;
             }
-            if (k == NITREF || nerr < thr || (k > 0 && nerr_prev < IRERRFACT * nerr)) break;
+            if (k == cfg.NITREF || nerr < thr || (k > 0 && nerr_prev < cfg.IRERRFACT * nerr)) break;
             nerr_prev = nerr;
             ldl.solve(e, dxref); n_ldlsolve++;
             for (int i = 0; i < N; i++) x[i] += dxref[i];
@@ -633,17 +650,17 @@ struct Solver {
         i.pres = std::max(nry, nrz) / w.tau;
         i.dres = norm2(rx) / std::max(resx0 + ny + nz, 1.) / w.tau;
         /* sticky: only ever set, never cleared (ref :720-728) */
-        if ((w.hz + w.by) / std::max(ny + nz, 1.) < -RELTOL) { i.pinfres = hresx / std::max(ny + nz, 1.); i.has_pinfres = true; }
-        if (w.cx / std::max(nx, 1.) < -RELTOL) {
+        if ((w.hz + w.by) / std::max(ny + nz, 1.) < -cfg.RELTOL) { i.pinfres = hresx / std::max(ny + nz, 1.); i.has_pinfres = true; }
+        if (w.cx / std::max(nx, 1.) < -cfg.RELTOL) {
             i.dinfres = std::max(hresy / std::max(nx, 1.), hresz / std::max(nx + ns, 1.)); i.has_dinfres = true;
         }
     }
 
     /* ---------- ref checkExitConditions src/eicos.cpp:526-641 ---------- */
     int check_exit(bool reduced) {
-        const double feastol = reduced ? FEASTOL_INACC : FEASTOL;
-        const double abstol = reduced ? ABSTOL_INACC : ABSTOL;
-        const double reltol = reduced ? RELTOL_INACC : RELTOL;
+        const double feastol = reduced ? cfg.FEASTOL_INACC : cfg.FEASTOL;
+        const double abstol = reduced ? cfg.ABSTOL_INACC : cfg.ABSTOL;
+        const double reltol = reduced ? cfg.RELTOL_INACC : cfg.RELTOL;
         Info &i = w.i;
         /* optional<double> < double is true for nullopt (C++17) */
         const bool relgap_lt = !i.has_relgap || i.relgap < reltol;
@@ -835,7 +852,7 @@ struct Solver {
         w.i.step = 0.; w.i.step_aff = 0.; w.i.pinf = false; w.i.dinf = false;
         double pres_prev = std::numeric_limits<double>::max();
 
-        for (w.i.iter = 0; w.i.iter <= ITER_MAX; w.i.iter++) {
+        for (w.i.iter = 0; w.i.iter <= cfg.ITER_MAX; w.i.iter++) {
             compute_residuals();
             update_statistics();
             history.push_back({w.i.pcost, w.i.dcost, w.i.gap, w.i.pres, w.i.dres, w.i.kapovert, w.i.mu, w.i.step,
@@ -858,7 +875,7 @@ struct Solver {
                     code = check_exit(true);
                     if (code == EX_NOT_CONVERGED) code = EX_NUMERICS;
                     break;
-                } else if (w.i.iter == ITER_MAX) { /* ref :1083-1109 */
+                } else if (w.i.iter == cfg.ITER_MAX) { /* ref :1083-1109 */
                     if (!better_than(w.i, wbest.i)) w = wbest;
                     code = check_exit(true);
                     if (code == EX_NOT_CONVERGED) code = EX_MAXIT;
@@ -972,6 +989,56 @@ void oracle_set_dynamic_regularization(void *s, double delta, double eps) {
     for (const Cone &sc : S->cones) { S->ldl.sign[k + sc.dim + 1] = 1; k += sc.dim + 2; }
 }
 void oracle_destroy(void *s) { delete static_cast<Solver *>(s); }
+
+/* The ten settings, per solver, with the ranges and refusals of eicos_batch_set_settings (include/eicos_amd.h): the eight doubles
+ * finite and positive, iter_max in [1, 100] (oracle_get_trace's callers size their buffers for 100 passes), nitref in [0, 100].
+ * A refused struct changes nothing; the message names the field. */
+static thread_local char g_settings_error[96] = "";
+const char *oracle_last_error(void) { return g_settings_error; }
+void oracle_settings_default(oracle_settings *o) {
+    if (!o) return;
+    const Settings d;
+    *o = oracle_settings{d.FEASTOL, d.ABSTOL, d.RELTOL, d.FEASTOL_INACC, d.ABSTOL_INACC, d.RELTOL_INACC, d.LINSYSACC, d.IRERRFACT,
+                         d.ITER_MAX, d.NITREF};
+}
+int oracle_set_settings(void *sv, const oracle_settings *st) {
+    auto refuse = [](const char *field, const char *rule) {
+        std::snprintf(g_settings_error, sizeof g_settings_error, "settings: %s %s", field, rule);
+        return -1;
+    };
+    if (!sv) return refuse("NULL", "handle");
+    if (!st) return refuse("NULL", "struct");
+    const struct { const char *name; double v; } pos[] = {
+        {"feastol", st->feastol}, {"abstol", st->abstol}, {"reltol", st->reltol}, {"feastol_inacc", st->feastol_inacc},
+        {"abstol_inacc", st->abstol_inacc}, {"reltol_inacc", st->reltol_inacc}, {"linsysacc", st->linsysacc}, {"irerrfact", st->irerrfact}};
+    for (const auto &f : pos)
+        if (!(std::isfinite(f.v) && f.v > 0.)) return refuse(f.name, "must be finite and positive");
+    if (st->iter_max < 1 || st->iter_max > 100) return refuse("iter_max", "must lie in [1, 100]");
+    if (st->nitref < 0 || st->nitref > 100) return refuse("nitref", "must lie in [0, 100]");
+    Settings &c = static_cast<Solver *>(sv)->cfg;
+    c.FEASTOL = st->feastol; c.ABSTOL = st->abstol; c.RELTOL = st->reltol;
+    c.FEASTOL_INACC = st->feastol_inacc; c.ABSTOL_INACC = st->abstol_inacc; c.RELTOL_INACC = st->reltol_inacc;
+    c.LINSYSACC = st->linsysacc; c.IRERRFACT = st->irerrfact; c.ITER_MAX = st->iter_max; c.NITREF = st->nitref;
+    return 0;
+}
+int oracle_get_settings(void *sv, oracle_settings *o) {
+    if (!sv || !o) return -1;
+    const Settings &c = static_cast<Solver *>(sv)->cfg;
+    *o = oracle_settings{c.FEASTOL, c.ABSTOL, c.RELTOL, c.FEASTOL_INACC, c.ABSTOL_INACC, c.RELTOL_INACC, c.LINSYSACC, c.IRERRFACT,
+                         c.ITER_MAX, c.NITREF};
+    return 0;
+}
+
+/* Test hook: make every LDL solve of this solver deliberately wrong.  In the backward substitution only, the last stored entry of
+ * every column j of L with j % 7 == 3 (j in the factor's own order) is multiplied by 1 + rel; rel = 0 restores the clean sweep.
+ * Returns the number of entries that are scaled: 0 means the hook changes nothing on this pattern. */
+int oracle_debug_perturb_sweep(void *sv, double rel) {
+    Solver *S = static_cast<Solver *>(sv);
+    S->ldl.perturb = rel;
+    int hit = 0;
+    for (int j = 3; j < S->ldl.N; j += 7) hit += (S->ldl.Lp[j + 1] > S->ldl.Lp[j]) ? 1 : 0;
+    return hit;
+}
 
 /* Test hook: what solve() does at ref :1160-1162 for given (s, z): updateScalings (return value ignored) followed
  * by updateKKTScalings; V_out receives the scaling block of K in the slot order of ref cacheIndices :1944-1987.

@@ -51,6 +51,21 @@ void oracle_set_warm_start(void *s, double shift);
 /* N4 (not in the reference): ECOS-style dynamic regularisation of the LDL' pivots; delta = 0 switches it off */
 void oracle_set_dynamic_regularization(void *s, double delta, double eps);
 void oracle_destroy(void *s);
+
+/* The ten runtime settings: the fields, the order, the ranges and the refusals of struct eicos_settings (include/eicos_amd.h).  They are
+ * per solver and start at the reference's values (oracle_settings_default).  oracle_set_settings returns 0, or -1 with the solver
+ * unchanged and oracle_last_error() naming the refused field.  oracle_batch_solve always runs on the defaults. */
+typedef struct oracle_settings {
+    double feastol, abstol, reltol, feastol_inacc, abstol_inacc, reltol_inacc, linsysacc, irerrfact;
+    int iter_max, nitref;
+} oracle_settings;
+void oracle_settings_default(oracle_settings *out);
+int oracle_set_settings(void *s, const oracle_settings *in);
+int oracle_get_settings(void *s, oracle_settings *out);
+const char *oracle_last_error(void);
+/* test hook (tests/test_unrefined_solves.py): a deliberately wrong backward substitution -- the last stored entry of every column
+ * j % 7 == 3 of L is scaled by 1 + rel in every LDL solve of this solver; rel = 0 switches it off.  Returns how many entries that is. */
+int oracle_debug_perturb_sweep(void *s, double rel);
 /* test hooks: updateScalings + updateKKTScalings for a given (s, z) -> scaling block of K in cacheIndices order
  * (ref :411-479, :1691-1732, :1944-1987); the KKT matrix as it stands (upper CSC; returns nnz) */
 int oracle_debug_scalings(void *s, const double *s_in, const double *z_in, double *V_out);

@@ -14,6 +14,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 _LIB_NATIVE = None
+_LIB_FMA = None
 
 
 class OracleInfo(C.Structure):
@@ -25,6 +26,18 @@ class OracleInfo(C.Structure):
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class OracleSettings(C.Structure):
+    """struct oracle_settings: the fields and the order of eicos_amd.binding.Settings."""
+    _fields_ = [(k, C.c_double) for k in ("feastol", "abstol", "reltol", "feastol_inacc", "abstol_inacc", "reltol_inacc",
+                                          "linsysacc", "irerrfact")] + [("iter_max", C.c_int), ("nitref", C.c_int)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+SETTINGS_FIELDS = tuple(k for k, _ in OracleSettings._fields_)
 
 
 def build(force: bool = False) -> str:
@@ -55,6 +68,23 @@ def build_native() -> str | None:
     return so
 
 
+def build_fma() -> str | None:
+    """The same oracle with fused multiply-adds contracted (`-mfma -ffp-contract=fast`): a second, equally legitimate rounding of the
+    same arithmetic, used by the calibration of tests/test_unrefined_solves.py.  Built where it runs, like liboracle_native.so; None
+    when this CPU has no FMA (no `fma` flag in /proc/cpuinfo) or the compiler is missing."""
+    so = os.path.join(_HERE, "liboracle_fma.so")
+    src = os.path.join(_HERE, "eicos_oracle.cpp")
+    try:
+        flags = next((l for l in open("/proc/cpuinfo") if l.startswith("flags")), "")
+        if "fma" not in flags.split():
+            return None
+        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(os.path.join(_HERE, "eicos_oracle.h"))):
+            subprocess.check_call(["make", "-C", _HERE, "-B", "liboracle_fma.so"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    except (OSError, subprocess.CalledProcessError):
+        return None
+    return so
+
+
 def _prototype_batch(L):
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
     L.oracle_batch_solve.restype = C.c_double
@@ -72,34 +102,51 @@ def lib_native():
     return _LIB_NATIVE or None
 
 
+def lib_fma():
+    """liboracle_fma.so with every prototype of lib(), or None when it cannot be built here."""
+    global _LIB_FMA
+    if _LIB_FMA is None:
+        so = build_fma()
+        _LIB_FMA = _prototype(C.CDLL(so)) if so else False
+    return _LIB_FMA or None
+
+
 def lib():
     global _LIB
     if _LIB is None:
-        L = C.CDLL(build())
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
-        L.oracle_create.restype = C.c_void_p
-        L.oracle_create.argtypes = [C.c_int] * 5 + [ip, dp, ip, ip, dp, ip, ip, dp, dp, dp]
-        L.oracle_update.argtypes = [C.c_void_p, dp, dp, dp, dp, dp]
-        L.oracle_solve.argtypes = [C.c_void_p]
-        L.oracle_solve.restype = C.c_int
-        L.oracle_get_info.argtypes = [C.c_void_p, C.POINTER(OracleInfo)]
-        L.oracle_get_x.argtypes = [C.c_void_p, dp]
-        L.oracle_get_yzs.argtypes = [C.c_void_p, dp, dp, dp]
-        L.oracle_get_dims.argtypes = [C.c_void_p, ip, ip, ip]
-        L.oracle_destroy.argtypes = [C.c_void_p]
-        L.oracle_set_warm_start.argtypes = [C.c_void_p, C.c_double]
-        L.oracle_set_dynamic_regularization.argtypes = [C.c_void_p, C.c_double, C.c_double]
-        L.oracle_get_trace.argtypes = [C.c_void_p, dp, C.c_int]
-        L.oracle_get_trace.restype = C.c_int
-        L.oracle_debug_scalings.argtypes = [C.c_void_p, dp, dp, dp]
-        L.oracle_debug_scalings.restype = C.c_int
-        L.oracle_debug_kkt.argtypes = [C.c_void_p, ip, ip, dp]
-        L.oracle_debug_kkt.restype = C.c_int
-        L.oracle_batch_solve.restype = C.c_double
-        L.oracle_batch_solve.argtypes = [C.c_int] * 4 + [ip] * 5 + [C.c_int] + [dp] * 5 + [C.c_int, ip, ip, dp, dp, dp,
-                                                                                  C.POINTER(C.c_longlong)]
-        _LIB = L
+        _LIB = _prototype(C.CDLL(build()))
     return _LIB
+
+
+def _prototype(L):
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    L.oracle_create.restype = C.c_void_p
+    L.oracle_create.argtypes = [C.c_int] * 5 + [ip, dp, ip, ip, dp, ip, ip, dp, dp, dp]
+    L.oracle_update.argtypes = [C.c_void_p, dp, dp, dp, dp, dp]
+    L.oracle_solve.argtypes = [C.c_void_p]
+    L.oracle_solve.restype = C.c_int
+    L.oracle_get_info.argtypes = [C.c_void_p, C.POINTER(OracleInfo)]
+    L.oracle_get_x.argtypes = [C.c_void_p, dp]
+    L.oracle_get_yzs.argtypes = [C.c_void_p, dp, dp, dp]
+    L.oracle_get_dims.argtypes = [C.c_void_p, ip, ip, ip]
+    L.oracle_destroy.argtypes = [C.c_void_p]
+    L.oracle_set_warm_start.argtypes = [C.c_void_p, C.c_double]
+    L.oracle_set_dynamic_regularization.argtypes = [C.c_void_p, C.c_double, C.c_double]
+    L.oracle_get_trace.argtypes = [C.c_void_p, dp, C.c_int]
+    L.oracle_get_trace.restype = C.c_int
+    L.oracle_debug_scalings.argtypes = [C.c_void_p, dp, dp, dp]
+    L.oracle_debug_scalings.restype = C.c_int
+    L.oracle_debug_kkt.argtypes = [C.c_void_p, ip, ip, dp]
+    L.oracle_debug_kkt.restype = C.c_int
+    sp = C.POINTER(OracleSettings)
+    L.oracle_settings_default.argtypes = [sp]
+    L.oracle_settings_default.restype = None
+    L.oracle_set_settings.argtypes = [C.c_void_p, sp]
+    L.oracle_get_settings.argtypes = [C.c_void_p, sp]
+    L.oracle_last_error.restype = C.c_char_p
+    L.oracle_debug_perturb_sweep.argtypes = [C.c_void_p, C.c_double]
+    L.oracle_debug_perturb_sweep.restype = C.c_int
+    return _prototype_batch(L)
 
 
 def _dp(a):
@@ -113,9 +160,15 @@ def _ip(a):
 class OracleSolver:
     """Mirror of the reference's raw-pointer Solver API (include/eicos.hpp:151-163)."""
 
-    def __init__(self, pat, vals):
+    def __init__(self, pat, vals, fma: bool = False):
+        """fma=True: the solver lives in liboracle_fma.so (lib_fma(): the same source, contracted multiply-adds); RuntimeError
+        when that build is not available here."""
         self.pat = pat
-        L = lib()
+        self._h = None
+        L = lib_fma() if fma else lib()
+        if L is None:
+            raise RuntimeError("liboracle_fma.so cannot be built on this machine")
+        self._L = L
         self._keep = [np.ascontiguousarray(a) for a in (pat.q.astype(np.int32), pat.Gjc, pat.Gir, pat.Ajc, pat.Air)]
         q, Gjc, Gir, Ajc, Air = self._keep
         haveG = pat.m > 0
@@ -137,40 +190,64 @@ class OracleSolver:
 
     def update(self, vals):
         v = self._c(vals)
-        lib().oracle_update(self._h, _dp(v.Gpr), _dp(v.Apr), _dp(v.c), _dp(v.h), _dp(v.b))
+        self._L.oracle_update(self._h, _dp(v.Gpr), _dp(v.Apr), _dp(v.c), _dp(v.h), _dp(v.b))
 
     def solve(self) -> int:
-        return lib().oracle_solve(self._h)
+        return self._L.oracle_solve(self._h)
 
     def info(self) -> dict:
         o = OracleInfo()
-        lib().oracle_get_info(self._h, C.byref(o))
+        self._L.oracle_get_info(self._h, C.byref(o))
         return o.asdict()
 
     def x(self):
         x = np.zeros(max(self.pat.n, 1))
-        lib().oracle_get_x(self._h, _dp(x))
+        self._L.oracle_get_x(self._h, _dp(x))
         return x[: self.pat.n]
 
     def yzs(self):
         y, z, s = np.zeros(max(self.pat.p, 1)), np.zeros(max(self.pat.m, 1)), np.zeros(max(self.pat.m, 1))
-        lib().oracle_get_yzs(self._h, _dp(y), _dp(z), _dp(s))
+        self._L.oracle_get_yzs(self._h, _dp(y), _dp(z), _dp(s))
         return y[: self.pat.p], z[: self.pat.m], s[: self.pat.m]
 
     def set_warm_start(self, shift: float):
-        lib().oracle_set_warm_start(self._h, float(shift))
+        self._L.oracle_set_warm_start(self._h, float(shift))
 
     def set_dynamic_regularization(self, delta: float, eps: float):
-        lib().oracle_set_dynamic_regularization(self._h, float(delta), float(eps))
+        self._L.oracle_set_dynamic_regularization(self._h, float(delta), float(eps))
+
+    def set_settings(self, **fields):
+        """The ten runtime settings with the names, ranges and refusals of eicos_amd.BatchSolver.set_settings: fields that are not
+        named keep their value, an unknown name raises TypeError before the library is called, a refused value RuntimeError with the
+        solver's settings unchanged."""
+        unknown = sorted(set(fields) - set(SETTINGS_FIELDS))
+        if unknown:
+            raise TypeError(f"set_settings: unknown field(s) {', '.join(unknown)} (the settings are {', '.join(SETTINGS_FIELDS)})")
+        st = OracleSettings()
+        self._L.oracle_get_settings(self._h, C.byref(st))
+        for k, v in fields.items():
+            setattr(st, k, int(v) if k in ("iter_max", "nitref") else float(v))
+        if self._L.oracle_set_settings(self._h, C.byref(st)) != 0:
+            raise RuntimeError(self._L.oracle_last_error().decode())
+
+    def settings(self) -> dict:
+        st = OracleSettings()
+        self._L.oracle_get_settings(self._h, C.byref(st))
+        return st.asdict()
+
+    def perturb_sweep(self, rel: float) -> int:
+        """Test hook oracle_debug_perturb_sweep: every LDL solve from now on scales the last stored entry of every column j % 7 == 3
+        of L by 1 + rel in the backward substitution (rel = 0: off).  Returns the number of entries concerned."""
+        return self._L.oracle_debug_perturb_sweep(self._h, float(rel))
 
     def trace(self):
         out = np.zeros((102, 12))
-        n = lib().oracle_get_trace(self._h, _dp(out), 102)
+        n = self._L.oracle_get_trace(self._h, _dp(out), 102)
         return out[:n]
 
     def dims(self):
         a, b, c = C.c_int(), C.c_int(), C.c_int()
-        lib().oracle_get_dims(self._h, C.byref(a), C.byref(b), C.byref(c))
+        self._L.oracle_get_dims(self._h, C.byref(a), C.byref(b), C.byref(c))
         return dict(dimK=a.value, nnzK=b.value, nnzL=c.value)
 
     def debug_scalings(self, s, z):
@@ -179,19 +256,19 @@ class OracleSolver:
         nV = pat.l + int(sum(3 * int(d) + 1 for d in pat.q))
         s, z = np.ascontiguousarray(s, np.float64), np.ascontiguousarray(z, np.float64)
         V = np.zeros(max(nV, 1))
-        ok = lib().oracle_debug_scalings(self._h, _dp(s), _dp(z), _dp(V))
+        ok = self._L.oracle_debug_scalings(self._h, _dp(s), _dp(z), _dp(V))
         return bool(ok), V[:nV]
 
     def debug_kkt(self):
         """Upper triangle of the KKT matrix as it stands (CSC: ptr, idx, val), reference column layout."""
         d = self.dims()
         Kp, Ki, Kx = np.zeros(d["dimK"] + 1, np.int32), np.zeros(max(d["nnzK"], 1), np.int32), np.zeros(max(d["nnzK"], 1))
-        nnz = lib().oracle_debug_kkt(self._h, _ip(Kp), _ip(Ki), _dp(Kx))
+        nnz = self._L.oracle_debug_kkt(self._h, _ip(Kp), _ip(Ki), _dp(Kx))
         return Kp, Ki[:nnz], Kx[:nnz]
 
     def close(self):
         if self._h:
-            lib().oracle_destroy(self._h)
+            self._L.oracle_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -199,6 +276,12 @@ class OracleSolver:
             self.close()
         except Exception:
             pass
+
+
+def default_settings() -> dict:
+    st = OracleSettings()
+    lib().oracle_settings_default(C.byref(st))
+    return st.asdict()
 
 
 def batch_solve(pat, Gpr, Apr, c, h, b, nthreads: int, want_x: bool = False, native: bool = False):

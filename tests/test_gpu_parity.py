@@ -164,18 +164,24 @@ def test_dense_front_socp():
     _check_batch(pat, feasible_batch(pat, base, 0, 6), 6, 6, x_rtol=1e-6)
 
 
-@pytest.mark.parametrize("env", [{"EICOS_NLDS": "0"}, {"EICOS_NLDS": "1"}, {"EICOS_NLDS": "2"}, {"EICOS_THREADS": "128"},
-                                 {"EICOS_THREADS": "256"}, {"EICOS_THREADS": "512"}, {"EICOS_IDX16": "0"}, {"EICOS_IDX16": "0", "EICOS_NLDS": "0"},
-                                 {"EICOS_TILES": "1"}, {"EICOS_TILES": "1", "EICOS_NLDS": "0"}, {"EICOS_TILES": "1", "EICOS_THREADS": "128", "EICOS_NLDS": "2"},
-                                 {"EICOS_TILES": "1", "EICOS_THREADS": "256", "EICOS_NLDS": "1"},
-                                 {"EICOS_NLDS": "1", "EICOS_DUAL": "0"}, {"EICOS_NLDS": "1", "EICOS_DUAL": "0", "EICOS_TILES": "2", "EICOS_THREADS": "256"},
-                                 {"EICOS_W2": "0", "EICOS_THREADS": "256"}, {"EICOS_W2": "1", "EICOS_THREADS": "256", "EICOS_NLDS": "0"},
-                                 {"EICOS_FAC_DEFER": "0"}, {"EICOS_FAC_DEFER": "1", "EICOS_TILES": "2"}, {"EICOS_FAC_DEFER": "1", "EICOS_IDX16": "0", "EICOS_TILES": "0"},
-                                 {"EICOS_FAC_DEFER": "1", "EICOS_LDSRES": "0", "EICOS_THREADS": "128", "EICOS_NLDS": "1"},
-                                 {"EICOS_LDSRES": "0"}, {"EICOS_LDSRES": "0", "EICOS_THREADS": "128", "EICOS_TILES": "0"},
-                                 {"EICOS_TILES": "1", "EICOS_GTILES": "2"}, {"EICOS_TILES": "1", "EICOS_GTILES": "2", "EICOS_DUAL": "0", "EICOS_THREADS": "256"},
-                                 {"EICOS_TILES": "1", "EICOS_GTILES": "0"},
-                                 {"EICOS_TILES": "0"}, {"EICOS_TILES": "2", "EICOS_NLDS": "0"}, {"EICOS_TILES": "2", "EICOS_THREADS": "128"}, {"EICOS_TILES": "2", "EICOS_THREADS": "512", "EICOS_IDX16": "0"}])
+# the environment sets that force each build of the solve kernel (test_every_kernel_variant_matches_oracle; tests/test_unrefined_solves.py
+# runs the same list), and the fixtures they are driven through
+KERNEL_VARIANT_ENVS = [{"EICOS_NLDS": "0"}, {"EICOS_NLDS": "1"}, {"EICOS_NLDS": "2"}, {"EICOS_THREADS": "128"},
+                       {"EICOS_THREADS": "256"}, {"EICOS_THREADS": "512"}, {"EICOS_IDX16": "0"}, {"EICOS_IDX16": "0", "EICOS_NLDS": "0"},
+                       {"EICOS_TILES": "1"}, {"EICOS_TILES": "1", "EICOS_NLDS": "0"}, {"EICOS_TILES": "1", "EICOS_THREADS": "128", "EICOS_NLDS": "2"},
+                       {"EICOS_TILES": "1", "EICOS_THREADS": "256", "EICOS_NLDS": "1"},
+                       {"EICOS_NLDS": "1", "EICOS_DUAL": "0"}, {"EICOS_NLDS": "1", "EICOS_DUAL": "0", "EICOS_TILES": "2", "EICOS_THREADS": "256"},
+                       {"EICOS_W2": "0", "EICOS_THREADS": "256"}, {"EICOS_W2": "1", "EICOS_THREADS": "256", "EICOS_NLDS": "0"},
+                       {"EICOS_FAC_DEFER": "0"}, {"EICOS_FAC_DEFER": "1", "EICOS_TILES": "2"}, {"EICOS_FAC_DEFER": "1", "EICOS_IDX16": "0", "EICOS_TILES": "0"},
+                       {"EICOS_FAC_DEFER": "1", "EICOS_LDSRES": "0", "EICOS_THREADS": "128", "EICOS_NLDS": "1"},
+                       {"EICOS_LDSRES": "0"}, {"EICOS_LDSRES": "0", "EICOS_THREADS": "128", "EICOS_TILES": "0"},
+                       {"EICOS_TILES": "1", "EICOS_GTILES": "2"}, {"EICOS_TILES": "1", "EICOS_GTILES": "2", "EICOS_DUAL": "0", "EICOS_THREADS": "256"},
+                       {"EICOS_TILES": "1", "EICOS_GTILES": "0"},
+                       {"EICOS_TILES": "0"}, {"EICOS_TILES": "2", "EICOS_NLDS": "0"}, {"EICOS_TILES": "2", "EICOS_THREADS": "128"}, {"EICOS_TILES": "2", "EICOS_THREADS": "512", "EICOS_IDX16": "0"}]
+KERNEL_VARIANT_FIXTURES = ("lp_bandm", "issue98", "infeasible1", "update_data")
+
+
+@pytest.mark.parametrize("env", KERNEL_VARIANT_ENVS)
 def test_every_kernel_variant_matches_oracle(env, monkeypatch):
     # the launch shape is chosen per pattern/batch; force each template instantiation (KKT vectors in LDS
     # or in the workspace slab, 128/256/512 threads, 16-/32-bit gather indices, and the tile (dense-front) factor/solve
