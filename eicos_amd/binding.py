@@ -70,6 +70,14 @@ class Settings(C.Structure):
 SETTINGS_FIELDS = tuple(k for k, _ in Settings._fields_)
 
 
+class Retry(C.Structure):
+    """struct eicos_retry: the retry policy of a handle (a second attempt inside the solve launch for the exit classes of `mask`)."""
+    _fields_ = [("mask", C.c_uint), ("warm", C.c_double), ("dyn_delta", C.c_double), ("dyn_eps", C.c_double), ("settings", Settings)]
+
+    def asdict(self):
+        return {"mask": int(self.mask), "warm": self.warm, "dyn": (self.dyn_delta, self.dyn_eps), "settings": self.settings.asdict()}
+
+
 def library_path() -> str:
     # EICOS_AMD_LIB: alternative build of the same library (used by tuning sweeps only)
     return os.environ.get("EICOS_AMD_LIB") or os.path.join(_HERE, "libeicos_amd.so")
@@ -183,6 +191,19 @@ def _lib():
             for f in ("set_settings", "get_settings"):
                 getattr(L, "eicos_batch_" + f).argtypes = getattr(L, "eicos_multi_" + f).argtypes = [vp, sp]
                 getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+        if hasattr(L, "eicos_batch_set_retry"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            rp = C.POINTER(Retry)
+            L.eicos_retry_default.argtypes = [rp]
+            L.eicos_retry_default.restype = None
+            L.eicos_retry_size.argtypes = []
+            L.eicos_retry_size.restype = C.c_size_t
+            if L.eicos_retry_size() != C.sizeof(Retry):
+                raise RuntimeError(f"{path}: struct eicos_retry has {L.eicos_retry_size()} bytes, the ctypes mirror {C.sizeof(Retry)}")
+            for f in ("set_retry", "get_retry"):
+                getattr(L, "eicos_batch_" + f).argtypes = getattr(L, "eicos_multi_" + f).argtypes = [vp, rp]
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+            L.eicos_batch_retry_counts.argtypes = L.eicos_multi_retry_counts.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int]
+            L.eicos_batch_retry_counts.restype = L.eicos_multi_retry_counts.restype = C.c_int
         if hasattr(L, "eicos_batch_solve_subset"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
             L.eicos_exit_class.argtypes = [C.c_int, C.c_int]
             L.eicos_exit_class.restype = C.c_int
@@ -273,6 +294,13 @@ def default_settings() -> dict:
     st = Settings()
     _lib().eicos_settings_default(C.byref(st))
     return st.asdict()
+
+
+def default_retry() -> dict:
+    """The retry policy that is no policy (eicos_retry_default: mask 0, cold, no regularisation, default settings); needs no GPU."""
+    r = Retry()
+    _lib().eicos_retry_default(C.byref(r))
+    return r.asdict()
 
 
 def exit_class(exitcode: int, n_factor: int = 1) -> int:
@@ -937,6 +965,39 @@ class _Solver:
         st = Settings()
         self._call("get_settings", C.byref(st))
         return st.asdict()
+
+    # ---- retry policy: a second attempt inside the solve launch (include/eicos_amd.h: eicos_retry) ----
+    def set_retry(self, mask=None, warm: float = 0.0, dyn=(0.0, 0.0), **settings_fields):
+        """An instance whose solve ends in an exit class of `mask` (an OR of SEL_* bits) is solved once more inside the same launch --
+        every launch of the handle, the steps of a one-launch rollout included -- before anything reads its result.  The second
+        attempt runs cold (warm = 0) or warm-started where its record allows it, under dyn = (delta, eps) and under the DEFAULT
+        settings with the named fields changed (the names of set_settings).  mask None or 0 removes the policy.  An unknown field
+        raises TypeError before the library is called, a refused value RuntimeError with the policy unchanged."""
+        unknown = sorted(set(settings_fields) - set(SETTINGS_FIELDS))
+        if unknown:
+            raise TypeError(f"set_retry: unknown field(s) {', '.join(unknown)} (the settings are {', '.join(SETTINGS_FIELDS)})")
+        if not mask:
+            self._call("set_retry", None)
+            return
+        r = Retry()
+        _lib().eicos_retry_default(C.byref(r))
+        r.mask, r.warm, r.dyn_delta, r.dyn_eps = int(mask), float(warm), float(dyn[0]), float(dyn[1])
+        for k, v in settings_fields.items():
+            setattr(r.settings, k, int(v) if k in ("iter_max", "nitref") else float(v))
+        self._call("set_retry", C.byref(r))
+
+    def retry(self) -> dict:
+        """The installed policy: {"mask", "warm", "dyn": (delta, eps), "settings": {...}}; mask 0 = none."""
+        r = Retry()
+        self._call("get_retry", C.byref(r))
+        return r.asdict()
+
+    def retry_counts(self, reset: bool = False):
+        """Per instance the second attempts it has run since its counter was last reset (cumulative: after a rollout, its retried
+        steps); reset=True zeroes the counters after reading them."""
+        out = np.zeros(self.batch, np.int32)
+        self._call("retry_counts", 0, self.batch, _ip(out), 1 if reset else 0)
+        return out
 
     # ---- results ----
     def solution(self):

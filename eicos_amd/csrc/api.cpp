@@ -179,7 +179,11 @@ struct eicos_batch {
     // shift map (eicos_batch_set_shift_map): one device allocation [ShiftMapDev (MAP_HEADER bytes) | base, val | rowptr, col]; every solve
     // launch of the handle carries its address (UpdArgs::smap), d_shift empty while none is installed
     ShiftMapDev shift{}; DevBuf d_shift;
-    TilePlan tiles;        // tile mode (Symbolic::tile): the dense-front plan
+    // retry policy (eicos_batch_set_retry): one device allocation [RetryDev (MAP_HEADER bytes) | counts [batch]], made by the first policy
+    // and kept; retry = the host copy of the record (its source for the copy on the handle's stream), retry.mask = 0 while no policy is
+    // installed -- then no launch carries the record's address (UpdArgs::retry)
+    RetryDev retry{0u, 0., 0., 0., solve_cfg_default(), nullptr}; DevBuf d_retry;
+    TilePlan tiles;       // tile mode (Symbolic::tile): the dense-front plan
     // Shared product values (eicos_batch_shared_values): ONE device word.  -1: every instance streams the product values of
     // its own slab.  0: the last writer of matrix values was a full updateData over [0, batch) from arrays the GPU addresses, and its
     // kernel found every row of Gpr / Apr bit-identical to row 0 -- the solve's products then all stream instance 0's copies.  ONE place
@@ -1210,6 +1214,76 @@ int eicos_batch_get_settings(eicos_batch *h, eicos_settings *out) {
     return EICOS_OK;
 }
 
+// ---- retry policy (include/eicos_amd.h: eicos_retry; launch.hpp: RetryDev) ----
+static_assert(sizeof(RetryDev) <= MAP_HEADER, "the retry record larger than its header");
+static eicos_settings settings_from(const SolveCfg &c) {
+    return eicos_settings{c.feastol, c.abstol, c.reltol, c.feastol_inacc, c.abstol_inacc, c.reltol_inacc, c.linsysacc, c.irerrfact, c.iter_max, c.nitref};
+}
+void eicos_retry_default(eicos_retry *out) {
+    if (!out) return;
+    *out = eicos_retry{0u, 0., 0., 0., settings_from(solve_cfg_default())};
+}
+size_t eicos_retry_size(void) { return sizeof(eicos_retry); }
+
+// the counters of the handle's retry record, behind its header
+static int *retry_counts_dev(const eicos_batch *h) { return reinterpret_cast<int *>(h->d_retry.as<char>() + MAP_HEADER); }
+
+int eicos_batch_set_retry(eicos_batch *h, const eicos_retry *r) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    RetryDev next{0u, 0., 0., 0., solve_cfg_default(), h->retry.counts};
+    if (r && r->mask != 0) {
+        if (r->mask & ~(unsigned)EICOS_SEL_ALL) return fail(EICOS_E_INVALID, "retry: mask has bits above bit 11 (EICOS_SEL_UNSOLVED)");
+        // (beside other classes the bit is idle and accepted: EICOS_SEL_NOT_OPTIMAL, the mask of most policies, holds it)
+        if (r->mask == EICOS_SEL_UNSOLVED) return fail(EICOS_E_INVALID, "retry: mask is EICOS_SEL_UNSOLVED alone, and an attempted instance is never in that class");
+        if (!(r->warm >= 0.)) return fail(EICOS_E_INVALID, "retry: warm must be >= 0");
+        if (!(r->dyn_delta >= 0.) || !(r->dyn_eps >= 0.)) return fail(EICOS_E_INVALID, "retry: dyn_delta and dyn_eps must be >= 0");
+        std::string msg;
+        if (settings_fault(r->settings, msg)) return fail(EICOS_E_INVALID, "retry: " + msg);
+        const eicos_settings &s = r->settings;
+        next.mask = r->mask; next.warm = r->warm; next.dyn_delta = r->dyn_delta; next.dyn_eps = r->dyn_eps;
+        next.cfg = SolveCfg{s.feastol, s.abstol, s.reltol, s.feastol_inacc, s.abstol_inacc, s.reltol_inacc, s.linsysacc, s.irerrfact, s.iter_max, s.nitref};
+    }
+    if (next.mask == 0 && !h->d_retry) { h->retry = next; return EICOS_OK; } // (no policy before, none now: nothing on the GPU)
+    HIP_TRY(hipSetDevice(h->device));
+    if (!h->d_retry) { // the first policy of the handle: the record and the counters, zeroed
+        DevBuf dev;
+        HIP_TRY_AS("hipMalloc", dev.alloc(MAP_HEADER + (size_t)h->batch * sizeof(int)));
+        HIP_TRY(hipMemsetAsync(dev.p, 0, dev.bytes, h->stream));
+        h->d_retry = std::move(dev);
+        next.counts = retry_counts_dev(h);
+    }
+    // (on the handle's stream, behind every launch that is enqueued: those keep the record they were enqueued with; a launch enqueued
+    // while the mask is 0 does not carry the record's address at all)
+    h->retry = next;
+    HIP_TRY(hipMemcpyAsync(h->d_retry.p, &h->retry, sizeof(RetryDev), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream)); // (the source is a member: the copy has left it when the call returns)
+    return EICOS_OK;
+}
+
+int eicos_batch_get_retry(eicos_batch *h, eicos_retry *out) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (!out) return fail(EICOS_E_INVALID, "retry: NULL struct");
+    const RetryDev &r = h->retry;
+    *out = eicos_retry{r.mask, r.warm, r.dyn_delta, r.dyn_eps, settings_from(r.cfg)};
+    return EICOS_OK;
+}
+
+int eicos_batch_retry_counts(eicos_batch *h, int first, int count, int *retries, int reset) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (first < 0 || count < 0 || first > h->batch - count) return fail(EICOS_E_INVALID, "retry counts: instance range out of bounds");
+    if (count > 0 && !retries) return fail(EICOS_E_INVALID, "retry counts: retries is NULL");
+    if (count == 0) return EICOS_OK;
+    if (!h->d_retry) { std::fill(retries, retries + count, 0); return EICOS_OK; } // (never had a policy: nothing was retried)
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(retries, retry_counts_dev(h) + first, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    if (reset) {
+        HIP_TRY(hipMemsetAsync(retry_counts_dev(h) + first, 0, (size_t)count * sizeof(int), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return EICOS_OK;
+}
+
 int eicos_batch_set_stream(eicos_batch *h, void *hip_stream) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
@@ -1865,6 +1939,7 @@ static int enqueue_solve(eicos_batch *h, const UpdArgs *step, int subset = -1) {
     UpdArgs args = step ? *step : UpdArgs{};
     // (a shift map and the shared-values word travel with EVERY launch, the ones without a fused update included: instance_begin reads them)
     args.smap = h->d_shift.as<const ShiftMapDev>();
+    args.retry = h->retry.mask ? h->d_retry.as<const RetryDev>() : nullptr; // (eicos_batch_set_retry: every launch of the handle, like the shift map)
     if (writes_matrix_values(args)) { const int rc = shared_clear(h); if (rc != EICOS_OK) return rc; } // (the step drops the shared values)
     args.shared = h->shared_on ? h->d_shared.as<int>() : nullptr;
     SolveLaunch L = solve_launch(h, subset);

@@ -170,6 +170,11 @@ struct alignas(16) Sh : ShI {
     // a parametric step over a chosen subset (UpdArgs::rows_at, set by k_solve once): the row map starts at queue[rows_at]; 0: row = instance.
     // Kept here (in what was padding) and read by list_row, so that k_solve's loop is the same code with and without a list.
     int rows_at;
+    // a retry policy (UpdArgs::retry; retry_between): attempt = 1 while the instance's second attempt runs; swapped = cfg, dyn_delta and
+    // dyn_eps above hold the policy's values, not the launch's (thread 0 only); rwarm = the policy's warm-start shift, read by every
+    // thread in front of the second attempt.  Kept here like `step`: k_solve carries no attempt state in registers across its stages.
+    int attempt, swapped;
+    double rwarm;
 };
 constexpr int KI_MAX = 2; // right-hand sides of a dual solve (kkt_solve<..., 2, true>)
 enum { TK_FACTOR = 0, TK_LDL, TK_KRES, TK_KPOST, TK_RESID, TK_FWD, TK_COUNT, TK_FA = 8, TK_FW1, TK_FB, TK_FW2 }; // 8..11: inside the factor
@@ -3503,6 +3508,27 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_ste
     }
 }
 
+// Between the attempts of an instance under a retry policy (k_solve with UpdArgs::retry, behind solve_instance and its barrier; the
+// instance's final record is in g_S.wi).  After the FIRST attempt thread 0 takes the exit class of the record: if it is in the policy's
+// mask it bumps the instance's counter -- a plain store: this workgroup owns the instance --, puts the policy's settings in the place of
+// the launch's (g_S.cfg, dyn_delta, dyn_eps; k_solve brings the launch's back behind the loop) and marks the second attempt.  After the
+// second attempt it only clears the mark: there is never a third.  Returns 1 when another attempt follows, the same value in every
+// thread (behind a barrier, which also stands between the swap and the next instance_begin).  The record is read here, on the rare path.
+static __device__ __noinline__ __attribute__((not_tail_called)) int retry_between(const RetryDev *Rp, int id) {
+    Rp = uni_ptr(Rp); id = uni(id);
+    if (threadIdx.x == 0) {
+        const int again = !g_S.attempt && (exit_class(g_S.wi.exitcode, g_S.wi.n_factor) & Rp->mask) != 0;
+        if (again) {
+            Rp->counts[id] = Rp->counts[id] + 1;
+            g_S.cfg = Rp->cfg; g_S.dyn_delta = Rp->dyn_delta; g_S.dyn_eps = Rp->dyn_eps; g_S.rwarm = Rp->warm;
+            g_S.swapped = 1;
+        }
+        g_S.attempt = again;
+    }
+    __syncthreads();
+    return uni(g_S.attempt);
+}
+
 template <int T, int NLDS, bool I16>
 __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     int ps, double *inst, double *work, int B, int *queue, const int *order, double warm, double dyn_delta, double dyn_eps, SolveCfg cfg, UpdArgs upd) {
@@ -3532,7 +3558,7 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     for (int q = threadIdx.x; q < P.ub_len; q += T) g_dyn[P.ub_lds + q] = 0.;
     __syncthreads();
 #endif
-    if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.cfg = cfg; g_S.step = 0; g_S.next = (int)blockIdx.x; g_S.smap = upd.smap; if constexpr (NLDS == 0) g_S.rows_at = 0; } // (next: the instance that is running)
+    if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.cfg = cfg; g_S.step = 0; g_S.next = (int)blockIdx.x; g_S.smap = upd.smap; g_S.attempt = 0; g_S.swapped = 0; if constexpr (NLDS == 0) g_S.rows_at = 0; } // (next: the instance that is running)
     if constexpr (NLDS >= 1) { if (threadIdx.x == 0) { g_S.roll = upd.roll; g_S.pmap = upd.pmap; g_S.omap = upd.omap; g_S.mmap = upd.mmap; } }
     // Instances differ in iteration count (12..18 on the headline batch): after its first instance (= its own index, so
     // that workspace slot g holds the history of instance g when the batch fits the grid) a workgroup pulls the next
@@ -3581,8 +3607,15 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
             g_S.vshared = ref >= 0;
         }
 #endif
-        solve_instance<T, NLDS, I16>(ps, I, W, warm);
-        __syncthreads();
+        // At most two attempts (launch.hpp: UpdArgs::retry): the second only under a policy whose mask holds the class the first ended in,
+        // with the policy's settings and warm-start shift (retry_between).  Nothing has read the first result by then; the fused update
+        // above ran once.  Behind the loop the launch's own settings come back for the next instance.
+        for (double wshift = warm;; wshift = g_S.rwarm) {
+            solve_instance<T, NLDS, I16>(ps, I, W, wshift);
+            __syncthreads();
+            if (!upd.retry || !retry_between(upd.retry, id)) break;
+        }
+        if (upd.retry) { if (threadIdx.x == 0 && g_S.swapped) { g_S.cfg = cfg; g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.swapped = 0; } }
         if (upd.x) solution_instance<T>(ps, I, (size_t)id, upd.x); // (fused path: the result straight to the caller's array)
         if (upd.u) outputs_instance<T>(ps, I, (size_t)id, upd.omap, upd.u); // (the selected outputs of x, r doubles, likewise)
         // A rollout keeps the instance for its next step (rollout_step: the step's u row and records, the plant map, the step counter) and

@@ -42,6 +42,7 @@ struct MatrixMapDev { int k; AffineDev g[2]; };
 // Shift map (eicos_batch_set_shift_map): the warm-start vectors x, y, z, s of an instance through one square affine map each -- g[0..3] with
 // n, p, m, m rows and as many columns, CSR, in device memory, shared by every instance; base == NULL: that vector is not shifted
 struct ShiftMapDev { AffineDev g[4]; };
+struct RetryDev; // (below, behind SolveCfg)
 struct UpdArgs { // UpdArgs{} = the neutral launch: no fused step, no maps; every builder assigns fields by name
     // inputs: rows of the five updateData arrays, [batch][...]
     const double *G = nullptr, *A = nullptr, *c = nullptr, *h = nullptr, *b = nullptr;
@@ -57,6 +58,10 @@ struct UpdArgs { // UpdArgs{} = the neutral launch: no fused step, no maps; ever
     // every-launch fields, mode 0 included.  smap: a solve that warm-starts an instance first takes its x, y, z, s through this map
     // (kernels.hip: shift_instance); NULL: no shift map.  One more word of kernel arguments, and one pointer test per instance.
     const ShiftMapDev *smap = nullptr;
+    // retry: the handle's retry policy (eicos_batch_set_retry), a record in device memory; NULL: none.  An instance whose solve ends in a
+    // class of the policy's mask is solved once more by the same workgroup, under the policy's settings, before anything reads its result
+    // (kernels.hip: retry_between).  One more word of kernel arguments, and one pointer test per instance.
+    const RetryDev *retry = nullptr;
     // shared: the handle's shared-values word (eicos_batch_shared_values), read by thread 0 once per instance before the
     // instance's solve.  -1: every instance streams the product values (the sliced-ELL copies of [A' G'], A, G and the G tiles) of its own
     // slab; r >= 0: every instance of the batch holds the bits of instance r there, and all of them stream instance r's.  NULL counts as -1.
@@ -71,6 +76,11 @@ inline bool writes_matrix_values(const UpdArgs &a) { return a.on == UPD_FULL || 
 // (linsysacc, irerrfact, nitref).  Every other constant of the reference's Settings stays compile-time (kernels.hip).
 struct SolveCfg { double feastol, abstol, reltol, feastol_inacc, abstol_inacc, reltol_inacc, linsysacc, irerrfact; int iter_max, nitref; };
 constexpr SolveCfg solve_cfg_default() { return {1e-8, 1e-8, 1e-8, 1e-4, 5e-5, 5e-5, 1e-14, 6., 100, 9}; }
+// Retry policy (eicos_batch_set_retry; eicos_retry of include/eicos_amd.h), in device memory, one per handle: mask = the exit classes
+// (exit_class.hpp) of a first attempt that trigger the second; warm, dyn_delta, dyn_eps, cfg = what the second attempt runs under in
+// place of the launch's own values; counts [batch] = second attempts per instance since the last reset, bumped by the workgroup that
+// owns the instance.  The host rewrites the record on the handle's stream, so a launch in flight keeps the policy it was enqueued with.
+struct RetryDev { unsigned mask; double warm, dyn_delta, dyn_eps; SolveCfg cfg; int *counts; };
 // One k_solve launch of a handle, as the host describes it: the pattern slot, the slabs and the queue, the launch shape, and what travels
 // to the kernel by value.  order = the longest-first order array (used when B > order_min); cfg is copied into the kernel arguments, so
 // a launch in flight keeps the settings it was enqueued with.

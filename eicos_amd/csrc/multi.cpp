@@ -612,6 +612,27 @@ int eicos_multi_get_settings(eicos_multi *mh, eicos_settings *out) {
     return rc != EICOS_OK ? mfail(rc, eicos_last_error()) : EICOS_OK;
 }
 
+// retry policy (validation does not depend on the shard either: every shard refuses what any would, before it has changed anything; the
+// record is written on each shard's own stream, so on the shard's host thread like the maps)
+int eicos_multi_set_retry(eicos_multi *mh, const eicos_retry *r) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    return for_shards(mh, [&](int s) { return eicos_batch_set_retry(mh->shard[s], r); });
+}
+
+int eicos_multi_get_retry(eicos_multi *mh, eicos_retry *out) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    const int rc = eicos_batch_get_retry(mh->shard[0], out);
+    return rc != EICOS_OK ? mfail(rc, eicos_last_error()) : EICOS_OK;
+}
+
+int eicos_multi_retry_counts(eicos_multi *mh, int first, int count, int *retries, int reset) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    if (count > 0 && !retries) return mfail(EICOS_E_INVALID, "retry counts: retries is NULL");
+    return for_range(mh, first, count, [&](int s, int f, int cnt, size_t off) {
+        return eicos_batch_retry_counts(mh->shard[s], f, cnt, retries + off, reset);
+    });
+}
+
 int eicos_multi_last_solve_ms(eicos_multi *mh, float *ms_max, float *per_shard) {
     if (!mh || !ms_max) return mfail(EICOS_E_INVALID, "NULL argument");
     *ms_max = 0.f;

@@ -102,6 +102,29 @@ namespace EiCOS
         }
     };
 
+    // Extension: the retry policy of a handle (eicos_retry of eicos_amd.h: contract and refusals there).  An instance whose solve ends in
+    // an exit class of `mask` (an OR of EiCOS::sel values) is solved once more INSIDE the same launch, under `settings`, `warm` (0 = cold,
+    // the default) and the dynamic regularisation given here, before anything reads its result.  mask 0 = no policy.
+    struct Retry
+    {
+        unsigned mask = 0;
+        double warm = 0., dyn_delta = 0., dyn_eps = 0.;
+        Settings settings;
+
+        eicos_retry to_c() const { return eicos_retry{mask, warm, dyn_delta, dyn_eps, settings.to_c()}; }
+        static Retry from(const eicos_retry &c)
+        {
+            Retry r;
+            r.mask = c.mask; r.warm = c.warm; r.dyn_delta = c.dyn_delta; r.dyn_eps = c.dyn_eps;
+            r.settings.feastol = c.settings.feastol; r.settings.abstol = c.settings.abstol; r.settings.reltol = c.settings.reltol;
+            r.settings.feastol_inacc = c.settings.feastol_inacc; r.settings.abstol_inacc = c.settings.abstol_inacc;
+            r.settings.reltol_inacc = c.settings.reltol_inacc; r.settings.linsysacc = c.settings.linsysacc;
+            r.settings.irerrfact = c.settings.irerrfact; r.settings.iter_max = (size_t)c.settings.iter_max;
+            r.settings.nitref = (size_t)c.settings.nitref;
+            return r;
+        }
+    };
+
     struct Information // reference include/eicos.hpp:49-73
     {
         double pcost = 0, dcost = 0, pres = 0, dres = 0;
@@ -284,6 +307,26 @@ namespace EiCOS
             eicos_settings c;
             mcheck(eicos_multi_get_settings(h_, &c), "eicos_multi_get_settings");
             return Settings::from(c);
+        }
+        // Retry policy (Retry, above), on every shard: in effect from the next solve, solveSubset, stepParam or rollout -- also between the
+        // steps of a one-launch rollout.  Retry{} (mask 0) removes it.  A refused value throws and changes nothing.
+        // retryCounts: per instance the second attempts since the counters were last reset (cumulative over launches and rollout steps).
+        void setRetry(const Retry &r)
+        {
+            const eicos_retry c = r.to_c();
+            mcheck(eicos_multi_set_retry(h_, &c), "eicos_multi_set_retry");
+        }
+        Retry retry() const
+        {
+            eicos_retry c;
+            mcheck(eicos_multi_get_retry(h_, &c), "eicos_multi_get_retry");
+            return Retry::from(c);
+        }
+        std::vector<int> retryCounts(bool reset = false)
+        {
+            std::vector<int> out(batch_);
+            mcheck(eicos_multi_retry_counts(h_, 0, batch_, out.data(), reset ? 1 : 0), "eicos_multi_retry_counts");
+            return out;
         }
         std::vector<exitcode> solve()
         {
@@ -534,6 +577,13 @@ namespace EiCOS
         // Extension (not in the reference, which cold-starts every solve): warm-start the next solves after updateData
         void setWarmStart(double shift) { eicos_batch_set_warm_start(h_, shift); }
         void setDynamicRegularization(double delta, double eps) { eicos_batch_set_dynamic_regularization(h_, delta, eps); }
+        // Extension: the retry policy (Retry, above): a solve() that ends in a class of r.mask runs once more inside the same launch.
+        // false: refused, eicos_last_error() names the cause
+        bool setRetry(const Retry &r)
+        {
+            const eicos_retry c = r.to_c();
+            return eicos_batch_set_retry(h_, &c) == EICOS_OK;
+        }
 
     private:
         eicos_batch *h_ = nullptr;

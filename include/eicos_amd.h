@@ -510,6 +510,45 @@ size_t eicos_settings_size(void);                     /* sizeof(eicos_settings),
 int eicos_batch_set_settings(eicos_batch *hd, const eicos_settings *s);
 int eicos_batch_get_settings(eicos_batch *hd, eicos_settings *out);
 
+/* ---- retry policy: a second attempt INSIDE the solve launch (no reference counterpart).  The solve kernel is a persistent workgroup per
+ * instance; with a policy installed, a workgroup whose instance ends in an exit class of `mask` (EICOS_SEL_*, above) solves the same
+ * instance once more, under the policy's own settings, before anything reads the result: the x row and the output row of a fused step,
+ * the records and the plant map of a rollout step, the pull of the workgroup's next instance.  At most ONE extra attempt; no second
+ * launch, no selection kernel, no barrier across the batch -- and it works between the steps of a one-launch eicos_batch_rollout, where
+ * no host retry can.  It applies to every solve launch of the handle: eicos_batch_solve(_async), _solve_subset, _solve_where,
+ * _update_solve, _update_rhs_solve, _update_param_solve and its subset form, and every step of eicos_batch_rollout, fused or per step,
+ * on every build of the solve kernel and on handles without an LDS vector.
+ * Contract: let a launch cover the instance set S (the batch, or a list).  Every instance ends bit-identical -- x, y, z, s, every info
+ * field except solve_us, eicos_debug_kkt, the u rows, the rollout records -- to this host sequence: (1) the same launch without the policy;
+ * (2) ids = the instances of S whose class is in mask; (3) eicos_batch_set_settings(settings), _set_warm_start(warm),
+ * _set_dynamic_regularization(dyn_delta, dyn_eps); (4) eicos_batch_solve_subset(ids); (5) the three settings restored -- with the outputs,
+ * the x rows and the plant map of a fused step taken after (5): per rollout step update from theta -> solve -> retry -> outputs -> plant.
+ * The fused update of an instance runs once, before the first attempt.  An instance outside the mask is untouched by the policy, and a
+ * handle without one behaves exactly as before.  Exit codes, the codes / iters of a rollout, eicos_batch_gather and _select see the
+ * final attempt.
+ * The second attempt is an ordinary solve of the instance: COLD by default (warm = 0).  With warm > 0 it warm-starts only if the record
+ * the first attempt left allows it (EICOS_OPTIMAL or EICOS_OPTIMAL + EICOS_INACC_OFFSET; a MAXIT or NUMERICS record starts cold whatever
+ * warm says), and a shift map (eicos_batch_set_shift_map) is then applied AGAIN, to the first attempt's result.
+ * eicos_batch_set_retry stores a copy; NULL or mask 0 removes the policy.  The record lives in device memory and is rewritten on the
+ * handle's stream, so a launch already enqueued keeps the policy it was enqueued with.  eicos_batch_retry_counts: retries[i] = second
+ * attempts instance first + i has run since its counter was last reset (cumulative: after a rollout, its retried steps); reset != 0
+ * zeroes the counters of the range after reading them.  Waits for the handle's stream.
+ * EICOS_E_INVALID, with a message naming the cause, and the policy UNCHANGED: a NULL handle (before any GPU call); mask bits above bit
+ * 11; a mask that is EICOS_SEL_UNSOLVED alone (an attempted instance is never in that class, so the policy could never act; beside
+ * other classes the bit is idle and accepted -- EICOS_SEL_NOT_OPTIMAL holds it); warm, dyn_delta or dyn_eps negative or NaN; any
+ * settings value eicos_batch_set_settings refuses (same check, the field named); a range outside [0, batch) or NULL retries. */
+typedef struct eicos_retry {
+    unsigned mask;             /* OR of EICOS_SEL_*: classes of the first attempt that trigger the second; 0 = no policy */
+    double warm;               /* warm-start shift of the second attempt (0 = cold, the default) */
+    double dyn_delta, dyn_eps; /* dynamic regularisation of the second attempt (0, 0 = off) */
+    eicos_settings settings;   /* runtime settings of the second attempt */
+} eicos_retry;
+void   eicos_retry_default(eicos_retry *out);   /* mask 0, warm 0, dyn 0 / 0, default settings; no handle, no GPU needed */
+size_t eicos_retry_size(void);                  /* sizeof(eicos_retry), for bindings that mirror the struct */
+int eicos_batch_set_retry(eicos_batch *hd, const eicos_retry *r);
+int eicos_batch_get_retry(eicos_batch *hd, eicos_retry *out);
+int eicos_batch_retry_counts(eicos_batch *hd, int first, int count, int *retries /* host [count] */, int reset);
+
 /* ---- plumbing */
 int eicos_batch_dims(eicos_batch *hd, eicos_dims *out);
 /* Which compilation of the solve kernel this handle launches (chosen at creation from pattern size and batch; no reference
@@ -661,6 +700,10 @@ int eicos_multi_set_dynamic_regularization(eicos_multi *mh, double delta, double
 /* runtime settings (eicos_batch_set_settings on every shard; a refused struct changes no shard); get: the first shard's */
 int eicos_multi_set_settings(eicos_multi *mh, const eicos_settings *s);
 int eicos_multi_get_settings(eicos_multi *mh, eicos_settings *out);
+/* retry policy (eicos_batch_set_retry on every shard; a refused policy changes no shard); get: the first shard's; counts: global ids */
+int eicos_multi_set_retry(eicos_multi *mh, const eicos_retry *r);
+int eicos_multi_get_retry(eicos_multi *mh, eicos_retry *out);
+int eicos_multi_retry_counts(eicos_multi *mh, int first, int count, int *retries /* host [count] */, int reset);
 /* the shards: their number, and shard s's single-GPU handle (every eicos_batch_* call works on it), instance range and device */
 int eicos_multi_num_shards(eicos_multi *mh);
 int eicos_multi_shard(eicos_multi *mh, int s, eicos_batch **handle, int *first, int *count, int *device);
