@@ -41,12 +41,12 @@ constexpr int DEVINFO_DOUBLES = 32;
 // over the same rows: `more` = another sub-slice of these rows follows, `cont` = this one continues the previous.
 struct SliceMeta { int row0, cnt, lg, K, off, newlev, more, cont; }; // host form (plan building, host emulation)
 constexpr int ELL_KMAX = 4;  // entries per lane that are software-prefetched
-// Destination codes of the factor program (DevPat::fac_dst), checked against each other in eicos_batch_create:
+// Destination codes of the factor program (DevPat::fac_dst), checked against each other in the plan step (plan_step.cpp):
 constexpr int DIAG_POS = 1 << 30; // diagonal targets: dst = -(j + 1) - (quasi-definite sign of pivot j is + ? DIAG_POS : 0)
 constexpr int IMG_BASE = 1 << 28; // hybrid: dst >= IMG_BASE = entry (dst - IMG_BASE) of the top block's tile image; UB slots stay below IMG_BASE
 
 // Device form of a slice: 16 bytes = one ds_read_b128 / s_load_dwordx4.  off16 = index of the slice's first lane
-// in the plan's packed 16-bit gather-index array (one 8-byte entry = ELL_KMAX indices per lane), see api.cpp.
+// in the plan's packed 16-bit gather-index array (one 8-byte entry = ELL_KMAX indices per lane), see plan_step.cpp.
 // bits: cnt [0,11) | lg [11,14) | K [14,17) | newlev 17 | last slice of its level 18 (factor plan) | more 19 | cont 20
 //       | static 21 (factor plan: no target of the slice takes its K entry from the scaling block -- DevPat::kt0; set by the host on the packed table)
 struct PackedSlice { int row0, off, off16, bits; };
@@ -203,7 +203,7 @@ struct DevPat {
     int lds_tab;                     // dynamic LDS: offset (doubles) of the slice tables behind the KKT-space vector(s)
     int dual, w_dual_xk, w_dual_ek;  // dual right-hand-side solves: flag + the two 2-interleaved vectors in the workspace
     int lr_inst, lr_work;            // LDS-resident variant: offsets (doubles) of the instance slab and the workspace slab in the dynamic LDS
-    // G in dense 16 x 16 tiles (api.cpp): gt_nrb row blocks of 16 rows, tiles [gt_rbptr[rb], gt_rbptr[rb+1]) of row block rb,
+    // G in dense 16 x 16 tiles (plan_step.cpp): gt_nrb row blocks of 16 rows, tiles [gt_rbptr[rb], gt_rbptr[rb+1]) of row block rb,
     // 16 columns per tile (gt_col: variable index or -1, gt_colk: elimination-order slot), gt_zslot: slot of z_i per row,
     // gt_cidx: per column gt_W indices into the partial sums, gt_src: value source of every tile element (updateData)
     int gt_on, gt_nrb, gt_nt, gt_W, i_Gt, w_gpart, w_gx, w_gz;

@@ -180,7 +180,7 @@ constexpr int KI_MAX = 2; // right-hand sides of a dual solve (kkt_solve<..., 2,
 enum { TK_FACTOR = 0, TK_LDL, TK_KRES, TK_KPOST, TK_RESID, TK_FWD, TK_COUNT, TK_FA = 8, TK_FW1, TK_FB, TK_FW2 }; // 8..11: inside the factor
 #define TICK_BEGIN unsigned long long tk0_ = (threadIdx.x == 0) ? wall_clock64() : 0ull
 #define TICK_END(slot) do { if (threadIdx.x == 0) { const unsigned long long t1_ = wall_clock64(); g_S.tick[slot] += t1_ - tk0_; tk0_ = t1_; } } while (0)
-static_assert(sizeof(Sh) <= 4096, "api.cpp budgets 4 KB of static LDS per workgroup");
+static_assert(sizeof(Sh) <= 4096, "plan_step.hpp budgets 4 KB of static LDS per workgroup (LDS_STATIC)");
 __shared__ __attribute__((aligned(16))) Sh g_S;
 struct IterBuf { gdbl_p x, y, z, s; };
 // (16-byte aligned: the dual right-hand-side vectors are read and written as 16-byte LDS accesses)
@@ -817,7 +817,7 @@ __device__ __forceinline__ void tri_sweep(const SM *sm, int ns, int nr, gint_p e
 // from the folded images behind the sweep plans' value arrays in the workspace slab (device_types.hpp: apex_img_at; zero where L has no entry)
 // -- a memory round trip per APEX_QD steps, slower than the level schedule on MPC02.  The product path is apex_solve_lds.
 constexpr int APEX_QD = 8;
-// (128-thread workgroups carry an apex only in the LDS-resident build -- 256 VGPRs, the images inside the LDS copy of the workspace slab: api.cpp)
+// (128-thread workgroups carry an apex only in the LDS-resident build -- 256 VGPRs, the images inside the LDS copy of the workspace slab: plan_step.cpp)
 template <int T> __device__ __forceinline__ bool apex_on(const DevPat &P) { if constexpr (T >= 256 || EICOS_LDSRES != 0) return P.apex_na > 0; else return false; }
 // the parts of the split row (DevPat::apex_split_*): their sum -- every lane reads the same few slots -- and the slots zeroed for the next sweep
 template <int KI, class WS>
@@ -1268,7 +1268,7 @@ enum Stage { ST_FACTOR = 0, ST_KKT_INIT1, ST_KKT_INIT2, ST_RESID, ST_KKT1, ST_KK
     (void)n; (void)p; (void)m; (void)l; (void)N; (void)np; (void)lane; (void)wave; (void)phase; (void)wi;
 
 // ---------------- ST_FACTOR: numeric LDL' (replaces ldlt.factorize, ref :900,1164) ----------------
-// Wg = the workgroup's workspace slab.  Left-looking sliced-ELL program over the level schedule (host: plans.cpp, api.cpp).
+// Wg = the workgroup's workspace slab.  Left-looking sliced-ELL program over the level schedule (host: plans.cpp, plan_step.cpp).
 // SH0 (a batch that shares its matrices, solve_instance's `plain`): the K entries of the level-0 passes and of the slices that hold no
 // scaling-block target (DevPat::kt0_pass, PS_STATIC) come from the batch's one copy DevPat::kt0 -- a uniform select of the base address.
 template <int T, int NLDS, bool I16, bool DEFER, bool SH0 = false>
@@ -1303,7 +1303,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void stage_facto
     // (DEFER = DevPat::fac_defer, a template parameter: the stored-L form must not pay for the pivot-column indices and the third operand)
     constexpr bool defer = DEFER;
     // 1/D[k] of a pair's pivot column: from the LDS mirror ([0, N] at the start of the dynamic LDS, slot fac_kpad = 0 for padding
-    // pairs), or -- kernels without an LDS vector: only the debug entry, api.cpp sets fac_defer with NLDS >= 1 -- from the array itself
+    // pairs), or -- kernels without an LDS vector: only the debug entry, lds_budget (plan_step.cpp) sets fac_defer with NLDS >= 1 -- from the array itself
     auto inv_of = [&](int k) -> double { if constexpr (NLDS >= 1) return g_dyn[k]; else return invD[k]; };
     // the pair's second operand: deferred -- U[j,k] (times 1/D[k] from the mirror); stored L -- the forward array
     auto ld_l = [&](int i) -> double { if constexpr (defer) return ld_u32((ubcdbl_p)U, i); else return ld_u32((gcdbl_p)UF, i); };
@@ -1352,7 +1352,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void stage_facto
         if constexpr (NLDS >= 1) { if (defer) g_dyn[j] = iv; }
     };
     // ---- level 0 (the leaves of the elimination tree: two thirds of the nodes of an MPC pattern) has no pairs at all:
-    // D_j = K_jj, U_ij = K_ij, L_ij = K_ij / D_j.  Two streaming passes over its targets (diagonals first, host: api.cpp)
+    // D_j = K_jj, U_ij = K_ij, L_ij = K_ij / D_j.  Two streaming passes over its targets (diagonals first, host: plan_step.cpp)
     // instead of a slice step per 256 targets: coalesced reads of the K stream, eight targets per thread in flight ----
     const int sbeg = P.fac_s1;
     if constexpr (NLDS >= 1) { if (defer) { if (tid == 0) g_dyn[P.fac_kpad] = 0.; __syncthreads(); } } // (what padding pairs read; the global array keeps a 0 there)
@@ -1797,7 +1797,7 @@ __device__ __forceinline__ void tile_solve(const DevPat &P, gdbl_p W, WS ws0) {
 #endif
 }
 
-// ---------------- G in dense tiles: G x and G' z in ONE pass over the values (DevPat::gt_on, host: api.cpp) ----------------
+// ---------------- G in dense tiles: G x and G' z in ONE pass over the values (DevPat::gt_on, host: plan_step.cpp) ----------------
 // One wavefront per row block of 16 rows: lane l = 16 kq + r holds G[r][4 reg + kq] of the current tile (tile-internal
 // operand order, two 16-byte loads), gathers the vector entries of its four columns and the z entry of its row, and
 //   * accumulates row r of G x over the tiles of the row block (folded over kq at the end: two cross-lane adds),

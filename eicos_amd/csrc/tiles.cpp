@@ -143,7 +143,7 @@ TileSweeps build_tile_sweeps(const TilePlan &T, int NW, int pf, int serial_max) 
     // A SMALL block system (the dense top of a hybrid pattern: lp_bandm's is a chain of seven blocks, one per level) is swept by ONE wavefront
     // as one flat list in dependency order: a wavefront's LDS accesses execute in order, so no barrier separates its levels and its tile queue
     // runs across them -- level by level the same system costs a barrier and a cold start of the queue per level while seven wavefronts wait.
-    // Same operations on the same operands in the same order per block: bit-identical.  (Needs the sweep vector in LDS: api.cpp.)
+    // Same operations on the same operands in the same order per block: bit-identical.  (Needs the sweep vector in LDS: plan_step.cpp.)
     W.serial = (T.nt + T.nb) <= serial_max ? 1 : 0;
     const bool allow_split = !(getenv("EICOS_EXPERIMENT") && getenv("EICOS_TILE_SPLIT") && !strcmp(getenv("EICOS_EXPERIMENT"), "1") && !strcmp(getenv("EICOS_TILE_SPLIT"), "0"));
     auto build = [&](bool fwd, std::vector<int> &ops, std::vector<int> &ptr, std::vector<int> &endr, std::vector<int> &split) {

@@ -32,10 +32,11 @@ F="-O3 -std=c++17 -fPIC -Wall -Wno-unused-parameter -ffp-contract=off"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 $F -c kernels.hip -o kernels.o &
 /opt/rocm/bin/hipcc --offload-arch=gfx950 $F -c kernels_ldsres.hip -o kernels_ldsres.o &
 /opt/rocm/bin/hipcc --offload-arch=gfx950 $F -c kernels_w2.hip -o kernels_w2.o &
-/opt/rocm/bin/hipcc $F -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c api.cpp -o api.o
-/opt/rocm/bin/hipcc $F -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -pthread -c multi.cpp -o multi.o
-for f in symbolic plans tiles; do /opt/rocm/bin/hipcc $F -x c++ -c $f.cpp -o $f.o; done
+# the host objects: the product's list and rules (HOSTOBJ of the Makefile, copied beside the sources), with this script's flags
+cp $root/eicos_amd/csrc/Makefile $src/
+hostobj=$(make -s hostobj)
+make -s CXXFLAGS="$F" $hostobj
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -pthread -o $root/build_exp/lib$tag.so kernels.o kernels_ldsres.o kernels_w2.o api.o multi.o symbolic.o plans.o tiles.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -pthread -o $root/build_exp/lib$tag.so kernels.o kernels_ldsres.o kernels_w2.o $hostobj
 rm -rf $src
 echo built build_exp/lib$tag.so
