@@ -230,6 +230,13 @@ def _lib():
                 getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
             for f in ("update_indexed", "update_rhs_indexed", "update_param_indexed", "set_iterate_indexed", "outputs_indexed"):
                 getattr(L, "eicos_batch_" + f + "_device").restype = C.c_int
+        if hasattr(L, "eicos_batch_adjoint"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            L.eicos_batch_adjoint.argtypes = L.eicos_multi_adjoint.argtypes = [vp, ip, C.c_int, C.c_int, dp, dp, dp, dp, dp]
+            L.eicos_batch_output_jacobian.argtypes = L.eicos_multi_output_jacobian.argtypes = [vp, ip, C.c_int, dp, dp]
+            L.eicos_batch_output_jacobian_device.argtypes = [vp, ip, C.c_int, vp, vp]
+            for f in ("adjoint", "output_jacobian"):
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+            L.eicos_batch_output_jacobian_device.restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -912,6 +919,61 @@ class _Solver:
         self._call("outputs_indexed", ptr, int(idx.size), _dp(u) if u.size else _dp(np.zeros(1)))
         return u
 
+    # ---- adjoint sensitivities (include/eicos_amd.h: eicos_batch_adjoint, _output_jacobian) ----
+    def _adjoint_rows(self, idx):
+        """(pointer or None, count) of an adjoint call: idx None = the whole batch."""
+        if idx is None:
+            return None, self.batch
+        ids, ptr = _index_rows(idx)
+        return ptr, int(ids.size)
+
+    def adjoint(self, g, idx=None):
+        """Gradients of g'x with respect to (c, h, b) at the iterate the last solve returned: g [count, nrhs, n] (or [count, n] for one
+        right-hand side), count = len(idx) or the batch.  Returns (grad_c [count, nrhs, n], grad_h [count, nrhs, m], grad_b
+        [count, nrhs, p], res [count, nrhs]); an instance whose last solve did not end OPTIMAL / OPTIMAL_INACC has NaN rows.  One
+        factorisation and nrhs refined KKT solves per instance; nothing a later call reads is changed.  At a degenerate optimum the
+        result is a smoothed value, not a derivative."""
+        ptr, count = self._adjoint_rows(idx)
+        pat = self.pat
+        g = np.ascontiguousarray(g, dtype=np.float64)
+        if g.ndim == 2:
+            g = g[:, None, :]
+        if g.ndim != 3 or g.shape[0] != count or g.shape[2] != pat.n:
+            raise ValueError(f"g must have shape [{count}, nrhs, {pat.n}], not {g.shape}")
+        nrhs = int(g.shape[1])
+        gc, gh, gb, res = (np.zeros((count, nrhs, w)) for w in (pat.n, pat.m, pat.p, 1))
+        self._call("adjoint", ptr, count, nrhs, *[_dp(a) if a.size else None for a in (g, gc, gh, gb)], _dp(res) if res.size else None)
+        return gc, gh, gb, res[:, :, 0]
+
+    def output_jacobian(self, idx=None, device=False):
+        """(J [count, r, k], res [count, r]): the Jacobian du / dtheta of the output map through the parameter map at the iterate the
+        last solve returned -- r adjoint solves per instance, contracted with the map on the GPU.  device=True (single-GPU handles):
+        the call that writes J and res into device memory, fetched here afterwards; the same bits."""
+        ptr, count = self._adjoint_rows(idx)
+        r, k = max(self.output_count(), 0), max(self.param_count(), 0)
+        J, res = np.zeros((count, r, k)), np.zeros((count, r))
+        if not device:
+            self._call("output_jacobian", ptr, count, _dp(J) if J.size else _dp(np.zeros(1)), _dp(res) if res.size else None)
+            return J, res
+        if self._prefix != "eicos_batch_":
+            raise ValueError("output_jacobian(device=True) needs a single-GPU handle")
+        hip = _lib()
+        hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        hip.hipFree.argtypes = [C.c_void_p]
+        dJ, dres = C.c_void_p(), C.c_void_p()
+        if hip.hipMalloc(C.byref(dJ), max(J.nbytes, 8)) != 0 or hip.hipMalloc(C.byref(dres), max(res.nbytes, 8)) != 0:
+            raise RuntimeError("hipMalloc failed")
+        try:
+            self._call("output_jacobian_device", ptr, count, dJ, dres)
+            self._call("sync")
+            for host, dev in ((J, dJ), (res, dres)):
+                if host.nbytes and hip.hipMemcpy(host.ctypes.data, dev, host.nbytes, 2) != 0:  # hipMemcpyDeviceToHost
+                    raise RuntimeError("hipMemcpy failed")
+        finally:
+            hip.hipFree(dJ); hip.hipFree(dres)
+        return J, res
+
     def update_param_solve_subset(self, indices, theta, u_out=None, x_out=None):
         """The closed-loop step over the instances `indices` in one call: update_param_indexed + solve_subset + outputs_indexed, theta
         [len(indices), k], u_out [len(indices), r] and x_out [len(indices), n] in list order -- with pinned / registered theta ONE subset
@@ -1099,6 +1161,11 @@ class BatchSolver(_Solver):
         """outputs_indexed() into a raw device pointer (int) to u [len(indices), r]."""
         idx, ptr = _index_rows(indices)
         self._call("outputs_indexed_device", ptr, int(idx.size), C.c_void_p(int(du) or None))
+
+    def output_jacobian_device(self, dJ, dres=0, idx=None):
+        """output_jacobian() into raw device pointers (int): J [count, r, k] and, optionally, res [count, r]; asynchronous (sync() waits)."""
+        ptr, count = self._adjoint_rows(idx)
+        self._call("output_jacobian_device", ptr, count, C.c_void_p(int(dJ) or None), C.c_void_p(int(dres) or None))
 
     def set_stream(self, stream_ptr: int):
         self._call("set_stream", C.c_void_p(int(stream_ptr) or None))

@@ -172,6 +172,11 @@ struct eicos_batch {
     // every launch that may leave the word above at 0 (launch_range) -- so its contents are valid exactly while the word is 0, and only the
     // stages' PLAIN instantiations, which run exactly then, read it.  Empty: not on this handle (eicos_dims.shared_operands = 0).
     DevBuf d_shop;
+    // Adjoint sensitivities (eicos_batch_adjoint, _output_jacobian): one device allocation, made by the first call and grown on
+    // demand: [AdjointDev (MAP_HEADER bytes) | ids [batch] | g | grad_c | grad_h | grad_b | res] -- the record of the launch, its index
+    // list and the staging of the host forms' rows (the Jacobian form keeps J where grad_c would be)
+    DevBuf d_adj; AdjointDev adj{}; // (adj: the host copy of the most recent launch's record, the source of its copy on the handle's stream)
+    hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr; bool adjoint_timed = false; // HIP events around the most recent adjoint launch (eicos_batch_last_adjoint_ms)
 
     // The events and the stream the handle made; the buffers free themselves after this body.  eicos_batch_destroy has set the device and
     // waited for both streams: nothing here synchronises.
@@ -179,6 +184,7 @@ struct eicos_batch {
         if (own_stream) (void)hipStreamDestroy(own_stream);
         for (int i = 0; i < EV_RING; i++)
             for (hipEvent_t e : {ring_s[i][0], ring_s[i][1], ring_u[i][0], ring_u[i][1]}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {ev_a0, ev_a1}) if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -1713,6 +1719,118 @@ int eicos_batch_outputs_indexed_device(eicos_batch *h, const int *idx, int count
     return outputs_indexed(h, idx, count, du, false, "eicos_batch_outputs_indexed_device");
 }
 
+// ---- adjoint sensitivities (include/eicos_amd.h) ----
+// One launch of the handle's adjoint kernel (launch.hpp: AdjointLaunch) behind everything on the handle's stream, under the handle's settings
+// and dynamic regularisation.  Every check stands in front of the first enqueue: a refused call changes nothing.
+namespace {
+struct AdjointCall {
+    const int *idx; int count, nrhs; // nrhs: right-hand sides per instance (the Jacobian form: r)
+    const double *g; double *grad_c, *grad_h, *grad_b, *res, *J; // host arrays of the gradient form; J / res of the Jacobian form
+    bool jac, device; // the Jacobian form; its J and res live in device memory (asynchronous)
+};
+}
+static int adjoint_list_fault(const eicos_batch *h, const int *idx, int count, const char *who) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (idx) return take_index_list(h, idx, count, who);
+    if (count < 0 || count > h->batch) return fail(EICOS_E_INVALID, std::string(who) + ": count must lie in [0, batch] when idx is NULL (instances 0 .. count-1)");
+    return EICOS_OK;
+}
+static int adjoint_run(eicos_batch *h, const AdjointCall &c) {
+    if (c.count == 0) return EICOS_OK;
+    const DevPat &D = h->dp;
+    const size_t rows = (size_t)c.count * c.nrhs, k = c.jac ? (size_t)h->param.k : 0;
+    HIP_TRY(hipSetDevice(h->device));
+    if (!c.device) HIP_TRY(hipStreamSynchronize(h->stream));
+    // the allocation: record | ids | g | grad_c (or J) | grad_h | grad_b | res, every part 64-byte aligned
+    auto pad = [](size_t b) { return (b + 63) & ~(size_t)63; };
+    const size_t at_ids = MAP_HEADER, at_g = at_ids + pad((size_t)h->batch * sizeof(int));
+    const size_t at_c = at_g + pad(c.jac ? 0 : rows * D.n * sizeof(double));
+    const size_t at_h = at_c + pad((c.jac ? (c.device ? 0 : rows * k) : rows * D.n) * sizeof(double));
+    const size_t at_b = at_h + pad(c.jac ? 0 : rows * D.m * sizeof(double));
+    const size_t at_r = at_b + pad(c.jac ? 0 : rows * D.p * sizeof(double));
+    const size_t total = at_r + pad(c.device ? 0 : rows * sizeof(double));
+    HIP_TRY_AS("hipMalloc", h->d_adj.reserve(total, h->stream));
+    char *base = h->d_adj.as<char>();
+    auto dbl = [&](size_t at) { return reinterpret_cast<double *>(base + at); };
+    const int *d_ids = nullptr;
+    if (c.idx) {
+        const int rc = upload_ids(h, c.idx, c.count, reinterpret_cast<int *>(base + at_ids));
+        if (rc != EICOS_OK) return rc;
+        d_ids = reinterpret_cast<const int *>(base + at_ids);
+    }
+    AdjointDev &rec = h->adj;
+    rec = AdjointDev{};
+    if (c.jac) {
+        rec.pmap = h->d_param.as<const ParamMapDev>(); rec.omap = h->d_out.as<const OutMapDev>();
+        rec.J = c.device ? c.J : dbl(at_c);
+        rec.res = c.device ? c.res : (c.res ? dbl(at_r) : nullptr);
+    } else {
+        rec.nrhs = c.nrhs; rec.g = dbl(at_g);
+        rec.grad_c = c.grad_c && D.n ? dbl(at_c) : nullptr; rec.grad_h = c.grad_h && D.m ? dbl(at_h) : nullptr;
+        rec.grad_b = c.grad_b && D.p ? dbl(at_b) : nullptr; rec.res = c.res ? dbl(at_r) : nullptr;
+        HIP_TRY(hipMemcpyAsync(dbl(at_g), c.g, rows * D.n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(base, &rec, sizeof rec, hipMemcpyHostToDevice, h->stream));
+    AdjointLaunch L{};
+    L.ps = h->pslot; L.inst = h->inst(); L.work = h->work(); L.count = c.count; L.list = d_ids; L.batch = h->batch;
+    L.grid = h->grid; L.threads = h->threads; L.nlds = h->nlds; L.idx16 = D.idx16;
+    L.dyn_delta = h->dyn_delta; L.dyn_eps = h->dyn_eps; L.cfg = h->cfg; L.dyn_lds = h->dyn_lds;
+    L.adj = h->d_adj.as<const AdjointDev>();
+    if (!h->ev_a0) { HIP_TRY(hipEventCreate(&h->ev_a0)); HIP_TRY(hipEventCreate(&h->ev_a1)); }
+    HIP_TRY(hipEventRecord(h->ev_a0, h->stream));
+    HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).adjoint(L, h->stream));
+    HIP_TRY(hipEventRecord(h->ev_a1, h->stream));
+    h->adjoint_timed = true;
+    if (c.device) return EICOS_OK;
+    auto back = [&](double *dst, const double *src, size_t n) -> int {
+        if (dst && src && n) HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        return EICOS_OK;
+    };
+    int rc = EICOS_OK;
+    if (c.jac) rc = back(c.J, rec.J, rows * k);
+    else {
+        rc = back(c.grad_c, rec.grad_c, rows * D.n);
+        if (rc == EICOS_OK) rc = back(c.grad_h, rec.grad_h, rows * D.m);
+        if (rc == EICOS_OK) rc = back(c.grad_b, rec.grad_b, rows * D.p);
+    }
+    if (rc == EICOS_OK) rc = back(c.res, rec.res, rows);
+    if (rc != EICOS_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return EICOS_OK;
+}
+
+int eicos_batch_adjoint(eicos_batch *h, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b,
+                        double *res) {
+    const int rc = adjoint_list_fault(h, idx, count, "eicos_batch_adjoint");
+    if (rc != EICOS_OK) return rc;
+    if (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS) return fail(EICOS_E_INVALID, "eicos_batch_adjoint: nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
+    if (!g && count > 0 && h->dp.n > 0) return fail(EICOS_E_INVALID, "eicos_batch_adjoint: g is NULL");
+    for (const double *q : {g, (const double *)grad_c, (const double *)grad_h, (const double *)grad_b, (const double *)res})
+        if (q && count > 0 && memory_kind(q, 1) == MEM_DEVICE) return fail(EICOS_E_INVALID, "eicos_batch_adjoint takes host pointers: an array lives in device memory");
+    return adjoint_run(h, AdjointCall{idx, count, nrhs, g, grad_c, grad_h, grad_b, res, nullptr, false, false});
+}
+
+static int output_jacobian(eicos_batch *h, const int *idx, int count, double *J, double *res, bool device, const char *who) {
+    const int rc = adjoint_list_fault(h, idx, count, who);
+    if (rc != EICOS_OK) return rc;
+    if (h->param.k == 0 || h->out.r == 0)
+        return fail(EICOS_E_INVALID, std::string(who) + ": needs a parameter map and an output map (eicos_batch_set_param_map, eicos_batch_set_output_map): J = d u / d theta");
+    if (h->mat.k != 0)
+        return fail(EICOS_E_INVALID, std::string(who) + ": a matrix map is installed -- the derivative then has dG and dA terms, which this call does not form (right-hand-side data only)");
+    if (!J && count > 0) return fail(EICOS_E_INVALID, std::string(who) + ": J is NULL");
+    if (count > 0 && (memory_kind(J, 1) == MEM_DEVICE) != device)
+        return fail(EICOS_E_INVALID, std::string(who) + (device ? ": J must live in device memory (eicos_batch_output_jacobian takes host pointers)"
+                                                                 : " takes host pointers: J lives in device memory (use eicos_batch_output_jacobian_device)"));
+    if (count > 0 && res && (memory_kind(res, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, std::string(who) + ": res must live where J lives");
+    return adjoint_run(h, AdjointCall{idx, count, h->out.r, nullptr, nullptr, nullptr, nullptr, res, J, true, device});
+}
+int eicos_batch_output_jacobian(eicos_batch *h, const int *idx, int count, double *J, double *res) {
+    return output_jacobian(h, idx, count, J, res, false, "eicos_batch_output_jacobian");
+}
+int eicos_batch_output_jacobian_device(eicos_batch *h, const int *idx, int count, double *dJ, double *dres) {
+    return output_jacobian(h, idx, count, dJ, dres, true, "eicos_batch_output_jacobian_device");
+}
+
 // The closed-loop step over a chosen subset: eicos_batch_update_param_indexed + eicos_batch_solve_subset + eicos_batch_outputs_indexed (+ the
 // x rows), every array in list order.  Fused under the conditions of eicos_batch_update_param_solve (update_solve, above: an LDS vector,
 // a theta row that fits, theta the GPU addresses, EICOS_FUSED_UPDATE not 0; witness 5): ONE subset launch whose selection kernel also
@@ -1976,6 +2094,7 @@ static int elapsed(eicos_batch *h, bool ok, hipEvent_t a, hipEvent_t b, float *m
     return EICOS_OK;
 }
 int eicos_batch_last_solve_ms(eicos_batch *h, float *ms) { return elapsed(h, h && h->solve_timed, h ? h->ev_s0 : nullptr, h ? h->ev_s1 : nullptr, ms); }
+int eicos_batch_last_adjoint_ms(eicos_batch *h, float *ms) { return elapsed(h, h && h->adjoint_timed, h ? h->ev_a0 : nullptr, h ? h->ev_a1 : nullptr, ms); }
 int eicos_batch_last_update_ms(eicos_batch *h, float *ms) { return elapsed(h, h && h->update_timed, h ? h->ev_u0 : nullptr, h ? h->ev_u1 : nullptr, ms); }
 // Durations (ms, HIP events on the handle's stream) of the most recent launches, oldest first: which = 0 the solve launches, 1 the
 // updateData calls, 2 the span from the start of the updateData call that preceded a solve launch to the end of that solve (one "step").  Returns how many were written (<= cap, <= 64: the ring's depth); waits for the most recent one to finish.

@@ -1899,7 +1899,10 @@ __device__ __forceinline__ gcdbl_p product_values(gdbl_p I) {
 }
 
 // ---------------- ST_RESID: residuals, statistics, exit logic, scalings ----------------
-template <int T, int NLDS, bool I16, bool PLAIN = false> // (PLAIN: the product values are the batch's shared copy -- ld_val)
+// ADJ (adjoint_instance, its own instantiation: the others compile to what they did): the scalings half alone -- updateScalings and the
+// KKT scaling block of the iterate in buffer set g_S.cur, no residuals, no statistics, no exit test, no lambda; returns ST_DONE when a
+// cone's scaling failed (the instance then has no sensitivity) and ST_FACTOR otherwise.
+template <int T, int NLDS, bool I16, bool PLAIN = false, bool ADJ = false> // (PLAIN: the product values are the batch's shared copy -- ld_val)
 static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(int ps, gdbl_p I, gdbl_p W, int iter) {
     STAGE_PROLOGUE
     iter = uni(iter);
@@ -1912,6 +1915,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(
     const gcdbl_p PV = product_values(I);
     gcdbl_p cagv = PV + P.i_cag, rAv = PV + P.i_rA, rGv = PV + P.i_rG;
     TICK_BEGIN;
+    if constexpr (!ADJ) {
     // ---- computeResiduals (ref :643-689) + updateStatistics (ref :691-754) ----
     const double tau = wi.tau;
     double r8[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // hresx2 rx2 cx nx2 | hresy2 ry2 by ny2
@@ -2026,6 +2030,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(
         if (tid == 0) g_S.cur = 0;
         return ST_DONE;
     }
+    } // (!ADJ)
     // ---- updateScalings (ref :411-479) + updateKKTScalings (ref :1691-1732) ----
     // the scaling block goes to the instance slab (Vv) and to the factor's target-ordered value stream (Kt)
     gdbl_p Kt = W + P.w_Kt;
@@ -2034,7 +2039,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(
         const double v = r.a / r.b;
         const double w = sqrt(v);
         lpv[i] = v; lpw[i] = w; Vv[i] = -v - DELTASTAT; Kt[r.i] = -v - DELTASTAT;
-        if (lp_only) lam[i] = w * r.b; // lambda = W z (ref :476) in the same pass when there is no cone that could fail
+        if (!ADJ && lp_only) lam[i] = w * r.b; // lambda = W z (ref :476) in the same pass when there is no cone that could fail
     });
     double firstfail = 1e300;
     if (P.nc > 0) {
@@ -2267,6 +2272,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(
         });
     }
     __syncthreads();
+    if constexpr (ADJ) return firstfail >= 1e299 ? ST_FACTOR : ST_DONE;
     if (!lp_only && firstfail >= 1e299) dev_scale<T>(ps, W, wz, lam); // lambda = W z only when every cone succeeded (ref :476)
     TICK_END(TK_RESID);
     return ST_FACTOR;
@@ -2280,7 +2286,13 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int stage_resid(
 // right-hand side k at 2 i + k); every right-hand side keeps its own refinement state (step count, previous error, done
 // flag): the loop runs until both have stopped, one that has stopped keeps its iterate while the other takes further
 // steps (its lanes still compute, the result is discarded).  amask: bit k set = right-hand side k takes part.
-template <int T, int NLDS, bool I16, int KI, bool DUAL = false, bool PLAIN = false> // (PLAIN: as stage_resid's)
+// ADJ (adjoint_instance, KI = 1, its own instantiation): the refinement residual is taken against the UNREGULARISED system -- the static
+// delta of the x, y and z rows, which a solve's residual carries like the factorised matrix, is left out (RDELTA = 0), so the iteration
+// removes the regularisation of the factor from the result (its contraction factor is delta |K^-1|; where that exceeds 1 the first
+// step gets worse, is undone, and the regularised solution stands), with one step beyond the linsysacc threshold (the stop test
+// below) -- and the error norm of the iterate the refinement kept, divided by
+// 1 + |rhs|_inf, is left in g_S.dots[1][0], the slot of the other right-hand side, which this solve does not use.
+template <int T, int NLDS, bool I16, int KI, bool DUAL = false, bool PLAIN = false, bool ADJ = false> // (PLAIN: as stage_resid's)
 static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(int ps, gdbl_p I0, gdbl_p I1, gdbl_p Wg, int stage, int amask) {
     ps = uni(ps); I0 = uni_ptr(I0); I1 = uni_ptr(I1); Wg = uni_ptr(Wg); stage = uni(stage); amask = uni(amask);
     const DevPat &P = c_pat[ps];
@@ -2350,6 +2362,9 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
     };
     // per-instance refinement state (workgroup-uniform: every thread sees the same reduction results)
     int kcnt[KI]; double nerr_prev[KI], thr[KI]; bool rdone[KI];
+    double adj_err = 0., adj_den = 1.; // (ADJ only)
+    constexpr double RDELTA = ADJ ? 0. : DELTASTAT; // the static regularisation as the refinement residual sees it
+    static_assert(!ADJ || KI == 1, "the adjoint solve has one right-hand side");
     {
         double nr[KI];
 #pragma unroll
@@ -2376,6 +2391,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
         blk_reduce<OpMax, T, KI>(phase, nr);
 #pragma unroll
         for (int k = 0; k < KI; k++) { thr[k] = (1. + nr[k]) * g_S.cfg.linsysacc; nerr_prev[k] = DBL_MAX; kcnt[k] = -1; rdone[k] = !((amask >> k) & 1); }
+        if constexpr (ADJ) adj_den = 1. + nr[0];
     }
     for (int pass = 0;; pass++) {
         // -------- SV <- L^-T D^-1 L^-1 SV in elimination order (replaces ldlt.solve, ref :1477,1599) --------
@@ -2492,14 +2508,14 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
                     [&](int k, int j) { return PreK{ld_u32(bx[k], j), 0., ld_u32(P.ipx, j), 0, gt ? gxv[j * KI + k] : 0.}; },
                     [&](int k, int j, double s, const PreK &pr) {
             const int o = pr.o;
-            const double e = pr.b - (s + pr.g) - DELTASTAT * X[o * KI + k]; // ex = bx - G'dz - A'dy - delta dx
+            const double e = pr.b - (s + pr.g) - RDELTA * X[o * KI + k]; // ex = bx - G'dz - A'dy - delta dx
             stE(o, k, e); nex[k] = fmax(nex[k], fabs(e));
         });
         ell_dots_k<T, I16, KI, DUAL, PLAIN>(tab_rA, P.rA_ns, P.rA_ns_r, P.rA_idx_k, P.rA_k16, P.rA_d16, rAv, X, P.rA_slots,
                     [&](int k, int r) { return PreK{ld_u32(by[k], r), 0., ld_u32(P.ipy, r), 0, 0.}; },
                     [&](int k, int r, double s, const PreK &pr) {
             const int o = pr.o;
-            const double e = pr.b - s + DELTASTAT * X[o * KI + k]; // ey = by - A dx + delta dy
+            const double e = pr.b - s + RDELTA * X[o * KI + k]; // ey = by - A dx + delta dy
             stE(o, k, e); ney[k] = fmax(ney[k], fabs(e));
         });
         ell_dots_k<T, I16, KI, DUAL, PLAIN>(tab_rG, P.rG_ns, P.rG_ns_r, P.rG_idx_k, P.rG_k16, P.rG_d16, rGv, X, P.rG_slots,
@@ -2507,7 +2523,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
                     [&](int k, int i, double s, const PreK &pr) {
             const int o = pr.o;
             const double xo = X[o * KI + k];
-            double v = pr.b - (s + pr.g) + (double)pr.sg * DELTASTAT * xo; // ez = bz - G dx +/- delta dz ...
+            double v = pr.b - (s + pr.g) + (double)pr.sg * RDELTA * xo; // ez = bz - G dx +/- delta dz ...
             if (i < l) { v += init ? xo : pr.w * xo; nez[k] = fmax(nez[k], fabs(v)); } // ... + V dz (LP part)
             stE(o, k, v);
         });
@@ -2631,6 +2647,19 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
             if (rdone[k]) continue;
             double nerr = fmax(nv[3 * k], nv[3 * k + 2]);
             if (p > 0) nerr = fmax(nerr, nv[3 * k + 1]);
+            if constexpr (ADJ) {
+                // The stop test is an infinity norm: it cannot see the components of size W^2 (grad_c at a vertex), in which the removal
+                // of delta still converges geometrically when the norm is at rounding level already (lp_bandm, MPC02: the x part 2e-8
+                // off at the first error norm under the threshold, 1e-15 one step later).  So the adjoint solve takes ONE step beyond
+                // the threshold and keeps it whenever it stays under the threshold; every other rule is the solve's.
+                const bool below = nerr < thr[k], was_below = nerr_prev[k] < thr[k];
+                const bool worse = kcnt[k] > 0 && nerr > nerr_prev[k] && !below;
+                adj_err = worse ? nerr_prev[k] : nerr; // (an undone step: the kept iterate's error)
+                if (worse) { undo[k] = true; kcnt[k]--; rdone[k] = true; }
+                else if (kcnt[k] == nitref || (below && was_below) || (!below && kcnt[k] > 0 && nerr_prev[k] < irerrfact * nerr)) rdone[k] = true;
+                else { nerr_prev[k] = nerr; all_done = false; }
+                continue;
+            }
             if (kcnt[k] > 0 && nerr > nerr_prev[k]) { undo[k] = true; kcnt[k]--; rdone[k] = true; } // got worse: undo and quit (ref :1579-1585)
             else if (kcnt[k] == nitref || nerr < thr[k] || (kcnt[k] > 0 && nerr_prev[k] < irerrfact * nerr)) rdone[k] = true;
             else { nerr_prev[k] = nerr; all_done = false; }
@@ -2697,6 +2726,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
             }
         }
     }
+    if constexpr (ADJ) { if (tid == 0) g_S.dots[1][0] = adj_err / adj_den; }
     __syncthreads();
     tick(TK_KRES);
 }
@@ -3529,6 +3559,130 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int retry_betwee
     return uni(g_S.attempt);
 }
 
+// ---------------- adjoint sensitivities of one instance (launch.hpp: AdjointDev) ----------------
+// At the (x, y, z, s) the instance's last solve returned: K [w_x; w_y; w_z] = [g; 0; 0] with the NT scaling of (s, z) in K's scaling
+// block, grad_c = -w_x, grad_h = w_z, grad_b = w_y, for every right-hand side g of the launch.  Four steps:
+//   1. the equilibrated (s, z) of the result rows into buffer set 1 of the iterate (the result rows themselves are only read), the KKT
+//      image as instance_begin leaves it, and the scalings half of stage_resid on that iterate (its ADJ instantiation);
+//   2. the factorisation of the handle's factor path, as solve_instance calls it;
+//   3. per right-hand side: D [g; 0; 0] into w_rhs1k, kkt_solve with its refinement (one right-hand side, ADJ: the error norm it
+//      stopped at), the direction scaled back by D = diag(1 / xe, 1 / ae, 1 / ge);
+//   4. the three gradient rows and res to the caller's arrays -- or, in the Jacobian form (A.J != NULL: g = row i of the output map),
+//      contracted with the CSR rows of the parameter map into J[i, :], columns in chunks of eight, every chunk one workgroup reduction in
+//      a fixed order (thread-private partial sums over the thread's rows in ascending order, then blk_reduce); no gradient row is stored.
+// An instance whose last solve did not end OPTIMAL / OPTIMAL_INACC, whose scalings fail or whose factorisation meets a zero pivot gets
+// NaN in every row and in res.  Nothing of the instance slab that a later call reads is written: the scaling block i_Vv is reset by every
+// solve's prologue, and the workspace slab belongs to the workgroup, not to an instance.  g_S is scratch here (no instance_end).
+// `row`: the instance's row in the caller's arrays (its position in the index list, or its id).
+template <int T, int NLDS, bool I16>
+static __device__ __noinline__ __attribute__((not_tail_called)) void adjoint_instance(int ps, gdbl_p I, gdbl_p W, const AdjointDev *Ap, int row) {
+    ps = uni(ps); I = uni_ptr(I); W = uni_ptr(W); Ap = uni_ptr(Ap); row = uni(row);
+    const DevPat &P = c_pat[ps];
+    const int n = P.n, p = P.p, m = P.m, l = P.l, np = P.n + P.p;
+    const int tid = threadIdx.x;
+    const AdjointDev A = *Ap;
+    gcdbl_p xe = I + P.i_xe, ae = I + P.i_ae, ge = I + P.i_ge;
+    gdbl_p rhs1k = W + P.w_rhs1k;
+    int phase = 0;
+    __syncthreads();
+    if (tid == 0) {
+        g_S.wi = *(DevInfo *)(I + P.i_info); g_S.bi = g_S.wi;
+        g_S.fl[FL_FATAL] = 0; g_S.fl[FL_CODE] = -7; g_S.fl[FL_WARM] = 0; g_S.done = 0; g_S.kref = 0;
+        g_S.cur = 1; g_S.best = -1; // the equilibrated iterate goes to the workspace set: the result rows stay as they are
+        for (int q = 0; q < 12; q++) g_S.tick[q] = 0;
+    }
+    { // the KKT image of instance_begin: scaling block reset, structural entries in the factor's target order
+        gdbl_p Vv = I + P.i_Vv;
+        FOR_T(i, l) Vv[i] = -1.;
+        for_cones<T>(ps, [&](int c, auto G, int ln) {
+            constexpr int g = decltype(G)::value;
+            const int d = P.cq[c];
+            gdbl_p v = Vv + P.cone_vbase[c];
+            for (int k = ln; k < d; k += g) { v[k] = -1.; v[2 * d + 1 + k] = 0.; if (k >= 1) v[d + k] = 0.; }
+            if (ln == 0) { v[d] = -1.; v[2 * d] = 1.; }
+        });
+        __syncthreads();
+        gdbl_p Kt = W + P.w_Kt;
+        if (P.tile) {
+            gdbl_p Kimg = W + P.w_Kimg;
+            const int nimg = (P.nb + P.nt) * 256;
+            FOR_T(t, nimg) Kimg[t] = 0.;
+            __syncthreads();
+            for_t_pre<T, 8>(P.tl_nimg, [&](int e) { return IV1{P.tl_img_dst[e], I[P.tl_img_src[e]]}; }, [&](int e, const IV1 &r) { Kimg[r.i] = r.a; });
+        }
+        if (P.tile != 1)
+        for_t_pre<T, 8>(P.fac_nt, [&](int t) { return V1{I[P.fac_src[t]]}; }, [&](int t, const V1 &r) { Kt[t] = r.a; });
+    }
+    { // (s, z) re-equilibrated as a warm start re-forms them, without the push into the cone; tau = 1: W is invariant under the common scaling
+        const IterBuf it = iter_buf(P, I, W, 1);
+        gcdbl_p rz = I + P.i_z, rs = I + P.i_s;
+        FOR_T(i, m) { const double g = ge[i]; it.z[i] = rz[i] * g; it.s[i] = rs[i] / g; }
+    }
+    __syncthreads();
+    bool ok = (exit_class(g_S.wi.exitcode, g_S.wi.n_factor) & (EICOS_SEL_OPTIMAL | EICOS_SEL_OPTIMAL_INACC)) != 0;
+    if (ok) ok = stage_resid<T, NLDS, I16, false, true>(ps, I, W, 0) != ST_DONE;
+    if (ok) {
+        if (P.tile != 1) { if (P.fac_defer) stage_factor<T, NLDS, I16, true>(ps, W); else stage_factor<T, NLDS, I16, false>(ps, W); }
+        if (P.tile) stage_factor_tiles<T, NLDS>(ps, I, W, 0);
+        __syncthreads();
+        ok = g_S.fl[FL_FATAL] == 0;
+    }
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const int nrhs = A.J ? A.omap->r : A.nrhs;
+    for (int r = 0; r < nrhs; r++) {
+        const size_t at = (size_t)row * nrhs + r;
+        if (ok) {
+            __syncthreads();
+            if (A.J) { // row r of the output map, densified: the entries of a column summed in stored order, then D
+                const AffineDev U = A.omap->a;
+                FOR_T(j, np + m) rhs1k[j] = 0.;
+                __syncthreads();
+                if (tid == 0) for (int t = U.rowptr[r]; t < U.rowptr[r + 1]; t++) rhs1k[U.col[t]] = rhs1k[U.col[t]] + U.val[t];
+                __syncthreads();
+                FOR_T(j, n) rhs1k[j] = rhs1k[j] / xe[j];
+            } else {
+                const double *g = A.g + at * n;
+                FOR_T(j, np + m) rhs1k[j] = j < n ? g[j] / xe[j] : 0.;
+            }
+            __syncthreads();
+            kkt_solve<T, NLDS, I16, 1, false, false, true>(ps, I, I, W, ST_KKT1, 1);
+        }
+        gcdbl_p dx = W + P.w_dx1, dy = W + P.w_dy1, dz = W + P.w_dz1;
+        if (!A.J) {
+            if (A.grad_c) { FOR_T(j, n) A.grad_c[at * n + j] = ok ? -(dx[j] / xe[j]) : nan; }
+            if (A.grad_h) { FOR_T(i, m) A.grad_h[at * m + i] = ok ? dz[i] / ge[i] : nan; }
+            if (A.grad_b) { FOR_T(q, p) A.grad_b[at * p + q] = ok ? dy[q] / ae[q] : nan; }
+        } else {
+            const ParamMapDev M = *A.pmap;
+            const int k = M.k;
+            for (int t0 = 0; t0 < k; t0 += 8) {
+                double acc[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
+                if (ok) FOR_T(e, n + m + p) {
+                    const int grp = e < n ? 0 : (e < n + m ? 1 : 2), q = e - (grp == 0 ? 0 : (grp == 1 ? n : n + m));
+                    const AffineDev G = M.g[grp];
+                    if (!G.base) continue;
+                    const double gr = grp == 0 ? -(dx[q] / xe[q]) : (grp == 1 ? dz[q] / ge[q] : dy[q] / ae[q]);
+                    for (int t = G.rowptr[q]; t < G.rowptr[q + 1]; t++) {
+                        const int c = G.col[t] - t0;
+                        const double v = gr * G.val[t];
+#pragma unroll
+                        for (int u = 0; u < 8; u++) acc[u] += (c == u) ? v : 0.;
+                    }
+                }
+                blk_reduce<OpSum, T, 8>(phase, acc);
+                if (tid < 8 && t0 + tid < k) {
+                    double v = acc[0];
+#pragma unroll
+                    for (int u = 1; u < 8; u++) v = (tid == u) ? acc[u] : v;
+                    A.J[at * k + t0 + tid] = ok ? v : nan;
+                }
+            }
+        }
+        if (A.res && tid == 0) A.res[at] = ok ? g_S.dots[1][0] : nan;
+    }
+    __syncthreads();
+}
+
 template <int T, int NLDS, bool I16>
 __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     int ps, double *inst, double *work, int B, int *queue, const int *order, double warm, double dyn_delta, double dyn_eps, SolveCfg cfg, UpdArgs upd) {
@@ -3635,6 +3789,56 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
         g = g_S.next;
     }
 }
+// The adjoint launch (launch.hpp: AdjointLaunch; eicos_batch_adjoint, _output_jacobian): k_solve's workgroup set-up -- slice tables and, per
+// build, the slabs or U in LDS -- around adjoint_instance instead of the solve.  A kernel of its own, so that no k_solve instantiation
+// changes by a register or a byte.  Every instance costs the same (one factorisation, nrhs refined solves): the workgroups stride
+// through the rows, no queue and no launch order.  list != NULL: row q belongs to instance list[q] (distinct ids, checked by the host).
+// Nothing goes back to the slabs in HBM in the LDS-resident build: the launch leaves no state behind.
+template <int T, int NLDS, bool I16>
+__global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_adjoint(
+    int ps, const double *inst, double *work, int count, const int *list, double dyn_delta, double dyn_eps, SolveCfg cfg, const AdjointDev *adj) {
+    const DevPat &P = c_pat[ps];
+#if EICOS_LDSRES
+    gdbl_p W = (gdbl_p)(g_dyn + P.lr_work), Il = (gdbl_p)(g_dyn + P.lr_inst);
+    const double *Wglob = work + (size_t)blockIdx.x * P.work_stride;
+    for (int q = threadIdx.x; q < (int)P.work_stride; q += T) W[q] = Wglob[q]; // (the zero padding slots)
+#else
+    gdbl_p W = (gdbl_p)work + (size_t)blockIdx.x * P.work_stride;
+#endif
+    if constexpr (NLDS >= 1) {
+        int *dst = reinterpret_cast<int *>(g_dyn + P.lds_tab);
+        auto stage = [&](const PackedSlice EICOS_GLOBAL *src, int cnt, int at) {
+            gint_p si = reinterpret_cast<gint_p>(src);
+            for (int q = threadIdx.x; q < cnt * 4; q += T) dst[at * 4 + q] = si[q];
+        };
+        stage(P.fsl, P.nfs + P.nfs_solo + P.nfs_ext, P.lm_f); stage(P.bsl, P.nbs + P.nbs_solo, P.lm_b); stage(P.cag_sl, P.cag_ns, P.lm_cag);
+        stage(P.rA_sl, P.rA_ns, P.lm_rA); stage(P.rG_sl, P.rG_ns, P.lm_rG);
+        if (P.lm_fac >= 0) stage(P.fac_sl, P.fac_ns, P.lm_fac);
+        __syncthreads();
+    }
+#if EICOS_UBL
+    for (int q = threadIdx.x; q < P.ub_len; q += T) g_dyn[P.ub_lds + q] = 0.;
+    __syncthreads();
+#endif
+    if (threadIdx.x == 0) { g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.cfg = cfg; g_S.step = 0; g_S.smap = nullptr; g_S.attempt = 0; g_S.swapped = 0; g_S.rows_at = 0; }
+    for (int q = blockIdx.x; q < count; q += (int)gridDim.x) {
+        const int id = uni(list ? list[q] : q);
+#if EICOS_LDSRES
+        gdbl_p I = Il;
+        {
+            const double *Ig = inst + (size_t)id * P.inst_stride;
+            __syncthreads();
+            for (int e = threadIdx.x; e < (int)P.inst_stride; e += T) Il[e] = Ig[e];
+            __syncthreads();
+        }
+#else
+        gdbl_p I = (gdbl_p)const_cast<double *>(inst) + (size_t)id * P.inst_stride; // (written: the scaling block i_Vv alone, which every solve's prologue resets)
+        if (threadIdx.x == 0) { g_S.vals = inst + (size_t)id * P.inst_stride; g_S.vshared = 0; } // (the instance's own product values: the same bits as a shared copy)
+#endif
+        adjoint_instance<T, NLDS, I16>(ps, I, W, adj, q);
+    }
+}
+
 // Longest-processing-time-first order for k_solve's queue: instances keyed by the number of LDL solves of their
 // previous solve (DevInfo::n_ldlsolve; 0 before the first solve), counting sort, descending.  One workgroup.
 // snake (one-round launches: B <= resident workgroups, several per CU): workgroup g lands on CU g mod ncu, so the instances are laid out
@@ -4144,6 +4348,25 @@ static hipError_t launch_solve(const SolveLaunch &launch, hipStream_t st, const 
         return hipLaunchKernel(fn, dim3(L.grid), dim3(L.threads), args, L.dyn_lds, st);
     });
 }
+// the k_adjoint instantiation that matches a handle's k_solve, with the same launch shape (launch.hpp: AdjointLaunch)
+template <class F> static auto dispatch_adjoint(int nlds, int idx16, F &&f) {
+    auto byI = [&](auto ic) {
+        constexpr bool I16 = decltype(ic)::value;
+        if (nlds >= 2) return f((const void *)k_adjoint<SOLVE_T, 2, I16>);
+        if constexpr (EICOS_LDSRES != 0 || EICOS_UBL != 0) return f((const void *)k_adjoint<SOLVE_T, 1, I16>);
+        else return nlds == 1 ? f((const void *)k_adjoint<SOLVE_T, 1, I16>) : f((const void *)k_adjoint<SOLVE_T, 0, I16>);
+    };
+    return idx16 ? byI(std::true_type{}) : byI(std::false_type{});
+}
+static hipError_t launch_adjoint(const AdjointLaunch &launch, hipStream_t st) {
+    AdjointLaunch L = launch;
+    if (L.count <= 0) return hipSuccess;
+    if (L.count > L.batch || L.grid <= 0 || !L.adj) return hipErrorInvalidValue;
+    return dispatch_adjoint(L.nlds, L.idx16, [&](const void *fn) {
+        void *args[] = {&L.ps, &L.inst, &L.work, &L.count, &L.list, &L.dyn_delta, &L.dyn_eps, &L.cfg, &L.adj};
+        return hipLaunchKernel(fn, dim3(L.grid < L.count ? L.grid : L.count), dim3(L.threads), args, L.dyn_lds, st);
+    });
+}
 #if EICOS_MAIN_BUILD
 hipError_t launch_update(int ps, double *inst, int first, int count, const double *Gpr, const double *Apr,
                          const double *c, const double *h, const double *b, double *scratch, int grid, size_t lds_bytes, int vals_in_lds, hipStream_t st,
@@ -4268,7 +4491,11 @@ static hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn
     // The attribute belongs to the kernel, not to a handle: several live handles (other patterns, the shards of an eicos_multi on one
     // device) launch the same instantiation with different dynamic LDS sizes, so it is always raised to the device's ceiling (160 KB
     // minus the 4 KB budgeted for the static block) and never lowered; the size a launch really uses is its own dyn_lds.
-    return dispatch_solve(nlds, idx16, [&](const void *fn) {
+    const hipError_t e = dispatch_solve(nlds, idx16, [&](const void *fn) {
+        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
+    });
+    if (e != hipSuccess) return e;
+    return dispatch_adjoint(nlds, idx16, [&](const void *fn) { // (the adjoint kernel of the same instantiation takes the same launch shape)
         return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
     });
 }
@@ -4277,7 +4504,7 @@ static hipError_t upload_pattern(int ps, const DevPat &P) {
     if (ps < 0 || ps >= MAX_PATTERNS) return hipErrorInvalidValue;
     return hipMemcpyToSymbol(HIP_SYMBOL(c_pat), &P, sizeof(DevPat), (size_t)ps * sizeof(DevPat), hipMemcpyHostToDevice);
 }
-SolveBuild solve_entries() { return {launch_solve, solve_occupancy, solve_set_max_lds, upload_pattern}; } // (launch.hpp: one per build namespace)
+SolveBuild solve_entries() { return {launch_solve, solve_occupancy, solve_set_max_lds, upload_pattern, launch_adjoint}; } // (launch.hpp: one per build namespace)
 #endif // EICOS_ISA_PROBE
 #if EICOS_LDSRES
 } // namespace ldsres

@@ -94,12 +94,31 @@ struct SolveLaunch {
     const int *list; int batch, full_grid; // subset launches: the chosen ids, the handle's batch and its whole-batch grid
     int *rows; // subset launches with a step in list order (UpdArgs::rows_at): the selection kernel leaves rows[list[q]] = q here; NULL: not asked for
 };
-// One k_solve build = these four entry points.  launch always receives an UpdArgs: UpdArgs{} when no step is fused into it.
+// Adjoint sensitivities (eicos_batch_adjoint, _output_jacobian), one record per launch in device memory.  Row q of every
+// array belongs to the q-th instance of the launch.
+// J == NULL, the gradient form: g [count][nrhs][n] in, grad_c [count][nrhs][n], grad_h [count][nrhs][m], grad_b [count][nrhs][p] and
+// res [count][nrhs] out, any of the four NULL = not wanted.
+// J != NULL, the Jacobian form: the right-hand sides are the omap->r rows of the output map, and every gradient is contracted with the
+// rows of the parameter map on the spot: J [count][r][k], res [count][r]; g, grad_* and nrhs are unused.
+struct AdjointDev {
+    int nrhs; const double *g; double *grad_c, *grad_h, *grad_b, *res;
+    const ParamMapDev *pmap; const OutMapDev *omap; double *J;
+};
+// One k_adjoint launch of a handle: the pattern slot, the slabs and the launch shape of its solves, the settings its kkt_solve and its
+// factorisation run under (by value), `count` instances -- list != NULL: those ids (device memory, distinct, inside [0, batch)), else
+// 0 .. count-1 -- and the record.  The grid is min(grid, count): every workgroup owns the workspace slab of its index.
+struct AdjointLaunch {
+    int ps; const double *inst; double *work; int count; const int *list; int batch;
+    int grid, threads, nlds, idx16; double dyn_delta, dyn_eps; SolveCfg cfg; size_t dyn_lds;
+    const AdjointDev *adj;
+};
+// One k_solve build = these five entry points.  launch always receives an UpdArgs: UpdArgs{} when no step is fused into it.
 struct SolveBuild {
     hipError_t (*launch)(const SolveLaunch &L, hipStream_t st, const UpdArgs &upd);
     hipError_t (*occupancy)(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
     hipError_t (*set_max_lds)(int threads, int nlds, int idx16, size_t dyn_lds);
     hipError_t (*upload)(int ps, const DevPat &P);
+    hipError_t (*adjoint)(const AdjointLaunch &L, hipStream_t st);
     bool operator==(const SolveBuild &o) const { return launch == o.launch; }
 };
 // The range launchers below (updateData in its four kinds and the output map) take an optional `list`: `count` ids of distinct instances

@@ -478,6 +478,56 @@ int eicos_multi_outputs_indexed(eicos_multi *mh, const int *idx, int count, doub
     });
 }
 
+// Adjoint sensitivities with global ids (eicos_batch_adjoint / _output_jacobian per shard), host arrays in list order; idx == NULL:
+// instances 0 .. count-1.  The calls change no state, so a shard's refusal (no maps, a matrix map, nrhs) leaves nothing behind either.
+static int adjoint_shares(eicos_multi *mh, const int *idx, int count, const char *who, Shares &sh) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    if (idx) return split_list(mh, idx, count, who, sh);
+    if (count < 0 || count > mh->batch) return mfail(EICOS_E_INVALID, std::string(who) + ": count must lie in [0, batch] when idx is NULL (instances 0 .. count-1)");
+    std::vector<int> all((size_t)count);
+    for (int q = 0; q < count; q++) all[q] = q;
+    return split_list(mh, all.data(), count, who, sh);
+}
+
+int eicos_multi_adjoint(eicos_multi *mh, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b,
+                        double *res) {
+    Shares sh;
+    const int rc = adjoint_shares(mh, idx, count, "eicos_multi_adjoint", sh);
+    if (rc != EICOS_OK) return rc;
+    if (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS) return mfail(EICOS_E_INVALID, "eicos_multi_adjoint: nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
+    if (!g && count > 0 && mh->n > 0) return mfail(EICOS_E_INVALID, "eicos_multi_adjoint: g is NULL");
+    return for_shards(mh, [&](int s) {
+        const std::vector<int> &pos = sh.pos[s];
+        if (pos.empty()) return (int)EICOS_OK;
+        const size_t k = pos.size();
+        const std::vector<double> tg = pack(g, pos, nrhs * mh->n);
+        std::vector<double> tc(grad_c ? k * nrhs * mh->n : 0), th(grad_h ? k * nrhs * mh->m : 0), tb(grad_b ? k * nrhs * mh->p : 0), tr(res ? k * nrhs : 0);
+        const int e = eicos_batch_adjoint(mh->shard[s], sh.ids[s].data(), (int)k, nrhs, given(g, tg), grad_c ? tc.data() : nullptr,
+                                          grad_h ? th.data() : nullptr, grad_b ? tb.data() : nullptr, res ? tr.data() : nullptr);
+        if (e != EICOS_OK) return e;
+        unpack(grad_c, tc, pos, nrhs * mh->n); unpack(grad_h, th, pos, nrhs * mh->m); unpack(grad_b, tb, pos, nrhs * mh->p); unpack(res, tr, pos, nrhs);
+        return (int)EICOS_OK;
+    });
+}
+
+int eicos_multi_output_jacobian(eicos_multi *mh, const int *idx, int count, double *J, double *res) {
+    Shares sh;
+    const int rc = adjoint_shares(mh, idx, count, "eicos_multi_output_jacobian", sh);
+    if (rc != EICOS_OK) return rc;
+    if (!J && count > 0) return mfail(EICOS_E_INVALID, "eicos_multi_output_jacobian: J is NULL");
+    const int r = std::max(0, eicos_batch_output_count(mh->shard[0])), kp = std::max(0, eicos_batch_param_count(mh->shard[0]));
+    return for_shards(mh, [&](int s) {
+        const std::vector<int> &pos = sh.pos[s];
+        if (pos.empty()) return (int)EICOS_OK;
+        // (a handle without its maps: one row, so that the shard's own refusal and message come back)
+        std::vector<double> tj(std::max<size_t>(1, pos.size() * (size_t)r * kp)), tr(res ? std::max<size_t>(1, pos.size() * (size_t)r) : 0);
+        const int e = eicos_batch_output_jacobian(mh->shard[s], sh.ids[s].data(), (int)pos.size(), tj.data(), res ? tr.data() : nullptr);
+        if (e != EICOS_OK) return e;
+        unpack(J, tj, pos, r * kp); unpack(res, tr, pos, r);
+        return (int)EICOS_OK;
+    });
+}
+
 int eicos_multi_update_param_solve_subset(eicos_multi *mh, const int *idx, int count, const double *theta, double *u_out, double *x_out,
                                           int *exitcodes) {
     Shares sh;

@@ -433,6 +433,28 @@ namespace EiCOS
             for (size_t i = 0; i < indices.size(); i++) out[i] = static_cast<exitcode>(codes[i]);
             return out;
         }
+        // Extension: adjoint sensitivities at the returned iterate (eicos_multi_adjoint / _output_jacobian; the definition and its
+        // degeneracy caveat: eicos_amd.h).  adjoint: g [count][nrhs][n] in, grad_c [count][nrhs][n], grad_h [count][nrhs][m],
+        // grad_b [count][nrhs][p], res [count][nrhs] out (any nullptr) -- the gradient of g'x with respect to (c, h, b); an instance whose
+        // last solve did not end OPTIMAL / OPTIMAL_INACC gets NaN rows.  outputJacobian: J [count][r][k] = du / dtheta under the installed
+        // parameter and output maps, res [count][r] (optional).  The whole batch, or the instances `indices` in list order.  Nothing a
+        // later call reads is changed.
+        void adjoint(int nrhs, const double *g, double *grad_c, double *grad_h = nullptr, double *grad_b = nullptr, double *res = nullptr)
+        {
+            mcheck(eicos_multi_adjoint(h_, nullptr, batch_, nrhs, g, grad_c, grad_h, grad_b, res), "eicos_multi_adjoint");
+        }
+        void adjoint(const std::vector<int> &indices, int nrhs, const double *g, double *grad_c, double *grad_h = nullptr, double *grad_b = nullptr,
+                     double *res = nullptr)
+        {
+            if (indices.empty()) return;
+            mcheck(eicos_multi_adjoint(h_, indices.data(), (int)indices.size(), nrhs, g, grad_c, grad_h, grad_b, res), "eicos_multi_adjoint");
+        }
+        void outputJacobian(double *J, double *res = nullptr) { mcheck(eicos_multi_output_jacobian(h_, nullptr, batch_, J, res), "eicos_multi_output_jacobian"); }
+        void outputJacobian(const std::vector<int> &indices, double *J, double *res = nullptr)
+        {
+            if (indices.empty()) return;
+            mcheck(eicos_multi_output_jacobian(h_, indices.data(), (int)indices.size(), J, res), "eicos_multi_output_jacobian");
+        }
         void solveAsync() { mcheck(eicos_multi_solve_async(h_), "eicos_multi_solve_async"); } // enqueue on every shard's stream
         void sync() { mcheck(eicos_multi_sync(h_), "eicos_multi_sync"); }
         std::vector<double> solution() const

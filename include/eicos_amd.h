@@ -388,6 +388,46 @@ int eicos_batch_set_iterate_indexed_device(eicos_batch *hd, const int *idx, int 
  * map, NULL u, a device pointer handed to the host form) and of the list check. */
 int eicos_batch_outputs_indexed(eicos_batch *hd, const int *idx, int count, double *u /* host [count][r] */);
 int eicos_batch_outputs_indexed_device(eicos_batch *hd, const int *idx, int count, double *du);
+/* ---- Adjoint sensitivities: gradients through a solve, and the Jacobian of the output map ----
+ * Definition.  For an instance whose last solve ended OPTIMAL or OPTIMAL_INACC (codes 0 and 10), with the returned (x, y, z, s) and the
+ * caller's un-equilibrated A, G:
+ *
+ *     K = [ 0  A'  G' ]      W^2 = the NT scaling of (s, z): s_i / z_i on an LP row, eta^2 * Wbar^2 per second-order cone
+ *         [ A  0   0  ]            (what every pass of the solve puts into its KKT matrix)
+ *         [ G  0  -W^2]
+ *     K [w_x; w_y; w_z] = [g; 0; 0],      grad_c = -w_x,   grad_b = w_y,   grad_h = w_z
+ *
+ * (grad_c, grad_h, grad_b) is the gradient of l = g'x with respect to (c, h, b).  It is exact for the central-path point at the
+ * iterate's mu, where ds = -W^2 dz holds exactly, and therefore the derivative of the solution map wherever that derivative exists: a
+ * unique solution and strict complementarity.  ELSEWHERE -- a degenerate or non-unique optimum -- IT IS A SMOOTHED VALUE, not a
+ * derivative: K is then close to singular and the result depends on where on the central path the solve stopped.
+ * With a parameter map c = c0 + C theta, h = h0 + H theta, b = b0 + B theta and an output map u = u0 + U x, row i of the Jacobian
+ * du / dtheta is J[i, :] = grad_c(U_i)' C + grad_h(U_i)' H + grad_b(U_i)' B: r adjoint solves instead of k forward solves.
+ * Invariances: W does not change under the common 1 / tau scaling of the embedding; equilibration enters as K = D^-1 K~ D^-1 with
+ * D = diag(1 / xe, 1 / ae, 1 / ge), so w = D K~^-1 D rhs; the static regularisation of the factor is removed by the iterative refinement
+ * of the KKT solve against the unregularised system, as in a solve.
+ * Cost: one factorisation and nrhs refined KKT solves per instance, in one launch over the chosen instances, under the handle's
+ * linsysacc, irerrfact, nitref and dynamic regularisation (the refinement takes one step beyond the linsysacc threshold: the small
+ * components of w, grad_c at a vertex, converge later than the error norm shows).
+ *
+ * eicos_batch_adjoint: idx = a host list of `count` distinct ids, or NULL = instances 0 .. count-1; g [count][nrhs][n], 1 <= nrhs <=
+ * EICOS_ADJOINT_MAX_RHS; outputs (host, each optional) grad_c [count][nrhs][n], grad_h [count][nrhs][m], grad_b [count][nrhs][p] and
+ * res [count][nrhs] = the error norm at which the refinement of that KKT solve stopped, divided by 1 + |rhs|_inf, in the equilibrated
+ * space in which it is measured.  An instance whose last solve did not end OPTIMAL / OPTIMAL_INACC, or whose recomputed scalings or
+ * factorisation fail, gets NaN in every row and in res; the call still returns EICOS_OK.  Synchronous.
+ * eicos_batch_output_jacobian / _device: J [count][r][k] and res [count][r] (optional) from the installed parameter and output maps; the
+ * right-hand sides are the rows of U and the gradients are contracted on the GPU without being stored.  The device form takes J and res in
+ * device memory and is asynchronous on the handle's stream; both forms return the same bits.
+ * Refusals (EICOS_E_INVALID with a message, nothing changed): a duplicate or out-of-range id, nrhs outside its range, NULL g or J,
+ * output_jacobian without a parameter map and an output map, or with a matrix map installed (its derivative has dG and dA terms, which
+ * are not formed).
+ * An adjoint call changes nothing a later call reads: x, y, z, s, every info field, the retry counts and what a warm start takes from the
+ * previous solve stay as they are (eicos_debug_kkt afterwards shows the scaling block at the returned iterate). */
+#define EICOS_ADJOINT_MAX_RHS 64
+int eicos_batch_adjoint(eicos_batch *hd, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h,
+                        double *grad_b, double *res);
+int eicos_batch_output_jacobian(eicos_batch *hd, const int *idx, int count, double *J, double *res);
+int eicos_batch_output_jacobian_device(eicos_batch *hd, const int *idx, int count, double *dJ, double *dres);
 /* eicos_batch_update_param_solve_subset: the closed-loop step over a subset = eicos_batch_update_param_indexed + eicos_batch_solve_subset
  * + eicos_batch_outputs_indexed (+ the x rows), every array in list order; synchronous.
  * Fused under exactly the conditions of eicos_batch_update_param_solve (an LDS vector, a theta row that fits it, GPU-addressable theta,
@@ -575,6 +615,8 @@ int eicos_batch_set_stream(eicos_batch *hd, void *hip_stream);
 /* HIP-event timing of the most recent solve / update kernels on the handle's stream (ms). */
 int eicos_batch_last_solve_ms(eicos_batch *hd, float *ms);
 int eicos_batch_last_update_ms(eicos_batch *hd, float *ms);
+/* ... and of the kernel of the most recent eicos_batch_adjoint / _output_jacobian call (ms) */
+int eicos_batch_last_adjoint_ms(eicos_batch *hd, float *ms);
 /* The durations (ms) of the most recent launches, oldest first: which = 0 the solve launches, 1 the updateData calls, 2 the span of a
  * whole step (start of the updateData call that preceded a solve launch -> end of that solve; meaningful when the two alternate).  The handle keeps a
  * ring of 64 event pairs, so a caller that enqueues K steps back to back (update + solve_async, no host synchronisation in between) can
@@ -689,6 +731,10 @@ int eicos_multi_update_rhs_indexed(eicos_multi *mh, const int *idx, int count, c
 int eicos_multi_update_param_indexed(eicos_multi *mh, const int *idx, int count, const double *theta);
 int eicos_multi_set_iterate_indexed(eicos_multi *mh, const int *idx, int count, const double *x, const double *y, const double *z, const double *s);
 int eicos_multi_outputs_indexed(eicos_multi *mh, const int *idx, int count, double *u);
+/* adjoint sensitivities (eicos_batch_adjoint, _output_jacobian) with GLOBAL ids and host arrays in list order; idx NULL = 0 .. count-1 */
+int eicos_multi_adjoint(eicos_multi *mh, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h,
+                        double *grad_b, double *res);
+int eicos_multi_output_jacobian(eicos_multi *mh, const int *idx, int count, double *J, double *res);
 int eicos_multi_update_param_solve_subset(eicos_multi *mh, const int *idx, int count, const double *theta, double *u_out, double *x_out,
                                           int *exitcodes);
 /* results gathered into the caller's host arrays in global instance order (the "gather" of north_star: per-device copies) */
