@@ -237,6 +237,16 @@ def _lib():
             for f in ("adjoint", "output_jacobian"):
                 getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
             L.eicos_batch_output_jacobian_device.restype = C.c_int
+        if hasattr(L, "eicos_batch_adjoint_data"):
+            L.eicos_batch_adjoint_data.argtypes = L.eicos_multi_adjoint_data.argtypes = [vp, ip, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp]
+            L.eicos_batch_param_jacobian.argtypes = L.eicos_multi_param_jacobian.argtypes = [vp, ip, C.c_int, dp, dp]
+            L.eicos_batch_param_gradient.argtypes = L.eicos_multi_param_gradient.argtypes = [vp, ip, C.c_int, C.c_int, dp, dp, dp]
+            L.eicos_batch_param_jacobian_device.argtypes = [vp, ip, C.c_int, vp, vp]
+            L.eicos_batch_param_gradient_device.argtypes = [vp, ip, C.c_int, C.c_int, vp, vp, vp]
+            L.eicos_batch_matrix_map_count.argtypes = L.eicos_multi_matrix_map_count.argtypes = [vp]
+            for f in ("adjoint_data", "param_jacobian", "param_gradient", "matrix_map_count"):
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+            L.eicos_batch_param_jacobian_device.restype = L.eicos_batch_param_gradient_device.restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -974,6 +984,88 @@ class _Solver:
             hip.hipFree(dJ); hip.hipFree(dres)
         return J, res
 
+    # ---- ... with respect to the matrix data (eicos_batch_adjoint_data, _param_jacobian, _param_gradient) ----
+    def _adjoint_g(self, g, count):
+        g = np.ascontiguousarray(g, dtype=np.float64)
+        if g.ndim == 2:
+            g = g[:, None, :]
+        if g.ndim != 3 or g.shape[0] != count or g.shape[2] != self.pat.n:
+            raise ValueError(f"g must have shape [{count}, nrhs, {self.pat.n}], not {g.shape}")
+        return g
+
+    def adjoint_data(self, g, idx=None):
+        """adjoint() with the gradients with respect to the stored values of G and A: returns (grad_c, grad_h, grad_b, grad_G
+        [count, nrhs, nnzG], grad_A [count, nrhs, nnzA], res), the matrix gradients in the CSC order of Gpr / Apr --
+        grad_G[e] = grad_c[j] z[i] - grad_h[i] x[j] and grad_A[e] = grad_c[j] y[i] - grad_b[i] x[j] for the stored value e = (i, j).
+        grad_c, grad_h, grad_b and res are the bits of adjoint(); no further factorisation or KKT solve."""
+        ptr, count = self._adjoint_rows(idx)
+        pat = self.pat
+        g = self._adjoint_g(g, count)
+        nrhs = int(g.shape[1])
+        gc, gh, gb, gG, gA, res = (np.zeros((count, nrhs, w)) for w in (pat.n, pat.m, pat.p, pat.nnzG, pat.nnzA, 1))
+        self._call("adjoint_data", ptr, count, nrhs, *[_dp(a) if a.size else None for a in (g, gc, gh, gb, gG, gA)], _dp(res) if res.size else None)
+        return gc, gh, gb, gG, gA, res[:, :, 0]
+
+    def matrix_map_count(self) -> int:
+        """k the installed matrix map was validated for, 0 without one."""
+        return int(getattr(_lib(), self._prefix + "matrix_map_count")(self._h))
+
+    def _theta_width(self):
+        return max(self.param_count(), 0) or max(self.matrix_map_count(), 0)
+
+    def _device_form(self, name, ptr, count, head, ins, outs):
+        """A *_device call on host arrays: device copies of `ins`, the call, sync, `outs` fetched -- the same bits as the host form."""
+        if self._prefix != "eicos_batch_":
+            raise ValueError(name + ": device=True needs a single-GPU handle")
+        hip = _lib()
+        hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        hip.hipFree.argtypes = [C.c_void_p]
+        bufs = []
+        try:
+            for a in list(ins) + list(outs):
+                d = C.c_void_p()
+                if hip.hipMalloc(C.byref(d), max(a.nbytes, 8)) != 0:
+                    raise RuntimeError("hipMalloc failed")
+                bufs.append(d)
+            for a, d in zip(ins, bufs):
+                if a.nbytes and hip.hipMemcpy(d, a.ctypes.data, a.nbytes, 1) != 0:  # hipMemcpyHostToDevice
+                    raise RuntimeError("hipMemcpy failed")
+            self._call(name, ptr, count, *head, *bufs)
+            self._call("sync")
+            for a, d in zip(outs, bufs[len(ins):]):
+                if a.nbytes and hip.hipMemcpy(a.ctypes.data, d, a.nbytes, 2) != 0:  # hipMemcpyDeviceToHost
+                    raise RuntimeError("hipMemcpy failed")
+        finally:
+            for d in bufs:
+                hip.hipFree(d)
+
+    def param_jacobian(self, idx=None, device=False):
+        """(J [count, r, k], res [count, r]): du / dtheta through the output map and whichever of the parameter map and the matrix map
+        are installed -- the matrix terms grad_G' M_G + grad_A' M_A join the contraction on the GPU.  Without a matrix map: the bits of
+        output_jacobian().  device=True (single-GPU handles): through the device form, fetched here; the same bits."""
+        ptr, count = self._adjoint_rows(idx)
+        r, k = max(self.output_count(), 0), self._theta_width()
+        J, res = np.zeros((count, r, k)), np.zeros((count, r))
+        if device:
+            self._device_form("param_jacobian_device", ptr, count, (), (), (J, res))
+        else:
+            self._call("param_jacobian", ptr, count, _dp(J) if J.size else _dp(np.zeros(1)), _dp(res) if res.size else None)
+        return J, res
+
+    def param_gradient(self, g, idx=None, device=False):
+        """(grad_theta [count, nrhs, k], res [count, nrhs]): the gradient of g'x with respect to theta through the installed parameter
+        and matrix maps, g [count, nrhs, n]; no output map is needed.  device=True as in param_jacobian()."""
+        ptr, count = self._adjoint_rows(idx)
+        g = self._adjoint_g(g, count)
+        nrhs = int(g.shape[1])
+        gt, res = np.zeros((count, nrhs, self._theta_width())), np.zeros((count, nrhs))
+        if device:
+            self._device_form("param_gradient_device", ptr, count, (nrhs,), (g,), (gt, res))
+        else:
+            self._call("param_gradient", ptr, count, nrhs, _dp(g) if g.size else None, _dp(gt) if gt.size else _dp(np.zeros(1)), _dp(res) if res.size else None)
+        return gt, res
+
     def update_param_solve_subset(self, indices, theta, u_out=None, x_out=None):
         """The closed-loop step over the instances `indices` in one call: update_param_indexed + solve_subset + outputs_indexed, theta
         [len(indices), k], u_out [len(indices), r] and x_out [len(indices), n] in list order -- with pinned / registered theta ONE subset
@@ -1166,6 +1258,17 @@ class BatchSolver(_Solver):
         """output_jacobian() into raw device pointers (int): J [count, r, k] and, optionally, res [count, r]; asynchronous (sync() waits)."""
         ptr, count = self._adjoint_rows(idx)
         self._call("output_jacobian_device", ptr, count, C.c_void_p(int(dJ) or None), C.c_void_p(int(dres) or None))
+
+    def param_jacobian_device(self, dJ, dres=0, idx=None):
+        """param_jacobian() into raw device pointers (int): J [count, r, k] and, optionally, res [count, r]; asynchronous (sync() waits)."""
+        ptr, count = self._adjoint_rows(idx)
+        self._call("param_jacobian_device", ptr, count, C.c_void_p(int(dJ) or None), C.c_void_p(int(dres) or None))
+
+    def param_gradient_device(self, nrhs, dg, dgrad_theta, dres=0, idx=None):
+        """param_gradient() on raw device pointers (int): g [count, nrhs, n] in, grad_theta [count, nrhs, k] and, optionally, res
+        [count, nrhs] out; asynchronous on the handle's stream (sync() waits) -- what a training loop on the GPU calls."""
+        ptr, count = self._adjoint_rows(idx)
+        self._call("param_gradient_device", ptr, count, int(nrhs), *[C.c_void_p(int(q) or None) for q in (dg, dgrad_theta, dres)])
 
     def set_stream(self, stream_ptr: int):
         self._call("set_stream", C.c_void_p(int(stream_ptr) or None))

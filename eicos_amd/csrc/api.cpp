@@ -172,9 +172,10 @@ struct eicos_batch {
     // every launch that may leave the word above at 0 (launch_range) -- so its contents are valid exactly while the word is 0, and only the
     // stages' PLAIN instantiations, which run exactly then, read it.  Empty: not on this handle (eicos_dims.shared_operands = 0).
     DevBuf d_shop;
-    // Adjoint sensitivities (eicos_batch_adjoint, _output_jacobian): one device allocation, made by the first call and grown on
-    // demand: [AdjointDev (MAP_HEADER bytes) | ids [batch] | g | grad_c | grad_h | grad_b | res] -- the record of the launch, its index
-    // list and the staging of the host forms' rows (the Jacobian form keeps J where grad_c would be)
+    // Adjoint sensitivities (eicos_batch_adjoint, _adjoint_data, _output_jacobian, _param_jacobian, _param_gradient): one device
+    // allocation, made by the first call and grown on demand: [AdjointDev (MAP_HEADER bytes) | ids [batch] | g | grad_c | grad_h | grad_b | res |
+    // grad_G | grad_A] -- the record of the launch, its index list and the staging of the host forms' rows (the contracted forms keep J /
+    // grad_theta where grad_c would be)
     DevBuf d_adj; AdjointDev adj{}; // (adj: the host copy of the most recent launch's record, the source of its copy on the handle's stream)
     hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr; bool adjoint_timed = false; // HIP events around the most recent adjoint launch (eicos_batch_last_adjoint_ms)
 
@@ -1719,15 +1720,18 @@ int eicos_batch_outputs_indexed_device(eicos_batch *h, const int *idx, int count
     return outputs_indexed(h, idx, count, du, false, "eicos_batch_outputs_indexed_device");
 }
 
-// ---- adjoint sensitivities (include/eicos_amd.h) ----
+// ---- adjoint sensitivities (include/eicos_amd.h): eicos_batch_adjoint, _adjoint_data, _output_jacobian, _param_jacobian, _param_gradient ----
 // One launch of the handle's adjoint kernel (launch.hpp: AdjointLaunch) behind everything on the handle's stream, under the handle's settings
 // and dynamic regularisation.  Every check stands in front of the first enqueue: a refused call changes nothing.
 namespace {
 struct AdjointCall {
     const int *idx; int count, nrhs; // nrhs: right-hand sides per instance (the Jacobian form: r)
-    const double *g; double *grad_c, *grad_h, *grad_b, *res, *J; // host arrays of the gradient form; J / res of the Jacobian form
-    bool jac, device; // the Jacobian form; its J and res live in device memory (asynchronous)
+    const double *g; double *grad_c, *grad_h, *grad_b, *res, *J; // host arrays of the gradient form; J / res of the contracted form
+    bool jac, device; // the contracted form (launch.hpp: AdjointDev::J); its J, res and g live in device memory (asynchronous)
+    double *grad_G = nullptr, *grad_A = nullptr; // the gradient form: the matrix gradients (host, optional)
+    bool mmap = false, grows = false; // the contracted form: the matrix map joins when one is installed; the right-hand sides are nrhs rows of g
 };
+static_assert(sizeof(AdjointDev) <= MAP_HEADER, "the adjoint record larger than its header");
 }
 static int adjoint_list_fault(const eicos_batch *h, const int *idx, int count, const char *who) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
@@ -1738,17 +1742,20 @@ static int adjoint_list_fault(const eicos_batch *h, const int *idx, int count, c
 static int adjoint_run(eicos_batch *h, const AdjointCall &c) {
     if (c.count == 0) return EICOS_OK;
     const DevPat &D = h->dp;
-    const size_t rows = (size_t)c.count * c.nrhs, k = c.jac ? (size_t)h->param.k : 0;
+    const size_t rows = (size_t)c.count * c.nrhs, k = c.jac ? (size_t)std::max(h->param.k, c.mmap ? h->mat.k : 0) : 0;
+    const bool up_g = !c.jac || (c.grows && !c.device); // g comes from the host
     HIP_TRY(hipSetDevice(h->device));
     if (!c.device) HIP_TRY(hipStreamSynchronize(h->stream));
-    // the allocation: record | ids | g | grad_c (or J) | grad_h | grad_b | res, every part 64-byte aligned
+    // the allocation: record | ids | g | grad_c (or J) | grad_h | grad_b | res | grad_G | grad_A, every part 64-byte aligned
     auto pad = [](size_t b) { return (b + 63) & ~(size_t)63; };
     const size_t at_ids = MAP_HEADER, at_g = at_ids + pad((size_t)h->batch * sizeof(int));
-    const size_t at_c = at_g + pad(c.jac ? 0 : rows * D.n * sizeof(double));
+    const size_t at_c = at_g + pad(up_g ? rows * D.n * sizeof(double) : 0);
     const size_t at_h = at_c + pad((c.jac ? (c.device ? 0 : rows * k) : rows * D.n) * sizeof(double));
     const size_t at_b = at_h + pad(c.jac ? 0 : rows * D.m * sizeof(double));
     const size_t at_r = at_b + pad(c.jac ? 0 : rows * D.p * sizeof(double));
-    const size_t total = at_r + pad(c.device ? 0 : rows * sizeof(double));
+    const size_t at_G = at_r + pad(c.device ? 0 : rows * sizeof(double));
+    const size_t at_A = at_G + pad(c.grad_G ? rows * D.nnzG * sizeof(double) : 0);
+    const size_t total = at_A + pad(c.grad_A ? rows * D.nnzA * sizeof(double) : 0);
     HIP_TRY_AS("hipMalloc", h->d_adj.reserve(total, h->stream));
     char *base = h->d_adj.as<char>();
     auto dbl = [&](size_t at) { return reinterpret_cast<double *>(base + at); };
@@ -1761,15 +1768,20 @@ static int adjoint_run(eicos_batch *h, const AdjointCall &c) {
     AdjointDev &rec = h->adj;
     rec = AdjointDev{};
     if (c.jac) {
-        rec.pmap = h->d_param.as<const ParamMapDev>(); rec.omap = h->d_out.as<const OutMapDev>();
+        rec.pmap = h->param.k ? h->d_param.as<const ParamMapDev>() : nullptr;
+        rec.mmap = c.mmap && h->mat.k ? h->d_mat.as<const MatrixMapDev>() : nullptr;
+        rec.k = (int)k;
+        if (c.grows) { rec.nrhs = c.nrhs; rec.g = c.device ? c.g : dbl(at_g); }
+        else rec.omap = h->d_out.as<const OutMapDev>();
         rec.J = c.device ? c.J : dbl(at_c);
         rec.res = c.device ? c.res : (c.res ? dbl(at_r) : nullptr);
     } else {
         rec.nrhs = c.nrhs; rec.g = dbl(at_g);
         rec.grad_c = c.grad_c && D.n ? dbl(at_c) : nullptr; rec.grad_h = c.grad_h && D.m ? dbl(at_h) : nullptr;
         rec.grad_b = c.grad_b && D.p ? dbl(at_b) : nullptr; rec.res = c.res ? dbl(at_r) : nullptr;
-        HIP_TRY(hipMemcpyAsync(dbl(at_g), c.g, rows * D.n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        rec.grad_G = c.grad_G && D.nnzG ? dbl(at_G) : nullptr; rec.grad_A = c.grad_A && D.nnzA ? dbl(at_A) : nullptr;
     }
+    if (up_g) HIP_TRY(hipMemcpyAsync(dbl(at_g), c.g, rows * D.n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(base, &rec, sizeof rec, hipMemcpyHostToDevice, h->stream));
     AdjointLaunch L{};
     L.ps = h->pslot; L.inst = h->inst(); L.work = h->work(); L.count = c.count; L.list = d_ids; L.batch = h->batch;
@@ -1792,6 +1804,8 @@ static int adjoint_run(eicos_batch *h, const AdjointCall &c) {
         rc = back(c.grad_c, rec.grad_c, rows * D.n);
         if (rc == EICOS_OK) rc = back(c.grad_h, rec.grad_h, rows * D.m);
         if (rc == EICOS_OK) rc = back(c.grad_b, rec.grad_b, rows * D.p);
+        if (rc == EICOS_OK) rc = back(c.grad_G, rec.grad_G, rows * D.nnzG);
+        if (rc == EICOS_OK) rc = back(c.grad_A, rec.grad_A, rows * D.nnzA);
     }
     if (rc == EICOS_OK) rc = back(c.res, rec.res, rows);
     if (rc != EICOS_OK) return rc;
@@ -1810,13 +1824,63 @@ int eicos_batch_adjoint(eicos_batch *h, const int *idx, int count, int nrhs, con
     return adjoint_run(h, AdjointCall{idx, count, nrhs, g, grad_c, grad_h, grad_b, res, nullptr, false, false});
 }
 
+int eicos_batch_adjoint_data(eicos_batch *h, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b,
+                             double *grad_G, double *grad_A, double *res) {
+    const int rc = adjoint_list_fault(h, idx, count, "eicos_batch_adjoint_data");
+    if (rc != EICOS_OK) return rc;
+    if (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS) return fail(EICOS_E_INVALID, "eicos_batch_adjoint_data: nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
+    if (!g && count > 0 && h->dp.n > 0) return fail(EICOS_E_INVALID, "eicos_batch_adjoint_data: g is NULL");
+    for (const double *q : {g, (const double *)grad_c, (const double *)grad_h, (const double *)grad_b, (const double *)grad_G, (const double *)grad_A, (const double *)res})
+        if (q && count > 0 && memory_kind(q, 1) == MEM_DEVICE) return fail(EICOS_E_INVALID, "eicos_batch_adjoint_data takes host pointers: an array lives in device memory");
+    AdjointCall c{idx, count, nrhs, g, grad_c, grad_h, grad_b, res, nullptr, false, false};
+    c.grad_G = grad_G; c.grad_A = grad_A;
+    return adjoint_run(h, c);
+}
+
+// The contracted forms through whichever of the parameter map and the matrix map are installed (eicos_batch_param_jacobian: the rows of
+// the output map; eicos_batch_param_gradient: nrhs rows of g per instance).  out = J or grad_theta.
+static int param_contracted(eicos_batch *h, const int *idx, int count, int nrhs, const double *g, bool grows, double *out, const char *out_name,
+                            double *res, bool device, const char *who) {
+    const int rc = adjoint_list_fault(h, idx, count, who);
+    if (rc != EICOS_OK) return rc;
+    const std::string w(who);
+    if (grows && (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS)) return fail(EICOS_E_INVALID, w + ": nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
+    if (!grows && h->out.r == 0) return fail(EICOS_E_INVALID, w + ": needs an output map (eicos_batch_set_output_map): J = d u / d theta");
+    if (h->param.k == 0 && h->mat.k == 0)
+        return fail(EICOS_E_INVALID, w + ": needs a parameter map or a matrix map (eicos_batch_set_param_map, eicos_batch_set_matrix_map): neither is installed");
+    if (h->param.k != 0 && h->mat.k != 0 && h->param.k != h->mat.k)
+        return fail(EICOS_E_INVALID, w + ": the matrix map was installed for k = " + std::to_string(h->mat.k) + ", the parameter map now installed has k = " +
+                                         std::to_string(h->param.k) + ": install it again");
+    if (grows && !g && count > 0 && h->dp.n > 0) return fail(EICOS_E_INVALID, w + ": g is NULL");
+    if (!out && count > 0) return fail(EICOS_E_INVALID, w + ": " + out_name + " is NULL");
+    const char *other = device ? " must live in device memory (the form without _device takes host pointers)" : " lives in device memory: this form takes host pointers (use the _device form)";
+    if (count > 0 && (memory_kind(out, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": " + out_name + other);
+    if (count > 0 && grows && g && (memory_kind(g, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": g" + other);
+    if (count > 0 && res && (memory_kind(res, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": res must live where " + out_name + " lives");
+    AdjointCall c{idx, count, grows ? nrhs : h->out.r, g, nullptr, nullptr, nullptr, res, out, true, device};
+    c.mmap = true; c.grows = grows;
+    return adjoint_run(h, c);
+}
+int eicos_batch_param_jacobian(eicos_batch *h, const int *idx, int count, double *J, double *res) {
+    return param_contracted(h, idx, count, 0, nullptr, false, J, "J", res, false, "eicos_batch_param_jacobian");
+}
+int eicos_batch_param_jacobian_device(eicos_batch *h, const int *idx, int count, double *dJ, double *dres) {
+    return param_contracted(h, idx, count, 0, nullptr, false, dJ, "J", dres, true, "eicos_batch_param_jacobian_device");
+}
+int eicos_batch_param_gradient(eicos_batch *h, const int *idx, int count, int nrhs, const double *g, double *grad_theta, double *res) {
+    return param_contracted(h, idx, count, nrhs, g, true, grad_theta, "grad_theta", res, false, "eicos_batch_param_gradient");
+}
+int eicos_batch_param_gradient_device(eicos_batch *h, const int *idx, int count, int nrhs, const double *dg, double *dgrad_theta, double *dres) {
+    return param_contracted(h, idx, count, nrhs, dg, true, dgrad_theta, "grad_theta", dres, true, "eicos_batch_param_gradient_device");
+}
+
 static int output_jacobian(eicos_batch *h, const int *idx, int count, double *J, double *res, bool device, const char *who) {
     const int rc = adjoint_list_fault(h, idx, count, who);
     if (rc != EICOS_OK) return rc;
     if (h->param.k == 0 || h->out.r == 0)
         return fail(EICOS_E_INVALID, std::string(who) + ": needs a parameter map and an output map (eicos_batch_set_param_map, eicos_batch_set_output_map): J = d u / d theta");
     if (h->mat.k != 0)
-        return fail(EICOS_E_INVALID, std::string(who) + ": a matrix map is installed -- the derivative then has dG and dA terms, which this call does not form (right-hand-side data only)");
+        return fail(EICOS_E_INVALID, std::string(who) + ": a matrix map is installed -- the derivative then has dG and dA terms, which this call does not form (right-hand-side data only; eicos_batch_param_jacobian forms them)");
     if (!J && count > 0) return fail(EICOS_E_INVALID, std::string(who) + ": J is NULL");
     if (count > 0 && (memory_kind(J, 1) == MEM_DEVICE) != device)
         return fail(EICOS_E_INVALID, std::string(who) + (device ? ": J must live in device memory (eicos_batch_output_jacobian takes host pointers)"
@@ -1925,6 +1989,7 @@ int eicos_batch_set_matrix_map(eicos_batch *h, const eicos_affine_map *G, const 
     return install_map(h, h->d_mat, h->mat, "matrix", g, 2, 0, remove ? nullptr : &M, M.g);
 }
 
+int eicos_batch_matrix_map_count(eicos_batch *h) { return h ? h->mat.k : fail(EICOS_E_INVALID, "NULL handle"); }
 int eicos_batch_has_matrix_map(eicos_batch *h) {
     return h ? ((h->mat.g[0].base ? 1 : 0) | (h->mat.g[1].base ? 2 : 0)) : fail(EICOS_E_INVALID, "NULL handle");
 }

@@ -437,6 +437,7 @@ template <int KI> struct VKI { double v[KI]; };
 template <int KI> struct IVK { int o; double v[KI]; };
 struct IV1 { int i; double a; };
 struct IV2 { int i; double a, b; };
+struct II { int i, j; };
 struct IIV { int i, j; double a; };
 struct IIV3 { int i, j; double a, b, c; };
 template <int T, int U0 = 4, class L, class F>
@@ -3567,9 +3568,14 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int retry_betwee
 //   2. the factorisation of the handle's factor path, as solve_instance calls it;
 //   3. per right-hand side: D [g; 0; 0] into w_rhs1k, kkt_solve with its refinement (one right-hand side, ADJ: the error norm it
 //      stopped at), the direction scaled back by D = diag(1 / xe, 1 / ae, 1 / ge);
-//   4. the three gradient rows and res to the caller's arrays -- or, in the Jacobian form (A.J != NULL: g = row i of the output map),
-//      contracted with the CSR rows of the parameter map into J[i, :], columns in chunks of eight, every chunk one workgroup reduction in
-//      a fixed order (thread-private partial sums over the thread's rows in ascending order, then blk_reduce); no gradient row is stored.
+//   4. the three gradient rows and res to the caller's arrays, and -- A.grad_G / A.grad_A != NULL -- the matrix gradients, one thread
+//      per stored value e = (i, j) in the CSC order of Gpr / Apr (DevPat::Gir, Gcol: coalesced stores, no column loop):
+//      grad_G[e] = grad_c[j] z[i] - grad_h[i] x[j], grad_A[e] = grad_c[j] y[i] - grad_b[i] x[j] with the un-equilibrated x, y, z of the
+//      instance's result rows (the LDS copy in the LDS-resident build) -- or, in the contracted form (A.J != NULL: g = row i of the
+//      output map, or of the caller's g when A.g != NULL), contracted with the CSR rows of the parameter map and of the matrix map (each
+//      NULL = not installed) into J[i, :], columns in chunks of eight, every chunk one workgroup reduction in a fixed order: thread-private
+//      partial sums over the thread's rows of the c, h, b groups in ascending order, then over its stored values of G, then of A, each
+//      ascending, then blk_reduce; no gradient row is stored.
 // An instance whose last solve did not end OPTIMAL / OPTIMAL_INACC, whose scalings fail or whose factorisation meets a zero pivot gets
 // NaN in every row and in res.  Nothing of the instance slab that a later call reads is written: the scaling block i_Vv is reset by every
 // solve's prologue, and the workspace slab belongs to the workgroup, not to an instance.  g_S is scratch here (no instance_end).
@@ -3628,12 +3634,14 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void adjoint_ins
         ok = g_S.fl[FL_FATAL] == 0;
     }
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    const int nrhs = A.J ? A.omap->r : A.nrhs;
+    const bool urows = A.J && !A.g; // the right-hand sides are the rows of the output map
+    const int nrhs = urows ? A.omap->r : A.nrhs;
+    gcdbl_p rx = I + P.i_x, ry = I + P.i_y, rz = I + P.i_z; // the result rows: un-equilibrated
     for (int r = 0; r < nrhs; r++) {
         const size_t at = (size_t)row * nrhs + r;
         if (ok) {
             __syncthreads();
-            if (A.J) { // row r of the output map, densified: the entries of a column summed in stored order, then D
+            if (urows) { // row r of the output map, densified: the entries of a column summed in stored order, then D
                 const AffineDev U = A.omap->a;
                 FOR_T(j, np + m) rhs1k[j] = 0.;
                 __syncthreads();
@@ -3652,21 +3660,44 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void adjoint_ins
             if (A.grad_c) { FOR_T(j, n) A.grad_c[at * n + j] = ok ? -(dx[j] / xe[j]) : nan; }
             if (A.grad_h) { FOR_T(i, m) A.grad_h[at * m + i] = ok ? dz[i] / ge[i] : nan; }
             if (A.grad_b) { FOR_T(q, p) A.grad_b[at * p + q] = ok ? dy[q] / ae[q] : nan; }
+            // the matrix gradients: a sampled outer product on the pattern, one thread per stored value
+            if (A.grad_G) for_t_pre<T, 4>(P.nnzG, [&](int e) { return II{P.Gir[e], P.Gcol[e]}; }, [&](int e, const II &q) {
+                A.grad_G[at * P.nnzG + e] = ok ? (-(dx[q.j] / xe[q.j])) * rz[q.i] - (dz[q.i] / ge[q.i]) * rx[q.j] : nan;
+            });
+            if (A.grad_A) for_t_pre<T, 4>(P.nnzA, [&](int e) { return II{P.Air[e], P.Acol[e]}; }, [&](int e, const II &q) {
+                A.grad_A[at * P.nnzA + e] = ok ? (-(dx[q.j] / xe[q.j])) * ry[q.i] - (dy[q.i] / ae[q.i]) * rx[q.j] : nan;
+            });
         } else {
-            const ParamMapDev M = *A.pmap;
-            const int k = M.k;
+            ParamMapDev M{};
+            MatrixMapDev MM{};
+            if (A.pmap) M = *A.pmap;
+            if (A.mmap) MM = *A.mmap;
+            const int k = A.k;
             for (int t0 = 0; t0 < k; t0 += 8) {
                 double acc[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
-                if (ok) FOR_T(e, n + m + p) {
-                    const int grp = e < n ? 0 : (e < n + m ? 1 : 2), q = e - (grp == 0 ? 0 : (grp == 1 ? n : n + m));
-                    const AffineDev G = M.g[grp];
-                    if (!G.base) continue;
-                    const double gr = grp == 0 ? -(dx[q] / xe[q]) : (grp == 1 ? dz[q] / ge[q] : dy[q] / ae[q]);
+                auto add_row = [&](const AffineDev &G, int q, double gr) { // gr times CSR row q of a map, the columns of this chunk
                     for (int t = G.rowptr[q]; t < G.rowptr[q + 1]; t++) {
                         const int c = G.col[t] - t0;
                         const double v = gr * G.val[t];
 #pragma unroll
                         for (int u = 0; u < 8; u++) acc[u] += (c == u) ? v : 0.;
+                    }
+                };
+                if (ok) {
+                    FOR_T(e, n + m + p) {
+                        const int grp = e < n ? 0 : (e < n + m ? 1 : 2), q = e - (grp == 0 ? 0 : (grp == 1 ? n : n + m));
+                        const AffineDev G = M.g[grp];
+                        if (!G.base) continue;
+                        add_row(G, q, grp == 0 ? -(dx[q] / xe[q]) : (grp == 1 ? dz[q] / ge[q] : dy[q] / ae[q]));
+                    }
+                    // the matrix map: the thread's stored values of G, then of A, the value of grad_G / grad_A formed as the gradient form stores it
+                    if (MM.g[0].base) FOR_T(e, P.nnzG) {
+                        const int i = P.Gir[e], j = P.Gcol[e];
+                        add_row(MM.g[0], e, (-(dx[j] / xe[j])) * rz[i] - (dz[i] / ge[i]) * rx[j]);
+                    }
+                    if (MM.g[1].base) FOR_T(e, P.nnzA) {
+                        const int i = P.Air[e], j = P.Acol[e];
+                        add_row(MM.g[1], e, (-(dx[j] / xe[j])) * ry[i] - (dy[i] / ae[i]) * rx[j]);
                     }
                 }
                 blk_reduce<OpSum, T, 8>(phase, acc);

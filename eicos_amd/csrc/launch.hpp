@@ -98,11 +98,16 @@ struct SolveLaunch {
 // array belongs to the q-th instance of the launch.
 // J == NULL, the gradient form: g [count][nrhs][n] in, grad_c [count][nrhs][n], grad_h [count][nrhs][m], grad_b [count][nrhs][p] and
 // res [count][nrhs] out, any of the four NULL = not wanted.
-// J != NULL, the Jacobian form: the right-hand sides are the omap->r rows of the output map, and every gradient is contracted with the
-// rows of the parameter map on the spot: J [count][r][k], res [count][r]; g, grad_* and nrhs are unused.
+// grad_G [count][nrhs][nnzG] and grad_A [count][nrhs][nnzA] (eicos_batch_adjoint_data; NULL = not wanted): the gradient with respect to
+// the stored values of G and A, in the CSC order of Gpr / Apr.
+// J != NULL, the contracted form: every gradient is contracted on the spot with the rows of the parameter map (pmap, NULL = none) and of
+// the matrix map (mmap, NULL = none or not wanted), both with k columns: J [count][rows][k], res [count][rows]; grad_* are unused.  Its
+// right-hand sides are the omap->r rows of the output map (g == NULL: the Jacobian, nrhs unused) or nrhs rows of the caller's g per
+// instance (g != NULL: the gradient with respect to theta, omap unused).
 struct AdjointDev {
     int nrhs; const double *g; double *grad_c, *grad_h, *grad_b, *res;
     const ParamMapDev *pmap; const OutMapDev *omap; double *J;
+    double *grad_G, *grad_A; const MatrixMapDev *mmap; int k;
 };
 // One k_adjoint launch of a handle: the pattern slot, the slabs and the launch shape of its solves, the settings its kkt_solve and its
 // factorisation run under (by value), `count` instances -- list != NULL: those ids (device memory, distinct, inside [0, batch)), else

@@ -528,6 +528,74 @@ int eicos_multi_output_jacobian(eicos_multi *mh, const int *idx, int count, doub
     });
 }
 
+int eicos_multi_adjoint_data(eicos_multi *mh, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b,
+                             double *grad_G, double *grad_A, double *res) {
+    Shares sh;
+    const int rc = adjoint_shares(mh, idx, count, "eicos_multi_adjoint_data", sh);
+    if (rc != EICOS_OK) return rc;
+    if (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS) return mfail(EICOS_E_INVALID, "eicos_multi_adjoint_data: nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
+    if (!g && count > 0 && mh->n > 0) return mfail(EICOS_E_INVALID, "eicos_multi_adjoint_data: g is NULL");
+    const int nnzG = mh->nnzG, nnzA = mh->nnzA;
+    return for_shards(mh, [&](int s) {
+        const std::vector<int> &pos = sh.pos[s];
+        if (pos.empty()) return (int)EICOS_OK;
+        const size_t k = pos.size();
+        const std::vector<double> tg = pack(g, pos, nrhs * mh->n);
+        std::vector<double> tc(grad_c ? k * nrhs * mh->n : 0), th(grad_h ? k * nrhs * mh->m : 0), tb(grad_b ? k * nrhs * mh->p : 0), tr(res ? k * nrhs : 0);
+        std::vector<double> tG(grad_G ? k * nrhs * nnzG : 0), tA(grad_A ? k * nrhs * nnzA : 0);
+        const int e = eicos_batch_adjoint_data(mh->shard[s], sh.ids[s].data(), (int)k, nrhs, given(g, tg), grad_c ? tc.data() : nullptr,
+                                               grad_h ? th.data() : nullptr, grad_b ? tb.data() : nullptr, grad_G ? tG.data() : nullptr,
+                                               grad_A ? tA.data() : nullptr, res ? tr.data() : nullptr);
+        if (e != EICOS_OK) return e;
+        unpack(grad_c, tc, pos, nrhs * mh->n); unpack(grad_h, th, pos, nrhs * mh->m); unpack(grad_b, tb, pos, nrhs * mh->p); unpack(res, tr, pos, nrhs);
+        unpack(grad_G, tG, pos, nrhs * nnzG); unpack(grad_A, tA, pos, nrhs * nnzA);
+        return (int)EICOS_OK;
+    });
+}
+
+// k of the contracted forms: the parameter map's, or -- without one -- the one the matrix map was installed for
+static int contracted_k(eicos_multi *mh) {
+    const int kp = std::max(0, eicos_batch_param_count(mh->shard[0]));
+    return kp ? kp : std::max(0, eicos_batch_matrix_map_count(mh->shard[0]));
+}
+int eicos_multi_param_jacobian(eicos_multi *mh, const int *idx, int count, double *J, double *res) {
+    Shares sh;
+    const int rc = adjoint_shares(mh, idx, count, "eicos_multi_param_jacobian", sh);
+    if (rc != EICOS_OK) return rc;
+    if (!J && count > 0) return mfail(EICOS_E_INVALID, "eicos_multi_param_jacobian: J is NULL");
+    const int r = std::max(0, eicos_batch_output_count(mh->shard[0])), kp = contracted_k(mh);
+    return for_shards(mh, [&](int s) {
+        const std::vector<int> &pos = sh.pos[s];
+        if (pos.empty()) return (int)EICOS_OK;
+        // (a handle without its maps: one row, so that the shard's own refusal and message come back)
+        std::vector<double> tj(std::max<size_t>(1, pos.size() * (size_t)r * kp)), tr(res ? std::max<size_t>(1, pos.size() * (size_t)r) : 0);
+        const int e = eicos_batch_param_jacobian(mh->shard[s], sh.ids[s].data(), (int)pos.size(), tj.data(), res ? tr.data() : nullptr);
+        if (e != EICOS_OK) return e;
+        unpack(J, tj, pos, r * kp); unpack(res, tr, pos, r);
+        return (int)EICOS_OK;
+    });
+}
+
+int eicos_multi_param_gradient(eicos_multi *mh, const int *idx, int count, int nrhs, const double *g, double *grad_theta, double *res) {
+    Shares sh;
+    const int rc = adjoint_shares(mh, idx, count, "eicos_multi_param_gradient", sh);
+    if (rc != EICOS_OK) return rc;
+    if (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS) return mfail(EICOS_E_INVALID, "eicos_multi_param_gradient: nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
+    if (!g && count > 0 && mh->n > 0) return mfail(EICOS_E_INVALID, "eicos_multi_param_gradient: g is NULL");
+    if (!grad_theta && count > 0) return mfail(EICOS_E_INVALID, "eicos_multi_param_gradient: grad_theta is NULL");
+    const int kp = contracted_k(mh);
+    return for_shards(mh, [&](int s) {
+        const std::vector<int> &pos = sh.pos[s];
+        if (pos.empty()) return (int)EICOS_OK;
+        const std::vector<double> tg = pack(g, pos, nrhs * mh->n);
+        std::vector<double> tt(std::max<size_t>(1, pos.size() * (size_t)nrhs * kp)), tr(res ? pos.size() * (size_t)nrhs : 0);
+        const int e = eicos_batch_param_gradient(mh->shard[s], sh.ids[s].data(), (int)pos.size(), nrhs, given(g, tg), tt.data(), res ? tr.data() : nullptr);
+        if (e != EICOS_OK) return e;
+        unpack(grad_theta, tt, pos, nrhs * kp); unpack(res, tr, pos, nrhs);
+        return (int)EICOS_OK;
+    });
+}
+
 int eicos_multi_update_param_solve_subset(eicos_multi *mh, const int *idx, int count, const double *theta, double *u_out, double *x_out,
                                           int *exitcodes) {
     Shares sh;
@@ -593,6 +661,7 @@ int eicos_multi_set_matrix_map(eicos_multi *mh, const eicos_affine_map *G, const
     if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
     return for_shards(mh, [&](int s) { return eicos_batch_set_matrix_map(mh->shard[s], G, A); });
 }
+int eicos_multi_matrix_map_count(eicos_multi *mh) { return mh ? eicos_batch_matrix_map_count(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
 int eicos_multi_has_matrix_map(eicos_multi *mh) { return mh ? eicos_batch_has_matrix_map(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
 
 int eicos_multi_set_shift_map(eicos_multi *mh, const eicos_affine_map *x, const eicos_affine_map *y, const eicos_affine_map *z, const eicos_affine_map *s) {

@@ -455,6 +455,38 @@ namespace EiCOS
             if (indices.empty()) return;
             mcheck(eicos_multi_output_jacobian(h_, indices.data(), (int)indices.size(), J, res), "eicos_multi_output_jacobian");
         }
+        // ... with respect to the matrix data (eicos_multi_adjoint_data / _param_jacobian / _param_gradient).  adjointData: adjoint with
+        // grad_G [count][nrhs][nnzG] and grad_A [count][nrhs][nnzA] (CSC order of Gpr / Apr; any nullptr): grad_G[e] = grad_c[j] z[i] -
+        // grad_h[i] x[j], grad_A[e] = grad_c[j] y[i] - grad_b[i] x[j] for the stored value e = (i, j).  paramJacobian: J [count][r][k] =
+        // du / dtheta through the output map and whichever of the parameter map and the matrix map are installed (without a matrix map:
+        // the bits of outputJacobian).  paramGradient: grad_theta [count][nrhs][k] = the gradient of g'x with respect to theta through
+        // the same maps; no output map is needed.
+        void adjointData(int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b, double *grad_G, double *grad_A, double *res = nullptr)
+        {
+            mcheck(eicos_multi_adjoint_data(h_, nullptr, batch_, nrhs, g, grad_c, grad_h, grad_b, grad_G, grad_A, res), "eicos_multi_adjoint_data");
+        }
+        void adjointData(const std::vector<int> &indices, int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b, double *grad_G,
+                         double *grad_A, double *res = nullptr)
+        {
+            if (indices.empty()) return;
+            mcheck(eicos_multi_adjoint_data(h_, indices.data(), (int)indices.size(), nrhs, g, grad_c, grad_h, grad_b, grad_G, grad_A, res),
+                   "eicos_multi_adjoint_data");
+        }
+        void paramJacobian(double *J, double *res = nullptr) { mcheck(eicos_multi_param_jacobian(h_, nullptr, batch_, J, res), "eicos_multi_param_jacobian"); }
+        void paramJacobian(const std::vector<int> &indices, double *J, double *res = nullptr)
+        {
+            if (indices.empty()) return;
+            mcheck(eicos_multi_param_jacobian(h_, indices.data(), (int)indices.size(), J, res), "eicos_multi_param_jacobian");
+        }
+        void paramGradient(int nrhs, const double *g, double *grad_theta, double *res = nullptr)
+        {
+            mcheck(eicos_multi_param_gradient(h_, nullptr, batch_, nrhs, g, grad_theta, res), "eicos_multi_param_gradient");
+        }
+        void paramGradient(const std::vector<int> &indices, int nrhs, const double *g, double *grad_theta, double *res = nullptr)
+        {
+            if (indices.empty()) return;
+            mcheck(eicos_multi_param_gradient(h_, indices.data(), (int)indices.size(), nrhs, g, grad_theta, res), "eicos_multi_param_gradient");
+        }
         void solveAsync() { mcheck(eicos_multi_solve_async(h_), "eicos_multi_solve_async"); } // enqueue on every shard's stream
         void sync() { mcheck(eicos_multi_sync(h_), "eicos_multi_sync"); }
         std::vector<double> solution() const

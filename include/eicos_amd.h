@@ -262,7 +262,7 @@ int eicos_batch_last_rollout_launches(eicos_batch *hd); /* solve-kernel launches
  * columns lie in [0, k), k = the installed parameter map's theta length).  Most rows of a realistic map are empty: that value is base[e].
  * eicos_batch_set_matrix_map COPIES the host arrays into one device allocation of its own; a NULL matrix is not mapped; a later call
  * replaces the map, both NULL removes it.  It needs a parameter map (k > 0) and remembers the k it was validated for.
- * eicos_batch_has_matrix_map: bit 0 = G mapped, bit 1 = A mapped, 0 = none.
+ * eicos_batch_has_matrix_map: bit 0 = G mapped, bit 1 = A mapped, 0 = none.  eicos_batch_matrix_map_count: that k, 0 = no matrix map.
  * Entry e of instance i:
  *     acc = base[e];  for t in rowptr[e] .. rowptr[e+1]-1, in stored order:  acc = acc + (val[t] * theta[i][col[t]])
  * with the product and the sum EACH rounded to fp64 (no fused multiply-add).
@@ -290,6 +290,7 @@ int eicos_batch_last_rollout_launches(eicos_batch *hd); /* solve-kernel launches
  * than the one now installed (the message names both). */
 int eicos_batch_set_matrix_map(eicos_batch *hd, const eicos_affine_map *G, const eicos_affine_map *A);
 int eicos_batch_has_matrix_map(eicos_batch *hd);
+int eicos_batch_matrix_map_count(eicos_batch *hd);
 
 /* ---- solve: replaces exitcode Solver::solve(bool) (reference include/eicos.hpp:158,
  * src/eicos.cpp:848-1262) for every instance of the batch.  exitcodes (host, [batch]) may be
@@ -419,8 +420,8 @@ int eicos_batch_outputs_indexed_device(eicos_batch *hd, const int *idx, int coun
  * right-hand sides are the rows of U and the gradients are contracted on the GPU without being stored.  The device form takes J and res in
  * device memory and is asynchronous on the handle's stream; both forms return the same bits.
  * Refusals (EICOS_E_INVALID with a message, nothing changed): a duplicate or out-of-range id, nrhs outside its range, NULL g or J,
- * output_jacobian without a parameter map and an output map, or with a matrix map installed (its derivative has dG and dA terms, which
- * are not formed).
+ * output_jacobian without a parameter map and an output map, or with a matrix map installed (its derivative has dG and dA terms:
+ * eicos_batch_param_jacobian, below, forms them).
  * An adjoint call changes nothing a later call reads: x, y, z, s, every info field, the retry counts and what a warm start takes from the
  * previous solve stay as they are (eicos_debug_kkt afterwards shows the scaling block at the returned iterate). */
 #define EICOS_ADJOINT_MAX_RHS 64
@@ -428,6 +429,37 @@ int eicos_batch_adjoint(eicos_batch *hd, const int *idx, int count, int nrhs, co
                         double *grad_b, double *res);
 int eicos_batch_output_jacobian(eicos_batch *hd, const int *idx, int count, double *J, double *res);
 int eicos_batch_output_jacobian_device(eicos_batch *hd, const int *idx, int count, double *dJ, double *dres);
+/* Matrix data.  Linearising the optimality conditions with dA, dG present (A'dy + G'dz = -dc - dA'y - dG'z, A dx = db - dA x,
+ * G dx - W^2 dz = dh - dG x) gives the gradient of l = g'x with respect to the stored value e = (row i, column j) of G and of A:
+ *
+ *     grad_G[e] = grad_c[j] z[i] - grad_h[i] x[j],      grad_A[e] = grad_c[j] y[i] - grad_b[i] x[j]
+ *
+ * with the returned, un-equilibrated x, y, z: a sampled outer product on the sparsity pattern, which costs no further factorisation and
+ * no further KKT solve.  Each is formed as written (two products, one difference, each rounded on its own) from the stored values of
+ * grad_c, grad_h, grad_b.  The caveat of the definition above applies unchanged.
+ * eicos_batch_adjoint_data: eicos_batch_adjoint with two more optional outputs, grad_G [count][nrhs][nnzG] and grad_A [count][nrhs][nnzA]
+ * in the CSC order of Gpr / Apr.  grad_c, grad_h, grad_b and res are those of eicos_batch_adjoint bit for bit; an ineligible instance
+ * gets NaN rows.  Host arrays, synchronous.
+ * With a matrix map Gpr = G0 + M_G theta, Apr = A0 + M_A theta the derivative with respect to theta gains grad_G' M_G + grad_A' M_A:
+ * eicos_batch_param_jacobian / _device: J [count][r][k] = du / dtheta through the output map and WHICHEVER of the parameter map and the
+ * matrix map are installed (at least one; installed for the same k).  Without a matrix map: the bits of eicos_batch_output_jacobian.
+ * eicos_batch_param_gradient / _device: grad_theta [count][nrhs][k] = the gradient of g'x with respect to theta through the same maps,
+ * g [count][nrhs][n] from the caller; no output map is needed.  With g = the rows of U: the bits of eicos_batch_param_jacobian.
+ * Contraction order (fixed): per chunk of eight columns every thread sums, over the rows it owns (row e of a group: thread e mod T), the
+ * c, h, b groups in ascending row order, then its stored values of G, then of A, each ascending; one workgroup reduction per chunk.  No
+ * gradient row is stored.  The device forms take g, J / grad_theta and res in device memory and are asynchronous on the handle's stream
+ * (what a training loop on the GPU calls); the host forms are synchronous; both return the same bits.
+ * Refusals (EICOS_E_INVALID with a message, nothing changed): those of eicos_batch_adjoint (a duplicate or out-of-range id, nrhs outside
+ * its range, NULL g / J / grad_theta); param_jacobian without an output map; param_jacobian and param_gradient with neither a parameter
+ * map nor a matrix map, or with a matrix map installed for another k than the parameter map; a host pointer handed to a device form or
+ * a device pointer handed to a host form. */
+int eicos_batch_adjoint_data(eicos_batch *hd, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h,
+                             double *grad_b, double *grad_G, double *grad_A, double *res);
+int eicos_batch_param_jacobian(eicos_batch *hd, const int *idx, int count, double *J, double *res);
+int eicos_batch_param_jacobian_device(eicos_batch *hd, const int *idx, int count, double *dJ, double *dres);
+int eicos_batch_param_gradient(eicos_batch *hd, const int *idx, int count, int nrhs, const double *g, double *grad_theta, double *res);
+int eicos_batch_param_gradient_device(eicos_batch *hd, const int *idx, int count, int nrhs, const double *dg, double *dgrad_theta,
+                                      double *dres);
 /* eicos_batch_update_param_solve_subset: the closed-loop step over a subset = eicos_batch_update_param_indexed + eicos_batch_solve_subset
  * + eicos_batch_outputs_indexed (+ the x rows), every array in list order; synchronous.
  * Fused under exactly the conditions of eicos_batch_update_param_solve (an LDS vector, a theta row that fits it, GPU-addressable theta,
@@ -615,7 +647,7 @@ int eicos_batch_set_stream(eicos_batch *hd, void *hip_stream);
 /* HIP-event timing of the most recent solve / update kernels on the handle's stream (ms). */
 int eicos_batch_last_solve_ms(eicos_batch *hd, float *ms);
 int eicos_batch_last_update_ms(eicos_batch *hd, float *ms);
-/* ... and of the kernel of the most recent eicos_batch_adjoint / _output_jacobian call (ms) */
+/* ... and of the kernel of the most recent eicos_batch_adjoint / _adjoint_data / _output_jacobian / _param_jacobian / _param_gradient call (ms) */
 int eicos_batch_last_adjoint_ms(eicos_batch *hd, float *ms);
 /* The durations (ms) of the most recent launches, oldest first: which = 0 the solve launches, 1 the updateData calls, 2 the span of a
  * whole step (start of the updateData call that preceded a solve launch -> end of that solve; meaningful when the two alternate).  The handle keeps a
@@ -702,6 +734,7 @@ int eicos_multi_rollout(eicos_multi *mh, int steps, const double *theta0, const 
  * it up shard by shard */
 int eicos_multi_set_matrix_map(eicos_multi *mh, const eicos_affine_map *G, const eicos_affine_map *A);
 int eicos_multi_has_matrix_map(eicos_multi *mh);
+int eicos_multi_matrix_map_count(eicos_multi *mh);
 /* starting point and shift map (eicos_batch_set_iterate / _set_shift_map / _has_shift_map): the rows of set_iterate are in global
  * instance order and every shard takes its own; the shift map is installed on every shard */
 int eicos_multi_set_iterate(eicos_multi *mh, int first, int count, const double *x, const double *y, const double *z, const double *s);
@@ -735,6 +768,11 @@ int eicos_multi_outputs_indexed(eicos_multi *mh, const int *idx, int count, doub
 int eicos_multi_adjoint(eicos_multi *mh, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h,
                         double *grad_b, double *res);
 int eicos_multi_output_jacobian(eicos_multi *mh, const int *idx, int count, double *J, double *res);
+/* ... and eicos_batch_adjoint_data, _param_jacobian, _param_gradient likewise */
+int eicos_multi_adjoint_data(eicos_multi *mh, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h,
+                             double *grad_b, double *grad_G, double *grad_A, double *res);
+int eicos_multi_param_jacobian(eicos_multi *mh, const int *idx, int count, double *J, double *res);
+int eicos_multi_param_gradient(eicos_multi *mh, const int *idx, int count, int nrhs, const double *g, double *grad_theta, double *res);
 int eicos_multi_update_param_solve_subset(eicos_multi *mh, const int *idx, int count, const double *theta, double *u_out, double *x_out,
                                           int *exitcodes);
 /* results gathered into the caller's host arrays in global instance order (the "gather" of north_star: per-device copies) */
