@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "internal.hpp"
+#include "shard_rows.hpp"
 
 namespace {
 // One persistent host thread per shard: blocking calls of the shards (symbolic analysis at creation, the chunked host-pointer
@@ -88,7 +89,18 @@ template <class F> int for_range(eicos_multi *mh, int first, int count, F &&fn) 
         return fn(s, a - mh->first[s], b - a, (size_t)(a - first));
     });
 }
-const double *at(const double *p, size_t row, int width) { return p ? p + row * (size_t)width : nullptr; }
+// fn(s) for every shard in turn on the caller's thread (calls that only enqueue, and settings); the first failure ends the loop.
+// name_shard: the shard's message behind "shard s: ", else as it is
+template <class F> int in_turn(eicos_multi *mh, bool name_shard, F &&fn) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    for (size_t s = 0; s < mh->shard.size(); s++) {
+        const int rc = fn((int)s);
+        if (rc != EICOS_OK) return mfail(rc, (name_shard ? "shard " + std::to_string(s) + ": " : std::string()) + eicos_last_error());
+    }
+    return EICOS_OK;
+}
+// row `row` of an array of `width` elements per row; NULL stays NULL
+template <class T> T *at(T *p, size_t row, size_t width) { return p ? p + row * width : nullptr; }
 } // namespace
 
 extern "C" {
@@ -103,7 +115,7 @@ int eicos_multi_create(int n, int m, int p, int l, int ncones, const int *q, con
     if (batch < ndev) return mfail(EICOS_E_INVALID, "batch smaller than the number of shards");
     eicos_multi *mh = new eicos_multi();
     mh->batch = batch;
-    mh->shard.assign(ndev, nullptr); mh->first.resize(ndev); mh->count.resize(ndev); mh->device.assign(device_ids, device_ids + ndev);
+    mh->shard.assign(ndev, nullptr); mh->device.assign(device_ids, device_ids + ndev);
     // a negative id means "the caller's current device": resolved HERE, on the calling thread (a worker thread's current device is 0)
     {
         int cur = 0, nvis = 0;
@@ -116,8 +128,7 @@ int eicos_multi_create(int n, int m, int p, int l, int ncones, const int *q, con
         for (int &d : mh->device) { if (d < 0) d = cur; if (d >= nvis) { delete mh; return mfail(EICOS_E_INVALID, "device index out of range (" + std::to_string(nvis) + " visible)"); } }
     }
     if (ndev > 1) for (int s = 0; s < ndev; s++) mh->worker.emplace_back(new Worker());
-    const int base = batch / ndev, rem = batch % ndev; // contiguous shards, the first `rem` one instance longer (= eicos_amd.generate.shard_range)
-    for (int s = 0; s < ndev; s++) { mh->first[s] = s * base + std::min(s, rem); mh->count[s] = base + (s < rem ? 1 : 0); }
+    eicos::shard_layout(batch, ndev, mh->first, mh->count);
     // every shard analyses the pattern and sets up its device on its own host thread (the analysis is deterministic: identical plans)
     const int rc = for_shards(mh, [&](int s) {
         return eicos_batch_create(n, m, p, l, ncones, q, Gjc, Gir, Ajc, Air, mh->count[s], mh->device[s], &mh->shard[s]);
@@ -237,28 +248,13 @@ int eicos_multi_output_count(eicos_multi *mh) { return mh ? eicos_batch_output_c
 int eicos_multi_outputs(eicos_multi *mh, int first, int count, double *u) {
     if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
     const int r = eicos_batch_output_count(mh->shard[0]); // (0: every shard refuses, "no output map")
-    return for_range(mh, first, count, [&](int s, int f, int cnt, size_t off) {
-        return eicos_batch_outputs(mh->shard[s], f, cnt, u ? u + off * (size_t)r : nullptr);
-    });
+    return for_range(mh, first, count, [&](int s, int f, int cnt, size_t off) { return eicos_batch_outputs(mh->shard[s], f, cnt, at(u, off, r)); });
 }
 
-int eicos_multi_solve_async(eicos_multi *mh) {
-    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
-    for (size_t s = 0; s < mh->shard.size(); s++) { // enqueue only: every shard's kernels start on its own stream, the call returns at once
-        const int rc = eicos_batch_solve_async(mh->shard[s]);
-        if (rc != EICOS_OK) return mfail(rc, "shard " + std::to_string(s) + ": " + eicos_last_error());
-    }
-    return EICOS_OK;
-}
+// enqueue only: every shard's kernels start on its own stream, the call returns at once
+int eicos_multi_solve_async(eicos_multi *mh) { return in_turn(mh, true, [&](int s) { return eicos_batch_solve_async(mh->shard[s]); }); }
 
-int eicos_multi_sync(eicos_multi *mh) {
-    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
-    for (size_t s = 0; s < mh->shard.size(); s++) {
-        const int rc = eicos_batch_sync(mh->shard[s]);
-        if (rc != EICOS_OK) return mfail(rc, "shard " + std::to_string(s) + ": " + eicos_last_error());
-    }
-    return EICOS_OK;
-}
+int eicos_multi_sync(eicos_multi *mh) { return in_turn(mh, true, [&](int s) { return eicos_batch_sync(mh->shard[s]); }); }
 
 int eicos_multi_info(eicos_multi *mh, eicos_info *info) {
     if (!mh || !info) return mfail(EICOS_E_INVALID, "NULL argument");
@@ -278,21 +274,53 @@ int eicos_multi_solve(eicos_multi *mh, int *exitcodes) {
 
 } // extern "C"
 
-// ---- subset calls (eicos_batch_select / _solve_subset / _solve_where / _gather per shard): GLOBAL instance ids.  A list is checked as a
-// whole before any shard sees its share, so a refused list changes no shard; shards with an empty share are skipped.
+// ---- Calls that take a list of GLOBAL instance ids with host arrays in list order (the eicos_batch_* namesake per shard).  Each is its
+// argument checks, a table of its list-ordered arrays (eicos::Column) and the namesake call; the routing is shard_rows.hpp's.  The list
+// is checked as a whole before any shard sees its share, so a refused call changes no shard; shards with an empty share are skipped; a
+// failing shard's rows of the caller's outputs stay as they were.
 namespace {
-struct Shares { std::vector<std::vector<int>> ids, pos; }; // per shard: its ids, reduced by the shard's first instance, and their positions in the caller's list
-int split_list(eicos_multi *mh, const int *idx, int count, const char *who, Shares &sh) {
+using eicos::Column;
+using eicos::Shares;
+using eicos::in;
+using eicos::out;
+// prefix_form: idx == NULL means instances 0 .. count-1 (the adjoint family)
+int split(eicos_multi *mh, const int *idx, int count, const char *who, Shares &sh, bool prefix_form = false) {
     if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
-    const std::string msg = eicos::index_list_fault(idx, count, mh->batch);
-    if (!msg.empty()) return mfail(EICOS_E_INVALID, std::string(who) + ": " + msg);
-    const int ns = (int)mh->shard.size();
-    sh.ids.assign(ns, {}); sh.pos.assign(ns, {});
-    for (int q = 0; q < count; q++) {
-        const int s = (int)(std::upper_bound(mh->first.begin(), mh->first.end(), idx[q]) - mh->first.begin()) - 1; // (first[] ascends from 0)
-        sh.ids[s].push_back(idx[q] - mh->first[s]); sh.pos[s].push_back(q);
-    }
-    return EICOS_OK;
+    const std::string msg = eicos::split_list(mh->first, mh->batch, idx, count, who, prefix_form, sh);
+    return msg.empty() ? (int)EICOS_OK : mfail(EICOS_E_INVALID, msg);
+}
+// every shard serves its share on its host thread: call(s, ids, k, p) with the shard's ids and the per-shard pointers, in column order
+template <size_t N, class F> int route(eicos_multi *mh, const Shares &sh, const Column (&cols)[N], F &&call) {
+    return for_shards(mh, [&](int s) {
+        return eicos::serve_share(sh.ids[s], sh.pos[s], cols, [&](const int *ids, int k, void *const *p) { return call(s, ids, k, p); });
+    });
+}
+// ... but a handle of ONE shard hands the caller's list and arrays on as they are: pinned arrays stay pinned, so the step over a subset
+// keeps its one-launch path (the five indexed updates and reads and the subset step)
+template <size_t N, class F> int route_or_pass(eicos_multi *mh, const Shares &sh, const int *idx, int count, const Column (&cols)[N], F &&call) {
+    if (mh->shard.size() != 1) return route(mh, sh, cols, call);
+    void *p[N];
+    for (size_t c = 0; c < N; c++) p[c] = cols[c].ptr;
+    return for_shards(mh, [&](int) { return call(0, idx, count, (void *const *)p); });
+}
+double *D(void *p) { return static_cast<double *>(p); }
+int *I(void *p) { return static_cast<int *>(p); }
+// the widths the maps give (0 without the map: the shard refuses)
+int param_k(eicos_multi *mh) { return std::max(0, eicos_batch_param_count(mh->shard[0])); }
+int output_r(eicos_multi *mh) { return std::max(0, eicos_batch_output_count(mh->shard[0])); }
+// k of the contracted forms: the parameter map's, or -- without one -- the one the matrix map was installed for
+int contracted_k(eicos_multi *mh) { return param_k(mh) ? param_k(mh) : std::max(0, eicos_batch_matrix_map_count(mh->shard[0])); }
+// the refusals of the adjoint family behind the list's, in this order: nrhs, a NULL g, a NULL J / grad_theta
+int check_nrhs(const char *who, int nrhs) {
+    if (nrhs >= 1 && nrhs <= EICOS_ADJOINT_MAX_RHS) return EICOS_OK;
+    return mfail(EICOS_E_INVALID, std::string(who) + ": nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
+}
+int check_given(const char *who, const char *name, const void *p, bool needed) {
+    return p || !needed ? (int)EICOS_OK : mfail(EICOS_E_INVALID, std::string(who) + ": " + name + " is NULL");
+}
+int check_g(eicos_multi *mh, const char *who, int nrhs, const double *g, int count) {
+    const int rc = check_nrhs(who, nrhs);
+    return rc != EICOS_OK ? rc : check_given(who, "g", g, count > 0 && mh->n > 0);
 }
 int check_mask(eicos_multi *mh, unsigned mask, const char *who) {
     if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
@@ -327,28 +355,19 @@ int eicos_multi_select(eicos_multi *mh, unsigned mask, int *idx_out, int *count_
 
 int eicos_multi_solve_subset_async(eicos_multi *mh, const int *idx, int count) {
     Shares sh;
-    const int rc = split_list(mh, idx, count, "eicos_multi_solve_subset", sh);
+    const int rc = split(mh, idx, count, "eicos_multi_solve_subset", sh);
     if (rc != EICOS_OK) return rc;
-    for (size_t s = 0; s < mh->shard.size(); s++) { // enqueue only, as eicos_multi_solve_async
-        if (sh.ids[s].empty()) continue;
-        const int r = eicos_batch_solve_subset_async(mh->shard[s], sh.ids[s].data(), (int)sh.ids[s].size());
-        if (r != EICOS_OK) return mfail(r, "shard " + std::to_string(s) + ": " + eicos_last_error());
-    }
-    return EICOS_OK;
+    return in_turn(mh, true, [&](int s) { // enqueue only, as eicos_multi_solve_async
+        return sh.ids[s].empty() ? (int)EICOS_OK : eicos_batch_solve_subset_async(mh->shard[s], sh.ids[s].data(), (int)sh.ids[s].size());
+    });
 }
 
 int eicos_multi_solve_subset(eicos_multi *mh, const int *idx, int count, int *exitcodes) {
     Shares sh;
-    const int rc = split_list(mh, idx, count, "eicos_multi_solve_subset", sh);
+    const int rc = split(mh, idx, count, "eicos_multi_solve_subset", sh);
     if (rc != EICOS_OK) return rc;
-    return for_shards(mh, [&](int s) {
-        const int k = (int)sh.ids[s].size();
-        if (k == 0) return (int)EICOS_OK;
-        std::vector<int> codes(k);
-        const int r = eicos_batch_solve_subset(mh->shard[s], sh.ids[s].data(), k, exitcodes ? codes.data() : nullptr);
-        for (int q = 0; r == EICOS_OK && exitcodes && q < k; q++) exitcodes[sh.pos[s][q]] = codes[q];
-        return r;
-    });
+    const Column cols[] = {out(exitcodes, 1)};
+    return route(mh, sh, cols, [&](int s, const int *ids, int k, void *const *p) { return eicos_batch_solve_subset(mh->shard[s], ids, k, I(p[0])); });
 }
 
 int eicos_multi_solve_where(eicos_multi *mh, unsigned mask, int *idx_out, int *count_out, int *exitcodes) {
@@ -364,258 +383,145 @@ int eicos_multi_solve_where(eicos_multi *mh, unsigned mask, int *idx_out, int *c
     return rc != EICOS_OK ? rc : concat_selected(mh, ids, cnt, &codes, idx_out, count_out, exitcodes);
 }
 
+// (a column of width 0 -- n, p or m = 0 -- copies nothing and reaches the shard as NULL)
 int eicos_multi_gather(eicos_multi *mh, const int *idx, int count, double *x, double *y, double *z, double *sl, eicos_info *info) {
     Shares sh;
-    const int rc = split_list(mh, idx, count, "eicos_multi_gather", sh);
+    const int rc = split(mh, idx, count, "eicos_multi_gather", sh);
     if (rc != EICOS_OK) return rc;
-    return for_shards(mh, [&](int s) {
-        const size_t k = sh.ids[s].size();
-        if (k == 0) return (int)EICOS_OK;
-        // the shard's rows in its own compact arrays, then every row to its position in the caller's list
-        std::vector<double> tx(x ? k * mh->n : 0), ty(y ? k * mh->p : 0), tz(z ? k * mh->m : 0), ts(sl ? k * mh->m : 0);
-        std::vector<eicos_info> ti(info ? k : 0);
-        const int r = eicos_batch_gather(mh->shard[s], sh.ids[s].data(), (int)k, x ? tx.data() : nullptr, y ? ty.data() : nullptr,
-                                         z ? tz.data() : nullptr, sl ? ts.data() : nullptr, info ? ti.data() : nullptr);
-        if (r != EICOS_OK) return r;
-        auto rows = [&](double *dst, const std::vector<double> &src, int w) {
-            if (dst && w > 0) for (size_t q = 0; q < k; q++) std::memcpy(dst + (size_t)sh.pos[s][q] * w, src.data() + q * w, (size_t)w * sizeof(double));
-        };
-        rows(x, tx, mh->n); rows(y, ty, mh->p); rows(z, tz, mh->m); rows(sl, ts, mh->m);
-        for (size_t q = 0; info && q < k; q++) info[sh.pos[s][q]] = ti[q];
-        return (int)EICOS_OK;
+    const Column cols[] = {out(x, mh->n), out(y, mh->p), out(z, mh->m), out(sl, mh->m), out(info, 1)};
+    return route(mh, sh, cols, [&](int s, const int *ids, int k, void *const *p) {
+        return eicos_batch_gather(mh->shard[s], ids, k, D(p[0]), D(p[1]), D(p[2]), D(p[3]), static_cast<eicos_info *>(p[4]));
     });
 }
 
-} // extern "C"
-
-// ---- index-list updates, output rows and the closed-loop step over a subset (eicos_batch_*_indexed per shard): global ids, host arrays
-// in list order.  The pattern of eicos_multi_gather: a shard's rows are packed into its own compact arrays (pack), results go back to
-// their positions in the caller's list (unpack).  A handle of ONE shard hands the caller's list and arrays on as they are: pinned arrays
-// stay pinned, so the step over a subset keeps its one-launch path.
-namespace {
-// rows pos[0 .. k) of src [count][w] behind each other; NULL or w = 0: nothing (data() of an empty vector is handed on as NULL)
-std::vector<double> pack(const double *src, const std::vector<int> &pos, int w) {
-    std::vector<double> out(src && w > 0 ? pos.size() * (size_t)w : 0);
-    for (size_t q = 0; q < pos.size() && !out.empty(); q++) std::memcpy(out.data() + q * w, src + (size_t)pos[q] * w, (size_t)w * sizeof(double));
-    return out;
-}
-void unpack(double *dst, const std::vector<double> &src, const std::vector<int> &pos, int w) {
-    if (dst && w > 0) for (size_t q = 0; q < pos.size(); q++) std::memcpy(dst + (size_t)pos[q] * w, src.data() + q * w, (size_t)w * sizeof(double));
-}
-// a group the caller gave stays given for the shard even where its width is 0 (the h / b rules look at the pointers)
-const double *given(const double *src, const std::vector<double> &packed) { return src ? (packed.empty() ? src : packed.data()) : nullptr; }
-} // namespace
-
-extern "C" {
-
+// Index-list updates, output rows and the closed-loop step over a subset.  An input group the caller gave stays given for the shard
+// even where its width is 0 (eicos::in); so does u, so that a handle without its output map refuses with its own words.
 int eicos_multi_update_indexed(eicos_multi *mh, const int *idx, int count, const double *G, const double *A, const double *c, const double *hh,
                                const double *b) {
     Shares sh;
-    const int rc = split_list(mh, idx, count, "eicos_multi_update_indexed", sh);
+    const int rc = split(mh, idx, count, "eicos_multi_update_indexed", sh);
     if (rc != EICOS_OK) return rc;
-    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_update_indexed(mh->shard[0], idx, count, G, A, c, hh, b); });
-    return for_shards(mh, [&](int s) {
-        const std::vector<int> &pos = sh.pos[s];
-        if (pos.empty()) return (int)EICOS_OK;
-        const std::vector<double> tG = pack(G, pos, mh->nnzG), tA = pack(A, pos, mh->nnzA), tc = pack(c, pos, mh->n), th = pack(hh, pos, mh->m), tb = pack(b, pos, mh->p);
-        return eicos_batch_update_indexed(mh->shard[s], sh.ids[s].data(), (int)pos.size(), given(G, tG), given(A, tA), given(c, tc), given(hh, th), given(b, tb));
+    const Column cols[] = {in(G, mh->nnzG), in(A, mh->nnzA), in(c, mh->n), in(hh, mh->m), in(b, mh->p)};
+    return route_or_pass(mh, sh, idx, count, cols, [&](int s, const int *ids, int k, void *const *p) {
+        return eicos_batch_update_indexed(mh->shard[s], ids, k, D(p[0]), D(p[1]), D(p[2]), D(p[3]), D(p[4]));
     });
 }
 
 int eicos_multi_update_rhs_indexed(eicos_multi *mh, const int *idx, int count, const double *c, const double *hh, const double *b) {
     Shares sh;
-    const int rc = split_list(mh, idx, count, "eicos_multi_update_rhs_indexed", sh);
+    const int rc = split(mh, idx, count, "eicos_multi_update_rhs_indexed", sh);
     if (rc != EICOS_OK) return rc;
-    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_update_rhs_indexed(mh->shard[0], idx, count, c, hh, b); });
-    return for_shards(mh, [&](int s) {
-        const std::vector<int> &pos = sh.pos[s];
-        if (pos.empty()) return (int)EICOS_OK;
-        const std::vector<double> tc = pack(c, pos, mh->n), th = pack(hh, pos, mh->m), tb = pack(b, pos, mh->p);
-        return eicos_batch_update_rhs_indexed(mh->shard[s], sh.ids[s].data(), (int)pos.size(), given(c, tc), given(hh, th), given(b, tb));
+    const Column cols[] = {in(c, mh->n), in(hh, mh->m), in(b, mh->p)};
+    return route_or_pass(mh, sh, idx, count, cols, [&](int s, const int *ids, int k, void *const *p) {
+        return eicos_batch_update_rhs_indexed(mh->shard[s], ids, k, D(p[0]), D(p[1]), D(p[2]));
     });
 }
 
 int eicos_multi_update_param_indexed(eicos_multi *mh, const int *idx, int count, const double *theta) {
     Shares sh;
-    const int rc = split_list(mh, idx, count, "eicos_multi_update_param_indexed", sh);
+    const int rc = split(mh, idx, count, "eicos_multi_update_param_indexed", sh);
     if (rc != EICOS_OK) return rc;
-    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_update_param_indexed(mh->shard[0], idx, count, theta); });
-    const int k = std::max(0, eicos_batch_param_count(mh->shard[0]));
-    return for_shards(mh, [&](int s) {
-        const std::vector<int> &pos = sh.pos[s];
-        if (pos.empty()) return (int)EICOS_OK;
-        const std::vector<double> tt = pack(theta, pos, k);
-        return eicos_batch_update_param_indexed(mh->shard[s], sh.ids[s].data(), (int)pos.size(), given(theta, tt));
+    const Column cols[] = {in(theta, param_k(mh))};
+    return route_or_pass(mh, sh, idx, count, cols, [&](int s, const int *ids, int k, void *const *p) {
+        return eicos_batch_update_param_indexed(mh->shard[s], ids, k, D(p[0]));
     });
 }
 
 int eicos_multi_set_iterate_indexed(eicos_multi *mh, const int *idx, int count, const double *x, const double *y, const double *z, const double *sl) {
     Shares sh;
-    const int rc = split_list(mh, idx, count, "eicos_multi_set_iterate_indexed", sh);
+    const int rc = split(mh, idx, count, "eicos_multi_set_iterate_indexed", sh);
     if (rc != EICOS_OK) return rc;
-    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_set_iterate_indexed(mh->shard[0], idx, count, x, y, z, sl); });
-    return for_shards(mh, [&](int s) {
-        const std::vector<int> &pos = sh.pos[s];
-        if (pos.empty()) return (int)EICOS_OK;
-        const std::vector<double> tx = pack(x, pos, mh->n), ty = pack(y, pos, mh->p), tz = pack(z, pos, mh->m), ts = pack(sl, pos, mh->m);
-        return eicos_batch_set_iterate_indexed(mh->shard[s], sh.ids[s].data(), (int)pos.size(), given(x, tx), given(y, ty), given(z, tz), given(sl, ts));
+    const Column cols[] = {in(x, mh->n), in(y, mh->p), in(z, mh->m), in(sl, mh->m)};
+    return route_or_pass(mh, sh, idx, count, cols, [&](int s, const int *ids, int k, void *const *p) {
+        return eicos_batch_set_iterate_indexed(mh->shard[s], ids, k, D(p[0]), D(p[1]), D(p[2]), D(p[3]));
     });
 }
 
 int eicos_multi_outputs_indexed(eicos_multi *mh, const int *idx, int count, double *u) {
     Shares sh;
-    const int rc = split_list(mh, idx, count, "eicos_multi_outputs_indexed", sh);
+    const int rc = split(mh, idx, count, "eicos_multi_outputs_indexed", sh);
     if (rc != EICOS_OK) return rc;
-    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_outputs_indexed(mh->shard[0], idx, count, u); });
-    const int r = std::max(0, eicos_batch_output_count(mh->shard[0]));
-    return for_shards(mh, [&](int s) {
-        const std::vector<int> &pos = sh.pos[s];
-        if (pos.empty()) return (int)EICOS_OK;
-        std::vector<double> tu(u ? pos.size() * (size_t)r : 0);
-        const int e = eicos_batch_outputs_indexed(mh->shard[s], sh.ids[s].data(), (int)pos.size(), u ? (tu.empty() ? u : tu.data()) : nullptr);
-        if (e == EICOS_OK) unpack(u, tu, pos, r);
-        return e;
+    const Column cols[] = {out(u, output_r(mh), Column::GIVEN)};
+    return route_or_pass(mh, sh, idx, count, cols, [&](int s, const int *ids, int k, void *const *p) {
+        return eicos_batch_outputs_indexed(mh->shard[s], ids, k, D(p[0]));
     });
 }
 
-// Adjoint sensitivities with global ids (eicos_batch_adjoint / _output_jacobian per shard), host arrays in list order; idx == NULL:
-// instances 0 .. count-1.  The calls change no state, so a shard's refusal (no maps, a matrix map, nrhs) leaves nothing behind either.
-static int adjoint_shares(eicos_multi *mh, const int *idx, int count, const char *who, Shares &sh) {
-    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
-    if (idx) return split_list(mh, idx, count, who, sh);
-    if (count < 0 || count > mh->batch) return mfail(EICOS_E_INVALID, std::string(who) + ": count must lie in [0, batch] when idx is NULL (instances 0 .. count-1)");
-    std::vector<int> all((size_t)count);
-    for (int q = 0; q < count; q++) all[q] = q;
-    return split_list(mh, all.data(), count, who, sh);
+// (x_out with n = 0 reaches the shard as NULL)
+int eicos_multi_update_param_solve_subset(eicos_multi *mh, const int *idx, int count, const double *theta, double *u_out, double *x_out,
+                                          int *exitcodes) {
+    Shares sh;
+    const int rc = split(mh, idx, count, "eicos_multi_update_param_solve_subset", sh);
+    if (rc != EICOS_OK) return rc;
+    const Column cols[] = {in(theta, param_k(mh)), out(u_out, output_r(mh), Column::GIVEN), out(x_out, mh->n), out(exitcodes, 1)};
+    return route_or_pass(mh, sh, idx, count, cols, [&](int s, const int *ids, int k, void *const *p) {
+        return eicos_batch_update_param_solve_subset(mh->shard[s], ids, k, D(p[0]), D(p[1]), D(p[2]), I(p[3]));
+    });
 }
 
+// Adjoint sensitivities (eicos_batch_adjoint / _output_jacobian / _adjoint_data / _param_jacobian / _param_gradient per shard); idx ==
+// NULL: instances 0 .. count-1.  The calls change no state, so a shard's refusal (no maps, a matrix map, nrhs) leaves nothing behind
+// either.  They pack on a handle of one shard too.  J, its res and grad_theta are AT_LEAST_ONE: a handle without its maps gives them
+// width 0, and the shard's own refusal and message come back.
 int eicos_multi_adjoint(eicos_multi *mh, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b,
                         double *res) {
+    const char *who = "eicos_multi_adjoint";
     Shares sh;
-    const int rc = adjoint_shares(mh, idx, count, "eicos_multi_adjoint", sh);
+    int rc = split(mh, idx, count, who, sh, true);
+    if (rc == EICOS_OK) rc = check_g(mh, who, nrhs, g, count);
     if (rc != EICOS_OK) return rc;
-    if (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS) return mfail(EICOS_E_INVALID, "eicos_multi_adjoint: nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
-    if (!g && count > 0 && mh->n > 0) return mfail(EICOS_E_INVALID, "eicos_multi_adjoint: g is NULL");
-    return for_shards(mh, [&](int s) {
-        const std::vector<int> &pos = sh.pos[s];
-        if (pos.empty()) return (int)EICOS_OK;
-        const size_t k = pos.size();
-        const std::vector<double> tg = pack(g, pos, nrhs * mh->n);
-        std::vector<double> tc(grad_c ? k * nrhs * mh->n : 0), th(grad_h ? k * nrhs * mh->m : 0), tb(grad_b ? k * nrhs * mh->p : 0), tr(res ? k * nrhs : 0);
-        const int e = eicos_batch_adjoint(mh->shard[s], sh.ids[s].data(), (int)k, nrhs, given(g, tg), grad_c ? tc.data() : nullptr,
-                                          grad_h ? th.data() : nullptr, grad_b ? tb.data() : nullptr, res ? tr.data() : nullptr);
-        if (e != EICOS_OK) return e;
-        unpack(grad_c, tc, pos, nrhs * mh->n); unpack(grad_h, th, pos, nrhs * mh->m); unpack(grad_b, tb, pos, nrhs * mh->p); unpack(res, tr, pos, nrhs);
-        return (int)EICOS_OK;
-    });
-}
-
-int eicos_multi_output_jacobian(eicos_multi *mh, const int *idx, int count, double *J, double *res) {
-    Shares sh;
-    const int rc = adjoint_shares(mh, idx, count, "eicos_multi_output_jacobian", sh);
-    if (rc != EICOS_OK) return rc;
-    if (!J && count > 0) return mfail(EICOS_E_INVALID, "eicos_multi_output_jacobian: J is NULL");
-    const int r = std::max(0, eicos_batch_output_count(mh->shard[0])), kp = std::max(0, eicos_batch_param_count(mh->shard[0]));
-    return for_shards(mh, [&](int s) {
-        const std::vector<int> &pos = sh.pos[s];
-        if (pos.empty()) return (int)EICOS_OK;
-        // (a handle without its maps: one row, so that the shard's own refusal and message come back)
-        std::vector<double> tj(std::max<size_t>(1, pos.size() * (size_t)r * kp)), tr(res ? std::max<size_t>(1, pos.size() * (size_t)r) : 0);
-        const int e = eicos_batch_output_jacobian(mh->shard[s], sh.ids[s].data(), (int)pos.size(), tj.data(), res ? tr.data() : nullptr);
-        if (e != EICOS_OK) return e;
-        unpack(J, tj, pos, r * kp); unpack(res, tr, pos, r);
-        return (int)EICOS_OK;
+    const Column cols[] = {in(g, nrhs * mh->n), out(grad_c, nrhs * mh->n), out(grad_h, nrhs * mh->m), out(grad_b, nrhs * mh->p), out(res, nrhs)};
+    return route(mh, sh, cols, [&](int s, const int *ids, int k, void *const *p) {
+        return eicos_batch_adjoint(mh->shard[s], ids, k, nrhs, D(p[0]), D(p[1]), D(p[2]), D(p[3]), D(p[4]));
     });
 }
 
 int eicos_multi_adjoint_data(eicos_multi *mh, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b,
                              double *grad_G, double *grad_A, double *res) {
+    const char *who = "eicos_multi_adjoint_data";
     Shares sh;
-    const int rc = adjoint_shares(mh, idx, count, "eicos_multi_adjoint_data", sh);
+    int rc = split(mh, idx, count, who, sh, true);
+    if (rc == EICOS_OK) rc = check_g(mh, who, nrhs, g, count);
     if (rc != EICOS_OK) return rc;
-    if (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS) return mfail(EICOS_E_INVALID, "eicos_multi_adjoint_data: nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
-    if (!g && count > 0 && mh->n > 0) return mfail(EICOS_E_INVALID, "eicos_multi_adjoint_data: g is NULL");
-    const int nnzG = mh->nnzG, nnzA = mh->nnzA;
-    return for_shards(mh, [&](int s) {
-        const std::vector<int> &pos = sh.pos[s];
-        if (pos.empty()) return (int)EICOS_OK;
-        const size_t k = pos.size();
-        const std::vector<double> tg = pack(g, pos, nrhs * mh->n);
-        std::vector<double> tc(grad_c ? k * nrhs * mh->n : 0), th(grad_h ? k * nrhs * mh->m : 0), tb(grad_b ? k * nrhs * mh->p : 0), tr(res ? k * nrhs : 0);
-        std::vector<double> tG(grad_G ? k * nrhs * nnzG : 0), tA(grad_A ? k * nrhs * nnzA : 0);
-        const int e = eicos_batch_adjoint_data(mh->shard[s], sh.ids[s].data(), (int)k, nrhs, given(g, tg), grad_c ? tc.data() : nullptr,
-                                               grad_h ? th.data() : nullptr, grad_b ? tb.data() : nullptr, grad_G ? tG.data() : nullptr,
-                                               grad_A ? tA.data() : nullptr, res ? tr.data() : nullptr);
-        if (e != EICOS_OK) return e;
-        unpack(grad_c, tc, pos, nrhs * mh->n); unpack(grad_h, th, pos, nrhs * mh->m); unpack(grad_b, tb, pos, nrhs * mh->p); unpack(res, tr, pos, nrhs);
-        unpack(grad_G, tG, pos, nrhs * nnzG); unpack(grad_A, tA, pos, nrhs * nnzA);
-        return (int)EICOS_OK;
+    const Column cols[] = {in(g, nrhs * mh->n), out(grad_c, nrhs * mh->n), out(grad_h, nrhs * mh->m), out(grad_b, nrhs * mh->p),
+                           out(grad_G, nrhs * mh->nnzG), out(grad_A, nrhs * mh->nnzA), out(res, nrhs)};
+    return route(mh, sh, cols, [&](int s, const int *ids, int k, void *const *p) {
+        return eicos_batch_adjoint_data(mh->shard[s], ids, k, nrhs, D(p[0]), D(p[1]), D(p[2]), D(p[3]), D(p[4]), D(p[5]), D(p[6]));
     });
 }
 
-// k of the contracted forms: the parameter map's, or -- without one -- the one the matrix map was installed for
-static int contracted_k(eicos_multi *mh) {
-    const int kp = std::max(0, eicos_batch_param_count(mh->shard[0]));
-    return kp ? kp : std::max(0, eicos_batch_matrix_map_count(mh->shard[0]));
-}
-int eicos_multi_param_jacobian(eicos_multi *mh, const int *idx, int count, double *J, double *res) {
+int eicos_multi_output_jacobian(eicos_multi *mh, const int *idx, int count, double *J, double *res) {
+    const char *who = "eicos_multi_output_jacobian";
     Shares sh;
-    const int rc = adjoint_shares(mh, idx, count, "eicos_multi_param_jacobian", sh);
+    int rc = split(mh, idx, count, who, sh, true);
+    if (rc == EICOS_OK) rc = check_given(who, "J", J, count > 0);
     if (rc != EICOS_OK) return rc;
-    if (!J && count > 0) return mfail(EICOS_E_INVALID, "eicos_multi_param_jacobian: J is NULL");
-    const int r = std::max(0, eicos_batch_output_count(mh->shard[0])), kp = contracted_k(mh);
-    return for_shards(mh, [&](int s) {
-        const std::vector<int> &pos = sh.pos[s];
-        if (pos.empty()) return (int)EICOS_OK;
-        // (a handle without its maps: one row, so that the shard's own refusal and message come back)
-        std::vector<double> tj(std::max<size_t>(1, pos.size() * (size_t)r * kp)), tr(res ? std::max<size_t>(1, pos.size() * (size_t)r) : 0);
-        const int e = eicos_batch_param_jacobian(mh->shard[s], sh.ids[s].data(), (int)pos.size(), tj.data(), res ? tr.data() : nullptr);
-        if (e != EICOS_OK) return e;
-        unpack(J, tj, pos, r * kp); unpack(res, tr, pos, r);
-        return (int)EICOS_OK;
-    });
+    const int r = output_r(mh);
+    const Column cols[] = {out(J, r * param_k(mh), Column::AT_LEAST_ONE), out(res, r, Column::AT_LEAST_ONE)};
+    return route(mh, sh, cols, [&](int s, const int *ids, int k, void *const *p) { return eicos_batch_output_jacobian(mh->shard[s], ids, k, D(p[0]), D(p[1])); });
+}
+
+int eicos_multi_param_jacobian(eicos_multi *mh, const int *idx, int count, double *J, double *res) {
+    const char *who = "eicos_multi_param_jacobian";
+    Shares sh;
+    int rc = split(mh, idx, count, who, sh, true);
+    if (rc == EICOS_OK) rc = check_given(who, "J", J, count > 0);
+    if (rc != EICOS_OK) return rc;
+    const int r = output_r(mh);
+    const Column cols[] = {out(J, r * contracted_k(mh), Column::AT_LEAST_ONE), out(res, r, Column::AT_LEAST_ONE)};
+    return route(mh, sh, cols, [&](int s, const int *ids, int k, void *const *p) { return eicos_batch_param_jacobian(mh->shard[s], ids, k, D(p[0]), D(p[1])); });
 }
 
 int eicos_multi_param_gradient(eicos_multi *mh, const int *idx, int count, int nrhs, const double *g, double *grad_theta, double *res) {
+    const char *who = "eicos_multi_param_gradient";
     Shares sh;
-    const int rc = adjoint_shares(mh, idx, count, "eicos_multi_param_gradient", sh);
+    int rc = split(mh, idx, count, who, sh, true);
+    if (rc == EICOS_OK) rc = check_g(mh, who, nrhs, g, count);
+    if (rc == EICOS_OK) rc = check_given(who, "grad_theta", grad_theta, count > 0);
     if (rc != EICOS_OK) return rc;
-    if (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS) return mfail(EICOS_E_INVALID, "eicos_multi_param_gradient: nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
-    if (!g && count > 0 && mh->n > 0) return mfail(EICOS_E_INVALID, "eicos_multi_param_gradient: g is NULL");
-    if (!grad_theta && count > 0) return mfail(EICOS_E_INVALID, "eicos_multi_param_gradient: grad_theta is NULL");
-    const int kp = contracted_k(mh);
-    return for_shards(mh, [&](int s) {
-        const std::vector<int> &pos = sh.pos[s];
-        if (pos.empty()) return (int)EICOS_OK;
-        const std::vector<double> tg = pack(g, pos, nrhs * mh->n);
-        std::vector<double> tt(std::max<size_t>(1, pos.size() * (size_t)nrhs * kp)), tr(res ? pos.size() * (size_t)nrhs : 0);
-        const int e = eicos_batch_param_gradient(mh->shard[s], sh.ids[s].data(), (int)pos.size(), nrhs, given(g, tg), tt.data(), res ? tr.data() : nullptr);
-        if (e != EICOS_OK) return e;
-        unpack(grad_theta, tt, pos, nrhs * kp); unpack(res, tr, pos, nrhs);
-        return (int)EICOS_OK;
-    });
-}
-
-int eicos_multi_update_param_solve_subset(eicos_multi *mh, const int *idx, int count, const double *theta, double *u_out, double *x_out,
-                                          int *exitcodes) {
-    Shares sh;
-    const int rc = split_list(mh, idx, count, "eicos_multi_update_param_solve_subset", sh);
-    if (rc != EICOS_OK) return rc;
-    if (mh->shard.size() == 1) return for_shards(mh, [&](int) { return eicos_batch_update_param_solve_subset(mh->shard[0], idx, count, theta, u_out, x_out, exitcodes); });
-    const int k = std::max(0, eicos_batch_param_count(mh->shard[0])), r = std::max(0, eicos_batch_output_count(mh->shard[0]));
-    return for_shards(mh, [&](int s) {
-        const std::vector<int> &pos = sh.pos[s];
-        if (pos.empty()) return (int)EICOS_OK;
-        const std::vector<double> tt = pack(theta, pos, k);
-        std::vector<double> tu(u_out ? pos.size() * (size_t)r : 0), tx(x_out ? pos.size() * (size_t)mh->n : 0);
-        std::vector<int> codes(exitcodes ? pos.size() : 0);
-        const int e = eicos_batch_update_param_solve_subset(mh->shard[s], sh.ids[s].data(), (int)pos.size(), given(theta, tt),
-                                                            u_out ? (tu.empty() ? u_out : tu.data()) : nullptr, tx.empty() ? nullptr : tx.data(),
-                                                            exitcodes ? codes.data() : nullptr);
-        if (e != EICOS_OK) return e;
-        unpack(u_out, tu, pos, r); unpack(x_out, tx, pos, mh->n);
-        for (size_t q = 0; exitcodes && q < pos.size(); q++) exitcodes[pos[q]] = codes[q];
-        return (int)EICOS_OK;
+    const Column cols[] = {in(g, nrhs * mh->n), out(grad_theta, nrhs * contracted_k(mh), Column::AT_LEAST_ONE), out(res, nrhs)};
+    return route(mh, sh, cols, [&](int s, const int *ids, int k, void *const *p) {
+        return eicos_batch_param_gradient(mh->shard[s], ids, k, nrhs, D(p[0]), D(p[1]), D(p[2]));
     });
 }
 
@@ -626,7 +532,7 @@ int eicos_multi_update_solve(eicos_multi *mh, const double *G, const double *A, 
     return for_shards(mh, [&](int s) {
         const size_t r = (size_t)mh->first[s];
         return eicos_batch_update_solve(mh->shard[s], at(G, r, mh->nnzG), at(A, r, mh->nnzA), at(c, r, mh->n), at(hh, r, mh->m), at(b, r, mh->p),
-                                        x_out ? x_out + r * (size_t)mh->n : nullptr, exitcodes ? exitcodes + r : nullptr);
+                                        at(x_out, r, mh->n), at(exitcodes, r, 1));
     });
 }
 
@@ -634,8 +540,7 @@ int eicos_multi_update_rhs_solve(eicos_multi *mh, const double *c, const double 
     if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
     return for_shards(mh, [&](int s) {
         const size_t r = (size_t)mh->first[s];
-        return eicos_batch_update_rhs_solve(mh->shard[s], at(c, r, mh->n), at(hh, r, mh->m), at(b, r, mh->p),
-                                            x_out ? x_out + r * (size_t)mh->n : nullptr, exitcodes ? exitcodes + r : nullptr);
+        return eicos_batch_update_rhs_solve(mh->shard[s], at(c, r, mh->n), at(hh, r, mh->m), at(b, r, mh->p), at(x_out, r, mh->n), at(exitcodes, r, 1));
     });
 }
 
@@ -645,8 +550,7 @@ int eicos_multi_update_param_solve(eicos_multi *mh, const double *theta, double 
     const int k = eicos_batch_param_count(mh->shard[0]), ro = eicos_batch_output_count(mh->shard[0]);
     return for_shards(mh, [&](int s) {
         const size_t r = (size_t)mh->first[s];
-        return eicos_batch_update_param_solve(mh->shard[s], at(theta, r, k), u_out ? u_out + r * (size_t)ro : nullptr,
-                                              x_out ? x_out + r * (size_t)mh->n : nullptr, exitcodes ? exitcodes + r : nullptr);
+        return eicos_batch_update_param_solve(mh->shard[s], at(theta, r, k), at(u_out, r, ro), at(x_out, r, mh->n), at(exitcodes, r, 1));
     });
 }
 
@@ -686,43 +590,36 @@ int eicos_multi_rollout(eicos_multi *mh, int steps, const double *theta0, const 
     const size_t k = (size_t)eicos_batch_param_count(mh->shard[0]), ro = (size_t)eicos_batch_output_count(mh->shard[0]), T = (size_t)steps;
     return for_shards(mh, [&](int s) {
         const size_t f = (size_t)mh->first[s];
-        return eicos_batch_rollout(mh->shard[s], steps, theta0 ? theta0 + f * k : nullptr, w ? w + f * T * k : nullptr,
-                                   u_traj ? u_traj + f * T * ro : nullptr, theta_traj ? theta_traj + f * (T + 1) * k : nullptr,
-                                   exitcodes ? exitcodes + f * T : nullptr, iters ? iters + f * T : nullptr);
+        return eicos_batch_rollout(mh->shard[s], steps, at(theta0, f, k), at(w, f, T * k), at(u_traj, f, T * ro), at(theta_traj, f, (T + 1) * k),
+                                   at(exitcodes, f, T), at(iters, f, T));
     });
 }
 
 int eicos_multi_solution(eicos_multi *mh, double *x) {
     if (!mh || !x) return mfail(EICOS_E_INVALID, "NULL argument");
     if (mh->n == 0) return EICOS_OK;
-    return for_shards(mh, [&](int s) { return eicos_batch_solution(mh->shard[s], x + (size_t)mh->first[s] * mh->n); });
+    return for_shards(mh, [&](int s) { return eicos_batch_solution(mh->shard[s], at(x, (size_t)mh->first[s], mh->n)); });
 }
 
 int eicos_multi_duals(eicos_multi *mh, double *y, double *z, double *sl) {
     if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
     return for_shards(mh, [&](int s) {
         const size_t f = (size_t)mh->first[s];
-        return eicos_batch_duals(mh->shard[s], y ? y + f * mh->p : nullptr, z ? z + f * mh->m : nullptr, sl ? sl + f * mh->m : nullptr);
+        return eicos_batch_duals(mh->shard[s], at(y, f, mh->p), at(z, f, mh->m), at(sl, f, mh->m));
     });
 }
 
 int eicos_multi_set_warm_start(eicos_multi *mh, double shift) {
-    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
-    for (eicos_batch *h : mh->shard) { const int rc = eicos_batch_set_warm_start(h, shift); if (rc != EICOS_OK) return mfail(rc, eicos_last_error()); }
-    return EICOS_OK;
+    return in_turn(mh, false, [&](int s) { return eicos_batch_set_warm_start(mh->shard[s], shift); });
 }
 
 int eicos_multi_set_dynamic_regularization(eicos_multi *mh, double delta, double eps) {
-    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
-    for (eicos_batch *h : mh->shard) { const int rc = eicos_batch_set_dynamic_regularization(h, delta, eps); if (rc != EICOS_OK) return mfail(rc, eicos_last_error()); }
-    return EICOS_OK;
+    return in_turn(mh, false, [&](int s) { return eicos_batch_set_dynamic_regularization(mh->shard[s], delta, eps); });
 }
 
 // (validation does not depend on the shard: the first shard refuses what any would, before one of them has changed)
 int eicos_multi_set_settings(eicos_multi *mh, const eicos_settings *st) {
-    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
-    for (eicos_batch *h : mh->shard) { const int rc = eicos_batch_set_settings(h, st); if (rc != EICOS_OK) return mfail(rc, eicos_last_error()); }
-    return EICOS_OK;
+    return in_turn(mh, false, [&](int s) { return eicos_batch_set_settings(mh->shard[s], st); });
 }
 
 int eicos_multi_get_settings(eicos_multi *mh, eicos_settings *out) {

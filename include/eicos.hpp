@@ -251,9 +251,7 @@ namespace EiCOS
         {
             std::vector<int> codes(batch_);
             mcheck(eicos_multi_update_param_solve(h_, theta, u_out, x_out, codes.data()), "eicos_multi_update_param_solve");
-            std::vector<exitcode> out(batch_);
-            for (int i = 0; i < batch_; i++) out[i] = static_cast<exitcode>(codes[i]);
-            return out;
+            return exitcodes(codes);
         }
         // Extension: the simulated plant of a closed loop, theta+ = f0 + F [theta | u] (+ w) (eicos_affine_map: base[k] + CSR matrix
         // k x (k + r)), installed behind the parameter and the output map; nullptr removes it.  rollout() then runs `steps` closed-loop
@@ -267,9 +265,7 @@ namespace EiCOS
         {
             std::vector<int> codes((size_t)batch_ * (steps > 0 ? steps : 0));
             mcheck(eicos_multi_rollout(h_, steps, theta0, w, u_traj, theta_traj, codes.data(), iters), "eicos_multi_rollout");
-            std::vector<exitcode> out(codes.size());
-            for (size_t i = 0; i < codes.size(); i++) out[i] = static_cast<exitcode>(codes[i]);
-            return out;
+            return exitcodes(codes);
         }
         // Extension: the stored values of G and A affine in theta (MatrixMap: per matrix an eicos_affine_map with one row per stored
         // value, CSC order, k columns), installed behind the parameter map; both nullptr removes it.  updateParam, stepParam and rollout
@@ -332,9 +328,7 @@ namespace EiCOS
         {
             std::vector<int> codes(batch_);
             mcheck(eicos_multi_solve(h_, codes.data()), "eicos_multi_solve");
-            std::vector<exitcode> out(batch_);
-            for (int i = 0; i < batch_; i++) out[i] = static_cast<exitcode>(codes[i]);
-            return out;
+            return exitcodes(codes);
         }
         // updateData(...) + solve() in ONE call (reference include/eicos.hpp:155-158 back to back): with arrays from hostAlloc / hostRegister the
         // solve kernel's workgroups pull every instance's inputs over PCIe themselves, behind each other's compute, and write x into a pinned
@@ -343,18 +337,14 @@ namespace EiCOS
         {
             std::vector<int> codes(batch_);
             mcheck(eicos_multi_update_solve(h_, Gpr, Apr, c, h, b, x_out, codes.data()), "eicos_multi_update_solve");
-            std::vector<exitcode> out(batch_);
-            for (int i = 0; i < batch_; i++) out[i] = static_cast<exitcode>(codes[i]);
-            return out;
+            return exitcodes(codes);
         }
         // updateRHS(...) + solve() in ONE call (same paths as the form above; the solve kernel scales the vectors of pinned arrays itself)
         std::vector<exitcode> solve(const double *c, const double *h, const double *b, double *x_out = nullptr)
         {
             std::vector<int> codes(batch_);
             mcheck(eicos_multi_update_rhs_solve(h_, c, h, b, x_out, codes.data()), "eicos_multi_update_rhs_solve");
-            std::vector<exitcode> out(batch_);
-            for (int i = 0; i < batch_; i++) out[i] = static_cast<exitcode>(codes[i]);
-            return out;
+            return exitcodes(codes);
         }
         // Extension: solve a chosen subset of the batch (eicos_batch_solve_subset / _solve_where of eicos_amd.h: contract and refusals
         // there).  Indices are global instance ids, each at most once.  An instance of the subset ends, bit for bit, as a solve() of the
@@ -374,9 +364,7 @@ namespace EiCOS
         {
             std::vector<int> codes(indices.size());
             mcheck(eicos_multi_solve_subset(h_, indices.data(), (int)indices.size(), codes.data()), "eicos_multi_solve_subset");
-            std::vector<exitcode> out(codes.size());
-            for (size_t i = 0; i < codes.size(); i++) out[i] = static_cast<exitcode>(codes[i]);
-            return out;
+            return exitcodes(codes);
         }
         // solveWhere: select(mask) + solveSubset with the id list used in place on the GPU; (ids ascending, their exit codes)
         std::pair<std::vector<int>, std::vector<exitcode>> solveWhere(unsigned mask)
@@ -384,10 +372,8 @@ namespace EiCOS
             std::vector<int> ids(batch_), codes(batch_);
             int count = 0;
             mcheck(eicos_multi_solve_where(h_, mask, ids.data(), &count, codes.data()), "eicos_multi_solve_where");
-            ids.resize(count);
-            std::vector<exitcode> out(count);
-            for (int i = 0; i < count; i++) out[i] = static_cast<exitcode>(codes[i]);
-            return {ids, out};
+            ids.resize(count); codes.resize(count);
+            return {ids, exitcodes(codes)};
         }
         // gather: the rows of `indices`, in list order, into x [count][n], y [count][p], z, s [count][m] and info [count] (any nullptr):
         // packed on the GPU and fetched with one copy, instead of whole-batch solution() / duals() / getInfo()
@@ -429,9 +415,7 @@ namespace EiCOS
             std::vector<int> codes(indices.size());
             mcheck(eicos_multi_update_param_solve_subset(h_, indices.data(), (int)indices.size(), theta, u_out, x_out, codes.data()),
                    "eicos_multi_update_param_solve_subset");
-            std::vector<exitcode> out(indices.size());
-            for (size_t i = 0; i < indices.size(); i++) out[i] = static_cast<exitcode>(codes[i]);
-            return out;
+            return exitcodes(codes);
         }
         // Extension: adjoint sensitivities at the returned iterate (eicos_multi_adjoint / _output_jacobian; the definition and its
         // degeneracy caveat: eicos_amd.h).  adjoint: g [count][nrhs][n] in, grad_c [count][nrhs][n], grad_h [count][nrhs][m],
@@ -535,6 +519,12 @@ namespace EiCOS
         static void mcheck(int rc, const char *what)
         {
             if (rc != EICOS_OK) throw std::runtime_error(std::string(what) + ": " + eicos_multi_last_error());
+        }
+        static std::vector<exitcode> exitcodes(const std::vector<int> &codes) // the C ABI's exit codes as the enum
+        {
+            std::vector<exitcode> out(codes.size());
+            for (size_t i = 0; i < codes.size(); i++) out[i] = static_cast<exitcode>(codes[i]);
+            return out;
         }
         eicos_multi *h_ = nullptr;
         int n_, m_, p_, batch_;
