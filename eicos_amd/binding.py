@@ -247,6 +247,14 @@ def _lib():
             for f in ("adjoint_data", "param_jacobian", "param_gradient", "matrix_map_count"):
                 getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
             L.eicos_batch_param_jacobian_device.restype = L.eicos_batch_param_gradient_device.restype = C.c_int
+        if hasattr(L, "eicos_batch_rollout_jacobian"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
+            L.eicos_batch_rollout_jacobian.argtypes = L.eicos_multi_rollout_jacobian.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip, ip, dp, dp]
+            L.eicos_batch_rollout_gradient.argtypes = L.eicos_multi_rollout_gradient.argtypes = [vp, dp, dp, dp, dp]
+            L.eicos_batch_rollout_gradient_device.argtypes = [vp, vp, vp, vp, vp]
+            L.eicos_batch_rollout_jacobian_steps.argtypes = [vp]
+            for f in ("rollout_jacobian", "rollout_gradient"):
+                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
+            L.eicos_batch_rollout_gradient_device.restype = L.eicos_batch_rollout_jacobian_steps.restype = C.c_int
         if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
             L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
             L.eicos_batch_ms_history.restype = C.c_int
@@ -490,6 +498,16 @@ def _output_map_ptr(omap, pat):
                        f"{omap.r} rows over {pat.n} variables", omap.n == pat.n)
 
 
+def _cotangent(a, shape, name):
+    """A cotangent array of a rollout (None passes through) as contiguous float64 of exactly `shape`."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != tuple(shape):
+        raise ValueError(f"{name} has shape {a.shape}, expected {list(shape)}")
+    return a
+
+
 class PlantMap:
     """The simulated plant of a closed loop, theta+ = f0 + F [theta | u] (+ w): `(base, rowptr, col, val)` -- base[k] and a CSR matrix
     with k rows whose columns index z = [theta (k) | u (r)], i.e. lie in [0, k + r) -- shared by all instances.  evaluate() is the host
@@ -511,6 +529,41 @@ class PlantMap:
                 raise ValueError(f"w has shape {w.shape}, expected {theta.shape}")
         acc = _affine_eval((self.base, self.rowptr, self.col, self.val), np.concatenate((theta, u), axis=1))
         return acc if w is None else acc + w
+
+    def backprop(self, J, gu=None, gtheta=None):
+        """(grad_theta0 [B, k], grad_w [B, T, k]): the gradient of L = sum_t gu_t' u_t + sum_t gtheta_t' theta_t over a rollout with
+        the step Jacobians J [B, T, r, k] (rollout_jacobian) -- gu [B, T, r] and gtheta [B, T + 1, k], each optional, one must be
+        given.  The scalar loop of eicos_batch_rollout_gradient in its stated order, every product and sum rounded on its own; a
+        missing cotangent counts as 0.0 and is still added.  A NaN row of J makes that instance's gradient NaN."""
+        k, r = self.k, self.r
+        J = np.ascontiguousarray(J, dtype=np.float64)
+        if J.ndim != 4 or J.shape[2:] != (r, k):
+            raise ValueError(f"J has shape {J.shape}, expected [batch, steps, {r}, {k}]")
+        B, T = int(J.shape[0]), int(J.shape[1])
+        if gu is None and gtheta is None:
+            raise ValueError("gu and gtheta are both None")
+        gu, gtheta = _cotangent(gu, (B, T, r), "gu"), _cotangent(gtheta, (B, T + 1, k), "gtheta")
+        rowptr, col, val = self.rowptr, self.col, self.val
+        g0, gw = np.zeros((B, k)), np.zeros((B, T, k))
+        zero = np.float64(0.0)
+        for b in range(B):
+            lam = [gtheta[b, T, c] if gtheta is not None else zero for c in range(k)]
+            for t in range(T - 1, -1, -1):
+                gw[b, t, :] = lam
+                v = [zero] * (k + r)
+                for i in range(k):
+                    for s in range(int(rowptr[i]), int(rowptr[i + 1])):
+                        v[col[s]] = v[col[s]] + (val[s] * lam[i])
+                mu = [(gu[b, t, j] if gu is not None else zero) + v[k + j] for j in range(r)]
+                new = []
+                for c in range(k):
+                    acc = (gtheta[b, t, c] if gtheta is not None else zero) + v[c]
+                    for j in range(r):
+                        acc = acc + (J[b, t, j, c] * mu[j])
+                    new.append(acc)
+                lam = new
+            g0[b, :] = lam
+        return g0, gw
 
 
 def _plant_map_ptr(fmap, k, r):
@@ -836,6 +889,51 @@ class _Solver:
                    _dp(u_traj if u_traj.size else one), _dp(theta_traj if theta_traj.size else one), _ip(codes), _ip(iters))
         return u_traj, theta_traj, codes, iters
 
+    def rollout_jacobian(self, theta0, steps: int, w=None):
+        """rollout() that also records the Jacobian of every step: returns (u_traj, theta_traj, exitcodes, iters, J [batch, steps, r, k],
+        res [batch, steps, r]) -- J[i, t] and res[i, t] are what param_jacobian() returns for instance i right after step t's solve, bit
+        for bit, the first four what rollout() returns; still one launch with an LDS vector on the handle.  A step that did not end
+        OPTIMAL / OPTIMAL_INACC has NaN rows, and the loop goes on.  The handle keeps J on the GPU for rollout_gradient()."""
+        steps = int(steps)
+        k, r = self.param_count(), self.output_count()
+        if k > 0:
+            theta0, _ = _theta_rows(theta0, k, self.batch)
+            w = _disturbance(w, self.batch, steps, k)
+        else:  # (the library refuses: "no parameter map")
+            theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
+            w = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
+        T = max(steps, 0)
+        u_traj, theta_traj = np.zeros((self.batch, T, r)), np.zeros((self.batch, T + 1, k))
+        codes, iters = np.zeros((self.batch, T), np.int32), np.zeros((self.batch, T), np.int32)
+        J, res = np.zeros((self.batch, T, r, k)), np.zeros((self.batch, T, r))
+        one = np.zeros(1)
+        self._call("rollout_jacobian", steps, _dp(theta0 if theta0.size else one), None if w is None else _dp(w if w.size else one),
+                   _dp(u_traj if u_traj.size else one), _dp(theta_traj if theta_traj.size else one), _ip(codes), _ip(iters),
+                   _dp(J if J.size else one), _dp(res if res.size else one))
+        self._rollout_shape = (T, k, r)
+        return u_traj, theta_traj, codes, iters, J, res
+
+    def rollout_gradient(self, gu=None, gtheta=None, device=False):
+        """(grad_theta0 [batch, k], grad_w [batch, T, k]): the gradient of L = sum_t gu_t' u_t + sum_t gtheta_t' theta_t over the most
+        recent rollout_jacobian() of the handle, by a backward sweep on the GPU -- gu [batch, T, r], gtheta [batch, T + 1, k], each
+        optional, one must be given.  Bit for bit PlantMap.backprop of the returned J.  device=True (single-GPU handles): through the
+        device form, fetched here; the same bits."""
+        shape = getattr(self, "_rollout_shape", None)
+        if shape is None:  # (no rollout_jacobian yet: the library refuses, with its message)
+            gu, gtheta = (None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (gu, gtheta))
+            self._call("rollout_gradient", None if gu is None else _dp(gu), None if gtheta is None else _dp(gtheta), _dp(np.zeros(1)), None)
+            raise RuntimeError("rollout_gradient: no rollout_jacobian() on this handle")
+        T, k, r = shape
+        gu, gtheta = _cotangent(gu, (self.batch, T, r), "gu"), _cotangent(gtheta, (self.batch, T + 1, k), "gtheta")
+        g0, gw = np.zeros((self.batch, k)), np.zeros((self.batch, T, k))
+        one = np.zeros(1)
+        if device:
+            self._device_form("rollout_gradient_device", None, 0, (), (gu, gtheta), (g0, gw), lead=())
+        else:
+            self._call("rollout_gradient", None if gu is None else _dp(gu if gu.size else one), None if gtheta is None else _dp(gtheta if gtheta.size else one),
+                       _dp(g0 if g0.size else one), _dp(gw if gw.size else one))
+        return g0, gw
+
     # ---- solve ----
     def solve(self):
         codes = np.zeros(self.batch, np.int32)
@@ -1013,8 +1111,9 @@ class _Solver:
     def _theta_width(self):
         return max(self.param_count(), 0) or max(self.matrix_map_count(), 0)
 
-    def _device_form(self, name, ptr, count, head, ins, outs):
-        """A *_device call on host arrays: device copies of `ins`, the call, sync, `outs` fetched -- the same bits as the host form."""
+    def _device_form(self, name, ptr, count, head, ins, outs, lead=None):
+        """A *_device call on host arrays: device copies of `ins`, the call, sync, `outs` fetched -- the same bits as the host form.
+        An input that is None travels as a NULL pointer; lead: the arguments in front of `head` when they are not (ptr, count)."""
         if self._prefix != "eicos_batch_":
             raise ValueError(name + ": device=True needs a single-GPU handle")
         hip = _lib()
@@ -1025,13 +1124,13 @@ class _Solver:
         try:
             for a in list(ins) + list(outs):
                 d = C.c_void_p()
-                if hip.hipMalloc(C.byref(d), max(a.nbytes, 8)) != 0:
+                if a is not None and hip.hipMalloc(C.byref(d), max(a.nbytes, 8)) != 0:
                     raise RuntimeError("hipMalloc failed")
                 bufs.append(d)
             for a, d in zip(ins, bufs):
-                if a.nbytes and hip.hipMemcpy(d, a.ctypes.data, a.nbytes, 1) != 0:  # hipMemcpyHostToDevice
+                if a is not None and a.nbytes and hip.hipMemcpy(d, a.ctypes.data, a.nbytes, 1) != 0:  # hipMemcpyHostToDevice
                     raise RuntimeError("hipMemcpy failed")
-            self._call(name, ptr, count, *head, *bufs)
+            self._call(name, *((ptr, count) if lead is None else lead), *head, *bufs)
             self._call("sync")
             for a, d in zip(outs, bufs[len(ins):]):
                 if a.nbytes and hip.hipMemcpy(a.ctypes.data, d, a.nbytes, 2) != 0:  # hipMemcpyDeviceToHost

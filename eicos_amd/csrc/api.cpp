@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <climits>
 #include <cstring>
 #include <atomic>
 #include <condition_variable>
@@ -177,6 +178,12 @@ struct eicos_batch {
     // grad_G | grad_A] -- the record of the launch, its index list and the staging of the host forms' rows (the contracted forms keep J /
     // grad_theta where grad_c would be)
     DevBuf d_adj; AdjointDev adj{}; // (adj: the host copy of the most recent launch's record, the source of its copy on the handle's stream)
+    // The rollout that records its Jacobians (eicos_batch_rollout_jacobian), kept for eicos_batch_rollout_gradient: one device allocation,
+    // grown on demand: [AdjointDev of the fused launch (MAP_HEADER bytes) | J trajectory [batch][steps][r][k] | res trajectory
+    // [batch][steps][r] | one step's J and res rows of the batch (the path that is not fused)]; d_rollG = [gu | gtheta | grad_theta0 |
+    // grad_w] of the gradient call's host form.  rollJ_steps = 0: no trajectory on the handle; rollJ_plant, rollJ_k / _r = the plant map and counts it was
+    // recorded under; map_gen counts the installs of the parameter, matrix, output and plant maps, rollJ_gen = its value at that rollout.
+    DevBuf d_rollJ, d_rollG; int rollJ_steps = 0, rollJ_k = 0, rollJ_r = 0; PlantMapDev rollJ_plant{}; unsigned long map_gen = 0, rollJ_gen = 0;
     hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr; bool adjoint_timed = false; // HIP events around the most recent adjoint launch (eicos_batch_last_adjoint_ms)
 
     // The events and the stream the handle made; the buffers free themselves after this body.  eicos_batch_destroy has set the device and
@@ -372,6 +379,7 @@ static int install_map(eicos_batch *h, DevBuf &slot, Desc &cur, const char *name
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
     slot.reset(); // (first, so that the old and the new map never coexist; a failure below leaves the handle without this map)
+    if (&slot != &h->d_shift) h->map_gen++; // (eicos_batch_rollout_gradient: a recorded rollout belongs to the maps it ran under; the shift map is not one of them)
     cur = Desc{};
     if (!M) return EICOS_OK;
     const AffineLayout lay = affine_layout(g, n, MAP_HEADER, gap);
@@ -1254,7 +1262,8 @@ static SolveLaunch solve_launch(const eicos_batch *h, int subset) {
 }
 // The one place that enqueues k_solve on the handle's stream.  step: the update fused into this launch (update_solve, the rollout), NULL
 // for a plain solve; it lives for this call only.  subset >= 0: the launch takes that many chosen instances (solve_launch).
-static int enqueue_solve(eicos_batch *h, const UpdArgs *step, int subset = -1) {
+// sens != NULL (the rollout that records its Jacobians): the build's k_roll_sens takes the launch, with that adjoint record.
+static int enqueue_solve(eicos_batch *h, const UpdArgs *step, int subset = -1, const AdjointDev *sens = nullptr) {
     HIP_TRY(hipSetDevice(h->device));
     { const int rc = next_events(h->ring_s, h->n_solve_rec, h->ev_s0, h->ev_s1); if (rc != EICOS_OK) return rc; }
     h->ring_step0[(h->n_solve_rec - 1) % eicos_batch::EV_RING] = h->update_timed ? h->ev_u0 : h->ev_s0;
@@ -1267,7 +1276,9 @@ static int enqueue_solve(eicos_batch *h, const UpdArgs *step, int subset = -1) {
     args.shared = h->shared_on ? h->d_shared.as<int>() : nullptr;
     SolveLaunch L = solve_launch(h, subset);
     if (args.rows_at) L.rows = h->queue() + args.rows_at; // (a step in list order: the selection kernel of this launch fills the row map it reads)
-    HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(L, h->stream, args));
+    const SolveBuild build = solve_build(h->threads, h->ldsres, h->w2, h->ubl);
+    if (sens) HIP_TRY(build.roll_sens(L, h->stream, args, sens));
+    else HIP_TRY(build.launch(L, h->stream, args));
     HIP_TRY(hipEventRecord(h->ev_s1, h->stream));
     h->solve_timed = true;
     h->last_subset = subset >= 0; h->last_count = subset >= 0 ? subset : h->batch;
@@ -2026,8 +2037,12 @@ int eicos_batch_last_rollout_launches(eicos_batch *h) { return h ? h->rollout_la
 // trajectories live in the handle's device buffer and the caller's arrays -- of any kind of memory -- are copied in before and out after.
 // Not fused: the same buffer, and per step four launches on the stream, the step's theta rows in two contiguous [batch][k] buffers that
 // take turns (the range kernels read and write rows k / r doubles apart; k_plant_range moves them into the trajectories).
-int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
-                        int *exitcodes, int *iters) {
+// sens (eicos_batch_rollout_jacobian): every step also leaves J_t = d u_t / d theta_t and its refinement residuals in the handle's J and res
+// trajectories (eicos_batch::d_rollJ) -- fused: k_roll_sens in the place of k_solve, still one launch; not fused: one adjoint launch in
+// its contracted device form (what eicos_batch_param_jacobian_device enqueues) between the step's output and plant kernels, its rows
+// moved into the trajectories on the stream.  No host synchronisation between the steps on either path.
+static int rollout_run(eicos_batch *h, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
+                       int *exitcodes, int *iters, bool sens, double *J_traj, double *res_traj) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     if (steps < 1) return fail(EICOS_E_INVALID, "rollout: steps must be at least 1");
     if (h->param.k == 0) return fail(EICOS_E_INVALID, "no parameter map (eicos_batch_set_param_map installs one)");
@@ -2040,8 +2055,17 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
     { const int rc = matrix_map_fits(h); if (rc != EICOS_OK) return rc; }
     if (!theta0) return fail(EICOS_E_INVALID, "rollout: theta0 is NULL");
     if (!u_traj) return fail(EICOS_E_INVALID, "rollout: u_traj is NULL");
+    if (sens && !J_traj) return fail(EICOS_E_INVALID, "rollout_jacobian: J_traj is NULL");
+    if (sens && (size_t)h->batch * (size_t)steps > (size_t)INT_MAX) return fail(EICOS_E_INVALID, "rollout_jacobian: batch * steps must fit an int");
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = (size_t)h->batch, T = (size_t)steps;
+    const size_t n_J = B * T * r * k, n_res = B * T * r, n_J1 = B * r * k, n_res1 = B * r;
+    double *d_J = nullptr, *d_res = nullptr, *d_J1 = nullptr, *d_res1 = nullptr;
+    if (sens) {
+        h->rollJ_steps = 0; // (until this rollout has been enqueued whole: a failure below leaves no trajectory)
+        HIP_TRY_AS("hipMalloc", h->d_rollJ.reserve(MAP_HEADER + (n_J + n_res + n_J1 + n_res1) * sizeof(double), h->stream));
+        d_J = reinterpret_cast<double *>(h->d_rollJ.as<char>() + MAP_HEADER); d_res = d_J + n_J; d_J1 = d_res + n_res; d_res1 = d_J1 + n_J1;
+    }
     const size_t n_th = B * (T + 1) * k, n_u = B * T * r, n_w = w ? B * T * k : 0, n_cur = 2 * B * k, n_rec = B * T;
     HIP_TRY_AS("hipMalloc", h->d_roll.reserve(MAP_HEADER + (n_th + n_u + n_w + n_cur) * sizeof(double) + 2 * n_rec * sizeof(int), h->stream));
     double *d_th = reinterpret_cast<double *>(h->d_roll.as<char>() + MAP_HEADER), *d_uu = d_th + n_th, *d_w = d_uu + n_u, *d_cur = d_w + n_w;
@@ -2060,7 +2084,13 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
         step.on = UPD_ROLL; step.roll = h->d_roll.as<const RolloutDev>();
         step.pmap = h->d_param.as<const ParamMapDev>(); step.omap = h->d_out.as<const OutMapDev>();
         if (h->mat.k) step.mmap = h->d_mat.as<const MatrixMapDev>();
-        rc = enqueue_solve(h, &step);
+        if (sens) { // the record of the launch's adjoints (launch.hpp: AdjointDev, the contracted form with the output map's rows), as adjoint_run fills it
+            AdjointDev rec{};
+            rec.pmap = h->d_param.as<const ParamMapDev>(); rec.mmap = h->mat.k ? h->d_mat.as<const MatrixMapDev>() : nullptr;
+            rec.omap = h->d_out.as<const OutMapDev>(); rec.k = k; rec.J = d_J; rec.res = d_res;
+            HIP_TRY(hipMemcpyAsync(h->d_rollJ.p, &rec, sizeof rec, hipMemcpyHostToDevice, h->stream));
+        }
+        rc = enqueue_solve(h, &step, -1, sens ? h->d_rollJ.as<const AdjointDev>() : nullptr);
         if (rc != EICOS_OK) return rc;
     } else {
         HIP_TRY(hipMemcpy2DAsync(d_cur, row_b, d_th, (T + 1) * row_b, row_b, B, hipMemcpyDeviceToDevice, h->stream));
@@ -2073,6 +2103,13 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
             if (rc == EICOS_OK) rc = enqueue_solve(h, nullptr);
             if (rc != EICOS_OK) return rc;
             HIP_TRY(launch_outputs(h->pslot, h->inst(), 0, h->batch, h->out, h->d_u, h->stream));
+            if (sens) {
+                rc = param_contracted(h, nullptr, h->batch, 0, nullptr, false, d_J1, "J", d_res1, true, "eicos_batch_rollout_jacobian");
+                if (rc != EICOS_OK) return rc;
+                const size_t jb = (size_t)r * k * sizeof(double), rb = (size_t)r * sizeof(double);
+                HIP_TRY(hipMemcpy2DAsync(d_J + (size_t)t * r * k, T * jb, d_J1, jb, jb, B, hipMemcpyDeviceToDevice, h->stream));
+                HIP_TRY(hipMemcpy2DAsync(d_res + (size_t)t * r, T * rb, d_res1, rb, rb, B, hipMemcpyDeviceToDevice, h->stream));
+            }
             HIP_TRY(launch_plant(h->pslot, h->inst(), 0, h->batch, h->roll, t, cur, h->d_u, next, h->stream));
         }
     }
@@ -2081,8 +2118,69 @@ int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const d
     if (theta_traj) HIP_TRY(hipMemcpyAsync(theta_traj, d_th, n_th * sizeof(double), hipMemcpyDefault, h->stream));
     if (exitcodes) HIP_TRY(hipMemcpyAsync(exitcodes, d_codes, n_rec * sizeof(int), hipMemcpyDefault, h->stream));
     if (iters) HIP_TRY(hipMemcpyAsync(iters, d_iters, n_rec * sizeof(int), hipMemcpyDefault, h->stream));
+    if (sens) {
+        HIP_TRY(hipMemcpyAsync(J_traj, d_J, n_J * sizeof(double), hipMemcpyDefault, h->stream));
+        if (res_traj) HIP_TRY(hipMemcpyAsync(res_traj, d_res, n_res * sizeof(double), hipMemcpyDefault, h->stream));
+        h->rollJ_steps = steps; h->rollJ_k = k; h->rollJ_r = r; h->rollJ_plant = h->plant; h->rollJ_gen = h->map_gen;
+    }
     HIP_TRY(hipStreamSynchronize(h->stream));
     return EICOS_OK;
+}
+int eicos_batch_rollout(eicos_batch *h, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
+                        int *exitcodes, int *iters) {
+    return rollout_run(h, steps, theta0, w, u_traj, theta_traj, exitcodes, iters, false, nullptr, nullptr);
+}
+int eicos_batch_rollout_jacobian(eicos_batch *h, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
+                                 int *exitcodes, int *iters, double *J_traj, double *res_traj) {
+    return rollout_run(h, steps, theta0, w, u_traj, theta_traj, exitcodes, iters, true, J_traj, res_traj);
+}
+
+// The backward sweep over the most recent eicos_batch_rollout_jacobian of the handle (launch.hpp: launch_rollout_backprop), behind
+// everything on the handle's stream.  Every check stands in front of the first enqueue.  The host form stages its arrays in d_rollG
+// and waits; the device form only enqueues.
+static int rollout_gradient(eicos_batch *h, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w, bool device, const char *who) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    const std::string w(who);
+    if (h->rollJ_steps == 0) return fail(EICOS_E_INVALID, w + ": the handle holds no Jacobian trajectory (eicos_batch_rollout_jacobian records one)");
+    if (h->rollJ_gen != h->map_gen) return fail(EICOS_E_INVALID, w + ": a parameter, matrix, output or plant map was installed after the rollout whose Jacobians the handle holds: run eicos_batch_rollout_jacobian again");
+    if (!gu && !gtheta) return fail(EICOS_E_INVALID, w + ": gu and gtheta are both NULL");
+    if (!grad_theta0) return fail(EICOS_E_INVALID, w + ": grad_theta0 is NULL");
+    const char *other = device ? " must live in device memory (the form without _device takes host pointers)" : " lives in device memory: this form takes host pointers (use the _device form)";
+    const struct { const void *p; const char *name; } arr[4] = {{gu, "gu"}, {gtheta, "gtheta"}, {grad_theta0, "grad_theta0"}, {grad_w, "grad_w"}};
+    for (const auto &a : arr) if (a.p && (memory_kind(a.p, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": " + a.name + other);
+    const size_t B = (size_t)h->batch, T = (size_t)h->rollJ_steps, k = (size_t)h->rollJ_k, r = (size_t)h->rollJ_r;
+    if (rollout_backprop_lds((int)k, (int)r) > 48 * 1024) return fail(EICOS_E_INVALID, w + ": 3 k + 2 r doubles must fit 48 KB of LDS");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t n_gu = B * T * r, n_gt = B * (T + 1) * k, n_g0 = B * k, n_gw = B * T * k;
+    const double *d_J = reinterpret_cast<const double *>(h->d_rollJ.as<char>() + MAP_HEADER);
+    const double *d_gu = gu, *d_gt = gtheta; double *d_g0 = grad_theta0, *d_gw = grad_w;
+    if (!device) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY_AS("hipMalloc", h->d_rollG.reserve((n_gu + n_gt + n_g0 + n_gw) * sizeof(double), h->stream));
+        double *at = h->d_rollG.as<double>();
+        if (gu) { HIP_TRY(hipMemcpyAsync(at, gu, n_gu * sizeof(double), hipMemcpyHostToDevice, h->stream)); d_gu = at; }
+        at += n_gu;
+        if (gtheta) { HIP_TRY(hipMemcpyAsync(at, gtheta, n_gt * sizeof(double), hipMemcpyHostToDevice, h->stream)); d_gt = at; }
+        at += n_gt;
+        d_g0 = at; d_gw = grad_w ? at + n_g0 : nullptr;
+    }
+    if (!h->ev_a0) { HIP_TRY(hipEventCreate(&h->ev_a0)); HIP_TRY(hipEventCreate(&h->ev_a1)); }
+    HIP_TRY(hipEventRecord(h->ev_a0, h->stream)); // (eicos_batch_last_adjoint_ms: the sweep counts as the handle's most recent adjoint launch)
+    HIP_TRY(launch_rollout_backprop(h->rollJ_plant, (int)T, h->batch, d_J, d_gu, d_gt, d_g0, d_gw, h->stream));
+    HIP_TRY(hipEventRecord(h->ev_a1, h->stream));
+    h->adjoint_timed = true;
+    if (device) return EICOS_OK;
+    HIP_TRY(hipMemcpyAsync(grad_theta0, d_g0, n_g0 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_w) HIP_TRY(hipMemcpyAsync(grad_w, d_gw, n_gw * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return EICOS_OK;
+}
+int eicos_batch_rollout_jacobian_steps(eicos_batch *h) { return h ? h->rollJ_steps : fail(EICOS_E_INVALID, "NULL handle"); }
+int eicos_batch_rollout_gradient(eicos_batch *h, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w) {
+    return rollout_gradient(h, gu, gtheta, grad_theta0, grad_w, false, "eicos_batch_rollout_gradient");
+}
+int eicos_batch_rollout_gradient_device(eicos_batch *h, const double *dgu, const double *dgtheta, double *dgrad_theta0, double *dgrad_w) {
+    return rollout_gradient(h, dgu, dgtheta, dgrad_theta0, dgrad_w, true, "eicos_batch_rollout_gradient_device");
 }
 
 int eicos_batch_solution(eicos_batch *h, double *x) {

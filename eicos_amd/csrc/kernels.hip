@@ -3520,23 +3520,32 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_par
     if (g_S.mmap) matrix_param_instance<T>(ps, I, 0, g_S.pmap, g_S.mmap, row);
     else param_instance<T>(ps, I, 0, g_S.pmap, row);
 }
+// (the two halves of a step, shared with k_roll_sens, which runs adjoint_instance between them: rollout_sens_step, below)
 template <int T>
-static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_step(int ps, gcdbl_p I, int id) {
-    ps = uni(ps); I = uni_ptr(I); id = uni(id);
-    const RolloutDev *Rp = uni_ptr(g_S.roll);
-    const int t = g_S.step, steps = Rp->steps;
+__device__ __forceinline__ void rollout_record(int ps, gcdbl_p I, const RolloutDev *Rp, int id, int t, int steps) {
     const size_t at = (size_t)id * steps + t;
     outputs_instance<T>(ps, I, 0, g_S.omap, Rp->u + at * Rp->plant.r);
     if (threadIdx.x == 0) {
         const DevInfo EICOS_DATA *di = reinterpret_cast<const DevInfo EICOS_DATA *>(I + c_pat[ps].i_info);
         Rp->codes[at] = di->exitcode; Rp->iters[at] = di->iter;
     }
+}
+template <int T>
+__device__ __forceinline__ void rollout_advance(const RolloutDev *Rp, int id, int t, int steps) {
     plant_instance<T>(Rp, id, t); // (ends with a barrier: every thread has read the step)
     if (threadIdx.x == 0) {
         const bool last = t + 1 >= steps;
         g_S.step = last ? 0 : t + 1;
         if (last) g_S.next = (int)gridDim.x + atomicAdd(g_S.queue, 1); // (k_solve's queue pull; otherwise g_S.next stays: the same instance again)
     }
+}
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_step(int ps, gcdbl_p I, int id) {
+    ps = uni(ps); I = uni_ptr(I); id = uni(id);
+    const RolloutDev *Rp = uni_ptr(g_S.roll);
+    const int t = g_S.step, steps = Rp->steps;
+    rollout_record<T>(ps, I, Rp, id, t, steps);
+    rollout_advance<T>(Rp, id, t, steps);
 }
 
 // Between the attempts of an instance under a retry policy (k_solve with UpdArgs::retry, behind solve_instance and its barrier; the
@@ -3714,6 +3723,26 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void adjoint_ins
     __syncthreads();
 }
 
+// One step of a rollout that records its Jacobians (k_roll_sens; g_S.step = the step that is running), behind the solve and its barrier:
+// rollout_step with adjoint_instance between its halves, while the iterate of step t is still in place.  The record's J and res are the
+// [batch][steps][r][k] and [batch][steps][r] trajectories, so row id * steps + t of adjoint_instance's arrays is the step's.
+// What adjoint_instance leaves behind and why the next step cannot read it: the scalars of g_S it sets (wi / bi, fl, cur, best, done,
+// kref, tick) are all set again by instance_begin's thread 0 from the slab's record before anything reads them; dots, sv, red and
+// kref2 are written before they are read by every solve, as between two instances of k_solve; the scaling block i_Vv is reset by
+// instance_begin; of the workspace it writes what a solve writes (Kt / Kimg, the right-hand sides, buffer set 1 of the iterate, the
+// factor and the sweep vectors), which instance_begin or the first stage that reads them fills again -- a warm start and the shift map
+// read buffer set 0, the slab's result rows, which adjoint_instance only reads.  cfg, dyn_delta and dyn_eps are the launch's again
+// (k_roll_sens brings them back behind the retry loop, in front of this call): the Jacobian runs under the handle's settings.
+template <int T, int NLDS, bool I16>
+static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_sens_step(int ps, gdbl_p I, gdbl_p W, int id, const AdjointDev *Ap) {
+    ps = uni(ps); I = uni_ptr(I); W = uni_ptr(W); id = uni(id); Ap = uni_ptr(Ap);
+    const RolloutDev *Rp = uni_ptr(g_S.roll);
+    const int t = uni(g_S.step), steps = Rp->steps;
+    rollout_record<T>(ps, I, Rp, id, t, steps);
+    adjoint_instance<T, NLDS, I16>(ps, I, W, Ap, id * steps + t); // (begins and ends with a barrier; batch * steps fits an int: api.cpp)
+    rollout_advance<T>(Rp, id, t, steps);
+}
+
 template <int T, int NLDS, bool I16>
 __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
     int ps, double *inst, double *work, int B, int *queue, const int *order, double warm, double dyn_delta, double dyn_eps, SolveCfg cfg, UpdArgs upd) {
@@ -3867,6 +3896,83 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_adjoint(
         if (threadIdx.x == 0) { g_S.vals = inst + (size_t)id * P.inst_stride; g_S.vshared = 0; } // (the instance's own product values: the same bits as a shared copy)
 #endif
         adjoint_instance<T, NLDS, I16>(ps, I, W, adj, q);
+    }
+}
+// The rollout that also records its Jacobians (launch.hpp: SolveBuild::roll_sens; eicos_batch_rollout_jacobian): k_solve's workgroup
+// set-up and queue loop restricted to UPD_ROLL (nothing is staged, no x / u rows of a single step), with rollout_sens_step in the place
+// of rollout_step -- per step rollout_param, the solve with its retry, the u row and the records, adjoint_instance in its contracted form
+// into rows [id][t] of the J and res trajectories, the plant map, the step counter and the queue pull.  A kernel of its own, as
+// k_adjoint is, so that no k_solve or k_adjoint instantiation changes by a register or a byte; NLDS >= 1 only, as every fused step.
+// The LDS-resident build writes the slabs back BEFORE the adjoint: HBM then holds what the step's solve left, the scaling block
+// included, as after a k_solve launch followed by a k_adjoint launch (which writes nothing back in that build).
+template <int T, int NLDS, bool I16>
+__global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_roll_sens(
+    int ps, double *inst, double *work, int B, int *queue, const int *order, double warm, double dyn_delta, double dyn_eps, SolveCfg cfg, UpdArgs upd,
+    const AdjointDev *adj) {
+    static_assert(NLDS >= 1, "a fused step keeps its vectors in the LDS sweep vector");
+    const DevPat &P = c_pat[ps];
+#if EICOS_LDSRES
+    gdbl_p W = (gdbl_p)(g_dyn + P.lr_work), Il = (gdbl_p)(g_dyn + P.lr_inst);
+    double *Wglob = work + (size_t)blockIdx.x * P.work_stride;
+    for (int q = threadIdx.x; q < (int)P.work_stride; q += T) W[q] = Wglob[q];
+#else
+    gdbl_p W = (gdbl_p)work + (size_t)blockIdx.x * P.work_stride;
+#endif
+    {
+        if (threadIdx.x == 0) { g_S.rows_at = 0; g_S.queue = queue; }
+        int *dst = reinterpret_cast<int *>(g_dyn + P.lds_tab);
+        auto stage = [&](const PackedSlice EICOS_GLOBAL *src, int cnt, int at) {
+            gint_p si = reinterpret_cast<gint_p>(src);
+            for (int q = threadIdx.x; q < cnt * 4; q += T) dst[at * 4 + q] = si[q];
+        };
+        stage(P.fsl, P.nfs + P.nfs_solo + P.nfs_ext, P.lm_f); stage(P.bsl, P.nbs + P.nbs_solo, P.lm_b); stage(P.cag_sl, P.cag_ns, P.lm_cag);
+        stage(P.rA_sl, P.rA_ns, P.lm_rA); stage(P.rG_sl, P.rG_ns, P.lm_rG);
+        if (P.lm_fac >= 0) stage(P.fac_sl, P.fac_ns, P.lm_fac);
+        __syncthreads();
+    }
+#if EICOS_UBL
+    for (int q = threadIdx.x; q < P.ub_len; q += T) g_dyn[P.ub_lds + q] = 0.;
+    __syncthreads();
+#endif
+    if (threadIdx.x == 0) {
+        g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.cfg = cfg; g_S.step = 0; g_S.next = (int)blockIdx.x; g_S.smap = upd.smap; g_S.attempt = 0; g_S.swapped = 0;
+        g_S.roll = upd.roll; g_S.pmap = upd.pmap; g_S.omap = upd.omap; g_S.mmap = upd.mmap;
+    }
+    for (int g = blockIdx.x; g < B;) {
+        const int id = uni(order ? order[g] : g);
+        rollout_param<T>(ps, (hbm_p)inst + (size_t)id * P.inst_stride, id);
+#if EICOS_LDSRES
+        gdbl_p I = Il;
+        {
+            const double *Ig = inst + (size_t)id * P.inst_stride;
+            __syncthreads();
+            for (int q = threadIdx.x; q < (int)P.inst_stride; q += T) Il[q] = Ig[q];
+            __syncthreads();
+        }
+#else
+        gdbl_p I = (gdbl_p)inst + (size_t)id * P.inst_stride;
+        if (threadIdx.x == 0) {
+            const int ref = upd.shared ? *upd.shared : -1;
+            g_S.vals = inst + (size_t)(ref >= 0 ? ref : id) * P.inst_stride;
+            g_S.vshared = ref >= 0;
+        }
+#endif
+        for (double wshift = warm;; wshift = g_S.rwarm) {
+            solve_instance<T, NLDS, I16>(ps, I, W, wshift);
+            __syncthreads();
+            if (!upd.retry || !retry_between(upd.retry, id)) break;
+        }
+        if (upd.retry) { if (threadIdx.x == 0 && g_S.swapped) { g_S.cfg = cfg; g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.swapped = 0; } }
+#if EICOS_LDSRES
+        {
+            double *Ig = inst + (size_t)id * P.inst_stride;
+            for (int q = threadIdx.x; q < (int)P.inst_stride; q += T) Ig[q] = Il[q];
+            for (int q = threadIdx.x; q < (int)P.work_stride; q += T) Wglob[q] = W[q];
+        }
+#endif
+        rollout_sens_step<T, NLDS, I16>(ps, I, W, id, adj); // (the adjoint's first barrier stands between the policy's settings going back and their first read)
+        __syncthreads();
+        g = g_S.next;
     }
 }
 
@@ -4259,6 +4365,52 @@ __global__ __launch_bounds__(T) void k_plant_range(int ps, const double *inst, i
 
 // Row gather (launch.hpp: launch_gather_rows): row q of dst = the wanted groups of instance list[q], back to back -- x, y, z, s as they
 // stand in the slab and the info record, each copied as doubles with plain loads and stores.  grid: x over a row's entries, y over the rows.
+// The backward sweep of a rollout that recorded its Jacobians (launch.hpp: launch_rollout_backprop; eicos_batch_rollout_gradient): the
+// gradient of L = sum_t gu_t' u_t + sum_t gth_t' theta_t with respect to theta_0 (and to the disturbances w_t) by the chain rule through
+// theta_{t+1} = f0 + F [theta_t | u_t] + w_t, u_t = u(theta_t) with the recorded J_t = d u_t / d theta_t.  One small workgroup per
+// instance; lambda, mu and v = F' lambda in LDS: [lam (k) | lam' (k) | v (k + r) | mu (r)].  The order is fixed and every product and
+// sum is rounded on its own; a missing cotangent array counts as 0.0 and is still added:
+//   lam = gth[T];  for t = T-1 .. 0:  grad_w[t] = lam;  v[c] = 0.0, then v[c] + (val[s] * lam[i]) over the rows i ascending and their
+//   stored entries s with col[s] == c;  mu[j] = gu[t][j] + v[k + j];  lam'[c] = gth[t][c] + v[c], then + (J[t][j][c] * mu[j]) for
+//   j ascending;  lam = lam'.   grad_theta0 = lam.
+// Thread c walks the whole map for its column: the map has at most k (k + r) entries, and T steps of it are a few microseconds.
+template <int T>
+__global__ __launch_bounds__(T) void k_rollout_backprop(PlantMapDev M, int steps, int batch, const double *J, const double *gu, const double *gth,
+                                                        double *grad0, double *gradw) {
+    const int k = M.k, r = M.r;
+    const AffineDev A = M.a;
+    double *lam = g_dyn, *lam2 = lam + k, *v = lam2 + k, *mu = v + k + r;
+    for (int b = blockIdx.x; b < batch; b += (int)gridDim.x) {
+        const size_t bt = (size_t)b * steps;
+        __syncthreads(); // (the instance before: its last reads of lam)
+        FOR_T(c, k) lam[c] = gth ? gth[(bt + b + steps) * k + c] : 0.;
+        __syncthreads();
+        for (int t = steps - 1; t >= 0; t--) {
+            if (gradw) { FOR_T(c, k) gradw[(bt + t) * k + c] = lam[c]; }
+            FOR_T(c, k + r) {
+                double acc = 0.;
+                for (int i = 0; i < k; i++)
+                    for (int s = A.rowptr[i]; s < A.rowptr[i + 1]; s++)
+                        if (A.col[s] == c) acc = __dadd_rn(acc, __dmul_rn(A.val[s], lam[i]));
+                v[c] = acc;
+            }
+            __syncthreads();
+            FOR_T(j, r) mu[j] = __dadd_rn(gu ? gu[(bt + t) * r + j] : 0., v[k + j]);
+            __syncthreads();
+            FOR_T(c, k) {
+                double acc = __dadd_rn(gth ? gth[(bt + b + t) * k + c] : 0., v[c]);
+                const double *Jt = J + (bt + t) * r * k;
+                for (int j = 0; j < r; j++) acc = __dadd_rn(acc, __dmul_rn(Jt[(size_t)j * k + c], mu[j]));
+                lam2[c] = acc;
+            }
+            __syncthreads();
+            FOR_T(c, k) lam[c] = lam2[c];
+            __syncthreads();
+        }
+        FOR_T(c, k) grad0[(size_t)b * k + c] = lam[c];
+    }
+}
+
 template <int T>
 __global__ __launch_bounds__(T) void k_gather_rows(int ps, const double *inst, const int *list, int count, int want, double *dst) {
     const DevPat &P = c_pat[ps];
@@ -4351,9 +4503,21 @@ template <class F> static auto dispatch_solve(int nlds, int idx16, F &&f) {
     };
     return idx16 ? byI(std::true_type{}) : byI(std::false_type{});
 }
-static hipError_t launch_solve(const SolveLaunch &launch, hipStream_t st, const UpdArgs &step) {
+// the k_roll_sens instantiation that matches a handle's k_solve (NLDS >= 1: there is none without an LDS vector)
+template <class F> static hipError_t dispatch_roll_sens(int nlds, int idx16, F &&f) {
+    auto byI = [&](auto ic) -> hipError_t {
+        constexpr bool I16 = decltype(ic)::value;
+        if (nlds >= 2) return f((const void *)k_roll_sens<SOLVE_T, 2, I16>);
+        if (nlds == 1) return f((const void *)k_roll_sens<SOLVE_T, 1, I16>);
+        return hipErrorInvalidValue;
+    };
+    return idx16 ? byI(std::true_type{}) : byI(std::false_type{});
+}
+// One launch of k_solve, or -- adj != NULL: SolveBuild::roll_sens -- of k_roll_sens with the same queue, order and shape
+static hipError_t launch_solve_as(const SolveLaunch &launch, hipStream_t st, const UpdArgs &step, const AdjointDev *adj) {
     // (copies: hipLaunchKernel takes non-const pointers; cfg travels by value, so a launch in flight keeps the settings it was enqueued with)
     SolveLaunch L = launch; UpdArgs upd = step;
+    if (adj && (upd.on != UPD_ROLL || !upd.roll || L.list)) return hipErrorInvalidValue; // (the whole batch, a rollout)
     if ((upd.rows_at != 0) != (L.rows != nullptr) || (L.rows && (!L.list || upd.on != UPD_PARAM || L.rows != L.queue + upd.rows_at))) return hipErrorInvalidValue; // (a step in list order reads the row map THIS launch's selection kernel writes)
     if (upd.on && L.nlds < 1) return hipErrorInvalidValue; // (the fused updateData keeps its maxima in the LDS sweep vector; both modes live in the NLDS >= 1 kernels)
     if (L.B <= 0) return hipSuccess;
@@ -4374,10 +4538,18 @@ static hipError_t launch_solve(const SolveLaunch &launch, hipStream_t st, const 
         hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, st, L.ps, L.inst, L.B, L.order, (snake_on && L.B <= L.grid) ? L.B : 0, L.order_min);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
+    if (adj) return dispatch_roll_sens(L.nlds, L.idx16, [&](const void *fn) {
+        void *args[] = {&L.ps, &L.inst, &L.work, &L.B, &L.queue, &L.order, &L.warm, &L.dyn_delta, &L.dyn_eps, &L.cfg, &upd, &adj};
+        return hipLaunchKernel(fn, dim3(L.grid), dim3(L.threads), args, L.dyn_lds, st);
+    });
     return dispatch_solve(L.nlds, L.idx16, [&](const void *fn) {
         void *args[] = {&L.ps, &L.inst, &L.work, &L.B, &L.queue, &L.order, &L.warm, &L.dyn_delta, &L.dyn_eps, &L.cfg, &upd};
         return hipLaunchKernel(fn, dim3(L.grid), dim3(L.threads), args, L.dyn_lds, st);
     });
+}
+static hipError_t launch_solve(const SolveLaunch &launch, hipStream_t st, const UpdArgs &step) { return launch_solve_as(launch, st, step, nullptr); }
+static hipError_t launch_roll_sens(const SolveLaunch &launch, hipStream_t st, const UpdArgs &step, const AdjointDev *adj) {
+    return adj ? launch_solve_as(launch, st, step, adj) : hipErrorInvalidValue;
 }
 // the k_adjoint instantiation that matches a handle's k_solve, with the same launch shape (launch.hpp: AdjointLaunch)
 template <class F> static auto dispatch_adjoint(int nlds, int idx16, F &&f) {
@@ -4482,6 +4654,15 @@ hipError_t launch_gather_rows(int ps, const double *inst, const int *list, int c
     hipLaunchKernelGGL(k_gather_rows<T>, dim3((unsigned)gx, (unsigned)(gy < 16384 ? gy : 16384)), dim3(T), 0, st, ps, inst, list, count, want, dst);
     return hipGetLastError();
 }
+hipError_t launch_rollout_backprop(const PlantMapDev &plant, int steps, int batch, const double *J, const double *gu, const double *gtheta,
+                                   double *grad_theta0, double *grad_w, hipStream_t st) {
+    if (batch <= 0) return hipSuccess;
+    constexpr int T = 64;
+    const size_t lds = rollout_backprop_lds(plant.k, plant.r);
+    if (steps < 1 || !J || !grad_theta0 || lds > 48 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rollout_backprop<T>, dim3((unsigned)(batch < 16384 ? batch : 16384)), dim3(T), lds, st, plant, steps, batch, J, gu, gtheta, grad_theta0, grad_w);
+    return hipGetLastError();
+}
 // the dynamic-LDS ceiling of the two entry-parallel updateData kernels, set once per handle on the handle's device
 hipError_t update_set_max_lds() {
     hipError_t e = hipFuncSetAttribute((const void *)k_update_lds<512, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
@@ -4526,7 +4707,11 @@ static hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn
         return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
     });
     if (e != hipSuccess) return e;
-    return dispatch_adjoint(nlds, idx16, [&](const void *fn) { // (the adjoint kernel of the same instantiation takes the same launch shape)
+    const hipError_t ea = dispatch_adjoint(nlds, idx16, [&](const void *fn) { // (the adjoint kernel of the same instantiation takes the same launch shape)
+        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
+    });
+    if (ea != hipSuccess || nlds < 1) return ea;
+    return dispatch_roll_sens(nlds, idx16, [&](const void *fn) { // (and so does the rollout that records its Jacobians)
         return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
     });
 }
@@ -4535,7 +4720,7 @@ static hipError_t upload_pattern(int ps, const DevPat &P) {
     if (ps < 0 || ps >= MAX_PATTERNS) return hipErrorInvalidValue;
     return hipMemcpyToSymbol(HIP_SYMBOL(c_pat), &P, sizeof(DevPat), (size_t)ps * sizeof(DevPat), hipMemcpyHostToDevice);
 }
-SolveBuild solve_entries() { return {launch_solve, solve_occupancy, solve_set_max_lds, upload_pattern, launch_adjoint}; } // (launch.hpp: one per build namespace)
+SolveBuild solve_entries() { return {launch_solve, solve_occupancy, solve_set_max_lds, upload_pattern, launch_adjoint, launch_roll_sens}; } // (launch.hpp: one per build namespace)
 #endif // EICOS_ISA_PROBE
 #if EICOS_LDSRES
 } // namespace ldsres

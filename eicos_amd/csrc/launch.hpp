@@ -117,13 +117,17 @@ struct AdjointLaunch {
     int grid, threads, nlds, idx16; double dyn_delta, dyn_eps; SolveCfg cfg; size_t dyn_lds;
     const AdjointDev *adj;
 };
-// One k_solve build = these five entry points.  launch always receives an UpdArgs: UpdArgs{} when no step is fused into it.
+// One k_solve build = these six entry points.  launch always receives an UpdArgs: UpdArgs{} when no step is fused into it.
 struct SolveBuild {
     hipError_t (*launch)(const SolveLaunch &L, hipStream_t st, const UpdArgs &upd);
     hipError_t (*occupancy)(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
     hipError_t (*set_max_lds)(int threads, int nlds, int idx16, size_t dyn_lds);
     hipError_t (*upload)(int ps, const DevPat &P);
     hipError_t (*adjoint)(const AdjointLaunch &L, hipStream_t st);
+    // the rollout that also records its Jacobians (eicos_batch_rollout_jacobian; kernels.hip: k_roll_sens): `launch` with upd.on = UPD_ROLL over
+    // the whole batch, every step followed by the contracted adjoint of *adj (device memory: J [batch][steps][r][k], res [batch][steps][r]
+    // or NULL, g == NULL) while the step's iterate is in place.  Kernels with an LDS vector only (L.nlds >= 1), as every fused step.
+    hipError_t (*roll_sens)(const SolveLaunch &L, hipStream_t st, const UpdArgs &upd, const AdjointDev *adj);
     bool operator==(const SolveBuild &o) const { return launch == o.launch; }
 };
 // The range launchers below (updateData in its four kinds and the output map) take an optional `list`: `count` ids of distinct instances
@@ -169,6 +173,13 @@ hipError_t launch_outputs(int ps, const double *inst, int first, int count, cons
 // and iteration count to its records (roll: the trajectories of the whole batch, host copy of the launch's RolloutDev)
 hipError_t launch_plant(int ps, const double *inst, int first, int count, const RolloutDev &roll, int t, const double *theta_cur,
                         const double *u_cur, double *theta_next, hipStream_t st);
+// The backward sweep over a recorded rollout (eicos_batch_rollout_gradient; kernels.hip: k_rollout_backprop): J [batch][steps][r][k] as the
+// rollout left it, gu [batch][steps][r] and gtheta [batch][steps + 1][k] (either NULL = 0.0) in, grad_theta0 [batch][k] and grad_w
+// [batch][steps][k] (NULL = not wanted) out, all in device memory; the map by value.  One 64-thread workgroup per instance with
+// rollout_backprop_lds bytes of LDS (at most 48 KB: the caller checks).
+inline size_t rollout_backprop_lds(int k, int r) { return ((size_t)3 * k + 2 * (size_t)r) * sizeof(double); }
+hipError_t launch_rollout_backprop(const PlantMapDev &plant, int steps, int batch, const double *J, const double *gu, const double *gtheta,
+                                   double *grad_theta0, double *grad_w, hipStream_t st);
 // Selection (eicos_batch_select, _solve_where): the instances of 0 .. batch-1 whose exit class (exit_class.hpp) is in `mask`, compacted
 // in ascending order into cand [batch], their number into *count (both device memory).  The kernel is the one that orders a subset launch
 // (kernels.hip: k_select_order), run without an order array.

@@ -595,6 +595,35 @@ int eicos_multi_rollout(eicos_multi *mh, int steps, const double *theta0, const 
     });
 }
 
+// the rollout that records its Jacobians, and the gradient over it: rows by shard, as eicos_multi_rollout's
+int eicos_multi_rollout_jacobian(eicos_multi *mh, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
+                                 int *exitcodes, int *iters, double *J_traj, double *res_traj) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    if (steps < 1) return mfail(EICOS_E_INVALID, "rollout: steps must be at least 1");
+    if (!J_traj) return mfail(EICOS_E_INVALID, "rollout_jacobian: J_traj is NULL");
+    const size_t k = (size_t)eicos_batch_param_count(mh->shard[0]), ro = (size_t)eicos_batch_output_count(mh->shard[0]), T = (size_t)steps;
+    return for_shards(mh, [&](int s) {
+        const size_t f = (size_t)mh->first[s];
+        return eicos_batch_rollout_jacobian(mh->shard[s], steps, at(theta0, f, k), at(w, f, T * k), at(u_traj, f, T * ro), at(theta_traj, f, (T + 1) * k),
+                                            at(exitcodes, f, T), at(iters, f, T), at(J_traj, f, T * ro * k), at(res_traj, f, T * ro));
+    });
+}
+// (T = the step count of the trajectory the shards hold: every shard ran the same eicos_multi_rollout_jacobian)
+int eicos_multi_rollout_gradient(eicos_multi *mh, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    if (!gu && !gtheta) return mfail(EICOS_E_INVALID, "rollout_gradient: gu and gtheta are both NULL");
+    if (!grad_theta0) return mfail(EICOS_E_INVALID, "rollout_gradient: grad_theta0 is NULL");
+    const int steps = eicos_batch_rollout_jacobian_steps(mh->shard[0]);
+    for (int s = 0; s < (int)mh->shard.size(); s++)
+        if (steps < 1 || eicos_batch_rollout_jacobian_steps(mh->shard[s]) != steps)
+            return mfail(EICOS_E_INVALID, "rollout_gradient: shard " + std::to_string(s) + " holds no Jacobian trajectory, or one of another length (eicos_multi_rollout_jacobian records one)");
+    const size_t k = (size_t)eicos_batch_param_count(mh->shard[0]), ro = (size_t)eicos_batch_output_count(mh->shard[0]), T = (size_t)steps;
+    return for_shards(mh, [&](int s) {
+        const size_t f = (size_t)mh->first[s];
+        return eicos_batch_rollout_gradient(mh->shard[s], at(gu, f, T * ro), at(gtheta, f, (T + 1) * k), at(grad_theta0, f, k), at(grad_w, f, T * k));
+    });
+}
+
 int eicos_multi_solution(eicos_multi *mh, double *x) {
     if (!mh || !x) return mfail(EICOS_E_INVALID, "NULL argument");
     if (mh->n == 0) return EICOS_OK;

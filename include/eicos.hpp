@@ -471,6 +471,23 @@ namespace EiCOS
             if (indices.empty()) return;
             mcheck(eicos_multi_param_gradient(h_, indices.data(), (int)indices.size(), nrhs, g, grad_theta, res), "eicos_multi_param_gradient");
         }
+        // Extension: rollout() that also records J_traj [batch][steps][r][k] = d u_t / d theta_t of every step (and, optionally, the
+        // refinement residuals res_traj [batch][steps][r]) -- what paramJacobian returns right after step t's solve, bit for bit, still
+        // in one launch per shard.  rolloutGradient then gives the gradient of L = sum_t gu_t' u_t + sum_t gtheta_t' theta_t over that
+        // rollout with respect to theta_0 (grad_theta0 [batch][k]) and, optionally, to the disturbances (grad_w [batch][steps][k]); gu
+        // [batch][steps][r] and gtheta [batch][steps + 1][k] are each optional, one must be given.  A step that did not end optimal has
+        // NaN rows, and the gradient of that instance is NaN (definition, order and caveats: eicos_batch_rollout_jacobian of eicos_amd.h).
+        std::vector<exitcode> rolloutJacobian(int steps, const double *theta0, double *u_traj, double *J_traj, const double *w = nullptr,
+                                              double *theta_traj = nullptr, int *iters = nullptr, double *res_traj = nullptr)
+        {
+            std::vector<int> codes((size_t)batch_ * (steps > 0 ? steps : 0));
+            mcheck(eicos_multi_rollout_jacobian(h_, steps, theta0, w, u_traj, theta_traj, codes.data(), iters, J_traj, res_traj), "eicos_multi_rollout_jacobian");
+            return exitcodes(codes);
+        }
+        void rolloutGradient(const double *gu, const double *gtheta, double *grad_theta0, double *grad_w = nullptr)
+        {
+            mcheck(eicos_multi_rollout_gradient(h_, gu, gtheta, grad_theta0, grad_w), "eicos_multi_rollout_gradient");
+        }
         void solveAsync() { mcheck(eicos_multi_solve_async(h_), "eicos_multi_solve_async"); } // enqueue on every shard's stream
         void sync() { mcheck(eicos_multi_sync(h_), "eicos_multi_sync"); }
         std::vector<double> solution() const

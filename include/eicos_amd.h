@@ -460,6 +460,51 @@ int eicos_batch_param_jacobian_device(eicos_batch *hd, const int *idx, int count
 int eicos_batch_param_gradient(eicos_batch *hd, const int *idx, int count, int nrhs, const double *g, double *grad_theta, double *res);
 int eicos_batch_param_gradient_device(eicos_batch *hd, const int *idx, int count, int nrhs, const double *dg, double *dgrad_theta,
                                       double *dres);
+/* ---- rollout sensitivities: the Jacobian of every step of a rollout, and the gradient of a closed-loop cost (no reference counterpart).
+ * eicos_batch_rollout_jacobian: eicos_batch_rollout -- the first eight arguments with exactly its meaning, arrays in pageable, pinned or
+ * device memory -- that also records J_traj [batch][steps][r][k] (required) and res_traj [batch][steps][r] (optional): J_traj[i][t] and
+ * res_traj[i][t] are what eicos_batch_param_jacobian returns for instance i when it is called right after step t's solve -- under the
+ * handle's linsysacc, irerrfact, nitref and dynamic regularisation, through whichever of the parameter map and the matrix map are
+ * installed, at the iterate the step ended with (after the second attempt, if a retry policy took one).  The rows of a step that did not
+ * end OPTIMAL / OPTIMAL_INACC are NaN, and the loop goes on.
+ * Defined by its HOST TWIN, bit for bit:  for t = 0 .. steps-1:  eicos_batch_update_param_solve(theta_t);  eicos_batch_param_jacobian;
+ * the plant map on the host.  Every returned array equals the twin's, and so does the handle afterwards: slabs, solution, duals, info,
+ * retry counts, eicos_debug_kkt.  u_traj, theta_traj, exitcodes, iters and x, y, z, s, info also equal those of plain
+ * eicos_batch_rollout; only the scaling block eicos_debug_kkt shows follows the adjoint, as documented for eicos_batch_adjoint.
+ * FUSED under the conditions of the fused rollout (eicos_batch_last_rollout_launches = 1): one launch of the rollout twin of the solve
+ * kernel, whose workgroups run the adjoint of a step while its iterate is still in place, between the step's records and its plant map.
+ * Otherwise the per-step enqueue of eicos_batch_rollout with one adjoint launch (the contracted device form) between the output and the
+ * plant kernels, no host synchronisation between steps; eicos_batch_last_rollout_launches = steps.  Same bits on either path.
+ * The handle keeps the device copy of the J trajectory of its most recent rollout_jacobian for:
+ * eicos_batch_rollout_gradient / _device: the gradient of  L = sum_t gu_t' u_t + sum_t gtheta_t' theta_t  over that rollout (T = its step
+ * count) with respect to theta_0 and, optionally, to the disturbances.  gu [batch][T][r] = dL/du_t and gtheta [batch][T+1][k] = dL/dtheta_t:
+ * each optional, at least one given; grad_theta0 [batch][k]; grad_w [batch][T][k], optional.  One small workgroup per instance sweeps
+ * backward through  dtheta_{t+1}/dtheta_t = F_theta + F_u J_t  (F = [F_theta | F_u] the plant map).  The order is fixed, every product
+ * and sum is rounded on its own (no FMA), a missing cotangent array counts as 0.0 and is still added:
+ *
+ *     lambda = gtheta[T]
+ *     for t = T-1 .. 0:
+ *         grad_w[t] = lambda
+ *         v[c] = 0.0;  for i = 0..k-1, s in rowptr[i]..rowptr[i+1]-1 (stored order), col[s] == c:  v[c] = v[c] + (val[s] * lambda[i])     (c in [0, k + r))
+ *         mu[j] = gu[t][j] + v[k + j]
+ *         lambda'[c] = gtheta[t][c] + v[c];  for j = 0..r-1:  lambda'[c] = lambda'[c] + (J[t][j][c] * mu[j])
+ *         lambda = lambda'
+ *     grad_theta0 = lambda
+ *
+ * A NaN Jacobian row (a step that did not end OPTIMAL / OPTIMAL_INACC) makes that instance's gradient NaN.  The host form is synchronous;
+ * the device form takes all four arrays in device memory, is asynchronous on the handle's stream and returns the same bits.
+ * Caveats, beside the one of the definition above (a degenerate optimum gives a smoothed value): with a warm start or a shift map the
+ * point step t + 1 returns depends on step t's iterate within the exit tolerance -- the gradient treats each step's solution as a
+ * function of theta_t alone; gradients with respect to the maps' own entries are out of scope.
+ * Refusals (EICOS_E_INVALID with a message, nothing changed): rollout_jacobian -- everything eicos_batch_rollout refuses, a NULL J_traj,
+ * a matrix map that does not fit the parameter map; rollout_gradient -- no J trajectory on the handle, a parameter, matrix, output or
+ * plant map installed since that rollout, both cotangents NULL, a NULL grad_theta0, host and device pointers mixed (as
+ * eicos_batch_param_gradient refuses them). */
+int eicos_batch_rollout_jacobian(eicos_batch *hd, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
+                                 int *exitcodes, int *iters, double *J_traj, double *res_traj);
+int eicos_batch_rollout_jacobian_steps(eicos_batch *hd); /* T of the J trajectory the handle holds; 0: none */
+int eicos_batch_rollout_gradient(eicos_batch *hd, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w);
+int eicos_batch_rollout_gradient_device(eicos_batch *hd, const double *dgu, const double *dgtheta, double *dgrad_theta0, double *dgrad_w);
 /* eicos_batch_update_param_solve_subset: the closed-loop step over a subset = eicos_batch_update_param_indexed + eicos_batch_solve_subset
  * + eicos_batch_outputs_indexed (+ the x rows), every array in list order; synchronous.
  * Fused under exactly the conditions of eicos_batch_update_param_solve (an LDS vector, a theta row that fits it, GPU-addressable theta,
@@ -730,6 +775,11 @@ int eicos_multi_set_plant_map(eicos_multi *mh, const eicos_affine_map *f);
 int eicos_multi_has_plant_map(eicos_multi *mh);
 int eicos_multi_rollout(eicos_multi *mh, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
                         int *exitcodes, int *iters);
+/* eicos_batch_rollout_jacobian / _gradient per shard on its rows, the shards concurrently (T of the gradient = the step count of the
+ * rollout_jacobian every shard ran last) */
+int eicos_multi_rollout_jacobian(eicos_multi *mh, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
+                                 int *exitcodes, int *iters, double *J_traj, double *res_traj);
+int eicos_multi_rollout_gradient(eicos_multi *mh, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w);
 /* matrix map (eicos_batch_set_matrix_map / _has_matrix_map on every shard): installed on every shard; the theta-consuming calls above pick
  * it up shard by shard */
 int eicos_multi_set_matrix_map(eicos_multi *mh, const eicos_affine_map *G, const eicos_affine_map *A);
