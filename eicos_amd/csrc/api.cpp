@@ -1276,9 +1276,7 @@ static int enqueue_solve(eicos_batch *h, const UpdArgs *step, int subset = -1, c
     args.shared = h->shared_on ? h->d_shared.as<int>() : nullptr;
     SolveLaunch L = solve_launch(h, subset);
     if (args.rows_at) L.rows = h->queue() + args.rows_at; // (a step in list order: the selection kernel of this launch fills the row map it reads)
-    const SolveBuild build = solve_build(h->threads, h->ldsres, h->w2, h->ubl);
-    if (sens) HIP_TRY(build.roll_sens(L, h->stream, args, sens));
-    else HIP_TRY(build.launch(L, h->stream, args));
+    HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).launch(L, h->stream, args, sens));
     HIP_TRY(hipEventRecord(h->ev_s1, h->stream));
     h->solve_timed = true;
     h->last_subset = subset >= 0; h->last_count = subset >= 0 ? subset : h->batch;

@@ -3898,7 +3898,8 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_adjoint(
         adjoint_instance<T, NLDS, I16>(ps, I, W, adj, q);
     }
 }
-// The rollout that also records its Jacobians (launch.hpp: SolveBuild::roll_sens; eicos_batch_rollout_jacobian): k_solve's workgroup
+// The rollout that also records its Jacobians (launch.hpp: SolveBuild::launch with an adjoint record; eicos_batch_rollout_jacobian):
+// k_solve's workgroup
 // set-up and queue loop restricted to UPD_ROLL (nothing is staged, no x / u rows of a single step), with rollout_sens_step in the place
 // of rollout_step -- per step rollout_param, the solve with its retry, the u row and the records, adjoint_instance in its contracted form
 // into rows [id][t] of the J and res trajectories, the plant map, the step counter and the queue pull.  A kernel of its own, as
@@ -4494,27 +4495,26 @@ __global__ __launch_bounds__(T, waves_per_eu<T>()) void k_debug_scalings(int ps,
 // The k_solve instantiations of this translation unit: ONE workgroup size (the LDS-resident build 128, kernels_t128.o / _t512.o / _ubl*.o theirs,
 // kernels.o / kernels_w2.o 256), 16- or 32-bit indices, and two, one or -- except LDS-resident and U-in-LDS: api.cpp never asks -- no vector in LDS.
 constexpr int SOLVE_T = EICOS_LDSRES ? 128 : EICOS_TSPLIT ? EICOS_TSPLIT : EICOS_UBL ? EICOS_UBL : 256;
-template <class F> static auto dispatch_solve(int nlds, int idx16, F &&f) {
+// The three kernel families take the same instantiation for a handle, and the same launch shape.  NULL: the family has no kernel for
+// that handle -- k_roll_sens alone today; every caller checks, so that a hole in another family is an error and not a launch of NULL.
+enum SolveFamily { FAM_SOLVE, FAM_ADJOINT, FAM_ROLL_SENS };
+template <int NLDS, bool I16> static const void *family_kernel(SolveFamily fam) {
+    if (fam == FAM_SOLVE) return (const void *)k_solve<SOLVE_T, NLDS, I16>;
+    if (fam == FAM_ADJOINT) return (const void *)k_adjoint<SOLVE_T, NLDS, I16>;
+    if constexpr (NLDS >= 1) return (const void *)k_roll_sens<SOLVE_T, NLDS, I16>; else return nullptr; // (solve_kernel never asks)
+}
+static const void *solve_kernel(SolveFamily fam, int nlds, int idx16) {
+    constexpr int NLDS_MIN = (EICOS_LDSRES != 0 || EICOS_UBL != 0) ? 1 : 0; // (the fewest LDS vectors this unit has a kernel for)
+    if (fam == FAM_ROLL_SENS && nlds < 1) return nullptr; // k_roll_sens exists with an LDS vector only: its callers answer hipErrorInvalidValue
     auto byI = [&](auto ic) {
         constexpr bool I16 = decltype(ic)::value;
-        if (nlds >= 2) return f((const void *)k_solve<SOLVE_T, 2, I16>);
-        if constexpr (EICOS_LDSRES != 0 || EICOS_UBL != 0) return f((const void *)k_solve<SOLVE_T, 1, I16>);
-        else return nlds == 1 ? f((const void *)k_solve<SOLVE_T, 1, I16>) : f((const void *)k_solve<SOLVE_T, 0, I16>);
+        if (nlds >= 2) return family_kernel<2, I16>(fam);
+        return nlds == 1 ? family_kernel<1, I16>(fam) : family_kernel<NLDS_MIN, I16>(fam);
     };
     return idx16 ? byI(std::true_type{}) : byI(std::false_type{});
 }
-// the k_roll_sens instantiation that matches a handle's k_solve (NLDS >= 1: there is none without an LDS vector)
-template <class F> static hipError_t dispatch_roll_sens(int nlds, int idx16, F &&f) {
-    auto byI = [&](auto ic) -> hipError_t {
-        constexpr bool I16 = decltype(ic)::value;
-        if (nlds >= 2) return f((const void *)k_roll_sens<SOLVE_T, 2, I16>);
-        if (nlds == 1) return f((const void *)k_roll_sens<SOLVE_T, 1, I16>);
-        return hipErrorInvalidValue;
-    };
-    return idx16 ? byI(std::true_type{}) : byI(std::false_type{});
-}
-// One launch of k_solve, or -- adj != NULL: SolveBuild::roll_sens -- of k_roll_sens with the same queue, order and shape
-static hipError_t launch_solve_as(const SolveLaunch &launch, hipStream_t st, const UpdArgs &step, const AdjointDev *adj) {
+// One launch of k_solve, or -- adj != NULL -- of k_roll_sens with the same queue, order and shape (launch.hpp: SolveBuild::launch)
+static hipError_t launch_solve(const SolveLaunch &launch, hipStream_t st, const UpdArgs &step, const AdjointDev *adj) {
     // (copies: hipLaunchKernel takes non-const pointers; cfg travels by value, so a launch in flight keeps the settings it was enqueued with)
     SolveLaunch L = launch; UpdArgs upd = step;
     if (adj && (upd.on != UPD_ROLL || !upd.roll || L.list)) return hipErrorInvalidValue; // (the whole batch, a rollout)
@@ -4538,37 +4538,20 @@ static hipError_t launch_solve_as(const SolveLaunch &launch, hipStream_t st, con
         hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, st, L.ps, L.inst, L.B, L.order, (snake_on && L.B <= L.grid) ? L.B : 0, L.order_min);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if (adj) return dispatch_roll_sens(L.nlds, L.idx16, [&](const void *fn) {
-        void *args[] = {&L.ps, &L.inst, &L.work, &L.B, &L.queue, &L.order, &L.warm, &L.dyn_delta, &L.dyn_eps, &L.cfg, &upd, &adj};
-        return hipLaunchKernel(fn, dim3(L.grid), dim3(L.threads), args, L.dyn_lds, st);
-    });
-    return dispatch_solve(L.nlds, L.idx16, [&](const void *fn) {
-        void *args[] = {&L.ps, &L.inst, &L.work, &L.B, &L.queue, &L.order, &L.warm, &L.dyn_delta, &L.dyn_eps, &L.cfg, &upd};
-        return hipLaunchKernel(fn, dim3(L.grid), dim3(L.threads), args, L.dyn_lds, st);
-    });
-}
-static hipError_t launch_solve(const SolveLaunch &launch, hipStream_t st, const UpdArgs &step) { return launch_solve_as(launch, st, step, nullptr); }
-static hipError_t launch_roll_sens(const SolveLaunch &launch, hipStream_t st, const UpdArgs &step, const AdjointDev *adj) {
-    return adj ? launch_solve_as(launch, st, step, adj) : hipErrorInvalidValue;
-}
-// the k_adjoint instantiation that matches a handle's k_solve, with the same launch shape (launch.hpp: AdjointLaunch)
-template <class F> static auto dispatch_adjoint(int nlds, int idx16, F &&f) {
-    auto byI = [&](auto ic) {
-        constexpr bool I16 = decltype(ic)::value;
-        if (nlds >= 2) return f((const void *)k_adjoint<SOLVE_T, 2, I16>);
-        if constexpr (EICOS_LDSRES != 0 || EICOS_UBL != 0) return f((const void *)k_adjoint<SOLVE_T, 1, I16>);
-        else return nlds == 1 ? f((const void *)k_adjoint<SOLVE_T, 1, I16>) : f((const void *)k_adjoint<SOLVE_T, 0, I16>);
-    };
-    return idx16 ? byI(std::true_type{}) : byI(std::false_type{});
+    const void *fn = solve_kernel(adj ? FAM_ROLL_SENS : FAM_SOLVE, L.nlds, L.idx16);
+    if (!fn) return hipErrorInvalidValue;
+    void *solve_args[] = {&L.ps, &L.inst, &L.work, &L.B, &L.queue, &L.order, &L.warm, &L.dyn_delta, &L.dyn_eps, &L.cfg, &upd};
+    void *sens_args[] = {&L.ps, &L.inst, &L.work, &L.B, &L.queue, &L.order, &L.warm, &L.dyn_delta, &L.dyn_eps, &L.cfg, &upd, &adj};
+    return hipLaunchKernel(fn, dim3(L.grid), dim3(L.threads), adj ? sens_args : solve_args, L.dyn_lds, st);
 }
 static hipError_t launch_adjoint(const AdjointLaunch &launch, hipStream_t st) {
     AdjointLaunch L = launch;
     if (L.count <= 0) return hipSuccess;
     if (L.count > L.batch || L.grid <= 0 || !L.adj) return hipErrorInvalidValue;
-    return dispatch_adjoint(L.nlds, L.idx16, [&](const void *fn) {
-        void *args[] = {&L.ps, &L.inst, &L.work, &L.count, &L.list, &L.dyn_delta, &L.dyn_eps, &L.cfg, &L.adj};
-        return hipLaunchKernel(fn, dim3(L.grid < L.count ? L.grid : L.count), dim3(L.threads), args, L.dyn_lds, st);
-    });
+    const void *fn = solve_kernel(FAM_ADJOINT, L.nlds, L.idx16);
+    if (!fn) return hipErrorInvalidValue;
+    void *args[] = {&L.ps, &L.inst, &L.work, &L.count, &L.list, &L.dyn_delta, &L.dyn_eps, &L.cfg, &L.adj};
+    return hipLaunchKernel(fn, dim3(L.grid < L.count ? L.grid : L.count), dim3(L.threads), args, L.dyn_lds, st);
 }
 #if EICOS_MAIN_BUILD
 hipError_t launch_update(int ps, double *inst, int first, int count, const double *Gpr, const double *Apr,
@@ -4694,33 +4677,28 @@ hipError_t launch_debug_scalings(int ps, double *inst, double *work, int i, int 
 }
 #endif // EICOS_MAIN_BUILD
 static hipError_t solve_occupancy(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu) {
-    return dispatch_solve(nlds, idx16, [&](const void *fn) {
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, threads, dyn_lds);
-    });
+    const void *fn = solve_kernel(FAM_SOLVE, nlds, idx16);
+    return fn ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, threads, dyn_lds) : hipErrorInvalidValue;
 }
 static hipError_t solve_set_max_lds(int threads, int nlds, int idx16, size_t dyn_lds) {
     if (dyn_lds == 0) return hipSuccess;
     // The attribute belongs to the kernel, not to a handle: several live handles (other patterns, the shards of an eicos_multi on one
     // device) launch the same instantiation with different dynamic LDS sizes, so it is always raised to the device's ceiling (160 KB
     // minus the 4 KB budgeted for the static block) and never lowered; the size a launch really uses is its own dyn_lds.
-    const hipError_t e = dispatch_solve(nlds, idx16, [&](const void *fn) {
-        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-    });
-    if (e != hipSuccess) return e;
-    const hipError_t ea = dispatch_adjoint(nlds, idx16, [&](const void *fn) { // (the adjoint kernel of the same instantiation takes the same launch shape)
-        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-    });
-    if (ea != hipSuccess || nlds < 1) return ea;
-    return dispatch_roll_sens(nlds, idx16, [&](const void *fn) { // (and so does the rollout that records its Jacobians)
-        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-    });
+    for (const SolveFamily fam : {FAM_SOLVE, FAM_ADJOINT, FAM_ROLL_SENS}) { // (the three families of one instantiation take the same launch shape)
+        const void *fn = solve_kernel(fam, nlds, idx16);
+        if (!fn) continue; // (no k_roll_sens without an LDS vector)
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 static hipError_t upload_pattern(int ps, const DevPat &P) {
     if (ps < 0 || ps >= MAX_PATTERNS) return hipErrorInvalidValue;
     return hipMemcpyToSymbol(HIP_SYMBOL(c_pat), &P, sizeof(DevPat), (size_t)ps * sizeof(DevPat), hipMemcpyHostToDevice);
 }
-SolveBuild solve_entries() { return {launch_solve, solve_occupancy, solve_set_max_lds, upload_pattern, launch_adjoint, launch_roll_sens}; } // (launch.hpp: one per build namespace)
+SolveBuild solve_entries() { return {launch_solve, solve_occupancy, solve_set_max_lds, upload_pattern, launch_adjoint}; } // (launch.hpp: one per build namespace)
 #endif // EICOS_ISA_PROBE
 #if EICOS_LDSRES
 } // namespace ldsres

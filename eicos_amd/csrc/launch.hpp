@@ -117,17 +117,17 @@ struct AdjointLaunch {
     int grid, threads, nlds, idx16; double dyn_delta, dyn_eps; SolveCfg cfg; size_t dyn_lds;
     const AdjointDev *adj;
 };
-// One k_solve build = these six entry points.  launch always receives an UpdArgs: UpdArgs{} when no step is fused into it.
+// One k_solve build = these five entry points.  launch always receives an UpdArgs: UpdArgs{} when no step is fused into it.
 struct SolveBuild {
-    hipError_t (*launch)(const SolveLaunch &L, hipStream_t st, const UpdArgs &upd);
+    // adj == NULL: one launch of k_solve.  adj != NULL, the rollout that also records its Jacobians (eicos_batch_rollout_jacobian;
+    // kernels.hip: k_roll_sens): the same launch with upd.on = UPD_ROLL over the whole batch, every step followed by the contracted adjoint
+    // of *adj (device memory: J [batch][steps][r][k], res [batch][steps][r] or NULL, g == NULL) while the step's iterate is in place.
+    // Kernels with an LDS vector only (L.nlds >= 1), as every fused step.
+    hipError_t (*launch)(const SolveLaunch &L, hipStream_t st, const UpdArgs &upd, const AdjointDev *adj);
     hipError_t (*occupancy)(int threads, int nlds, int idx16, size_t dyn_lds, int *blocks_per_cu);
-    hipError_t (*set_max_lds)(int threads, int nlds, int idx16, size_t dyn_lds);
+    hipError_t (*set_max_lds)(int threads, int nlds, int idx16, size_t dyn_lds); // (the build's k_solve, k_adjoint and k_roll_sens alike)
     hipError_t (*upload)(int ps, const DevPat &P);
     hipError_t (*adjoint)(const AdjointLaunch &L, hipStream_t st);
-    // the rollout that also records its Jacobians (eicos_batch_rollout_jacobian; kernels.hip: k_roll_sens): `launch` with upd.on = UPD_ROLL over
-    // the whole batch, every step followed by the contracted adjoint of *adj (device memory: J [batch][steps][r][k], res [batch][steps][r]
-    // or NULL, g == NULL) while the step's iterate is in place.  Kernels with an LDS vector only (L.nlds >= 1), as every fused step.
-    hipError_t (*roll_sens)(const SolveLaunch &L, hipStream_t st, const UpdArgs &upd, const AdjointDev *adj);
     bool operator==(const SolveBuild &o) const { return launch == o.launch; }
 };
 // The range launchers below (updateData in its four kinds and the output map) take an optional `list`: `count` ids of distinct instances
