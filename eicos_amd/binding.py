@@ -91,6 +91,81 @@ def build_library(force: bool = False) -> str:
     return library_path()
 
 
+def _signatures():
+    """The C ABI as ctypes sees it, one entry per function of include/eicos_amd.h: (name, argument types[, return type if not int]).
+    `eicos_*_name` stands for eicos_batch_name and eicos_multi_name, one argument list (the handle is a void * in both); the multi-GPU
+    *_device forms take a source device in front and are entries of their own.  A new entry point is one entry here;
+    tests/test_abi_and_symbolic.py holds every entry against the header.  Returns [(full name, argument types, return type)]."""
+    i, u, d, size, vp, hp = C.c_int, C.c_uint, C.c_double, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)
+    dp, ip, fp, infop = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(Info)
+    mp, sp, rp = C.POINTER(AffineMap), C.POINTER(Settings), C.POINTER(Retry)
+    problem = [i] * 4 + [ip] * 5  # n, m, p, ncones, then q, Gjc, Gir, Ajc, Air
+    host_check = problem + [u, i, ip]
+    table = [
+        # process-wide
+        ("eicos_set_arithmetic_profile", [i]), ("eicos_get_arithmetic_profile", []), ("eicos_device_count", []), ("eicos_exit_class", [i, i]),
+        ("eicos_last_error", [], C.c_char_p), ("eicos_multi_last_error", [], C.c_char_p),
+        ("eicos_host_alloc", [size], vp), ("eicos_host_free", [vp]), ("eicos_host_register", [vp, size]), ("eicos_host_unregister", [vp]),
+        ("eicos_settings_default", [sp], None), ("eicos_settings_size", [], size), ("eicos_retry_default", [rp], None), ("eicos_retry_size", [], size),
+        # handles
+        ("eicos_batch_create", [i] * 5 + [ip] * 5 + [i, i, hp]), ("eicos_multi_create", [i] * 5 + [ip] * 5 + [i, ip, i, hp]), ("eicos_*_destroy", [vp]),
+        ("eicos_batch_dims", [vp, C.POINTER(Dims)]), ("eicos_batch_kernel_build", [vp]), ("eicos_batch_set_stream", [vp, vp]),
+        ("eicos_multi_num_shards", [vp]), ("eicos_multi_shard", [vp, i, hp, ip, ip, ip]),
+        # updateData: all five groups, the right-hand sides, theta under the installed maps
+        ("eicos_*_update", [vp, i, i] + [dp] * 5), ("eicos_batch_update_device", [vp, i, i] + [vp] * 5), ("eicos_multi_update_device", [vp, i, i, i] + [vp] * 5),
+        ("eicos_*_update_rhs", [vp, i, i] + [dp] * 3), ("eicos_batch_update_rhs_device", [vp, i, i] + [vp] * 3), ("eicos_multi_update_rhs_device", [vp, i, i, i] + [vp] * 3),
+        ("eicos_*_update_param", [vp, i, i, dp]), ("eicos_batch_update_param_device", [vp, i, i, vp]), ("eicos_multi_update_param_device", [vp, i, i, i, vp]),
+        ("eicos_*_update_solve", [vp] + [dp] * 6 + [ip]), ("eicos_*_update_rhs_solve", [vp] + [dp] * 4 + [ip]), ("eicos_*_update_param_solve", [vp, dp, dp, dp, ip]),
+        ("eicos_batch_shared_values", [vp]), ("eicos_batch_last_update_path", [vp]),
+        # the five maps
+        ("eicos_*_set_param_map", [vp, i, mp, mp, mp]), ("eicos_*_param_count", [vp]), ("eicos_*_set_output_map", [vp, i, mp]), ("eicos_*_output_count", [vp]),
+        ("eicos_*_set_plant_map", [vp, mp]), ("eicos_*_has_plant_map", [vp]), ("eicos_*_set_shift_map", [vp] + [mp] * 4), ("eicos_*_has_shift_map", [vp]),
+        ("eicos_*_set_matrix_map", [vp, mp, mp]), ("eicos_*_has_matrix_map", [vp]), ("eicos_*_matrix_map_count", [vp]),
+        # starting point, outputs, rollout
+        ("eicos_*_set_iterate", [vp, i, i] + [dp] * 4), ("eicos_batch_set_iterate_device", [vp, i, i] + [vp] * 4),
+        ("eicos_*_outputs", [vp, i, i, dp]), ("eicos_batch_outputs_device", [vp, i, i, vp]),
+        ("eicos_*_rollout", [vp, i] + [dp] * 4 + [ip, ip]), ("eicos_*_rollout_jacobian", [vp, i] + [dp] * 4 + [ip, ip, dp, dp]),
+        ("eicos_*_rollout_gradient", [vp] + [dp] * 4), ("eicos_batch_rollout_gradient_device", [vp] + [vp] * 4),
+        ("eicos_batch_last_rollout_launches", [vp]), ("eicos_batch_rollout_jacobian_steps", [vp]),
+        # solve, subset solves, results
+        ("eicos_*_solve", [vp, ip]), ("eicos_*_solve_async", [vp]), ("eicos_*_sync", [vp]), ("eicos_*_select", [vp, u, ip, ip]),
+        ("eicos_*_solve_subset_async", [vp, ip, i]), ("eicos_*_solve_subset", [vp, ip, i, ip]), ("eicos_*_solve_where", [vp, u, ip, ip, ip]),
+        ("eicos_*_gather", [vp, ip, i] + [dp] * 4 + [infop]), ("eicos_*_solution", [vp, dp]), ("eicos_*_duals", [vp, dp, dp, dp]), ("eicos_*_info", [vp, infop]),
+        ("eicos_batch_solution_device", [vp, hp, C.POINTER(size)]),
+        # the indexed calls
+        ("eicos_*_update_indexed", [vp, ip, i] + [dp] * 5), ("eicos_batch_update_indexed_device", [vp, ip, i] + [vp] * 5),
+        ("eicos_*_update_rhs_indexed", [vp, ip, i] + [dp] * 3), ("eicos_batch_update_rhs_indexed_device", [vp, ip, i] + [vp] * 3),
+        ("eicos_*_update_param_indexed", [vp, ip, i, dp]), ("eicos_batch_update_param_indexed_device", [vp, ip, i, vp]),
+        ("eicos_*_set_iterate_indexed", [vp, ip, i] + [dp] * 4), ("eicos_batch_set_iterate_indexed_device", [vp, ip, i] + [vp] * 4),
+        ("eicos_*_outputs_indexed", [vp, ip, i, dp]), ("eicos_batch_outputs_indexed_device", [vp, ip, i, vp]),
+        ("eicos_*_update_param_solve_subset", [vp, ip, i, dp, dp, dp, ip]),
+        # adjoint sensitivities
+        ("eicos_*_adjoint", [vp, ip, i, i] + [dp] * 5), ("eicos_*_adjoint_data", [vp, ip, i, i] + [dp] * 7),
+        ("eicos_*_output_jacobian", [vp, ip, i, dp, dp]), ("eicos_batch_output_jacobian_device", [vp, ip, i, vp, vp]),
+        ("eicos_*_param_jacobian", [vp, ip, i, dp, dp]), ("eicos_batch_param_jacobian_device", [vp, ip, i, vp, vp]),
+        ("eicos_*_param_gradient", [vp, ip, i, i, dp, dp, dp]), ("eicos_batch_param_gradient_device", [vp, ip, i, i, vp, vp, vp]),
+        # policies and timers
+        ("eicos_*_set_warm_start", [vp, d]), ("eicos_*_set_dynamic_regularization", [vp, d, d]), ("eicos_*_retry_counts", [vp, i, i, ip, i]),
+        ("eicos_*_set_settings", [vp, sp]), ("eicos_*_get_settings", [vp, sp]), ("eicos_*_set_retry", [vp, rp]), ("eicos_*_get_retry", [vp, rp]),
+        ("eicos_batch_last_solve_ms", [vp, fp]), ("eicos_multi_last_solve_ms", [vp, fp, fp]), ("eicos_batch_last_update_ms", [vp, fp]),
+        ("eicos_batch_last_adjoint_ms", [vp, fp]), ("eicos_batch_ms_history", [vp, i, fp, i]),
+        # the single-instance form (include/ecos.h sits on it; Python does not call it)
+        ("eicos_create", [i] * 5 + [ip, dp, ip, ip, dp, ip, ip, dp, dp, dp, i, hp]), ("eicos_update", [vp] + [dp] * 5), ("eicos_solve", [vp, ip]),
+        ("eicos_solution", [vp, dp]), ("eicos_info_get", [vp, infop]), ("eicos_destroy", [vp]),
+        # debug
+        ("eicos_debug_factor", [vp, i, dp, dp]), ("eicos_debug_pattern", [vp, ip, ip, ip]), ("eicos_debug_trace", [vp, i, dp]),
+        ("eicos_debug_kkt", [vp, i, ip, ip, dp]), ("eicos_debug_scalings", [vp, i, dp, dp, dp, ip]), ("eicos_debug_host_tile_order", problem + [i] + [ip] * 5),
+        ("eicos_debug_host_check", host_check, d), ("eicos_debug_host_check_tiles", host_check, d), ("eicos_debug_host_check_hybrid", host_check, d),
+        # the HIP runtime the library is linked against, as _device_form uses it
+        ("hipMalloc", [hp, size]), ("hipMemcpy", [vp, vp, size, i]), ("hipFree", [vp]),
+    ]
+    return [(full, args, ret[0] if ret else i) for name, args, *ret in table
+            for full in ((name.replace("*", "batch"), name.replace("*", "multi")) if "*" in name else (name,))]
+
+
+_SIGNATURES = _signatures()
+
+
 def _lib():
     global _LIB
     if _LIB is None:
@@ -99,212 +174,16 @@ def _lib():
             raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(there is no CPU fallback)")
         L = C.CDLL(path)
-        dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p
-        L.eicos_last_error.restype = C.c_char_p
-        L.eicos_batch_create.argtypes = [C.c_int] * 5 + [ip] * 5 + [C.c_int, C.c_int, C.POINTER(vp)]
-        L.eicos_batch_update.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp]
-        L.eicos_batch_update_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-        L.eicos_batch_solve.argtypes = [vp, ip]
-        L.eicos_batch_solve_async.argtypes = [vp]
-        L.eicos_batch_sync.argtypes = [vp]
-        L.eicos_batch_solution.argtypes = [vp, dp]
-        L.eicos_batch_duals.argtypes = [vp, dp, dp, dp]
-        L.eicos_batch_info.argtypes = [vp, C.POINTER(Info)]
-        L.eicos_batch_solution_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
-        L.eicos_batch_dims.argtypes = [vp, C.POINTER(Dims)]
-        L.eicos_batch_kernel_build.argtypes = [vp]
-        if hasattr(L, "eicos_batch_shared_values"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            L.eicos_batch_shared_values.argtypes = [vp]
-            L.eicos_batch_shared_values.restype = C.c_int
-        L.eicos_batch_set_stream.argtypes = [vp, vp]
-        L.eicos_batch_set_warm_start.argtypes = [vp, C.c_double]
-        L.eicos_batch_set_warm_start.restype = C.c_int
-        L.eicos_batch_set_dynamic_regularization.argtypes = [vp, C.c_double, C.c_double]
-        L.eicos_batch_set_dynamic_regularization.restype = C.c_int
-        L.eicos_batch_last_solve_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.eicos_batch_last_update_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.eicos_batch_destroy.argtypes = [vp]
-        if hasattr(L, "eicos_batch_update_solve"):  # (round 6)
-            L.eicos_batch_update_solve.argtypes = [vp, dp, dp, dp, dp, dp, dp, ip]
-            L.eicos_batch_update_solve.restype = C.c_int
-        if hasattr(L, "eicos_batch_update_rhs"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            L.eicos_batch_update_rhs.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp]
-            L.eicos_batch_update_rhs_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
-            L.eicos_batch_update_rhs_solve.argtypes = [vp, dp, dp, dp, dp, ip]
-            L.eicos_multi_update_rhs.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp]
-            L.eicos_multi_update_rhs_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
-            L.eicos_multi_update_rhs_solve.argtypes = [vp, dp, dp, dp, dp, ip]
-            for f in ("eicos_batch_update_rhs", "eicos_batch_update_rhs_device", "eicos_batch_update_rhs_solve", "eicos_multi_update_rhs",
-                      "eicos_multi_update_rhs_device", "eicos_multi_update_rhs_solve"):
-                getattr(L, f).restype = C.c_int
-        if hasattr(L, "eicos_batch_set_param_map"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            mp = C.POINTER(AffineMap)
-            L.eicos_batch_set_param_map.argtypes = L.eicos_multi_set_param_map.argtypes = [vp, C.c_int, mp, mp, mp]
-            L.eicos_batch_param_count.argtypes = L.eicos_multi_param_count.argtypes = [vp]
-            L.eicos_batch_update_param.argtypes = L.eicos_multi_update_param.argtypes = [vp, C.c_int, C.c_int, dp]
-            L.eicos_batch_update_param_device.argtypes = [vp, C.c_int, C.c_int, vp]
-            L.eicos_multi_update_param_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
-            for f in ("set_param_map", "param_count", "update_param", "update_param_device"):
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-        if hasattr(L, "eicos_batch_set_output_map"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            mp = C.POINTER(AffineMap)
-            L.eicos_batch_set_output_map.argtypes = L.eicos_multi_set_output_map.argtypes = [vp, C.c_int, mp]
-            L.eicos_batch_output_count.argtypes = L.eicos_multi_output_count.argtypes = [vp]
-            L.eicos_batch_outputs.argtypes = L.eicos_multi_outputs.argtypes = [vp, C.c_int, C.c_int, dp]
-            L.eicos_batch_outputs_device.argtypes = [vp, C.c_int, C.c_int, vp]
-            L.eicos_batch_update_param_solve.argtypes = L.eicos_multi_update_param_solve.argtypes = [vp, dp, dp, dp, ip]
-            for f in ("set_output_map", "output_count", "outputs", "update_param_solve"):
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-            L.eicos_batch_outputs_device.restype = C.c_int
-        if hasattr(L, "eicos_batch_set_plant_map"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            mp = C.POINTER(AffineMap)
-            L.eicos_batch_set_plant_map.argtypes = L.eicos_multi_set_plant_map.argtypes = [vp, mp]
-            L.eicos_batch_has_plant_map.argtypes = L.eicos_multi_has_plant_map.argtypes = [vp]
-            L.eicos_batch_rollout.argtypes = L.eicos_multi_rollout.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip, ip]
-            for f in ("set_plant_map", "has_plant_map", "rollout"):
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-            L.eicos_batch_last_rollout_launches.argtypes = [vp]
-            L.eicos_batch_last_rollout_launches.restype = C.c_int
-        if hasattr(L, "eicos_batch_set_matrix_map"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            mp = C.POINTER(AffineMap)
-            L.eicos_batch_set_matrix_map.argtypes = L.eicos_multi_set_matrix_map.argtypes = [vp, mp, mp]
-            L.eicos_batch_has_matrix_map.argtypes = L.eicos_multi_has_matrix_map.argtypes = [vp]
-            for f in ("set_matrix_map", "has_matrix_map"):
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-        if hasattr(L, "eicos_batch_set_shift_map"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            mp = C.POINTER(AffineMap)
-            L.eicos_batch_set_shift_map.argtypes = L.eicos_multi_set_shift_map.argtypes = [vp, mp, mp, mp, mp]
-            L.eicos_batch_has_shift_map.argtypes = L.eicos_multi_has_shift_map.argtypes = [vp]
-            L.eicos_batch_set_iterate.argtypes = L.eicos_multi_set_iterate.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp]
-            L.eicos_batch_set_iterate_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
-            for f in ("set_shift_map", "has_shift_map", "set_iterate"):
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-            L.eicos_batch_set_iterate_device.restype = C.c_int
-        if hasattr(L, "eicos_batch_set_settings"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            sp = C.POINTER(Settings)
-            L.eicos_settings_default.argtypes = [sp]
-            L.eicos_settings_default.restype = None
-            L.eicos_settings_size.argtypes = []
-            L.eicos_settings_size.restype = C.c_size_t
-            if L.eicos_settings_size() != C.sizeof(Settings):
-                raise RuntimeError(f"{path}: struct eicos_settings has {L.eicos_settings_size()} bytes, the ctypes mirror {C.sizeof(Settings)}")
-            for f in ("set_settings", "get_settings"):
-                getattr(L, "eicos_batch_" + f).argtypes = getattr(L, "eicos_multi_" + f).argtypes = [vp, sp]
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-        if hasattr(L, "eicos_batch_set_retry"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            rp = C.POINTER(Retry)
-            L.eicos_retry_default.argtypes = [rp]
-            L.eicos_retry_default.restype = None
-            L.eicos_retry_size.argtypes = []
-            L.eicos_retry_size.restype = C.c_size_t
-            if L.eicos_retry_size() != C.sizeof(Retry):
-                raise RuntimeError(f"{path}: struct eicos_retry has {L.eicos_retry_size()} bytes, the ctypes mirror {C.sizeof(Retry)}")
-            for f in ("set_retry", "get_retry"):
-                getattr(L, "eicos_batch_" + f).argtypes = getattr(L, "eicos_multi_" + f).argtypes = [vp, rp]
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-            L.eicos_batch_retry_counts.argtypes = L.eicos_multi_retry_counts.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int]
-            L.eicos_batch_retry_counts.restype = L.eicos_multi_retry_counts.restype = C.c_int
-        if hasattr(L, "eicos_batch_solve_subset"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            L.eicos_exit_class.argtypes = [C.c_int, C.c_int]
-            L.eicos_exit_class.restype = C.c_int
-            L.eicos_batch_select.argtypes = L.eicos_multi_select.argtypes = [vp, C.c_uint, ip, ip]
-            L.eicos_batch_solve_subset_async.argtypes = L.eicos_multi_solve_subset_async.argtypes = [vp, ip, C.c_int]
-            L.eicos_batch_solve_subset.argtypes = L.eicos_multi_solve_subset.argtypes = [vp, ip, C.c_int, ip]
-            L.eicos_batch_solve_where.argtypes = L.eicos_multi_solve_where.argtypes = [vp, C.c_uint, ip, ip, ip]
-            L.eicos_batch_gather.argtypes = L.eicos_multi_gather.argtypes = [vp, ip, C.c_int, dp, dp, dp, dp, C.POINTER(Info)]
-            for f in ("select", "solve_subset_async", "solve_subset", "solve_where", "gather"):
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-        if hasattr(L, "eicos_batch_update_param_solve_subset"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            L.eicos_batch_update_indexed.argtypes = L.eicos_multi_update_indexed.argtypes = [vp, ip, C.c_int, dp, dp, dp, dp, dp]
-            L.eicos_batch_update_rhs_indexed.argtypes = L.eicos_multi_update_rhs_indexed.argtypes = [vp, ip, C.c_int, dp, dp, dp]
-            L.eicos_batch_update_param_indexed.argtypes = L.eicos_multi_update_param_indexed.argtypes = [vp, ip, C.c_int, dp]
-            L.eicos_batch_set_iterate_indexed.argtypes = L.eicos_multi_set_iterate_indexed.argtypes = [vp, ip, C.c_int, dp, dp, dp, dp]
-            L.eicos_batch_outputs_indexed.argtypes = L.eicos_multi_outputs_indexed.argtypes = [vp, ip, C.c_int, dp]
-            L.eicos_batch_update_param_solve_subset.argtypes = L.eicos_multi_update_param_solve_subset.argtypes = [vp, ip, C.c_int, dp, dp, dp, ip]
-            L.eicos_batch_update_indexed_device.argtypes = [vp, ip, C.c_int, vp, vp, vp, vp, vp]
-            L.eicos_batch_update_rhs_indexed_device.argtypes = [vp, ip, C.c_int, vp, vp, vp]
-            L.eicos_batch_update_param_indexed_device.argtypes = [vp, ip, C.c_int, vp]
-            L.eicos_batch_set_iterate_indexed_device.argtypes = [vp, ip, C.c_int, vp, vp, vp, vp]
-            L.eicos_batch_outputs_indexed_device.argtypes = [vp, ip, C.c_int, vp]
-            for f in ("update_indexed", "update_rhs_indexed", "update_param_indexed", "set_iterate_indexed", "outputs_indexed", "update_param_solve_subset"):
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-            for f in ("update_indexed", "update_rhs_indexed", "update_param_indexed", "set_iterate_indexed", "outputs_indexed"):
-                getattr(L, "eicos_batch_" + f + "_device").restype = C.c_int
-        if hasattr(L, "eicos_batch_adjoint"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            L.eicos_batch_adjoint.argtypes = L.eicos_multi_adjoint.argtypes = [vp, ip, C.c_int, C.c_int, dp, dp, dp, dp, dp]
-            L.eicos_batch_output_jacobian.argtypes = L.eicos_multi_output_jacobian.argtypes = [vp, ip, C.c_int, dp, dp]
-            L.eicos_batch_output_jacobian_device.argtypes = [vp, ip, C.c_int, vp, vp]
-            for f in ("adjoint", "output_jacobian"):
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-            L.eicos_batch_output_jacobian_device.restype = C.c_int
-        if hasattr(L, "eicos_batch_adjoint_data"):
-            L.eicos_batch_adjoint_data.argtypes = L.eicos_multi_adjoint_data.argtypes = [vp, ip, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp]
-            L.eicos_batch_param_jacobian.argtypes = L.eicos_multi_param_jacobian.argtypes = [vp, ip, C.c_int, dp, dp]
-            L.eicos_batch_param_gradient.argtypes = L.eicos_multi_param_gradient.argtypes = [vp, ip, C.c_int, C.c_int, dp, dp, dp]
-            L.eicos_batch_param_jacobian_device.argtypes = [vp, ip, C.c_int, vp, vp]
-            L.eicos_batch_param_gradient_device.argtypes = [vp, ip, C.c_int, C.c_int, vp, vp, vp]
-            L.eicos_batch_matrix_map_count.argtypes = L.eicos_multi_matrix_map_count.argtypes = [vp]
-            for f in ("adjoint_data", "param_jacobian", "param_gradient", "matrix_map_count"):
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-            L.eicos_batch_param_jacobian_device.restype = L.eicos_batch_param_gradient_device.restype = C.c_int
-        if hasattr(L, "eicos_batch_rollout_jacobian"):  # (absent from an older library: EICOS_AMD_LIB A/B runs)
-            L.eicos_batch_rollout_jacobian.argtypes = L.eicos_multi_rollout_jacobian.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip, ip, dp, dp]
-            L.eicos_batch_rollout_gradient.argtypes = L.eicos_multi_rollout_gradient.argtypes = [vp, dp, dp, dp, dp]
-            L.eicos_batch_rollout_gradient_device.argtypes = [vp, vp, vp, vp, vp]
-            L.eicos_batch_rollout_jacobian_steps.argtypes = [vp]
-            for f in ("rollout_jacobian", "rollout_gradient"):
-                getattr(L, "eicos_batch_" + f).restype = getattr(L, "eicos_multi_" + f).restype = C.c_int
-            L.eicos_batch_rollout_gradient_device.restype = L.eicos_batch_rollout_jacobian_steps.restype = C.c_int
-        if hasattr(L, "eicos_batch_ms_history"):  # (round 6; absent from a previous round's library)
-            L.eicos_batch_ms_history.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
-            L.eicos_batch_ms_history.restype = C.c_int
-        if hasattr(L, "eicos_host_alloc"):  # absent from a previous round's library (EICOS_AMD_LIB: same-box A/B runs, bench.py's prev_round leg)
-            L.eicos_batch_last_update_path.argtypes = [vp]
-            L.eicos_batch_last_update_path.restype = C.c_int
-            L.eicos_host_alloc.argtypes = [C.c_size_t]
-            L.eicos_host_alloc.restype = vp
-            L.eicos_host_free.argtypes = [vp]
-            L.eicos_host_free.restype = C.c_int
-            L.eicos_host_register.argtypes = [vp, C.c_size_t]
-            L.eicos_host_register.restype = C.c_int
-            L.eicos_host_unregister.argtypes = [vp]
-            L.eicos_host_unregister.restype = C.c_int
-        L.eicos_debug_factor.argtypes = [vp, C.c_int, dp, dp]
-        L.eicos_debug_pattern.argtypes = [vp, ip, ip, ip]
-        L.eicos_debug_trace.argtypes = [vp, C.c_int, dp]
-        L.eicos_debug_kkt.argtypes = [vp, C.c_int, ip, ip, dp]
-        L.eicos_debug_scalings.argtypes = [vp, C.c_int, dp, dp, dp, ip]
-        L.eicos_debug_host_check.restype = C.c_double
-        L.eicos_debug_host_check.argtypes = [C.c_int] * 4 + [ip] * 5 + [C.c_uint, C.c_int, ip]
-        for fn in (L.eicos_debug_host_check_tiles, L.eicos_debug_host_check_hybrid):
-            fn.restype = C.c_double
-            fn.argtypes = [C.c_int] * 4 + [ip] * 5 + [C.c_uint, C.c_int, ip]
-        for f in ("create", "update", "update_device", "solve", "solve_async", "sync", "solution", "duals", "info",
-                  "solution_device", "dims", "set_stream", "last_solve_ms", "last_update_ms", "destroy"):
-            getattr(L, "eicos_batch_" + f).restype = C.c_int
-        # multi-GPU layer (one process, several devices)
-        L.eicos_multi_last_error.restype = C.c_char_p
-        L.eicos_multi_create.argtypes = [C.c_int] * 5 + [ip] * 5 + [C.c_int, ip, C.c_int, C.POINTER(vp)]
-        L.eicos_multi_update.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp]
-        L.eicos_multi_update_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-        if hasattr(L, "eicos_multi_update_solve"):
-            L.eicos_multi_update_solve.argtypes = [vp, dp, dp, dp, dp, dp, dp, ip]
-            L.eicos_multi_update_solve.restype = C.c_int
-        L.eicos_multi_solve.argtypes = [vp, ip]
-        L.eicos_multi_solve_async.argtypes = [vp]
-        L.eicos_multi_sync.argtypes = [vp]
-        L.eicos_multi_solution.argtypes = [vp, dp]
-        L.eicos_multi_duals.argtypes = [vp, dp, dp, dp]
-        L.eicos_multi_info.argtypes = [vp, C.POINTER(Info)]
-        L.eicos_multi_set_warm_start.argtypes = [vp, C.c_double]
-        L.eicos_multi_set_dynamic_regularization.argtypes = [vp, C.c_double, C.c_double]
-        L.eicos_multi_num_shards.argtypes = [vp]
-        L.eicos_multi_shard.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, ip]
-        L.eicos_multi_last_solve_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        L.eicos_multi_destroy.argtypes = [vp]
-        for f in ("create", "update", "update_device", "solve", "solve_async", "sync", "solution", "duals", "info", "set_warm_start",
-                  "set_dynamic_regularization", "num_shards", "shard", "last_solve_ms", "destroy"):
-            getattr(L, "eicos_multi_" + f).restype = C.c_int
+        found = set()
+        for name, args, restype in _SIGNATURES:
+            fn = getattr(L, name, None)
+            if fn is not None:  # (an older library -- EICOS_AMD_LIB A/B runs, bench.py's prev_round leg -- lacks some: calling one fails at the call)
+                fn.argtypes, fn.restype = args, restype
+                found.add(name)
+        if "eicos_settings_size" in found and L.eicos_settings_size() != C.sizeof(Settings):
+            raise RuntimeError(f"{path}: struct eicos_settings has {L.eicos_settings_size()} bytes, the ctypes mirror {C.sizeof(Settings)}")
+        if "eicos_retry_size" in found and L.eicos_retry_size() != C.sizeof(Retry):
+            raise RuntimeError(f"{path}: struct eicos_retry has {L.eicos_retry_size()} bytes, the ctypes mirror {C.sizeof(Retry)}")
         _LIB = L
     return _LIB
 
@@ -349,6 +228,51 @@ def _ip(a):
 
 def _dp(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# How an array travels when it may be None or empty.  A pointer made by _ip / _dp keeps its array alive, dummies included.
+def _dp_or_dummy(a):
+    """None as NULL; an empty array as a pointer to a one-element dummy (the library gets a valid address)."""
+    return _dp(a if a is None or a.size else np.zeros(1))
+
+
+def _ip_or_dummy(a):
+    return _ip(a if a is None or a.size else np.zeros(1, np.int32))
+
+
+def _dp_or_null(a):
+    """None and an empty array as NULL."""
+    return _dp(a) if (a is not None and a.size) else None
+
+
+def _dev(*addresses):
+    """Raw device addresses (ints) as void pointers; 0 as NULL."""
+    return [C.c_void_p(int(p) or None) for p in addresses]
+
+
+def _nonneg(v):
+    """The value of a call that returns a count or a flag, or a negative error code (raised)."""
+    if v < 0:
+        _chk(v)
+    return v
+
+
+def _info_columns(arr, count):
+    """The first `count` records of an Info array as a dict of arrays, one per field in declaration order."""
+    raw = np.frombuffer(arr, dtype=np.dtype([(k, "f8" if t is C.c_double else "i4") for k, t in Info._fields_]))[:count]
+    return {k: raw[k].copy() for k in raw.dtype.names}
+
+
+def _known_settings(who, fields):
+    """TypeError for a name that is no field of eicos_settings."""
+    unknown = sorted(set(fields) - set(SETTINGS_FIELDS))
+    if unknown:
+        raise TypeError(f"{who}: unknown field(s) {', '.join(unknown)} (the settings are {', '.join(SETTINGS_FIELDS)})")
+
+
+def _assign_settings(st, fields):
+    for k, v in fields.items():
+        setattr(st, k, int(v) if k in ("iter_max", "nitref") else float(v))
 
 
 class PinnedArray:
@@ -398,7 +322,7 @@ def _group_ptrs(groups, widths, count):
             if a.size != count * w:
                 raise ValueError(f"array has {a.size} elements, expected {count}x{w}")
         arrs.append(a)
-        ptrs.append(None if a is None else _dp(a) if a.size else _dp(np.zeros(1)))  # (zero-width groups: NULL-safe dummies)
+        ptrs.append(_dp_or_dummy(a))  # (zero-width groups: NULL-safe dummies)
     return arrs, ptrs
 
 
@@ -683,7 +607,7 @@ def _index_rows(indices):
     if idx.ndim > 1:
         raise ValueError(f"indices must be one-dimensional, not of shape {idx.shape}")
     idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
-    return idx, (_ip(idx) if idx.size else _ip(np.zeros(1, np.int32)))
+    return idx, _ip_or_dummy(idx)
 
 
 def _indexed_groups(names, groups, widths, count):
@@ -721,6 +645,10 @@ class _Solver:
         if rc != 0:
             raise RuntimeError(f"eicos_amd error {rc}: {getattr(_lib(), self._error)().decode()}")
 
+    def _query(self, name) -> int:
+        """A call that only returns a number of the handle (a count, a flag set)."""
+        return int(getattr(_lib(), self._prefix + name)(self._h))
+
     def _widths(self):
         pat = self.pat
         return pat.nnzG, pat.nnzA, pat.n, pat.m, pat.p
@@ -729,7 +657,7 @@ class _Solver:
         if x_out is not None:
             assert x_out.dtype == np.float64 and x_out.flags.c_contiguous and x_out.shape == (self.batch, self.pat.n)
         codes = np.zeros(self.batch, np.int32)
-        self._call(name, *ptr, _dp(x_out) if (x_out is not None and x_out.size) else None, _ip(codes))
+        self._call(name, *ptr, _dp_or_null(x_out), _ip(codes))
         return codes
 
     # ---- updateData ----
@@ -764,7 +692,7 @@ class _Solver:
 
     def param_count(self) -> int:
         """k of the installed parameter map, 0 without one."""
-        return int(getattr(_lib(), self._prefix + "param_count")(self._h))
+        return self._query("param_count")
 
     def update_param(self, theta, first: int = 0, count: int | None = None):
         """theta [count, k] (host array) for instances [first, first + count): the GPU expands it into the mapped groups of c, h, b and
@@ -775,7 +703,7 @@ class _Solver:
         else:  # (the library refuses: "no parameter map")
             theta = np.ascontiguousarray(theta, dtype=np.float64)
             count = (theta.shape[0] if theta.ndim == 2 else self.batch) if count is None else count
-        self._call("update_param", first, count, _dp(theta) if theta.size else _dp(np.zeros(1)))
+        self._call("update_param", first, count, _dp_or_dummy(theta))
 
     # ---- output map and the closed-loop step (include/eicos_amd.h: eicos_batch_set_output_map / eicos_batch_update_param_solve) ----
     def set_output_map(self, omap: "OutputMap | None"):
@@ -788,14 +716,14 @@ class _Solver:
 
     def output_count(self) -> int:
         """r of the installed output map, 0 without one."""
-        return int(getattr(_lib(), self._prefix + "output_count")(self._h))
+        return self._query("output_count")
 
     def outputs(self, first: int = 0, count: int | None = None):
         """u [count, r] of instances [first, first + count): the output map applied to their current x -- bit for bit
         OutputMap.evaluate(solution()[first:first + count])."""
         count = self.batch - first if count is None else count
         u = np.zeros((max(count, 0), self.output_count()))
-        self._call("outputs", first, count, _dp(u) if u.size else _dp(np.zeros(1)))
+        self._call("outputs", first, count, _dp_or_dummy(u))
         return u
 
     def update_param_solve(self, theta, u_out=None, x_out=None):
@@ -810,8 +738,7 @@ class _Solver:
         _result_rows(u_out, self.batch, self.output_count(), "u_out")
         _result_rows(x_out, self.batch, self.pat.n, "x_out")
         codes = np.zeros(self.batch, np.int32)
-        self._call("update_param_solve", _dp(theta) if theta.size else _dp(np.zeros(1)), _dp(u_out) if (u_out is not None and u_out.size) else None,
-                   _dp(x_out) if (x_out is not None and x_out.size) else None, _ip(codes))
+        self._call("update_param_solve", _dp_or_dummy(theta), _dp_or_null(u_out), _dp_or_null(x_out), _ip(codes))
         return codes
 
     # ---- plant map and the closed-loop rollout (include/eicos_amd.h: eicos_batch_set_plant_map / eicos_batch_rollout) ----
@@ -824,7 +751,7 @@ class _Solver:
         self._call("set_plant_map", ptr)
 
     def has_plant_map(self) -> bool:
-        return bool(getattr(_lib(), self._prefix + "has_plant_map")(self._h))
+        return bool(self._query("has_plant_map"))
 
     # ---- matrix map: G and A affine in theta (include/eicos_amd.h: eicos_batch_set_matrix_map) ----
     def set_matrix_map(self, mmap: "MatrixMap | None"):
@@ -839,7 +766,7 @@ class _Solver:
 
     def has_matrix_map(self) -> int:
         """Bit 0: G is mapped, bit 1: A is mapped; 0: no matrix map."""
-        return int(getattr(_lib(), self._prefix + "has_matrix_map")(self._h))
+        return self._query("has_matrix_map")
 
     # ---- starting point and shift map (include/eicos_amd.h: eicos_batch_set_iterate / eicos_batch_set_shift_map) ----
     def set_iterate(self, x=None, y=None, z=None, s=None, first: int = 0, count: int | None = None):
@@ -866,13 +793,18 @@ class _Solver:
 
     def has_shift_map(self) -> int:
         """Bit 0: x, 1: y, 2: z, 3: s is mapped; 0: no shift map."""
-        return int(getattr(_lib(), self._prefix + "has_shift_map")(self._h))
+        return self._query("has_shift_map")
 
     def rollout(self, theta0, steps: int, w=None):
         """`steps` closed-loop steps of the whole batch in one call: from theta0 [batch, k], every step is update_param_solve on the
         current theta row and then the plant map, theta+ = PlantMap.evaluate(theta, u, w[:, t]) -- with an LDS vector on the handle one
         launch in which every workgroup takes its instances through all their steps.  Returns u_traj [batch, steps, r], theta_traj
         [batch, steps + 1, k], exitcodes and iters [batch, steps]: bit for bit what the host loop over update_param_solve gives."""
+        return self._rollout("rollout", theta0, steps, w, False)[0]
+
+    def _rollout(self, name, theta0, steps, w, jacobian):
+        """rollout and rollout_jacobian: the checked inputs, the four trajectories and, with `jacobian`, J and res behind them.
+        Returns (the result arrays in the call's order, (T, k, r))."""
         steps = int(steps)
         k, r = self.param_count(), self.output_count()
         if k > 0:
@@ -884,34 +816,18 @@ class _Solver:
         T = max(steps, 0)
         u_traj, theta_traj = np.zeros((self.batch, T, r)), np.zeros((self.batch, T + 1, k))
         codes, iters = np.zeros((self.batch, T), np.int32), np.zeros((self.batch, T), np.int32)
-        one = np.zeros(1)
-        self._call("rollout", steps, _dp(theta0 if theta0.size else one), None if w is None else _dp(w if w.size else one),
-                   _dp(u_traj if u_traj.size else one), _dp(theta_traj if theta_traj.size else one), _ip(codes), _ip(iters))
-        return u_traj, theta_traj, codes, iters
+        more = [np.zeros((self.batch, T, r, k)), np.zeros((self.batch, T, r))] if jacobian else []
+        self._call(name, steps, _dp_or_dummy(theta0), _dp_or_dummy(w), _dp_or_dummy(u_traj), _dp_or_dummy(theta_traj), _ip(codes), _ip(iters),
+                   *[_dp_or_dummy(a) for a in more])
+        return (u_traj, theta_traj, codes, iters, *more), (T, k, r)
 
     def rollout_jacobian(self, theta0, steps: int, w=None):
         """rollout() that also records the Jacobian of every step: returns (u_traj, theta_traj, exitcodes, iters, J [batch, steps, r, k],
         res [batch, steps, r]) -- J[i, t] and res[i, t] are what param_jacobian() returns for instance i right after step t's solve, bit
         for bit, the first four what rollout() returns; still one launch with an LDS vector on the handle.  A step that did not end
         OPTIMAL / OPTIMAL_INACC has NaN rows, and the loop goes on.  The handle keeps J on the GPU for rollout_gradient()."""
-        steps = int(steps)
-        k, r = self.param_count(), self.output_count()
-        if k > 0:
-            theta0, _ = _theta_rows(theta0, k, self.batch)
-            w = _disturbance(w, self.batch, steps, k)
-        else:  # (the library refuses: "no parameter map")
-            theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
-            w = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
-        T = max(steps, 0)
-        u_traj, theta_traj = np.zeros((self.batch, T, r)), np.zeros((self.batch, T + 1, k))
-        codes, iters = np.zeros((self.batch, T), np.int32), np.zeros((self.batch, T), np.int32)
-        J, res = np.zeros((self.batch, T, r, k)), np.zeros((self.batch, T, r))
-        one = np.zeros(1)
-        self._call("rollout_jacobian", steps, _dp(theta0 if theta0.size else one), None if w is None else _dp(w if w.size else one),
-                   _dp(u_traj if u_traj.size else one), _dp(theta_traj if theta_traj.size else one), _ip(codes), _ip(iters),
-                   _dp(J if J.size else one), _dp(res if res.size else one))
-        self._rollout_shape = (T, k, r)
-        return u_traj, theta_traj, codes, iters, J, res
+        out, self._rollout_shape = self._rollout("rollout_jacobian", theta0, steps, w, True)
+        return out
 
     def rollout_gradient(self, gu=None, gtheta=None, device=False):
         """(grad_theta0 [batch, k], grad_w [batch, T, k]): the gradient of L = sum_t gu_t' u_t + sum_t gtheta_t' theta_t over the most
@@ -921,17 +837,15 @@ class _Solver:
         shape = getattr(self, "_rollout_shape", None)
         if shape is None:  # (no rollout_jacobian yet: the library refuses, with its message)
             gu, gtheta = (None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (gu, gtheta))
-            self._call("rollout_gradient", None if gu is None else _dp(gu), None if gtheta is None else _dp(gtheta), _dp(np.zeros(1)), None)
+            self._call("rollout_gradient", _dp(gu), _dp(gtheta), _dp(np.zeros(1)), None)
             raise RuntimeError("rollout_gradient: no rollout_jacobian() on this handle")
         T, k, r = shape
         gu, gtheta = _cotangent(gu, (self.batch, T, r), "gu"), _cotangent(gtheta, (self.batch, T + 1, k), "gtheta")
         g0, gw = np.zeros((self.batch, k)), np.zeros((self.batch, T, k))
-        one = np.zeros(1)
         if device:
             self._device_form("rollout_gradient_device", None, 0, (), (gu, gtheta), (g0, gw), lead=())
         else:
-            self._call("rollout_gradient", None if gu is None else _dp(gu if gu.size else one), None if gtheta is None else _dp(gtheta if gtheta.size else one),
-                       _dp(g0 if g0.size else one), _dp(gw if gw.size else one))
+            self._call("rollout_gradient", *[_dp_or_dummy(a) for a in (gu, gtheta, g0, gw)])
         return g0, gw
 
     # ---- solve ----
@@ -951,7 +865,7 @@ class _Solver:
     def _index_list(indices):
         """indices as a contiguous int32 vector (the library checks range and duplicates); a 1-element dummy keeps the pointer valid."""
         idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
-        return idx, (_ip(idx) if idx.size else _ip(np.zeros(1, np.int32)))
+        return idx, _ip_or_dummy(idx)
 
     def select(self, mask: int):
         """The ascending ids of the instances whose exit class is in `mask` (an OR of SEL_* bits), found by the selection kernel on the
@@ -988,9 +902,8 @@ class _Solver:
         pat, k = self.pat, int(idx.size)
         x, y, z, s = np.zeros((k, pat.n)), np.zeros((k, pat.p)), np.zeros((k, pat.m)), np.zeros((k, pat.m))
         arr = (Info * max(k, 1))()
-        self._call("gather", ptr, k, *[_dp(a) if a.size else None for a in (x, y, z, s)], arr)
-        raw = np.frombuffer(arr, dtype=np.dtype([(f, "f8" if t is C.c_double else "i4") for f, t in Info._fields_]))[:k]
-        return {"x": x, "y": y, "z": z, "s": s, "info": {f: raw[f].copy() for f in raw.dtype.names}}
+        self._call("gather", ptr, k, *[_dp_or_null(a) for a in (x, y, z, s)], arr)
+        return {"x": x, "y": y, "z": z, "s": s, "info": _info_columns(arr, k)}
 
     # ---- update, read and step a chosen subset (include/eicos_amd.h: eicos_batch_update_indexed ... _update_param_solve_subset) ----
     def update_indexed(self, indices, Gpr=None, Apr=None, c=None, h=None, b=None):
@@ -1011,7 +924,7 @@ class _Solver:
         """update_param() for the instances `indices`: theta [len(indices), k], row q for instance indices[q]."""
         idx, ptr = _index_rows(indices)
         theta = self._theta_for(theta, int(idx.size))
-        self._call("update_param_indexed", ptr, int(idx.size), _dp(theta) if theta.size else _dp(np.zeros(1)))
+        self._call("update_param_indexed", ptr, int(idx.size), _dp_or_dummy(theta))
 
     def set_iterate_indexed(self, indices, x=None, y=None, z=None, s=None):
         """set_iterate() for the instances `indices`, rows in list order."""
@@ -1024,7 +937,7 @@ class _Solver:
         """u [len(indices), r]: row q = the output map on the current x of instance indices[q] -- row indices[q] of outputs()."""
         idx, ptr = _index_rows(indices)
         u = np.zeros((int(idx.size), self.output_count()))
-        self._call("outputs_indexed", ptr, int(idx.size), _dp(u) if u.size else _dp(np.zeros(1)))
+        self._call("outputs_indexed", ptr, int(idx.size), _dp_or_dummy(u))
         return u
 
     # ---- adjoint sensitivities (include/eicos_amd.h: eicos_batch_adjoint, _output_jacobian; DESIGN.md 4.1) ----
@@ -1043,14 +956,10 @@ class _Solver:
         result is a smoothed value, not a derivative."""
         ptr, count = self._adjoint_rows(idx)
         pat = self.pat
-        g = np.ascontiguousarray(g, dtype=np.float64)
-        if g.ndim == 2:
-            g = g[:, None, :]
-        if g.ndim != 3 or g.shape[0] != count or g.shape[2] != pat.n:
-            raise ValueError(f"g must have shape [{count}, nrhs, {pat.n}], not {g.shape}")
+        g = self._adjoint_g(g, count)
         nrhs = int(g.shape[1])
         gc, gh, gb, res = (np.zeros((count, nrhs, w)) for w in (pat.n, pat.m, pat.p, 1))
-        self._call("adjoint", ptr, count, nrhs, *[_dp(a) if a.size else None for a in (g, gc, gh, gb)], _dp(res) if res.size else None)
+        self._call("adjoint", ptr, count, nrhs, *[_dp_or_null(a) for a in (g, gc, gh, gb, res)])
         return gc, gh, gb, res[:, :, 0]
 
     def output_jacobian(self, idx=None, device=False):
@@ -1061,25 +970,11 @@ class _Solver:
         r, k = max(self.output_count(), 0), max(self.param_count(), 0)
         J, res = np.zeros((count, r, k)), np.zeros((count, r))
         if not device:
-            self._call("output_jacobian", ptr, count, _dp(J) if J.size else _dp(np.zeros(1)), _dp(res) if res.size else None)
-            return J, res
-        if self._prefix != "eicos_batch_":
-            raise ValueError("output_jacobian(device=True) needs a single-GPU handle")
-        hip = _lib()
-        hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        hip.hipFree.argtypes = [C.c_void_p]
-        dJ, dres = C.c_void_p(), C.c_void_p()
-        if hip.hipMalloc(C.byref(dJ), max(J.nbytes, 8)) != 0 or hip.hipMalloc(C.byref(dres), max(res.nbytes, 8)) != 0:
-            raise RuntimeError("hipMalloc failed")
-        try:
-            self._call("output_jacobian_device", ptr, count, dJ, dres)
-            self._call("sync")
-            for host, dev in ((J, dJ), (res, dres)):
-                if host.nbytes and hip.hipMemcpy(host.ctypes.data, dev, host.nbytes, 2) != 0:  # hipMemcpyDeviceToHost
-                    raise RuntimeError("hipMemcpy failed")
-        finally:
-            hip.hipFree(dJ); hip.hipFree(dres)
+            self._call("output_jacobian", ptr, count, _dp_or_dummy(J), _dp_or_null(res))
+        elif self._prefix != "eicos_batch_":
+            raise ValueError("output_jacobian(device=True) needs a single-GPU handle")  # (this call's own wording, older than _device_form's)
+        else:
+            self._device_form("output_jacobian_device", ptr, count, (), (), (J, res))
         return J, res
 
     # ---- ... with respect to the matrix data (eicos_batch_adjoint_data, _param_jacobian, _param_gradient) ----
@@ -1101,12 +996,12 @@ class _Solver:
         g = self._adjoint_g(g, count)
         nrhs = int(g.shape[1])
         gc, gh, gb, gG, gA, res = (np.zeros((count, nrhs, w)) for w in (pat.n, pat.m, pat.p, pat.nnzG, pat.nnzA, 1))
-        self._call("adjoint_data", ptr, count, nrhs, *[_dp(a) if a.size else None for a in (g, gc, gh, gb, gG, gA)], _dp(res) if res.size else None)
+        self._call("adjoint_data", ptr, count, nrhs, *[_dp_or_null(a) for a in (g, gc, gh, gb, gG, gA, res)])
         return gc, gh, gb, gG, gA, res[:, :, 0]
 
     def matrix_map_count(self) -> int:
         """k the installed matrix map was validated for, 0 without one."""
-        return int(getattr(_lib(), self._prefix + "matrix_map_count")(self._h))
+        return self._query("matrix_map_count")
 
     def _theta_width(self):
         return max(self.param_count(), 0) or max(self.matrix_map_count(), 0)
@@ -1116,10 +1011,7 @@ class _Solver:
         An input that is None travels as a NULL pointer; lead: the arguments in front of `head` when they are not (ptr, count)."""
         if self._prefix != "eicos_batch_":
             raise ValueError(name + ": device=True needs a single-GPU handle")
-        hip = _lib()
-        hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        hip.hipFree.argtypes = [C.c_void_p]
+        hip = _lib()  # (the HIP runtime the library is linked against: hipMalloc, hipMemcpy, hipFree of the signature table)
         bufs = []
         try:
             for a in list(ins) + list(outs):
@@ -1149,7 +1041,7 @@ class _Solver:
         if device:
             self._device_form("param_jacobian_device", ptr, count, (), (), (J, res))
         else:
-            self._call("param_jacobian", ptr, count, _dp(J) if J.size else _dp(np.zeros(1)), _dp(res) if res.size else None)
+            self._call("param_jacobian", ptr, count, _dp_or_dummy(J), _dp_or_null(res))
         return J, res
 
     def param_gradient(self, g, idx=None, device=False):
@@ -1162,7 +1054,7 @@ class _Solver:
         if device:
             self._device_form("param_gradient_device", ptr, count, (nrhs,), (g,), (gt, res))
         else:
-            self._call("param_gradient", ptr, count, nrhs, _dp(g) if g.size else None, _dp(gt) if gt.size else _dp(np.zeros(1)), _dp(res) if res.size else None)
+            self._call("param_gradient", ptr, count, nrhs, _dp_or_null(g), _dp_or_dummy(gt), _dp_or_null(res))
         return gt, res
 
     def update_param_solve_subset(self, indices, theta, u_out=None, x_out=None):
@@ -1176,9 +1068,7 @@ class _Solver:
         _result_rows(u_out, count, self.output_count(), "u_out")
         _result_rows(x_out, count, self.pat.n, "x_out")
         codes = np.zeros(count, np.int32)
-        self._call("update_param_solve_subset", ptr, count, _dp(theta) if theta.size else _dp(np.zeros(1)),
-                   _dp(u_out) if (u_out is not None and u_out.size) else None, _dp(x_out) if (x_out is not None and x_out.size) else None,
-                   _ip(codes) if count else None)
+        self._call("update_param_solve_subset", ptr, count, _dp_or_dummy(theta), _dp_or_null(u_out), _dp_or_null(x_out), _ip(codes) if count else None)
         return codes
 
     def _theta_for(self, theta, count):
@@ -1205,13 +1095,10 @@ class _Solver:
         linsysacc, irerrfact, iter_max, nitref (ranges and semantics: eicos_settings of include/eicos_amd.h).  Fields that are not
         named keep their current value; the change takes effect from the next solve launch.  An unknown name raises TypeError before
         the library is called, a refused value RuntimeError with the handle's settings unchanged."""
-        unknown = sorted(set(fields) - set(SETTINGS_FIELDS))
-        if unknown:
-            raise TypeError(f"set_settings: unknown field(s) {', '.join(unknown)} (the settings are {', '.join(SETTINGS_FIELDS)})")
+        _known_settings("set_settings", fields)
         st = Settings()
         self._call("get_settings", C.byref(st))
-        for k, v in fields.items():
-            setattr(st, k, int(v) if k in ("iter_max", "nitref") else float(v))
+        _assign_settings(st, fields)
         self._call("set_settings", C.byref(st))
 
     def settings(self) -> dict:
@@ -1226,17 +1113,14 @@ class _Solver:
         attempt runs cold (warm = 0) or warm-started where its record allows it, under dyn = (delta, eps) and under the DEFAULT
         settings with the named fields changed (the names of set_settings).  mask None or 0 removes the policy.  An unknown field
         raises TypeError before the library is called, a refused value RuntimeError with the policy unchanged."""
-        unknown = sorted(set(settings_fields) - set(SETTINGS_FIELDS))
-        if unknown:
-            raise TypeError(f"set_retry: unknown field(s) {', '.join(unknown)} (the settings are {', '.join(SETTINGS_FIELDS)})")
+        _known_settings("set_retry", settings_fields)
         if not mask:
             self._call("set_retry", None)
             return
         r = Retry()
         _lib().eicos_retry_default(C.byref(r))
         r.mask, r.warm, r.dyn_delta, r.dyn_eps = int(mask), float(warm), float(dyn[0]), float(dyn[1])
-        for k, v in settings_fields.items():
-            setattr(r.settings, k, int(v) if k in ("iter_max", "nitref") else float(v))
+        _assign_settings(r.settings, settings_fields)
         self._call("set_retry", C.byref(r))
 
     def retry(self) -> dict:
@@ -1268,8 +1152,7 @@ class _Solver:
     def info_arrays(self):
         arr = (Info * self.batch)()
         self._call("info", arr)
-        raw = np.frombuffer(arr, dtype=np.dtype([(k, "f8" if t is C.c_double else "i4") for k, t in Info._fields_]))  # (declaration order)
-        return {k: raw[k].copy() for k in raw.dtype.names}
+        return _info_columns(arr, self.batch)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1308,69 +1191,69 @@ class BatchSolver(_Solver):
     def update_device(self, dG=0, dA=0, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
         """Raw device pointers (ints, e.g. torch.Tensor.data_ptr()); 0 keeps the group."""
         count = self.batch if count is None else count
-        self._call("update_device", first, count, *[C.c_void_p(int(p) or None) for p in (dG, dA, dc, dh, db)])
+        self._call("update_device", first, count, *_dev(dG, dA, dc, dh, db))
 
     def update_rhs_device(self, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
         """update_rhs from raw device pointers (ints); 0 keeps the group.  Asynchronous, like update_device."""
         count = self.batch if count is None else count
-        self._call("update_rhs_device", first, count, *[C.c_void_p(int(p) or None) for p in (dc, dh, db)])
+        self._call("update_rhs_device", first, count, *_dev(dc, dh, db))
 
     def update_param_device(self, dtheta, first: int = 0, count: int | None = None):
         """update_param from a raw device pointer (int) to theta [count, k].  Asynchronous, like update_rhs_device."""
         count = self.batch if count is None else count
-        self._call("update_param_device", first, count, C.c_void_p(int(dtheta) or None))
+        self._call("update_param_device", first, count, *_dev(dtheta))
 
     def set_iterate_device(self, dx=0, dy=0, dz=0, ds=0, first: int = 0, count: int | None = None):
         """set_iterate from raw device pointers (ints) to x [count, n], y [count, p], z, s [count, m]; 0 keeps the group.  Asynchronous on
         the handle's stream."""
         count = self.batch - first if count is None else count
-        self._call("set_iterate_device", first, count, *[C.c_void_p(int(p) or None) for p in (dx, dy, dz, ds)])
+        self._call("set_iterate_device", first, count, *_dev(dx, dy, dz, ds))
 
     def outputs_device(self, du, first: int = 0, count: int | None = None):
         """outputs() into a raw device pointer (int) to u [count, r].  Asynchronous on the handle's stream."""
         count = self.batch - first if count is None else count
-        self._call("outputs_device", first, count, C.c_void_p(int(du) or None))
+        self._call("outputs_device", first, count, *_dev(du))
 
     # ---- the indexed calls from raw device pointers (ints); `indices` stays a host list.  Asynchronous on the handle's stream ----
     def update_indexed_device(self, indices, dG=0, dA=0, dc=0, dh=0, db=0):
         idx, ptr = _index_rows(indices)
-        self._call("update_indexed_device", ptr, int(idx.size), *[C.c_void_p(int(p) or None) for p in (dG, dA, dc, dh, db)])
+        self._call("update_indexed_device", ptr, int(idx.size), *_dev(dG, dA, dc, dh, db))
 
     def update_rhs_indexed_device(self, indices, dc=0, dh=0, db=0):
         idx, ptr = _index_rows(indices)
-        self._call("update_rhs_indexed_device", ptr, int(idx.size), *[C.c_void_p(int(p) or None) for p in (dc, dh, db)])
+        self._call("update_rhs_indexed_device", ptr, int(idx.size), *_dev(dc, dh, db))
 
     def update_param_indexed_device(self, indices, dtheta):
         idx, ptr = _index_rows(indices)
-        self._call("update_param_indexed_device", ptr, int(idx.size), C.c_void_p(int(dtheta) or None))
+        self._call("update_param_indexed_device", ptr, int(idx.size), *_dev(dtheta))
 
     def set_iterate_indexed_device(self, indices, dx=0, dy=0, dz=0, ds=0):
         idx, ptr = _index_rows(indices)
-        self._call("set_iterate_indexed_device", ptr, int(idx.size), *[C.c_void_p(int(p) or None) for p in (dx, dy, dz, ds)])
+        self._call("set_iterate_indexed_device", ptr, int(idx.size), *_dev(dx, dy, dz, ds))
 
     def outputs_indexed_device(self, indices, du):
         """outputs_indexed() into a raw device pointer (int) to u [len(indices), r]."""
         idx, ptr = _index_rows(indices)
-        self._call("outputs_indexed_device", ptr, int(idx.size), C.c_void_p(int(du) or None))
+        self._call("outputs_indexed_device", ptr, int(idx.size), *_dev(du))
 
     def output_jacobian_device(self, dJ, dres=0, idx=None):
         """output_jacobian() into raw device pointers (int): J [count, r, k] and, optionally, res [count, r]; asynchronous (sync() waits)."""
         ptr, count = self._adjoint_rows(idx)
-        self._call("output_jacobian_device", ptr, count, C.c_void_p(int(dJ) or None), C.c_void_p(int(dres) or None))
+        self._call("output_jacobian_device", ptr, count, *_dev(dJ, dres))
 
     def param_jacobian_device(self, dJ, dres=0, idx=None):
         """param_jacobian() into raw device pointers (int): J [count, r, k] and, optionally, res [count, r]; asynchronous (sync() waits)."""
         ptr, count = self._adjoint_rows(idx)
-        self._call("param_jacobian_device", ptr, count, C.c_void_p(int(dJ) or None), C.c_void_p(int(dres) or None))
+        self._call("param_jacobian_device", ptr, count, *_dev(dJ, dres))
 
     def param_gradient_device(self, nrhs, dg, dgrad_theta, dres=0, idx=None):
         """param_gradient() on raw device pointers (int): g [count, nrhs, n] in, grad_theta [count, nrhs, k] and, optionally, res
         [count, nrhs] out; asynchronous on the handle's stream (sync() waits) -- what a training loop on the GPU calls."""
         ptr, count = self._adjoint_rows(idx)
-        self._call("param_gradient_device", ptr, count, int(nrhs), *[C.c_void_p(int(q) or None) for q in (dg, dgrad_theta, dres)])
+        self._call("param_gradient_device", ptr, count, int(nrhs), *_dev(dg, dgrad_theta, dres))
 
     def set_stream(self, stream_ptr: int):
-        self._call("set_stream", C.c_void_p(int(stream_ptr) or None))
+        self._call("set_stream", *_dev(stream_ptr))
 
     def info(self):
         arr = (Info * self.batch)()
@@ -1385,18 +1268,12 @@ class BatchSolver(_Solver):
     def kernel_build(self) -> str:
         """Which compilation of the solve kernel the handle launches: 'default', 'lds-resident', 'w2' (256 VGPRs, <= 2 workgroups per CU) or
         'u-in-lds' (one workgroup per CU, the factor operand array in LDS)."""
-        v = _lib().eicos_batch_kernel_build(self._h)
-        if v < 0:
-            _chk(v)
-        return ("default", "lds-resident", "w2", "u-in-lds")[v]
+        return ("default", "lds-resident", "w2", "u-in-lds")[_nonneg(_lib().eicos_batch_kernel_build(self._h))]
 
     def shared_values(self) -> bool:
         """True when the handle's last updateData found every instance's G and A bit-identical to instance 0's, so that the next solve's
         products stream one copy of the values (eicos_batch_shared_values); waits for the handle's stream."""
-        v = _lib().eicos_batch_shared_values(self._h)
-        if v < 0:
-            _chk(v)
-        return bool(v)
+        return bool(_nonneg(_lib().eicos_batch_shared_values(self._h)))
 
     def last_solve_ms(self) -> float:
         ms = C.c_float()
@@ -1415,14 +1292,12 @@ class BatchSolver(_Solver):
         if not hasattr(L, "eicos_batch_ms_history"):
             return None
         buf = (C.c_float * cap)()
-        n = L.eicos_batch_ms_history(self._h, {"solve": 0, "update": 1, "step": 2}[which], buf, cap)
-        if n < 0:
-            _chk(n)
+        n = _nonneg(L.eicos_batch_ms_history(self._h, {"solve": 0, "update": 1, "step": 2}[which], buf, cap))
         return [float(buf[i]) for i in range(n)]
 
     def last_rollout_launches(self) -> int:
         """Solve-kernel launches of the most recent rollout(): 1 = the steps ran inside one launch, `steps` = one launch per step."""
-        return int(_lib().eicos_batch_last_rollout_launches(self._h))
+        return self._query("last_rollout_launches")
 
     def last_update_path(self) -> str:
         """How the most recent host-pointer / peer updateData moved its inputs (UPDATE_PATHS)."""
@@ -1494,17 +1369,17 @@ class MultiBatchSolver(_Solver):
     def update_device(self, src_device: int, dG=0, dA=0, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
         """Raw pointers into the HBM of GPU `src_device` (arrays [count, ...]); 0 keeps the group."""
         count = self.batch if count is None else count
-        self._call("update_device", int(src_device), first, count, *[C.c_void_p(int(p) or None) for p in (dG, dA, dc, dh, db)])
+        self._call("update_device", int(src_device), first, count, *_dev(dG, dA, dc, dh, db))
 
     def update_rhs_device(self, src_device: int, dc=0, dh=0, db=0, first: int = 0, count: int | None = None):
         """update_rhs from raw pointers into the HBM of GPU `src_device` (arrays [count, ...]); 0 keeps the group.  Asynchronous."""
         count = self.batch if count is None else count
-        self._call("update_rhs_device", int(src_device), first, count, *[C.c_void_p(int(p) or None) for p in (dc, dh, db)])
+        self._call("update_rhs_device", int(src_device), first, count, *_dev(dc, dh, db))
 
     def update_param_device(self, src_device: int, dtheta, first: int = 0, count: int | None = None):
         """update_param from a raw pointer into the HBM of GPU `src_device` (theta [count, k], global instance order).  Asynchronous."""
         count = self.batch if count is None else count
-        self._call("update_param_device", int(src_device), first, count, C.c_void_p(int(dtheta) or None))
+        self._call("update_param_device", int(src_device), first, count, *_dev(dtheta))
 
     def shards(self):
         """[(first, count, device)] of every shard."""
@@ -1515,35 +1390,33 @@ class MultiBatchSolver(_Solver):
             out.append((f.value, c.value, d.value))
         return out
 
+    def _shard_handle(self, s, count=None):
+        """The eicos_batch handle of shard s (eicos_multi_shard); count: a c_int that receives the shard's instance count."""
+        hh = C.c_void_p()
+        _mchk(_lib().eicos_multi_shard(self._h, s, C.byref(hh), None, None if count is None else C.byref(count), None))
+        return hh
+
     def shard_update_device(self, s: int, dG=0, dA=0, dc=0, dh=0, db=0):
         """updateData of shard s from raw pointers into the HBM of THAT shard's GPU (arrays [count of the shard, ...]): inputs resident
         on every device -- no copy at all (eicos_batch_update_device on the shard's handle)."""
-        hh, c = C.c_void_p(), C.c_int()
-        _mchk(_lib().eicos_multi_shard(self._h, s, C.byref(hh), None, C.byref(c), None))
-        _chk(_lib().eicos_batch_update_device(hh, 0, c.value, *[C.c_void_p(int(p) or None) for p in (dG, dA, dc, dh, db)]))
+        c = C.c_int()
+        hh = self._shard_handle(s, c)
+        _chk(_lib().eicos_batch_update_device(hh, 0, c.value, *_dev(dG, dA, dc, dh, db)))
 
     def shard_last_update(self, s: int):
         """(path, HIP-event ms) of shard s's most recent updateData."""
-        hh = C.c_void_p()
-        _mchk(_lib().eicos_multi_shard(self._h, s, C.byref(hh), None, None, None))
+        hh = self._shard_handle(s)
         ms = C.c_float()
         _chk(_lib().eicos_batch_last_update_ms(hh, C.byref(ms)))
         return UPDATE_PATHS[_lib().eicos_batch_last_update_path(hh)], float(ms.value)
 
     def shard_shared_values(self, s: int) -> bool:
         """BatchSolver.shared_values of shard s: every shard compares with ITS first instance and reads its own reference."""
-        hh = C.c_void_p()
-        _mchk(_lib().eicos_multi_shard(self._h, s, C.byref(hh), None, None, None))
-        v = _lib().eicos_batch_shared_values(hh)
-        if v < 0:
-            _chk(v)
-        return bool(v)
+        return bool(_nonneg(_lib().eicos_batch_shared_values(self._shard_handle(s))))
 
     def shard_dims(self, s: int = 0) -> dict:
-        hh = C.c_void_p()
-        _mchk(_lib().eicos_multi_shard(self._h, s, C.byref(hh), None, None, None))
         d = Dims()
-        _chk(_lib().eicos_batch_dims(hh, C.byref(d)))
+        _chk(_lib().eicos_batch_dims(self._shard_handle(s), C.byref(d)))
         return d.asdict()
 
     def last_solve_ms(self):

@@ -27,6 +27,55 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), f"{s} declared in include/eicos_amd.h but not exported"
 
 
+def declared_prototypes():
+    """{name: (return type, [parameter types])} of every prototype of include/eicos_amd.h, as C text without `const`, parameter names
+    and spare blanks: "int", "double *", "eicos_batch * *", ..."""
+    text = open(os.path.join(ROOT, "include", "eicos_amd.h")).read()
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    text = re.sub(r"^[ \t]*#[^\n]*", ";", text, flags=re.M)  # (preprocessor lines: not part of a declaration)
+
+    def ctype_text(decl, named):
+        decl = re.sub(r"\bconst\b", " ", decl).replace("*", " * ").split()
+        return " ".join(decl[:-1] if named and decl[-1] != "*" else decl)
+
+    protos = {}
+    for ret, name, params in re.findall(r"([\w\s\*]*?)\b(eicos_[a-z_0-9]+)\s*\(([^();{}]*)\)\s*;", text):
+        assert name not in protos, name
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        protos[name] = (ctype_text(ret, False), [ctype_text(p, True) for p in params])
+    return protos
+
+
+def test_binding_prototypes_are_the_header():
+    """What eicos_amd.binding installs on the library is what include/eicos_amd.h declares: for EVERY declared function the argument
+    count, scalar against scalar ctype, pointer against pointer ctype (c_void_p passes for any pointer: raw device addresses), the
+    pointee of a typed pointer, and the return type; and the binding's table names no eicos_ function the header lacks."""
+    from eicos_amd import binding
+    lib = binding._lib()
+    scalars = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "double": ctypes.c_double, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+    structs = {"eicos_info": binding.Info, "eicos_dims": binding.Dims, "eicos_affine_map": binding.AffineMap,
+               "eicos_settings": binding.Settings, "eicos_retry": binding.Retry}
+    returns = dict(scalars, **{"char *": ctypes.c_char_p, "void *": ctypes.c_void_p, "void": None})
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols()  # (the parser found every declared function)
+    for name, (ret, params) in protos.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None, f"{name}: no argtypes installed"
+        assert len(fn.argtypes) == len(params), f"{name}: {len(fn.argtypes)} argtypes, the header has {len(params)} parameters"
+        assert ret in returns and fn.restype is returns[ret], f"{name}: restype {fn.restype}, the header returns {ret}"
+        for k, (param, ct) in enumerate(zip(params, fn.argtypes)):
+            where = f"{name}, argument {k}: header `{param}`, ctypes {ct.__name__}"
+            base, stars = param.split()[0], param.count("*")
+            if stars == 0:
+                assert param in scalars and ct is scalars[param], where
+            elif ct is not ctypes.c_void_p:
+                assert issubclass(ct, ctypes._Pointer), where
+                pointee = ctypes.c_void_p if stars == 2 else scalars.get(base) or structs.get(base)
+                assert stars <= 2 and pointee is not None and ct._type_ is pointee, where
+    listed = {full for full, _, _ in binding._SIGNATURES if full.startswith("eicos_")}
+    assert listed <= set(protos), f"in the binding's table but not in the header: {sorted(listed - set(protos))}"
+
+
 def test_cpp_header_compiles_against_c_header():
     # include/eicos.hpp (EiCOS::Solver wrapper) must at least parse with a host compiler
     import subprocess, tempfile
