@@ -2652,9 +2652,12 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void kkt_solve(i
                 // The stop test is an infinity norm: it cannot see the components of size W^2 (grad_c at a vertex), in which the removal
                 // of delta still converges geometrically when the norm is at rounding level already (lp_bandm, MPC02: the x part 2e-8
                 // off at the first error norm under the threshold, 1e-15 one step later).  So the adjoint solve takes ONE step beyond
-                // the threshold and keeps it whenever it stays under the threshold; every other rule is the solve's.
+                // the threshold and keeps it whenever it stays under the threshold -- or within irerrfact of the norm it had there: a norm
+                // that sits just under the threshold is at rounding level, the next one lands on either side of it, and undoing that step
+                // for its norm throws away what it did to the small components (a 390-row pattern with one cone of every class, cond 2.7e3:
+                // norms 8.7e-15 and then above 1e-14, grad_c 4.7e-6 off without the step and 4.4e-11 with it); every other rule is the solve's.
                 const bool below = nerr < thr[k], was_below = nerr_prev[k] < thr[k];
-                const bool worse = kcnt[k] > 0 && nerr > nerr_prev[k] && !below;
+                const bool worse = kcnt[k] > 0 && !below && (was_below ? nerr > irerrfact * nerr_prev[k] : nerr > nerr_prev[k]);
                 adj_err = worse ? nerr_prev[k] : nerr; // (an undone step: the kept iterate's error)
                 if (worse) { undo[k] = true; kcnt[k]--; rdone[k] = true; }
                 else if (kcnt[k] == nitref || (below && was_below) || (!below && kcnt[k] > 0 && nerr_prev[k] < irerrfact * nerr)) rdone[k] = true;
