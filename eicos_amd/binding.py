@@ -117,10 +117,11 @@ def _signatures():
         ("eicos_*_update_param", [vp, i, i, dp]), ("eicos_batch_update_param_device", [vp, i, i, vp]), ("eicos_multi_update_param_device", [vp, i, i, i, vp]),
         ("eicos_*_update_solve", [vp] + [dp] * 6 + [ip]), ("eicos_*_update_rhs_solve", [vp] + [dp] * 4 + [ip]), ("eicos_*_update_param_solve", [vp, dp, dp, dp, ip]),
         ("eicos_batch_shared_values", [vp]), ("eicos_batch_last_update_path", [vp]),
-        # the five maps
+        # the six maps
         ("eicos_*_set_param_map", [vp, i, mp, mp, mp]), ("eicos_*_param_count", [vp]), ("eicos_*_set_output_map", [vp, i, mp]), ("eicos_*_output_count", [vp]),
         ("eicos_*_set_plant_map", [vp, mp]), ("eicos_*_has_plant_map", [vp]), ("eicos_*_set_shift_map", [vp] + [mp] * 4), ("eicos_*_has_shift_map", [vp]),
         ("eicos_*_set_matrix_map", [vp, mp, mp]), ("eicos_*_has_matrix_map", [vp]), ("eicos_*_matrix_map_count", [vp]),
+        ("eicos_*_set_fallback_map", [vp, u, mp]), ("eicos_*_fallback_mask", [vp]), ("eicos_*_fallback_counts", [vp, i, i, ip, i]),
         # starting point, outputs, rollout
         ("eicos_*_set_iterate", [vp, i, i] + [dp] * 4), ("eicos_batch_set_iterate_device", [vp, i, i] + [vp] * 4),
         ("eicos_*_outputs", [vp, i, i, dp]), ("eicos_batch_outputs_device", [vp, i, i, vp]),
@@ -496,6 +497,48 @@ def _plant_map_ptr(fmap, k, r):
                        f"{k} rows over {k} parameters and {r} outputs", fmap.k == k and fmap.r == r)
 
 
+class FallbackMap:
+    """The backup output law of a closed loop, u = v0 + V theta: `v0` [r] and `V` = `(rowptr, col, val)`, a CSR matrix with r rows and k
+    columns, shared by all instances, with `mask`, an OR of SEL_* bits -- a step whose final record falls in one of these exit classes
+    takes its u row from this law instead of from the output map (eicos_batch_set_fallback_map).  evaluate() is the host restatement
+    of what such a step computes on the GPU, in the same rounding order."""
+
+    def __init__(self, v0, V, mask: int, k: int | None = None):
+        self.base, self.rowptr, self.col, self.val = _as_group((v0, *V))
+        self.r, self.mask = int(self.base.size), int(mask)
+        self.k = int(k) if k is not None else (int(self.col.max()) + 1 if self.col.size else 0)
+
+    def evaluate(self, theta):
+        """u [B, r] for theta [B, k]: row j is acc = v0[j], then acc = acc + (val[t] * theta[col[t]]) over the row's entries in stored
+        order, numpy float64 scalars throughout -- the product and the sum each rounded on their own."""
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != self.k:
+            raise ValueError(f"theta has shape {theta.shape}, expected [count, {self.k}]")
+        u = np.zeros((theta.shape[0], self.r))
+        for b in range(theta.shape[0]):
+            for j in range(self.r):
+                acc = self.base[j]
+                for t in range(int(self.rowptr[j]), int(self.rowptr[j + 1])):
+                    acc = acc + (self.val[t] * theta[b, self.col[t]])
+                u[b, j] = acc
+        return u
+
+    def dense(self, k: int | None = None):
+        """V as the dense [r, k] block a fired step of rollout_jacobian records: zero-filled, then J[j, col[t]] = J[j, col[t]] + val[t]
+        in stored order (duplicates of a column accumulate in that order)."""
+        J = np.zeros((self.r, self.k if k is None else int(k)))
+        for j in range(self.r):
+            for t in range(int(self.rowptr[j]), int(self.rowptr[j + 1])):
+                J[j, self.col[t]] = J[j, self.col[t]] + self.val[t]
+        return J
+
+
+def _fallback_map_ptr(fmap, k, r):
+    """A FallbackMap as (keep-alive objects, C pointer to eicos_affine_map) for a handle with k parameters and r outputs."""
+    return _affine_ptr((fmap.base, fmap.rowptr, fmap.col, fmap.val), r, f"fallback map: r = {fmap.r}, ",
+                       f"{r} rows over {k} parameters", fmap.r == r)
+
+
 class MatrixMap:
     """The stored values of G and A affine in the parameter row theta of length k: Gpr = G0 + Gm theta, Apr = A0 + Am theta.  Per matrix
     `(base, rowptr, col, val)` -- base[nnz] and a CSR matrix with one row per stored value (CSC order of Gpr / Apr) and k columns -- or
@@ -752,6 +795,32 @@ class _Solver:
 
     def has_plant_map(self) -> bool:
         return bool(self._query("has_plant_map"))
+
+    # ---- fallback map: the backup output law of steps that do not end well (include/eicos_amd.h: eicos_batch_set_fallback_map) ----
+    def set_fallback_map(self, fmap: "FallbackMap | None"):
+        """Install (copy) a FallbackMap for all instances, behind the parameter and the output map it refers to; None, or a map with
+        mask 0, removes it.  From then on update_param_solve, update_param_solve_subset, rollout and rollout_jacobian form the u row of
+        an instance whose final record is in a class of the mask as fmap.evaluate(theta); everything else they return is unchanged."""
+        if fmap is None or not fmap.mask:
+            self._call("set_fallback_map", 0, None)
+            return
+        k, r = self.param_count(), self.output_count()
+        if k > 0 and r > 0:
+            _keep, ptr = _fallback_map_ptr(fmap, k, r)
+        else:  # (the library refuses: "no parameter map" / "no output map")
+            _keep, ptr = _fallback_map_ptr(fmap, k, fmap.r)
+        self._call("set_fallback_map", fmap.mask, ptr)
+
+    def fallback_mask(self) -> int:
+        """The mask of the installed fallback map, 0 without one."""
+        return _nonneg(self._query("fallback_mask"))
+
+    def fallback_counts(self, reset: bool = False):
+        """Per instance the steps whose u row the fallback law has formed since its counter was last zeroed (cumulative: after a
+        rollout, its fired steps); reset=True zeroes the counters after reading them."""
+        out = np.zeros(self.batch, np.int32)
+        self._call("fallback_counts", 0, self.batch, _ip(out), 1 if reset else 0)
+        return out
 
     # ---- matrix map: G and A affine in theta (include/eicos_amd.h: eicos_batch_set_matrix_map) ----
     def set_matrix_map(self, mmap: "MatrixMap | None"):

@@ -1,4 +1,4 @@
-// Affine maps on the host, one path for all of them (parameter, output, plant, matrix and shift map): every map is a handful of groups
+// Affine maps on the host, one path for all of them (parameter, output, plant, matrix, shift and fallback map): every map is a handful of groups
 // "base vector + CSR matrix" (eicos_affine_map) that is validated by affine_fault and packed by affine_pack into ONE device allocation
 //     [header | gap | base, val of every present group (doubles) | rowptr, col of every present group (ints)]
 // whose header takes the map's descriptor.  Host only: no HIP, so that the sanitizer check under tests/host compiles it on its own.

@@ -160,7 +160,11 @@ struct eicos_batch {
     // and kept; retry = the host copy of the record (its source for the copy on the handle's stream), retry.mask = 0 while no policy is
     // installed -- then no launch carries the record's address (UpdArgs::retry)
     RetryDev retry{0u, 0., 0., 0., solve_cfg_default(), nullptr}; DevBuf d_retry;
-    TilePlan tiles;       // tile mode (Symbolic::tile): the dense-front plan
+    // fallback map (eicos_batch_set_fallback_map): one device allocation [FallbackDev (MAP_HEADER bytes) | counts [batch] | base, val |
+    // rowptr, col], fb.mask = 0 while none is installed -- then no launch carries the record's address (UpdArgs::fb); d_fb_theta = the
+    // [batch][k] device copy of a step's pageable theta rows, which the range kernel reads behind a step that is not fused
+    FallbackDev fb{}; DevBuf d_fb, d_fb_theta;
+    TilePlan tiles;      // tile mode (Symbolic::tile): the dense-front plan
     // Shared product values (eicos_batch_shared_values): ONE device word.  -1: every instance streams the product values of
     // its own slab.  0: the last writer of matrix values was a full updateData over [0, batch) from arrays the GPU addresses, and its
     // kernel found every row of Gpr / Apr bit-identical to row 0 -- the solve's products then all stream instance 0's copies.  ONE place
@@ -182,7 +186,7 @@ struct eicos_batch {
     // grown on demand: [AdjointDev of the fused launch (MAP_HEADER bytes) | J trajectory [batch][steps][r][k] | res trajectory
     // [batch][steps][r] | one step's J and res rows of the batch (the path that is not fused)]; d_rollG = [gu | gtheta | grad_theta0 |
     // grad_w] of the gradient call's host form.  rollJ_steps = 0: no trajectory on the handle; rollJ_plant, rollJ_k / _r = the plant map and counts it was
-    // recorded under; map_gen counts the installs of the parameter, matrix, output and plant maps, rollJ_gen = its value at that rollout.
+    // recorded under; map_gen counts the installs of the parameter, matrix, output, plant and fallback maps, rollJ_gen = its value at that rollout.
     DevBuf d_rollJ, d_rollG; int rollJ_steps = 0, rollJ_k = 0, rollJ_r = 0; PlantMapDev rollJ_plant{}; unsigned long map_gen = 0, rollJ_gen = 0;
     hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr; bool adjoint_timed = false; // HIP events around the most recent adjoint launch (eicos_batch_last_adjoint_ms)
 
@@ -362,13 +366,14 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
     return EICOS_OK;
 }
 
-// ---- affine maps (no reference counterpart): parameter, output, plant, matrix and shift map through one path ----
+// ---- affine maps (no reference counterpart): parameter, output, plant, matrix, shift and fallback map through one path ----
 // A setter states its own preconditions and its groups (affine_pack.hpp: AffineGroup); affine_fault validates a group, install_map packs
 // the groups into ONE device allocation [descriptor (MAP_HEADER bytes) | gap | base, val per group | rowptr, col per group] and swaps it
 // for the one in the handle.  A later call replaces a map; DESIGN.md, "Affine maps: one path".
 static constexpr size_t MAP_HEADER = 128; // bytes kept for the descriptor in front of a map's arrays (keeps the doubles aligned)
 static_assert(sizeof(ParamMapDev) <= MAP_HEADER && sizeof(OutMapDev) <= MAP_HEADER && sizeof(PlantMapDev) <= MAP_HEADER &&
-              sizeof(RolloutDev) <= MAP_HEADER && sizeof(MatrixMapDev) <= MAP_HEADER && sizeof(ShiftMapDev) <= MAP_HEADER,
+              sizeof(RolloutDev) <= MAP_HEADER && sizeof(MatrixMapDev) <= MAP_HEADER && sizeof(ShiftMapDev) <= MAP_HEADER &&
+              sizeof(FallbackDev) <= MAP_HEADER,
               "map descriptor larger than its header");
 
 // The map in `slot` (its device allocation) and `cur` (the handle's copy of its descriptor) goes away; M != NULL: the n validated groups
@@ -1219,14 +1224,40 @@ static int take_output_range(eicos_batch *h, int first, int count, const double 
     return EICOS_OK;
 }
 
+// ---- fallback map (eicos_batch_set_fallback_map, with the plant map below): what the steps that hold theta need of it ----
+// Every such step checks the map against the maps installed NOW: the parameter or the output map may have been replaced
+static int fallback_fits(const eicos_batch *h) {
+    if (h->fb.mask == 0 || (h->fb.k == h->param.k && h->fb.r == h->out.r)) return EICOS_OK;
+    return fail(EICOS_E_INVALID, "fallback map: installed for (k, r) = (" + std::to_string(h->fb.k) + ", " + std::to_string(h->fb.r) +
+                                     "), the maps now installed have (" + std::to_string(h->param.k) + ", " + std::to_string(h->out.r) + "): install it again");
+}
+// The theta rows [count][k] of a step that is not fused, where launch_fallback can read them: pinned and device memory as it is,
+// pageable memory through the handle's device copy (on the handle's stream; the step waits for the stream before it returns)
+static int fallback_theta(eicos_batch *h, const double *theta, MemKind kind, int count, const double *&out) {
+    out = theta;
+    if (kind != MEM_PAGEABLE) return EICOS_OK;
+    const size_t bytes = (size_t)count * h->fb.k * sizeof(double);
+    HIP_TRY_AS("hipMalloc", h->d_fb_theta.reserve(bytes, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_fb_theta.p, theta, bytes, hipMemcpyHostToDevice, h->stream));
+    out = h->d_fb_theta.as<const double>();
+    return EICOS_OK;
+}
+
 // the output rows of instances [first, first + count) into `u` [count][r], wherever it lives: device memory is written by the range kernel
 // itself (asynchronous), host memory gets the handle's rows d_u over the paths of fetch_strided (synchronous)
 // list != NULL (device memory, `count` ids): row q is the output row of instance list[q] and `first` is unused
-static int outputs_to(eicos_batch *h, int first, int count, double *u, MemKind kind, const int *list = nullptr) {
+// fb_theta != NULL (a step under a fallback map whose launch did not write these rows): theta [count][k] the GPU addresses, row q beside
+// row q of u -- the fallback kernel follows the output kernel on the same rows (launch.hpp: launch_fallback)
+static int outputs_to(eicos_batch *h, int first, int count, double *u, MemKind kind, const int *list = nullptr, const double *fb_theta = nullptr) {
     if (count == 0) return EICOS_OK;
-    if (kind == MEM_DEVICE) { HIP_TRY(launch_outputs(h->pslot, h->inst(), first, count, h->out, u, h->stream, list)); return EICOS_OK; }
+    if (kind == MEM_DEVICE) {
+        HIP_TRY(launch_outputs(h->pslot, h->inst(), first, count, h->out, u, h->stream, list));
+        if (fb_theta) HIP_TRY(launch_fallback(h->pslot, h->inst(), first, count, h->fb, fb_theta, u, h->stream, list));
+        return EICOS_OK;
+    }
     double *rows = h->d_u + (list ? 0 : (size_t)first * h->out.r);
     HIP_TRY(launch_outputs(h->pslot, h->inst(), first, count, h->out, rows, h->stream, list));
+    if (fb_theta) HIP_TRY(launch_fallback(h->pslot, h->inst(), first, count, h->fb, fb_theta, rows, h->stream, list));
     const int rc = fetch_strided(h, u, rows, (size_t)h->out.r * sizeof(double), h->out.r, count);
     if (rc != EICOS_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1512,7 +1543,9 @@ static int grow_staging(eicos_batch *h, size_t doubles, int nchunks) {
     return EICOS_OK;
 }
 // x_out [batch][n], u_out [batch][r] (NULL: not asked for) behind a finished solve, by kind of memory unless the kernel wrote it; complete on return
-static int deliver_results(eicos_batch *h, double *x_out, MemKind x_kind, bool x_written, double *u_out, MemKind u_kind, bool u_written) {
+// fb_theta (outputs_to): the step's theta rows when a fallback map applies to u rows the kernel did not write
+static int deliver_results(eicos_batch *h, double *x_out, MemKind x_kind, bool x_written, double *u_out, MemKind u_kind, bool u_written,
+                           const double *fb_theta = nullptr) {
     const DevPat &D = h->dp;
     if (x_out && !x_written) {
         if (x_kind == MEM_DEVICE) { // a result array in device memory: one strided copy on the device
@@ -1522,7 +1555,7 @@ static int deliver_results(eicos_batch *h, double *x_out, MemKind x_kind, bool x
         } else { const int rc = fetch_rows(h, x_out, D.i_x, D.n); if (rc != EICOS_OK) return rc; }
     }
     if (u_out && !u_written) {
-        const int rc = outputs_to(h, 0, h->batch, u_out, u_kind);
+        const int rc = outputs_to(h, 0, h->batch, u_out, u_kind, nullptr, fb_theta);
         if (rc != EICOS_OK) return rc;
         if (u_kind == MEM_DEVICE) HIP_TRY(hipStreamSynchronize(h->stream)); // (the range kernel writes device memory asynchronously)
     }
@@ -1555,6 +1588,10 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
     int rc = param ? take_theta(in, h, 0, h ? h->batch : 0, theta, true) : take_inputs(in, h, 0, h ? h->batch : 0, G, A, c, hh, b, rhs, true);
     if (rc != EICOS_OK) return rc;
     if (u_out && h->out.r == 0) return fail(EICOS_E_INVALID, "no output map (eicos_batch_set_output_map installs one)");
+    if (param && (rc = fallback_fits(h)) != EICOS_OK) return rc;
+    // the fallback map (eicos_batch_set_fallback_map) applies to the u rows of a parametric step: formed by the kernel that writes them, or
+    // by the range kernel behind the output kernel (deliver_results)
+    const bool fb_on = param && u_out && h->fb.mask != 0;
     const DevPat &D = h->dp;
     // arrays the GPU cannot address (pageable memory) are STAGED: copied into the handle's pinned staging buffer while the kernel runs
     const bool any_staged = in.any(MEM_PAGEABLE);
@@ -1570,10 +1607,12 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
     // slow that copy further; EICOS_FUSED_STAGED=1 under EICOS_EXPERIMENT=1 turns it on: docs/HISTORY.md A.11 item 9)
     if (!fused || (any_staged && (param || !env_knob("EICOS_FUSED_STAGED", 0, 0, 1)))) {
         // ---- separate launches (device arrays on a handle without the fused path: the device-pointer updateData)
-        rc = in.all(MEM_DEVICE) ? update_in_place(in, 0) : staged_update(in, -1);
+        const double *fb_theta = nullptr;
+        rc = fb_on ? fallback_theta(h, in.src[2], in.kind[2], h->batch, fb_theta) : EICOS_OK;
+        if (rc == EICOS_OK) rc = in.all(MEM_DEVICE) ? update_in_place(in, 0) : staged_update(in, -1);
         if (rc == EICOS_OK) rc = enqueue_solve(h, nullptr);
         if (rc == EICOS_OK) rc = eicos_batch_sync(h);
-        if (rc == EICOS_OK) rc = deliver_results(h, x_out, x_kind, false, u_out, u_kind, false);
+        if (rc == EICOS_OK) rc = deliver_results(h, x_out, x_kind, false, u_out, u_kind, false, fb_theta);
         return rc != EICOS_OK ? rc : exit_codes(h, exitcodes);
     }
     // ---- one launch: the kernel reads the arrays and writes the outputs it can address
@@ -1606,6 +1645,7 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
     step.flags = any_staged ? h->stage_flags.as<unsigned>() : nullptr; step.chunk = chunk; step.seq = h->stage_seq; step.err = h->d_err.as<int>();
     step.pmap = h->d_param.as<const ParamMapDev>(); step.omap = h->d_out.as<const OutMapDev>();
     if (param && h->mat.k) step.mmap = h->d_mat.as<const MatrixMapDev>();
+    if (fb_on && u_written) step.fb = h->d_fb.as<const FallbackDev>();
     rc = enqueue_solve(h, &step);
     if (rc != EICOS_OK) return rc; // (nothing was launched: no workgroup waits for a flag)
     if (any_staged) { // the kernel is running: copy chunk by chunk and release each chunk's flag behind its rows
@@ -1623,7 +1663,8 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
         HIP_TRY(hipMemcpy(&err, h->d_err.p, sizeof(int), hipMemcpyDeviceToHost));
         if (err) { HIP_TRY(hipMemset(h->d_err.p, 0, sizeof(int))); return fail(EICOS_E_HIP, "fused updateData: a workgroup timed out waiting for its staged rows"); }
     }
-    rc = deliver_results(h, x_out, x_kind, x_written, u_out, u_kind, u_written);
+    // (a fused parametric step never stages theta: the range kernel reads the rows the launch read)
+    rc = deliver_results(h, x_out, x_kind, x_written, u_out, u_kind, u_written, fb_on && !u_written ? ptr[2] : nullptr);
     return rc != EICOS_OK ? rc : exit_codes(h, exitcodes);
 }
 
@@ -1923,8 +1964,12 @@ int eicos_batch_update_param_solve_subset(eicos_batch *h, const int *idx, int co
     const MemKind x_kind = memory_kind(x_out, (size_t)count * D.n * sizeof(double));
     const MemKind u_kind = memory_kind(u_out, (size_t)count * h->out.r * sizeof(double));
     const bool fused = fused_param_fits(fit_shape(h), h->param.k, h->mat.k != 0) && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1) && !in.any(MEM_PAGEABLE);
+    if ((rc = fallback_fits(h)) != EICOS_OK) return rc;
+    const bool fb_on = u_out && h->fb.mask != 0; // (eicos_batch_set_fallback_map: the rows of theta and u are in list order alike)
+    const double *fb_theta = nullptr;
     bool x_written = false, u_written = false;
     if (!fused) { // the update on its own, then the subset launch
+        if (fb_on && (rc = fallback_theta(h, in.src[2], in.kind[2], count, fb_theta)) != EICOS_OK) return rc;
         rc = ids_to_device(in, idx);
         if (rc == EICOS_OK) rc = in.all(MEM_DEVICE) ? update_in_place(in, 0) : staged_update(in, -1);
         if (rc == EICOS_OK) rc = upload_ids(h, idx, count, subset_ids(h));
@@ -1939,13 +1984,15 @@ int eicos_batch_update_param_solve_subset(eicos_batch *h, const int *idx, int co
         step.x = x_written ? x_out : nullptr; step.u = u_written ? u_out : nullptr;
         step.pmap = h->d_param.as<const ParamMapDev>(); step.omap = h->d_out.as<const OutMapDev>();
         if (h->mat.k) step.mmap = h->d_mat.as<const MatrixMapDev>();
+        if (fb_on && u_written) step.fb = h->d_fb.as<const FallbackDev>();
+        else if (fb_on) fb_theta = in.src[2]; // (memory the GPU addresses: the launch reads it too)
         rc = enqueue_solve(h, &step, count);
     }
     if (rc == EICOS_OK) rc = eicos_batch_sync(h);
     if (rc != EICOS_OK) return rc;
     // ---- the rows the kernel did not write, and the exit codes (deliver_results for a subset)
     if (u_out && !u_written) {
-        rc = outputs_to(h, 0, count, u_out, u_kind, subset_ids(h));
+        rc = outputs_to(h, 0, count, u_out, u_kind, subset_ids(h), fb_theta);
         if (rc != EICOS_OK) return rc;
         if (u_kind == MEM_DEVICE) HIP_TRY(hipStreamSynchronize(h->stream));
     }
@@ -1973,6 +2020,52 @@ int eicos_batch_set_plant_map(eicos_batch *h, const eicos_affine_map *f) {
     PlantMapDev M{};
     M.k = k; M.r = r;
     return install_map(h, h->d_plant, h->plant, "plant", &g, 1, 0, f ? &M : nullptr, &M.a);
+}
+
+// ---- fallback map: the backup output law u = v0 + V theta of steps whose solve ends in a class of the mask (launch.hpp: FallbackDev) ----
+// The sixth map of install_map.  The counters sit in the gap between the descriptor and the arrays, so a map that is installed again
+// starts them at zero.  Range kernels take the descriptor by value, the fused launches through a pointer (UpdArgs::fb).
+static size_t fallback_counts_bytes(const eicos_batch *h) { return ((size_t)h->batch * sizeof(int) + 63) & ~(size_t)63; }
+int eicos_batch_set_fallback_map(eicos_batch *h, unsigned mask, const eicos_affine_map *v) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    const int k = h->param.k, r = h->out.r;
+    const AffineGroup g = {v, r, k, "fallback map: ", "[0, k)"};
+    const bool remove = !v || mask == 0;
+    std::string msg;
+    if (!remove) {
+        if (mask & ~(unsigned)EICOS_SEL_ALL) return fail(EICOS_E_INVALID, g.who + "mask has bits above bit 11 (EICOS_SEL_UNSOLVED)");
+        // (beside other classes the bit is idle and accepted, as in a retry policy: EICOS_SEL_NOT_OPTIMAL holds it)
+        if (mask == EICOS_SEL_UNSOLVED) return fail(EICOS_E_INVALID, g.who + "mask is EICOS_SEL_UNSOLVED alone, and an attempted instance is never in that class");
+        if (k == 0) return fail(EICOS_E_INVALID, g.who + "no parameter map (eicos_batch_set_param_map installs one)");
+        if (r == 0) return fail(EICOS_E_INVALID, g.who + "no output map (eicos_batch_set_output_map installs one)");
+        if (affine_fault(g, msg)) return fail(EICOS_E_INVALID, msg);
+    }
+    FallbackDev M{};
+    M.mask = mask; M.k = k; M.r = r;
+    const int rc = install_map(h, h->d_fb, h->fb, "fallback", &g, 1, fallback_counts_bytes(h), remove ? nullptr : &M, &M.a);
+    if (rc != EICOS_OK || remove) return rc;
+    // the counters: zeroed, and their address into the descriptor on both sides
+    h->fb.counts = reinterpret_cast<int *>(h->d_fb.as<char>() + MAP_HEADER);
+    hipError_t e = hipMemset(h->fb.counts, 0, fallback_counts_bytes(h));
+    if (e == hipSuccess) e = hipMemcpy(h->d_fb.p, &h->fb, sizeof(FallbackDev), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { h->d_fb.reset(); h->fb = FallbackDev{}; return fail(EICOS_E_HIP, std::string("fallback map: ") + hipGetErrorString(e)); }
+    return EICOS_OK;
+}
+int eicos_batch_fallback_mask(eicos_batch *h) { return h ? (int)h->fb.mask : fail(EICOS_E_INVALID, "NULL handle"); }
+int eicos_batch_fallback_counts(eicos_batch *h, int first, int count, int *fired, int reset) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (first < 0 || count < 0 || first > h->batch - count) return fail(EICOS_E_INVALID, "fallback counts: instance range out of bounds");
+    if (count > 0 && !fired) return fail(EICOS_E_INVALID, "fallback counts: fired is NULL");
+    if (count == 0) return EICOS_OK;
+    if (!h->d_fb) { std::fill(fired, fired + count, 0); return EICOS_OK; } // (no map: nothing has fired since it was installed)
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(fired, h->fb.counts + first, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    if (reset) {
+        HIP_TRY(hipMemsetAsync(h->fb.counts + first, 0, (size_t)count * sizeof(int), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return EICOS_OK;
 }
 
 // ---- matrix map: the stored values of G and A affine in theta ----
@@ -2051,6 +2144,7 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
         return fail(EICOS_E_INVALID, "rollout: the plant map was installed for (k, r) = (" + std::to_string(h->plant.k) + ", " + std::to_string(h->plant.r) +
                                          "), the maps now installed have (" + std::to_string(k) + ", " + std::to_string(r) + "): install it again");
     { const int rc = matrix_map_fits(h); if (rc != EICOS_OK) return rc; }
+    { const int rc = fallback_fits(h); if (rc != EICOS_OK) return rc; }
     if (!theta0) return fail(EICOS_E_INVALID, "rollout: theta0 is NULL");
     if (!u_traj) return fail(EICOS_E_INVALID, "rollout: u_traj is NULL");
     if (sens && !J_traj) return fail(EICOS_E_INVALID, "rollout_jacobian: J_traj is NULL");
@@ -2082,6 +2176,7 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
         step.on = UPD_ROLL; step.roll = h->d_roll.as<const RolloutDev>();
         step.pmap = h->d_param.as<const ParamMapDev>(); step.omap = h->d_out.as<const OutMapDev>();
         if (h->mat.k) step.mmap = h->d_mat.as<const MatrixMapDev>();
+        if (h->fb.mask) step.fb = h->d_fb.as<const FallbackDev>(); // (every step's u row, and with sens its J and res rows: kernels.hip, rollout_record)
         if (sens) { // the record of the launch's adjoints (launch.hpp: AdjointDev, the contracted form with the output map's rows), as adjoint_run fills it
             AdjointDev rec{};
             rec.pmap = h->d_param.as<const ParamMapDev>(); rec.mmap = h->mat.k ? h->d_mat.as<const MatrixMapDev>() : nullptr;
@@ -2101,9 +2196,11 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
             if (rc == EICOS_OK) rc = enqueue_solve(h, nullptr);
             if (rc != EICOS_OK) return rc;
             HIP_TRY(launch_outputs(h->pslot, h->inst(), 0, h->batch, h->out, h->d_u, h->stream));
+            if (h->fb.mask) HIP_TRY(launch_fallback(h->pslot, h->inst(), 0, h->batch, h->fb, cur, h->d_u, h->stream));
             if (sens) {
                 rc = param_contracted(h, nullptr, h->batch, 0, nullptr, false, d_J1, "J", d_res1, true, "eicos_batch_rollout_jacobian");
                 if (rc != EICOS_OK) return rc;
+                if (h->fb.mask) HIP_TRY(launch_fallback_jacobian(h->pslot, h->inst(), 0, h->batch, h->fb, d_J1, d_res1, h->stream));
                 const size_t jb = (size_t)r * k * sizeof(double), rb = (size_t)r * sizeof(double);
                 HIP_TRY(hipMemcpy2DAsync(d_J + (size_t)t * r * k, T * jb, d_J1, jb, jb, B, hipMemcpyDeviceToDevice, h->stream));
                 HIP_TRY(hipMemcpy2DAsync(d_res + (size_t)t * r, T * rb, d_res1, rb, rb, B, hipMemcpyDeviceToDevice, h->stream));
@@ -2140,7 +2237,7 @@ static int rollout_gradient(eicos_batch *h, const double *gu, const double *gthe
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     const std::string w(who);
     if (h->rollJ_steps == 0) return fail(EICOS_E_INVALID, w + ": the handle holds no Jacobian trajectory (eicos_batch_rollout_jacobian records one)");
-    if (h->rollJ_gen != h->map_gen) return fail(EICOS_E_INVALID, w + ": a parameter, matrix, output or plant map was installed after the rollout whose Jacobians the handle holds: run eicos_batch_rollout_jacobian again");
+    if (h->rollJ_gen != h->map_gen) return fail(EICOS_E_INVALID, w + ": a parameter, matrix, output, plant or fallback map was installed after the rollout whose Jacobians the handle holds: run eicos_batch_rollout_jacobian again");
     if (!gu && !gtheta) return fail(EICOS_E_INVALID, w + ": gu and gtheta are both NULL");
     if (!grad_theta0) return fail(EICOS_E_INVALID, w + ": grad_theta0 is NULL");
     const char *other = device ? " must live in device memory (the form without _device takes host pointers)" : " lives in device memory: this form takes host pointers (use the _device form)";

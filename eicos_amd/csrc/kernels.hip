@@ -3485,6 +3485,47 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void outputs_ins
     FOR_T(row, r) u[q * (size_t)r + row] = affine_row(A, row, x);
 }
 
+// The fallback map of one instance by one workgroup (k_solve and k_roll_sens, right behind outputs_instance on the same u row; launch.hpp:
+// FallbackDev).  The verdict is the exit class of the instance's FINAL record against the map's mask: the record is read where
+// rollout_record reads it, in the slab instance_end wrote it to in front of solve_instance's last barrier -- in the LDS-resident build
+// the LDS copy, which is current before and after the write-back.  Every thread takes the verdict from the same two words, so it is
+// uniform without a barrier of its own.  Fired: thread 0 bumps the instance's counter (a plain store: this workgroup owns the instance)
+// and the threads run over the r rows, u[row] = base[row] + sum val * theta[col] in stored order, product and sum rounded on their own,
+// each thread overwriting the entries outputs_instance had it store.  The theta row -- row list_row(q) of `theta`, the POSITION in the
+// caller's list in a step over a subset; a rollout passes q = 0 with its own row pointers -- is read from global memory: k numbers,
+// written by this workgroup behind a barrier (a rollout) or by the caller.  Returns 1 when the law fired, the same value in every thread.
+// Out of line: a launch without a map pays the pointer test of the call site and nothing else.
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) int fallback_instance(int ps, gcdbl_p I, int id, size_t q, const FallbackDev *Fp,
+                                                                                      const double *theta, double *u) {
+    ps = uni(ps); I = uni_ptr(I); id = uni(id); Fp = uni_ptr(Fp); theta = uni_ptr(theta); u = uni_ptr(u); q = list_row(q);
+    const DevInfo EICOS_DATA *di = reinterpret_cast<const DevInfo EICOS_DATA *>(I + c_pat[ps].i_info);
+    const int fired = uni((int)((exit_class(di->exitcode, di->n_factor) & Fp->mask) != 0));
+    if (!fired) return 0;
+    const int k = Fp->k, r = Fp->r;
+    const AffineDev A = Fp->a;
+    const double *th = theta + q * (size_t)k;
+    if (threadIdx.x == 0) Fp->counts[id] = Fp->counts[id] + 1;
+    FOR_T(row, r) u[q * (size_t)r + row] = affine_row(A, row, th);
+    return 1;
+}
+// J_t of a step whose fallback fired (k_roll_sens, in the place of adjoint_instance): row `row` of the record's J [..][r][k] and res [..][r]
+// arrays = V as a dense block -- every row zero-filled, then J[j][col[t]] = J[j][col[t]] + val[t] in stored order -- and 0.0.
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void fallback_jacobian_instance(const FallbackDev *Fp, const AdjointDev *Ap, int row) {
+    Fp = uni_ptr(Fp); Ap = uni_ptr(Ap); row = uni(row);
+    const int k = Fp->k, r = Fp->r;
+    const AffineDev A = Fp->a;
+    double *J = Ap->J + (size_t)row * r * k, *res = Ap->res ? Ap->res + (size_t)row * r : nullptr;
+    FOR_T(j, r) {
+        double *Jr = J + (size_t)j * k;
+        for (int c = 0; c < k; c++) Jr[c] = 0.;
+        const int t1 = A.rowptr[j + 1];
+        for (int t = A.rowptr[j]; t < t1; t++) Jr[A.col[t]] = __dadd_rn(Jr[A.col[t]], A.val[t]);
+        if (res) res[j] = 0.;
+    }
+}
+
 // The plant map of one instance by one workgroup (k_solve, a rollout: after outputs_instance and the record of step t): row t + 1 of the
 // instance's theta trajectory = base + F z (+ w), z = [theta row t | u row t].  Both rows were written by THIS workgroup a moment ago
 // (the u row by outputs_instance, the theta row by the previous step), so they are read with ordinary global loads behind a barrier and
@@ -3524,14 +3565,19 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_par
     else param_instance<T>(ps, I, 0, g_S.pmap, row);
 }
 // (the two halves of a step, shared with k_roll_sens, which runs adjoint_instance between them: rollout_sens_step, below)
+// fb (UpdArgs::fb, NULL: none): the fallback map overwrites the u row of a step whose final record is in its mask, from row t of the
+// instance's theta trajectory, before the plant map reads the row.  Returns 1 when it fired (uniform).
 template <int T>
-__device__ __forceinline__ void rollout_record(int ps, gcdbl_p I, const RolloutDev *Rp, int id, int t, int steps) {
+__device__ __forceinline__ int rollout_record(int ps, gcdbl_p I, const RolloutDev *Rp, int id, int t, int steps, const FallbackDev *fb) {
     const size_t at = (size_t)id * steps + t;
     outputs_instance<T>(ps, I, 0, g_S.omap, Rp->u + at * Rp->plant.r);
+    int fired = 0;
+    if (fb) fired = fallback_instance<T>(ps, I, id, 0, fb, Rp->theta + (at + id) * Rp->plant.k, Rp->u + at * Rp->plant.r);
     if (threadIdx.x == 0) {
         const DevInfo EICOS_DATA *di = reinterpret_cast<const DevInfo EICOS_DATA *>(I + c_pat[ps].i_info);
         Rp->codes[at] = di->exitcode; Rp->iters[at] = di->iter;
     }
+    return fired;
 }
 template <int T>
 __device__ __forceinline__ void rollout_advance(const RolloutDev *Rp, int id, int t, int steps) {
@@ -3543,11 +3589,11 @@ __device__ __forceinline__ void rollout_advance(const RolloutDev *Rp, int id, in
     }
 }
 template <int T>
-static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_step(int ps, gcdbl_p I, int id) {
-    ps = uni(ps); I = uni_ptr(I); id = uni(id);
+static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_step(int ps, gcdbl_p I, int id, const FallbackDev *fb) {
+    ps = uni(ps); I = uni_ptr(I); id = uni(id); fb = uni_ptr(fb);
     const RolloutDev *Rp = uni_ptr(g_S.roll);
     const int t = g_S.step, steps = Rp->steps;
-    rollout_record<T>(ps, I, Rp, id, t, steps);
+    (void)rollout_record<T>(ps, I, Rp, id, t, steps, fb);
     rollout_advance<T>(Rp, id, t, steps);
 }
 
@@ -3737,12 +3783,14 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void adjoint_ins
 // read buffer set 0, the slab's result rows, which adjoint_instance only reads.  cfg, dyn_delta and dyn_eps are the launch's again
 // (k_roll_sens brings them back behind the retry loop, in front of this call): the Jacobian runs under the handle's settings.
 template <int T, int NLDS, bool I16>
-static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_sens_step(int ps, gdbl_p I, gdbl_p W, int id, const AdjointDev *Ap) {
-    ps = uni(ps); I = uni_ptr(I); W = uni_ptr(W); id = uni(id); Ap = uni_ptr(Ap);
+static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_sens_step(int ps, gdbl_p I, gdbl_p W, int id, const AdjointDev *Ap,
+                                                                                       const FallbackDev *fb) {
+    ps = uni(ps); I = uni_ptr(I); W = uni_ptr(W); id = uni(id); Ap = uni_ptr(Ap); fb = uni_ptr(fb);
     const RolloutDev *Rp = uni_ptr(g_S.roll);
     const int t = uni(g_S.step), steps = Rp->steps;
-    rollout_record<T>(ps, I, Rp, id, t, steps);
-    adjoint_instance<T, NLDS, I16>(ps, I, W, Ap, id * steps + t); // (begins and ends with a barrier; batch * steps fits an int: api.cpp)
+    // a step whose fallback fired records J_t = V dense and res_t = 0.0 and runs no adjoint (a workgroup-uniform branch)
+    if (rollout_record<T>(ps, I, Rp, id, t, steps, fb)) fallback_jacobian_instance<T>(fb, Ap, id * steps + t);
+    else adjoint_instance<T, NLDS, I16>(ps, I, W, Ap, id * steps + t); // (begins and ends with a barrier; batch * steps fits an int: api.cpp)
     rollout_advance<T>(Rp, id, t, steps);
 }
 
@@ -3835,11 +3883,13 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_solve(
         if (upd.retry) { if (threadIdx.x == 0 && g_S.swapped) { g_S.cfg = cfg; g_S.dyn_delta = dyn_delta; g_S.dyn_eps = dyn_eps; g_S.swapped = 0; } }
         if (upd.x) solution_instance<T>(ps, I, (size_t)id, upd.x); // (fused path: the result straight to the caller's array)
         if (upd.u) outputs_instance<T>(ps, I, (size_t)id, upd.omap, upd.u); // (the selected outputs of x, r doubles, likewise)
+        // (the fallback map of a parametric step, launch.hpp: UpdArgs::fb -- the host sets it only beside theta and u)
+        if constexpr (NLDS >= 1) { if (upd.fb && upd.u) (void)fallback_instance<T>(ps, I, id, (size_t)id, upd.fb, upd.theta, upd.u); }
         // A rollout keeps the instance for its next step (rollout_step: the step's u row and records, the plant map, the step counter) and
         // pulls the next one from the queue after its last step; everything else pulls here.
         bool rolling = false;
         if constexpr (NLDS >= 1) { rolling = upd.on == UPD_ROLL; }
-        if (rolling) rollout_step<T>(ps, I, id);
+        if (rolling) rollout_step<T>(ps, I, id, upd.fb);
         else if (threadIdx.x == 0) g_S.next = (int)gridDim.x + atomicAdd(queue, 1);
 #if EICOS_LDSRES
         { // results, persistent per-instance state and (for the debug readbacks) the workspace go back to HBM
@@ -3974,7 +4024,7 @@ __global__ __launch_bounds__(T, (waves_per_eu<T>())) void k_roll_sens(
             for (int q = threadIdx.x; q < (int)P.work_stride; q += T) Wglob[q] = W[q];
         }
 #endif
-        rollout_sens_step<T, NLDS, I16>(ps, I, W, id, adj); // (the adjoint's first barrier stands between the policy's settings going back and their first read)
+        rollout_sens_step<T, NLDS, I16>(ps, I, W, id, adj, upd.fb); // (the adjoint's first barrier stands between the policy's settings going back and their first read)
         __syncthreads();
         g = g_S.next;
     }
@@ -4315,6 +4365,46 @@ __global__ __launch_bounds__(T) void k_outputs_range(int ps, const double *inst,
     }
 }
 
+// The fallback map over a range of instances (launch.hpp: launch_fallback; fallback_instance is the fused form), behind k_outputs_range
+// on the same rows: ROW-parallel over the count * r rows, the map by value and served from L2.  Every thread reads its instance's record
+// from the slab; where the record's class is in the mask it overwrites its entry of u from row q of theta, and the thread of row 0 bumps
+// the instance's counter (the ids of a launch are distinct: one writer per counter).  Same arithmetic as fallback_instance.
+__device__ __forceinline__ bool fallback_fires(const DevPat &P, const double *inst, int id, unsigned mask) {
+    const DevInfo *di = reinterpret_cast<const DevInfo *>(inst + (size_t)id * P.inst_stride + P.i_info);
+    return (exit_class(di->exitcode, di->n_factor) & mask) != 0;
+}
+template <int T>
+__global__ __launch_bounds__(T) void k_fallback_range(int ps, const double *inst, int first, int count, FallbackDev F, const double *theta, double *u,
+                                                      const int *list) {
+    const DevPat &P = c_pat[ps];
+    const size_t r = (size_t)F.r, k = (size_t)F.k, total = (size_t)count * r;
+    for (size_t e = (size_t)blockIdx.x * T + threadIdx.x; e < total; e += (size_t)gridDim.x * T) {
+        const size_t q = e / r;
+        const int row = (int)(e - q * r), id = slab_of(list, first, (int)q);
+        if (!fallback_fires(P, inst, id, F.mask)) continue;
+        u[e] = affine_row(F.a, row, theta + q * k);
+        if (row == 0) F.counts[id] = F.counts[id] + 1;
+    }
+}
+// Its companion on the rollout-Jacobian path that is not fused (launch.hpp: launch_fallback_jacobian): one thread per row of J
+// [count][r][k]; a fired instance's row becomes the row of V, dense -- zero-filled, then J[col] = J[col] + val in stored order -- and its
+// res 0.0.  The record has not changed since k_fallback_range read it: the adjoint launch between them writes the scaling block alone.
+template <int T>
+__global__ __launch_bounds__(T) void k_fallback_jacobian_range(int ps, const double *inst, int first, int count, FallbackDev F, double *J, double *res) {
+    const DevPat &P = c_pat[ps];
+    const size_t r = (size_t)F.r, k = (size_t)F.k, total = (size_t)count * r;
+    for (size_t e = (size_t)blockIdx.x * T + threadIdx.x; e < total; e += (size_t)gridDim.x * T) {
+        const size_t q = e / r;
+        const int row = (int)(e - q * r);
+        if (!fallback_fires(P, inst, first + (int)q, F.mask)) continue;
+        double *Jr = J + e * k;
+        for (size_t c = 0; c < k; c++) Jr[c] = 0.;
+        const int t1 = F.a.rowptr[row + 1];
+        for (int t = F.a.rowptr[row]; t < t1; t++) Jr[F.a.col[t]] = __dadd_rn(Jr[F.a.col[t]], F.a.val[t]);
+        if (res) res[e] = 0.;
+    }
+}
+
 // A caller-supplied starting point for a range of instances (launch.hpp: launch_set_iterate): ENTRY-parallel like k_update_rhs_range --
 // blockIdx.y strides over the instances, the x dimension over the given entries [x | y | z | s] of one instance (unit stride in the inputs
 // and in the slab, plain 8-byte stores, no scaling: the slab holds these vectors backscaled between two solves).  One thread per instance
@@ -4618,6 +4708,23 @@ hipError_t launch_outputs(int ps, const double *inst, int first, int count, cons
     constexpr int T = 256;
     const size_t nb = ((size_t)count * map.r + T - 1) / T;
     hipLaunchKernelGGL(k_outputs_range<T>, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(T), 0, st, ps, inst, first, count, map, u, list);
+    return hipGetLastError();
+}
+hipError_t launch_fallback(int ps, const double *inst, int first, int count, const FallbackDev &fb, const double *theta, double *u, hipStream_t st,
+                           const int *list) {
+    if (count <= 0 || fb.r <= 0 || fb.mask == 0) return hipSuccess;
+    if (!theta || !u || !fb.counts) return hipErrorInvalidValue;
+    constexpr int T = 256;
+    const size_t nb = ((size_t)count * fb.r + T - 1) / T;
+    hipLaunchKernelGGL(k_fallback_range<T>, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(T), 0, st, ps, inst, first, count, fb, theta, u, list);
+    return hipGetLastError();
+}
+hipError_t launch_fallback_jacobian(int ps, const double *inst, int first, int count, const FallbackDev &fb, double *J, double *res, hipStream_t st) {
+    if (count <= 0 || fb.r <= 0 || fb.mask == 0) return hipSuccess;
+    if (!J) return hipErrorInvalidValue;
+    constexpr int T = 256;
+    const size_t nb = ((size_t)count * fb.r + T - 1) / T;
+    hipLaunchKernelGGL(k_fallback_jacobian_range<T>, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(T), 0, st, ps, inst, first, count, fb, J, res);
     return hipGetLastError();
 }
 hipError_t launch_plant(int ps, const double *inst, int first, int count, const RolloutDev &roll, int t, const double *theta_cur,

@@ -43,6 +43,11 @@ struct MatrixMapDev { int k; AffineDev g[2]; };
 // n, p, m, m rows and as many columns, CSR, in device memory, shared by every instance; base == NULL: that vector is not shifted
 struct ShiftMapDev { AffineDev g[4]; };
 struct RetryDev; // (below, behind SolveCfg)
+// Fallback map (eicos_batch_set_fallback_map): the backup output law u = base + V theta, r rows, CSR with k columns, in device memory,
+// shared by every instance; mask = the exit classes (exit_class.hpp) of a step's FINAL record whose u row comes from this law instead of
+// from the output map; k, r = the parameter and output counts it was validated for; counts [batch] = steps per instance whose u row the
+// law has formed since the last reset, bumped by the workgroup (fused) or the one thread (range kernel) that owns the instance.
+struct FallbackDev { unsigned mask; int k, r; AffineDev a; int *counts; };
 struct UpdArgs { // UpdArgs{} = the neutral launch: no fused step, no maps; every builder assigns fields by name
     // inputs: rows of the five updateData arrays, [batch][...]
     const double *G = nullptr, *A = nullptr, *c = nullptr, *h = nullptr, *b = nullptr;
@@ -62,6 +67,11 @@ struct UpdArgs { // UpdArgs{} = the neutral launch: no fused step, no maps; ever
     // class of the policy's mask is solved once more by the same workgroup, under the policy's settings, before anything reads its result
     // (kernels.hip: retry_between).  One more word of kernel arguments, and one pointer test per instance.
     const RetryDev *retry = nullptr;
+    // fb: the handle's fallback map (eicos_batch_set_fallback_map), a record in device memory; NULL: none.  Only launches that hold theta
+    // carry it (on = UPD_PARAM with u, UPD_ROLL): an instance whose final record -- after the second attempt, when the retry policy took
+    // one -- is in a class of the map's mask gets its u row from the law (kernels.hip: fallback_instance).  One more word of kernel
+    // arguments, and one pointer test per instance.
+    const FallbackDev *fb = nullptr;
     // shared: the handle's shared-values word (eicos_batch_shared_values), read by thread 0 once per instance before the
     // instance's solve.  -1: every instance streams the product values (the sliced-ELL copies of [A' G'], A, G and the G tiles) of its own
     // slab; r >= 0: every instance of the batch holds the bits of instance r there, and all of them stream instance r's.  NULL counts as -1.
@@ -166,6 +176,16 @@ hipError_t launch_set_iterate(int ps, double *inst, int first, int count, const 
 // rows [first, first + count) of u [count][map.r] = the output map applied to the current x of those instances: acc = base[row], then
 // acc = acc + (val * x[col]) in stored order, every product and sum rounded on its own
 hipError_t launch_outputs(int ps, const double *inst, int first, int count, const OutMapDev &map, double *u, hipStream_t st, const int *list = nullptr);
+// The fallback map over rows [first, first + count) (or the `count` ids of `list`), behind launch_outputs on the same u rows: the rows of
+// every instance whose record is in a class of fb.mask are overwritten by base + V theta-row -- acc = base[row], then acc = acc +
+// (val * theta[col]) in stored order, every product and sum rounded on its own -- and its counter is bumped by one.  theta [count][fb.k]
+// and u [count][fb.r] in memory the GPU addresses, row q of both belonging to instance first + q (list[q]); the map by value.
+hipError_t launch_fallback(int ps, const double *inst, int first, int count, const FallbackDev &fb, const double *theta, double *u, hipStream_t st,
+                           const int *list = nullptr);
+// Its companion on the rollout-Jacobian path that is not fused, behind the step's adjoint launch: rows [first, first + count) of
+// J [count][fb.r][fb.k] and res [count][fb.r] (NULL: not kept) of the same instances become V as a dense block -- the row zero-filled, then
+// J[row][col] = J[row][col] + val in stored order -- and 0.0.  Counts nothing.
+hipError_t launch_fallback_jacobian(int ps, const double *inst, int first, int count, const FallbackDev &fb, double *J, double *res, hipStream_t st);
 // One step of a rollout that is not fused into the solve launch, for instances [first, first + count), behind that step's solve and
 // output kernels: z = [row of theta_cur [count][k] | row of u_cur [count][r]] goes through the plant map -- acc = base[row], then
 // acc = acc + (val * z[col]) in stored order, then + w when given, every product and sum rounded on its own -- into theta_next [count][k]

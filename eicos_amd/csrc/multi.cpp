@@ -670,6 +670,22 @@ int eicos_multi_get_retry(eicos_multi *mh, eicos_retry *out) {
     return rc != EICOS_OK ? mfail(rc, eicos_last_error()) : EICOS_OK;
 }
 
+// fallback map (validated against the shard's own maps, which are the same on every shard: all refuse what any would)
+int eicos_multi_set_fallback_map(eicos_multi *mh, unsigned mask, const eicos_affine_map *v) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    return for_shards(mh, [&](int s) { return eicos_batch_set_fallback_map(mh->shard[s], mask, v); });
+}
+
+int eicos_multi_fallback_mask(eicos_multi *mh) { return mh ? eicos_batch_fallback_mask(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
+
+int eicos_multi_fallback_counts(eicos_multi *mh, int first, int count, int *fired, int reset) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    if (count > 0 && !fired) return mfail(EICOS_E_INVALID, "fallback counts: fired is NULL");
+    return for_range(mh, first, count, [&](int s, int f, int cnt, size_t off) {
+        return eicos_batch_fallback_counts(mh->shard[s], f, cnt, fired + off, reset);
+    });
+}
+
 int eicos_multi_retry_counts(eicos_multi *mh, int first, int count, int *retries, int reset) {
     if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
     if (count > 0 && !retries) return mfail(EICOS_E_INVALID, "retry counts: retries is NULL");

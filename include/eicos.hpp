@@ -177,6 +177,15 @@ namespace EiCOS
         const eicos_affine_map *s = nullptr;
     };
 
+    // Extension: the fallback map of BatchSolver::setFallbackMap -- the backup output law u = v0 + V theta (eicos_affine_map: base[r] +
+    // CSR matrix r x k) that a step whose final record falls in an exit class of `mask` (an OR of EICOS_SEL_*) takes its u row from.
+    // The arrays are the caller's and are copied at installation; map == nullptr or mask == 0 removes the installed one.
+    struct FallbackMap
+    {
+        unsigned mask = 0;
+        const eicos_affine_map *map = nullptr;
+    };
+
     // Batched engine: one pattern, `batch` instances.  Arrays are [batch][...] row-major in global instance order.
     // One GPU (device, -1 = current) or several: with a list of device ids the batch is cut into contiguous shards, one per
     // list entry, solved concurrently (eicos_multi_* of eicos_amd.h; a device may be listed more than once).
@@ -322,6 +331,28 @@ namespace EiCOS
         {
             std::vector<int> out(batch_);
             mcheck(eicos_multi_retry_counts(h_, 0, batch_, out.data(), reset ? 1 : 0), "eicos_multi_retry_counts");
+            return out;
+        }
+        // Extension: the backup output law (FallbackMap, above), on every shard, behind the parameter and the output map: from the next
+        // stepParam, stepParamSubset, rollout or rolloutJacobian on, an instance whose final record -- after the retry, when one ran --
+        // is in a class of the mask gets its u row as v0 + V theta; states, exit codes and x_out stay what they are without it
+        // (eicos_batch_set_fallback_map of eicos_amd.h).  A refused map throws and changes nothing.
+        // fallbackMask: 0 = none installed.  fallbackCounts: per instance the steps whose u row the law has formed since the last reset.
+        void setFallbackMap(unsigned mask, const eicos_affine_map *map)
+        {
+            mcheck(eicos_multi_set_fallback_map(h_, mask, map), "eicos_multi_set_fallback_map");
+        }
+        void setFallbackMap(const FallbackMap &f) { setFallbackMap(f.mask, f.map); }
+        unsigned fallbackMask() const
+        {
+            const int v = eicos_multi_fallback_mask(h_);
+            if (v < 0) mcheck(v, "eicos_multi_fallback_mask");
+            return (unsigned)v;
+        }
+        std::vector<int> fallbackCounts(bool reset = false)
+        {
+            std::vector<int> out(batch_);
+            mcheck(eicos_multi_fallback_counts(h_, 0, batch_, out.data(), reset ? 1 : 0), "eicos_multi_fallback_counts");
             return out;
         }
         std::vector<exitcode> solve()
@@ -645,6 +676,9 @@ namespace EiCOS
             const eicos_retry c = r.to_c();
             return eicos_batch_set_retry(h_, &c) == EICOS_OK;
         }
+        // Extension: the backup output law (FallbackMap, above) of the handle; it acts in the step calls of eicos_amd.h that hold
+        // theta.  false: refused, eicos_last_error() names the cause
+        bool setFallbackMap(unsigned mask, const eicos_affine_map *map) { return eicos_batch_set_fallback_map(h_, mask, map) == EICOS_OK; }
 
     private:
         eicos_batch *h_ = nullptr;

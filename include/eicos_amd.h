@@ -200,7 +200,8 @@ int eicos_batch_update_param_device(eicos_batch *hd, int first, int count, const
  *     acc = base[row];  for t in rowptr[row] .. rowptr[row+1]-1, in stored order:  acc = acc + (val[t] * x[i][col[t]])
  * with the product and the sum EACH rounded to fp64 (no fused multiply-add) and x the solution as eicos_batch_solution returns it: u is,
  * bit for bit, what a host restatement in that order computes from eicos_batch_solution.  It is computed from whatever x the instance
- * ended with, whatever its exit code (as x_out is).
+ * ended with, whatever its exit code (as x_out is) -- unless the call is a step that holds theta and the handle has a fallback map
+ * (eicos_batch_set_fallback_map, below) whose mask holds the class the instance ended in.
  * eicos_batch_outputs: synchronous -- waits for the handle's stream, evaluates the map on the current x of instances [first, first+count)
  * and fetches the rows (a pinned destination gets one copy, a pageable one goes through the bounce buffers like eicos_batch_solution).
  * eicos_batch_outputs_device: the same into caller-owned device memory, asynchronous on the handle's stream.  Both: EICOS_E_INVALID
@@ -254,6 +255,39 @@ int eicos_batch_rollout(eicos_batch *hd, int steps, const double *theta0 /* [bat
                         double *u_traj /* [batch][steps][r] */, double *theta_traj /* [batch][steps + 1][k], optional */,
                         int *exitcodes /* [batch][steps], optional */, int *iters /* [batch][steps], optional */);
 int eicos_batch_last_rollout_launches(eicos_batch *hd); /* solve-kernel launches of the most recent rollout: 1 = fused */
+
+/* ---- fallback map: a backup output law for steps whose solve does not end well (no reference counterpart).  A step that stops at the
+ * iteration cap or ends NUMERICS / PINF would hand the plant a u row formed from a meaningless iterate.  A handle may hold one affine
+ * law u = v0 + V theta for all its instances -- eicos_affine_map with base[r] and a CSR matrix r x k (rowptr[r + 1], col / val[rowptr[r]];
+ * columns index theta) -- and a mask of exit classes (EICOS_SEL_*).
+ * The rule: in a step call that has theta in hand -- eicos_batch_update_param_solve, eicos_batch_update_param_solve_subset,
+ * eicos_batch_rollout, eicos_batch_rollout_jacobian and their eicos_multi_* forms --, an instance whose FINAL record (after the second
+ * attempt, when a retry policy took one) falls in a class of the mask gets its u row from the law instead of from the output map,
+ * wherever that row is read: the caller's u_out, the rollout's u trajectory, the plant map, and the recorded Jacobian.  Row j of instance i:
+ *     acc = v0[j];  for t in rowptr[j] .. rowptr[j+1]-1, in stored order:  acc = acc + (val[t] * theta[i][col[t]])
+ * with the product and the sum EACH rounded to fp64, like every other map.  In a step over a subset theta[i] is the row at the
+ * instance's position in the list.  On every path (fused or not; theta and u_out pageable, pinned or device memory; every kernel build)
+ * the bits are the same.  A step that is asked for no u row (u_out == NULL) forms none and counts nothing.
+ * The fallback leaves x, y, z, s, the info records, the retry counts, x_out, the exit codes a call returns and the codes / iters of a
+ * rollout bit for bit what they are without the map: that the law fired for a step is eicos_exit_class(code, 1) & mask, and per instance
+ * the cumulative counter eicos_batch_fallback_counts reads (fired[i] = steps of instance first + i whose u row the law formed since the
+ * counter was last zeroed; reset != 0 zeroes the counters read; it waits for the handle's stream).
+ * In eicos_batch_rollout_jacobian a step whose fallback fired records J_t = V as a dense r x k block -- every row zero-filled, then
+ * J[j][col[t]] = J[j][col[t]] + val[t] in stored order -- and res_t = 0.0, and runs no adjoint; eicos_batch_rollout_gradient then sees
+ * finite rows for it.
+ * The calls that hold no theta -- eicos_batch_outputs*, eicos_batch_param_jacobian*, eicos_batch_output_jacobian*, eicos_batch_adjoint* --
+ * stay the plain map of x (and NaN rows for instances that did not end OPTIMAL / OPTIMAL_INACC), with or without a fallback map.
+ * eicos_batch_set_fallback_map COPIES the host arrays into one device allocation and starts the counters at zero; a later call
+ * replaces the map, v == NULL or mask == 0 removes it.  It needs a parameter map (k > 0) and an output map (r > 0) and remembers the (k, r)
+ * it was validated for: a step under maps with another (k, r) is refused ("install it again").  Installing or removing it counts as a
+ * map install for eicos_batch_rollout_gradient, which refuses a Jacobian trajectory recorded before it.  EICOS_E_INVALID, with a message
+ * naming the fault and nothing changed, for rowptr[0] != 0, decreasing row pointers, a column outside [0, k), mask bits outside
+ * EICOS_SEL_ALL, a mask that is EICOS_SEL_UNSOLVED alone (an attempted instance is never in that class), "no parameter map" and "no
+ * output map".  A mask that holds EICOS_SEL_OPTIMAL is accepted: every step then takes the law.
+ * eicos_batch_fallback_mask: the installed mask, 0 = no fallback map. */
+int eicos_batch_set_fallback_map(eicos_batch *hd, unsigned mask, const eicos_affine_map *v);
+int eicos_batch_fallback_mask(eicos_batch *hd);
+int eicos_batch_fallback_counts(eicos_batch *hd, int first, int count, int *fired /* host [count] */, int reset);
 
 /* ---- matrix map: G and A affine in theta (no reference counterpart).  When a model is linearised around the measured state, a gain is
  * scheduled or a cone constraint depends on the state, the VALUES of G and A move with theta as well: Gpr = G0 + Gm theta,
@@ -838,6 +872,10 @@ int eicos_multi_get_settings(eicos_multi *mh, eicos_settings *out);
 int eicos_multi_set_retry(eicos_multi *mh, const eicos_retry *r);
 int eicos_multi_get_retry(eicos_multi *mh, eicos_retry *out);
 int eicos_multi_retry_counts(eicos_multi *mh, int first, int count, int *retries /* host [count] */, int reset);
+/* fallback map (eicos_batch_set_fallback_map on every shard; a refused map changes no shard); mask: the first shard's; counts: global ids */
+int eicos_multi_set_fallback_map(eicos_multi *mh, unsigned mask, const eicos_affine_map *v);
+int eicos_multi_fallback_mask(eicos_multi *mh);
+int eicos_multi_fallback_counts(eicos_multi *mh, int first, int count, int *fired /* host [count] */, int reset);
 /* the shards: their number, and shard s's single-GPU handle (every eicos_batch_* call works on it), instance range and device */
 int eicos_multi_num_shards(eicos_multi *mh);
 int eicos_multi_shard(eicos_multi *mh, int s, eicos_batch **handle, int *first, int *count, int *device);
