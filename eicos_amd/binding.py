@@ -128,6 +128,10 @@ def _signatures():
         ("eicos_*_rollout", [vp, i] + [dp] * 4 + [ip, ip]), ("eicos_*_rollout_jacobian", [vp, i] + [dp] * 4 + [ip, ip, dp, dp]),
         ("eicos_*_rollout_gradient", [vp] + [dp] * 4), ("eicos_batch_rollout_gradient_device", [vp] + [vp] * 4),
         ("eicos_batch_last_rollout_launches", [vp]), ("eicos_batch_rollout_jacobian_steps", [vp]),
+        # per-instance plant values and the gradient with respect to the plant's entries
+        ("eicos_*_set_plant_values", [vp, i, i, dp, dp]), ("eicos_batch_set_plant_values_device", [vp, i, i, vp, vp]),
+        ("eicos_*_plant_values", [vp, i, i, dp, dp]), ("eicos_*_has_plant_values", [vp]), ("eicos_*_clear_plant_values", [vp]),
+        ("eicos_*_rollout_plant_gradient", [vp] + [dp] * 8), ("eicos_batch_rollout_plant_gradient_device", [vp] + [vp] * 8),
         # solve, subset solves, results
         ("eicos_*_solve", [vp, ip]), ("eicos_*_solve_async", [vp]), ("eicos_*_sync", [vp]), ("eicos_*_select", [vp, u, ip, ip]),
         ("eicos_*_solve_subset_async", [vp, ip, i]), ("eicos_*_solve_subset", [vp, ip, i, ip]), ("eicos_*_solve_where", [vp, u, ip, ip, ip]),
@@ -341,17 +345,19 @@ def _as_group(g):
             np.ascontiguousarray(g[3], np.float64))
 
 
-def _affine_eval(group, v):
+def _affine_eval(group, v, base_i=None, val_i=None):
     """base + M v for the rows of v [B, columns]: [B, rows].  Row r: acc = base[r], then for every stored entry t of the row, in stored
     order, acc = acc + (val[t] * v[col[t]]) -- the product and the sum each rounded to float64 (numpy has no fused multiply-add).  This
-    is the rounding order every map keeps on the GPU; the evaluate() of all five map classes is this function."""
+    is the rounding order every map keeps on the GPU; the evaluate() of all five map classes is this function.
+    base_i [B, rows] / val_i [B, stored entries] (the plant map's per-instance values): row b of them stands in for base / val in
+    row b of the result, the same arithmetic."""
     base, rowptr, col, val = group
-    acc = np.repeat(base[None, :], v.shape[0], axis=0)
+    acc = np.repeat(base[None, :], v.shape[0], axis=0) if base_i is None else base_i.copy()
     length = np.diff(rowptr)
     for j in range(int(length.max()) if length.size else 0):  # entry j of every row that has one
         rows = np.nonzero(length > j)[0]
         t = rowptr[rows] + j
-        acc[:, rows] = acc[:, rows] + val[t][None, :] * v[:, col[t]]
+        acc[:, rows] = acc[:, rows] + (val[t][None, :] if val_i is None else val_i[:, t]) * v[:, col[t]]
     return acc
 
 
@@ -442,9 +448,26 @@ class PlantMap:
         self.k, self.r = int(k), int(r)
         self.base, self.rowptr, self.col, self.val = _as_group(f)
 
-    def evaluate(self, theta, u, w=None):
+    def nnz(self) -> int:
+        """Stored entries of F the map uses: rowptr[k]."""
+        return int(self.rowptr[-1])
+
+    def _instance_values(self, B, f0, val):
+        """The per-instance values of a call as contiguous float64 [B, k] / [B, nnz] (None passes); ValueError otherwise."""
+        out = []
+        for name, a, width in (("f0", f0, self.k), ("val", val, self.nnz())):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (B, width):
+                    raise ValueError(f"{name} has shape {a.shape}, expected [{B}, {width}] (one row per instance)")
+            out.append(a)
+        return out
+
+    def evaluate(self, theta, u, w=None, f0=None, val=None):
         """theta+ [B, k] for theta [B, k], u [B, r] and, optionally, the disturbance w [B, k]: the map over z = [theta | u]
-        (_affine_eval), then acc = acc + w[j], one more rounded sum -- the order of eicos_batch_rollout."""
+        (_affine_eval), then acc = acc + w[j], one more rounded sum -- the order of eicos_batch_rollout.  f0 [B, k] / val [B, nnz]
+        (eicos_batch_set_plant_values): row b of them in the place of base / val for instance b, the same arithmetic; None: the
+        shared values."""
         theta, u = _theta_rows(theta, self.k, None)[0], np.ascontiguousarray(u, dtype=np.float64)
         if u.shape != (theta.shape[0], self.r):
             raise ValueError(f"u has shape {u.shape}, expected [{theta.shape[0]}, {self.r}]")
@@ -452,14 +475,36 @@ class PlantMap:
             w = np.ascontiguousarray(w, dtype=np.float64)
             if w.shape != theta.shape:
                 raise ValueError(f"w has shape {w.shape}, expected {theta.shape}")
-        acc = _affine_eval((self.base, self.rowptr, self.col, self.val), np.concatenate((theta, u), axis=1))
+        f0, val = self._instance_values(theta.shape[0], f0, val)
+        acc = _affine_eval((self.base, self.rowptr, self.col, self.val), np.concatenate((theta, u), axis=1), f0, val)
         return acc if w is None else acc + w
 
-    def backprop(self, J, gu=None, gtheta=None):
+    def backprop(self, J, gu=None, gtheta=None, val=None):
         """(grad_theta0 [B, k], grad_w [B, T, k]): the gradient of L = sum_t gu_t' u_t + sum_t gtheta_t' theta_t over a rollout with
         the step Jacobians J [B, T, r, k] (rollout_jacobian) -- gu [B, T, r] and gtheta [B, T + 1, k], each optional, one must be
         given.  The scalar loop of eicos_batch_rollout_gradient in its stated order, every product and sum rounded on its own; a
-        missing cotangent counts as 0.0 and is still added.  A NaN row of J makes that instance's gradient NaN."""
+        missing cotangent counts as 0.0 and is still added.  A NaN row of J makes that instance's gradient NaN.  val [B, nnz]: the
+        per-instance values the rollout ran under (None: the shared ones)."""
+        return self._sweep(J, gu, gtheta, val, None, None)[:2]
+
+    def backprop_values(self, J, u, theta, gu=None, gtheta=None, val=None):
+        """(grad_theta0 [B, k], grad_w [B, T, k], grad_f0 [B, k], grad_val [B, nnz]): backprop() that also returns the gradient with
+        respect to the plant's own entries, per instance -- u [B, T, r] and theta [B, T + 1, k] the trajectories of the rollout, which
+        the plant read.  The scalar loop of eicos_batch_rollout_plant_gradient in its stated order: before the recursion of step t,
+        grad_f0[i] = grad_f0[i] + lambda[i] and grad_val[s] = grad_val[s] + (lambda[row(s)] * z_t[col[s]]), z_t = [theta_t | u_t];
+        after step 0, 0.0 * grad_theta0[row] is added to every entry, so that a NaN of J_0 reaches them as those of later steps do.
+        For the shared plant sum the rows over the batch."""
+        k, r = self.k, self.r
+        J = np.ascontiguousarray(J, dtype=np.float64)
+        if J.ndim != 4:
+            raise ValueError(f"J has shape {J.shape}, expected [batch, steps, {r}, {k}]")
+        B, T = int(J.shape[0]), int(J.shape[1])
+        u, theta = _cotangent(u, (B, T, r), "u"), _cotangent(theta, (B, T + 1, k), "theta")
+        if u is None or theta is None:
+            raise ValueError("u and theta (the trajectories of the rollout) are both needed")
+        return self._sweep(J, gu, gtheta, val, u, theta)
+
+    def _sweep(self, J, gu, gtheta, val_i, u, theta):
         k, r = self.k, self.r
         J = np.ascontiguousarray(J, dtype=np.float64)
         if J.ndim != 4 or J.shape[2:] != (r, k):
@@ -468,12 +513,22 @@ class PlantMap:
         if gu is None and gtheta is None:
             raise ValueError("gu and gtheta are both None")
         gu, gtheta = _cotangent(gu, (B, T, r), "gu"), _cotangent(gtheta, (B, T + 1, k), "gtheta")
-        rowptr, col, val = self.rowptr, self.col, self.val
+        val_i = self._instance_values(B, None, val_i)[1]
+        rowptr, col = self.rowptr, self.col
+        nnz = self.nnz()
         g0, gw = np.zeros((B, k)), np.zeros((B, T, k))
+        gf0, gval = np.zeros((B, k)), np.zeros((B, nnz))
         zero = np.float64(0.0)
         for b in range(B):
+            val = self.val if val_i is None else val_i[b]
             lam = [gtheta[b, T, c] if gtheta is not None else zero for c in range(k)]
             for t in range(T - 1, -1, -1):
+                if u is not None:
+                    z = [theta[b, t, c] for c in range(k)] + [u[b, t, j] for j in range(r)]
+                    for i in range(k):
+                        gf0[b, i] = gf0[b, i] + lam[i]
+                        for s in range(int(rowptr[i]), int(rowptr[i + 1])):
+                            gval[b, s] = gval[b, s] + (lam[i] * z[col[s]])
                 gw[b, t, :] = lam
                 v = [zero] * (k + r)
                 for i in range(k):
@@ -488,7 +543,14 @@ class PlantMap:
                     new.append(acc)
                 lam = new
             g0[b, :] = lam
-        return g0, gw
+            if u is not None:
+                with np.errstate(invalid="ignore"):
+                    for i in range(k):
+                        poison = zero * lam[i]
+                        gf0[b, i] = gf0[b, i] + poison
+                        for s in range(int(rowptr[i]), int(rowptr[i + 1])):
+                            gval[b, s] = gval[b, s] + poison
+        return g0, gw, gf0, gval
 
 
 def _plant_map_ptr(fmap, k, r):
@@ -786,12 +848,14 @@ class _Solver:
 
     # ---- plant map and the closed-loop rollout (include/eicos_amd.h: eicos_batch_set_plant_map / eicos_batch_rollout) ----
     def set_plant_map(self, fmap: "PlantMap | None"):
-        """Install (copy) a PlantMap for all instances, behind the parameter and the output map it refers to; None removes it."""
+        """Install (copy) a PlantMap for all instances, behind the parameter and the output map it refers to; None removes it.  Either
+        way the per-instance values of set_plant_values() are dropped (the pattern may have changed)."""
         if fmap is None:
             self._call("set_plant_map", None)
             return
         _keep, ptr = _plant_map_ptr(fmap, self.param_count(), self.output_count())
         self._call("set_plant_map", ptr)
+        self._plant_shape = (fmap.k, fmap.nnz())  # (the widths of the per-instance value rows: set_plant_values)
 
     def has_plant_map(self) -> bool:
         return bool(self._query("has_plant_map"))
@@ -916,6 +980,75 @@ class _Solver:
         else:
             self._call("rollout_gradient", *[_dp_or_dummy(a) for a in (gu, gtheta, g0, gw)])
         return g0, gw
+
+    # ---- per-instance plant values (include/eicos_amd.h: eicos_batch_set_plant_values / _rollout_plant_gradient) ----
+    def _plant_widths(self):
+        """(k, nnzF) of the installed plant map as set_plant_map() last saw it; (0, 0) without one."""
+        return getattr(self, "_plant_shape", (0, 0)) if self.has_plant_map() else (0, 0)
+
+    def set_plant_values(self, f0=None, val=None, first: int = 0, device=False):
+        """Per-instance values of the installed plant map for instances [first, first + count), count = the rows given: f0 [count, k]
+        in the place of its base, val [count, nnzF] in the place of its stored values (same pattern, stored order); None keeps a
+        group.  The first call of a group fills every instance with the shared values first.  Every rollout form then runs instance i
+        against PlantMap.evaluate(..., f0=, val=) with its own rows.  device=True (single-GPU handles): through the device form."""
+        k, nnz = self._plant_widths()
+        if f0 is None and val is None:
+            raise ValueError("f0 and val are both None")
+        count = _rows((f0, val), None)
+        for name, a, w in (("f0", f0, k), ("val", val, nnz)):
+            if a is not None and (np.ndim(a) != 2 or np.shape(a) != (count, w)):
+                raise ValueError(f"{name} has shape {np.shape(a)}, expected [{count}, {w}] (one row per instance)")
+        first = int(first)
+        if first < 0 or count > self.batch - first:
+            raise ValueError(f"instances [{first}, {first + count}) lie outside [0, {self.batch})")
+        arrs, ptrs = _group_ptrs((f0, val), (k, nnz), count)
+        if device:
+            self._device_form("set_plant_values_device", None, 0, (), arrs, (), lead=(first, count))
+        else:
+            self._call("set_plant_values", first, count, *ptrs)
+
+    def plant_values(self, first: int = 0, count: int | None = None):
+        """(f0 [count, k], val [count, nnzF]) of instances [first, first + count) as the rollouts read them: the installed per-instance
+        rows, and the shared values where none are installed."""
+        k, nnz = self._plant_widths()
+        first = int(first)
+        count = self.batch - first if count is None else int(count)
+        f0, val = np.zeros((max(count, 0), k)), np.zeros((max(count, 0), nnz))
+        self._call("plant_values", first, count, _dp_or_dummy(f0), _dp_or_dummy(val))
+        return f0, val
+
+    def has_plant_values(self) -> int:
+        """Bit 0: per-instance f0 rows are installed, bit 1: per-instance val rows; 0: every instance runs the shared plant."""
+        return _nonneg(self._query("has_plant_values"))
+
+    def clear_plant_values(self):
+        """Drop the per-instance values: every instance runs the shared plant map again."""
+        self._call("clear_plant_values")
+
+    def rollout_plant_gradient(self, u, theta, gu=None, gtheta=None, device=False):
+        """(grad_theta0 [batch, k], grad_w [batch, T, k], grad_f0 [batch, k], grad_val [batch, nnzF]): rollout_gradient() that also
+        returns the gradient with respect to the plant's own entries, per instance -- u [batch, T, r] and theta [batch, T + 1, k] the
+        trajectories the most recent rollout_jacobian() returned.  Bit for bit PlantMap.backprop_values of the returned J (with the
+        per-instance val where installed).  With the shared plant, sum the rows over the batch.  device=True as in rollout_gradient()."""
+        shape = getattr(self, "_rollout_shape", None)
+        if shape is None:  # (no rollout_jacobian yet: the library refuses, with its message)
+            one = _dp(np.zeros(1))
+            self._call("rollout_plant_gradient", one, None, one, one, one, None, None, None)
+            raise RuntimeError("rollout_plant_gradient: no rollout_jacobian() on this handle")
+        T, k, r = shape
+        nnz = self._plant_widths()[1]
+        if gu is None and gtheta is None:
+            raise ValueError("gu and gtheta are both None")
+        gu, gtheta = _cotangent(gu, (self.batch, T, r), "gu"), _cotangent(gtheta, (self.batch, T + 1, k), "gtheta")
+        u, theta = _cotangent(u, (self.batch, T, r), "u"), _cotangent(theta, (self.batch, T + 1, k), "theta")
+        if u is None or theta is None:
+            raise ValueError("u and theta (the trajectories of the rollout) are both needed")
+        outs = (np.zeros((self.batch, k)), np.zeros((self.batch, T, k)), np.zeros((self.batch, k)), np.zeros((self.batch, nnz)))
+        if device:
+            self._device_form("rollout_plant_gradient_device", None, 0, (), (gu, gtheta, u, theta), outs, lead=())
+        else:
+            self._call("rollout_plant_gradient", *[_dp_or_dummy(a) for a in (gu, gtheta, u, theta) + outs])
+        return outs
 
     # ---- solve ----
     def solve(self):

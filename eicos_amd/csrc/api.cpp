@@ -146,6 +146,9 @@ struct eicos_batch {
     OutMapDev out{}; DevBuf d_out; double *d_u = nullptr;
     // plant map (eicos_batch_set_plant_map): one device allocation [PlantMapDev (MAP_HEADER bytes) | base, val | rowptr, col], plant.k = 0 while none is installed
     PlantMapDev plant{}; DevBuf d_plant;
+    // per-instance plant values (eicos_batch_set_plant_values): one allocation per group, [batch][k] and [batch][plant.nnz], made and filled
+    // with the shared values by the group's first call; plant.ibase / plant.ival point at them (NULL: the group is the shared one)
+    DevBuf d_plant_f0, d_plant_val;
     // rollout (eicos_batch_rollout): one device allocation: [RolloutDev (MAP_HEADER bytes) | theta, u, w trajectories | two
     // theta rows of the batch (the path that is not fused) | codes, iters]; roll = the host copy of the record of the most recent call
     RolloutDev roll{}; DevBuf d_roll; int rollout_launches = 0;
@@ -2018,8 +2021,86 @@ int eicos_batch_set_plant_map(eicos_batch *h, const eicos_affine_map *f) {
         if (affine_fault(g, msg)) return fail(EICOS_E_INVALID, msg);
     }
     PlantMapDev M{};
-    M.k = k; M.r = r;
-    return install_map(h, h->d_plant, h->plant, "plant", &g, 1, 0, f ? &M : nullptr, &M.a);
+    M.k = k; M.r = r; M.nnz = f ? f->rowptr[k] : 0;
+    // the per-instance values go with the map they were given for (the pattern may change); install_map waits for the stream first
+    // and clears the descriptor that points at them
+    const int rc = install_map(h, h->d_plant, h->plant, "plant", &g, 1, 0, f ? &M : nullptr, &M.a);
+    h->d_plant_f0.reset(); h->d_plant_val.reset();
+    h->plant.ibase = h->plant.ival = nullptr;
+    return rc;
+}
+
+// ---- per-instance plant values: rows of base / val of the plant map that belong to one instance each (launch.hpp: PlantMapDev) ----
+// The descriptor travels by value inside the rollout's record, so the next rollout picks the pointers up; every check stands in front of
+// the first enqueue.  The host form copies on the handle's stream and waits, the device form only enqueues.
+static int plant_values_range(const eicos_batch *h, int first, int count, const std::string &w) {
+    if (h->plant.k == 0) return fail(EICOS_E_INVALID, w + ": no plant map (eicos_batch_set_plant_map installs one)");
+    if (first < 0 || count < 0 || first > h->batch - count) return fail(EICOS_E_INVALID, w + ": instance range out of bounds");
+    return EICOS_OK;
+}
+static int set_plant_values(eicos_batch *h, int first, int count, const double *f0, const double *val, bool device, const char *who) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    const std::string w(who);
+    { const int rc = plant_values_range(h, first, count, w); if (rc != EICOS_OK) return rc; }
+    if (!f0 && !val) return fail(EICOS_E_INVALID, w + ": f0 and val are both NULL");
+    const char *other = device ? " must live in device memory (the form without _device takes host pointers)" : " lives in device memory: this form takes host pointers (use the _device form)";
+    const struct { const void *p; const char *name; } arr[2] = {{f0, "f0"}, {val, "val"}};
+    for (const auto &a : arr) if (a.p && (memory_kind(a.p, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": " + a.name + other);
+    HIP_TRY(hipSetDevice(h->device));
+    struct Group { const double *src, *shared; size_t width; DevBuf &buf; const double *&at; };
+    Group grp[2] = {{f0, h->plant.a.base, (size_t)h->plant.k, h->d_plant_f0, h->plant.ibase}, {val, h->plant.a.val, (size_t)h->plant.nnz, h->d_plant_val, h->plant.ival}};
+    for (Group &g : grp) {
+        if (!g.src || g.width == 0) continue; // (a map without stored entries has no val rows to give)
+        if (!g.buf) {
+            HIP_TRY_AS("hipMalloc", g.buf.alloc((size_t)h->batch * g.width * sizeof(double)));
+            HIP_TRY(launch_fill_rows(g.shared, (int)g.width, h->batch, g.buf.as<double>(), h->stream));
+            g.at = g.buf.as<double>();
+        }
+        if (count > 0)
+            HIP_TRY(hipMemcpyAsync(g.buf.as<double>() + (size_t)first * g.width, g.src, (size_t)count * g.width * sizeof(double),
+                                   device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    }
+    h->map_gen++; // (eicos_batch_rollout_gradient: a recorded rollout belongs to the plant values it ran under)
+    if (!device) HIP_TRY(hipStreamSynchronize(h->stream));
+    return EICOS_OK;
+}
+int eicos_batch_set_plant_values(eicos_batch *h, int first, int count, const double *f0, const double *val) {
+    return set_plant_values(h, first, count, f0, val, false, "eicos_batch_set_plant_values");
+}
+int eicos_batch_set_plant_values_device(eicos_batch *h, int first, int count, const double *df0, const double *dval) {
+    return set_plant_values(h, first, count, df0, dval, true, "eicos_batch_set_plant_values_device");
+}
+int eicos_batch_plant_values(eicos_batch *h, int first, int count, double *f0_out, double *val_out) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    const std::string w("eicos_batch_plant_values");
+    { const int rc = plant_values_range(h, first, count, w); if (rc != EICOS_OK) return rc; }
+    if (!f0_out && !val_out) return fail(EICOS_E_INVALID, w + ": f0_out and val_out are both NULL");
+    for (const void *p : {(const void *)f0_out, (const void *)val_out})
+        if (p && memory_kind(p, 1) == MEM_DEVICE) return fail(EICOS_E_INVALID, w + ": the outputs are host arrays");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const struct { double *dst; const double *rows, *shared; size_t width; } grp[2] = {
+        {f0_out, h->plant.ibase, h->plant.a.base, (size_t)h->plant.k}, {val_out, h->plant.ival, h->plant.a.val, (size_t)h->plant.nnz}};
+    for (const auto &g : grp) {
+        if (!g.dst || g.width == 0 || count == 0) continue;
+        if (g.rows) { HIP_TRY(hipMemcpy(g.dst, g.rows + (size_t)first * g.width, (size_t)count * g.width * sizeof(double), hipMemcpyDeviceToHost)); continue; }
+        HIP_TRY(hipMemcpy(g.dst, g.shared, g.width * sizeof(double), hipMemcpyDeviceToHost));
+        for (int q = 1; q < count; q++) std::memcpy(g.dst + (size_t)q * g.width, g.dst, g.width * sizeof(double));
+    }
+    return EICOS_OK;
+}
+int eicos_batch_has_plant_values(eicos_batch *h) {
+    return h ? ((h->plant.ibase ? 1 : 0) | (h->plant.ival ? 2 : 0)) : fail(EICOS_E_INVALID, "NULL handle");
+}
+int eicos_batch_clear_plant_values(eicos_batch *h) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (!h->d_plant_f0 && !h->d_plant_val) { h->map_gen++; return EICOS_OK; }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream)); // (a sweep in flight may still read the rows that go away)
+    h->d_plant_f0.reset(); h->d_plant_val.reset();
+    h->plant.ibase = h->plant.ival = nullptr;
+    h->map_gen++;
+    return EICOS_OK;
 }
 
 // ---- fallback map: the backup output law u = v0 + V theta of steps whose solve ends in a class of the mask (launch.hpp: FallbackDev) ----
@@ -2233,40 +2314,63 @@ int eicos_batch_rollout_jacobian(eicos_batch *h, int steps, const double *theta0
 // The backward sweep over the most recent eicos_batch_rollout_jacobian of the handle (launch.hpp: launch_rollout_backprop), behind
 // everything on the handle's stream.  Every check stands in front of the first enqueue.  The host form stages its arrays in d_rollG
 // and waits; the device form only enqueues.
-static int rollout_gradient(eicos_batch *h, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w, bool device, const char *who) {
+// pv != NULL (eicos_batch_rollout_plant_gradient): the sweep also forms the gradient with respect to the plant's own entries from the
+// caller's u and theta trajectories; grad_theta0 is optional then, one of the four outputs is not.
+struct PlantGradArgs { const double *u_traj, *theta_traj; double *grad_f0, *grad_val; };
+static int rollout_gradient(eicos_batch *h, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w, bool device, const char *who,
+                            const PlantGradArgs *pv = nullptr) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     const std::string w(who);
     if (h->rollJ_steps == 0) return fail(EICOS_E_INVALID, w + ": the handle holds no Jacobian trajectory (eicos_batch_rollout_jacobian records one)");
-    if (h->rollJ_gen != h->map_gen) return fail(EICOS_E_INVALID, w + ": a parameter, matrix, output, plant or fallback map was installed after the rollout whose Jacobians the handle holds: run eicos_batch_rollout_jacobian again");
+    if (h->rollJ_gen != h->map_gen) return fail(EICOS_E_INVALID, w + ": a parameter, matrix, output, plant or fallback map was installed after the rollout whose Jacobians the handle holds (setting or clearing per-instance plant values counts as one): run eicos_batch_rollout_jacobian again");
     if (!gu && !gtheta) return fail(EICOS_E_INVALID, w + ": gu and gtheta are both NULL");
-    if (!grad_theta0) return fail(EICOS_E_INVALID, w + ": grad_theta0 is NULL");
+    if (!pv && !grad_theta0) return fail(EICOS_E_INVALID, w + ": grad_theta0 is NULL");
+    if (pv && !pv->u_traj) return fail(EICOS_E_INVALID, w + ": u_traj is NULL");
+    if (pv && !pv->theta_traj) return fail(EICOS_E_INVALID, w + ": theta_traj is NULL");
+    if (pv && !grad_theta0 && !grad_w && !pv->grad_f0 && !pv->grad_val) return fail(EICOS_E_INVALID, w + ": grad_theta0, grad_w, grad_f0 and grad_val are all NULL");
     const char *other = device ? " must live in device memory (the form without _device takes host pointers)" : " lives in device memory: this form takes host pointers (use the _device form)";
-    const struct { const void *p; const char *name; } arr[4] = {{gu, "gu"}, {gtheta, "gtheta"}, {grad_theta0, "grad_theta0"}, {grad_w, "grad_w"}};
+    const struct { const void *p; const char *name; } arr[8] = {{gu, "gu"}, {gtheta, "gtheta"}, {grad_theta0, "grad_theta0"}, {grad_w, "grad_w"},
+        {pv ? pv->u_traj : nullptr, "u_traj"}, {pv ? pv->theta_traj : nullptr, "theta_traj"}, {pv ? pv->grad_f0 : nullptr, "grad_f0"}, {pv ? pv->grad_val : nullptr, "grad_val"}};
     for (const auto &a : arr) if (a.p && (memory_kind(a.p, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": " + a.name + other);
-    const size_t B = (size_t)h->batch, T = (size_t)h->rollJ_steps, k = (size_t)h->rollJ_k, r = (size_t)h->rollJ_r;
-    if (rollout_backprop_lds((int)k, (int)r) > 48 * 1024) return fail(EICOS_E_INVALID, w + ": 3 k + 2 r doubles must fit 48 KB of LDS");
+    const size_t B = (size_t)h->batch, T = (size_t)h->rollJ_steps, k = (size_t)h->rollJ_k, r = (size_t)h->rollJ_r, nnz = (size_t)h->rollJ_plant.nnz;
+    const bool want_val = pv && pv->grad_val && nnz > 0;
+    if (pv && !grad_theta0 && !grad_w && !pv->grad_f0 && !want_val) return EICOS_OK; // (grad_val alone of a map without stored entries: no row to form)
+    if (rollout_backprop_lds((int)k, (int)r, want_val) > 48 * 1024)
+        return fail(EICOS_E_INVALID, w + (want_val ? ": 4 k + 3 r doubles must fit 48 KB of LDS" : ": 3 k + 2 r doubles must fit 48 KB of LDS"));
     HIP_TRY(hipSetDevice(h->device));
-    const size_t n_gu = B * T * r, n_gt = B * (T + 1) * k, n_g0 = B * k, n_gw = B * T * k;
+    const size_t n_gu = B * T * r, n_gt = B * (T + 1) * k, n_g0 = B * k, n_gw = B * T * k, n_gv = B * nnz;
     const double *d_J = reinterpret_cast<const double *>(h->d_rollJ.as<char>() + MAP_HEADER);
     const double *d_gu = gu, *d_gt = gtheta; double *d_g0 = grad_theta0, *d_gw = grad_w;
+    const double *d_u = pv ? pv->u_traj : nullptr, *d_th = pv ? pv->theta_traj : nullptr;
+    double *d_gf = pv ? pv->grad_f0 : nullptr, *d_gv = want_val ? pv->grad_val : nullptr;
     if (!device) {
         HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY_AS("hipMalloc", h->d_rollG.reserve((n_gu + n_gt + n_g0 + n_gw) * sizeof(double), h->stream));
+        HIP_TRY_AS("hipMalloc", h->d_rollG.reserve((n_gu + n_gt + n_g0 + n_gw + (pv ? n_gu + n_gt + n_g0 + n_gv : 0)) * sizeof(double), h->stream));
         double *at = h->d_rollG.as<double>();
         if (gu) { HIP_TRY(hipMemcpyAsync(at, gu, n_gu * sizeof(double), hipMemcpyHostToDevice, h->stream)); d_gu = at; }
         at += n_gu;
         if (gtheta) { HIP_TRY(hipMemcpyAsync(at, gtheta, n_gt * sizeof(double), hipMemcpyHostToDevice, h->stream)); d_gt = at; }
         at += n_gt;
         d_g0 = at; d_gw = grad_w ? at + n_g0 : nullptr;
+        at += n_g0 + n_gw;
+        if (pv) {
+            if (!grad_theta0) d_g0 = nullptr;
+            HIP_TRY(hipMemcpyAsync(at, pv->u_traj, n_gu * sizeof(double), hipMemcpyHostToDevice, h->stream)); d_u = at; at += n_gu;
+            HIP_TRY(hipMemcpyAsync(at, pv->theta_traj, n_gt * sizeof(double), hipMemcpyHostToDevice, h->stream)); d_th = at; at += n_gt;
+            d_gf = pv->grad_f0 ? at : nullptr; at += n_g0;
+            d_gv = want_val ? at : nullptr;
+        }
     }
     if (!h->ev_a0) { HIP_TRY(hipEventCreate(&h->ev_a0)); HIP_TRY(hipEventCreate(&h->ev_a1)); }
     HIP_TRY(hipEventRecord(h->ev_a0, h->stream)); // (eicos_batch_last_adjoint_ms: the sweep counts as the handle's most recent adjoint launch)
-    HIP_TRY(launch_rollout_backprop(h->rollJ_plant, (int)T, h->batch, d_J, d_gu, d_gt, d_g0, d_gw, h->stream));
+    HIP_TRY(launch_rollout_backprop(h->rollJ_plant, (int)T, h->batch, d_J, d_gu, d_gt, d_g0, d_gw, h->stream, d_u, d_th, d_gf, d_gv));
     HIP_TRY(hipEventRecord(h->ev_a1, h->stream));
     h->adjoint_timed = true;
     if (device) return EICOS_OK;
-    HIP_TRY(hipMemcpyAsync(grad_theta0, d_g0, n_g0 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_theta0) HIP_TRY(hipMemcpyAsync(grad_theta0, d_g0, n_g0 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_w) HIP_TRY(hipMemcpyAsync(grad_w, d_gw, n_gw * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (d_gf) HIP_TRY(hipMemcpyAsync(pv->grad_f0, d_gf, n_g0 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (d_gv) HIP_TRY(hipMemcpyAsync(pv->grad_val, d_gv, n_gv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return EICOS_OK;
 }
@@ -2276,6 +2380,16 @@ int eicos_batch_rollout_gradient(eicos_batch *h, const double *gu, const double 
 }
 int eicos_batch_rollout_gradient_device(eicos_batch *h, const double *dgu, const double *dgtheta, double *dgrad_theta0, double *dgrad_w) {
     return rollout_gradient(h, dgu, dgtheta, dgrad_theta0, dgrad_w, true, "eicos_batch_rollout_gradient_device");
+}
+int eicos_batch_rollout_plant_gradient(eicos_batch *h, const double *gu, const double *gtheta, const double *u_traj, const double *theta_traj,
+                                       double *grad_theta0, double *grad_w, double *grad_f0, double *grad_val) {
+    const PlantGradArgs pv{u_traj, theta_traj, grad_f0, grad_val};
+    return rollout_gradient(h, gu, gtheta, grad_theta0, grad_w, false, "eicos_batch_rollout_plant_gradient", &pv);
+}
+int eicos_batch_rollout_plant_gradient_device(eicos_batch *h, const double *dgu, const double *dgtheta, const double *du_traj, const double *dtheta_traj,
+                                              double *dgrad_theta0, double *dgrad_w, double *dgrad_f0, double *dgrad_val) {
+    const PlantGradArgs pv{du_traj, dtheta_traj, dgrad_f0, dgrad_val};
+    return rollout_gradient(h, dgu, dgtheta, dgrad_theta0, dgrad_w, true, "eicos_batch_rollout_plant_gradient_device", &pv);
 }
 
 int eicos_batch_solution(eicos_batch *h, double *x) {
@@ -2316,6 +2430,11 @@ int eicos_batch_kernel_build(eicos_batch *h) {
 }
 
 int eicos_internal_device(const eicos_batch *h) { return h ? h->device : -1; }
+int eicos_internal_plant_dims(const eicos_batch *h, int *k, int *nnz) {
+    if (!h || !k || !nnz) return EICOS_E_INVALID;
+    *k = h->plant.k; *nnz = h->plant.nnz;
+    return EICOS_OK;
+}
 // ms from the start of `from`'s most recent solve to the end of `to`'s (two handles on ONE device: the span of a device that holds
 // several shards of an eicos_multi); both solves must have completed
 int eicos_internal_solve_span_ms(eicos_batch *from, eicos_batch *to, float *ms) {

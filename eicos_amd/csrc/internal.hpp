@@ -13,6 +13,8 @@ int eicos_internal_update_staged(eicos_batch *h, int first, int count, const dou
 // the parametric update (eicos_batch_update_param) from such buffers: theta [count][k]
 int eicos_internal_update_param_staged(eicos_batch *h, int first, int count, const double *theta, int src_dev);
 int eicos_internal_device(const eicos_batch *h);
+// the row widths of the per-instance plant values: k the installed plant map was validated for and its stored entries rowptr[k]; 0, 0 without one
+int eicos_internal_plant_dims(const eicos_batch *h, int *k, int *nnz);
 // ms from the start of `from`'s most recent solve to the end of `to`'s (two handles on one device)
 int eicos_internal_solve_span_ms(eicos_batch *from, eicos_batch *to, float *ms);
 }

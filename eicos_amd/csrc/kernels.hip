@@ -3531,6 +3531,8 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void fallback_ja
 // (the u row by outputs_instance, the theta row by the previous step), so they are read with ordinary global loads behind a barrier and
 // staged in the LDS KKT-space vector, idle between two solves (k + r <= Npad: api.cpp); threads then run over the k rows, accumulating
 // in stored order, product and sum rounded on their own, the disturbance added last.  plant_row = one row (k_plant_range shares it, with z = PlantZ).
+// base and val are the instance's own rows where the handle holds per-instance plant values (plant_of: row `id`, never the block's index --
+// a workgroup pulls whole trajectories from the queue); id is uniform, so their loads stay scalar like those of the shared map.
 template <class ZP> __device__ __forceinline__ double plant_row(const AffineDev &A, int row, ZP z, const double *w) {
     const double acc = affine_row(A, row, z);
     return w ? __dadd_rn(acc, w[row]) : acc;
@@ -3539,7 +3541,7 @@ template <int T>
 static __device__ __noinline__ __attribute__((not_tail_called)) void plant_instance(const RolloutDev *Rp, int id, int t) {
     Rp = uni_ptr(Rp); id = uni(id); t = uni(t);
     const int steps = Rp->steps, k = Rp->plant.k, r = Rp->plant.r;
-    const AffineDev A = Rp->plant.a;
+    const AffineDev A = plant_of(Rp->plant, (size_t)id); // (the instance's own base / val rows where the handle holds them: launch.hpp)
     const size_t at = (size_t)id * steps + t;
     double *th = Rp->theta + (at + id) * k; // row t of [steps + 1] rows; row t + 1 follows it
     const double *u = Rp->u + at * r, *w = Rp->w ? Rp->w + at * k : nullptr;
@@ -4446,7 +4448,7 @@ __global__ __launch_bounds__(T) void k_plant_range(int ps, const double *inst, i
         const size_t q = e / k, at = (first + q) * steps + t;
         const int row = (int)(e - q * k);
         const double *th = theta_cur + q * k, *u = u_cur + q * r;
-        const double acc = plant_row(R.plant.a, row, PlantZ{th, u, k}, R.w ? R.w + at * k : nullptr);
+        const double acc = plant_row(plant_of(R.plant, first + q), row, PlantZ{th, u, k}, R.w ? R.w + at * k : nullptr);
         theta_next[e] = acc;
         R.theta[(at + first + q + 1) * k + row] = acc;
         for (size_t j = row; j < r; j += k) R.u[at * r + j] = u[j];
@@ -4468,18 +4470,41 @@ __global__ __launch_bounds__(T) void k_plant_range(int ps, const double *inst, i
 //   stored entries s with col[s] == c;  mu[j] = gu[t][j] + v[k + j];  lam'[c] = gth[t][c] + v[c], then + (J[t][j][c] * mu[j]) for
 //   j ascending;  lam = lam'.   grad_theta0 = lam.
 // Thread c walks the whole map for its column: the map has at most k (k + r) entries, and T steps of it are a few microseconds.
+// Instance b sweeps with row b of the per-instance values where the map holds them (launch.hpp: plant_of).
+// The plant's own entries (eicos_batch_rollout_plant_gradient; gf0 / gval, either NULL = not wanted, with the trajectories ut / tht the
+// plant read): in front of step t's recursion  gf0[i] = gf0[i] + lam[i]  and  gval[s] = gval[s] + (lam[row(s)] * z_t[col[s]]),
+// z_t = [theta_t | u_t] staged in LDS behind mu; after step 0, 0.0 * grad_theta0[row] is added to every entry -- a NaN of J_0, which
+// the sums never meet, reaches them like one of a later step.  The thread of row i owns gf0[i] and the stored values of that row and
+// accumulates them in place over t = T-1 .. 0, so no sum depends on how threads are scheduled.  Neither wanted: the sweep as it was.
 template <int T>
 __global__ __launch_bounds__(T) void k_rollout_backprop(PlantMapDev M, int steps, int batch, const double *J, const double *gu, const double *gth,
-                                                        double *grad0, double *gradw) {
+                                                        double *grad0, double *gradw, const double *ut, const double *tht, double *gf0, double *gval) {
     const int k = M.k, r = M.r;
-    const AffineDev A = M.a;
-    double *lam = g_dyn, *lam2 = lam + k, *v = lam2 + k, *mu = v + k + r;
+    double *lam = g_dyn, *lam2 = lam + k, *v = lam2 + k, *mu = v + k + r, *z = mu + r;
+    const bool values = gf0 || gval;
     for (int b = blockIdx.x; b < batch; b += (int)gridDim.x) {
         const size_t bt = (size_t)b * steps;
+        const AffineDev A = plant_of(M, (size_t)b);
+        double *f0b = gf0 ? gf0 + (size_t)b * k : nullptr, *valb = gval ? gval + (size_t)b * M.nnz : nullptr;
         __syncthreads(); // (the instance before: its last reads of lam)
         FOR_T(c, k) lam[c] = gth ? gth[(bt + b + steps) * k + c] : 0.;
+        if (values) FOR_T(i, k) {
+            if (f0b) f0b[i] = 0.;
+            if (valb) for (int s = A.rowptr[i]; s < A.rowptr[i + 1]; s++) valb[s] = 0.;
+        }
         __syncthreads();
         for (int t = steps - 1; t >= 0; t--) {
+            if (values) {
+                if (valb) {
+                    FOR_T(c, k + r) z[c] = c < k ? tht[(bt + b + t) * k + c] : ut[(bt + t) * r + (c - k)];
+                    __syncthreads();
+                }
+                FOR_T(i, k) {
+                    const double l = lam[i];
+                    if (f0b) f0b[i] = __dadd_rn(f0b[i], l);
+                    if (valb) for (int s = A.rowptr[i]; s < A.rowptr[i + 1]; s++) valb[s] = __dadd_rn(valb[s], __dmul_rn(l, z[A.col[s]]));
+                }
+            }
             if (gradw) { FOR_T(c, k) gradw[(bt + t) * k + c] = lam[c]; }
             FOR_T(c, k + r) {
                 double acc = 0.;
@@ -4501,8 +4526,19 @@ __global__ __launch_bounds__(T) void k_rollout_backprop(PlantMapDev M, int steps
             FOR_T(c, k) lam[c] = lam2[c];
             __syncthreads();
         }
-        FOR_T(c, k) grad0[(size_t)b * k + c] = lam[c];
+        if (grad0) { FOR_T(c, k) grad0[(size_t)b * k + c] = lam[c]; }
+        if (values) FOR_T(i, k) {
+            const double poison = __dmul_rn(0., lam[i]);
+            if (f0b) f0b[i] = __dadd_rn(f0b[i], poison);
+            if (valb) for (int s = A.rowptr[i]; s < A.rowptr[i + 1]; s++) valb[s] = __dadd_rn(valb[s], poison);
+        }
     }
+}
+
+// rows [0, rows) of dst [rows][width] = src [width] (launch.hpp: launch_fill_rows), grid-stride over the entries
+template <int T>
+__global__ __launch_bounds__(T) void k_fill_rows(const double *src, int width, size_t total, double *dst) {
+    for (size_t e = (size_t)blockIdx.x * T + threadIdx.x; e < total; e += (size_t)gridDim.x * T) dst[e] = src[e % (size_t)width];
 }
 
 template <int T>
@@ -4748,12 +4784,24 @@ hipError_t launch_gather_rows(int ps, const double *inst, const int *list, int c
     return hipGetLastError();
 }
 hipError_t launch_rollout_backprop(const PlantMapDev &plant, int steps, int batch, const double *J, const double *gu, const double *gtheta,
-                                   double *grad_theta0, double *grad_w, hipStream_t st) {
+                                   double *grad_theta0, double *grad_w, hipStream_t st, const double *u_traj, const double *theta_traj,
+                                   double *grad_f0, double *grad_val) {
     if (batch <= 0) return hipSuccess;
     constexpr int T = 64;
-    const size_t lds = rollout_backprop_lds(plant.k, plant.r);
-    if (steps < 1 || !J || !grad_theta0 || lds > 48 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_rollout_backprop<T>, dim3((unsigned)(batch < 16384 ? batch : 16384)), dim3(T), lds, st, plant, steps, batch, J, gu, gtheta, grad_theta0, grad_w);
+    const bool values = grad_f0 || grad_val;
+    const size_t lds = rollout_backprop_lds(plant.k, plant.r, grad_val != nullptr);
+    if (steps < 1 || !J || (!grad_theta0 && !grad_w && !values) || lds > 48 * 1024) return hipErrorInvalidValue;
+    if (grad_val && (!u_traj || !theta_traj)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rollout_backprop<T>, dim3((unsigned)(batch < 16384 ? batch : 16384)), dim3(T), lds, st, plant, steps, batch, J, gu, gtheta, grad_theta0, grad_w,
+                       u_traj, theta_traj, grad_f0, grad_val);
+    return hipGetLastError();
+}
+hipError_t launch_fill_rows(const double *src, int width, int rows, double *dst, hipStream_t st) {
+    if (rows <= 0 || width <= 0) return hipSuccess;
+    if (!src || !dst) return hipErrorInvalidValue;
+    constexpr int T = 256;
+    const size_t total = (size_t)rows * (size_t)width, nb = (total + T - 1) / T;
+    hipLaunchKernelGGL(k_fill_rows<T>, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(T), 0, st, src, width, total, dst);
     return hipGetLastError();
 }
 // the dynamic-LDS ceiling of the two entry-parallel updateData kernels, set once per handle on the handle's device

@@ -30,8 +30,20 @@ struct ParamMapDev { int k; AffineDev g[3]; };
 // Output map (eicos_batch_set_output_map): u = base + U x, r rows, CSR with n columns, in device memory, shared by every instance
 struct OutMapDev { int r; AffineDev a; };
 // Plant map (eicos_batch_set_plant_map): theta+ = base + F z, k rows, CSR with k + r columns over z = [theta (k) | u (r)], in device
-// memory, shared by every instance; k, r = the parameter and output counts it was validated for
-struct PlantMapDev { int k, r; AffineDev a; };
+// memory, shared by every instance; k, r = the parameter and output counts it was validated for.
+// Per-instance plant values (eicos_batch_set_plant_values): ibase [batch][k] / ival [batch][nnz] in device memory, nnz = rowptr[k] --
+// instance i reads row i of them in the place of a.base / a.val, the pattern stays the shared one; NULL: that group is the shared one.
+struct PlantMapDev { int k, r; AffineDev a; const double *ibase, *ival; int nnz; };
+// the map as instance `id` reads it (uniform id: the two rows stay scalar addresses)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline AffineDev plant_of(const PlantMapDev &M, size_t id) {
+    AffineDev A = M.a;
+    if (M.ibase) A.base = M.ibase + id * (size_t)M.k;
+    if (M.ival) A.val = M.ival + id * (size_t)M.nnz;
+    return A;
+}
 // One rollout, in device memory: theta [batch][steps + 1][k] (row 0 given, the others written by the plant map), u [batch][steps][r],
 // w [batch][steps][k] (NULL: no disturbance), codes / iters [batch][steps]
 struct RolloutDev { int steps; PlantMapDev plant; double *theta, *u; const double *w; int *codes, *iters; };
@@ -197,9 +209,16 @@ hipError_t launch_plant(int ps, const double *inst, int first, int count, const 
 // rollout left it, gu [batch][steps][r] and gtheta [batch][steps + 1][k] (either NULL = 0.0) in, grad_theta0 [batch][k] and grad_w
 // [batch][steps][k] (NULL = not wanted) out, all in device memory; the map by value.  One 64-thread workgroup per instance with
 // rollout_backprop_lds bytes of LDS (at most 48 KB: the caller checks).
-inline size_t rollout_backprop_lds(int k, int r) { return ((size_t)3 * k + 2 * (size_t)r) * sizeof(double); }
+// The plant's own entries (eicos_batch_rollout_plant_gradient): with u_traj [batch][steps][r] and theta_traj [batch][steps + 1][k] of that
+// rollout also grad_f0 [batch][k] and grad_val [batch][plant.nnz] (either NULL = not wanted; grad_theta0 is optional then) -- z_t =
+// [theta_t | u_t] is staged in LDS behind mu (values = true: k + r more doubles).  Instance b sweeps with row b of the per-instance
+// values where the map holds them.  Without the four new arguments: the bits of the sweep as it was.
+inline size_t rollout_backprop_lds(int k, int r, bool values = false) { return ((size_t)(values ? 4 : 3) * k + (values ? 3 : 2) * (size_t)r) * sizeof(double); }
 hipError_t launch_rollout_backprop(const PlantMapDev &plant, int steps, int batch, const double *J, const double *gu, const double *gtheta,
-                                   double *grad_theta0, double *grad_w, hipStream_t st);
+                                   double *grad_theta0, double *grad_w, hipStream_t st, const double *u_traj = nullptr,
+                                   const double *theta_traj = nullptr, double *grad_f0 = nullptr, double *grad_val = nullptr);
+// rows [0, rows) of dst [rows][width] = src [width] (device memory): what the first eicos_batch_set_plant_values of a group starts from
+hipError_t launch_fill_rows(const double *src, int width, int rows, double *dst, hipStream_t st);
 // Selection (eicos_batch_select, _solve_where): the instances of 0 .. batch-1 whose exit class (exit_class.hpp) is in `mask`, compacted
 // in ascending order into cand [batch], their number into *count (both device memory).  The kernel is the one that orders a subset launch
 // (kernels.hip: k_select_order), run without an order array.

@@ -624,6 +624,64 @@ int eicos_multi_rollout_gradient(eicos_multi *mh, const double *gu, const double
     });
 }
 
+// per-instance plant values: rows by global instance id, every shard takes the part of the range it owns.  The row widths are those of
+// the plant map shard 0 holds (eicos_internal_plant_dims: the k it was installed for and its stored entries)
+namespace {
+void plant_dims(eicos_multi *mh, size_t &k, size_t &nnz) {
+    int k_ = 0, nnz_ = 0;
+    (void)eicos_internal_plant_dims(mh->shard[0], &k_, &nnz_);
+    k = (size_t)k_; nnz = (size_t)nnz_;
+}
+} // namespace
+int eicos_multi_set_plant_values(eicos_multi *mh, int first, int count, const double *f0, const double *val) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    if (!eicos_batch_has_plant_map(mh->shard[0])) return mfail(EICOS_E_INVALID, "set_plant_values: no plant map (eicos_multi_set_plant_map installs one)");
+    if (!f0 && !val) return mfail(EICOS_E_INVALID, "set_plant_values: f0 and val are both NULL");
+    size_t k, nnz;
+    plant_dims(mh, k, nnz);
+    const int rc = for_range(mh, first, count, [&](int s, int f, int cnt, size_t off) {
+        return eicos_batch_set_plant_values(mh->shard[s], f, cnt, at(f0, off, k), at(val, off, nnz));
+    });
+    if (rc != EICOS_OK) return rc;
+    // the shards the range missed hold the group too, filled with the shared values: every shard answers has_plant_values alike
+    return for_shards(mh, [&](int s) { return eicos_batch_set_plant_values(mh->shard[s], 0, 0, f0, val); });
+}
+int eicos_multi_plant_values(eicos_multi *mh, int first, int count, double *f0_out, double *val_out) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    if (!eicos_batch_has_plant_map(mh->shard[0])) return mfail(EICOS_E_INVALID, "plant_values: no plant map (eicos_multi_set_plant_map installs one)");
+    if (!f0_out && !val_out) return mfail(EICOS_E_INVALID, "plant_values: f0_out and val_out are both NULL");
+    size_t k, nnz;
+    plant_dims(mh, k, nnz);
+    return for_range(mh, first, count, [&](int s, int f, int cnt, size_t off) {
+        return eicos_batch_plant_values(mh->shard[s], f, cnt, at(f0_out, off, k), at(val_out, off, nnz));
+    });
+}
+int eicos_multi_has_plant_values(eicos_multi *mh) { return mh ? eicos_batch_has_plant_values(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
+int eicos_multi_clear_plant_values(eicos_multi *mh) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    return for_shards(mh, [&](int s) { return eicos_batch_clear_plant_values(mh->shard[s]); });
+}
+// (rows by shard, T = the step count of the trajectory the shards hold: eicos_multi_rollout_gradient)
+int eicos_multi_rollout_plant_gradient(eicos_multi *mh, const double *gu, const double *gtheta, const double *u_traj, const double *theta_traj,
+                                       double *grad_theta0, double *grad_w, double *grad_f0, double *grad_val) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    if (!gu && !gtheta) return mfail(EICOS_E_INVALID, "rollout_plant_gradient: gu and gtheta are both NULL");
+    if (!u_traj || !theta_traj) return mfail(EICOS_E_INVALID, "rollout_plant_gradient: u_traj or theta_traj is NULL");
+    if (!grad_theta0 && !grad_w && !grad_f0 && !grad_val) return mfail(EICOS_E_INVALID, "rollout_plant_gradient: grad_theta0, grad_w, grad_f0 and grad_val are all NULL");
+    const int steps = eicos_batch_rollout_jacobian_steps(mh->shard[0]);
+    for (int s = 0; s < (int)mh->shard.size(); s++)
+        if (steps < 1 || eicos_batch_rollout_jacobian_steps(mh->shard[s]) != steps)
+            return mfail(EICOS_E_INVALID, "rollout_plant_gradient: shard " + std::to_string(s) + " holds no Jacobian trajectory, or one of another length (eicos_multi_rollout_jacobian records one)");
+    const size_t k = (size_t)eicos_batch_param_count(mh->shard[0]), ro = (size_t)eicos_batch_output_count(mh->shard[0]), T = (size_t)steps;
+    size_t k_plant, nnz;
+    plant_dims(mh, k_plant, nnz);
+    return for_shards(mh, [&](int s) {
+        const size_t f = (size_t)mh->first[s];
+        return eicos_batch_rollout_plant_gradient(mh->shard[s], at(gu, f, T * ro), at(gtheta, f, (T + 1) * k), at(u_traj, f, T * ro), at(theta_traj, f, (T + 1) * k),
+                                                  at(grad_theta0, f, k), at(grad_w, f, T * k), at(grad_f0, f, k), at(grad_val, f, nnz));
+    });
+}
+
 int eicos_multi_solution(eicos_multi *mh, double *x) {
     if (!mh || !x) return mfail(EICOS_E_INVALID, "NULL argument");
     if (mh->n == 0) return EICOS_OK;

@@ -519,6 +519,36 @@ namespace EiCOS
         {
             mcheck(eicos_multi_rollout_gradient(h_, gu, gtheta, grad_theta0, grad_w), "eicos_multi_rollout_gradient");
         }
+        // Extension: per-instance plant values -- one controller against many plants.  setPlantValues gives instances [first, first +
+        // count) rows of their own in the place of the plant map's base (f0 [count][k]) and / or stored values (val [count][nnzF],
+        // the map's CSR order; the pattern stays shared); nullptr keeps a group, and the first call of a group starts every instance
+        // from the shared values.  Every rollout form then runs instance i against its own plant, bit for bit the host loop with the
+        // plant evaluated per instance.  plantValues reads rows back (the shared values where none are installed), hasPlantValues: bit
+        // 0 f0, bit 1 val; clearPlantValues and setPlantMap drop them.  rolloutPlantGradient is rolloutGradient over the recorded
+        // trajectory that also returns the gradient with respect to the plant's own entries per instance, grad_f0 [batch][k] and
+        // grad_val [batch][nnzF], from the u_traj and theta_traj rolloutJacobian returned; each output is optional, one must be given
+        // (definition and order: eicos_batch_rollout_plant_gradient of eicos_amd.h).  For the shared plant sum the rows over the batch.
+        void setPlantValues(int first, int count, const double *f0, const double *val)
+        {
+            mcheck(eicos_multi_set_plant_values(h_, first, count, f0, val), "eicos_multi_set_plant_values");
+        }
+        void plantValues(int first, int count, double *f0_out, double *val_out) const
+        {
+            mcheck(eicos_multi_plant_values(h_, first, count, f0_out, val_out), "eicos_multi_plant_values");
+        }
+        int hasPlantValues() const
+        {
+            const int v = eicos_multi_has_plant_values(h_);
+            if (v < 0) mcheck(v, "eicos_multi_has_plant_values");
+            return v;
+        }
+        void clearPlantValues() { mcheck(eicos_multi_clear_plant_values(h_), "eicos_multi_clear_plant_values"); }
+        void rolloutPlantGradient(const double *gu, const double *gtheta, const double *u_traj, const double *theta_traj, double *grad_theta0,
+                                  double *grad_w, double *grad_f0, double *grad_val)
+        {
+            mcheck(eicos_multi_rollout_plant_gradient(h_, gu, gtheta, u_traj, theta_traj, grad_theta0, grad_w, grad_f0, grad_val),
+                   "eicos_multi_rollout_plant_gradient");
+        }
         void solveAsync() { mcheck(eicos_multi_solve_async(h_), "eicos_multi_solve_async"); } // enqueue on every shard's stream
         void sync() { mcheck(eicos_multi_sync(h_), "eicos_multi_sync"); }
         std::vector<double> solution() const

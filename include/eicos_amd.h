@@ -225,7 +225,7 @@ int eicos_batch_update_param_solve(eicos_batch *hd, const double *theta /* [batc
  * affine in the current one and in the move just computed: theta+ = f0 + F [theta | u] (+ w).  A handle holds one such map beside the
  * other two: eicos_affine_map with base[k] and a CSR matrix k x (k + r) (rowptr[k + 1], col / val[rowptr[k]]; columns index
  * z = [theta (k) | u (r)], i.e. lie in [0, k + r)).  eicos_batch_set_plant_map COPIES the host arrays into one device allocation; a later
- * call replaces the map, f = NULL removes it.  It needs a parameter map (k > 0) and an output map (r > 0) and remembers the (k, r) it was
+ * call replaces the map, f = NULL removes it (either way the per-instance values of eicos_batch_set_plant_values are dropped).  It needs a parameter map (k > 0) and an output map (r > 0) and remembers the (k, r) it was
  * validated for.  EICOS_E_INVALID, with a message naming the fault, for rowptr[0] != 0, decreasing row pointers, a column outside
  * [0, k + r), "no parameter map" and "no output map".  eicos_batch_has_plant_map: 1 / 0.
  * eicos_batch_rollout takes every instance through `steps` closed-loop steps in ONE synchronous call.  For instance i:
@@ -529,7 +529,8 @@ int eicos_batch_param_gradient_device(eicos_batch *hd, const int *idx, int count
  * the device form takes all four arrays in device memory, is asynchronous on the handle's stream and returns the same bits.
  * Caveats, beside the one of the definition above (a degenerate optimum gives a smoothed value): with a warm start or a shift map the
  * point step t + 1 returns depends on step t's iterate within the exit tolerance -- the gradient treats each step's solution as a
- * function of theta_t alone; gradients with respect to the maps' own entries are out of scope.
+ * function of theta_t alone; gradients with respect to the plant map's own entries come from eicos_batch_rollout_plant_gradient (below),
+ * those with respect to the entries of the parameter, matrix, output and fallback maps are out of scope.
  * Refusals (EICOS_E_INVALID with a message, nothing changed): rollout_jacobian -- everything eicos_batch_rollout refuses, a NULL J_traj,
  * a matrix map that does not fit the parameter map; rollout_gradient -- no J trajectory on the handle, a parameter, matrix, output or
  * plant map installed since that rollout, both cotangents NULL, a NULL grad_theta0, host and device pointers mixed (as
@@ -539,6 +540,61 @@ int eicos_batch_rollout_jacobian(eicos_batch *hd, int steps, const double *theta
 int eicos_batch_rollout_jacobian_steps(eicos_batch *hd); /* T of the J trajectory the handle holds; 0: none */
 int eicos_batch_rollout_gradient(eicos_batch *hd, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w);
 int eicos_batch_rollout_gradient_device(eicos_batch *hd, const double *dgu, const double *dgtheta, double *dgrad_theta0, double *dgrad_w);
+
+/* ---- per-instance plant values, and the gradient with respect to the plant's entries (no reference counterpart).  A robustness study
+ * runs ONE controller against MANY plants: every instance of the batch simulated against its own true system.  That cannot go through
+ * theta (F(phi) [theta | u] is bilinear), so a handle with a plant map may also hold, per instance, values of its own for the map:
+ * f0_i [batch][k] in the place of base and / or val_i [batch][nnzF] in the place of val, nnzF = rowptr[k] of the installed map, in its
+ * stored CSR order.  The pattern (rowptr, col) stays the shared one.  In every rollout form -- eicos_batch_rollout, _rollout_jacobian,
+ * fused or not, _rollout_gradient, and the eicos_multi_* forms -- the plant row of instance i is then formed with exactly the arithmetic
+ * stated at eicos_batch_rollout, reading f0_i[i] / val_i[i]:  acc = f0_i[i][j];  acc = acc + (val_i[i][s] * z[col[s]]) in stored order;
+ * then + w.  A group that was never given stays the shared one.  The contract is the usual one, bit for bit: the rollout equals the host
+ * loop of eicos_batch_update_param_solve with the plant evaluated per instance on the host, rollout_jacobian equals its host twin with
+ * the same plant, and rollout_gradient sweeps with val_i of each instance.  A handle without per-instance values takes exactly the code
+ * paths and returns exactly the bits it did before.
+ * eicos_batch_set_plant_values: rows of instances [first, first + count) from host arrays f0 [count][k] and / or val [count][nnzF]
+ * (either NULL = keep that group; synchronous).  The FIRST call of a group allocates its [batch][...] array and fills EVERY instance
+ * with the shared values, then overwrites the given range: instances outside every range given so far behave exactly as under the
+ * shared map.  _device: the same from device arrays, asynchronous on the handle's stream.  eicos_batch_plant_values reads rows back
+ * into host arrays (either NULL = not wanted): the installed rows, and the shared values where none are installed.
+ * eicos_batch_has_plant_values: bit 0 f0, bit 1 val.  eicos_batch_clear_plant_values drops both groups (it waits for the handle's
+ * stream).  eicos_batch_set_plant_map, whether it installs or removes a map, drops them too: the pattern may have changed.  Setting and
+ * clearing values count as a map install for eicos_batch_rollout_gradient, which refuses a Jacobian trajectory recorded before them.
+ * eicos_batch_rollout_plant_gradient / _device: eicos_batch_rollout_gradient over the handle's recorded J trajectory -- the same
+ * grad_theta0 / grad_w bits, each optional here -- that also returns the gradient of L with respect to the plant's own entries, per
+ * instance: grad_f0 [batch][k] and grad_val [batch][nnzF] (each optional; at least one of the four outputs).  u_traj [batch][T][r] and
+ * theta_traj [batch][T+1][k] are the arrays that rollout_jacobian returned -- the fallback law's rows included where it fired, because
+ * that is what the plant read.  For instance b, every product and sum rounded on its own:
+ *
+ *     gf0[i] = 0.0, gval[s] = 0.0;  lambda = gtheta[T]
+ *     for t = T-1 .. 0:
+ *         gf0[i]  = gf0[i]  + lambda[i]                                 (i in [0, k))
+ *         gval[s] = gval[s] + (lambda[row(s)] * z_t[col[s]])            (s in stored order; z_t = [theta_traj[b][t] | u_traj[b][t]])
+ *         ... the recursion of eicos_batch_rollout_gradient for grad_w[t], v, mu, lambda' ...   (with val_i of instance b where installed)
+ *     grad_theta0 = lambda
+ *     gf0[i] = gf0[i] + (0.0 * lambda[i]);  gval[s] = gval[s] + (0.0 * lambda[row(s)])
+ *
+ * A NaN Jacobian row makes all of that instance's rows NaN: one of a step t >= 1 through lambda, one of step 0 -- which the sums never
+ * meet -- through the last line, which leaves finite rows as they are.  The call also works with the shared plant; the gradient of a
+ * shared entry is the sum of its rows over the batch, which the caller forms.  One thread owns f0 row i and the stored values of row i
+ * and accumulates them over t in the stated order, so the bits do not depend on the launch.
+ * Refusals (EICOS_E_INVALID with the cause named, nothing changed): no plant map; an instance range out of bounds; both groups NULL; host
+ * and device pointers mixed or handed to the wrong form (as eicos_batch_param_gradient refuses them); for the gradient call everything
+ * eicos_batch_rollout_gradient refuses except a NULL grad_theta0, a NULL u_traj or theta_traj, and all four outputs NULL.
+ * Out of scope: per-instance patterns, an indexed form, per-instance parameter / output / fallback maps. */
+int eicos_batch_set_plant_values(eicos_batch *hd, int first, int count, const double *f0 /* [count][k], optional */,
+                                 const double *val /* [count][nnzF], optional */);
+int eicos_batch_set_plant_values_device(eicos_batch *hd, int first, int count, const double *df0, const double *dval);
+int eicos_batch_plant_values(eicos_batch *hd, int first, int count, double *f0_out, double *val_out);
+int eicos_batch_has_plant_values(eicos_batch *hd); /* bit 0: f0, bit 1: val */
+int eicos_batch_clear_plant_values(eicos_batch *hd);
+int eicos_batch_rollout_plant_gradient(eicos_batch *hd, const double *gu, const double *gtheta, const double *u_traj /* [batch][T][r] */,
+                                       const double *theta_traj /* [batch][T+1][k] */, double *grad_theta0 /* optional */,
+                                       double *grad_w /* optional */, double *grad_f0 /* [batch][k], optional */,
+                                       double *grad_val /* [batch][nnzF], optional */);
+int eicos_batch_rollout_plant_gradient_device(eicos_batch *hd, const double *dgu, const double *dgtheta, const double *du_traj,
+                                              const double *dtheta_traj, double *dgrad_theta0, double *dgrad_w, double *dgrad_f0,
+                                              double *dgrad_val);
 /* eicos_batch_update_param_solve_subset: the closed-loop step over a subset = eicos_batch_update_param_indexed + eicos_batch_solve_subset
  * + eicos_batch_outputs_indexed (+ the x rows), every array in list order; synchronous.
  * Fused under exactly the conditions of eicos_batch_update_param_solve (an LDS vector, a theta row that fits it, GPU-addressable theta,
@@ -814,6 +870,15 @@ int eicos_multi_rollout(eicos_multi *mh, int steps, const double *theta0, const 
 int eicos_multi_rollout_jacobian(eicos_multi *mh, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
                                  int *exitcodes, int *iters, double *J_traj, double *res_traj);
 int eicos_multi_rollout_gradient(eicos_multi *mh, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w);
+/* per-instance plant values (eicos_batch_set_plant_values / _plant_values / _has_plant_values / _clear_plant_values): rows by global
+ * instance id, every shard takes the part of the range it owns; eicos_multi_rollout_plant_gradient: rows by shard, as
+ * eicos_multi_rollout_gradient's */
+int eicos_multi_set_plant_values(eicos_multi *mh, int first, int count, const double *f0, const double *val);
+int eicos_multi_plant_values(eicos_multi *mh, int first, int count, double *f0_out, double *val_out);
+int eicos_multi_has_plant_values(eicos_multi *mh);
+int eicos_multi_clear_plant_values(eicos_multi *mh);
+int eicos_multi_rollout_plant_gradient(eicos_multi *mh, const double *gu, const double *gtheta, const double *u_traj, const double *theta_traj,
+                                       double *grad_theta0, double *grad_w, double *grad_f0, double *grad_val);
 /* matrix map (eicos_batch_set_matrix_map / _has_matrix_map on every shard): installed on every shard; the theta-consuming calls above pick
  * it up shard by shard */
 int eicos_multi_set_matrix_map(eicos_multi *mh, const eicos_affine_map *G, const eicos_affine_map *A);
