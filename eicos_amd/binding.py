@@ -70,12 +70,20 @@ class Settings(C.Structure):
 SETTINGS_FIELDS = tuple(k for k, _ in Settings._fields_)
 
 
+DATA_GRADIENT_KEYS = ("grad_c", "grad_h", "grad_b", "grad_G", "grad_A", "grad_Cval", "grad_Hval", "grad_Bval", "grad_u0", "grad_Uval")
+
+
 class Retry(C.Structure):
     """struct eicos_retry: the retry policy of a handle (a second attempt inside the solve launch for the exit classes of `mask`)."""
     _fields_ = [("mask", C.c_uint), ("warm", C.c_double), ("dyn_delta", C.c_double), ("dyn_eps", C.c_double), ("settings", Settings)]
 
     def asdict(self):
         return {"mask": int(self.mask), "warm": self.warm, "dyn": (self.dyn_delta, self.dyn_eps), "settings": self.settings.asdict()}
+
+
+class DataGradient(C.Structure):
+    """eicos_data_gradient: the output pointers of eicos_batch_rollout_data_gradient, NULL = not wanted."""
+    _fields_ = [(k, C.c_void_p) for k in DATA_GRADIENT_KEYS]
 
 
 def library_path() -> str:
@@ -132,6 +140,10 @@ def _signatures():
         ("eicos_*_set_plant_values", [vp, i, i, dp, dp]), ("eicos_batch_set_plant_values_device", [vp, i, i, vp, vp]),
         ("eicos_*_plant_values", [vp, i, i, dp, dp]), ("eicos_*_has_plant_values", [vp]), ("eicos_*_clear_plant_values", [vp]),
         ("eicos_*_rollout_plant_gradient", [vp] + [dp] * 8), ("eicos_batch_rollout_plant_gradient_device", [vp] + [vp] * 8),
+        # a recording rollout and the gradient with respect to the controller's own data (the struct of output pointers travels as void *)
+        ("eicos_data_gradient_size", [], size), ("eicos_*_set_rollout_recording", [vp, i]), ("eicos_*_rollout_recording", [vp]),
+        ("eicos_*_rollout_records", [vp] + [dp] * 6), ("eicos_*_rollout_data_gradient", [vp, dp, dp, dp, vp]),
+        ("eicos_batch_rollout_data_gradient_device", [vp, vp, vp, vp, vp]),
         # solve, subset solves, results
         ("eicos_*_solve", [vp, ip]), ("eicos_*_solve_async", [vp]), ("eicos_*_sync", [vp]), ("eicos_*_select", [vp, u, ip, ip]),
         ("eicos_*_solve_subset_async", [vp, ip, i]), ("eicos_*_solve_subset", [vp, ip, i, ip]), ("eicos_*_solve_where", [vp, u, ip, ip, ip]),
@@ -189,6 +201,8 @@ def _lib():
             raise RuntimeError(f"{path}: struct eicos_settings has {L.eicos_settings_size()} bytes, the ctypes mirror {C.sizeof(Settings)}")
         if "eicos_retry_size" in found and L.eicos_retry_size() != C.sizeof(Retry):
             raise RuntimeError(f"{path}: struct eicos_retry has {L.eicos_retry_size()} bytes, the ctypes mirror {C.sizeof(Retry)}")
+        if "eicos_data_gradient_size" in found and L.eicos_data_gradient_size() != C.sizeof(DataGradient):
+            raise RuntimeError(f"{path}: struct eicos_data_gradient has {L.eicos_data_gradient_size()} bytes, the ctypes mirror {C.sizeof(DataGradient)}")
         _LIB = L
     return _LIB
 
@@ -553,6 +567,101 @@ class PlantMap:
         return g0, gw, gf0, gval
 
 
+def _dense_rows(omap):
+    """The rows of an OutputMap as a dense [r, n] block, formed as the contracted adjoint forms its right-hand sides: zero-filled, then
+    the entries of a column summed in stored order."""
+    U = np.zeros((omap.r, omap.n))
+    for a in range(omap.r):
+        for t in range(int(omap.rowptr[a]), int(omap.rowptr[a + 1])):
+            U[a, omap.col[t]] = U[a, omap.col[t]] + omap.val[t]
+    return U
+
+
+def rollout_data_backprop(pattern, pmap, omap, fmap, J, W, x, y, z, theta, gu=None, gtheta=None, val=None, want=DATA_GRADIENT_KEYS):
+    """The host restatement of eicos_batch_rollout_data_gradient, bit for bit: the gradient of L = sum_t gu_t' u_t + sum_t gtheta_t'
+    theta_t with respect to the controller's own data, per instance, as a dict over `want` (DATA_GRADIENT_KEYS).  pattern: the Pattern
+    (Gjc, Gir, Ajc, Air give the (row, column) of every stored value); pmap / omap / fmap: the ParamMap, OutputMap and PlantMap of the
+    rollout; J [B, T, r, k] what rollout_jacobian returned; W = (Wc [B, T, r, n], Wh [B, T, r, m], Wb [B, T, r, p]) and x [B, T, n],
+    y [B, T, p], z [B, T, m] its records (rollout_records); theta [B, T + 1, k] its theta trajectory; val [B, nnzF]: the per-instance
+    plant values it ran under.  mu_t is PlantMap.backprop's; behind it, for t = T-1 .. 0, every product and sum rounded on its own:
+    d[i] = 0.0, then d[i] + (mu_t[a] * W_t[a][i]) for a ascending; grad_c[i] + d_c[i]; grad_Cval[s] + (d_c[i] * theta_t[col[s]]);
+    grad_G[e] + ((d_c[j] * z_t[i]) - (d_h[i] * x_t[j])), grad_A with y_t and d_b; grad_u0[a] + mu_t[a]; grad_Uval[s] + (mu_t[row(s)] *
+    x_t[col[s]]).  A NaN row of W makes the sums it enters NaN; other instances are untouched."""
+    k, r = fmap.k, fmap.r
+    J = np.ascontiguousarray(J, dtype=np.float64)
+    if J.ndim != 4 or J.shape[2:] != (r, k):
+        raise ValueError(f"J has shape {J.shape}, expected [batch, steps, {r}, {k}]")
+    B, T = int(J.shape[0]), int(J.shape[1])
+    n, m, p = int(pattern.n), int(pattern.m), int(pattern.p)
+    if omap.r != r or omap.n != n or pmap.k != k:
+        raise ValueError(f"the maps do not fit: output map {omap.r} x {omap.n}, parameter map k = {pmap.k}, plant map (k, r) = ({k}, {r}), n = {n}")
+    if gu is None and gtheta is None:
+        raise ValueError("gu and gtheta are both None")
+    gu, gtheta = _cotangent(gu, (B, T, r), "gu"), _cotangent(gtheta, (B, T + 1, k), "gtheta")
+    theta = _cotangent(theta, (B, T + 1, k), "theta")
+    if theta is None or W is None or len(W) != 3:
+        raise ValueError("theta and W = (Wc, Wh, Wb) are needed")
+    W = [_cotangent(a, (B, T, r, w), name) for a, w, name in zip(W, (n, m, p), ("Wc", "Wh", "Wb"))]
+    x, y, z = _cotangent(x, (B, T, n), "x"), _cotangent(y, (B, T, p), "y"), _cotangent(z, (B, T, m), "z")
+    if any(a is None for a in W + [x, y, z]):
+        raise ValueError("Wc, Wh, Wb, x, y and z (rollout_records) are all needed")
+    unknown = [q for q in want if q not in DATA_GRADIENT_KEYS]
+    if unknown or not want:
+        raise ValueError(f"want must name some of {DATA_GRADIENT_KEYS}, got {tuple(want)}")
+    groups = pmap.groups()
+    for q, name in enumerate(("grad_Cval", "grad_Hval", "grad_Bval")):
+        if name in want and groups[q] is None:
+            raise ValueError(f"{name} asked, but the parameter map has no {'chb'[q]} group")
+    val_i = fmap._instance_values(B, None, val)[1]
+    Gcol = np.repeat(np.arange(n), np.diff(pattern.Gjc)) if pattern.nnzG else np.zeros(0, np.int64)
+    Acol = np.repeat(np.arange(n), np.diff(pattern.Ajc)) if pattern.nnzA else np.zeros(0, np.int64)
+    Gir, Air = np.asarray(pattern.Gir, np.int64)[:pattern.nnzG], np.asarray(pattern.Air, np.int64)[:pattern.nnzA]
+    Urow = np.repeat(np.arange(r), np.diff(omap.rowptr[:r + 1]))
+    nnzU = int(omap.rowptr[r])
+    Ucol = np.asarray(omap.col[:nnzU], np.int64)
+    rows_of = [None if g is None else np.repeat(np.arange(w), np.diff(g[1][:w + 1])) for g, w in zip(groups, (n, m, p))]
+    out = {"grad_c": np.zeros((B, n)), "grad_h": np.zeros((B, m)), "grad_b": np.zeros((B, p)), "grad_G": np.zeros((B, pattern.nnzG)),
+           "grad_A": np.zeros((B, pattern.nnzA)), "grad_u0": np.zeros((B, r)), "grad_Uval": np.zeros((B, nnzU))}
+    for q, name in enumerate(("grad_Cval", "grad_Hval", "grad_Bval")):
+        out[name] = np.zeros((B, 0 if groups[q] is None else int(groups[q][1][(n, m, p)[q]])))
+    rowptr, col = fmap.rowptr, fmap.col
+    zero = np.float64(0.0)
+    with np.errstate(invalid="ignore"):
+        for b in range(B):
+            fval = fmap.val if val_i is None else val_i[b]
+            lam = [gtheta[b, T, c] if gtheta is not None else zero for c in range(k)]
+            for t in range(T - 1, -1, -1):
+                v = [zero] * (k + r)
+                for i in range(k):
+                    for s in range(int(rowptr[i]), int(rowptr[i + 1])):
+                        v[col[s]] = v[col[s]] + (fval[s] * lam[i])
+                mu = np.array([(gu[b, t, j] if gu is not None else zero) + v[k + j] for j in range(r)])
+                d = []
+                for Wg, w in zip(W, (n, m, p)):
+                    acc = np.zeros(w)
+                    for a in range(r):
+                        acc = acc + (mu[a] * Wg[b, t, a])
+                    d.append(acc)
+                for q, name in enumerate(("grad_c", "grad_h", "grad_b")):
+                    out[name][b] = out[name][b] + d[q]
+                for q, name in enumerate(("grad_Cval", "grad_Hval", "grad_Bval")):
+                    if groups[q] is not None and out[name].shape[1]:
+                        nz = out[name].shape[1]
+                        out[name][b] = out[name][b] + (d[q][rows_of[q]] * theta[b, t, groups[q][2][:nz]])
+                out["grad_G"][b] = out["grad_G"][b] + ((d[0][Gcol] * z[b, t, Gir]) - (d[1][Gir] * x[b, t, Gcol]))
+                out["grad_A"][b] = out["grad_A"][b] + ((d[0][Acol] * y[b, t, Air]) - (d[2][Air] * x[b, t, Acol]))
+                out["grad_u0"][b] = out["grad_u0"][b] + mu
+                out["grad_Uval"][b] = out["grad_Uval"][b] + (mu[Urow] * x[b, t, Ucol])
+                new = []
+                for c in range(k):
+                    acc = (gtheta[b, t, c] if gtheta is not None else zero) + v[c]
+                    for j in range(r):
+                        acc = acc + (J[b, t, j, c] * mu[j])
+                    new.append(acc)
+                lam = new
+    return {q: out[q] for q in want}
+
+
 def _plant_map_ptr(fmap, k, r):
     """A PlantMap as (keep-alive objects, C pointer to eicos_affine_map) for a handle with k parameters and r outputs."""
     return _affine_ptr((fmap.base, fmap.rowptr, fmap.col, fmap.val), k, f"plant map: k = {fmap.k}, r = {fmap.r}, ",
@@ -789,11 +898,13 @@ class _Solver:
     # ---- parametric right-hand sides (include/eicos_amd.h: eicos_batch_set_param_map / eicos_batch_update_param) ----
     def set_param_map(self, pmap: "ParamMap | None"):
         """Install (copy) a ParamMap for all instances; None, or a map without groups, removes the installed one."""
+        self._param_nnz = (0, 0, 0)  # (the widths of rollout_data_gradient's slope outputs: the stored entries of the installed groups)
         if pmap is None:
             self._call("set_param_map", 0, None, None, None)
             return
         _keep, ptr = _param_map_ptrs(pmap, self.pat)
         self._call("set_param_map", pmap.k, *ptr)
+        self._param_nnz = tuple(0 if g is None else int(g[1][-1]) for g in pmap.groups())
 
     def param_count(self) -> int:
         """k of the installed parameter map, 0 without one."""
@@ -813,11 +924,13 @@ class _Solver:
     # ---- output map and the closed-loop step (include/eicos_amd.h: eicos_batch_set_output_map / eicos_batch_update_param_solve) ----
     def set_output_map(self, omap: "OutputMap | None"):
         """Install (copy) an OutputMap for all instances; None, or a map without rows, removes the installed one."""
+        self._out_nnz = 0
         if omap is None or omap.r == 0:
             self._call("set_output_map", 0, None)
             return
         _keep, ptr = _output_map_ptr(omap, self.pat)
         self._call("set_output_map", omap.r, ptr)
+        self._out_nnz = int(omap.rowptr[-1])
 
     def output_count(self) -> int:
         """r of the installed output map, 0 without one."""
@@ -980,6 +1093,87 @@ class _Solver:
         else:
             self._call("rollout_gradient", *[_dp_or_dummy(a) for a in (gu, gtheta, g0, gw)])
         return g0, gw
+
+    # ---- a recording rollout and the gradient with respect to the controller's own data (include/eicos_amd.h) ----
+    def set_rollout_recording(self, on: bool):
+        """From now on rollout_jacobian() also records, on the GPU, the gradient rows of every step's output rows and the step's x, y, z
+        (off by default; batch * T * (r + 1) * (n + m + p) * 8 bytes): what rollout_data_gradient() sweeps over.  Everything
+        rollout_jacobian() returns, and the handle's state afterwards, keep their bits."""
+        self._call("set_rollout_recording", 1 if on else 0)
+
+    def rollout_recording(self) -> bool:
+        return _nonneg(self._query("rollout_recording")) != 0
+
+    def rollout_records(self):
+        """(Wc [batch, T, r, n], Wh [batch, T, r, m], Wb [batch, T, r, p], x [batch, T, n], y [batch, T, p], z [batch, T, m]) of the most
+        recent rollout_jacobian() under recording: per step the rows adjoint(g = the dense rows of the output map) returns there (0.0
+        where the fallback law fired, NaN where the step did not end optimal) and the result rows the step's u was formed from."""
+        shape = getattr(self, "_rollout_shape", None)
+        if shape is None:  # (no rollout_jacobian yet: the library refuses, with its message)
+            self._call("rollout_records", *[None] * 6)
+            raise RuntimeError("rollout_records: no rollout_jacobian() on this handle")
+        T, k, r = shape
+        B, n, m, p = self.batch, self.pat.n, self.pat.m, self.pat.p
+        outs = (np.zeros((B, T, r, n)), np.zeros((B, T, r, m)), np.zeros((B, T, r, p)), np.zeros((B, T, n)), np.zeros((B, T, p)), np.zeros((B, T, m)))
+        self._call("rollout_records", *[_dp_or_dummy(a) for a in outs])
+        return outs
+
+    def rollout_data_gradient(self, theta, gu=None, gtheta=None, want=DATA_GRADIENT_KEYS, device=False):
+        """The gradient of L = sum_t gu_t' u_t + sum_t gtheta_t' theta_t over the most recent rollout_jacobian() under recording with
+        respect to the controller's own data, per instance (sum the rows over the batch for shared data): a dict over `want`, some of
+        DATA_GRADIENT_KEYS -- grad_c [batch, n], grad_h, grad_b, grad_G [batch, nnzG], grad_A, grad_Cval / _Hval / _Bval [batch, stored
+        entries of the parameter map's group], grad_u0 [batch, r], grad_Uval [batch, nnzU].  theta [batch, T + 1, k]: the trajectory
+        that rollout returned.  Bit for bit rollout_data_backprop() of the records.  device=True as in rollout_gradient()."""
+        shape = getattr(self, "_rollout_shape", None)
+        want = tuple(want)
+        unknown = [q for q in want if q not in DATA_GRADIENT_KEYS]
+        if unknown or not want:
+            raise ValueError(f"want must name some of {DATA_GRADIENT_KEYS}, got {want}")
+        if shape is None:  # (no rollout_jacobian yet: the library refuses, with its message)
+            one = np.zeros(1)
+            st = DataGradient(grad_c=one.ctypes.data)
+            self._call("rollout_data_gradient", _dp(one), None, _dp(one), C.byref(st))
+            raise RuntimeError("rollout_data_gradient: no rollout_jacobian() on this handle")
+        T, k, r = shape
+        B = self.batch
+        if gu is None and gtheta is None:
+            raise ValueError("gu and gtheta are both None")
+        gu, gtheta = _cotangent(gu, (B, T, r), "gu"), _cotangent(gtheta, (B, T + 1, k), "gtheta")
+        theta = _cotangent(theta, (B, T + 1, k), "theta")
+        if theta is None:
+            raise ValueError("theta (the trajectory of the rollout) is needed")
+        nnzG, nnzA, n, m, p = self._widths()
+        widths = dict(zip(DATA_GRADIENT_KEYS, (n, m, p, nnzG, nnzA) + tuple(getattr(self, "_param_nnz", (0, 0, 0))) + (r, getattr(self, "_out_nnz", 0))))
+        outs = {q: np.zeros((B, widths[q])) for q in want}
+        if not device:
+            # (an empty array travels as a one-element dummy: the library sees that the output was asked for)
+            keep = {q: (a if a.size else np.zeros(1)) for q, a in outs.items()}
+            st = DataGradient(**{q: a.ctypes.data for q, a in keep.items()})
+            self._call("rollout_data_gradient", _dp_or_dummy(gu), _dp_or_dummy(gtheta), _dp_or_dummy(theta), C.byref(st))
+            return outs
+        if self._prefix != "eicos_batch_":
+            raise ValueError("rollout_data_gradient: device=True needs a single-GPU handle")
+        hip = _lib()
+        ins, names, bufs = (gu, gtheta, theta), list(outs), []
+        try:
+            for a in list(ins) + [outs[q] for q in names]:
+                d = C.c_void_p()
+                if a is not None and hip.hipMalloc(C.byref(d), max(a.nbytes, 8)) != 0:
+                    raise RuntimeError("hipMalloc failed")
+                bufs.append(d)
+            for a, d in zip(ins, bufs):
+                if a is not None and a.nbytes and hip.hipMemcpy(d, a.ctypes.data, a.nbytes, 1) != 0:  # hipMemcpyHostToDevice
+                    raise RuntimeError("hipMemcpy failed")
+            st = DataGradient(**{q: d.value for q, d in zip(names, bufs[3:])})
+            self._call("rollout_data_gradient_device", *bufs[:3], C.byref(st))
+            self._call("sync")
+            for q, d in zip(names, bufs[3:]):
+                if outs[q].nbytes and hip.hipMemcpy(outs[q].ctypes.data, d, outs[q].nbytes, 2) != 0:  # hipMemcpyDeviceToHost
+                    raise RuntimeError("hipMemcpy failed")
+        finally:
+            for d in bufs:
+                hip.hipFree(d)
+        return outs
 
     # ---- per-instance plant values (include/eicos_amd.h: eicos_batch_set_plant_values / _rollout_plant_gradient) ----
     def _plant_widths(self):

@@ -191,6 +191,13 @@ struct eicos_batch {
     // grad_w] of the gradient call's host form.  rollJ_steps = 0: no trajectory on the handle; rollJ_plant, rollJ_k / _r = the plant map and counts it was
     // recorded under; map_gen counts the installs of the parameter, matrix, output, plant and fallback maps, rollJ_gen = its value at that rollout.
     DevBuf d_rollJ, d_rollG; int rollJ_steps = 0, rollJ_k = 0, rollJ_r = 0; PlantMapDev rollJ_plant{}; unsigned long map_gen = 0, rollJ_gen = 0;
+    // A recording rollout (eicos_batch_set_rollout_recording; launch.hpp: AdjointDev::x_rec): d_rollW = [Wc [batch][steps][r][n] | Wh
+    // [..][m] | Wb [..][p] | x [batch][steps][n] | y [..][p] | z [..][m] | one step's rows of the six (the path that is not fused)],
+    // made by the first recording rollout and grown on demand, freed (with d_rollD) when recording is switched off -- never touched while it is off.  rollW_on: the trajectory the
+    // handle holds (rollJ_steps) was recorded with its rows.  d_rollD = the staging of eicos_batch_rollout_data_gradient: the
+    // workgroups' contracted rows and, in the host form, its inputs and outputs.
+    DevBuf d_rollW, d_rollD; bool roll_recording = false, rollW_on = false;
+    int param_nnz[3] = {0, 0, 0}, out_nnz = 0; // stored entries of the installed parameter map's groups and of the output map (the widths of their slope gradients)
     hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr; bool adjoint_timed = false; // HIP events around the most recent adjoint launch (eicos_batch_last_adjoint_ms)
 
     // The events and the stream the handle made; the buffers free themselves after this body.  eicos_batch_destroy has set the device and
@@ -1173,7 +1180,9 @@ int eicos_batch_set_param_map(eicos_batch *h, int k, const eicos_affine_map *c, 
     }
     ParamMapDev M{};
     M.k = k;
-    return install_map(h, h->d_param, h->param, "parameter", g, 3, 0, remove ? nullptr : &M, M.g);
+    const int rc = install_map(h, h->d_param, h->param, "parameter", g, 3, 0, remove ? nullptr : &M, M.g);
+    for (int q = 0; q < 3; q++) h->param_nnz[q] = h->param.g[q].base ? g[q].map->rowptr[g[q].rows] : 0;
+    return rc;
 }
 
 int eicos_batch_param_count(eicos_batch *h) { return h ? h->param.k : fail(EICOS_E_INVALID, "NULL handle"); }
@@ -1212,6 +1221,7 @@ int eicos_batch_set_output_map(eicos_batch *h, int r, const eicos_affine_map *u)
     M.r = r;
     const int rc = install_map(h, h->d_out, h->out, "output", &g, 1, (size_t)h->batch * r * sizeof(double), remove ? nullptr : &M, &M.a);
     h->d_u = h->d_out ? reinterpret_cast<double *>(h->d_out.as<char>() + MAP_HEADER) : nullptr;
+    h->out_nnz = h->out.r ? u->rowptr[r] : 0;
     return rc;
 }
 
@@ -1777,13 +1787,17 @@ int eicos_batch_outputs_indexed_device(eicos_batch *h, const int *idx, int count
 // One launch of the handle's adjoint kernel (launch.hpp: AdjointLaunch) behind everything on the handle's stream, under the handle's settings
 // and dynamic regularisation.  Every check stands in front of the first enqueue: a refused call changes nothing.
 namespace {
+struct RecordRows;
 struct AdjointCall {
     const int *idx; int count, nrhs; // nrhs: right-hand sides per instance (the Jacobian form: r)
     const double *g; double *grad_c, *grad_h, *grad_b, *res, *J; // host arrays of the gradient form; J / res of the contracted form
     bool jac, device; // the contracted form (launch.hpp: AdjointDev::J); its J, res and g live in device memory (asynchronous)
     double *grad_G = nullptr, *grad_A = nullptr; // the gradient form: the matrix gradients (host, optional)
     bool mmap = false, grows = false; // the contracted form: the matrix map joins when one is installed; the right-hand sides are nrhs rows of g
+    const struct RecordRows *rec = nullptr; // the contracted device form of a recording rollout: where the step's rows go (device memory)
 };
+// One step's rows of a recording rollout, or the whole record (eicos_batch::d_rollW)
+struct RecordRows { double *Wc, *Wh, *Wb, *x, *y, *z; };
 static_assert(sizeof(AdjointDev) <= MAP_HEADER, "the adjoint record larger than its header");
 }
 static int adjoint_list_fault(const eicos_batch *h, const int *idx, int count, const char *who) {
@@ -1828,6 +1842,7 @@ static int adjoint_run(eicos_batch *h, const AdjointCall &c) {
         else rec.omap = h->d_out.as<const OutMapDev>();
         rec.J = c.device ? c.J : dbl(at_c);
         rec.res = c.device ? c.res : (c.res ? dbl(at_r) : nullptr);
+        if (c.rec) { rec.grad_c = c.rec->Wc; rec.grad_h = c.rec->Wh; rec.grad_b = c.rec->Wb; rec.x_rec = c.rec->x; rec.y_rec = c.rec->y; rec.z_rec = c.rec->z; }
     } else {
         rec.nrhs = c.nrhs; rec.g = dbl(at_g);
         rec.grad_c = c.grad_c && D.n ? dbl(at_c) : nullptr; rec.grad_h = c.grad_h && D.m ? dbl(at_h) : nullptr;
@@ -1893,7 +1908,7 @@ int eicos_batch_adjoint_data(eicos_batch *h, const int *idx, int count, int nrhs
 // The contracted forms through whichever of the parameter map and the matrix map are installed (eicos_batch_param_jacobian: the rows of
 // the output map; eicos_batch_param_gradient: nrhs rows of g per instance).  out = J or grad_theta.
 static int param_contracted(eicos_batch *h, const int *idx, int count, int nrhs, const double *g, bool grows, double *out, const char *out_name,
-                            double *res, bool device, const char *who) {
+                            double *res, bool device, const char *who, const RecordRows *rows = nullptr) {
     const int rc = adjoint_list_fault(h, idx, count, who);
     if (rc != EICOS_OK) return rc;
     const std::string w(who);
@@ -1911,7 +1926,7 @@ static int param_contracted(eicos_batch *h, const int *idx, int count, int nrhs,
     if (count > 0 && grows && g && (memory_kind(g, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": g" + other);
     if (count > 0 && res && (memory_kind(res, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": res must live where " + out_name + " lives");
     AdjointCall c{idx, count, grows ? nrhs : h->out.r, g, nullptr, nullptr, nullptr, res, out, true, device};
-    c.mmap = true; c.grows = grows;
+    c.mmap = true; c.grows = grows; c.rec = rows;
     return adjoint_run(h, c);
 }
 int eicos_batch_param_jacobian(eicos_batch *h, const int *idx, int count, double *J, double *res) {
@@ -2239,6 +2254,27 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
         HIP_TRY_AS("hipMalloc", h->d_rollJ.reserve(MAP_HEADER + (n_J + n_res + n_J1 + n_res1) * sizeof(double), h->stream));
         d_J = reinterpret_cast<double *>(h->d_rollJ.as<char>() + MAP_HEADER); d_res = d_J + n_J; d_J1 = d_res + n_res; d_res1 = d_J1 + n_J1;
     }
+    const bool fused = fused_rollout_fits(fit_shape(h), k, r, h->mat.k != 0) && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
+    // a recording rollout: the whole record and, on the path that is not fused, one step's rows behind it (launch.hpp: AdjointDev::x_rec)
+    const bool recording = sens && h->roll_recording;
+    RecordRows W{}, W1{};
+    const size_t wn = (size_t)h->dp.n, wm = (size_t)h->dp.m, wp = (size_t)h->dp.p;
+    if (recording) {
+        h->rollW_on = false;
+        const size_t bytes = (B * T + (fused ? 0 : B)) * ((size_t)r + 1) * (wn + wm + wp) * sizeof(double);
+        if (h->d_rollW.reserve(bytes, h->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(EICOS_E_HIP, "rollout_jacobian: the record of a recording rollout (batch * steps * (r + 1) * (n + m + p) * 8, and one step more where the rollout is not fused: " + std::to_string(bytes) +
+                                         " bytes) could not be allocated: record fewer steps or a smaller batch, or switch recording off");
+        }
+        double *at = h->d_rollW.as<double>();
+        auto take = [&](RecordRows &R, size_t rows) {
+            R.Wc = at; at += rows * r * wn; R.Wh = at; at += rows * r * wm; R.Wb = at; at += rows * r * wp;
+            R.x = at; at += rows * wn; R.y = at; at += rows * wp; R.z = at; at += rows * wm;
+        };
+        take(W, B * T);
+        if (!fused) take(W1, B);
+    }
     const size_t n_th = B * (T + 1) * k, n_u = B * T * r, n_w = w ? B * T * k : 0, n_cur = 2 * B * k, n_rec = B * T;
     HIP_TRY_AS("hipMalloc", h->d_roll.reserve(MAP_HEADER + (n_th + n_u + n_w + n_cur) * sizeof(double) + 2 * n_rec * sizeof(int), h->stream));
     double *d_th = reinterpret_cast<double *>(h->d_roll.as<char>() + MAP_HEADER), *d_uu = d_th + n_th, *d_w = d_uu + n_u, *d_cur = d_w + n_w;
@@ -2248,7 +2284,6 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
     HIP_TRY(hipMemcpyAsync(h->d_roll.p, &h->roll, sizeof(RolloutDev), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpy2DAsync(d_th, (T + 1) * row_b, theta0, row_b, row_b, B, hipMemcpyDefault, h->stream)); // row 0 of every trajectory
     if (w) HIP_TRY(hipMemcpyAsync(d_w, w, n_w * sizeof(double), hipMemcpyDefault, h->stream));
-    const bool fused = fused_rollout_fits(fit_shape(h), k, r, h->mat.k != 0) && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
     int rc = EICOS_OK;
     if (fused) {
         rc = fused_step_begins(h, 5);
@@ -2262,6 +2297,7 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
             AdjointDev rec{};
             rec.pmap = h->d_param.as<const ParamMapDev>(); rec.mmap = h->mat.k ? h->d_mat.as<const MatrixMapDev>() : nullptr;
             rec.omap = h->d_out.as<const OutMapDev>(); rec.k = k; rec.J = d_J; rec.res = d_res;
+            if (recording) { rec.grad_c = W.Wc; rec.grad_h = W.Wh; rec.grad_b = W.Wb; rec.x_rec = W.x; rec.y_rec = W.y; rec.z_rec = W.z; }
             HIP_TRY(hipMemcpyAsync(h->d_rollJ.p, &rec, sizeof rec, hipMemcpyHostToDevice, h->stream));
         }
         rc = enqueue_solve(h, &step, -1, sens ? h->d_rollJ.as<const AdjointDev>() : nullptr);
@@ -2279,9 +2315,18 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
             HIP_TRY(launch_outputs(h->pslot, h->inst(), 0, h->batch, h->out, h->d_u, h->stream));
             if (h->fb.mask) HIP_TRY(launch_fallback(h->pslot, h->inst(), 0, h->batch, h->fb, cur, h->d_u, h->stream));
             if (sens) {
-                rc = param_contracted(h, nullptr, h->batch, 0, nullptr, false, d_J1, "J", d_res1, true, "eicos_batch_rollout_jacobian");
+                rc = param_contracted(h, nullptr, h->batch, 0, nullptr, false, d_J1, "J", d_res1, true, "eicos_batch_rollout_jacobian", recording ? &W1 : nullptr);
                 if (rc != EICOS_OK) return rc;
                 if (h->fb.mask) HIP_TRY(launch_fallback_jacobian(h->pslot, h->inst(), 0, h->batch, h->fb, d_J1, d_res1, h->stream));
+                if (recording) { // the step's rows into the record, as J is moved
+                    if (h->fb.mask) HIP_TRY(launch_fallback_records(h->pslot, h->inst(), 0, h->batch, h->fb, W1.Wc, W1.Wh, W1.Wb, h->stream));
+                    const struct { double *dst; const double *src; size_t width; } mv[6] = {{W.Wc, W1.Wc, r * wn}, {W.Wh, W1.Wh, r * wm}, {W.Wb, W1.Wb, r * wp},
+                                                                                          {W.x, W1.x, wn}, {W.y, W1.y, wp}, {W.z, W1.z, wm}};
+                    for (const auto &q : mv) {
+                        const size_t wb = q.width * sizeof(double);
+                        if (wb) HIP_TRY(hipMemcpy2DAsync(q.dst + (size_t)t * q.width, T * wb, q.src, wb, wb, B, hipMemcpyDeviceToDevice, h->stream));
+                    }
+                }
                 const size_t jb = (size_t)r * k * sizeof(double), rb = (size_t)r * sizeof(double);
                 HIP_TRY(hipMemcpy2DAsync(d_J + (size_t)t * r * k, T * jb, d_J1, jb, jb, B, hipMemcpyDeviceToDevice, h->stream));
                 HIP_TRY(hipMemcpy2DAsync(d_res + (size_t)t * r, T * rb, d_res1, rb, rb, B, hipMemcpyDeviceToDevice, h->stream));
@@ -2298,6 +2343,7 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
         HIP_TRY(hipMemcpyAsync(J_traj, d_J, n_J * sizeof(double), hipMemcpyDefault, h->stream));
         if (res_traj) HIP_TRY(hipMemcpyAsync(res_traj, d_res, n_res * sizeof(double), hipMemcpyDefault, h->stream));
         h->rollJ_steps = steps; h->rollJ_k = k; h->rollJ_r = r; h->rollJ_plant = h->plant; h->rollJ_gen = h->map_gen;
+        h->rollW_on = recording;
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
     return EICOS_OK;
@@ -2392,6 +2438,130 @@ int eicos_batch_rollout_plant_gradient_device(eicos_batch *h, const double *dgu,
     return rollout_gradient(h, dgu, dgtheta, dgrad_theta0, dgrad_w, true, "eicos_batch_rollout_plant_gradient_device", &pv);
 }
 
+// ---- a recording rollout and the gradient with respect to the controller's own data (include/eicos_amd.h) ----
+size_t eicos_data_gradient_size(void) { return sizeof(eicos_data_gradient); }
+int eicos_batch_set_rollout_recording(eicos_batch *h, int on) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    h->roll_recording = on != 0;
+    if (!on && (h->d_rollW || h->d_rollD)) { // the record goes with the switch: up to gigabytes (a sweep in flight may still read it)
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->d_rollW.reset(); h->d_rollD.reset();
+        h->rollW_on = false;
+    }
+    return EICOS_OK;
+}
+int eicos_batch_rollout_recording(eicos_batch *h) { return h ? (h->roll_recording ? 1 : 0) : fail(EICOS_E_INVALID, "NULL handle"); }
+// the whole record of the trajectory the handle holds (rollW_on), as rollout_run laid it out
+static RecordRows record_rows(const eicos_batch *h) {
+    const size_t rows = (size_t)h->batch * h->rollJ_steps, r = (size_t)h->rollJ_r, n = (size_t)h->dp.n, m = (size_t)h->dp.m, p = (size_t)h->dp.p;
+    RecordRows R{};
+    double *at = h->d_rollW.as<double>();
+    R.Wc = at; at += rows * r * n; R.Wh = at; at += rows * r * m; R.Wb = at; at += rows * r * p;
+    R.x = at; at += rows * n; R.y = at; at += rows * p; R.z = at;
+    return R;
+}
+static int records_fault(const eicos_batch *h, const std::string &w) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (h->rollJ_steps == 0) return fail(EICOS_E_INVALID, w + ": the handle holds no Jacobian trajectory (eicos_batch_rollout_jacobian records one)");
+    if (!h->rollW_on) return fail(EICOS_E_INVALID, w + ": the handle holds no recorded rows: recording was off for the rollout it holds (eicos_batch_set_rollout_recording, then eicos_batch_rollout_jacobian)");
+    return EICOS_OK;
+}
+int eicos_batch_rollout_records(eicos_batch *h, double *Wc, double *Wh, double *Wb, double *x_rec, double *y_rec, double *z_rec) {
+    const int rc = records_fault(h, "eicos_batch_rollout_records");
+    if (rc != EICOS_OK) return rc;
+    for (const double *q : {Wc, Wh, Wb, x_rec, y_rec, z_rec})
+        if (q && memory_kind(q, 1) == MEM_DEVICE) return fail(EICOS_E_INVALID, "eicos_batch_rollout_records takes host pointers: an array lives in device memory");
+    HIP_TRY(hipSetDevice(h->device));
+    const RecordRows R = record_rows(h);
+    const size_t rows = (size_t)h->batch * h->rollJ_steps, r = (size_t)h->rollJ_r, n = (size_t)h->dp.n, m = (size_t)h->dp.m, p = (size_t)h->dp.p;
+    const struct { double *dst; const double *src; size_t count; } cp[6] = {{Wc, R.Wc, rows * r * n}, {Wh, R.Wh, rows * r * m}, {Wb, R.Wb, rows * r * p},
+                                                                           {x_rec, R.x, rows * n}, {y_rec, R.y, rows * p}, {z_rec, R.z, rows * m}};
+    for (const auto &q : cp)
+        if (q.dst && q.count) HIP_TRY(hipMemcpyAsync(q.dst, q.src, q.count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return EICOS_OK;
+}
+// The second backward sweep (launch.hpp: launch_rollout_data_backprop), behind everything on the handle's stream.  Every check stands in
+// front of the first enqueue.  The host form stages its arrays in d_rollD and waits; the device form only enqueues.
+static int rollout_data_gradient(eicos_batch *h, const double *gu, const double *gtheta, const double *theta_traj, const eicos_data_gradient *out,
+                                 bool device, const char *who) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    const std::string w(who);
+    if (h->rollJ_steps == 0) return fail(EICOS_E_INVALID, w + ": the handle holds no Jacobian trajectory (eicos_batch_rollout_jacobian records one)");
+    if (h->rollJ_gen != h->map_gen) return fail(EICOS_E_INVALID, w + ": a parameter, matrix, output, plant or fallback map was installed after the rollout whose Jacobians the handle holds (setting or clearing per-instance plant values counts as one): run eicos_batch_rollout_jacobian again");
+    { const int rc = records_fault(h, w); if (rc != EICOS_OK) return rc; }
+    if (!gu && !gtheta) return fail(EICOS_E_INVALID, w + ": gu and gtheta are both NULL");
+    if (!theta_traj) return fail(EICOS_E_INVALID, w + ": theta_traj is NULL");
+    if (!out) return fail(EICOS_E_INVALID, w + ": out is NULL");
+    const DevPat &P = h->dp;
+    const size_t B = (size_t)h->batch, T = (size_t)h->rollJ_steps, k = (size_t)h->rollJ_k, r = (size_t)h->rollJ_r;
+    const size_t n = (size_t)P.n, m = (size_t)P.m, p = (size_t)P.p;
+    // (rollJ_gen == map_gen: the maps on the handle are the ones the rollout ran under)
+    const size_t nnzC = (size_t)h->param_nnz[0], nnzH = (size_t)h->param_nnz[1], nnzB = (size_t)h->param_nnz[2], nnzU = (size_t)h->out_nnz;
+    const char *slope[3] = {"grad_Cval", "grad_Hval", "grad_Bval"};
+    double *const sl[3] = {out->grad_Cval, out->grad_Hval, out->grad_Bval};
+    for (int q = 0; q < 3; q++)
+        if (sl[q] && !h->param.g[q].base) return fail(EICOS_E_INVALID, w + ": " + slope[q] + " asked, but the parameter map has no " + "chb"[q] + " group");
+    struct Out { double *host; size_t width; const char *name; double *dev; };
+    Out o[10] = {{out->grad_c, n, "grad_c", nullptr}, {out->grad_h, m, "grad_h", nullptr}, {out->grad_b, p, "grad_b", nullptr},
+                 {out->grad_G, (size_t)P.nnzG, "grad_G", nullptr}, {out->grad_A, (size_t)P.nnzA, "grad_A", nullptr},
+                 {out->grad_Cval, nnzC, "grad_Cval", nullptr}, {out->grad_Hval, nnzH, "grad_Hval", nullptr}, {out->grad_Bval, nnzB, "grad_Bval", nullptr},
+                 {out->grad_u0, r, "grad_u0", nullptr}, {out->grad_Uval, nnzU, "grad_Uval", nullptr}};
+    bool any = false;
+    for (const Out &q : o) any = any || q.host;
+    if (!any) return fail(EICOS_E_INVALID, w + ": every output of out is NULL");
+    const char *other = device ? " must live in device memory (the form without _device takes host pointers)" : " lives in device memory: this form takes host pointers (use the _device form)";
+    const struct { const void *p; const char *name; } in[3] = {{gu, "gu"}, {gtheta, "gtheta"}, {theta_traj, "theta_traj"}};
+    for (const auto &a : in) if (a.p && (memory_kind(a.p, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": " + a.name + other);
+    for (const Out &q : o) if (q.host && (memory_kind(q.host, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": " + q.name + other);
+    if (rollout_backprop_lds((int)k, (int)r) > 48 * 1024) return fail(EICOS_E_INVALID, w + ": 3 k + 2 r doubles must fit 48 KB of LDS");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t n_gu = B * T * r, n_gt = B * (T + 1) * k, n_stage = (size_t)rollout_data_backprop_grid(h->batch) * (n + m + p);
+    size_t n_out = 0;
+    for (const Out &q : o) if (q.host) n_out += B * q.width;
+    if (!device) HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY_AS("hipMalloc", h->d_rollD.reserve((n_stage + (device ? 0 : n_gu + 2 * n_gt + n_out) + 1) * sizeof(double), h->stream));
+    double *at = h->d_rollD.as<double>();
+    DataGradDev D{};
+    D.stage = at; at += n_stage;
+    D.gu = gu; D.gth = gtheta; D.theta = theta_traj;
+    if (!device) {
+        if (gu) { HIP_TRY(hipMemcpyAsync(at, gu, n_gu * sizeof(double), hipMemcpyHostToDevice, h->stream)); D.gu = at; }
+        at += n_gu;
+        if (gtheta) { HIP_TRY(hipMemcpyAsync(at, gtheta, n_gt * sizeof(double), hipMemcpyHostToDevice, h->stream)); D.gth = at; }
+        at += n_gt;
+        HIP_TRY(hipMemcpyAsync(at, theta_traj, n_gt * sizeof(double), hipMemcpyHostToDevice, h->stream)); D.theta = at; at += n_gt;
+    }
+    for (Out &q : o) {
+        if (!q.host) continue;
+        if (device) q.dev = q.host; else { q.dev = at; at += B * q.width; }
+        if (q.width == 0) q.dev = nullptr; // (a group the pattern or the map does not have: no row to form)
+    }
+    const RecordRows R = record_rows(h);
+    D.J = reinterpret_cast<const double *>(h->d_rollJ.as<char>() + MAP_HEADER);
+    D.Wc = R.Wc; D.Wh = R.Wh; D.Wb = R.Wb; D.x = R.x; D.y = R.y; D.z = R.z;
+    D.pmap = h->param; D.omap = h->out;
+    D.grad_c = o[0].dev; D.grad_h = o[1].dev; D.grad_b = o[2].dev; D.grad_G = o[3].dev; D.grad_A = o[4].dev;
+    D.grad_val[0] = o[5].dev; D.grad_val[1] = o[6].dev; D.grad_val[2] = o[7].dev; D.grad_u0 = o[8].dev; D.grad_Uval = o[9].dev;
+    if (!h->ev_a0) { HIP_TRY(hipEventCreate(&h->ev_a0)); HIP_TRY(hipEventCreate(&h->ev_a1)); }
+    HIP_TRY(hipEventRecord(h->ev_a0, h->stream)); // (eicos_batch_last_adjoint_ms: the sweep counts as the handle's most recent adjoint launch)
+    HIP_TRY(launch_rollout_data_backprop(h->pslot, h->rollJ_plant, (int)T, h->batch, D, h->stream));
+    HIP_TRY(hipEventRecord(h->ev_a1, h->stream));
+    h->adjoint_timed = true;
+    if (device) return EICOS_OK;
+    for (const Out &q : o)
+        if (q.host && q.dev) HIP_TRY(hipMemcpyAsync(q.host, q.dev, B * q.width * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return EICOS_OK;
+}
+int eicos_batch_rollout_data_gradient(eicos_batch *h, const double *gu, const double *gtheta, const double *theta_traj, const eicos_data_gradient *out) {
+    return rollout_data_gradient(h, gu, gtheta, theta_traj, out, false, "eicos_batch_rollout_data_gradient");
+}
+int eicos_batch_rollout_data_gradient_device(eicos_batch *h, const double *dgu, const double *dgtheta, const double *dtheta_traj, const eicos_data_gradient *dout) {
+    return rollout_data_gradient(h, dgu, dgtheta, dtheta_traj, dout, true, "eicos_batch_rollout_data_gradient_device");
+}
+
 int eicos_batch_solution(eicos_batch *h, double *x) {
     if (!h || !x) return fail(EICOS_E_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(h->device));
@@ -2433,6 +2603,12 @@ int eicos_internal_device(const eicos_batch *h) { return h ? h->device : -1; }
 int eicos_internal_plant_dims(const eicos_batch *h, int *k, int *nnz) {
     if (!h || !k || !nnz) return EICOS_E_INVALID;
     *k = h->plant.k; *nnz = h->plant.nnz;
+    return EICOS_OK;
+}
+int eicos_internal_map_nnz(const eicos_batch *h, int *nnz_chb, int *nnz_u) {
+    if (!h || !nnz_chb || !nnz_u) return EICOS_E_INVALID;
+    for (int q = 0; q < 3; q++) nnz_chb[q] = h->param_nnz[q];
+    *nnz_u = h->out_nnz;
     return EICOS_OK;
 }
 // ms from the start of `from`'s most recent solve to the end of `to`'s (two handles on ONE device: the span of a device that holds

@@ -15,6 +15,9 @@ int eicos_internal_update_param_staged(eicos_batch *h, int first, int count, con
 int eicos_internal_device(const eicos_batch *h);
 // the row widths of the per-instance plant values: k the installed plant map was validated for and its stored entries rowptr[k]; 0, 0 without one
 int eicos_internal_plant_dims(const eicos_batch *h, int *k, int *nnz);
+// the row widths of eicos_batch_rollout_data_gradient's slope outputs: stored entries of the c, h, b groups of the installed parameter map
+// (0 for a group without one) and of the output map
+int eicos_internal_map_nnz(const eicos_batch *h, int *nnz_chb, int *nnz_u);
 // ms from the start of `from`'s most recent solve to the end of `to`'s (two handles on one device)
 int eicos_internal_solve_span_ms(eicos_batch *from, eicos_batch *to, float *ms);
 }

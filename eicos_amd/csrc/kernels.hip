@@ -3525,6 +3525,22 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void fallback_ja
         if (res) res[j] = 0.;
     }
 }
+// The records of a step whose fallback fired in a recording rollout (k_roll_sens, behind fallback_jacobian_instance; launch.hpp:
+// AdjointDev): its u row does not depend on the controller's data, so row `row` of the gradient-row arrays [..][r][n], [..][r][m],
+// [..][r][p] becomes 0.0; the x, y, z records take the instance's result rows as adjoint_instance stores them.
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void fallback_records_instance(int ps, gcdbl_p I, const AdjointDev *Ap, int row) {
+    ps = uni(ps); I = uni_ptr(I); Ap = uni_ptr(Ap); row = uni(row);
+    const DevPat &P = c_pat[ps];
+    const AdjointDev A = *Ap;
+    const size_t n = (size_t)P.n, m = (size_t)P.m, p = (size_t)P.p, r = (size_t)A.omap->r;
+    if (A.grad_c) { FOR_T(e, (int)(r * n)) A.grad_c[(size_t)row * r * n + e] = 0.; }
+    if (A.grad_h) { FOR_T(e, (int)(r * m)) A.grad_h[(size_t)row * r * m + e] = 0.; }
+    if (A.grad_b) { FOR_T(e, (int)(r * p)) A.grad_b[(size_t)row * r * p + e] = 0.; }
+    if (A.x_rec) { FOR_T(j, P.n) A.x_rec[(size_t)row * n + j] = I[P.i_x + j]; }
+    if (A.y_rec) { FOR_T(j, P.p) A.y_rec[(size_t)row * p + j] = I[P.i_y + j]; }
+    if (A.z_rec) { FOR_T(j, P.m) A.z_rec[(size_t)row * m + j] = I[P.i_z + j]; }
+}
 
 // The plant map of one instance by one workgroup (k_solve, a rollout: after outputs_instance and the record of step t): row t + 1 of the
 // instance's theta trajectory = base + F z (+ w), z = [theta row t | u row t].  Both rows were written by THIS workgroup a moment ago
@@ -3635,7 +3651,8 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int retry_betwee
 //      output map, or of the caller's g when A.g != NULL), contracted with the CSR rows of the parameter map and of the matrix map (each
 //      NULL = not installed) into J[i, :], columns in chunks of eight, every chunk one workgroup reduction in a fixed order: thread-private
 //      partial sums over the thread's rows of the c, h, b groups in ascending order, then over its stored values of G, then of A, each
-//      ascending, then blk_reduce; no gradient row is stored.
+//      ascending, then blk_reduce; the gradient rows themselves are stored only for a recording rollout (A.grad_c / _h / _b != NULL;
+//      A.x_rec / y_rec / z_rec: the result rows once per instance).
 // An instance whose last solve did not end OPTIMAL / OPTIMAL_INACC, whose scalings fail or whose factorisation meets a zero pivot gets
 // NaN in every row and in res.  Nothing of the instance slab that a later call reads is written: the scaling block i_Vv is reset by every
 // solve's prologue, and the workspace slab belongs to the workgroup, not to an instance.  g_S is scratch here (no instance_end).
@@ -3697,6 +3714,10 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void adjoint_ins
     const bool urows = A.J && !A.g; // the right-hand sides are the rows of the output map
     const int nrhs = urows ? A.omap->r : A.nrhs;
     gcdbl_p rx = I + P.i_x, ry = I + P.i_y, rz = I + P.i_z; // the result rows: un-equilibrated
+    // a recording rollout (launch.hpp: AdjointDev::x_rec): the result rows the step's u row was formed from, whatever the exit code
+    if (A.x_rec) { FOR_T(j, n) A.x_rec[(size_t)row * n + j] = rx[j]; }
+    if (A.y_rec) { FOR_T(q, p) A.y_rec[(size_t)row * p + q] = ry[q]; }
+    if (A.z_rec) { FOR_T(i, m) A.z_rec[(size_t)row * m + i] = rz[i]; }
     for (int r = 0; r < nrhs; r++) {
         const size_t at = (size_t)row * nrhs + r;
         if (ok) {
@@ -3728,6 +3749,10 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void adjoint_ins
                 A.grad_A[at * P.nnzA + e] = ok ? (-(dx[q.j] / xe[q.j])) * ry[q.i] - (dy[q.i] / ae[q.i]) * rx[q.j] : nan;
             });
         } else {
+            // a recording rollout: the three gradient rows of this right-hand side, the expressions of the gradient form
+            if (A.grad_c) { FOR_T(j, n) A.grad_c[at * n + j] = ok ? -(dx[j] / xe[j]) : nan; }
+            if (A.grad_h) { FOR_T(i, m) A.grad_h[at * m + i] = ok ? dz[i] / ge[i] : nan; }
+            if (A.grad_b) { FOR_T(q, p) A.grad_b[at * p + q] = ok ? dy[q] / ae[q] : nan; }
             ParamMapDev M{};
             MatrixMapDev MM{};
             if (A.pmap) M = *A.pmap;
@@ -3791,8 +3816,10 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void rollout_sen
     const RolloutDev *Rp = uni_ptr(g_S.roll);
     const int t = uni(g_S.step), steps = Rp->steps;
     // a step whose fallback fired records J_t = V dense and res_t = 0.0 and runs no adjoint (a workgroup-uniform branch)
-    if (rollout_record<T>(ps, I, Rp, id, t, steps, fb)) fallback_jacobian_instance<T>(fb, Ap, id * steps + t);
-    else adjoint_instance<T, NLDS, I16>(ps, I, W, Ap, id * steps + t); // (begins and ends with a barrier; batch * steps fits an int: api.cpp)
+    if (rollout_record<T>(ps, I, Rp, id, t, steps, fb)) {
+        fallback_jacobian_instance<T>(fb, Ap, id * steps + t);
+        if (Ap->x_rec) fallback_records_instance<T>(ps, I, Ap, id * steps + t); // (a recording rollout: 0.0 rows, the result rows as they are)
+    } else adjoint_instance<T, NLDS, I16>(ps, I, W, Ap, id * steps + t); // (begins and ends with a barrier; batch * steps fits an int: api.cpp)
     rollout_advance<T>(Rp, id, t, steps);
 }
 
@@ -4406,6 +4433,21 @@ __global__ __launch_bounds__(T) void k_fallback_jacobian_range(int ps, const dou
         if (res) res[e] = 0.;
     }
 }
+// The recorded gradient rows of the same instances (launch.hpp: launch_fallback_records): grid-stride over the entries of one instance's
+// rows [r][n | m | p] back to back, blockIdx.y over the instances; the entries of a fired instance become 0.0.
+template <int T>
+__global__ __launch_bounds__(T) void k_fallback_records_range(int ps, const double *inst, int first, int count, FallbackDev F, double *Wc, double *Wh, double *Wb) {
+    const DevPat &P = c_pat[ps];
+    const size_t rn = (size_t)F.r * P.n, rm = (size_t)F.r * P.m, rp = (size_t)F.r * P.p, width = rn + rm + rp;
+    for (int q = blockIdx.y; q < count; q += (int)gridDim.y) {
+        if (!fallback_fires(P, inst, first + q, F.mask)) continue;
+        for (size_t e = (size_t)blockIdx.x * T + threadIdx.x; e < width; e += (size_t)gridDim.x * T) {
+            if (e < rn) { if (Wc) Wc[q * rn + e] = 0.; }
+            else if (e < rn + rm) { if (Wh) Wh[q * rm + (e - rn)] = 0.; }
+            else if (Wb) Wb[q * rp + (e - rn - rm)] = 0.;
+        }
+    }
+}
 
 // A caller-supplied starting point for a range of instances (launch.hpp: launch_set_iterate): ENTRY-parallel like k_update_rhs_range --
 // blockIdx.y strides over the instances, the x dimension over the given entries [x | y | z | s] of one instance (unit stride in the inputs
@@ -4531,6 +4573,100 @@ __global__ __launch_bounds__(T) void k_rollout_backprop(PlantMapDev M, int steps
             const double poison = __dmul_rn(0., lam[i]);
             if (f0b) f0b[i] = __dadd_rn(f0b[i], poison);
             if (valb) for (int s = A.rowptr[i]; s < A.rowptr[i + 1]; s++) valb[s] = __dadd_rn(valb[s], poison);
+        }
+    }
+}
+
+// The backward sweep with respect to the controller's own data (launch.hpp: launch_rollout_data_backprop, DataGradDev;
+// eicos_batch_rollout_data_gradient): the lambda / mu recursion of k_rollout_backprop in its order and its bits, and behind mu_t of
+// every step t = T-1 .. 0, with W_t = the recorded rows of u_a = (row a of U)' x at step t:
+//   1. the step's contracted rows d_c [n], d_h [m], d_b [p]: d = 0.0, then d + (mu[a] * W_t[a][i]) for a ascending, into the workgroup's
+//      staging row in device memory (one path for every size), one thread per entry;
+//   2. grad_c[i] = grad_c[i] + d_c[i], likewise h and b (the thread that formed d);
+//   3. a group with a map: grad_val[s] = grad_val[s] + (d[i] * theta_t[col[s]]) over the stored entries s of row i (the same thread);
+//   4. behind a barrier, one thread per stored value e = (i, j): grad_G[e] = grad_G[e] + ((d_c[j] * z_t[i]) - (d_h[i] * x_t[j])), grad_A
+//      with y_t and d_b in the place of z_t and d_h -- adjoint_instance's expression on the contracted rows;
+//   5. grad_u0[a] = grad_u0[a] + mu[a], grad_Uval[s] = grad_Uval[s] + (mu[a] * x_t[col[s]]) over the stored entries of row a (thread a).
+// Every product and sum is rounded on its own and every output entry is zeroed, owned and accumulated in place by one thread over
+// t = T-1 .. 0, so no sum depends on how threads are scheduled.  A step with NaN rows (not OPTIMAL) makes the sums it enters NaN.
+template <int T>
+__global__ __launch_bounds__(T) void k_rollout_data_backprop(int ps, PlantMapDev M, int steps, int batch, DataGradDev D) {
+    const DevPat &P = c_pat[ps];
+    const int k = M.k, r = M.r, n = P.n, m = P.m, p = P.p, nmp = n + m + p, nnzG = P.nnzG, nnzA = P.nnzA;
+    double *lam = g_dyn, *lam2 = lam + k, *v = lam2 + k, *mu = v + k + r;
+    double *dst = D.stage + (size_t)blockIdx.x * nmp;
+    const double *dc = dst, *dh = dst + n, *db = dst + n + m;
+    const AffineDev U = D.omap.a;
+    const int nnzU = U.rowptr[r];
+    for (int b = blockIdx.x; b < batch; b += (int)gridDim.x) {
+        const size_t bt = (size_t)b * steps;
+        const AffineDev A = plant_of(M, (size_t)b);
+        double *gc = D.grad_c ? D.grad_c + (size_t)b * n : nullptr, *gh = D.grad_h ? D.grad_h + (size_t)b * m : nullptr;
+        double *gb = D.grad_b ? D.grad_b + (size_t)b * p : nullptr;
+        double *gG = D.grad_G ? D.grad_G + (size_t)b * nnzG : nullptr, *gA = D.grad_A ? D.grad_A + (size_t)b * nnzA : nullptr;
+        double *gu0 = D.grad_u0 ? D.grad_u0 + (size_t)b * r : nullptr, *gU = D.grad_Uval ? D.grad_Uval + (size_t)b * nnzU : nullptr;
+        double *gval[3];
+        for (int q = 0; q < 3; q++) gval[q] = D.grad_val[q] ? D.grad_val[q] + (size_t)b * D.pmap.g[q].rowptr[q == 0 ? n : (q == 1 ? m : p)] : nullptr;
+        __syncthreads(); // (the instance before: its last reads of lam and of the staging row)
+        FOR_T(c, k) lam[c] = D.gth ? D.gth[(bt + b + steps) * k + c] : 0.;
+        FOR_T(e, nmp) {
+            const int grp = e < n ? 0 : (e < n + m ? 1 : 2), i = e - (grp == 0 ? 0 : (grp == 1 ? n : n + m));
+            double *go = grp == 0 ? gc : (grp == 1 ? gh : gb);
+            if (go) go[i] = 0.;
+            if (gval[grp]) { const AffineDev G = D.pmap.g[grp]; for (int s = G.rowptr[i]; s < G.rowptr[i + 1]; s++) gval[grp][s] = 0.; }
+        }
+        if (gG) { FOR_T(e, nnzG) gG[e] = 0.; }
+        if (gA) { FOR_T(e, nnzA) gA[e] = 0.; }
+        FOR_T(a, r) {
+            if (gu0) gu0[a] = 0.;
+            if (gU) for (int s = U.rowptr[a]; s < U.rowptr[a + 1]; s++) gU[s] = 0.;
+        }
+        __syncthreads();
+        for (int t = steps - 1; t >= 0; t--) {
+            FOR_T(c, k + r) {
+                double acc = 0.;
+                for (int i = 0; i < k; i++)
+                    for (int s = A.rowptr[i]; s < A.rowptr[i + 1]; s++)
+                        if (A.col[s] == c) acc = __dadd_rn(acc, __dmul_rn(A.val[s], lam[i]));
+                v[c] = acc;
+            }
+            __syncthreads();
+            FOR_T(j, r) mu[j] = __dadd_rn(D.gu ? D.gu[(bt + t) * r + j] : 0., v[k + j]);
+            __syncthreads();
+            // ---- the controller's data, behind mu_t ----
+            const double *Wc = D.Wc + (bt + t) * r * n, *Wh = D.Wh + (bt + t) * r * m, *Wb = D.Wb + (bt + t) * r * p;
+            const double *xt = D.x + (bt + t) * n, *yt = D.y + (bt + t) * p, *zt = D.z + (bt + t) * m, *tht = D.theta + (bt + b + t) * k;
+            FOR_T(e, nmp) {
+                const int grp = e < n ? 0 : (e < n + m ? 1 : 2), i = e - (grp == 0 ? 0 : (grp == 1 ? n : n + m));
+                const int width = grp == 0 ? n : (grp == 1 ? m : p);
+                const double *W = grp == 0 ? Wc : (grp == 1 ? Wh : Wb);
+                double d = 0.;
+                for (int a = 0; a < r; a++) d = __dadd_rn(d, __dmul_rn(mu[a], W[(size_t)a * width + i]));
+                dst[e] = d;
+                double *go = grp == 0 ? gc : (grp == 1 ? gh : gb);
+                if (go) go[i] = __dadd_rn(go[i], d);
+                if (gval[grp]) {
+                    const AffineDev G = D.pmap.g[grp];
+                    for (int s = G.rowptr[i]; s < G.rowptr[i + 1]; s++) gval[grp][s] = __dadd_rn(gval[grp][s], __dmul_rn(d, tht[G.col[s]]));
+                }
+            }
+            __syncthreads(); // (the staging row is complete)
+            if (gG) { FOR_T(e, nnzG) { const int i = P.Gir[e], j = P.Gcol[e]; gG[e] = __dadd_rn(gG[e], __dsub_rn(__dmul_rn(dc[j], zt[i]), __dmul_rn(dh[i], xt[j]))); } }
+            if (gA) { FOR_T(e, nnzA) { const int i = P.Air[e], j = P.Acol[e]; gA[e] = __dadd_rn(gA[e], __dsub_rn(__dmul_rn(dc[j], yt[i]), __dmul_rn(db[i], xt[j]))); } }
+            FOR_T(a, r) {
+                if (gu0) gu0[a] = __dadd_rn(gu0[a], mu[a]);
+                if (gU) for (int s = U.rowptr[a]; s < U.rowptr[a + 1]; s++) gU[s] = __dadd_rn(gU[s], __dmul_rn(mu[a], xt[U.col[s]]));
+            }
+            // ---- the recursion goes on ----
+            FOR_T(c, k) {
+                double acc = __dadd_rn(D.gth ? D.gth[(bt + b + t) * k + c] : 0., v[c]);
+                const double *Jt = D.J + (bt + t) * r * k;
+                for (int j = 0; j < r; j++) acc = __dadd_rn(acc, __dmul_rn(Jt[(size_t)j * k + c], mu[j]));
+                lam2[c] = acc;
+            }
+            __syncthreads();
+            FOR_T(c, k) lam[c] = lam2[c];
+            __syncthreads(); // (also: every read of the staging row stands in front of the next step's stores)
         }
     }
 }
@@ -4763,6 +4899,12 @@ hipError_t launch_fallback_jacobian(int ps, const double *inst, int first, int c
     hipLaunchKernelGGL(k_fallback_jacobian_range<T>, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(T), 0, st, ps, inst, first, count, fb, J, res);
     return hipGetLastError();
 }
+hipError_t launch_fallback_records(int ps, const double *inst, int first, int count, const FallbackDev &fb, double *Wc, double *Wh, double *Wb, hipStream_t st) {
+    if (count <= 0 || fb.r <= 0 || fb.mask == 0 || (!Wc && !Wh && !Wb)) return hipSuccess;
+    constexpr int T = 256;
+    hipLaunchKernelGGL(k_fallback_records_range<T>, dim3(4, (unsigned)(count < 16384 ? count : 16384)), dim3(T), 0, st, ps, inst, first, count, fb, Wc, Wh, Wb);
+    return hipGetLastError();
+}
 hipError_t launch_plant(int ps, const double *inst, int first, int count, const RolloutDev &roll, int t, const double *theta_cur,
                         const double *u_cur, double *theta_next, hipStream_t st) {
     if (count <= 0 || roll.plant.k <= 0) return hipSuccess;
@@ -4794,6 +4936,15 @@ hipError_t launch_rollout_backprop(const PlantMapDev &plant, int steps, int batc
     if (grad_val && (!u_traj || !theta_traj)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_rollout_backprop<T>, dim3((unsigned)(batch < 16384 ? batch : 16384)), dim3(T), lds, st, plant, steps, batch, J, gu, gtheta, grad_theta0, grad_w,
                        u_traj, theta_traj, grad_f0, grad_val);
+    return hipGetLastError();
+}
+hipError_t launch_rollout_data_backprop(int ps, const PlantMapDev &plant, int steps, int batch, const DataGradDev &D, hipStream_t st) {
+    if (batch <= 0) return hipSuccess;
+    constexpr int T = 256;
+    const size_t lds = rollout_backprop_lds(plant.k, plant.r);
+    if (steps < 1 || lds > 48 * 1024 || !D.J || !D.Wc || !D.Wh || !D.Wb || !D.x || !D.y || !D.z || !D.theta || !D.stage || D.omap.r != plant.r) return hipErrorInvalidValue;
+    for (int q = 0; q < 3; q++) if (D.grad_val[q] && !D.pmap.g[q].base) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rollout_data_backprop<T>, dim3((unsigned)rollout_data_backprop_grid(batch)), dim3(T), lds, st, ps, plant, steps, batch, D);
     return hipGetLastError();
 }
 hipError_t launch_fill_rows(const double *src, int width, int rows, double *dst, hipStream_t st) {

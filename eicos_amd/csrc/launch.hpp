@@ -126,10 +126,15 @@ struct SolveLaunch {
 // the matrix map (mmap, NULL = none or not wanted), both with k columns: J [count][rows][k], res [count][rows]; grad_* are unused.  Its
 // right-hand sides are the omap->r rows of the output map (g == NULL: the Jacobian, nrhs unused) or nrhs rows of the caller's g per
 // instance (g != NULL: the gradient with respect to theta, omap unused).
+// A recording rollout (eicos_batch_set_rollout_recording) runs the contracted form with grad_c / grad_h / grad_b non-NULL: the rows
+// [count][rows][n], [count][rows][m], [count][rows][p] are then stored as well, with the expressions of the gradient form, in front of
+// the contraction; x_rec [count][n], y_rec [count][p], z_rec [count][m] (NULL = not recorded) take the instance's un-equilibrated result
+// rows, whatever the exit code.  The gradient form leaves the three NULL.
 struct AdjointDev {
     int nrhs; const double *g; double *grad_c, *grad_h, *grad_b, *res;
     const ParamMapDev *pmap; const OutMapDev *omap; double *J;
     double *grad_G, *grad_A; const MatrixMapDev *mmap; int k;
+    double *x_rec, *y_rec, *z_rec;
 };
 // One k_adjoint launch of a handle: the pattern slot, the slabs and the launch shape of its solves, the settings its kkt_solve and its
 // factorisation run under (by value), `count` instances -- list != NULL: those ids (device memory, distinct, inside [0, batch)), else
@@ -198,6 +203,10 @@ hipError_t launch_fallback(int ps, const double *inst, int first, int count, con
 // J [count][fb.r][fb.k] and res [count][fb.r] (NULL: not kept) of the same instances become V as a dense block -- the row zero-filled, then
 // J[row][col] = J[row][col] + val in stored order -- and 0.0.  Counts nothing.
 hipError_t launch_fallback_jacobian(int ps, const double *inst, int first, int count, const FallbackDev &fb, double *J, double *res, hipStream_t st);
+// The same for the recorded gradient rows of a recording rollout that is not fused: rows [first, first + count) of Wc [count][fb.r][n],
+// Wh [count][fb.r][m] and Wb [count][fb.r][p] of every instance whose fallback fired become 0.0 (its u row does not depend on the
+// controller's data); the x, y, z records stay.
+hipError_t launch_fallback_records(int ps, const double *inst, int first, int count, const FallbackDev &fb, double *Wc, double *Wh, double *Wb, hipStream_t st);
 // One step of a rollout that is not fused into the solve launch, for instances [first, first + count), behind that step's solve and
 // output kernels: z = [row of theta_cur [count][k] | row of u_cur [count][r]] goes through the plant map -- acc = base[row], then
 // acc = acc + (val * z[col]) in stored order, then + w when given, every product and sum rounded on its own -- into theta_next [count][k]
@@ -217,6 +226,21 @@ inline size_t rollout_backprop_lds(int k, int r, bool values = false) { return (
 hipError_t launch_rollout_backprop(const PlantMapDev &plant, int steps, int batch, const double *J, const double *gu, const double *gtheta,
                                    double *grad_theta0, double *grad_w, hipStream_t st, const double *u_traj = nullptr,
                                    const double *theta_traj = nullptr, double *grad_f0 = nullptr, double *grad_val = nullptr);
+// The backward sweep with respect to the controller's own data (eicos_batch_rollout_data_gradient; kernels.hip: k_rollout_data_backprop),
+// over a rollout that recorded its Jacobians AND its gradient rows: J as above, Wc [batch][steps][r][n], Wh [..][m], Wb [..][p] and the
+// x [batch][steps][n], y [..][p], z [..][m] records, gu / gtheta as above, theta_traj [batch][steps + 1][k]; pmap / omap = the handle's
+// maps (host copies: device pointers, by value).  Outputs, each NULL = not wanted, one row per instance: grad_c [batch][n], grad_h
+// [batch][m], grad_b [batch][p], grad_G [batch][nnzG], grad_A [batch][nnzA], grad_val[0..2] [batch][nnz of the c, h, b group of pmap],
+// grad_u0 [batch][r], grad_Uval [batch][nnzU].  stage = (n + m + p) doubles per workgroup of the grid (rollout_data_backprop_grid) in
+// device memory: the step's contracted rows between two barriers.  One 256-thread workgroup per instance, rollout_backprop_lds(k, r)
+// bytes of LDS for the lambda / mu recursion, which is k_rollout_backprop's, bit for bit.
+struct DataGradDev {
+    const double *J, *Wc, *Wh, *Wb, *x, *y, *z, *gu, *gth, *theta;
+    ParamMapDev pmap; OutMapDev omap;
+    double *grad_c, *grad_h, *grad_b, *grad_G, *grad_A, *grad_val[3], *grad_u0, *grad_Uval, *stage;
+};
+inline int rollout_data_backprop_grid(int batch) { return batch < 4096 ? batch : 4096; }
+hipError_t launch_rollout_data_backprop(int ps, const PlantMapDev &plant, int steps, int batch, const DataGradDev &D, hipStream_t st);
 // rows [0, rows) of dst [rows][width] = src [width] (device memory): what the first eicos_batch_set_plant_values of a group starts from
 hipError_t launch_fill_rows(const double *src, int width, int rows, double *dst, hipStream_t st);
 // Selection (eicos_batch_select, _solve_where): the instances of 0 .. batch-1 whose exit class (exit_class.hpp) is in `mask`, compacted

@@ -682,6 +682,51 @@ int eicos_multi_rollout_plant_gradient(eicos_multi *mh, const double *gu, const 
     });
 }
 
+// recording on every shard; records and the data gradient are rows by shard, T = the step count of the trajectory the shards hold
+int eicos_multi_set_rollout_recording(eicos_multi *mh, int on) {
+    return in_turn(mh, false, [&](int s) { return eicos_batch_set_rollout_recording(mh->shard[s], on); });
+}
+int eicos_multi_rollout_recording(eicos_multi *mh) { return mh ? eicos_batch_rollout_recording(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
+namespace {
+int shard_steps(eicos_multi *mh, const char *who, int &steps) {
+    steps = eicos_batch_rollout_jacobian_steps(mh->shard[0]);
+    for (int s = 0; s < (int)mh->shard.size(); s++)
+        if (steps < 1 || eicos_batch_rollout_jacobian_steps(mh->shard[s]) != steps)
+            return mfail(EICOS_E_INVALID, std::string(who) + ": shard " + std::to_string(s) + " holds no Jacobian trajectory, or one of another length (eicos_multi_rollout_jacobian records one)");
+    return EICOS_OK;
+}
+} // namespace
+int eicos_multi_rollout_records(eicos_multi *mh, double *Wc, double *Wh, double *Wb, double *x_rec, double *y_rec, double *z_rec) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    int steps = 0;
+    const int rc = shard_steps(mh, "rollout_records", steps);
+    if (rc != EICOS_OK) return rc;
+    const size_t T = (size_t)steps, ro = (size_t)eicos_batch_output_count(mh->shard[0]);
+    return for_shards(mh, [&](int s) {
+        const size_t f = (size_t)mh->first[s];
+        return eicos_batch_rollout_records(mh->shard[s], at(Wc, f, T * ro * mh->n), at(Wh, f, T * ro * mh->m), at(Wb, f, T * ro * mh->p),
+                                           at(x_rec, f, T * mh->n), at(y_rec, f, T * mh->p), at(z_rec, f, T * mh->m));
+    });
+}
+int eicos_multi_rollout_data_gradient(eicos_multi *mh, const double *gu, const double *gtheta, const double *theta_traj, const eicos_data_gradient *out) {
+    if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
+    if (!gu && !gtheta) return mfail(EICOS_E_INVALID, "rollout_data_gradient: gu and gtheta are both NULL");
+    if (!theta_traj || !out) return mfail(EICOS_E_INVALID, "rollout_data_gradient: theta_traj or out is NULL");
+    int steps = 0;
+    const int rc = shard_steps(mh, "rollout_data_gradient", steps);
+    if (rc != EICOS_OK) return rc;
+    const size_t k = (size_t)eicos_batch_param_count(mh->shard[0]), ro = (size_t)eicos_batch_output_count(mh->shard[0]), T = (size_t)steps;
+    int nnz[3] = {0, 0, 0}, nnzU = 0;
+    (void)eicos_internal_map_nnz(mh->shard[0], nnz, &nnzU);
+    return for_shards(mh, [&](int s) {
+        const size_t f = (size_t)mh->first[s];
+        const eicos_data_gradient o = {at(out->grad_c, f, mh->n), at(out->grad_h, f, mh->m), at(out->grad_b, f, mh->p), at(out->grad_G, f, mh->nnzG),
+                                       at(out->grad_A, f, mh->nnzA), at(out->grad_Cval, f, nnz[0]), at(out->grad_Hval, f, nnz[1]),
+                                       at(out->grad_Bval, f, nnz[2]), at(out->grad_u0, f, ro), at(out->grad_Uval, f, nnzU)};
+        return eicos_batch_rollout_data_gradient(mh->shard[s], at(gu, f, T * ro), at(gtheta, f, (T + 1) * k), at(theta_traj, f, (T + 1) * k), &o);
+    });
+}
+
 int eicos_multi_solution(eicos_multi *mh, double *x) {
     if (!mh || !x) return mfail(EICOS_E_INVALID, "NULL argument");
     if (mh->n == 0) return EICOS_OK;

@@ -549,6 +549,29 @@ namespace EiCOS
             mcheck(eicos_multi_rollout_plant_gradient(h_, gu, gtheta, u_traj, theta_traj, grad_theta0, grad_w, grad_f0, grad_val),
                    "eicos_multi_rollout_plant_gradient");
         }
+        // Extension: the gradient with respect to the CONTROLLER's own data.  setRolloutRecording(true): rolloutJacobian then also
+        // records, on the GPU, the gradient rows of every step's output rows and the step's x, y, z (batch * steps * (r + 1) *
+        // (n + m + p) * 8 bytes; everything rolloutJacobian returns keeps its bits).  rolloutRecords copies whichever of the six
+        // arrays are wanted to the host.  rolloutDataGradient sweeps backwards over the recorded rollout, for rolloutGradient's cost
+        // L, and fills the non-null members of `out`, one row per instance: grad_c / grad_h / grad_b, grad_G / grad_A (stored values,
+        // CSC order), grad_Cval / grad_Hval / grad_Bval (the parameter map's slopes) and grad_u0 / grad_Uval (the output map);
+        // theta_traj is the array rolloutJacobian returned (definition, order and what is out of scope:
+        // eicos_batch_rollout_data_gradient of eicos_amd.h).  For data shared by the batch sum the rows.
+        void setRolloutRecording(bool on) { mcheck(eicos_multi_set_rollout_recording(h_, on ? 1 : 0), "eicos_multi_set_rollout_recording"); }
+        bool rolloutRecording() const
+        {
+            const int v = eicos_multi_rollout_recording(h_);
+            if (v < 0) mcheck(v, "eicos_multi_rollout_recording");
+            return v != 0;
+        }
+        void rolloutRecords(double *Wc, double *Wh, double *Wb, double *x_rec = nullptr, double *y_rec = nullptr, double *z_rec = nullptr) const
+        {
+            mcheck(eicos_multi_rollout_records(h_, Wc, Wh, Wb, x_rec, y_rec, z_rec), "eicos_multi_rollout_records");
+        }
+        void rolloutDataGradient(const double *gu, const double *gtheta, const double *theta_traj, const eicos_data_gradient &out)
+        {
+            mcheck(eicos_multi_rollout_data_gradient(h_, gu, gtheta, theta_traj, &out), "eicos_multi_rollout_data_gradient");
+        }
         void solveAsync() { mcheck(eicos_multi_solve_async(h_), "eicos_multi_solve_async"); } // enqueue on every shard's stream
         void sync() { mcheck(eicos_multi_sync(h_), "eicos_multi_sync"); }
         std::vector<double> solution() const

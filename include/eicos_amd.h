@@ -595,6 +595,62 @@ int eicos_batch_rollout_plant_gradient(eicos_batch *hd, const double *gu, const 
 int eicos_batch_rollout_plant_gradient_device(eicos_batch *hd, const double *dgu, const double *dgtheta, const double *du_traj,
                                               const double *dtheta_traj, double *dgrad_theta0, double *dgrad_w, double *dgrad_f0,
                                               double *dgrad_val);
+/* The gradient of a closed-loop cost with respect to the CONTROLLER's own data: the data vectors c, h, b, the stored
+ * values of G and A, the slopes of the parameter map and the output map.
+ *
+ * Recording (off by default).  eicos_batch_set_rollout_recording(hd, 1): from then on eicos_batch_rollout_jacobian also leaves, in
+ * device memory owned by the handle, for every instance and step
+ *     Wc [batch][T][r][n], Wh [batch][T][r][m], Wb [batch][T][r][p]   the rows grad_c, grad_h, grad_b of u_a = (row a of U)' x: the bits
+ *         eicos_batch_adjoint returns at that step for g = the dense rows of the output map (entries of a column summed in stored order);
+ *     x_rec [batch][T][n], y_rec [batch][T][p], z_rec [batch][T][m]    the un-equilibrated result the step's u row was formed from (the
+ *         final attempt under a retry policy).
+ * A step whose fallback law fired records 0.0 in its W rows (its u does not depend on the controller's data) and still records x, y, z;
+ * a step that did not end OPTIMAL / OPTIMAL_INACC records NaN W rows, as J does.  u, theta, codes, iters, J, res and the handle's state
+ * afterwards are bit-identical with recording on and off; with recording off every call keeps its code path and its allocations.  The
+ * record takes batch * T * (r + 1) * (n + m + p) * 8 bytes (MPC02 at batch 1024, r = 4, T = 20: about 4.9 GB), and one step more of
+ * it (T + 1 in the place of T) where the rollout is not fused; an allocation that fails is refused with EICOS_E_HIP and a message
+ * naming the size, and the handle is left without a trajectory.  The handle keeps the record until recording is switched off:
+ * eicos_batch_set_rollout_recording(hd, 0) waits for the handle's stream and frees it (and the staging of the data-gradient call); the J
+ * trajectory stays, eicos_batch_rollout_records and eicos_batch_rollout_data_gradient then refuse ("no recorded rows").
+ * eicos_batch_rollout_recording: 1 / 0.  eicos_batch_rollout_records copies whichever arrays are wanted to the host (any NULL).
+ *
+ * eicos_batch_rollout_data_gradient / _device: a second backward sweep over the recorded rollout, for the cost of
+ * eicos_batch_rollout_gradient, L = sum_t gu_t' u_t + sum_t gtheta_t' theta_t; theta_traj [batch][T+1][k] is the array rollout_jacobian
+ * returned.  Outputs: the non-NULL members of *out, one row per instance (for data shared by the batch the caller sums the rows):
+ *     grad_c [batch][n], grad_h [batch][m], grad_b [batch][p]   a perturbation of the data vector applied at every step (= the base
+ *                                                              vectors of the parameter map)
+ *     grad_G [batch][nnzG], grad_A [batch][nnzA]                the same for the stored values, CSC order of Gpr / Apr (= the base values
+ *                                                              under a matrix map)
+ *     grad_Cval, grad_Hval, grad_Bval [batch][nnz of the group] the slopes of the parameter map, stored CSR order
+ *     grad_u0 [batch][r], grad_Uval [batch][nnzU]               the output map
+ * For instance b, with mu_t of eicos_batch_rollout_gradient's recursion (the same bits; per-instance plant values where installed) and
+ * every product and sum rounded on its own, for t = T-1 .. 0:
+ *     d_c[i] = 0.0, then d_c[i] + (mu_t[a] * Wc_t[a][i]) for a ascending; likewise d_h, d_b
+ *     grad_c[i] = grad_c[i] + d_c[i]; likewise h, b
+ *     grad_Cval[s] = grad_Cval[s] + (d_c[i] * theta_t[col[s]])          (s over row i in stored order; likewise Hval, Bval)
+ *     grad_G[e] = grad_G[e] + ((d_c[j] * z_t[i]) - (d_h[i] * x_t[j]))   (e = (i, j)); grad_A with y_t, d_b in the place of z_t, d_h
+ *     grad_u0[a] = grad_u0[a] + mu_t[a];  grad_Uval[s] = grad_Uval[s] + (mu_t[row(s)] * x_t[col[s]])
+ * One thread owns every output entry, so the bits do not depend on the launch.  A step with NaN rows makes grad_c, grad_h, grad_b, grad_G,
+ * grad_A and the slopes of that instance NaN and leaves other instances as they are.  The output-map gradients count every step,
+ * also one whose fallback fired.
+ * Refusals (EICOS_E_INVALID with a message, nothing changed): everything eicos_batch_rollout_gradient refuses; no recorded rows on the
+ * handle (recording was off for the rollout it holds); a NULL theta_traj or out; a slope output of a group without a map; all outputs
+ * NULL; host and device pointers mixed or handed to the wrong form.
+ * Out of scope: the matrix map's slopes, the fallback law's V, the shift map, subset rollouts, a reduction over the batch on the GPU. */
+typedef struct eicos_data_gradient {
+    double *grad_c, *grad_h, *grad_b;
+    double *grad_G, *grad_A;
+    double *grad_Cval, *grad_Hval, *grad_Bval;
+    double *grad_u0, *grad_Uval;
+} eicos_data_gradient;
+size_t eicos_data_gradient_size(void); /* sizeof(eicos_data_gradient), for bindings that mirror the struct */
+int eicos_batch_set_rollout_recording(eicos_batch *hd, int on);
+int eicos_batch_rollout_recording(eicos_batch *hd);
+int eicos_batch_rollout_records(eicos_batch *hd, double *Wc, double *Wh, double *Wb, double *x_rec, double *y_rec, double *z_rec);
+int eicos_batch_rollout_data_gradient(eicos_batch *hd, const double *gu, const double *gtheta, const double *theta_traj,
+                                      const eicos_data_gradient *out);
+int eicos_batch_rollout_data_gradient_device(eicos_batch *hd, const double *dgu, const double *dgtheta, const double *dtheta_traj,
+                                             const eicos_data_gradient *dout);
 /* eicos_batch_update_param_solve_subset: the closed-loop step over a subset = eicos_batch_update_param_indexed + eicos_batch_solve_subset
  * + eicos_batch_outputs_indexed (+ the x rows), every array in list order; synchronous.
  * Fused under exactly the conditions of eicos_batch_update_param_solve (an LDS vector, a theta row that fits it, GPU-addressable theta,
@@ -879,6 +935,13 @@ int eicos_multi_has_plant_values(eicos_multi *mh);
 int eicos_multi_clear_plant_values(eicos_multi *mh);
 int eicos_multi_rollout_plant_gradient(eicos_multi *mh, const double *gu, const double *gtheta, const double *u_traj, const double *theta_traj,
                                        double *grad_theta0, double *grad_w, double *grad_f0, double *grad_val);
+/* recording and the data gradient (eicos_batch_set_rollout_recording / _rollout_recording / _rollout_records / _rollout_data_gradient):
+ * recording is switched on every shard; records and gradients are rows by shard, as eicos_multi_rollout_plant_gradient's */
+int eicos_multi_set_rollout_recording(eicos_multi *mh, int on);
+int eicos_multi_rollout_recording(eicos_multi *mh);
+int eicos_multi_rollout_records(eicos_multi *mh, double *Wc, double *Wh, double *Wb, double *x_rec, double *y_rec, double *z_rec);
+int eicos_multi_rollout_data_gradient(eicos_multi *mh, const double *gu, const double *gtheta, const double *theta_traj,
+                                      const eicos_data_gradient *out);
 /* matrix map (eicos_batch_set_matrix_map / _has_matrix_map on every shard): installed on every shard; the theta-consuming calls above pick
  * it up shard by shard */
 int eicos_multi_set_matrix_map(eicos_multi *mh, const eicos_affine_map *G, const eicos_affine_map *A);
