@@ -34,6 +34,7 @@
 #include "fused_fit.hpp"
 #include "exit_class.hpp"
 #include "resources.hpp"
+#include "call_arrays.hpp"
 #include "last_error.hpp"
 #include "plan_step.hpp"
 
@@ -181,21 +182,20 @@ struct eicos_batch {
     // stages' PLAIN instantiations, which run exactly then, read it.  Empty: not on this handle (eicos_dims.shared_operands = 0).
     DevBuf d_shop;
     // Adjoint sensitivities (eicos_batch_adjoint, _adjoint_data, _output_jacobian, _param_jacobian, _param_gradient): one device
-    // allocation, made by the first call and grown on demand: [AdjointDev (MAP_HEADER bytes) | ids [batch] | g | grad_c | grad_h | grad_b | res |
-    // grad_G | grad_A] -- the record of the launch, its index list and the staging of the host forms' rows (the contracted forms keep J /
-    // grad_theta where grad_c would be)
+    // allocation, made by the first call and grown on demand: the record of the launch (AdjointDev, MAP_HEADER bytes), its index list and
+    // the staging of the host forms' arrays, as adjoint_run declares them (call_arrays.hpp)
     DevBuf d_adj; AdjointDev adj{}; // (adj: the host copy of the most recent launch's record, the source of its copy on the handle's stream)
     // The rollout that records its Jacobians (eicos_batch_rollout_jacobian), kept for eicos_batch_rollout_gradient: one device allocation,
     // grown on demand: [AdjointDev of the fused launch (MAP_HEADER bytes) | J trajectory [batch][steps][r][k] | res trajectory
-    // [batch][steps][r] | one step's J and res rows of the batch (the path that is not fused)]; d_rollG = [gu | gtheta | grad_theta0 |
-    // grad_w] of the gradient call's host form.  rollJ_steps = 0: no trajectory on the handle; rollJ_plant, rollJ_k / _r = the plant map and counts it was
+    // [batch][steps][r] | one step's J and res rows of the batch (the path that is not fused)]; d_rollG = the staging of the gradient
+    // call's host form, as rollout_gradient declares its arrays (call_arrays.hpp).  rollJ_steps = 0: no trajectory on the handle; rollJ_plant, rollJ_k / _r = the plant map and counts it was
     // recorded under; map_gen counts the installs of the parameter, matrix, output, plant and fallback maps, rollJ_gen = its value at that rollout.
     DevBuf d_rollJ, d_rollG; int rollJ_steps = 0, rollJ_k = 0, rollJ_r = 0; PlantMapDev rollJ_plant{}; unsigned long map_gen = 0, rollJ_gen = 0;
-    // A recording rollout (eicos_batch_set_rollout_recording; launch.hpp: AdjointDev::x_rec): d_rollW = [Wc [batch][steps][r][n] | Wh
-    // [..][m] | Wb [..][p] | x [batch][steps][n] | y [..][p] | z [..][m] | one step's rows of the six (the path that is not fused)],
+    // A recording rollout (eicos_batch_set_rollout_recording; launch.hpp: AdjointDev::x_rec): d_rollW = the record and, on the path that
+    // is not fused, one step's rows behind it, each as lay_records lays them out,
     // made by the first recording rollout and grown on demand, freed (with d_rollD) when recording is switched off -- never touched while it is off.  rollW_on: the trajectory the
-    // handle holds (rollJ_steps) was recorded with its rows.  d_rollD = the staging of eicos_batch_rollout_data_gradient: the
-    // workgroups' contracted rows and, in the host form, its inputs and outputs.
+    // handle holds (rollJ_steps) was recorded with its rows.  d_rollD = the staging of eicos_batch_rollout_data_gradient, as
+    // rollout_data_gradient declares its arrays (call_arrays.hpp): the workgroups' contracted rows and, in the host form, its inputs and outputs.
     DevBuf d_rollW, d_rollD; bool roll_recording = false, rollW_on = false;
     int param_nnz[3] = {0, 0, 0}, out_nnz = 0; // stored entries of the installed parameter map's groups and of the output map (the widths of their slope gradients)
     hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr; bool adjoint_timed = false; // HIP events around the most recent adjoint launch (eicos_batch_last_adjoint_ms)
@@ -777,6 +777,13 @@ MemKind memory_kind(const void *p, size_t bytes) {
     for (size_t o = 2u << 20; o < bytes - 1; o += 2u << 20) if (probe(b + o) != MEM_PINNED) return MEM_PAGEABLE;
     return MEM_PINNED;
 }
+// The policy of a call's arrays (call_arrays.hpp; beside DeviceMem and PinnedMem, above): where an array lives, and the two copies
+struct StageMem : HipPolicy {
+    static bool on_device(const void *p) { return memory_kind(p, 1) == MEM_DEVICE; }
+    static hipError_t to_device(void *dst, const void *src, size_t bytes, hipStream_t s) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s); }
+    static hipError_t to_host(void *dst, const void *src, size_t bytes, hipStream_t s) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s); }
+};
+using Arrays = CallArrays<StageMem>;
 // the handle's two pinned bounce buffers hold at least `doubles` each
 int ensure_pin(eicos_batch *h, size_t doubles) {
     for (PinSlot &s : h->pin) HIP_TRY_AS("hipHostMalloc", s.reserve(doubles * sizeof(double)));
@@ -1787,18 +1794,70 @@ int eicos_batch_outputs_indexed_device(eicos_batch *h, const int *idx, int count
 // One launch of the handle's adjoint kernel (launch.hpp: AdjointLaunch) behind everything on the handle's stream, under the handle's settings
 // and dynamic regularisation.  Every check stands in front of the first enqueue: a refused call changes nothing.
 namespace {
-struct RecordRows;
-struct AdjointCall {
-    const int *idx; int count, nrhs; // nrhs: right-hand sides per instance (the Jacobian form: r)
-    const double *g; double *grad_c, *grad_h, *grad_b, *res, *J; // host arrays of the gradient form; J / res of the contracted form
-    bool jac, device; // the contracted form (launch.hpp: AdjointDev::J); its J, res and g live in device memory (asynchronous)
-    double *grad_G = nullptr, *grad_A = nullptr; // the gradient form: the matrix gradients (host, optional)
-    bool mmap = false, grows = false; // the contracted form: the matrix map joins when one is installed; the right-hand sides are nrhs rows of g
-    const struct RecordRows *rec = nullptr; // the contracted device form of a recording rollout: where the step's rows go (device memory)
+// Recorded rows of a recording rollout -- one step's, or the whole record (eicos_batch::d_rollW) --: six arrays one behind the other,
+// [rows][width[q]] each
+struct RecordRows {
+    double *Wc, *Wh, *Wb, *x, *y, *z; size_t width[6];
+    double *part(int q) const { double *const a[6] = {Wc, Wh, Wb, x, y, z}; return a[q]; }
+    void into(AdjointDev &rec) const { rec.grad_c = Wc; rec.grad_h = Wh; rec.grad_b = Wb; rec.x_rec = x; rec.y_rec = y; rec.z_rec = z; }
 };
-// One step's rows of a recording rollout, or the whole record (eicos_batch::d_rollW)
-struct RecordRows { double *Wc, *Wh, *Wb, *x, *y, *z; };
+struct AdjointCall {
+    const char *who;
+    const int *idx; int count, nrhs; // nrhs: right-hand sides per instance (the Jacobian form: r)
+    const double *g; double *grad_c, *grad_h, *grad_b, *res, *J; // arrays of the gradient form; J / res of the contracted form; NULL: not of the form, or not wanted
+    bool jac, device; // the contracted form (launch.hpp: AdjointDev::J); its J, res and g live in device memory (asynchronous)
+    double *grad_G = nullptr, *grad_A = nullptr; // the gradient form: the matrix gradients (optional)
+    bool mmap = false, grows = false; // the contracted form: the matrix map joins when one is installed; the right-hand sides are nrhs rows of g
+    const RecordRows *rec = nullptr; // the contracted device form of a recording rollout: where the step's rows go (device memory)
+    const char *out_name = "J"; // what the C header calls J
+};
 static_assert(sizeof(AdjointDev) <= MAP_HEADER, "the adjoint record larger than its header");
+}
+// The one layout of recorded rows: `rows` rows from base, widths per row [Wc r n | Wh r m | Wb r p | x n | y p | z m]; returns the end
+static double *lay_records(RecordRows &R, double *base, size_t rows, size_t r, size_t n, size_t m, size_t p) {
+    const size_t width[6] = {r * n, r * m, r * p, n, p, m};
+    double **const part[6] = {&R.Wc, &R.Wh, &R.Wb, &R.x, &R.y, &R.z};
+    for (int q = 0; q < 6; q++) { R.width[q] = width[q]; *part[q] = base; base += rows * width[q]; }
+    return base;
+}
+// ---- what the sensitivity and rollout calls share: their arrays (call_arrays.hpp), the timing bracket, the held trajectory ----
+static int kind_check(const Arrays &a, const char *who, bool paired = true) {
+    const std::string msg = a.kind_fault(who, paired);
+    return msg.empty() ? EICOS_OK : fail(EICOS_E_INVALID, msg);
+}
+// The arrays into `buf`.  The host form waits for the stream, grows the buffer and enqueues the copies of its inputs; the device form
+// only grows the buffer for the parts both forms have.
+static int stage(eicos_batch *h, DevBuf &buf, Arrays &a) {
+    if (!a.device) HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY_AS("hipMalloc", buf.reserve(a.bytes(), h->stream));
+    a.place(buf.p);
+    HIP_TRY_AS("hipMemcpyAsync", a.copy_in(h->stream));
+    return EICOS_OK;
+}
+// ... and back: the host form enqueues the copies of its outputs and waits; the device form has only enqueued
+static int unstage(eicos_batch *h, const Arrays &a) {
+    if (a.device) return EICOS_OK;
+    HIP_TRY_AS("hipMemcpyAsync", a.copy_out(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return EICOS_OK;
+}
+// A launch between the handle's adjoint events (eicos_batch_last_adjoint_ms: it counts as the handle's most recent adjoint launch)
+static int timed_adjoint_launch(eicos_batch *h, const char *what, const std::function<hipError_t()> &launch) {
+    if (!h->ev_a0) { HIP_TRY(hipEventCreate(&h->ev_a0)); HIP_TRY(hipEventCreate(&h->ev_a1)); }
+    HIP_TRY(hipEventRecord(h->ev_a0, h->stream));
+    HIP_TRY_AS(what, launch());
+    HIP_TRY(hipEventRecord(h->ev_a1, h->stream));
+    h->adjoint_timed = true;
+    return EICOS_OK;
+}
+// The trajectory a backward sweep or a read of the record needs on the handle.  current: it must belong to the maps now installed.
+static int held_trajectory_fault(const eicos_batch *h, const char *who, bool need_records, bool current = true) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    const std::string w(who);
+    if (h->rollJ_steps == 0) return fail(EICOS_E_INVALID, w + ": the handle holds no Jacobian trajectory (eicos_batch_rollout_jacobian records one)");
+    if (current && h->rollJ_gen != h->map_gen) return fail(EICOS_E_INVALID, w + ": a parameter, matrix, output, plant or fallback map was installed after the rollout whose Jacobians the handle holds (setting or clearing per-instance plant values counts as one): run eicos_batch_rollout_jacobian again");
+    if (need_records && !h->rollW_on) return fail(EICOS_E_INVALID, w + ": the handle holds no recorded rows: recording was off for the rollout it holds (eicos_batch_set_rollout_recording, then eicos_batch_rollout_jacobian)");
+    return EICOS_OK;
 }
 static int adjoint_list_fault(const eicos_batch *h, const int *idx, int count, const char *who) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
@@ -1810,99 +1869,66 @@ static int adjoint_run(eicos_batch *h, const AdjointCall &c) {
     if (c.count == 0) return EICOS_OK;
     const DevPat &D = h->dp;
     const size_t rows = (size_t)c.count * c.nrhs, k = c.jac ? (size_t)std::max(h->param.k, c.mmap ? h->mat.k : 0) : 0;
-    const bool up_g = !c.jac || (c.grows && !c.device); // g comes from the host
+    // The arrays, declared once -- in the order their kind is checked --, behind the launch's record and its index list.  Which of them
+    // a form has is in the call: the gradient forms (no device form) take g and give a row per data group, the contracted forms give
+    // J and take g only as nrhs rows (grows); every other pointer of the call is NULL.
+    Arrays a(c.device);
+    const int i_rec = a.fixed(MAP_HEADER), i_ids = a.fixed((size_t)h->batch * sizeof(int));
+    const int i_J = a.out(c.out_name, c.J, rows * k), i_g = a.in("g", c.g, rows * D.n);
+    const int i_c = a.out("grad_c", c.grad_c, rows * D.n), i_h = a.out("grad_h", c.grad_h, rows * D.m), i_b = a.out("grad_b", c.grad_b, rows * D.p);
+    const int i_G = a.out("grad_G", c.grad_G, rows * D.nnzG), i_A = a.out("grad_A", c.grad_A, rows * D.nnzA), i_res = a.out("res", c.res, rows);
+    int rc = kind_check(a, c.who, c.jac);
+    if (rc != EICOS_OK) return rc;
     HIP_TRY(hipSetDevice(h->device));
-    if (!c.device) HIP_TRY(hipStreamSynchronize(h->stream));
-    // the allocation: record | ids | g | grad_c (or J) | grad_h | grad_b | res | grad_G | grad_A, every part 64-byte aligned
-    auto pad = [](size_t b) { return (b + 63) & ~(size_t)63; };
-    const size_t at_ids = MAP_HEADER, at_g = at_ids + pad((size_t)h->batch * sizeof(int));
-    const size_t at_c = at_g + pad(up_g ? rows * D.n * sizeof(double) : 0);
-    const size_t at_h = at_c + pad((c.jac ? (c.device ? 0 : rows * k) : rows * D.n) * sizeof(double));
-    const size_t at_b = at_h + pad(c.jac ? 0 : rows * D.m * sizeof(double));
-    const size_t at_r = at_b + pad(c.jac ? 0 : rows * D.p * sizeof(double));
-    const size_t at_G = at_r + pad(c.device ? 0 : rows * sizeof(double));
-    const size_t at_A = at_G + pad(c.grad_G ? rows * D.nnzG * sizeof(double) : 0);
-    const size_t total = at_A + pad(c.grad_A ? rows * D.nnzA * sizeof(double) : 0);
-    HIP_TRY_AS("hipMalloc", h->d_adj.reserve(total, h->stream));
-    char *base = h->d_adj.as<char>();
-    auto dbl = [&](size_t at) { return reinterpret_cast<double *>(base + at); };
-    const int *d_ids = nullptr;
+    if ((rc = stage(h, h->d_adj, a)) != EICOS_OK) return rc;
+    int *d_ids = nullptr;
     if (c.idx) {
-        const int rc = upload_ids(h, c.idx, c.count, reinterpret_cast<int *>(base + at_ids));
-        if (rc != EICOS_OK) return rc;
-        d_ids = reinterpret_cast<const int *>(base + at_ids);
+        d_ids = static_cast<int *>(a.at(i_ids));
+        if ((rc = upload_ids(h, c.idx, c.count, d_ids)) != EICOS_OK) return rc;
     }
     AdjointDev &rec = h->adj;
     rec = AdjointDev{};
+    rec.g = a.dbl(i_g); rec.res = a.dbl(i_res);
     if (c.jac) {
         rec.pmap = h->param.k ? h->d_param.as<const ParamMapDev>() : nullptr;
         rec.mmap = c.mmap && h->mat.k ? h->d_mat.as<const MatrixMapDev>() : nullptr;
         rec.k = (int)k;
-        if (c.grows) { rec.nrhs = c.nrhs; rec.g = c.device ? c.g : dbl(at_g); }
+        if (c.grows) rec.nrhs = c.nrhs;
         else rec.omap = h->d_out.as<const OutMapDev>();
-        rec.J = c.device ? c.J : dbl(at_c);
-        rec.res = c.device ? c.res : (c.res ? dbl(at_r) : nullptr);
-        if (c.rec) { rec.grad_c = c.rec->Wc; rec.grad_h = c.rec->Wh; rec.grad_b = c.rec->Wb; rec.x_rec = c.rec->x; rec.y_rec = c.rec->y; rec.z_rec = c.rec->z; }
+        rec.J = a.dbl(i_J);
+        if (c.rec) c.rec->into(rec);
     } else {
-        rec.nrhs = c.nrhs; rec.g = dbl(at_g);
-        rec.grad_c = c.grad_c && D.n ? dbl(at_c) : nullptr; rec.grad_h = c.grad_h && D.m ? dbl(at_h) : nullptr;
-        rec.grad_b = c.grad_b && D.p ? dbl(at_b) : nullptr; rec.res = c.res ? dbl(at_r) : nullptr;
-        rec.grad_G = c.grad_G && D.nnzG ? dbl(at_G) : nullptr; rec.grad_A = c.grad_A && D.nnzA ? dbl(at_A) : nullptr;
+        rec.nrhs = c.nrhs;
+        rec.grad_c = a.dbl(i_c); rec.grad_h = a.dbl(i_h); rec.grad_b = a.dbl(i_b); rec.grad_G = a.dbl(i_G); rec.grad_A = a.dbl(i_A);
     }
-    if (up_g) HIP_TRY(hipMemcpyAsync(dbl(at_g), c.g, rows * D.n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(base, &rec, sizeof rec, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a.at(i_rec), &rec, sizeof rec, hipMemcpyHostToDevice, h->stream));
     AdjointLaunch L{};
     L.ps = h->pslot; L.inst = h->inst(); L.work = h->work(); L.count = c.count; L.list = d_ids; L.batch = h->batch;
     L.grid = h->grid; L.threads = h->threads; L.nlds = h->nlds; L.idx16 = D.idx16;
     L.dyn_delta = h->dyn_delta; L.dyn_eps = h->dyn_eps; L.cfg = h->cfg; L.dyn_lds = h->dyn_lds;
-    L.adj = h->d_adj.as<const AdjointDev>();
-    if (!h->ev_a0) { HIP_TRY(hipEventCreate(&h->ev_a0)); HIP_TRY(hipEventCreate(&h->ev_a1)); }
-    HIP_TRY(hipEventRecord(h->ev_a0, h->stream));
-    HIP_TRY(solve_build(h->threads, h->ldsres, h->w2, h->ubl).adjoint(L, h->stream));
-    HIP_TRY(hipEventRecord(h->ev_a1, h->stream));
-    h->adjoint_timed = true;
-    if (c.device) return EICOS_OK;
-    auto back = [&](double *dst, const double *src, size_t n) -> int {
-        if (dst && src && n) HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        return EICOS_OK;
-    };
-    int rc = EICOS_OK;
-    if (c.jac) rc = back(c.J, rec.J, rows * k);
-    else {
-        rc = back(c.grad_c, rec.grad_c, rows * D.n);
-        if (rc == EICOS_OK) rc = back(c.grad_h, rec.grad_h, rows * D.m);
-        if (rc == EICOS_OK) rc = back(c.grad_b, rec.grad_b, rows * D.p);
-        if (rc == EICOS_OK) rc = back(c.grad_G, rec.grad_G, rows * D.nnzG);
-        if (rc == EICOS_OK) rc = back(c.grad_A, rec.grad_A, rows * D.nnzA);
-    }
-    if (rc == EICOS_OK) rc = back(c.res, rec.res, rows);
-    if (rc != EICOS_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return EICOS_OK;
+    L.adj = static_cast<const AdjointDev *>(a.at(i_rec));
+    rc = timed_adjoint_launch(h, "adjoint launch", [&] { return solve_build(h->threads, h->ldsres, h->w2, h->ubl).adjoint(L, h->stream); });
+    return rc != EICOS_OK ? rc : unstage(h, a);
 }
 
-int eicos_batch_adjoint(eicos_batch *h, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b,
-                        double *res) {
-    const int rc = adjoint_list_fault(h, idx, count, "eicos_batch_adjoint");
+// eicos_batch_adjoint and, with the matrix gradients, eicos_batch_adjoint_data
+static int adjoint_gradients(eicos_batch *h, const char *who, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h,
+                             double *grad_b, double *grad_G, double *grad_A, double *res) {
+    const int rc = adjoint_list_fault(h, idx, count, who);
     if (rc != EICOS_OK) return rc;
-    if (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS) return fail(EICOS_E_INVALID, "eicos_batch_adjoint: nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
-    if (!g && count > 0 && h->dp.n > 0) return fail(EICOS_E_INVALID, "eicos_batch_adjoint: g is NULL");
-    for (const double *q : {g, (const double *)grad_c, (const double *)grad_h, (const double *)grad_b, (const double *)res})
-        if (q && count > 0 && memory_kind(q, 1) == MEM_DEVICE) return fail(EICOS_E_INVALID, "eicos_batch_adjoint takes host pointers: an array lives in device memory");
-    return adjoint_run(h, AdjointCall{idx, count, nrhs, g, grad_c, grad_h, grad_b, res, nullptr, false, false});
-}
-
-int eicos_batch_adjoint_data(eicos_batch *h, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b,
-                             double *grad_G, double *grad_A, double *res) {
-    const int rc = adjoint_list_fault(h, idx, count, "eicos_batch_adjoint_data");
-    if (rc != EICOS_OK) return rc;
-    if (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS) return fail(EICOS_E_INVALID, "eicos_batch_adjoint_data: nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
-    if (!g && count > 0 && h->dp.n > 0) return fail(EICOS_E_INVALID, "eicos_batch_adjoint_data: g is NULL");
-    for (const double *q : {g, (const double *)grad_c, (const double *)grad_h, (const double *)grad_b, (const double *)grad_G, (const double *)grad_A, (const double *)res})
-        if (q && count > 0 && memory_kind(q, 1) == MEM_DEVICE) return fail(EICOS_E_INVALID, "eicos_batch_adjoint_data takes host pointers: an array lives in device memory");
-    AdjointCall c{idx, count, nrhs, g, grad_c, grad_h, grad_b, res, nullptr, false, false};
+    if (nrhs < 1 || nrhs > EICOS_ADJOINT_MAX_RHS) return fail(EICOS_E_INVALID, std::string(who) + ": nrhs must lie in [1, " + std::to_string(EICOS_ADJOINT_MAX_RHS) + "], got " + std::to_string(nrhs));
+    if (!g && count > 0 && h->dp.n > 0) return fail(EICOS_E_INVALID, std::string(who) + ": g is NULL");
+    AdjointCall c{who, idx, count, nrhs, g, grad_c, grad_h, grad_b, res, nullptr, false, false};
     c.grad_G = grad_G; c.grad_A = grad_A;
     return adjoint_run(h, c);
+}
+int eicos_batch_adjoint(eicos_batch *h, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b,
+                        double *res) {
+    return adjoint_gradients(h, "eicos_batch_adjoint", idx, count, nrhs, g, grad_c, grad_h, grad_b, nullptr, nullptr, res);
+}
+int eicos_batch_adjoint_data(eicos_batch *h, const int *idx, int count, int nrhs, const double *g, double *grad_c, double *grad_h, double *grad_b,
+                             double *grad_G, double *grad_A, double *res) {
+    return adjoint_gradients(h, "eicos_batch_adjoint_data", idx, count, nrhs, g, grad_c, grad_h, grad_b, grad_G, grad_A, res);
 }
 
 // The contracted forms through whichever of the parameter map and the matrix map are installed (eicos_batch_param_jacobian: the rows of
@@ -1921,12 +1947,8 @@ static int param_contracted(eicos_batch *h, const int *idx, int count, int nrhs,
                                          std::to_string(h->param.k) + ": install it again");
     if (grows && !g && count > 0 && h->dp.n > 0) return fail(EICOS_E_INVALID, w + ": g is NULL");
     if (!out && count > 0) return fail(EICOS_E_INVALID, w + ": " + out_name + " is NULL");
-    const char *other = device ? " must live in device memory (the form without _device takes host pointers)" : " lives in device memory: this form takes host pointers (use the _device form)";
-    if (count > 0 && (memory_kind(out, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": " + out_name + other);
-    if (count > 0 && grows && g && (memory_kind(g, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": g" + other);
-    if (count > 0 && res && (memory_kind(res, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": res must live where " + out_name + " lives");
-    AdjointCall c{idx, count, grows ? nrhs : h->out.r, g, nullptr, nullptr, nullptr, res, out, true, device};
-    c.mmap = true; c.grows = grows; c.rec = rows;
+    AdjointCall c{who, idx, count, grows ? nrhs : h->out.r, grows ? g : nullptr, nullptr, nullptr, nullptr, res, out, true, device};
+    c.mmap = true; c.grows = grows; c.rec = rows; c.out_name = out_name;
     return adjoint_run(h, c);
 }
 int eicos_batch_param_jacobian(eicos_batch *h, const int *idx, int count, double *J, double *res) {
@@ -1950,11 +1972,7 @@ static int output_jacobian(eicos_batch *h, const int *idx, int count, double *J,
     if (h->mat.k != 0)
         return fail(EICOS_E_INVALID, std::string(who) + ": a matrix map is installed -- the derivative then has dG and dA terms, which this call does not form (right-hand-side data only; eicos_batch_param_jacobian forms them)");
     if (!J && count > 0) return fail(EICOS_E_INVALID, std::string(who) + ": J is NULL");
-    if (count > 0 && (memory_kind(J, 1) == MEM_DEVICE) != device)
-        return fail(EICOS_E_INVALID, std::string(who) + (device ? ": J must live in device memory (eicos_batch_output_jacobian takes host pointers)"
-                                                                 : " takes host pointers: J lives in device memory (use eicos_batch_output_jacobian_device)"));
-    if (count > 0 && res && (memory_kind(res, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, std::string(who) + ": res must live where J lives");
-    return adjoint_run(h, AdjointCall{idx, count, h->out.r, nullptr, nullptr, nullptr, nullptr, res, J, true, device});
+    return adjoint_run(h, AdjointCall{who, idx, count, h->out.r, nullptr, nullptr, nullptr, nullptr, res, J, true, device});
 }
 int eicos_batch_output_jacobian(eicos_batch *h, const int *idx, int count, double *J, double *res) {
     return output_jacobian(h, idx, count, J, res, false, "eicos_batch_output_jacobian");
@@ -2058,9 +2076,9 @@ static int set_plant_values(eicos_batch *h, int first, int count, const double *
     const std::string w(who);
     { const int rc = plant_values_range(h, first, count, w); if (rc != EICOS_OK) return rc; }
     if (!f0 && !val) return fail(EICOS_E_INVALID, w + ": f0 and val are both NULL");
-    const char *other = device ? " must live in device memory (the form without _device takes host pointers)" : " lives in device memory: this form takes host pointers (use the _device form)";
-    const struct { const void *p; const char *name; } arr[2] = {{f0, "f0"}, {val, "val"}};
-    for (const auto &a : arr) if (a.p && (memory_kind(a.p, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": " + a.name + other);
+    Arrays a(device); // (for their kind alone: the rows go straight into the handle's own)
+    a.in("f0", f0, (size_t)count * h->plant.k); a.in("val", val, (size_t)count * h->plant.nnz);
+    { const int rc = kind_check(a, who); if (rc != EICOS_OK) return rc; }
     HIP_TRY(hipSetDevice(h->device));
     struct Group { const double *src, *shared; size_t width; DevBuf &buf; const double *&at; };
     Group grp[2] = {{f0, h->plant.a.base, (size_t)h->plant.k, h->d_plant_f0, h->plant.ibase}, {val, h->plant.a.val, (size_t)h->plant.nnz, h->d_plant_val, h->plant.ival}};
@@ -2090,8 +2108,10 @@ int eicos_batch_plant_values(eicos_batch *h, int first, int count, double *f0_ou
     const std::string w("eicos_batch_plant_values");
     { const int rc = plant_values_range(h, first, count, w); if (rc != EICOS_OK) return rc; }
     if (!f0_out && !val_out) return fail(EICOS_E_INVALID, w + ": f0_out and val_out are both NULL");
-    for (const void *p : {(const void *)f0_out, (const void *)val_out})
-        if (p && memory_kind(p, 1) == MEM_DEVICE) return fail(EICOS_E_INVALID, w + ": the outputs are host arrays");
+    Arrays a(false); // (for their kind alone: the rows come straight from the handle's own)
+    a.out("f0_out", f0_out, (size_t)count * h->plant.k); a.out("val_out", val_out, (size_t)count * h->plant.nnz);
+    const std::string fault = a.kind_fault(w.c_str(), false);
+    if (!fault.empty()) return fail(EICOS_E_INVALID, fault + " (the outputs are host arrays)");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const struct { double *dst; const double *rows, *shared; size_t width; } grp[2] = {
@@ -2267,13 +2287,8 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
             return fail(EICOS_E_HIP, "rollout_jacobian: the record of a recording rollout (batch * steps * (r + 1) * (n + m + p) * 8, and one step more where the rollout is not fused: " + std::to_string(bytes) +
                                          " bytes) could not be allocated: record fewer steps or a smaller batch, or switch recording off");
         }
-        double *at = h->d_rollW.as<double>();
-        auto take = [&](RecordRows &R, size_t rows) {
-            R.Wc = at; at += rows * r * wn; R.Wh = at; at += rows * r * wm; R.Wb = at; at += rows * r * wp;
-            R.x = at; at += rows * wn; R.y = at; at += rows * wp; R.z = at; at += rows * wm;
-        };
-        take(W, B * T);
-        if (!fused) take(W1, B);
+        double *const end = lay_records(W, h->d_rollW.as<double>(), B * T, r, wn, wm, wp);
+        if (!fused) lay_records(W1, end, B, r, wn, wm, wp);
     }
     const size_t n_th = B * (T + 1) * k, n_u = B * T * r, n_w = w ? B * T * k : 0, n_cur = 2 * B * k, n_rec = B * T;
     HIP_TRY_AS("hipMalloc", h->d_roll.reserve(MAP_HEADER + (n_th + n_u + n_w + n_cur) * sizeof(double) + 2 * n_rec * sizeof(int), h->stream));
@@ -2297,7 +2312,7 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
             AdjointDev rec{};
             rec.pmap = h->d_param.as<const ParamMapDev>(); rec.mmap = h->mat.k ? h->d_mat.as<const MatrixMapDev>() : nullptr;
             rec.omap = h->d_out.as<const OutMapDev>(); rec.k = k; rec.J = d_J; rec.res = d_res;
-            if (recording) { rec.grad_c = W.Wc; rec.grad_h = W.Wh; rec.grad_b = W.Wb; rec.x_rec = W.x; rec.y_rec = W.y; rec.z_rec = W.z; }
+            if (recording) W.into(rec);
             HIP_TRY(hipMemcpyAsync(h->d_rollJ.p, &rec, sizeof rec, hipMemcpyHostToDevice, h->stream));
         }
         rc = enqueue_solve(h, &step, -1, sens ? h->d_rollJ.as<const AdjointDev>() : nullptr);
@@ -2320,11 +2335,9 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
                 if (h->fb.mask) HIP_TRY(launch_fallback_jacobian(h->pslot, h->inst(), 0, h->batch, h->fb, d_J1, d_res1, h->stream));
                 if (recording) { // the step's rows into the record, as J is moved
                     if (h->fb.mask) HIP_TRY(launch_fallback_records(h->pslot, h->inst(), 0, h->batch, h->fb, W1.Wc, W1.Wh, W1.Wb, h->stream));
-                    const struct { double *dst; const double *src; size_t width; } mv[6] = {{W.Wc, W1.Wc, r * wn}, {W.Wh, W1.Wh, r * wm}, {W.Wb, W1.Wb, r * wp},
-                                                                                          {W.x, W1.x, wn}, {W.y, W1.y, wp}, {W.z, W1.z, wm}};
-                    for (const auto &q : mv) {
-                        const size_t wb = q.width * sizeof(double);
-                        if (wb) HIP_TRY(hipMemcpy2DAsync(q.dst + (size_t)t * q.width, T * wb, q.src, wb, wb, B, hipMemcpyDeviceToDevice, h->stream));
+                    for (int q = 0; q < 6; q++) {
+                        const size_t wb = W.width[q] * sizeof(double);
+                        if (wb) HIP_TRY(hipMemcpy2DAsync(W.part(q) + (size_t)t * W.width[q], T * wb, W1.part(q), wb, wb, B, hipMemcpyDeviceToDevice, h->stream));
                     }
                 }
                 const size_t jb = (size_t)r * k * sizeof(double), rb = (size_t)r * sizeof(double);
@@ -2365,60 +2378,33 @@ int eicos_batch_rollout_jacobian(eicos_batch *h, int steps, const double *theta0
 struct PlantGradArgs { const double *u_traj, *theta_traj; double *grad_f0, *grad_val; };
 static int rollout_gradient(eicos_batch *h, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w, bool device, const char *who,
                             const PlantGradArgs *pv = nullptr) {
-    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    int rc = held_trajectory_fault(h, who, false);
+    if (rc != EICOS_OK) return rc;
     const std::string w(who);
-    if (h->rollJ_steps == 0) return fail(EICOS_E_INVALID, w + ": the handle holds no Jacobian trajectory (eicos_batch_rollout_jacobian records one)");
-    if (h->rollJ_gen != h->map_gen) return fail(EICOS_E_INVALID, w + ": a parameter, matrix, output, plant or fallback map was installed after the rollout whose Jacobians the handle holds (setting or clearing per-instance plant values counts as one): run eicos_batch_rollout_jacobian again");
     if (!gu && !gtheta) return fail(EICOS_E_INVALID, w + ": gu and gtheta are both NULL");
     if (!pv && !grad_theta0) return fail(EICOS_E_INVALID, w + ": grad_theta0 is NULL");
     if (pv && !pv->u_traj) return fail(EICOS_E_INVALID, w + ": u_traj is NULL");
     if (pv && !pv->theta_traj) return fail(EICOS_E_INVALID, w + ": theta_traj is NULL");
     if (pv && !grad_theta0 && !grad_w && !pv->grad_f0 && !pv->grad_val) return fail(EICOS_E_INVALID, w + ": grad_theta0, grad_w, grad_f0 and grad_val are all NULL");
-    const char *other = device ? " must live in device memory (the form without _device takes host pointers)" : " lives in device memory: this form takes host pointers (use the _device form)";
-    const struct { const void *p; const char *name; } arr[8] = {{gu, "gu"}, {gtheta, "gtheta"}, {grad_theta0, "grad_theta0"}, {grad_w, "grad_w"},
-        {pv ? pv->u_traj : nullptr, "u_traj"}, {pv ? pv->theta_traj : nullptr, "theta_traj"}, {pv ? pv->grad_f0 : nullptr, "grad_f0"}, {pv ? pv->grad_val : nullptr, "grad_val"}};
-    for (const auto &a : arr) if (a.p && (memory_kind(a.p, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": " + a.name + other);
     const size_t B = (size_t)h->batch, T = (size_t)h->rollJ_steps, k = (size_t)h->rollJ_k, r = (size_t)h->rollJ_r, nnz = (size_t)h->rollJ_plant.nnz;
+    const size_t n_gu = B * T * r, n_gt = B * (T + 1) * k, n_g0 = B * k, n_gw = B * T * k, n_gv = B * nnz;
+    Arrays a(device); // (the plant-gradient form's four are NULL in the other)
+    const int i_gu = a.in("gu", gu, n_gu), i_gt = a.in("gtheta", gtheta, n_gt), i_g0 = a.out("grad_theta0", grad_theta0, n_g0), i_gw = a.out("grad_w", grad_w, n_gw);
+    const int i_u = a.in("u_traj", pv ? pv->u_traj : nullptr, n_gu), i_th = a.in("theta_traj", pv ? pv->theta_traj : nullptr, n_gt);
+    const int i_gf = a.out("grad_f0", pv ? pv->grad_f0 : nullptr, n_g0), i_gv = a.out("grad_val", pv ? pv->grad_val : nullptr, n_gv);
+    if ((rc = kind_check(a, who)) != EICOS_OK) return rc;
     const bool want_val = pv && pv->grad_val && nnz > 0;
     if (pv && !grad_theta0 && !grad_w && !pv->grad_f0 && !want_val) return EICOS_OK; // (grad_val alone of a map without stored entries: no row to form)
     if (rollout_backprop_lds((int)k, (int)r, want_val) > 48 * 1024)
         return fail(EICOS_E_INVALID, w + (want_val ? ": 4 k + 3 r doubles must fit 48 KB of LDS" : ": 3 k + 2 r doubles must fit 48 KB of LDS"));
     HIP_TRY(hipSetDevice(h->device));
-    const size_t n_gu = B * T * r, n_gt = B * (T + 1) * k, n_g0 = B * k, n_gw = B * T * k, n_gv = B * nnz;
+    if ((rc = stage(h, h->d_rollG, a)) != EICOS_OK) return rc;
     const double *d_J = reinterpret_cast<const double *>(h->d_rollJ.as<char>() + MAP_HEADER);
-    const double *d_gu = gu, *d_gt = gtheta; double *d_g0 = grad_theta0, *d_gw = grad_w;
-    const double *d_u = pv ? pv->u_traj : nullptr, *d_th = pv ? pv->theta_traj : nullptr;
-    double *d_gf = pv ? pv->grad_f0 : nullptr, *d_gv = want_val ? pv->grad_val : nullptr;
-    if (!device) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY_AS("hipMalloc", h->d_rollG.reserve((n_gu + n_gt + n_g0 + n_gw + (pv ? n_gu + n_gt + n_g0 + n_gv : 0)) * sizeof(double), h->stream));
-        double *at = h->d_rollG.as<double>();
-        if (gu) { HIP_TRY(hipMemcpyAsync(at, gu, n_gu * sizeof(double), hipMemcpyHostToDevice, h->stream)); d_gu = at; }
-        at += n_gu;
-        if (gtheta) { HIP_TRY(hipMemcpyAsync(at, gtheta, n_gt * sizeof(double), hipMemcpyHostToDevice, h->stream)); d_gt = at; }
-        at += n_gt;
-        d_g0 = at; d_gw = grad_w ? at + n_g0 : nullptr;
-        at += n_g0 + n_gw;
-        if (pv) {
-            if (!grad_theta0) d_g0 = nullptr;
-            HIP_TRY(hipMemcpyAsync(at, pv->u_traj, n_gu * sizeof(double), hipMemcpyHostToDevice, h->stream)); d_u = at; at += n_gu;
-            HIP_TRY(hipMemcpyAsync(at, pv->theta_traj, n_gt * sizeof(double), hipMemcpyHostToDevice, h->stream)); d_th = at; at += n_gt;
-            d_gf = pv->grad_f0 ? at : nullptr; at += n_g0;
-            d_gv = want_val ? at : nullptr;
-        }
-    }
-    if (!h->ev_a0) { HIP_TRY(hipEventCreate(&h->ev_a0)); HIP_TRY(hipEventCreate(&h->ev_a1)); }
-    HIP_TRY(hipEventRecord(h->ev_a0, h->stream)); // (eicos_batch_last_adjoint_ms: the sweep counts as the handle's most recent adjoint launch)
-    HIP_TRY(launch_rollout_backprop(h->rollJ_plant, (int)T, h->batch, d_J, d_gu, d_gt, d_g0, d_gw, h->stream, d_u, d_th, d_gf, d_gv));
-    HIP_TRY(hipEventRecord(h->ev_a1, h->stream));
-    h->adjoint_timed = true;
-    if (device) return EICOS_OK;
-    if (grad_theta0) HIP_TRY(hipMemcpyAsync(grad_theta0, d_g0, n_g0 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (grad_w) HIP_TRY(hipMemcpyAsync(grad_w, d_gw, n_gw * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (d_gf) HIP_TRY(hipMemcpyAsync(pv->grad_f0, d_gf, n_g0 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (d_gv) HIP_TRY(hipMemcpyAsync(pv->grad_val, d_gv, n_gv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return EICOS_OK;
+    rc = timed_adjoint_launch(h, "launch_rollout_backprop", [&] {
+        return launch_rollout_backprop(h->rollJ_plant, (int)T, h->batch, d_J, a.dbl(i_gu), a.dbl(i_gt), a.dbl(i_g0), a.dbl(i_gw), h->stream,
+                                       a.dbl(i_u), a.dbl(i_th), a.dbl(i_gf), a.dbl(i_gv));
+    });
+    return rc != EICOS_OK ? rc : unstage(h, a);
 }
 int eicos_batch_rollout_jacobian_steps(eicos_batch *h) { return h ? h->rollJ_steps : fail(EICOS_E_INVALID, "NULL handle"); }
 int eicos_batch_rollout_gradient(eicos_batch *h, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w) {
@@ -2454,31 +2440,24 @@ int eicos_batch_set_rollout_recording(eicos_batch *h, int on) {
 int eicos_batch_rollout_recording(eicos_batch *h) { return h ? (h->roll_recording ? 1 : 0) : fail(EICOS_E_INVALID, "NULL handle"); }
 // the whole record of the trajectory the handle holds (rollW_on), as rollout_run laid it out
 static RecordRows record_rows(const eicos_batch *h) {
-    const size_t rows = (size_t)h->batch * h->rollJ_steps, r = (size_t)h->rollJ_r, n = (size_t)h->dp.n, m = (size_t)h->dp.m, p = (size_t)h->dp.p;
     RecordRows R{};
-    double *at = h->d_rollW.as<double>();
-    R.Wc = at; at += rows * r * n; R.Wh = at; at += rows * r * m; R.Wb = at; at += rows * r * p;
-    R.x = at; at += rows * n; R.y = at; at += rows * p; R.z = at;
+    lay_records(R, h->d_rollW.as<double>(), (size_t)h->batch * h->rollJ_steps, (size_t)h->rollJ_r, (size_t)h->dp.n, (size_t)h->dp.m, (size_t)h->dp.p);
     return R;
 }
-static int records_fault(const eicos_batch *h, const std::string &w) {
-    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
-    if (h->rollJ_steps == 0) return fail(EICOS_E_INVALID, w + ": the handle holds no Jacobian trajectory (eicos_batch_rollout_jacobian records one)");
-    if (!h->rollW_on) return fail(EICOS_E_INVALID, w + ": the handle holds no recorded rows: recording was off for the rollout it holds (eicos_batch_set_rollout_recording, then eicos_batch_rollout_jacobian)");
-    return EICOS_OK;
-}
 int eicos_batch_rollout_records(eicos_batch *h, double *Wc, double *Wh, double *Wb, double *x_rec, double *y_rec, double *z_rec) {
-    const int rc = records_fault(h, "eicos_batch_rollout_records");
+    const char *who = "eicos_batch_rollout_records";
+    int rc = held_trajectory_fault(h, who, true, false); // (the record is what the rollout left, whatever has been installed since)
     if (rc != EICOS_OK) return rc;
-    for (const double *q : {Wc, Wh, Wb, x_rec, y_rec, z_rec})
-        if (q && memory_kind(q, 1) == MEM_DEVICE) return fail(EICOS_E_INVALID, "eicos_batch_rollout_records takes host pointers: an array lives in device memory");
-    HIP_TRY(hipSetDevice(h->device));
     const RecordRows R = record_rows(h);
-    const size_t rows = (size_t)h->batch * h->rollJ_steps, r = (size_t)h->rollJ_r, n = (size_t)h->dp.n, m = (size_t)h->dp.m, p = (size_t)h->dp.p;
-    const struct { double *dst; const double *src; size_t count; } cp[6] = {{Wc, R.Wc, rows * r * n}, {Wh, R.Wh, rows * r * m}, {Wb, R.Wb, rows * r * p},
-                                                                           {x_rec, R.x, rows * n}, {y_rec, R.y, rows * p}, {z_rec, R.z, rows * m}};
-    for (const auto &q : cp)
-        if (q.dst && q.count) HIP_TRY(hipMemcpyAsync(q.dst, q.src, q.count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    const size_t rows = (size_t)h->batch * h->rollJ_steps;
+    double *const dst[6] = {Wc, Wh, Wb, x_rec, y_rec, z_rec};
+    const char *const name[6] = {"Wc", "Wh", "Wb", "x_rec", "y_rec", "z_rec"};
+    Arrays a(false); // (for their kind alone: the rows come straight from the record)
+    for (int q = 0; q < 6; q++) a.out(name[q], dst[q], rows * R.width[q]);
+    if ((rc = kind_check(a, who, false)) != EICOS_OK) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    for (int q = 0; q < 6; q++)
+        if (dst[q] && R.width[q]) HIP_TRY(hipMemcpyAsync(dst[q], R.part(q), rows * R.width[q] * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return EICOS_OK;
 }
@@ -2486,11 +2465,9 @@ int eicos_batch_rollout_records(eicos_batch *h, double *Wc, double *Wh, double *
 // front of the first enqueue.  The host form stages its arrays in d_rollD and waits; the device form only enqueues.
 static int rollout_data_gradient(eicos_batch *h, const double *gu, const double *gtheta, const double *theta_traj, const eicos_data_gradient *out,
                                  bool device, const char *who) {
-    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    int rc = held_trajectory_fault(h, who, true);
+    if (rc != EICOS_OK) return rc;
     const std::string w(who);
-    if (h->rollJ_steps == 0) return fail(EICOS_E_INVALID, w + ": the handle holds no Jacobian trajectory (eicos_batch_rollout_jacobian records one)");
-    if (h->rollJ_gen != h->map_gen) return fail(EICOS_E_INVALID, w + ": a parameter, matrix, output, plant or fallback map was installed after the rollout whose Jacobians the handle holds (setting or clearing per-instance plant values counts as one): run eicos_batch_rollout_jacobian again");
-    { const int rc = records_fault(h, w); if (rc != EICOS_OK) return rc; }
     if (!gu && !gtheta) return fail(EICOS_E_INVALID, w + ": gu and gtheta are both NULL");
     if (!theta_traj) return fail(EICOS_E_INVALID, w + ": theta_traj is NULL");
     if (!out) return fail(EICOS_E_INVALID, w + ": out is NULL");
@@ -2503,57 +2480,35 @@ static int rollout_data_gradient(eicos_batch *h, const double *gu, const double 
     double *const sl[3] = {out->grad_Cval, out->grad_Hval, out->grad_Bval};
     for (int q = 0; q < 3; q++)
         if (sl[q] && !h->param.g[q].base) return fail(EICOS_E_INVALID, w + ": " + slope[q] + " asked, but the parameter map has no " + "chb"[q] + " group");
-    struct Out { double *host; size_t width; const char *name; double *dev; };
-    Out o[10] = {{out->grad_c, n, "grad_c", nullptr}, {out->grad_h, m, "grad_h", nullptr}, {out->grad_b, p, "grad_b", nullptr},
-                 {out->grad_G, (size_t)P.nnzG, "grad_G", nullptr}, {out->grad_A, (size_t)P.nnzA, "grad_A", nullptr},
-                 {out->grad_Cval, nnzC, "grad_Cval", nullptr}, {out->grad_Hval, nnzH, "grad_Hval", nullptr}, {out->grad_Bval, nnzB, "grad_Bval", nullptr},
-                 {out->grad_u0, r, "grad_u0", nullptr}, {out->grad_Uval, nnzU, "grad_Uval", nullptr}};
+    // The arrays: the sweep's own rows (launch.hpp: DataGradDev::stage), the three inputs, and the outputs in the order of the struct
+    // -- a group the pattern or the map does not have has no width: no row to form
+    const struct { double *host; size_t width; const char *name; } o[10] = {
+        {out->grad_c, n, "grad_c"}, {out->grad_h, m, "grad_h"}, {out->grad_b, p, "grad_b"}, {out->grad_G, (size_t)P.nnzG, "grad_G"}, {out->grad_A, (size_t)P.nnzA, "grad_A"},
+        {out->grad_Cval, nnzC, "grad_Cval"}, {out->grad_Hval, nnzH, "grad_Hval"}, {out->grad_Bval, nnzB, "grad_Bval"}, {out->grad_u0, r, "grad_u0"}, {out->grad_Uval, nnzU, "grad_Uval"}};
     bool any = false;
-    for (const Out &q : o) any = any || q.host;
+    for (const auto &q : o) any = any || q.host;
     if (!any) return fail(EICOS_E_INVALID, w + ": every output of out is NULL");
-    const char *other = device ? " must live in device memory (the form without _device takes host pointers)" : " lives in device memory: this form takes host pointers (use the _device form)";
-    const struct { const void *p; const char *name; } in[3] = {{gu, "gu"}, {gtheta, "gtheta"}, {theta_traj, "theta_traj"}};
-    for (const auto &a : in) if (a.p && (memory_kind(a.p, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": " + a.name + other);
-    for (const Out &q : o) if (q.host && (memory_kind(q.host, 1) == MEM_DEVICE) != device) return fail(EICOS_E_INVALID, w + ": " + q.name + other);
+    const size_t n_gu = B * T * r, n_gt = B * (T + 1) * k;
+    Arrays a(device);
+    const int i_stage = a.fixed((size_t)rollout_data_backprop_grid(h->batch) * (n + m + p) * sizeof(double));
+    const int i_gu = a.in("gu", gu, n_gu), i_gt = a.in("gtheta", gtheta, n_gt), i_th = a.in("theta_traj", theta_traj, n_gt);
+    int i_o[10];
+    for (int q = 0; q < 10; q++) i_o[q] = a.out(o[q].name, o[q].host, B * o[q].width);
+    if ((rc = kind_check(a, who)) != EICOS_OK) return rc;
     if (rollout_backprop_lds((int)k, (int)r) > 48 * 1024) return fail(EICOS_E_INVALID, w + ": 3 k + 2 r doubles must fit 48 KB of LDS");
     HIP_TRY(hipSetDevice(h->device));
-    const size_t n_gu = B * T * r, n_gt = B * (T + 1) * k, n_stage = (size_t)rollout_data_backprop_grid(h->batch) * (n + m + p);
-    size_t n_out = 0;
-    for (const Out &q : o) if (q.host) n_out += B * q.width;
-    if (!device) HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY_AS("hipMalloc", h->d_rollD.reserve((n_stage + (device ? 0 : n_gu + 2 * n_gt + n_out) + 1) * sizeof(double), h->stream));
-    double *at = h->d_rollD.as<double>();
+    if ((rc = stage(h, h->d_rollD, a)) != EICOS_OK) return rc;
     DataGradDev D{};
-    D.stage = at; at += n_stage;
-    D.gu = gu; D.gth = gtheta; D.theta = theta_traj;
-    if (!device) {
-        if (gu) { HIP_TRY(hipMemcpyAsync(at, gu, n_gu * sizeof(double), hipMemcpyHostToDevice, h->stream)); D.gu = at; }
-        at += n_gu;
-        if (gtheta) { HIP_TRY(hipMemcpyAsync(at, gtheta, n_gt * sizeof(double), hipMemcpyHostToDevice, h->stream)); D.gth = at; }
-        at += n_gt;
-        HIP_TRY(hipMemcpyAsync(at, theta_traj, n_gt * sizeof(double), hipMemcpyHostToDevice, h->stream)); D.theta = at; at += n_gt;
-    }
-    for (Out &q : o) {
-        if (!q.host) continue;
-        if (device) q.dev = q.host; else { q.dev = at; at += B * q.width; }
-        if (q.width == 0) q.dev = nullptr; // (a group the pattern or the map does not have: no row to form)
-    }
+    D.stage = a.dbl(i_stage);
+    D.gu = a.dbl(i_gu); D.gth = a.dbl(i_gt); D.theta = a.dbl(i_th);
     const RecordRows R = record_rows(h);
     D.J = reinterpret_cast<const double *>(h->d_rollJ.as<char>() + MAP_HEADER);
     D.Wc = R.Wc; D.Wh = R.Wh; D.Wb = R.Wb; D.x = R.x; D.y = R.y; D.z = R.z;
     D.pmap = h->param; D.omap = h->out;
-    D.grad_c = o[0].dev; D.grad_h = o[1].dev; D.grad_b = o[2].dev; D.grad_G = o[3].dev; D.grad_A = o[4].dev;
-    D.grad_val[0] = o[5].dev; D.grad_val[1] = o[6].dev; D.grad_val[2] = o[7].dev; D.grad_u0 = o[8].dev; D.grad_Uval = o[9].dev;
-    if (!h->ev_a0) { HIP_TRY(hipEventCreate(&h->ev_a0)); HIP_TRY(hipEventCreate(&h->ev_a1)); }
-    HIP_TRY(hipEventRecord(h->ev_a0, h->stream)); // (eicos_batch_last_adjoint_ms: the sweep counts as the handle's most recent adjoint launch)
-    HIP_TRY(launch_rollout_data_backprop(h->pslot, h->rollJ_plant, (int)T, h->batch, D, h->stream));
-    HIP_TRY(hipEventRecord(h->ev_a1, h->stream));
-    h->adjoint_timed = true;
-    if (device) return EICOS_OK;
-    for (const Out &q : o)
-        if (q.host && q.dev) HIP_TRY(hipMemcpyAsync(q.host, q.dev, B * q.width * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return EICOS_OK;
+    D.grad_c = a.dbl(i_o[0]); D.grad_h = a.dbl(i_o[1]); D.grad_b = a.dbl(i_o[2]); D.grad_G = a.dbl(i_o[3]); D.grad_A = a.dbl(i_o[4]);
+    D.grad_val[0] = a.dbl(i_o[5]); D.grad_val[1] = a.dbl(i_o[6]); D.grad_val[2] = a.dbl(i_o[7]); D.grad_u0 = a.dbl(i_o[8]); D.grad_Uval = a.dbl(i_o[9]);
+    rc = timed_adjoint_launch(h, "launch_rollout_data_backprop", [&] { return launch_rollout_data_backprop(h->pslot, h->rollJ_plant, (int)T, h->batch, D, h->stream); });
+    return rc != EICOS_OK ? rc : unstage(h, a);
 }
 int eicos_batch_rollout_data_gradient(eicos_batch *h, const double *gu, const double *gtheta, const double *theta_traj, const eicos_data_gradient *out) {
     return rollout_data_gradient(h, gu, gtheta, theta_traj, out, false, "eicos_batch_rollout_data_gradient");

@@ -11,6 +11,7 @@ import test_param_update as P  # (its _data, _map, _theta, _twins)
 import test_rhs_update as R    # (its _second_rhs)
 import test_rollout as RO      # (its _fmap)
 from test_param_step import _omap
+from test_rollout_data_gradient import _wanted
 
 B = 8
 KEYS = R.KEYS
@@ -105,6 +106,72 @@ def test_rollout_buffer_grows_between_two_rollouts():
 
 
 @pytest.mark.gpu
+def test_adjoint_staging_grows_between_two_adjoint_calls():
+    """d_adj: one right-hand side for instance 3 alone, then two for every instance of the batch."""
+    pat, d = _case()
+    g, ref = P._twins(pat, d, B)
+    rhs = np.random.default_rng(5).standard_normal((B, 2, pat.n))
+    small = g.adjoint_data(rhs[[3], :1], idx=[3])
+    got, want = g.adjoint_data(rhs), ref.adjoint_data(rhs)
+    _assert_same(got, want, "adjoint")  # grad_c, grad_h, grad_b, grad_G, grad_A, res
+    _assert_same(small, ref.adjoint_data(rhs[[3], :1], idx=[3]), "adjoint: the small call, in the grown buffer")
+    _still_usable(g, ref, "adjoint")
+
+
+def _recording_twins():
+    """Two solved handles under the closed-loop maps with recording on, and theta0."""
+    pat, d = _case()
+    g, ref = P._twins(pat, d, B)
+    pm, om, fm = _closed_loop_maps(pat, d)
+    for s in (g, ref):
+        s.set_param_map(pm); s.set_output_map(om); s.set_plant_map(fm); s.set_rollout_recording(True)
+    return g, ref, P._theta(B, pm.k), pm
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fused", ["1", "0"])
+def test_jacobian_trajectory_and_record_grow_between_two_recording_rollouts(fused, monkeypatch):
+    """d_rollJ and d_rollW: one step, then three.  Not fused, both also hold one step's rows behind the trajectories."""
+    monkeypatch.setenv("EICOS_FUSED_UPDATE", fused)
+    g, ref, theta0, _ = _recording_twins()
+    short = list(g.rollout_jacobian(theta0, 1)) + list(g.rollout_records())
+    got, want = list(g.rollout_jacobian(theta0, 3)), list(ref.rollout_jacobian(theta0, 3))
+    got += g.rollout_records(); want += ref.rollout_records()
+    assert g.last_rollout_launches() == ref.last_rollout_launches() and (fused == "1" or g.last_rollout_launches() == 3)
+    _assert_same(got, want, "recording rollout")  # u, theta, codes, iters, J, res, Wc, Wh, Wb, x, y, z
+    first = [q for q in range(len(want)) if q != 1]  # (theta has a row more than steps)
+    _assert_same([short[q][:, :1] for q in first], [want[q][:, :1] for q in first], "first step")
+    _assert_same([short[1][:, :2]], [want[1][:, :2]], "first step: theta")
+    _still_usable(g, ref, "recording rollout")
+
+
+def _sweeps_after_each_rollout(sweep, what):
+    """g: a recording rollout of one step and the sweep over it, then the same over three steps; ref: the three steps alone."""
+    g, ref, theta0, pm = _recording_twins()
+
+    def run(s, steps):
+        out = s.rollout_jacobian(theta0, steps)
+        rng = np.random.default_rng(7)
+        return list(sweep(s, pm, out[0], out[1], rng.standard_normal(out[0].shape), rng.standard_normal(out[1].shape)))
+
+    run(g, 1)
+    _assert_same(run(g, 3), run(ref, 3), what)
+    _still_usable(g, ref, what)
+
+
+@pytest.mark.gpu
+def test_gradient_staging_grows_between_two_rollout_gradients():
+    """d_rollG, through both of its calls."""
+    _sweeps_after_each_rollout(lambda s, pm, u, th, gu, gth: s.rollout_gradient(gu, gth) + s.rollout_plant_gradient(u, th, gu, gth), "rollout gradient")
+
+
+@pytest.mark.gpu
+def test_data_gradient_staging_grows_between_two_data_gradients():
+    """d_rollD: every output the maps allow."""
+    _sweeps_after_each_rollout(lambda s, pm, u, th, gu, gth: s.rollout_data_gradient(th, gu, gth, want=_wanted(pm)).values(), "data gradient")
+
+
+@pytest.mark.gpu
 def test_matrix_staging_buffer_grows_between_two_param_updates(monkeypatch):
     monkeypatch.setenv("EICOS_MATRIX_STAGE_MB", "1")  # (conftest.py sets EICOS_EXPERIMENT=1; as tests/test_matrix_param.py sets the knob)
     pat, d = _case()
@@ -172,6 +239,12 @@ def test_destroying_a_handle_with_every_optional_buffer_leaves_the_device_usable
     monkeypatch.delenv("EICOS_FUSED_STAGED")
     g.set_param_map(pm); g.set_output_map(om); g.set_plant_map(fm)
     g.rollout(P._theta(B, pm.k), 2)                          # rollout buffer, behind three maps
+    g.adjoint_data(np.ones((B, 1, pat.n)))                   # adjoint staging
+    g.set_rollout_recording(True)
+    out = g.rollout_jacobian(P._theta(B, pm.k), 2)           # Jacobian trajectory and record
+    g.rollout_gradient(gu=np.ones_like(out[0]))              # gradient staging
+    g.rollout_plant_gradient(out[0], out[1], gu=np.ones_like(out[0]))
+    g.rollout_data_gradient(out[1], gu=np.ones_like(out[0]), want=_wanted(pm))  # data-gradient staging
     g.set_matrix_map(M._mmap(d, pm.k))
     g.update_param(P._theta(B, pm.k))                        # matrix staging buffer
     g.close()
