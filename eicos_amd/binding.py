@@ -161,6 +161,7 @@ def _signatures():
         ("eicos_*_output_jacobian", [vp, ip, i, dp, dp]), ("eicos_batch_output_jacobian_device", [vp, ip, i, vp, vp]),
         ("eicos_*_param_jacobian", [vp, ip, i, dp, dp]), ("eicos_batch_param_jacobian_device", [vp, ip, i, vp, vp]),
         ("eicos_*_param_gradient", [vp, ip, i, i, dp, dp, dp]), ("eicos_batch_param_gradient_device", [vp, ip, i, i, vp, vp, vp]),
+        ("eicos_*_set_adjoint_scaling", [vp, i]), ("eicos_*_adjoint_scaling", [vp]),
         # policies and timers
         ("eicos_*_set_warm_start", [vp, d]), ("eicos_*_set_dynamic_regularization", [vp, d, d]), ("eicos_*_retry_counts", [vp, i, i, ip, i]),
         ("eicos_*_set_settings", [vp, sp]), ("eicos_*_get_settings", [vp, sp]), ("eicos_*_set_retry", [vp, rp]), ("eicos_*_get_retry", [vp, rp]),
@@ -280,6 +281,47 @@ def _info_columns(arr, count):
     """The first `count` records of an Info array as a dict of arrays, one per field in declaration order."""
     raw = np.frombuffer(arr, dtype=np.dtype([(k, "f8" if t is C.c_double else "i4") for k, t in Info._fields_]))[:count]
     return {k: raw[k].copy() for k in raw.dtype.names}
+
+
+# the cone scaling of the adjoint's K (EICOS_ADJOINT_* of include/eicos_amd.h)
+ADJOINT_NT, ADJOINT_CENTRED = 0, 1
+ADJOINT_SCALINGS = {"nt": ADJOINT_NT, "centred": ADJOINT_CENTRED}
+
+
+def centred_pair(pat, s, z):
+    """The pair (s, z) [m] the centred adjoint scaling is formed from (EICOS_ADJOINT_CENTRED; include/eicos_amd.h): per second-order
+    cone, in the Jordan frame (1, +-u) that s and z share, the larger eigenvalue of each complementary pair (l1, w1), (l2, w2) is kept
+    and the smaller one replaced so that l1 w1 = l2 w2 = sqrt(l1 w1 l2 w2).  LP rows, cones of dimension 1, cones whose s and z are
+    parallel and cones with an eigenvalue <= 0 are returned as they are.  The numpy restatement of what adjoint_instance does on the
+    un-equilibrated result rows; returns new arrays."""
+    s, z = np.array(s, dtype=np.float64), np.array(z, dtype=np.float64)
+    o = pat.l
+    for d in (int(v) for v in pat.q):
+        sc, zc = s[o:o + d], z[o:o + d]
+        o += d
+        if d == 1:
+            continue
+        v = sc[1:] / sc[0] - zc[1:] / zc[0]
+        nv = np.sqrt(v @ v)
+        if not nv > 0.0:
+            continue
+        u = v / nv
+        su, zu = sc[1:] @ u, zc[1:] @ u
+        l1, l2, w1, w2 = sc[0] + su, sc[0] - su, zc[0] + zu, zc[0] - zu
+        if not min(l1, l2, w1, w2) > 0.0:
+            continue
+        mu = np.sqrt(l1 * w1 * l2 * w2)
+        if l1 >= w1:
+            w1 = mu / l1
+        else:
+            l1 = mu / w1
+        if l2 >= w2:
+            w2 = mu / l2
+        else:
+            l2 = mu / w2
+        sc[0], sc[1:] = 0.5 * (l1 + l2), 0.5 * (l1 - l2) * u
+        zc[0], zc[1:] = 0.5 * (w1 + w2), 0.5 * (w1 - w2) * u
+    return s, z
 
 
 def _known_settings(who, fields):
@@ -1093,6 +1135,20 @@ class _Solver:
         else:
             self._call("rollout_gradient", *[_dp_or_dummy(a) for a in (gu, gtheta, g0, gw)])
         return g0, gw
+
+    # ---- the cone scaling of the adjoint (include/eicos_amd.h: EICOS_ADJOINT_NT / _CENTRED) ----
+    def set_adjoint_scaling(self, mode: str):
+        """"nt" (the default): K of every adjoint carries the NT scaling of the returned (s, z).  "centred": of centred_pair(s, z) --
+        the derivative of the solution map where an active second-order cone's curvature fixes the optimum; use it on any pattern
+        with cones.  Holds from the next adjoint launch, for adjoint(), adjoint_data(), output_jacobian(), param_jacobian(),
+        param_gradient() and rollout_jacobian(); a J trajectory the handle holds stays as it was recorded."""
+        if mode not in ADJOINT_SCALINGS:
+            raise ValueError(f"set_adjoint_scaling: mode must be one of {', '.join(map(repr, ADJOINT_SCALINGS))}, got {mode!r}")
+        self._call("set_adjoint_scaling", ADJOINT_SCALINGS[mode])
+
+    def adjoint_scaling(self) -> str:
+        v = _nonneg(self._query("adjoint_scaling"))
+        return {c: k for k, c in ADJOINT_SCALINGS.items()}[v]
 
     # ---- a recording rollout and the gradient with respect to the controller's own data (include/eicos_amd.h) ----
     def set_rollout_recording(self, on: bool):

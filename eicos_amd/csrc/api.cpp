@@ -198,6 +198,7 @@ struct eicos_batch {
     // rollout_data_gradient declares its arrays (call_arrays.hpp): the workgroups' contracted rows and, in the host form, its inputs and outputs.
     DevBuf d_rollW, d_rollD; bool roll_recording = false, rollW_on = false;
     int param_nnz[3] = {0, 0, 0}, out_nnz = 0; // stored entries of the installed parameter map's groups and of the output map (the widths of their slope gradients)
+    int adjoint_scaling = EICOS_ADJOINT_NT; // eicos_batch_set_adjoint_scaling: what adjoint_run and rollout_run put into AdjointDev::centred
     hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr; bool adjoint_timed = false; // HIP events around the most recent adjoint launch (eicos_batch_last_adjoint_ms)
 
     // The events and the stream the handle made; the buffers free themselves after this body.  eicos_batch_destroy has set the device and
@@ -1888,6 +1889,7 @@ static int adjoint_run(eicos_batch *h, const AdjointCall &c) {
     }
     AdjointDev &rec = h->adj;
     rec = AdjointDev{};
+    rec.centred = h->adjoint_scaling == EICOS_ADJOINT_CENTRED;
     rec.g = a.dbl(i_g); rec.res = a.dbl(i_res);
     if (c.jac) {
         rec.pmap = h->param.k ? h->d_param.as<const ParamMapDev>() : nullptr;
@@ -2310,6 +2312,7 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
         if (h->fb.mask) step.fb = h->d_fb.as<const FallbackDev>(); // (every step's u row, and with sens its J and res rows: kernels.hip, rollout_record)
         if (sens) { // the record of the launch's adjoints (launch.hpp: AdjointDev, the contracted form with the output map's rows), as adjoint_run fills it
             AdjointDev rec{};
+            rec.centred = h->adjoint_scaling == EICOS_ADJOINT_CENTRED;
             rec.pmap = h->d_param.as<const ParamMapDev>(); rec.mmap = h->mat.k ? h->d_mat.as<const MatrixMapDev>() : nullptr;
             rec.omap = h->d_out.as<const OutMapDev>(); rec.k = k; rec.J = d_J; rec.res = d_res;
             if (recording) W.into(rec);
@@ -2423,6 +2426,16 @@ int eicos_batch_rollout_plant_gradient_device(eicos_batch *h, const double *dgu,
     const PlantGradArgs pv{du_traj, dtheta_traj, dgrad_f0, dgrad_val};
     return rollout_gradient(h, dgu, dgtheta, dgrad_theta0, dgrad_w, true, "eicos_batch_rollout_plant_gradient_device", &pv);
 }
+
+// ---- the cone scaling of the adjoint (include/eicos_amd.h: EICOS_ADJOINT_NT / _CENTRED): host state only, read by the next adjoint launch ----
+int eicos_batch_set_adjoint_scaling(eicos_batch *h, int mode) {
+    if (!h) return fail(EICOS_E_INVALID, "NULL handle");
+    if (mode != EICOS_ADJOINT_NT && mode != EICOS_ADJOINT_CENTRED)
+        return fail(EICOS_E_INVALID, "set_adjoint_scaling: mode must be EICOS_ADJOINT_NT (0) or EICOS_ADJOINT_CENTRED (1), got " + std::to_string(mode));
+    h->adjoint_scaling = mode;
+    return EICOS_OK;
+}
+int eicos_batch_adjoint_scaling(eicos_batch *h) { return h ? h->adjoint_scaling : fail(EICOS_E_INVALID, "NULL handle"); }
 
 // ---- a recording rollout and the gradient with respect to the controller's own data (include/eicos_amd.h) ----
 size_t eicos_data_gradient_size(void) { return sizeof(eicos_data_gradient); }

@@ -3636,10 +3636,51 @@ static __device__ __noinline__ __attribute__((not_tail_called)) int retry_betwee
     return uni(g_S.attempt);
 }
 
+// ---------------- the re-centred pair of every second-order cone (AdjointDev::centred; include/eicos_amd.h: EICOS_ADJOINT_CENTRED) ----------------
+// (s, z) [m], un-equilibrated, in place.  Per cone, in the Jordan frame (1, +-u), u = v / |v|, v = s_t / s_0 - z_t / z_0, that s and z
+// share: s = (l1 c1 + l2 c2) / 2, z = (w1 c1 + w2 c2) / 2; the larger eigenvalue of each complementary pair (l1, w1), (l2, w2) stays
+// and the smaller one is replaced so that l1 w1 = l2 w2 = sqrt(l1 w1 l2 w2).  A cone with v = 0 (dimension 1; s and z parallel) or
+// with an eigenvalue that is not positive stays as it is, and so do the LP rows.  The three dot products over the tail are one pass:
+// s_t'u and z_t'u as (s_t'v) / |v| and (z_t'v) / |v|.  Begins and ends with a barrier.
+template <int T>
+static __device__ __noinline__ __attribute__((not_tail_called)) void dev_centre_cones(int ps, gdbl_p s, gdbl_p z) {
+    ps = uni(ps); s = uni_ptr(s); z = uni_ptr(z);
+    const DevPat &P = c_pat[ps];
+    __syncthreads();
+    for_cones<T>(ps, [&](int c, auto G, int ln) {
+        constexpr int g = decltype(G)::value;
+        const int d = P.cq[c];
+        gdbl_p sc = s + P.cone_off[c], zc = z + P.cone_off[c];
+        const double s0 = sc[0], z0 = zc[0];
+        double vv = 0., sv = 0., zv = 0.;
+        for (int k = 1 + ln; k < d; k += g) {
+            const double a = sc[k], b = zc[k], v = a / s0 - b / z0;
+            vv += v * v; sv += a * v; zv += b * v;
+        }
+        vv = grp_sum<g>(vv); sv = grp_sum<g>(sv); zv = grp_sum<g>(zv);
+        const double nv = sqrt(vv);
+        if (!(nv > 0.)) return; // (the same on every lane of the cone's wavefront, as every test below)
+        const double su = sv / nv, zu = zv / nv;
+        double l1 = s0 + su, l2 = s0 - su, w1 = z0 + zu, w2 = z0 - zu;
+        if (!(l1 > 0. && l2 > 0. && w1 > 0. && w2 > 0.)) return;
+        const double mu = sqrt(l1 * w1 * l2 * w2);
+        if (l1 >= w1) w1 = mu / l1; else l1 = mu / w1;
+        if (l2 >= w2) w2 = mu / l2; else l2 = mu / w2;
+        const double sa = 0.5 * (l1 - l2), za = 0.5 * (w1 - w2);
+        for (int k = 1 + ln; k < d; k += g) { // (s0, z0: the old heads, in registers)
+            const double u = (sc[k] / s0 - zc[k] / z0) / nv;
+            sc[k] = sa * u; zc[k] = za * u;
+        }
+        if (ln == 0) { sc[0] = 0.5 * (l1 + l2); zc[0] = 0.5 * (w1 + w2); }
+    });
+    __syncthreads();
+}
+
 // ---------------- adjoint sensitivities of one instance (launch.hpp: AdjointDev) ----------------
 // At the (x, y, z, s) the instance's last solve returned: K [w_x; w_y; w_z] = [g; 0; 0] with the NT scaling of (s, z) in K's scaling
 // block, grad_c = -w_x, grad_h = w_z, grad_b = w_y, for every right-hand side g of the launch.  Four steps:
-//   1. the equilibrated (s, z) of the result rows into buffer set 1 of the iterate (the result rows themselves are only read), the KKT
+//   1. the equilibrated (s, z) of the result rows into buffer set 1 of the iterate (the result rows themselves are only read) -- with
+//      A.centred, one workgroup-uniform branch, the cones' pairs of that copy re-centred first (dev_centre_cones) --, the KKT
 //      image as instance_begin leaves it, and the scalings half of stage_resid on that iterate (its ADJ instantiation);
 //   2. the factorisation of the handle's factor path, as solve_instance calls it;
 //   3. per right-hand side: D [g; 0; 0] into w_rhs1k, kkt_solve with its refinement (one right-hand side, ADJ: the error norm it
@@ -3699,6 +3740,11 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void adjoint_ins
     { // (s, z) re-equilibrated as a warm start re-forms them, without the push into the cone; tau = 1: W is invariant under the common scaling
         const IterBuf it = iter_buf(P, I, W, 1);
         gcdbl_p rz = I + P.i_z, rs = I + P.i_s;
+        if (uni(A.centred)) { // EICOS_ADJOINT_CENTRED: the cones' pairs re-centred in the caller's space (ge is not constant within a cone), then ge
+            FOR_T(i, m) { it.z[i] = rz[i]; it.s[i] = rs[i]; }
+            dev_centre_cones<T>(ps, it.s, it.z); // (begins and ends with a barrier)
+            FOR_T(i, m) { const double g = ge[i]; it.z[i] = it.z[i] * g; it.s[i] = it.s[i] / g; }
+        } else
         FOR_T(i, m) { const double g = ge[i]; it.z[i] = rz[i] * g; it.s[i] = rs[i] / g; }
     }
     __syncthreads();

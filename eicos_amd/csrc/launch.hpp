@@ -130,8 +130,10 @@ struct SolveLaunch {
 // [count][rows][n], [count][rows][m], [count][rows][p] are then stored as well, with the expressions of the gradient form, in front of
 // the contraction; x_rec [count][n], y_rec [count][p], z_rec [count][m] (NULL = not recorded) take the instance's un-equilibrated result
 // rows, whatever the exit code.  The gradient form leaves the three NULL.
+// centred != 0 (eicos_batch_set_adjoint_scaling, EICOS_ADJOINT_CENTRED; in the padding behind nrhs: the record keeps its size): the
+// scaling block is formed from the re-centred pair of every second-order cone (kernels.hip: centre_cones) instead of the result rows'.
 struct AdjointDev {
-    int nrhs; const double *g; double *grad_c, *grad_h, *grad_b, *res;
+    int nrhs, centred; const double *g; double *grad_c, *grad_h, *grad_b, *res;
     const ParamMapDev *pmap; const OutMapDev *omap; double *J;
     double *grad_G, *grad_A; const MatrixMapDev *mmap; int k;
     double *x_rec, *y_rec, *z_rec;

@@ -754,6 +754,12 @@ int eicos_multi_set_settings(eicos_multi *mh, const eicos_settings *st) {
     return in_turn(mh, false, [&](int s) { return eicos_batch_set_settings(mh->shard[s], st); });
 }
 
+// the cone scaling of the adjoint (the mode is validated alike by every shard: the first refuses before any has changed)
+int eicos_multi_set_adjoint_scaling(eicos_multi *mh, int mode) {
+    return in_turn(mh, false, [&](int s) { return eicos_batch_set_adjoint_scaling(mh->shard[s], mode); });
+}
+int eicos_multi_adjoint_scaling(eicos_multi *mh) { return mh ? eicos_batch_adjoint_scaling(mh->shard[0]) : mfail(EICOS_E_INVALID, "NULL handle"); }
+
 int eicos_multi_get_settings(eicos_multi *mh, eicos_settings *out) {
     if (!mh) return mfail(EICOS_E_INVALID, "NULL handle");
     const int rc = eicos_batch_get_settings(mh->shard[0], out);

@@ -502,6 +502,16 @@ namespace EiCOS
             if (indices.empty()) return;
             mcheck(eicos_multi_param_gradient(h_, indices.data(), (int)indices.size(), nrhs, g, grad_theta, res), "eicos_multi_param_gradient");
         }
+        // The cone scaling of K in every call above and in rolloutJacobian (eicos_multi_set_adjoint_scaling): EICOS_ADJOINT_NT (the
+        // default) or EICOS_ADJOINT_CENTRED -- the NT scaling of the re-centred pair of every second-order cone, the derivative where an
+        // active cone's curvature fixes the optimum: for any pattern with cones.  Holds from the next adjoint launch on every shard.
+        void setAdjointScaling(int mode) { mcheck(eicos_multi_set_adjoint_scaling(h_, mode), "eicos_multi_set_adjoint_scaling"); }
+        int adjointScaling() const
+        {
+            const int v = eicos_multi_adjoint_scaling(h_);
+            if (v < 0) mcheck(v, "eicos_multi_adjoint_scaling");
+            return v;
+        }
         // Extension: rollout() that also records J_traj [batch][steps][r][k] = d u_t / d theta_t of every step (and, optionally, the
         // refinement residuals res_traj [batch][steps][r]) -- what paramJacobian returns right after step t's solve, bit for bit, still
         // in one launch per shard.  rolloutGradient then gives the gradient of L = sum_t gu_t' u_t + sum_t gtheta_t' theta_t over that

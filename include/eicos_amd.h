@@ -494,6 +494,39 @@ int eicos_batch_param_jacobian_device(eicos_batch *hd, const int *idx, int count
 int eicos_batch_param_gradient(eicos_batch *hd, const int *idx, int count, int nrhs, const double *g, double *grad_theta, double *res);
 int eicos_batch_param_gradient_device(eicos_batch *hd, const int *idx, int count, int nrhs, const double *dg, double *dgrad_theta,
                                       double *dres);
+/* The cone scaling of the adjoint's K, per handle.  EICOS_ADJOINT_NT (the default): W^2 = the NT scaling of the returned (s, z), as
+ * defined above.  On an LP row that is s_i / z_i, which needs no centrality.  On an ACTIVE, strictly complementary second-order cone --
+ * s = (l1 c1 + l2 c2) / 2, z = (w1 c1 + w2 c2) / 2 in a common Jordan frame c1,2 = (1, +-u), l1 and w2 of order one, l2 and w1 close to
+ * zero -- W^2 has the eigenvalues l1 / w1 and l2 / w2 on the frame and eta^2 = (l1 / w2) sqrt(l2 w2 / (l1 w1)) on the d - 2 directions
+ * perpendicular to u, along which the optimum slides on the cone's surface.  The tangent of the complementarity manifold there is
+ * ds = -(l1 / w2) dz, so eta^2 is right only up to the ratio of the two complementary products: whatever centrality error the last
+ * step of the solve left, a factor of order one.  Where the cone's curvature fixes the optimum, the NT-mode gradients are wrong by
+ * that factor.
+ * EICOS_ADJOINT_CENTRED: the same K with W^2 = the NT scaling of the RE-CENTRED pair, formed per second-order cone (rows o .. o+d-1,
+ * head o, tail 1:) from the un-equilibrated result rows; LP rows are untouched:
+ *
+ *     v = s[1:] / s[0] - z[1:] / z[0];  nv = |v|_2;  nv == 0 (which covers d == 1): the cone stays as it is
+ *     u = v / nv
+ *     l1 = s[0] + s[1:]'u;  l2 = s[0] - s[1:]'u;  w1 = z[0] + z[1:]'u;  w2 = z[0] - z[1:]'u
+ *     min(l1, l2, w1, w2) <= 0: the cone stays as it is
+ *     mu = sqrt(l1 w1 l2 w2)
+ *     l1 >= w1: w1 = mu / l1, else l1 = mu / w1;      l2 >= w2: w2 = mu / l2, else l2 = mu / w2
+ *     s = ((l1 + l2) / 2, (l1 - l2) / 2 u);   z = ((w1 + w2) / 2, (w1 - w2) / 2 u)
+ *
+ * -- the large eigenvalue of each complementary pair is kept, the small one replaced so that l1 w1 = l2 w2.  Everything else of the
+ * definition is unchanged (the factor path, the refinement against the unregularised system, the NaN rules, the gradient and contraction
+ * formulas), and a cone the rule leaves alone behaves exactly as under EICOS_ADJOINT_NT.  Use it on any pattern with cones; on a pattern
+ * without cones both modes give the same bits.
+ * eicos_batch_set_adjoint_scaling: the mode holds from the next adjoint launch, for every path: eicos_batch_adjoint, _adjoint_data,
+ * _output_jacobian, _param_jacobian, _param_gradient and their device forms, and the adjoints of eicos_batch_rollout_jacobian (fused or
+ * not) -- through its J and its recorded rows, the three rollout gradients.  A J trajectory already on the handle stays as it was
+ * recorded; setting the mode is no map install.  eicos_debug_kkt after an adjoint call then shows the CENTRED scaling block.  A solve
+ * never sees the mode.  An unknown mode is EICOS_E_INVALID with a message naming the value, and nothing changes.
+ * eicos_batch_adjoint_scaling: the handle's mode (negative: an error code). */
+#define EICOS_ADJOINT_NT 0
+#define EICOS_ADJOINT_CENTRED 1
+int eicos_batch_set_adjoint_scaling(eicos_batch *hd, int mode);
+int eicos_batch_adjoint_scaling(eicos_batch *hd);
 /* ---- rollout sensitivities: the Jacobian of every step of a rollout, and the gradient of a closed-loop cost (no reference counterpart).
  * eicos_batch_rollout_jacobian: eicos_batch_rollout -- the first eight arguments with exactly its meaning, arrays in pageable, pinned or
  * device memory -- that also records J_traj [batch][steps][r][k] (required) and res_traj [batch][steps][r] (optional): J_traj[i][t] and
@@ -985,6 +1018,9 @@ int eicos_multi_adjoint_data(eicos_multi *mh, const int *idx, int count, int nrh
                              double *grad_b, double *grad_G, double *grad_A, double *res);
 int eicos_multi_param_jacobian(eicos_multi *mh, const int *idx, int count, double *J, double *res);
 int eicos_multi_param_gradient(eicos_multi *mh, const int *idx, int count, int nrhs, const double *g, double *grad_theta, double *res);
+/* the cone scaling of the adjoint (eicos_batch_set_adjoint_scaling on every shard; a refused mode changes no shard); get: the first shard's */
+int eicos_multi_set_adjoint_scaling(eicos_multi *mh, int mode);
+int eicos_multi_adjoint_scaling(eicos_multi *mh);
 int eicos_multi_update_param_solve_subset(eicos_multi *mh, const int *idx, int count, const double *theta, double *u_out, double *x_out,
                                           int *exitcodes);
 /* results gathered into the caller's host arrays in global instance order (the "gather" of north_star: per-device copies) */
