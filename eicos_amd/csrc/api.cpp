@@ -35,6 +35,7 @@
 #include "exit_class.hpp"
 #include "resources.hpp"
 #include "call_arrays.hpp"
+#include "rollout_layout.hpp"
 #include "last_error.hpp"
 #include "plan_step.hpp"
 
@@ -150,9 +151,13 @@ struct eicos_batch {
     // per-instance plant values (eicos_batch_set_plant_values): one allocation per group, [batch][k] and [batch][plant.nnz], made and filled
     // with the shared values by the group's first call; plant.ibase / plant.ival point at them (NULL: the group is the shared one)
     DevBuf d_plant_f0, d_plant_val;
-    // rollout (eicos_batch_rollout): one device allocation: [RolloutDev (MAP_HEADER bytes) | theta, u, w trajectories | two
-    // theta rows of the batch (the path that is not fused) | codes, iters]; roll = the host copy of the record of the most recent call
-    RolloutDev roll{}; DevBuf d_roll; int rollout_launches = 0;
+    // rollout (eicos_batch_rollout): d_roll, d_rollJ and d_rollW as rollout_layout.hpp lays them out -- the trajectories of the most
+    // recent rollout; with eicos_batch_rollout_jacobian its Jacobians, kept for the backward sweeps; the rows of a recording rollout
+    // (eicos_batch_set_rollout_recording), made by the first recording rollout and freed, with d_rollD, when recording is switched off.
+    // All three grow on demand.  roll = the host copy of the record of the most recent call; held = the trajectory the handle holds
+    // for the calls that read it back; map_gen counts the installs of the parameter, matrix, output, plant and fallback maps.
+    RolloutDev roll{}; DevBuf d_roll, d_rollJ, d_rollW; int rollout_launches = 0; bool roll_recording = false;
+    HeldTrajectory<PlantMapDev> held; unsigned long map_gen = 0;
     // matrix map (eicos_batch_set_matrix_map): one device allocation [MatrixMapDev (MAP_HEADER bytes) | base, val | rowptr, col], mat.k = 0
     // while none is installed; d_mstage = the device staging buffer the range path expands [Gpr | Apr | c | h | b] of a chunk of instances
     // into (param_range), up to MSTAGE_CAP_MB
@@ -185,20 +190,11 @@ struct eicos_batch {
     // allocation, made by the first call and grown on demand: the record of the launch (AdjointDev, MAP_HEADER bytes), its index list and
     // the staging of the host forms' arrays, as adjoint_run declares them (call_arrays.hpp)
     DevBuf d_adj; AdjointDev adj{}; // (adj: the host copy of the most recent launch's record, the source of its copy on the handle's stream)
-    // The rollout that records its Jacobians (eicos_batch_rollout_jacobian), kept for eicos_batch_rollout_gradient: one device allocation,
-    // grown on demand: [AdjointDev of the fused launch (MAP_HEADER bytes) | J trajectory [batch][steps][r][k] | res trajectory
-    // [batch][steps][r] | one step's J and res rows of the batch (the path that is not fused)]; d_rollG = the staging of the gradient
-    // call's host form, as rollout_gradient declares its arrays (call_arrays.hpp).  rollJ_steps = 0: no trajectory on the handle; rollJ_plant, rollJ_k / _r = the plant map and counts it was
-    // recorded under; map_gen counts the installs of the parameter, matrix, output, plant and fallback maps, rollJ_gen = its value at that rollout.
-    DevBuf d_rollJ, d_rollG; int rollJ_steps = 0, rollJ_k = 0, rollJ_r = 0; PlantMapDev rollJ_plant{}; unsigned long map_gen = 0, rollJ_gen = 0;
-    // A recording rollout (eicos_batch_set_rollout_recording; launch.hpp: AdjointDev::x_rec): d_rollW = the record and, on the path that
-    // is not fused, one step's rows behind it, each as lay_records lays them out,
-    // made by the first recording rollout and grown on demand, freed (with d_rollD) when recording is switched off -- never touched while it is off.  rollW_on: the trajectory the
-    // handle holds (rollJ_steps) was recorded with its rows.  d_rollD = the staging of eicos_batch_rollout_data_gradient, as
-    // rollout_data_gradient declares its arrays (call_arrays.hpp): the workgroups' contracted rows and, in the host form, its inputs and outputs.
-    DevBuf d_rollW, d_rollD; bool roll_recording = false, rollW_on = false;
+    // the staging of eicos_batch_rollout_gradient and of eicos_batch_rollout_data_gradient, as rollout_gradient and rollout_data_gradient
+    // declare their arrays (call_arrays.hpp): the latter also the workgroups' contracted rows
+    DevBuf d_rollG, d_rollD;
     int param_nnz[3] = {0, 0, 0}, out_nnz = 0; // stored entries of the installed parameter map's groups and of the output map (the widths of their slope gradients)
-    int adjoint_scaling = EICOS_ADJOINT_NT; // eicos_batch_set_adjoint_scaling: what adjoint_run and rollout_run put into AdjointDev::centred
+    int adjoint_scaling = EICOS_ADJOINT_NT; // eicos_batch_set_adjoint_scaling: what adjoint_record puts into AdjointDev::centred
     hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr; bool adjoint_timed = false; // HIP events around the most recent adjoint launch (eicos_batch_last_adjoint_ms)
 
     // The events and the stream the handle made; the buffers free themselves after this body.  eicos_batch_destroy has set the device and
@@ -384,7 +380,7 @@ static int allocate(ProblemPattern &&P, Plan &pl, const Shape &sh, int batch, in
 static constexpr size_t MAP_HEADER = 128; // bytes kept for the descriptor in front of a map's arrays (keeps the doubles aligned)
 static_assert(sizeof(ParamMapDev) <= MAP_HEADER && sizeof(OutMapDev) <= MAP_HEADER && sizeof(PlantMapDev) <= MAP_HEADER &&
               sizeof(RolloutDev) <= MAP_HEADER && sizeof(MatrixMapDev) <= MAP_HEADER && sizeof(ShiftMapDev) <= MAP_HEADER &&
-              sizeof(FallbackDev) <= MAP_HEADER,
+              sizeof(FallbackDev) <= MAP_HEADER && ROLLOUT_HEADER == MAP_HEADER,
               "map descriptor larger than its header");
 
 // The map in `slot` (its device allocation) and `cur` (the handle's copy of its descriptor) goes away; M != NULL: the n validated groups
@@ -395,7 +391,7 @@ static int install_map(eicos_batch *h, DevBuf &slot, Desc &cur, const char *name
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream)); // (a launch in flight may still read the map that goes away)
     slot.reset(); // (first, so that the old and the new map never coexist; a failure below leaves the handle without this map)
-    if (&slot != &h->d_shift) h->map_gen++; // (eicos_batch_rollout_gradient: a recorded rollout belongs to the maps it ran under; the shift map is not one of them)
+    if (&slot != &h->d_shift) h->map_gen++; // (HeldTrajectory::fault: a recorded rollout belongs to the maps it ran under; the shift map is not one of them)
     cur = Desc{};
     if (!M) return EICOS_OK;
     const AffineLayout lay = affine_layout(g, n, MAP_HEADER, gap);
@@ -1563,6 +1559,13 @@ static int grow_staging(eicos_batch *h, size_t doubles, int nchunks) {
     if (!h->d_err) { HIP_TRY_AS("hipMalloc", h->d_err.alloc(sizeof(int))); HIP_TRY(hipMemset(h->d_err.p, 0, sizeof(int))); }
     return EICOS_OK;
 }
+// The maps of a fused parametric step or rollout, as device copies of the handle's descriptors.  matrix: the step may carry the matrix
+// map (where one is installed).  fb: the caller's own condition for the fallback record -- it travels only where the kernel writes u.
+static void step_maps(const eicos_batch *h, UpdArgs &step, bool matrix, bool fb) {
+    step.pmap = h->d_param.as<const ParamMapDev>(); step.omap = h->d_out.as<const OutMapDev>();
+    if (matrix && h->mat.k) step.mmap = h->d_mat.as<const MatrixMapDev>();
+    if (fb) step.fb = h->d_fb.as<const FallbackDev>();
+}
 // x_out [batch][n], u_out [batch][r] (NULL: not asked for) behind a finished solve, by kind of memory unless the kernel wrote it; complete on return
 // fb_theta (outputs_to): the step's theta rows when a fallback map applies to u rows the kernel did not write
 static int deliver_results(eicos_batch *h, double *x_out, MemKind x_kind, bool x_written, double *u_out, MemKind u_kind, bool u_written,
@@ -1664,9 +1667,7 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
     step.G = ptr[0]; step.A = ptr[1]; (param ? step.theta : step.c) = ptr[2]; step.h = ptr[3]; step.b = ptr[4];
     step.x = x_written ? x_out : nullptr; step.u = u_written ? u_out : nullptr;
     step.flags = any_staged ? h->stage_flags.as<unsigned>() : nullptr; step.chunk = chunk; step.seq = h->stage_seq; step.err = h->d_err.as<int>();
-    step.pmap = h->d_param.as<const ParamMapDev>(); step.omap = h->d_out.as<const OutMapDev>();
-    if (param && h->mat.k) step.mmap = h->d_mat.as<const MatrixMapDev>();
-    if (fb_on && u_written) step.fb = h->d_fb.as<const FallbackDev>();
+    step_maps(h, step, param, fb_on && u_written);
     rc = enqueue_solve(h, &step);
     if (rc != EICOS_OK) return rc; // (nothing was launched: no workgroup waits for a flag)
     if (any_staged) { // the kernel is running: copy chunk by chunk and release each chunk's flag behind its rows
@@ -1795,13 +1796,6 @@ int eicos_batch_outputs_indexed_device(eicos_batch *h, const int *idx, int count
 // One launch of the handle's adjoint kernel (launch.hpp: AdjointLaunch) behind everything on the handle's stream, under the handle's settings
 // and dynamic regularisation.  Every check stands in front of the first enqueue: a refused call changes nothing.
 namespace {
-// Recorded rows of a recording rollout -- one step's, or the whole record (eicos_batch::d_rollW) --: six arrays one behind the other,
-// [rows][width[q]] each
-struct RecordRows {
-    double *Wc, *Wh, *Wb, *x, *y, *z; size_t width[6];
-    double *part(int q) const { double *const a[6] = {Wc, Wh, Wb, x, y, z}; return a[q]; }
-    void into(AdjointDev &rec) const { rec.grad_c = Wc; rec.grad_h = Wh; rec.grad_b = Wb; rec.x_rec = x; rec.y_rec = y; rec.z_rec = z; }
-};
 struct AdjointCall {
     const char *who;
     const int *idx; int count, nrhs; // nrhs: right-hand sides per instance (the Jacobian form: r)
@@ -1813,13 +1807,6 @@ struct AdjointCall {
     const char *out_name = "J"; // what the C header calls J
 };
 static_assert(sizeof(AdjointDev) <= MAP_HEADER, "the adjoint record larger than its header");
-}
-// The one layout of recorded rows: `rows` rows from base, widths per row [Wc r n | Wh r m | Wb r p | x n | y p | z m]; returns the end
-static double *lay_records(RecordRows &R, double *base, size_t rows, size_t r, size_t n, size_t m, size_t p) {
-    const size_t width[6] = {r * n, r * m, r * p, n, p, m};
-    double **const part[6] = {&R.Wc, &R.Wh, &R.Wb, &R.x, &R.y, &R.z};
-    for (int q = 0; q < 6; q++) { R.width[q] = width[q]; *part[q] = base; base += rows * width[q]; }
-    return base;
 }
 // ---- what the sensitivity and rollout calls share: their arrays (call_arrays.hpp), the timing bracket, the held trajectory ----
 static int kind_check(const Arrays &a, const char *who, bool paired = true) {
@@ -1854,17 +1841,34 @@ static int timed_adjoint_launch(eicos_batch *h, const char *what, const std::fun
 // The trajectory a backward sweep or a read of the record needs on the handle.  current: it must belong to the maps now installed.
 static int held_trajectory_fault(const eicos_batch *h, const char *who, bool need_records, bool current = true) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
-    const std::string w(who);
-    if (h->rollJ_steps == 0) return fail(EICOS_E_INVALID, w + ": the handle holds no Jacobian trajectory (eicos_batch_rollout_jacobian records one)");
-    if (current && h->rollJ_gen != h->map_gen) return fail(EICOS_E_INVALID, w + ": a parameter, matrix, output, plant or fallback map was installed after the rollout whose Jacobians the handle holds (setting or clearing per-instance plant values counts as one): run eicos_batch_rollout_jacobian again");
-    if (need_records && !h->rollW_on) return fail(EICOS_E_INVALID, w + ": the handle holds no recorded rows: recording was off for the rollout it holds (eicos_batch_set_rollout_recording, then eicos_batch_rollout_jacobian)");
-    return EICOS_OK;
+    const std::string msg = h->held.fault(who, h->map_gen, need_records, current);
+    return msg.empty() ? EICOS_OK : fail(EICOS_E_INVALID, msg);
 }
 static int adjoint_list_fault(const eicos_batch *h, const int *idx, int count, const char *who) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     if (idx) return take_index_list(h, idx, count, who);
     if (count < 0 || count > h->batch) return fail(EICOS_E_INVALID, std::string(who) + ": count must lie in [0, batch] when idx is NULL (instances 0 .. count-1)");
     return EICOS_OK;
+}
+// What every adjoint record carries, whatever its form: the handle's cone scaling
+static AdjointDev adjoint_record(const eicos_batch *h) {
+    AdjointDev rec{};
+    rec.centred = h->adjoint_scaling == EICOS_ADJOINT_CENTRED;
+    return rec;
+}
+// The record of the contracted form (launch.hpp: AdjointDev::J), filled in ONE place for adjoint_run and the fused rollout: the gradients
+// contracted with the parameter map and -- matrix -- with the matrix map, where one is installed, k columns each; right-hand sides the
+// rows of the output map, or -- nrhs > 0 -- nrhs rows of the caller's g (which the caller sets); rows != NULL: a recording rollout's rows.
+static AdjointDev contracted_record(const eicos_batch *h, bool matrix, int nrhs, int k, double *J, double *res, const RecordRows *rows) {
+    AdjointDev rec = adjoint_record(h);
+    rec.pmap = h->param.k ? h->d_param.as<const ParamMapDev>() : nullptr;
+    rec.mmap = matrix && h->mat.k ? h->d_mat.as<const MatrixMapDev>() : nullptr;
+    rec.k = k;
+    if (nrhs > 0) rec.nrhs = nrhs;
+    else rec.omap = h->d_out.as<const OutMapDev>();
+    rec.J = J; rec.res = res;
+    if (rows) { rec.grad_c = rows->Wc; rec.grad_h = rows->Wh; rec.grad_b = rows->Wb; rec.x_rec = rows->x; rec.y_rec = rows->y; rec.z_rec = rows->z; }
+    return rec;
 }
 static int adjoint_run(eicos_batch *h, const AdjointCall &c) {
     if (c.count == 0) return EICOS_OK;
@@ -1888,27 +1892,18 @@ static int adjoint_run(eicos_batch *h, const AdjointCall &c) {
         if ((rc = upload_ids(h, c.idx, c.count, d_ids)) != EICOS_OK) return rc;
     }
     AdjointDev &rec = h->adj;
-    rec = AdjointDev{};
-    rec.centred = h->adjoint_scaling == EICOS_ADJOINT_CENTRED;
-    rec.g = a.dbl(i_g); rec.res = a.dbl(i_res);
-    if (c.jac) {
-        rec.pmap = h->param.k ? h->d_param.as<const ParamMapDev>() : nullptr;
-        rec.mmap = c.mmap && h->mat.k ? h->d_mat.as<const MatrixMapDev>() : nullptr;
-        rec.k = (int)k;
-        if (c.grows) rec.nrhs = c.nrhs;
-        else rec.omap = h->d_out.as<const OutMapDev>();
-        rec.J = a.dbl(i_J);
-        if (c.rec) c.rec->into(rec);
-    } else {
-        rec.nrhs = c.nrhs;
+    if (c.jac) rec = contracted_record(h, c.mmap, c.grows ? c.nrhs : 0, (int)k, a.dbl(i_J), a.dbl(i_res), c.rec);
+    else {
+        rec = adjoint_record(h);
+        rec.nrhs = c.nrhs; rec.res = a.dbl(i_res);
         rec.grad_c = a.dbl(i_c); rec.grad_h = a.dbl(i_h); rec.grad_b = a.dbl(i_b); rec.grad_G = a.dbl(i_G); rec.grad_A = a.dbl(i_A);
     }
+    rec.g = a.dbl(i_g);
     HIP_TRY(hipMemcpyAsync(a.at(i_rec), &rec, sizeof rec, hipMemcpyHostToDevice, h->stream));
-    AdjointLaunch L{};
-    L.ps = h->pslot; L.inst = h->inst(); L.work = h->work(); L.count = c.count; L.list = d_ids; L.batch = h->batch;
-    L.grid = h->grid; L.threads = h->threads; L.nlds = h->nlds; L.idx16 = D.idx16;
-    L.dyn_delta = h->dyn_delta; L.dyn_eps = h->dyn_eps; L.cfg = h->cfg; L.dyn_lds = h->dyn_lds;
-    L.adj = static_cast<const AdjointDev *>(a.at(i_rec));
+    // (the slabs, the launch shape and the settings of the handle's solves: solve_launch)
+    const SolveLaunch S = solve_launch(h, -1);
+    const AdjointLaunch L{S.ps, S.inst, S.work, c.count, d_ids, S.batch, S.grid, S.threads, S.nlds, S.idx16, S.dyn_delta, S.dyn_eps, S.cfg, S.dyn_lds,
+                          static_cast<const AdjointDev *>(a.at(i_rec))};
     rc = timed_adjoint_launch(h, "adjoint launch", [&] { return solve_build(h->threads, h->ldsres, h->w2, h->ubl).adjoint(L, h->stream); });
     return rc != EICOS_OK ? rc : unstage(h, a);
 }
@@ -2020,10 +2015,8 @@ int eicos_batch_update_param_solve_subset(eicos_batch *h, const int *idx, int co
         UpdArgs step;
         step.on = UPD_PARAM; step.rows_at = subset_rows_at(h); step.theta = in.src[2];
         step.x = x_written ? x_out : nullptr; step.u = u_written ? u_out : nullptr;
-        step.pmap = h->d_param.as<const ParamMapDev>(); step.omap = h->d_out.as<const OutMapDev>();
-        if (h->mat.k) step.mmap = h->d_mat.as<const MatrixMapDev>();
-        if (fb_on && u_written) step.fb = h->d_fb.as<const FallbackDev>();
-        else if (fb_on) fb_theta = in.src[2]; // (memory the GPU addresses: the launch reads it too)
+        step_maps(h, step, true, fb_on && u_written);
+        if (fb_on && !u_written) fb_theta = in.src[2]; // (memory the GPU addresses: the launch reads it too)
         rc = enqueue_solve(h, &step, count);
     }
     if (rc == EICOS_OK) rc = eicos_batch_sync(h);
@@ -2250,8 +2243,9 @@ int eicos_batch_last_rollout_launches(eicos_batch *h) { return h ? h->rollout_la
 // trajectories (eicos_batch::d_rollJ) -- fused: k_roll_sens in the place of k_solve, still one launch; not fused: one adjoint launch in
 // its contracted device form (what eicos_batch_param_jacobian_device enqueues) between the step's output and plant kernels, its rows
 // moved into the trajectories on the stream.  No host synchronisation between the steps on either path.
-static int rollout_run(eicos_batch *h, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
-                       int *exitcodes, int *iters, bool sens, double *J_traj, double *res_traj) {
+// In pieces: the checks, the layout and the reserves (rollout_layout.hpp), rollout_fused or rollout_stepwise, the copies out.
+// every check of a rollout that needs no layout, in front of the first allocation
+static int rollout_checks(const eicos_batch *h, int steps, const double *theta0, const double *u_traj, bool sens, const double *J_traj) {
     if (!h) return fail(EICOS_E_INVALID, "NULL handle");
     if (steps < 1) return fail(EICOS_E_INVALID, "rollout: steps must be at least 1");
     if (h->param.k == 0) return fail(EICOS_E_INVALID, "no parameter map (eicos_batch_set_param_map installs one)");
@@ -2266,100 +2260,103 @@ static int rollout_run(eicos_batch *h, int steps, const double *theta0, const do
     if (!theta0) return fail(EICOS_E_INVALID, "rollout: theta0 is NULL");
     if (!u_traj) return fail(EICOS_E_INVALID, "rollout: u_traj is NULL");
     if (sens && !J_traj) return fail(EICOS_E_INVALID, "rollout_jacobian: J_traj is NULL");
-    if (sens && (size_t)h->batch * (size_t)steps > (size_t)INT_MAX) return fail(EICOS_E_INVALID, "rollout_jacobian: batch * steps must fit an int");
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->batch, T = (size_t)steps;
-    const size_t n_J = B * T * r * k, n_res = B * T * r, n_J1 = B * r * k, n_res1 = B * r;
-    double *d_J = nullptr, *d_res = nullptr, *d_J1 = nullptr, *d_res1 = nullptr;
-    if (sens) {
-        h->rollJ_steps = 0; // (until this rollout has been enqueued whole: a failure below leaves no trajectory)
-        HIP_TRY_AS("hipMalloc", h->d_rollJ.reserve(MAP_HEADER + (n_J + n_res + n_J1 + n_res1) * sizeof(double), h->stream));
-        d_J = reinterpret_cast<double *>(h->d_rollJ.as<char>() + MAP_HEADER); d_res = d_J + n_J; d_J1 = d_res + n_res; d_res1 = d_J1 + n_J1;
+    return EICOS_OK;
+}
+// the three buffers grown to the layout's totals, and every pointer of the call out of the layout
+static int rollout_reserve(eicos_batch *h, const RolloutShape &s, const RolloutLayout &L, RolloutArrays &a) {
+    if (s.sens) {
+        h->held.invalidate();
+        HIP_TRY_AS("hipMalloc", h->d_rollJ.reserve(L.rollJ_bytes, h->stream));
     }
-    const bool fused = fused_rollout_fits(fit_shape(h), k, r, h->mat.k != 0) && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
-    // a recording rollout: the whole record and, on the path that is not fused, one step's rows behind it (launch.hpp: AdjointDev::x_rec)
-    const bool recording = sens && h->roll_recording;
-    RecordRows W{}, W1{};
-    const size_t wn = (size_t)h->dp.n, wm = (size_t)h->dp.m, wp = (size_t)h->dp.p;
-    if (recording) {
-        h->rollW_on = false;
-        const size_t bytes = (B * T + (fused ? 0 : B)) * ((size_t)r + 1) * (wn + wm + wp) * sizeof(double);
-        if (h->d_rollW.reserve(bytes, h->stream) != hipSuccess) {
+    if (s.recording) {
+        if (h->d_rollW.reserve(L.rollW_bytes, h->stream) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(EICOS_E_HIP, "rollout_jacobian: the record of a recording rollout (batch * steps * (r + 1) * (n + m + p) * 8, and one step more where the rollout is not fused: " + std::to_string(bytes) +
+            return fail(EICOS_E_HIP, "rollout_jacobian: the record of a recording rollout (batch * steps * (r + 1) * (n + m + p) * 8, and one step more where the rollout is not fused: " + std::to_string(L.rollW_bytes) +
                                          " bytes) could not be allocated: record fewer steps or a smaller batch, or switch recording off");
         }
-        double *const end = lay_records(W, h->d_rollW.as<double>(), B * T, r, wn, wm, wp);
-        if (!fused) lay_records(W1, end, B, r, wn, wm, wp);
     }
-    const size_t n_th = B * (T + 1) * k, n_u = B * T * r, n_w = w ? B * T * k : 0, n_cur = 2 * B * k, n_rec = B * T;
-    HIP_TRY_AS("hipMalloc", h->d_roll.reserve(MAP_HEADER + (n_th + n_u + n_w + n_cur) * sizeof(double) + 2 * n_rec * sizeof(int), h->stream));
-    double *d_th = reinterpret_cast<double *>(h->d_roll.as<char>() + MAP_HEADER), *d_uu = d_th + n_th, *d_w = d_uu + n_u, *d_cur = d_w + n_w;
-    int *d_codes = reinterpret_cast<int *>(d_cur + n_cur), *d_iters = d_codes + n_rec;
-    h->roll = RolloutDev{steps, h->plant, d_th, d_uu, w ? d_w : nullptr, d_codes, d_iters};
-    const size_t row_b = (size_t)k * sizeof(double);
-    HIP_TRY(hipMemcpyAsync(h->d_roll.p, &h->roll, sizeof(RolloutDev), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpy2DAsync(d_th, (T + 1) * row_b, theta0, row_b, row_b, B, hipMemcpyDefault, h->stream)); // row 0 of every trajectory
-    if (w) HIP_TRY(hipMemcpyAsync(d_w, w, n_w * sizeof(double), hipMemcpyDefault, h->stream));
-    int rc = EICOS_OK;
-    if (fused) {
-        rc = fused_step_begins(h, 5);
+    HIP_TRY_AS("hipMalloc", h->d_roll.reserve(L.roll_bytes, h->stream));
+    a = L.in(h->d_roll.p, h->d_rollJ.p, h->d_rollW.p);
+    return EICOS_OK;
+}
+// ONE solve launch whose workgroups run the steps of their instances; sens: k_roll_sens, with the contracted record in front of d_rollJ
+static int rollout_fused(eicos_batch *h, const RolloutShape &s, const RolloutArrays &a) {
+    const int rc = fused_step_begins(h, 5);
+    if (rc != EICOS_OK) return rc;
+    UpdArgs step;
+    step.on = UPD_ROLL; step.roll = static_cast<const RolloutDev *>(a.roll_rec);
+    step_maps(h, step, true, h->fb.mask != 0); // (the fallback record: every step's u row, and with sens its J and res rows: kernels.hip, rollout_record)
+    if (s.sens) {
+        const AdjointDev rec = contracted_record(h, true, 0, (int)s.k, a.J, a.res, s.recording ? &a.W : nullptr);
+        HIP_TRY(hipMemcpyAsync(a.adj_rec, &rec, sizeof rec, hipMemcpyHostToDevice, h->stream));
+    }
+    return enqueue_solve(h, &step, -1, static_cast<const AdjointDev *>(a.adj_rec));
+}
+// one step's rows [batch][width] into row t of the trajectory [batch][steps][width], on the handle's stream
+static int step_into_trajectory(eicos_batch *h, double *traj, const double *rows, size_t width, size_t t, size_t steps) {
+    const size_t wb = width * sizeof(double);
+    if (wb) HIP_TRY(hipMemcpy2DAsync(traj + t * width, steps * wb, rows, wb, wb, (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
+    return EICOS_OK;
+}
+// Per step four launches on the stream (five with sens), the step's theta rows in the two buffers of `cur` that take turns
+static int rollout_stepwise(eicos_batch *h, const RolloutShape &s, const RolloutArrays &a) {
+    const size_t row_b = s.k * sizeof(double);
+    HIP_TRY(hipMemcpy2DAsync(a.cur, row_b, a.theta, (s.T + 1) * row_b, row_b, s.B, hipMemcpyDeviceToDevice, h->stream));
+    for (size_t t = 0; t < s.T; t++) {
+        const double *cur = a.cur + (t & 1) * s.B * s.k;
+        double *next = a.cur + ((t + 1) & 1) * s.B * s.k;
+        int rc = begin_update_timing(h);
+        if (rc == EICOS_OK) rc = param_range(h, 0, h->batch, cur, nullptr);
+        rc = end_update_timing(h, rc);
+        if (rc == EICOS_OK) rc = enqueue_solve(h, nullptr);
         if (rc != EICOS_OK) return rc;
-        UpdArgs step;
-        step.on = UPD_ROLL; step.roll = h->d_roll.as<const RolloutDev>();
-        step.pmap = h->d_param.as<const ParamMapDev>(); step.omap = h->d_out.as<const OutMapDev>();
-        if (h->mat.k) step.mmap = h->d_mat.as<const MatrixMapDev>();
-        if (h->fb.mask) step.fb = h->d_fb.as<const FallbackDev>(); // (every step's u row, and with sens its J and res rows: kernels.hip, rollout_record)
-        if (sens) { // the record of the launch's adjoints (launch.hpp: AdjointDev, the contracted form with the output map's rows), as adjoint_run fills it
-            AdjointDev rec{};
-            rec.centred = h->adjoint_scaling == EICOS_ADJOINT_CENTRED;
-            rec.pmap = h->d_param.as<const ParamMapDev>(); rec.mmap = h->mat.k ? h->d_mat.as<const MatrixMapDev>() : nullptr;
-            rec.omap = h->d_out.as<const OutMapDev>(); rec.k = k; rec.J = d_J; rec.res = d_res;
-            if (recording) W.into(rec);
-            HIP_TRY(hipMemcpyAsync(h->d_rollJ.p, &rec, sizeof rec, hipMemcpyHostToDevice, h->stream));
-        }
-        rc = enqueue_solve(h, &step, -1, sens ? h->d_rollJ.as<const AdjointDev>() : nullptr);
-        if (rc != EICOS_OK) return rc;
-    } else {
-        HIP_TRY(hipMemcpy2DAsync(d_cur, row_b, d_th, (T + 1) * row_b, row_b, B, hipMemcpyDeviceToDevice, h->stream));
-        for (int t = 0; t < steps; t++) {
-            const double *cur = d_cur + (size_t)(t & 1) * B * k;
-            double *next = d_cur + (size_t)((t + 1) & 1) * B * k;
-            rc = begin_update_timing(h);
-            if (rc == EICOS_OK) rc = param_range(h, 0, h->batch, cur, nullptr);
-            rc = end_update_timing(h, rc);
-            if (rc == EICOS_OK) rc = enqueue_solve(h, nullptr);
+        HIP_TRY(launch_outputs(h->pslot, h->inst(), 0, h->batch, h->out, h->d_u, h->stream));
+        if (h->fb.mask) HIP_TRY(launch_fallback(h->pslot, h->inst(), 0, h->batch, h->fb, cur, h->d_u, h->stream));
+        if (s.sens) {
+            rc = param_contracted(h, nullptr, h->batch, 0, nullptr, false, a.J1, "J", a.res1, true, "eicos_batch_rollout_jacobian", s.recording ? &a.W1 : nullptr);
             if (rc != EICOS_OK) return rc;
-            HIP_TRY(launch_outputs(h->pslot, h->inst(), 0, h->batch, h->out, h->d_u, h->stream));
-            if (h->fb.mask) HIP_TRY(launch_fallback(h->pslot, h->inst(), 0, h->batch, h->fb, cur, h->d_u, h->stream));
-            if (sens) {
-                rc = param_contracted(h, nullptr, h->batch, 0, nullptr, false, d_J1, "J", d_res1, true, "eicos_batch_rollout_jacobian", recording ? &W1 : nullptr);
-                if (rc != EICOS_OK) return rc;
-                if (h->fb.mask) HIP_TRY(launch_fallback_jacobian(h->pslot, h->inst(), 0, h->batch, h->fb, d_J1, d_res1, h->stream));
-                if (recording) { // the step's rows into the record, as J is moved
-                    if (h->fb.mask) HIP_TRY(launch_fallback_records(h->pslot, h->inst(), 0, h->batch, h->fb, W1.Wc, W1.Wh, W1.Wb, h->stream));
-                    for (int q = 0; q < 6; q++) {
-                        const size_t wb = W.width[q] * sizeof(double);
-                        if (wb) HIP_TRY(hipMemcpy2DAsync(W.part(q) + (size_t)t * W.width[q], T * wb, W1.part(q), wb, wb, B, hipMemcpyDeviceToDevice, h->stream));
-                    }
-                }
-                const size_t jb = (size_t)r * k * sizeof(double), rb = (size_t)r * sizeof(double);
-                HIP_TRY(hipMemcpy2DAsync(d_J + (size_t)t * r * k, T * jb, d_J1, jb, jb, B, hipMemcpyDeviceToDevice, h->stream));
-                HIP_TRY(hipMemcpy2DAsync(d_res + (size_t)t * r, T * rb, d_res1, rb, rb, B, hipMemcpyDeviceToDevice, h->stream));
+            if (h->fb.mask) HIP_TRY(launch_fallback_jacobian(h->pslot, h->inst(), 0, h->batch, h->fb, a.J1, a.res1, h->stream));
+            if (s.recording) { // the step's rows into the record, as J is moved
+                if (h->fb.mask) HIP_TRY(launch_fallback_records(h->pslot, h->inst(), 0, h->batch, h->fb, a.W1.Wc, a.W1.Wh, a.W1.Wb, h->stream));
+                for (int q = 0; q < 6; q++)
+                    if ((rc = step_into_trajectory(h, a.W.part(q), a.W1.part(q), a.W.width[q], t, s.T)) != EICOS_OK) return rc;
             }
-            HIP_TRY(launch_plant(h->pslot, h->inst(), 0, h->batch, h->roll, t, cur, h->d_u, next, h->stream));
+            if ((rc = step_into_trajectory(h, a.J, a.J1, s.r * s.k, t, s.T)) != EICOS_OK) return rc;
+            if ((rc = step_into_trajectory(h, a.res, a.res1, s.r, t, s.T)) != EICOS_OK) return rc;
         }
+        HIP_TRY(launch_plant(h->pslot, h->inst(), 0, h->batch, h->roll, (int)t, cur, h->d_u, next, h->stream));
     }
+    return EICOS_OK;
+}
+static int rollout_run(eicos_batch *h, int steps, const double *theta0, const double *w, double *u_traj, double *theta_traj,
+                       int *exitcodes, int *iters, bool sens, double *J_traj, double *res_traj) {
+    int rc = rollout_checks(h, steps, theta0, u_traj, sens, J_traj);
+    if (rc != EICOS_OK) return rc;
+    const int k = h->param.k, r = h->out.r;
+    const bool fused = fused_rollout_fits(fit_shape(h), k, r, h->mat.k != 0) && env_knob("EICOS_FUSED_UPDATE", 1, 0, 1);
+    const RolloutShape s{(size_t)h->batch, (size_t)steps, (size_t)k, (size_t)r, (size_t)h->dp.n, (size_t)h->dp.m, (size_t)h->dp.p,
+                         w != nullptr, sens, sens && h->roll_recording, fused};
+    const std::string fault = rollout_shape_fault(s);
+    if (!fault.empty()) return fail(EICOS_E_INVALID, fault);
+    HIP_TRY(hipSetDevice(h->device));
+    const RolloutLayout L(s);
+    RolloutArrays a;
+    if ((rc = rollout_reserve(h, s, L, a)) != EICOS_OK) return rc;
+    h->roll = RolloutDev{steps, h->plant, a.theta, a.u, a.w, a.codes, a.iters};
+    const size_t row_b = s.k * sizeof(double);
+    HIP_TRY(hipMemcpyAsync(a.roll_rec, &h->roll, sizeof(RolloutDev), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpy2DAsync(a.theta, (s.T + 1) * row_b, theta0, row_b, row_b, s.B, hipMemcpyDefault, h->stream)); // row 0 of every trajectory
+    if (w) HIP_TRY(hipMemcpyAsync(a.w, w, L.w.bytes, hipMemcpyDefault, h->stream));
+    if ((rc = fused ? rollout_fused(h, s, a) : rollout_stepwise(h, s, a)) != EICOS_OK) return rc;
     h->rollout_launches = fused ? 1 : steps;
-    HIP_TRY(hipMemcpyAsync(u_traj, d_uu, n_u * sizeof(double), hipMemcpyDefault, h->stream));
-    if (theta_traj) HIP_TRY(hipMemcpyAsync(theta_traj, d_th, n_th * sizeof(double), hipMemcpyDefault, h->stream));
-    if (exitcodes) HIP_TRY(hipMemcpyAsync(exitcodes, d_codes, n_rec * sizeof(int), hipMemcpyDefault, h->stream));
-    if (iters) HIP_TRY(hipMemcpyAsync(iters, d_iters, n_rec * sizeof(int), hipMemcpyDefault, h->stream));
+    HIP_TRY(hipMemcpyAsync(u_traj, a.u, L.u.bytes, hipMemcpyDefault, h->stream));
+    if (theta_traj) HIP_TRY(hipMemcpyAsync(theta_traj, a.theta, L.theta.bytes, hipMemcpyDefault, h->stream));
+    if (exitcodes) HIP_TRY(hipMemcpyAsync(exitcodes, a.codes, L.codes.bytes, hipMemcpyDefault, h->stream));
+    if (iters) HIP_TRY(hipMemcpyAsync(iters, a.iters, L.iters.bytes, hipMemcpyDefault, h->stream));
     if (sens) {
-        HIP_TRY(hipMemcpyAsync(J_traj, d_J, n_J * sizeof(double), hipMemcpyDefault, h->stream));
-        if (res_traj) HIP_TRY(hipMemcpyAsync(res_traj, d_res, n_res * sizeof(double), hipMemcpyDefault, h->stream));
-        h->rollJ_steps = steps; h->rollJ_k = k; h->rollJ_r = r; h->rollJ_plant = h->plant; h->rollJ_gen = h->map_gen;
-        h->rollW_on = recording;
+        HIP_TRY(hipMemcpyAsync(J_traj, a.J, L.J.bytes, hipMemcpyDefault, h->stream));
+        if (res_traj) HIP_TRY(hipMemcpyAsync(res_traj, a.res, L.res.bytes, hipMemcpyDefault, h->stream));
+        h->held.hold(s.B, steps, k, r, h->plant, h->map_gen, a.J, a.res, s.recording ? &a.W : nullptr);
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
     return EICOS_OK;
@@ -2389,7 +2386,8 @@ static int rollout_gradient(eicos_batch *h, const double *gu, const double *gthe
     if (pv && !pv->u_traj) return fail(EICOS_E_INVALID, w + ": u_traj is NULL");
     if (pv && !pv->theta_traj) return fail(EICOS_E_INVALID, w + ": theta_traj is NULL");
     if (pv && !grad_theta0 && !grad_w && !pv->grad_f0 && !pv->grad_val) return fail(EICOS_E_INVALID, w + ": grad_theta0, grad_w, grad_f0 and grad_val are all NULL");
-    const size_t B = (size_t)h->batch, T = (size_t)h->rollJ_steps, k = (size_t)h->rollJ_k, r = (size_t)h->rollJ_r, nnz = (size_t)h->rollJ_plant.nnz;
+    const auto &held = h->held;
+    const size_t B = (size_t)h->batch, T = (size_t)held.steps, k = (size_t)held.k, r = (size_t)held.r, nnz = (size_t)held.plant.nnz;
     const size_t n_gu = B * T * r, n_gt = B * (T + 1) * k, n_g0 = B * k, n_gw = B * T * k, n_gv = B * nnz;
     Arrays a(device); // (the plant-gradient form's four are NULL in the other)
     const int i_gu = a.in("gu", gu, n_gu), i_gt = a.in("gtheta", gtheta, n_gt), i_g0 = a.out("grad_theta0", grad_theta0, n_g0), i_gw = a.out("grad_w", grad_w, n_gw);
@@ -2402,14 +2400,13 @@ static int rollout_gradient(eicos_batch *h, const double *gu, const double *gthe
         return fail(EICOS_E_INVALID, w + (want_val ? ": 4 k + 3 r doubles must fit 48 KB of LDS" : ": 3 k + 2 r doubles must fit 48 KB of LDS"));
     HIP_TRY(hipSetDevice(h->device));
     if ((rc = stage(h, h->d_rollG, a)) != EICOS_OK) return rc;
-    const double *d_J = reinterpret_cast<const double *>(h->d_rollJ.as<char>() + MAP_HEADER);
     rc = timed_adjoint_launch(h, "launch_rollout_backprop", [&] {
-        return launch_rollout_backprop(h->rollJ_plant, (int)T, h->batch, d_J, a.dbl(i_gu), a.dbl(i_gt), a.dbl(i_g0), a.dbl(i_gw), h->stream,
+        return launch_rollout_backprop(held.plant, (int)T, h->batch, held.J(), a.dbl(i_gu), a.dbl(i_gt), a.dbl(i_g0), a.dbl(i_gw), h->stream,
                                        a.dbl(i_u), a.dbl(i_th), a.dbl(i_gf), a.dbl(i_gv));
     });
     return rc != EICOS_OK ? rc : unstage(h, a);
 }
-int eicos_batch_rollout_jacobian_steps(eicos_batch *h) { return h ? h->rollJ_steps : fail(EICOS_E_INVALID, "NULL handle"); }
+int eicos_batch_rollout_jacobian_steps(eicos_batch *h) { return h ? h->held.steps : fail(EICOS_E_INVALID, "NULL handle"); }
 int eicos_batch_rollout_gradient(eicos_batch *h, const double *gu, const double *gtheta, double *grad_theta0, double *grad_w) {
     return rollout_gradient(h, gu, gtheta, grad_theta0, grad_w, false, "eicos_batch_rollout_gradient");
 }
@@ -2446,23 +2443,17 @@ int eicos_batch_set_rollout_recording(eicos_batch *h, int on) {
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->d_rollW.reset(); h->d_rollD.reset();
-        h->rollW_on = false;
+        h->held.drop_rows();
     }
     return EICOS_OK;
 }
 int eicos_batch_rollout_recording(eicos_batch *h) { return h ? (h->roll_recording ? 1 : 0) : fail(EICOS_E_INVALID, "NULL handle"); }
-// the whole record of the trajectory the handle holds (rollW_on), as rollout_run laid it out
-static RecordRows record_rows(const eicos_batch *h) {
-    RecordRows R{};
-    lay_records(R, h->d_rollW.as<double>(), (size_t)h->batch * h->rollJ_steps, (size_t)h->rollJ_r, (size_t)h->dp.n, (size_t)h->dp.m, (size_t)h->dp.p);
-    return R;
-}
 int eicos_batch_rollout_records(eicos_batch *h, double *Wc, double *Wh, double *Wb, double *x_rec, double *y_rec, double *z_rec) {
     const char *who = "eicos_batch_rollout_records";
     int rc = held_trajectory_fault(h, who, true, false); // (the record is what the rollout left, whatever has been installed since)
     if (rc != EICOS_OK) return rc;
-    const RecordRows R = record_rows(h);
-    const size_t rows = (size_t)h->batch * h->rollJ_steps;
+    const RecordRows &R = h->held.records();
+    const size_t rows = h->held.rows;
     double *const dst[6] = {Wc, Wh, Wb, x_rec, y_rec, z_rec};
     const char *const name[6] = {"Wc", "Wh", "Wb", "x_rec", "y_rec", "z_rec"};
     Arrays a(false); // (for their kind alone: the rows come straight from the record)
@@ -2485,9 +2476,10 @@ static int rollout_data_gradient(eicos_batch *h, const double *gu, const double 
     if (!theta_traj) return fail(EICOS_E_INVALID, w + ": theta_traj is NULL");
     if (!out) return fail(EICOS_E_INVALID, w + ": out is NULL");
     const DevPat &P = h->dp;
-    const size_t B = (size_t)h->batch, T = (size_t)h->rollJ_steps, k = (size_t)h->rollJ_k, r = (size_t)h->rollJ_r;
+    const auto &held = h->held;
+    const size_t B = (size_t)h->batch, T = (size_t)held.steps, k = (size_t)held.k, r = (size_t)held.r;
     const size_t n = (size_t)P.n, m = (size_t)P.m, p = (size_t)P.p;
-    // (rollJ_gen == map_gen: the maps on the handle are the ones the rollout ran under)
+    // (held.gen == map_gen: the maps on the handle are the ones the rollout ran under)
     const size_t nnzC = (size_t)h->param_nnz[0], nnzH = (size_t)h->param_nnz[1], nnzB = (size_t)h->param_nnz[2], nnzU = (size_t)h->out_nnz;
     const char *slope[3] = {"grad_Cval", "grad_Hval", "grad_Bval"};
     double *const sl[3] = {out->grad_Cval, out->grad_Hval, out->grad_Bval};
@@ -2514,13 +2506,13 @@ static int rollout_data_gradient(eicos_batch *h, const double *gu, const double 
     DataGradDev D{};
     D.stage = a.dbl(i_stage);
     D.gu = a.dbl(i_gu); D.gth = a.dbl(i_gt); D.theta = a.dbl(i_th);
-    const RecordRows R = record_rows(h);
-    D.J = reinterpret_cast<const double *>(h->d_rollJ.as<char>() + MAP_HEADER);
+    const RecordRows &R = held.records();
+    D.J = held.J();
     D.Wc = R.Wc; D.Wh = R.Wh; D.Wb = R.Wb; D.x = R.x; D.y = R.y; D.z = R.z;
     D.pmap = h->param; D.omap = h->out;
     D.grad_c = a.dbl(i_o[0]); D.grad_h = a.dbl(i_o[1]); D.grad_b = a.dbl(i_o[2]); D.grad_G = a.dbl(i_o[3]); D.grad_A = a.dbl(i_o[4]);
     D.grad_val[0] = a.dbl(i_o[5]); D.grad_val[1] = a.dbl(i_o[6]); D.grad_val[2] = a.dbl(i_o[7]); D.grad_u0 = a.dbl(i_o[8]); D.grad_Uval = a.dbl(i_o[9]);
-    rc = timed_adjoint_launch(h, "launch_rollout_data_backprop", [&] { return launch_rollout_data_backprop(h->pslot, h->rollJ_plant, (int)T, h->batch, D, h->stream); });
+    rc = timed_adjoint_launch(h, "launch_rollout_data_backprop", [&] { return launch_rollout_data_backprop(h->pslot, held.plant, (int)T, h->batch, D, h->stream); });
     return rc != EICOS_OK ? rc : unstage(h, a);
 }
 int eicos_batch_rollout_data_gradient(eicos_batch *h, const double *gu, const double *gtheta, const double *theta_traj, const eicos_data_gradient *out) {

@@ -399,6 +399,18 @@ def test_records_without_the_fused_path_give_the_same_bits(env, monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("env,launches", [({}, 1), ({"EICOS_FUSED_UPDATE": "0"}, 2)])
+def test_records_with_parts_of_no_width_give_the_same_bits_on_both_paths(env, launches, monkeypatch):
+    """feas, the smallest fixture without equality rows (p = 0): the record's parts Wb and y have no width, so each starts where the
+    part behind it starts.  B = 3, T = 2, k = 3, r = 2; the fused path and the one that is not, against the same host twin."""
+    for k_, v in env.items():
+        monkeypatch.setenv(k_, v)
+    c = _record_case("feas", 3, 3, 2, 2, launches=launches)
+    assert c["pat"].p == 0 and c["recs"][2].shape[-1] == 0 and c["recs"][4].shape[-1] == 0 and c["recs"][0].size > 0
+    c["g"].close()
+
+
+@pytest.mark.gpu
 def test_data_gradient_is_bit_identical_to_the_restatement():
     c = _record_case("MPC02", 4, 5, 4, 3, launches=1, twin=False)
     g, got = c["g"], c["got"]
