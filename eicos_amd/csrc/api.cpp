@@ -4,8 +4,6 @@
 #include "../../include/eicos_amd.h"
 
 #include <hip/hip_runtime_api.h>
-#include <sched.h>
-#include <emmintrin.h>
 
 #include <algorithm>
 #include <cmath>
@@ -14,13 +12,11 @@
 #include <climits>
 #include <cstring>
 #include <atomic>
-#include <condition_variable>
 #include <functional>
 #include <map>
 #include <mutex>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "device_types.hpp"
@@ -38,6 +34,8 @@
 #include "rollout_layout.hpp"
 #include "last_error.hpp"
 #include "plan_step.hpp"
+#include "host_copy.hpp"
+#include "chunk_plan.hpp"
 
 using namespace eicos;
 
@@ -657,98 +655,8 @@ static int end_update_timing(eicos_batch *h, int rc) {
 }
 
 // ---- host memory helpers -------------------------------------------------------------------------------------------------
-// A few persistent host threads that split large memcpy calls between pageable and pinned memory (one core copies ~10 GB/s, a PCIe 5
-// x16 link moves ~50 GB/s: a single-threaded bounce copy would be the slowest stage of a host-pointer updateData).  Shared by every
-// handle of the process, started on first use, joined at exit.
+// (the host's own copies -- stream_copy, the copy pool -- are host_copy.hpp; what follows asks the runtime)
 namespace {
-// memcpy with non-temporal stores: the destination of a bounce copy is read next by the GPU over PCIe (or is the caller's result array), never
-// by this core -- regular stores would first read every destination line into the cache (read-for-ownership: a third more memory traffic)
-// and evict the caller's working set.  glibc switches to such stores only above a few MB per call; the pool's pieces are ~1.5 MB.
-static void stream_copy(void *dst, const void *src, size_t bytes) {
-    static const bool nt = env_knob("EICOS_COPY_NT", 1, 0, 1) != 0;
-    char *d = (char *)dst; const char *s = (const char *)src;
-    if (!nt || bytes < 4096) { std::memcpy(d, s, bytes); return; }
-    const size_t head = std::min(bytes, (size_t)((16 - ((uintptr_t)d & 15)) & 15));
-    std::memcpy(d, s, head); d += head; s += head; bytes -= head;
-    const size_t blocks = bytes / 64;
-    for (size_t i = 0; i < blocks; i++, d += 64, s += 64) {
-        const __m128i a = _mm_loadu_si128((const __m128i *)s), b = _mm_loadu_si128((const __m128i *)(s + 16));
-        const __m128i c = _mm_loadu_si128((const __m128i *)(s + 32)), e = _mm_loadu_si128((const __m128i *)(s + 48));
-        _mm_stream_si128((__m128i *)d, a); _mm_stream_si128((__m128i *)(d + 16), b);
-        _mm_stream_si128((__m128i *)(d + 32), c); _mm_stream_si128((__m128i *)(d + 48), e);
-    }
-    _mm_sfence();
-    std::memcpy(d, s, bytes - blocks * 64);
-}
-class CopyPool {
-  public:
-    static CopyPool &get() { static CopyPool p; return p; }
-    // dst[0, bytes) = src[0, bytes), cut into pieces of >= 1 MB over the pool's threads and the caller
-    void copy(void *dst, const void *src, size_t bytes) {
-        const size_t piece = 1u << 20;
-        const int parts = (int)std::min<size_t>((size_t)nthreads_ + 1, (bytes + piece - 1) / piece);
-        if (parts <= 1) { stream_copy(dst, src, bytes); return; }
-        const size_t per = ((bytes + parts - 1) / parts + 63) & ~(size_t)63;
-        // completion state on the caller's stack: the count is changed and the caller notified INSIDE the lock, so a helper's last access to
-        // these objects is its unlock, which the caller's wait cannot overtake
-        int left = parts - 1;
-        std::mutex done_mu; std::condition_variable done_cv;
-        for (int k = 1; k < parts; k++) {
-            const size_t a = std::min(bytes, (size_t)k * per), b = std::min(bytes, a + per);
-            push([=, &left, &done_mu, &done_cv] {
-                if (b > a) stream_copy((char *)dst + a, (const char *)src + a, b - a);
-                std::lock_guard<std::mutex> lk(done_mu);
-                if (--left == 0) done_cv.notify_one();
-            });
-        }
-        stream_copy(dst, src, std::min(bytes, per));
-        std::unique_lock<std::mutex> lk(done_mu);
-        done_cv.wait(lk, [&] { return left == 0; });
-    }
-  private:
-    // cores this process may really use: the affinity mask, capped by the cgroup CPU quota (a container's hardware_concurrency() is the host's)
-    static int usable_cores() {
-        int n = (int)std::max(1u, std::thread::hardware_concurrency());
-        cpu_set_t set;
-        if (sched_getaffinity(0, sizeof set, &set) == 0) n = std::max(1, CPU_COUNT(&set));
-        if (FILE *f = std::fopen("/sys/fs/cgroup/cpu.max", "r")) {
-            char q[32] = {0}; long period = 0;
-            if (std::fscanf(f, "%31s %ld", q, &period) == 2 && std::strcmp(q, "max") != 0 && period > 0) n = std::max(1, std::min(n, (int)(std::atol(q) / period)));
-            std::fclose(f);
-        }
-        return n;
-    }
-    CopyPool() {
-        // the bounce copy of a host-pointer updateData must keep up with the PCIe link (~50 GB/s; one core copies ~10 GB/s): up to ten
-        // helper threads, two cores left to the caller and the runtime; EICOS_COPY_THREADS overrides (experiments)
-        const int cores = usable_cores();
-        nthreads_ = env_knob("EICOS_COPY_THREADS", std::max(0, std::min(10, cores - 2)), 0, 64);
-        for (int i = 0; i < nthreads_; i++) th_.emplace_back([this] { run(); });
-    }
-    ~CopyPool() {
-        { std::lock_guard<std::mutex> lk(mu_); stop_ = true; }
-        cv_.notify_all();
-        for (auto &t : th_) t.join();
-    }
-    void push(std::function<void()> f) { { std::lock_guard<std::mutex> lk(mu_); q_.push_back(std::move(f)); } cv_.notify_one(); }
-    void run() {
-        for (;;) {
-            std::function<void()> f;
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return stop_ || !q_.empty(); });
-                if (q_.empty()) return;
-                f = std::move(q_.front()); q_.erase(q_.begin());
-            }
-            f();
-        }
-    }
-    int nthreads_ = 0; bool stop_ = false;
-    std::vector<std::thread> th_;
-    std::vector<std::function<void()>> q_;
-    std::mutex mu_; std::condition_variable cv_;
-};
-
 // What kind of memory the extent [p, p + bytes) is -- the one place that asks the runtime:
 //   MEM_DEVICE  : the first byte is device memory
 //   MEM_PINNED  : the WHOLE extent is host memory the GPU addresses directly (hipHostMalloc / hipHostRegister / eicos_host_alloc): kernels read
@@ -786,7 +694,6 @@ int ensure_pin(eicos_batch *h, size_t doubles) {
     for (PinSlot &s : h->pin) HIP_TRY_AS("hipHostMalloc", s.reserve(doubles * sizeof(double)));
     return EICOS_OK;
 }
-constexpr size_t PIN_CHUNK_BYTES = 16u << 20; // bounce buffer size aimed at (per buffer)
 } // namespace
 
 void *eicos_host_alloc(size_t bytes) {
@@ -841,6 +748,11 @@ struct UpdateInputs {
     bool detect = false;  // eicos_batch_update_device: arrays in the GPU's own memory, where reading row 0 once more per instance is an L2 hit (pinned host
                           // rows and another GPU's would cross the link twice) -- its launch may set the shared-values word
     bool holds_data(int k) const { return src[k] && w[k]; }
+    // the arrays of `rows` instances packed into a staging area (chunk_plan.hpp): every given array has a place, one of no width too
+    PackedChunk packed(size_t rows) const {
+        const bool given[5] = {src[0] != nullptr, src[1] != nullptr, src[2] != nullptr, src[3] != nullptr, src[4] != nullptr};
+        return pack_chunk(w, given, rows, ChunkPad::Gap8);
+    }
     bool any(MemKind m) const { for (int k = 0; k < 5; k++) if (holds_data(k) && kind[k] == m) return true; return false; }
     bool all(MemKind m) const { for (int k = 0; k < 5; k++) if (holds_data(k) && kind[k] != m) return false; return true; }
 };
@@ -936,21 +848,21 @@ static int param_range(eicos_batch *h, int first, int count, const double *theta
     const bool mG = h->mat.g[0].base != nullptr, mA = h->mat.g[1].base != nullptr;
     const AffineDev *src[5] = {mG ? &h->mat.g[0] : nullptr, mA ? &h->mat.g[1] : nullptr, M.g[0].base ? &M.g[0] : nullptr,
                                mG && D.m > 0 ? &M.g[1] : nullptr, mA && D.p > 0 ? &M.g[2] : nullptr};
-    const int w[5] = {D.nnzG, D.nnzA, D.n, D.m, D.p};
-    size_t per = 0;
-    for (int g = 0; g < 5; g++) if (src[g]) per += (size_t)w[g] + 8; // (+ 8 doubles per array: every array of a chunk starts 64-byte aligned)
+    const size_t w[5] = {(size_t)D.nnzG, (size_t)D.nnzA, (size_t)D.n, (size_t)D.m, (size_t)D.p};
+    const bool given[5] = {src[0] != nullptr, src[1] != nullptr, src[2] != nullptr, src[3] != nullptr, src[4] != nullptr};
+    const size_t row = matrix_stage_row(w, given);
     const size_t cap = (size_t)env_knob("EICOS_MATRIX_STAGE_MB", MSTAGE_CAP_MB, 1, 4096) * ((1u << 20) / sizeof(double));
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, cap / per));
-    HIP_TRY_AS("hipMalloc", h->d_mstage.reserve((size_t)chunk * per * sizeof(double), h->stream));
+    const int chunk = matrix_stage_chunk(row, count, cap);
+    HIP_TRY_AS("hipMalloc", h->d_mstage.reserve((size_t)chunk * row * sizeof(double), h->stream));
     for (int o = 0; o < count; o += chunk) {
         const int cnt = std::min(chunk, count - o);
+        const PackedChunk pk = pack_chunk(w, given, (size_t)cnt, ChunkPad::RoundUp8); // (every array of a chunk starts 64-byte aligned)
         const double *arr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        double *at = h->d_mstage.as<double>();
         for (int g = 0; g < 5; g++) {
             if (!src[g]) continue;
+            double *at = h->d_mstage.as<double>() + pk.off[g];
             arr[g] = at;
-            HIP_TRY(launch_expand_affine(*src[g], w[g], M.k, theta + (size_t)o * M.k, cnt, at, h->stream));
-            at += ((size_t)cnt * w[g] + 7) / 8 * 8;
+            HIP_TRY(launch_expand_affine(*src[g], (int)w[g], M.k, theta + (size_t)o * M.k, cnt, at, h->stream));
         }
         HIP_TRY(launch_update(h->pslot, h->inst(), first + o, cnt, arr[0], arr[1], arr[2], arr[3], arr[4], h->d_scratch.as<double>(), std::min(cnt, h->upd_grid),
                               h->upd_lds, h->upd_vals_lds, h->stream, nullptr, list ? list + o : nullptr));
@@ -997,20 +909,20 @@ static int update_in_place(const UpdateInputs &in, int path) {
 }
 
 // The two staged paths: rows travel in chunks of `chunk` instances through a staging area the GPU addresses, the given arrays of a chunk
-// packed behind each other (+ 8 doubles of padding per array keep every row 64-byte aligned), one launch per chunk on the packed pointers.
-static size_t staging_doubles(const UpdateInputs &in, int chunk) { return (size_t)chunk * (in.per + 5 * 8); }
+// packed behind each other (UpdateInputs::packed: 8 doubles between two arrays, which keeps them on lines of their own but aligns only
+// the first to 64 bytes), one launch per chunk on the packed pointers; an area holds staging_doubles(in.per, chunk) (chunk_plan.hpp).
 static int update_in_chunks(const UpdateInputs &in, int chunk, const Staging &st) {
     int rc = begin_update_timing(in.h), k = 0;
     for (int o = 0; o < in.count && rc == EICOS_OK; o += chunk, k++) {
         const int cnt = std::min(chunk, in.count - o);
+        const PackedChunk pk = in.packed((size_t)cnt);
         const double *packed[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        double *at = nullptr;
-        rc = st.area(k, at);
+        double *area = nullptr;
+        rc = st.area(k, area);
         for (int q = 0; q < 5 && rc == EICOS_OK; q++) {
             if (!in.src[q]) continue;
-            packed[q] = at;
-            if (in.w[q]) rc = st.put(at, in.src[q] + (size_t)o * in.w[q], (size_t)cnt * in.w[q] * sizeof(double));
-            at += (size_t)cnt * in.w[q] + 8;
+            packed[q] = area + pk.off[q];
+            if (in.w[q]) rc = st.put(area + pk.off[q], in.src[q] + (size_t)o * in.w[q], (size_t)cnt * in.w[q] * sizeof(double));
         }
         if (rc == EICOS_OK) rc = launch_range(in, in.first + o, cnt, packed);
         if (rc == EICOS_OK) rc = st.launched(k);
@@ -1033,8 +945,8 @@ static int peer_update(const UpdateInputs &in, int src_dev) {
     if (can && !env_knob("EICOS_PEER_STAGED", 0, 0, 1)) return update_in_place(in, 3);
     // no peer access: staged peer copies, one chunk at a time through the device staging buffer
     h->last_update_path = 4;
-    const int chunk = 256;
-    HIP_TRY_AS("hipMalloc", h->d_stage.reserve(staging_doubles(in, std::min(in.count, chunk)) * sizeof(double), h->stream));
+    const int chunk = PEER_CHUNK;
+    HIP_TRY_AS("hipMalloc", h->d_stage.reserve(staging_doubles(in.per, std::min(in.count, chunk)) * sizeof(double), h->stream));
     Staging st;
     st.area = [&](int, double *&area) -> int { area = h->d_stage.as<double>(); return EICOS_OK; };
     st.put = [&](double *dst, const double *src, size_t bytes) -> int {
@@ -1066,10 +978,8 @@ static int host_update(const UpdateInputs &in) {
         return EICOS_OK;
     }
     h->last_update_path = 1;
-    int chunk = (int)std::max<size_t>(16, PIN_CHUNK_BYTES / (staging_doubles(in, 1) * sizeof(double)));
-    chunk = std::min(chunk, in.count);
-    if (in.count > chunk && in.count < 2 * chunk) chunk = (in.count + 1) / 2; // two even chunks rather than a long one and a stub
-    const int rc = ensure_pin(h, staging_doubles(in, chunk));
+    const int chunk = bounce_in_chunk(in.per, in.count);
+    const int rc = ensure_pin(h, staging_doubles(in.per, chunk));
     if (rc != EICOS_OK) return rc;
     CopyPool &pool = CopyPool::get();
     Staging st;
@@ -1349,14 +1259,12 @@ static int fetch_strided(eicos_batch *h, double *dst, const double *src, size_t 
     if (!dst || width == 0 || count == 0) return EICOS_OK;
     const size_t wb = (size_t)width * sizeof(double), stride = pitch / sizeof(double);
     // (a small result takes the one strided copy as well, unless it starts in pinned memory that ends before it does)
-    if (memory_kind(dst, (size_t)count * wb) == MEM_PINNED || ((size_t)count * wb < (256u << 10) && memory_kind(dst, 1) != MEM_PINNED)) {
+    if (memory_kind(dst, (size_t)count * wb) == MEM_PINNED || (small_result((size_t)count * wb) && memory_kind(dst, 1) != MEM_PINNED)) {
         HIP_TRY(hipMemcpy2DAsync(dst, wb, src, pitch, wb, (size_t)count, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         return EICOS_OK;
     }
-    // (chunks of ~4 MB: small enough that the device-to-host copy of one chunk and the host copy of the previous one overlap on a result of a few MB)
-    int chunk = (int)std::max<size_t>(16, (PIN_CHUNK_BYTES / 4) / wb);
-    chunk = std::min(chunk, count);
+    const int chunk = bounce_out_chunk(wb, count);
     int rc = ensure_pin(h, (size_t)chunk * width);
     if (rc != EICOS_OK) return rc;
     for (PinSlot &s : h->pin) HIP_TRY_AS("hipEventSynchronize", s.wait());
@@ -1642,20 +1550,19 @@ static int update_solve(eicos_batch *h, const double *G, const double *A, const 
     // ---- one launch: the kernel reads the arrays and writes the outputs it can address
     const double *ptr[5] = {in.src[0], in.src[1], in.src[2], in.src[3], in.src[4]};
     bool staged[5];
-    size_t per = 0, stage_need = 0;
+    size_t per = 0;
     for (int k = 0; k < 5; k++) {
         staged[k] = in.holds_data(k) && in.kind[k] == MEM_PAGEABLE;
-        if (staged[k]) { per += in.w[k]; stage_need += (size_t)h->batch * in.w[k] + 8; }
+        if (staged[k]) per += in.w[k];
     }
-    // chunks of ~12 MB over the staged arrays: the copy pool splits an array's share of a chunk into pieces of >= 1 MB over its threads, so
-    // a chunk must be large enough to keep them busy and small enough that the first workgroups start after a fraction of the whole copy
-    const int chunk = any_staged ? (int)std::max<size_t>(8, std::min<size_t>((size_t)h->batch, (12u << 20) / std::max<size_t>(per * sizeof(double), 1))) : h->batch;
-    const int nchunks = (h->batch + chunk - 1) / chunk;
+    // the staged arrays of the whole batch are ONE packed chunk in the staging buffer, filled in copy chunks of ~12 MB (chunk_plan.hpp)
+    const PackedChunk pk = pack_chunk(in.w, staged, (size_t)h->batch, ChunkPad::Gap8);
+    const int chunk = any_staged ? fused_stage_chunk(per, h->batch) : h->batch;
+    const int nchunks = chunk_count(h->batch, chunk);
     if (any_staged) {
-        rc = grow_staging(h, stage_need, nchunks);
+        rc = grow_staging(h, pk.total, nchunks);
         if (rc != EICOS_OK) return rc;
-        double *at = h->stage_pin.as<double>();
-        for (int k = 0; k < 5; k++) if (staged[k]) { ptr[k] = at; at += (size_t)h->batch * in.w[k] + 8; }
+        for (int k = 0; k < 5; k++) if (staged[k]) ptr[k] = h->stage_pin.as<double>() + pk.off[k];
         h->stage_seq++;
         if (h->stage_seq == 0) { std::memset(h->stage_flags.p, 0, h->stage_flags.bytes); h->stage_seq = 1; } // (wrapped)
     }
